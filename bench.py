@@ -3,15 +3,20 @@
 per GPU (BASELINE.json configs[1]), inputs resident in HBM.
 
     python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run)
+    python bench.py ... --full                           (every further leg: roofline, CPU baseline, other models, ...)
+    python bench.py ... --dump-outputs DIR               (the last timed step's outputs as DIR/<name>.npy)
 
 One "step" = one whole pass of the hot path over one batch per GPU: the launch plan (front end,
 CNN, head), the top-K kernel, and the device-to-host copies of the logits rows and top-K results
 (bn_step_device).  With N > 1 the segments of a step are sharded contiguously over the ranks
 (weak scaling: 32 per GPU) and the per-rank logits are all-gathered with RCCL.
 
-Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement").  The roofline / per-kernel numbers
-come from HIP events recorded on the context's stream around every launch (bn_ctx_time_kernels);
-cpu_baseline times the CPU oracle (torch CPU, fp32) on a bounded sample on rank 0 at N=1 only.
+Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement").  A plain run sets up, warms up, times
+the K steps and prints the headline (`value`, `ms_per_step`, the per-step interval statistics).
+With --full the line also carries the legs that take runs of their own: the roofline / per-kernel
+numbers from HIP events recorded on the context's stream around every launch (bn_ctx_time_kernels),
+own_buffer, host_to_host, latency_b1, extra.v30 / extra.perch, and cpu_baseline, which times the CPU
+oracle (torch CPU, fp32) on a bounded sample on rank 0 at N=1 only.
 """
 from __future__ import annotations
 
@@ -31,6 +36,7 @@ if ROOT not in sys.path:
 
 HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 MFMA_F32_PEAK_TF = 157.3     # MI355X_MICROARCH.md: f32-input MFMA peak (= vector peak)
+DUMP_MAX_BYTES = 64 << 20    # --dump-outputs: larger outputs are cut to a fixed, seeded sample of rows
 
 
 def main():
@@ -60,6 +66,14 @@ def main():
                     help="rehearsal: run the N > 1 code path (process group, staging copy, all-gather) with a single rank")
     ap.add_argument("--model", choices=["v24", "v30", "perch"], default="v24",
                     help="v24 = the benchmark (BASELINE configs[1]); v30 / perch = configs[2] / [3], informational (use --batch 64 / 128)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline: per-launch roofline timing, own_buffer, host_to_host, latency_b1, "
+                         "extra.v30 / extra.perch, cpu_baseline and the checks of the last step's results (the --no-* options trim these)")
+    ap.add_argument("--warmup-min-s", type=float, default=0.25,
+                    help="plain runs: the warm-up goes on past W steps until it has lasted this long (a --full run warms the device with its "
+                         "per-launch timing passes instead)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller (logits, top-K rows) as DIR/<name>.npy")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -239,15 +253,15 @@ def main():
         if use_dist:
             dist.barrier()
 
-    # ---- order of the legs: the per-launch HIP-event timing that `roofline` needs (one context, every launch bracketed by events on
+    # ---- order of the legs (--full): the per-launch HIP-event timing that `roofline` needs (one context, every launch bracketed by events on
     # the context's stream: 12 passes at the workload's batch, one uncounted pass in front) runs FIRST, then the W warm-up steps, then
     # the K timed steps.  It used to run last; measured per round of four steps, a process that starts on an idle GPU (sclk at its
     # 577 MHz idle level while the model is authored on the host) delivers 2.65 ms per round for its first ~8 rounds (~20 ms) and
     # 2.2 ms from then on in EITHER input protocol -- the clock governor's ramp, not the code under test -- and the driver's
     # `--steps 20 --warmup 5` run lies entirely inside that ramp.  The roofline leg is device work of this same benchmark; running it
     # first changes nothing in what W and K mean (W untimed steps, then exactly K timed steps between the fences).
-    kernel_rows, kernel_rows4 = None, None
-    if rank == 0:
+    kernel_rows, kernel_rows4, kernel_rows_shared = None, None, None
+    if rank == 0 and args.full:
         ctxs[0].infer(bufs[0].cpu().numpy())  # puts a real batch into the context's own input buffer
         # Launches whose grid is a trade between one launch's latency and the work per block come in two forms (bn_set_sharing_mode): the
         # per-launch table of `roofline` -- one context ALONE on the device -- is timed in the form a lone context runs (what `--streams 1`
@@ -262,22 +276,35 @@ def main():
         NPASS = 12
         bn.set_sharing_mode(bn.SHARING_ALONE)
         kernel_rows = _timed_rows(NPASS)
-        kernel_rows_shared = None
         if len(ctxs) > 1:
             bn.set_sharing_mode(bn.SHARING_SHARED)
             kernel_rows_shared = _timed_rows(6)
-        bn.set_sharing_mode(bn.SHARING_AUTO)
         # (the same passes at four times the batch -- `roofline.saturated` -- run BEHIND the timed steps since round 4: measured on one box,
         # `--steps 20 --warmup 5` reads 58.9-59.0 k with that leg in front of the timed region and 60.8-61.3 k without it (tools/ab_legs.sh);
         # the timed steps' own ramp-up is what the passes above are for, a fifth context of 1.4 GB is not part of the workload)
         # (ctxs[0]'s own buffer was overwritten by infer(): put its batch back for --own-buffer and the own_buffer leg)
         torch.as_tensor(_DevBuf(own_ptr[0], (B, S)), device="cuda").copy_(bufs[0])
         torch.cuda.synchronize()
+    if rank == 0:
+        bn.set_sharing_mode(bn.SHARING_AUTO)
     if use_dist:
         dist.barrier()
-    for i in range(args.warmup):
-        step(i)
-    drain(args.warmup)
+    # a plain run has no timing passes in front of its warm-up to bring the device out of its idle clock (see above), so the warm-up
+    # goes on past the W steps, one round of contexts at a time, until it has lasted --warmup-min-s; the ranks agree on every round
+    nwarm, target, t_warm = 0, args.warmup, time.perf_counter()
+    while True:
+        while nwarm < target:
+            step(nwarm)
+            nwarm += 1
+        more = not args.full and time.perf_counter() - t_warm < args.warmup_min_s
+        if use_dist:
+            flag = torch.tensor([1.0 if more else 0.0], dtype=torch.float64, device="cuda" if args.backend == "nccl" else "cpu")
+            dist.all_reduce(flag, op=dist.ReduceOp.MAX)
+            more = float(flag.item()) > 0.0
+        if not more:
+            break
+        target = nwarm + S_
+    drain(nwarm)
     fence()
     ev_base.record(ev_streams[0])
     t0 = time.perf_counter()
@@ -302,23 +329,32 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
 
-    # sanity of the last step's results (not timed): top-1 of the device top-K == argmax of the logits
-    lg, ix, cf, ct = ctxs[(args.steps - 1) % len(ctxs)].step_results(B)
-    assert np.isfinite(lg).all()
-    if on_gpu_dist:  # ... and this rank's rows of the last all-gather are that step's logits
-        slot = (args.steps - 1) % S_
-        mine = gathered[(rank * S_ + slot) * B:(rank * S_ + slot + 1) * B].cpu().numpy()
-        assert np.array_equal(mine.view(np.uint32), lg.reshape(B, -1).view(np.uint32)), "all-gather rows differ from the step's logits"
-    for r in range(B):
-        if ct[r]:
-            assert ix[r, 0] == int(np.argmax(lg[r]))
+    if args.full or args.dump_outputs:
+        lg, ix, cf, ct = ctxs[(args.steps - 1) % len(ctxs)].step_results(B)
+    if args.full:
+        # sanity of the last step's results (not timed): top-1 of the device top-K == argmax of the logits
+        assert np.isfinite(lg).all()
+        if on_gpu_dist:  # ... and this rank's rows of the last all-gather are that step's logits
+            slot = (args.steps - 1) % S_
+            mine = gathered[(rank * S_ + slot) * B:(rank * S_ + slot + 1) * B].cpu().numpy()
+            assert np.array_equal(mine.view(np.uint32), lg.reshape(B, -1).view(np.uint32)), "all-gather rows differ from the step's logits"
+        for r in range(B):
+            if ct[r]:
+                assert ix[r, 0] == int(np.argmax(lg[r]))
+    if args.dump_outputs:
+        all_rows = None
+        if on_gpu_dist:  # the last all-gather's rows of that step, every rank's batch in global segment order
+            slot = (args.steps - 1) % S_
+            all_rows = gathered.view(world, S_ * B, -1)[:, slot * B:(slot + 1) * B].reshape(world * B, -1).cpu().numpy()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, lg, ix, cf, ct, all_rows)
 
     total_segments = args.steps * B * world
     value = total_segments / dt
 
     # the round-3 protocol next to it (never `value`): the same loop with each context re-reading the batch in its own buffer
     own_buffer = None
-    if not args.own_buffer:  # (every world size since round 5: the round-to-round comparison must not depend on prose)
+    if args.full and not args.own_buffer:  # (every world size since round 5: the round-to-round comparison must not depend on prose)
         def run_own(n):
             for i in range(n):
                 if i >= S_:
@@ -349,7 +385,7 @@ def main():
     # staging into pinned memory by the library's pool, PCIe upload, plan, top-K, logits + top-K rows back to
     # pageable host arrays.  Same contexts, two batches in flight per context.
     host_to_host = None
-    if rank == 0 and world == 1 and not args.no_host_leg:
+    if args.full and rank == 0 and world == 1 and not args.no_host_leg:
         from collections import deque
 
         hbufs = [b_.cpu().numpy() for b_ in bufs]
@@ -398,6 +434,7 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "warmup_steps_run": nwarm,  # W, or more in a plain run whose W steps took less than --warmup-min-s
         "ms_per_step": round(dt / args.steps * 1e3, 4),
         "median_ms": step_stats["median_ms"],
         "p10_ms": step_stats["p10_ms"],
@@ -406,7 +443,7 @@ def main():
         "step_done_ms": [round(float(v), 3) for v in done_ms] if (len(done_ms) <= 64 or args.dump_steps) else None,  # completion time of every timed step since the start of the timed region (short runs only)
         "higher_is_better": True,
         "protocol": "r4-own-buffer" if args.own_buffer else "r4-rotating-input",  # r4-rotating-input: a fresh device batch per step, one D2D copy inside the timed region (BENCH_r01-r03: own-buffer)
-        "pre_warmup_device_passes": (13 + (7 if max(1, args.streams) > 1 else 0)) if rank == 0 else 0,  # per-launch HIP-event timing passes (roofline leg: 13 in the default forms, 7 in the shared ones) that run before the W warm-up steps
+        "pre_warmup_device_passes": (13 + (7 if max(1, args.streams) > 1 else 0)) if rank == 0 and args.full else 0,  # per-launch HIP-event timing passes (roofline leg: 13 in the default forms, 7 in the shared ones) that run before the W warm-up steps
         "scaling": "weak",
         "vs_baseline": None,
         "dtype": "f32",
@@ -437,7 +474,7 @@ def main():
                 break
             try:
                 r_ = subprocess.run([sys.executable, os.path.abspath(__file__), "--model", key, "--batch", str(bsz), "--steps", "60", "--warmup", "8",
-                                     "--streams", str(S_), "--no-extras", "--no-cpu-baseline", "--no-host-leg", "--no-saturated"],
+                                     "--streams", str(S_), "--full", "--no-extras", "--no-cpu-baseline", "--no-host-leg", "--no-saturated"],
                                     capture_output=True, text=True, timeout=600)
                 line = [l for l in r_.stdout.splitlines() if l.startswith("{")][-1]
                 j_ = json.loads(line)
@@ -510,7 +547,7 @@ def main():
         out["own_buffer"] = own_buffer
     if host_to_host is not None:
         out["host_to_host"] = host_to_host
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         # ---- BASELINE configs[0]: ONE 3 s segment through predict's path, host slice in -> logits + top-K on the host
         # (bn_infer_submit + collect on a batch-1 context, what Classifier::predict costs a caller, classifier.rs:610-643),
         # and the same segment device-resident (bn_step_device, batch 1); median of 60 calls after 10 warm-up calls
@@ -537,6 +574,7 @@ def main():
         del c1
     if rank == 0:
         out["capture_fallbacks"] = sum(c.stats()["capture_fallbacks"] for c in ctxs)
+    if rank == 0 and args.full:
         out["whole_path_frac_mfma_f32"] = None  # filled below from the plan's flop count
         # ---- per-kernel device times (HIP events on the context's stream), roofline of the dominant kernel
         rows = kernel_rows  # measured before the warm-up steps (see "order of the legs" above)
@@ -830,9 +868,38 @@ def main():
             ctxs.clear()
             gc.collect()
             run_extras()
+    if rank == 0:
         print(json.dumps(out))
     if use_dist:
         dist.destroy_process_group()
+
+
+def dump_outputs(dirname: str, lg, ix, cf, ct, all_rows=None) -> None:
+    """--dump-outputs: what the last timed step handed its caller (bn_step_results), one DIR/<name>.npy per array.  Top-K entries
+    past a row's count are not results: their indices are written as -1 and their confidences as 0.  Integers go out as float64
+    (exact).  If the arrays would pass DUMP_MAX_BYTES, they keep a fixed, seeded sample of the batch's segments (rows.npy names them;
+    logits_all_ranks, with N > 1, its own sample in logits_all_ranks_rows.npy)."""
+    k = np.arange(ix.shape[1])[None, :]
+    valid = k < ct[:, None]
+    groups = [("rows", {"logits": lg.reshape(lg.shape[0], -1).astype(np.float32),
+                        "topk_indices": np.where(valid, ix.astype(np.float64), -1.0),
+                        "topk_confidences": np.where(valid, cf, np.float32(0.0)).astype(np.float32),
+                        "topk_counts": ct.astype(np.float64)})]
+    if all_rows is not None:
+        groups.append(("logits_all_ranks_rows", {"logits_all_ranks": all_rows.astype(np.float32)}))
+    total = sum(a.nbytes for _, g in groups for a in g.values())
+    out = {}
+    rng = np.random.default_rng(0)
+    for rows_name, g in groups:
+        if total > DUMP_MAX_BYTES:
+            n = next(iter(g.values())).shape[0]
+            rows = np.sort(rng.choice(n, max(1, int(n * 0.9 * DUMP_MAX_BYTES / total)), replace=False))
+            g = {name: a[rows] for name, a in g.items()}
+            g[rows_name] = rows.astype(np.float64)
+        out.update(g)
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 _describe_path = None

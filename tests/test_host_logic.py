@@ -74,13 +74,13 @@ def test_parse_csv_labels(bn):  # labels.rs:51-95
 
 
 def test_reference_label_files_parse_to_the_pinned_counts(bn):
+    import gzip
     import os
-    base = "/root/reference/data/labels"
-    if not os.path.isdir(base):
-        pytest.skip("reference tree not present (GPU box)")
-    txt = open(os.path.join(base, "birdnet_v2.4", "BirdNET_GLOBAL_6K_V2.4_Labels_en_uk.txt"), encoding="utf-8").read()
+    # the reference's label lists (data/labels/birdnet_v2.4/..._en_uk.txt, data/labels/perch_v2/labels.csv), committed byte for byte, gzipped
+    base = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "labels")
+    txt = gzip.open(os.path.join(base, "BirdNET_GLOBAL_6K_V2.4_Labels_en_uk.txt.gz"), "rt", encoding="utf-8").read()
     assert len(bn.parse_labels(txt, False)) == 6522
-    csv = open(os.path.join(base, "perch_v2", "labels.csv"), encoding="utf-8").read()
+    csv = gzip.open(os.path.join(base, "perch_v2_labels.csv.gz"), "rt", encoding="utf-8").read()
     assert len(bn.parse_labels(csv, True)) == 14795
 
 
