@@ -348,6 +348,96 @@ fn group_last_error() -> String {
     String::from_utf8_lossy(&buf).trim_end_matches('\0').to_string()
 }
 
+/// Device-resident embedding store with exact top-M cosine search (`bn_index_*`).  Rows are L2-normalised on the way in; ids
+/// are the append order, so appending the windows of a recording in order makes the id the window index.  Results are
+/// `(id, score)` per query, score descending, ties by id ascending.
+pub struct EmbeddingIndex {
+    pub(crate) x: *mut bn_index,
+    dim: usize,
+}
+
+impl EmbeddingIndex {
+    pub fn new(device: i32, dim: usize, capacity_rows: usize) -> Result<Self> {
+        let mut x: *mut bn_index = std::ptr::null_mut();
+        match unsafe { bn_index_create(device, dim, capacity_rows, &mut x) } {
+            BN_OK => Ok(Self { x, dim }),
+            _ => Err(Error::Inference(last_error())),
+        }
+    }
+
+    pub fn len(&self) -> usize {
+        unsafe { bn_index_size(self.x) }
+    }
+
+    pub fn is_empty(&self) -> bool {
+        self.len() == 0
+    }
+
+    pub fn dim(&self) -> usize {
+        unsafe { bn_index_dim(self.x) }
+    }
+
+    /// Appends host rows (`rows.len()` a multiple of `dim`); returns the first id.
+    pub fn add(&mut self, rows: &[f32]) -> Result<u64> {
+        if rows.len() % self.dim != 0 {
+            return Err(Error::Inference(format!("{} floats are not whole rows of {}", rows.len(), self.dim)));
+        }
+        let mut first = 0u64;
+        match unsafe { bn_index_add_host(self.x, rows.as_ptr(), rows.len() / self.dim, &mut first) } {
+            BN_OK => Ok(first),
+            _ => Err(Error::Inference(last_error())),
+        }
+    }
+
+    /// Appends the embeddings of the context's last run (rows `0..batch`), device to device; returns the first id.
+    pub fn add_context(&mut self, context: &mut BatchInferenceContext, batch: usize) -> Result<u64> {
+        let mut first = 0u64;
+        match unsafe { bn_index_add_ctx(self.x, context.ctx, batch, &mut first) } {
+            BN_OK => Ok(first),
+            _ => Err(Error::Inference(last_error())),
+        }
+    }
+
+    /// Top `top_m` rows by cosine for each query (`queries.len()` a multiple of `dim`).
+    pub fn search(&mut self, queries: &[f32], top_m: usize) -> Result<Vec<Vec<(u64, f32)>>> {
+        if queries.len() % self.dim != 0 {
+            return Err(Error::Inference(format!("{} floats are not whole queries of {}", queries.len(), self.dim)));
+        }
+        let n = queries.len() / self.dim;
+        let (mut ids, mut scores, mut counts) = (vec![0u64; n * top_m], vec![0f32; n * top_m], vec![0u32; n]);
+        let st = unsafe { bn_index_search(self.x, queries.as_ptr(), n, top_m, top_m, ids.as_mut_ptr(), scores.as_mut_ptr(), counts.as_mut_ptr()) };
+        Self::collect(st, top_m, &ids, &scores, &counts)
+    }
+
+    /// Query by example: stored rows `ids` are the queries; rows whose id is within `exclude_radius` of the query's own are
+    /// skipped (`< 0`: none; `0`: the row itself).
+    pub fn search_ids(&mut self, query_ids: &[u64], exclude_radius: i64, top_m: usize) -> Result<Vec<Vec<(u64, f32)>>> {
+        let n = query_ids.len();
+        let (mut ids, mut scores, mut counts) = (vec![0u64; n * top_m], vec![0f32; n * top_m], vec![0u32; n]);
+        let st = unsafe {
+            bn_index_search_ids(self.x, query_ids.as_ptr(), n, exclude_radius, top_m, top_m, ids.as_mut_ptr(), scores.as_mut_ptr(), counts.as_mut_ptr())
+        };
+        Self::collect(st, top_m, &ids, &scores, &counts)
+    }
+
+    fn collect(st: i32, top_m: usize, ids: &[u64], scores: &[f32], counts: &[u32]) -> Result<Vec<Vec<(u64, f32)>>> {
+        if st != BN_OK {
+            return Err(Error::Inference(last_error()));
+        }
+        Ok(counts
+            .iter()
+            .enumerate()
+            .map(|(q, &c)| (0..c as usize).map(|j| (ids[q * top_m + j], scores[q * top_m + j])).collect())
+            .collect())
+    }
+}
+
+impl Drop for EmbeddingIndex {
+    fn drop(&mut self) {
+        unsafe { bn_index_free(self.x) }
+    }
+}
+
 /// How launches size their grids where one launch's latency trades against the work per block (`bn_set_sharing_mode`): `Alone` (default)
 /// for the lowest latency of one batch, `Shared` for a caller that keeps several `BatchInferenceContext`s busy (identical results, bit
 /// for bit; BirdNET v2.4 with four contexts: +7 % segments/s), `Auto` = `Shared` while more than one context lives on the device.

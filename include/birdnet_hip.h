@@ -400,6 +400,54 @@ bn_status bn_group_analyze_recording(bn_group *g, const void *pcm, size_t n_samp
                                      uint32_t *count_out, size_t *n_windows_out);
 size_t bn_group_last_error(char *buf, size_t cap);
 
+/*
+ * Embedding index: a device-resident store of L2-normalised f32 embedding rows on one device, answering exact top-M
+ * cosine-similarity queries (retrieval over a season of audio: "find the windows that sound like this one").  The
+ * reference has embeddings but no search; the contract is what an exact float64 brute-force search returns, up to f32
+ * rounding, in a total order that makes results deterministic.
+ *
+ * Row ids are the append order: appending the windows of bn_infer_windows in order makes the id the window index, so
+ * start = id * step / sample_rate as chunk_audio reports it (src/bin/birdnet-analyze.rs:707-743).
+ *
+ *   Normalisation  stored row = x / sqrt(sum x^2).  A row with zero norm or any non-finite element (or whose sum of
+ *                  squares overflows f32) is stored as zeros, counts toward bn_index_size and is never returned.  A query
+ *                  with zero norm or a non-finite element returns count = 0.
+ *   Score          the f32 dot product of the normalised query and the normalised row.  For one (query, row) pair its
+ *                  summation order depends only on dim: not on where the row lands in a tile, the number of queries of
+ *                  the call, the index size or how the index was appended.
+ *   Order          score descending, ties by id ascending (-0.0 == +0.0).  count = min(top_m, eligible rows); entries
+ *                  past count are not written.
+ *   Limits         1 <= top_m <= 256 and m_stride >= top_m, otherwise BN_ERR_INVALID_ARG.  An append past capacity_rows
+ *                  is refused whole (nothing appended, size unchanged).  An empty index returns count = 0.
+ *
+ * Outputs are host arrays [n_queries * m_stride] (id_out, score_out) and count_out [n_queries].  Errors through
+ * bn_last_error().  Threading: one thread at a time per index, like a context.
+ */
+typedef struct bn_index bn_index;
+/* dim >= 1, 1 <= capacity_rows < 2^32 - 1; the slab (capacity x dim rounded up to the scan's k-step) is allocated here */
+bn_status bn_index_create(int32_t device, size_t dim, size_t capacity_rows, bn_index **out);
+void bn_index_free(bn_index *x);
+/* rows appended so far */
+size_t bn_index_size(const bn_index *x);
+size_t bn_index_dim(const bn_index *x);
+/* append n host rows [n * dim]; their ids are *first_id .. *first_id + n - 1 (first_id may be NULL) */
+bn_status bn_index_add_host(bn_index *x, const float *rows, size_t n, uint64_t *first_id);
+/* append the embedding output of the last run of c (rows 0 .. batch_size-1, batch_size <= that run's batch), device to device,
+ * ordered after that run on the context's stream (the call returns without waiting; the index's next use waits for it).
+ * Refused, with the index unchanged, for a model without embeddings, a dimension mismatch, a context on another device or a
+ * batch_size larger than the last run's. */
+bn_status bn_index_add_ctx(bn_index *x, bn_ctx *c, size_t batch_size, uint64_t *first_id);
+/* copy stored (normalised) rows [first, first + count) to host [count * dim] */
+bn_status bn_index_read(const bn_index *x, uint64_t first, size_t count, float *host_out);
+/* top-M by cosine for n_queries host query vectors [n_queries * dim] */
+bn_status bn_index_search(bn_index *x, const float *queries, size_t n_queries, size_t top_m, size_t m_stride,
+                          uint64_t *id_out, float *score_out, uint32_t *count_out);
+/* query by example: the queries are stored rows (used as stored, not normalised again); rows whose id lies within
+ * exclude_radius of the query's own id are skipped (exclude_radius < 0: none skipped; 0: the row itself; with overlapping
+ * windows the neighbours are near-duplicates).  A query id >= bn_index_size is BN_ERR_INVALID_ARG. */
+bn_status bn_index_search_ids(bn_index *x, const uint64_t *query_ids, size_t n_queries, int64_t exclude_radius,
+                              size_t top_m, size_t m_stride, uint64_t *id_out, float *score_out, uint32_t *count_out);
+
 /* Diagnostic, needs no device: parse the file, build the launch plan (all graph
  * outputs when all_outputs != 0, else logits + embeddings only) and write a
  * text description (one line per launch, then totals) into buf.  Returns the

@@ -51,6 +51,8 @@ ENGINE_SYMBOLS = [
     "bn_recording_create", "bn_recording_create_async", "bn_recording_wait", "bn_recording_free", "bn_recording_samples", "bn_chunk_count", "bn_recording_windows",
     "bn_infer_windows", "bn_step_windows", "bn_ctx_step_device_rows", "bn_group_create", "bn_group_destroy", "bn_group_size",
     "bn_group_uses_rccl", "bn_group_get_stats", "bn_shard_range", "bn_group_analyze_recording", "bn_group_last_error", "bn_recording_create_resampled", "bn_resample_table", "bn_recording_read_f32", "bn_last_error",
+    "bn_index_create", "bn_index_free", "bn_index_size", "bn_index_dim", "bn_index_add_host", "bn_index_add_ctx", "bn_index_read",
+    "bn_index_search", "bn_index_search_ids",
 ]
 HOST_SYMBOLS = [
     "bnh_classifier_build", "bnh_classifier_free", "bnh_classifier_config", "bnh_classifier_provider",
@@ -166,6 +168,15 @@ def _load() -> C.CDLL:
         "bn_shard_range": (None, [sz, i32, i32, C.POINTER(sz), C.POINTER(sz)]),
         "bn_group_analyze_recording": (i32, [vp, vp, sz, i32, sz, sz, i32, C.c_float, f32p, sz, u32p, f32p, u32p, C.POINTER(sz)]),
         "bn_group_last_error": (sz, [C.c_char_p, sz]),
+        "bn_index_create": (i32, [i32, sz, sz, C.POINTER(vp)]),
+        "bn_index_free": (None, [vp]),
+        "bn_index_size": (sz, [vp]),
+        "bn_index_dim": (sz, [vp]),
+        "bn_index_add_host": (i32, [vp, f32p, sz, C.POINTER(C.c_uint64)]),
+        "bn_index_add_ctx": (i32, [vp, vp, sz, C.POINTER(C.c_uint64)]),
+        "bn_index_read": (i32, [vp, C.c_uint64, sz, f32p]),
+        "bn_index_search": (i32, [vp, f32p, sz, sz, sz, C.POINTER(C.c_uint64), f32p, u32p]),
+        "bn_index_search_ids": (i32, [vp, C.POINTER(C.c_uint64), sz, C.c_int64, sz, sz, C.POINTER(C.c_uint64), f32p, u32p]),
         # host mirror
         "bnh_classifier_build": (i32, [C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), sz, i32, C.c_int64, i32,
                                        C.c_float, i32, C.POINTER(vp), C.POINTER(BnhError)]),
@@ -874,6 +885,84 @@ class Recording:
             raise EngineError(st)
         return out
 
+
+
+class Index:
+    """bn_index: a device-resident store of L2-normalised embedding rows with exact top-M cosine search.  Row ids are the
+    append order.  search / search_ids return (ids [n, top_m] uint64, scores [n, top_m] float32, counts [n] uint32); entries
+    past counts[i] are left as written here (ids 0, scores NaN)."""
+
+    def __init__(self, device: int, dim: int, capacity: int):
+        h = C.c_void_p()
+        st = lib.bn_index_create(device, dim, capacity, C.byref(h))
+        if st:
+            raise EngineError(st)
+        self._h, self.device, self.dim, self.capacity = h, device, dim, capacity
+
+    def __del__(self):
+        if getattr(self, "_h", None) and lib is not None:
+            lib.bn_index_free(self._h)
+            self._h = None
+
+    def close(self):
+        self.__del__()
+
+    def __len__(self) -> int:
+        return int(lib.bn_index_size(self._h))
+
+    def add(self, rows) -> int:
+        """Append host rows [n, dim]; returns the id of the first."""
+        a = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, self.dim)
+        first = C.c_uint64()
+        st = lib.bn_index_add_host(self._h, a.ctypes.data_as(C.POINTER(C.c_float)), a.shape[0], C.byref(first))
+        if st:
+            raise EngineError(st)
+        return int(first.value)
+
+    def add_context(self, ctx: "Context", batch: int) -> int:
+        """Append rows 0 .. batch-1 of the embedding output of ctx's last run, device to device; returns the id of the first."""
+        first = C.c_uint64()
+        st = lib.bn_index_add_ctx(self._h, ctx._h, batch, C.byref(first))
+        if st:
+            raise EngineError(st)
+        return int(first.value)
+
+    def read(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """Stored (normalised) rows [first, first + count) as f32 [count, dim]."""
+        count = len(self) - first if count is None else count
+        out = np.zeros((max(count, 0), self.dim), dtype=np.float32)
+        st = lib.bn_index_read(self._h, first, count, out.ctypes.data_as(C.POINTER(C.c_float)))
+        if st:
+            raise EngineError(st)
+        return out
+
+    @staticmethod
+    def _outputs(n: int, m_stride: int):
+        return (np.zeros((n, m_stride), dtype=np.uint64), np.full((n, m_stride), np.nan, dtype=np.float32), np.zeros(n, dtype=np.uint32))
+
+    def search(self, queries, top_m: int, m_stride: Optional[int] = None):
+        """Top-M rows by cosine for host queries [n, dim]."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
+        m_stride = top_m if m_stride is None else m_stride
+        ids, scores, counts = self._outputs(q.shape[0], max(m_stride, 0))
+        st = lib.bn_index_search(self._h, q.ctypes.data_as(C.POINTER(C.c_float)), q.shape[0], top_m, m_stride,
+                                 ids.ctypes.data_as(C.POINTER(C.c_uint64)), scores.ctypes.data_as(C.POINTER(C.c_float)),
+                                 counts.ctypes.data_as(C.POINTER(C.c_uint32)))
+        if st:
+            raise EngineError(st)
+        return ids, scores, counts
+
+    def search_ids(self, ids, top_m: int, exclude_radius: int = -1, m_stride: Optional[int] = None):
+        """Query by example: the stored rows `ids` are the queries; rows within exclude_radius of a query's id are skipped."""
+        qi = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+        m_stride = top_m if m_stride is None else m_stride
+        out_ids, scores, counts = self._outputs(qi.shape[0], max(m_stride, 0))
+        st = lib.bn_index_search_ids(self._h, qi.ctypes.data_as(C.POINTER(C.c_uint64)), qi.shape[0], exclude_radius, top_m, m_stride,
+                                     out_ids.ctypes.data_as(C.POINTER(C.c_uint64)), scores.ctypes.data_as(C.POINTER(C.c_float)),
+                                     counts.ctypes.data_as(C.POINTER(C.c_uint32)))
+        if st:
+            raise EngineError(st)
+        return out_ids, scores, counts
 
 # ---- range filter (reference src/rangefilter.rs) ----
 @dataclass

@@ -21,6 +21,7 @@
 #include <thread>
 #include <vector>
 
+#include "capi_internal.h"
 #include "detect.h"
 #include "engine.h"
 #include "kernels.h"
@@ -1864,3 +1865,17 @@ size_t bn_last_error(char *buf, size_t cap) {
 }
 
 }  // extern "C"
+
+bn_status bn::set_last_error(bn_status st, const std::string &msg) { return fail(st, msg); }
+
+bn_status bn::ctx_embedding(const bn_ctx *c, CtxEmbedding *out) {
+    if (!c || !out) return fail(BN_ERR_INVALID_ARG, "null argument");
+    const bn_model_config &cfg = c->model->cfg;
+    if (!cfg.has_embedding || cfg.embedding_output < 0) return fail(BN_ERR_INVALID_ARG, "the context's model has no embedding output");
+    bn_status st = bn_ctx_output_device(c, cfg.embedding_output, &out->d_rows, &out->row_elems);
+    if (st != BN_OK) return st;
+    out->device = c->model->device;
+    out->stream = c->stream;
+    out->last_batch = c->last_batch;
+    return BN_OK;
+}

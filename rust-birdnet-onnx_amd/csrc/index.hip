@@ -1,0 +1,596 @@
+// Embedding index behind the C ABI (include/birdnet_hip.h, bn_index_*): a device-resident slab of L2-normalised f32 rows and
+// an exact top-M cosine search over it.
+//
+// Kernels:
+//   * index_normalise_kernel -- one wave per row: sum of squares in a fixed order (lane-strided chains, then a fixed xor
+//     butterfly), a validity flag, and the row x / sqrt(sum) stored with its stride padded with zeros to a multiple of KC, so
+//     the scan has no k tail.  Appends (host rows or a context's embedding output) and host queries go through it.
+//   * index_scan_kernel -- each workgroup streams its contiguous range of 64-row tiles ONCE for all queries of the pass (up to
+//     64).  The products run on the exact-f32 MFMA v_mfma_f32_16x16x4_f32, which is bit for bit a k-ordered fmaf chain: the
+//     k order of a (query, row) pair is fixed by the padded dim alone, never by the tile, the pass or the query count.  Each
+//     tile's [64 queries x 64 rows] scores go to LDS, rows are masked there (invalid, excluded id, past the end), and a row
+//     that beats the query's running M-th candidate joins a pending list; pending lists are merged into the workgroup's
+//     running top-M (kept in its slice of the candidate buffer) when they fill.  Out: [workgroups x queries x M] candidates.
+//   * index_merge_kernel -- one wave per query merges the workgroups' sorted lists into the final top-M, reading each list
+//     only while its entries still beat the running M-th.
+// Order everywhere: score descending, ties by id ascending (-0.0 == +0.0 through the float compare).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "capi_internal.h"
+#include "hip_gate.h"
+
+namespace {
+
+constexpr int KC = 128;    // k-step of the scan; slab and query rows are padded to a multiple of it
+constexpr int TILE = 64;   // rows per workgroup tile: 4 waves x 16 rows
+constexpr int QP = 64;     // queries per scan pass
+constexpr int MMAX = 256;  // largest top_m
+constexpr int PEND = 128;  // pending candidates per query before they are merged into the running list
+constexpr int QS_LD = KC + 4;
+constexpr int S_LD = TILE + 1;
+constexpr size_t QCHUNK = 1024;  // queries normalised / searched per round of a call
+constexpr size_t STAGE_ROWS = 1024;
+
+struct Cand {
+    float s;
+    uint32_t id;
+};
+
+constexpr size_t SCAN_LDS = (size_t)QP * QS_LD * 4 + (size_t)QP * S_LD * 4 + (size_t)QP * PEND * sizeof(Cand) + 4 * MMAX * sizeof(Cand) +
+                            QP * sizeof(Cand) + 2 * QP * sizeof(int);
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+__device__ inline bool ahead(Cand a, Cand b) { return a.s > b.s || (a.s == b.s && a.id < b.id); }
+
+// LDS and global writes of this wave visible to its other lanes
+__device__ inline void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+}
+
+__device__ inline int lanes_below(uint64_t m) {
+    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+
+// One wave: merge np unordered pending candidates into the sorted running list (len entries), keeping the first M of the union.
+// Every element's new position is its rank in the union (the order is strict: ids are distinct).  scratch: MMAX entries of
+// LDS; *thr receives the M-th entry when the list is full.  Returns the new length.
+__device__ int merge_pending(const Cand *pend, int np, Cand *list, int len, int M, Cand *scratch, Cand *thr) {
+    const int lane = threadIdx.x & 63;
+    for (int i = lane; i < len; i += 64) scratch[i] = list[i];
+    wave_sync();
+    for (int i = lane; i < len; i += 64) {
+        const Cand e = scratch[i];
+        int r = i;
+        for (int j = 0; j < np; j++) r += ahead(pend[j], e) ? 1 : 0;
+        if (r < M) {
+            list[r] = e;
+            if (r == M - 1) *thr = e;
+        }
+    }
+    for (int p = lane; p < np; p += 64) {
+        const Cand e = pend[p];
+        int r = 0;
+        for (int j = 0; j < np; j++) r += ahead(pend[j], e) ? 1 : 0;
+        int lo = 0, hi = len;  // list entries ahead of e: a prefix of the sorted list
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (ahead(scratch[mid], e)) lo = mid + 1;
+            else hi = mid;
+        }
+        r += lo;
+        if (r < M) {
+            list[r] = e;
+            if (r == M - 1) *thr = e;
+        }
+    }
+    wave_sync();
+    return min(M, len + np);
+}
+
+// rows [n, dim] at src (row stride src_stride) -> normalised rows [n, dpad] at dst + validity flags
+__global__ __launch_bounds__(256) void index_normalise_kernel(const float *__restrict__ src, size_t src_stride, uint32_t n, uint32_t dim,
+                                                              float *__restrict__ dst, uint32_t dpad, uint8_t *__restrict__ valid) {
+    const uint32_t r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63;
+    if (r >= n) return;
+    const float *x = src + (size_t)r * src_stride;
+    float ss = 0.f;
+    bool fin = true;
+    for (uint32_t k = lane; k < dim; k += 64) {
+        const float v = x[k];
+        fin = fin && isfinite(v);
+        ss = fmaf(v, v, ss);
+    }
+    for (int off = 32; off; off >>= 1) ss += __shfl_xor(ss, off);
+    const bool ok = __ballot(!fin) == 0 && ss > 0.f && isfinite(ss);
+    const float nrm = __fsqrt_rn(ss);
+    float *y = dst + (size_t)r * dpad;
+    for (uint32_t k = lane; k < dpad; k += 64) y[k] = (ok && k < dim) ? x[k] / nrm : 0.f;
+    if (lane == 0) valid[r] = ok ? 1 : 0;
+}
+
+// stored rows ids[q] -> query rows (as stored) + their validity
+__global__ __launch_bounds__(256) void index_gather_kernel(const float *__restrict__ slab, const uint8_t *__restrict__ valid,
+                                                           const uint32_t *__restrict__ ids, uint32_t dpad, float *__restrict__ dst,
+                                                           uint8_t *__restrict__ dvalid) {
+    const uint32_t q = blockIdx.x;
+    const size_t row = ids[q];
+    for (uint32_t k = threadIdx.x; k < dpad; k += 256) dst[(size_t)q * dpad + k] = slab[row * dpad + k];
+    if (threadIdx.x == 0) dvalid[q] = valid[row];
+}
+
+// Scan of one pass (nq <= QP queries, QB = ceil(nq / 16) query blocks).  Workgroup g owns tiles [g * tiles_per_wg, ...).
+// Lane l of wave w: A operand = row (tile row 16w + (l & 15)), k = 16s + 4(l >> 4) + t of each KC chunk (t = component of the
+// float4); B operand = query 16qb + (l & 15) at the same k.  D: query 16qb + (l & 15), row 16w + 4(l >> 4) + reg.
+template <int QB>
+__global__ __launch_bounds__(256) void index_scan_kernel(const float *__restrict__ slab, const uint8_t *__restrict__ valid, uint32_t n_rows,
+                                                         uint32_t dpad, const float *__restrict__ q, const uint8_t *__restrict__ qvalid, int nq,
+                                                         const uint32_t *__restrict__ qid, int64_t radius, int M, uint32_t tiles_per_wg,
+                                                         Cand *__restrict__ cand, int *__restrict__ cand_len) {
+    extern __shared__ __align__(16) float idx_lds[];
+    float *Qs = idx_lds;                               // [QP][QS_LD]: the queries' current k chunk
+    float *S = Qs + QP * QS_LD;                        // [QP][S_LD]: scores of the current tile
+    Cand *pend = reinterpret_cast<Cand *>(S + QP * S_LD);  // [QP][PEND]
+    Cand *scratch = pend + QP * PEND;                  // [4][MMAX]
+    Cand *thr = scratch + 4 * MMAX;                    // [QP]
+    int *len = reinterpret_cast<int *>(thr + QP);      // [QP]
+    int *pn = len + QP;                                // [QP]
+
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int r16 = lane & 15, h = lane >> 4;
+    for (int i = tid; i < QP; i += 256) {
+        len[i] = 0;
+        pn[i] = 0;
+    }
+    const uint32_t n_tiles = (n_rows + TILE - 1) / TILE;
+    const uint32_t t0 = blockIdx.x * tiles_per_wg;
+    const uint32_t t1 = min(n_tiles, t0 + tiles_per_wg);
+    const uint32_t nkc = dpad / KC;
+    const uint32_t steps = t0 < t1 ? (t1 - t0) * nkc : 0;
+    Cand *my_cand = cand + (size_t)blockIdx.x * QP * MMAX;
+
+    // step u = (tile t0 + u / nkc, chunk u % nkc); the row chunk and the query chunk of step u + 1 are loaded during step u
+    auto row_ptr = [&](uint32_t u) {
+        const size_t row = (size_t)(t0 + u / nkc) * TILE + w * 16 + r16;  // < the slab's rows (padded to TILE)
+        return slab + row * dpad + (u % nkc) * KC + 4 * h;
+    };
+    constexpr int QV = QB * 16 * (KC / 4) / 256;  // float4 of the query chunk per thread
+    auto load_q = [&](uint32_t u, float4 *qr) {
+        const uint32_t c = u % nkc;
+#pragma unroll
+        for (int j = 0; j < QV; j++) {
+            const int e = tid + 256 * j, qq = e >> 5, kk = (e & 31) * 4;
+            qr[j] = qq < nq ? *reinterpret_cast<const float4 *>(q + (size_t)qq * dpad + c * KC + kk) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    };
+    float4 a[8], qr[QV];
+    if (steps) {
+        const float *rp = row_ptr(0);
+#pragma unroll
+        for (int s = 0; s < 8; s++) a[s] = *reinterpret_cast<const float4 *>(rp + 16 * s);
+        load_q(0, qr);
+    }
+    f32x4 acc[QB];
+#pragma unroll
+    for (int b = 0; b < QB; b++) acc[b] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    for (uint32_t u = 0; u < steps; u++) {
+        __syncthreads();  // the previous chunk's Qs reads are done
+#pragma unroll
+        for (int j = 0; j < QV; j++) {
+            const int e = tid + 256 * j, qq = e >> 5, kk = (e & 31) * 4;
+            *reinterpret_cast<float4 *>(Qs + qq * QS_LD + kk) = qr[j];
+        }
+        __syncthreads();
+        float4 an[8];
+        if (u + 1 < steps) {
+            const float *rp = row_ptr(u + 1);
+#pragma unroll
+            for (int s = 0; s < 8; s++) an[s] = *reinterpret_cast<const float4 *>(rp + 16 * s);
+            load_q(u + 1, qr);
+        }
+#pragma unroll
+        for (int s = 0; s < 8; s++) {
+#pragma unroll
+            for (int b = 0; b < QB; b++) {
+                const float4 bq = *reinterpret_cast<const float4 *>(Qs + (b * 16 + r16) * QS_LD + 16 * s + 4 * h);
+                acc[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s].x, bq.x, acc[b], 0, 0, 0);
+                acc[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s].y, bq.y, acc[b], 0, 0, 0);
+                acc[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s].z, bq.z, acc[b], 0, 0, 0);
+                acc[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s].w, bq.w, acc[b], 0, 0, 0);
+            }
+        }
+        if (u + 1 < steps) {
+#pragma unroll
+            for (int s = 0; s < 8; s++) a[s] = an[s];
+        }
+        if ((u + 1) % nkc) continue;
+
+        // ---- end of a tile: scores to LDS, then selection (wave w owns queries w, w + 4, ...)
+        const uint32_t t = t0 + u / nkc;
+#pragma unroll
+        for (int b = 0; b < QB; b++) {
+#pragma unroll
+            for (int r = 0; r < 4; r++) S[(b * 16 + r16) * S_LD + w * 16 + h * 4 + r] = acc[b][r];
+            acc[b] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+        __syncthreads();
+        const uint32_t grow = t * TILE + lane;
+        const bool row_ok = grow < n_rows && valid[grow];
+        for (int qq = w; qq < nq; qq += 4) {
+            if (!qvalid[qq]) continue;
+            bool ok = row_ok;
+            if (radius >= 0) {
+                const int64_t d = (int64_t)grow - (int64_t)qid[qq];
+                ok = ok && (d > radius || d < -radius);
+            }
+            const Cand e{S[qq * S_LD + lane], grow};
+            int L = len[qq];
+            const bool pass = ok && (L < M || ahead(e, thr[qq]));
+            const uint64_t m = __ballot(pass);
+            if (!m) continue;
+            int np = pn[qq];
+            if (np + 64 > PEND) {
+                L = merge_pending(pend + qq * PEND, np, my_cand + qq * MMAX, L, M, scratch + w * MMAX, thr + qq);
+                np = 0;
+            }
+            if (pass) pend[qq * PEND + np + lanes_below(m)] = e;
+            wave_sync();
+            if (lane == 0) {
+                len[qq] = L;
+                pn[qq] = np + __popcll(m);
+            }
+            wave_sync();
+        }
+    }
+    __syncthreads();
+    for (int qq = w; qq < nq; qq += 4) {
+        int L = len[qq];
+        const int np = pn[qq];
+        if (np) L = merge_pending(pend + qq * PEND, np, my_cand + qq * MMAX, L, M, scratch + w * MMAX, thr + qq);
+        if (lane == 0) cand_len[blockIdx.x * QP + qq] = L;
+    }
+}
+
+// one wave per query: the workgroups' sorted lists -> the final top-M (out [nq][M], count [nq])
+__global__ __launch_bounds__(64) void index_merge_kernel(const Cand *__restrict__ cand, const int *__restrict__ cand_len, int n_wg, int M,
+                                                         Cand *__restrict__ out, uint32_t *__restrict__ count) {
+    __shared__ Cand list[MMAX], scratch[MMAX], pend[PEND];
+    __shared__ Cand thr;
+    const int q = blockIdx.x, lane = threadIdx.x;
+    int len = 0, np = 0;
+    for (int g = 0; g < n_wg; g++) {
+        const Cand *src = cand + ((size_t)g * QP + q) * MMAX;
+        const int lg = cand_len[g * QP + q];
+        for (int j = 0; j < lg; j += 64) {
+            const bool in = j + lane < lg;
+            const Cand e = in ? src[j + lane] : Cand{0.f, 0u};
+            const bool pass = in && (len < M || ahead(e, thr));
+            const uint64_t m = __ballot(pass);
+            if (!m) break;  // the list is sorted: nothing after a rejected entry can pass
+            if (np + 64 > PEND) {
+                len = merge_pending(pend, np, list, len, M, scratch, &thr);
+                np = 0;
+            }
+            if (pass) pend[np + lanes_below(m)] = e;
+            np += __popcll(m);
+            wave_sync();
+        }
+    }
+    if (np) len = merge_pending(pend, np, list, len, M, scratch, &thr);
+    for (int i = lane; i < len; i += 64) out[(size_t)q * M + i] = list[i];
+    if (lane == 0) count[q] = (uint32_t)len;
+}
+
+std::mutex g_lds_mu;
+uint64_t g_lds_ready = 0;  // devices (ordinal < 64) on which the scan kernels may use SCAN_LDS bytes
+
+// the > 64 KB LDS opt-in of the scan kernels, once per device (under the capture gate: it may not overlap a capture)
+hipError_t prepare_scan(int dev) {
+    std::lock_guard<std::mutex> lk(g_lds_mu);
+    if (dev < 64 && ((g_lds_ready >> dev) & 1)) return hipSuccess;
+    bn::gated::Shared g;
+    const void *ks[] = {reinterpret_cast<const void *>(index_scan_kernel<1>), reinterpret_cast<const void *>(index_scan_kernel<2>),
+                        reinterpret_cast<const void *>(index_scan_kernel<3>), reinterpret_cast<const void *>(index_scan_kernel<4>)};
+    for (const void *k : ks) {
+        hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SCAN_LDS);
+        if (e != hipSuccess) return e;
+    }
+    if (dev < 64) g_lds_ready |= 1ull << dev;
+    return hipSuccess;
+}
+
+}  // namespace
+
+struct bn_index {
+    int device = 0;
+    size_t dim = 0, dpad = 0, cap = 0, cap_pad = 0, size = 0;
+    int max_wg = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev = nullptr;  // recorded after the last bn_index_add_ctx on the context's stream
+    bool pending = false;
+    float *slab = nullptr;      // [cap_pad, dpad]
+    uint8_t *valid = nullptr;   // [cap_pad]
+    float *d_stage = nullptr;   // [STAGE_ROWS, dim]: host rows / queries on their way in
+    float *d_q = nullptr;       // [QCHUNK, dpad]
+    uint8_t *d_qvalid = nullptr;
+    uint32_t *d_qid = nullptr;  // [QCHUNK]
+    Cand *d_cand = nullptr;     // [max_wg, QP, MMAX]
+    int *d_cand_len = nullptr;  // [max_wg, QP]
+    Cand *d_out = nullptr;      // [QCHUNK, MMAX]
+    uint32_t *d_count = nullptr;
+    Cand *h_out = nullptr;  // pinned mirrors of d_out / d_count
+    uint32_t *h_count = nullptr;
+};
+
+namespace {
+
+using bn::set_last_error;
+
+#define IDX_TRY(expr)                                                                                              \
+    do {                                                                                                           \
+        hipError_t e_ = (expr);                                                                                    \
+        if (e_ != hipSuccess) return set_last_error(BN_ERR_BACKEND, std::string(#expr) + " failed: " + hipGetErrorString(e_)); \
+    } while (0)
+
+void release(bn_index *x) {
+    if (!x) return;
+    (void)bn::use_device(x->device);
+    if (x->stream) (void)hipStreamSynchronize(x->stream);
+    if (x->ev) {
+        (void)hipEventSynchronize(x->ev);
+        (void)bn::gated::EventDestroy(x->ev);
+    }
+    for (void *p : {(void *)x->slab, (void *)x->valid, (void *)x->d_stage, (void *)x->d_q, (void *)x->d_qvalid, (void *)x->d_qid, (void *)x->d_cand,
+                    (void *)x->d_cand_len, (void *)x->d_out, (void *)x->d_count})
+        if (p) (void)bn::gated::Free(p);
+    if (x->h_out) (void)bn::gated::HostFree(x->h_out);
+    if (x->h_count) (void)bn::gated::HostFree(x->h_count);
+    if (x->stream) (void)bn::gated::StreamDestroy(x->stream);
+    delete x;
+}
+
+// device and stream of the index current, and the index's stream ordered after the last bn_index_add_ctx
+bn_status begin(const bn_index *x) {
+    IDX_TRY(bn::use_device(x->device));
+    if (x->pending) IDX_TRY(hipStreamWaitEvent(x->stream, x->ev, 0));
+    return BN_OK;
+}
+
+bn_status check_launch(const char *what) {
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return set_last_error(BN_ERR_BACKEND, std::string(what) + " launch failed: " + hipGetErrorString(e));
+    return BN_OK;
+}
+
+bn_status check_search_args(const bn_index *x, const void *queries, size_t n_queries, size_t top_m, size_t m_stride, const uint64_t *id_out,
+                            const float *score_out, const uint32_t *count_out) {
+    if (!x) return set_last_error(BN_ERR_INVALID_ARG, "null index");
+    if (top_m < 1 || top_m > MMAX) return set_last_error(BN_ERR_INVALID_ARG, "top_m must be in 1..256, got " + std::to_string(top_m));
+    if (m_stride < top_m) return set_last_error(BN_ERR_INVALID_ARG, "m_stride < top_m");
+    if (n_queries && (!queries || !id_out || !score_out || !count_out)) return set_last_error(BN_ERR_INVALID_ARG, "null argument");
+    return BN_OK;
+}
+
+// the scan + merge passes over d_q[0 .. nq) (nq <= QCHUNK), results into the pinned mirrors; synchronous
+bn_status run_search(bn_index *x, size_t nq, bool by_id, int64_t radius, int M) {
+    const uint32_t n_rows = (uint32_t)x->size;
+    const uint32_t n_tiles = (n_rows + TILE - 1) / TILE;
+    const uint32_t tpw = (n_tiles + x->max_wg - 1) / x->max_wg;
+    const uint32_t n_wg = (n_tiles + tpw - 1) / tpw;
+    for (size_t p0 = 0; p0 < nq; p0 += QP) {
+        const int np = (int)std::min<size_t>(QP, nq - p0);
+        const float *q = x->d_q + p0 * x->dpad;
+        const uint8_t *qv = x->d_qvalid + p0;
+        const uint32_t *qid = by_id ? x->d_qid + p0 : nullptr;
+        const int64_t rad = by_id ? radius : -1;
+        const dim3 grid(n_wg), block(256);
+        switch ((np + 15) / 16) {
+            case 1: hipLaunchKernelGGL(index_scan_kernel<1>, grid, block, SCAN_LDS, x->stream, x->slab, x->valid, n_rows, (uint32_t)x->dpad, q, qv, np, qid, rad, M, tpw, x->d_cand, x->d_cand_len); break;
+            case 2: hipLaunchKernelGGL(index_scan_kernel<2>, grid, block, SCAN_LDS, x->stream, x->slab, x->valid, n_rows, (uint32_t)x->dpad, q, qv, np, qid, rad, M, tpw, x->d_cand, x->d_cand_len); break;
+            case 3: hipLaunchKernelGGL(index_scan_kernel<3>, grid, block, SCAN_LDS, x->stream, x->slab, x->valid, n_rows, (uint32_t)x->dpad, q, qv, np, qid, rad, M, tpw, x->d_cand, x->d_cand_len); break;
+            default: hipLaunchKernelGGL(index_scan_kernel<4>, grid, block, SCAN_LDS, x->stream, x->slab, x->valid, n_rows, (uint32_t)x->dpad, q, qv, np, qid, rad, M, tpw, x->d_cand, x->d_cand_len); break;
+        }
+        bn_status st = check_launch("index scan");
+        if (st != BN_OK) return st;
+        hipLaunchKernelGGL(index_merge_kernel, dim3(np), dim3(64), 0, x->stream, x->d_cand, x->d_cand_len, (int)n_wg, M, x->d_out + p0 * M, x->d_count + p0);
+        st = check_launch("index merge");
+        if (st != BN_OK) return st;
+    }
+    IDX_TRY(hipMemcpyAsync(x->h_out, x->d_out, nq * M * sizeof(Cand), hipMemcpyDeviceToHost, x->stream));
+    IDX_TRY(hipMemcpyAsync(x->h_count, x->d_count, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, x->stream));
+    IDX_TRY(hipStreamSynchronize(x->stream));
+    return BN_OK;
+}
+
+void scatter(const bn_index *x, size_t nq, size_t M, size_t m_stride, uint64_t *id_out, float *score_out, uint32_t *count_out) {
+    for (size_t i = 0; i < nq; i++) {
+        const uint32_t n = x->h_count[i];
+        count_out[i] = n;
+        for (uint32_t j = 0; j < n; j++) {
+            id_out[i * m_stride + j] = x->h_out[i * M + j].id;
+            score_out[i * m_stride + j] = x->h_out[i * M + j].s;
+        }
+    }
+}
+
+bn_status reserve_rows(const bn_index *x, size_t n) {
+    if (n > x->cap - x->size)
+        return set_last_error(BN_ERR_INVALID_ARG, "append of " + std::to_string(n) + " rows exceeds the index capacity (" + std::to_string(x->size) + " of " +
+                                                      std::to_string(x->cap) + " rows used)");
+    return BN_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+bn_status bn_index_create(int32_t device, size_t dim, size_t capacity_rows, bn_index **out) {
+    if (!out) return set_last_error(BN_ERR_INVALID_ARG, "null argument");
+    *out = nullptr;
+    if (dim == 0) return set_last_error(BN_ERR_INVALID_ARG, "dim must be at least 1");
+    if (dim > (1u << 20)) return set_last_error(BN_ERR_INVALID_ARG, "dim above 2^20");
+    if (capacity_rows == 0) return set_last_error(BN_ERR_INVALID_ARG, "capacity_rows must be at least 1");
+    if (capacity_rows >= 0xffffffffull - TILE) return set_last_error(BN_ERR_INVALID_ARG, "capacity_rows must be below 2^32 - 64");
+    if (bn_device_count() <= 0) return set_last_error(BN_ERR_NO_DEVICE, "no gfx950 device visible");
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) return set_last_error(BN_ERR_NO_DEVICE, "no such device");
+    IDX_TRY(bn::use_device(device));
+    IDX_TRY(prepare_scan(device));
+    std::unique_ptr<bn_index, void (*)(bn_index *)> x(new bn_index, release);
+    x->device = device;
+    x->dim = dim;
+    x->dpad = (dim + KC - 1) / KC * KC;
+    x->cap = capacity_rows;
+    x->cap_pad = (capacity_rows + TILE - 1) / TILE * TILE;
+    int cus = 0;
+    IDX_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+    x->max_wg = std::max(1, cus);
+    IDX_TRY(bn::gated::StreamCreateWithFlags(&x->stream, hipStreamNonBlocking));
+    IDX_TRY(bn::gated::EventCreateWithFlags(&x->ev, hipEventDisableTiming));
+    IDX_TRY(bn::gated::Malloc(&x->slab, x->cap_pad * x->dpad * sizeof(float)));
+    IDX_TRY(bn::gated::Memset(x->slab, 0, x->cap_pad * x->dpad * sizeof(float)));
+    IDX_TRY(bn::gated::Malloc(&x->valid, x->cap_pad));
+    IDX_TRY(bn::gated::Memset(x->valid, 0, x->cap_pad));
+    IDX_TRY(bn::gated::Malloc(&x->d_stage, STAGE_ROWS * dim * sizeof(float)));
+    IDX_TRY(bn::gated::Malloc(&x->d_q, QCHUNK * x->dpad * sizeof(float)));
+    IDX_TRY(bn::gated::Malloc(&x->d_qvalid, QCHUNK));
+    IDX_TRY(bn::gated::Malloc(&x->d_qid, QCHUNK * sizeof(uint32_t)));
+    IDX_TRY(bn::gated::Malloc(&x->d_cand, (size_t)x->max_wg * QP * MMAX * sizeof(Cand)));
+    IDX_TRY(bn::gated::Malloc(&x->d_cand_len, (size_t)x->max_wg * QP * sizeof(int)));
+    IDX_TRY(bn::gated::Malloc(&x->d_out, QCHUNK * MMAX * sizeof(Cand)));
+    IDX_TRY(bn::gated::Malloc(&x->d_count, QCHUNK * sizeof(uint32_t)));
+    IDX_TRY(bn::gated::HostMalloc(&x->h_out, QCHUNK * MMAX * sizeof(Cand), 0));
+    IDX_TRY(bn::gated::HostMalloc(&x->h_count, QCHUNK * sizeof(uint32_t), 0));
+    *out = x.release();
+    return BN_OK;
+}
+
+void bn_index_free(bn_index *x) { release(x); }
+
+size_t bn_index_size(const bn_index *x) { return x ? x->size : 0; }
+size_t bn_index_dim(const bn_index *x) { return x ? x->dim : 0; }
+
+bn_status bn_index_add_host(bn_index *x, const float *rows, size_t n, uint64_t *first_id) {
+    if (!x) return set_last_error(BN_ERR_INVALID_ARG, "null index");
+    if (n && !rows) return set_last_error(BN_ERR_INVALID_ARG, "null rows");
+    bn_status st = reserve_rows(x, n);
+    if (st != BN_OK) return st;
+    if ((st = begin(x)) != BN_OK) return st;
+    const size_t first = x->size;
+    for (size_t r0 = 0; r0 < n; r0 += STAGE_ROWS) {
+        const size_t k = std::min(STAGE_ROWS, n - r0);
+        IDX_TRY(hipStreamSynchronize(x->stream));  // the previous chunk's kernel has read the staging buffer
+        IDX_TRY(bn::gated::Memcpy(x->d_stage, rows + r0 * x->dim, k * x->dim * sizeof(float), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(index_normalise_kernel, dim3((unsigned)((k + 3) / 4)), dim3(256), 0, x->stream, x->d_stage, x->dim, (uint32_t)k,
+                           (uint32_t)x->dim, x->slab + (first + r0) * x->dpad, (uint32_t)x->dpad, x->valid + first + r0);
+        if ((st = check_launch("index normalise")) != BN_OK) return st;
+    }
+    IDX_TRY(hipStreamSynchronize(x->stream));
+    x->size = first + n;
+    if (first_id) *first_id = first;
+    return BN_OK;
+}
+
+bn_status bn_index_add_ctx(bn_index *x, bn_ctx *c, size_t batch_size, uint64_t *first_id) {
+    if (!x || !c) return set_last_error(BN_ERR_INVALID_ARG, "null argument");
+    bn::CtxEmbedding e;
+    bn_status st = bn::ctx_embedding(c, &e);
+    if (st != BN_OK) return st;
+    if (e.row_elems != x->dim)
+        return set_last_error(BN_ERR_INVALID_ARG, "embedding dimension " + std::to_string(e.row_elems) + " differs from the index's " + std::to_string(x->dim));
+    if (e.device != x->device) return set_last_error(BN_ERR_INVALID_ARG, "the context lives on device " + std::to_string(e.device) + ", the index on " + std::to_string(x->device));
+    if (batch_size > e.last_batch)
+        return set_last_error(BN_ERR_INVALID_ARG, "batch_size " + std::to_string(batch_size) + " exceeds the context's last run (" + std::to_string(e.last_batch) + " rows)");
+    if ((st = reserve_rows(x, batch_size)) != BN_OK) return st;
+    const size_t first = x->size;
+    if (batch_size) {
+        IDX_TRY(bn::use_device(x->device));
+        // the index's own stream is idle between calls; appends from several contexts stay in call order
+        if (x->pending) IDX_TRY(hipStreamWaitEvent(e.stream, x->ev, 0));
+        hipLaunchKernelGGL(index_normalise_kernel, dim3((unsigned)((batch_size + 3) / 4)), dim3(256), 0, e.stream, e.d_rows, e.row_elems,
+                           (uint32_t)batch_size, (uint32_t)x->dim, x->slab + first * x->dpad, (uint32_t)x->dpad, x->valid + first);
+        if ((st = check_launch("index normalise")) != BN_OK) return st;
+        IDX_TRY(hipEventRecord(x->ev, e.stream));
+        x->pending = true;
+        x->size = first + batch_size;
+    }
+    if (first_id) *first_id = first;
+    return BN_OK;
+}
+
+bn_status bn_index_read(const bn_index *x, uint64_t first, size_t count, float *host_out) {
+    if (!x) return set_last_error(BN_ERR_INVALID_ARG, "null index");
+    if (first > x->size || count > x->size - first) return set_last_error(BN_ERR_INVALID_ARG, "rows out of range");
+    if (count && !host_out) return set_last_error(BN_ERR_INVALID_ARG, "null host buffer");
+    bn_status st = begin(x);
+    if (st != BN_OK) return st;
+    IDX_TRY(hipStreamSynchronize(x->stream));
+    std::vector<float> tmp;
+    for (size_t r0 = 0; r0 < count; r0 += STAGE_ROWS) {
+        const size_t k = std::min(STAGE_ROWS, count - r0);
+        tmp.resize(k * x->dpad);
+        IDX_TRY(bn::gated::Memcpy(tmp.data(), x->slab + (first + r0) * x->dpad, k * x->dpad * sizeof(float), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < k; i++) memcpy(host_out + (r0 + i) * x->dim, tmp.data() + i * x->dpad, x->dim * sizeof(float));
+    }
+    return BN_OK;
+}
+
+bn_status bn_index_search(bn_index *x, const float *queries, size_t n_queries, size_t top_m, size_t m_stride, uint64_t *id_out, float *score_out,
+                          uint32_t *count_out) {
+    bn_status st = check_search_args(x, queries, n_queries, top_m, m_stride, id_out, score_out, count_out);
+    if (st != BN_OK) return st;
+    if ((st = begin(x)) != BN_OK) return st;
+    for (size_t q0 = 0; q0 < n_queries; q0 += QCHUNK) {
+        const size_t nq = std::min(QCHUNK, n_queries - q0);
+        if (x->size == 0) {
+            std::fill(count_out + q0, count_out + q0 + nq, 0u);
+            continue;
+        }
+        for (size_t s0 = 0; s0 < nq; s0 += STAGE_ROWS) {
+            const size_t k = std::min(STAGE_ROWS, nq - s0);
+            IDX_TRY(hipStreamSynchronize(x->stream));
+            IDX_TRY(bn::gated::Memcpy(x->d_stage, queries + (q0 + s0) * x->dim, k * x->dim * sizeof(float), hipMemcpyHostToDevice));
+            hipLaunchKernelGGL(index_normalise_kernel, dim3((unsigned)((k + 3) / 4)), dim3(256), 0, x->stream, x->d_stage, x->dim, (uint32_t)k,
+                               (uint32_t)x->dim, x->d_q + s0 * x->dpad, (uint32_t)x->dpad, x->d_qvalid + s0);
+            if ((st = check_launch("index normalise")) != BN_OK) return st;
+        }
+        if ((st = run_search(x, nq, false, -1, (int)top_m)) != BN_OK) return st;
+        scatter(x, nq, top_m, m_stride, id_out + q0 * m_stride, score_out + q0 * m_stride, count_out + q0);
+    }
+    return BN_OK;
+}
+
+bn_status bn_index_search_ids(bn_index *x, const uint64_t *query_ids, size_t n_queries, int64_t exclude_radius, size_t top_m, size_t m_stride,
+                              uint64_t *id_out, float *score_out, uint32_t *count_out) {
+    bn_status st = check_search_args(x, query_ids, n_queries, top_m, m_stride, id_out, score_out, count_out);
+    if (st != BN_OK) return st;
+    for (size_t i = 0; i < n_queries; i++)
+        if (query_ids[i] >= x->size) return set_last_error(BN_ERR_INVALID_ARG, "query id " + std::to_string(query_ids[i]) + " is not in the index");
+    if ((st = begin(x)) != BN_OK) return st;
+    std::vector<uint32_t> ids;
+    for (size_t q0 = 0; q0 < n_queries; q0 += QCHUNK) {
+        const size_t nq = std::min(QCHUNK, n_queries - q0);
+        ids.assign(query_ids + q0, query_ids + q0 + nq);
+        IDX_TRY(hipStreamSynchronize(x->stream));
+        IDX_TRY(bn::gated::Memcpy(x->d_qid, ids.data(), nq * sizeof(uint32_t), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(index_gather_kernel, dim3((unsigned)nq), dim3(256), 0, x->stream, x->slab, x->valid, x->d_qid, (uint32_t)x->dpad, x->d_q,
+                           x->d_qvalid);
+        if ((st = check_launch("index gather")) != BN_OK) return st;
+        if ((st = run_search(x, nq, true, exclude_radius, (int)top_m)) != BN_OK) return st;
+        scatter(x, nq, top_m, m_stride, id_out + q0 * m_stride, score_out + q0 * m_stride, count_out + q0);
+    }
+    return BN_OK;
+}
+
+}  // extern "C"
