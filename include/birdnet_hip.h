@@ -448,6 +448,60 @@ bn_status bn_index_search(bn_index *x, const float *queries, size_t n_queries, s
 bn_status bn_index_search_ids(bn_index *x, const uint64_t *query_ids, size_t n_queries, int64_t exclude_radius,
                               size_t top_m, size_t m_stride, uint64_t *id_out, float *score_out, uint32_t *count_out);
 
+/*
+ * Live ingest: a device-resident pool of per-source ring buffers for continuous audio (many recorders, each producing a
+ * window every `step` seconds).  Callers push PCM as it arrives, in the storage format (i16: half the PCIe bytes, and no
+ * overlap sample crosses the bus twice); bn_step_live batches the ready windows of ALL sources into one context batch, cut on
+ * the device.  Per source, every window is bit-identical to bn_step_windows over a bn_recording of that source's
+ * concatenated pushes.
+ *
+ *   Windows     chunk_audio's (src/bin/birdnet-analyze.rs:707-743) over everything pushed to a source since its creation or
+ *               last reset: window k starts at sample k * step.  Before close window k is ready once k*step + S <= pushed;
+ *               at close every remaining window with k*step < pushed becomes ready, samples past the end reading 0.  A
+ *               source closed with 0 samples has no windows.  i16 converts as v / 32768.0f.
+ *   Geometry    S % 4 == 0, 1 <= step <= S, S + step <= ring_samples < 2^31; otherwise BN_ERR_INVALID_ARG.
+ *   Scheduling  FIFO by readiness: a window gets a sequence number when it becomes ready (in k order within a push or close,
+ *               in array order within a push_many); a step takes the lowest sequence numbers, its rows in that order.  Every
+ *               window is scheduled exactly once, a source's windows in increasing k.
+ *   Room        host accounting only: needed_from = min(pushed, next_unscheduled_k * step), room = ring_samples - (pushed -
+ *               needed_from).  A push past the room is refused whole (push_many: the whole call, nothing written).
+ *   Ordering    the pool has a stream of its own.  A step makes the context's stream wait for the pool's last scatter; a
+ *               scatter waits for every gather (of any context) that read ring space it overwrites; pinned staging is
+ *               reused only after the scatter that read it completed.  Several contexts may step one pool with sync = 0.
+ *   Refusals    BN_ERR_INVALID_ARG (message in bn_last_error, pool unchanged): a source out of range, an unknown format, a
+ *               push or close after close (until reset), max_windows > bn_ctx_max_batch, a context on another device or of
+ *               another segment length, NULL where data is required.  Without a gfx950 device: BN_ERR_NO_DEVICE.
+ *   Threading   one thread at a time per pool, like a context.
+ */
+typedef struct bn_live bn_live;
+bn_status bn_live_create(int32_t device, int32_t n_sources, int32_t format, size_t segment_samples, size_t step_samples,
+                         size_t ring_samples, bn_live **out);
+void bn_live_free(bn_live *l);
+/* append samples to one source; the caller's buffer is not referenced after return */
+bn_status bn_live_push(bn_live *l, int32_t source, const void *pcm, size_t n_samples);
+/* n chunks in one call (one staging block, one scatter launch); chunk i goes to sources[i] */
+bn_status bn_live_push_many(bn_live *l, size_t n, const int32_t *sources, const void *const *pcm, const size_t *n_samples);
+/* end of stream: the tail windows become ready (zero-padded) */
+bn_status bn_live_close(bn_live *l, int32_t source);
+/* drop the source's unscheduled windows and start a new stream at sample 0 (steps already taken still complete correctly) */
+bn_status bn_live_reset(bn_live *l, int32_t source);
+/* ready, unscheduled windows of a source (source < 0: of all sources); 0 for a NULL pool or a source out of range */
+size_t bn_live_ready(const bn_live *l, int32_t source);
+/* samples a push to this source may add now */
+size_t bn_live_room(const bn_live *l, int32_t source);
+/* diagnostic: HIP events the pool holds to order scatters after gathers (those of gathers in flight plus recycled ones);
+ * completed gathers are retired on every push and step, so this stays bounded by the steps in flight */
+size_t bn_live_event_count(const bn_live *l);
+/* diagnostic: ready, unscheduled window `window` of a source as host f32 [segment_samples], cut by the step's kernel */
+bn_status bn_live_read_window(const bn_live *l, int32_t source, uint64_t window, float *host_out);
+/* the hot call: take up to max_windows (<= bn_ctx_max_batch) ready windows, cut them into the context's input buffer and run
+ * plan + top-K + D2H exactly as bn_step_windows does (results through bn_step_results / bn_ctx_output_device).  Row i is
+ * window window_out[i] of source source_out[i]; *n_out = rows taken (0: nothing ran).  A refusal takes no window.  A backend
+ * error of the step itself, after the windows were taken, returns with *n_out and the provenance naming them: they are
+ * scheduled and their results are lost. */
+bn_status bn_step_live(bn_ctx *c, bn_live *l, size_t max_windows, size_t top_k, int32_t has_min, float min_conf,
+                       int32_t *source_out, uint64_t *window_out, size_t *n_out, int32_t sync);
+
 /* Diagnostic, needs no device: parse the file, build the launch plan (all graph
  * outputs when all_outputs != 0, else logits + embeddings only) and write a
  * text description (one line per launch, then totals) into buf.  Returns the

@@ -187,6 +187,17 @@ struct ChunkResult {
     PredictionResult result;
 };
 
+/* One window of a live source (predict_live): the source, the window's index k in chunk_audio's numbering of that source's
+ * concatenated pushes, its start time (k * step / sample_rate, as chunk_audio reports it) and the prediction. */
+struct LiveChunkResult {
+    int source;
+    size_t chunk;
+    float start_time;
+    PredictionResult result;
+};
+
+class LiveSources;
+
 class Classifier {
    public:
     const ModelConfig &config() const;
@@ -211,10 +222,34 @@ class Classifier {
      * count == SIZE_MAX means "to the end".  overlap >= segment duration => Error::Inference. */
     std::vector<ChunkResult> predict_recording(BatchInferenceContext &ctx, const Recording &rec, float overlap_secs, size_t first_chunk = 0,
                                                size_t count = (size_t)-1, const InferenceOptions &options = {}) const;
+    /* Native extension: up to max_windows (<= ctx.max_batch_size()) ready windows of ALL live sources, oldest first (bn_step_live),
+     * through one batch; labels, top_k, min_confidence, timeout and cancel as predict_recording.  Empty when nothing is ready. */
+    std::vector<LiveChunkResult> predict_live(BatchInferenceContext &ctx, LiveSources &live, size_t max_windows, const InferenceOptions &options = {}) const;
 
    private:
     friend class ClassifierBuilder;
+    friend class LiveSources;
     std::shared_ptr<ClassifierInner> inner_;
+};
+
+/* Live audio from many sources (bn_live): a device-resident ring per source, fed as PCM arrives; windows are chunk_audio's over
+ * each source's concatenated pushes with the classifier's segment length and the given overlap.  Throws Error::Inference when the
+ * pool cannot be created or a push / close / reset is refused (message from the library). */
+class LiveSources {
+   public:
+    /* format: BN_PCM_I16 or BN_PCM_F32; ring_samples 0 => 2 * segment + step; device < 0 => the classifier's (with_rocm) */
+    LiveSources(const Classifier &cl, int32_t n_sources, int32_t format, float overlap_secs = 0.0f, size_t ring_samples = 0, int device = -1);
+    void push(int32_t source, const void *pcm, size_t n_samples);
+    void close(int32_t source);
+    void reset(int32_t source);
+    size_t ready(int32_t source = -1) const;  /* ready, unscheduled windows (source < 0: all sources) */
+    size_t room(int32_t source) const;        /* samples a push to this source may add now */
+    size_t step_samples() const { return step_; }
+    bn_live *raw() const { return live_.get(); }
+
+   private:
+    std::shared_ptr<bn_live> live_;
+    size_t step_ = 0;
 };
 
 class ClassifierBuilder {
@@ -382,6 +417,17 @@ size_t bnh_context_read_output(const bnh_context *ctx, int32_t index, size_t bat
 int32_t bnh_predict_recording(const bnh_classifier *c, bnh_context *ctx, const void *pcm, size_t n_samples, int32_t format, float overlap_secs,
                               size_t first_chunk, size_t count, int64_t timeout_ns, const volatile int32_t *cancel, bnh_results **out,
                               float *start_times, size_t times_cap, bnh_error *err);
+/* LiveSources + Classifier::predict_live.  source_out / chunk_out / start_times receive row i's provenance for i < cap. */
+typedef struct bnh_live bnh_live;
+/* device < 0 => the classifier's device */
+int32_t bnh_live_create(const bnh_classifier *c, int32_t n_sources, int32_t format, float overlap_secs, size_t ring_samples, int32_t device,
+                        bnh_live **out, bnh_error *err);
+void bnh_live_free(bnh_live *l);
+int32_t bnh_live_push(bnh_live *l, int32_t source, const void *pcm, size_t n_samples, bnh_error *err);
+int32_t bnh_live_close(bnh_live *l, int32_t source, bnh_error *err);
+size_t bnh_live_ready(const bnh_live *l, int32_t source);
+int32_t bnh_predict_live(const bnh_classifier *c, bnh_context *ctx, bnh_live *l, size_t max_windows, int64_t timeout_ns, const volatile int32_t *cancel,
+                         bnh_results **out, int32_t *source_out, uint64_t *chunk_out, float *start_times, size_t cap, bnh_error *err);
 size_t bnh_results_len(const bnh_results *r);
 int32_t bnh_result_model_type(const bnh_results *r, size_t i);
 size_t bnh_result_n_predictions(const bnh_results *r, size_t i);

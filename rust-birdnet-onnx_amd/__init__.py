@@ -39,6 +39,7 @@ LIB_PATH = os.environ.get("BN_LIB") or os.path.join(_HERE, "libbirdnet_hip.so") 
 
 BN_MAX_OUTPUTS, BN_MAX_RANK, BN_NAME_LEN = 8, 6, 64
 BN_CTX_DEFAULT, BN_CTX_ALL_OUTPUTS, BN_CTX_NO_GRAPH = 0, 1, 2
+BN_PCM_I16, BN_PCM_F32 = 0, 1
 BN_ERR_MODEL_LOAD, BN_ERR_UNSUPPORTED_MODEL, BN_ERR_MODEL_DETECTION, BN_ERR_NO_DEVICE = 6, 7, 8, 9  # bn_status values the harness names
 
 # every symbol include/birdnet_hip.h and include/birdnet_host.h declare
@@ -53,6 +54,8 @@ ENGINE_SYMBOLS = [
     "bn_group_uses_rccl", "bn_group_get_stats", "bn_shard_range", "bn_group_analyze_recording", "bn_group_last_error", "bn_recording_create_resampled", "bn_resample_table", "bn_recording_read_f32", "bn_last_error",
     "bn_index_create", "bn_index_free", "bn_index_size", "bn_index_dim", "bn_index_add_host", "bn_index_add_ctx", "bn_index_read",
     "bn_index_search", "bn_index_search_ids",
+    "bn_live_create", "bn_live_free", "bn_live_push", "bn_live_push_many", "bn_live_close", "bn_live_reset", "bn_live_ready",
+    "bn_live_room", "bn_live_event_count", "bn_live_read_window", "bn_step_live",
 ]
 HOST_SYMBOLS = [
     "bnh_classifier_build", "bnh_classifier_free", "bnh_classifier_config", "bnh_classifier_provider",
@@ -64,6 +67,7 @@ HOST_SYMBOLS = [
     "bnh_result_embeddings", "bnh_results_free", "bnh_parse_labels", "bnh_parse_labels_format", "bnh_chunk_plan",
     "bnh_calculate_week", "bnh_validate_coordinates", "bnh_validate_date", "bnh_range_filter_build", "bnh_range_filter_free",
     "bnh_range_filter_predict", "bnh_range_filter_label", "bnh_filter_predictions",
+    "bnh_live_create", "bnh_live_free", "bnh_live_push", "bnh_live_close", "bnh_live_ready", "bnh_predict_live",
 ]
 
 
@@ -177,6 +181,17 @@ def _load() -> C.CDLL:
         "bn_index_read": (i32, [vp, C.c_uint64, sz, f32p]),
         "bn_index_search": (i32, [vp, f32p, sz, sz, sz, C.POINTER(C.c_uint64), f32p, u32p]),
         "bn_index_search_ids": (i32, [vp, C.POINTER(C.c_uint64), sz, C.c_int64, sz, sz, C.POINTER(C.c_uint64), f32p, u32p]),
+        "bn_live_create": (i32, [i32, i32, i32, sz, sz, sz, C.POINTER(vp)]),
+        "bn_live_free": (None, [vp]),
+        "bn_live_push": (i32, [vp, i32, vp, sz]),
+        "bn_live_push_many": (i32, [vp, sz, C.POINTER(C.c_int32), C.POINTER(vp), C.POINTER(sz)]),
+        "bn_live_close": (i32, [vp, i32]),
+        "bn_live_reset": (i32, [vp, i32]),
+        "bn_live_ready": (sz, [vp, i32]),
+        "bn_live_room": (sz, [vp, i32]),
+        "bn_live_event_count": (sz, [vp]),
+        "bn_live_read_window": (i32, [vp, i32, C.c_uint64, f32p]),
+        "bn_step_live": (i32, [vp, vp, sz, sz, i32, C.c_float, C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.POINTER(sz), i32]),
         # host mirror
         "bnh_classifier_build": (i32, [C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), sz, i32, C.c_int64, i32,
                                        C.c_float, i32, C.POINTER(vp), C.POINTER(BnhError)]),
@@ -210,6 +225,13 @@ def _load() -> C.CDLL:
         "bnh_range_filter_predict": (i32, [vp, C.c_float, C.c_float, C.c_uint32, C.c_uint32, u32p, f32p, sz, C.POINTER(sz), C.POINTER(BnhError)]),
         "bnh_range_filter_label": (C.c_char_p, [vp, sz]),
         "bnh_filter_predictions": (sz, [C.POINTER(C.c_char_p), f32p, sz, C.POINTER(C.c_char_p), f32p, sz, C.c_float, i32, u32p, f32p]),
+        "bnh_live_create": (i32, [vp, i32, i32, C.c_float, sz, i32, C.POINTER(vp), C.POINTER(BnhError)]),
+        "bnh_live_free": (None, [vp]),
+        "bnh_live_push": (i32, [vp, i32, vp, sz, C.POINTER(BnhError)]),
+        "bnh_live_close": (i32, [vp, i32, C.POINTER(BnhError)]),
+        "bnh_live_ready": (sz, [vp, i32]),
+        "bnh_predict_live": (i32, [vp, vp, vp, sz, C.c_int64, C.POINTER(C.c_int32), C.POINTER(vp), C.POINTER(C.c_int32),
+                                   C.POINTER(C.c_uint64), f32p, sz, C.POINTER(BnhError)]),
         "bnh_results_len": (sz, [vp]),
         "bnh_result_model_type": (i32, [vp, sz]),
         "bnh_result_n_predictions": (sz, [vp, sz]),
@@ -520,6 +542,52 @@ class Classifier:
         results = _collect(res)
         return list(zip(times[:len(results)].tolist(), results))
 
+    def predict_live(self, context: BatchInferenceContext, live: "LiveSources", max_windows: int,
+                     options: Optional[InferenceOptions] = None) -> list:
+        """Classifier::predict_live: up to max_windows ready windows of all live sources, oldest first, as one batch.
+        Returns [(source, chunk, start_time, PredictionResult)]."""
+        options = options or InferenceOptions()
+        t, c = options._raw()
+        res, err = C.c_void_p(), BnhError()
+        cap = max(max_windows, 1)
+        src, chunk, times = np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.uint64), np.zeros(cap, dtype=np.float32)
+        if lib.bnh_predict_live(self._h, context._h, live._h, max_windows, t, c, C.byref(res), src.ctypes.data_as(C.POINTER(C.c_int32)),
+                                chunk.ctypes.data_as(C.POINTER(C.c_uint64)), times.ctypes.data_as(C.POINTER(C.c_float)), cap, C.byref(err)):
+            raise Error(err)
+        results = _collect(res)
+        return [(int(src[i]), int(chunk[i]), float(times[i]), r) for i, r in enumerate(results)]
+
+
+class LiveSources:
+    """birdnet::LiveSources: live pools through the host mirror (windows of the classifier's segment length, chunk_audio's step
+    for the given overlap; ring_samples 0 => 2 * segment + step; device < 0 => the classifier's)."""
+
+    def __init__(self, classifier: Classifier, n_sources: int, fmt: int = BN_PCM_I16, overlap_secs: float = 0.0, ring_samples: int = 0,
+                 device: int = -1):
+        h, err = C.c_void_p(), BnhError()
+        if lib.bnh_live_create(classifier._h, n_sources, fmt, C.c_float(overlap_secs), ring_samples, device, C.byref(h), C.byref(err)):
+            raise Error(err)
+        self._h, self._dtype = h, (np.int16 if fmt == BN_PCM_I16 else np.float32)
+
+    def __del__(self):
+        if getattr(self, "_h", None) and lib is not None:
+            lib.bnh_live_free(self._h)
+            self._h = None
+
+    def push(self, source: int, samples):
+        a = np.ascontiguousarray(samples, dtype=self._dtype).reshape(-1)
+        err = BnhError()
+        if lib.bnh_live_push(self._h, source, a.ctypes.data_as(C.c_void_p), a.shape[0], C.byref(err)):
+            raise Error(err)
+
+    def close(self, source: int):
+        err = BnhError()
+        if lib.bnh_live_close(self._h, source, C.byref(err)):
+            raise Error(err)
+
+    def ready(self, source: int = -1) -> int:
+        return int(lib.bnh_live_ready(self._h, source))
+
 
 class ClassifierBuilder:
     """reference src/classifier.rs:46-383."""
@@ -785,6 +853,19 @@ class Context:
         if st:
             raise EngineError(st)
 
+    def step_live(self, live: "Live", max_windows: int, top_k: int = 10, min_confidence: Optional[float] = None,
+                  sync: bool = False):
+        """bn_step_live: up to max_windows ready windows of a live pool through the hot path; returns (sources, windows) of the
+        rows taken (empty: nothing ran).  Results through step_results(len(sources))."""
+        src = np.zeros(max(max_windows, 1), dtype=np.int32)
+        win = np.zeros(max(max_windows, 1), dtype=np.uint64)
+        n = C.c_size_t()
+        st = lib.bn_step_live(self._h, live._h, max_windows, top_k, 0 if min_confidence is None else 1, C.c_float(min_confidence or 0.0),
+                              src.ctypes.data_as(C.POINTER(C.c_int32)), win.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(n), 1 if sync else 0)
+        if st:
+            raise EngineError(st)
+        return src[:n.value].copy(), win[:n.value].copy()
+
     def time_kernels(self, batch: int):
         cap = 1024
         names = C.create_string_buffer(cap * BN_NAME_LEN)
@@ -963,6 +1044,76 @@ class Index:
         if st:
             raise EngineError(st)
         return out_ids, scores, counts
+
+class Live:
+    """bn_live: a device-resident pool of per-source ring buffers for continuous audio.  Push int16 / float32 PCM as it arrives;
+    Context.step_live batches the ready windows of all sources, cut on the device (chunk_audio per source)."""
+
+    def __init__(self, device: int, n_sources: int, segment_samples: int, step_samples: int, ring_samples: int, fmt: int = BN_PCM_I16):
+        h = C.c_void_p()
+        st = lib.bn_live_create(device, n_sources, fmt, segment_samples, step_samples, ring_samples, C.byref(h))
+        if st:
+            raise EngineError(st)
+        self._h, self.device, self.n_sources, self.format = h, device, n_sources, fmt
+        self.segment_samples, self.step_samples, self.ring_samples = segment_samples, step_samples, ring_samples
+        self._dtype = np.int16 if fmt == BN_PCM_I16 else np.float32
+
+    def __del__(self):
+        if getattr(self, "_h", None) and lib is not None:
+            lib.bn_live_free(self._h)
+            self._h = None
+
+    def free(self):
+        self.__del__()
+
+    def _pcm(self, samples):
+        a = np.ascontiguousarray(samples, dtype=self._dtype).reshape(-1)
+        return a
+
+    def push(self, source: int, samples):
+        a = self._pcm(samples)
+        st = lib.bn_live_push(self._h, source, a.ctypes.data_as(C.c_void_p), a.shape[0])
+        if st:
+            raise EngineError(st)
+
+    def push_many(self, sources, chunks):
+        """One call for many chunks: chunk i goes to sources[i]; refused whole if any chunk exceeds its source's room."""
+        arrs = [self._pcm(c) for c in chunks]
+        n = len(arrs)
+        src = (C.c_int32 * max(n, 1))(*[int(s) for s in sources])
+        ptrs = (C.c_void_p * max(n, 1))(*[a.ctypes.data for a in arrs])
+        lens = (C.c_size_t * max(n, 1))(*[a.shape[0] for a in arrs])
+        st = lib.bn_live_push_many(self._h, n, src, ptrs, lens)
+        if st:
+            raise EngineError(st)
+
+    def close(self, source: int):
+        st = lib.bn_live_close(self._h, source)
+        if st:
+            raise EngineError(st)
+
+    def reset(self, source: int):
+        st = lib.bn_live_reset(self._h, source)
+        if st:
+            raise EngineError(st)
+
+    def ready(self, source: int = -1) -> int:
+        return int(lib.bn_live_ready(self._h, source))
+
+    def room(self, source: int) -> int:
+        return int(lib.bn_live_room(self._h, source))
+
+    def event_count(self) -> int:
+        """bn_live_event_count: HIP events held for scatter / gather ordering (bounded by the steps in flight)."""
+        return int(lib.bn_live_event_count(self._h))
+
+    def read_window(self, source: int, window: int) -> np.ndarray:
+        out = np.empty(self.segment_samples, dtype=np.float32)
+        st = lib.bn_live_read_window(self._h, source, window, out.ctypes.data_as(C.POINTER(C.c_float)))
+        if st:
+            raise EngineError(st)
+        return out
+
 
 # ---- range filter (reference src/rangefilter.rs) ----
 @dataclass

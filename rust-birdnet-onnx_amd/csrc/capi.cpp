@@ -1879,3 +1879,17 @@ bn_status bn::ctx_embedding(const bn_ctx *c, CtxEmbedding *out) {
     out->last_batch = c->last_batch;
     return BN_OK;
 }
+
+bn_status bn::ctx_step_input(const bn_ctx *c, size_t top_k, CtxStepInput *out) {
+    if (!c || !out) return fail(BN_ERR_INVALID_ARG, "null argument");
+    const Plan &p = *c->pd->plan;
+    const size_t n = (size_t)p.outputs[c->model->cfg.logits_output].row_elems;
+    const size_t k = std::min(top_k, n);
+    if (k == 0 || topk_lds_bytes((int64_t)n, (int64_t)k) == 0) return fail(BN_ERR_INVALID_ARG, "top_k must be in 1..9000");
+    out->device = c->model->device;
+    out->stream = c->stream;
+    out->d_input = c->d_input;
+    out->sample_count = (size_t)p.sample_count;
+    out->max_batch = c->max_batch;
+    return BN_OK;
+}

@@ -19,4 +19,14 @@ struct CtxEmbedding {
     size_t last_batch = 0;
 };
 bn_status ctx_embedding(const bn_ctx *c, CtxEmbedding *out);
+// what bn_step_live needs of a context: its device, stream and input buffer [max_batch, sample_count]; BN_ERR_INVALID_ARG
+// (message set) for a top_k that bn_step_device would refuse
+struct CtxStepInput {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    float *d_input = nullptr;
+    size_t sample_count = 0;
+    size_t max_batch = 0;
+};
+bn_status ctx_step_input(const bn_ctx *c, size_t top_k, CtxStepInput *out);
 }  // namespace bn

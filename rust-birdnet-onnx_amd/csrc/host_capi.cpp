@@ -12,6 +12,9 @@ struct bnh_classifier {
 struct bnh_context {
     std::unique_ptr<BatchInferenceContext> ctx;
 };
+struct bnh_live {
+    LiveSources live;
+};
 struct bnh_results {
     std::vector<PredictionResult> v;
 };
@@ -191,6 +194,40 @@ int32_t bnh_predict_recording(const bnh_classifier *c, bnh_context *ctx, const v
         for (size_t i = 0; i < chunks.size(); i++) {
             if (start_times && i < times_cap) start_times[i] = chunks[i].start_time;
             r->v.push_back(std::move(chunks[i].result));
+        }
+        *out = r.release();
+    });
+}
+
+int32_t bnh_live_create(const bnh_classifier *c, int32_t n_sources, int32_t format, float overlap_secs, size_t ring_samples, int32_t device,
+                        bnh_live **out, bnh_error *err) {
+    if (!out) return set_other(err, "null argument");
+    *out = nullptr;
+    return guarded(err, [&] { *out = new bnh_live{LiveSources(c->cl, n_sources, format, overlap_secs, ring_samples, device)}; });
+}
+void bnh_live_free(bnh_live *l) { delete l; }
+int32_t bnh_live_push(bnh_live *l, int32_t source, const void *pcm, size_t n_samples, bnh_error *err) {
+    return guarded(err, [&] { l->live.push(source, pcm, n_samples); });
+}
+int32_t bnh_live_close(bnh_live *l, int32_t source, bnh_error *err) {
+    return guarded(err, [&] { l->live.close(source); });
+}
+size_t bnh_live_ready(const bnh_live *l, int32_t source) { return l ? l->live.ready(source) : 0; }
+
+int32_t bnh_predict_live(const bnh_classifier *c, bnh_context *ctx, bnh_live *l, size_t max_windows, int64_t timeout_ns, const volatile int32_t *cancel,
+                         bnh_results **out, int32_t *source_out, uint64_t *chunk_out, float *start_times, size_t cap, bnh_error *err) {
+    if (out) *out = nullptr;
+    return guarded(err, [&] {
+        InferenceOptions o = make_opts(timeout_ns, cancel);
+        auto rows = c->cl.predict_live(*ctx->ctx, l->live, max_windows, o);
+        auto r = std::make_unique<bnh_results>();
+        for (size_t i = 0; i < rows.size(); i++) {
+            if (i < cap) {
+                if (source_out) source_out[i] = rows[i].source;
+                if (chunk_out) chunk_out[i] = rows[i].chunk;
+                if (start_times) start_times[i] = rows[i].start_time;
+            }
+            r->v.push_back(std::move(rows[i].result));
         }
         *out = r.release();
     });

@@ -4,6 +4,8 @@
 // lookup, result assembly, buffer/context ownership and locking.
 #include "../../include/birdnet_host.h"
 
+#include <hip/hip_runtime.h>
+
 #include <algorithm>
 #include <cctype>
 #include <cstdio>
@@ -11,6 +13,7 @@
 #include <fstream>
 #include <sstream>
 #include <stdexcept>
+#include <thread>
 
 namespace birdnet {
 
@@ -295,6 +298,89 @@ std::vector<ChunkResult> Classifier::predict_recording(BatchInferenceContext &ct
             const float t = (float)((first + i) * step) / (float)cfg.sample_rate;
             out.push_back(ChunkResult{t, std::move(part[i])});
         }
+    }
+    return out;
+}
+
+LiveSources::LiveSources(const Classifier &cl, int32_t n_sources, int32_t format, float overlap_secs, size_t ring_samples, int device) {
+    const ModelConfig &cfg = cl.config();
+    // chunk_audio's step, as predict_recording computes it
+    const size_t overlap_samples = (size_t)(overlap_secs * (float)cfg.sample_rate);
+    if (overlap_secs < 0.0f || overlap_samples >= cfg.sample_count) throw inference("overlap must be shorter than the segment duration");
+    step_ = cfg.sample_count - overlap_samples;
+    if (ring_samples == 0) ring_samples = 2 * cfg.sample_count + step_;
+    if (device < 0) device = bn_model_device(cl.inner_->model);
+    bn_live *l = nullptr;
+    if (bn_live_create(device, n_sources, format, cfg.sample_count, step_, ring_samples, &l) != BN_OK)
+        throw inference("failed to create the live pool: " + last_backend_error());
+    live_ = std::shared_ptr<bn_live>(l, [](bn_live *p) { bn_live_free(p); });
+}
+
+void LiveSources::push(int32_t source, const void *pcm, size_t n_samples) {
+    if (bn_live_push(live_.get(), source, pcm, n_samples) != BN_OK) throw inference(last_backend_error());
+}
+size_t LiveSources::ready(int32_t source) const { return bn_live_ready(live_.get(), source); }
+size_t LiveSources::room(int32_t source) const { return bn_live_room(live_.get(), source); }
+void LiveSources::close(int32_t source) {
+    if (bn_live_close(live_.get(), source) != BN_OK) throw inference(last_backend_error());
+}
+void LiveSources::reset(int32_t source) {
+    if (bn_live_reset(live_.get(), source) != BN_OK) throw inference(last_backend_error());
+}
+
+std::vector<LiveChunkResult> Classifier::predict_live(BatchInferenceContext &ctx, LiveSources &live, size_t max_windows,
+                                                      const InferenceOptions &options) const {
+    ClassifierInner &in = *inner_;
+    const volatile int32_t *cancel = options.cancellation_token ? options.cancellation_token->raw() : nullptr;
+    if (cancel && *cancel) throw from_status(BN_ERR_CANCELLED, options);
+    const size_t n_ready = std::min(max_windows, live.ready(-1));
+    if (n_ready == 0) return {};
+    std::vector<int32_t> src(n_ready);
+    std::vector<uint64_t> win(n_ready);
+    size_t n = 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    // top_k 0 still runs the step (bn_step_live takes k >= 1) and reports no predictions, as bn_topk does
+    bn_status st = bn_step_live(ctx.ctx_, live.raw(), n_ready, std::max<size_t>(in.top_k, 1), in.min_confidence ? 1 : 0,
+                                in.min_confidence.value_or(0.0f), src.data(), win.data(), &n, 0);
+    if (st != BN_OK) throw from_status(st, options);
+    // wait for the step, honouring cancel / deadline like bn_infer_windows (the stream is polled)
+    hipStream_t stream = static_cast<hipStream_t>(bn_ctx_stream(ctx.ctx_));
+    for (;;) {
+        const hipError_t q = hipStreamQuery(stream);
+        if (q == hipSuccess) break;
+        if (q != hipErrorNotReady) throw inference(std::string("live step failed: ") + hipGetErrorString(q));
+        if (cancel && *cancel) throw from_status(BN_ERR_CANCELLED, options);
+        if (options.timeout && std::chrono::steady_clock::now() - t0 > *options.timeout) throw from_status(BN_ERR_TIMEOUT, options);
+        std::this_thread::sleep_for(std::chrono::microseconds(50));
+    }
+    const float *logits = nullptr, *conf = nullptr;
+    const uint32_t *idx = nullptr, *cnt = nullptr;
+    size_t kstride = 0;
+    if (bn_step_results(ctx.ctx_, &logits, &idx, &conf, &cnt, &kstride) != BN_OK) throw inference(last_backend_error());
+    size_t N = in.config.num_species, E = in.config.embedding_dim.value_or(0);
+    {
+        const float *dp = nullptr;
+        size_t row = 0;
+        if (bn_ctx_output_device(ctx.ctx_, in.raw_cfg.logits_output, &dp, &row) == BN_OK) N = row;
+        if (E && bn_ctx_output_device(ctx.ctx_, in.raw_cfg.embedding_output, &dp, &row) == BN_OK) E = row;
+    }
+    std::vector<float> emb(n * E);
+    if (E && bn_ctx_read_output(ctx.ctx_, in.raw_cfg.embedding_output, n, emb.data()) != BN_OK) throw inference(last_backend_error());
+    const float sr = (float)in.config.sample_rate;
+    std::vector<LiveChunkResult> out;
+    out.reserve(n);
+    for (size_t i = 0; i < n; i++) {
+        PredictionResult r;
+        r.model_type = in.config.model_type;
+        r.raw_scores.assign(logits + i * N, logits + (i + 1) * N);
+        if (E) r.embeddings = std::vector<float>(emb.begin() + i * E, emb.begin() + (i + 1) * E);
+        const size_t c = in.top_k ? cnt[i] : 0;
+        for (size_t j = 0; j < c; j++) {
+            const size_t id = idx[i * kstride + j];
+            r.predictions.push_back(Prediction{id < in.labels.size() ? in.labels[id] : "unknown_" + std::to_string(id), conf[i * kstride + j], id});
+        }
+        // start_time = pos as f32 / sample_rate as f32 (birdnet-analyze.rs:736)
+        out.push_back(LiveChunkResult{src[i], (size_t)win[i], (float)(win[i] * live.step_samples()) / sr, std::move(r)});
     }
     return out;
 }

@@ -1,0 +1,474 @@
+// Live ingest pool behind the C ABI (include/birdnet_hip.h, bn_live_*, bn_step_live): per-source rings in one device slab
+// [n_sources][ring_samples] in the storage format, host bookkeeping of what is pushed, ready and scheduled, and the device
+// ordering between the pool's scatters and the contexts' gathers.  Kernels in live.hip.
+//
+// Ring coordinates.  A source's sample x lives at ring index (base + x) % ring_samples.  A reset moves base past everything
+// pushed so far, so "ring-absolute" positions (base + x) only grow and a gather of the old stream that is still in flight is
+// ordered against the new stream's scatters by the same rule as any other.
+//
+// Ordering.  Each scatter records `scatter_ev` on the pool's stream; a step makes its context's stream wait for it before the
+// gather.  Each gather records an event on its context's stream; per source the pool keeps (first ring-absolute start read,
+// gather id) of the gathers not yet known complete, and a scatter that overwrites ring-absolute positions below p makes the
+// pool's stream wait for every such gather that started reading below p.  The per-row descriptors travel as kernel
+// arguments, so nothing a step writes on the host can race with an earlier step still in flight.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <deque>
+#include <memory>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "capi_internal.h"
+#include "hip_gate.h"
+#include "live.h"
+
+namespace {
+
+constexpr int N_STAGE = 3;  // pinned staging blocks in rotation
+
+struct Source {
+    uint64_t base = 0;       // ring-absolute position of sample 0 of the current stream
+    uint64_t pushed = 0;     // samples pushed since creation / the last reset
+    uint64_t n_ready = 0;    // windows [0, n_ready) have become ready
+    uint64_t sched = 0;      // windows [0, sched) have been scheduled
+    bool closed = false;
+    std::deque<std::pair<uint64_t, uint64_t>> reads;  // (first ring-absolute start read, gather id), increasing
+};
+
+struct Gather {
+    uint64_t id;
+    hipEvent_t ev;
+    bool done;
+};
+
+struct Stage {
+    char *h = nullptr;  // pinned: [tiles][data]
+    char *d = nullptr;  // device copy of the block (copy mode only)
+    size_t cap = 0;
+    hipEvent_t ev = nullptr;
+    bool used = false;
+};
+
+}  // namespace
+
+struct bn_live {
+    int device = 0;
+    int32_t n_sources = 0;
+    int32_t format = BN_PCM_I16;
+    size_t esz = 2;
+    size_t S = 0, step = 0, R = 0;
+    void *slab = nullptr;
+    float *d_window = nullptr;  // bn_live_read_window's output [S]
+    hipStream_t stream = nullptr;
+    hipEvent_t scatter_ev = nullptr;
+    bool scattered = false;
+    bool copy_mode = false;  // BN_LIVE_SCATTER=copy: one async H2D copy of the staging block, then the kernel on device memory
+    std::vector<Source> src;
+    std::deque<std::pair<int32_t, uint64_t>> queue;  // ready, unscheduled windows (source, k) in sequence order
+    std::deque<Gather> gathers;                       // gathers not yet known complete, ids increasing
+    uint64_t next_gather = 0;
+    std::vector<hipEvent_t> free_events;
+    std::vector<int32_t> touched;  // push_impl: per source, its entry in the call's list of touched sources (-1: none)
+    Stage stage[N_STAGE];
+    int next_stage = 0;
+};
+
+namespace {
+
+using bn::set_last_error;
+
+#define LIVE_TRY(expr)                                                                                                             \
+    do {                                                                                                                           \
+        hipError_t e_ = (expr);                                                                                                    \
+        if (e_ != hipSuccess) return set_last_error(BN_ERR_BACKEND, std::string(#expr) + " failed: " + hipGetErrorString(e_)); \
+    } while (0)
+
+bn_status invalid(const std::string &msg) { return set_last_error(BN_ERR_INVALID_ARG, msg); }
+
+bool source_ok(const bn_live *l, int32_t s) { return l && s >= 0 && s < l->n_sources; }
+
+size_t room_of(const bn_live *l, const Source &s) {
+    const uint64_t needed_from = std::min<uint64_t>(s.pushed, s.sched * l->step);
+    return l->R - (size_t)(s.pushed - needed_from);
+}
+
+// windows that are ready given what was pushed (and whether the stream is closed)
+uint64_t ready_limit(const bn_live *l, const Source &s) {
+    if (s.closed) return s.pushed ? (s.pushed + l->step - 1) / l->step : 0;
+    return s.pushed >= l->S ? (s.pushed - l->S) / l->step + 1 : 0;
+}
+
+void make_ready(bn_live *l, int32_t source) {
+    Source &s = l->src[source];
+    const uint64_t lim = ready_limit(l, s);
+    for (uint64_t k = s.n_ready; k < lim; k++) l->queue.emplace_back(source, k);
+    s.n_ready = std::max(s.n_ready, lim);
+}
+
+bn::LiveRow row_of(const bn_live *l, const Source &s, uint64_t k) {
+    const uint64_t start = k * l->step;
+    bn::LiveRow r;
+    r.base = 0;  // set by the caller (slot offset)
+    r.pos = (uint32_t)((s.base + start) % l->R);
+    r.valid = (uint32_t)std::min<uint64_t>(l->S, s.pushed - start);
+    return r;
+}
+
+// retire completed gathers from the front, whichever sources they read, and recycle their events: every push and step calls
+// this, so the pool holds an event only for gathers in flight (and a few recycled ones), however its sources come and go
+void retire_gathers(bn_live *l) {
+    while (!l->gathers.empty()) {
+        Gather &g = l->gathers.front();
+        if (!g.done && hipEventQuery(g.ev) == hipSuccess) g.done = true;
+        if (!g.done) break;
+        l->free_events.push_back(g.ev);
+        l->gathers.pop_front();
+    }
+}
+
+// is gather `id` complete?  (queries its event once)
+bool gather_done(bn_live *l, uint64_t id) {
+    if (l->gathers.empty() || id < l->gathers.front().id) return true;
+    Gather &g = l->gathers[id - l->gathers.front().id];
+    if (!g.done && hipEventQuery(g.ev) == hipSuccess) g.done = true;
+    const bool d = g.done;
+    retire_gathers(l);
+    return d;
+}
+
+// the pool's stream waits for every gather of source s that read ring-absolute positions below `limit`
+bn_status wait_readers(bn_live *l, Source &s, uint64_t limit, std::vector<uint64_t> &waited) {
+    while (!s.reads.empty() && gather_done(l, s.reads.front().second)) s.reads.pop_front();
+    for (const auto &rd : s.reads) {
+        if (rd.first >= limit) break;
+        if (std::find(waited.begin(), waited.end(), rd.second) != waited.end() || gather_done(l, rd.second)) continue;
+        LIVE_TRY(hipStreamWaitEvent(l->stream, l->gathers[rd.second - l->gathers.front().id].ev, 0));
+        waited.push_back(rd.second);
+    }
+    return BN_OK;
+}
+
+bn_status push_impl(bn_live *l, size_t n, const int32_t *sources, const void *const *pcm, const size_t *n_samples) {
+    if (!l) return invalid("null pool");
+    if (n && (!sources || !pcm || !n_samples)) return invalid("null argument");
+    // validate the whole call before anything changes
+    std::vector<std::pair<int32_t, uint64_t>> want;  // per source touched: samples asked for (l->touched maps a source to its entry)
+    struct Untouch {  // l->touched is all -1 again whenever this call returns
+        bn_live *l;
+        std::vector<std::pair<int32_t, uint64_t>> &want;
+        ~Untouch() {
+            for (const auto &w : want) l->touched[w.first] = -1;
+        }
+    } untouch{l, want};
+    uint64_t total = 0;
+    for (size_t i = 0; i < n; i++) {
+        const int32_t s = sources[i];
+        if (!source_ok(l, s)) return invalid("source " + std::to_string(s) + " out of range [0, " + std::to_string(l->n_sources) + ")");
+        if (n_samples[i] && !pcm[i]) return invalid("null PCM buffer for source " + std::to_string(s));
+        if (l->src[s].closed) return invalid("source " + std::to_string(s) + " is closed (reset it to start a new stream)");
+        if (l->touched[s] < 0) {
+            l->touched[s] = (int32_t)want.size();
+            want.emplace_back(s, n_samples[i]);
+        } else {
+            want[l->touched[s]].second += n_samples[i];
+        }
+        total += n_samples[i];
+    }
+    for (const auto &w : want)
+        if (w.second > room_of(l, l->src[w.first]))
+            return invalid("push of " + std::to_string(w.second) + " samples to source " + std::to_string(w.first) + " exceeds its room of " +
+                           std::to_string(room_of(l, l->src[w.first])) + " samples");
+    if (total == 0) return BN_OK;
+    if (total >= 0xffffffffull) return invalid("a push may stage at most 2^32 - 2 samples");
+    // tiles: every chunk split at ring wraps and every LIVE_TILE samples
+    std::vector<bn::LiveTile> tiles;
+    {
+        std::vector<uint64_t> at(want.size());  // ring-absolute write position per touched source
+        for (size_t j = 0; j < want.size(); j++) {
+            const Source &s = l->src[want[j].first];
+            at[j] = s.base + s.pushed;
+        }
+        uint32_t off = 0;
+        for (size_t i = 0; i < n; i++) {
+            const size_t j = (size_t)l->touched[sources[i]];
+            const uint64_t slot = (uint64_t)sources[i] * l->R;
+            size_t left = n_samples[i];
+            while (left) {
+                const uint64_t pos = at[j] % l->R;
+                const uint32_t len = (uint32_t)std::min<uint64_t>({left, l->R - pos, bn::LIVE_TILE});
+                tiles.push_back(bn::LiveTile{slot + pos, off, len});
+                at[j] += len;
+                off += len;
+                left -= len;
+            }
+        }
+    }
+    const size_t tiles_b = (tiles.size() * sizeof(bn::LiveTile) + 255) / 256 * 256;
+    const size_t bytes = tiles_b + total * l->esz;
+    LIVE_TRY(bn::use_device(l->device));
+    retire_gathers(l);
+    // a staging block is reused only after the scatter that read it completed
+    Stage &st = l->stage[l->next_stage];
+    if (st.used) LIVE_TRY(hipEventSynchronize(st.ev));
+    if (bytes > st.cap) {
+        const size_t cap = std::max(bytes, st.cap * 3 / 2);
+        if (st.h) (void)bn::gated::HostFree(st.h);
+        if (st.d) (void)bn::gated::Free(st.d);
+        st.h = st.d = nullptr;
+        st.cap = 0;
+        LIVE_TRY(bn::gated::HostMalloc(&st.h, cap, hipHostMallocDefault));
+        if (l->copy_mode) LIVE_TRY(bn::gated::Malloc(&st.d, cap));
+        st.cap = cap;
+    }
+    memcpy(st.h, tiles.data(), tiles.size() * sizeof(bn::LiveTile));
+    {
+        char *p = st.h + tiles_b;
+        for (size_t i = 0; i < n; i++) {
+            if (!n_samples[i]) continue;
+            memcpy(p, pcm[i], n_samples[i] * l->esz);
+            p += n_samples[i] * l->esz;
+        }
+    }
+    // the scatter waits for the gathers that read the ring space it overwrites: positions below (write end - R)
+    std::vector<uint64_t> waited;
+    for (const auto &w : want) {
+        Source &s = l->src[w.first];
+        const uint64_t end = s.base + s.pushed + w.second;
+        if (end > l->R) {
+            bn_status bs = wait_readers(l, s, end - l->R, waited);
+            if (bs != BN_OK) return bs;
+        }
+    }
+    (void)hipGetLastError();
+    const char *blk = st.h;
+    if (l->copy_mode) {
+        LIVE_TRY(hipMemcpyAsync(st.d, st.h, bytes, hipMemcpyHostToDevice, l->stream));
+        blk = st.d;
+    }
+    bn::launch_live_scatter(l->stream, l->slab, l->format == BN_PCM_I16, reinterpret_cast<const bn::LiveTile *>(blk), (uint32_t)tiles.size(),
+                            blk + tiles_b);
+    LIVE_TRY(hipGetLastError());
+    LIVE_TRY(hipEventRecord(st.ev, l->stream));
+    LIVE_TRY(hipEventRecord(l->scatter_ev, l->stream));
+    st.used = true;
+    l->scattered = true;
+    l->next_stage = (l->next_stage + 1) % N_STAGE;
+    // windows become ready in array order
+    for (size_t i = 0; i < n; i++) {
+        if (!n_samples[i]) continue;
+        l->src[sources[i]].pushed += n_samples[i];
+        make_ready(l, sources[i]);
+    }
+    return BN_OK;
+}
+
+void release(bn_live *l) {
+    if (!l) return;
+    (void)bn::use_device(l->device);
+    if (l->stream) (void)hipStreamSynchronize(l->stream);
+    for (auto &g : l->gathers) {
+        (void)hipEventSynchronize(g.ev);
+        (void)bn::gated::EventDestroy(g.ev);
+    }
+    for (auto e : l->free_events) (void)bn::gated::EventDestroy(e);
+    for (auto &st : l->stage) {
+        if (st.h) (void)bn::gated::HostFree(st.h);
+        if (st.d) (void)bn::gated::Free(st.d);
+        if (st.ev) (void)bn::gated::EventDestroy(st.ev);
+    }
+    if (l->scatter_ev) (void)bn::gated::EventDestroy(l->scatter_ev);
+    if (l->slab) (void)bn::gated::Free(l->slab);
+    if (l->d_window) (void)bn::gated::Free(l->d_window);
+    if (l->stream) (void)bn::gated::StreamDestroy(l->stream);
+    delete l;
+}
+
+}  // namespace
+
+extern "C" {
+
+bn_status bn_live_create(int32_t device, int32_t n_sources, int32_t format, size_t segment_samples, size_t step_samples, size_t ring_samples,
+                         bn_live **out) {
+    if (!out) return invalid("null argument");
+    *out = nullptr;
+    if (format != BN_PCM_I16 && format != BN_PCM_F32) return invalid("unknown PCM format " + std::to_string(format));
+    if (n_sources < 1) return invalid("n_sources must be at least 1");
+    if (segment_samples == 0 || segment_samples % 4 != 0) return invalid("segment_samples must be a positive multiple of 4");
+    if (step_samples < 1 || step_samples > segment_samples) return invalid("step_samples must be in 1..segment_samples");
+    if (ring_samples < segment_samples + step_samples) return invalid("ring_samples must be at least segment_samples + step_samples");
+    if (ring_samples >= (1ull << 31)) return invalid("ring_samples must be below 2^31");
+    if (bn_device_count() <= 0) return set_last_error(BN_ERR_NO_DEVICE, "no gfx950 device visible");
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) return set_last_error(BN_ERR_NO_DEVICE, "no such device");
+    LIVE_TRY(bn::use_device(device));
+    std::unique_ptr<bn_live, void (*)(bn_live *)> l(new bn_live, release);
+    l->device = device;
+    l->n_sources = n_sources;
+    l->format = format;
+    l->esz = format == BN_PCM_I16 ? sizeof(int16_t) : sizeof(float);
+    l->S = segment_samples;
+    l->step = step_samples;
+    l->R = ring_samples;
+    const char *mode = getenv("BN_LIVE_SCATTER");
+    l->copy_mode = mode && strcmp(mode, "copy") == 0;
+    l->src.resize((size_t)n_sources);
+    l->touched.assign((size_t)n_sources, -1);
+    const size_t slab_b = (size_t)n_sources * ring_samples * l->esz;
+    LIVE_TRY(bn::gated::StreamCreateWithFlags(&l->stream, hipStreamNonBlocking));
+    LIVE_TRY(bn::gated::EventCreateWithFlags(&l->scatter_ev, hipEventDisableTiming));
+    for (auto &st : l->stage) LIVE_TRY(bn::gated::EventCreateWithFlags(&st.ev, hipEventDisableTiming));
+    LIVE_TRY(bn::gated::Malloc(&l->slab, slab_b));
+    LIVE_TRY(bn::gated::Memset(l->slab, 0, slab_b));
+    LIVE_TRY(bn::gated::Malloc(&l->d_window, segment_samples * sizeof(float)));
+    *out = l.release();
+    return BN_OK;
+}
+
+void bn_live_free(bn_live *l) { release(l); }
+
+bn_status bn_live_push(bn_live *l, int32_t source, const void *pcm, size_t n_samples) {
+    return push_impl(l, 1, &source, &pcm, &n_samples);
+}
+
+bn_status bn_live_push_many(bn_live *l, size_t n, const int32_t *sources, const void *const *pcm, const size_t *n_samples) {
+    return push_impl(l, n, sources, pcm, n_samples);
+}
+
+bn_status bn_live_close(bn_live *l, int32_t source) {
+    if (!l) return invalid("null pool");
+    if (!source_ok(l, source)) return invalid("source " + std::to_string(source) + " out of range [0, " + std::to_string(l->n_sources) + ")");
+    Source &s = l->src[source];
+    if (s.closed) return invalid("source " + std::to_string(source) + " is already closed");
+    s.closed = true;
+    make_ready(l, source);
+    return BN_OK;
+}
+
+bn_status bn_live_reset(bn_live *l, int32_t source) {
+    if (!l) return invalid("null pool");
+    if (!source_ok(l, source)) return invalid("source " + std::to_string(source) + " out of range [0, " + std::to_string(l->n_sources) + ")");
+    Source &s = l->src[source];
+    std::deque<std::pair<int32_t, uint64_t>> keep;
+    for (const auto &q : l->queue)
+        if (q.first != source) keep.push_back(q);
+    l->queue.swap(keep);
+    s.base += s.pushed;  // in-flight gathers of the old stream stay ordered against the new stream's scatters (s.reads is kept)
+    s.pushed = s.n_ready = s.sched = 0;
+    s.closed = false;
+    return BN_OK;
+}
+
+size_t bn_live_ready(const bn_live *l, int32_t source) {
+    if (!l) return 0;
+    if (source < 0) return l->queue.size();
+    if (!source_ok(l, source)) return 0;
+    const Source &s = l->src[source];
+    return (size_t)(s.n_ready - s.sched);
+}
+
+size_t bn_live_event_count(const bn_live *l) { return l ? l->gathers.size() + l->free_events.size() : 0; }
+
+size_t bn_live_room(const bn_live *l, int32_t source) {
+    if (!source_ok(l, source)) return 0;
+    return room_of(l, l->src[source]);
+}
+
+bn_status bn_live_read_window(const bn_live *lc, int32_t source, uint64_t window, float *host_out) {
+    bn_live *l = const_cast<bn_live *>(lc);
+    if (!l || !host_out) return invalid("null argument");
+    if (!source_ok(l, source)) return invalid("source " + std::to_string(source) + " out of range [0, " + std::to_string(l->n_sources) + ")");
+    const Source &s = l->src[source];
+    if (window < s.sched || window >= s.n_ready)
+        return invalid("window " + std::to_string(window) + " of source " + std::to_string(source) + " is not ready and unscheduled (ready: [" +
+                       std::to_string(s.sched) + ", " + std::to_string(s.n_ready) + "))");
+    LIVE_TRY(bn::use_device(l->device));
+    bn::LiveGatherRows rows;
+    rows.r[0] = row_of(l, s, window);
+    rows.r[0].base = (uint64_t)source * l->R;
+    (void)hipGetLastError();
+    bn::launch_live_gather(l->stream, l->d_window, l->slab, l->format == BN_PCM_I16, (uint32_t)l->R, (uint32_t)l->S, rows, 1);
+    LIVE_TRY(hipGetLastError());
+    LIVE_TRY(hipStreamSynchronize(l->stream));
+    LIVE_TRY(bn::gated::Memcpy(host_out, l->d_window, l->S * sizeof(float), hipMemcpyDeviceToHost));
+    return BN_OK;
+}
+
+bn_status bn_step_live(bn_ctx *c, bn_live *l, size_t max_windows, size_t top_k, int32_t has_min, float min_conf, int32_t *source_out,
+                       uint64_t *window_out, size_t *n_out, int32_t sync) {
+    if (!c || !l || !n_out || !source_out || !window_out) return invalid("null argument");
+    *n_out = 0;
+    bn::CtxStepInput ci;
+    bn_status st = bn::ctx_step_input(c, top_k, &ci);
+    if (st != BN_OK) return st;
+    if (max_windows > ci.max_batch) return invalid("max_windows " + std::to_string(max_windows) + " exceeds context max " + std::to_string(ci.max_batch));
+    if (ci.device != l->device) return invalid("pool and context live on different devices");
+    if (ci.sample_count != l->S)
+        return invalid("the context's model takes " + std::to_string(ci.sample_count) + "-sample segments, the pool cuts " + std::to_string(l->S));
+    const size_t B = std::min(max_windows, l->queue.size());
+    if (B == 0) return BN_OK;
+    LIVE_TRY(bn::use_device(l->device));
+    retire_gathers(l);
+    // the gather's event first: once the gather is launched, its order against later scatters must not be lost
+    hipEvent_t ev = nullptr;
+    if (!l->free_events.empty()) {
+        ev = l->free_events.back();
+        l->free_events.pop_back();
+    } else {
+        LIVE_TRY(bn::gated::EventCreateWithFlags(&ev, hipEventDisableTiming));
+    }
+    const hipError_t we = l->scattered ? hipStreamWaitEvent(ci.stream, l->scatter_ev, 0) : hipSuccess;
+    if (we != hipSuccess) {
+        l->free_events.push_back(ev);
+        return set_last_error(BN_ERR_BACKEND, std::string("hipStreamWaitEvent failed: ") + hipGetErrorString(we));
+    }
+    // gather first, bookkeeping after: a launch failure leaves the pool unchanged
+    (void)hipGetLastError();
+    for (size_t r0 = 0; r0 < B; r0 += bn::LIVE_GATHER_ROWS) {
+        const size_t m = std::min<size_t>(bn::LIVE_GATHER_ROWS, B - r0);
+        bn::LiveGatherRows rows;
+        for (size_t i = 0; i < m; i++) {
+            const auto &q = l->queue[r0 + i];
+            rows.r[i] = row_of(l, l->src[q.first], q.second);
+            rows.r[i].base = (uint64_t)q.first * l->R;
+        }
+        bn::launch_live_gather(ci.stream, ci.d_input + r0 * l->S, l->slab, l->format == BN_PCM_I16, (uint32_t)l->R, (uint32_t)l->S, rows,
+                               (uint32_t)m);
+    }
+    const hipError_t le = hipGetLastError();
+    if (le != hipSuccess) {
+        l->free_events.push_back(ev);
+        return set_last_error(BN_ERR_BACKEND, std::string("live gather launch failed: ") + hipGetErrorString(le));
+    }
+    const hipError_t re = hipEventRecord(ev, ci.stream);
+    if (re != hipSuccess) {
+        (void)hipStreamSynchronize(ci.stream);  // the gather's order is lost: wait for it instead
+        l->free_events.push_back(ev);
+    } else {
+        const uint64_t id = l->next_gather++;
+        l->gathers.push_back(Gather{id, ev, false});
+        int32_t last = -1;
+        for (size_t i = 0; i < B; i++) {
+            const auto &q = l->queue[i];
+            Source &s = l->src[q.first];
+            // one read record per (source, gather): the first window of the source in this step has the lowest start
+            if (q.first != last && (s.reads.empty() || s.reads.back().second != id)) s.reads.emplace_back(s.base + q.second * l->step, id);
+            last = q.first;
+        }
+    }
+    for (size_t i = 0; i < B; i++) {
+        const auto &q = l->queue.front();
+        source_out[i] = q.first;
+        window_out[i] = q.second;
+        l->src[q.first].sched = q.second + 1;
+        l->queue.pop_front();
+    }
+    // the windows are taken from here on: on a failure of the step itself *n_out still names them (their results are lost)
+    *n_out = B;
+    return bn_step_device(c, ci.d_input, B, top_k, has_min, min_conf, sync);
+}
+
+}  // extern "C"

@@ -20,7 +20,7 @@ OUT = os.path.join(ROOT, "bindings", "rust", "src", "ffi.rs")
 
 SCALARS = {"int32_t": "i32", "uint32_t": "u32", "int64_t": "i64", "uint64_t": "u64", "size_t": "usize", "float": "f32", "double": "f64",
            "char": "c_char", "void": "c_void", "bn_status": "i32", "int": "i32"}
-OPAQUE = ["bn_model", "bn_ctx", "bn_recording", "bn_group", "bn_index"]
+OPAQUE = ["bn_model", "bn_ctx", "bn_recording", "bn_group", "bn_index", "bn_live"]
 RUST_KEYWORDS = {"type", "in", "ref", "box", "fn", "loop", "match", "move", "mod", "impl", "use", "where", "as"}
 
 
