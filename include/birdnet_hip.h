@@ -472,10 +472,42 @@ bn_status bn_index_search_ids(bn_index *x, const uint64_t *query_ids, size_t n_q
  *               push or close after close (until reset), max_windows > bn_ctx_max_batch, a context on another device or of
  *               another segment length, NULL where data is required.  Without a gfx950 device: BN_ERR_NO_DEVICE.
  *   Threading   one thread at a time per pool, like a context.
+ *
+ * Resampling pools (bn_live_create_rates): every source declares its own sample rate, and pushes are converted to dst_rate ON
+ * THE DEVICE as they arrive, in the scatter, by the polyphase FIR of bn_recording_create_resampled (same table, same fmaf
+ * chain; the last T - 1 source samples of every source are carried across pushes on the device).  Per source, every window is
+ * bit-identical to bn_step_windows over bn_recording_create_resampled(concatenation of its pushes, src_rate, dst_rate,
+ * zero_crossings).  segment / step / ring_samples are in output (dst_rate) samples, pushes and room in source samples.
+ *
+ *   Ring        f32 at dst_rate, whatever `format` the pushes have.
+ *   Finality    output n reads source samples up to (n*M)/L + T/2 (L/M = dst/src reduced, T taps per phase), so after p
+ *               pushed samples F(p) = ceil(max(0, p - T/2) * L / M) outputs are final (bn_live_resampled_samples); after
+ *               close ceil(p * L / M), the length bn_recording_create_resampled reports, the taps past the end reading 0.
+ *   Windows     a plain pool's with "pushed" replaced by the final outputs: window k is ready once k*step + S <= F(pushed);
+ *               at close every window with k*step < ceil(pushed * L / M) becomes ready, zero-padded.  A resampling source
+ *               is therefore T/2 source samples later than a plain one (0.5 ms at 48 -> 32 kHz).
+ *   Room        host accounting only, in source samples: needed_from = min(F(pushed), next_unscheduled_k * step), room =
+ *               floor((ring_samples + needed_from) * M / L) - pushed, the largest n for which ceil((pushed + n) * L / M) -
+ *               needed_from <= ring_samples.  The ring thus always keeps space for the tail a close flushes (at most
+ *               ceil(T/2 * L / M) + 1 outputs): a close is never refused for room.
+ *   Geometry    as above, and ring_samples >= S + step + ceil((T/2 + 1) * L / M) for every resampled source, so that a source
+ *               without room always has a ready window.  T <= 512 and L * T <= 2^22; a pair beyond that is refused at creation.
+ *   Reset       the new stream starts at sample 0 and sees zeros before it, not the old stream's history.
+ *   Same rate   a source with src_rate == dst_rate behaves as a plain pool's (i16 -> v / 32768 is exact in f32).
  */
 typedef struct bn_live bn_live;
 bn_status bn_live_create(int32_t device, int32_t n_sources, int32_t format, size_t segment_samples, size_t step_samples,
                          size_t ring_samples, bn_live **out);
+/* a resampling pool: source s delivers `format` PCM at src_rates[s] (> 0), the windows are cut at dst_rate (> 0);
+ * zero_crossings as bn_recording_create_resampled (0 => 16).  One table per distinct rate of the pool. */
+bn_status bn_live_create_rates(int32_t device, int32_t n_sources, int32_t format, size_t segment_samples, size_t step_samples,
+                               size_t ring_samples, uint32_t dst_rate, const uint32_t *src_rates, uint32_t zero_crossings,
+                               bn_live **out);
+/* F(pushed) above (closed != 0: ceil(pushed * L / M)); `pushed` itself for src_rate == dst_rate, 0 for a zero rate.  Needs no
+ * device. */
+size_t bn_live_resampled_samples(uint32_t src_rate, uint32_t dst_rate, uint32_t zero_crossings, uint64_t pushed, int32_t closed);
+/* the rate a source of a resampling pool was created with; 0 for a plain pool, a NULL pool or a source out of range */
+uint32_t bn_live_source_rate(const bn_live *l, int32_t source);
 void bn_live_free(bn_live *l);
 /* append samples to one source; the caller's buffer is not referenced after return */
 bn_status bn_live_push(bn_live *l, int32_t source, const void *pcm, size_t n_samples);
@@ -487,7 +519,7 @@ bn_status bn_live_close(bn_live *l, int32_t source);
 bn_status bn_live_reset(bn_live *l, int32_t source);
 /* ready, unscheduled windows of a source (source < 0: of all sources); 0 for a NULL pool or a source out of range */
 size_t bn_live_ready(const bn_live *l, int32_t source);
-/* samples a push to this source may add now */
+/* samples a push to this source may add now (source samples of that source in a resampling pool) */
 size_t bn_live_room(const bn_live *l, int32_t source);
 /* diagnostic: HIP events the pool holds to order scatters after gathers (those of gathers in flight plus recycled ones);
  * completed gathers are retired on every push and step, so this stays bounded by the steps in flight */

@@ -239,6 +239,11 @@ class LiveSources {
    public:
     /* format: BN_PCM_I16 or BN_PCM_F32; ring_samples 0 => 2 * segment + step; device < 0 => the classifier's (with_rocm) */
     LiveSources(const Classifier &cl, int32_t n_sources, int32_t format, float overlap_secs = 0.0f, size_t ring_samples = 0, int device = -1);
+    /* a resampling pool (bn_live_create_rates): source s delivers PCM at source_rates[s], converted on the device to the
+     * classifier's sample_rate as it arrives; n_sources = source_rates.size(), zero_crossings 0 => 16.  Windows, step and
+     * predict_live's start times stay in the classifier's rate; push and room count source samples. */
+    LiveSources(const Classifier &cl, const std::vector<uint32_t> &source_rates, int32_t format, float overlap_secs = 0.0f, size_t ring_samples = 0,
+                int device = -1, uint32_t zero_crossings = 0);
     void push(int32_t source, const void *pcm, size_t n_samples);
     void close(int32_t source);
     void reset(int32_t source);
@@ -248,6 +253,8 @@ class LiveSources {
     bn_live *raw() const { return live_.get(); }
 
    private:
+    void create(const Classifier &cl, int32_t n_sources, const uint32_t *source_rates, int32_t format, float overlap_secs, size_t ring_samples, int device,
+                uint32_t zero_crossings);
     std::shared_ptr<bn_live> live_;
     size_t step_ = 0;
 };
@@ -422,6 +429,9 @@ typedef struct bnh_live bnh_live;
 /* device < 0 => the classifier's device */
 int32_t bnh_live_create(const bnh_classifier *c, int32_t n_sources, int32_t format, float overlap_secs, size_t ring_samples, int32_t device,
                         bnh_live **out, bnh_error *err);
+/* the resampling pool: source_rates [n_sources] in Hz, converted to the classifier's sample rate on the device */
+int32_t bnh_live_create_rates(const bnh_classifier *c, int32_t n_sources, const uint32_t *source_rates, int32_t format, float overlap_secs,
+                              size_t ring_samples, int32_t device, uint32_t zero_crossings, bnh_live **out, bnh_error *err);
 void bnh_live_free(bnh_live *l);
 int32_t bnh_live_push(bnh_live *l, int32_t source, const void *pcm, size_t n_samples, bnh_error *err);
 int32_t bnh_live_close(bnh_live *l, int32_t source, bnh_error *err);

@@ -56,6 +56,7 @@ ENGINE_SYMBOLS = [
     "bn_index_search", "bn_index_search_ids",
     "bn_live_create", "bn_live_free", "bn_live_push", "bn_live_push_many", "bn_live_close", "bn_live_reset", "bn_live_ready",
     "bn_live_room", "bn_live_event_count", "bn_live_read_window", "bn_step_live",
+    "bn_live_create_rates", "bn_live_resampled_samples", "bn_live_source_rate",
 ]
 HOST_SYMBOLS = [
     "bnh_classifier_build", "bnh_classifier_free", "bnh_classifier_config", "bnh_classifier_provider",
@@ -67,7 +68,7 @@ HOST_SYMBOLS = [
     "bnh_result_embeddings", "bnh_results_free", "bnh_parse_labels", "bnh_parse_labels_format", "bnh_chunk_plan",
     "bnh_calculate_week", "bnh_validate_coordinates", "bnh_validate_date", "bnh_range_filter_build", "bnh_range_filter_free",
     "bnh_range_filter_predict", "bnh_range_filter_label", "bnh_filter_predictions",
-    "bnh_live_create", "bnh_live_free", "bnh_live_push", "bnh_live_close", "bnh_live_ready", "bnh_predict_live",
+    "bnh_live_create", "bnh_live_create_rates", "bnh_live_free", "bnh_live_push", "bnh_live_close", "bnh_live_ready", "bnh_predict_live",
 ]
 
 
@@ -182,6 +183,9 @@ def _load() -> C.CDLL:
         "bn_index_search": (i32, [vp, f32p, sz, sz, sz, C.POINTER(C.c_uint64), f32p, u32p]),
         "bn_index_search_ids": (i32, [vp, C.POINTER(C.c_uint64), sz, C.c_int64, sz, sz, C.POINTER(C.c_uint64), f32p, u32p]),
         "bn_live_create": (i32, [i32, i32, i32, sz, sz, sz, C.POINTER(vp)]),
+        "bn_live_create_rates": (i32, [i32, i32, i32, sz, sz, sz, C.c_uint32, u32p, C.c_uint32, C.POINTER(vp)]),
+        "bn_live_resampled_samples": (sz, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, i32]),
+        "bn_live_source_rate": (C.c_uint32, [vp, i32]),
         "bn_live_free": (None, [vp]),
         "bn_live_push": (i32, [vp, i32, vp, sz]),
         "bn_live_push_many": (i32, [vp, sz, C.POINTER(C.c_int32), C.POINTER(vp), C.POINTER(sz)]),
@@ -226,6 +230,7 @@ def _load() -> C.CDLL:
         "bnh_range_filter_label": (C.c_char_p, [vp, sz]),
         "bnh_filter_predictions": (sz, [C.POINTER(C.c_char_p), f32p, sz, C.POINTER(C.c_char_p), f32p, sz, C.c_float, i32, u32p, f32p]),
         "bnh_live_create": (i32, [vp, i32, i32, C.c_float, sz, i32, C.POINTER(vp), C.POINTER(BnhError)]),
+        "bnh_live_create_rates": (i32, [vp, i32, u32p, i32, C.c_float, sz, i32, C.c_uint32, C.POINTER(vp), C.POINTER(BnhError)]),
         "bnh_live_free": (None, [vp]),
         "bnh_live_push": (i32, [vp, i32, vp, sz, C.POINTER(BnhError)]),
         "bnh_live_close": (i32, [vp, i32, C.POINTER(BnhError)]),
@@ -560,12 +565,22 @@ class Classifier:
 
 class LiveSources:
     """birdnet::LiveSources: live pools through the host mirror (windows of the classifier's segment length, chunk_audio's step
-    for the given overlap; ring_samples 0 => 2 * segment + step; device < 0 => the classifier's)."""
+    for the given overlap; ring_samples 0 => 2 * segment + step; device < 0 => the classifier's).  source_rates (one rate in Hz
+    per source, len == n_sources) makes it a resampling pool: pushes arrive at those rates and are converted on the device to the
+    classifier's sample rate (bn_live_create_rates); start times stay in the classifier's rate."""
 
     def __init__(self, classifier: Classifier, n_sources: int, fmt: int = BN_PCM_I16, overlap_secs: float = 0.0, ring_samples: int = 0,
-                 device: int = -1):
+                 device: int = -1, source_rates=None, zero_crossings: int = 0):
         h, err = C.c_void_p(), BnhError()
-        if lib.bnh_live_create(classifier._h, n_sources, fmt, C.c_float(overlap_secs), ring_samples, device, C.byref(h), C.byref(err)):
+        if source_rates is None:
+            st = lib.bnh_live_create(classifier._h, n_sources, fmt, C.c_float(overlap_secs), ring_samples, device, C.byref(h), C.byref(err))
+        else:
+            rates = np.ascontiguousarray(source_rates, dtype=np.uint32).reshape(-1)
+            if rates.shape[0] != n_sources:
+                raise ValueError("source_rates needs one rate per source")
+            st = lib.bnh_live_create_rates(classifier._h, n_sources, rates.ctypes.data_as(C.POINTER(C.c_uint32)), fmt, C.c_float(overlap_secs),
+                                           ring_samples, device, zero_crossings, C.byref(h), C.byref(err))
+        if st:
             raise Error(err)
         self._h, self._dtype = h, (np.int16 if fmt == BN_PCM_I16 else np.float32)
 
@@ -1049,9 +1064,21 @@ class Live:
     """bn_live: a device-resident pool of per-source ring buffers for continuous audio.  Push int16 / float32 PCM as it arrives;
     Context.step_live batches the ready windows of all sources, cut on the device (chunk_audio per source)."""
 
-    def __init__(self, device: int, n_sources: int, segment_samples: int, step_samples: int, ring_samples: int, fmt: int = BN_PCM_I16):
+    def __init__(self, device: int, n_sources: int, segment_samples: int, step_samples: int, ring_samples: int, fmt: int = BN_PCM_I16,
+                 dst_rate: Optional[int] = None, src_rates=None, zero_crossings: int = 0):
+        """dst_rate and src_rates (one rate in Hz per source) given: a resampling pool (bn_live_create_rates) -- pushes arrive at
+        the sources' own rates and are converted to dst_rate on the device; segment / step / ring stay in dst_rate samples."""
         h = C.c_void_p()
-        st = lib.bn_live_create(device, n_sources, fmt, segment_samples, step_samples, ring_samples, C.byref(h))
+        if src_rates is None and dst_rate is None:
+            st = lib.bn_live_create(device, n_sources, fmt, segment_samples, step_samples, ring_samples, C.byref(h))
+        else:
+            if src_rates is None or dst_rate is None:
+                raise ValueError("a resampling pool needs both dst_rate and src_rates")
+            rates = np.ascontiguousarray(src_rates, dtype=np.uint32).reshape(-1)
+            if rates.shape[0] != n_sources:
+                raise ValueError("src_rates needs one rate per source")
+            st = lib.bn_live_create_rates(device, n_sources, fmt, segment_samples, step_samples, ring_samples, dst_rate,
+                                          rates.ctypes.data_as(C.POINTER(C.c_uint32)), zero_crossings, C.byref(h))
         if st:
             raise EngineError(st)
         self._h, self.device, self.n_sources, self.format = h, device, n_sources, fmt
@@ -1099,6 +1126,10 @@ class Live:
 
     def ready(self, source: int = -1) -> int:
         return int(lib.bn_live_ready(self._h, source))
+
+    def source_rate(self, source: int) -> int:
+        """bn_live_source_rate: the rate a source of a resampling pool was created with (0 for a plain pool)."""
+        return int(lib.bn_live_source_rate(self._h, source))
 
     def room(self, source: int) -> int:
         return int(lib.bn_live_room(self._h, source))
@@ -1229,6 +1260,12 @@ class RangeFilterBuilder:
         if st:
             raise Error(err)
         return RangeFilter(h, self._threshold)
+
+
+def live_resampled_samples(src_rate: int, dst_rate: int, pushed: int, closed: bool = False, zero_crossings: int = 0) -> int:
+    """bn_live_resampled_samples: outputs of a resampling live source that are final after `pushed` source samples (closed: all
+    of them, the length of the resampled recording) -- host arithmetic, needs no device."""
+    return int(lib.bn_live_resampled_samples(src_rate, dst_rate, zero_crossings, pushed, 1 if closed else 0))
 
 
 def resample_table(src_rate: int, dst_rate: int, zero_crossings: int = 0):

@@ -1501,11 +1501,9 @@ double bessel_i0(double x) {
     }
     return sum;
 }
-struct ResampleTable {
-    uint32_t L = 1, M = 1, T = 0;
-    std::vector<float> coef;  // [L][T]
-};
-ResampleTable make_resample_table(uint32_t src_rate, uint32_t dst_rate, uint32_t zc) {
+}  // namespace
+// shared with the live pool's streaming resampler (live.cpp): one table design, one implementation
+extern "C++" ResampleTable bn::resample_factors(uint32_t src_rate, uint32_t dst_rate, uint32_t zc) {
     ResampleTable t;
     if (zc == 0) zc = 16;
     uint32_t a = dst_rate, b = src_rate;
@@ -1515,7 +1513,16 @@ ResampleTable make_resample_table(uint32_t src_rate, uint32_t dst_rate, uint32_t
     const double ratio = (double)t.L / (double)t.M;
     const double fc = 0.5 * std::min(1.0, ratio);        // cutoff in cycles per SOURCE sample
     const double half = (double)zc / (2.0 * fc);          // support half-width in source samples
-    t.T = 2u * (uint32_t)std::ceil(half);                 // taps per phase (even)
+    const double taps = 2.0 * std::ceil(half);            // taps per phase (even)
+    t.T = taps < 4294967295.0 ? (uint32_t)taps : 0xffffffffu;
+    return t;
+}
+extern "C++" ResampleTable bn::make_resample_table(uint32_t src_rate, uint32_t dst_rate, uint32_t zc) {
+    ResampleTable t = resample_factors(src_rate, dst_rate, zc);
+    if (zc == 0) zc = 16;
+    const double ratio = (double)t.L / (double)t.M;
+    const double fc = 0.5 * std::min(1.0, ratio);
+    const double half = (double)zc / (2.0 * fc);
     const double beta = 8.6, i0b = bessel_i0(beta), pi = 3.14159265358979323846;
     t.coef.assign((size_t)t.L * t.T, 0.0f);
     for (uint32_t p = 0; p < t.L; p++) {
@@ -1536,7 +1543,6 @@ ResampleTable make_resample_table(uint32_t src_rate, uint32_t dst_rate, uint32_t
     }
     return t;
 }
-}  // namespace
 
 size_t bn_resample_table(uint32_t src_rate, uint32_t dst_rate, uint32_t zero_crossings, float *table, size_t cap, uint32_t *L_out, uint32_t *M_out,
                          uint32_t *T_out) {

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <string>
+#include <vector>
 
 #include "../../include/birdnet_hip.h"
 
@@ -29,4 +30,12 @@ struct CtxStepInput {
     size_t max_batch = 0;
 };
 bn_status ctx_step_input(const bn_ctx *c, size_t top_k, CtxStepInput *out);
+// the polyphase table of the resampler (design in include/birdnet_hip.h): L/M = dst/src reduced, T taps per phase; zc 0 => 16
+struct ResampleTable {
+    uint32_t L = 1, M = 1, T = 0;
+    std::vector<float> coef;  // [L][T]
+};
+// L, M and T alone (coef left empty): what the table would be, without building it
+ResampleTable resample_factors(uint32_t src_rate, uint32_t dst_rate, uint32_t zc);
+ResampleTable make_resample_table(uint32_t src_rate, uint32_t dst_rate, uint32_t zc);
 }  // namespace bn

@@ -205,6 +205,16 @@ int32_t bnh_live_create(const bnh_classifier *c, int32_t n_sources, int32_t form
     *out = nullptr;
     return guarded(err, [&] { *out = new bnh_live{LiveSources(c->cl, n_sources, format, overlap_secs, ring_samples, device)}; });
 }
+int32_t bnh_live_create_rates(const bnh_classifier *c, int32_t n_sources, const uint32_t *source_rates, int32_t format, float overlap_secs,
+                              size_t ring_samples, int32_t device, uint32_t zero_crossings, bnh_live **out, bnh_error *err) {
+    if (!out) return set_other(err, "null argument");
+    *out = nullptr;
+    if (!source_rates || n_sources < 1) return set_other(err, "a live pool needs at least one source rate");
+    return guarded(err, [&] {
+        *out = new bnh_live{LiveSources(c->cl, std::vector<uint32_t>(source_rates, source_rates + n_sources), format, overlap_secs, ring_samples, device,
+                                        zero_crossings)};
+    });
+}
 void bnh_live_free(bnh_live *l) { delete l; }
 int32_t bnh_live_push(bnh_live *l, int32_t source, const void *pcm, size_t n_samples, bnh_error *err) {
     return guarded(err, [&] { l->live.push(source, pcm, n_samples); });

@@ -303,6 +303,17 @@ std::vector<ChunkResult> Classifier::predict_recording(BatchInferenceContext &ct
 }
 
 LiveSources::LiveSources(const Classifier &cl, int32_t n_sources, int32_t format, float overlap_secs, size_t ring_samples, int device) {
+    create(cl, n_sources, nullptr, format, overlap_secs, ring_samples, device, 0);
+}
+
+LiveSources::LiveSources(const Classifier &cl, const std::vector<uint32_t> &source_rates, int32_t format, float overlap_secs, size_t ring_samples,
+                         int device, uint32_t zero_crossings) {
+    if (source_rates.empty()) throw inference("a live pool needs at least one source rate");
+    create(cl, (int32_t)source_rates.size(), source_rates.data(), format, overlap_secs, ring_samples, device, zero_crossings);
+}
+
+void LiveSources::create(const Classifier &cl, int32_t n_sources, const uint32_t *source_rates, int32_t format, float overlap_secs, size_t ring_samples,
+                         int device, uint32_t zero_crossings) {
     const ModelConfig &cfg = cl.config();
     // chunk_audio's step, as predict_recording computes it
     const size_t overlap_samples = (size_t)(overlap_secs * (float)cfg.sample_rate);
@@ -311,7 +322,10 @@ LiveSources::LiveSources(const Classifier &cl, int32_t n_sources, int32_t format
     if (ring_samples == 0) ring_samples = 2 * cfg.sample_count + step_;
     if (device < 0) device = bn_model_device(cl.inner_->model);
     bn_live *l = nullptr;
-    if (bn_live_create(device, n_sources, format, cfg.sample_count, step_, ring_samples, &l) != BN_OK)
+    const bn_status st = source_rates ? bn_live_create_rates(device, n_sources, format, cfg.sample_count, step_, ring_samples, cfg.sample_rate,
+                                                             source_rates, zero_crossings, &l)
+                                      : bn_live_create(device, n_sources, format, cfg.sample_count, step_, ring_samples, &l);
+    if (st != BN_OK)
         throw inference("failed to create the live pool: " + last_backend_error());
     live_ = std::shared_ptr<bn_live>(l, [](bn_live *p) { bn_live_free(p); });
 }

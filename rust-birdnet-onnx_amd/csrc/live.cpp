@@ -11,6 +11,12 @@
 // gather id) of the gathers not yet known complete, and a scatter that overwrites ring-absolute positions below p makes the
 // pool's stream wait for every such gather that started reading below p.  The per-row descriptors travel as kernel
 // arguments, so nothing a step writes on the host can race with an earlier step still in flight.
+//
+// Resampling pools (bn_live_create_rates).  The ring holds f32 at the model's rate; `pushed` counts the FINAL outputs written to
+// it, `in_pushed` the source samples received.  A push converts [F(in_pushed), F(in_pushed + n)) in its scatter
+// (live_resample_kernel), then a second launch on the pool's stream moves the source's last T - 1 samples into its device
+// history; a close converts the tail [F, ceil(in_pushed * L / M)) with zeros past the end.  Everything downstream of `pushed`
+// (readiness, rows, ordering, reset) is the plain pool's code.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -36,6 +42,9 @@ struct Source {
     uint64_t n_ready = 0;    // windows [0, n_ready) have become ready
     uint64_t sched = 0;      // windows [0, sched) have been scheduled
     bool closed = false;
+    uint64_t in_pushed = 0;  // resampling pools: source samples pushed since creation / the last reset
+    int32_t table = -1;      // resampling pools: the source's table in bn_live::tables (-1: at the model's rate)
+    uint32_t rate = 0;       // resampling pools: the source's sample rate
     std::deque<std::pair<uint64_t, uint64_t>> reads;  // (first ring-absolute start read, gather id), increasing
 };
 
@@ -75,6 +84,19 @@ struct bn_live {
     std::vector<int32_t> touched;  // push_impl: per source, its entry in the call's list of touched sources (-1: none)
     Stage stage[N_STAGE];
     int next_stage = 0;
+    // what pushes carry: the storage format of a plain pool, the sources' format of a resampling pool (whose ring is f32)
+    bool in_i16 = true;
+    size_t in_esz = 2;
+    // resampling pools
+    bool rates = false;
+    uint32_t dst_rate = 0;
+    std::vector<bn::LiveRsTable> tables;
+    std::vector<uint32_t> table_tile;  // outputs per tile, per table: the span of a tile fits the table's span_cap
+    bn::LiveRsTable *d_tables = nullptr;
+    float *d_coef = nullptr;
+    float *d_hist = nullptr;  // [n_sources][hist_cap]
+    size_t hist_cap = 0;
+    uint32_t lds_bytes = 0;
 };
 
 namespace {
@@ -91,8 +113,28 @@ bn_status invalid(const std::string &msg) { return set_last_error(BN_ERR_INVALID
 
 bool source_ok(const bn_live *l, int32_t s) { return l && s >= 0 && s < l->n_sources; }
 
+uint64_t ceil_muldiv(uint64_t a, uint32_t mul, uint32_t div) { return (uint64_t)(((unsigned __int128)a * mul + div - 1) / div); }
+
+// outputs of a resampled stream that are final after `pushed` source samples: output n reads sources up to (n*M)/L + T/2
+uint64_t final_outputs(uint32_t L, uint32_t M, uint32_t T, uint64_t pushed, bool closed) {
+    if (closed) return ceil_muldiv(pushed, L, M);
+    return pushed > T / 2 ? ceil_muldiv(pushed - T / 2, L, M) : 0;
+}
+
+uint64_t outputs_of(const bn_live *l, const Source &s, uint64_t in_pushed, bool closed) {
+    if (s.table < 0) return in_pushed;
+    const bn::LiveRsTable &t = l->tables[(size_t)s.table];
+    return final_outputs(t.L, t.M, t.T, in_pushed, closed);
+}
+
 size_t room_of(const bn_live *l, const Source &s) {
     const uint64_t needed_from = std::min<uint64_t>(s.pushed, s.sched * l->step);
+    if (l->rates && s.table >= 0) {
+        // the ring must hold every output up to the tail a close flushes: ceil((in_pushed + n) * L / M) <= R + needed_from
+        const bn::LiveRsTable &t = l->tables[(size_t)s.table];
+        const uint64_t lim = (uint64_t)(((unsigned __int128)(l->R + needed_from) * t.M) / t.L);
+        return lim > s.in_pushed ? (size_t)(lim - s.in_pushed) : 0;
+    }
     return l->R - (size_t)(s.pushed - needed_from);
 }
 
@@ -152,6 +194,109 @@ bn_status wait_readers(bn_live *l, Source &s, uint64_t limit, std::vector<uint64
     return BN_OK;
 }
 
+// the next pinned staging block, free to be written and at least `bytes` large
+bn_status acquire_stage(bn_live *l, size_t bytes, Stage **out) {
+    Stage &st = l->stage[l->next_stage];
+    if (st.used) LIVE_TRY(hipEventSynchronize(st.ev));
+    if (bytes > st.cap) {
+        const size_t cap = std::max(bytes, st.cap * 3 / 2);
+        if (st.h) (void)bn::gated::HostFree(st.h);
+        if (st.d) (void)bn::gated::Free(st.d);
+        st.h = st.d = nullptr;
+        st.cap = 0;
+        LIVE_TRY(bn::gated::HostMalloc(&st.h, cap, hipHostMallocDefault));
+        if (l->copy_mode) LIVE_TRY(bn::gated::Malloc(&st.d, cap));
+        st.cap = cap;
+    }
+    *out = &st;
+    return BN_OK;
+}
+
+size_t pad256(size_t b) { return (b + 255) / 256 * 256; }
+
+// The scatter of a resampling pool.  want: per touched source the source samples this call adds (0 with closing: the tail).
+// Staging block: [jobs][tiles][data], the data grouped by source so that a job's new samples are contiguous.  On success the
+// sources' rings hold their outputs up to outputs_of(in_pushed + added, closing); the caller does the bookkeeping.
+bn_status scatter_rates(bn_live *l, const std::vector<std::pair<int32_t, uint64_t>> &want, size_t n, const int32_t *sources, const void *const *pcm,
+                        const size_t *n_samples, bool closing) {
+    std::vector<bn::LiveRsJob> jobs(want.size());
+    std::vector<bn::LiveRsTile> tiles;
+    std::vector<uint64_t> out_end(want.size());
+    uint64_t total = 0;
+    for (size_t j = 0; j < want.size(); j++) {
+        const int32_t si = want[j].first;
+        const Source &s = l->src[si];
+        bn::LiveRsJob &jb = jobs[j];
+        jb.p0 = s.in_pushed;
+        jb.hist = (uint64_t)si * l->hist_cap;
+        jb.src = (uint32_t)total;
+        jb.n_in = (uint32_t)want[j].second;
+        jb.table = s.table < 0 ? bn::LIVE_RS_PASS : (uint32_t)s.table;
+        jb.pad = 0;
+        total += want[j].second;
+        const uint64_t out1 = outputs_of(l, s, s.in_pushed + want[j].second, closing);
+        out_end[j] = out1;
+        const uint32_t tile = s.table < 0 ? bn::LIVE_TILE : l->table_tile[(size_t)s.table];
+        const uint64_t slot = (uint64_t)si * l->R;
+        for (uint64_t o = s.pushed; o < out1;) {
+            const uint64_t pos = (s.base + o) % l->R;
+            const uint32_t len = (uint32_t)std::min<uint64_t>({out1 - o, l->R - pos, tile});
+            tiles.push_back(bn::LiveRsTile{slot + pos, o, len, (uint32_t)j});
+            o += len;
+        }
+    }
+    LIVE_TRY(bn::use_device(l->device));
+    retire_gathers(l);
+    if (tiles.empty() && total == 0) return BN_OK;
+    const size_t jobs_b = pad256(jobs.size() * sizeof(bn::LiveRsJob));
+    const size_t tiles_b = pad256(tiles.size() * sizeof(bn::LiveRsTile));
+    const size_t bytes = jobs_b + tiles_b + total * l->in_esz;
+    Stage *stp = nullptr;
+    bn_status bs = acquire_stage(l, bytes, &stp);
+    if (bs != BN_OK) return bs;
+    Stage &st = *stp;
+    memcpy(st.h, jobs.data(), jobs.size() * sizeof(bn::LiveRsJob));
+    memcpy(st.h + jobs_b, tiles.data(), tiles.size() * sizeof(bn::LiveRsTile));
+    {
+        std::vector<size_t> cursor(want.size());
+        for (size_t j = 0; j < want.size(); j++) cursor[j] = (size_t)jobs[j].src;
+        char *data = st.h + jobs_b + tiles_b;
+        for (size_t i = 0; i < n; i++) {
+            if (!n_samples[i]) continue;
+            size_t &c = cursor[(size_t)l->touched[sources[i]]];
+            memcpy(data + c * l->in_esz, pcm[i], n_samples[i] * l->in_esz);
+            c += n_samples[i];
+        }
+    }
+    // the scatter waits for the gathers that read the ring space it overwrites: positions below (write end - R)
+    std::vector<uint64_t> waited;
+    for (size_t j = 0; j < want.size(); j++) {
+        Source &s = l->src[want[j].first];
+        const uint64_t end = s.base + out_end[j];
+        if (out_end[j] > s.pushed && end > l->R) {
+            bs = wait_readers(l, s, end - l->R, waited);
+            if (bs != BN_OK) return bs;
+        }
+    }
+    (void)hipGetLastError();
+    const char *blk = st.h;
+    if (l->copy_mode) {
+        LIVE_TRY(hipMemcpyAsync(st.d, st.h, bytes, hipMemcpyHostToDevice, l->stream));
+        blk = st.d;
+    }
+    const bn::LiveRsJob *d_jobs = reinterpret_cast<const bn::LiveRsJob *>(blk);
+    bn::launch_live_resample(l->stream, static_cast<float *>(l->slab), l->in_i16, l->d_tables, l->d_coef, l->d_hist, d_jobs,
+                             reinterpret_cast<const bn::LiveRsTile *>(blk + jobs_b), (uint32_t)tiles.size(), blk + jobs_b + tiles_b, l->lds_bytes);
+    if (!closing) bn::launch_live_history(l->stream, l->d_hist, l->in_i16, l->d_tables, d_jobs, (uint32_t)jobs.size(), blk + jobs_b + tiles_b);
+    LIVE_TRY(hipGetLastError());
+    LIVE_TRY(hipEventRecord(st.ev, l->stream));
+    LIVE_TRY(hipEventRecord(l->scatter_ev, l->stream));
+    st.used = true;
+    l->scattered = true;
+    l->next_stage = (l->next_stage + 1) % N_STAGE;
+    return BN_OK;
+}
+
 bn_status push_impl(bn_live *l, size_t n, const int32_t *sources, const void *const *pcm, const size_t *n_samples) {
     if (!l) return invalid("null pool");
     if (n && (!sources || !pcm || !n_samples)) return invalid("null argument");
@@ -184,6 +329,19 @@ bn_status push_impl(bn_live *l, size_t n, const int32_t *sources, const void *co
                            std::to_string(room_of(l, l->src[w.first])) + " samples");
     if (total == 0) return BN_OK;
     if (total >= 0xffffffffull) return invalid("a push may stage at most 2^32 - 2 samples");
+    if (l->rates) {
+        bn_status bs = scatter_rates(l, want, n, sources, pcm, n_samples, false);
+        if (bs != BN_OK) return bs;
+        // windows become ready in array order
+        for (size_t i = 0; i < n; i++) {
+            if (!n_samples[i]) continue;
+            Source &s = l->src[sources[i]];
+            s.in_pushed += n_samples[i];
+            s.pushed = outputs_of(l, s, s.in_pushed, false);
+            make_ready(l, sources[i]);
+        }
+        return BN_OK;
+    }
     // tiles: every chunk split at ring wraps and every LIVE_TILE samples
     std::vector<bn::LiveTile> tiles;
     {
@@ -212,18 +370,12 @@ bn_status push_impl(bn_live *l, size_t n, const int32_t *sources, const void *co
     LIVE_TRY(bn::use_device(l->device));
     retire_gathers(l);
     // a staging block is reused only after the scatter that read it completed
-    Stage &st = l->stage[l->next_stage];
-    if (st.used) LIVE_TRY(hipEventSynchronize(st.ev));
-    if (bytes > st.cap) {
-        const size_t cap = std::max(bytes, st.cap * 3 / 2);
-        if (st.h) (void)bn::gated::HostFree(st.h);
-        if (st.d) (void)bn::gated::Free(st.d);
-        st.h = st.d = nullptr;
-        st.cap = 0;
-        LIVE_TRY(bn::gated::HostMalloc(&st.h, cap, hipHostMallocDefault));
-        if (l->copy_mode) LIVE_TRY(bn::gated::Malloc(&st.d, cap));
-        st.cap = cap;
+    Stage *stp = nullptr;
+    {
+        bn_status bs = acquire_stage(l, bytes, &stp);
+        if (bs != BN_OK) return bs;
     }
+    Stage &st = *stp;
     memcpy(st.h, tiles.data(), tiles.size() * sizeof(bn::LiveTile));
     {
         char *p = st.h + tiles_b;
@@ -282,17 +434,76 @@ void release(bn_live *l) {
     }
     if (l->scatter_ev) (void)bn::gated::EventDestroy(l->scatter_ev);
     if (l->slab) (void)bn::gated::Free(l->slab);
+    if (l->d_tables) (void)bn::gated::Free(l->d_tables);
+    if (l->d_coef) (void)bn::gated::Free(l->d_coef);
+    if (l->d_hist) (void)bn::gated::Free(l->d_hist);
     if (l->d_window) (void)bn::gated::Free(l->d_window);
     if (l->stream) (void)bn::gated::StreamDestroy(l->stream);
     delete l;
 }
 
-}  // namespace
+// the tables of a resampling pool, one per distinct source rate, the tile size of each, and the device buffers
+bn_status setup_rates(bn_live *l, uint32_t dst_rate, const uint32_t *src_rates, uint32_t zero_crossings) {
+    std::vector<float> coef;
+    std::vector<uint32_t> table_rate;
+    uint32_t lds_floats = 1;
+    size_t max_T = 2;
+    for (int32_t si = 0; si < l->n_sources; si++) {
+        Source &s = l->src[(size_t)si];
+        s.rate = src_rates[si];
+        if (s.rate == dst_rate) continue;
+        const auto known = std::find(table_rate.begin(), table_rate.end(), s.rate);
+        if (known != table_rate.end()) {
+            s.table = (int32_t)(known - table_rate.begin());
+            continue;
+        }
+        const std::string who = "source " + std::to_string(si) + " (" + std::to_string(s.rate) + " -> " + std::to_string(dst_rate) + " Hz)";
+        // refuse before the table is built: L * T may be huge for rates without a large common divisor
+        const bn::ResampleTable f = bn::resample_factors(s.rate, dst_rate, zero_crossings);
+        if (f.T > bn::LIVE_RS_MAX_T || (uint64_t)f.L * f.T > (1ull << 22) || (uint64_t)bn::LIVE_TILE * f.M + f.L >= (1ull << 32))
+            return invalid(who + ": the polyphase table (L = " + std::to_string(f.L) + ", M = " + std::to_string(f.M) + ", T = " + std::to_string(f.T) +
+                           ") exceeds what a live pool accepts (T <= " + std::to_string(bn::LIVE_RS_MAX_T) + ", L * T <= 2^22, M < 2^20)");
+        const bn::ResampleTable rt = bn::make_resample_table(s.rate, dst_rate, zero_crossings);
+        bn::LiveRsTable t;
+        t.L = rt.L;
+        t.M = rt.M;
+        t.T = rt.T;
+        t.coef_off = (uint32_t)coef.size();
+        // span of a tile of n outputs, whatever its phase: ((n - 1) * M + L - 1) / L + T floats
+        auto span_of = [&](uint64_t n_out) { return (uint32_t)(((n_out - 1) * t.M + t.L - 1) / t.L + t.T); };
+        const uint32_t table_floats = t.L * t.T;
+        t.lds_table = table_floats < bn::LIVE_RS_LDS_FLOATS && span_of(1024) <= bn::LIVE_RS_LDS_FLOATS - table_floats;
+        const uint32_t avail = bn::LIVE_RS_LDS_FLOATS - (t.lds_table ? table_floats : 0);
+        uint32_t tile = bn::LIVE_TILE;
+        while (tile > 1 && span_of(tile) > avail) tile = std::min<uint32_t>(tile - 1, (uint32_t)((uint64_t)(avail - t.T) * t.L / t.M + 1));
+        t.span_cap = span_of(tile);
+        lds_floats = std::max(lds_floats, t.span_cap + (t.lds_table ? table_floats : 0));
+        max_T = std::max<size_t>(max_T, t.T);
+        coef.insert(coef.end(), rt.coef.begin(), rt.coef.end());
+        s.table = (int32_t)l->tables.size();
+        l->tables.push_back(t);
+        l->table_tile.push_back(tile);
+        table_rate.push_back(s.rate);
+    }
+    l->rates = true;
+    l->dst_rate = dst_rate;
+    l->lds_bytes = lds_floats * (uint32_t)sizeof(float);
+    l->hist_cap = max_T - 1;
+    const size_t hist_b = (size_t)l->n_sources * l->hist_cap * sizeof(float);
+    LIVE_TRY(bn::gated::Malloc(reinterpret_cast<void **>(&l->d_hist), hist_b));
+    LIVE_TRY(bn::gated::Memset(l->d_hist, 0, hist_b));
+    if (!l->tables.empty()) {
+        LIVE_TRY(bn::gated::Malloc(reinterpret_cast<void **>(&l->d_tables), l->tables.size() * sizeof(bn::LiveRsTable)));
+        LIVE_TRY(bn::gated::Memcpy(l->d_tables, l->tables.data(), l->tables.size() * sizeof(bn::LiveRsTable), hipMemcpyHostToDevice));
+        LIVE_TRY(bn::gated::Malloc(reinterpret_cast<void **>(&l->d_coef), coef.size() * sizeof(float)));
+        LIVE_TRY(bn::gated::Memcpy(l->d_coef, coef.data(), coef.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    return BN_OK;
+}
 
-extern "C" {
-
-bn_status bn_live_create(int32_t device, int32_t n_sources, int32_t format, size_t segment_samples, size_t step_samples, size_t ring_samples,
-                         bn_live **out) {
+// bn_live_create (src_rates == nullptr) and bn_live_create_rates
+bn_status create_pool(int32_t device, int32_t n_sources, int32_t format, size_t segment_samples, size_t step_samples, size_t ring_samples,
+                      uint32_t dst_rate, const uint32_t *src_rates, uint32_t zero_crossings, bn_live **out) {
     if (!out) return invalid("null argument");
     *out = nullptr;
     if (format != BN_PCM_I16 && format != BN_PCM_F32) return invalid("unknown PCM format " + std::to_string(format));
@@ -301,6 +512,11 @@ bn_status bn_live_create(int32_t device, int32_t n_sources, int32_t format, size
     if (step_samples < 1 || step_samples > segment_samples) return invalid("step_samples must be in 1..segment_samples");
     if (ring_samples < segment_samples + step_samples) return invalid("ring_samples must be at least segment_samples + step_samples");
     if (ring_samples >= (1ull << 31)) return invalid("ring_samples must be below 2^31");
+    if (src_rates) {
+        if (dst_rate == 0) return invalid("dst_rate must be positive");
+        for (int32_t s = 0; s < n_sources; s++)
+            if (src_rates[s] == 0) return invalid("source " + std::to_string(s) + ": sample rates must be positive");
+    }
     if (bn_device_count() <= 0) return set_last_error(BN_ERR_NO_DEVICE, "no gfx950 device visible");
     int n_dev = 0;
     if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) return set_last_error(BN_ERR_NO_DEVICE, "no such device");
@@ -310,6 +526,8 @@ bn_status bn_live_create(int32_t device, int32_t n_sources, int32_t format, size
     l->n_sources = n_sources;
     l->format = format;
     l->esz = format == BN_PCM_I16 ? sizeof(int16_t) : sizeof(float);
+    l->in_i16 = format == BN_PCM_I16;
+    l->in_esz = l->esz;
     l->S = segment_samples;
     l->step = step_samples;
     l->R = ring_samples;
@@ -317,6 +535,22 @@ bn_status bn_live_create(int32_t device, int32_t n_sources, int32_t format, size
     l->copy_mode = mode && strcmp(mode, "copy") == 0;
     l->src.resize((size_t)n_sources);
     l->touched.assign((size_t)n_sources, -1);
+    if (src_rates) {
+        // the ring of a resampling pool holds f32 at the model's rate, whatever the sources deliver
+        l->format = BN_PCM_F32;
+        l->esz = sizeof(float);
+        bn_status st = setup_rates(l.get(), dst_rate, src_rates, zero_crossings);
+        if (st != BN_OK) return st;
+        // a full ring must still hold a ready window: the outputs not yet final plus one source sample's worth stay below
+        // ceil((T/2 + 1) * L / M)
+        for (size_t i = 0; i < l->tables.size(); i++) {
+            const bn::LiveRsTable &t = l->tables[i];
+            const uint64_t tail = ceil_muldiv(t.T / 2 + 1, t.L, t.M);
+            if (ring_samples < segment_samples + step_samples + tail)
+                return invalid("ring_samples must be at least segment_samples + step_samples + " + std::to_string(tail) + " for a source resampled by " +
+                               std::to_string(t.L) + "/" + std::to_string(t.M));
+        }
+    }
     const size_t slab_b = (size_t)n_sources * ring_samples * l->esz;
     LIVE_TRY(bn::gated::StreamCreateWithFlags(&l->stream, hipStreamNonBlocking));
     LIVE_TRY(bn::gated::EventCreateWithFlags(&l->scatter_ev, hipEventDisableTiming));
@@ -326,6 +560,36 @@ bn_status bn_live_create(int32_t device, int32_t n_sources, int32_t format, size
     LIVE_TRY(bn::gated::Malloc(&l->d_window, segment_samples * sizeof(float)));
     *out = l.release();
     return BN_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+bn_status bn_live_create(int32_t device, int32_t n_sources, int32_t format, size_t segment_samples, size_t step_samples, size_t ring_samples,
+                         bn_live **out) {
+    return create_pool(device, n_sources, format, segment_samples, step_samples, ring_samples, 0, nullptr, 0, out);
+}
+
+bn_status bn_live_create_rates(int32_t device, int32_t n_sources, int32_t format, size_t segment_samples, size_t step_samples, size_t ring_samples,
+                               uint32_t dst_rate, const uint32_t *src_rates, uint32_t zero_crossings, bn_live **out) {
+    if (!src_rates) {
+        if (out) *out = nullptr;
+        return invalid("null argument");
+    }
+    return create_pool(device, n_sources, format, segment_samples, step_samples, ring_samples, dst_rate, src_rates, zero_crossings, out);
+}
+
+size_t bn_live_resampled_samples(uint32_t src_rate, uint32_t dst_rate, uint32_t zero_crossings, uint64_t pushed, int32_t closed) {
+    if (src_rate == 0 || dst_rate == 0) return 0;
+    if (src_rate == dst_rate) return (size_t)pushed;
+    const bn::ResampleTable f = bn::resample_factors(src_rate, dst_rate, zero_crossings);
+    return (size_t)final_outputs(f.L, f.M, f.T, pushed, closed != 0);
+}
+
+uint32_t bn_live_source_rate(const bn_live *l, int32_t source) {
+    if (!source_ok(l, source) || !l->rates) return 0;
+    return l->src[source].rate;
 }
 
 void bn_live_free(bn_live *l) { release(l); }
@@ -343,6 +607,13 @@ bn_status bn_live_close(bn_live *l, int32_t source) {
     if (!source_ok(l, source)) return invalid("source " + std::to_string(source) + " out of range [0, " + std::to_string(l->n_sources) + ")");
     Source &s = l->src[source];
     if (s.closed) return invalid("source " + std::to_string(source) + " is already closed");
+    if (l->rates && s.table >= 0) {
+        // the tail: outputs whose taps reach past the end, computed with zeros there (room always keeps space for them)
+        std::vector<std::pair<int32_t, uint64_t>> want{{source, 0}};
+        bn_status bs = scatter_rates(l, want, 0, nullptr, nullptr, nullptr, true);
+        if (bs != BN_OK) return bs;
+        s.pushed = outputs_of(l, s, s.in_pushed, true);
+    }
     s.closed = true;
     make_ready(l, source);
     return BN_OK;
@@ -358,6 +629,7 @@ bn_status bn_live_reset(bn_live *l, int32_t source) {
     l->queue.swap(keep);
     s.base += s.pushed;  // in-flight gathers of the old stream stay ordered against the new stream's scatters (s.reads is kept)
     s.pushed = s.n_ready = s.sched = 0;
+    s.in_pushed = 0;  // the new stream sees zeros before its sample 0: the kernel never reads history below stream sample 0
     s.closed = false;
     return BN_OK;
 }

@@ -6,6 +6,17 @@
 //     0 (the zero-padded tail after close), i16 converts as v / 32768 exactly like windows_kernel.  grid (ceil(S/1024), rows)
 //   * live_scatter_kernel -- one workgroup per tile of a push's staged chunks; the host splits chunks at ring wraps and every
 //     LIVE_TILE samples, so a tile is one contiguous copy and lanes move consecutive samples.
+//   * live_resample_kernel -- the scatter of a resampling pool (bn_live_create_rates): one workgroup per tile of consecutive
+//     FINAL outputs of one source.  The source span the tile's taps touch, [(n0*M)/L - (T/2-1), (n1*M)/L + T/2], is read
+//     ONCE into LDS as f32 -- from the source's history (the last T-1 samples before this push) and the staged chunk, 0
+//     before sample 0 of the stream and past the staged end (the tail a close flushes) -- and the phase table too when it fits
+//     behind the span.  One lane = one output: kernels.hip's resample_kernel chain, fmaf(table[phase][j], x, acc) for
+//     j = 0..T-1 in that order, so the ring holds the bits bn_recording_create_resampled computes.  LDS reads: lanes of a wave
+//     read span[(o*M + r0)/L + j], a stride of M/L between lanes -- upsampling repeats addresses (broadcast), integer M/L odd
+//     is conflict-free, 3/2 puts 48 addresses on ds_read_b32's 32 banks (2-way on a third of them); table rows of one wave
+//     are at most L distinct addresses.  A tile of a source at the model's rate is a converting copy.
+//   * live_history_kernel -- one workgroup per job: the last T-1 source samples of the stream after the push, from the old
+//     history (shifted) and the staged chunk, read into registers before any is written.
 #include "live.h"
 
 namespace bn {
@@ -42,6 +53,94 @@ __global__ __launch_bounds__(256) void live_scatter_kernel(T *__restrict__ slab,
     for (uint32_t i = threadIdx.x; i < t.len; i += 256u) dst[i] = src[i];
 }
 
+template <class T>
+__device__ __forceinline__ float live_to_f32(T v) {
+    if constexpr (sizeof(T) == 2) return (float)v * (1.0f / 32768.0f);
+    else return (float)v;
+}
+
+template <class T_>
+__global__ __launch_bounds__(256) void live_resample_kernel(float *__restrict__ slab, const LiveRsTable *__restrict__ tables,
+                                                            const float *__restrict__ coef, const float *__restrict__ hist,
+                                                            const LiveRsJob *__restrict__ jobs, const LiveRsTile *__restrict__ tiles,
+                                                            const T_ *__restrict__ data) {
+    extern __shared__ float lds[];
+    const LiveRsTile t = tiles[blockIdx.x];
+    const LiveRsJob jb = jobs[t.job];
+    float *dst = slab + t.dst;
+    const T_ *staged = data + jb.src;
+    if (jb.table == LIVE_RS_PASS) {
+        const uint32_t first = (uint32_t)(t.n0 - jb.p0);
+        for (uint32_t i = threadIdx.x; i < t.len; i += 256u) dst[i] = live_to_f32(staged[first + i]);
+        return;
+    }
+    const LiveRsTable tb = tables[jb.table];
+    const uint32_t L = tb.L, M = tb.M, T = tb.T;
+    const uint64_t pos0 = t.n0 * M;
+    const uint64_t base0 = pos0 / L;
+    const uint32_t r0 = (uint32_t)(pos0 - base0 * L);
+    // span index i holds stream sample q_lo + i; output o's first tap is span index (o*M + r0) / L
+    const int64_t q_lo = (int64_t)base0 - (int64_t)(T / 2 - 1);
+    const uint32_t span_len = ((t.len - 1u) * M + r0) / L + T;
+    if (span_len > tb.span_cap) return;  // the host sizes tiles so that this never happens
+    const int64_t p0 = (int64_t)jb.p0;
+    const int64_t h0 = p0 - (int64_t)(T - 1);  // stream sample in history slot 0
+    const float *hs = hist + jb.hist;
+    for (uint32_t i = threadIdx.x; i < span_len; i += 256u) {
+        const int64_t q = q_lo + i;
+        float v = 0.0f;
+        if (q >= p0) {
+            if (q - p0 < (int64_t)jb.n_in) v = live_to_f32(staged[q - p0]);
+        } else if (q >= 0 && q >= h0) {
+            v = hs[q - h0];
+        }
+        lds[i] = v;
+    }
+    const float *tab = coef + tb.coef_off;
+    if (tb.lds_table) {
+        float *lt = lds + tb.span_cap;
+        for (uint32_t i = threadIdx.x; i < L * T; i += 256u) lt[i] = tab[i];
+        tab = lt;
+    }
+    __syncthreads();
+    for (uint32_t o = threadIdx.x; o < t.len; o += 256u) {
+        const uint32_t pos = o * M + r0;
+        const uint32_t b = pos / L;
+        const float *row = tab + (pos - b * L) * T;
+        const float *x = lds + b;
+        float acc = 0.0f;
+        for (uint32_t j = 0; j < T; j++) acc = fmaf(row[j], x[j], acc);
+        dst[o] = acc;
+    }
+}
+
+template <class T_>
+__global__ __launch_bounds__(256) void live_history_kernel(float *__restrict__ hist, const LiveRsTable *__restrict__ tables,
+                                                           const LiveRsJob *__restrict__ jobs, const T_ *__restrict__ data) {
+    const LiveRsJob jb = jobs[blockIdx.x];
+    if (jb.table == LIVE_RS_PASS || jb.n_in == 0) return;
+    const uint32_t H = tables[jb.table].T - 1u;  // <= LIVE_RS_MAX_T - 1 = 2 * 256 - 1
+    float *hs = hist + jb.hist;
+    const T_ *staged = data + jb.src;
+    // slot h of the new history holds stream sample p0 + n_in - H + h: staged sample n_in - H + h, or old slot h + n_in
+    float v[2];
+#pragma unroll
+    for (int u = 0; u < 2; u++) {
+        const uint32_t h = threadIdx.x + 256u * u;
+        v[u] = 0.0f;
+        if (h < H) {
+            const int64_t k = (int64_t)jb.n_in - (int64_t)H + (int64_t)h;
+            v[u] = k >= 0 ? live_to_f32(staged[k]) : hs[h + jb.n_in];
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < 2; u++) {
+        const uint32_t h = threadIdx.x + 256u * u;
+        if (h < H) hs[h] = v[u];
+    }
+}
+
 }  // namespace
 
 void launch_live_gather(hipStream_t s, float *dst, const void *slab, int32_t is_i16, uint32_t ring_samples, uint32_t S, const LiveGatherRows &rows,
@@ -57,6 +156,24 @@ void launch_live_scatter(hipStream_t s, void *slab, int32_t is_i16, const LiveTi
     if (is_i16)
         hipLaunchKernelGGL(live_scatter_kernel<int16_t>, dim3(n_tiles), dim3(256), 0, s, static_cast<int16_t *>(slab), tiles, static_cast<const int16_t *>(data));
     else hipLaunchKernelGGL(live_scatter_kernel<float>, dim3(n_tiles), dim3(256), 0, s, static_cast<float *>(slab), tiles, static_cast<const float *>(data));
+}
+
+void launch_live_resample(hipStream_t s, float *slab, int32_t in_i16, const LiveRsTable *tables, const float *coef, const float *hist,
+                          const LiveRsJob *jobs, const LiveRsTile *tiles, uint32_t n_tiles, const void *data, uint32_t lds_bytes) {
+    if (n_tiles == 0) return;
+    if (in_i16)
+        hipLaunchKernelGGL(live_resample_kernel<int16_t>, dim3(n_tiles), dim3(256), lds_bytes, s, slab, tables, coef, hist, jobs, tiles,
+                           static_cast<const int16_t *>(data));
+    else
+        hipLaunchKernelGGL(live_resample_kernel<float>, dim3(n_tiles), dim3(256), lds_bytes, s, slab, tables, coef, hist, jobs, tiles,
+                           static_cast<const float *>(data));
+}
+
+void launch_live_history(hipStream_t s, float *hist, int32_t in_i16, const LiveRsTable *tables, const LiveRsJob *jobs, uint32_t n_jobs,
+                         const void *data) {
+    if (n_jobs == 0) return;
+    if (in_i16) hipLaunchKernelGGL(live_history_kernel<int16_t>, dim3(n_jobs), dim3(256), 0, s, hist, tables, jobs, static_cast<const int16_t *>(data));
+    else hipLaunchKernelGGL(live_history_kernel<float>, dim3(n_jobs), dim3(256), 0, s, hist, tables, jobs, static_cast<const float *>(data));
 }
 
 }  // namespace bn
