@@ -102,7 +102,7 @@ class StagePool {
     StagePool() {
         unsigned hw = std::thread::hardware_concurrency();
         long n = hw > 2 ? std::min<long>(6, (long)hw / 2) : 0;
-        if (const char *e = getenv("BN_STAGE_THREADS")) n = std::max<long>(0, std::min<long>(64, atol(e)));
+        if (sw_is_set(sw::BN_STAGE_THREADS)) n = std::max<long>(0, std::min<long>(64, (long)sw_i64(sw::BN_STAGE_THREADS)));
         for (long k = 0; k < n; k++) th_.emplace_back([this] { loop(); });
     }
     ~StagePool() {
@@ -165,7 +165,7 @@ struct bn_ctx {
     size_t h_out_elems = 0;
     size_t device_bytes = 0;
     bool holds_model = false;  // counted in model->refs (set once creation succeeded)
-    bool counted = false;      // counted in the device's live-context count (kernels.h device_context_count)
+    bool counted = false;      // counted in the device's live-context count (kernels.h device_shared)
     bool in_flight = false;  // a cancelled/timed-out run may still be executing
     size_t last_batch = 0;
     // top-K scratch
@@ -198,8 +198,8 @@ struct bn_ctx {
     uint64_t next_ticket = 1;
     struct GraphKey {
         size_t batch;
-        const float *in;
-        bool operator<(const GraphKey &o) const { return batch != o.batch ? batch < o.batch : in < o.in; }
+        bool shared;  // the grid form the launches were captured in (kernels.h device_shared)
+        bool operator<(const GraphKey &o) const { return batch != o.batch ? batch < o.batch : shared < o.shared; }
     };
     std::map<GraphKey, hipGraphExec_t> graphs;
     std::map<GraphKey, uint64_t> graph_used;  // replay counter value at each graph's last launch (least recently used goes first)
@@ -322,12 +322,16 @@ void launch_op(const bn_ctx *c, const PlanOp &op, const float *d_in, int64_t bat
 bn_status enqueue_plan(bn_ctx *c, const float *d_in, size_t batch, const volatile int32_t *cancel) {
     const Plan &p = *c->pd->plan;
     bool use_graph = !(c->flags & BN_CTX_NO_GRAPH);
+    // the grids of some launches depend on whether the device is shared: decided here, once, for every launch of this batch -- captured
+    // or not -- and for the graph's key
+    const bool shared = bn::device_shared();
+    const bn::SharedFormPin pin(shared);
     // The plan always reads the batch from the CONTEXT'S OWN input buffer: a captured graph then depends on the batch
     // size alone (one capture + instantiate per batch size, whatever buffers the caller cycles through), and a caller
     // that wants no copy at all writes its batch into that buffer (bn_ctx_input_device).  Any other device pointer is
     // copied in on the context's stream, ahead of the plan: 18 MB at batch 32, about 10 us.
     if (d_in != c->d_input) {
-        static const bool runtime_copy = getenv("BN_INPUT_MEMCPY") && atoi(getenv("BN_INPUT_MEMCPY")) != 0;
+        static const bool runtime_copy = sw_int(sw::BN_INPUT_MEMCPY) != 0;
         if (runtime_copy) HIP_TRY(hipMemcpyAsync(c->d_input, d_in, batch * (size_t)p.sample_count * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
         else {
             launch_copy_dev(c->stream, c->d_input, d_in, batch * (size_t)p.sample_count * sizeof(float));
@@ -337,8 +341,7 @@ bn_status enqueue_plan(bn_ctx *c, const float *d_in, size_t batch, const volatil
         d_in = c->d_input;
     }
     if (use_graph) {
-        // (the grids of some launches depend on whether the device is shared, kernels.h: one graph per form)
-        bn_ctx::GraphKey key{batch, bn::device_context_count() > 1 ? reinterpret_cast<const float *>(uintptr_t(1)) : nullptr};
+        bn_ctx::GraphKey key{batch, shared};  // one graph per (batch, form)
         auto it = c->graphs.find(key);
         if (it == c->graphs.end()) {
             hipGraph_t g = nullptr;
@@ -388,7 +391,7 @@ bn_status enqueue_plan(bn_ctx *c, const float *d_in, size_t batch, const volatil
                 if (c->n_capture_fallbacks == 1)
                     fprintf(stderr, "libbirdnet_hip: graph capture for batch %zu failed (%s); running the plan launch by launch\n", batch,
                             c->last_fallback.c_str());
-                static const bool strict = getenv("BN_STRICT_GRAPH") && atoi(getenv("BN_STRICT_GRAPH")) != 0;
+                static const bool strict = sw_int(sw::BN_STRICT_GRAPH) != 0;
                 if (strict) return fail(BN_ERR_BACKEND, "graph capture failed: " + c->last_fallback);
                 use_graph = false;
             } else {
@@ -493,7 +496,7 @@ bn_status finish_load(std::unique_ptr<bn_model> m, int32_t device, int32_t model
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return fail(BN_ERR_NO_DEVICE, "no HIP device is visible; this path has no CPU fallback");
     if (device < 0 || device >= n) return fail(BN_ERR_NO_DEVICE, "device index " + std::to_string(device) + " out of range (" + std::to_string(n) + " visible)");
-    if (!device_is_gfx950(device) && !getenv("BN_ALLOW_ANY_ARCH")) return fail(BN_ERR_NO_DEVICE, "device " + std::to_string(device) + " is not gfx950 (MI355X)");
+    if (!device_is_gfx950(device) && !sw_present(sw::BN_ALLOW_ANY_ARCH)) return fail(BN_ERR_NO_DEVICE, "device " + std::to_string(device) + " is not gfx950 (MI355X)");
     m->device = device;
     m->io = read_io_meta(m->onnx);
     if (m->onnx.inputs.size() != 1) return fail(BN_ERR_MODEL_DETECTION, "model has " + std::to_string(m->onnx.inputs.size()) + " inputs, expected 1");
@@ -665,7 +668,7 @@ bn_status bn_ctx_create(bn_model *m, size_t max_batch, uint32_t flags, bn_ctx **
         }
         pd = m->full_plan.get();
     }
-    if (getenv("BN_NO_GRAPH")) flags |= BN_CTX_NO_GRAPH;
+    if (sw_present(sw::BN_NO_GRAPH)) flags |= BN_CTX_NO_GRAPH;
     auto c = std::make_unique<bn_ctx>();
     c->model = m;
     c->pd = pd;
@@ -804,7 +807,7 @@ struct OutRegion {
     size_t bytes;
 };
 static bn_status results_to_host(bn_ctx *c, const OutRegion *regs, int n) {
-    static const bool sdma = getenv("BN_SDMA_COPY") && atoi(getenv("BN_SDMA_COPY")) != 0;
+    static const bool sdma = sw_int(sw::BN_SDMA_COPY) != 0;
     CopyOut co{};
     bool kernel_ok = !sdma && n <= 3;
     for (int r = 0; r < n && kernel_ok; r++) {
@@ -1443,7 +1446,7 @@ bn_status bn_recording_create_async(int32_t device, const void *pcm, size_t n_sa
     // the uploader holds the capture gate (shared) for one chunk's synchronous copy and a context's first-time graph capture takes it
     // exclusively: 4 MiB keeps a capture's wait behind a chunk well under a millisecond (32 MiB chunks stalled exactly the first
     // windows' captures the overlap was meant to help)
-    const size_t chunk_mb = getenv("BN_UPLOAD_CHUNK_MB") ? (size_t)std::max(1, atoi(getenv("BN_UPLOAD_CHUNK_MB"))) : 4;
+    const size_t chunk_mb = (size_t)std::max(1, sw_int(sw::BN_UPLOAD_CHUNK_MB));
     auto r = std::make_unique<bn_recording>();
     r->device = device;
     r->format = format;

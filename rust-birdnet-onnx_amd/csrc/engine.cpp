@@ -593,7 +593,7 @@ class Builder {
     // fold, so that all three spellings reach the same plan.  Only the exact patterns are rewritten (every intermediate has ONE consumer and
     // is no graph output); anything else keeps its nodes and goes through lower_stft / lower_dft, which map the general case.
     void canonicalize_spectrogram_dialects() {
-        if (env_int("BN_CANON_SPECTRO", 1) == 0) return;
+        if (sw_int(sw::BN_CANON_SPECTRO) == 0) return;
         std::map<std::string, int> uses;
         for (auto &nd : nodes_)
             for (auto &i : nd.inputs)
@@ -800,10 +800,9 @@ class Builder {
     // evaluates in 512 taps each where 96 merged filters would need 1024.  Costs in f32-MFMA SIMD-cycles per frame, the scale emit_stft
     // calibrated.  The filters are summed in double and rounded once.  BN_CONVMERGE=0 disables, =1 merges wherever the pattern matches.
     void merge_framing_products() {
-        const int mode = env_int("BN_CONVMERGE", -1);
+        const int mode = sw_int(sw::BN_CONVMERGE);
         if (mode == 0) return;
-        const std::string stft_mode = getenv("BN_STFT") ? getenv("BN_STFT") : "auto";
-        if (stft_mode == "1" && mode != 1) return;  // every recognised bank as an FFT: the banks stay banks
+        if (sw_is(sw::BN_STFT, "1") && mode != 1) return;  // every recognised bank as an FFT: the banks stay banks
         for (size_t k = 0; k < nodes_.size(); k++) {
             if (!live_[k] || nodes_[k].op_type != "Conv") continue;
             OnnxNode &conv = nodes_[k];
@@ -847,7 +846,7 @@ class Builder {
             double bank = (double)C * (double)(all_folded ? L / 2 : L) / 32.0;
             bool product_inside = false;
             if (all_sym && L % 128 == 0 && C <= 160) bank = std::min(bank, (double)C * (double)(L / 4 + 1) / 32.0);  // quarter fold
-            if (all_folded && fft_size && stft_mode != "0") {
+            if (all_folded && fft_size && !sw_is(sw::BN_STFT, "0")) {
                 const double fft = 0.18 * (double)L * std::log2((double)L);  // (with its mel phase: emit_stft's calibration)
                 if (fft < bank) { bank = fft; product_inside = true; }
             }
@@ -953,7 +952,7 @@ class Builder {
     bool detect_dft_bank(const std::vector<float> &wf, int64_t Cout, int64_t L, const std::vector<int> &cls, DftBank &bank) {
         const bool pow2 = (L & (L - 1)) == 0;
         if (L < 128 || L > 2048 || !(pow2 || fft_five_pow2(L))) return false;
-        const double tol = getenv("BN_STFT_TOL") ? atof(getenv("BN_STFT_TOL")) : 4e-7;
+        const double tol = sw_double(sw::BN_STFT_TOL);
         bank.L = L;
         bank.k.assign((size_t)Cout, 0);
         bank.a.assign((size_t)Cout, 0.0);
@@ -1098,7 +1097,7 @@ class Builder {
                 const double res = den > 0 ? energy[(size_t)c] - num * num / den : INFINITY;
                 if (res < best_res) { best_res = res; best = k; }
             }
-            if (getenv("BN_STFT_DEBUG") && (c < 4 || best != k0))
+            if (sw_present(sw::BN_STFT_DEBUG) && (c < 4 || best != k0))
                 fprintf(stderr, "stft: row %lld %s peak bin %d -> %d (residual %.3g of energy %.3g)\n", (long long)c, is_sin[(size_t)c] ? "sin" : "cos", k0, best,
                         best_res, energy[(size_t)c]);
             bank.k[(size_t)c] = best;
@@ -1124,7 +1123,7 @@ class Builder {
             for (int64_t n = 0; n < L; n++) {
                 const double model = amp[(size_t)c] * win[(size_t)n] * trig(c, n);
                 if (!(std::fabs(model - (double)wf[(size_t)(c * L + n)]) <= tol * rowmax[(size_t)c])) {
-                    if (getenv("BN_STFT_DEBUG"))
+                    if (sw_present(sw::BN_STFT_DEBUG))
                         fprintf(stderr, "stft: row %lld (bin %d, %s) tap %lld: model %.9g vs %.9g (row max %.3g)\n", (long long)c, bank.k[(size_t)c],
                                 is_sin[(size_t)c] ? "sin" : "cos", (long long)n, model, (double)wf[(size_t)(c * L + n)], rowmax[(size_t)c]);
                     return false;
@@ -1149,11 +1148,9 @@ class Builder {
         // product 69 us, FFT 76-93 us; L = 1024 with 309 live bins -- 85 us vs 62-75 us).  Default ("auto"): FFT when the
         // matrix product is estimated at more than 1.5x the FFT.  BN_STFT=1: every recognised bank; BN_STFT=0: none;
         // BN_STFT_MINBINS=<n> additionally keeps banks with fewer live bins on the matrix path.
-        const char *env = getenv("BN_STFT");
-        const std::string mode = env ? env : "auto";
-        if (mode == "0") return false;
-        if (getenv("BN_STFT_MINBINS") && Cout < atoll(getenv("BN_STFT_MINBINS"))) return false;
-        if (mode != "1") {
+        if (sw_is(sw::BN_STFT, "0")) return false;
+        if (Cout < sw_i64(sw::BN_STFT_MINBINS)) return false;
+        if (!sw_is(sw::BN_STFT, "1")) {
             const double lg = std::log2((double)bank.L);
             const double gemm_cycles = (double)Cout * (double)(bank.L / 2) / 32.0, fft_cycles = 0.18 * (double)bank.L * lg;
             if (!(gemm_cycles > 1.5 * fft_cycles)) return false;
@@ -1253,8 +1250,8 @@ class Builder {
     // padded to 32, then odd bins) and a column map sends every result to its output channel.  v2.4's 127 mel-live bins of the 2048-point
     // branch: 17 K steps instead of 32.  BN_CONVFOLD2=0 keeps the half fold.
     bool emit_quarter_fold(const OnnxNode &n, const PlanOp &base, const DftBank &bank, const std::vector<int> &cls, int64_t Cout, int64_t OW, bool has_bias) {
-        if (env_int("BN_CONVFOLD2", 1) == 0) return false;
-        if (env_int("BN_FRAMEPAIR", 0) == 1) return false;  // (opt-in rule J fuses the mel product behind the HALF fold's launch)
+        if (sw_int(sw::BN_CONVFOLD2) == 0) return false;
+        if (sw_int(sw::BN_FRAMEPAIR) == 1) return false;  // (opt-in rule J fuses the mel product behind the HALF fold's launch)
         const int64_t L = bank.L;
         if (L % 128 != 0) return false;
         for (int64_t c = 0; c < Cout; c++)
@@ -1279,7 +1276,7 @@ class Builder {
         float wmax = 0.0f;
         for (float v : w) wmax = std::max(wmax, std::fabs(v));
         const float eps = 4e-7f * wmax;
-        const bool dbg = getenv("BN_STFT_DEBUG") != nullptr;
+        const bool dbg = sw_present(sw::BN_STFT_DEBUG);
         if (!(std::fabs(w[0]) <= eps)) {
             if (dbg) fprintf(stderr, "quarter fold: window tap 0 = %.3g\n", (double)w[0]);
             return false;
@@ -1393,10 +1390,9 @@ class Builder {
     // each (cos block, sin block), writing column slices of the same output.  BN_CONVFOLD=0 disables.
     bool fold_framing_conv(const OnnxNode &n, const PlanOp &base, const std::vector<float> &wf, int64_t Cout, int64_t L, int64_t OW,
                            bool has_bias) {
-        const char *env = getenv("BN_CONVFOLD");
-        if (env && std::string(env) == "0") return false;
+        if (sw_is(sw::BN_CONVFOLD, "0")) return false;
         if (L < 128 || L % 64 != 0) return false;  // K = L/2 must be a whole number of 32-wide K steps
-        const double tol = getenv("BN_CONVFOLD_TOL") ? atof(getenv("BN_CONVFOLD_TOL")) : 1.1920929e-7;
+        const double tol = sw_double(sw::BN_CONVFOLD_TOL);
         float maxabs = 0.0f;
         for (float v : wf) maxabs = std::max(maxabs, std::fabs(v));
         if (!(maxabs > 0.0f) || !std::isfinite(maxabs)) return false;
@@ -1465,8 +1461,7 @@ class Builder {
     // and `halo` the pixels it expands per sample.  Per-sample shapes only, so a segment's bits do not depend on its batch.
     // BN_MBROW=0 keeps the tiled kernels.
     static void row_streaming(MbDesc &m, double &halo) {
-        const char *env = getenv("BN_MBROW");
-        if (env && std::string(env) == "0") return;
+        if (sw_is(sw::BN_MBROW, "0")) return;
         if (!mbconv_row_supported(m)) return;
         const int outw = mbconv_row_outw(m.k, m.s);
         // a strip expands 32 halo columns for `outw` outputs whatever the map's width: on narrow maps (Perch: 32 or 16
@@ -1475,13 +1470,12 @@ class Builder {
         // 63 x 16) -- the kernel then streams along the map's rows' direction instead (MbDesc::row_tr: strips across the
         // height), if that fills its strips.  BN_MBROW=force takes the row kernel regardless (tests), BN_MBROW_TR=0 never
         // transposes, =1 always does where the kernel supports it
-        const bool force = env && std::string(env) == "force";
-        const char *tre = getenv("BN_MBROW_TR");
+        const bool force = sw_is(sw::BN_MBROW, "force");
         const int strips = (m.OW + outw - 1) / outw, strips_t = (m.OH + outw - 1) / outw;
         const double util = (double)m.OW / (double)(strips * outw), util_t = (double)m.OH / (double)(strips_t * outw);
         bool tr = m.k1 == 0 && m.k == 3 && util_t >= 0.7 && util_t > util + 0.08;  // (5 x 5 instances: no register to spare for the second addressing form)
-        if (tre && std::string(tre) == "0") tr = false;
-        if (tre && std::string(tre) == "1") tr = m.k1 == 0 && m.k == 3;
+        if (sw_is(sw::BN_MBROW_TR, "0")) tr = false;
+        if (sw_is(sw::BN_MBROW_TR, "1")) tr = m.k1 == 0 && m.k == 3;
         if (tr) {
             MbDesc probe = m;
             probe.row_tr = 1;
@@ -1490,7 +1484,7 @@ class Builder {
         if (!force && !tr && util < 0.7) return;
         m.row_mode = 1;
         m.row_tr = tr ? 1 : 0;
-        m.row_b3 = (env_int("BN_MBROW_B3", 1) != 0 && env_int("BN_GEMM3", 2) != 0 && m.k1 == 0 && m.Cin % 8 == 0) ? 1 : 0;
+        m.row_b3 = (sw_int(sw::BN_MBROW_B3) != 0 && sw_int(sw::BN_GEMM3) != 0 && m.k1 == 0 && m.Cin % 8 == 0) ? 1 : 0;
         const int rows_k = tr ? m.OW : m.OH, cols_k = tr ? m.OH : m.OW;  // the kernel's output rows / columns
         // band height: a band of toh output rows expands (toh - 1) s + k halo rows, so taller bands recompute less (12 rows of a
         // 5x5 block: 16 halo rows instead of 2 x 10) -- what several contexts sharing the chip pay for; a block with one or two
@@ -1499,7 +1493,7 @@ class Builder {
         const int toh_target = (m.C + 31) / 32 >= 3 ? 12 : 8;
         const int nbands = std::max(1, (rows_k + toh_target / 2 - 1) / toh_target);
         const int toh_default = (rows_k + nbands - 1) / nbands;
-        m.toh = std::min<int32_t>(rows_k, getenv("BN_MBROW_TOH") ? std::max(1, atoi(getenv("BN_MBROW_TOH"))) : toh_default);
+        m.toh = std::min<int32_t>(rows_k, sw_is_set(sw::BN_MBROW_TOH) ? std::max(1, sw_int(sw::BN_MBROW_TOH)) : toh_default);
         m.tiles_x = (cols_k + outw - 1) / outw;
         m.tiles_y = (rows_k + m.toh - 1) / m.toh;
         halo = 32.0 * m.tiles_x * (double)m.tiles_y * ((m.toh - 1) * m.s + m.k);
@@ -3025,7 +3019,7 @@ class Builder {
             // v2.4 plan -- the last block streams both excite matrices through ONE compute unit (442 KB at C = 1152:
             // +26 us per whole-map depthwise launch against 8-10 us for the multi-block excite kernel), and every block of
             // a fused MBConv launch pays a store drain + returning atomic (+13 us per launch); DESIGN.md section 4.12.
-            const std::string mode = getenv("BN_SEFUSE") ? getenv("BN_SEFUSE") : "0";  // 0 | dw | mb | 1 (both)
+            const std::string mode = sw_text(sw::BN_SEFUSE);  // 0 | dw | mb | 1 (both)
             if (mbp && !mbp->mb.whole_map && !mbp->mb.row_mode && (mode == "1" || mode == "mb")) host = mbp;  // the row-streaming form has no block that could be "last"
             else if (dwp && dwp->dw.tiled == 2 && (mode == "1" || mode == "dw")) host = dwp;
         }
@@ -3079,7 +3073,7 @@ class Builder {
         // max(x - s) == max(x) - s exactly when s is one number per reduced range (rounding is monotone), same for min:
         // the reduction reads x itself and the shifted signal is no longer needed for it -- in the min-max normalisation
         // of the v2.4 front end the Sub then has a single consumer left and fuses into the scaling chain (one pass less).
-        if ((t == "ReduceMax" || t == "ReduceMin") && !(getenv("BN_REDUCE_SHIFT") && std::string(getenv("BN_REDUCE_SHIFT")) == "0")) {
+        if ((t == "ReduceMax" || t == "ReduceMin") && sw_on(sw::BN_REDUCE_SHIFT)) {
             int prod = -1;
             for (size_t k = 0; k < nodes_.size() && prod < 0; k++)
                 if (live_[k] && !absorbed_[k] && nodes_[k].op_type == "Sub" && nodes_[k].outputs.size() == 1 && nodes_[k].outputs[0] == n.inputs[0]) prod = (int)k;
@@ -3180,7 +3174,7 @@ class Builder {
         // into c chunks reduced by c blocks per sample and a second tiny launch reduces the c partials: bit-identical
         // result, ~4x less time.  Sums keep their single fixed-order pass.  BN_REDUCE_SPLIT=0 disables.
         if ((op == RED_MAX || op == RED_MIN) && d.nk == 0 && d.nr == 1 && d.rin[0] == 1 && d.red >= 32768 &&
-            !(getenv("BN_REDUCE_SPLIT") && std::string(getenv("BN_REDUCE_SPLIT")) == "0")) {
+            sw_on(sw::BN_REDUCE_SPLIT)) {
             int64_t c = 0;
             for (int64_t q = 64; q >= 4 && !c; q--)
                 if (d.red % q == 0 && (d.red / q) % 4 == 0 && d.red / q >= 8192) c = q;
@@ -3397,10 +3391,10 @@ class Builder {
                 // small feature maps: one block stages the whole map of 32 channels in LDS (one round of
                 // coalesced loads instead of a load-use chain per kernel row) and emits the complete
                 // squeeze sums, so the excite kernel adds nothing up
-                const bool map_off = getenv("BN_DWMAP") && std::string(getenv("BN_DWMAP")) == "0";
+                const bool map_off = !sw_on(sw::BN_DWMAP);
                 if (!map_off && kh == kw && strides[0] == strides[1] && H * W <= 768) {
                     d.tiled = 2;
-                    d.mapt = env_int("BN_DWMAPT", 1) != 0 ? 1 : 0;
+                    d.mapt = sw_int(sw::BN_DWMAPT) != 0 ? 1 : 0;
                     d.nblk = 1;
                 }
             }
@@ -3416,13 +3410,12 @@ class Builder {
             // the 6x32 maps (2 tiles per sample) and for K >= 80 the separate launches win, so the rule
             // below keeps those unfused.  The rule only looks at per-sample shapes (batch invariance).
             // BN_MBFUSE=0 disables, BN_MBFUSE=force fuses every eligible pair (tests).
-            const char *mbenv = getenv("BN_MBFUSE");
-            const bool mb_off = mbenv && std::string(mbenv) == "0";
+            const bool mb_off = sw_is(sw::BN_MBFUSE, "0");
             // Stem variant: the producer is a dense k1 x k1 convolution with few input channels (k1*k1*Cin1 <= 48,
             // e.g. the 3x3 stride-2 conv over the 2-channel spectrogram image).  Its output tile is rebuilt from im2col
             // rows staged in LDS and never written to HBM either (same kernel, different staging).  BN_STEMFUSE=0 disables.
             if (d.tiled && kh == kw && strides[0] == strides[1] && !mb_off && !plan_.ops.empty() &&
-                !(getenv("BN_STEMFUSE") && std::string(getenv("BN_STEMFUSE")) == "0")) {
+                sw_on(sw::BN_STEMFUSE)) {
                 PlanOp &pe = plan_.ops.back();
                 const ConvDesc &cd = pe.conv;
                 const int a1 = cd.act;
@@ -3431,7 +3424,7 @@ class Builder {
                 const bool stem = pe.kind == OpKind::CONV && pe.out.space == Space::ARENA && pe.out.id == x.storage && pe.out.offset == 0 && x.offset == 0 &&
                                   cd.groups == 1 && cd.kh == cd.kw && cd.sh == cd.sw && cd.dh == 1 && cd.dw == 1 && !cd.has_res && cd.Cin <= 4 &&
                                   cd.kh * cd.kw * cd.Cin <= 48 && cd.OH == H && cd.OW == W && cd.Cout == Cin && act_zero &&
-                                  (H * W >= 3072 || (mbenv && std::string(mbenv) == "force"));
+                                  (H * W >= 3072 || sw_is(sw::BN_MBFUSE, "force"));
                 MbDesc probe{};
                 probe.k = (int32_t)kw; probe.s = (int32_t)strides[1]; probe.Cin = stem ? cd.kh * cd.kw * cd.Cin : 4; probe.C = (int32_t)Cin;
                 if (stem && mbconv_lds_bytes(probe) <= 150 * 1024 && sole_consumer(n.inputs[0]) == cur_) {
@@ -3477,20 +3470,20 @@ class Builder {
             }
             if (d.tiled && kh == kw && strides[0] == strides[1] && !mb_off && !plan_.ops.empty()) {
                 PlanOp &pe = plan_.ops.back();
-                const int maxk = std::min(48, getenv("BN_MBFUSE_MAXK") ? atoi(getenv("BN_MBFUSE_MAXK")) : 48);  // kernel: <= 6 K groups in registers
+                const int maxk = std::min(48, sw_int(sw::BN_MBFUSE_MAXK));  // kernel: <= 6 K groups in registers
                 // the kernel relies on act(0) == 0 for the expand activation (pixels outside the image)
                 const int a1 = pe.gemm.act;
                 const bool act_zero = a1 == ACT_NONE || a1 == ACT_RELU || (a1 == ACT_CLIP && pe.gemm.p0 <= 0.f && pe.gemm.p1 >= 0.f) ||
                                       a1 == ACT_SILU || a1 == ACT_HSWISH || a1 == ACT_LEAKY || a1 == ACT_TANH;
-                const double maxhalo = getenv("BN_MBFUSE_HALO") ? atof(getenv("BN_MBFUSE_HALO")) : 3.0;
+                const double maxhalo = sw_double(sw::BN_MBFUSE_HALO);
                 // small feature maps can take the whole-map kernel (one block = 32 mid channels x the whole map:
                 // no halo, any K up to 256, complete squeeze sums).  Opt-in (BN_MBMAP=1): measured on MI355X at
                 // batch 32 it saves 10 launches and ~1% of single-stream latency, but its per-block fixed costs
                 // (filter slab + A rows per 32-channel chunk, half the waves idle on 3x16 maps) make the
                 // marginal cost per extra batch ~30% higher than GEMM + whole-map depthwise, and the three-
                 // context throughput drops from 34.2k to 33.1k seg/s.
-                const bool map_off = !(getenv("BN_MBMAP") && std::string(getenv("BN_MBMAP")) == "1");
-                const int64_t map_maxhw = getenv("BN_MBMAP_MAXHW") ? atoll(getenv("BN_MBMAP_MAXHW")) : 512;
+                const bool map_off = !sw_is(sw::BN_MBMAP, "1");
+                const int64_t map_maxhw = sw_i64(sw::BN_MBMAP_MAXHW);
                 const bool producer0 = pe.kind == OpKind::GEMM && pe.out.space == Space::ARENA && pe.out.id == x.storage && pe.out.offset == 0 &&
                                        x.offset == 0 && !pe.gemm.has_scale && !pe.gemm.has_res && pe.gemm.rows == H * W && pe.gemm.N == Cin &&
                                        pe.gemm.lda == pe.gemm.K && pe.gemm.K % 4 == 0 && pe.a.offset % 4 == 0 && !pe.gemm.fold && !pe.gemm.npost &&
@@ -3516,7 +3509,7 @@ class Builder {
                 const int toh0 = strides[1] == 1 ? 8 : 4, tow0 = strides[1] == 1 ? 16 : 8;
                 const int64_t hp = ((toh0 - 1) * strides[1] + kw) * ((tow0 - 1) * strides[1] + kw);
                 const double halo_factor = (double)((hp + 31) / 32 * 32) * ((OW + tow0 - 1) / tow0) * ((OH + toh0 - 1) / toh0) / (double)(H * W);
-                const bool force = mbenv && std::string(mbenv) == "force";  // tests: small feature maps too
+                const bool force = sw_is(sw::BN_MBFUSE, "force");  // tests: small feature maps too
                 // (round 3: stride-2 blocks on 768-pixel maps too -- with the row-streaming kernel the 12x64x40->240 s2 pair
                 // runs in 17.5 us instead of 16.5 + 16.4, marginal cost per extra batch 8.6 against 24 us)
                 const bool big_enough = H * W >= 768;
@@ -3842,7 +3835,7 @@ class Builder {
     // over 80 per sample; the prologue is a chain of load latencies (K = 672: project conv 20 -> 52 us against 20 + 8 for
     // the two launches), four contexts 52.7 k -> 47.2 k segments/s.  Opt-in (BN_SEGEMM=1), kept under test.
     void absorb_se_into_gemms() {
-        if (!(getenv("BN_SEGEMM") && atoi(getenv("BN_SEGEMM")) == 1)) return;
+        if (!(sw_int(sw::BN_SEGEMM) == 1)) return;
         const int max_c = gemm_dma_se_max_channels();
         std::vector<Ref *> refs;
         for (size_t j = 0; j < plan_.ops.size(); j++) {
@@ -3887,8 +3880,8 @@ class Builder {
     //    min-max normalisation of the v2.4 graph) and every reader of its result is an STFT launch: the chain runs
     //    while the span is loaded, the normalised segment is never written.  BN_STFT_PRE=0 disables.
     void absorb_into_stft() {
-        const bool mel_on = !(getenv("BN_STFT_MEL") && std::string(getenv("BN_STFT_MEL")) == "0");
-        const bool pre_on = !(getenv("BN_STFT_PRE") && std::string(getenv("BN_STFT_PRE")) == "0");
+        const bool mel_on = !sw_is(sw::BN_STFT_MEL, "0");
+        const bool pre_on = sw_on(sw::BN_STFT_PRE);
         auto users_of = [&]() {
             std::vector<std::vector<int>> users(plan_.storages.size());
             std::vector<Ref *> refs;
@@ -3903,7 +3896,7 @@ class Builder {
         //    the two halves of every spectrum row, whose only reader it is -- the launch computes both linear forms of a bin
         //    in one lane and stores f(u^2 + v^2): half the spectrum bytes written, none read back, one launch less, and the
         //    mel bank that follows becomes a direct neighbour (next rule).  BN_STFT_POWER=0 disables.
-        if (!(getenv("BN_STFT_POWER") && std::string(getenv("BN_STFT_POWER")) == "0")) {
+        if (sw_on(sw::BN_STFT_POWER)) {
             bool again = true;
             while (again) {
                 again = false;
@@ -4002,7 +3995,7 @@ class Builder {
                 // the tile's spectrum rows join the LDS image.  Where 16 frames per tile no longer fit (v3.0: 513 bins, 128 bands)
                 // tiles of 8 would, but the launch then loses to FFT + dense mel GEMM (200 us against 97 + 66 at batch 64,
                 // 41.5 k against 44.0 k segments/s): BN_STFT_MEL=force takes the smaller tile anyway (tests)
-                if (getenv("BN_STFT_MEL") && std::string(getenv("BN_STFT_MEL")) == "force")
+                if (sw_is(sw::BN_STFT_MEL, "force"))
                     while (stft_lds_bytes(probe, 8) > 156 * 1024 && probe.tpb > 8 && (probe.tpb / 2) % probe.F == 0) probe.tpb /= 2;
                 if (stft_lds_bytes(probe, 8) > 156 * 1024) continue;
                 FftDesc &d = f.fft;
@@ -4013,7 +4006,7 @@ class Builder {
                 // the bank as 16 x 16 tiles for the matrix cores (kernels.h, FftDesc::mel_mode): tile rows of 16 bands, of each
                 // only the 16-bin groups that hold a non-zero; a tile is stored in the lane order of the A fragment (lane (i, q)
                 // holds band i, bins 16 g + 4 q + 0..3).  BN_STFT_MELMFMA=0 keeps the (column, weight) lists on the vector ALU.
-                if (!(getenv("BN_STFT_MELMFMA") && std::string(getenv("BN_STFT_MELMFMA")) == "0") && d.tpb == 16) {
+                if (sw_on(sw::BN_STFT_MELMFMA) && d.tpb == 16) {
                     const int64_t ntile = (N + 15) / 16, ngrp = (K + 15) / 16;
                     std::vector<float> tab((size_t)ntile + 1, 0.0f), glist, pack;
                     for (int64_t t = 0; t < ntile; t++) {
@@ -4089,8 +4082,8 @@ class Builder {
                 // is certain to run on its LDS-resident kernel (half fold: frame_fold_post_ok; quarter fold: always)
                 auto framing_gemm = [&](const PlanOp &f) {
                     const GemmDesc &g = f.gemm;
-                    if (f.kind != OpKind::GEMM || f.pre.n != 0 || f.gemm2.N > 0 || f.se_fused || env_int("BN_FRAME_PRE", 1) == 0) return false;
-                    if (env_int("BN_FRAMEPAIR", 0) == 1) return false;  // (opt-in rule J runs later and its kernel does not carry the chain)
+                    if (f.kind != OpKind::GEMM || f.pre.n != 0 || f.gemm2.N > 0 || f.se_fused || sw_int(sw::BN_FRAME_PRE) == 0) return false;
+                    if (sw_int(sw::BN_FRAMEPAIR) == 1) return false;  // (opt-in rule J runs later and its kernel does not carry the chain)
                     if (!(g.fold == 2 ? frame_fold2_shape_ok(g, nullptr) : (g.fold == 1 || g.fold == -1) && frame_fold_post_ok(g))) return false;
                     return g.a_bs == ed.bo && (g.rows - 1) * g.lda + g.fold_n <= ed.per_sample;
                 };
@@ -4136,7 +4129,7 @@ class Builder {
         // (round 5) the zero-padded copy of the signal a padded framing conv reads (pad_copy: one fill + one copy launch) in the STFT's span
         // load: where the only reader of that copy is an FFT launch, the launch reads the signal itself and zero-fills the positions that
         // fall into the padding (FftDesc::pad_l, in_len).  Perch's front end: two launches and a round trip of the signal less.
-        changed = env_int("BN_STFT_PAD", 1) != 0;
+        changed = sw_int(sw::BN_STFT_PAD) != 0;
         while (changed) {
             changed = false;
             auto users = users_of();
@@ -4177,7 +4170,7 @@ class Builder {
     // rows of a tile), the [48, N] tensor is neither written nor read and the reduction launch is gone.  v2.4's head: Conv_261 (320 -> 1024,
     // ReLU) + GlobalAveragePool_264.  BN_GEMMGAP=0 disables.
     void fuse_gap_into_gemm() {
-        if (env_int("BN_GEMMGAP", 1) == 0) return;
+        if (sw_int(sw::BN_GEMMGAP) == 0) return;
         bool changed = true;
         while (changed) {
             changed = false;
@@ -4288,7 +4281,7 @@ class Builder {
     // after the max(x - s) rewrite) read it in one pass: the later launch is folded into the earlier one (kernels.h,
     // ReduceDesc::pair).  Exact, order-independent operations: same bits.  BN_REDUCE_PAIR=0 disables.
     void pair_minmax_reductions() {
-        if (getenv("BN_REDUCE_PAIR") && std::string(getenv("BN_REDUCE_PAIR")) == "0") return;
+        if (!sw_on(sw::BN_REDUCE_PAIR)) return;
         for (size_t i = 0; i < plan_.ops.size(); i++) {
             PlanOp &a = plan_.ops[i];
             if (a.kind != OpKind::REDUCE || a.red.pair || a.red.op != RED_MIN) continue;
@@ -4326,7 +4319,7 @@ class Builder {
     // out_strided).  v2.4 front end: mel MatMul -> x^2 -> x^p -> flip / transpose into the 2-channel image, per
     // branch one launch instead of two and no dense [frames, mels] round trip.  BN_GEMMPOST=0 disables.
     void absorb_chains_into_gemms() {
-        if (getenv("BN_GEMMPOST") && std::string(getenv("BN_GEMMPOST")) == "0") return;
+        if (!sw_on(sw::BN_GEMMPOST)) return;
         bool changed = true;
         while (changed) {
             changed = false;

@@ -268,8 +268,8 @@ bool launch_gemm_b3(hipStream_t s, const GemmDesc &d, float *C, const float *A, 
     // the parallelism, and the weight traffic decides: 64-row tiles throughout gain 1.9 % on the v2.4 step with four contexts (68.8 -> 70.1 k
     // segments/s) and cost the one-context chain 65 us -- so they are taken as soon as a second live context exists (kernels.h).
     const int64_t cus = device_cu_count();
-    const int force_mt = env_int("BN_GEMMB3_MT", 0);  // tests / experiments
-    int mt = (device_context_count() > 1 || (total_rows + 63) / 64 * nb >= cus) ? 4 : 2;
+    const int force_mt = sw_int(sw::BN_GEMMB3_MT);  // tests / experiments
+    int mt = (device_shared() || (total_rows + 63) / 64 * nb >= cus) ? 4 : 2;
     if (d.gap) mt = 3;
     else if (force_mt == 2 || force_mt == 3 || force_mt == 4) mt = force_mt;
 #define GB_GO(MT)                                                                                          \
@@ -284,7 +284,7 @@ bool launch_gemm_b3(hipStream_t s, const GemmDesc &d, float *C, const float *A, 
     } while (0)
     if (nw < 4) return false;
     // two channel tiles per wave: the large products (64-row tiles, at least 16 channel tiles, enough blocks to fill the device twice over)
-    const int ntw_env = env_int("BN_GEMMB3_NTW", 0);
+    const int ntw_env = sw_int(sw::BN_GEMMB3_NTW);
     if (mt == 4 && !d.gap && nt16 >= 16 && ntw_env != 1 && (ntw_env == 2 || (total_rows + 63) / 64 * ((nt16 + 15) / 16) >= 2 * cus)) {
         const int nb2 = (nt16 + 15) / 16;                  // channel blocks of at most 16 tiles (256 channels), evenly sized, two tiles per wave
         const int nw2 = ((nt16 + nb2 - 1) / nb2 + 1) / 2;  // waves per block

@@ -633,12 +633,12 @@ bool launch_gemm_dma(hipStream_t s, const GemmDesc &d, float *C, const float *A,
             }
         }
         const bool r64 = d.rows % 64 == 0;
-        const bool r128 = d.rows % 128 == 0 && getenv("BN_GEMMSTREAM_TR") && atoi(getenv("BN_GEMMSTREAM_TR")) == 128;  // experiment: 128-row tiles measured slower (191 against 125 us)
+        const bool r128 = d.rows % 128 == 0 && sw_int(sw::BN_GEMMSTREAM_TR) == 128;  // experiment: 128-row tiles measured slower (191 against 125 us)
         const int tr = r128 ? 128 : r64 ? 64 : 32;
         const int tps = (int)(d.rows / tr);
         const int64_t tiles = batch * tps, nbn = (d.N + 16 * ntw - 1) / (16 * ntw);
         const int64_t want_blocks = 2 * (int64_t)device_cu_count();
-        const int force_tpb = getenv("BN_GEMMSTREAM_TPB") ? atoi(getenv("BN_GEMMSTREAM_TPB")) : 0;  // tests / experiments
+        const int force_tpb = sw_int(sw::BN_GEMMSTREAM_TPB);  // tests / experiments
         // (whole rounds: grid.x * nbn must not exceed what is resident at once, or a handful of left-over blocks run a round of their own --
         // measured: 516 blocks on 512 slots 180 us, 474 blocks 125 us)
         const int64_t gx = std::max<int64_t>(1, want_blocks / nbn);
@@ -667,7 +667,7 @@ bool launch_gemm_dma(hipStream_t s, const GemmDesc &d, float *C, const float *A,
     // not by any launch's own latency (three contexts already reach 94 % of four), so the efficient tile wins even when
     // one launch alone leaves CUs idle: measured 54.6 k -> 55.5 k segments/s against a threshold of 192 blocks.
     // BN_GEMMDMA_MINBLOCKS moves the line.
-    const int64_t min_blocks = getenv("BN_GEMMDMA_MINBLOCKS") ? atoll(getenv("BN_GEMMDMA_MINBLOCKS")) : (device_context_count() > 1 ? 1 : 64);  // (a shared device: the efficient tile always, +0.7 %)
+    const int64_t min_blocks = gemm_dma_min_blocks();
 #define GD_GO(MTW, NTW, WM, WN)                                                                  \
     do {                                                                                         \
         if (ks == 2) launch_cfg<MTW, NTW, WM, WN, 2, 3>(s, d, C, A, W, bias, res, scale, batch, se); \

@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include "hip_gate.h"
+#include "switches.h"
 
 #include <algorithm>
 #include <atomic>
@@ -54,7 +55,8 @@ Rccl &rccl() {
     std::call_once(once, [] {
         // BN_RCCL_LIB names the library to load instead (a site's own build -- or the test stub that lets the RCCL branch
         // below execute on a one-GPU box, tests/stubs/rccl_stub.cpp); when it is set, nothing else is tried
-        if (const char *forced = getenv("BN_RCCL_LIB")) {
+        if (sw_is_set(sw::BN_RCCL_LIB)) {
+            const char *forced = sw_text(sw::BN_RCCL_LIB);
             r.lib = dlopen(forced, RTLD_NOW | RTLD_LOCAL);
             if (!r.lib) fprintf(stderr, "libbirdnet_hip: BN_RCCL_LIB=%s could not be loaded (%s); the group gathers with device copies\n", forced, dlerror());
         } else {
@@ -183,8 +185,8 @@ bn_status bn_group_create(bn_model *const *models, const int32_t *devices, int32
     // RCCL only for n > 1 ranks on pairwise distinct devices (one communicator per device in this process)
     // (BN_GROUP_FORCE_RCCL=1 takes the branch for ranks that SHARE a device too: the real library refuses such a communicator --
     // its error is reported below --, the test stub accepts it, which is how the branch is exercised on a one-GPU box)
-    const bool force_rccl = getenv("BN_GROUP_FORCE_RCCL") && atoi(getenv("BN_GROUP_FORCE_RCCL")) != 0;
-    if (n > 1 && ((int)distinct.size() == n || force_rccl) && !getenv("BN_GROUP_NO_RCCL")) {
+    const bool force_rccl = sw_int(sw::BN_GROUP_FORCE_RCCL) != 0;
+    if (n > 1 && ((int)distinct.size() == n || force_rccl) && !sw_present(sw::BN_GROUP_NO_RCCL)) {
         Rccl &rc = rccl();
         if (rc.ok()) {
             std::vector<void *> comms((size_t)n, nullptr);

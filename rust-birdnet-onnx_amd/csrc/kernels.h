@@ -7,6 +7,8 @@
 #include <cstdint>
 #include <cstdlib>
 
+#include "switches.h"
+
 namespace bn {
 
 // Epilogue / unary function codes.
@@ -308,8 +310,8 @@ struct FramePre {
 
 // (host logic shared by the launcher and the planner)
 inline bool gemm_use_splitk(const GemmDesc &d) {
-    static const int min_k = getenv("BN_SPLITK_MINK") ? atoi(getenv("BN_SPLITK_MINK")) : 256;
-    static const int max_rows = getenv("BN_SPLITK_MAXROWS") ? atoi(getenv("BN_SPLITK_MAXROWS")) : 256;
+    static const int min_k = sw_int(sw::BN_SPLITK_MINK);
+    static const int max_rows = sw_int(sw::BN_SPLITK_MAXROWS);
     // deep K, few output tiles per sample (measured: pays below ~8 tiles of 128x32 per sample);
     // the split-K kernel has no K-tail step
     const double tiles = (double)d.rows / 128 * ((d.N + 31) / 32);
@@ -430,8 +432,21 @@ void note_launch_device(int dev);
 bool ensure_dynamic_lds(const void *kernel, size_t bytes);
 int device_cu_count();
 void device_context_count_add(int dev, int delta);  // capi.cpp: a context was created (+1) / destroyed (-1) on the device
-int device_context_count();                        // live contexts on the launching thread's device (>= 1; bn_set_sharing_mode overrides: 1 / >= 2)
 void device_sharing_mode(int mode);
+// Which of their two grid forms the launchers take: true where the launching thread's device is shared -- several live contexts, or as
+// bn_set_sharing_mode says.  enqueue_plan asks ONCE per batch, keys its graph cache on the answer and pins it for its launches (a context
+// created or destroyed on another thread meanwhile must not mix the forms inside one graph); launches outside it are answered afresh.
+bool device_shared();
+class SharedFormPin {  // device_shared() == shared on this thread while the object lives
+   public:
+    explicit SharedFormPin(bool shared);
+    ~SharedFormPin();
+    SharedFormPin(const SharedFormPin &) = delete;
+    SharedFormPin &operator=(const SharedFormPin &) = delete;
+
+   private:
+    int prev_;
+};
 const float *device_zero_page();  // 4 KiB of zeros on the thread's launch device (allocated by prepare_device)
 size_t topk_lds_bytes(int64_t n, int64_t k);
 

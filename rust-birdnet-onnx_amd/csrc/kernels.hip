@@ -153,12 +153,16 @@ void device_context_count_add(int dev, int delta) {
 }
 static std::atomic<int> g_sharing_mode{0};  // bn_set_sharing_mode: 0 = alone (default), 1 = shared, -1 = by the count of live contexts
 void device_sharing_mode(int mode) { g_sharing_mode.store(mode < 0 ? -1 : (mode ? 1 : 0), std::memory_order_relaxed); }
-int device_context_count() {
-    const int dev = t_launch_dev;
-    int n = (dev >= 0 && dev < 64) ? g_ctx_count[dev].load(std::memory_order_relaxed) : 1;
-    n = n < 1 ? 1 : n;
+// the form enqueue_plan fixed for the launches of its batch on this thread (-1: none pinned)
+static thread_local int t_shared_pin = -1;
+SharedFormPin::SharedFormPin(bool shared) : prev_(t_shared_pin) { t_shared_pin = shared ? 1 : 0; }
+SharedFormPin::~SharedFormPin() { t_shared_pin = prev_; }
+bool device_shared() {
+    if (t_shared_pin >= 0) return t_shared_pin != 0;
     const int mode = g_sharing_mode.load(std::memory_order_relaxed);
-    return mode == 0 ? 1 : (mode == 1 && n < 2 ? 2 : n);
+    if (mode >= 0) return mode == 1;
+    const int dev = t_launch_dev;
+    return dev >= 0 && dev < 64 && g_ctx_count[dev].load(std::memory_order_relaxed) > 1;
 }
 int device_cu_count() {
     const uint64_t m = g_prepared_mask.load(std::memory_order_acquire);
@@ -3405,7 +3409,7 @@ static void launch_gemm_tiled(hipStream_t s, const GemmDesc &d, float *C, const 
     // widest N tile that still fills the 256 CUs a couple of times over
     // N tile: the least padded of {128, 96, 64, 32} that still fills the 256 CUs a couple of times over
     auto waste = [&](int bn) { return (int64_t)((d.N + bn - 1) / bn) * bn - d.N; };
-    static const int force_bn = getenv("BN_FORCE_BN") ? atoi(getenv("BN_FORCE_BN")) : 0;  // experiments only
+    static const int force_bn = sw_int(sw::BN_FORCE_BN);  // experiments only
     if (force_bn == 128) return launch_gemm_bn<128, false>(s, d, C, A, W, bias, res, scale, total_rows);
     if (force_bn == 96) return launch_gemm_bn<96, false>(s, d, C, A, W, bias, res, scale, total_rows);
     if (force_bn == 64) return launch_gemm_bn<64, false>(s, d, C, A, W, bias, res, scale, total_rows);
@@ -3414,8 +3418,8 @@ static void launch_gemm_tiled(hipStream_t s, const GemmDesc &d, float *C, const 
     // smaller blocks hide the load latency better than wider tiles save operand re-reads.  Wider
     // tiles only pay once the grid is several thousand blocks deep (high-resolution expand convs).
     if (d.fold) {
-        static const int fold_bn_wide = getenv("BN_FOLD_BN") ? atoi(getenv("BN_FOLD_BN")) : 0;  // experiments only
-        static const int fold_bn_narrow = getenv("BN_FOLD_BN_NARROW") ? atoi(getenv("BN_FOLD_BN_NARROW")) : fold_bn_wide;
+        static const int fold_bn_wide = sw_int(sw::BN_FOLD_BN);  // experiments only
+        static const int fold_bn_narrow = sw_is_set(sw::BN_FOLD_BN_NARROW) ? sw_int(sw::BN_FOLD_BN_NARROW) : fold_bn_wide;
         const int fold_bn = d.N > 200 ? fold_bn_wide : fold_bn_narrow;
         if (fold_bn == 128) return launch_gemm_bn<128, false>(s, d, C, A, W, bias, res, scale, total_rows);
         if (fold_bn == 96) return launch_gemm_bn<96, false>(s, d, C, A, W, bias, res, scale, total_rows);
@@ -3426,7 +3430,7 @@ static void launch_gemm_tiled(hipStream_t s, const GemmDesc &d, float *C, const 
         if (d.N > 32) return launch_gemm_bn<64, false>(s, d, C, A, W, bias, res, scale, total_rows);
         return launch_gemm_bn<32, false>(s, d, C, A, W, bias, res, scale, total_rows);
     }
-    static const int deep_bn = getenv("BN_DEEPK_BN") ? atoi(getenv("BN_DEEPK_BN")) : 0;  // experiments: N tile for K >= 1024
+    static const int deep_bn = sw_int(sw::BN_DEEPK_BN);  // experiments: N tile for K >= 1024
     if (deep_bn && d.K >= 1024) {
         if (deep_bn == 128) return launch_gemm_bn<128, false>(s, d, C, A, W, bias, res, scale, total_rows);
         if (deep_bn == 96) return launch_gemm_bn<96, false>(s, d, C, A, W, bias, res, scale, total_rows);
@@ -3446,7 +3450,7 @@ static void launch_gemm_splitk(hipStream_t s, const GemmDesc &d, float *C, const
     {
         // few output tiles and a deep K: 32-row tiles with the 4 waves of a block splitting K
         const int64_t m32 = (total_rows + 31) / 32;
-        static const int force_bn = getenv("BN_FORCE_SPLITK_BN") ? atoi(getenv("BN_FORCE_SPLITK_BN")) : 0;  // experiments only
+        static const int force_bn = sw_int(sw::BN_FORCE_SPLITK_BN);  // experiments only
         if (force_bn == 96 && d.N > 64) return launch_gemm_bn<96, true>(s, d, C, A, W, bias, res, scale, total_rows);
         if (force_bn >= 64 && d.N > 32) return launch_gemm_bn<64, true>(s, d, C, A, W, bias, res, scale, total_rows);
         if (force_bn == 32) return launch_gemm_bn<32, true>(s, d, C, A, W, bias, res, scale, total_rows);
@@ -3474,7 +3478,7 @@ static bool launch_frame_fold(hipStream_t s, const GemmDesc &d, float *C, const 
     for (int q = 0; q < 4; q++) { f.post_act[q] = d.post_act[q]; f.post_p0[q] = d.post_p0[q]; f.post_p1[q] = d.post_p1[q]; }
     if (pair && (d.npost || d.out_strided)) return false;  // (the fused second product carries its own chain)
     // wave columns: the N tile (32 * WN) with the least padding among 128 and 160 (fewer, wider tiles on a tie)
-    static const int force_wn = getenv("BN_FRAME_WN") ? atoi(getenv("BN_FRAME_WN")) : 0;  // experiments only
+    static const int force_wn = sw_int(sw::BN_FRAME_WN);  // experiments only
     auto padded = [&](int bn) { return (d.N + bn - 1) / bn * bn; };
     int wn = padded(160) <= padded(128) ? 5 : 4;
     if (d.N <= 96) wn = (d.N + 31) / 32 < 2 ? 2 : (d.N + 31) / 32;
@@ -3482,7 +3486,7 @@ static bool launch_frame_fold(hipStream_t s, const GemmDesc &d, float *C, const 
     // enter any output's arithmetic (47 -> 27 us for one segment)
     // K slices (round 4): from the tile width N ALONE would get -- three wave columns leave the SIMDs unbalanced, see frame_foldh_kernel --
     // so that a segment's bits do not depend on the batch-dependent choices around it
-    const int ks = (!pair && wn == 3 && env_int("BN_FRAME_KS", 2) == 2) ? 2 : 1;
+    const int ks = (!pair && wn == 3 && sw_int(sw::BN_FRAME_KS) == 2) ? 2 : 1;
     if ((int64_t)f.tiles * batch <= 32 && d.N > 64) wn = 2;
     if (force_wn >= 2 && force_wn <= 5) wn = force_wn;
     if (pair) wn = std::max(2, (d.N + 31) / 32);  // one N tile holds the whole spectrum row (N <= 128)
@@ -3498,12 +3502,12 @@ static bool launch_frame_fold(hipStream_t s, const GemmDesc &d, float *C, const 
     if (!ensure_dynamic_lds(fn, lds)) return false;
     // enough row tiles to fill the chip: one block walks all N tiles of its rows (span loaded once); else spread them
     const int64_t row_blocks = (int64_t)f.tiles * batch;
-    const int walk_env = getenv("BN_FRAME_WALK") ? atoi(getenv("BN_FRAME_WALK")) : -1;  // tests / experiments
+    const int walk_env = sw_int(sw::BN_FRAME_WALK);  // tests / experiments
     const bool walk = walk_env >= 0 ? walk_env != 0 : row_blocks >= 256;
     dim3 grid((unsigned)row_blocks, (walk || pair) ? 1u : (unsigned)((d.N + bn - 1) / bn));
     GemmDesc none{};
     if (pair) hipLaunchKernelGGL(frame_fold_kernel<true>, grid, dim3(128 * wn), lds, s, f, C, A, W, bias, *pair, C2, W2, bias2);
-    else if (env_int("BN_FRAMEH", 1) == 0 && ks == 1 && pre_v.n == 0)  // the round-3 form of the same launch (A/B; bit-identical)
+    else if (sw_int(sw::BN_FRAMEH) == 0 && ks == 1 && pre_v.n == 0)  // the round-3 form of the same launch (A/B; bit-identical)
         hipLaunchKernelGGL(frame_fold_kernel<false>, grid, dim3(128 * wn), lds, s, f, C, A, W, bias, none, nullptr, nullptr, nullptr);
     else if (ks == 2 && wn == 2) hipLaunchKernelGGL((frame_foldh_kernel<2, 2>), grid, dim3(512), lds, s, f, C, A, W, bias, pre_v);
     else if (ks == 2) hipLaunchKernelGGL((frame_foldh_kernel<3, 2>), grid, dim3(768), lds, s, f, C, A, W, bias, pre_v);
@@ -3646,7 +3650,7 @@ void launch_se_fc(hipStream_t s, const SeFcDesc &d, float *gate, float *hidden, 
     // the wide layers at batch 128 take 17 us instead of 21) -- but with four samples' accumulators there is no room to
     // keep as many weight loads in flight, a launch at batch 32 takes 15 us instead of 9.5, and with four contexts the
     // two cancel (55.2 - 56.1 k against 55.6 k segments/s, one box): kept as a tested option, not the default
-    const int force_g = getenv("BN_SEFC_G") ? atoi(getenv("BN_SEFC_G")) : 0;  // (read per call: the tests flip it)
+    const int force_g = sw_int(sw::BN_SEFC_G);  // (read per call: the tests flip it)
     const int G = force_g == 4 ? 4 : 1;
     const int64_t groups = (batch + G - 1) / G;
     // blocks per group: one per 256-channel slice, capped so that the whole launch stays near two blocks per CU
@@ -3710,7 +3714,7 @@ void launch_mbconv(hipStream_t s, const MbDesc &d, float *out, const float *in, 
     // four waves per CU): its eight waves overlap the matrix-core and vector phases inside the block (47 -> 40 us).
     // Where two or more plain blocks fit, those already overlap each other and the plain kernel is faster.
     // BN_MBPIPE=0 never, =1 always (results are bit-identical either way).
-    const int pipe_mode = getenv("BN_MBPIPE") ? atoi(getenv("BN_MBPIPE")) : -1;  // read per launch (launches are captured once per graph)
+    const int pipe_mode = sw_int(sw::BN_MBPIPE);  // read per launch (launches are captured once per graph)
     size_t plds = mbconv_pipe_lds_bytes(d);
     if (tail.on) plds = std::max(plds, se_tail_lds_bytes(tail.se));
     const bool pipe = pipe_mode == 1 || (pipe_mode == -1 && mbconv_lds_bytes(d) > 80 * 1024);

@@ -31,6 +31,7 @@
 #include "capi_internal.h"
 #include "hip_gate.h"
 #include "live.h"
+#include "switches.h"
 
 namespace {
 
@@ -531,8 +532,7 @@ bn_status create_pool(int32_t device, int32_t n_sources, int32_t format, size_t 
     l->S = segment_samples;
     l->step = step_samples;
     l->R = ring_samples;
-    const char *mode = getenv("BN_LIVE_SCATTER");
-    l->copy_mode = mode && strcmp(mode, "copy") == 0;
+    l->copy_mode = bn::sw_is(bn::sw::BN_LIVE_SCATTER, "copy");
     l->src.resize((size_t)n_sources);
     l->touched.assign((size_t)n_sources, -1);
     if (src_rates) {

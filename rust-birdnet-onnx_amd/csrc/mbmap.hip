@@ -438,12 +438,12 @@ inline bool mm_al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15
 // 68.7 k, a quarter: 69.0 k) and one launch alone loses 30 % (160 -> 209 us for the ten launches; a third: 255 us) -- so the share is 2
 // as soon as a second live context exists on the device (capi.cpp counts them; BN_MBMAP_SHARE=n fixes it, 1 = the latency form).
 int mbmap_chunks_per_block(const MbDesc &d, const MbmapShape &sh, int64_t batch) {
-    const int force = getenv("BN_MBMAP2_NCH") ? atoi(getenv("BN_MBMAP2_NCH")) : 0;
+    const int force = sw_int(sw::BN_MBMAP2_NCH);
     const int nc = (!d.map_ws && (sh.cfg == 1 || sh.cfg == 3)) ? 64 : 32;
     const int chunks = (d.C + nc - 1) / nc;
     if (force > 0) return std::min(force, chunks);
-    const int share_env = getenv("BN_MBMAP_SHARE") ? atoi(getenv("BN_MBMAP_SHARE")) : 0;
-    const int share = share_env > 0 ? share_env : std::min(device_context_count(), 2);
+    const int share_env = sw_int(sw::BN_MBMAP_SHARE);
+    const int share = share_env > 0 ? share_env : (device_shared() ? 2 : 1);
     const int64_t ncu = std::max<int64_t>(1, device_cu_count() / share);
     return (int)std::max<int64_t>(1, std::min<int64_t>(chunks, (chunks * batch * sh.bands + ncu - 1) / ncu));
 }
@@ -482,7 +482,7 @@ bool launch_mbmap(hipStream_t s, const MbDesc &d, float *out, const float *in, c
     if (nsw && nsw != mbmap_b3_steps(d, sh)) return false;
     if (d.map_ws) return d.map_ws == mbmap_ws_steps(d, sh) && mm_al16(in) && launch_mbmap_ws(s, d, out, in, w1, b1, w2, b2, gap, batch, mbmap_chunks_per_block(d, sh, batch));
     MbDesc dd = d;
-    dd.dbg = getenv("BN_MM_DBG") ? atoi(getenv("BN_MM_DBG")) : 0;
+    dd.dbg = sw_int(sw::BN_MM_DBG);
     const int nch = mbmap_chunks_per_block(d, sh, batch);
     const int nst = nsw * (sh.cfg >= 3 ? 2 : 1);
     const uint32_t inv_ch = (uint32_t)(((uint64_t)1 << 32) / (uint64_t)(sh.cin_pad / 4)) + 1u;  // slot -> row of the swizzled copies

@@ -1,6 +1,6 @@
 // Shape rules the planner (engine.cpp, host C++) and the launchers (*.hip) must agree on: which kernel a descriptor may
 // take and how much LDS that kernel carves up for it.  They are pure functions of per-sample quantities (and of the
-// documented BN_* switches, read per call because the tests flip them), defined ONCE here and included by both sides --
+// BN_* switches, every one a row of the table in switches.h, read per call because the tests flip them), defined ONCE here and included by both sides --
 // so the host-only sanitizer build of the planner (tools/asan_plan.cpp, tests/test_planner_sanitizers.py) links without
 // any HIP object and without restating a rule.
 #pragma once
@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "switches.h"
 
 #if defined(__HIPCC__)
 #define BN_HD __host__ __device__
@@ -22,10 +23,6 @@
 namespace bn {
 
 inline bool ptr_aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-inline int env_int(const char *name, int dflt) {
-    const char *e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
 
 // ---- tiled GEMM family (kernels.hip) ------------------------------------------------------------------------------
 constexpr int GEMM_BK_RULE = 32, GEMM_LD_RULE = GEMM_BK_RULE + 4, FRAME_BM_RULE = 64;
@@ -33,7 +30,7 @@ constexpr int GEMM_BK_RULE = 32, GEMM_LD_RULE = GEMM_BK_RULE + 4, FRAME_BM_RULE 
 // Folded framing GEMM from an LDS-resident signal span (frame_fold_kernel): per-sample quantities and, when given, the
 // filter pointer's alignment.  BN_FRAMELDS=0 disables.
 inline bool frame_fold_shape_ok(const GemmDesc &d, const float *W) {
-    if (env_int("BN_FRAMELDS", 1) == 0) return false;
+    if (sw_int(sw::BN_FRAMELDS) == 0) return false;
     if (d.has_res || d.has_scale || d.act != ACT_NONE || d.K % GEMM_BK_RULE || d.fold_n != 2 * d.K || d.K % 4 || (W && !ptr_aligned16(W))) return false;
     if (d.lda <= 0 || d.lda > 4096 || d.rows < 32 || d.c_bs < 0) return false;
     return true;
@@ -66,10 +63,10 @@ inline size_t frame_fold2q_lds_bytes(const GemmDesc &d) {
     const int64_t span = (int64_t)31 * d.lda + d.fold_n + 4;
     return (size_t)(((span + 3) & ~3) + 2 * d.K) * sizeof(float) + (size_t)2 * 6 * 32 * 80;
 }
-inline bool frame_fold2q_ok(const GemmDesc &d) { return env_int("BN_FRAME2_B3", 1) != 0 && env_int("BN_GEMM3", 2) != 0 && frame_fold2q_lds_bytes(d) <= 80 * 1024; }
-inline bool frame_fold2p_ok(const GemmDesc &d) { return env_int("BN_FRAME2_WPK", 1) != 0 && frame_fold2p_lds_bytes(d) <= 80 * 1024; }
+inline bool frame_fold2q_ok(const GemmDesc &d) { return sw_int(sw::BN_FRAME2_B3) != 0 && sw_int(sw::BN_GEMM3) != 0 && frame_fold2q_lds_bytes(d) <= 80 * 1024; }
+inline bool frame_fold2p_ok(const GemmDesc &d) { return sw_int(sw::BN_FRAME2_WPK) != 0 && frame_fold2p_lds_bytes(d) <= 80 * 1024; }
 inline bool frame_fold2_shape_ok(const GemmDesc &d, const float *W) {
-    if (env_int("BN_FRAMELDS", 1) == 0 || env_int("BN_CONVFOLD2", 1) == 0) return false;
+    if (sw_int(sw::BN_FRAMELDS) == 0 || sw_int(sw::BN_CONVFOLD2) == 0) return false;
     if (d.fold != 2 || d.has_res || d.has_scale || d.act != ACT_NONE || d.npost || d.out_strided || d.se_inline) return false;
     if (d.fold_n < 256 || d.fold_n % 128 || d.K != d.fold_n / 4 + GEMM_BK_RULE || (W && !ptr_aligned16(W))) return false;
     if (d.N % 32 || d.N < 64 || d.N > 160 || d.fold_ne % 32 || d.fold_ne < 0 || d.fold_ne > d.N) return false;
@@ -83,7 +80,7 @@ inline bool frame_fold2_shape_ok(const GemmDesc &d, const float *W) {
 // waves stage the second product's filter rows and run its epilogue with the CU to themselves, 68.4 us against 50 + 19 at batch 32 and
 // 63 against 56 us of marginal cost, where the separate launch spreads the same work over the chip beside the other contexts' kernels
 inline bool frame_fold_pair_ok(const GemmDesc &d, const GemmDesc &d2) {
-    if (env_int("BN_FRAMEPAIR", 0) != 1) return false;
+    if (sw_int(sw::BN_FRAMEPAIR) != 1) return false;
     if (!d.fold || !frame_fold_shape_ok(d, nullptr)) return false;
     if (d.N > 128 || d.ldc != d.N) return false;
     const int wn = std::max(2, (d.N + 31) / 32);
@@ -116,7 +113,7 @@ inline size_t gemm_dma_lds_bytes(const GemmDesc &d, int mtw, int ntw, int wm, in
 // which block family the LDS-DMA kernel would take for this GEMM (0 = not eligible; 1 / 2: one tile per block, 64- / 48-row tiles;
 // 3: the streaming form): per-sample quantities only
 inline int gemm_dma_shape(const GemmDesc &d) {
-    const int mode = env_int("BN_GEMMDMA", 1);
+    const int mode = sw_int(sw::BN_GEMMDMA);
     if (mode == 0) return 0;
     if (d.fold || d.npost || d.out_strided || d.lda != d.K || d.K % 16 || d.K < 32 || d.N % 4 || d.N < 16 || !gemm_dma_act_ok(d.act)) return 0;
     if (d.ldc % 4 || d.c_bs % 4 || d.a_bs % 4 || (d.has_res && (d.ldr % 4 || d.r_bs % 4)) || (d.has_scale && d.s_bs % 4)) return 0;
@@ -129,14 +126,14 @@ inline int gemm_dma_shape(const GemmDesc &d) {
     // the tiled kernel spends 17 - 27 vector instructions per matrix instruction on them, and at four contexts every
     // vector instruction is taken from the budget the other contexts' matrix work needs (BN_GEMMDMA_SMALLN=0 keeps
     // them on the tiled kernel)
-    const bool small_n = d.N <= 32 && d.has_scale && env_int("BN_GEMMDMA_SMALLN", 1) != 0;
+    const bool small_n = d.N <= 32 && d.has_scale && sw_int(sw::BN_GEMMDMA_SMALLN) != 0;
     // Round 4: the expand convs of the late stages (K 64 .. 127 here, N >= 128, no gate, no residual) CAN take the streaming form of the
     // kernel (gemm_dma_stream_kernel: a block walks consecutive row tiles, its ring never drains) -- family 3.  Opt-in (BN_GEMMSTREAM=1):
     // measured EQUAL to the tiled kernel on these shapes (BirdNET v3.0, K = 112 -> N = 672: 37.4 - 38.0 against 37.5 us at batch 64, 125
     // against 124 us at batch 256, i.e. 79 TF/s either way; K = 80 -> 480: 76 against 82 us at batch 256, 26.0 against 25.6 at 64) --
     // removing the per-tile prologue does not move a launch that already runs at the rate every f32-MFMA kernel of this library
     // reaches at saturation.  The default plan is unchanged (and so are its bits).
-    if (env_int("BN_GEMMSTREAM", 0) != 0 && !d.has_scale && !d.has_res && !d.se_inline && d.K >= 64 && d.K < 128 && d.N >= 128 && d.rows % 32 == 0) return 3;
+    if (sw_int(sw::BN_GEMMSTREAM) != 0 && !d.has_scale && !d.has_res && !d.se_inline && d.K >= 64 && d.K < 128 && d.N >= 128 && d.rows % 32 == 0) return 3;
     if (mode != 2 && d.K < 128 && !small_n) return 0;
     if (d.rows % 32 == 0) return 1;  // 64- or 32-row tiles x up to 128 channels, waves along the rows
     if (d.rows % 48 == 0) return 2;  // 48-row tiles x 32 / 64 / 128 channels, waves along the channels
@@ -148,7 +145,7 @@ inline int gemm_dma_shape(const GemmDesc &d) {
 // for this layer would not fit the LDS: the tile follows the batch, so "fall back to one slice for the big tile only"
 // would make a segment's bits depend on its batch (gated layers with K > 3072).
 inline int gemm_dma_kslices(const GemmDesc &d, int se_cr = 0) {
-    const int force = env_int("BN_GEMMDMA_KS", 0);
+    const int force = sw_int(sw::BN_GEMMDMA_KS);
     int ks = (force == 1 || force == 2) ? force : (d.K >= 192 ? 2 : 1);
     if (ks == 2) {
         const size_t cap = 156 * 1024;
@@ -158,6 +155,10 @@ inline int gemm_dma_kslices(const GemmDesc &d, int se_cr = 0) {
     }
     return ks;
 }
+
+// blocks a big tile must give before the launchers of both LDS-DMA GEMMs (gemm_dma.hip, gemm_dma3.hip) take it: 64 for a launch that has
+// the device to itself, 1 on a shared device (the efficient tile always, +0.7 %); BN_GEMMDMA_MINBLOCKS moves the line
+inline int64_t gemm_dma_min_blocks() { return sw_is_set(sw::BN_GEMMDMA_MINBLOCKS) ? sw_i64(sw::BN_GEMMDMA_MINBLOCKS) : (device_shared() ? 1 : 64); }
 
 // ---- the same GEMMs on the bf16 matrix pipe with f32-complete products (gemm_dma3.hip, round 5) ------------------------------------
 // bytes of LDS of a (tile, K-slice count, ring depth) configuration: activations f32 (128 B per row and stage), weights three bf16 planes
@@ -172,7 +173,7 @@ inline size_t gemm_dma3_lds_bytes(const GemmDesc &d, int mtw, int ntw, int wm, i
 // K slices of the layer (they enter the summation order: a property of the SHAPE, never of the batch): deep products run as two
 // interleaved slices through rings of TWO stages each (three would not fit the widest tile), unless even that does not fit
 inline int gemm_dma3_kslices(const GemmDesc &d, int se_cr = 0) {
-    const int force = env_int("BN_GEMM3_KS", 0);
+    const int force = sw_int(sw::BN_GEMM3_KS);
     int ks = (force == 1 || force == 2) ? force : (d.K >= 192 ? 2 : 1);
     if (ks == 2) {
         const size_t cap = 156 * 1024;
@@ -183,7 +184,7 @@ inline int gemm_dma3_kslices(const GemmDesc &d, int se_cr = 0) {
 }
 // which GEMMs take the form: every one-tile-per-block LDS-DMA shape (BN_GEMM3=0 keeps the exact-f32 kernel)
 inline bool gemm_dma3_wanted(const GemmDesc &d) {
-    if (env_int("BN_GEMM3", 1) == 0 || d.w3) return false;
+    if (sw_int(sw::BN_GEMM3) == 0 || d.w3) return false;
     const int shape = gemm_dma_shape(d);
     return shape == 1 || shape == 2;
 }
@@ -229,7 +230,7 @@ inline std::vector<float> pack_w3(const float *W, int64_t N, int64_t K) {
 // gives a block too few waves there, and those layers (the project convs of the large maps, N = 16 .. 48) are bound by their activation
 // traffic, not by the product.  Per-sample quantities only.
 inline bool gemm_b3_shape_ok(const GemmDesc &d) {
-    if (env_int("BN_GEMM3", 2) < 2) return false;
+    if (sw_int(sw::BN_GEMM3) < 2) return false;
     if (d.fold || d.npost || d.out_strided || d.se_inline || d.K % 8 || d.K < 32 || d.N % 4 || d.N <= 48 || !gemm_dma_act_ok(d.act)) return false;
     if (d.lda % 4 || d.lda < d.K || d.ldc % 4 || d.c_bs % 4 || d.a_bs % 4 || (d.has_res && (d.ldr % 4 || d.r_bs % 4)) || (d.has_scale && d.s_bs % 4)) return false;
     if (d.gap && !(gemm_gap_shape_ok(d) && d.rows == 48)) return false;
@@ -266,7 +267,7 @@ inline std::vector<float> pack_w3f(const float *W, int64_t N, int64_t K) {
 }
 
 // the largest channel count whose excite products a GEMM block computes for itself (BN_SEGEMM_MAXC; 0 = never)
-inline int gemm_dma_se_max_channels() { return env_int("BN_SEGEMM_MAXC", 768); }
+inline int gemm_dma_se_max_channels() { return sw_int(sw::BN_SEGEMM_MAXC); }
 
 // ---- tiled fused MBConv (kernels.hip) -----------------------------------------------------------------------------
 // dynamic LDS of mbconv_expand_dw_kernel for this shape
@@ -327,8 +328,8 @@ struct MbmapShape {
 };
 inline MbmapShape mbmap_shape(const MbDesc &d) {
     MbmapShape none, sh;
-    if (env_int("BN_MBMAP2", 1) == 0) return none;
-    const bool r4 = env_int("BN_MBMAP3", 0) != 0;
+    if (sw_int(sw::BN_MBMAP2) == 0) return none;
+    const bool r4 = sw_int(sw::BN_MBMAP3) != 0;
     if (d.k1 > 0 || !((d.k == 3 || d.k == 5) && (d.s == 1 || d.s == 2))) return none;
     if (d.Cin % 4 || d.Cin < 16 || d.C % 4 || d.in_bs % 4) return none;
     const int pad = (d.k - 1) / 2;  // the kernels are compiled for symmetric "same" padding
@@ -339,11 +340,11 @@ inline MbmapShape mbmap_shape(const MbDesc &d) {
     // round 5: a 32 x 8 map is walked transposed by DEFAULT where the banded wave-specialised kernel serves it (Perch: K = 96 / 136 -> 3 / 5
     // steps of 32; any K % 16 == 0 -- its fragment reads happen once per block, so no padded k for the bank pattern)
     const int nst_ws = (d.Cin + 31) / 32;
-    const bool ws_on = env_int("BN_MBMAP_WS", 1) != 0 && env_int("BN_MBMAP_WS_BANDS", 1) != 0 && env_int("BN_MBMAP_B3", 1) != 0 && env_int("BN_GEMM3", 2) != 0;
-    const bool ws_tr = !r4 && ws_on && d.W == 8 && d.H == 32 && d.Cin % 8 == 0 && nst_ws >= 3 && nst_ws <= 5 && env_int("BN_MBMAP_WS_TR", 1) != 0;
+    const bool ws_on = sw_int(sw::BN_MBMAP_WS) != 0 && sw_int(sw::BN_MBMAP_WS_BANDS) != 0 && sw_int(sw::BN_MBMAP_B3) != 0 && sw_int(sw::BN_GEMM3) != 0;
+    const bool ws_tr = !r4 && ws_on && d.W == 8 && d.H == 32 && d.Cin % 8 == 0 && nst_ws >= 3 && nst_ws <= 5 && sw_int(sw::BN_MBMAP_WS_TR) != 0;
     // ... and a 16 x 4 map with K in eight steps of 32 (Perch: K = 232) by its one-pixel-tile-per-wave form
     const bool ws_deep = !r4 && ws_on && d.W == 4 && d.H == 16 && d.Cin % 8 == 0 && d.Cin % 64 != 0 && nst_ws == 8 && d.s == 1 &&
-                         env_int("BN_MBMAP_WS_DEEP", 1) != 0;
+                         sw_int(sw::BN_MBMAP_WS_DEEP) != 0;
     if ((r4 && d.W < 16 && (d.H == 32 || d.H == 16)) || ws_tr || (ws_deep && d.W == 4)) { R = d.W; Wc = d.H; sh.tr = 1; }
     if (Wc % 4) return none;
     sh.cin_pad = (d.Cin + 15) & ~15;
@@ -371,7 +372,7 @@ inline MbmapShape mbmap_shape(const MbDesc &d) {
         if (mbmap_lds_bytes(p, 2, 1, 2, 2, 1) <= cap) sh.cfg = 6;
     } else if (ws_bands && R == 8 && Wc == 32) {
         sh.cfg = 5; sh.bands = 2;  // (mbmap_ws.hip: its LDS carve-up fits for every K it is compiled for; no padded k)
-    } else if (r4 && R == 8 && Wc == 32 && env_int("BN_MBMAP_BANDS", 1) != 0) {
+    } else if (r4 && R == 8 && Wc == 32 && sw_int(sw::BN_MBMAP_BANDS) != 0) {
         // rows whose length is 0 or 32 mod 64 floats (Perch: Cin = 96) would meet the fragment reads' bank pattern: one more k group
         // of zeros moves them into a class the compiled swizzle serves (96 -> 112: a sixth more expand work, still ahead of the
         // GEMM + depthwise pair it replaces)
@@ -389,7 +390,7 @@ inline int mbmap_config(const MbDesc &d) { return mbmap_shape(d).cfg; }
 // (Cin = 128 / 192 / 256).  BN_MBMAP_B3=0 (or BN_GEMM3=0) keeps the exact-f32 instruction.
 inline int mbmap_b3_steps(const MbDesc &d, const MbmapShape &sh) {
     if (!sh.cfg || sh.cfg > 4 || sh.tr || sh.bands != 1 || sh.cin_pad != d.Cin || d.Cin % 8) return 0;
-    if (env_int("BN_MBMAP_B3", 1) == 0 || env_int("BN_GEMM3", 2) == 0) return 0;
+    if (sw_int(sw::BN_MBMAP_B3) == 0 || sw_int(sw::BN_GEMM3) == 0) return 0;
     const int nst = (d.Cin + 31) / 32, ksp = sh.cfg >= 3 ? 2 : 1;
     if (nst % ksp) return 0;
     const int nsw = nst / ksp;
@@ -417,16 +418,16 @@ inline std::vector<float> pack_mbmap_w3f(const float *w, int64_t C, int64_t K) {
 // same phase, chunks of 32 channels): 32-deep steps of the whole product, or 0.  BN_MBMAP_WS=0 keeps mbmap.hip; BN_MBMAP_WS_SMALL=0 keeps it for
 // the 3 x 16 / 4 x 16 maps only.
 inline int mbmap_ws_steps(const MbDesc &d, const MbmapShape &sh) {
-    if (env_int("BN_MBMAP_WS", 1) == 0 || env_int("BN_MBMAP_B3", 1) == 0 || env_int("BN_GEMM3", 2) == 0) return 0;
+    if (sw_int(sw::BN_MBMAP_WS) == 0 || sw_int(sw::BN_MBMAP_B3) == 0 || sw_int(sw::BN_GEMM3) == 0) return 0;
     const int nst = (d.Cin + 31) / 32;
     if (sh.cfg == 6)  // 4 x 16 (Perch: transposed 16 x 4) with eight steps: one pixel tile per expand wave
-        return (sh.bands == 1 && sh.cin_pad % 16 == 0 && nst == 8 && d.s == 1 && d.Cin % 64 != 0 && env_int("BN_MBMAP_WS_DEEP", 1) != 0) ? nst : 0;
+        return (sh.bands == 1 && sh.cin_pad % 16 == 0 && nst == 8 && d.s == 1 && d.Cin % 64 != 0 && sw_int(sw::BN_MBMAP_WS_DEEP) != 0) ? nst : 0;
     if (sh.cfg == 5)  // 8 x 32 in two bands of six rows: the 6 x 32 kernel per band
-        return (sh.bands == 2 && (sh.tr || sh.cin_pad == d.Cin) && sh.cin_pad % 16 == 0 && nst >= 3 && nst <= (sh.tr ? 5 : 4) && env_int("BN_MBMAP_WS_BANDS", 1) != 0 &&
-                (!sh.tr || env_int("BN_MBMAP_WS_TR", 1) != 0)) ? nst : 0;
+        return (sh.bands == 2 && (sh.tr || sh.cin_pad == d.Cin) && sh.cin_pad % 16 == 0 && nst >= 3 && nst <= (sh.tr ? 5 : 4) && sw_int(sw::BN_MBMAP_WS_BANDS) != 0 &&
+                (!sh.tr || sw_int(sw::BN_MBMAP_WS_TR) != 0)) ? nst : 0;
     if (mbmap_b3_steps(d, sh) == 0) return 0;
     if (sh.cfg <= 2) return nst;                                               // 6 x 32: 2 .. 4 steps (mbmap_b3_steps)
-    return (env_int("BN_MBMAP_WS_SMALL", 1) != 0 && (nst == 4 || nst == 6)) ? nst : 0;  // 3 x 16 / 4 x 16: Cin = 128 / 192
+    return (sw_int(sw::BN_MBMAP_WS_SMALL) != 0 && (nst == 4 || nst == 6)) ? nst : 0;  // 3 x 16 / 4 x 16: Cin = 128 / 192
 }
 // the same filters as three bf16 planes for mbmap_ws.hip, whose expand waves share their SIMD's vector ALU with the depthwise waves and
 // should not spend it on splitting filters: [tile][step][plane hi | mid | lo][lane (q, c)][8 bf16], element e of lane (q, c) = k
@@ -483,7 +484,7 @@ BN_HD inline StftLds stft_layout(const FftDesc &d, int nw, int slots) {
 // 16 waves x 512 slots where a frame fits 512 complex points (opt-in BN_STFT_NW=16: measured slower -- 128-register cap at
 // 16 waves: 156 B of scratch per lane; 74.6 vs 69.1 us), else 8 x 1024
 inline bool stft_wide(const FftDesc &d) {
-    if (env_int("BN_STFT_NW", 8) != 16) return false;
+    if (sw_int(sw::BN_STFT_NW) != 16) return false;
     return d.M <= 512 && d.tpb % (512 / d.M) == 0;
 }
 inline size_t stft_lds_bytes(const FftDesc &d, int /*nwaves*/) {

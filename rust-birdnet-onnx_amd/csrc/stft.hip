@@ -629,7 +629,7 @@ void launch_stft(hipStream_t s, const FftDesc &d, const StftPtrs &p, int64_t bat
         return;
     }
     FftDesc dd = d;
-    dd.dbg = getenv("BN_STFT_DBG") ? atoi(getenv("BN_STFT_DBG")) : 0;
+    dd.dbg = sw_int(sw::BN_STFT_DBG);
     // float4 span loads need 16-byte aligned tile starts (base pointer, batch stride, a tile's first sample) and must
     // not run past the sample row: the last chunk of a span is rounded up to 4 floats
     dd.a_vec4 = (reinterpret_cast<uintptr_t>(p.in) & 15u) == 0 && d.a_bs % 4 == 0 && ((int64_t)d.tpb * d.hop) % 4 == 0 &&

@@ -523,8 +523,8 @@ void launch_topk(hipStream_t s, const float *logits, int64_t rows, int64_t n, in
                  uint32_t *count, uint32_t *flags) {
     if (rows <= 0 || k <= 0 || n <= 0) return;
     // fast path needs k+1 lane maxima; BN_TOPK_EXACT=1 forces the exact heap kernel (tests)
-    if (flags && (k > 62 || n < 64 || getenv("BN_TOPK_EXACT"))) flags = nullptr;
-    if (flags && n <= 64 * 112 && !getenv("BN_TOPK_TWOPASS"))
+    if (flags && (k > 62 || n < 64 || sw_present(sw::BN_TOPK_EXACT))) flags = nullptr;
+    if (flags && n <= 64 * 112 && !sw_present(sw::BN_TOPK_TWOPASS))
         hipLaunchKernelGGL(topk_fast_reg_kernel<112>, dim3((unsigned)rows), dim3(64), 0, s, logits, n, (uint32_t)k, has_min, min_conf, k_stride, idx,
                            conf, count, flags);
     else if (flags)
