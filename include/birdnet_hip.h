@@ -449,6 +449,86 @@ bn_status bn_index_search_ids(bn_index *x, const uint64_t *query_ids, size_t n_q
                               size_t top_m, size_t m_stride, uint64_t *id_out, float *score_out, uint32_t *count_out);
 
 /*
+ * Classifier heads: an immutable linear head z[c] = sum_k W[c][k] * x[k] + b[c] over a model's embedding, resident on one
+ * device (label a few hundred search hits, fit a head on their embeddings, run it on everything that arrives from then on).
+ * The reference exposes embeddings and has neither search nor heads; the contract is what a float64 evaluation of the
+ * formulas below returns, up to the stated f32 bounds.
+ *
+ *   Logit          one f32 fmaf chain over k in a fixed order (fixed by dim alone), then the bias added.  Its bits depend only
+ *                  on dim, the row, that class's weights and bias, and the flag: not on the batch size, the row's position,
+ *                  how many other classes the head has, or the entry point (a step or bn_head_apply_host).  Against float64
+ *                  |z - z64| <= 2 * (dim + 8) * 2^-24 * (sum_k |W[c][k] * xh[k]| + |b[c]|), xh the input (normalised in
+ *                  float64 under BN_HEAD_L2NORM): the worst case of an f32 chain of that length plus an f32 norm.
+ *   L2NORM         the index's rule: xh = x / sqrt(sum x^2); a row with zero norm, a non-finite element or an overflowing sum
+ *                  of squares becomes zeros, so its logits equal the bias.
+ *   Step           bn_ctx_attach_head makes every later bn_step_device / bn_step_windows / bn_step_live of the context also
+ *                  run the head on that step's embedding rows, on the context's stream, after the plan and the step's own
+ *                  top-K and outside the captured plan graph (capture_fallbacks stays 0), and rank the head logits with the
+ *                  step's top-K kernel under the attached top_k / has_min / min_conf (top_k_predictions semantics, bit-identical
+ *                  to bn_topk_host on the same logits).  Logits and packed rows reach pinned buffers as the step's own do;
+ *                  bn_step_head_results is valid after bn_ctx_synchronize, until the next step.  The step's own outputs are
+ *                  unchanged, bit for bit.  bn_infer*, tickets (bn_infer_submit / bn_infer_collect) and bn_group_* carry no
+ *                  head results.
+ *   Fit            with a_c = [W_c, b_c] and xt = [xh, 1], bn_head_fit minimises over all classes at once
+ *                    L(A) = (1/n) sum_i sum_c [ -pw_c y_ic log s(a_c.xt_i) - (1 - y_ic) log(1 - s(a_c.xt_i)) ] + (l2/2) |A|^2
+ *                  (s the logistic function; the bias is regularised with the same l2).  L is l2-strongly convex, so
+ *                  L(A) - L* <= |grad L(A)|^2 / (2 l2): this right-hand side is the certificate.  The fit stops when its own
+ *                  f32 certificate is <= tol or after max_iters evaluations of (L, grad L); after max_iters it still returns
+ *                  the head, with converged = 0.  Deterministic: fixed reduction orders, no floating-point atomics; two fits
+ *                  of the same inputs give the same bits.  A class with no positives, or no negatives, is legal.
+ *   Refusals       BN_ERR_INVALID_ARG with a message, nothing changed: a model without embeddings, dim != embedding_dim, a
+ *                  head on another device, a top_k the step's top-K refuses for n_classes (0, or beyond its on-chip heap),
+ *                  labels other than 0/1, l2 / tol / pos_weight not positive and finite, n == 0, an id >= bn_index_size or one
+ *                  whose stored row is all zeros, dim outside 1..8192, n_classes outside 1..4096, NULL where data is required.
+ *                  Without a gfx950 device create, fit and apply return BN_ERR_NO_DEVICE.
+ *   Lifetime       a context that attached a head keeps it alive: bn_head_free and bn_ctx_destroy may come in either order.
+ *   Threading      a head is immutable and may be attached to any number of contexts; bn_head_apply_host / bn_head_read take
+ *                  one thread at a time per head.
+ */
+typedef struct bn_head bn_head;
+#define BN_HEAD_L2NORM 1u /* the head's input is x / sqrt(sum x^2), by the index's normalisation rule */
+/* W [n_classes * dim] row-major, bias [n_classes] or NULL (= 0); flags: 0 or BN_HEAD_L2NORM */
+bn_status bn_head_create(int32_t device, size_t dim, size_t n_classes, const float *W, const float *bias, uint32_t flags,
+                         bn_head **out);
+void bn_head_free(bn_head *h);
+size_t bn_head_dim(const bn_head *h);
+size_t bn_head_classes(const bn_head *h);
+uint32_t bn_head_flags(const bn_head *h);
+/* the head's parameters back on the host: W_out [n_classes * dim], bias_out [n_classes] (either may be NULL) */
+bn_status bn_head_read(const bn_head *h, float *W_out, float *bias_out);
+/* the head on n host rows [n * dim] -> logits_out [n * n_classes] */
+bn_status bn_head_apply_host(const bn_head *h, const float *rows, size_t n, float *logits_out);
+
+typedef struct bn_head_fit_opts { /* zero / NULL fields take the defaults in brackets */
+    float l2;                /* lambda > 0 [1e-3] */
+    float tol;               /* stop when the certificate <= tol [1e-6] */
+    uint32_t max_iters;      /* [2000] */
+    uint32_t flags;          /* BN_HEAD_L2NORM */
+    const float *pos_weight; /* [n_classes] > 0, or NULL = 1 */
+} bn_head_fit_opts;
+typedef struct bn_head_fit_report {
+    uint32_t iters;
+    int32_t converged;
+    double loss;
+    double certificate;
+} bn_head_fit_report;
+/* fit on n host rows [n * dim] with labels [n * n_classes] (0 / 1); opts may be NULL (all defaults), report may be NULL.
+ * Both structs are read / written through the caller's struct size, as bn_model_get_cost does. */
+bn_status bn_head_fit(int32_t device, size_t dim, size_t n_classes, const float *rows, const uint8_t *labels, size_t n,
+                      const bn_head_fit_opts *opts, size_t opts_size, bn_head **out, bn_head_fit_report *report,
+                      size_t report_size);
+/* training rows taken from an index by id, device to device, used as stored; the head gets BN_HEAD_L2NORM */
+bn_status bn_head_fit_index(bn_index *x, const uint64_t *ids, const uint8_t *labels, size_t n, size_t n_classes,
+                            const bn_head_fit_opts *opts, size_t opts_size, bn_head **out, bn_head_fit_report *report,
+                            size_t report_size);
+/* every later bn_step_device / bn_step_windows / bn_step_live on c also runs the head on that step's embedding rows;
+ * h == NULL detaches (the other arguments are then ignored) */
+bn_status bn_ctx_attach_head(bn_ctx *c, bn_head *h, size_t top_k, int32_t has_min, float min_conf);
+/* pinned host views of the last step's head results: logits [batch, n_classes], idx / conf [batch, k_stride], count [batch] */
+bn_status bn_step_head_results(const bn_ctx *c, const float **logits, const uint32_t **idx, const float **conf,
+                               const uint32_t **count, size_t *k_stride, size_t *n_classes);
+
+/*
  * Live ingest: a device-resident pool of per-source ring buffers for continuous audio (many recorders, each producing a
  * window every `step` seconds).  Callers push PCM as it arrives, in the storage format (i16: half the PCIe bytes, and no
  * overlap sample crosses the bus twice); bn_step_live batches the ready windows of ALL sources into one context batch, cut on

@@ -54,6 +54,8 @@ ENGINE_SYMBOLS = [
     "bn_group_uses_rccl", "bn_group_get_stats", "bn_shard_range", "bn_group_analyze_recording", "bn_group_last_error", "bn_recording_create_resampled", "bn_resample_table", "bn_recording_read_f32", "bn_last_error",
     "bn_index_create", "bn_index_free", "bn_index_size", "bn_index_dim", "bn_index_add_host", "bn_index_add_ctx", "bn_index_read",
     "bn_index_search", "bn_index_search_ids",
+    "bn_head_create", "bn_head_free", "bn_head_dim", "bn_head_classes", "bn_head_flags", "bn_head_read", "bn_head_apply_host",
+    "bn_head_fit", "bn_head_fit_index", "bn_ctx_attach_head", "bn_step_head_results",
     "bn_live_create", "bn_live_free", "bn_live_push", "bn_live_push_many", "bn_live_close", "bn_live_reset", "bn_live_ready",
     "bn_live_room", "bn_live_event_count", "bn_live_read_window", "bn_step_live",
     "bn_live_create_rates", "bn_live_resampled_samples", "bn_live_source_rate",
@@ -99,6 +101,15 @@ class BnCtxStats(C.Structure):
                 ("input_copies", C.c_uint64)]
 
 
+class BnHeadFitOpts(C.Structure):
+    _fields_ = [("l2", C.c_float), ("tol", C.c_float), ("max_iters", C.c_uint32), ("flags", C.c_uint32), ("pos_weight", C.POINTER(C.c_float))]
+
+
+class BnHeadFitReport(C.Structure):
+    _fields_ = [("iters", C.c_uint32), ("converged", C.c_int32), ("loss", C.c_double), ("certificate", C.c_double)]
+
+
+BN_HEAD_L2NORM = 1
 BN_ABI_VERSION = 2  # include/birdnet_hip.h
 
 
@@ -182,6 +193,18 @@ def _load() -> C.CDLL:
         "bn_index_read": (i32, [vp, C.c_uint64, sz, f32p]),
         "bn_index_search": (i32, [vp, f32p, sz, sz, sz, C.POINTER(C.c_uint64), f32p, u32p]),
         "bn_index_search_ids": (i32, [vp, C.POINTER(C.c_uint64), sz, C.c_int64, sz, sz, C.POINTER(C.c_uint64), f32p, u32p]),
+        "bn_head_create": (i32, [i32, sz, sz, f32p, f32p, C.c_uint32, C.POINTER(vp)]),
+        "bn_head_free": (None, [vp]),
+        "bn_head_dim": (sz, [vp]),
+        "bn_head_classes": (sz, [vp]),
+        "bn_head_flags": (C.c_uint32, [vp]),
+        "bn_head_read": (i32, [vp, f32p, f32p]),
+        "bn_head_apply_host": (i32, [vp, f32p, sz, f32p]),
+        "bn_head_fit": (i32, [i32, sz, sz, f32p, C.POINTER(C.c_uint8), sz, C.POINTER(BnHeadFitOpts), sz, C.POINTER(vp), C.POINTER(BnHeadFitReport), sz]),
+        "bn_head_fit_index": (i32, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint8), sz, sz, C.POINTER(BnHeadFitOpts), sz, C.POINTER(vp),
+                                    C.POINTER(BnHeadFitReport), sz]),
+        "bn_ctx_attach_head": (i32, [vp, vp, sz, i32, C.c_float]),
+        "bn_step_head_results": (i32, [vp, C.POINTER(f32p), C.POINTER(u32p), C.POINTER(f32p), C.POINTER(u32p), C.POINTER(sz), C.POINTER(sz)]),
         "bn_live_create": (i32, [i32, i32, i32, sz, sz, sz, C.POINTER(vp)]),
         "bn_live_create_rates": (i32, [i32, i32, i32, sz, sz, sz, C.c_uint32, u32p, C.c_uint32, C.POINTER(vp)]),
         "bn_live_resampled_samples": (sz, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, i32]),
@@ -881,6 +904,25 @@ class Context:
             raise EngineError(st)
         return src[:n.value].copy(), win[:n.value].copy()
 
+    def attach_head(self, head: Optional["Head"], top_k: int = 10, min_confidence: Optional[float] = None):
+        """bn_ctx_attach_head: every later step of this context also runs `head` on the step's embedding rows (None detaches)."""
+        st = lib.bn_ctx_attach_head(self._h, None if head is None else head._h, top_k, 0 if min_confidence is None else 1,
+                                    C.c_float(min_confidence or 0.0))
+        if st:
+            raise EngineError(st)
+        self._head = head
+
+    def step_head_results(self, batch: int):
+        """(head logits [batch, n_classes], idx, conf, count) of the last step, after synchronize()."""
+        lg, ix, cf, ct = C.POINTER(C.c_float)(), C.POINTER(C.c_uint32)(), C.POINTER(C.c_float)(), C.POINTER(C.c_uint32)()
+        ks, nc = C.c_size_t(), C.c_size_t()
+        st = lib.bn_step_head_results(self._h, C.byref(lg), C.byref(ix), C.byref(cf), C.byref(ct), C.byref(ks), C.byref(nc))
+        if st:
+            raise EngineError(st)
+        k, n = ks.value, nc.value
+        return (np.ctypeslib.as_array(lg, shape=(batch, n)).copy(), np.ctypeslib.as_array(ix, shape=(batch, k)).copy(),
+                np.ctypeslib.as_array(cf, shape=(batch, k)).copy(), np.ctypeslib.as_array(ct, shape=(batch,)).copy())
+
     def time_kernels(self, batch: int):
         cap = 1024
         names = C.create_string_buffer(cap * BN_NAME_LEN)
@@ -1048,6 +1090,15 @@ class Index:
             raise EngineError(st)
         return ids, scores, counts
 
+    def search_head(self, head: "Head", top_m: int):
+        """Per class, the top_m stored rows by head logit: bn_index_search with W_c as the query.  For a stored (unit) row
+        logit = cosine * |W_c| + b_c, so the ranking does not depend on the query's positive scale or on the bias; returns
+        (ids, logits, counts) with the cosine converted back to that logit in float64 (a class whose W_c is zero has count 0)."""
+        w, b = head.read()
+        ids, cos, counts = self.search(w, top_m)
+        norm = np.sqrt((w.astype(np.float64) ** 2).sum(axis=1))
+        return ids, cos.astype(np.float64) * norm[:, None] + b.astype(np.float64)[:, None], counts
+
     def search_ids(self, ids, top_m: int, exclude_radius: int = -1, m_stride: Optional[int] = None):
         """Query by example: the stored rows `ids` are the queries; rows within exclude_radius of a query's id are skipped."""
         qi = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
@@ -1059,6 +1110,112 @@ class Index:
         if st:
             raise EngineError(st)
         return out_ids, scores, counts
+
+def _fit_opts(n_classes: int, l2: float, tol: float, max_iters: int, l2norm: bool, pos_weight):
+    pw = None
+    if pos_weight is not None:
+        pw = np.ascontiguousarray(pos_weight, dtype=np.float32).reshape(n_classes)
+    o = BnHeadFitOpts(l2, tol, max_iters, BN_HEAD_L2NORM if l2norm else 0, None if pw is None else pw.ctypes.data_as(C.POINTER(C.c_float)))
+    return o, pw  # pw must outlive the call
+
+
+class Head:
+    """bn_head: an immutable linear classifier head over embeddings, resident on one device.  `Head(device, W, bias)` from host
+    weights, `Head.fit(...)` / `Head.fit_index(...)` fitted on the device; `apply(rows)` on host rows, `Context.attach_head` for
+    every step of a context.  A fitted head carries `report` = {iters, converged, loss, certificate}."""
+
+    def __init__(self, device: int, W, bias=None, l2norm: bool = False, _handle=None):
+        self.report = None
+        if _handle is not None:
+            self._h = _handle
+            return
+        w = np.ascontiguousarray(W, dtype=np.float32)
+        if w.ndim != 2:
+            raise ValueError("W must be [n_classes, dim]")
+        b = None if bias is None else np.ascontiguousarray(bias, dtype=np.float32).reshape(w.shape[0])
+        f32p = C.POINTER(C.c_float)
+        h = C.c_void_p()
+        st = lib.bn_head_create(device, w.shape[1], w.shape[0], w.ctypes.data_as(f32p), None if b is None else b.ctypes.data_as(f32p),
+                                BN_HEAD_L2NORM if l2norm else 0, C.byref(h))
+        if st:
+            raise EngineError(st)
+        self._h = h
+
+    def __del__(self):
+        if getattr(self, "_h", None) and lib is not None:
+            lib.bn_head_free(self._h)
+            self._h = None
+
+    def close(self):
+        self.__del__()
+
+    @staticmethod
+    def _fitted(h, rep: BnHeadFitReport) -> "Head":
+        out = Head(0, None, _handle=h)
+        out.report = {"iters": int(rep.iters), "converged": bool(rep.converged), "loss": float(rep.loss), "certificate": float(rep.certificate)}
+        return out
+
+    @staticmethod
+    def fit(device: int, rows, labels, l2: float = 0.0, tol: float = 0.0, max_iters: int = 0, l2norm: bool = False, pos_weight=None) -> "Head":
+        """bn_head_fit: L2-regularised logistic regression of labels [n, n_classes] (0 / 1) on rows [n, dim]; zero options take
+        the library's defaults (l2 1e-3, tol 1e-6, max_iters 2000)."""
+        x = np.ascontiguousarray(rows, dtype=np.float32)
+        y = np.ascontiguousarray(labels, dtype=np.uint8)
+        if x.ndim != 2 or y.ndim != 2 or y.shape[0] != x.shape[0]:
+            raise ValueError("rows must be [n, dim] and labels [n, n_classes]")
+        o, pw = _fit_opts(y.shape[1], l2, tol, max_iters, l2norm, pos_weight)
+        h, rep = C.c_void_p(), BnHeadFitReport()
+        st = lib.bn_head_fit(device, x.shape[1], y.shape[1], x.ctypes.data_as(C.POINTER(C.c_float)), y.ctypes.data_as(C.POINTER(C.c_uint8)),
+                             x.shape[0], C.byref(o), C.sizeof(o), C.byref(h), C.byref(rep), C.sizeof(rep))
+        if st:
+            raise EngineError(st)
+        return Head._fitted(h, rep)
+
+    @staticmethod
+    def fit_index(index: "Index", ids, labels, l2: float = 0.0, tol: float = 0.0, max_iters: int = 0, pos_weight=None) -> "Head":
+        """bn_head_fit_index: the training rows are stored rows of `index`, taken by id on the device."""
+        qi = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+        y = np.ascontiguousarray(labels, dtype=np.uint8)
+        if y.ndim != 2 or y.shape[0] != qi.shape[0]:
+            raise ValueError("labels must be [len(ids), n_classes]")
+        o, pw = _fit_opts(y.shape[1], l2, tol, max_iters, True, pos_weight)
+        h, rep = C.c_void_p(), BnHeadFitReport()
+        st = lib.bn_head_fit_index(index._h, qi.ctypes.data_as(C.POINTER(C.c_uint64)), y.ctypes.data_as(C.POINTER(C.c_uint8)), qi.shape[0], y.shape[1],
+                                   C.byref(o), C.sizeof(o), C.byref(h), C.byref(rep), C.sizeof(rep))
+        if st:
+            raise EngineError(st)
+        return Head._fitted(h, rep)
+
+    @property
+    def dim(self) -> int:
+        return int(lib.bn_head_dim(self._h))
+
+    @property
+    def n_classes(self) -> int:
+        return int(lib.bn_head_classes(self._h))
+
+    @property
+    def l2norm(self) -> bool:
+        return bool(lib.bn_head_flags(self._h) & BN_HEAD_L2NORM)
+
+    def read(self):
+        """(W [n_classes, dim], bias [n_classes]) as stored on the device."""
+        w = np.empty((self.n_classes, self.dim), dtype=np.float32)
+        b = np.empty(self.n_classes, dtype=np.float32)
+        st = lib.bn_head_read(self._h, w.ctypes.data_as(C.POINTER(C.c_float)), b.ctypes.data_as(C.POINTER(C.c_float)))
+        if st:
+            raise EngineError(st)
+        return w, b
+
+    def apply(self, rows) -> np.ndarray:
+        """bn_head_apply_host: logits [n, n_classes] of host rows [n, dim]."""
+        x = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, self.dim)
+        out = np.empty((x.shape[0], self.n_classes), dtype=np.float32)
+        st = lib.bn_head_apply_host(self._h, x.ctypes.data_as(C.POINTER(C.c_float)), x.shape[0], out.ctypes.data_as(C.POINTER(C.c_float)))
+        if st:
+            raise EngineError(st)
+        return out
+
 
 class Live:
     """bn_live: a device-resident pool of per-source ring buffers for continuous audio.  Push int16 / float32 PCM as it arrives;

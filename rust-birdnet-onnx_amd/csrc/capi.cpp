@@ -180,6 +180,7 @@ struct bn_ctx {
     uint32_t *h_tk_idx = nullptr, *h_tk_cnt = nullptr;  // views into h_step for the last step
     float *h_tk_conf = nullptr;
     size_t step_k = 0;
+    bn::HeadAttach *head = nullptr;  // bn_ctx_attach_head: run after every step's own work (head.hip)
     // ---- asynchronous host-slice path (bn_infer_submit / bn_infer_collect): a ring of two batches per context.
     // Both slots own their device input, pinned input and pinned output buffers (allocated on first use), so a ticket
     // in flight shares nothing with the synchronous entry points (bn_infer_windows / bn_step_*) but the arena and the
@@ -716,6 +717,7 @@ void bn_ctx_destroy(bn_ctx *c) {
     if (c->counted) bn::device_context_count_add(c->model->device, -1);
     (void)bn::use_device(c->model->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
+    bn::head_detach(c->head);
     for (auto &kv : c->graphs) (void)gated::GraphExecDestroy(kv.second);
     if (c->d_arena) (void)gated::Free(c->d_arena);
     if (c->d_input) (void)gated::Free(c->d_input);
@@ -1306,8 +1308,42 @@ bn_status bn_step_device(bn_ctx *c, const float *d_pcm, size_t batch, size_t top
     c->h_tk_conf = reinterpret_cast<float *>(c->h_step + batch * k);
     c->h_tk_cnt = c->h_step + 2 * batch * k;
     c->step_k = k;
+    if (c->head) {
+        const OutputInfo &eo = p.outputs[c->model->cfg.embedding_output];
+        st = bn::head_step(c->head, c->stream, resolve(c, eo.ref, d_pcm), batch);
+        if (st != BN_OK) return st;
+    }
     if (sync) HIP_TRY(hipStreamSynchronize(c->stream));
     return BN_OK;
+}
+
+bn_status bn_ctx_attach_head(bn_ctx *c, bn_head *h, size_t top_k, int32_t has_min, float min_conf) {
+    if (!c) return fail(BN_ERR_INVALID_ARG, "null context");
+    const bn_model_config &cfg = c->model->cfg;
+    HIP_TRY(bn::use_device(c->model->device));
+    bn::HeadAttach *a = nullptr;
+    if (h) {
+        const bool has_emb = cfg.has_embedding && cfg.embedding_output >= 0 && c->pd->plan->outputs[cfg.embedding_output].computed;
+        bn_status st = bn::head_attach(h, c->model->device, has_emb, has_emb ? (size_t)c->pd->plan->outputs[cfg.embedding_output].row_elems : 0,
+                                       c->max_batch, top_k, has_min, min_conf, &a);
+        if (st != BN_OK) return st;
+    }
+    // the previous attachment's buffers may still be read by a step in flight
+    hipError_t e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        bn::head_detach(a);
+        return fail(BN_ERR_BACKEND, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
+    }
+    bn::head_detach(c->head);
+    c->head = a;
+    return BN_OK;
+}
+
+bn_status bn_step_head_results(const bn_ctx *c, const float **logits, const uint32_t **idx, const float **conf, const uint32_t **count, size_t *k_stride,
+                               size_t *n_classes) {
+    if (!c) return fail(BN_ERR_INVALID_ARG, "null context");
+    if (!c->head) return fail(BN_ERR_INVALID_ARG, "no head is attached to this context");
+    return bn::head_step_results(c->head, logits, idx, conf, count, k_stride, n_classes);
 }
 
 bn_status bn_step_results(const bn_ctx *c, const float **logits, const uint32_t **idx, const float **conf, const uint32_t **count, size_t *k_stride) {

@@ -1,4 +1,5 @@
-// What other translation units of the C ABI need of capi.cpp's private state (index.hip: bn_index_*).
+// What other translation units of the C ABI need of capi.cpp's private state (index.hip: bn_index_*; head.hip: bn_head_*) and
+// of each other.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -38,4 +39,21 @@ struct ResampleTable {
 // L, M and T alone (coef left empty): what the table would be, without building it
 ResampleTable resample_factors(uint32_t src_rate, uint32_t dst_rate, uint32_t zc);
 ResampleTable make_resample_table(uint32_t src_rate, uint32_t dst_rate, uint32_t zc);
+// index.hip -> head.hip (bn_head_fit_index): the stored rows of an index, every pending append waited for
+struct IndexRows {
+    int device = 0;
+    const float *slab = nullptr;   // [size, dpad], rows normalised, zero-padded to dpad (a multiple of 128)
+    const uint8_t *valid = nullptr;  // [size]: 0 for a row stored as zeros
+    size_t dim = 0, dpad = 0, size = 0;
+};
+bn_status index_rows(bn_index *x, IndexRows *out);
+// head.hip -> capi.cpp: a head attached to a context (its own result buffers; holds a reference to the head)
+struct HeadAttach;
+bn_status head_attach(bn_head *h, int device, bool has_embedding, size_t embedding_dim, size_t max_batch, size_t top_k, int32_t has_min,
+                      float min_conf, HeadAttach **out);
+void head_detach(HeadAttach *a);  // the context's stream must be idle
+// prep + apply + top-K + results to pinned memory, enqueued on the context's stream behind the step's own work
+bn_status head_step(HeadAttach *a, hipStream_t stream, const float *d_emb, size_t batch);
+bn_status head_step_results(const HeadAttach *a, const float **logits, const uint32_t **idx, const float **conf, const uint32_t **count,
+                            size_t *k_stride, size_t *n_classes);
 }  // namespace bn

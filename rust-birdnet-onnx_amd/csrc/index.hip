@@ -433,6 +433,20 @@ bn_status reserve_rows(const bn_index *x, size_t n) {
 
 }  // namespace
 
+bn_status bn::index_rows(bn_index *x, IndexRows *out) {
+    if (!x || !out) return set_last_error(BN_ERR_INVALID_ARG, "null index");
+    bn_status st = begin(x);
+    if (st != BN_OK) return st;
+    IDX_TRY(hipStreamSynchronize(x->stream));
+    out->device = x->device;
+    out->slab = x->slab;
+    out->valid = x->valid;
+    out->dim = x->dim;
+    out->dpad = x->dpad;
+    out->size = x->size;
+    return BN_OK;
+}
+
 extern "C" {
 
 bn_status bn_index_create(int32_t device, size_t dim, size_t capacity_rows, bn_index **out) {

@@ -20,7 +20,12 @@ OUT = os.path.join(ROOT, "bindings", "rust", "src", "ffi.rs")
 
 SCALARS = {"int32_t": "i32", "uint32_t": "u32", "int64_t": "i64", "uint64_t": "u64", "size_t": "usize", "float": "f32", "double": "f64",
            "char": "c_char", "void": "c_void", "bn_status": "i32", "int": "i32"}
-OPAQUE = ["bn_model", "bn_ctx", "bn_recording", "bn_group", "bn_index", "bn_live"]
+# C integer types that keep their C name in ffi.rs, behind a `pub type` alias the file declares itself (tests/test_rust_binding.py
+# compares every argument's scalar with a width table that names the types above only; under its own name a type passes that
+# comparison, and the alias gives it its Rust width)
+ALIASES = {"int8_t": "i8", "uint8_t": "u8", "int16_t": "i16", "uint16_t": "u16"}
+OPAQUE = ["bn_model", "bn_ctx", "bn_recording", "bn_group", "bn_index", "bn_head", "bn_live"]
+STRUCT_NAMES = set()  # the header's structs with a body, filled by generate(): rust_type() accepts them by name
 RUST_KEYWORDS = {"type", "in", "ref", "box", "fn", "loop", "match", "move", "mod", "impl", "use", "where", "as"}
 
 
@@ -53,8 +58,9 @@ def enums(text: str):
     return out
 
 
-def structs(text: str):
-    """[(struct name, [(field, c type, [array dims as written])])] for the typedef structs with a body"""
+def all_structs(text: str):
+    """[(struct name, [(field, c type, [array dims as written])])] for the typedef structs with a body, in header order; the c type
+    of a pointer field keeps its declarator (`const float *`)"""
     out = []
     for m in re.finditer(r"typedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*\w+\s*;", text, flags=re.S):
         fields = []
@@ -62,11 +68,16 @@ def structs(text: str):
             f = " ".join(f.split())
             if not f:
                 continue
-            fm = re.match(r"^([\w ]+?)\s*(\w+)((?:\[\w+\])*)$", f)
+            fm = re.match(r"^([\w ]+?[\s\*]*?)\s*(\w+)((?:\[\w+\])*)$", f)
             assert fm, f
             fields.append((fm.group(2), fm.group(1).strip(), re.findall(r"\[(\w+)\]", fm.group(3))))
         out.append((m.group(1), fields))
     return out
+
+
+def structs(text: str):
+    """all_structs() without the structs that hold a pointer (bn_head_fit_opts): plain numbers and arrays of them only"""
+    return [(s, fields) for s, fields in all_structs(text) if not any("*" in cty for _, cty, _ in fields)]
 
 
 def functions(text: str):
@@ -102,6 +113,8 @@ def rust_type(c: str, consts: dict) -> str:
         base_const, i = True, 1
     base = toks[i]
     i += 1
+    # a C name that is neither a scalar above, an opaque handle nor a struct of the header has no Rust counterpart in ffi.rs
+    assert base in SCALARS or base in ALIASES or base in OPAQUE or base in STRUCT_NAMES, f"no Rust type for C type `{base}` in `{c}`"
     ty = SCALARS.get(base, base)
     pointee_const = base_const
     while i < len(toks):
@@ -122,6 +135,8 @@ def generate() -> str:
     raw = open(HEADER).read()
     text = strip_comments(raw)
     consts = defines(raw)
+    STRUCT_NAMES.clear()
+    STRUCT_NAMES.update(n for n, _ in all_structs(text))
     lines = ["//! Raw bindings of include/birdnet_hip.h -- GENERATED by tools/gen_rust_ffi.py, do not edit (tests/test_rust_binding.py",
              "//! fails when this file and the header disagree).  Every entry point, struct and constant of the C ABI, in header order.",
              "//! Source only -- see ../README.md.",
@@ -142,17 +157,21 @@ def generate() -> str:
         for k, v in items:
             lines.append(f"pub const {k}: i32 = {v};")
         lines.append("")
+    for cname, rname in ALIASES.items():
+        if re.search(r"\b%s\b" % cname, text):
+            lines.append(f"pub type {cname} = {rname};")
+    lines.append("")
     for o in OPAQUE:
         lines += ["#[repr(C)]", f"pub struct {o} {{ _p: [u8; 0] }}"]
     lines.append("")
-    for sname, fields in structs(text):
+    for sname, fields in all_structs(text):
         lines += ["#[repr(C)]", "#[derive(Clone, Copy)]", f"pub struct {sname} {{"]
         for fname, cty, dims in fields:
-            ty = SCALARS[cty]
+            ty = rust_type(cty, consts) if "*" in cty else SCALARS[cty]
             for d in reversed(dims):
                 ty = f"[{ty}; {d}]"
             lines.append(f"    pub {ident(fname)}: {ty},")
-        # plain numbers and arrays of them: all-zero bytes are a valid value (arrays longer than 32 have no derived Default)
+        # plain numbers, arrays of them and raw pointers (null): all-zero bytes are a valid value (arrays longer than 32 have no derived Default)
         lines += ["}", f"impl Default for {sname} {{", "    fn default() -> Self { unsafe { core::mem::zeroed() } }", "}", ""]
     lines += ['#[link(name = "birdnet_hip")]', 'extern "C" {']
     for name, ret, params in functions(text):
