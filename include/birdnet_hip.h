@@ -529,6 +529,82 @@ bn_status bn_step_head_results(const bn_ctx *c, const float **logits, const uint
                                const uint32_t **count, size_t *k_stride, size_t *n_classes);
 
 /*
+ * Per-site species priors: the location / date prior of the reference's RangeFilter (src/rangefilter.rs) as an immutable
+ * device table P[n_sites][n_species] (f32, row-major), applied to every row of a step.  The reference filters one
+ * prediction list at a time on the host, by species name, after the cut to K; a table on the device serves a pool of a
+ * thousand recorders at a thousand sites inside the step, and can pick the K best species AMONG THOSE THAT OCCUR at the
+ * site.  A table row is the meta model's raw output for (lat, lon, week), not RangeFilter::predict's list, which holds only
+ * scores >= threshold: filter_predictions keeps every species absent from its list, so fed its own predict output the
+ * reference never drops anything.
+ *
+ *   Entry p        p >= 0: the meta model's score of the species at the site.  p < 0 (BN_PRIOR_UNKNOWN): the meta model does
+ *                  not know the species; it is kept unchanged (rangefilter.rs:368-375).  Non-finite: refused at creation.
+ *   Per species    for logit z of species j in a row at site s, p = P[s][j]:
+ *                    admitted = p < 0 || p >= threshold
+ *                    conf     = sigmoid(z), the step's own (bit-exact to the reference's)
+ *                    conf'    = conf * p under BN_PRIOR_RERANK when p >= 0 (one f32 multiply, fused with nothing), else conf
+ *   SELECT         (flags without BN_PRIOR_AFTER_TOPK) the row holds the first K = min(top_k, n_species) admitted species in
+ *                  the order: descending conf' under f32::total_cmp, ties by ascending species index.  With has_min the
+ *                  entries for which conf' >= min_conf fails (IEEE comparison: NaN fails) are then removed.  count may be
+ *                  below K: fewer species admitted, or cut by the minimum.  This order is defined by the sort alone; the
+ *                  reference has no counterpart to it, and the BinaryHeap tie arrangement the step's own top-K reproduces
+ *                  does not apply.  top_k is 1..1024.
+ *   AFTER_TOPK     exactly filter_predictions(the step's own top-K row, the site's full score row, threshold, rerank) with
+ *                  species matched by index: entries that are not admitted are dropped, the survivors' confidences
+ *                  multiplied when reranking, then (when reranking) sorted descending under total_cmp, equal ones keeping
+ *                  their order.  K, has_min and min_conf are the step's own; those given at attach are ignored.
+ *   Bits           a row's result depends only on the row's logits, its site's table row, threshold, the flags and K / has_min
+ *                  / min_conf: not on the batch size, the row's position or the entry point.  No floating-point atomics, no
+ *                  order that depends on scheduling; two runs give the same bits.
+ *   Step           bn_ctx_attach_prior makes every later bn_step_device / bn_step_windows / bn_step_live of the context also
+ *                  produce the prior-filtered rows of that step, on the context's stream, after the plan and the step's own
+ *                  top-K and outside the captured plan graph (capture_fallbacks stays 0).  The packed rows reach pinned
+ *                  memory as the step's own do; bn_step_prior_results is valid after bn_ctx_synchronize, until the next
+ *                  step.  Rows of bn_step_device / bn_step_windows are at the context's site (bn_ctx_prior_site, 0 after
+ *                  every attach); row i of bn_step_live is at source_sites[source_out[i]], or at the context's site when
+ *                  the map is NULL.  The site ids reach the device in pinned memory the kernel reads in place, without a
+ *                  synchronisation.  The step's own outputs are unchanged, bit for bit.  bn_infer*, tickets and bn_group_*
+ *                  carry no prior results.
+ *   Refusals       BN_ERR_INVALID_ARG with a message, nothing changed (a previous attachment stays): NULL where data is
+ *                  required, n_sites == 0, n_species != the model's num_species at attach, a non-finite table entry or
+ *                  threshold, unknown flag bits, a prior on another device, top_k outside 1..1024 for SELECT, for AFTER_TOPK
+ *                  whatever the step's top-K refuses, a site id outside 0..n_sites, a live step whose pool has more sources
+ *                  than the attached map, bn_ctx_prior_site without a prior.  Without a gfx950 device create and apply
+ *                  return BN_ERR_NO_DEVICE.
+ *   Lifetime       a context that attached a prior keeps it alive: bn_prior_free and bn_ctx_destroy may come in either order.
+ *   Threading      a prior is immutable and may be attached to any number of contexts; bn_prior_apply_host / bn_prior_read
+ *                  serialise per prior.  A new week or a moved recorder is a new prior and a re-attach (26.7 MB for 1024
+ *                  sites x 6522 species).
+ */
+typedef struct bn_prior bn_prior;
+#define BN_PRIOR_UNKNOWN (-1.0f) /* table entry of a species the meta model does not know */
+#define BN_PRIOR_SELECT 0u       /* the K best admitted species of all n_species (default) */
+#define BN_PRIOR_AFTER_TOPK 1u   /* filter_predictions over the step's own top-K row */
+#define BN_PRIOR_RERANK 2u       /* conf' = conf * p for known species */
+bn_status bn_prior_create(int32_t device, size_t n_sites, size_t n_species, const float *table, float threshold, uint32_t flags,
+                          bn_prior **out);
+void bn_prior_free(bn_prior *p);
+size_t bn_prior_sites(const bn_prior *p);
+size_t bn_prior_species(const bn_prior *p);
+float bn_prior_threshold(const bn_prior *p);
+uint32_t bn_prior_flags(const bn_prior *p);
+/* table rows first_site .. first_site + count back on the host: out [count * n_species] */
+bn_status bn_prior_read(const bn_prior *p, size_t first_site, size_t count, float *out);
+/* the prior on host logits [rows * n_species], row r at sites[r]; the same kernels as a step runs (for AFTER_TOPK behind the
+ * step's top-K kernel under top_k / has_min / min_conf).  idx_out / conf_out [rows * k_stride], k_stride >= min(top_k,
+ * n_species); count_out [rows].  Slots past a row's count up to K are zero. */
+bn_status bn_prior_apply_host(const bn_prior *p, const float *logits, size_t rows, const int32_t *sites, size_t top_k, int32_t has_min,
+                              float min_conf, size_t k_stride, uint32_t *idx_out, float *conf_out, uint32_t *count_out);
+/* p == NULL detaches (the other arguments are then ignored).  source_sites [n_source_sites]: the site of every source of
+ * the live pools this context steps, or NULL */
+bn_status bn_ctx_attach_prior(bn_ctx *c, bn_prior *p, const int32_t *source_sites, size_t n_source_sites, size_t top_k, int32_t has_min,
+                              float min_conf);
+/* the site of every row of bn_step_device / bn_step_windows (and of bn_step_live without a map) */
+bn_status bn_ctx_prior_site(bn_ctx *c, int32_t site);
+/* pinned host views of the last step's prior rows: idx / conf [batch, k_stride], count [batch] */
+bn_status bn_step_prior_results(const bn_ctx *c, const uint32_t **idx, const float **conf, const uint32_t **count, size_t *k_stride);
+
+/*
  * Live ingest: a device-resident pool of per-source ring buffers for continuous audio (many recorders, each producing a
  * window every `step` seconds).  Callers push PCM as it arrives, in the storage format (i16: half the PCIe bytes, and no
  * overlap sample crosses the bus twice); bn_step_live batches the ready windows of ALL sources into one context batch, cut on

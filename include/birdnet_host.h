@@ -138,6 +138,33 @@ struct InferenceOptions {
 
 class Classifier;
 
+/* A per-site species prior resident on one device (bn_prior, include/birdnet_hip.h): the RangeFilter's location / date
+ * prior as a table [n_sites][n_species] in classifier order, rows as RangeFilter::prior_row returns them.  Immutable;
+ * attachable to any number of contexts, which keep it alive. */
+class Prior {
+   public:
+    /* flags: BN_PRIOR_SELECT / BN_PRIOR_AFTER_TOPK, | BN_PRIOR_RERANK; throws Error::Inference with the backend's message */
+    Prior(int device, size_t n_sites, size_t n_species, const float *table, float threshold, uint32_t flags = BN_PRIOR_SELECT);
+    ~Prior();
+    Prior(const Prior &) = delete;
+    Prior &operator=(const Prior &) = delete;
+    size_t sites() const;
+    size_t species() const;
+    float threshold() const;
+    uint32_t flags() const;
+    bn_prior *handle() const { return p_; }
+
+   private:
+    bn_prior *p_ = nullptr;
+};
+/* prior-filtered rows of a context's last step (copies of bn_step_prior_results) */
+struct PriorRows {
+    size_t k_stride = 0;
+    std::vector<uint32_t> idx;   /* [batch, k_stride] */
+    std::vector<float> conf;     /* [batch, k_stride] */
+    std::vector<uint32_t> count; /* [batch] */
+};
+
 /* BatchInferenceContext (src/batch_context.rs:70-165): not thread-safe, one per thread. */
 class BatchInferenceContext {
    public:
@@ -153,6 +180,12 @@ class BatchInferenceContext {
      * [batch, row_elems] -- e.g. Perch's spatial embedding (1) and spectrogram (2), which the reference
      * discards.  Only for contexts made by create_native_batch_context(.., all_outputs = true). */
     std::vector<float> read_output(int index, size_t batch, size_t *row_elems = nullptr) const;
+    /* bn_ctx_attach_prior / bn_ctx_prior_site / bn_step_prior_results on the context (prior == nullptr detaches); the steps
+     * of the context (predict_recording, predict_live) then also produce the prior-filtered rows */
+    void attach_prior(const Prior *prior, const std::vector<int32_t> *source_sites = nullptr, size_t top_k = 10,
+                      std::optional<float> min_confidence = std::nullopt);
+    void set_prior_site(int32_t site);
+    PriorRows prior_results(size_t batch) const;
 
    private:
     friend class Classifier;
@@ -316,6 +349,12 @@ class RangeFilter {
     /* rangefilter.rs:435-502: validate, week, run the meta model on [lat, lon, week], keep scores >= threshold,
      * sort descending.  The model runs on the MI355X through the same engine (BN_MODEL_GENERIC). */
     std::vector<LocationScore> predict(float latitude, float longitude, uint32_t month, uint32_t day) const;
+    /* the meta model's raw output row for (lat, lon, week): predict's validation and week rule, no threshold, meta order */
+    std::vector<float> scores(float latitude, float longitude, uint32_t month, uint32_t day) const;
+    /* one row of a Prior's table: the score of every classifier label, in classifier order; a label the meta model lacks
+     * gets BN_PRIOR_UNKNOWN (a label the meta model holds twice takes the later entry, as filter_predictions does) */
+    std::vector<float> prior_row(const std::vector<std::string> &classifier_labels, float latitude, float longitude, uint32_t month,
+                                 uint32_t day) const;
     std::vector<Prediction> filter_predictions(const std::vector<Prediction> &predictions, const std::vector<LocationScore> &location_scores,
                                                bool rerank) const;
     std::vector<std::vector<Prediction>> filter_batch_predictions(const std::vector<std::vector<Prediction>> &predictions_batch,
@@ -462,6 +501,25 @@ void bnh_range_filter_free(bnh_range_filter *f);
 int32_t bnh_range_filter_predict(const bnh_range_filter *f, float latitude, float longitude, uint32_t month, uint32_t day, uint32_t *idx_out,
                                  float *score_out, size_t cap, size_t *n_out, bnh_error *err);
 const char *bnh_range_filter_label(const bnh_range_filter *f, size_t i);
+/* RangeFilter::scores: writes up to cap raw scores in meta-model order; *n_out = the meta model's species count */
+int32_t bnh_range_filter_scores(const bnh_range_filter *f, float latitude, float longitude, uint32_t month, uint32_t day, float *score_out, size_t cap,
+                                size_t *n_out, bnh_error *err);
+/* RangeFilter::prior_row: row_out [n_labels] in the order of `labels` */
+int32_t bnh_range_filter_prior_row(const bnh_range_filter *f, const char *const *labels, size_t n_labels, float latitude, float longitude, uint32_t month,
+                                   uint32_t day, float *row_out, bnh_error *err);
+/* class Prior and the context's side of it */
+typedef struct bnh_prior bnh_prior;
+int32_t bnh_prior_create(int32_t device, size_t n_sites, size_t n_species, const float *table, float threshold, uint32_t flags, bnh_prior **out,
+                         bnh_error *err);
+void bnh_prior_free(bnh_prior *p);
+bn_prior *bnh_prior_handle(const bnh_prior *p);
+/* p NULL detaches; source_sites NULL => no map */
+int32_t bnh_context_attach_prior(bnh_context *ctx, const bnh_prior *p, const int32_t *source_sites, size_t n_source_sites, size_t top_k, int32_t has_min,
+                                 float min_conf, bnh_error *err);
+int32_t bnh_context_set_prior_site(bnh_context *ctx, int32_t site, bnh_error *err);
+/* copies of the last step's prior rows: idx_out / conf_out take up to cap entries of [batch, *k_stride], count_out [batch] */
+int32_t bnh_context_prior_results(const bnh_context *ctx, size_t batch, uint32_t *idx_out, float *conf_out, size_t cap, uint32_t *count_out,
+                                  size_t *k_stride, bnh_error *err);
 /* filter_predictions_impl on parallel arrays (species by name): returns the number of survivors, their positions
  * in the input in keep_pos and their confidences in conf_out */
 size_t bnh_filter_predictions(const char *const *pred_species, const float *pred_conf, size_t n_pred, const char *const *loc_species,

@@ -56,6 +56,8 @@ ENGINE_SYMBOLS = [
     "bn_index_search", "bn_index_search_ids",
     "bn_head_create", "bn_head_free", "bn_head_dim", "bn_head_classes", "bn_head_flags", "bn_head_read", "bn_head_apply_host",
     "bn_head_fit", "bn_head_fit_index", "bn_ctx_attach_head", "bn_step_head_results",
+    "bn_prior_create", "bn_prior_free", "bn_prior_sites", "bn_prior_species", "bn_prior_threshold", "bn_prior_flags", "bn_prior_read",
+    "bn_prior_apply_host", "bn_ctx_attach_prior", "bn_ctx_prior_site", "bn_step_prior_results",
     "bn_live_create", "bn_live_free", "bn_live_push", "bn_live_push_many", "bn_live_close", "bn_live_reset", "bn_live_ready",
     "bn_live_room", "bn_live_event_count", "bn_live_read_window", "bn_step_live",
     "bn_live_create_rates", "bn_live_resampled_samples", "bn_live_source_rate",
@@ -70,6 +72,8 @@ HOST_SYMBOLS = [
     "bnh_result_embeddings", "bnh_results_free", "bnh_parse_labels", "bnh_parse_labels_format", "bnh_chunk_plan",
     "bnh_calculate_week", "bnh_validate_coordinates", "bnh_validate_date", "bnh_range_filter_build", "bnh_range_filter_free",
     "bnh_range_filter_predict", "bnh_range_filter_label", "bnh_filter_predictions",
+    "bnh_range_filter_scores", "bnh_range_filter_prior_row", "bnh_prior_create", "bnh_prior_free", "bnh_prior_handle",
+    "bnh_context_attach_prior", "bnh_context_set_prior_site", "bnh_context_prior_results",
     "bnh_live_create", "bnh_live_create_rates", "bnh_live_free", "bnh_live_push", "bnh_live_close", "bnh_live_ready", "bnh_predict_live",
 ]
 
@@ -110,6 +114,8 @@ class BnHeadFitReport(C.Structure):
 
 
 BN_HEAD_L2NORM = 1
+BN_PRIOR_UNKNOWN = -1.0  # table entry of a species the meta model does not know
+BN_PRIOR_SELECT, BN_PRIOR_AFTER_TOPK, BN_PRIOR_RERANK = 0, 1, 2
 BN_ABI_VERSION = 2  # include/birdnet_hip.h
 
 
@@ -205,6 +211,17 @@ def _load() -> C.CDLL:
                                     C.POINTER(BnHeadFitReport), sz]),
         "bn_ctx_attach_head": (i32, [vp, vp, sz, i32, C.c_float]),
         "bn_step_head_results": (i32, [vp, C.POINTER(f32p), C.POINTER(u32p), C.POINTER(f32p), C.POINTER(u32p), C.POINTER(sz), C.POINTER(sz)]),
+        "bn_prior_create": (i32, [i32, sz, sz, f32p, C.c_float, C.c_uint32, C.POINTER(vp)]),
+        "bn_prior_free": (None, [vp]),
+        "bn_prior_sites": (sz, [vp]),
+        "bn_prior_species": (sz, [vp]),
+        "bn_prior_threshold": (C.c_float, [vp]),
+        "bn_prior_flags": (C.c_uint32, [vp]),
+        "bn_prior_read": (i32, [vp, sz, sz, f32p]),
+        "bn_prior_apply_host": (i32, [vp, f32p, sz, C.POINTER(C.c_int32), sz, i32, C.c_float, sz, u32p, f32p, u32p]),
+        "bn_ctx_attach_prior": (i32, [vp, vp, C.POINTER(C.c_int32), sz, sz, i32, C.c_float]),
+        "bn_ctx_prior_site": (i32, [vp, i32]),
+        "bn_step_prior_results": (i32, [vp, C.POINTER(u32p), C.POINTER(f32p), C.POINTER(u32p), C.POINTER(sz)]),
         "bn_live_create": (i32, [i32, i32, i32, sz, sz, sz, C.POINTER(vp)]),
         "bn_live_create_rates": (i32, [i32, i32, i32, sz, sz, sz, C.c_uint32, u32p, C.c_uint32, C.POINTER(vp)]),
         "bn_live_resampled_samples": (sz, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, i32]),
@@ -251,6 +268,14 @@ def _load() -> C.CDLL:
         "bnh_range_filter_free": (None, [vp]),
         "bnh_range_filter_predict": (i32, [vp, C.c_float, C.c_float, C.c_uint32, C.c_uint32, u32p, f32p, sz, C.POINTER(sz), C.POINTER(BnhError)]),
         "bnh_range_filter_label": (C.c_char_p, [vp, sz]),
+        "bnh_range_filter_scores": (i32, [vp, C.c_float, C.c_float, C.c_uint32, C.c_uint32, f32p, sz, C.POINTER(sz), C.POINTER(BnhError)]),
+        "bnh_range_filter_prior_row": (i32, [vp, C.POINTER(C.c_char_p), sz, C.c_float, C.c_float, C.c_uint32, C.c_uint32, f32p, C.POINTER(BnhError)]),
+        "bnh_prior_create": (i32, [i32, sz, sz, f32p, C.c_float, C.c_uint32, C.POINTER(vp), C.POINTER(BnhError)]),
+        "bnh_prior_free": (None, [vp]),
+        "bnh_prior_handle": (vp, [vp]),
+        "bnh_context_attach_prior": (i32, [vp, vp, C.POINTER(C.c_int32), sz, sz, i32, C.c_float, C.POINTER(BnhError)]),
+        "bnh_context_set_prior_site": (i32, [vp, i32, C.POINTER(BnhError)]),
+        "bnh_context_prior_results": (i32, [vp, sz, u32p, f32p, sz, u32p, C.POINTER(sz), C.POINTER(BnhError)]),
         "bnh_filter_predictions": (sz, [C.POINTER(C.c_char_p), f32p, sz, C.POINTER(C.c_char_p), f32p, sz, C.c_float, i32, u32p, f32p]),
         "bnh_live_create": (i32, [vp, i32, i32, C.c_float, sz, i32, C.POINTER(vp), C.POINTER(BnhError)]),
         "bnh_live_create_rates": (i32, [vp, i32, u32p, i32, C.c_float, sz, i32, C.c_uint32, C.POINTER(vp), C.POINTER(BnhError)]),
@@ -904,6 +929,33 @@ class Context:
             raise EngineError(st)
         return src[:n.value].copy(), win[:n.value].copy()
 
+    def attach_prior(self, prior: Optional["Prior"], source_sites=None, top_k: int = 10, min_confidence: Optional[float] = None):
+        """bn_ctx_attach_prior: every later step of this context also produces that step's prior-filtered top-K rows (None
+        detaches).  source_sites: the site of every source of the live pools this context steps; without it, and in step_device /
+        step_windows, every row is at the context's site (set_prior_site, 0 after every attach)."""
+        m = None if source_sites is None else np.ascontiguousarray(source_sites, dtype=np.int32).reshape(-1)
+        st = lib.bn_ctx_attach_prior(self._h, None if prior is None else prior._h, None if m is None else m.ctypes.data_as(C.POINTER(C.c_int32)),
+                                     0 if m is None else m.shape[0], top_k, 0 if min_confidence is None else 1, C.c_float(min_confidence or 0.0))
+        if st:
+            raise EngineError(st)
+        self._prior = prior
+
+    def set_prior_site(self, site: int):
+        """bn_ctx_prior_site: the site of every row of step_device / step_windows."""
+        st = lib.bn_ctx_prior_site(self._h, site)
+        if st:
+            raise EngineError(st)
+
+    def step_prior_results(self, batch: int):
+        """(idx [batch, k], conf [batch, k], count [batch]) of the last step's prior-filtered rows, after synchronize()."""
+        ix, cf, ct, ks = C.POINTER(C.c_uint32)(), C.POINTER(C.c_float)(), C.POINTER(C.c_uint32)(), C.c_size_t()
+        st = lib.bn_step_prior_results(self._h, C.byref(ix), C.byref(cf), C.byref(ct), C.byref(ks))
+        if st:
+            raise EngineError(st)
+        k = ks.value
+        return (np.ctypeslib.as_array(ix, shape=(batch, k)).copy(), np.ctypeslib.as_array(cf, shape=(batch, k)).copy(),
+                np.ctypeslib.as_array(ct, shape=(batch,)).copy())
+
     def attach_head(self, head: Optional["Head"], top_k: int = 10, min_confidence: Optional[float] = None):
         """bn_ctx_attach_head: every later step of this context also runs `head` on the step's embedding rows (None detaches)."""
         st = lib.bn_ctx_attach_head(self._h, None if head is None else head._h, top_k, 0 if min_confidence is None else 1,
@@ -1217,6 +1269,77 @@ class Head:
         return out
 
 
+class Prior:
+    """bn_prior: an immutable table of species priors per site, [n_sites, n_species] f32, resident on one device (rows as
+    RangeFilter.prior_row returns them; BN_PRIOR_UNKNOWN for species the meta model does not know).  `apply(logits, sites, ...)`
+    on host rows, `Context.attach_prior` for every step of a context.  after_topk=False: the K best admitted species of all
+    (BN_PRIOR_SELECT); True: filter_predictions over the step's own top-K row."""
+
+    def __init__(self, device: int, table, threshold: float = 0.01, after_topk: bool = False, rerank: bool = False, flags: Optional[int] = None):
+        t = np.ascontiguousarray(table, dtype=np.float32)
+        if t.ndim != 2:
+            raise ValueError("table must be [n_sites, n_species]")
+        if flags is None:
+            flags = (BN_PRIOR_AFTER_TOPK if after_topk else 0) | (BN_PRIOR_RERANK if rerank else 0)
+        h = C.c_void_p()
+        st = lib.bn_prior_create(device, t.shape[0], t.shape[1], t.ctypes.data_as(C.POINTER(C.c_float)), C.c_float(threshold), flags, C.byref(h))
+        if st:
+            raise EngineError(st)
+        self._h = h
+
+    def __del__(self):
+        if getattr(self, "_h", None) and lib is not None:
+            lib.bn_prior_free(self._h)
+            self._h = None
+
+    def close(self):
+        self.__del__()
+
+    @property
+    def n_sites(self) -> int:
+        return int(lib.bn_prior_sites(self._h))
+
+    @property
+    def n_species(self) -> int:
+        return int(lib.bn_prior_species(self._h))
+
+    @property
+    def threshold(self) -> float:
+        return float(lib.bn_prior_threshold(self._h))
+
+    @property
+    def flags(self) -> int:
+        return int(lib.bn_prior_flags(self._h))
+
+    def read(self, first_site: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """Table rows [count, n_species] as stored on the device."""
+        count = self.n_sites - first_site if count is None else count
+        out = np.empty((max(count, 0), self.n_species), dtype=np.float32)
+        st = lib.bn_prior_read(self._h, first_site, count, out.ctypes.data_as(C.POINTER(C.c_float)))
+        if st:
+            raise EngineError(st)
+        return out
+
+    def apply(self, logits, sites, top_k: int = 10, min_confidence: Optional[float] = None, k_stride: Optional[int] = None):
+        """bn_prior_apply_host: (idx [rows, k_stride], conf [rows, k_stride], count [rows]) of host logits [rows, n_species], row r at
+        sites[r]; the kernels a step runs."""
+        x = np.ascontiguousarray(logits, dtype=np.float32).reshape(-1, self.n_species)
+        sv = np.ascontiguousarray(sites, dtype=np.int32).reshape(-1)
+        if sv.shape[0] != x.shape[0]:
+            raise ValueError("one site per row")
+        ks = max(min(top_k, self.n_species), 1) if k_stride is None else k_stride
+        idx = np.zeros((x.shape[0], ks), dtype=np.uint32)
+        conf = np.zeros((x.shape[0], ks), dtype=np.float32)
+        cnt = np.zeros(x.shape[0], dtype=np.uint32)
+        u32p = C.POINTER(C.c_uint32)
+        st = lib.bn_prior_apply_host(self._h, x.ctypes.data_as(C.POINTER(C.c_float)), x.shape[0], sv.ctypes.data_as(C.POINTER(C.c_int32)), top_k,
+                                     0 if min_confidence is None else 1, C.c_float(min_confidence or 0.0), ks, idx.ctypes.data_as(u32p),
+                                     conf.ctypes.data_as(C.POINTER(C.c_float)), cnt.ctypes.data_as(u32p))
+        if st:
+            raise EngineError(st)
+        return idx, conf, cnt
+
+
 class Live:
     """bn_live: a device-resident pool of per-source ring buffers for continuous audio.  Push int16 / float32 PCM as it arrives;
     Context.step_live batches the ready windows of all sources, cut on the device (chunk_audio per source)."""
@@ -1364,6 +1487,27 @@ class RangeFilter:
         if lib.bnh_range_filter_predict(self._h, C.c_float(latitude), C.c_float(longitude), month, day, idx, sc, cap, C.byref(n), C.byref(err)):
             raise Error(err)
         return [LocationScore(lib.bnh_range_filter_label(self._h, idx[i]).decode(), float(sc[i]), int(idx[i])) for i in range(min(n.value, cap))]
+
+    def scores(self, latitude: float, longitude: float, month: int, day: int) -> np.ndarray:
+        """The meta model's raw output row for (lat, lon, week), in meta-model order: predict's validation and week rule, no threshold."""
+        err, n = BnhError(), C.c_size_t()
+        cap = 1 << 16
+        sc = np.zeros(cap, dtype=np.float32)
+        if lib.bnh_range_filter_scores(self._h, C.c_float(latitude), C.c_float(longitude), month, day, sc.ctypes.data_as(C.POINTER(C.c_float)), cap,
+                                       C.byref(n), C.byref(err)):
+            raise Error(err)
+        return sc[:min(n.value, cap)].copy()
+
+    def prior_row(self, classifier_labels: list, latitude: float, longitude: float, month: int, day: int) -> np.ndarray:
+        """One row of a Prior's table: the score of every classifier label in classifier order, BN_PRIOR_UNKNOWN where the meta model
+        lacks the label."""
+        err = BnhError()
+        labels = (C.c_char_p * max(len(classifier_labels), 1))(*[x.encode() for x in classifier_labels])
+        row = np.zeros(max(len(classifier_labels), 1), dtype=np.float32)
+        if lib.bnh_range_filter_prior_row(self._h, labels, len(classifier_labels), C.c_float(latitude), C.c_float(longitude), month, day,
+                                          row.ctypes.data_as(C.POINTER(C.c_float)), C.byref(err)):
+            raise Error(err)
+        return row[:len(classifier_labels)].copy()
 
     def filter_predictions(self, predictions: list, location_scores: list, rerank: bool) -> list:
         return filter_predictions(predictions, location_scores, self.threshold, rerank)

@@ -181,6 +181,7 @@ struct bn_ctx {
     float *h_tk_conf = nullptr;
     size_t step_k = 0;
     bn::HeadAttach *head = nullptr;  // bn_ctx_attach_head: run after every step's own work (head.hip)
+    bn::PriorAttach *prior = nullptr;  // bn_ctx_attach_prior: the same, on the step's logits rows (prior.hip)
     // ---- asynchronous host-slice path (bn_infer_submit / bn_infer_collect): a ring of two batches per context.
     // Both slots own their device input, pinned input and pinned output buffers (allocated on first use), so a ticket
     // in flight shares nothing with the synchronous entry points (bn_infer_windows / bn_step_*) but the arena and the
@@ -718,6 +719,7 @@ void bn_ctx_destroy(bn_ctx *c) {
     (void)bn::use_device(c->model->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     bn::head_detach(c->head);
+    bn::prior_detach(c->prior);
     for (auto &kv : c->graphs) (void)gated::GraphExecDestroy(kv.second);
     if (c->d_arena) (void)gated::Free(c->d_arena);
     if (c->d_input) (void)gated::Free(c->d_input);
@@ -1313,6 +1315,10 @@ bn_status bn_step_device(bn_ctx *c, const float *d_pcm, size_t batch, size_t top
         st = bn::head_step(c->head, c->stream, resolve(c, eo.ref, d_pcm), batch);
         if (st != BN_OK) return st;
     }
+    if (c->prior) {
+        st = bn::prior_step(c->prior, c->stream, d_logits, batch, c->d_step, k);
+        if (st != BN_OK) return st;
+    }
     if (sync) HIP_TRY(hipStreamSynchronize(c->stream));
     return BN_OK;
 }
@@ -1344,6 +1350,38 @@ bn_status bn_step_head_results(const bn_ctx *c, const float **logits, const uint
     if (!c) return fail(BN_ERR_INVALID_ARG, "null context");
     if (!c->head) return fail(BN_ERR_INVALID_ARG, "no head is attached to this context");
     return bn::head_step_results(c->head, logits, idx, conf, count, k_stride, n_classes);
+}
+
+bn_status bn_ctx_attach_prior(bn_ctx *c, bn_prior *p, const int32_t *source_sites, size_t n_source_sites, size_t top_k, int32_t has_min, float min_conf) {
+    if (!c) return fail(BN_ERR_INVALID_ARG, "null context");
+    HIP_TRY(bn::use_device(c->model->device));
+    bn::PriorAttach *a = nullptr;
+    if (p) {
+        const size_t n = (size_t)c->pd->plan->outputs[c->model->cfg.logits_output].row_elems;
+        bn_status st = bn::prior_attach(p, c->model->device, n, c->max_batch, source_sites, n_source_sites, top_k, has_min, min_conf, &a);
+        if (st != BN_OK) return st;
+    }
+    // the previous attachment's buffers may still be read by a step in flight
+    hipError_t e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        bn::prior_detach(a);
+        return fail(BN_ERR_BACKEND, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
+    }
+    bn::prior_detach(c->prior);
+    c->prior = a;
+    return BN_OK;
+}
+
+bn_status bn_ctx_prior_site(bn_ctx *c, int32_t site) {
+    if (!c) return fail(BN_ERR_INVALID_ARG, "null context");
+    if (!c->prior) return fail(BN_ERR_INVALID_ARG, "no prior is attached to this context");
+    return bn::prior_set_site(c->prior, site);
+}
+
+bn_status bn_step_prior_results(const bn_ctx *c, const uint32_t **idx, const float **conf, const uint32_t **count, size_t *k_stride) {
+    if (!c) return fail(BN_ERR_INVALID_ARG, "null context");
+    if (!c->prior) return fail(BN_ERR_INVALID_ARG, "no prior is attached to this context");
+    return bn::prior_step_results(c->prior, idx, conf, count, k_stride);
 }
 
 bn_status bn_step_results(const bn_ctx *c, const float **logits, const uint32_t **idx, const float **conf, const uint32_t **count, size_t *k_stride) {
@@ -1913,6 +1951,8 @@ size_t bn_last_error(char *buf, size_t cap) {
 }  // extern "C"
 
 bn_status bn::set_last_error(bn_status st, const std::string &msg) { return fail(st, msg); }
+
+bn::PriorAttach *bn::ctx_prior(bn_ctx *c) { return c ? c->prior : nullptr; }
 
 bn_status bn::ctx_embedding(const bn_ctx *c, CtxEmbedding *out) {
     if (!c || !out) return fail(BN_ERR_INVALID_ARG, "null argument");

@@ -1,5 +1,5 @@
 // What other translation units of the C ABI need of capi.cpp's private state (index.hip: bn_index_*; head.hip: bn_head_*) and
-// of each other.
+// of each other (prior.hip: bn_prior_*).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -56,4 +56,21 @@ void head_detach(HeadAttach *a);  // the context's stream must be idle
 bn_status head_step(HeadAttach *a, hipStream_t stream, const float *d_emb, size_t batch);
 bn_status head_step_results(const HeadAttach *a, const float **logits, const uint32_t **idx, const float **conf, const uint32_t **count,
                             size_t *k_stride, size_t *n_classes);
+// prior.hip -> capi.cpp / live.cpp: a prior attached to a context (its own result buffers; holds a reference to the prior)
+struct PriorAttach;
+bn_status prior_attach(bn_prior *p, int device, size_t num_species, size_t max_batch, const int32_t *source_sites, size_t n_source_sites, size_t top_k,
+                       int32_t has_min, float min_conf, PriorAttach **out);
+void prior_detach(PriorAttach *a);  // the context's stream must be idle
+bn_status prior_set_site(PriorAttach *a, int32_t site);
+// bn_step_live: refuses a pool with more sources than the attached map, before anything is taken from the pool
+bn_status prior_live_check(const PriorAttach *a, size_t n_sources);
+// bn_step_live: the sites of the coming step's rows (by source) into the next pinned block; prior_step consumes it
+bn_status prior_stage_rows(PriorAttach *a, const int32_t *sources, size_t rows);
+void prior_clear_rows(PriorAttach *a);
+// the prior kernel + results to pinned memory, enqueued on the context's stream behind the step's own top-K;
+// d_step_rows / step_k: the step's packed [idx][conf][count] block on the device
+bn_status prior_step(PriorAttach *a, hipStream_t stream, const float *d_logits, size_t batch, const uint32_t *d_step_rows, size_t step_k);
+bn_status prior_step_results(const PriorAttach *a, const uint32_t **idx, const float **conf, const uint32_t **count, size_t *k_stride);
+// capi.cpp -> live.cpp: the context's attached prior, NULL if none
+PriorAttach *ctx_prior(bn_ctx *c);
 }  // namespace bn

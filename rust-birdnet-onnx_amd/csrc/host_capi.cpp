@@ -15,6 +15,9 @@ struct bnh_context {
 struct bnh_live {
     LiveSources live;
 };
+struct bnh_prior {
+    std::unique_ptr<Prior> p;
+};
 struct bnh_results {
     std::vector<PredictionResult> v;
 };
@@ -309,6 +312,64 @@ int32_t bnh_range_filter_predict(const bnh_range_filter *f, float latitude, floa
             if (idx_out) idx_out[i] = (uint32_t)v[i].index;
             if (score_out) score_out[i] = v[i].score;
         }
+    });
+}
+
+int32_t bnh_range_filter_scores(const bnh_range_filter *f, float latitude, float longitude, uint32_t month, uint32_t day, float *score_out, size_t cap,
+                                size_t *n_out, bnh_error *err) {
+    if (n_out) *n_out = 0;
+    return guarded(err, [&] {
+        auto v = f->f.scores(latitude, longitude, month, day);
+        if (n_out) *n_out = v.size();
+        for (size_t i = 0; i < v.size() && i < cap; i++)
+            if (score_out) score_out[i] = v[i];
+    });
+}
+
+int32_t bnh_range_filter_prior_row(const bnh_range_filter *f, const char *const *labels, size_t n_labels, float latitude, float longitude, uint32_t month,
+                                   uint32_t day, float *row_out, bnh_error *err) {
+    return guarded(err, [&] {
+        std::vector<std::string> l;
+        for (size_t i = 0; i < n_labels; i++) l.emplace_back(labels[i]);
+        auto v = f->f.prior_row(l, latitude, longitude, month, day);
+        for (size_t i = 0; i < v.size(); i++) row_out[i] = v[i];
+    });
+}
+
+int32_t bnh_prior_create(int32_t device, size_t n_sites, size_t n_species, const float *table, float threshold, uint32_t flags, bnh_prior **out,
+                         bnh_error *err) {
+    if (out) *out = nullptr;
+    return guarded(err, [&] {
+        auto r = std::make_unique<bnh_prior>();
+        r->p = std::make_unique<Prior>(device, n_sites, n_species, table, threshold, flags);
+        *out = r.release();
+    });
+}
+void bnh_prior_free(bnh_prior *p) { delete p; }
+bn_prior *bnh_prior_handle(const bnh_prior *p) { return p ? p->p->handle() : nullptr; }
+
+int32_t bnh_context_attach_prior(bnh_context *ctx, const bnh_prior *p, const int32_t *source_sites, size_t n_source_sites, size_t top_k, int32_t has_min,
+                                 float min_conf, bnh_error *err) {
+    return guarded(err, [&] {
+        std::vector<int32_t> map;
+        if (source_sites) map.assign(source_sites, source_sites + n_source_sites);
+        ctx->ctx->attach_prior(p ? p->p.get() : nullptr, source_sites ? &map : nullptr, top_k, has_min ? std::optional<float>(min_conf) : std::nullopt);
+    });
+}
+int32_t bnh_context_set_prior_site(bnh_context *ctx, int32_t site, bnh_error *err) {
+    return guarded(err, [&] { ctx->ctx->set_prior_site(site); });
+}
+int32_t bnh_context_prior_results(const bnh_context *ctx, size_t batch, uint32_t *idx_out, float *conf_out, size_t cap, uint32_t *count_out,
+                                  size_t *k_stride, bnh_error *err) {
+    return guarded(err, [&] {
+        const PriorRows r = ctx->ctx->prior_results(batch);
+        if (k_stride) *k_stride = r.k_stride;
+        for (size_t i = 0; i < r.idx.size() && i < cap; i++) {
+            if (idx_out) idx_out[i] = r.idx[i];
+            if (conf_out) conf_out[i] = r.conf[i];
+        }
+        for (size_t i = 0; i < batch; i++)
+            if (count_out) count_out[i] = r.count[i];
     });
 }
 

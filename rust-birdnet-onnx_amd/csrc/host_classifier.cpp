@@ -258,6 +258,36 @@ std::vector<float> BatchInferenceContext::read_output(int index, size_t batch, s
     return out;
 }
 
+Prior::Prior(int device, size_t n_sites, size_t n_species, const float *table, float threshold, uint32_t flags) {
+    if (bn_prior_create(device, n_sites, n_species, table, threshold, flags, &p_) != BN_OK) throw inference(last_backend_error());
+}
+Prior::~Prior() { bn_prior_free(p_); }
+size_t Prior::sites() const { return bn_prior_sites(p_); }
+size_t Prior::species() const { return bn_prior_species(p_); }
+float Prior::threshold() const { return bn_prior_threshold(p_); }
+uint32_t Prior::flags() const { return bn_prior_flags(p_); }
+
+void BatchInferenceContext::attach_prior(const Prior *prior, const std::vector<int32_t> *source_sites, size_t top_k, std::optional<float> min_confidence) {
+    if (bn_ctx_attach_prior(ctx_, prior ? prior->handle() : nullptr, source_sites ? source_sites->data() : nullptr, source_sites ? source_sites->size() : 0,
+                            top_k, min_confidence ? 1 : 0, min_confidence.value_or(0.0f)) != BN_OK)
+        throw inference(last_backend_error());
+}
+
+void BatchInferenceContext::set_prior_site(int32_t site) {
+    if (bn_ctx_prior_site(ctx_, site) != BN_OK) throw inference(last_backend_error());
+}
+
+PriorRows BatchInferenceContext::prior_results(size_t batch) const {
+    const uint32_t *idx = nullptr, *count = nullptr;
+    const float *conf = nullptr;
+    PriorRows r;
+    if (bn_ctx_synchronize(ctx_) != BN_OK || bn_step_prior_results(ctx_, &idx, &conf, &count, &r.k_stride) != BN_OK) throw inference(last_backend_error());
+    r.idx.assign(idx, idx + batch * r.k_stride);
+    r.conf.assign(conf, conf + batch * r.k_stride);
+    r.count.assign(count, count + batch);
+    return r;
+}
+
 std::vector<PredictionResult> Classifier::predict_batch_with_context(BatchInferenceContext &ctx, const float *const *segments, const size_t *lens, size_t n,
                                                                      const InferenceOptions &options) const {
     if (n == 0) return {};

@@ -141,21 +141,37 @@ RangeFilter RangeFilterBuilder::build() {
     return f;
 }
 
-std::vector<LocationScore> RangeFilter::predict(float latitude, float longitude, uint32_t month, uint32_t day) const {
+std::vector<float> RangeFilter::scores(float latitude, float longitude, uint32_t month, uint32_t day) const {
     validate_coordinates(latitude, longitude);
     validate_date(month, day);
     const float input[3] = {latitude, longitude, calculate_week(month, day)};
     const float *segs[1] = {input};
     std::vector<float> data(inner_->n_out);
-    {
-        std::lock_guard<std::mutex> lk(inner_->mu);
-        if (bn_infer(inner_->ctx, segs, 1, data.data(), nullptr, nullptr, 0) != BN_OK) throw rf_inference(backend_error());
-    }
+    std::lock_guard<std::mutex> lk(inner_->mu);
+    if (bn_infer(inner_->ctx, segs, 1, data.data(), nullptr, nullptr, 0) != BN_OK) throw rf_inference(backend_error());
+    return data;
+}
+
+std::vector<LocationScore> RangeFilter::predict(float latitude, float longitude, uint32_t month, uint32_t day) const {
+    const std::vector<float> data = scores(latitude, longitude, month, day);
     std::vector<LocationScore> scores;
     for (size_t i = 0; i < data.size(); i++)
         if (data[i] >= inner_->threshold && i < inner_->labels.size()) scores.push_back(LocationScore{inner_->labels[i], data[i], i});
     std::stable_sort(scores.begin(), scores.end(), [](const LocationScore &a, const LocationScore &b) { return total_key(a.score) > total_key(b.score); });
     return scores;
+}
+
+std::vector<float> RangeFilter::prior_row(const std::vector<std::string> &classifier_labels, float latitude, float longitude, uint32_t month,
+                                          uint32_t day) const {
+    const std::vector<float> data = scores(latitude, longitude, month, day);
+    std::unordered_map<std::string, float> by_label;  // a later duplicate overrides an earlier one, as in filter_predictions
+    for (size_t i = 0; i < data.size() && i < inner_->labels.size(); i++) by_label[inner_->labels[i]] = data[i];
+    std::vector<float> row(classifier_labels.size(), BN_PRIOR_UNKNOWN);
+    for (size_t j = 0; j < classifier_labels.size(); j++) {
+        auto it = by_label.find(classifier_labels[j]);
+        if (it != by_label.end()) row[j] = it->second;
+    }
+    return row;
 }
 
 std::vector<Prediction> RangeFilter::filter_predictions(const std::vector<Prediction> &predictions, const std::vector<LocationScore> &location_scores,

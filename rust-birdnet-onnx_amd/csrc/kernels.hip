@@ -74,6 +74,7 @@ void register_gemm_dma_kernels();  // gemm_dma.hip
 void register_mbmap_kernels();     // mbmap.hip
 void register_mbmap_ws_kernels();  // mbmap_ws.hip
 void register_gemm_dma3_kernels();  // gemm_dma3.hip
+void register_prior_kernels();      // prior.hip
 
 bool prepare_device(int dev) {
     if (dev < 0 || dev >= 64) return false;
@@ -88,6 +89,7 @@ bool prepare_device(int dev) {
         register_mbmap_kernels();
         register_mbmap_ws_kernels();
         register_gemm_dma3_kernels();
+        register_prior_kernels();
     }
     int cur = -1;
     if (hipGetDevice(&cur) != hipSuccess) return false;

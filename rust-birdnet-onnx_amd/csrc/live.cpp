@@ -680,6 +680,8 @@ bn_status bn_step_live(bn_ctx *c, bn_live *l, size_t max_windows, size_t top_k, 
     if (ci.device != l->device) return invalid("pool and context live on different devices");
     if (ci.sample_count != l->S)
         return invalid("the context's model takes " + std::to_string(ci.sample_count) + "-sample segments, the pool cuts " + std::to_string(l->S));
+    bn::PriorAttach *prior = bn::ctx_prior(c);
+    if (prior && (st = bn::prior_live_check(prior, l->src.size())) != BN_OK) return st;
     const size_t B = std::min(max_windows, l->queue.size());
     if (B == 0) return BN_OK;
     LIVE_TRY(bn::use_device(l->device));
@@ -740,7 +742,11 @@ bn_status bn_step_live(bn_ctx *c, bn_live *l, size_t max_windows, size_t top_k, 
     }
     // the windows are taken from here on: on a failure of the step itself *n_out still names them (their results are lost)
     *n_out = B;
-    return bn_step_device(c, ci.d_input, B, top_k, has_min, min_conf, sync);
+    // the rows' sites by their sources, in pinned memory the prior kernel reads in place: no copy, no synchronisation
+    if (prior && (st = bn::prior_stage_rows(prior, source_out, B)) != BN_OK) return st;
+    st = bn_step_device(c, ci.d_input, B, top_k, has_min, min_conf, sync);
+    if (prior) bn::prior_clear_rows(prior);
+    return st;
 }
 
 }  // extern "C"

@@ -116,7 +116,8 @@
     X(integer,     BN_MM_DBG,             0,      "bit mask: mbmap.hip skips phases to time the rest (wrong results)") \
     X(integer,     BN_STFT_DBG,           0,      "bit mask: the STFT KERNEL skips phases to time the rest (wrong results); not BN_STFT_DEBUG") \
     X(present,     BN_TOPK_EXACT,         false,  "top-K by the exact heap kernel alone, without the flagged fast path (presence only: =0 also forces it)") \
-    X(present,     BN_TOPK_TWOPASS,       false,  "the fast top-K path by its general kernel even where the in-register one serves the row length (presence only)")
+    X(present,     BN_TOPK_TWOPASS,       false,  "the fast top-K path by its general kernel even where the in-register one serves the row length (presence only)") \
+    X(present,     BN_PRIOR_GENERAL,      false,  "priors attached or applied from here on keep the select kernel's keys in global scratch, as rows over 16384 species do (presence only)")
 // clang-format on
 
 namespace bn {
