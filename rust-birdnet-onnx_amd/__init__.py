@@ -399,6 +399,18 @@ class EngineError(RuntimeError):
         self.status = status
 
 
+def _min_args(min_confidence: Optional[float]):
+    """The (has_min, min_conf) pair of arguments the C ABI takes for an optional minimum confidence."""
+    return 0 if min_confidence is None else 1, C.c_float(min_confidence or 0.0)
+
+
+def _step_arrays(batch: int, k: int, ix, cf, ct, lg=None, n: int = 0):
+    """Copies of the pinned results of a step: (idx [batch, k], conf [batch, k], count [batch]), behind logits [batch, n] if given."""
+    rows = (np.ctypeslib.as_array(ix, shape=(batch, k)).copy(), np.ctypeslib.as_array(cf, shape=(batch, k)).copy(),
+            np.ctypeslib.as_array(ct, shape=(batch,)).copy())
+    return rows if lg is None else (np.ctypeslib.as_array(lg, shape=(batch, n)).copy(),) + rows
+
+
 class CancellationToken:
     """reference src/inference_options.rs:24-47 (an int32 flag shared with the C ABI)."""
 
@@ -808,7 +820,7 @@ class Context:
         b = len(rows)
         ptrs = (f32p * max(b, 1))(*[r.ctypes.data_as(f32p) for r in rows])
         t = C.c_uint64(0)
-        st = lib.bn_infer_submit(self._h, ptrs, b, top_k, 0 if min_confidence is None else 1, C.c_float(min_confidence or 0.0), C.byref(t))
+        st = lib.bn_infer_submit(self._h, ptrs, b, top_k, *_min_args(min_confidence), C.byref(t))
         if st:
             raise EngineError(st)
         self._tickets = getattr(self, "_tickets", {})
@@ -843,8 +855,7 @@ class Context:
     def step_device(self, d_ptr: int, batch: int, top_k: int = 10, min_confidence: Optional[float] = None,
                     sync: bool = False):
         """One whole hot-path pass (plan + top-K + D2H of logits / top-K) on a device-resident batch."""
-        st = lib.bn_step_device(self._h, C.c_void_p(d_ptr), batch, top_k, 0 if min_confidence is None else 1,
-                                C.c_float(min_confidence or 0.0), 1 if sync else 0)
+        st = lib.bn_step_device(self._h, C.c_void_p(d_ptr), batch, top_k, *_min_args(min_confidence), 1 if sync else 0)
         if st:
             raise EngineError(st)
 
@@ -854,10 +865,7 @@ class Context:
         st = lib.bn_step_results(self._h, C.byref(lg), C.byref(ix), C.byref(cf), C.byref(ct), C.byref(ks))
         if st:
             raise EngineError(st)
-        n = self.output_device(self.model.config.logits_output)[1]
-        k = ks.value
-        return (np.ctypeslib.as_array(lg, shape=(batch, n)).copy(), np.ctypeslib.as_array(ix, shape=(batch, k)).copy(),
-                np.ctypeslib.as_array(cf, shape=(batch, k)).copy(), np.ctypeslib.as_array(ct, shape=(batch,)).copy())
+        return _step_arrays(batch, ks.value, ix, cf, ct, lg, self.output_device(self.model.config.logits_output)[1])
 
     def synchronize(self):
         st = lib.bn_ctx_synchronize(self._h)
@@ -886,8 +894,7 @@ class Context:
         conf = np.zeros((batch, k), dtype=np.float32)
         cnt = np.zeros(batch, dtype=np.uint32)
         u32p = C.POINTER(C.c_uint32)
-        st = lib.bn_topk(self._h, batch, top_k, 0 if min_confidence is None else 1,
-                         C.c_float(min_confidence or 0.0), k, idx.ctypes.data_as(u32p),
+        st = lib.bn_topk(self._h, batch, top_k, *_min_args(min_confidence), k, idx.ctypes.data_as(u32p),
                          conf.ctypes.data_as(C.POINTER(C.c_float)), cnt.ctypes.data_as(u32p))
         if st:
             raise EngineError(st)
@@ -911,8 +918,7 @@ class Context:
     def step_windows(self, rec: "Recording", step_samples: int, first: int, count: int, top_k: int = 10,
                      min_confidence: Optional[float] = None, sync: bool = False):
         """bn_step_windows: one asynchronous hot-path pass over windows of an uploaded recording."""
-        st = lib.bn_step_windows(self._h, rec._h, step_samples, first, count, top_k, 0 if min_confidence is None else 1,
-                                 C.c_float(min_confidence or 0.0), 1 if sync else 0)
+        st = lib.bn_step_windows(self._h, rec._h, step_samples, first, count, top_k, *_min_args(min_confidence), 1 if sync else 0)
         if st:
             raise EngineError(st)
 
@@ -923,7 +929,7 @@ class Context:
         src = np.zeros(max(max_windows, 1), dtype=np.int32)
         win = np.zeros(max(max_windows, 1), dtype=np.uint64)
         n = C.c_size_t()
-        st = lib.bn_step_live(self._h, live._h, max_windows, top_k, 0 if min_confidence is None else 1, C.c_float(min_confidence or 0.0),
+        st = lib.bn_step_live(self._h, live._h, max_windows, top_k, *_min_args(min_confidence),
                               src.ctypes.data_as(C.POINTER(C.c_int32)), win.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(n), 1 if sync else 0)
         if st:
             raise EngineError(st)
@@ -935,7 +941,7 @@ class Context:
         step_windows, every row is at the context's site (set_prior_site, 0 after every attach)."""
         m = None if source_sites is None else np.ascontiguousarray(source_sites, dtype=np.int32).reshape(-1)
         st = lib.bn_ctx_attach_prior(self._h, None if prior is None else prior._h, None if m is None else m.ctypes.data_as(C.POINTER(C.c_int32)),
-                                     0 if m is None else m.shape[0], top_k, 0 if min_confidence is None else 1, C.c_float(min_confidence or 0.0))
+                                     0 if m is None else m.shape[0], top_k, *_min_args(min_confidence))
         if st:
             raise EngineError(st)
         self._prior = prior
@@ -952,14 +958,11 @@ class Context:
         st = lib.bn_step_prior_results(self._h, C.byref(ix), C.byref(cf), C.byref(ct), C.byref(ks))
         if st:
             raise EngineError(st)
-        k = ks.value
-        return (np.ctypeslib.as_array(ix, shape=(batch, k)).copy(), np.ctypeslib.as_array(cf, shape=(batch, k)).copy(),
-                np.ctypeslib.as_array(ct, shape=(batch,)).copy())
+        return _step_arrays(batch, ks.value, ix, cf, ct)
 
     def attach_head(self, head: Optional["Head"], top_k: int = 10, min_confidence: Optional[float] = None):
         """bn_ctx_attach_head: every later step of this context also runs `head` on the step's embedding rows (None detaches)."""
-        st = lib.bn_ctx_attach_head(self._h, None if head is None else head._h, top_k, 0 if min_confidence is None else 1,
-                                    C.c_float(min_confidence or 0.0))
+        st = lib.bn_ctx_attach_head(self._h, None if head is None else head._h, top_k, *_min_args(min_confidence))
         if st:
             raise EngineError(st)
         self._head = head
@@ -971,9 +974,7 @@ class Context:
         st = lib.bn_step_head_results(self._h, C.byref(lg), C.byref(ix), C.byref(cf), C.byref(ct), C.byref(ks), C.byref(nc))
         if st:
             raise EngineError(st)
-        k, n = ks.value, nc.value
-        return (np.ctypeslib.as_array(lg, shape=(batch, n)).copy(), np.ctypeslib.as_array(ix, shape=(batch, k)).copy(),
-                np.ctypeslib.as_array(cf, shape=(batch, k)).copy(), np.ctypeslib.as_array(ct, shape=(batch,)).copy())
+        return _step_arrays(batch, ks.value, ix, cf, ct, lg, nc.value)
 
     def time_kernels(self, batch: int):
         cap = 1024
@@ -1333,7 +1334,7 @@ class Prior:
         cnt = np.zeros(x.shape[0], dtype=np.uint32)
         u32p = C.POINTER(C.c_uint32)
         st = lib.bn_prior_apply_host(self._h, x.ctypes.data_as(C.POINTER(C.c_float)), x.shape[0], sv.ctypes.data_as(C.POINTER(C.c_int32)), top_k,
-                                     0 if min_confidence is None else 1, C.c_float(min_confidence or 0.0), ks, idx.ctypes.data_as(u32p),
+                                     *_min_args(min_confidence), ks, idx.ctypes.data_as(u32p),
                                      conf.ctypes.data_as(C.POINTER(C.c_float)), cnt.ctypes.data_as(u32p))
         if st:
             raise EngineError(st)
@@ -1590,7 +1591,7 @@ def topk_host(logits: np.ndarray, top_k: int, min_confidence: Optional[float] = 
     cnt = np.zeros(rows, dtype=np.uint32)
     u32p = C.POINTER(C.c_uint32)
     st = lib.bn_topk_host(device, a.ctypes.data_as(C.POINTER(C.c_float)), rows, n, min(top_k, 2 ** 63 - 1),
-                          0 if min_confidence is None else 1, C.c_float(min_confidence or 0.0), k,
+                          *_min_args(min_confidence), k,
                           idx.ctypes.data_as(u32p), conf.ctypes.data_as(C.POINTER(C.c_float)), cnt.ctypes.data_as(u32p))
     if st:
         raise EngineError(st)
@@ -1648,7 +1649,7 @@ class Group:
         idx, conf, cnt = np.zeros((G, max(k, 1)), dtype=np.uint32), np.zeros((G, max(k, 1)), dtype=np.float32), np.zeros(G, dtype=np.uint32)
         ng = C.c_size_t(0)
         st = lib.bn_group_analyze_recording(self._h, x.ctypes.data_as(C.c_void_p), x.shape[0], fmt, step_samples, top_k,
-                                            0 if min_confidence is None else 1, C.c_float(min_confidence or 0.0),
+                                            *_min_args(min_confidence),
                                             None if logits is None else logits.ctypes.data_as(f32p), max(k, 1), idx.ctypes.data_as(u32p),
                                             conf.ctypes.data_as(f32p), cnt.ctypes.data_as(u32p), C.byref(ng))
         if st:

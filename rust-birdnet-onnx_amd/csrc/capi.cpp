@@ -37,12 +37,6 @@ bn_status fail(bn_status st, const std::string &msg) {
     g_err = msg;
     return st;
 }
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess)                                                                      \
-            return fail(BN_ERR_BACKEND, std::string(#expr) + " failed: " + hipGetErrorString(e_)); \
-    } while (0)
 
 struct PlanDev {
     std::unique_ptr<Plan> plan;
@@ -172,14 +166,9 @@ struct bn_ctx {
     uint32_t *d_tk_idx = nullptr, *d_tk_cnt = nullptr, *d_tk_flags = nullptr;
     float *d_tk_conf = nullptr;
     size_t tk_cap = 0;  // elements of idx/conf
-    // pinned mirrors for bn_step_device
-    // bn_step_device: top-K rows of a step live packed [idx: batch*k][conf: batch*k][count: batch] in one device block
-    // and one pinned host block, so they cross the bus as ONE copy (each async copy is a ~7 us blit launch)
-    uint32_t *d_step = nullptr, *h_step = nullptr;
-    size_t step_cap = 0;  // words
-    uint32_t *h_tk_idx = nullptr, *h_tk_cnt = nullptr;  // views into h_step for the last step
-    float *h_tk_conf = nullptr;
-    size_t step_k = 0;
+    // bn_step_device: the top-K rows of a step in one device block and one pinned mirror, so they cross the bus as ONE copy (each
+    // async copy is a ~7 us blit launch); bn_infer_submit fills the device block too, its mirror is the slot's
+    bn::TopkRows step;
     bn::HeadAttach *head = nullptr;  // bn_ctx_attach_head: run after every step's own work (head.hip)
     bn::PriorAttach *prior = nullptr;  // bn_ctx_attach_prior: the same, on the step's logits rows (prior.hip)
     // ---- asynchronous host-slice path (bn_infer_submit / bn_infer_collect): a ring of two batches per context.
@@ -188,8 +177,7 @@ struct bn_ctx {
     // top-K block, and those are ordered by the context's stream.
     struct HostSlot {
         float *d_input = nullptr, *h_input = nullptr, *h_out = nullptr;
-        uint32_t *h_tk = nullptr;  // pinned [idx: batch*k][conf: batch*k][count: batch]
-        size_t tk_cap = 0;         // words
+        bn::TopkRows tk;  // pinned only
         hipEvent_t h2d_done = nullptr, plan_done = nullptr, out_done = nullptr;
         bool owned = false, used = false, busy = false;
         uint64_t ticket = 0;
@@ -334,10 +322,11 @@ bn_status enqueue_plan(bn_ctx *c, const float *d_in, size_t batch, const volatil
     // copied in on the context's stream, ahead of the plan: 18 MB at batch 32, about 10 us.
     if (d_in != c->d_input) {
         static const bool runtime_copy = sw_int(sw::BN_INPUT_MEMCPY) != 0;
-        if (runtime_copy) HIP_TRY(hipMemcpyAsync(c->d_input, d_in, batch * (size_t)p.sample_count * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+        if (runtime_copy) BN_HIP_TRY(hipMemcpyAsync(c->d_input, d_in, batch * (size_t)p.sample_count * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
         else {
             launch_copy_dev(c->stream, c->d_input, d_in, batch * (size_t)p.sample_count * sizeof(float));
-            HIP_TRY(hipGetLastError());
+            bn_status st = check_launch("input copy");
+            if (st != BN_OK) return st;
         }
         c->n_input_copies++;
         d_in = c->d_input;
@@ -356,7 +345,7 @@ bn_status enqueue_plan(bn_ctx *c, const float *d_in, size_t batch, const volatil
             // ranks) is none of this capture's business.
             std::unique_lock<std::shared_mutex> capture_lock(capture_gate());  // hip_gate.h: no allocation / free / synchronous copy of the library overlaps a capture
             (void)hipGetLastError();  // drop stale sticky errors of unrelated earlier calls
-            HIP_TRY(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+            BN_HIP_TRY(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
             c->n_captures++;
             hipError_t le = hipSuccess;
             std::string bad;
@@ -418,7 +407,7 @@ bn_status enqueue_plan(bn_ctx *c, const float *d_in, size_t batch, const volatil
         }
         if (use_graph) {
             c->graph_used[it->first] = ++c->graph_tick;
-            HIP_TRY(hipGraphLaunch(it->second, c->stream));
+            BN_HIP_TRY(hipGraphLaunch(it->second, c->stream));
             c->n_replays++;
         }
     }
@@ -439,9 +428,23 @@ bn_status enqueue_plan(bn_ctx *c, const float *d_in, size_t batch, const volatil
 
 bn_status drain_if_needed(bn_ctx *c) {
     if (c->in_flight) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
+        BN_HIP_TRY(hipStreamSynchronize(c->stream));
         c->in_flight = false;
     }
+    return BN_OK;
+}
+
+// the tail of an attach: `fresh` (NULL: detach only) takes the place of *slot once the context's stream is idle -- the previous
+// attachment's buffers may still be read by a step in flight
+template <class A>
+bn_status install_attachment(hipStream_t stream, A *&slot, A *fresh, void (*detach)(A *)) {
+    hipError_t e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) {
+        detach(fresh);
+        return fail(BN_ERR_BACKEND, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
+    }
+    detach(slot);
+    slot = fresh;
     return BN_OK;
 }
 
@@ -449,7 +452,7 @@ bn_status drain_if_needed(bn_ctx *c) {
 // 10 ms; here the stream is polled, so a finished batch is never reported as timed out).
 bn_status wait_stream(bn_ctx *c, const volatile int32_t *cancel, uint64_t timeout_ns) {
     if (!cancel && timeout_ns == 0) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
+        BN_HIP_TRY(hipStreamSynchronize(c->stream));
         return BN_OK;
     }
     const auto start = std::chrono::steady_clock::now();
@@ -483,13 +486,13 @@ bn_status make_plan(bn_model *m, const std::vector<int> &wanted, std::unique_ptr
     } catch (const std::exception &e) {
         return fail(BN_ERR_MODEL_LOAD, e.what());
     }
-    HIP_TRY(bn::use_device(m->device));
+    BN_HIP_TRY(bn::use_device(m->device));
     if (!prepare_device(m->device)) return fail(BN_ERR_BACKEND, "device " + std::to_string(m->device) + " refused the kernels' dynamic-LDS opt-in");
     const Plan &p = *pd->plan;
-    HIP_TRY(gated::Malloc(&pd->d_consts, (size_t)p.consts_elems * sizeof(float)));
+    BN_HIP_TRY(gated::Malloc(&pd->d_consts, (size_t)p.consts_elems * sizeof(float)));
     for (size_t k = 0; k < p.consts.size(); k++)
         if (!p.consts[k].empty())
-            HIP_TRY(gated::Memcpy(pd->d_consts + p.const_off[k], p.consts[k].data(), p.consts[k].size() * sizeof(float), hipMemcpyHostToDevice));
+            BN_HIP_TRY(gated::Memcpy(pd->d_consts + p.const_off[k], p.consts[k].data(), p.consts[k].size() * sizeof(float), hipMemcpyHostToDevice));
     out = std::move(pd);
     return BN_OK;
 }
@@ -677,22 +680,22 @@ bn_status bn_ctx_create(bn_model *m, size_t max_batch, uint32_t flags, bn_ctx **
     c->max_batch = max_batch;
     c->flags = flags;
     const Plan &p = *pd->plan;
-    HIP_TRY(bn::use_device(m->device));
+    BN_HIP_TRY(bn::use_device(m->device));
     if (!prepare_device(m->device)) return fail(BN_ERR_BACKEND, "device " + std::to_string(m->device) + " refused the kernels' dynamic-LDS opt-in");
-    HIP_TRY(gated::StreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    BN_HIP_TRY(gated::StreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     const size_t arena_b = (size_t)p.arena_elems * max_batch * sizeof(float);
     const size_t in_b = (size_t)p.sample_count * max_batch * sizeof(float);
-    HIP_TRY(gated::Malloc(&c->d_arena, arena_b));
+    BN_HIP_TRY(gated::Malloc(&c->d_arena, arena_b));
     // the squeeze-excite ticket counters live here and must start at zero; on the context's OWN stream (a legacy-stream
     // hipMemset would serialise against -- and be seen by -- whatever sibling contexts are capturing or running)
-    HIP_TRY(hipMemsetAsync(c->d_arena, 0, arena_b, c->stream));
-    HIP_TRY(gated::Malloc(&c->d_input, in_b));
+    BN_HIP_TRY(hipMemsetAsync(c->d_arena, 0, arena_b, c->stream));
+    BN_HIP_TRY(gated::Malloc(&c->d_input, in_b));
     {
         size_t row = (size_t)p.outputs[m->cfg.logits_output].row_elems;
         if (m->cfg.embedding_output >= 0) row += (size_t)p.outputs[m->cfg.embedding_output].row_elems;
         c->h_out_elems = row * max_batch;
     }
-    HIP_TRY(gated::HostMalloc(&c->h_out, c->h_out_elems * sizeof(float), hipHostMallocDefault));
+    BN_HIP_TRY(gated::HostMalloc(&c->h_out, c->h_out_elems * sizeof(float), hipHostMallocDefault));
     c->device_bytes = arena_b + in_b;
     m->refs.fetch_add(1, std::memory_order_relaxed);
     c->holds_model = true;
@@ -706,7 +709,7 @@ bn_status bn_ctx_create(bn_model *m, size_t max_batch, uint32_t flags, bn_ctx **
             return st;
         }
     }
-    HIP_TRY(hipStreamSynchronize(c->stream));  // arena zeroed before anyone captures or launches
+    BN_HIP_TRY(hipStreamSynchronize(c->stream));  // arena zeroed before anyone captures or launches
     bn::device_context_count_add(m->device, 1);
     c->counted = true;
     *out = c.release();
@@ -728,8 +731,7 @@ void bn_ctx_destroy(bn_ctx *c) {
     if (c->d_tk_conf) (void)gated::Free(c->d_tk_conf);
     if (c->d_tk_cnt) (void)gated::Free(c->d_tk_cnt);
     if (c->d_tk_flags) (void)gated::Free(c->d_tk_flags);
-    if (c->d_step) (void)gated::Free(c->d_step);
-    if (c->h_step) (void)gated::HostFree(c->h_step);
+    c->step.release();
     if (c->copy_stream) {
         (void)hipStreamSynchronize(c->copy_stream);
         (void)gated::StreamDestroy(c->copy_stream);
@@ -740,7 +742,7 @@ void bn_ctx_destroy(bn_ctx *c) {
             if (sl.h_input) (void)gated::HostFree(sl.h_input);
             if (sl.h_out) (void)gated::HostFree(sl.h_out);
         }
-        if (sl.h_tk) (void)gated::HostFree(sl.h_tk);
+        sl.tk.release();
         if (sl.h2d_done) (void)gated::EventDestroy(sl.h2d_done);
         if (sl.plan_done) (void)gated::EventDestroy(sl.plan_done);
         if (sl.out_done) (void)gated::EventDestroy(sl.out_done);
@@ -780,8 +782,8 @@ bn_status bn_ctx_input_device(const bn_ctx *c, float **d_ptr, size_t *capacity_f
 
 bn_status bn_ctx_synchronize(bn_ctx *c) {
     if (!c) return fail(BN_ERR_INVALID_ARG, "null context");
-    HIP_TRY(bn::use_device(c->model->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    BN_HIP_TRY(bn::use_device(c->model->device));
+    BN_HIP_TRY(hipStreamSynchronize(c->stream));
     c->in_flight = false;
     return BN_OK;
 }
@@ -792,47 +794,13 @@ bn_status bn_infer_device(bn_ctx *c, const float *d_pcm, size_t batch, int32_t s
     if (!d_pcm) return fail(BN_ERR_INVALID_ARG, "null input");
     if (reinterpret_cast<uintptr_t>(d_pcm) & 15u) return fail(BN_ERR_INVALID_ARG, "device input must be 16-byte aligned");
     if (batch > c->max_batch) return fail(BN_ERR_INVALID_ARG, "batch size " + std::to_string(batch) + " exceeds context max " + std::to_string(c->max_batch));
-    HIP_TRY(bn::use_device(c->model->device));
+    BN_HIP_TRY(bn::use_device(c->model->device));
     bn_status st = drain_if_needed(c);
     if (st != BN_OK) return st;
     st = enqueue_plan(c, d_pcm, batch, nullptr);
     if (st != BN_OK) return st;
     c->last_batch = batch;
-    if (sync) HIP_TRY(hipStreamSynchronize(c->stream));
-    return BN_OK;
-}
-
-// Device results -> pinned host buffers on the context's stream, by ONE kernel launch storing straight into the
-// (device-mapped) pinned memory (topk.hip, copy_out_kernel) instead of one copy-engine transfer per region.
-// BN_SDMA_COPY=1 restores the hipMemcpyAsync transfers (A/B measurements).
-struct OutRegion {
-    void *host;
-    const void *dev;
-    size_t bytes;
-};
-static bn_status results_to_host(bn_ctx *c, const OutRegion *regs, int n) {
-    static const bool sdma = sw_int(sw::BN_SDMA_COPY) != 0;
-    CopyOut co{};
-    bool kernel_ok = !sdma && n <= 3;
-    for (int r = 0; r < n && kernel_ok; r++) {
-        void *dp = nullptr;
-        if (regs[r].bytes % 4 || regs[r].bytes / 4 > 0xffffffffull || hipHostGetDevicePointer(&dp, regs[r].host, 0) != hipSuccess || !dp) {
-            (void)hipGetLastError();
-            kernel_ok = false;
-            break;
-        }
-        co.dst[r] = dp;
-        co.src[r] = regs[r].dev;
-        co.words[r] = (uint32_t)(regs[r].bytes / 4);
-    }
-    if (kernel_ok) {
-        co.n = n;
-        launch_copy_out(c->stream, co);
-        HIP_TRY(hipGetLastError());
-        return BN_OK;
-    }
-    for (int r = 0; r < n; r++)
-        if (regs[r].bytes) HIP_TRY(hipMemcpyAsync(regs[r].host, regs[r].dev, regs[r].bytes, hipMemcpyDeviceToHost, c->stream));
+    if (sync) BN_HIP_TRY(hipStreamSynchronize(c->stream));
     return BN_OK;
 }
 
@@ -855,7 +823,7 @@ static bn_status finish_infer(bn_ctx *c, size_t batch, float *logits_out, float 
         E = (size_t)eo.row_elems;
         regs[nreg++] = OutRegion{h_emb, resolve(c, eo.ref, c->d_input), batch * E * sizeof(float)};
     }
-    st = results_to_host(c, regs, nreg);
+    st = results_to_host(c->stream, regs, nreg);
     if (st != BN_OK) return st;
     st = wait_stream(c, cancel, timeout_ns);
     if (st != BN_OK) return st;
@@ -869,19 +837,19 @@ static bn_status ensure_step_block(bn_ctx *c, size_t k);
 
 static bn_status ensure_slot(bn_ctx *c, bn_ctx::HostSlot &sl, int index) {
     const Plan &p = *c->pd->plan;
-    if (!c->copy_stream) HIP_TRY(gated::StreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+    if (!c->copy_stream) BN_HIP_TRY(gated::StreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
     if (!sl.h2d_done) {
-        HIP_TRY(gated::EventCreateWithFlags(&sl.h2d_done, hipEventDisableTiming));
-        HIP_TRY(gated::EventCreateWithFlags(&sl.plan_done, hipEventDisableTiming));
-        HIP_TRY(gated::EventCreateWithFlags(&sl.out_done, hipEventDisableTiming));
+        BN_HIP_TRY(gated::EventCreateWithFlags(&sl.h2d_done, hipEventDisableTiming));
+        BN_HIP_TRY(gated::EventCreateWithFlags(&sl.plan_done, hipEventDisableTiming));
+        BN_HIP_TRY(gated::EventCreateWithFlags(&sl.out_done, hipEventDisableTiming));
     }
     if (sl.d_input) return BN_OK;
     (void)index;
     const size_t in_b = (size_t)p.sample_count * c->max_batch * sizeof(float);
     sl.owned = true;
-    HIP_TRY(gated::Malloc(&sl.d_input, in_b));
-    HIP_TRY(gated::HostMalloc(&sl.h_input, in_b, hipHostMallocDefault));
-    HIP_TRY(gated::HostMalloc(&sl.h_out, c->h_out_elems * sizeof(float), hipHostMallocDefault));
+    BN_HIP_TRY(gated::Malloc(&sl.d_input, in_b));
+    BN_HIP_TRY(gated::HostMalloc(&sl.h_input, in_b, hipHostMallocDefault));
+    BN_HIP_TRY(gated::HostMalloc(&sl.h_out, c->h_out_elems * sizeof(float), hipHostMallocDefault));
     c->device_bytes += in_b;
     return BN_OK;
 }
@@ -898,9 +866,12 @@ bn_status bn_infer_submit(bn_ctx *c, const float *const *segs, size_t batch, siz
     const bn_model_config &cfg = c->model->cfg;
     const OutputInfo &lo = p.outputs[cfg.logits_output];
     const size_t N = (size_t)lo.row_elems;
-    const size_t k = std::min(top_k, N);
-    if (k && topk_lds_bytes((int64_t)N, (int64_t)k) == 0) return fail(BN_ERR_INVALID_ARG, "top_k too large for the on-chip heap (k <= 9000)");
-    HIP_TRY(bn::use_device(c->model->device));
+    size_t k = std::min(top_k, N);  // 0: no top-K rows wanted
+    if (k) {
+        bn_status kst = check_top_k(N, top_k, &k);
+        if (kst != BN_OK) return kst;
+    }
+    BN_HIP_TRY(bn::use_device(c->model->device));
     bn_ctx::HostSlot *slp = nullptr;
     int index = 0;
     for (int q = 0; q < 2 && !slp; q++) {
@@ -912,26 +883,20 @@ bn_status bn_infer_submit(bn_ctx *c, const float *const *segs, size_t batch, siz
     bn_status st = ensure_slot(c, sl, index);
     if (st != BN_OK) return st;
     if (c->in_flight) {  // a timed-out / cancelled batch may still be running: let everything settle first
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        HIP_TRY(hipStreamSynchronize(c->copy_stream));
+        BN_HIP_TRY(hipStreamSynchronize(c->stream));
+        BN_HIP_TRY(hipStreamSynchronize(c->copy_stream));
         c->in_flight = false;
     }
     if (k) {
         st = ensure_step_block(c, k);
         if (st != BN_OK) return st;
-        const size_t need = c->max_batch * (2 * k + 1);
-        if (need > sl.tk_cap) {
-            if (sl.h_tk) (void)gated::HostFree(sl.h_tk);
-            sl.h_tk = nullptr;
-            sl.tk_cap = 0;
-            HIP_TRY(gated::HostMalloc(&sl.h_tk, need * sizeof(uint32_t), hipHostMallocDefault));
-            sl.tk_cap = need;
-        }
+        st = sl.tk.reserve(c->max_batch, k, nullptr, false, true);  // (the slot is not busy: nothing writes its block)
+        if (st != BN_OK) return st;
     }
     const size_t S = (size_t)p.sample_count;
     if (sl.used) {
-        HIP_TRY(hipEventSynchronize(sl.h2d_done));                      // the pinned buffer's last upload has left it
-        HIP_TRY(hipStreamWaitEvent(c->copy_stream, sl.plan_done, 0));  // the plan that read the device buffer is through
+        BN_HIP_TRY(hipEventSynchronize(sl.h2d_done));                      // the pinned buffer's last upload has left it
+        BN_HIP_TRY(hipStreamWaitEvent(c->copy_stream, sl.plan_done, 0));  // the plan that read the device buffer is through
     }
     // stage + upload in chunks: pool threads (and this one) copy segment by segment; a chunk goes on the wire as soon
     // as its segments have landed in pinned memory, while the later chunks are still being copied
@@ -965,23 +930,19 @@ bn_status bn_infer_submit(bn_ctx *c, const float *const *segs, size_t batch, siz
         if (e != hipSuccess) return fail(BN_ERR_BACKEND, std::string("input upload failed: ") + hipGetErrorString(e));
     }
     sl.used = true;
-    HIP_TRY(hipEventRecord(sl.h2d_done, c->copy_stream));
-    HIP_TRY(hipStreamWaitEvent(c->stream, sl.h2d_done, 0));
+    BN_HIP_TRY(hipEventRecord(sl.h2d_done, c->copy_stream));
+    BN_HIP_TRY(hipStreamWaitEvent(c->stream, sl.h2d_done, 0));
     st = enqueue_plan(c, sl.d_input, batch, nullptr);
     if (st != BN_OK) {
         c->in_flight = true;
         return st;
     }
-    HIP_TRY(hipEventRecord(sl.plan_done, c->stream));
+    BN_HIP_TRY(hipEventRecord(sl.plan_done, c->stream));
     c->last_batch = batch;
     const float *d_logits = resolve(c, lo.ref, sl.d_input);
     if (k) {
-        (void)hipGetLastError();
-        uint32_t *d_idx = c->d_step, *d_cnt = c->d_step + 2 * batch * k;
-        float *d_conf = reinterpret_cast<float *>(c->d_step + batch * k);
-        launch_topk(c->stream, d_logits, (int64_t)batch, (int64_t)N, (int64_t)k, has_min, min_conf, (int64_t)k, d_idx, d_conf, d_cnt, c->d_tk_flags);
-        if (const char *why = take_launch_error()) return fail(BN_ERR_INVALID_ARG, std::string("top-K launch refused: ") + why);
-        HIP_TRY(hipGetLastError());
+        st = enqueue_topk_rows(c->stream, d_logits, batch, N, k, has_min, min_conf, TopkRows::view(c->step.d, batch, k), c->d_tk_flags);
+        if (st != BN_OK) return st;
     }
     {
         OutRegion regs[3] = {{sl.h_out, d_logits, batch * N * sizeof(float)}, {nullptr, nullptr, 0}, {nullptr, nullptr, 0}};
@@ -990,14 +951,14 @@ bn_status bn_infer_submit(bn_ctx *c, const float *const *segs, size_t batch, siz
             const OutputInfo &eo = p.outputs[cfg.embedding_output];
             regs[nreg++] = OutRegion{sl.h_out + N * c->max_batch, resolve(c, eo.ref, sl.d_input), batch * (size_t)eo.row_elems * sizeof(float)};
         }
-        if (k) regs[nreg++] = OutRegion{sl.h_tk, c->d_step, batch * (2 * k + 1) * sizeof(uint32_t)};
-        st = results_to_host(c, regs, nreg);
+        if (k) regs[nreg++] = OutRegion{sl.tk.h, c->step.d, TopkRows::bytes(batch, k)};
+        st = results_to_host(c->stream, regs, nreg);
         if (st != BN_OK) {
             c->in_flight = true;
             return st;
         }
     }
-    HIP_TRY(hipEventRecord(sl.out_done, c->stream));
+    BN_HIP_TRY(hipEventRecord(sl.out_done, c->stream));
     sl.busy = true;
     sl.batch = batch;
     sl.k = k;
@@ -1016,7 +977,7 @@ bn_status bn_infer_collect(bn_ctx *c, uint64_t ticket, float *logits_out, float 
     if (!slp) return fail(BN_ERR_INVALID_ARG, "unknown or already collected ticket");
     bn_ctx::HostSlot &sl = *slp;
     // batches complete in submission order: collecting the younger one first simply waits for both
-    HIP_TRY(bn::use_device(c->model->device));
+    BN_HIP_TRY(bn::use_device(c->model->device));
     const auto start = std::chrono::steady_clock::now();
     int spins = 0;
     while (true) {
@@ -1069,13 +1030,12 @@ bn_status bn_infer_collect(bn_ctx *c, uint64_t ticket, float *logits_out, float 
                 sl.busy = false;
                 return fail(BN_ERR_INVALID_ARG, "top-K outputs need idx / conf buffers with k_stride >= min(top_k, num_species)");
             }
-            const uint32_t *h_idx = sl.h_tk, *h_cnt = sl.h_tk + 2 * batch * k;
-            const float *h_conf = reinterpret_cast<const float *>(sl.h_tk + batch * k);
+            const TopkRows::ConstView v = TopkRows::view(static_cast<const uint32_t *>(sl.tk.h), batch, k);
             for (size_t r = 0; r < batch; r++) {
-                count_out[r] = h_cnt[r];
-                for (size_t j = 0; j < h_cnt[r]; j++) {
-                    idx_out[r * k_stride + j] = h_idx[r * k + j];
-                    conf_out[r * k_stride + j] = h_conf[r * k + j];
+                count_out[r] = v.count[r];
+                for (size_t j = 0; j < v.count[r]; j++) {
+                    idx_out[r * k_stride + j] = v.idx[r * k + j];
+                    conf_out[r * k_stride + j] = v.conf[r * k + j];
                 }
             }
         }
@@ -1112,10 +1072,10 @@ bn_status bn_ctx_read_output(bn_ctx *c, int32_t index, size_t batch, float *host
     bn_status st = bn_ctx_output_device(c, index, &d, &row);
     if (st != BN_OK) return st;
     if (!host_out || batch > c->max_batch) return fail(BN_ERR_INVALID_ARG, "bad host buffer / batch");
-    HIP_TRY(bn::use_device(c->model->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    BN_HIP_TRY(bn::use_device(c->model->device));
+    BN_HIP_TRY(hipStreamSynchronize(c->stream));
     c->in_flight = false;
-    HIP_TRY(gated::Memcpy(host_out, d, batch * row * sizeof(float), hipMemcpyDeviceToHost));
+    BN_HIP_TRY(gated::Memcpy(host_out, d, batch * row * sizeof(float), hipMemcpyDeviceToHost));
     return BN_OK;
 }
 
@@ -1193,18 +1153,17 @@ static bn_status topk_run(int device, hipStream_t stream, const float *d_logits,
                           float min_conf, size_t k_stride, uint32_t *d_idx, float *d_conf, uint32_t *d_cnt, uint32_t *d_flags,
                           uint32_t *idx_out, float *conf_out, uint32_t *count_out) {
     (void)device;
-    const size_t k = std::min(top_k, n);
+    size_t k = 0;  // (not 0 below: the callers answer an empty selection themselves)
+    bn_status st = check_top_k(n, top_k, &k);
+    if (st != BN_OK) return st;
     if (k_stride < k) return fail(BN_ERR_INVALID_ARG, "k_stride smaller than min(top_k, n)");
-    if (topk_lds_bytes((int64_t)n, (int64_t)k) == 0) return fail(BN_ERR_INVALID_ARG, "top_k too large for the on-chip heap (k <= 9000)");
-    (void)hipGetLastError();
-    launch_topk(stream, d_logits, (int64_t)rows, (int64_t)n, (int64_t)k, has_min, min_conf, (int64_t)k, d_idx, d_conf, d_cnt, d_flags);
-    HIP_TRY(hipGetLastError());
+    if ((st = enqueue_topk_rows(stream, d_logits, rows, n, k, has_min, min_conf, TopkRows::View{d_idx, d_conf, d_cnt, k}, d_flags)) != BN_OK) return st;
     std::vector<uint32_t> h_idx(rows * k), h_cnt(rows);
     std::vector<float> h_conf(rows * k);
-    HIP_TRY(hipMemcpyAsync(h_cnt.data(), d_cnt, rows * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipMemcpyAsync(h_idx.data(), d_idx, rows * k * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipMemcpyAsync(h_conf.data(), d_conf, rows * k * sizeof(float), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
+    BN_HIP_TRY(hipMemcpyAsync(h_cnt.data(), d_cnt, rows * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    BN_HIP_TRY(hipMemcpyAsync(h_idx.data(), d_idx, rows * k * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    BN_HIP_TRY(hipMemcpyAsync(h_conf.data(), d_conf, rows * k * sizeof(float), hipMemcpyDeviceToHost, stream));
+    BN_HIP_TRY(hipStreamSynchronize(stream));
     for (size_t r = 0; r < rows; r++) {
         count_out[r] = h_cnt[r];
         for (size_t j = 0; j < h_cnt[r]; j++) {
@@ -1231,7 +1190,7 @@ bn_status bn_topk(bn_ctx *c, size_t batch, size_t top_k, int32_t has_min, float 
         return BN_OK;
     }
     if (!idx_out || !conf_out) return fail(BN_ERR_INVALID_ARG, "null output");
-    HIP_TRY(bn::use_device(c->model->device));
+    BN_HIP_TRY(bn::use_device(c->model->device));
     {
         bn_status est = ensure_topk_buffers(c, k);
         if (est != BN_OK) return est;
@@ -1247,12 +1206,12 @@ static bn_status ensure_topk_buffers(bn_ctx *c, size_t k) {
         if (c->d_tk_conf) (void)gated::Free(c->d_tk_conf);
         c->d_tk_idx = nullptr;
         c->d_tk_conf = nullptr;
-        HIP_TRY(gated::Malloc(&c->d_tk_idx, need * sizeof(uint32_t)));
-        HIP_TRY(gated::Malloc(&c->d_tk_conf, need * sizeof(float)));
+        BN_HIP_TRY(gated::Malloc(&c->d_tk_idx, need * sizeof(uint32_t)));
+        BN_HIP_TRY(gated::Malloc(&c->d_tk_conf, need * sizeof(float)));
         c->tk_cap = need;
     }
-    if (!c->d_tk_cnt) HIP_TRY(gated::Malloc(&c->d_tk_cnt, c->max_batch * sizeof(uint32_t)));
-    if (!c->d_tk_flags) HIP_TRY(gated::Malloc(&c->d_tk_flags, c->max_batch * sizeof(uint32_t)));
+    if (!c->d_tk_cnt) BN_HIP_TRY(gated::Malloc(&c->d_tk_cnt, c->max_batch * sizeof(uint32_t)));
+    if (!c->d_tk_flags) BN_HIP_TRY(gated::Malloc(&c->d_tk_flags, c->max_batch * sizeof(uint32_t)));
     return BN_OK;
 }
 
@@ -1261,20 +1220,7 @@ static bn_status ensure_topk_buffers(bn_ctx *c, size_t k) {
 static bn_status ensure_step_block(bn_ctx *c, size_t k) {
     bn_status st = ensure_topk_buffers(c, k);
     if (st != BN_OK) return st;
-    const size_t need = c->max_batch * (2 * k + 1);
-    if (need > c->step_cap) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (c->d_step) (void)gated::Free(c->d_step);
-        if (c->h_step) (void)gated::HostFree(c->h_step);
-        c->d_step = c->h_step = nullptr;
-        c->h_tk_idx = c->h_tk_cnt = nullptr;
-        c->h_tk_conf = nullptr;
-        c->step_cap = 0;
-        HIP_TRY(gated::Malloc(&c->d_step, need * sizeof(uint32_t)));
-        HIP_TRY(gated::HostMalloc(&c->h_step, need * sizeof(uint32_t), hipHostMallocDefault));
-        c->step_cap = need;
-    }
-    return BN_OK;
+    return c->step.reserve(c->max_batch, k, c->stream, true, true);
 }
 
 bn_status bn_step_device(bn_ctx *c, const float *d_pcm, size_t batch, size_t top_k, int32_t has_min, float min_conf, int32_t sync) {
@@ -1285,10 +1231,11 @@ bn_status bn_step_device(bn_ctx *c, const float *d_pcm, size_t batch, size_t top
     const Plan &p = *c->pd->plan;
     const OutputInfo &lo = p.outputs[c->model->cfg.logits_output];
     const size_t n = (size_t)lo.row_elems;
-    const size_t k = std::min(top_k, n);
-    if (k == 0 || topk_lds_bytes((int64_t)n, (int64_t)k) == 0) return fail(BN_ERR_INVALID_ARG, "top_k must be in 1..9000");
-    HIP_TRY(bn::use_device(c->model->device));
-    bn_status st = drain_if_needed(c);
+    size_t k = 0;
+    bn_status st = check_top_k(n, top_k, &k);
+    if (st != BN_OK) return st;
+    BN_HIP_TRY(bn::use_device(c->model->device));
+    st = drain_if_needed(c);
     if (st != BN_OK) return st;
     st = ensure_step_block(c, k);
     if (st != BN_OK) return st;
@@ -1296,37 +1243,31 @@ bn_status bn_step_device(bn_ctx *c, const float *d_pcm, size_t batch, size_t top
     if (st != BN_OK) return st;
     c->last_batch = batch;
     const float *d_logits = resolve(c, lo.ref, d_pcm);
-    (void)hipGetLastError();
-    uint32_t *d_idx = c->d_step, *d_cnt = c->d_step + 2 * batch * k;
-    float *d_conf = reinterpret_cast<float *>(c->d_step + batch * k);
-    launch_topk(c->stream, d_logits, (int64_t)batch, (int64_t)n, (int64_t)k, has_min, min_conf, (int64_t)k, d_idx, d_conf, d_cnt, c->d_tk_flags);
-    HIP_TRY(hipGetLastError());
+    st = enqueue_topk_rows(c->stream, d_logits, batch, n, k, has_min, min_conf, TopkRows::view(c->step.d, batch, k), c->d_tk_flags);
+    if (st != BN_OK) return st;
     {
-        const OutRegion regs[2] = {{c->h_out, d_logits, batch * n * sizeof(float)}, {c->h_step, c->d_step, batch * (2 * k + 1) * sizeof(uint32_t)}};
-        st = results_to_host(c, regs, 2);
+        const OutRegion regs[2] = {{c->h_out, d_logits, batch * n * sizeof(float)}, {c->step.h, c->step.d, TopkRows::bytes(batch, k)}};
+        st = results_to_host(c->stream, regs, 2);
         if (st != BN_OK) return st;
     }
-    c->h_tk_idx = c->h_step;
-    c->h_tk_conf = reinterpret_cast<float *>(c->h_step + batch * k);
-    c->h_tk_cnt = c->h_step + 2 * batch * k;
-    c->step_k = k;
+    c->step.mark(batch, k);
     if (c->head) {
         const OutputInfo &eo = p.outputs[c->model->cfg.embedding_output];
         st = bn::head_step(c->head, c->stream, resolve(c, eo.ref, d_pcm), batch);
         if (st != BN_OK) return st;
     }
     if (c->prior) {
-        st = bn::prior_step(c->prior, c->stream, d_logits, batch, c->d_step, k);
+        st = bn::prior_step(c->prior, c->stream, d_logits, batch, TopkRows::view(static_cast<const uint32_t *>(c->step.d), batch, k));
         if (st != BN_OK) return st;
     }
-    if (sync) HIP_TRY(hipStreamSynchronize(c->stream));
+    if (sync) BN_HIP_TRY(hipStreamSynchronize(c->stream));
     return BN_OK;
 }
 
 bn_status bn_ctx_attach_head(bn_ctx *c, bn_head *h, size_t top_k, int32_t has_min, float min_conf) {
     if (!c) return fail(BN_ERR_INVALID_ARG, "null context");
     const bn_model_config &cfg = c->model->cfg;
-    HIP_TRY(bn::use_device(c->model->device));
+    BN_HIP_TRY(bn::use_device(c->model->device));
     bn::HeadAttach *a = nullptr;
     if (h) {
         const bool has_emb = cfg.has_embedding && cfg.embedding_output >= 0 && c->pd->plan->outputs[cfg.embedding_output].computed;
@@ -1334,15 +1275,7 @@ bn_status bn_ctx_attach_head(bn_ctx *c, bn_head *h, size_t top_k, int32_t has_mi
                                        c->max_batch, top_k, has_min, min_conf, &a);
         if (st != BN_OK) return st;
     }
-    // the previous attachment's buffers may still be read by a step in flight
-    hipError_t e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) {
-        bn::head_detach(a);
-        return fail(BN_ERR_BACKEND, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
-    }
-    bn::head_detach(c->head);
-    c->head = a;
-    return BN_OK;
+    return install_attachment(c->stream, c->head, a, bn::head_detach);
 }
 
 bn_status bn_step_head_results(const bn_ctx *c, const float **logits, const uint32_t **idx, const float **conf, const uint32_t **count, size_t *k_stride,
@@ -1354,22 +1287,14 @@ bn_status bn_step_head_results(const bn_ctx *c, const float **logits, const uint
 
 bn_status bn_ctx_attach_prior(bn_ctx *c, bn_prior *p, const int32_t *source_sites, size_t n_source_sites, size_t top_k, int32_t has_min, float min_conf) {
     if (!c) return fail(BN_ERR_INVALID_ARG, "null context");
-    HIP_TRY(bn::use_device(c->model->device));
+    BN_HIP_TRY(bn::use_device(c->model->device));
     bn::PriorAttach *a = nullptr;
     if (p) {
         const size_t n = (size_t)c->pd->plan->outputs[c->model->cfg.logits_output].row_elems;
         bn_status st = bn::prior_attach(p, c->model->device, n, c->max_batch, source_sites, n_source_sites, top_k, has_min, min_conf, &a);
         if (st != BN_OK) return st;
     }
-    // the previous attachment's buffers may still be read by a step in flight
-    hipError_t e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) {
-        bn::prior_detach(a);
-        return fail(BN_ERR_BACKEND, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
-    }
-    bn::prior_detach(c->prior);
-    c->prior = a;
-    return BN_OK;
+    return install_attachment(c->stream, c->prior, a, bn::prior_detach);
 }
 
 bn_status bn_ctx_prior_site(bn_ctx *c, int32_t site) {
@@ -1385,19 +1310,16 @@ bn_status bn_step_prior_results(const bn_ctx *c, const uint32_t **idx, const flo
 }
 
 bn_status bn_step_results(const bn_ctx *c, const float **logits, const uint32_t **idx, const float **conf, const uint32_t **count, size_t *k_stride) {
-    if (!c || !c->h_tk_idx) return fail(BN_ERR_INVALID_ARG, "no step has run on this context");
-    if (logits) *logits = c->h_out;
-    if (idx) *idx = c->h_tk_idx;
-    if (conf) *conf = c->h_tk_conf;
-    if (count) *count = c->h_tk_cnt;
-    if (k_stride) *k_stride = c->step_k;
-    return BN_OK;
+    if (!c) return fail(BN_ERR_INVALID_ARG, "no step has run on this context");
+    bn_status st = c->step.results("no step has run on this context", idx, conf, count, k_stride);
+    if (st == BN_OK && logits) *logits = c->h_out;
+    return st;
 }
 
 bn_status bn_ctx_step_device_rows(const bn_ctx *c, const uint32_t **d_rows) {
     if (!c || !d_rows) return fail(BN_ERR_INVALID_ARG, "null argument");
-    if (!c->d_step) return fail(BN_ERR_INVALID_ARG, "no step has run on this context");
-    *d_rows = c->d_step;
+    if (!c->step.d) return fail(BN_ERR_INVALID_ARG, "no step has run on this context");
+    *d_rows = c->step.d;
     return BN_OK;
 }
 
@@ -1413,14 +1335,14 @@ bn_status bn_topk_device(int32_t device, const float *d_logits, size_t rows, siz
     if (!d_logits || !idx_out || !conf_out) return fail(BN_ERR_INVALID_ARG, "null argument");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(BN_ERR_NO_DEVICE, "no HIP device is visible; this path has no CPU fallback");
-    HIP_TRY(bn::use_device(device));
+    BN_HIP_TRY(bn::use_device(device));
     if (!prepare_device(device)) return fail(BN_ERR_BACKEND, "device refused the kernels' dynamic-LDS opt-in");
     uint32_t *d_idx = nullptr, *d_cnt = nullptr, *d_flags = nullptr;
     float *d_conf = nullptr;
-    HIP_TRY(gated::Malloc(&d_idx, rows * k * sizeof(uint32_t)));
-    HIP_TRY(gated::Malloc(&d_conf, rows * k * sizeof(float)));
-    HIP_TRY(gated::Malloc(&d_cnt, rows * sizeof(uint32_t)));
-    HIP_TRY(gated::Malloc(&d_flags, rows * sizeof(uint32_t)));
+    BN_HIP_TRY(gated::Malloc(&d_idx, rows * k * sizeof(uint32_t)));
+    BN_HIP_TRY(gated::Malloc(&d_conf, rows * k * sizeof(float)));
+    BN_HIP_TRY(gated::Malloc(&d_cnt, rows * sizeof(uint32_t)));
+    BN_HIP_TRY(gated::Malloc(&d_flags, rows * sizeof(uint32_t)));
     bn_status st = topk_run(device, nullptr, d_logits, rows, n, top_k, has_min, min_conf, k_stride, d_idx, d_conf, d_cnt, d_flags, idx_out, conf_out,
                             count_out);
     (void)gated::Free(d_idx);
@@ -1441,9 +1363,9 @@ bn_status bn_topk_host(int32_t device, const float *logits, size_t rows, size_t 
     if (!logits) return fail(BN_ERR_INVALID_ARG, "null argument");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(BN_ERR_NO_DEVICE, "no HIP device is visible; this path has no CPU fallback");
-    HIP_TRY(bn::use_device(device));
+    BN_HIP_TRY(bn::use_device(device));
     float *d = nullptr;
-    HIP_TRY(gated::Malloc(&d, rows * n * sizeof(float)));
+    BN_HIP_TRY(gated::Malloc(&d, rows * n * sizeof(float)));
     hipError_t e = gated::Memcpy(d, logits, rows * n * sizeof(float), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         (void)gated::Free(d);
@@ -1490,14 +1412,14 @@ bn_status bn_recording_create(int32_t device, const void *pcm, size_t n_samples,
     *out = nullptr;
     if (format != BN_PCM_I16 && format != BN_PCM_F32) return fail(BN_ERR_INVALID_ARG, "unknown PCM format");
     if (n_samples && !pcm) return fail(BN_ERR_INVALID_ARG, "null PCM buffer");
-    if (bn_device_count() <= 0) return fail(BN_ERR_NO_DEVICE, "no gfx950 device visible");
-    HIP_TRY(bn::use_device(device));
+    if (bn_status dst = require_any_device(); dst != BN_OK) return dst;
+    BN_HIP_TRY(bn::use_device(device));
     auto r = std::make_unique<bn_recording>();
     r->device = device;
     r->format = format;
     r->n_samples = n_samples;
     const size_t bytes = n_samples * (format == BN_PCM_I16 ? sizeof(int16_t) : sizeof(float));
-    HIP_TRY(gated::Malloc(&r->d_pcm, std::max<size_t>(bytes, 16)));
+    BN_HIP_TRY(gated::Malloc(&r->d_pcm, std::max<size_t>(bytes, 16)));
     if (bytes) {
         hipError_t e = gated::Memcpy(r->d_pcm, pcm, bytes, hipMemcpyHostToDevice);
         if (e != hipSuccess) {
@@ -1514,8 +1436,8 @@ bn_status bn_recording_create_async(int32_t device, const void *pcm, size_t n_sa
     *out = nullptr;
     if (format != BN_PCM_I16 && format != BN_PCM_F32) return fail(BN_ERR_INVALID_ARG, "unknown PCM format");
     if (n_samples && !pcm) return fail(BN_ERR_INVALID_ARG, "null PCM buffer");
-    if (bn_device_count() <= 0) return fail(BN_ERR_NO_DEVICE, "no gfx950 device visible");
-    HIP_TRY(bn::use_device(device));
+    if (bn_status dst = require_any_device(); dst != BN_OK) return dst;
+    BN_HIP_TRY(bn::use_device(device));
     const size_t esz = format == BN_PCM_I16 ? sizeof(int16_t) : sizeof(float);
     // the uploader holds the capture gate (shared) for one chunk's synchronous copy and a context's first-time graph capture takes it
     // exclusively: 4 MiB keeps a capture's wait behind a chunk well under a millisecond (32 MiB chunks stalled exactly the first
@@ -1525,7 +1447,7 @@ bn_status bn_recording_create_async(int32_t device, const void *pcm, size_t n_sa
     r->device = device;
     r->format = format;
     r->n_samples = n_samples;
-    HIP_TRY(gated::Malloc(&r->d_pcm, std::max<size_t>(n_samples * esz, 16)));
+    BN_HIP_TRY(gated::Malloc(&r->d_pcm, std::max<size_t>(n_samples * esz, 16)));
     r->chunk_samples = std::max<size_t>(1, (chunk_mb << 20) / esz);
     r->n_chunks = (n_samples + r->chunk_samples - 1) / r->chunk_samples;
     bn_recording *raw = r.get();
@@ -1673,8 +1595,8 @@ bn_status bn_recording_read_f32(const bn_recording *r, size_t first, size_t coun
     if (first > r->n_samples || count > r->n_samples - first) return fail(BN_ERR_INVALID_ARG, "sample range exceeds the recording");
     if (count == 0) return BN_OK;
     if (!recording_wait_samples(r, first + count - 1)) return fail(BN_ERR_BACKEND, "recording upload failed");
-    HIP_TRY(bn::use_device(r->device));
-    HIP_TRY(gated::Memcpy(host_out, static_cast<const float *>(r->d_pcm) + first, count * sizeof(float), hipMemcpyDeviceToHost));
+    BN_HIP_TRY(bn::use_device(r->device));
+    BN_HIP_TRY(gated::Memcpy(host_out, static_cast<const float *>(r->d_pcm) + first, count * sizeof(float), hipMemcpyDeviceToHost));
     return BN_OK;
 }
 
@@ -1710,9 +1632,9 @@ bn_status bn_recording_windows(const bn_recording *r, size_t segment_samples, si
     if (st != BN_OK) return st;
     if (count == 0) return BN_OK;
     if (!host_out) return fail(BN_ERR_INVALID_ARG, "null host buffer");
-    HIP_TRY(bn::use_device(r->device));
+    BN_HIP_TRY(bn::use_device(r->device));
     float *d = nullptr;
-    HIP_TRY(gated::Malloc(reinterpret_cast<void **>(&d), count * segment_samples * sizeof(float)));
+    BN_HIP_TRY(gated::Malloc(reinterpret_cast<void **>(&d), count * segment_samples * sizeof(float)));
     (void)hipGetLastError();
     launch_windows(nullptr, d, r->d_pcm, r->format == BN_PCM_I16, r->n_samples, (uint64_t)first_window * step_samples, step_samples, (uint32_t)segment_samples,
                    (uint32_t)count);
@@ -1733,7 +1655,7 @@ bn_status bn_infer_windows(bn_ctx *c, const bn_recording *r, size_t step_samples
     if (!logits_out) return fail(BN_ERR_INVALID_ARG, "null argument");
     if (count > c->max_batch) return fail(BN_ERR_INVALID_ARG, "batch size " + std::to_string(count) + " exceeds context max " + std::to_string(c->max_batch));
     if (r->device != c->model->device) return fail(BN_ERR_INVALID_ARG, "recording and context live on different devices");
-    HIP_TRY(bn::use_device(c->model->device));
+    BN_HIP_TRY(bn::use_device(c->model->device));
     st = drain_if_needed(c);
     if (st != BN_OK) return st;
     if (cancel && *cancel) return fail(BN_ERR_CANCELLED, "inference was cancelled");
@@ -1759,7 +1681,7 @@ bn_status bn_step_windows(bn_ctx *c, const bn_recording *r, size_t step_samples,
     if (count == 0) return BN_OK;
     if (count > c->max_batch) return fail(BN_ERR_INVALID_ARG, "batch size " + std::to_string(count) + " exceeds context max " + std::to_string(c->max_batch));
     if (r->device != c->model->device) return fail(BN_ERR_INVALID_ARG, "recording and context live on different devices");
-    HIP_TRY(bn::use_device(c->model->device));
+    BN_HIP_TRY(bn::use_device(c->model->device));
     (void)hipGetLastError();
     // stream order keeps this behind whatever the context still has in flight
     launch_windows(c->stream, c->d_input, r->d_pcm, r->format == BN_PCM_I16, r->n_samples, (uint64_t)first_window * step_samples, step_samples, (uint32_t)S,
@@ -1970,8 +1892,9 @@ bn_status bn::ctx_step_input(const bn_ctx *c, size_t top_k, CtxStepInput *out) {
     if (!c || !out) return fail(BN_ERR_INVALID_ARG, "null argument");
     const Plan &p = *c->pd->plan;
     const size_t n = (size_t)p.outputs[c->model->cfg.logits_output].row_elems;
-    const size_t k = std::min(top_k, n);
-    if (k == 0 || topk_lds_bytes((int64_t)n, (int64_t)k) == 0) return fail(BN_ERR_INVALID_ARG, "top_k must be in 1..9000");
+    size_t k = 0;
+    bn_status st = check_top_k(n, top_k, &k);
+    if (st != BN_OK) return st;
     out->device = c->model->device;
     out->stream = c->stream;
     out->d_input = c->d_input;

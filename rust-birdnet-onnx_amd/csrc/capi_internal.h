@@ -1,5 +1,6 @@
-// What other translation units of the C ABI need of capi.cpp's private state (index.hip: bn_index_*; head.hip: bn_head_*) and
-// of each other (prior.hip: bn_prior_*).
+// What the translation units of the C ABI share: the plumbing every entry point repeats (the error macro, launch and device checks,
+// the packed top-K block TopkRows, results_to_host, scoped scratch: step_common.cpp) and what they need of capi.cpp's private state
+// (index.hip: bn_index_*; head.hip: bn_head_*) and of each other (prior.hip: bn_prior_*).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -7,10 +8,99 @@
 #include <vector>
 
 #include "../../include/birdnet_hip.h"
+#include "hip_gate.h"
+
+// a failed runtime call ends the enclosing function with BN_ERR_BACKEND and the call's text in the message
+#define BN_HIP_TRY(expr)                                                                                                   \
+    do {                                                                                                                   \
+        hipError_t e_ = (expr);                                                                                            \
+        if (e_ != hipSuccess) return bn::set_last_error(BN_ERR_BACKEND, std::string(#expr) + " failed: " + hipGetErrorString(e_)); \
+    } while (0)
 
 namespace bn {
 // sets the message bn_last_error() returns on this thread; returns st
 bn_status set_last_error(bn_status st, const std::string &msg);
+
+// ---- step_common.cpp ----
+// before a launch: drops the thread's pending launcher refusal and the runtime's sticky error, both of unrelated earlier calls
+void clear_launch_state();
+// after a launch: a launcher's refusal (kernels.h launch_error) is BN_ERR_INVALID_ARG "`what` refused: why", a runtime error
+// BN_ERR_BACKEND "`what` launch failed: ..."
+bn_status check_launch(const char *what);
+// BN_ERR_NO_DEVICE (message set) without a gfx950 device / for an ordinal the runtime does not list
+bn_status require_any_device();
+bn_status require_device(int32_t device);
+// *k = min(top_k, n); refuses k == 0 and a k beyond the top-K heap's LDS
+bn_status check_top_k(size_t n, size_t top_k, size_t *k);
+
+// The top-K rows of `batch` rows packed [idx: batch*k][conf: batch*k][count: batch] in one block of 32-bit words, so that they cross
+// the bus as ONE region; a device block, a pinned mirror, or both.  The offsets are known here and nowhere else.
+struct TopkRows {
+    struct View {
+        uint32_t *idx;
+        float *conf;
+        uint32_t *count;
+        size_t k;
+    };
+    struct ConstView {
+        const uint32_t *idx;
+        const float *conf;
+        const uint32_t *count;
+        size_t k;
+    };
+    uint32_t *d = nullptr, *h = nullptr;
+    size_t cap = 0;                     // words
+    size_t last_batch = 0, last_k = 0;  // the rows last enqueued into the block (mark); last_k == 0: none since it was (re)allocated
+
+    static size_t words(size_t batch, size_t k) { return batch * (2 * k + 1); }
+    static size_t bytes(size_t batch, size_t k) { return words(batch, k) * sizeof(uint32_t); }
+    static View view(uint32_t *base, size_t batch, size_t k) { return {base, reinterpret_cast<float *>(base + batch * k), base + 2 * batch * k, k}; }
+    static ConstView view(const uint32_t *base, size_t batch, size_t k) {
+        return {base, reinterpret_cast<const float *>(base + batch * k), base + 2 * batch * k, k};
+    }
+    // room for max_batch rows of k; grows by free + allocate after waiting for `drain` (may be NULL: nothing can be using the block),
+    // which forgets the marked rows; empty on failure
+    bn_status reserve(size_t max_batch, size_t k, hipStream_t drain, bool device, bool pinned);
+    void release();
+    void mark(size_t batch, size_t k) { last_batch = batch, last_k = k; }
+    // the pinned mirror's marked rows for a *_step_results accessor (any output may be NULL); BN_ERR_INVALID_ARG `none_msg` if none
+    bn_status results(const char *none_msg, const uint32_t **idx, const float **conf, const uint32_t **count, size_t *k_stride) const;
+};
+
+// Device results -> pinned host buffers on `stream`, by ONE kernel launch storing straight into the (device-mapped) pinned memory
+// (topk.hip, copy_out_kernel) instead of one copy-engine transfer per region; hipMemcpyAsync transfers where a switch asks for them
+// or the kernel cannot take a region (step_common.cpp).
+struct OutRegion {
+    void *host;
+    const void *dev;
+    size_t bytes;
+};
+bn_status results_to_host(hipStream_t stream, const OutRegion *regs, int n);
+// top-K of `rows` device rows of n logits into a packed block, on `stream`; a launch the heap's LDS refuses is an error
+bn_status enqueue_topk_rows(hipStream_t stream, const float *d_logits, size_t rows, size_t n, size_t k, int32_t has_min, float min_conf,
+                            const TopkRows::View &out, uint32_t *d_flags);
+
+// device buffers, one pinned buffer and a stream of one call: on every way out the stream is waited for, the buffers freed and the
+// stream, if owned, destroyed
+struct Scratch {
+    std::vector<void *> ptrs;
+    void *pinned = nullptr;
+    hipStream_t stream = nullptr;
+    bool owns_stream = false;
+    Scratch() = default;
+    Scratch(const Scratch &) = delete;
+    Scratch &operator=(const Scratch &) = delete;
+    ~Scratch();
+    template <class T>
+    hipError_t alloc(T **p, size_t bytes, bool zero = false) {
+        hipError_t e = gated::Malloc(p, bytes);
+        if (e != hipSuccess) return e;
+        ptrs.push_back(*p);
+        return zero ? hipMemsetAsync(*p, 0, bytes, stream) : hipSuccess;  // on the stream that uses the buffer: ordered before every kernel
+    }
+};
+
+// ---- capi.cpp ----
 // the embedding output of a context's last run: device, stream, rows [last_batch, row_elems]; BN_ERR_INVALID_ARG (message set)
 // for a model without embeddings
 struct CtxEmbedding {
@@ -68,8 +158,8 @@ bn_status prior_live_check(const PriorAttach *a, size_t n_sources);
 bn_status prior_stage_rows(PriorAttach *a, const int32_t *sources, size_t rows);
 void prior_clear_rows(PriorAttach *a);
 // the prior kernel + results to pinned memory, enqueued on the context's stream behind the step's own top-K;
-// d_step_rows / step_k: the step's packed [idx][conf][count] block on the device
-bn_status prior_step(PriorAttach *a, hipStream_t stream, const float *d_logits, size_t batch, const uint32_t *d_step_rows, size_t step_k);
+// step_rows: the step's own rows on the device (AFTER_TOPK filters them)
+bn_status prior_step(PriorAttach *a, hipStream_t stream, const float *d_logits, size_t batch, const TopkRows::ConstView &step_rows);
 bn_status prior_step_results(const PriorAttach *a, const uint32_t **idx, const float **conf, const uint32_t **count, size_t *k_stride);
 // capi.cpp -> live.cpp: the context's attached prior, NULL if none
 PriorAttach *ctx_prior(bn_ctx *c);

@@ -14,6 +14,7 @@
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 
+#include "capi_internal.h"
 #include "hip_gate.h"
 #include "switches.h"
 
@@ -250,7 +251,7 @@ bn_status bn_group_analyze_recording(bn_group *g, const void *pcm, size_t n_samp
     if (count_out && k && (!idx_out || !conf_out || k_stride < k)) return gfail(BN_ERR_INVALID_ARG, "top-K outputs need idx / conf buffers with k_stride >= min(top_k, num_species)");
     const size_t R = g->ranks.size();
     const size_t per = (G + R - 1) / R;  // rows per rank in the gathered buffers (the last ranks' tails are padding)
-    const size_t tkw = 2 * k + 1;        // words of one packed top-K row
+    const size_t tkw = bn::TopkRows::words(1, k);       // words of one packed top-K row
     const size_t esz = format == BN_PCM_I16 ? sizeof(int16_t) : sizeof(float);
 
     // ---- per-rank work: upload the slice, step the windows, collect rows device-to-device into the rank's slab
@@ -313,11 +314,12 @@ bn_status bn_group_analyze_recording(bn_group *g, const void *pcm, size_t n_samp
             if (k) {
                 const uint32_t *d_step = nullptr;
                 if (bn_ctx_step_device_rows(c, &d_step) != BN_OK) return false;
-                // the step block is [idx: m*k][conf: m*k][count: m] for the m rows of the step: re-pack row by row on the way
+                // the step block holds the m rows of the step region by region: re-pack row by row on the way
+                const bn::TopkRows::ConstView v = bn::TopkRows::view(d_step, jb.count, k);
                 uint32_t *dst = rk.d_topk + (r * per + jb.first) * tkw;
-                if (hipMemcpy2DAsync(dst, tkw * 4, d_step, k * 4, k * 4, jb.count, hipMemcpyDeviceToDevice, cs) != hipSuccess) return false;
-                if (hipMemcpy2DAsync(dst + k, tkw * 4, d_step + jb.count * k, k * 4, k * 4, jb.count, hipMemcpyDeviceToDevice, cs) != hipSuccess) return false;
-                if (hipMemcpy2DAsync(dst + 2 * k, tkw * 4, d_step + 2 * jb.count * k, 4, 4, jb.count, hipMemcpyDeviceToDevice, cs) != hipSuccess) return false;
+                if (hipMemcpy2DAsync(dst, tkw * 4, v.idx, k * 4, k * 4, jb.count, hipMemcpyDeviceToDevice, cs) != hipSuccess) return false;
+                if (hipMemcpy2DAsync(dst + k, tkw * 4, v.conf, k * 4, k * 4, jb.count, hipMemcpyDeviceToDevice, cs) != hipSuccess) return false;
+                if (hipMemcpy2DAsync(dst + 2 * k, tkw * 4, v.count, 4, 4, jb.count, hipMemcpyDeviceToDevice, cs) != hipSuccess) return false;
             }
             return true;
         };

@@ -342,29 +342,16 @@ struct bn::HeadAttach {
     float min_conf = 0.f;
     float *d_x = nullptr;       // [max_batch padded to 16, dpad]
     float *d_z = nullptr;       // [max_batch, classes]
-    uint32_t *d_rows = nullptr;  // packed [idx: b*k][conf: b*k][count: b] of the last step
+    bn::TopkRows rows;          // the last step's top-K rows: device block and pinned mirror
     uint32_t *d_flags = nullptr;
-    float *h_z = nullptr;  // pinned mirrors
-    uint32_t *h_rows = nullptr;
-    size_t last_batch = 0;
-    bool stepped = false;
+    float *h_z = nullptr;  // pinned mirror of d_z
 };
 
 namespace {
 
 using bn::set_last_error;
 
-#define HEAD_TRY(expr)                                                                                             \
-    do {                                                                                                           \
-        hipError_t e_ = (expr);                                                                                    \
-        if (e_ != hipSuccess) return set_last_error(BN_ERR_BACKEND, std::string(#expr) + " failed: " + hipGetErrorString(e_)); \
-    } while (0)
-
-bn_status check_launch(const char *what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_last_error(BN_ERR_BACKEND, std::string(what) + " launch failed: " + hipGetErrorString(e));
-    return BN_OK;
-}
+using bn::check_launch;
 
 size_t round_up(size_t v, size_t m) { return (v + m - 1) / m * m; }
 
@@ -378,43 +365,16 @@ void head_unref(bn_head *h) {
     delete h;
 }
 
-// frees device allocations on every way out of a fit
-struct DevBufs {
-    std::vector<void *> ptrs;
-    hipStream_t stream = nullptr;
-    void *pinned = nullptr;
-    ~DevBufs() {
-        if (stream) (void)hipStreamSynchronize(stream);
-        for (void *p : ptrs) (void)bn::gated::Free(p);
-        if (pinned) (void)bn::gated::HostFree(pinned);
-        if (stream) (void)bn::gated::StreamDestroy(stream);
-    }
-    template <class T>
-    hipError_t alloc(T **p, size_t bytes, bool zero) {
-        hipError_t e = bn::gated::Malloc(p, bytes);
-        if (e != hipSuccess) return e;
-        ptrs.push_back(*p);
-        return zero ? hipMemsetAsync(*p, 0, bytes, stream) : hipSuccess;  // on the stream that uses the buffer: ordered before every kernel
-    }
-};
-
 bn_status check_shape(size_t dim, size_t n_classes) {
     if (dim < 1 || dim > DIM_MAX) return set_last_error(BN_ERR_INVALID_ARG, "dim must be in 1..8192, got " + std::to_string(dim));
     if (n_classes < 1 || n_classes > CLS_MAX) return set_last_error(BN_ERR_INVALID_ARG, "n_classes must be in 1..4096, got " + std::to_string(n_classes));
     return BN_OK;
 }
 
-bn_status check_device(int32_t device) {
-    if (bn_device_count() <= 0) return set_last_error(BN_ERR_NO_DEVICE, "no gfx950 device visible");
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) return set_last_error(BN_ERR_NO_DEVICE, "no such device");
-    return BN_OK;
-}
-
 // a head on `device` whose weights and bias the caller fills WHOLE, padding included (bn_head_create from the host, a fit from
 // its solution)
 bn_status new_head(int32_t device, size_t dim, size_t n_classes, uint32_t flags, std::unique_ptr<bn_head, void (*)(bn_head *)> &h) {
-    HEAD_TRY(bn::use_device(device));
+    BN_HIP_TRY(bn::use_device(device));
     if (!bn::prepare_device(device)) return set_last_error(BN_ERR_BACKEND, "device refused the kernels' dynamic-LDS opt-in");
     h.reset(new bn_head);
     h->device = device;
@@ -423,8 +383,8 @@ bn_status new_head(int32_t device, size_t dim, size_t n_classes, uint32_t flags,
     h->classes = n_classes;
     h->cpad = round_up(n_classes, 16);
     h->flags = flags;
-    HEAD_TRY(bn::gated::Malloc(&h->d_W, h->cpad * h->dpad * sizeof(float)));
-    HEAD_TRY(bn::gated::Malloc(&h->d_b, h->cpad * sizeof(float)));
+    BN_HIP_TRY(bn::gated::Malloc(&h->d_W, h->cpad * h->dpad * sizeof(float)));
+    BN_HIP_TRY(bn::gated::Malloc(&h->d_b, h->cpad * sizeof(float)));
     return BN_OK;
 }
 
@@ -480,7 +440,7 @@ bn_status check_labels(const uint8_t *labels, size_t count) {
 // The solver.  d_X: the training slab [npad (multiple of RB), dpad], padding zero.  L-BFGS over all classes at once with Armijo
 // backtracking (the objective is strongly convex: every accepted pair has s.y > 0, no curvature condition is needed).  One
 // "iteration" is one evaluation of (L, grad L) at a trial point; the scalars of an evaluation cross the bus once.
-bn_status solve(DevBufs &bufs, bn_head *h, const float *d_X, size_t n, size_t npad, const uint8_t *labels, const std::vector<float> &pw, const FitOpts &o,
+bn_status solve(bn::Scratch &bufs, bn_head *h, const float *d_X, size_t n, size_t npad, const uint8_t *labels, const std::vector<float> &pw, const FitOpts &o,
                 bn_head_fit_report *rep) {
     const size_t C = h->classes, cpad = h->cpad, dpad = h->dpad;
     const size_t wv = cpad * dpad, pv = wv + cpad;
@@ -495,24 +455,24 @@ bn_status solve(DevBufs &bufs, bn_head *h, const float *d_X, size_t n, size_t np
     float *d_pw = nullptr, *d_Z = nullptr, *d_R = nullptr, *d_Rb = nullptr, *d_Gp = nullptr, *d_hist = nullptr, *d_x[2] = {nullptr, nullptr},
           *d_g[2] = {nullptr, nullptr};
     double *d_lossp = nullptr, *d_part = nullptr, *d_out = nullptr;
-    HEAD_TRY(bufs.alloc(&d_Y, n * C, false));
-    HEAD_TRY(bn::gated::Memcpy(d_Y, labels, n * C, hipMemcpyHostToDevice));
-    HEAD_TRY(bufs.alloc(&d_pw, C * sizeof(float), false));
-    HEAD_TRY(bn::gated::Memcpy(d_pw, pw.data(), C * sizeof(float), hipMemcpyHostToDevice));
-    HEAD_TRY(bufs.alloc(&d_Z, n * C * sizeof(float), false));
-    HEAD_TRY(bufs.alloc(&d_R, npad * cpad * sizeof(float), false));
-    HEAD_TRY(bufs.alloc(&d_Rb, (size_t)n_rblocks * cpad * sizeof(float), false));
-    HEAD_TRY(bufs.alloc(&d_Gp, (size_t)n_slices * wv * sizeof(float), false));
-    HEAD_TRY(bufs.alloc(&d_hist, (size_t)2 * HM * pv * sizeof(float), true));
+    BN_HIP_TRY(bufs.alloc(&d_Y, n * C, false));
+    BN_HIP_TRY(bn::gated::Memcpy(d_Y, labels, n * C, hipMemcpyHostToDevice));
+    BN_HIP_TRY(bufs.alloc(&d_pw, C * sizeof(float), false));
+    BN_HIP_TRY(bn::gated::Memcpy(d_pw, pw.data(), C * sizeof(float), hipMemcpyHostToDevice));
+    BN_HIP_TRY(bufs.alloc(&d_Z, n * C * sizeof(float), false));
+    BN_HIP_TRY(bufs.alloc(&d_R, npad * cpad * sizeof(float), false));
+    BN_HIP_TRY(bufs.alloc(&d_Rb, (size_t)n_rblocks * cpad * sizeof(float), false));
+    BN_HIP_TRY(bufs.alloc(&d_Gp, (size_t)n_slices * wv * sizeof(float), false));
+    BN_HIP_TRY(bufs.alloc(&d_hist, (size_t)2 * HM * pv * sizeof(float), true));
     for (int i = 0; i < 2; i++) {
-        HEAD_TRY(bufs.alloc(&d_x[i], pv * sizeof(float), true));
-        HEAD_TRY(bufs.alloc(&d_g[i], pv * sizeof(float), true));
+        BN_HIP_TRY(bufs.alloc(&d_x[i], pv * sizeof(float), true));
+        BN_HIP_TRY(bufs.alloc(&d_g[i], pv * sizeof(float), true));
     }
-    HEAD_TRY(bufs.alloc(&d_lossp, n_rblocks * sizeof(double), false));
-    HEAD_TRY(bufs.alloc(&d_part, (size_t)RED_BLOCKS * NQ * sizeof(double), true));
-    HEAD_TRY(bufs.alloc(&d_out, NQ * sizeof(double), false));
+    BN_HIP_TRY(bufs.alloc(&d_lossp, n_rblocks * sizeof(double), false));
+    BN_HIP_TRY(bufs.alloc(&d_part, (size_t)RED_BLOCKS * NQ * sizeof(double), true));
+    BN_HIP_TRY(bufs.alloc(&d_out, NQ * sizeof(double), false));
     double *h_out = nullptr;
-    HEAD_TRY(bn::gated::HostMalloc(&h_out, NQ * sizeof(double), 0));
+    BN_HIP_TRY(bn::gated::HostMalloc(&h_out, NQ * sizeof(double), 0));
     bufs.pinned = h_out;
 
     int cur = 0;  // d_x[cur], d_g[cur]: the current point and its gradient; [1 - cur]: the trial
@@ -530,8 +490,8 @@ bn_status solve(DevBufs &bufs, bn_head *h, const float *d_X, size_t n, size_t np
         hipLaunchKernelGGL(head_scalars_kernel, dim3(1), dim3(64), 0, s, d_part, d_lossp, n_rblocks, d_out);
         bn_status st = check_launch("head fit");
         if (st != BN_OK) return st;
-        HEAD_TRY(hipMemcpyAsync(h_out, d_out, NQ * sizeof(double), hipMemcpyDeviceToHost, s));
-        HEAD_TRY(hipStreamSynchronize(s));
+        BN_HIP_TRY(hipMemcpyAsync(h_out, d_out, NQ * sizeof(double), hipMemcpyDeviceToHost, s));
+        BN_HIP_TRY(hipStreamSynchronize(s));
         return BN_OK;
     };
     auto dot = [&](int a, int col) { return h_out[a * NCOL + col]; };  // a: 0 s_cand, 1 y_cand, 2 g_trial
@@ -652,9 +612,9 @@ bn_status solve(DevBufs &bufs, bn_head *h, const float *d_X, size_t n, size_t np
         }
     }
     // the current point becomes the head (the same padded layout)
-    HEAD_TRY(hipMemcpyAsync(h->d_W, d_x[cur], wv * sizeof(float), hipMemcpyDeviceToDevice, s));
-    HEAD_TRY(hipMemcpyAsync(h->d_b, d_x[cur] + wv, cpad * sizeof(float), hipMemcpyDeviceToDevice, s));
-    HEAD_TRY(hipStreamSynchronize(s));
+    BN_HIP_TRY(hipMemcpyAsync(h->d_W, d_x[cur], wv * sizeof(float), hipMemcpyDeviceToDevice, s));
+    BN_HIP_TRY(hipMemcpyAsync(h->d_b, d_x[cur] + wv, cpad * sizeof(float), hipMemcpyDeviceToDevice, s));
+    BN_HIP_TRY(hipStreamSynchronize(s));
     rep->iters = iters;
     rep->converged = converged ? 1 : 0;
     rep->loss = f;
@@ -675,22 +635,20 @@ bn_status bn::head_attach(bn_head *h, int device, bool has_embedding, size_t emb
     if (embedding_dim != h->dim)
         return set_last_error(BN_ERR_INVALID_ARG, "the head's dim " + std::to_string(h->dim) + " differs from the model's embedding_dim " + std::to_string(embedding_dim));
     if (device != h->device) return set_last_error(BN_ERR_INVALID_ARG, "the context lives on device " + std::to_string(device) + ", the head on " + std::to_string(h->device));
-    const size_t k = std::min(top_k, h->classes);
-    if (k == 0 || bn::topk_lds_bytes((int64_t)h->classes, (int64_t)k) == 0)
-        return set_last_error(BN_ERR_INVALID_ARG, "top_k must be in 1..9000, got " + std::to_string(top_k));
-    HEAD_TRY(bn::use_device(device));
+    size_t k = 0;
+    bn_status st = bn::check_top_k(h->classes, top_k, &k);
+    if (st != BN_OK) return st;
+    BN_HIP_TRY(bn::use_device(device));
     std::unique_ptr<HeadAttach, void (*)(HeadAttach *)> a(new HeadAttach, head_detach);
     a->max_batch = max_batch;
     a->k = k;
     a->has_min = has_min;
     a->min_conf = min_conf;
-    const size_t rows_words = max_batch * (2 * k + 1);
-    HEAD_TRY(bn::gated::Malloc(&a->d_x, round_up(max_batch, 16) * h->dpad * sizeof(float)));
-    HEAD_TRY(bn::gated::Malloc(&a->d_z, max_batch * h->classes * sizeof(float)));
-    HEAD_TRY(bn::gated::Malloc(&a->d_rows, rows_words * sizeof(uint32_t)));
-    HEAD_TRY(bn::gated::Malloc(&a->d_flags, max_batch * sizeof(uint32_t)));
-    HEAD_TRY(bn::gated::HostMalloc(&a->h_z, max_batch * h->classes * sizeof(float), hipHostMallocDefault));
-    HEAD_TRY(bn::gated::HostMalloc(&a->h_rows, rows_words * sizeof(uint32_t), hipHostMallocDefault));
+    BN_HIP_TRY(bn::gated::Malloc(&a->d_x, round_up(max_batch, 16) * h->dpad * sizeof(float)));
+    BN_HIP_TRY(bn::gated::Malloc(&a->d_z, max_batch * h->classes * sizeof(float)));
+    if ((st = a->rows.reserve(max_batch, k, nullptr, true, true)) != BN_OK) return st;
+    BN_HIP_TRY(bn::gated::Malloc(&a->d_flags, max_batch * sizeof(uint32_t)));
+    BN_HIP_TRY(bn::gated::HostMalloc(&a->h_z, max_batch * h->classes * sizeof(float), hipHostMallocDefault));
     h->refs.fetch_add(1, std::memory_order_relaxed);
     a->head = h;
     *out = a.release();
@@ -699,10 +657,10 @@ bn_status bn::head_attach(bn_head *h, int device, bool has_embedding, size_t emb
 
 void bn::head_detach(HeadAttach *a) {
     if (!a) return;
-    for (void *p : {(void *)a->d_x, (void *)a->d_z, (void *)a->d_rows, (void *)a->d_flags})
+    for (void *p : {(void *)a->d_x, (void *)a->d_z, (void *)a->d_flags})
         if (p) (void)bn::gated::Free(p);
     if (a->h_z) (void)bn::gated::HostFree(a->h_z);
-    if (a->h_rows) (void)bn::gated::HostFree(a->h_rows);
+    a->rows.release();
     head_unref(a->head);
     delete a;
 }
@@ -713,44 +671,21 @@ bn_status bn::head_step(HeadAttach *a, hipStream_t stream, const float *d_emb, s
     bn_status st = enqueue_apply(h, stream, d_emb, batch, a->d_x, a->d_z);
     if (st != BN_OK) return st;
     const size_t k = a->k, C = h->classes;
-    uint32_t *d_idx = a->d_rows, *d_cnt = a->d_rows + 2 * batch * k;
-    float *d_conf = reinterpret_cast<float *>(a->d_rows + batch * k);
-    bn::launch_topk(stream, a->d_z, (int64_t)batch, (int64_t)C, (int64_t)k, a->has_min, a->min_conf, (int64_t)k, d_idx, d_conf, d_cnt, a->d_flags);
-    if ((st = check_launch("head top-K")) != BN_OK) return st;
-    // results into the pinned mirrors by one store kernel, as the step's own (capi.cpp, results_to_host); copies otherwise
-    const size_t z_bytes = batch * C * sizeof(float), r_bytes = batch * (2 * k + 1) * sizeof(uint32_t);
-    void *pz = nullptr, *pr = nullptr;
-    static const bool sdma = sw_int(sw::BN_SDMA_COPY) != 0;
-    if (!sdma && hipHostGetDevicePointer(&pz, a->h_z, 0) == hipSuccess && pz && hipHostGetDevicePointer(&pr, a->h_rows, 0) == hipSuccess && pr) {
-        bn::CopyOut co{};
-        co.dst[0] = pz;
-        co.src[0] = a->d_z;
-        co.words[0] = (uint32_t)(z_bytes / 4);
-        co.dst[1] = pr;
-        co.src[1] = a->d_rows;
-        co.words[1] = (uint32_t)(r_bytes / 4);
-        co.n = 2;
-        bn::launch_copy_out(stream, co);
-        if ((st = check_launch("head results")) != BN_OK) return st;
-    } else {
-        (void)hipGetLastError();
-        HEAD_TRY(hipMemcpyAsync(a->h_z, a->d_z, z_bytes, hipMemcpyDeviceToHost, stream));
-        HEAD_TRY(hipMemcpyAsync(a->h_rows, a->d_rows, r_bytes, hipMemcpyDeviceToHost, stream));
-    }
-    a->last_batch = batch;
-    a->stepped = true;
+    st = bn::enqueue_topk_rows(stream, a->d_z, batch, C, k, a->has_min, a->min_conf, bn::TopkRows::view(a->rows.d, batch, k), a->d_flags);
+    if (st != BN_OK) return st;
+    const bn::OutRegion regs[2] = {{a->h_z, a->d_z, batch * C * sizeof(float)}, {a->rows.h, a->rows.d, bn::TopkRows::bytes(batch, k)}};
+    if ((st = bn::results_to_host(stream, regs, 2)) != BN_OK) return st;
+    a->rows.mark(batch, k);
     return BN_OK;
 }
 
 bn_status bn::head_step_results(const HeadAttach *a, const float **logits, const uint32_t **idx, const float **conf, const uint32_t **count, size_t *k_stride,
                                 size_t *n_classes) {
-    if (!a || !a->stepped) return set_last_error(BN_ERR_INVALID_ARG, "no step has run on this context since a head was attached");
-    const size_t b = a->last_batch, k = a->k;
+    static const char *none = "no step has run on this context since a head was attached";
+    if (!a) return set_last_error(BN_ERR_INVALID_ARG, none);
+    bn_status st = a->rows.results(none, idx, conf, count, k_stride);
+    if (st != BN_OK) return st;
     if (logits) *logits = a->h_z;
-    if (idx) *idx = a->h_rows;
-    if (conf) *conf = reinterpret_cast<const float *>(a->h_rows + b * k);
-    if (count) *count = a->h_rows + 2 * b * k;
-    if (k_stride) *k_stride = k;
     if (n_classes) *n_classes = a->head->classes;
     return BN_OK;
 }
@@ -764,15 +699,15 @@ bn_status bn_head_create(int32_t device, size_t dim, size_t n_classes, const flo
     if (st != BN_OK) return st;
     if (!W) return set_last_error(BN_ERR_INVALID_ARG, "null weights");
     if (flags & ~BN_HEAD_L2NORM) return set_last_error(BN_ERR_INVALID_ARG, "unknown flag");
-    if ((st = check_device(device)) != BN_OK) return st;
+    if ((st = bn::require_device(device)) != BN_OK) return st;
     std::unique_ptr<bn_head, void (*)(bn_head *)> h(nullptr, head_unref);
     if ((st = new_head(device, dim, n_classes, flags, h)) != BN_OK) return st;
     std::vector<float> pad(h->cpad * h->dpad, 0.f);
     for (size_t c = 0; c < n_classes; c++) memcpy(pad.data() + c * h->dpad, W + c * dim, dim * sizeof(float));
-    HEAD_TRY(bn::gated::Memcpy(h->d_W, pad.data(), pad.size() * sizeof(float), hipMemcpyHostToDevice));
+    BN_HIP_TRY(bn::gated::Memcpy(h->d_W, pad.data(), pad.size() * sizeof(float), hipMemcpyHostToDevice));
     std::vector<float> bpad(h->cpad, 0.f);
     if (bias) memcpy(bpad.data(), bias, n_classes * sizeof(float));
-    HEAD_TRY(bn::gated::Memcpy(h->d_b, bpad.data(), bpad.size() * sizeof(float), hipMemcpyHostToDevice));
+    BN_HIP_TRY(bn::gated::Memcpy(h->d_b, bpad.data(), bpad.size() * sizeof(float), hipMemcpyHostToDevice));
     *out = h.release();
     return BN_OK;
 }
@@ -785,34 +720,34 @@ uint32_t bn_head_flags(const bn_head *h) { return h ? h->flags : 0; }
 
 bn_status bn_head_read(const bn_head *h, float *W_out, float *bias_out) {
     if (!h) return set_last_error(BN_ERR_INVALID_ARG, "null head");
-    HEAD_TRY(bn::use_device(h->device));
+    BN_HIP_TRY(bn::use_device(h->device));
     if (W_out) {
         std::vector<float> pad(h->cpad * h->dpad);
-        HEAD_TRY(bn::gated::Memcpy(pad.data(), h->d_W, pad.size() * sizeof(float), hipMemcpyDeviceToHost));
+        BN_HIP_TRY(bn::gated::Memcpy(pad.data(), h->d_W, pad.size() * sizeof(float), hipMemcpyDeviceToHost));
         for (size_t c = 0; c < h->classes; c++) memcpy(W_out + c * h->dim, pad.data() + c * h->dpad, h->dim * sizeof(float));
     }
-    if (bias_out) HEAD_TRY(bn::gated::Memcpy(bias_out, h->d_b, h->classes * sizeof(float), hipMemcpyDeviceToHost));
+    if (bias_out) BN_HIP_TRY(bn::gated::Memcpy(bias_out, h->d_b, h->classes * sizeof(float), hipMemcpyDeviceToHost));
     return BN_OK;
 }
 
 bn_status bn_head_apply_host(const bn_head *hc, const float *rows, size_t n, float *logits_out) {
-    if (bn_device_count() <= 0) return set_last_error(BN_ERR_NO_DEVICE, "no gfx950 device visible");
+    if (bn_status dst = bn::require_any_device(); dst != BN_OK) return dst;
     if (!hc) return set_last_error(BN_ERR_INVALID_ARG, "null head");
     if (n && (!rows || !logits_out)) return set_last_error(BN_ERR_INVALID_ARG, "null argument");
     bn_head *h = const_cast<bn_head *>(hc);  // the staging buffers are not part of the head's value
-    HEAD_TRY(bn::use_device(h->device));
+    BN_HIP_TRY(bn::use_device(h->device));
     // each piece on its own: a call that failed half way leaves the rest to the next one
-    if (!h->stream) HEAD_TRY(bn::gated::StreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    if (!h->d_raw) HEAD_TRY(bn::gated::Malloc(&h->d_raw, CHUNK * h->dim * sizeof(float)));
-    if (!h->d_x) HEAD_TRY(bn::gated::Malloc(&h->d_x, CHUNK * h->dpad * sizeof(float)));
-    if (!h->d_z) HEAD_TRY(bn::gated::Malloc(&h->d_z, CHUNK * h->classes * sizeof(float)));
+    if (!h->stream) BN_HIP_TRY(bn::gated::StreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    if (!h->d_raw) BN_HIP_TRY(bn::gated::Malloc(&h->d_raw, CHUNK * h->dim * sizeof(float)));
+    if (!h->d_x) BN_HIP_TRY(bn::gated::Malloc(&h->d_x, CHUNK * h->dpad * sizeof(float)));
+    if (!h->d_z) BN_HIP_TRY(bn::gated::Malloc(&h->d_z, CHUNK * h->classes * sizeof(float)));
     for (size_t r0 = 0; r0 < n; r0 += CHUNK) {
         const size_t k = std::min(CHUNK, n - r0);
-        HEAD_TRY(bn::gated::Memcpy(h->d_raw, rows + r0 * h->dim, k * h->dim * sizeof(float), hipMemcpyHostToDevice));
+        BN_HIP_TRY(bn::gated::Memcpy(h->d_raw, rows + r0 * h->dim, k * h->dim * sizeof(float), hipMemcpyHostToDevice));
         bn_status st = enqueue_apply(h, h->stream, h->d_raw, k, h->d_x, h->d_z);
         if (st != BN_OK) return st;
-        HEAD_TRY(hipStreamSynchronize(h->stream));
-        HEAD_TRY(bn::gated::Memcpy(logits_out + r0 * h->classes, h->d_z, k * h->classes * sizeof(float), hipMemcpyDeviceToHost));
+        BN_HIP_TRY(hipStreamSynchronize(h->stream));
+        BN_HIP_TRY(bn::gated::Memcpy(logits_out + r0 * h->classes, h->d_z, k * h->classes * sizeof(float), hipMemcpyDeviceToHost));
     }
     return BN_OK;
 }
@@ -830,22 +765,23 @@ bn_status bn_head_fit(int32_t device, size_t dim, size_t n_classes, const float 
     std::vector<float> pw;
     if ((st = read_opts(opts, opts_size, n_classes, &o, &pw)) != BN_OK) return st;
     if ((st = check_labels(labels, n * n_classes)) != BN_OK) return st;
-    if ((st = check_device(device)) != BN_OK) return st;
+    if ((st = bn::require_device(device)) != BN_OK) return st;
     std::unique_ptr<bn_head, void (*)(bn_head *)> h(nullptr, head_unref);
     if ((st = new_head(device, dim, n_classes, o.flags, h)) != BN_OK) return st;
-    DevBufs bufs;
-    HEAD_TRY(bn::gated::StreamCreateWithFlags(&bufs.stream, hipStreamNonBlocking));
+    bn::Scratch bufs;
+    BN_HIP_TRY(bn::gated::StreamCreateWithFlags(&bufs.stream, hipStreamNonBlocking));
+    bufs.owns_stream = true;
     const size_t npad = round_up(n, RB);
     float *d_X = nullptr, *d_raw = nullptr;
-    HEAD_TRY(bufs.alloc(&d_X, npad * h->dpad * sizeof(float), false));
-    HEAD_TRY(bufs.alloc(&d_raw, CHUNK * dim * sizeof(float), false));
+    BN_HIP_TRY(bufs.alloc(&d_X, npad * h->dpad * sizeof(float), false));
+    BN_HIP_TRY(bufs.alloc(&d_raw, CHUNK * dim * sizeof(float), false));
     for (size_t r0 = 0; r0 < npad; r0 += CHUNK) {  // the last round also zeroes the slab's padding rows
         const size_t rows_here = std::min(CHUNK, npad - r0), real = r0 < n ? std::min(CHUNK, n - r0) : 0;
-        if (real) HEAD_TRY(bn::gated::Memcpy(d_raw, rows + r0 * dim, real * dim * sizeof(float), hipMemcpyHostToDevice));
+        if (real) BN_HIP_TRY(bn::gated::Memcpy(d_raw, rows + r0 * dim, real * dim * sizeof(float), hipMemcpyHostToDevice));
         hipLaunchKernelGGL(head_prep_kernel, dim3((unsigned)((rows_here + 3) / 4)), dim3(256), 0, bufs.stream, d_raw, dim, (uint32_t)real, (uint32_t)rows_here,
                            (uint32_t)dim, (o.flags & BN_HEAD_L2NORM) ? 1 : 0, d_X + r0 * h->dpad, (uint32_t)h->dpad);
         if ((st = check_launch("head prep")) != BN_OK) return st;
-        HEAD_TRY(hipStreamSynchronize(bufs.stream));
+        BN_HIP_TRY(hipStreamSynchronize(bufs.stream));
     }
     bn_head_fit_report rep{};
     if ((st = solve(bufs, h.get(), d_X, n, npad, labels, pw, o, &rep)) != BN_OK) return st;
@@ -858,7 +794,7 @@ bn_status bn_head_fit_index(bn_index *x, const uint64_t *ids, const uint8_t *lab
                             size_t opts_size, bn_head **out, bn_head_fit_report *report, size_t report_size) {
     if (!out) return set_last_error(BN_ERR_INVALID_ARG, "null argument");
     *out = nullptr;
-    if (bn_device_count() <= 0) return set_last_error(BN_ERR_NO_DEVICE, "no gfx950 device visible");
+    if (bn_status dst = bn::require_any_device(); dst != BN_OK) return dst;
     if (!x) return set_last_error(BN_ERR_INVALID_ARG, "null index");
     bn::IndexRows ir;
     bn_status st = bn::index_rows(x, &ir);
@@ -872,9 +808,9 @@ bn_status bn_head_fit_index(bn_index *x, const uint64_t *ids, const uint8_t *lab
     if ((st = read_opts(opts, opts_size, n_classes, &o, &pw)) != BN_OK) return st;
     o.flags = BN_HEAD_L2NORM;
     if ((st = check_labels(labels, n * n_classes)) != BN_OK) return st;
-    HEAD_TRY(bn::use_device(ir.device));
+    BN_HIP_TRY(bn::use_device(ir.device));
     std::vector<uint8_t> valid(ir.size);
-    if (ir.size) HEAD_TRY(bn::gated::Memcpy(valid.data(), ir.valid, ir.size, hipMemcpyDeviceToHost));
+    if (ir.size) BN_HIP_TRY(bn::gated::Memcpy(valid.data(), ir.valid, ir.size, hipMemcpyDeviceToHost));
     std::vector<uint32_t> id32(n);
     for (size_t i = 0; i < n; i++) {
         if (ids[i] >= ir.size) return set_last_error(BN_ERR_INVALID_ARG, "id " + std::to_string(ids[i]) + " is not in the index");
@@ -883,14 +819,15 @@ bn_status bn_head_fit_index(bn_index *x, const uint64_t *ids, const uint8_t *lab
     }
     std::unique_ptr<bn_head, void (*)(bn_head *)> h(nullptr, head_unref);
     if ((st = new_head(ir.device, ir.dim, n_classes, o.flags, h)) != BN_OK) return st;
-    DevBufs bufs;
-    HEAD_TRY(bn::gated::StreamCreateWithFlags(&bufs.stream, hipStreamNonBlocking));
+    bn::Scratch bufs;
+    BN_HIP_TRY(bn::gated::StreamCreateWithFlags(&bufs.stream, hipStreamNonBlocking));
+    bufs.owns_stream = true;
     const size_t npad = round_up(n, RB);
     float *d_X = nullptr;
     uint32_t *d_ids = nullptr;
-    HEAD_TRY(bufs.alloc(&d_X, npad * h->dpad * sizeof(float), false));
-    HEAD_TRY(bufs.alloc(&d_ids, n * sizeof(uint32_t), false));
-    HEAD_TRY(bn::gated::Memcpy(d_ids, id32.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    BN_HIP_TRY(bufs.alloc(&d_X, npad * h->dpad * sizeof(float), false));
+    BN_HIP_TRY(bufs.alloc(&d_ids, n * sizeof(uint32_t), false));
+    BN_HIP_TRY(bn::gated::Memcpy(d_ids, id32.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
     hipLaunchKernelGGL(head_gather_kernel, dim3((unsigned)npad), dim3(256), 0, bufs.stream, ir.slab, d_ids, (uint32_t)n, (uint32_t)h->dpad, d_X);
     if ((st = check_launch("head gather")) != BN_OK) return st;
     bn_head_fit_report rep{};

@@ -337,11 +337,7 @@ namespace {
 
 using bn::set_last_error;
 
-#define IDX_TRY(expr)                                                                                              \
-    do {                                                                                                           \
-        hipError_t e_ = (expr);                                                                                    \
-        if (e_ != hipSuccess) return set_last_error(BN_ERR_BACKEND, std::string(#expr) + " failed: " + hipGetErrorString(e_)); \
-    } while (0)
+using bn::check_launch;
 
 void release(bn_index *x) {
     if (!x) return;
@@ -362,14 +358,8 @@ void release(bn_index *x) {
 
 // device and stream of the index current, and the index's stream ordered after the last bn_index_add_ctx
 bn_status begin(const bn_index *x) {
-    IDX_TRY(bn::use_device(x->device));
-    if (x->pending) IDX_TRY(hipStreamWaitEvent(x->stream, x->ev, 0));
-    return BN_OK;
-}
-
-bn_status check_launch(const char *what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_last_error(BN_ERR_BACKEND, std::string(what) + " launch failed: " + hipGetErrorString(e));
+    BN_HIP_TRY(bn::use_device(x->device));
+    if (x->pending) BN_HIP_TRY(hipStreamWaitEvent(x->stream, x->ev, 0));
     return BN_OK;
 }
 
@@ -407,9 +397,9 @@ bn_status run_search(bn_index *x, size_t nq, bool by_id, int64_t radius, int M) 
         st = check_launch("index merge");
         if (st != BN_OK) return st;
     }
-    IDX_TRY(hipMemcpyAsync(x->h_out, x->d_out, nq * M * sizeof(Cand), hipMemcpyDeviceToHost, x->stream));
-    IDX_TRY(hipMemcpyAsync(x->h_count, x->d_count, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, x->stream));
-    IDX_TRY(hipStreamSynchronize(x->stream));
+    BN_HIP_TRY(hipMemcpyAsync(x->h_out, x->d_out, nq * M * sizeof(Cand), hipMemcpyDeviceToHost, x->stream));
+    BN_HIP_TRY(hipMemcpyAsync(x->h_count, x->d_count, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, x->stream));
+    BN_HIP_TRY(hipStreamSynchronize(x->stream));
     return BN_OK;
 }
 
@@ -437,7 +427,7 @@ bn_status bn::index_rows(bn_index *x, IndexRows *out) {
     if (!x || !out) return set_last_error(BN_ERR_INVALID_ARG, "null index");
     bn_status st = begin(x);
     if (st != BN_OK) return st;
-    IDX_TRY(hipStreamSynchronize(x->stream));
+    BN_HIP_TRY(hipStreamSynchronize(x->stream));
     out->device = x->device;
     out->slab = x->slab;
     out->valid = x->valid;
@@ -456,11 +446,9 @@ bn_status bn_index_create(int32_t device, size_t dim, size_t capacity_rows, bn_i
     if (dim > (1u << 20)) return set_last_error(BN_ERR_INVALID_ARG, "dim above 2^20");
     if (capacity_rows == 0) return set_last_error(BN_ERR_INVALID_ARG, "capacity_rows must be at least 1");
     if (capacity_rows >= 0xffffffffull - TILE) return set_last_error(BN_ERR_INVALID_ARG, "capacity_rows must be below 2^32 - 64");
-    if (bn_device_count() <= 0) return set_last_error(BN_ERR_NO_DEVICE, "no gfx950 device visible");
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) return set_last_error(BN_ERR_NO_DEVICE, "no such device");
-    IDX_TRY(bn::use_device(device));
-    IDX_TRY(prepare_scan(device));
+    if (bn_status dst = bn::require_device(device); dst != BN_OK) return dst;
+    BN_HIP_TRY(bn::use_device(device));
+    BN_HIP_TRY(prepare_scan(device));
     std::unique_ptr<bn_index, void (*)(bn_index *)> x(new bn_index, release);
     x->device = device;
     x->dim = dim;
@@ -468,24 +456,24 @@ bn_status bn_index_create(int32_t device, size_t dim, size_t capacity_rows, bn_i
     x->cap = capacity_rows;
     x->cap_pad = (capacity_rows + TILE - 1) / TILE * TILE;
     int cus = 0;
-    IDX_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+    BN_HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
     x->max_wg = std::max(1, cus);
-    IDX_TRY(bn::gated::StreamCreateWithFlags(&x->stream, hipStreamNonBlocking));
-    IDX_TRY(bn::gated::EventCreateWithFlags(&x->ev, hipEventDisableTiming));
-    IDX_TRY(bn::gated::Malloc(&x->slab, x->cap_pad * x->dpad * sizeof(float)));
-    IDX_TRY(bn::gated::Memset(x->slab, 0, x->cap_pad * x->dpad * sizeof(float)));
-    IDX_TRY(bn::gated::Malloc(&x->valid, x->cap_pad));
-    IDX_TRY(bn::gated::Memset(x->valid, 0, x->cap_pad));
-    IDX_TRY(bn::gated::Malloc(&x->d_stage, STAGE_ROWS * dim * sizeof(float)));
-    IDX_TRY(bn::gated::Malloc(&x->d_q, QCHUNK * x->dpad * sizeof(float)));
-    IDX_TRY(bn::gated::Malloc(&x->d_qvalid, QCHUNK));
-    IDX_TRY(bn::gated::Malloc(&x->d_qid, QCHUNK * sizeof(uint32_t)));
-    IDX_TRY(bn::gated::Malloc(&x->d_cand, (size_t)x->max_wg * QP * MMAX * sizeof(Cand)));
-    IDX_TRY(bn::gated::Malloc(&x->d_cand_len, (size_t)x->max_wg * QP * sizeof(int)));
-    IDX_TRY(bn::gated::Malloc(&x->d_out, QCHUNK * MMAX * sizeof(Cand)));
-    IDX_TRY(bn::gated::Malloc(&x->d_count, QCHUNK * sizeof(uint32_t)));
-    IDX_TRY(bn::gated::HostMalloc(&x->h_out, QCHUNK * MMAX * sizeof(Cand), 0));
-    IDX_TRY(bn::gated::HostMalloc(&x->h_count, QCHUNK * sizeof(uint32_t), 0));
+    BN_HIP_TRY(bn::gated::StreamCreateWithFlags(&x->stream, hipStreamNonBlocking));
+    BN_HIP_TRY(bn::gated::EventCreateWithFlags(&x->ev, hipEventDisableTiming));
+    BN_HIP_TRY(bn::gated::Malloc(&x->slab, x->cap_pad * x->dpad * sizeof(float)));
+    BN_HIP_TRY(bn::gated::Memset(x->slab, 0, x->cap_pad * x->dpad * sizeof(float)));
+    BN_HIP_TRY(bn::gated::Malloc(&x->valid, x->cap_pad));
+    BN_HIP_TRY(bn::gated::Memset(x->valid, 0, x->cap_pad));
+    BN_HIP_TRY(bn::gated::Malloc(&x->d_stage, STAGE_ROWS * dim * sizeof(float)));
+    BN_HIP_TRY(bn::gated::Malloc(&x->d_q, QCHUNK * x->dpad * sizeof(float)));
+    BN_HIP_TRY(bn::gated::Malloc(&x->d_qvalid, QCHUNK));
+    BN_HIP_TRY(bn::gated::Malloc(&x->d_qid, QCHUNK * sizeof(uint32_t)));
+    BN_HIP_TRY(bn::gated::Malloc(&x->d_cand, (size_t)x->max_wg * QP * MMAX * sizeof(Cand)));
+    BN_HIP_TRY(bn::gated::Malloc(&x->d_cand_len, (size_t)x->max_wg * QP * sizeof(int)));
+    BN_HIP_TRY(bn::gated::Malloc(&x->d_out, QCHUNK * MMAX * sizeof(Cand)));
+    BN_HIP_TRY(bn::gated::Malloc(&x->d_count, QCHUNK * sizeof(uint32_t)));
+    BN_HIP_TRY(bn::gated::HostMalloc(&x->h_out, QCHUNK * MMAX * sizeof(Cand), 0));
+    BN_HIP_TRY(bn::gated::HostMalloc(&x->h_count, QCHUNK * sizeof(uint32_t), 0));
     *out = x.release();
     return BN_OK;
 }
@@ -504,13 +492,13 @@ bn_status bn_index_add_host(bn_index *x, const float *rows, size_t n, uint64_t *
     const size_t first = x->size;
     for (size_t r0 = 0; r0 < n; r0 += STAGE_ROWS) {
         const size_t k = std::min(STAGE_ROWS, n - r0);
-        IDX_TRY(hipStreamSynchronize(x->stream));  // the previous chunk's kernel has read the staging buffer
-        IDX_TRY(bn::gated::Memcpy(x->d_stage, rows + r0 * x->dim, k * x->dim * sizeof(float), hipMemcpyHostToDevice));
+        BN_HIP_TRY(hipStreamSynchronize(x->stream));  // the previous chunk's kernel has read the staging buffer
+        BN_HIP_TRY(bn::gated::Memcpy(x->d_stage, rows + r0 * x->dim, k * x->dim * sizeof(float), hipMemcpyHostToDevice));
         hipLaunchKernelGGL(index_normalise_kernel, dim3((unsigned)((k + 3) / 4)), dim3(256), 0, x->stream, x->d_stage, x->dim, (uint32_t)k,
                            (uint32_t)x->dim, x->slab + (first + r0) * x->dpad, (uint32_t)x->dpad, x->valid + first + r0);
         if ((st = check_launch("index normalise")) != BN_OK) return st;
     }
-    IDX_TRY(hipStreamSynchronize(x->stream));
+    BN_HIP_TRY(hipStreamSynchronize(x->stream));
     x->size = first + n;
     if (first_id) *first_id = first;
     return BN_OK;
@@ -529,13 +517,13 @@ bn_status bn_index_add_ctx(bn_index *x, bn_ctx *c, size_t batch_size, uint64_t *
     if ((st = reserve_rows(x, batch_size)) != BN_OK) return st;
     const size_t first = x->size;
     if (batch_size) {
-        IDX_TRY(bn::use_device(x->device));
+        BN_HIP_TRY(bn::use_device(x->device));
         // the index's own stream is idle between calls; appends from several contexts stay in call order
-        if (x->pending) IDX_TRY(hipStreamWaitEvent(e.stream, x->ev, 0));
+        if (x->pending) BN_HIP_TRY(hipStreamWaitEvent(e.stream, x->ev, 0));
         hipLaunchKernelGGL(index_normalise_kernel, dim3((unsigned)((batch_size + 3) / 4)), dim3(256), 0, e.stream, e.d_rows, e.row_elems,
                            (uint32_t)batch_size, (uint32_t)x->dim, x->slab + first * x->dpad, (uint32_t)x->dpad, x->valid + first);
         if ((st = check_launch("index normalise")) != BN_OK) return st;
-        IDX_TRY(hipEventRecord(x->ev, e.stream));
+        BN_HIP_TRY(hipEventRecord(x->ev, e.stream));
         x->pending = true;
         x->size = first + batch_size;
     }
@@ -549,12 +537,12 @@ bn_status bn_index_read(const bn_index *x, uint64_t first, size_t count, float *
     if (count && !host_out) return set_last_error(BN_ERR_INVALID_ARG, "null host buffer");
     bn_status st = begin(x);
     if (st != BN_OK) return st;
-    IDX_TRY(hipStreamSynchronize(x->stream));
+    BN_HIP_TRY(hipStreamSynchronize(x->stream));
     std::vector<float> tmp;
     for (size_t r0 = 0; r0 < count; r0 += STAGE_ROWS) {
         const size_t k = std::min(STAGE_ROWS, count - r0);
         tmp.resize(k * x->dpad);
-        IDX_TRY(bn::gated::Memcpy(tmp.data(), x->slab + (first + r0) * x->dpad, k * x->dpad * sizeof(float), hipMemcpyDeviceToHost));
+        BN_HIP_TRY(bn::gated::Memcpy(tmp.data(), x->slab + (first + r0) * x->dpad, k * x->dpad * sizeof(float), hipMemcpyDeviceToHost));
         for (size_t i = 0; i < k; i++) memcpy(host_out + (r0 + i) * x->dim, tmp.data() + i * x->dpad, x->dim * sizeof(float));
     }
     return BN_OK;
@@ -573,8 +561,8 @@ bn_status bn_index_search(bn_index *x, const float *queries, size_t n_queries, s
         }
         for (size_t s0 = 0; s0 < nq; s0 += STAGE_ROWS) {
             const size_t k = std::min(STAGE_ROWS, nq - s0);
-            IDX_TRY(hipStreamSynchronize(x->stream));
-            IDX_TRY(bn::gated::Memcpy(x->d_stage, queries + (q0 + s0) * x->dim, k * x->dim * sizeof(float), hipMemcpyHostToDevice));
+            BN_HIP_TRY(hipStreamSynchronize(x->stream));
+            BN_HIP_TRY(bn::gated::Memcpy(x->d_stage, queries + (q0 + s0) * x->dim, k * x->dim * sizeof(float), hipMemcpyHostToDevice));
             hipLaunchKernelGGL(index_normalise_kernel, dim3((unsigned)((k + 3) / 4)), dim3(256), 0, x->stream, x->d_stage, x->dim, (uint32_t)k,
                                (uint32_t)x->dim, x->d_q + s0 * x->dpad, (uint32_t)x->dpad, x->d_qvalid + s0);
             if ((st = check_launch("index normalise")) != BN_OK) return st;
@@ -596,8 +584,8 @@ bn_status bn_index_search_ids(bn_index *x, const uint64_t *query_ids, size_t n_q
     for (size_t q0 = 0; q0 < n_queries; q0 += QCHUNK) {
         const size_t nq = std::min(QCHUNK, n_queries - q0);
         ids.assign(query_ids + q0, query_ids + q0 + nq);
-        IDX_TRY(hipStreamSynchronize(x->stream));
-        IDX_TRY(bn::gated::Memcpy(x->d_qid, ids.data(), nq * sizeof(uint32_t), hipMemcpyHostToDevice));
+        BN_HIP_TRY(hipStreamSynchronize(x->stream));
+        BN_HIP_TRY(bn::gated::Memcpy(x->d_qid, ids.data(), nq * sizeof(uint32_t), hipMemcpyHostToDevice));
         hipLaunchKernelGGL(index_gather_kernel, dim3((unsigned)nq), dim3(256), 0, x->stream, x->slab, x->valid, x->d_qid, (uint32_t)x->dpad, x->d_q,
                            x->d_qvalid);
         if ((st = check_launch("index gather")) != BN_OK) return st;

@@ -104,12 +104,6 @@ namespace {
 
 using bn::set_last_error;
 
-#define LIVE_TRY(expr)                                                                                                             \
-    do {                                                                                                                           \
-        hipError_t e_ = (expr);                                                                                                    \
-        if (e_ != hipSuccess) return set_last_error(BN_ERR_BACKEND, std::string(#expr) + " failed: " + hipGetErrorString(e_)); \
-    } while (0)
-
 bn_status invalid(const std::string &msg) { return set_last_error(BN_ERR_INVALID_ARG, msg); }
 
 bool source_ok(const bn_live *l, int32_t s) { return l && s >= 0 && s < l->n_sources; }
@@ -189,7 +183,7 @@ bn_status wait_readers(bn_live *l, Source &s, uint64_t limit, std::vector<uint64
     for (const auto &rd : s.reads) {
         if (rd.first >= limit) break;
         if (std::find(waited.begin(), waited.end(), rd.second) != waited.end() || gather_done(l, rd.second)) continue;
-        LIVE_TRY(hipStreamWaitEvent(l->stream, l->gathers[rd.second - l->gathers.front().id].ev, 0));
+        BN_HIP_TRY(hipStreamWaitEvent(l->stream, l->gathers[rd.second - l->gathers.front().id].ev, 0));
         waited.push_back(rd.second);
     }
     return BN_OK;
@@ -198,15 +192,15 @@ bn_status wait_readers(bn_live *l, Source &s, uint64_t limit, std::vector<uint64
 // the next pinned staging block, free to be written and at least `bytes` large
 bn_status acquire_stage(bn_live *l, size_t bytes, Stage **out) {
     Stage &st = l->stage[l->next_stage];
-    if (st.used) LIVE_TRY(hipEventSynchronize(st.ev));
+    if (st.used) BN_HIP_TRY(hipEventSynchronize(st.ev));
     if (bytes > st.cap) {
         const size_t cap = std::max(bytes, st.cap * 3 / 2);
         if (st.h) (void)bn::gated::HostFree(st.h);
         if (st.d) (void)bn::gated::Free(st.d);
         st.h = st.d = nullptr;
         st.cap = 0;
-        LIVE_TRY(bn::gated::HostMalloc(&st.h, cap, hipHostMallocDefault));
-        if (l->copy_mode) LIVE_TRY(bn::gated::Malloc(&st.d, cap));
+        BN_HIP_TRY(bn::gated::HostMalloc(&st.h, cap, hipHostMallocDefault));
+        if (l->copy_mode) BN_HIP_TRY(bn::gated::Malloc(&st.d, cap));
         st.cap = cap;
     }
     *out = &st;
@@ -246,7 +240,7 @@ bn_status scatter_rates(bn_live *l, const std::vector<std::pair<int32_t, uint64_
             o += len;
         }
     }
-    LIVE_TRY(bn::use_device(l->device));
+    BN_HIP_TRY(bn::use_device(l->device));
     retire_gathers(l);
     if (tiles.empty() && total == 0) return BN_OK;
     const size_t jobs_b = pad256(jobs.size() * sizeof(bn::LiveRsJob));
@@ -279,19 +273,19 @@ bn_status scatter_rates(bn_live *l, const std::vector<std::pair<int32_t, uint64_
             if (bs != BN_OK) return bs;
         }
     }
-    (void)hipGetLastError();
+    bn::clear_launch_state();
     const char *blk = st.h;
     if (l->copy_mode) {
-        LIVE_TRY(hipMemcpyAsync(st.d, st.h, bytes, hipMemcpyHostToDevice, l->stream));
+        BN_HIP_TRY(hipMemcpyAsync(st.d, st.h, bytes, hipMemcpyHostToDevice, l->stream));
         blk = st.d;
     }
     const bn::LiveRsJob *d_jobs = reinterpret_cast<const bn::LiveRsJob *>(blk);
     bn::launch_live_resample(l->stream, static_cast<float *>(l->slab), l->in_i16, l->d_tables, l->d_coef, l->d_hist, d_jobs,
                              reinterpret_cast<const bn::LiveRsTile *>(blk + jobs_b), (uint32_t)tiles.size(), blk + jobs_b + tiles_b, l->lds_bytes);
     if (!closing) bn::launch_live_history(l->stream, l->d_hist, l->in_i16, l->d_tables, d_jobs, (uint32_t)jobs.size(), blk + jobs_b + tiles_b);
-    LIVE_TRY(hipGetLastError());
-    LIVE_TRY(hipEventRecord(st.ev, l->stream));
-    LIVE_TRY(hipEventRecord(l->scatter_ev, l->stream));
+    if (bn_status lst = bn::check_launch("live resample"); lst != BN_OK) return lst;
+    BN_HIP_TRY(hipEventRecord(st.ev, l->stream));
+    BN_HIP_TRY(hipEventRecord(l->scatter_ev, l->stream));
     st.used = true;
     l->scattered = true;
     l->next_stage = (l->next_stage + 1) % N_STAGE;
@@ -368,7 +362,7 @@ bn_status push_impl(bn_live *l, size_t n, const int32_t *sources, const void *co
     }
     const size_t tiles_b = (tiles.size() * sizeof(bn::LiveTile) + 255) / 256 * 256;
     const size_t bytes = tiles_b + total * l->esz;
-    LIVE_TRY(bn::use_device(l->device));
+    BN_HIP_TRY(bn::use_device(l->device));
     retire_gathers(l);
     // a staging block is reused only after the scatter that read it completed
     Stage *stp = nullptr;
@@ -396,17 +390,17 @@ bn_status push_impl(bn_live *l, size_t n, const int32_t *sources, const void *co
             if (bs != BN_OK) return bs;
         }
     }
-    (void)hipGetLastError();
+    bn::clear_launch_state();
     const char *blk = st.h;
     if (l->copy_mode) {
-        LIVE_TRY(hipMemcpyAsync(st.d, st.h, bytes, hipMemcpyHostToDevice, l->stream));
+        BN_HIP_TRY(hipMemcpyAsync(st.d, st.h, bytes, hipMemcpyHostToDevice, l->stream));
         blk = st.d;
     }
     bn::launch_live_scatter(l->stream, l->slab, l->format == BN_PCM_I16, reinterpret_cast<const bn::LiveTile *>(blk), (uint32_t)tiles.size(),
                             blk + tiles_b);
-    LIVE_TRY(hipGetLastError());
-    LIVE_TRY(hipEventRecord(st.ev, l->stream));
-    LIVE_TRY(hipEventRecord(l->scatter_ev, l->stream));
+    if (bn_status lst = bn::check_launch("live scatter"); lst != BN_OK) return lst;
+    BN_HIP_TRY(hipEventRecord(st.ev, l->stream));
+    BN_HIP_TRY(hipEventRecord(l->scatter_ev, l->stream));
     st.used = true;
     l->scattered = true;
     l->next_stage = (l->next_stage + 1) % N_STAGE;
@@ -491,13 +485,13 @@ bn_status setup_rates(bn_live *l, uint32_t dst_rate, const uint32_t *src_rates, 
     l->lds_bytes = lds_floats * (uint32_t)sizeof(float);
     l->hist_cap = max_T - 1;
     const size_t hist_b = (size_t)l->n_sources * l->hist_cap * sizeof(float);
-    LIVE_TRY(bn::gated::Malloc(reinterpret_cast<void **>(&l->d_hist), hist_b));
-    LIVE_TRY(bn::gated::Memset(l->d_hist, 0, hist_b));
+    BN_HIP_TRY(bn::gated::Malloc(reinterpret_cast<void **>(&l->d_hist), hist_b));
+    BN_HIP_TRY(bn::gated::Memset(l->d_hist, 0, hist_b));
     if (!l->tables.empty()) {
-        LIVE_TRY(bn::gated::Malloc(reinterpret_cast<void **>(&l->d_tables), l->tables.size() * sizeof(bn::LiveRsTable)));
-        LIVE_TRY(bn::gated::Memcpy(l->d_tables, l->tables.data(), l->tables.size() * sizeof(bn::LiveRsTable), hipMemcpyHostToDevice));
-        LIVE_TRY(bn::gated::Malloc(reinterpret_cast<void **>(&l->d_coef), coef.size() * sizeof(float)));
-        LIVE_TRY(bn::gated::Memcpy(l->d_coef, coef.data(), coef.size() * sizeof(float), hipMemcpyHostToDevice));
+        BN_HIP_TRY(bn::gated::Malloc(reinterpret_cast<void **>(&l->d_tables), l->tables.size() * sizeof(bn::LiveRsTable)));
+        BN_HIP_TRY(bn::gated::Memcpy(l->d_tables, l->tables.data(), l->tables.size() * sizeof(bn::LiveRsTable), hipMemcpyHostToDevice));
+        BN_HIP_TRY(bn::gated::Malloc(reinterpret_cast<void **>(&l->d_coef), coef.size() * sizeof(float)));
+        BN_HIP_TRY(bn::gated::Memcpy(l->d_coef, coef.data(), coef.size() * sizeof(float), hipMemcpyHostToDevice));
     }
     return BN_OK;
 }
@@ -518,10 +512,8 @@ bn_status create_pool(int32_t device, int32_t n_sources, int32_t format, size_t 
         for (int32_t s = 0; s < n_sources; s++)
             if (src_rates[s] == 0) return invalid("source " + std::to_string(s) + ": sample rates must be positive");
     }
-    if (bn_device_count() <= 0) return set_last_error(BN_ERR_NO_DEVICE, "no gfx950 device visible");
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) return set_last_error(BN_ERR_NO_DEVICE, "no such device");
-    LIVE_TRY(bn::use_device(device));
+    if (bn_status dst = bn::require_device(device); dst != BN_OK) return dst;
+    BN_HIP_TRY(bn::use_device(device));
     std::unique_ptr<bn_live, void (*)(bn_live *)> l(new bn_live, release);
     l->device = device;
     l->n_sources = n_sources;
@@ -552,12 +544,12 @@ bn_status create_pool(int32_t device, int32_t n_sources, int32_t format, size_t 
         }
     }
     const size_t slab_b = (size_t)n_sources * ring_samples * l->esz;
-    LIVE_TRY(bn::gated::StreamCreateWithFlags(&l->stream, hipStreamNonBlocking));
-    LIVE_TRY(bn::gated::EventCreateWithFlags(&l->scatter_ev, hipEventDisableTiming));
-    for (auto &st : l->stage) LIVE_TRY(bn::gated::EventCreateWithFlags(&st.ev, hipEventDisableTiming));
-    LIVE_TRY(bn::gated::Malloc(&l->slab, slab_b));
-    LIVE_TRY(bn::gated::Memset(l->slab, 0, slab_b));
-    LIVE_TRY(bn::gated::Malloc(&l->d_window, segment_samples * sizeof(float)));
+    BN_HIP_TRY(bn::gated::StreamCreateWithFlags(&l->stream, hipStreamNonBlocking));
+    BN_HIP_TRY(bn::gated::EventCreateWithFlags(&l->scatter_ev, hipEventDisableTiming));
+    for (auto &st : l->stage) BN_HIP_TRY(bn::gated::EventCreateWithFlags(&st.ev, hipEventDisableTiming));
+    BN_HIP_TRY(bn::gated::Malloc(&l->slab, slab_b));
+    BN_HIP_TRY(bn::gated::Memset(l->slab, 0, slab_b));
+    BN_HIP_TRY(bn::gated::Malloc(&l->d_window, segment_samples * sizeof(float)));
     *out = l.release();
     return BN_OK;
 }
@@ -657,15 +649,15 @@ bn_status bn_live_read_window(const bn_live *lc, int32_t source, uint64_t window
     if (window < s.sched || window >= s.n_ready)
         return invalid("window " + std::to_string(window) + " of source " + std::to_string(source) + " is not ready and unscheduled (ready: [" +
                        std::to_string(s.sched) + ", " + std::to_string(s.n_ready) + "))");
-    LIVE_TRY(bn::use_device(l->device));
+    BN_HIP_TRY(bn::use_device(l->device));
     bn::LiveGatherRows rows;
     rows.r[0] = row_of(l, s, window);
     rows.r[0].base = (uint64_t)source * l->R;
-    (void)hipGetLastError();
+    bn::clear_launch_state();
     bn::launch_live_gather(l->stream, l->d_window, l->slab, l->format == BN_PCM_I16, (uint32_t)l->R, (uint32_t)l->S, rows, 1);
-    LIVE_TRY(hipGetLastError());
-    LIVE_TRY(hipStreamSynchronize(l->stream));
-    LIVE_TRY(bn::gated::Memcpy(host_out, l->d_window, l->S * sizeof(float), hipMemcpyDeviceToHost));
+    if (bn_status lst = bn::check_launch("live gather"); lst != BN_OK) return lst;
+    BN_HIP_TRY(hipStreamSynchronize(l->stream));
+    BN_HIP_TRY(bn::gated::Memcpy(host_out, l->d_window, l->S * sizeof(float), hipMemcpyDeviceToHost));
     return BN_OK;
 }
 
@@ -684,7 +676,7 @@ bn_status bn_step_live(bn_ctx *c, bn_live *l, size_t max_windows, size_t top_k, 
     if (prior && (st = bn::prior_live_check(prior, l->src.size())) != BN_OK) return st;
     const size_t B = std::min(max_windows, l->queue.size());
     if (B == 0) return BN_OK;
-    LIVE_TRY(bn::use_device(l->device));
+    BN_HIP_TRY(bn::use_device(l->device));
     retire_gathers(l);
     // the gather's event first: once the gather is launched, its order against later scatters must not be lost
     hipEvent_t ev = nullptr;
@@ -692,7 +684,7 @@ bn_status bn_step_live(bn_ctx *c, bn_live *l, size_t max_windows, size_t top_k, 
         ev = l->free_events.back();
         l->free_events.pop_back();
     } else {
-        LIVE_TRY(bn::gated::EventCreateWithFlags(&ev, hipEventDisableTiming));
+        BN_HIP_TRY(bn::gated::EventCreateWithFlags(&ev, hipEventDisableTiming));
     }
     const hipError_t we = l->scattered ? hipStreamWaitEvent(ci.stream, l->scatter_ev, 0) : hipSuccess;
     if (we != hipSuccess) {
@@ -700,7 +692,7 @@ bn_status bn_step_live(bn_ctx *c, bn_live *l, size_t max_windows, size_t top_k, 
         return set_last_error(BN_ERR_BACKEND, std::string("hipStreamWaitEvent failed: ") + hipGetErrorString(we));
     }
     // gather first, bookkeeping after: a launch failure leaves the pool unchanged
-    (void)hipGetLastError();
+    bn::clear_launch_state();
     for (size_t r0 = 0; r0 < B; r0 += bn::LIVE_GATHER_ROWS) {
         const size_t m = std::min<size_t>(bn::LIVE_GATHER_ROWS, B - r0);
         bn::LiveGatherRows rows;
@@ -712,10 +704,9 @@ bn_status bn_step_live(bn_ctx *c, bn_live *l, size_t max_windows, size_t top_k, 
         bn::launch_live_gather(ci.stream, ci.d_input + r0 * l->S, l->slab, l->format == BN_PCM_I16, (uint32_t)l->R, (uint32_t)l->S, rows,
                                (uint32_t)m);
     }
-    const hipError_t le = hipGetLastError();
-    if (le != hipSuccess) {
+    if (bn_status lst = bn::check_launch("live gather"); lst != BN_OK) {
         l->free_events.push_back(ev);
-        return set_last_error(BN_ERR_BACKEND, std::string("live gather launch failed: ") + hipGetErrorString(le));
+        return lst;
     }
     const hipError_t re = hipEventRecord(ev, ci.stream);
     if (re != hipSuccess) {

@@ -352,9 +352,8 @@ struct bn::PriorAttach {
     bool has_map = false;
     std::vector<int32_t> source_sites;
     int32_t site = 0;
-    uint32_t *d_rows = nullptr, *h_rows = nullptr;  // packed [idx: b*k][conf: b*k][count: b] of the last step
-    size_t rows_cap = 0;                            // words
-    uint32_t *d_gkeys = nullptr;                    // general select form: [max_batch, n_species]
+    bn::TopkRows rows;            // the last step's filtered rows: device block and pinned mirror
+    uint32_t *d_gkeys = nullptr;  // general select form: [max_batch, n_species]
     // per-row site ids of a live step: pinned, read by the kernel in place; a block is rewritten only after the step that
     // read it has completed (its event)
     int32_t *h_sites[N_STAGE] = {};
@@ -362,28 +361,15 @@ struct bn::PriorAttach {
     bool ev_used[N_STAGE] = {};
     int next_stage = 0, pending = -1;  // pending: the block staged for the step about to run
     size_t pending_rows = 0;
-    size_t last_batch = 0, k = 0;
-    bool stepped = false;
 };
 
 namespace {
 
 using bn::set_last_error;
 
-#define PRIOR_TRY(expr)                                                                                           \
-    do {                                                                                                          \
-        hipError_t e_ = (expr);                                                                                   \
-        if (e_ != hipSuccess) return set_last_error(BN_ERR_BACKEND, std::string(#expr) + " failed: " + hipGetErrorString(e_)); \
-    } while (0)
+using bn::check_launch;
 
 constexpr uint32_t KNOWN_FLAGS = BN_PRIOR_AFTER_TOPK | BN_PRIOR_RERANK;
-
-bn_status check_launch(const char *what) {
-    if (const char *why = bn::take_launch_error()) return set_last_error(BN_ERR_INVALID_ARG, std::string(what) + " refused: " + why);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_last_error(BN_ERR_BACKEND, std::string(what) + " launch failed: " + hipGetErrorString(e));
-    return BN_OK;
-}
 
 void prior_unref(bn_prior *p) {
     if (!p || p->refs.fetch_sub(1, std::memory_order_acq_rel) != 1) return;
@@ -466,40 +452,9 @@ bn_status enqueue_after(const bn_prior *p, hipStream_t stream, const uint32_t *i
     return check_launch("prior filter");
 }
 
-// the device buffers of one bn_prior_apply_host call, freed on every way out
-struct CallBufs {
-    std::vector<void *> ptrs;
-    hipStream_t stream = nullptr;
-    ~CallBufs() {
-        if (stream) (void)hipStreamSynchronize(stream);
-        for (void *q : ptrs) (void)bn::gated::Free(q);
-    }
-    template <class T>
-    hipError_t alloc(T **q, size_t bytes) {
-        hipError_t e = bn::gated::Malloc(q, bytes);
-        if (e == hipSuccess) ptrs.push_back(*q);
-        return e;
-    }
-};
-
 bn_status check_site(const bn_prior *p, int64_t site, const char *what) {
     if (site < 0 || (uint64_t)site >= p->n_sites)
         return set_last_error(BN_ERR_INVALID_ARG, std::string(what) + " " + std::to_string(site) + " is outside 0.." + std::to_string(p->n_sites));
-    return BN_OK;
-}
-
-bn_status grow_rows(bn::PriorAttach *a, hipStream_t stream, size_t k) {
-    const size_t need = a->max_batch * (2 * k + 1);
-    if (need <= a->rows_cap) return BN_OK;
-    if (stream) PRIOR_TRY(hipStreamSynchronize(stream));  // the last step may still write the old blocks
-    if (a->d_rows) (void)bn::gated::Free(a->d_rows);
-    if (a->h_rows) (void)bn::gated::HostFree(a->h_rows);
-    a->d_rows = a->h_rows = nullptr;
-    a->rows_cap = 0;
-    a->stepped = false;
-    PRIOR_TRY(bn::gated::Malloc(&a->d_rows, need * sizeof(uint32_t)));
-    PRIOR_TRY(bn::gated::HostMalloc(&a->h_rows, need * sizeof(uint32_t), hipHostMallocDefault));
-    a->rows_cap = need;
     return BN_OK;
 }
 
@@ -520,7 +475,7 @@ bn_status bn::prior_attach(bn_prior *p, int device, size_t num_species, size_t m
         bn_status st = check_site(p, source_sites[i], "the site of a source,");
         if (st != BN_OK) return st;
     }
-    PRIOR_TRY(bn::use_device(device));
+    BN_HIP_TRY(bn::use_device(device));
     std::unique_ptr<PriorAttach, void (*)(PriorAttach *)> a(new PriorAttach, prior_detach);
     a->max_batch = max_batch;
     a->top_k = top_k;
@@ -529,13 +484,13 @@ bn_status bn::prior_attach(bn_prior *p, int device, size_t num_species, size_t m
     a->has_map = source_sites != nullptr;
     if (source_sites) a->source_sites.assign(source_sites, source_sites + n_source_sites);
     if (!after) {
-        bn_status st = grow_rows(a.get(), nullptr, k);
+        bn_status st = a->rows.reserve(max_batch, k, nullptr, true, true);
         if (st != BN_OK) return st;
-        if (general_form(p)) PRIOR_TRY(bn::gated::Malloc(&a->d_gkeys, max_batch * p->n_species * sizeof(uint32_t)));
+        if (general_form(p)) BN_HIP_TRY(bn::gated::Malloc(&a->d_gkeys, max_batch * p->n_species * sizeof(uint32_t)));
     }
     for (int i = 0; i < N_STAGE; i++) {
-        PRIOR_TRY(bn::gated::HostMalloc(&a->h_sites[i], std::max<size_t>(max_batch, 1) * sizeof(int32_t), hipHostMallocDefault));
-        PRIOR_TRY(bn::gated::EventCreateWithFlags(&a->ev[i], hipEventDisableTiming));
+        BN_HIP_TRY(bn::gated::HostMalloc(&a->h_sites[i], std::max<size_t>(max_batch, 1) * sizeof(int32_t), hipHostMallocDefault));
+        BN_HIP_TRY(bn::gated::EventCreateWithFlags(&a->ev[i], hipEventDisableTiming));
     }
     p->refs.fetch_add(1, std::memory_order_relaxed);
     a->prior = p;
@@ -545,8 +500,7 @@ bn_status bn::prior_attach(bn_prior *p, int device, size_t num_species, size_t m
 
 void bn::prior_detach(PriorAttach *a) {
     if (!a) return;
-    if (a->d_rows) (void)bn::gated::Free(a->d_rows);
-    if (a->h_rows) (void)bn::gated::HostFree(a->h_rows);
+    a->rows.release();
     if (a->d_gkeys) (void)bn::gated::Free(a->d_gkeys);
     for (int i = 0; i < N_STAGE; i++) {
         if (a->h_sites[i]) (void)bn::gated::HostFree(a->h_sites[i]);
@@ -575,7 +529,7 @@ bn_status bn::prior_stage_rows(PriorAttach *a, const int32_t *sources, size_t ro
     if (!a->has_map) return BN_OK;  // every row at the context's site
     if (rows > a->max_batch) return set_last_error(BN_ERR_INVALID_ARG, "batch exceeds the context's max_batch");
     const int slot = a->next_stage;
-    if (a->ev_used[slot]) PRIOR_TRY(hipEventSynchronize(a->ev[slot]));
+    if (a->ev_used[slot]) BN_HIP_TRY(hipEventSynchronize(a->ev[slot]));
     for (size_t i = 0; i < rows; i++) {
         const int32_t src = sources[i];
         if (src < 0 || (size_t)src >= a->source_sites.size()) return set_last_error(BN_ERR_INVALID_ARG, "a source outside the attached prior's site map");
@@ -589,63 +543,41 @@ bn_status bn::prior_stage_rows(PriorAttach *a, const int32_t *sources, size_t ro
 
 void bn::prior_clear_rows(PriorAttach *a) { a->pending = -1; }
 
-bn_status bn::prior_step(PriorAttach *a, hipStream_t stream, const float *d_logits, size_t batch, const uint32_t *d_step_rows, size_t step_k) {
+bn_status bn::prior_step(PriorAttach *a, hipStream_t stream, const float *d_logits, size_t batch, const TopkRows::ConstView &step_rows) {
     const bn_prior *p = a->prior;
     if (batch > a->max_batch) return set_last_error(BN_ERR_INVALID_ARG, "batch exceeds the context's max_batch");
     const bool after = (p->flags & BN_PRIOR_AFTER_TOPK) != 0;
-    const size_t k = after ? step_k : std::min(a->top_k, p->n_species);
-    bn_status st = grow_rows(a, stream, k);
+    const size_t k = after ? step_rows.k : std::min(a->top_k, p->n_species);
+    bn_status st = a->rows.reserve(a->max_batch, k, stream, true, true);
     if (st != BN_OK) return st;
     const int32_t *sites = nullptr;
     const int slot = a->pending;
     a->pending = -1;
     if (slot >= 0 && a->pending_rows == batch) {
         void *dp = nullptr;
-        PRIOR_TRY(hipHostGetDevicePointer(&dp, a->h_sites[slot], 0));
+        BN_HIP_TRY(hipHostGetDevicePointer(&dp, a->h_sites[slot], 0));
         sites = static_cast<const int32_t *>(dp);
     }
-    uint32_t *d_idx = a->d_rows, *d_cnt = a->d_rows + 2 * batch * k;
-    float *d_conf = reinterpret_cast<float *>(a->d_rows + batch * k);
+    const TopkRows::View out = TopkRows::view(a->rows.d, batch, k);
     if (after)
-        st = enqueue_after(p, stream, d_step_rows, reinterpret_cast<const float *>(d_step_rows + batch * step_k), d_step_rows + 2 * batch * step_k, batch,
-                           sites, a->site, k, k, d_idx, d_conf, d_cnt);
+        st = enqueue_after(p, stream, step_rows.idx, step_rows.conf, step_rows.count, batch, sites, a->site, k, k, out.idx, out.conf, out.count);
     else
-        st = enqueue_select(p, stream, d_logits, batch, sites, a->site, k, a->has_min, a->min_conf, k, a->d_gkeys, d_idx, d_conf, d_cnt);
+        st = enqueue_select(p, stream, d_logits, batch, sites, a->site, k, a->has_min, a->min_conf, k, a->d_gkeys, out.idx, out.conf, out.count);
     if (st != BN_OK) return st;
     if (sites) {
-        PRIOR_TRY(hipEventRecord(a->ev[slot], stream));
+        BN_HIP_TRY(hipEventRecord(a->ev[slot], stream));
         a->ev_used[slot] = true;
     }
-    // the packed rows into the pinned mirror by the store kernel, as the step's own (capi.cpp, results_to_host); a copy otherwise
-    const size_t r_bytes = batch * (2 * k + 1) * sizeof(uint32_t);
-    void *pr = nullptr;
-    static const bool sdma = sw_int(sw::BN_SDMA_COPY) != 0;
-    if (!sdma && hipHostGetDevicePointer(&pr, a->h_rows, 0) == hipSuccess && pr) {
-        bn::CopyOut co{};
-        co.dst[0] = pr;
-        co.src[0] = a->d_rows;
-        co.words[0] = (uint32_t)(r_bytes / 4);
-        co.n = 1;
-        bn::launch_copy_out(stream, co);
-        if ((st = check_launch("prior results")) != BN_OK) return st;
-    } else {
-        (void)hipGetLastError();
-        PRIOR_TRY(hipMemcpyAsync(a->h_rows, a->d_rows, r_bytes, hipMemcpyDeviceToHost, stream));
-    }
-    a->last_batch = batch;
-    a->k = k;
-    a->stepped = true;
+    const bn::OutRegion reg{a->rows.h, a->rows.d, TopkRows::bytes(batch, k)};
+    if ((st = bn::results_to_host(stream, &reg, 1)) != BN_OK) return st;
+    a->rows.mark(batch, k);
     return BN_OK;
 }
 
 bn_status bn::prior_step_results(const PriorAttach *a, const uint32_t **idx, const float **conf, const uint32_t **count, size_t *k_stride) {
-    if (!a || !a->stepped) return set_last_error(BN_ERR_INVALID_ARG, "no step has run on this context since a prior was attached");
-    const size_t b = a->last_batch, k = a->k;
-    if (idx) *idx = a->h_rows;
-    if (conf) *conf = reinterpret_cast<const float *>(a->h_rows + b * k);
-    if (count) *count = a->h_rows + 2 * b * k;
-    if (k_stride) *k_stride = k;
-    return BN_OK;
+    static const char *none = "no step has run on this context since a prior was attached";
+    if (!a) return set_last_error(BN_ERR_INVALID_ARG, none);
+    return a->rows.results(none, idx, conf, count, k_stride);
 }
 
 extern "C" {
@@ -661,10 +593,8 @@ bn_status bn_prior_create(int32_t device, size_t n_sites, size_t n_species, cons
     for (size_t i = 0; i < n_sites * n_species; i++)
         if (!std::isfinite(table[i]))
             return set_last_error(BN_ERR_INVALID_ARG, "table entry [" + std::to_string(i / n_species) + "][" + std::to_string(i % n_species) + "] is not finite");
-    if (bn_device_count() <= 0) return set_last_error(BN_ERR_NO_DEVICE, "no gfx950 device visible");
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) return set_last_error(BN_ERR_NO_DEVICE, "no such device");
-    PRIOR_TRY(bn::use_device(device));
+    if (bn_status dst = bn::require_device(device); dst != BN_OK) return dst;
+    BN_HIP_TRY(bn::use_device(device));
     if (!bn::prepare_device(device)) return set_last_error(BN_ERR_BACKEND, "device refused the kernels' dynamic-LDS opt-in");
     std::unique_ptr<bn_prior, void (*)(bn_prior *)> p(new bn_prior, prior_unref);
     p->device = device;
@@ -673,13 +603,13 @@ bn_status bn_prior_create(int32_t device, size_t n_sites, size_t n_species, cons
     p->tstride = (n_species + 3) / 4 * 4;
     p->threshold = threshold;
     p->flags = flags;
-    PRIOR_TRY(bn::gated::Malloc(&p->d_table, n_sites * p->tstride * sizeof(float)));
+    BN_HIP_TRY(bn::gated::Malloc(&p->d_table, n_sites * p->tstride * sizeof(float)));
     if (p->tstride == n_species) {
-        PRIOR_TRY(bn::gated::Memcpy(p->d_table, table, n_sites * n_species * sizeof(float), hipMemcpyHostToDevice));
+        BN_HIP_TRY(bn::gated::Memcpy(p->d_table, table, n_sites * n_species * sizeof(float), hipMemcpyHostToDevice));
     } else {
         std::vector<float> pad(n_sites * p->tstride, BN_PRIOR_UNKNOWN);
         for (size_t s = 0; s < n_sites; s++) memcpy(pad.data() + s * p->tstride, table + s * n_species, n_species * sizeof(float));
-        PRIOR_TRY(bn::gated::Memcpy(p->d_table, pad.data(), pad.size() * sizeof(float), hipMemcpyHostToDevice));
+        BN_HIP_TRY(bn::gated::Memcpy(p->d_table, pad.data(), pad.size() * sizeof(float), hipMemcpyHostToDevice));
     }
     *out = p.release();
     return BN_OK;
@@ -699,26 +629,26 @@ bn_status bn_prior_read(const bn_prior *pc, size_t first_site, size_t count, flo
     if (!out) return set_last_error(BN_ERR_INVALID_ARG, "null output");
     bn_prior *p = const_cast<bn_prior *>(pc);
     std::lock_guard<std::mutex> lk(p->mu);
-    PRIOR_TRY(bn::use_device(p->device));
+    BN_HIP_TRY(bn::use_device(p->device));
     bn::gated::Shared gate;
-    PRIOR_TRY(hipMemcpy2D(out, p->n_species * sizeof(float), p->d_table + first_site * p->tstride, p->tstride * sizeof(float),
+    BN_HIP_TRY(hipMemcpy2D(out, p->n_species * sizeof(float), p->d_table + first_site * p->tstride, p->tstride * sizeof(float),
                           p->n_species * sizeof(float), count, hipMemcpyDeviceToHost));
     return BN_OK;
 }
 
 bn_status bn_prior_apply_host(const bn_prior *pc, const float *logits, size_t rows, const int32_t *sites, size_t top_k, int32_t has_min, float min_conf,
                               size_t k_stride, uint32_t *idx_out, float *conf_out, uint32_t *count_out) {
-    if (bn_device_count() <= 0) return set_last_error(BN_ERR_NO_DEVICE, "no gfx950 device visible");
+    if (bn_status dst = bn::require_any_device(); dst != BN_OK) return dst;
     if (!pc) return set_last_error(BN_ERR_INVALID_ARG, "null prior");
     if (rows == 0) return BN_OK;
     if (!logits || !sites || !idx_out || !conf_out || !count_out) return set_last_error(BN_ERR_INVALID_ARG, "null argument");
     bn_prior *p = const_cast<bn_prior *>(pc);  // the stream is not part of the prior's value
     const bool after = (p->flags & BN_PRIOR_AFTER_TOPK) != 0;
     const size_t n = p->n_species;
-    size_t k;
+    size_t k = 0;
     if (after) {
-        k = std::min(top_k, n);
-        if (k == 0 || bn::topk_lds_bytes((int64_t)n, (int64_t)k) == 0) return set_last_error(BN_ERR_INVALID_ARG, "top_k must be in 1..9000");
+        bn_status kst = bn::check_top_k(n, top_k, &k);
+        if (kst != BN_OK) return kst;
     } else if ((k = select_k(p, top_k)) == 0) {
         return BN_ERR_INVALID_ARG;
     }
@@ -728,48 +658,45 @@ bn_status bn_prior_apply_host(const bn_prior *pc, const float *logits, size_t ro
         if (st != BN_OK) return st;
     }
     std::lock_guard<std::mutex> lk(p->mu);
-    PRIOR_TRY(bn::use_device(p->device));
-    if (!p->stream) PRIOR_TRY(bn::gated::StreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
-    CallBufs bufs;
-    bufs.stream = p->stream;
+    BN_HIP_TRY(bn::use_device(p->device));
+    if (!p->stream) BN_HIP_TRY(bn::gated::StreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
+    bn::Scratch bufs;
+    bufs.stream = p->stream;  // the prior's own: waited for, not destroyed
     constexpr size_t CHUNK = 1024;  // rows per round
     const size_t cr = std::min(CHUNK, rows);
     float *d_logits = nullptr, *d_conf = nullptr;
     int32_t *d_sites = nullptr;
     uint32_t *d_idx = nullptr, *d_cnt = nullptr, *d_gkeys = nullptr, *d_tk = nullptr, *d_flags = nullptr;
-    PRIOR_TRY(bufs.alloc(&d_logits, cr * n * sizeof(float)));
-    PRIOR_TRY(bufs.alloc(&d_sites, cr * sizeof(int32_t)));
-    PRIOR_TRY(bufs.alloc(&d_idx, cr * k * sizeof(uint32_t)));
-    PRIOR_TRY(bufs.alloc(&d_conf, cr * k * sizeof(float)));
-    PRIOR_TRY(bufs.alloc(&d_cnt, cr * sizeof(uint32_t)));
+    BN_HIP_TRY(bufs.alloc(&d_logits, cr * n * sizeof(float)));
+    BN_HIP_TRY(bufs.alloc(&d_sites, cr * sizeof(int32_t)));
+    BN_HIP_TRY(bufs.alloc(&d_idx, cr * k * sizeof(uint32_t)));
+    BN_HIP_TRY(bufs.alloc(&d_conf, cr * k * sizeof(float)));
+    BN_HIP_TRY(bufs.alloc(&d_cnt, cr * sizeof(uint32_t)));
     if (after) {
-        PRIOR_TRY(bufs.alloc(&d_tk, cr * (2 * k + 1) * sizeof(uint32_t)));
-        PRIOR_TRY(bufs.alloc(&d_flags, cr * sizeof(uint32_t)));
+        BN_HIP_TRY(bufs.alloc(&d_tk, bn::TopkRows::bytes(cr, k)));  // the rows of a chunk's own top-K
+        BN_HIP_TRY(bufs.alloc(&d_flags, cr * sizeof(uint32_t)));
     } else if (general_form(p)) {
-        PRIOR_TRY(bufs.alloc(&d_gkeys, cr * n * sizeof(uint32_t)));
+        BN_HIP_TRY(bufs.alloc(&d_gkeys, cr * n * sizeof(uint32_t)));
     }
     std::vector<uint32_t> h_idx(cr * k), h_cnt(cr);
     std::vector<float> h_conf(cr * k);
     for (size_t r0 = 0; r0 < rows; r0 += CHUNK) {
         const size_t m = std::min(CHUNK, rows - r0);
-        PRIOR_TRY(bn::gated::Memcpy(d_logits, logits + r0 * n, m * n * sizeof(float), hipMemcpyHostToDevice));
-        PRIOR_TRY(bn::gated::Memcpy(d_sites, sites + r0, m * sizeof(int32_t), hipMemcpyHostToDevice));
+        BN_HIP_TRY(bn::gated::Memcpy(d_logits, logits + r0 * n, m * n * sizeof(float), hipMemcpyHostToDevice));
+        BN_HIP_TRY(bn::gated::Memcpy(d_sites, sites + r0, m * sizeof(int32_t), hipMemcpyHostToDevice));
         bn_status st;
         if (after) {
-            uint32_t *t_idx = d_tk, *t_cnt = d_tk + 2 * m * k;
-            float *t_conf = reinterpret_cast<float *>(d_tk + m * k);
-            (void)hipGetLastError();
-            bn::launch_topk(p->stream, d_logits, (int64_t)m, (int64_t)n, (int64_t)k, has_min, min_conf, (int64_t)k, t_idx, t_conf, t_cnt, d_flags);
-            if ((st = check_launch("top-K")) != BN_OK) return st;
-            st = enqueue_after(p, p->stream, t_idx, t_conf, t_cnt, m, d_sites, 0, k, k, d_idx, d_conf, d_cnt);
+            const bn::TopkRows::View t = bn::TopkRows::view(d_tk, m, k);
+            if ((st = bn::enqueue_topk_rows(p->stream, d_logits, m, n, k, has_min, min_conf, t, d_flags)) != BN_OK) return st;
+            st = enqueue_after(p, p->stream, t.idx, t.conf, t.count, m, d_sites, 0, k, k, d_idx, d_conf, d_cnt);
         } else {
             st = enqueue_select(p, p->stream, d_logits, m, d_sites, 0, k, has_min, min_conf, k, d_gkeys, d_idx, d_conf, d_cnt);
         }
         if (st != BN_OK) return st;
-        PRIOR_TRY(hipStreamSynchronize(p->stream));
-        PRIOR_TRY(bn::gated::Memcpy(h_idx.data(), d_idx, m * k * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        PRIOR_TRY(bn::gated::Memcpy(h_conf.data(), d_conf, m * k * sizeof(float), hipMemcpyDeviceToHost));
-        PRIOR_TRY(bn::gated::Memcpy(h_cnt.data(), d_cnt, m * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        BN_HIP_TRY(hipStreamSynchronize(p->stream));
+        BN_HIP_TRY(bn::gated::Memcpy(h_idx.data(), d_idx, m * k * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        BN_HIP_TRY(bn::gated::Memcpy(h_conf.data(), d_conf, m * k * sizeof(float), hipMemcpyDeviceToHost));
+        BN_HIP_TRY(bn::gated::Memcpy(h_cnt.data(), d_cnt, m * sizeof(uint32_t), hipMemcpyDeviceToHost));
         for (size_t r = 0; r < m; r++) {
             memcpy(idx_out + (r0 + r) * k_stride, h_idx.data() + r * k, k * sizeof(uint32_t));
             memcpy(conf_out + (r0 + r) * k_stride, h_conf.data() + r * k, k * sizeof(float));
