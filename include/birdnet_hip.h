@@ -409,9 +409,10 @@ size_t bn_group_last_error(char *buf, size_t cap);
  * Row ids are the append order: appending the windows of bn_infer_windows in order makes the id the window index, so
  * start = id * step / sample_rate as chunk_audio reports it (src/bin/birdnet-analyze.rs:707-743).
  *
- *   Normalisation  stored row = x / sqrt(sum x^2).  A row with zero norm or any non-finite element (or whose sum of
- *                  squares overflows f32) is stored as zeros, counts toward bn_index_size and is never returned.  A query
- *                  with zero norm or a non-finite element returns count = 0.
+ *   Normalisation  stored row = x / sqrt(sum x^2).  A row with zero norm or any non-finite element (or whose f32 sum of
+ *                  squares overflows, or whose f32 sum of squares underflows to zero) is stored as zeros, counts toward
+ *                  bn_index_size and is never returned.  A query with zero norm or a non-finite element returns
+ *                  count = 0.  The "up to f32 rounding" above holds while that sum is a normal f32.
  *   Score          the f32 dot product of the normalised query and the normalised row.  For one (query, row) pair its
  *                  summation order depends only on dim: not on where the row lands in a tile, the number of queries of
  *                  the call, the index size or how the index was appended.
