@@ -11,7 +11,14 @@
 namespace bn {
 namespace {
 
+typedef float floatx4 __attribute__((ext_vector_type(4)));
 typedef float floatx16 __attribute__((ext_vector_type(16)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+// operands of __builtin_amdgcn_global_load_lds: the global source and the LDS destination in their address spaces
+#define BN_GLB_PTR(p) ((const __attribute__((address_space(1))) void *)(p))
+#define BN_LDS_PTR(p) ((__attribute__((address_space(3))) void *)(p))
 
 // Logistic function inside the network (SE gates, SiLU): hardware exp2 and reciprocal
 // (v_exp_f32 / v_rcp_f32, ~1 ulp each; the argument scaling adds |x| * 2^-24 relative), 6
@@ -39,88 +46,99 @@ __device__ __forceinline__ void map_array(float (&v)[N], F f) {
     for (int i = 0; i < N; i++) v[i] = f(v[i]);
 }
 
-__device__ __forceinline__ float act_apply(int act, float x, float p0, float p1) {
-    switch (act) {
-        case ACT_NONE: return x;
-        case ACT_RELU: return fmaxf(x, 0.0f);
-        case ACT_CLIP: return fminf(fmaxf(x, p0), p1);
-        case ACT_SIGMOID: return net_sigmoid(x);
-        case ACT_SILU: return x * net_sigmoid(x);
-        case ACT_HSIGMOID: return fminf(fmaxf(p0 * x + p1, 0.0f), 1.0f);
-        case ACT_HSWISH: return x * fminf(fmaxf(x * (1.0f / 6.0f) + 0.5f, 0.0f), 1.0f);
-        case ACT_LEAKY: return x >= 0.0f ? x : p0 * x;
-        case ACT_TANH: return tanhf(x);
-        case ACT_EXP: return net_exp(x);
-        case ACT_LOG: return net_log(x);
-        case ACT_SQRT: return sqrtf(x);
-        case ACT_ABS: return fabsf(x);
-        case ACT_NEG: return -x;
-        case ACT_RECIP: return 1.0f / x;
-        case ACT_POW: return net_pow(x, p0);
-        case ACT_AFFINE: return p0 * x + p1;
-        case ACT_MAXC: return fmaxf(x, p0);
-        case ACT_MINC: return fminf(x, p0);
-        case ACT_RSUB: return p0 - x;
-        case ACT_RDIV: return p0 / x;
-        case ACT_SQUARE: return x * x;
-        case ACT_FLOOR: return floorf(x);
-        case ACT_CEIL: return ceilf(x);
-        case ACT_ERF: return erff(x);
-        case ACT_SOFTPLUS: return log1pf(expf(x));
-        case ACT_GTC: return x > p0 ? 1.0f : 0.0f;
-        case ACT_LTC: return x < p0 ? 1.0f : 0.0f;
-        case ACT_GEC: return x >= p0 ? 1.0f : 0.0f;
-        case ACT_LEC: return x <= p0 ? 1.0f : 0.0f;
-        case ACT_EQC: return x == p0 ? 1.0f : 0.0f;
-        case ACT_NEZ: return x != 0.0f ? 1.0f : 0.0f;
-        case ACT_TRUNC: return truncf(x);
-        case ACT_ROUND: return rintf(x);
-        default: return x;
+// x^p without libm: exp2(p log2 |x|) (hardware exp2 / log2, ~1e-6 relative), the sign and the special cases by hand
+__device__ __forceinline__ float pow_compact(float x, float p) {
+    const float ax = fabsf(x);
+    float r = __builtin_amdgcn_exp2f(p * __builtin_amdgcn_logf(ax));
+    if (x < 0.0f) {
+        const float fl = floorf(p);
+        if (fl != p) r = __builtin_nanf("");                 // negative base, non-integer exponent
+        else if (fl * 0.5f != floorf(fl * 0.5f)) r = -r;     // odd integer exponent keeps the sign
     }
+    if (p == 0.0f) r = 1.0f;
+    return r;
 }
 
-// Stage ops over a small register array with ONE dispatch on the (launch-uniform) op code: the
-// per-element switch of act_apply / bin_apply costs a branch tree per element per stage.
-template <int N>
-__device__ __forceinline__ void act_array_all(int act, float p0, float p1, float (&v)[N]) {
+// THE definition of every unary stage code (Act, kernels.h): X(code, its value at x with the parameters p0, p1).  POW has two forms:
+// the compact family (COMPACT: no libm anywhere in its code) computes it with pow_compact, every other one with net_pow.
+#define BN_ACT_TABLE(X)                                                               \
+    X(ACT_RELU, fmaxf(x, 0.0f))                                                       \
+    X(ACT_CLIP, fminf(fmaxf(x, p0), p1))                                              \
+    X(ACT_SIGMOID, net_sigmoid(x))                                                    \
+    X(ACT_SILU, x * net_sigmoid(x))                                                   \
+    X(ACT_HSIGMOID, fminf(fmaxf(p0 * x + p1, 0.0f), 1.0f))                            \
+    X(ACT_HSWISH, x * fminf(fmaxf(x * (1.0f / 6.0f) + 0.5f, 0.0f), 1.0f))             \
+    X(ACT_LEAKY, x >= 0.0f ? x : p0 * x)                                              \
+    X(ACT_TANH, tanhf(x))                                                             \
+    X(ACT_EXP, net_exp(x))                                                            \
+    X(ACT_LOG, net_log(x))                                                            \
+    X(ACT_SQRT, sqrtf(x))                                                             \
+    X(ACT_ABS, fabsf(x))                                                              \
+    X(ACT_NEG, -x)                                                                    \
+    X(ACT_RECIP, 1.0f / x)                                                            \
+    X(ACT_POW, COMPACT ? pow_compact(x, p0) : net_pow(x, p0))                         \
+    X(ACT_AFFINE, p0 * x + p1)                                                        \
+    X(ACT_MAXC, fmaxf(x, p0))                                                         \
+    X(ACT_MINC, fminf(x, p0))                                                         \
+    X(ACT_RSUB, p0 - x)                                                               \
+    X(ACT_RDIV, p0 / x)                                                               \
+    X(ACT_SQUARE, x * x)                                                              \
+    X(ACT_FLOOR, floorf(x))                                                           \
+    X(ACT_CEIL, ceilf(x))                                                             \
+    X(ACT_ERF, erff(x))                                                               \
+    X(ACT_SOFTPLUS, log1pf(expf(x)))                                                  \
+    X(ACT_GTC, x > p0 ? 1.0f : 0.0f)                                                  \
+    X(ACT_LTC, x < p0 ? 1.0f : 0.0f)                                                  \
+    X(ACT_GEC, x >= p0 ? 1.0f : 0.0f)                                                 \
+    X(ACT_LEC, x <= p0 ? 1.0f : 0.0f)                                                 \
+    X(ACT_EQC, x == p0 ? 1.0f : 0.0f)                                                 \
+    X(ACT_NEZ, x != 0.0f ? 1.0f : 0.0f)                                               \
+    X(ACT_TRUNC, truncf(x))                                                           \
+    X(ACT_ROUND, rintf(x))
+
+// one code's formula, the code known at compile time
+template <int ACT, bool COMPACT = false>
+__device__ __forceinline__ float act_fn(float x, float p0, float p1) {
+#define BN_ACT_FN(code, value) if constexpr (ACT == code) return value; else
+    BN_ACT_TABLE(BN_ACT_FN) return x;
+#undef BN_ACT_FN
+}
+
+// THE dispatcher: ONE branch on the (launch-uniform) code, then `apply` receives the selected formula as a float -> float function
+// and runs it over whatever the caller holds (a register array, an accumulator tile, one value) -- a dispatch per element
+// would cost a branch tree per element per stage.  SET (an ACT_SET_* of kernels.h) is the family's set: a code outside it
+// generates no code here and is the identity, which the planner's predicates on the same constant keep from being asked for.
+template <uint64_t SET, bool COMPACT = false, class Apply>
+__device__ __forceinline__ void act_dispatch(int act, float p0, float p1, Apply apply) {
     switch (act) {
-        case ACT_NONE: return;
-        case ACT_RELU: map_array<N>(v, [](float x) { return fmaxf(x, 0.0f); }); return;
-        case ACT_CLIP: map_array<N>(v, [=](float x) { return fminf(fmaxf(x, p0), p1); }); return;
-        case ACT_SIGMOID: map_array<N>(v, [](float x) { return net_sigmoid(x); }); return;
-        case ACT_SILU: map_array<N>(v, [](float x) { return x * net_sigmoid(x); }); return;
-        case ACT_HSIGMOID: map_array<N>(v, [=](float x) { return fminf(fmaxf(p0 * x + p1, 0.0f), 1.0f); }); return;
-        case ACT_HSWISH: map_array<N>(v, [](float x) { return x * fminf(fmaxf(x * (1.0f / 6.0f) + 0.5f, 0.0f), 1.0f); }); return;
-        case ACT_LEAKY: map_array<N>(v, [=](float x) { return x >= 0.0f ? x : p0 * x; }); return;
-        case ACT_TANH: map_array<N>(v, [](float x) { return tanhf(x); }); return;
-        case ACT_EXP: map_array<N>(v, [](float x) { return net_exp(x); }); return;
-        case ACT_LOG: map_array<N>(v, [](float x) { return net_log(x); }); return;
-        case ACT_SQRT: map_array<N>(v, [](float x) { return sqrtf(x); }); return;
-        case ACT_ABS: map_array<N>(v, [](float x) { return fabsf(x); }); return;
-        case ACT_NEG: map_array<N>(v, [](float x) { return -x; }); return;
-        case ACT_RECIP: map_array<N>(v, [](float x) { return 1.0f / x; }); return;
-        case ACT_POW: map_array<N>(v, [=](float x) { return net_pow(x, p0); }); return;
-        case ACT_AFFINE: map_array<N>(v, [=](float x) { return p0 * x + p1; }); return;
-        case ACT_MAXC: map_array<N>(v, [=](float x) { return fmaxf(x, p0); }); return;
-        case ACT_MINC: map_array<N>(v, [=](float x) { return fminf(x, p0); }); return;
-        case ACT_RSUB: map_array<N>(v, [=](float x) { return p0 - x; }); return;
-        case ACT_RDIV: map_array<N>(v, [=](float x) { return p0 / x; }); return;
-        case ACT_SQUARE: map_array<N>(v, [](float x) { return x * x; }); return;
-        case ACT_FLOOR: map_array<N>(v, [](float x) { return floorf(x); }); return;
-        case ACT_CEIL: map_array<N>(v, [](float x) { return ceilf(x); }); return;
-        case ACT_ERF: map_array<N>(v, [](float x) { return erff(x); }); return;
-        case ACT_SOFTPLUS: map_array<N>(v, [](float x) { return log1pf(expf(x)); }); return;
-        case ACT_GTC: map_array<N>(v, [=](float x) { return x > p0 ? 1.0f : 0.0f; }); return;
-        case ACT_LTC: map_array<N>(v, [=](float x) { return x < p0 ? 1.0f : 0.0f; }); return;
-        case ACT_GEC: map_array<N>(v, [=](float x) { return x >= p0 ? 1.0f : 0.0f; }); return;
-        case ACT_LEC: map_array<N>(v, [=](float x) { return x <= p0 ? 1.0f : 0.0f; }); return;
-        case ACT_EQC: map_array<N>(v, [=](float x) { return x == p0 ? 1.0f : 0.0f; }); return;
-        case ACT_NEZ: map_array<N>(v, [](float x) { return x != 0.0f ? 1.0f : 0.0f; }); return;
-        case ACT_TRUNC: map_array<N>(v, [](float x) { return truncf(x); }); return;
-        case ACT_ROUND: map_array<N>(v, [](float x) { return rintf(x); }); return;
+#define BN_ACT_CASE(code, value)                                                                             \
+    case code:                                                                                               \
+        if constexpr (act_in(SET, code)) apply([=](float x) { return act_fn<code, COMPACT>(x, p0, p1); });   \
+        return;
+        BN_ACT_TABLE(BN_ACT_CASE)
+#undef BN_ACT_CASE
         default: return;
     }
 }
+template <uint64_t SET, bool COMPACT = false, int N>
+__device__ __forceinline__ void act_array(int act, float p0, float p1, float (&v)[N]) {
+    act_dispatch<SET, COMPACT>(act, p0, p1, [&](auto f) { map_array<N>(v, f); });
+}
+template <uint64_t SET, int NT>
+__device__ __forceinline__ void act_tile(int act, float p0, float p1, floatx16 (&acc)[NT]) {
+    act_dispatch<SET>(act, p0, p1, [&](auto f) {
+#pragma unroll
+        for (int t = 0; t < NT; t++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) acc[t][r] = f(acc[t][r]);
+    });
+}
+// one value of a kernel that applies its activation per element (every code)
+__device__ __forceinline__ float act_apply(int act, float x, float p0, float p1) {
+    act_dispatch<ACT_SET_ALL>(act, p0, p1, [&](auto f) { x = f(x); });
+    return x;
+}
+
 template <int N, class F>
 __device__ __forceinline__ void zip_array(float (&v)[N], const float (&w)[N], F f) {
 #pragma unroll
@@ -150,48 +168,14 @@ __device__ __forceinline__ void bin_array(int bin, int bsq, float (&v)[N], float
 }
 
 }  // namespace
-// Stage functions of the absorbed chains, COMPACT on purpose: the generic act_array_all / bin_array dispatchers inline
+// Stage functions of the absorbed chains, COMPACT on purpose: the full set and bin_array inline
 // libm (tanhf, erff, powf, ...) for every instantiation -- with nine stage slots that made this kernel 676 KB of code,
 // and walking through it ran at instruction-fetch speed (a 4-stage chain over 16 floats per thread cost 19 us per
-// tile).  Only codes with a few-instruction body are accepted here (kernels.h, stft_stage_supported: the planner
-// absorbs nothing else), dispatched by compare chains on the launch-uniform code.
-__device__ __forceinline__ float pow_compact(float x, float p) {
-    // x^p without libm: exp2(p log2 |x|) (hardware exp2 / log2, ~1e-6 relative), the sign and the special cases by hand
-    const float ax = fabsf(x);
-    float r = __builtin_amdgcn_exp2f(p * __builtin_amdgcn_logf(ax));
-    if (x < 0.0f) {
-        const float fl = floorf(p);
-        if (fl != p) r = __builtin_nanf("");                 // negative base, non-integer exponent
-        else if (fl * 0.5f != floorf(fl * 0.5f)) r = -r;     // odd integer exponent keeps the sign
-    }
-    if (p == 0.0f) r = 1.0f;
-    return r;
-}
-// ONE dispatch per stage for a whole register array (the code is launch-uniform): a compare chain per element would
-// be re-evaluated, operands reloaded, for every value.
+// tile).  Only codes with a few-instruction body are accepted here (kernels.h, ACT_SET_COMPACT: the planner
+// absorbs nothing else).
 template <int N>
 __device__ __forceinline__ void act_small(int act, float p0, float p1, float (&v)[N]) {
-    if (act == ACT_NONE) return;
-    if (act == ACT_AFFINE) map_array<N>(v, [=](float x) { return p0 * x + p1; });
-    else if (act == ACT_SQUARE) map_array<N>(v, [](float x) { return x * x; });
-    else if (act == ACT_POW) map_array<N>(v, [=](float x) { return pow_compact(x, p0); });
-    else if (act == ACT_LOG) map_array<N>(v, [](float x) { return net_log(x); });
-    else if (act == ACT_EXP) map_array<N>(v, [](float x) { return net_exp(x); });
-    else if (act == ACT_SQRT) map_array<N>(v, [](float x) { return sqrtf(x); });
-    else if (act == ACT_ABS) map_array<N>(v, [](float x) { return fabsf(x); });
-    else if (act == ACT_MAXC) map_array<N>(v, [=](float x) { return fmaxf(x, p0); });
-    else if (act == ACT_MINC) map_array<N>(v, [=](float x) { return fminf(x, p0); });
-    else if (act == ACT_RELU) map_array<N>(v, [](float x) { return fmaxf(x, 0.0f); });
-    else if (act == ACT_CLIP) map_array<N>(v, [=](float x) { return fminf(fmaxf(x, p0), p1); });
-    else if (act == ACT_NEG) map_array<N>(v, [](float x) { return -x; });
-    else if (act == ACT_RECIP) map_array<N>(v, [](float x) { return 1.0f / x; });
-    else if (act == ACT_RSUB) map_array<N>(v, [=](float x) { return p0 - x; });
-    else if (act == ACT_RDIV) map_array<N>(v, [=](float x) { return p0 / x; });
-    else if (act == ACT_SIGMOID) map_array<N>(v, [](float x) { return net_sigmoid(x); });
-    else if (act == ACT_SILU) map_array<N>(v, [](float x) { return x * net_sigmoid(x); });
-    else if (act == ACT_LEAKY) map_array<N>(v, [=](float x) { return x >= 0.0f ? x : p0 * x; });
-    else if (act == ACT_FLOOR) map_array<N>(v, [](float x) { return floorf(x); });
-    else if (act == ACT_CEIL) map_array<N>(v, [](float x) { return ceilf(x); });
+    act_array<ACT_SET_COMPACT, true>(act, p0, p1, v);
 }
 
 // binary stage against ONE scalar for the whole array (the absorbed per-sample chains: stft.hip, the framing GEMMs of kernels.hip)

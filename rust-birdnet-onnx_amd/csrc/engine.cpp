@@ -2713,18 +2713,11 @@ class Builder {
             const OnnxNode &c = nodes_[cons[0]];
             if (c.inputs.empty() || c.inputs[0] != cur) return false;
             ActSpec s;
-            if (c.op_type == "Sigmoid" || c.op_type == "Relu" || c.op_type == "Clip" || c.op_type == "HardSwish" ||
-                c.op_type == "HardSigmoid" || c.op_type == "LeakyRelu" || c.op_type == "Tanh") {
-                if (c.op_type == "Sigmoid") {
-                    // keep a bare Sigmoid fusable too
-                }
-                if (!unary_spec(c, s)) return false;
-                a = s;
-                absorbed_[cons[0]] = true;
-                cur = c.outputs[0];
-                return true;
-            }
-            return false;
+            if (!unary_spec(c, s) || !act_in(ACT_SET_CONV, s.act)) return false;  // (a bare Sigmoid is fusable too)
+            a = s;
+            absorbed_[cons[0]] = true;
+            cur = c.outputs[0];
+            return true;
         }
         if (cons.size() == 2) {  // x * sigmoid(x)
             int si = -1, mi = -1;
@@ -3418,9 +3411,7 @@ class Builder {
                 sw_on(sw::BN_STEMFUSE)) {
                 PlanOp &pe = plan_.ops.back();
                 const ConvDesc &cd = pe.conv;
-                const int a1 = cd.act;
-                const bool act_zero = a1 == ACT_NONE || a1 == ACT_RELU || (a1 == ACT_CLIP && cd.p0 <= 0.f && cd.p1 >= 0.f) || a1 == ACT_SILU ||
-                                      a1 == ACT_HSWISH || a1 == ACT_LEAKY || a1 == ACT_TANH;
+                const bool act_zero = act_keeps_zero(cd.act, cd.p0, cd.p1);
                 const bool stem = pe.kind == OpKind::CONV && pe.out.space == Space::ARENA && pe.out.id == x.storage && pe.out.offset == 0 && x.offset == 0 &&
                                   cd.groups == 1 && cd.kh == cd.kw && cd.sh == cd.sw && cd.dh == 1 && cd.dw == 1 && !cd.has_res && cd.Cin <= 4 &&
                                   cd.kh * cd.kw * cd.Cin <= 48 && cd.OH == H && cd.OW == W && cd.Cout == Cin && act_zero &&
@@ -3472,9 +3463,7 @@ class Builder {
                 PlanOp &pe = plan_.ops.back();
                 const int maxk = std::min(48, sw_int(sw::BN_MBFUSE_MAXK));  // kernel: <= 6 K groups in registers
                 // the kernel relies on act(0) == 0 for the expand activation (pixels outside the image)
-                const int a1 = pe.gemm.act;
-                const bool act_zero = a1 == ACT_NONE || a1 == ACT_RELU || (a1 == ACT_CLIP && pe.gemm.p0 <= 0.f && pe.gemm.p1 >= 0.f) ||
-                                      a1 == ACT_SILU || a1 == ACT_HSWISH || a1 == ACT_LEAKY || a1 == ACT_TANH;
+                const bool act_zero = act_keeps_zero(pe.gemm.act, pe.gemm.p0, pe.gemm.p1);
                 const double maxhalo = sw_double(sw::BN_MBFUSE_HALO);
                 // small feature maps can take the whole-map kernel (one block = 32 mid channels x the whole map:
                 // no halo, any K up to 256, complete squeeze sums).  Opt-in (BN_MBMAP=1): measured on MI355X at

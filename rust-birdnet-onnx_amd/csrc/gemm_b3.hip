@@ -41,19 +41,6 @@
 namespace bn {
 namespace {
 
-typedef b3_floatx4 floatx4;
-typedef b3_u32x4 u32x4;
-
-template <int N>
-__device__ __forceinline__ void gb_act(int act, float p0, float p1, float (&v)[N]) {
-    if (act == ACT_RELU) map_array<N>(v, [](float x) { return fmaxf(x, 0.0f); });
-    else if (act == ACT_CLIP) map_array<N>(v, [=](float x) { return fminf(fmaxf(x, p0), p1); });
-    else if (act == ACT_SILU) map_array<N>(v, [](float x) { return x * net_sigmoid(x); });
-    else if (act == ACT_HSWISH) map_array<N>(v, [](float x) { return x * fminf(fmaxf(x * (1.0f / 6.0f) + 0.5f, 0.0f), 1.0f); });
-    else if (act == ACT_SIGMOID) map_array<N>(v, [](float x) { return net_sigmoid(x); });
-    else if (act == ACT_HSIGMOID) map_array<N>(v, [=](float x) { return fminf(fmaxf(p0 * x + p1, 0.0f), 1.0f); });
-}
-
 // MT 16-row tiles per block (every wave multiplies all of them), NW waves of NTW 16-channel tiles each.  NTW = 2 (round 5, the large
 // products of v3.0 / Perch): an activation fragment read from LDS feeds twelve matrix instructions instead of six -- with one tile per wave
 // the eight waves of a block read 96 KB of planes per K step for 768 matrix cycles per SIMD: exactly the LDS pipe's 768 cycles.
@@ -203,7 +190,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_b3_kernel(GemmDesc d, float *__r
         for (int mt = 0; mt < MT; mt++)
 #pragma unroll
             for (int i = 0; i < 4; i++) v[mt * 4 + i] = acc[mt][jt][i] + bv[i];
-        gb_act<MT * 4>(d.act, d.p0, d.p1, v);
+        act_array<ACT_SET_GEMM_DMA>(d.act, d.p0, d.p1, v);
         if (d.gap) {  // (launcher: TR == rows, one block per sample) the sample's mean over its rows: m-tiles ascending, then a fixed butterfly over the 16 rows
             floatx4 sm = floatx4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll

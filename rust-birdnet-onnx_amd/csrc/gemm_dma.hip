@@ -36,18 +36,6 @@
 namespace bn {
 namespace {
 
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-
-template <int N>
-__device__ __forceinline__ void gd_act(int act, float p0, float p1, float (&v)[N]) {
-    if (act == ACT_RELU) map_array<N>(v, [](float x) { return fmaxf(x, 0.0f); });
-    else if (act == ACT_CLIP) map_array<N>(v, [=](float x) { return fminf(fmaxf(x, p0), p1); });
-    else if (act == ACT_SILU) map_array<N>(v, [](float x) { return x * net_sigmoid(x); });
-    else if (act == ACT_HSWISH) map_array<N>(v, [](float x) { return x * fminf(fmaxf(x * (1.0f / 6.0f) + 0.5f, 0.0f), 1.0f); });
-    else if (act == ACT_SIGMOID) map_array<N>(v, [](float x) { return net_sigmoid(x); });
-    else if (act == ACT_HSIGMOID) map_array<N>(v, [=](float x) { return fminf(fmaxf(p0 * x + p1, 0.0f), 1.0f); });
-}
-
 #ifdef BN_GD_STAMPS  // tools/gemm_stamps.cpp: shader-clock stamps of block (0, 0)'s waves around every K step (diagnostic build only)
 __device__ unsigned long long bn_gd_stamps[8][96][3];  // [wave][iteration][before the wait | behind the barrier + refill | behind the matrix instructions]
 #define GD_STAMP(IT, WHICH)                                                                                                \
@@ -57,9 +45,6 @@ __device__ unsigned long long bn_gd_stamps[8][96][3];  // [wave][iteration][befo
 #else
 #define GD_STAMP(IT, WHICH)
 #endif
-
-#define GD_LDS_PTR(p) ((__attribute__((address_space(3))) void *)(p))
-#define GD_GLB_PTR(p) ((const __attribute__((address_space(1))) void *)(p))
 
 // MTW x NTW 16x16 tiles per wave, WM x WN waves per K slice (2 or 4), KS K slices (slice ks takes the 32-deep K
 // steps ks, ks + KS, ... through a ring of D stages of its own; the slices' partial tiles are summed through LDS in
@@ -133,7 +118,7 @@ __global__ __launch_bounds__(64 * WM * WN * KS) void gemm_dma_kernel(GemmDesc d,
         const float *xk = Xb + k0, *wk = W + k0;  // uniform bases; the lane offsets are 32-bit
 #pragma unroll
         for (int j = 0; j < NP; j++)
-            __builtin_amdgcn_global_load_lds(GD_GLB_PTR((is_w[j] ? wk : xk) + off[j]), GD_LDS_PTR(sb + dst[j]), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds(BN_GLB_PTR((is_w[j] ? wk : xk) + off[j]), BN_LDS_PTR(sb + dst[j]), 16, 0, 0);
     };
 
     // ---- prologue: the sample's gate (older than every stage piece, so the first counted wait covers it), D - 1 steps
@@ -143,7 +128,7 @@ __global__ __launch_bounds__(64 * WM * WN * KS) void gemm_dma_kernel(GemmDesc d,
         for (int c0 = wave * 64; c0 < gate_floats / 4; c0 += 64 * WPS * KS) {
             int c = c0 + lane;
             c = c < n16 ? c : n16 - 1;
-            __builtin_amdgcn_global_load_lds(GD_GLB_PTR(gsrc + 4 * c), GD_LDS_PTR(gate + 4 * c0), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds(BN_GLB_PTR(gsrc + 4 * c), BN_LDS_PTR(gate + 4 * c0), 16, 0, 0);
         }
     }
 #pragma unroll
@@ -174,7 +159,7 @@ __global__ __launch_bounds__(64 * WM * WN * KS) void gemm_dma_kernel(GemmDesc d,
             for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
             if (lane == 0) {
                 float hv[1] = {a + (sei.b1 ? sei.b1[j] : 0.0f)};
-                gd_act<1>(se.act1, se.p0_1, se.p1_1, hv);
+                act_array<ACT_SET_GEMM_DMA>(se.act1, se.p0_1, se.p1_1, hv);
                 hbuf[j] = hv[0];
             }
         }
@@ -185,7 +170,7 @@ __global__ __launch_bounds__(64 * WM * WN * KS) void gemm_dma_kernel(GemmDesc d,
             float a = 0.0f;
             for (int j = 0; j < se.Cr; j++) a = fmaf(sei.w2t[(int64_t)j * se.C + c], hbuf[j], a);
             float gv[1] = {a + (sei.b2 ? sei.b2[c] : 0.0f)};
-            gd_act<1>(se.act2, se.p0_2, se.p1_2, gv);
+            act_array<ACT_SET_GEMM_DMA>(se.act2, se.p0_2, se.p1_2, gv);
             gate[c] = gv[0];
         }
         // (visible to every wave behind the barrier of the first turn() below, which also waits lgkmcnt(0))
@@ -337,7 +322,7 @@ __global__ __launch_bounds__(64 * WM * WN * KS) void gemm_dma_kernel(GemmDesc d,
 #pragma unroll
             for (int i = 0; i < 4; i++) v[(mt * NTW + nt) * 4 + i] = acc[mt][nt][i] + bv[i];
     }
-    gd_act<MTW * NTW * 4>(d.act, d.p0, d.p1, v);
+    act_array<ACT_SET_GEMM_DMA>(d.act, d.p0, d.p1, v);
     if constexpr (WM == 1) {
         if (d.gap) {  // the sample's mean over its rows (all TR of them sit in this wave): m-tiles ascending, then the 16 rows of a tile by a
                       // fixed butterfly over the lanes lc -- one dwordx4 per n-tile and lane group instead of TR rows
@@ -445,7 +430,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_dma_stream_kernel(GemmDesc 
         const float *xk = is_x + k0, *wk = W + k0;
 #pragma unroll
         for (int j = 0; j < NP; j++)
-            __builtin_amdgcn_global_load_lds(GD_GLB_PTR((is_w[j] ? wk : xk) + off[j]), GD_LDS_PTR(sb + dst[j]), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds(BN_GLB_PTR((is_w[j] ? wk : xk) + off[j]), BN_LDS_PTR(sb + dst[j]), 16, 0, 0);
         is_slot = is_slot + 1 == D ? 0 : is_slot + 1;
         if (++is_s == nst) {
             is_s = 0;
@@ -550,7 +535,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_dma_stream_kernel(GemmDesc 
 #pragma unroll
                 for (int i = 0; i < 4; i++) v[(mt * NTW + nt) * 4 + i] = acc[mt][nt][i] + bv[i];
         }
-        gd_act<MTW * NTW * 4>(d.act, d.p0, d.p1, v);
+        act_array<ACT_SET_GEMM_DMA>(d.act, d.p0, d.p1, v);
 #pragma unroll
         for (int mt = 0; mt < MTW; mt++) {
             const int64_t m = (int64_t)rt * TR + (wm * MTW + mt) * 16 + lc;

@@ -33,50 +33,13 @@
 #include <cstdint>
 #include <cstdlib>
 
+#include "bf16x3.h"
 #include "device_common.h"
 #include "kernels.h"
 #include "plan_rules.h"
 
 namespace bn {
 namespace {
-
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-template <int N>
-__device__ __forceinline__ void g3_act(int act, float p0, float p1, float (&v)[N]) {
-    if (act == ACT_RELU) map_array<N>(v, [](float x) { return fmaxf(x, 0.0f); });
-    else if (act == ACT_CLIP) map_array<N>(v, [=](float x) { return fminf(fmaxf(x, p0), p1); });
-    else if (act == ACT_SILU) map_array<N>(v, [](float x) { return x * net_sigmoid(x); });
-    else if (act == ACT_HSWISH) map_array<N>(v, [](float x) { return x * fminf(fmaxf(x * (1.0f / 6.0f) + 0.5f, 0.0f), 1.0f); });
-    else if (act == ACT_SIGMOID) map_array<N>(v, [](float x) { return net_sigmoid(x); });
-    else if (act == ACT_HSIGMOID) map_array<N>(v, [=](float x) { return fminf(fmaxf(p0 * x + p1, 0.0f), 1.0f); });
-}
-
-#define G3_LDS_PTR(p) ((__attribute__((address_space(3))) void *)(p))
-#define G3_GLB_PTR(p) ((const __attribute__((address_space(1))) void *)(p))
-
-// the eight f32 values of a lane's k group -> three vectors of eight bf16 (hi, mid, lo), exactly: x = hi + mid + lo
-__device__ __forceinline__ void split3(const floatx4 &a, const floatx4 &b, u32x4 &hi, u32x4 &mid, u32x4 &lo) {
-    float x[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-    float r1[8], r2[8];
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-        r1[j] = x[j] - __uint_as_float(__float_as_uint(x[j]) & 0xffff0000u);    // exact: the low 16 significand bits
-        r2[j] = r1[j] - __uint_as_float(__float_as_uint(r1[j]) & 0xffff0000u);  // exact: at most 8 significant bits are left
-    }
-#pragma unroll
-    for (int p = 0; p < 4; p++) {  // bf16 element 2p in the low half, 2p + 1 in the high half: the top 16 bits of each f32
-        hi[p] = __builtin_amdgcn_perm(__float_as_uint(x[2 * p + 1]), __float_as_uint(x[2 * p]), 0x07060302u);
-        mid[p] = __builtin_amdgcn_perm(__float_as_uint(r1[2 * p + 1]), __float_as_uint(r1[2 * p]), 0x07060302u);
-        lo[p] = __builtin_amdgcn_perm(__float_as_uint(r2[2 * p + 1]), __float_as_uint(r2[2 * p]), 0x07060302u);
-    }
-}
-
-__device__ __forceinline__ floatx4 mm(const u32x4 &w, const u32x4 &x, const floatx4 &acc) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, x), acc, 0, 0, 0);
-}
 
 // MTW x NTW 16x16 tiles per wave, WM x WN waves per K slice, KS K slices (slice ks takes the 32-deep K steps ks, ks + KS, ...
 // through a ring of D stages of its own), block = 64 WM WN KS threads, tile = (16 MTW WM) rows x (16 NTW WN) channels.
@@ -150,8 +113,8 @@ __global__ __launch_bounds__(64 * WM * WN * KS) void gemm_dma3_kernel(GemmDesc d
         const uint16_t *wk = W3 + 32 * s;                                       // ... the planes hold their own (zero-padded) last step
 #pragma unroll
         for (int j = 0; j < NP; j++) {
-            if (is_w[j]) __builtin_amdgcn_global_load_lds(G3_GLB_PTR(wk + off[j]), G3_LDS_PTR(sb + dst[j]), 16, 0, 0);
-            else __builtin_amdgcn_global_load_lds(G3_GLB_PTR(xk + off[j]), G3_LDS_PTR(sb + dst[j]), 16, 0, 0);
+            if (is_w[j]) __builtin_amdgcn_global_load_lds(BN_GLB_PTR(wk + off[j]), BN_LDS_PTR(sb + dst[j]), 16, 0, 0);
+            else __builtin_amdgcn_global_load_lds(BN_GLB_PTR(xk + off[j]), BN_LDS_PTR(sb + dst[j]), 16, 0, 0);
         }
     };
 
@@ -161,7 +124,7 @@ __global__ __launch_bounds__(64 * WM * WN * KS) void gemm_dma3_kernel(GemmDesc d
         for (int c0 = wave * 64; c0 < gate_floats / 4; c0 += 64 * WPS * KS) {
             int c = c0 + lane;
             c = c < n16 ? c : n16 - 1;
-            __builtin_amdgcn_global_load_lds(G3_GLB_PTR(gsrc + 4 * c), G3_LDS_PTR(gate + 4 * c0), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds(BN_GLB_PTR(gsrc + 4 * c), BN_LDS_PTR(gate + 4 * c0), 16, 0, 0);
         }
     }
 #pragma unroll
@@ -189,7 +152,7 @@ __global__ __launch_bounds__(64 * WM * WN * KS) void gemm_dma3_kernel(GemmDesc d
             for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
             if (lane == 0) {
                 float hv[1] = {a + (sei.b1 ? sei.b1[j] : 0.0f)};
-                g3_act<1>(se.act1, se.p0_1, se.p1_1, hv);
+                act_array<ACT_SET_GEMM_DMA>(se.act1, se.p0_1, se.p1_1, hv);
                 hbuf[j] = hv[0];
             }
         }
@@ -200,7 +163,7 @@ __global__ __launch_bounds__(64 * WM * WN * KS) void gemm_dma3_kernel(GemmDesc d
             float a = 0.0f;
             for (int j = 0; j < se.Cr; j++) a = fmaf(sei.w2t[(int64_t)j * se.C + c], hbuf[j], a);
             float gv[1] = {a + (sei.b2 ? sei.b2[c] : 0.0f)};
-            g3_act<1>(se.act2, se.p0_2, se.p1_2, gv);
+            act_array<ACT_SET_GEMM_DMA>(se.act2, se.p0_2, se.p1_2, gv);
             gate[c] = gv[0];
         }
     }
@@ -246,16 +209,7 @@ __global__ __launch_bounds__(64 * WM * WN * KS) void gemm_dma3_kernel(GemmDesc d
             const u32x4 wmd = *reinterpret_cast<const u32x4 *>(sb + woff[nt] + P_BYTES);
             const u32x4 wl = *reinterpret_cast<const u32x4 *>(sb + woff[nt] + 2 * P_BYTES);
 #pragma unroll
-            for (int mt = 0; mt < MTW; mt++) {
-                floatx4 a = acc[mt][nt];
-                a = mm(wl, xh[mt], a);
-                a = mm(wh, xl[mt], a);
-                a = mm(wmd, xm[mt], a);
-                a = mm(wmd, xh[mt], a);
-                a = mm(wh, xm[mt], a);
-                a = mm(wh, xh[mt], a);
-                acc[mt][nt] = a;
-            }
+            for (int mt = 0; mt < MTW; mt++) acc[mt][nt] = mm6(wh, wmd, wl, xh[mt], xm[mt], xl[mt], acc[mt][nt]);
         }
     };
     auto turn = [&](int i) {
@@ -326,7 +280,7 @@ __global__ __launch_bounds__(64 * WM * WN * KS) void gemm_dma3_kernel(GemmDesc d
 #pragma unroll
             for (int i = 0; i < 4; i++) v[(mt * NTW + nt) * 4 + i] = acc[mt][nt][i] + bv[i];
     }
-    g3_act<MTW * NTW * 4>(d.act, d.p0, d.p1, v);
+    act_array<ACT_SET_GEMM_DMA>(d.act, d.p0, d.p1, v);
     if constexpr (WM == 1) {
         if (d.gap) {  // the sample's mean over its rows (all TR of them sit in this wave): same order as gemm_dma_kernel's
 #pragma unroll

@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "capi_internal.h"
+#include "device_common.h"
 #include "hip_gate.h"
 #include "kernels.h"
 
@@ -47,7 +48,7 @@ constexpr int RED_BLOCKS = 128;    // blocks of head_reduce_kernel (fixed: the o
 constexpr int PREP_REGS = 32;      // head_prep_kernel keeps a row of up to 64 * 32 = 2048 elements in registers
 constexpr int RB = 64;             // rows per block of head_residual_kernel
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using bn::floatx4;
 
 // raw rows [n, dim] (stride src_stride) -> operand rows [npad, dpad]; rows >= n are zeros
 __global__ __launch_bounds__(256) void head_prep_kernel(const float *__restrict__ src, size_t src_stride, uint32_t n, uint32_t npad, uint32_t dim,
@@ -132,7 +133,7 @@ __global__ __launch_bounds__(256) void head_apply_kernel(const float *__restrict
         a[s] = *reinterpret_cast<const float4 *>(xp + 16 * s);
         b[s] = *reinterpret_cast<const float4 *>(wp + 16 * s);
     }
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    floatx4 acc = {0.f, 0.f, 0.f, 0.f};
     const uint32_t nkc = dpad / KC;
     for (uint32_t u = 0; u < nkc; u++) {
         float4 an[8], bn_[8];
@@ -218,9 +219,9 @@ __global__ __launch_bounds__(256) void head_grad_kernel(const float *__restrict_
     const uint32_t col0 = (blockIdx.x * 4 + w) * 64;
     if (col0 >= dpad) return;  // wave-uniform; dpad % 64 == 0
     const uint32_t i0 = blockIdx.z * slice_rows, i1 = min(npad, i0 + slice_rows);  // both multiples of 4
-    f32x4 acc[4];
+    floatx4 acc[4];
 #pragma unroll
-    for (int j = 0; j < 4; j++) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < 4; j++) acc[j] = floatx4{0.f, 0.f, 0.f, 0.f};
     const float *rp = R + (size_t)h * cpad + blockIdx.y * 16 + r16;
     const float *xp = X + (size_t)h * dpad + col0 + r16;
     for (uint32_t i = i0; i < i1; i += 4) {

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "capi_internal.h"
+#include "device_common.h"
 #include "hip_gate.h"
 
 namespace {
@@ -47,7 +48,7 @@ struct Cand {
 constexpr size_t SCAN_LDS = (size_t)QP * QS_LD * 4 + (size_t)QP * S_LD * 4 + (size_t)QP * PEND * sizeof(Cand) + 4 * MMAX * sizeof(Cand) +
                             QP * sizeof(Cand) + 2 * QP * sizeof(int);
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using bn::floatx4;
 
 __device__ inline bool ahead(Cand a, Cand b) { return a.s > b.s || (a.s == b.s && a.id < b.id); }
 
@@ -180,9 +181,9 @@ __global__ __launch_bounds__(256) void index_scan_kernel(const float *__restrict
         for (int s = 0; s < 8; s++) a[s] = *reinterpret_cast<const float4 *>(rp + 16 * s);
         load_q(0, qr);
     }
-    f32x4 acc[QB];
+    floatx4 acc[QB];
 #pragma unroll
-    for (int b = 0; b < QB; b++) acc[b] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int b = 0; b < QB; b++) acc[b] = floatx4{0.f, 0.f, 0.f, 0.f};
 
     for (uint32_t u = 0; u < steps; u++) {
         __syncthreads();  // the previous chunk's Qs reads are done
@@ -222,7 +223,7 @@ __global__ __launch_bounds__(256) void index_scan_kernel(const float *__restrict
         for (int b = 0; b < QB; b++) {
 #pragma unroll
             for (int r = 0; r < 4; r++) S[(b * 16 + r16) * S_LD + w * 16 + h * 4 + r] = acc[b][r];
-            acc[b] = f32x4{0.f, 0.f, 0.f, 0.f};
+            acc[b] = floatx4{0.f, 0.f, 0.f, 0.f};
         }
         __syncthreads();
         const uint32_t grow = t * TILE + lane;

@@ -50,6 +50,25 @@ enum Act : int32_t {
     ACT_ROUND,     // to nearest, ties to even (ONNX Round)
 };
 
+// The activation sets of the kernel families, declared ONCE: a kernel's dispatch is instantiated with its family's set
+// (device_common.h, act_dispatch: codes outside the set generate no code) and the planner's predicates test the same
+// constant, so a launcher can never be handed a code its kernel would pass through as the identity.  ACT_NONE is in
+// every set.
+template <class... A>
+constexpr uint64_t act_set(A... acts) { return (uint64_t{1} | ... | (uint64_t{1} << acts)); }
+constexpr bool act_in(uint64_t set, int act) { return act >= 0 && act < 64 && ((set >> act) & 1) != 0; }
+constexpr uint64_t ACT_SET_MBCONV = act_set(ACT_RELU, ACT_CLIP, ACT_SILU, ACT_HSWISH);  // fused MBConv: row-streaming and small-map kernels
+constexpr uint64_t ACT_SET_GEMM_DMA = ACT_SET_MBCONV | act_set(ACT_SIGMOID, ACT_HSIGMOID);  // LDS-DMA GEMMs (exact f32, dma3, b3)
+constexpr uint64_t ACT_SET_CONV = ACT_SET_GEMM_DMA | act_set(ACT_LEAKY, ACT_TANH);  // what a conv / GEMM epilogue absorbs from the graph
+// the compact stage functions (absorbed chains of stft.hip and the framing GEMMs): bodies of a few instructions, no libm
+constexpr uint64_t ACT_SET_COMPACT = act_set(ACT_RELU, ACT_CLIP, ACT_SIGMOID, ACT_SILU, ACT_LEAKY, ACT_EXP, ACT_LOG, ACT_SQRT, ACT_ABS, ACT_NEG,
+                                             ACT_RECIP, ACT_POW, ACT_AFFINE, ACT_MAXC, ACT_MINC, ACT_RSUB, ACT_RDIV, ACT_SQUARE, ACT_FLOOR, ACT_CEIL);
+constexpr uint64_t ACT_SET_ALL = (uint64_t{1} << (ACT_ROUND + 1)) - 1;
+// act(0) == 0: what a kernel that expands pixels outside the image to zeros needs of its first activation
+inline bool act_keeps_zero(int act, float p0, float p1) {
+    return (act == ACT_CLIP && p0 <= 0.f && p1 >= 0.f) || act_in(act_set(ACT_RELU, ACT_SILU, ACT_HSWISH, ACT_LEAKY, ACT_TANH), act);
+}
+
 enum BinOp : int32_t { BIN_NONE = 0, BIN_ADD, BIN_SUB, BIN_MUL, BIN_DIV, BIN_POW, BIN_MAX, BIN_MIN,
                        // (round 5) comparisons -> 0.0 / 1.0; the two halves of Where(cond, a, b) = SELA(a, cond) + SELB(b, cond)
                        BIN_GT, BIN_LT, BIN_GE, BIN_LE, BIN_EQ, BIN_NE,
@@ -222,7 +241,7 @@ struct PoolDesc {
 void launch_pool(hipStream_t s, const PoolDesc &d, float *out, const float *in, int64_t batch);
 
 // Row-streaming form (mbrow.hip): which blocks it takes (planner and launcher agree through these), outputs per strip
-inline bool mbconv_row_act_supported(int act) { return act == ACT_NONE || act == ACT_RELU || act == ACT_CLIP || act == ACT_SILU || act == ACT_HSWISH; }
+inline bool mbconv_row_act_supported(int act) { return act_in(ACT_SET_MBCONV, act); }
 inline bool mbconv_row_supported(const MbDesc &d) {
     const int ng = (d.Cin + 7) / 8;
     if (d.whole_map) return false;
@@ -408,7 +427,13 @@ struct StftPtrs {
     const float *mstart, *mcol, *mval, *mel_bias;  // CSR of the mel filter bank: row starts, (column, value) pairs in mcol (indices stored as floats); mval unused
 };
 // stage codes stft_kernel implements (a compact subset: no libm bodies); the planner absorbs only chains made of these
-inline bool stft_act_supported(int act) { return act != ACT_TANH && act != ACT_ERF && act != ACT_SOFTPLUS && act != ACT_HSIGMOID && act != ACT_HSWISH && act < ACT_GTC; }
+constexpr bool stft_act_supported(int act) { return act_in(ACT_SET_COMPACT, act); }
+constexpr bool compact_set_is_former_rule() {  // the negative list this predicate used to be, code by code
+    for (int a = ACT_NONE; a <= ACT_ROUND; a++)
+        if (stft_act_supported(a) != (a != ACT_TANH && a != ACT_ERF && a != ACT_SOFTPLUS && a != ACT_HSIGMOID && a != ACT_HSWISH && a < ACT_GTC)) return false;
+    return true;
+}
+static_assert(compact_set_is_former_rule(), "ACT_SET_COMPACT differs from what stft_act_supported accepted before");
 inline bool stft_bin_supported(int bin) { return bin != BIN_POW && bin < BIN_GT; }
 void launch_stft(hipStream_t s, const FftDesc &d, const StftPtrs &p, int64_t batch);
 

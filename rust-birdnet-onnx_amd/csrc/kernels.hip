@@ -237,7 +237,7 @@ __global__ __launch_bounds__(256) void elt_strided_kernel(EltDesc d, EltDiv dv, 
                     for (int u = 0; u < 4; u++) w[u] = pb[ob[s][u]];
                     bin_array<4>(st.bin, st.bsq, v, w);
                 }
-                act_array_all<4>(st.act, st.p0, st.p1, v);
+                act_array<ACT_SET_ALL>(st.act, st.p0, st.p1, v);
             }
         }
 #pragma unroll
@@ -288,7 +288,7 @@ __global__ __launch_bounds__(256) void elt_flat4_kernel(EltDesc d, EltFlat f, fl
                     }
                     bin_array<4>(st.bin, st.bsq, v, w);
                 }
-                act_array_all<4>(st.act, st.p0, st.p1, v);
+                act_array<ACT_SET_ALL>(st.act, st.p0, st.p1, v);
             }
         }
         o[i] = make_float4(v[0], v[1], v[2], v[3]);
@@ -594,66 +594,6 @@ __device__ __forceinline__ void mfma_ktile_partial(const float *__restrict__ ap,
     }
 }
 
-// Activation over a whole accumulator tile with ONE dispatch on the (wave-uniform) code.
-template <int NT, class F>
-__device__ __forceinline__ void map_tile(floatx16 (&acc)[NT], F f) {
-#pragma unroll
-    for (int t = 0; t < NT; t++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) acc[t][r] = f(acc[t][r]);
-}
-// activation over a small register array with ONE dispatch on the (uniform) code
-template <int N>
-__device__ __forceinline__ void act_array(int act, float p0, float p1, float (&v)[N]) {
-    if (act == ACT_NONE) return;
-    if (act == ACT_RELU) map_array<N>(v, [](float x) { return fmaxf(x, 0.0f); });
-    else if (act == ACT_CLIP) map_array<N>(v, [=](float x) { return fminf(fmaxf(x, p0), p1); });
-    else if (act == ACT_SILU) map_array<N>(v, [](float x) { return x * net_sigmoid(x); });
-    else if (act == ACT_SIGMOID) map_array<N>(v, [](float x) { return net_sigmoid(x); });
-    else if (act == ACT_HSWISH) map_array<N>(v, [](float x) { return x * fminf(fmaxf(x * (1.0f / 6.0f) + 0.5f, 0.0f), 1.0f); });
-    else if (act == ACT_HSIGMOID) map_array<N>(v, [=](float x) { return fminf(fmaxf(p0 * x + p1, 0.0f), 1.0f); });
-    else if (act == ACT_LEAKY) map_array<N>(v, [=](float x) { return x >= 0.0f ? x : p0 * x; });
-    else if (act == ACT_TANH) map_array<N>(v, [](float x) { return tanhf(x); });
-}
-
-template <int NT>
-__device__ __forceinline__ void act_tile(int act, float p0, float p1, floatx16 (&acc)[NT]) {
-    if (act == ACT_NONE) return;
-    if (act == ACT_RELU) map_tile<NT>(acc, [](float x) { return fmaxf(x, 0.0f); });
-    else if (act == ACT_CLIP) map_tile<NT>(acc, [=](float x) { return fminf(fmaxf(x, p0), p1); });
-    else if (act == ACT_SILU) map_tile<NT>(acc, [](float x) { return x * net_sigmoid(x); });
-    else if (act == ACT_SIGMOID) map_tile<NT>(acc, [](float x) { return net_sigmoid(x); });
-    else if (act == ACT_HSWISH) map_tile<NT>(acc, [](float x) { return x * fminf(fmaxf(x * (1.0f / 6.0f) + 0.5f, 0.0f), 1.0f); });
-    else if (act == ACT_HSIGMOID) map_tile<NT>(acc, [=](float x) { return fminf(fmaxf(p0 * x + p1, 0.0f), 1.0f); });
-    else if (act == ACT_LEAKY) map_tile<NT>(acc, [=](float x) { return x >= 0.0f ? x : p0 * x; });
-    else if (act == ACT_TANH) map_tile<NT>(acc, [](float x) { return tanhf(x); });
-}
-
-// every unary stage code (the elementwise kernels' set) over an accumulator tile: absorbed elementwise chains
-template <int NT>
-__device__ __forceinline__ void act_tile_all(int act, float p0, float p1, floatx16 (&acc)[NT]) {
-    switch (act) {
-        case ACT_EXP: map_tile<NT>(acc, [](float x) { return net_exp(x); }); return;
-        case ACT_LOG: map_tile<NT>(acc, [](float x) { return net_log(x); }); return;
-        case ACT_SQRT: map_tile<NT>(acc, [](float x) { return sqrtf(x); }); return;
-        case ACT_ABS: map_tile<NT>(acc, [](float x) { return fabsf(x); }); return;
-        case ACT_NEG: map_tile<NT>(acc, [](float x) { return -x; }); return;
-        case ACT_RECIP: map_tile<NT>(acc, [](float x) { return 1.0f / x; }); return;
-        case ACT_POW: map_tile<NT>(acc, [=](float x) { return net_pow(x, p0); }); return;
-        case ACT_AFFINE: map_tile<NT>(acc, [=](float x) { return p0 * x + p1; }); return;
-        case ACT_MAXC: map_tile<NT>(acc, [=](float x) { return fmaxf(x, p0); }); return;
-        case ACT_MINC: map_tile<NT>(acc, [=](float x) { return fminf(x, p0); }); return;
-        case ACT_RSUB: map_tile<NT>(acc, [=](float x) { return p0 - x; }); return;
-        case ACT_RDIV: map_tile<NT>(acc, [=](float x) { return p0 / x; }); return;
-        case ACT_SQUARE: map_tile<NT>(acc, [](float x) { return x * x; }); return;
-        case ACT_FLOOR: map_tile<NT>(acc, [](float x) { return floorf(x); }); return;
-        case ACT_CEIL: map_tile<NT>(acc, [](float x) { return ceilf(x); }); return;
-        case ACT_ERF: map_tile<NT>(acc, [](float x) { return erff(x); }); return;
-        case ACT_SOFTPLUS: map_tile<NT>(acc, [](float x) { return log1pf(expf(x)); }); return;
-        default: act_tile<NT>(act, p0, p1, acc); return;
-    }
-}
-
 // Shared epilogue: bias, activation, residual, store.  Lane (lr, lh) of a wave holds, in
 // acc[t][reg], C[rbase + (reg&3) + 8*(reg>>2) + 4*lh][n0 + 32*t + lr].  Output (and residual) rows
 // of one launch are contiguous across samples (ldc == N-stride of a dense [rows*batch, ldc]
@@ -680,9 +620,9 @@ __device__ __forceinline__ void gemm_epilogue(const GemmDesc &d, float *__restri
 #pragma unroll
             for (int r = 0; r < 16; r++) acc[t][r] += bv[t];
     }
-    act_tile<NT>(d.act, d.p0, d.p1, acc);
+    act_tile<ACT_SET_CONV>(d.act, d.p0, d.p1, acc);
     if constexpr (POST) {
-        for (int sidx = 0; sidx < d.npost; sidx++) act_tile_all<NT>(d.post_act[sidx], d.post_p0[sidx], d.post_p1[sidx], acc);
+        for (int sidx = 0; sidx < d.npost; sidx++) act_tile<ACT_SET_ALL>(d.post_act[sidx], d.post_p0[sidx], d.post_p1[sidx], acc);
         if (d.out_strided) {
 #pragma unroll
             for (int reg = 0; reg < 16; reg++) {
@@ -1566,7 +1506,7 @@ __global__ __launch_bounds__(64 * WN, 2) void frame_fold2p_kernel(Frame2Desc d, 
 // Arithmetic: per output one chain -- steps ascending, per step two 16-deep groups, per group the six partial products smallest terms
 // first.  Other bits than the f32 forms (BN_FRAME2_B3=0 keeps those), the same tolerance of the oracle.
 template <int WN>
-__global__ __launch_bounds__(64 * WN, 2) void frame_fold2q_kernel(Frame2Desc d, float *__restrict__ C, const float *__restrict__ A, const b3_u32x4 *__restrict__ Wq,
+__global__ __launch_bounds__(64 * WN, 2) void frame_fold2q_kernel(Frame2Desc d, float *__restrict__ C, const float *__restrict__ A, const u32x4 *__restrict__ Wq,
                                                                   const float *__restrict__ bias, const float *__restrict__ wtab, const int32_t *__restrict__ colmap,
                                                                   FramePre pre) {
     extern __shared__ __align__(16) float frame_lds[];
@@ -1614,8 +1554,6 @@ __global__ __launch_bounds__(64 * WN, 2) void frame_fold2q_kernel(Frame2Desc d, 
             xp[i] = make_float2(lds_ld(a_hp[i]), lds_ld(a_hp[i] + 4));
         }
     };
-    auto top = [](float v) { return __uint_as_float(__float_as_uint(v) & 0xffff0000u); };
-    auto pack = [](float hi16, float lo16) { return __builtin_amdgcn_perm(__float_as_uint(hi16), __float_as_uint(lo16), 0x07060302u); };
     auto st32 = [](uint32_t off, uint32_t v) { *(__attribute__((address_space(3))) uint32_t *)(uintptr_t)off = v; };
     auto finish_a = [&](uint32_t buf_off) {
 #pragma unroll
@@ -1625,19 +1563,15 @@ __global__ __launch_bounds__(64 * WN, 2) void frame_fold2q_kernel(Frame2Desc d, 
                 const float b0 = xm[i].y + xp[i].x, b1 = xm[i].x + xp[i].y;
                 const float ya0 = cwa.x * a0, ya1 = cwa.y * a1, yb0 = cwb.x * b0, yb1 = cwb.y * b1;
                 const float v[4] = {ya0 + yb0, ya1 + yb1, ya0 - yb0, ya1 - yb1};  // S pair, D pair
-                float r1[4], r2[4];
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    r1[q] = v[q] - top(v[q]);
-                    r2[q] = r1[q] - top(r1[q]);
-                }
+                uint32_t sp[3], dp[3];
+                split3_pair(v[0], v[1], sp[0], sp[1], sp[2]);
+                split3_pair(v[2], v[3], dp[0], dp[1], dp[2]);
                 const uint32_t dst = a_dst[i] + buf_off;
-                st32(dst, pack(v[1], v[0]));
-                st32(dst + PT, pack(r1[1], r1[0]));
-                st32(dst + 2 * PT, pack(r2[1], r2[0]));
-                st32(dst + 3 * PT, pack(v[3], v[2]));
-                st32(dst + 4 * PT, pack(r1[3], r1[2]));
-                st32(dst + 5 * PT, pack(r2[3], r2[2]));
+#pragma unroll
+                for (int q = 0; q < 3; q++) {
+                    st32(dst + q * PT, sp[q]);
+                    st32(dst + (3 + q) * PT, dp[q]);
+                }
             }
             a_fw[i] += 4 * GEMM_BK; a_hp[i] += 4 * GEMM_BK;
             a_rv[i] -= 4 * GEMM_BK; a_hm[i] -= 4 * GEMM_BK;
@@ -1647,8 +1581,8 @@ __global__ __launch_bounds__(64 * WN, 2) void frame_fold2q_kernel(Frame2Desc d, 
     const int wn = tid >> 6, lane = tid & 63, lr = lane & 31, lh = lane >> 5;
     const int kind = wn * 32 < d.n_even ? 0 : 1;
     // this wave's filter fragments: [wn][step][g][plane][lane] x 16 bytes
-    const b3_u32x4 *wf = Wq + ((int64_t)wn * nsteps * 6) * 64 + lane;
-    b3_u32x4 w[6], nw[6];
+    const u32x4 *wf = Wq + ((int64_t)wn * nsteps * 6) * 64 + lane;
+    u32x4 w[6], nw[6];
 #pragma unroll
     for (int q = 0; q < 6; q++) w[q] = wf[q * 64];
     __syncthreads();  // signal span and window tables complete
@@ -1659,14 +1593,11 @@ __global__ __launch_bounds__(64 * WN, 2) void frame_fold2q_kernel(Frame2Desc d, 
 #pragma unroll
     for (int r = 0; r < 16; r++) acc[r] = 0.0f;
     const uint32_t ap0 = as0 + (uint32_t)kind * 3u * PT + (uint32_t)lr * PITCH + 16u * (uint32_t)lh;
-    auto ld128 = [](uint32_t off) { return *(const __attribute__((address_space(3))) b3_u32x4 *)(uintptr_t)off; };
-    auto mm32 = [](const b3_u32x4 &a, const b3_u32x4 &wv, const floatx16 &c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(b3_bf16x8, a), __builtin_bit_cast(b3_bf16x8, wv), c, 0, 0, 0);
-    };
+    auto ld128 = [](uint32_t off) { return *(const __attribute__((address_space(3))) u32x4 *)(uintptr_t)off; };
     for (int ks = 0; ks < nsteps; ks++) {
         const int cur = ks & 1;
         {  // the fragments of the next step (the last step re-reads its own: loads of this loop are unconditional)
-            const b3_u32x4 *wn_ = wf + (int64_t)min(ks + 1, nsteps - 1) * 384;
+            const u32x4 *wn_ = wf + (int64_t)min(ks + 1, nsteps - 1) * 384;
 #pragma unroll
             for (int q = 0; q < 6; q++) nw[q] = wn_[q * 64];
         }
@@ -1674,14 +1605,14 @@ __global__ __launch_bounds__(64 * WN, 2) void frame_fold2q_kernel(Frame2Desc d, 
         const uint32_t ap = ap0 + (uint32_t)cur * BUF;
 #pragma unroll
         for (int g = 0; g < 2; g++) {
-            const b3_u32x4 ah = ld128(ap + 32u * g), am = ld128(ap + 32u * g + PT), al = ld128(ap + 32u * g + 2 * PT);
-            const b3_u32x4 &wh = w[3 * g], &wm = w[3 * g + 1], &wl = w[3 * g + 2];
-            acc = mm32(ah, wl, acc);
-            acc = mm32(al, wh, acc);
-            acc = mm32(am, wm, acc);
-            acc = mm32(ah, wm, acc);
-            acc = mm32(am, wh, acc);
-            acc = mm32(ah, wh, acc);
+            const u32x4 ah = ld128(ap + 32u * g), am = ld128(ap + 32u * g + PT), al = ld128(ap + 32u * g + 2 * PT);
+            const u32x4 &wh = w[3 * g], &wm = w[3 * g + 1], &wl = w[3 * g + 2];
+            acc = mm32_bf16(ah, wl, acc);
+            acc = mm32_bf16(al, wh, acc);
+            acc = mm32_bf16(am, wm, acc);
+            acc = mm32_bf16(ah, wm, acc);
+            acc = mm32_bf16(am, wh, acc);
+            acc = mm32_bf16(ah, wh, acc);
         }
         if (ks + 1 < nsteps) finish_a((uint32_t)(cur ^ 1) * BUF);
 #pragma unroll
@@ -2352,7 +2283,7 @@ __global__ __launch_bounds__(256) void mbconv_expand_dw_kernel(MbDesc d, float *
                         acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.z, bw[g].z, acc[0], 0, 0, 0);
                         acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.w, bw[g].w, acc[0], 0, 0, 0);
                     }
-                act_tile<1>(d.act1, d.p0_1, d.p1_1, acc);
+                act_tile<ACT_SET_CONV>(d.act1, d.p0_1, d.p1_1, acc);
                 float *ep = Es + (mt * 32 + 4 * lh) * 32 + lr;
 #pragma unroll
                 for (int reg = 0; reg < 16; reg++) ep[((reg & 3) + 8 * (reg >> 2)) * 32] = acc[0][reg];
@@ -2376,7 +2307,7 @@ __global__ __launch_bounds__(256) void mbconv_expand_dw_kernel(MbDesc d, float *
                         ov[(ix - kx) / S] = fmaf(v, wd[ky * K + kx], ov[(ix - kx) / S]);
             }
         }
-        act_array<PPG>(d.act2, d.p0_2, d.p1_2, ov);
+        act_array<ACT_SET_CONV>(d.act2, d.p0_2, d.p1_2, ov);
         float sum = 0.0f;
         if (seg_full && c0 + 32 <= d.C) {  // block-uniform per lane group: no per-pixel predicates
 #pragma unroll
@@ -2724,7 +2655,7 @@ __global__ __launch_bounds__(512) void mbconv_pipe_kernel(MbDesc d, float *__res
                                 acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.z, bw[g].z, acc[0], 0, 0, 0);
                                 acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.w, bw[g].w, acc[0], 0, 0, 0);
                             }
-                        act_tile<1>(d.act1, d.p0_1, d.p1_1, acc);
+                        act_tile<ACT_SET_CONV>(d.act1, d.p0_1, d.p1_1, acc);
                         float *ep = Es + (mt * 32 + 4 * lh) * 32 + lr;
 #pragma unroll
                         for (int reg = 0; reg < 16; reg++) ep[((reg & 3) + 8 * (reg >> 2)) * 32] = acc[0][reg];
@@ -2757,7 +2688,7 @@ __global__ __launch_bounds__(512) void mbconv_pipe_kernel(MbDesc d, float *__res
                             ov[(ix - kx) / S] = fmaf(v, wd[ky * K + kx], ov[(ix - kx) / S]);
                 }
             }
-            act_array<PPG>(d.act2, d.p0_2, d.p1_2, ov);
+            act_array<ACT_SET_CONV>(d.act2, d.p0_2, d.p1_2, ov);
             float sum = 0.0f;
             if (seg_full && c0 + 32 <= d.C) {
 #pragma unroll
@@ -2826,7 +2757,7 @@ __device__ __forceinline__ void dw_map_from_lds(const float *In, float *red, con
                 }
             }
         }
-        act_array<PPG>(act, p0, p1, ov);
+        act_array<ACT_SET_CONV>(act, p0, p1, ov);
 #pragma unroll
         for (int q = 0; q < PPG; q++) {
             if (cact && ox0 + q < OW) {
@@ -2968,7 +2899,7 @@ __global__ __launch_bounds__(256) void dwconv_mapt_kernel(DwDesc d, float *__res
                     if (iy - ky >= 0 && (iy - ky) % S == 0 && (iy - ky) / S < R && ix - kx >= 0 && (ix - kx) % S == 0 && (ix - kx) / S < CW)
                         ov[((iy - ky) / S) * CW + (ix - kx) / S] = fmaf(v, wd[ky * K + kx], ov[((iy - ky) / S) * CW + (ix - kx) / S]);
         }
-    act_array<R * CW>(d.act, d.p0, d.p1, ov);
+    act_array<ACT_SET_CONV>(d.act, d.p0, d.p1, ov);
     float sum = 0.0f;
     if (cact) {
         float *ob = out + b * d.out_bs + cg;
@@ -3077,7 +3008,7 @@ __global__ __launch_bounds__(256) void mbconv_map_kernel(MbDesc d, float *__rest
         floatx16 at[1] = {acc};
 #pragma unroll
         for (int reg = 0; reg < 16; reg++) at[0][reg] += bv;
-        act_tile<1>(d.act1, d.p0_1, d.p1_1, at);
+        act_tile<ACT_SET_CONV>(d.act1, d.p0_1, d.p1_1, at);
         float *ep = Es + (mt * 32 + 4 * lh) * 32 + lr;
 #pragma unroll
         for (int reg = 0; reg < 16; reg++) ep[((reg & 3) + 8 * (reg >> 2)) * 32] = at[0][reg];
@@ -3546,7 +3477,7 @@ void launch_gemm_fold2(hipStream_t s, const GemmDesc &d, float *C, const float *
         f.vec4 = d.a_bs % 4 == 0 && (32 * (int64_t)f.hop) % 4 == 0 && aligned16(A);
         const size_t ldsq = frame_fold2q_lds_bytes(d);
         const dim3 gridq((unsigned)((int64_t)f.tiles * batch));
-        const b3_u32x4 *Wq = reinterpret_cast<const b3_u32x4 *>(W);
+        const u32x4 *Wq = reinterpret_cast<const u32x4 *>(W);
 #define FOLD2Q_GO(WN)                                                                                                       \
     do {                                                                                                                    \
         if (!ensure_dynamic_lds(reinterpret_cast<const void *>(frame_fold2q_kernel<WN>), ldsq)) {                           \

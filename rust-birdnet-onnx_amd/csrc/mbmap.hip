@@ -107,7 +107,7 @@ __global__ __launch_bounds__(64 * WM * WN * KSP) void mbmap_kernel(MbDesc d, flo
 
     if (d.dbg & 32) return;  // (tools/mbmap_phases.py: the cost of the empty launch)
     // ---- prologue: the sample's input and the first filter chunk on their way, the padding of the chunk image zeroed
-    b3_u32x4 xh[B3 ? MW : 1][B3 ? NSW : 1], xm[B3 ? MW : 1][B3 ? NSW : 1], xl[B3 ? MW : 1][B3 ? NSW : 1];
+    u32x4 xh[B3 ? MW : 1][B3 ? NSW : 1], xm[B3 ? MW : 1][B3 ? NSW : 1], xl[B3 ? MW : 1][B3 ? NSW : 1];
     floatx4 raw[B3 ? MW : 1][B3 ? NSW : 1][2];
     if constexpr (B3) {
         // The sample's input goes through LDS once: the f32 form's dense copy (whole cache lines, 1 KiB per wave instruction) into an image
@@ -214,7 +214,7 @@ __global__ __launch_bounds__(64 * WM * WN * KSP) void mbmap_kernel(MbDesc d, flo
 #pragma unroll
             for (int st = 0; st < NSW; st++) {
                 if (d.dbg & 16) {
-                    xh[mt][st] = xm[mt][st] = xl[mt][st] = __builtin_bit_cast(b3_u32x4, raw[mt][st][0] + raw[mt][st][1]);
+                    xh[mt][st] = xm[mt][st] = xl[mt][st] = __builtin_bit_cast(u32x4, raw[mt][st][0] + raw[mt][st][1]);
                 } else {
                     split3(raw[mt][st][0], raw[mt][st][1], xh[mt][st], xm[mt][st], xl[mt][st]);
                 }
@@ -275,7 +275,7 @@ __global__ __launch_bounds__(64 * WM * WN * KSP) void mbmap_kernel(MbDesc d, flo
 #pragma unroll
             for (int f = 0; f < NSW * NW; f++) {
                 if (f + 1 < NSW * NW) rdw(wr[(f + 1) & 1], f + 1);
-                b3_u32x4 wh, wmid, wl;
+                u32x4 wh, wmid, wl;
                 split3(wr[f & 1][0], wr[f & 1][1], wh, wmid, wl);
 #pragma unroll
                 for (int mt = 0; mt < MW; mt++) acc[mt][f % NW] = mm6(wh, wmid, wl, xh[mt][f / NW], xm[mt][f / NW], xl[mt][f / NW], acc[mt][f % NW]);
@@ -330,7 +330,7 @@ __global__ __launch_bounds__(64 * WM * WN * KSP) void mbmap_kernel(MbDesc d, flo
                 for (int nt = 0; nt < NW; nt++)
 #pragma unroll
                     for (int i = 0; i < 4; i++) v[(mt * NW + nt) * 4 + i] = acc[mt][nt][i];
-            mm_act<MW * NW * 4>(d.act1, d.p0_1, d.p1_1, v);
+            act_array<ACT_SET_MBCONV>(d.act1, d.p0_1, d.p1_1, v);
 #pragma unroll
             for (int mt = 0; mt < MW; mt++)
 #pragma unroll
@@ -390,7 +390,7 @@ __global__ __launch_bounds__(64 * WM * WN * KSP) void mbmap_kernel(MbDesc d, flo
                 float r[PPG];
 #pragma unroll
                 for (int q = 0; q < PPG; q++) r[q] = ov[oy][q];
-                mm_act<PPG>(d.act2, d.p0_2, d.p1_2, r);
+                act_array<ACT_SET_MBCONV>(d.act2, d.p0_2, d.p1_2, r);
                 if (cact) {
 #pragma unroll
                     for (int q = 0; q < PPG; q++) {

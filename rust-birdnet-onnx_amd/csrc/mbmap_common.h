@@ -1,12 +1,6 @@
-// Helpers shared by the small-map MBConv kernels (mbmap.hip, mbmap_ws.hip): LDS image swizzles, the dense global -> LDS copies, the
-// activation dispatch.  Included inside namespace bn { namespace { ... } } of each translation unit.
+// Helpers shared by the small-map MBConv kernels (mbmap.hip, mbmap_ws.hip): LDS image swizzles, the dense global -> LDS copies.
+// Included inside namespace bn { namespace { ... } } of each translation unit.
 #pragma once
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-
-#define MM_LDS_PTR(p) ((__attribute__((address_space(3))) void *)(p))
-#define MM_GLB_PTR(p) ((const __attribute__((address_space(1))) void *)(p))
-
-
 // Row swizzle of the [rows][Cin] LDS images (input map, filter chunk).  A ds_read_b128 fragment read touches 16 rows at
 // one k position; with a row stride of Cin floats they fall on 64 / gcd(64, Cin mod 64) ... banks: 2-way conflicts for
 // Cin = 80 / 112, 8-way for Cin = 192 (measured: 45 - 83 % of the LDS cycles of the first version were conflicts).  The
@@ -30,7 +24,7 @@ __device__ __forceinline__ void mm_copy(float *lds_dst, const float *gsrc, int r
         const int r = (int)__umulhi((uint32_t)sl, inv_ch);
         const int c = sl - r * CH;
         const int src = r * CH + (c ^ mm_swz<SWZ16>(r));
-        __builtin_amdgcn_global_load_lds(MM_GLB_PTR(gsrc + 4 * src), MM_LDS_PTR(lds_dst + 4 * c0), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds(BN_GLB_PTR(gsrc + 4 * src), BN_LDS_PTR(lds_dst + 4 * c0), 16, 0, 0);
     }
 }
 
@@ -63,7 +57,7 @@ __device__ __forceinline__ void mm_copy_in(float *lds_dst, const float *gsrc, co
         const int pr = r / W, pc = r - pr * W;  // W is a power of two
         const int pix = tr ? pc * HM + gy0 + pr : gy0 * W + r;
         const float *src = cl < CHS ? gsrc + (size_t)pix * (size_t)Cin + 4 * cl : zpage;
-        __builtin_amdgcn_global_load_lds(MM_GLB_PTR(src), MM_LDS_PTR(lds_dst + 4 * c0), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds(BN_GLB_PTR(src), BN_LDS_PTR(lds_dst + 4 * c0), 16, 0, 0);
     }
 }
 
@@ -75,21 +69,12 @@ __device__ __forceinline__ void mm_copy_in(float *lds_dst, const float *gsrc, co
 template <int NWAVES>
 __device__ __forceinline__ void mm_copy_w3(float *lds_dst, const float *gsrc, int npieces, int wave, int lane) {
     for (int i = wave; i < 2 * npieces; i += NWAVES)
-        __builtin_amdgcn_global_load_lds(MM_GLB_PTR(gsrc + i * 256 + lane * 4), MM_LDS_PTR(lds_dst + i * 256), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds(BN_GLB_PTR(gsrc + i * 256 + lane * 4), BN_LDS_PTR(lds_dst + i * 256), 16, 0, 0);
 }
 
 // dense copy of `kib` KiB, piece i by wave i % NWAVES
 template <int NWAVES>
 __device__ __forceinline__ void mm_copy_lin(float *lds_dst, const float *gsrc, int kib, int wave, int lane) {
     for (int i = wave; i < kib; i += NWAVES)
-        __builtin_amdgcn_global_load_lds(MM_GLB_PTR(gsrc + i * 256 + lane * 4), MM_LDS_PTR(lds_dst + i * 256), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds(BN_GLB_PTR(gsrc + i * 256 + lane * 4), BN_LDS_PTR(lds_dst + i * 256), 16, 0, 0);
 }
-
-template <int N>
-__device__ __forceinline__ void mm_act(int act, float p0, float p1, float (&v)[N]) {
-    if (act == ACT_RELU) map_array<N>(v, [](float x) { return fmaxf(x, 0.0f); });
-    else if (act == ACT_CLIP) map_array<N>(v, [=](float x) { return fminf(fmaxf(x, p0), p1); });
-    else if (act == ACT_SILU) map_array<N>(v, [](float x) { return x * net_sigmoid(x); });
-    else if (act == ACT_HSWISH) map_array<N>(v, [](float x) { return x * fminf(fmaxf(x * (1.0f / 6.0f) + 0.5f, 0.0f), 1.0f); });
-}
-

@@ -130,7 +130,7 @@ __global__ __launch_bounds__(512) void mbmap_ws_kernel(MbDesc d, float *__restri
         __builtin_amdgcn_s_barrier();  // the image's space is free
         asm volatile("" ::: "memory");
         zero_padding();
-        b3_u32x4 xh[MW][NSW], xm[MW][NSW], xl[MW][NSW];
+        u32x4 xh[MW][NSW], xm[MW][NSW], xl[MW][NSW];
         int epix[MW];
 #pragma unroll
         for (int mt = 0; mt < MW; mt++) {
@@ -168,11 +168,11 @@ __global__ __launch_bounds__(512) void mbmap_ws_kernel(MbDesc d, float *__restri
                 mm_copy_lin<EWV>(Ws + ((p + 1) & 1) * WSZ, w1 + (int64_t)((c0 + NC) / 16) * (NSW * 768), WSZ / 256, wave, lane);
                 fetch_bias(nbias, c0 + NC);
             }
-            b3_u32x4 wr[2][3];
-            auto rdw = [&](b3_u32x4 (&r)[3], int f) {  // f = st * NW + nt, compile time at every call site: the three planes of the fragment
+            u32x4 wr[2][3];
+            auto rdw = [&](u32x4 (&r)[3], int f) {  // f = st * NW + nt, compile time at every call site: the three planes of the fragment
                 const float *wb = Wc + (((nt0 + f % NW) * NSW + f / NW) * 3 * 64 + lane) * 4;
 #pragma unroll
-                for (int pp = 0; pp < 3; pp++) r[pp] = *reinterpret_cast<const b3_u32x4 *>(wb + pp * 256);
+                for (int pp = 0; pp < 3; pp++) r[pp] = *reinterpret_cast<const u32x4 *>(wb + pp * 256);
             };
             rdw(wr[0], 0);
 #pragma unroll
@@ -190,7 +190,7 @@ __global__ __launch_bounds__(512) void mbmap_ws_kernel(MbDesc d, float *__restri
                 for (int nt = 0; nt < NW; nt++)
 #pragma unroll
                     for (int i = 0; i < 4; i++) v[(mt * NW + nt) * 4 + i] = acc[mt][nt][i];
-            mm_act<MW * NW * 4>(d.act1, d.p0_1, d.p1_1, v);
+            act_array<ACT_SET_MBCONV>(d.act1, d.p0_1, d.p1_1, v);
 #pragma unroll
             for (int mt = 0; mt < MW; mt++)
 #pragma unroll
@@ -291,7 +291,7 @@ __global__ __launch_bounds__(512) void mbmap_ws_kernel(MbDesc d, float *__restri
                 float r[PPG];
 #pragma unroll
                 for (int x = 0; x < PPG; x++) r[x] = ov[oy][x];
-                mm_act<PPG>(d.act2, d.p0_2, d.p1_2, r);
+                act_array<ACT_SET_MBCONV>(d.act2, d.p0_2, d.p1_2, r);
                 if (cact) {
 #pragma unroll
                     for (int x = 0; x < PPG; x++) {

@@ -38,14 +38,13 @@
 namespace bn {
 namespace {
 
-// activations the row kernel carries: mbconv_row_act_supported (kernels.h); each call site is replicated per row slot, so
-// the set is kept small and the planner sends every other code to the tiled kernel
-template <int N>
-__device__ __forceinline__ void row_act(int act, float p0, float p1, float (&v)[N]) {
-    if (act == ACT_RELU) map_array<N>(v, [](float x) { return fmaxf(x, 0.0f); });
-    else if (act == ACT_SILU) map_array<N>(v, [](float x) { return x * net_sigmoid(x); });
-    else if (act == ACT_HSWISH) map_array<N>(v, [](float x) { return x * fminf(fmaxf(x * (1.0f / 6.0f) + 0.5f, 0.0f), 1.0f); });
-    else if (act == ACT_CLIP) map_array<N>(v, [=](float x) { return fminf(fmaxf(x, p0), p1); });
+// activations the row kernel carries: ACT_SET_MBCONV (kernels.h); each call site is replicated per row slot, so the set is
+// kept small and the planner sends every other code to the tiled kernel.  ACT >= 0: both activations of the block are
+// this code, known at compile time; ACT < 0: run-time dispatch.
+template <int ACT, int N>
+__device__ __forceinline__ void row_act_t(int act, float p0, float p1, float (&v)[N]) {
+    if constexpr (ACT == ACT_RELU || ACT == ACT_SILU) map_array<N>(v, [=](float x) { return act_fn<ACT>(x, p0, p1); });
+    else act_array<ACT_SET_MBCONV>(act, p0, p1, v);
 }
 
 // value of the same register in the lane 32 places up (lanes 0..31 receive lanes 32..63; the upper half keeps its own)
@@ -93,14 +92,6 @@ __device__ __forceinline__ void dw_rows(const float (&rows)[K][XW_], const float
                 if (ix - kx >= 0 && (ix - kx) % S == 0 && (ix - kx) / S < NOUT) ov[(ix - kx) / S] = fmaf(v, wd[ky * K + kx], ov[(ix - kx) / S]);
         }
     }
-}
-
-// Compile-time activation (ACT >= 0: both activations of the block are this code) or run-time dispatch (ACT < 0).
-template <int ACT, int N>
-__device__ __forceinline__ void row_act_t(int act, float p0, float p1, float (&v)[N]) {
-    if constexpr (ACT == ACT_RELU) map_array<N>(v, [](float x) { return fmaxf(x, 0.0f); });
-    else if constexpr (ACT == ACT_SILU) map_array<N>(v, [](float x) { return x * net_sigmoid(x); });
-    else row_act<N>(act, p0, p1, v);
 }
 
 // Schedule of one unit (nrows halo rows, J = 0 .. nrows; step J expands row J and emits the output row that row J - 1
@@ -161,7 +152,7 @@ __global__ __launch_bounds__(256, (mbrow_waves_per_simd<K, NG, S, IM2COL, ACT, B
     constexpr int NG16 = (NG + 1) / 2;        // B3: 16-deep k groups; an odd NG leaves the last group's upper half (lh == 1) as padding
     constexpr bool B3_PAD = B3 && (NG & 1);
     float4 bw[B3 ? 1 : NG];
-    b3_u32x4 bwh[B3 ? NG16 : 1], bwm[B3 ? NG16 : 1], bwl[B3 ? NG16 : 1];
+    u32x4 bwh[B3 ? NG16 : 1], bwm[B3 ? NG16 : 1], bwl[B3 ? NG16 : 1];
     {
         const int n = min(ch * 32 + lr, d.C - 1);
         if constexpr (B3) {
@@ -170,8 +161,8 @@ __global__ __launch_bounds__(256, (mbrow_waves_per_simd<K, NG, S, IM2COL, ACT, B
             for (int G = 0; G < NG16; G++) {
                 const bool pad = B3_PAD && G == NG16 - 1 && lh == 1;
                 const float *p = wr + (pad ? 0 : 16 * G + 8 * lh);
-                b3_floatx4 lo4 = *reinterpret_cast<const b3_floatx4 *>(p), hi4 = *reinterpret_cast<const b3_floatx4 *>(p + 4);
-                if (pad) lo4 = hi4 = b3_floatx4{0.f, 0.f, 0.f, 0.f};
+                floatx4 lo4 = *reinterpret_cast<const floatx4 *>(p), hi4 = *reinterpret_cast<const floatx4 *>(p + 4);
+                if (pad) lo4 = hi4 = floatx4{0.f, 0.f, 0.f, 0.f};
                 split3(lo4, hi4, bwh[G], bwm[G], bwl[G]);
             }
         } else {
@@ -348,9 +339,9 @@ __global__ __launch_bounds__(256, (mbrow_waves_per_simd<K, NG, S, IM2COL, ACT, B
         }                                                                                                                       \
         if constexpr (B3) {                                                                                                     \
             _Pragma("unroll") for (int G = 0; G < NG16; G++) {                                                                  \
-                b3_u32x4 xh_, xm_, xl_;                                                                                         \
-                split3(b3_floatx4{A[2 * G].x, A[2 * G].y, A[2 * G].z, A[2 * G].w},                                              \
-                       b3_floatx4{A[2 * G + 1].x, A[2 * G + 1].y, A[2 * G + 1].z, A[2 * G + 1].w}, xh_, xm_, xl_);              \
+                u32x4 xh_, xm_, xl_;                                                                                         \
+                split3(floatx4{A[2 * G].x, A[2 * G].y, A[2 * G].z, A[2 * G].w},                                              \
+                       floatx4{A[2 * G + 1].x, A[2 * G + 1].y, A[2 * G + 1].z, A[2 * G + 1].w}, xh_, xm_, xl_);              \
                 acc = mm32_bf16(xh_, bwl[G], G == 0 ? bvec : acc);                                                              \
                 acc = mm32_bf16(xl_, bwh[G], acc);                                                                              \
                 acc = mm32_bf16(xm_, bwm[G], acc);                                                                              \

@@ -98,9 +98,7 @@ inline bool frame_fold_pair_ok(const GemmDesc &d, const GemmDesc &d2) {
 
 // ---- LDS-DMA GEMM (gemm_dma.hip) ----------------------------------------------------------------------------------
 // epilogue activations the kernel carries (one dispatch on the launch-uniform code); other codes keep the older kernels
-BN_HD inline bool gemm_dma_act_ok(int act) {
-    return act == ACT_NONE || act == ACT_RELU || act == ACT_CLIP || act == ACT_SILU || act == ACT_HSWISH || act == ACT_SIGMOID || act == ACT_HSIGMOID;
-}
+BN_HD inline bool gemm_dma_act_ok(int act) { return act_in(ACT_SET_GEMM_DMA, act); }
 
 // floats of LDS a (tile, K-slice count, ring depth) configuration needs for this layer
 inline size_t gemm_dma_lds_bytes(const GemmDesc &d, int mtw, int ntw, int wm, int wn, int ks, int depth, int se_cr = 0) {

@@ -173,8 +173,7 @@ __device__ __forceinline__ void async_copy(float *lds_dst, const float *gsrc, in
     for (int c0 = wave * 64; c0 < n16; c0 += NW * 64) {
         int c = c0 + lane;
         c = c < n16 ? c : n16 - 1;
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(gsrc + 4 * c),
-                                         (__attribute__((address_space(3))) void *)(lds_dst + 4 * c0), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds(BN_GLB_PTR(gsrc + 4 * c), BN_LDS_PTR(lds_dst + 4 * c0), 16, 0, 0);
     }
 }
 
@@ -386,7 +385,6 @@ __global__ __launch_bounds__(NW * 64) void stft_kernel(FftDesc d, StftPtrs p, in
 
     // (the wave <-> band tile assignment is the same for every frame tile: filter tiles, group indices and bias are loaded ONCE per
     // block and stay in registers -- per tile they were three dependent L2 round trips behind the barrier, 5 - 6 us of a 16 us tile)
-    typedef float floatx4 __attribute__((ext_vector_type(4)));
     constexpr int MPRE = 8;
     const bool mel_mfma = nmel && mel_mode == 1 && !(dbg & 4);
     const int ntile = (nmel + 15) >> 4;

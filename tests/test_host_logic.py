@@ -592,3 +592,24 @@ def test_round5_small_map_forms_in_the_three_plans(bn, tmp_path, monkeypatch):
     monkeypatch.setenv("BN_MBMAP_B3", "0")
     d24c = plan(synth.birdnet_v24(), "a.onnx")
     assert d24c.count("map=cfg") == 10 and ",b3" not in d24c and ",ws" not in d24c
+
+
+def test_dma_gemm_predicates_follow_the_declared_activation_set(bn, tmp_path, monkeypatch):
+    """The LDS-DMA GEMM kernels dispatch on ACT_SET_GEMM_DMA (kernels.h) and gemm_dma_act_ok tests the same constant: behind the
+    1x1 conv 144 -> 40 on an 8 x 16 map the six codes of the set ride in the dma3 launch (the exact-f32 dma launch under BN_GEMM3=0),
+    LeakyRelu and Tanh -- conv-epilogue codes outside it -- keep the activation in the launch but take another kernel."""
+    import activation_routes as R
+    for act, code in R.ACTS.items():
+        p = tmp_path / f"{act}.onnx"
+        p.write_bytes(R.pointwise(144, 8, 16, 40, act))
+        for gemm3, kernel in ((None, "dma3"), ("0", "dma")):
+            if gemm3 is None:
+                monkeypatch.delenv("BN_GEMM3", raising=False)
+            else:
+                monkeypatch.setenv("BN_GEMM3", gemm3)
+            line = [l for l in bn.plan_describe(str(p)).splitlines() if " K=144 N=40 " in l]
+            assert len(line) == 1 and f" act={code} " in line[0], (act, line)
+            if act in R.GEMM_DMA_SET:
+                assert f"kernel={kernel} " in line[0] + " ", (act, line)
+            else:
+                assert not any(f"kernel={k} " in line[0] + " " for k in ("dma3", "b3", "dma")), (act, line)
