@@ -606,6 +606,92 @@ bn_status bn_ctx_prior_site(bn_ctx *c, int32_t site);
 bn_status bn_step_prior_results(const bn_ctx *c, const uint32_t **idx, const float **conf, const uint32_t **count, size_t *k_stride);
 
 /*
+ * Detection events: a device-resident tracker that turns the per-window logits rows of many sources into DETECTIONS -- species j
+ * was heard at source s from window a to window b, h times, with a peak confidence and the window of that peak.  It is the one
+ * stage of the live pipeline that carries state from a step to the next: one small record per (source, species), n_sources x
+ * n_species fixed at creation, updated by every step of a context it is attached to, like heads and priors.  Only finished
+ * events leave the device.  The reference has no counterpart (its CLI prints per-window lists, src/bin/birdnet-analyze.rs:556-650);
+ * the definition below is the contract.
+ *
+ *   Per row        for a row that is window k of source s, and species j with logit z:
+ *                    conf = sigmoid(z), the step's own (bit-exact to the reference's)
+ *                    under BN_TRACK_PRIOR, with p = P[site][j] of the prior passed with the update or attached to the context:
+ *                      a species that is not admitted (bn_prior: p < 0 || p >= threshold) is never a hit;
+ *                      conf = conf' of the prior (conf * p under its BN_PRIOR_RERANK for p >= 0)
+ *                    hit  = conf >= enter_conf (IEEE comparison: NaN is not a hit)
+ *   Open event     (hits > 0, last hit window `last`): misses = (k - last - 1) + (hit ? 0 : 1); misses > max_gap CLOSES the event.
+ *                  A closed event is emitted iff hits >= min_hits, otherwise dropped silently.
+ *   Hit            opens a new event (first = k, sum = 0, hits = 0, peak = conf, peak_window = k) or extends the open one; then
+ *                  last = k, hits += 1, sum += conf (f32, in increasing k: deterministic); conf > peak (strict: the earliest peak
+ *                  wins a tie) sets peak and peak_window.
+ *   Windows        are absolute numbers below 2^31: a window that never arrives counts as a miss.  Per source they must be
+ *                  strictly increasing over the tracker's life, until bn_track_reset.
+ *   Flush / reset  bn_track_flush closes every open event of a source (or of all: source -1) under the same min_hits rule: end of
+ *                  stream.  The source's last window stays.  bn_track_reset forgets a source's open events and its last window.
+ *   Events         an update's (a step's, a flush's) events reach the caller sorted by (source, species, first_window); that key is
+ *                  unique.  At most max_events (given at creation) are kept per update: the rest are counted in `dropped` and
+ *                  lost, which ones is unspecified; with dropped == 0 the list is fully determined.
+ *   Bits           an event depends only on that (source, species)'s sequence of (k, logit, prior row) and the configuration: not
+ *                  on how windows were batched into steps, on a row's position, on the context that ran the step or on the entry
+ *                  point.  Two runs give the same bytes.  No floating-point atomics; integer atomics only reserve output slots.
+ *   Step           bn_ctx_attach_track makes every later bn_step_windows / bn_step_live of the context also update the tracker,
+ *                  on the context's stream, after the plan, the step's own top-K, the head and the prior, outside the captured
+ *                  plan graph (capture_fallbacks stays 0).  Row i of bn_step_windows is window first_window + i of the context's
+ *                  source (bn_ctx_track_source, 0 after every attach); row i of bn_step_live is window window_out[i] of source
+ *                  source_out[i].  bn_step_device rows carry no window number and are not tracked.  Sources and windows reach
+ *                  the device in pinned memory the kernel reads in place.  Under BN_TRACK_PRIOR the rows' sites are those the
+ *                  attached prior gives them.  The step's own outputs, head rows and prior rows are unchanged, bit for bit.
+ *   Ordering       updates are applied in the order the step calls are made (a live pool: the scheduling order).  The tracker
+ *                  keeps the event of its last update; every update makes its stream wait for it and records a new one, so
+ *                  several contexts stepping one pool with sync = 0 serialise their tracker kernels only, not their plans.
+ *   Stale rows     a bn_step_live row whose window does not exceed its source's last has already been taken from the pool: it is
+ *                  skipped and counted in stale_rows.  This arises only after bn_live_reset without bn_track_reset.
+ *   Refusals       BN_ERR_INVALID_ARG with a message, nothing changed: NULL where data is required, zero sizes, a non-finite
+ *                  enter_conf, min_hits == 0, unknown flags, n_species != the model's at attach, another device, a source out of
+ *                  range, a live pool with more sources than the tracker, BN_TRACK_PRIOR without a prior (passed or attached),
+ *                  bn_track_update_host rows that do not increase per source, a bn_step_windows whose first window does not
+ *                  exceed the source's last (refused before anything runs).  Without a gfx950 device create, update and flush
+ *                  return BN_ERR_NO_DEVICE.
+ *   Lifetime       a context that attached a tracker keeps it alive: bn_track_free and bn_ctx_destroy may come in either order.
+ *   Threading      one thread at a time per tracker (and the contexts it is attached to).
+ */
+typedef struct bn_track bn_track;
+#define BN_TRACK_PRIOR 1u /* hits are those of admitted species, on the prior's conf' */
+typedef struct bn_event {
+    int32_t source;
+    uint32_t species;
+    uint32_t first_window; /* first HIT window */
+    uint32_t last_window;  /* last HIT window */
+    uint32_t hits;
+    uint32_t peak_window;
+    float peak_conf;
+    float mean_conf; /* sum / (float)hits, one f32 divide */
+} bn_event;
+bn_status bn_track_create(int32_t device, size_t n_sources, size_t n_species, float enter_conf, uint32_t min_hits, uint32_t max_gap,
+                          size_t max_events, uint32_t flags, bn_track **out);
+void bn_track_free(bn_track *t);
+size_t bn_track_sources(const bn_track *t);
+size_t bn_track_species(const bn_track *t);
+/* diagnostic: open events of a source (source -1: of all), every pending update waited for; 0 for a NULL tracker or a source out
+ * of range */
+size_t bn_track_open_events(const bn_track *t, int32_t source);
+/* ONE update, by the step's kernel, on host logits [rows * n_species]: row r is window windows[r] of source sources[r], at site
+ * sites[r] of `prior` under BN_TRACK_PRIOR (both may be NULL without it).  The first min(events, cap) events of the sorted list go
+ * to events_out, *n_out of them; *dropped counts the rest. */
+bn_status bn_track_update_host(bn_track *t, const float *logits, size_t rows, const int32_t *sources, const uint64_t *windows,
+                               const bn_prior *prior, const int32_t *sites, bn_event *events_out, size_t cap, size_t *n_out,
+                               size_t *dropped);
+bn_status bn_track_flush(bn_track *t, int32_t source, bn_event *events_out, size_t cap, size_t *n_out, size_t *dropped);
+bn_status bn_track_reset(bn_track *t, int32_t source);
+/* t == NULL detaches */
+bn_status bn_ctx_attach_track(bn_ctx *c, bn_track *t);
+/* the source of every row of bn_step_windows */
+bn_status bn_ctx_track_source(bn_ctx *c, int32_t source);
+/* pinned host view of the events of the last tracked step, sorted; valid after bn_ctx_synchronize until the next step.  Any
+ * output may be NULL. */
+bn_status bn_step_track_results(bn_ctx *c, const bn_event **events, size_t *n, size_t *dropped, size_t *stale_rows);
+
+/*
  * Live ingest: a device-resident pool of per-source ring buffers for continuous audio (many recorders, each producing a
  * window every `step` seconds).  Callers push PCM as it arrives, in the storage format (i16: half the PCIe bytes, and no
  * overlap sample crosses the bus twice); bn_step_live batches the ready windows of ALL sources into one context batch, cut on

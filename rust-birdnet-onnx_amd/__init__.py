@@ -58,6 +58,8 @@ ENGINE_SYMBOLS = [
     "bn_head_fit", "bn_head_fit_index", "bn_ctx_attach_head", "bn_step_head_results",
     "bn_prior_create", "bn_prior_free", "bn_prior_sites", "bn_prior_species", "bn_prior_threshold", "bn_prior_flags", "bn_prior_read",
     "bn_prior_apply_host", "bn_ctx_attach_prior", "bn_ctx_prior_site", "bn_step_prior_results",
+    "bn_track_create", "bn_track_free", "bn_track_sources", "bn_track_species", "bn_track_open_events", "bn_track_update_host",
+    "bn_track_flush", "bn_track_reset", "bn_ctx_attach_track", "bn_ctx_track_source", "bn_step_track_results",
     "bn_live_create", "bn_live_free", "bn_live_push", "bn_live_push_many", "bn_live_close", "bn_live_reset", "bn_live_ready",
     "bn_live_room", "bn_live_event_count", "bn_live_read_window", "bn_step_live",
     "bn_live_create_rates", "bn_live_resampled_samples", "bn_live_source_rate",
@@ -116,7 +118,18 @@ class BnHeadFitReport(C.Structure):
 BN_HEAD_L2NORM = 1
 BN_PRIOR_UNKNOWN = -1.0  # table entry of a species the meta model does not know
 BN_PRIOR_SELECT, BN_PRIOR_AFTER_TOPK, BN_PRIOR_RERANK = 0, 1, 2
+BN_TRACK_PRIOR = 1  # bn_track_create flag: hits are those of admitted species, on the prior's conf'
 BN_ABI_VERSION = 2  # include/birdnet_hip.h
+
+
+class BnEvent(C.Structure):
+    _fields_ = [("source", C.c_int32), ("species", C.c_uint32), ("first_window", C.c_uint32), ("last_window", C.c_uint32),
+                ("hits", C.c_uint32), ("peak_window", C.c_uint32), ("peak_conf", C.c_float), ("mean_conf", C.c_float)]
+
+
+# bn_event as a numpy record: arrays of it are what Tracker and Context.step_track_results return
+EVENT_DTYPE = np.dtype([("source", np.int32), ("species", np.uint32), ("first_window", np.uint32), ("last_window", np.uint32),
+                        ("hits", np.uint32), ("peak_window", np.uint32), ("peak_conf", np.float32), ("mean_conf", np.float32)])
 
 
 class BnhError(C.Structure):
@@ -222,6 +235,18 @@ def _load() -> C.CDLL:
         "bn_ctx_attach_prior": (i32, [vp, vp, C.POINTER(C.c_int32), sz, sz, i32, C.c_float]),
         "bn_ctx_prior_site": (i32, [vp, i32]),
         "bn_step_prior_results": (i32, [vp, C.POINTER(u32p), C.POINTER(f32p), C.POINTER(u32p), C.POINTER(sz)]),
+        "bn_track_create": (i32, [i32, sz, sz, C.c_float, C.c_uint32, C.c_uint32, sz, C.c_uint32, C.POINTER(vp)]),
+        "bn_track_free": (None, [vp]),
+        "bn_track_sources": (sz, [vp]),
+        "bn_track_species": (sz, [vp]),
+        "bn_track_open_events": (sz, [vp, i32]),
+        "bn_track_update_host": (i32, [vp, f32p, sz, C.POINTER(C.c_int32), C.POINTER(C.c_uint64), vp, C.POINTER(C.c_int32), C.POINTER(BnEvent), sz,
+                                       C.POINTER(sz), C.POINTER(sz)]),
+        "bn_track_flush": (i32, [vp, i32, C.POINTER(BnEvent), sz, C.POINTER(sz), C.POINTER(sz)]),
+        "bn_track_reset": (i32, [vp, i32]),
+        "bn_ctx_attach_track": (i32, [vp, vp]),
+        "bn_ctx_track_source": (i32, [vp, i32]),
+        "bn_step_track_results": (i32, [vp, C.POINTER(C.POINTER(BnEvent)), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]),
         "bn_live_create": (i32, [i32, i32, i32, sz, sz, sz, C.POINTER(vp)]),
         "bn_live_create_rates": (i32, [i32, i32, i32, sz, sz, sz, C.c_uint32, u32p, C.c_uint32, C.POINTER(vp)]),
         "bn_live_resampled_samples": (sz, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, i32]),
@@ -960,6 +985,34 @@ class Context:
             raise EngineError(st)
         return _step_arrays(batch, ks.value, ix, cf, ct)
 
+    def attach_track(self, tracker: Optional["Tracker"]):
+        """bn_ctx_attach_track: every later step_windows / step_live of this context also updates the tracker with that step's rows
+        (None detaches).  Rows of step_windows are windows first + i of the context's source (set_track_source, 0 after every attach);
+        rows of step_live carry their own source and window."""
+        st = lib.bn_ctx_attach_track(self._h, None if tracker is None else tracker._h)
+        if st:
+            raise EngineError(st)
+        self._track = tracker
+
+    def set_track_source(self, source: int):
+        """bn_ctx_track_source: the source of every row of step_windows."""
+        st = lib.bn_ctx_track_source(self._h, source)
+        if st:
+            raise EngineError(st)
+
+    def step_track_results(self):
+        """(events, dropped, stale_rows) of the last tracked step, after synchronize(): the events that step closed as an EVENT_DTYPE
+        array sorted by (source, species, first_window), the number lost to the tracker's max_events, and the live rows skipped
+        because their window did not exceed their source's last."""
+        ev, n, dr, stale = C.POINTER(BnEvent)(), C.c_size_t(), C.c_size_t(), C.c_size_t()
+        st = lib.bn_step_track_results(self._h, C.byref(ev), C.byref(n), C.byref(dr), C.byref(stale))
+        if st:
+            raise EngineError(st)
+        out = np.empty(n.value, dtype=EVENT_DTYPE)
+        if n.value:
+            C.memmove(out.ctypes.data, ev, n.value * C.sizeof(BnEvent))
+        return out, int(dr.value), int(stale.value)
+
     def attach_head(self, head: Optional["Head"], top_k: int = 10, min_confidence: Optional[float] = None):
         """bn_ctx_attach_head: every later step of this context also runs `head` on the step's embedding rows (None detaches)."""
         st = lib.bn_ctx_attach_head(self._h, None if head is None else head._h, top_k, *_min_args(min_confidence))
@@ -1339,6 +1392,83 @@ class Prior:
         if st:
             raise EngineError(st)
         return idx, conf, cnt
+
+
+class Tracker:
+    """bn_track: detection events on the device -- one record per (source, species), updated with the logits row of every window of
+    every source, emitting finished events only: species j was heard at source s from first_window to last_window, `hits` times,
+    with a peak and a mean confidence.  A window is a hit when its confidence is at least enter_conf; an event closes after more
+    than max_gap missed windows and is emitted with at least min_hits hits.  `update(logits, sources, windows)` on host rows,
+    `Context.attach_track` for every step of a context; `flush` at end of stream.  use_prior: hits are those of the species a Prior
+    admits, on its (reranked) confidence.  Events come back as EVENT_DTYPE arrays sorted by (source, species, first_window)."""
+
+    def __init__(self, device: int, n_sources: int, n_species: int, enter_conf: float, min_hits: int = 1, max_gap: int = 0, max_events: int = 4096,
+                 use_prior: bool = False, flags: Optional[int] = None):
+        if flags is None:
+            flags = BN_TRACK_PRIOR if use_prior else 0
+        h = C.c_void_p()
+        st = lib.bn_track_create(device, n_sources, n_species, C.c_float(enter_conf), min_hits, max_gap, max_events, flags, C.byref(h))
+        if st:
+            raise EngineError(st)
+        self._h, self.max_events = h, max_events
+
+    def __del__(self):
+        if getattr(self, "_h", None) and lib is not None:
+            lib.bn_track_free(self._h)
+            self._h = None
+
+    def close(self):
+        self.__del__()
+
+    @property
+    def n_sources(self) -> int:
+        return int(lib.bn_track_sources(self._h))
+
+    @property
+    def n_species(self) -> int:
+        return int(lib.bn_track_species(self._h))
+
+    def open_events(self, source: int = -1) -> int:
+        """bn_track_open_events: (source, species) records with an open event, of one source or of all."""
+        return int(lib.bn_track_open_events(self._h, source))
+
+    def update(self, logits, sources, windows, prior: Optional["Prior"] = None, sites=None, cap: Optional[int] = None):
+        """bn_track_update_host: one update with host logits [rows, n_species], row r being window windows[r] of source sources[r] (at
+        site sites[r] of `prior` under use_prior).  Returns (events, dropped)."""
+        x = np.ascontiguousarray(logits, dtype=np.float32).reshape(-1, self.n_species)
+        sv = np.ascontiguousarray(sources, dtype=np.int32).reshape(-1)
+        wv = np.ascontiguousarray(windows, dtype=np.uint64).reshape(-1)
+        if sv.shape[0] != x.shape[0] or wv.shape[0] != x.shape[0]:
+            raise ValueError("one source and one window per row")
+        tv = None if sites is None else np.ascontiguousarray(sites, dtype=np.int32).reshape(-1)
+        if tv is not None and tv.shape[0] != x.shape[0]:
+            raise ValueError("one site per row")
+        cap = self.max_events if cap is None else cap
+        out = np.empty(max(cap, 1), dtype=EVENT_DTYPE)
+        n, dr = C.c_size_t(), C.c_size_t()
+        st = lib.bn_track_update_host(self._h, x.ctypes.data_as(C.POINTER(C.c_float)), x.shape[0], sv.ctypes.data_as(C.POINTER(C.c_int32)),
+                                      wv.ctypes.data_as(C.POINTER(C.c_uint64)), None if prior is None else prior._h,
+                                      None if tv is None else tv.ctypes.data_as(C.POINTER(C.c_int32)), out.ctypes.data_as(C.POINTER(BnEvent)), cap,
+                                      C.byref(n), C.byref(dr))
+        if st:
+            raise EngineError(st)
+        return out[:n.value].copy(), int(dr.value)
+
+    def flush(self, source: int = -1, cap: Optional[int] = None):
+        """bn_track_flush: close every open event of a source (-1: of all sources).  Returns (events, dropped)."""
+        cap = self.max_events if cap is None else cap
+        out = np.empty(max(cap, 1), dtype=EVENT_DTYPE)
+        n, dr = C.c_size_t(), C.c_size_t()
+        st = lib.bn_track_flush(self._h, source, out.ctypes.data_as(C.POINTER(BnEvent)), cap, C.byref(n), C.byref(dr))
+        if st:
+            raise EngineError(st)
+        return out[:n.value].copy(), int(dr.value)
+
+    def reset(self, source: int):
+        """bn_track_reset: forget the source's open events and its last window."""
+        st = lib.bn_track_reset(self._h, source)
+        if st:
+            raise EngineError(st)
 
 
 class Live:

@@ -171,6 +171,12 @@ struct bn_ctx {
     bn::TopkRows step;
     bn::HeadAttach *head = nullptr;  // bn_ctx_attach_head: run after every step's own work (head.hip)
     bn::PriorAttach *prior = nullptr;  // bn_ctx_attach_prior: the same, on the step's logits rows (prior.hip)
+    bn::TrackAttach *track = nullptr;  // bn_ctx_attach_track: the same, for the steps whose rows carry window numbers (track.hip)
+    // the (source, window) of the rows of the bn_step_device call in progress, set by bn_step_windows / bn_step_live around it
+    bool trk_rows = false;
+    const int32_t *trk_sources = nullptr;  // NULL: every row at the attachment's source
+    const uint64_t *trk_windows = nullptr;  // NULL: row i is window trk_first + i
+    uint64_t trk_first = 0;
     // ---- asynchronous host-slice path (bn_infer_submit / bn_infer_collect): a ring of two batches per context.
     // Both slots own their device input, pinned input and pinned output buffers (allocated on first use), so a ticket
     // in flight shares nothing with the synchronous entry points (bn_infer_windows / bn_step_*) but the arena and the
@@ -723,6 +729,7 @@ void bn_ctx_destroy(bn_ctx *c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     bn::head_detach(c->head);
     bn::prior_detach(c->prior);
+    bn::track_detach(c->track);
     for (auto &kv : c->graphs) (void)gated::GraphExecDestroy(kv.second);
     if (c->d_arena) (void)gated::Free(c->d_arena);
     if (c->d_input) (void)gated::Free(c->d_input);
@@ -1260,6 +1267,10 @@ bn_status bn_step_device(bn_ctx *c, const float *d_pcm, size_t batch, size_t top
         st = bn::prior_step(c->prior, c->stream, d_logits, batch, TopkRows::view(static_cast<const uint32_t *>(c->step.d), batch, k));
         if (st != BN_OK) return st;
     }
+    if (c->track && c->trk_rows) {
+        st = bn::track_step(c->track, c->stream, d_logits, batch, c->trk_sources, c->trk_windows, c->trk_first, c->prior);
+        if (st != BN_OK) return st;
+    }
     if (sync) BN_HIP_TRY(hipStreamSynchronize(c->stream));
     return BN_OK;
 }
@@ -1307,6 +1318,30 @@ bn_status bn_step_prior_results(const bn_ctx *c, const uint32_t **idx, const flo
     if (!c) return fail(BN_ERR_INVALID_ARG, "null context");
     if (!c->prior) return fail(BN_ERR_INVALID_ARG, "no prior is attached to this context");
     return bn::prior_step_results(c->prior, idx, conf, count, k_stride);
+}
+
+bn_status bn_ctx_attach_track(bn_ctx *c, bn_track *t) {
+    if (!c) return fail(BN_ERR_INVALID_ARG, "null context");
+    BN_HIP_TRY(bn::use_device(c->model->device));
+    bn::TrackAttach *a = nullptr;
+    if (t) {
+        const size_t n = (size_t)c->pd->plan->outputs[c->model->cfg.logits_output].row_elems;
+        bn_status st = bn::track_attach(t, c->model->device, n, c->max_batch, &a);
+        if (st != BN_OK) return st;
+    }
+    return install_attachment(c->stream, c->track, a, bn::track_detach);
+}
+
+bn_status bn_ctx_track_source(bn_ctx *c, int32_t source) {
+    if (!c) return fail(BN_ERR_INVALID_ARG, "null context");
+    if (!c->track) return fail(BN_ERR_INVALID_ARG, "no tracker is attached to this context");
+    return bn::track_set_source(c->track, source);
+}
+
+bn_status bn_step_track_results(bn_ctx *c, const bn_event **events, size_t *n, size_t *dropped, size_t *stale_rows) {
+    if (!c) return fail(BN_ERR_INVALID_ARG, "null context");
+    if (!c->track) return fail(BN_ERR_INVALID_ARG, "no tracker is attached to this context");
+    return bn::track_step_results(c->track, events, n, dropped, stale_rows);
 }
 
 bn_status bn_step_results(const bn_ctx *c, const float **logits, const uint32_t **idx, const float **conf, const uint32_t **count, size_t *k_stride) {
@@ -1681,6 +1716,7 @@ bn_status bn_step_windows(bn_ctx *c, const bn_recording *r, size_t step_samples,
     if (count == 0) return BN_OK;
     if (count > c->max_batch) return fail(BN_ERR_INVALID_ARG, "batch size " + std::to_string(count) + " exceeds context max " + std::to_string(c->max_batch));
     if (r->device != c->model->device) return fail(BN_ERR_INVALID_ARG, "recording and context live on different devices");
+    if (c->track && (st = bn::track_step_check(c->track, c->prior, 0, first_window, count)) != BN_OK) return st;
     BN_HIP_TRY(bn::use_device(c->model->device));
     (void)hipGetLastError();
     // stream order keeps this behind whatever the context still has in flight
@@ -1688,7 +1724,13 @@ bn_status bn_step_windows(bn_ctx *c, const bn_recording *r, size_t step_samples,
                    (uint32_t)count);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(BN_ERR_BACKEND, std::string("window kernel launch failed: ") + hipGetErrorString(e));
-    return bn_step_device(c, c->d_input, count, top_k, has_min, min_conf, sync);
+    c->trk_rows = true;  // row i is window first_window + i of the tracker attachment's source
+    c->trk_sources = nullptr;
+    c->trk_windows = nullptr;
+    c->trk_first = first_window;
+    st = bn_step_device(c, c->d_input, count, top_k, has_min, min_conf, sync);
+    c->trk_rows = false;
+    return st;
 }
 
 size_t bn_model_survey(const char *onnx_path, char *buf, size_t cap, bn_status *status) {
@@ -1875,6 +1917,15 @@ size_t bn_last_error(char *buf, size_t cap) {
 bn_status bn::set_last_error(bn_status st, const std::string &msg) { return fail(st, msg); }
 
 bn::PriorAttach *bn::ctx_prior(bn_ctx *c) { return c ? c->prior : nullptr; }
+
+bn::TrackAttach *bn::ctx_track(bn_ctx *c) { return c ? c->track : nullptr; }
+
+void bn::ctx_track_rows(bn_ctx *c, const int32_t *sources, const uint64_t *windows) {
+    c->trk_rows = sources != nullptr;
+    c->trk_sources = sources;
+    c->trk_windows = windows;
+    c->trk_first = 0;
+}
 
 bn_status bn::ctx_embedding(const bn_ctx *c, CtxEmbedding *out) {
     if (!c || !out) return fail(BN_ERR_INVALID_ARG, "null argument");

@@ -1,6 +1,6 @@
 // What the translation units of the C ABI share: the plumbing every entry point repeats (the error macro, launch and device checks,
 // the packed top-K block TopkRows, results_to_host, scoped scratch: step_common.cpp) and what they need of capi.cpp's private state
-// (index.hip: bn_index_*; head.hip: bn_head_*) and of each other (prior.hip: bn_prior_*).
+// (index.hip: bn_index_*; head.hip: bn_head_*) and of each other (prior.hip: bn_prior_*; track.hip: bn_track_*).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -163,4 +163,34 @@ bn_status prior_step(PriorAttach *a, hipStream_t stream, const float *d_logits, 
 bn_status prior_step_results(const PriorAttach *a, const uint32_t **idx, const float **conf, const uint32_t **count, size_t *k_stride);
 // capi.cpp -> live.cpp: the context's attached prior, NULL if none
 PriorAttach *ctx_prior(bn_ctx *c);
+// prior.hip -> track.hip: what a kernel needs of a prior's table (rows padded to tstride floats)
+struct PriorView {
+    int device;
+    const float *d_table;
+    size_t n_sites, n_species, tstride;
+    float threshold;
+    int rerank;
+};
+PriorView prior_view(const bn_prior *p);
+// the prior of an attachment (NULL attachment: NULL) and the site of one of its rows: the map's for `source` of a live step under a
+// map, else the context's site
+const bn_prior *prior_of(const PriorAttach *a);
+int32_t prior_site_of(const PriorAttach *a, int32_t source);
+// track.hip -> capi.cpp / live.cpp: a tracker attached to a context (its own pinned row lists and event lists; holds a reference)
+struct TrackAttach;
+bn_status track_attach(bn_track *t, int device, size_t num_species, size_t max_batch, TrackAttach **out);
+void track_detach(TrackAttach *a);  // the context's stream must be idle
+bn_status track_set_source(TrackAttach *a, int32_t source);
+// the refusals of a step that need nothing of the step: BN_TRACK_PRIOR without an attached prior; bn_step_live (n_sources > 0): a pool
+// with more sources than the tracker; bn_step_windows (count > 0): a first window that does not exceed the source's last
+bn_status track_step_check(const TrackAttach *a, const PriorAttach *prior, size_t n_sources, uint64_t first_window, size_t count);
+// the tracker's update for the step's rows + its event list to pinned memory, enqueued on the context's stream behind the step's own
+// work; row i is window windows[i] of sources[i] (bn_step_live) or, with sources == NULL, window first_window + i of the
+// attachment's source (bn_step_windows)
+bn_status track_step(TrackAttach *a, hipStream_t stream, const float *d_logits, size_t batch, const int32_t *sources, const uint64_t *windows,
+                     uint64_t first_window, const PriorAttach *prior);
+bn_status track_step_results(TrackAttach *a, const bn_event **events, size_t *n, size_t *dropped, size_t *stale_rows);
+// capi.cpp -> live.cpp: the context's attached tracker, NULL if none; the rows of the step bn_step_live is about to run
+TrackAttach *ctx_track(bn_ctx *c);
+void ctx_track_rows(bn_ctx *c, const int32_t *sources, const uint64_t *windows);
 }  // namespace bn

@@ -36,6 +36,7 @@
 #include "capi_internal.h"
 #include "hip_gate.h"
 #include "kernels.h"
+#include "prior_rules.h"
 #include "sigmoid_ref.h"
 
 namespace bn {
@@ -80,9 +81,6 @@ __device__ __forceinline__ float4 load4(const float *p) {
     return make_float4(p[0], p[1], p[2], p[3]);
 }
 
-__device__ __forceinline__ bool admitted(float p, float thr) { return p < 0.0f || p >= thr; }
-// conf' of the contract: one f32 multiply when reranking a known species (the file is compiled with -ffp-contract=off)
-__device__ __forceinline__ float prior_conf(float conf, float p, int rerank) { return (rerank && p >= 0.0f) ? conf * p : conf; }
 __device__ __forceinline__ uint32_t select_key(float z, float p, float thr, int rerank, uint32_t &adm) {
     adm = admitted(p, thr) ? 1u : 0u;
     const float c = prior_conf(sigmoid_ref(z), p, rerank);
@@ -572,6 +570,17 @@ bn_status bn::prior_step(PriorAttach *a, hipStream_t stream, const float *d_logi
     if ((st = bn::results_to_host(stream, &reg, 1)) != BN_OK) return st;
     a->rows.mark(batch, k);
     return BN_OK;
+}
+
+bn::PriorView bn::prior_view(const bn_prior *p) {
+    return PriorView{p->device, p->d_table, p->n_sites, p->n_species, p->tstride, p->threshold, (p->flags & BN_PRIOR_RERANK) ? 1 : 0};
+}
+
+const bn_prior *bn::prior_of(const PriorAttach *a) { return a ? a->prior : nullptr; }
+
+int32_t bn::prior_site_of(const PriorAttach *a, int32_t source) {
+    if (a->has_map && source >= 0 && (size_t)source < a->source_sites.size()) return a->source_sites[(size_t)source];
+    return a->site;
 }
 
 bn_status bn::prior_step_results(const PriorAttach *a, const uint32_t **idx, const float **conf, const uint32_t **count, size_t *k_stride) {
