@@ -172,11 +172,6 @@ struct bn_ctx {
     bn::HeadAttach *head = nullptr;  // bn_ctx_attach_head: run after every step's own work (head.hip)
     bn::PriorAttach *prior = nullptr;  // bn_ctx_attach_prior: the same, on the step's logits rows (prior.hip)
     bn::TrackAttach *track = nullptr;  // bn_ctx_attach_track: the same, for the steps whose rows carry window numbers (track.hip)
-    // the (source, window) of the rows of the bn_step_device call in progress, set by bn_step_windows / bn_step_live around it
-    bool trk_rows = false;
-    const int32_t *trk_sources = nullptr;  // NULL: every row at the attachment's source
-    const uint64_t *trk_windows = nullptr;  // NULL: row i is window trk_first + i
-    uint64_t trk_first = 0;
     // ---- asynchronous host-slice path (bn_infer_submit / bn_infer_collect): a ring of two batches per context.
     // Both slots own their device input, pinned input and pinned output buffers (allocated on first use), so a ticket
     // in flight shares nothing with the synchronous entry points (bn_infer_windows / bn_step_*) but the arena and the
@@ -1230,8 +1225,11 @@ static bn_status ensure_step_block(bn_ctx *c, size_t k) {
     return c->step.reserve(c->max_batch, k, c->stream, true, true);
 }
 
-bn_status bn_step_device(bn_ctx *c, const float *d_pcm, size_t batch, size_t top_k, int32_t has_min, float min_conf, int32_t sync) {
+}  // extern "C"
+
+bn_status bn::step_device(bn_ctx *c, const float *d_pcm, const StepRows &rows, size_t top_k, int32_t has_min, float min_conf, int32_t sync) {
     if (!c) return fail(BN_ERR_INVALID_ARG, "null context");
+    const size_t batch = rows.batch;
     if (batch == 0) return BN_OK;
     if (!d_pcm || batch > c->max_batch) return fail(BN_ERR_INVALID_ARG, "bad input / batch size exceeds context max");
     if (reinterpret_cast<uintptr_t>(d_pcm) & 15u) return fail(BN_ERR_INVALID_ARG, "device input must be 16-byte aligned");
@@ -1264,15 +1262,21 @@ bn_status bn_step_device(bn_ctx *c, const float *d_pcm, size_t batch, size_t top
         if (st != BN_OK) return st;
     }
     if (c->prior) {
-        st = bn::prior_step(c->prior, c->stream, d_logits, batch, TopkRows::view(static_cast<const uint32_t *>(c->step.d), batch, k));
+        st = bn::prior_step(c->prior, c->stream, d_logits, TopkRows::view(static_cast<const uint32_t *>(c->step.d), batch, k), rows);
         if (st != BN_OK) return st;
     }
-    if (c->track && c->trk_rows) {
-        st = bn::track_step(c->track, c->stream, d_logits, batch, c->trk_sources, c->trk_windows, c->trk_first, c->prior);
+    if (c->track && rows.numbered) {
+        st = bn::track_step(c->track, c->stream, d_logits, rows, c->prior);
         if (st != BN_OK) return st;
     }
     if (sync) BN_HIP_TRY(hipStreamSynchronize(c->stream));
     return BN_OK;
+}
+
+extern "C" {
+
+bn_status bn_step_device(bn_ctx *c, const float *d_pcm, size_t batch, size_t top_k, int32_t has_min, float min_conf, int32_t sync) {
+    return bn::step_device(c, d_pcm, bn::StepRows{batch, false, nullptr, nullptr, 0}, top_k, has_min, min_conf, sync);
 }
 
 bn_status bn_ctx_attach_head(bn_ctx *c, bn_head *h, size_t top_k, int32_t has_min, float min_conf) {
@@ -1716,7 +1720,7 @@ bn_status bn_step_windows(bn_ctx *c, const bn_recording *r, size_t step_samples,
     if (count == 0) return BN_OK;
     if (count > c->max_batch) return fail(BN_ERR_INVALID_ARG, "batch size " + std::to_string(count) + " exceeds context max " + std::to_string(c->max_batch));
     if (r->device != c->model->device) return fail(BN_ERR_INVALID_ARG, "recording and context live on different devices");
-    if (c->track && (st = bn::track_step_check(c->track, c->prior, 0, first_window, count)) != BN_OK) return st;
+    if ((st = bn::ctx_step_check(c, 0, first_window, count)) != BN_OK) return st;
     BN_HIP_TRY(bn::use_device(c->model->device));
     (void)hipGetLastError();
     // stream order keeps this behind whatever the context still has in flight
@@ -1724,13 +1728,8 @@ bn_status bn_step_windows(bn_ctx *c, const bn_recording *r, size_t step_samples,
                    (uint32_t)count);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(BN_ERR_BACKEND, std::string("window kernel launch failed: ") + hipGetErrorString(e));
-    c->trk_rows = true;  // row i is window first_window + i of the tracker attachment's source
-    c->trk_sources = nullptr;
-    c->trk_windows = nullptr;
-    c->trk_first = first_window;
-    st = bn_step_device(c, c->d_input, count, top_k, has_min, min_conf, sync);
-    c->trk_rows = false;
-    return st;
+    // row i is window first_window + i of the tracker attachment's source
+    return bn::step_device(c, c->d_input, bn::StepRows{count, true, nullptr, nullptr, first_window}, top_k, has_min, min_conf, sync);
 }
 
 size_t bn_model_survey(const char *onnx_path, char *buf, size_t cap, bn_status *status) {
@@ -1916,15 +1915,10 @@ size_t bn_last_error(char *buf, size_t cap) {
 
 bn_status bn::set_last_error(bn_status st, const std::string &msg) { return fail(st, msg); }
 
-bn::PriorAttach *bn::ctx_prior(bn_ctx *c) { return c ? c->prior : nullptr; }
-
-bn::TrackAttach *bn::ctx_track(bn_ctx *c) { return c ? c->track : nullptr; }
-
-void bn::ctx_track_rows(bn_ctx *c, const int32_t *sources, const uint64_t *windows) {
-    c->trk_rows = sources != nullptr;
-    c->trk_sources = sources;
-    c->trk_windows = windows;
-    c->trk_first = 0;
+bn_status bn::ctx_step_check(const bn_ctx *c, size_t n_sources, uint64_t first_window, size_t count) {
+    bn_status st = c->prior ? bn::prior_step_check(c->prior, n_sources) : BN_OK;
+    if (st == BN_OK && c->track) st = bn::track_step_check(c->track, c->prior, n_sources, first_window, count);
+    return st;
 }
 
 bn_status bn::ctx_embedding(const bn_ctx *c, CtxEmbedding *out) {

@@ -1,6 +1,7 @@
 // What the translation units of the C ABI share: the plumbing every entry point repeats (the error macro, launch and device checks,
-// the packed top-K block TopkRows, results_to_host, scoped scratch: step_common.cpp) and what they need of capi.cpp's private state
-// (index.hip: bn_index_*; head.hip: bn_head_*) and of each other (prior.hip: bn_prior_*; track.hip: bn_track_*).
+// the packed top-K block TopkRows, results_to_host, the pinned ring PinnedRing, scoped scratch: step_common.cpp), what they need of
+// capi.cpp's private state (index.hip: bn_index_*; head.hip: bn_head_*; live.cpp: bn_step_live) and of each other (prior.hip:
+// bn_prior_*; track.hip: bn_track_*).  A step's rows reach its stages as an argument (StepRows), never through a context's state.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -80,6 +81,23 @@ bn_status results_to_host(hipStream_t stream, const OutRegion *regs, int n);
 bn_status enqueue_topk_rows(hipStream_t stream, const float *d_logits, size_t rows, size_t n, size_t k, int32_t has_min, float min_conf,
                             const TopkRows::View &out, uint32_t *d_flags);
 
+// Four pinned blocks of one size in rotation, for lists the host writes per step and a kernel reads in place (no copy): a block is
+// rewritten only after the work that read it has completed (its event).  acquire, fill, enqueue the reader, commit; a slot that was
+// acquired but not committed (the enqueue failed) is the next acquire's.
+struct PinnedRing {
+    static constexpr int SLOTS = 4;
+    void *h[SLOTS] = {}, *d[SLOTS] = {};  // a block and its device alias
+    hipEvent_t ev[SLOTS] = {};
+    bool busy[SLOTS] = {};  // ev was recorded behind a reader of the block
+    int next = 0;
+
+    hipError_t create(size_t bytes);  // empty on failure
+    void release();
+    hipError_t acquire(int *slot, void **host);  // waits for the slot's last reader
+    void *device_ptr(int slot) const { return d[slot]; }
+    hipError_t commit(int slot, hipStream_t stream);  // the event behind what was just enqueued on `stream`; advances the ring
+};
+
 // device buffers, one pinned buffer and a stream of one call: on every way out the stream is waited for, the buffers freed and the
 // stream, if owned, destroyed
 struct Scratch {
@@ -111,6 +129,19 @@ struct CtxEmbedding {
     size_t last_batch = 0;
 };
 bn_status ctx_embedding(const bn_ctx *c, CtxEmbedding *out);
+// The identity of a step's rows, for the stages that need it (prior: the site of a row; tracker: its source and window)
+struct StepRows {
+    size_t batch;
+    bool numbered;            // false: plain bn_step_device, the tracker is not run
+    const int32_t *sources;   // NULL: every row belongs to the attachment's source / the context's site
+    const uint64_t *windows;  // NULL: row i is window first_window + i
+    uint64_t first_window;
+};
+// the body of bn_step_device, bn_step_windows and bn_step_live
+bn_status step_device(bn_ctx *c, const float *d_pcm, const StepRows &rows, size_t top_k, int32_t has_min, float min_conf, int32_t sync);
+// the refusals of bn_step_windows (n_sources == 0) and bn_step_live (count == 0) that the attached prior and tracker make, before
+// anything is enqueued or taken from a pool: prior_step_check, track_step_check
+bn_status ctx_step_check(const bn_ctx *c, size_t n_sources, uint64_t first_window, size_t count);
 // what bn_step_live needs of a context: its device, stream and input buffer [max_batch, sample_count]; BN_ERR_INVALID_ARG
 // (message set) for a top_k that bn_step_device would refuse
 struct CtxStepInput {
@@ -146,23 +177,19 @@ void head_detach(HeadAttach *a);  // the context's stream must be idle
 bn_status head_step(HeadAttach *a, hipStream_t stream, const float *d_emb, size_t batch);
 bn_status head_step_results(const HeadAttach *a, const float **logits, const uint32_t **idx, const float **conf, const uint32_t **count,
                             size_t *k_stride, size_t *n_classes);
-// prior.hip -> capi.cpp / live.cpp: a prior attached to a context (its own result buffers; holds a reference to the prior)
+// prior.hip -> capi.cpp: a prior attached to a context (its own result buffers; holds a reference to the prior)
 struct PriorAttach;
 bn_status prior_attach(bn_prior *p, int device, size_t num_species, size_t max_batch, const int32_t *source_sites, size_t n_source_sites, size_t top_k,
                        int32_t has_min, float min_conf, PriorAttach **out);
 void prior_detach(PriorAttach *a);  // the context's stream must be idle
 bn_status prior_set_site(PriorAttach *a, int32_t site);
-// bn_step_live: refuses a pool with more sources than the attached map, before anything is taken from the pool
-bn_status prior_live_check(const PriorAttach *a, size_t n_sources);
-// bn_step_live: the sites of the coming step's rows (by source) into the next pinned block; prior_step consumes it
-bn_status prior_stage_rows(PriorAttach *a, const int32_t *sources, size_t rows);
-void prior_clear_rows(PriorAttach *a);
-// the prior kernel + results to pinned memory, enqueued on the context's stream behind the step's own top-K;
+// refuses a pool with more sources than the attached map
+bn_status prior_step_check(const PriorAttach *a, size_t n_sources);
+// the prior kernel + results to pinned memory, enqueued on the context's stream behind the step's own top-K; under a site map the
+// rows of a live step (rows.sources) run at their sources' sites, every other row at the context's site;
 // step_rows: the step's own rows on the device (AFTER_TOPK filters them)
-bn_status prior_step(PriorAttach *a, hipStream_t stream, const float *d_logits, size_t batch, const TopkRows::ConstView &step_rows);
+bn_status prior_step(PriorAttach *a, hipStream_t stream, const float *d_logits, const TopkRows::ConstView &step_rows, const StepRows &rows);
 bn_status prior_step_results(const PriorAttach *a, const uint32_t **idx, const float **conf, const uint32_t **count, size_t *k_stride);
-// capi.cpp -> live.cpp: the context's attached prior, NULL if none
-PriorAttach *ctx_prior(bn_ctx *c);
 // prior.hip -> track.hip: what a kernel needs of a prior's table (rows padded to tstride floats)
 struct PriorView {
     int device;
@@ -176,7 +203,7 @@ PriorView prior_view(const bn_prior *p);
 // map, else the context's site
 const bn_prior *prior_of(const PriorAttach *a);
 int32_t prior_site_of(const PriorAttach *a, int32_t source);
-// track.hip -> capi.cpp / live.cpp: a tracker attached to a context (its own pinned row lists and event lists; holds a reference)
+// track.hip -> capi.cpp: a tracker attached to a context (its own pinned row lists and event lists; holds a reference)
 struct TrackAttach;
 bn_status track_attach(bn_track *t, int device, size_t num_species, size_t max_batch, TrackAttach **out);
 void track_detach(TrackAttach *a);  // the context's stream must be idle
@@ -185,12 +212,8 @@ bn_status track_set_source(TrackAttach *a, int32_t source);
 // with more sources than the tracker; bn_step_windows (count > 0): a first window that does not exceed the source's last
 bn_status track_step_check(const TrackAttach *a, const PriorAttach *prior, size_t n_sources, uint64_t first_window, size_t count);
 // the tracker's update for the step's rows + its event list to pinned memory, enqueued on the context's stream behind the step's own
-// work; row i is window windows[i] of sources[i] (bn_step_live) or, with sources == NULL, window first_window + i of the
-// attachment's source (bn_step_windows)
-bn_status track_step(TrackAttach *a, hipStream_t stream, const float *d_logits, size_t batch, const int32_t *sources, const uint64_t *windows,
-                     uint64_t first_window, const PriorAttach *prior);
+// work; only for numbered rows: row i is window rows.windows[i] of rows.sources[i] (bn_step_live) or, with sources == NULL, window
+// rows.first_window + i of the attachment's source (bn_step_windows)
+bn_status track_step(TrackAttach *a, hipStream_t stream, const float *d_logits, const StepRows &rows, const PriorAttach *prior);
 bn_status track_step_results(TrackAttach *a, const bn_event **events, size_t *n, size_t *dropped, size_t *stale_rows);
-// capi.cpp -> live.cpp: the context's attached tracker, NULL if none; the rows of the step bn_step_live is about to run
-TrackAttach *ctx_track(bn_ctx *c);
-void ctx_track_rows(bn_ctx *c, const int32_t *sources, const uint64_t *windows);
 }  // namespace bn

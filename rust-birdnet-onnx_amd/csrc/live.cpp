@@ -672,10 +672,7 @@ bn_status bn_step_live(bn_ctx *c, bn_live *l, size_t max_windows, size_t top_k, 
     if (ci.device != l->device) return invalid("pool and context live on different devices");
     if (ci.sample_count != l->S)
         return invalid("the context's model takes " + std::to_string(ci.sample_count) + "-sample segments, the pool cuts " + std::to_string(l->S));
-    bn::PriorAttach *prior = bn::ctx_prior(c);
-    if (prior && (st = bn::prior_live_check(prior, l->src.size())) != BN_OK) return st;
-    bn::TrackAttach *track = bn::ctx_track(c);
-    if (track && (st = bn::track_step_check(track, prior, l->src.size(), 0, 0)) != BN_OK) return st;
+    if ((st = bn::ctx_step_check(c, l->src.size(), 0, 0)) != BN_OK) return st;
     const size_t B = std::min(max_windows, l->queue.size());
     if (B == 0) return BN_OK;
     BN_HIP_TRY(bn::use_device(l->device));
@@ -735,14 +732,8 @@ bn_status bn_step_live(bn_ctx *c, bn_live *l, size_t max_windows, size_t top_k, 
     }
     // the windows are taken from here on: on a failure of the step itself *n_out still names them (their results are lost)
     *n_out = B;
-    // the rows' sites by their sources, in pinned memory the prior kernel reads in place: no copy, no synchronisation
-    if (prior && (st = bn::prior_stage_rows(prior, source_out, B)) != BN_OK) return st;
-    // the tracker's rows are these sources and windows (the caller's arrays, read before the step returns)
-    if (track) bn::ctx_track_rows(c, source_out, window_out);
-    st = bn_step_device(c, ci.d_input, B, top_k, has_min, min_conf, sync);
-    if (track) bn::ctx_track_rows(c, nullptr, nullptr);
-    if (prior) bn::prior_clear_rows(prior);
-    return st;
+    // the prior's and the tracker's rows are these sources and windows (the caller's arrays, read before the step returns)
+    return bn::step_device(c, ci.d_input, bn::StepRows{B, true, source_out, window_out, 0}, top_k, has_min, min_conf, sync);
 }
 
 }  // extern "C"

@@ -338,10 +338,6 @@ struct bn_prior {
     hipStream_t stream = nullptr;
 };
 
-namespace {
-constexpr int N_STAGE = 4;  // pinned blocks of per-row site ids in rotation
-}
-
 struct bn::PriorAttach {
     bn_prior *prior = nullptr;
     size_t max_batch = 0, top_k = 0;
@@ -352,13 +348,7 @@ struct bn::PriorAttach {
     int32_t site = 0;
     bn::TopkRows rows;            // the last step's filtered rows: device block and pinned mirror
     uint32_t *d_gkeys = nullptr;  // general select form: [max_batch, n_species]
-    // per-row site ids of a live step: pinned, read by the kernel in place; a block is rewritten only after the step that
-    // read it has completed (its event)
-    int32_t *h_sites[N_STAGE] = {};
-    hipEvent_t ev[N_STAGE] = {};
-    bool ev_used[N_STAGE] = {};
-    int next_stage = 0, pending = -1;  // pending: the block staged for the step about to run
-    size_t pending_rows = 0;
+    bn::PinnedRing sites;  // per-row site ids of a live step under a map: [max_batch] int32, read by the kernel in place
 };
 
 namespace {
@@ -486,10 +476,7 @@ bn_status bn::prior_attach(bn_prior *p, int device, size_t num_species, size_t m
         if (st != BN_OK) return st;
         if (general_form(p)) BN_HIP_TRY(bn::gated::Malloc(&a->d_gkeys, max_batch * p->n_species * sizeof(uint32_t)));
     }
-    for (int i = 0; i < N_STAGE; i++) {
-        BN_HIP_TRY(bn::gated::HostMalloc(&a->h_sites[i], std::max<size_t>(max_batch, 1) * sizeof(int32_t), hipHostMallocDefault));
-        BN_HIP_TRY(bn::gated::EventCreateWithFlags(&a->ev[i], hipEventDisableTiming));
-    }
+    BN_HIP_TRY(a->sites.create(std::max<size_t>(max_batch, 1) * sizeof(int32_t)));
     p->refs.fetch_add(1, std::memory_order_relaxed);
     a->prior = p;
     *out = a.release();
@@ -500,10 +487,7 @@ void bn::prior_detach(PriorAttach *a) {
     if (!a) return;
     a->rows.release();
     if (a->d_gkeys) (void)bn::gated::Free(a->d_gkeys);
-    for (int i = 0; i < N_STAGE; i++) {
-        if (a->h_sites[i]) (void)bn::gated::HostFree(a->h_sites[i]);
-        if (a->ev[i]) (void)bn::gated::EventDestroy(a->ev[i]);
-    }
+    a->sites.release();
     prior_unref(a->prior);
     delete a;
 }
@@ -515,46 +499,33 @@ bn_status bn::prior_set_site(PriorAttach *a, int32_t site) {
     return BN_OK;
 }
 
-bn_status bn::prior_live_check(const PriorAttach *a, size_t n_sources) {
+bn_status bn::prior_step_check(const PriorAttach *a, size_t n_sources) {
     if (a->has_map && n_sources > a->source_sites.size())
         return set_last_error(BN_ERR_INVALID_ARG, "the pool has " + std::to_string(n_sources) + " sources, the attached prior's site map " +
                                                       std::to_string(a->source_sites.size()));
     return BN_OK;
 }
 
-bn_status bn::prior_stage_rows(PriorAttach *a, const int32_t *sources, size_t rows) {
-    a->pending = -1;
-    if (!a->has_map) return BN_OK;  // every row at the context's site
-    if (rows > a->max_batch) return set_last_error(BN_ERR_INVALID_ARG, "batch exceeds the context's max_batch");
-    const int slot = a->next_stage;
-    if (a->ev_used[slot]) BN_HIP_TRY(hipEventSynchronize(a->ev[slot]));
-    for (size_t i = 0; i < rows; i++) {
-        const int32_t src = sources[i];
-        if (src < 0 || (size_t)src >= a->source_sites.size()) return set_last_error(BN_ERR_INVALID_ARG, "a source outside the attached prior's site map");
-        a->h_sites[slot][i] = a->source_sites[(size_t)src];
-    }
-    a->pending = slot;
-    a->pending_rows = rows;
-    a->next_stage = (slot + 1) % N_STAGE;
-    return BN_OK;
-}
-
-void bn::prior_clear_rows(PriorAttach *a) { a->pending = -1; }
-
-bn_status bn::prior_step(PriorAttach *a, hipStream_t stream, const float *d_logits, size_t batch, const TopkRows::ConstView &step_rows) {
+bn_status bn::prior_step(PriorAttach *a, hipStream_t stream, const float *d_logits, const TopkRows::ConstView &step_rows, const StepRows &rows) {
     const bn_prior *p = a->prior;
+    const size_t batch = rows.batch;
     if (batch > a->max_batch) return set_last_error(BN_ERR_INVALID_ARG, "batch exceeds the context's max_batch");
     const bool after = (p->flags & BN_PRIOR_AFTER_TOPK) != 0;
     const size_t k = after ? step_rows.k : std::min(a->top_k, p->n_species);
     bn_status st = a->rows.reserve(a->max_batch, k, stream, true, true);
     if (st != BN_OK) return st;
+    // the rows' sites by their sources, in pinned memory the kernel reads in place: no copy, no synchronisation
     const int32_t *sites = nullptr;
-    const int slot = a->pending;
-    a->pending = -1;
-    if (slot >= 0 && a->pending_rows == batch) {
-        void *dp = nullptr;
-        BN_HIP_TRY(hipHostGetDevicePointer(&dp, a->h_sites[slot], 0));
-        sites = static_cast<const int32_t *>(dp);
+    int slot = -1;
+    if (a->has_map && rows.sources) {
+        void *hp = nullptr;
+        BN_HIP_TRY(a->sites.acquire(&slot, &hp));
+        for (size_t i = 0; i < batch; i++) {
+            const int32_t src = rows.sources[i];
+            if (src < 0 || (size_t)src >= a->source_sites.size()) return set_last_error(BN_ERR_INVALID_ARG, "a source outside the attached prior's site map");
+            static_cast<int32_t *>(hp)[i] = a->source_sites[(size_t)src];
+        }
+        sites = static_cast<const int32_t *>(a->sites.device_ptr(slot));
     }
     const TopkRows::View out = TopkRows::view(a->rows.d, batch, k);
     if (after)
@@ -562,10 +533,7 @@ bn_status bn::prior_step(PriorAttach *a, hipStream_t stream, const float *d_logi
     else
         st = enqueue_select(p, stream, d_logits, batch, sites, a->site, k, a->has_min, a->min_conf, k, a->d_gkeys, out.idx, out.conf, out.count);
     if (st != BN_OK) return st;
-    if (sites) {
-        BN_HIP_TRY(hipEventRecord(a->ev[slot], stream));
-        a->ev_used[slot] = true;
-    }
+    if (sites) BN_HIP_TRY(a->sites.commit(slot, stream));
     const bn::OutRegion reg{a->rows.h, a->rows.d, TopkRows::bytes(batch, k)};
     if ((st = bn::results_to_host(stream, &reg, 1)) != BN_OK) return st;
     a->rows.mark(batch, k);

@@ -1,5 +1,5 @@
 // The plumbing the entry points of the C ABI share (declared in capi_internal.h): launch and device checks, the packed top-K block,
-// results to pinned memory, scoped scratch.
+// results to pinned memory, the pinned ring, scoped scratch.
 #include <algorithm>
 
 #include "capi_internal.h"
@@ -103,6 +103,43 @@ bn_status enqueue_topk_rows(hipStream_t stream, const float *d_logits, size_t ro
     clear_launch_state();
     launch_topk(stream, d_logits, (int64_t)rows, (int64_t)n, (int64_t)k, has_min, min_conf, (int64_t)k, out.idx, out.conf, out.count, d_flags);
     return check_launch("top-K");
+}
+
+hipError_t PinnedRing::create(size_t bytes) {
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < SLOTS && e == hipSuccess; i++) {
+        e = gated::HostMalloc(&h[i], bytes, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipHostGetDevicePointer(&d[i], h[i], 0);
+        if (e == hipSuccess) e = gated::EventCreateWithFlags(&ev[i], hipEventDisableTiming);
+    }
+    if (e != hipSuccess) release();
+    return e;
+}
+
+void PinnedRing::release() {
+    for (int i = 0; i < SLOTS; i++) {
+        if (h[i]) (void)gated::HostFree(h[i]);
+        if (ev[i]) (void)gated::EventDestroy(ev[i]);
+    }
+    *this = PinnedRing{};
+}
+
+hipError_t PinnedRing::acquire(int *slot, void **host) {
+    if (busy[next]) {
+        hipError_t e = hipEventSynchronize(ev[next]);
+        if (e != hipSuccess) return e;
+    }
+    *slot = next;
+    *host = h[next];
+    return hipSuccess;
+}
+
+hipError_t PinnedRing::commit(int slot, hipStream_t stream) {
+    hipError_t e = hipEventRecord(ev[slot], stream);
+    if (e != hipSuccess) return e;
+    busy[slot] = true;
+    next = (slot + 1) % SLOTS;
+    return hipSuccess;
 }
 
 Scratch::~Scratch() {

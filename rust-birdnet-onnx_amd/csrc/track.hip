@@ -231,19 +231,12 @@ struct bn_track {
     std::mutex mu;
 };
 
-namespace {
-constexpr int N_STAGE = 4;  // pinned blocks in rotation per attachment
-}
-
 struct bn::TrackAttach {
     bn_track *track = nullptr;
     size_t max_batch = 0;
     int32_t source = 0;
-    // a block is rewritten only after the step that read it has completed (its event)
-    bn::Stage stage[N_STAGE];
-    hipEvent_t ev[N_STAGE] = {};
-    bool ev_used[N_STAGE] = {};
-    int next_stage = 0;
+    bn::PinnedRing ring;  // a step's lists and events, read and written by the kernels in place
+    bn::Stage stage[bn::PinnedRing::SLOTS];  // the ring's blocks, carved
     // the last tracked step
     int res_slot = -1;   // -1: none since the attach; -2: a step whose rows were all stale (no launch)
     bool res_sorted = false;
@@ -400,12 +393,8 @@ bn_status bn::track_attach(bn_track *t, int device, size_t num_species, size_t m
     std::unique_ptr<TrackAttach, void (*)(TrackAttach *)> a(new TrackAttach, track_detach);
     a->max_batch = max_batch;
     const size_t rows = std::max<size_t>(max_batch, 1);
-    for (int i = 0; i < N_STAGE; i++) {
-        void *b = nullptr;
-        BN_HIP_TRY(bn::gated::HostMalloc(&b, Stage::bytes(rows, rows, t->max_events), hipHostMallocDefault));
-        a->stage[i].carve(b, rows, rows, t->max_events);
-        BN_HIP_TRY(bn::gated::EventCreateWithFlags(&a->ev[i], hipEventDisableTiming));
-    }
+    BN_HIP_TRY(a->ring.create(Stage::bytes(rows, rows, t->max_events)));
+    for (int i = 0; i < PinnedRing::SLOTS; i++) a->stage[i].carve(a->ring.h[i], rows, rows, t->max_events);
     t->refs.fetch_add(1, std::memory_order_relaxed);
     a->track = t;
     *out = a.release();
@@ -414,10 +403,7 @@ bn_status bn::track_attach(bn_track *t, int device, size_t num_species, size_t m
 
 void bn::track_detach(TrackAttach *a) {
     if (!a) return;
-    for (int i = 0; i < N_STAGE; i++) {
-        if (a->stage[i].base) (void)bn::gated::HostFree(a->stage[i].base);
-        if (a->ev[i]) (void)bn::gated::EventDestroy(a->ev[i]);
-    }
+    a->ring.release();
     track_unref(a->track);
     delete a;
 }
@@ -447,9 +433,10 @@ bn_status bn::track_step_check(const TrackAttach *a, const PriorAttach *prior, s
     return BN_OK;
 }
 
-bn_status bn::track_step(TrackAttach *a, hipStream_t stream, const float *d_logits, size_t batch, const int32_t *sources, const uint64_t *windows,
-                         uint64_t first_window, const PriorAttach *prior) {
+bn_status bn::track_step(TrackAttach *a, hipStream_t stream, const float *d_logits, const StepRows &rows, const PriorAttach *prior) {
     bn_track *t = a->track;
+    const size_t batch = rows.batch;
+    const int32_t *sources = rows.sources;
     std::lock_guard<std::mutex> lk(t->mu);
     if (batch > a->max_batch) return set_last_error(BN_ERR_INVALID_ARG, "batch exceeds the context's max_batch");
     PriorView pv{};
@@ -469,7 +456,7 @@ bn_status bn::track_step(TrackAttach *a, hipStream_t stream, const float *d_logi
     size_t stale = 0;
     for (size_t i = 0; i < batch; i++) {
         src[i] = sources ? sources[i] : a->source;
-        win[i] = windows ? windows[i] : first_window + i;
+        win[i] = rows.windows ? rows.windows[i] : rows.first_window + i;
         if ((st = check_source(t, src[i], "the source of a row,")) != BN_OK || win[i] >= WINDOW_LIMIT) {
             take_back();
             return st != BN_OK ? st : set_last_error(BN_ERR_INVALID_ARG, "a tracked window number must be below 2^31");
@@ -489,14 +476,15 @@ bn_status bn::track_step(TrackAttach *a, hipStream_t stream, const float *d_logi
         a->res_slot = -2;
         return BN_OK;
     }
-    const int slot = a->next_stage;
-    Stage &sg = a->stage[slot];
-    hipError_t we = a->ev_used[slot] ? hipEventSynchronize(a->ev[slot]) : hipSuccess;
+    int slot = 0;
+    void *block = nullptr;
+    hipError_t we = a->ring.acquire(&slot, &block);
     if (we == hipSuccess) {
+        Stage &sg = a->stage[slot];
         const size_t groups = build_groups(sg, src.data(), win.data(), site.data(), skip.data(), batch, a->order);
         *sg.total = 0;
         st = enqueue_update(t, stream, d_logits, sg, groups, use ? &pv : nullptr, false);
-        if (st == BN_OK) we = hipEventRecord(a->ev[slot], stream);
+        if (st == BN_OK) we = a->ring.commit(slot, stream);
     }
     if (we != hipSuccess || st != BN_OK) {
         take_back();
@@ -504,8 +492,6 @@ bn_status bn::track_step(TrackAttach *a, hipStream_t stream, const float *d_logi
         if (st != BN_OK) return st;
         return set_last_error(BN_ERR_BACKEND, std::string("tracker step: ") + hipGetErrorString(we));
     }
-    a->ev_used[slot] = true;
-    a->next_stage = (slot + 1) % N_STAGE;
     a->res_slot = slot;
     a->res_sorted = false;
     return BN_OK;
