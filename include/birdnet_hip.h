@@ -522,6 +522,41 @@ bn_status bn_head_fit(int32_t device, size_t dim, size_t n_classes, const float 
 bn_status bn_head_fit_index(bn_index *x, const uint64_t *ids, const uint8_t *labels, size_t n, size_t n_classes,
                             const bn_head_fit_opts *opts, size_t opts_size, bn_head **out, bn_head_fit_report *report,
                             size_t report_size);
+/*
+ * Ranking an index by a head: per class, the top_m stored rows by the head's own logit, computed where the slab lives (re-score
+ * the archive after a fit; choose the rows worth labelling next).  One pass over the slab serves up to 64 classes.
+ *
+ *   Logit          for class c and stored row r, z = chain(W_c, stored row r) + b_c, chain the head block's accumulation: one
+ *                  accumulator, the k order fixed by the padded dim alone, then the bias added.  The row is used AS STORED
+ *                  (normalised once at append, not again), which is what bn_head_fit_index trains on.  So the bits equal
+ *                  bn_head_apply_host's for a head with the same W, b and flags 0 on the row as bn_index_read returns it; and,
+ *                  the head's normalisation being the index's (the same bits), for a window appended by bn_index_add_ctx they
+ *                  equal that step's bn_step_head_results logit of the same head.  A logit's bits depend on dim, the row, W_c
+ *                  and b_c only: not on the row's position, the index size, the id range, the exclusions, top_m, the mode or
+ *                  how many classes the head has.
+ *   Eligible rows  inside the id range, not in exclude_ids, and valid: a row the index stored as zeros is never returned, as in
+ *                  a search.  A row whose logit is NaN is never returned in either mode.
+ *   Order          BN_RANK_TOP: z descending, ties by id ascending (-0.0 == +0.0, the index's rule).  BN_RANK_UNCERTAIN: |z|
+ *                  ascending, ties by id ascending, so z and -z tie.  count = min(top_m, eligible rows); entries past count
+ *                  are not written.  logit_out holds z itself in both modes; the caller applies the sigmoid.
+ *   Refusals       BN_ERR_INVALID_ARG with a message, no output written and nothing changed: NULL where data is required, an
+ *                  unknown mode, top_m outside 1..256, m_stride < top_m, first_id > bn_index_size or a range that runs past the
+ *                  end, an excluded id >= bn_index_size, bn_head_dim != bn_index_dim, a head on another device, a head without
+ *                  BN_HEAD_L2NORM (its weights expect raw embeddings, and the index no longer has them).
+ *   Empty cases    an empty index or an empty range gives every count = 0.  Duplicates in exclude_ids are legal.
+ *   No device      without a gfx950 device the call returns BN_ERR_NO_DEVICE.
+ *   Determinism    no floating-point atomics; two calls give the same bytes.  The head and the index are unchanged.
+ *   Threading      one thread at a time per index; the head is immutable and may be in use elsewhere.
+ *
+ * Outputs are host arrays: id_out and logit_out [n_classes * m_stride] (class c's list starts at c * m_stride), count_out
+ * [n_classes].  The call is synchronous; like bn_index_search it first waits for a pending bn_index_add_ctx.
+ */
+#define BN_RANK_TOP 0u       /* logit descending */
+#define BN_RANK_UNCERTAIN 1u /* |logit| ascending: nearest the decision boundary */
+/* rows [first_id, first_id + n_ids), n_ids == 0: to the end; exclude_ids [n_exclude] (e.g. the rows already labelled), NULL / 0: none */
+bn_status bn_head_rank_index(const bn_head *h, bn_index *x, uint32_t mode, uint64_t first_id, uint64_t n_ids,
+                             const uint64_t *exclude_ids, size_t n_exclude, size_t top_m, size_t m_stride, uint64_t *id_out,
+                             float *logit_out, uint32_t *count_out);
 /* every later bn_step_device / bn_step_windows / bn_step_live on c also runs the head on that step's embedding rows;
  * h == NULL detaches (the other arguments are then ignored) */
 bn_status bn_ctx_attach_head(bn_ctx *c, bn_head *h, size_t top_k, int32_t has_min, float min_conf);

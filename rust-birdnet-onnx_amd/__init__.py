@@ -55,7 +55,7 @@ ENGINE_SYMBOLS = [
     "bn_index_create", "bn_index_free", "bn_index_size", "bn_index_dim", "bn_index_add_host", "bn_index_add_ctx", "bn_index_read",
     "bn_index_search", "bn_index_search_ids",
     "bn_head_create", "bn_head_free", "bn_head_dim", "bn_head_classes", "bn_head_flags", "bn_head_read", "bn_head_apply_host",
-    "bn_head_fit", "bn_head_fit_index", "bn_ctx_attach_head", "bn_step_head_results",
+    "bn_head_fit", "bn_head_fit_index", "bn_head_rank_index", "bn_ctx_attach_head", "bn_step_head_results",
     "bn_prior_create", "bn_prior_free", "bn_prior_sites", "bn_prior_species", "bn_prior_threshold", "bn_prior_flags", "bn_prior_read",
     "bn_prior_apply_host", "bn_ctx_attach_prior", "bn_ctx_prior_site", "bn_step_prior_results",
     "bn_track_create", "bn_track_free", "bn_track_sources", "bn_track_species", "bn_track_open_events", "bn_track_update_host",
@@ -116,6 +116,7 @@ class BnHeadFitReport(C.Structure):
 
 
 BN_HEAD_L2NORM = 1
+BN_RANK_TOP, BN_RANK_UNCERTAIN = 0, 1
 BN_PRIOR_UNKNOWN = -1.0  # table entry of a species the meta model does not know
 BN_PRIOR_SELECT, BN_PRIOR_AFTER_TOPK, BN_PRIOR_RERANK = 0, 1, 2
 BN_TRACK_PRIOR = 1  # bn_track_create flag: hits are those of admitted species, on the prior's conf'
@@ -222,6 +223,7 @@ def _load() -> C.CDLL:
         "bn_head_fit": (i32, [i32, sz, sz, f32p, C.POINTER(C.c_uint8), sz, C.POINTER(BnHeadFitOpts), sz, C.POINTER(vp), C.POINTER(BnHeadFitReport), sz]),
         "bn_head_fit_index": (i32, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint8), sz, sz, C.POINTER(BnHeadFitOpts), sz, C.POINTER(vp),
                                     C.POINTER(BnHeadFitReport), sz]),
+        "bn_head_rank_index": (i32, [vp, vp, C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), sz, sz, sz, C.POINTER(C.c_uint64), f32p, u32p]),
         "bn_ctx_attach_head": (i32, [vp, vp, sz, i32, C.c_float]),
         "bn_step_head_results": (i32, [vp, C.POINTER(f32p), C.POINTER(u32p), C.POINTER(f32p), C.POINTER(u32p), C.POINTER(sz), C.POINTER(sz)]),
         "bn_prior_create": (i32, [i32, sz, sz, f32p, C.c_float, C.c_uint32, C.POINTER(vp)]),
@@ -1312,6 +1314,26 @@ class Head:
         if st:
             raise EngineError(st)
         return w, b
+
+    def rank_index(self, index: "Index", top_m: int, mode="top", first_id: int = 0, n_ids: int = 0, exclude=None, m_stride: Optional[int] = None):
+        """bn_head_rank_index: per class, the top_m stored rows of `index` by this head's logit ("top": logit descending) or by
+        nearness to the decision boundary ("uncertain": |logit| ascending), among rows [first_id, first_id + n_ids) (n_ids 0: to
+        the end) that are not in `exclude`.  Returns (ids [n_classes, m_stride] uint64, logits [n_classes, m_stride] float32,
+        counts [n_classes] uint32); entries past counts[c] are left as written here (ids 0, logits NaN)."""
+        if isinstance(mode, str):
+            modes = {"top": BN_RANK_TOP, "uncertain": BN_RANK_UNCERTAIN}
+            if mode not in modes:
+                raise ValueError("mode must be 'top' or 'uncertain'")
+            mode = modes[mode]
+        m_stride = top_m if m_stride is None else m_stride
+        ex = None if exclude is None else np.ascontiguousarray(exclude, dtype=np.uint64).reshape(-1)
+        ids, logits, counts = Index._outputs(self.n_classes, max(m_stride, 0))
+        st = lib.bn_head_rank_index(self._h, index._h, mode, first_id, n_ids, None if ex is None else ex.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                    0 if ex is None else ex.shape[0], top_m, m_stride, ids.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                    logits.ctypes.data_as(C.POINTER(C.c_float)), counts.ctypes.data_as(C.POINTER(C.c_uint32)))
+        if st:
+            raise EngineError(st)
+        return ids, logits, counts
 
     def apply(self, rows) -> np.ndarray:
         """bn_head_apply_host: logits [n, n_classes] of host rows [n, dim]."""

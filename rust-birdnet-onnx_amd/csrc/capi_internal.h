@@ -1,6 +1,6 @@
 // What the translation units of the C ABI share: the plumbing every entry point repeats (the error macro, launch and device checks,
 // the packed top-K block TopkRows, results_to_host, the pinned ring PinnedRing, scoped scratch: step_common.cpp), what they need of
-// capi.cpp's private state (index.hip: bn_index_*; head.hip: bn_head_*; live.cpp: bn_step_live) and of each other (prior.hip:
+// capi.cpp's private state (index.hip: bn_index_*; head.hip: bn_head_*; rank.hip: bn_head_rank_index; live.cpp: bn_step_live) and of each other (prior.hip:
 // bn_prior_*; track.hip: bn_track_*).  A step's rows reach its stages as an argument (StepRows), never through a context's state.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -168,6 +168,33 @@ struct IndexRows {
     size_t dim = 0, dpad = 0, size = 0;
 };
 bn_status index_rows(bn_index *x, IndexRows *out);
+// index.hip -> rank.hip (bn_head_rank_index): what a scan of the slab on the index's own stream needs.  The device is made current
+// and the stream ordered after a pending bn_index_add_ctx, without waiting; the buffers are the search's own (one thread at a time
+// per index): candidates [max_wg][lists][256] + lengths [max_wg][lists], results [out_lists][256] + counts with pinned mirrors
+namespace topm {
+struct Cand;
+}
+struct IndexScan {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    const float *slab = nullptr;     // rows padded to a multiple of 64, [.., dpad]
+    const uint8_t *valid = nullptr;  // likewise
+    size_t dim = 0, dpad = 0, size = 0;
+    int max_wg = 0;
+    size_t lists = 0, out_lists = 0;
+    topm::Cand *d_cand = nullptr, *d_out = nullptr, *h_out = nullptr;
+    int *d_cand_len = nullptr;
+    uint32_t *d_count = nullptr, *h_count = nullptr;
+};
+bn_status index_scan_state(bn_index *x, IndexScan *out);
+// head.hip -> rank.hip: what a kernel needs of a head (weights [cpad = classes rounded up to 16][dpad], bias [cpad], padding zero)
+struct HeadView {
+    int device;
+    size_t dim, dpad, classes, cpad;
+    uint32_t flags;
+    const float *d_W, *d_b;
+};
+HeadView head_view(const bn_head *h);
 // head.hip -> capi.cpp: a head attached to a context (its own result buffers; holds a reference to the head)
 struct HeadAttach;
 bn_status head_attach(bn_head *h, int device, bool has_embedding, size_t embedding_dim, size_t max_batch, size_t top_k, int32_t has_min,

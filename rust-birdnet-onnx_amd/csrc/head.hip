@@ -629,6 +629,8 @@ void write_report(const bn_head_fit_report &rep, bn_head_fit_report *out, size_t
 
 }  // namespace
 
+bn::HeadView bn::head_view(const bn_head *h) { return {h->device, h->dim, h->dpad, h->classes, h->cpad, h->flags, h->d_W, h->d_b}; }
+
 bn_status bn::head_attach(bn_head *h, int device, bool has_embedding, size_t embedding_dim, size_t max_batch, size_t top_k, int32_t has_min, float min_conf,
                           HeadAttach **out) {
     if (!h || !out) return set_last_error(BN_ERR_INVALID_ARG, "null argument");

@@ -13,7 +13,9 @@
 //     running top-M (kept in its slice of the candidate buffer) when they fill.  Out: [workgroups x queries x M] candidates.
 //   * index_merge_kernel -- one wave per query merges the workgroups' sorted lists into the final top-M, reading each list
 //     only while its entries still beat the running M-th.
-// Order everywhere: score descending, ties by id ascending (-0.0 == +0.0 through the float compare).
+// Order everywhere: score descending, ties by id ascending (-0.0 == +0.0 through the float compare).  The candidate, the order and
+// the two merges live in topm_select.h, which rank.hip (bn_head_rank_index) shares; it also borrows this index's stream and
+// candidate buffers (index_scan_state).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -27,76 +29,30 @@
 #include "capi_internal.h"
 #include "device_common.h"
 #include "hip_gate.h"
+#include "topm_select.h"
 
 namespace {
 
 constexpr int KC = 128;    // k-step of the scan; slab and query rows are padded to a multiple of it
 constexpr int TILE = 64;   // rows per workgroup tile: 4 waves x 16 rows
 constexpr int QP = 64;     // queries per scan pass
-constexpr int MMAX = 256;  // largest top_m
-constexpr int PEND = 128;  // pending candidates per query before they are merged into the running list
 constexpr int QS_LD = KC + 4;
 constexpr int S_LD = TILE + 1;
 constexpr size_t QCHUNK = 1024;  // queries normalised / searched per round of a call
 constexpr size_t STAGE_ROWS = 1024;
 
-struct Cand {
-    float s;
-    uint32_t id;
-};
+using bn::topm::Cand;
+using bn::topm::lanes_below;
+using bn::topm::merge_pending;
+using bn::topm::MMAX;
+using bn::topm::PEND;
+using bn::topm::wave_sync;
+using Ord = bn::topm::ScoreDesc;  // the search's order: score descending, ties by id ascending
 
 constexpr size_t SCAN_LDS = (size_t)QP * QS_LD * 4 + (size_t)QP * S_LD * 4 + (size_t)QP * PEND * sizeof(Cand) + 4 * MMAX * sizeof(Cand) +
                             QP * sizeof(Cand) + 2 * QP * sizeof(int);
 
 using bn::floatx4;
-
-__device__ inline bool ahead(Cand a, Cand b) { return a.s > b.s || (a.s == b.s && a.id < b.id); }
-
-// LDS and global writes of this wave visible to its other lanes
-__device__ inline void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-}
-
-__device__ inline int lanes_below(uint64_t m) {
-    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
-
-// One wave: merge np unordered pending candidates into the sorted running list (len entries), keeping the first M of the union.
-// Every element's new position is its rank in the union (the order is strict: ids are distinct).  scratch: MMAX entries of
-// LDS; *thr receives the M-th entry when the list is full.  Returns the new length.
-__device__ int merge_pending(const Cand *pend, int np, Cand *list, int len, int M, Cand *scratch, Cand *thr) {
-    const int lane = threadIdx.x & 63;
-    for (int i = lane; i < len; i += 64) scratch[i] = list[i];
-    wave_sync();
-    for (int i = lane; i < len; i += 64) {
-        const Cand e = scratch[i];
-        int r = i;
-        for (int j = 0; j < np; j++) r += ahead(pend[j], e) ? 1 : 0;
-        if (r < M) {
-            list[r] = e;
-            if (r == M - 1) *thr = e;
-        }
-    }
-    for (int p = lane; p < np; p += 64) {
-        const Cand e = pend[p];
-        int r = 0;
-        for (int j = 0; j < np; j++) r += ahead(pend[j], e) ? 1 : 0;
-        int lo = 0, hi = len;  // list entries ahead of e: a prefix of the sorted list
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (ahead(scratch[mid], e)) lo = mid + 1;
-            else hi = mid;
-        }
-        r += lo;
-        if (r < M) {
-            list[r] = e;
-            if (r == M - 1) *thr = e;
-        }
-    }
-    wave_sync();
-    return min(M, len + np);
-}
 
 // rows [n, dim] at src (row stride src_stride) -> normalised rows [n, dpad] at dst + validity flags
 __global__ __launch_bounds__(256) void index_normalise_kernel(const float *__restrict__ src, size_t src_stride, uint32_t n, uint32_t dim,
@@ -237,12 +193,12 @@ __global__ __launch_bounds__(256) void index_scan_kernel(const float *__restrict
             }
             const Cand e{S[qq * S_LD + lane], grow};
             int L = len[qq];
-            const bool pass = ok && (L < M || ahead(e, thr[qq]));
+            const bool pass = ok && (L < M || Ord::ahead(e, thr[qq]));
             const uint64_t m = __ballot(pass);
             if (!m) continue;
             int np = pn[qq];
             if (np + 64 > PEND) {
-                L = merge_pending(pend + qq * PEND, np, my_cand + qq * MMAX, L, M, scratch + w * MMAX, thr + qq);
+                L = merge_pending<Ord>(pend + qq * PEND, np, my_cand + qq * MMAX, L, M, scratch + w * MMAX, thr + qq);
                 np = 0;
             }
             if (pass) pend[qq * PEND + np + lanes_below(m)] = e;
@@ -258,7 +214,7 @@ __global__ __launch_bounds__(256) void index_scan_kernel(const float *__restrict
     for (int qq = w; qq < nq; qq += 4) {
         int L = len[qq];
         const int np = pn[qq];
-        if (np) L = merge_pending(pend + qq * PEND, np, my_cand + qq * MMAX, L, M, scratch + w * MMAX, thr + qq);
+        if (np) L = merge_pending<Ord>(pend + qq * PEND, np, my_cand + qq * MMAX, L, M, scratch + w * MMAX, thr + qq);
         if (lane == 0) cand_len[blockIdx.x * QP + qq] = L;
     }
 }
@@ -266,31 +222,7 @@ __global__ __launch_bounds__(256) void index_scan_kernel(const float *__restrict
 // one wave per query: the workgroups' sorted lists -> the final top-M (out [nq][M], count [nq])
 __global__ __launch_bounds__(64) void index_merge_kernel(const Cand *__restrict__ cand, const int *__restrict__ cand_len, int n_wg, int M,
                                                          Cand *__restrict__ out, uint32_t *__restrict__ count) {
-    __shared__ Cand list[MMAX], scratch[MMAX], pend[PEND];
-    __shared__ Cand thr;
-    const int q = blockIdx.x, lane = threadIdx.x;
-    int len = 0, np = 0;
-    for (int g = 0; g < n_wg; g++) {
-        const Cand *src = cand + ((size_t)g * QP + q) * MMAX;
-        const int lg = cand_len[g * QP + q];
-        for (int j = 0; j < lg; j += 64) {
-            const bool in = j + lane < lg;
-            const Cand e = in ? src[j + lane] : Cand{0.f, 0u};
-            const bool pass = in && (len < M || ahead(e, thr));
-            const uint64_t m = __ballot(pass);
-            if (!m) break;  // the list is sorted: nothing after a rejected entry can pass
-            if (np + 64 > PEND) {
-                len = merge_pending(pend, np, list, len, M, scratch, &thr);
-                np = 0;
-            }
-            if (pass) pend[np + lanes_below(m)] = e;
-            np += __popcll(m);
-            wave_sync();
-        }
-    }
-    if (np) len = merge_pending(pend, np, list, len, M, scratch, &thr);
-    for (int i = lane; i < len; i += 64) out[(size_t)q * M + i] = list[i];
-    if (lane == 0) count[q] = (uint32_t)len;
+    bn::topm::merge_lists<Ord>(cand, cand_len, QP, n_wg, M, out, count);
 }
 
 std::mutex g_lds_mu;
@@ -435,6 +367,29 @@ bn_status bn::index_rows(bn_index *x, IndexRows *out) {
     out->dim = x->dim;
     out->dpad = x->dpad;
     out->size = x->size;
+    return BN_OK;
+}
+
+bn_status bn::index_scan_state(bn_index *x, IndexScan *out) {
+    if (!x || !out) return set_last_error(BN_ERR_INVALID_ARG, "null index");
+    bn_status st = begin(x);
+    if (st != BN_OK) return st;
+    out->device = x->device;
+    out->stream = x->stream;
+    out->slab = x->slab;
+    out->valid = x->valid;
+    out->dim = x->dim;
+    out->dpad = x->dpad;
+    out->size = x->size;
+    out->max_wg = x->max_wg;
+    out->lists = QP;
+    out->out_lists = QCHUNK;
+    out->d_cand = x->d_cand;
+    out->d_cand_len = x->d_cand_len;
+    out->d_out = x->d_out;
+    out->d_count = x->d_count;
+    out->h_out = x->h_out;
+    out->h_count = x->h_count;
     return BN_OK;
 }
 
