@@ -565,6 +565,86 @@ bn_status bn_step_head_results(const bn_ctx *c, const float **logits, const uint
                                const uint32_t **count, size_t *k_stride, size_t *n_classes);
 
 /*
+ * Clustering an index: what is in the archive, before there is a window to search from or a label to fit on.  bn_index_assign
+ * gives every stored row its nearest centroid; bn_index_cluster is spherical k-means (Lloyd) on top of it.  Both run where the
+ * slab lives: one pass over it serves up to 64 centroids, and no row crosses the bus.  The reference has embeddings and nothing
+ * built on them; this comment is the contract.
+ *
+ *   Score          for stored row r and centroid c, s = chain(centroid c, stored row r) + 0.0f, chain the head block's
+ *                  accumulation: one accumulator, the k order fixed by the padded dim alone.  So the bits equal
+ *                  bn_head_apply_host's for a head with W = centroids, no bias and flags 0 on the row as bn_index_read returns it.
+ *                  Host centroids are used AS GIVEN (not normalised), as a head's W is.  A score's bits depend on dim, the row
+ *                  and that centroid only: not on k, the centroid's position, the pass of 64 it falls in, the row's position,
+ *                  the id range or the index size.
+ *   Order          the centroid of largest score wins; ties go to the lowest centroid index (-0.0 == +0.0); a NaN score never
+ *                  wins.  Centroids beyond 64 take further passes over the slab; a row's running (best score, best index) is
+ *                  carried from pass to pass on the device, and a later pass replaces it only on a strictly larger score.
+ *   Eligible rows  inside the id range and valid.  A row the index stored as zeros, or one all of whose scores are NaN, gets
+ *                  BN_CLUSTER_NONE and score NaN, belongs to no cluster and counts toward no centroid.
+ *   Start          (cluster) init_ids: the stored rows of k ids, as stored.  init_centroids: host vectors, as given.  Neither:
+ *                  max-min.  The first centroid is the lowest-id valid row of the range; each further one is the valid row, not
+ *                  yet chosen, whose best score against the centroids so far is smallest, ties by lowest id (one single-centroid
+ *                  pass per centroid).  Rows that coincide with chosen ones tie at their own score, so when nothing else is left
+ *                  the next unchosen row in id order is taken.  start_ids_out receives the chosen ids (or init_ids).
+ *   Update         (cluster) per cluster, its member rows summed in ascending id order: segments of 256 consecutive members,
+ *                  each summed member by member in float64, the segments added in order in float64; then the float64 norm, and
+ *                  sum / norm stored as f32.  The association depends on a member's rank inside its cluster alone, never on the
+ *                  device.  Against a float64 evaluation, per component, with n_c members and s the sum,
+ *                  |c - c64| <= 2^-24 |c64| + n_c * 2^-52 * (sum_members |x|) / |s|.  A cluster with no members, or whose sum
+ *                  has zero or non-finite norm, keeps its centroid; report.empty_clusters counts those of the last update.
+ *   Stop           (cluster) assign, update, assign, ...: the call stops after an assignment pass that moved no row against the
+ *                  pass before it (converged = 1), or after max_iters updates, and always right after an assignment pass.  So
+ *                  assign_out / score_out are the exact assignment under centroids_out, counts_out its cluster sizes, and with
+ *                  converged = 1 centroids_out is also the update of assign_out.  moved_last is the last pass's count (the first
+ *                  pass of a call moves every row of the range).  objective is the float64 sum, in id order, of the last pass's
+ *                  winning scores; objective_history receives the same sum for every pass (history_len of them, at most
+ *                  history_capacity).
+ *   Refusals       BN_ERR_INVALID_ARG with a message, no output written and nothing changed: NULL where data is required (the
+ *                  index, centroids, assign_out, centroids_out, counts_out), k outside 1..1024, first_id > bn_index_size or a
+ *                  range that runs past the end, a non-finite centroid or init centroid, an init id outside the range, one whose
+ *                  stored row is all zeros, a duplicate init id, both init_ids and init_centroids, and (cluster) a range with
+ *                  fewer valid rows than k.
+ *   Empty cases    an empty index or an empty range is legal for bn_index_assign and writes nothing; for bn_index_cluster it
+ *                  falls under the fewer-rows refusal.
+ *   No device      without a gfx950 device both calls return BN_ERR_NO_DEVICE and leave the outputs untouched.
+ *   Determinism    no floating-point atomics; two calls with the same inputs give the same bytes in every output.  t iterations
+ *                  in one call give the same centroids_out, assign_out, score_out and counts_out as t calls of one iteration each,
+ *                  every call started from the previous call's centroids_out through init_centroids.
+ *   Memory         the centroids [k, dim padded], the running best and previous-assignment planes and the member lists (4 words
+ *                  per row), and partial sums of at most 32 MB or one slot of k x padded dim doubles: allocated by the first
+ *                  call that needs them, kept for the next, freed with the index.  An index that never clusters allocates none.
+ *   Threading      one thread at a time per index.
+ *
+ * Outputs are host arrays: assign_out (u32) and score_out (f32, may be NULL) [rows of the range], entry i for row first_id + i;
+ * centroids_out [k * dim]; counts_out [k].  Both calls are synchronous; like bn_index_search they first wait for a pending
+ * bn_index_add_ctx.  The index is unchanged.
+ */
+#define BN_CLUSTER_NONE 4294967295u /* 0xFFFFFFFF: the assignment of a row that belongs to no cluster */
+/* rows [first_id, first_id + n_ids), n_ids == 0: to the end; centroids host [k * dim] */
+bn_status bn_index_assign(bn_index *x, const float *centroids, size_t k, uint64_t first_id, uint64_t n_ids,
+                          uint32_t *assign_out, float *score_out);
+typedef struct bn_cluster_opts { /* zero / NULL fields take the defaults in brackets */
+    uint32_t max_iters;          /* updates at most [50] */
+    const uint64_t *init_ids;    /* [k] stored rows as the first centroids, or NULL */
+    const float *init_centroids; /* [k * dim] first centroids, or NULL; neither: the max-min start */
+    uint64_t *start_ids_out;     /* [k]: receives the rows the start used (not written under init_centroids), or NULL */
+    double *objective_history;   /* [history_capacity]: receives the objective of every assignment pass, or NULL */
+    size_t history_capacity;
+} bn_cluster_opts;
+typedef struct bn_cluster_report {
+    uint32_t iters;          /* updates made */
+    int32_t converged;
+    uint32_t empty_clusters; /* centroids the last update kept */
+    uint32_t moved_last;
+    double objective;
+    uint32_t history_len;    /* entries written to objective_history */
+} bn_cluster_report;
+/* opts may be NULL (all defaults), report may be NULL; both structs are read / written through the caller's struct size */
+bn_status bn_index_cluster(bn_index *x, size_t k, uint64_t first_id, uint64_t n_ids, const bn_cluster_opts *opts,
+                           size_t opts_size, float *centroids_out, uint32_t *assign_out, float *score_out,
+                           uint32_t *counts_out, bn_cluster_report *report, size_t report_size);
+
+/*
  * Per-site species priors: the location / date prior of the reference's RangeFilter (src/rangefilter.rs) as an immutable
  * device table P[n_sites][n_species] (f32, row-major), applied to every row of a step.  The reference filters one
  * prediction list at a time on the host, by species name, after the cut to K; a table on the device serves a pool of a

@@ -53,7 +53,7 @@ ENGINE_SYMBOLS = [
     "bn_infer_windows", "bn_step_windows", "bn_ctx_step_device_rows", "bn_group_create", "bn_group_destroy", "bn_group_size",
     "bn_group_uses_rccl", "bn_group_get_stats", "bn_shard_range", "bn_group_analyze_recording", "bn_group_last_error", "bn_recording_create_resampled", "bn_resample_table", "bn_recording_read_f32", "bn_last_error",
     "bn_index_create", "bn_index_free", "bn_index_size", "bn_index_dim", "bn_index_add_host", "bn_index_add_ctx", "bn_index_read",
-    "bn_index_search", "bn_index_search_ids",
+    "bn_index_search", "bn_index_search_ids", "bn_index_assign", "bn_index_cluster",
     "bn_head_create", "bn_head_free", "bn_head_dim", "bn_head_classes", "bn_head_flags", "bn_head_read", "bn_head_apply_host",
     "bn_head_fit", "bn_head_fit_index", "bn_head_rank_index", "bn_ctx_attach_head", "bn_step_head_results",
     "bn_prior_create", "bn_prior_free", "bn_prior_sites", "bn_prior_species", "bn_prior_threshold", "bn_prior_flags", "bn_prior_read",
@@ -115,6 +115,17 @@ class BnHeadFitReport(C.Structure):
     _fields_ = [("iters", C.c_uint32), ("converged", C.c_int32), ("loss", C.c_double), ("certificate", C.c_double)]
 
 
+class BnClusterOpts(C.Structure):
+    _fields_ = [("max_iters", C.c_uint32), ("init_ids", C.POINTER(C.c_uint64)), ("init_centroids", C.POINTER(C.c_float)),
+                ("start_ids_out", C.POINTER(C.c_uint64)), ("objective_history", C.POINTER(C.c_double)), ("history_capacity", C.c_size_t)]
+
+
+class BnClusterReport(C.Structure):
+    _fields_ = [("iters", C.c_uint32), ("converged", C.c_int32), ("empty_clusters", C.c_uint32), ("moved_last", C.c_uint32),
+                ("objective", C.c_double), ("history_len", C.c_uint32)]
+
+
+BN_CLUSTER_NONE = 0xFFFFFFFF  # the assignment of a row that belongs to no cluster
 BN_HEAD_L2NORM = 1
 BN_RANK_TOP, BN_RANK_UNCERTAIN = 0, 1
 BN_PRIOR_UNKNOWN = -1.0  # table entry of a species the meta model does not know
@@ -213,6 +224,8 @@ def _load() -> C.CDLL:
         "bn_index_read": (i32, [vp, C.c_uint64, sz, f32p]),
         "bn_index_search": (i32, [vp, f32p, sz, sz, sz, C.POINTER(C.c_uint64), f32p, u32p]),
         "bn_index_search_ids": (i32, [vp, C.POINTER(C.c_uint64), sz, C.c_int64, sz, sz, C.POINTER(C.c_uint64), f32p, u32p]),
+        "bn_index_assign": (i32, [vp, f32p, sz, C.c_uint64, C.c_uint64, u32p, f32p]),
+        "bn_index_cluster": (i32, [vp, sz, C.c_uint64, C.c_uint64, C.POINTER(BnClusterOpts), sz, f32p, u32p, f32p, u32p, C.POINTER(BnClusterReport), sz]),
         "bn_head_create": (i32, [i32, sz, sz, f32p, f32p, C.c_uint32, C.POINTER(vp)]),
         "bn_head_free": (None, [vp]),
         "bn_head_dim": (sz, [vp]),
@@ -1218,6 +1231,53 @@ class Index:
         if st:
             raise EngineError(st)
         return out_ids, scores, counts
+
+    def _range(self, first_id: int, n_ids: int) -> int:
+        return max((n_ids if n_ids else len(self) - first_id), 0)
+
+    def assign(self, centroids, first_id: int = 0, n_ids: int = 0):
+        """bn_index_assign: the nearest of `centroids` [k, dim] (used as given) for rows [first_id, first_id + n_ids) (n_ids 0: to
+        the end).  Returns (assign [rows] uint32, scores [rows] float32); a row without a cluster has BN_CLUSTER_NONE and NaN."""
+        c = np.ascontiguousarray(centroids, dtype=np.float32).reshape(-1, self.dim)
+        n = self._range(first_id, n_ids)
+        assign = np.full(n, BN_CLUSTER_NONE, dtype=np.uint32)
+        scores = np.full(n, np.nan, dtype=np.float32)
+        st = lib.bn_index_assign(self._h, c.ctypes.data_as(C.POINTER(C.c_float)), c.shape[0], first_id, n_ids,
+                                 assign.ctypes.data_as(C.POINTER(C.c_uint32)), scores.ctypes.data_as(C.POINTER(C.c_float)))
+        if st:
+            raise EngineError(st)
+        return assign, scores
+
+    def cluster(self, k: int, first_id: int = 0, n_ids: int = 0, max_iters: int = 0, init_ids=None, init_centroids=None, history: int = 0):
+        """bn_index_cluster: spherical k-means of rows [first_id, first_id + n_ids) into k clusters, started from the stored rows
+        `init_ids`, from `init_centroids` [k, dim], or from the built-in max-min start.  Returns (centroids [k, dim] float32,
+        assign [rows] uint32, scores [rows] float32, counts [k] uint32, report); report = {iters, converged, empty_clusters,
+        moved_last, objective, start_ids (None under init_centroids), objective_history (the first `history` passes)}."""
+        n = self._range(first_id, n_ids)
+        cent = np.zeros((k, self.dim), dtype=np.float32)
+        assign = np.full(n, BN_CLUSTER_NONE, dtype=np.uint32)
+        scores = np.full(n, np.nan, dtype=np.float32)
+        counts = np.zeros(k, dtype=np.uint32)
+        ids = None if init_ids is None else np.ascontiguousarray(init_ids, dtype=np.uint64).reshape(-1)
+        ic = None if init_centroids is None else np.ascontiguousarray(init_centroids, dtype=np.float32).reshape(-1, self.dim)
+        if (ids is not None and ids.shape[0] != k) or (ic is not None and ic.shape[0] != k):
+            raise ValueError("init_ids / init_centroids must hold k entries")
+        start = np.zeros(k, dtype=np.uint64)
+        hist = np.full(max(history, 1), np.nan, dtype=np.float64)
+        o = BnClusterOpts(max_iters, None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_uint64)),
+                          None if ic is None else ic.ctypes.data_as(C.POINTER(C.c_float)), start.ctypes.data_as(C.POINTER(C.c_uint64)),
+                          hist.ctypes.data_as(C.POINTER(C.c_double)) if history else None, history)
+        rep = BnClusterReport()
+        st = lib.bn_index_cluster(self._h, k, first_id, n_ids, C.byref(o), C.sizeof(o), cent.ctypes.data_as(C.POINTER(C.c_float)),
+                                  assign.ctypes.data_as(C.POINTER(C.c_uint32)), scores.ctypes.data_as(C.POINTER(C.c_float)),
+                                  counts.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(rep), C.sizeof(rep))
+        if st:
+            raise EngineError(st)
+        report = {"iters": int(rep.iters), "converged": bool(rep.converged), "empty_clusters": int(rep.empty_clusters),
+                  "moved_last": int(rep.moved_last), "objective": float(rep.objective), "start_ids": None if ic is not None else start,
+                  "objective_history": hist[:int(rep.history_len)].copy()}
+        return cent, assign, scores, counts, report
+
 
 def _fit_opts(n_classes: int, l2: float, tol: float, max_iters: int, l2norm: bool, pos_weight):
     pw = None

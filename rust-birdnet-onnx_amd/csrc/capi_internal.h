@@ -1,6 +1,6 @@
 // What the translation units of the C ABI share: the plumbing every entry point repeats (the error macro, launch and device checks,
 // the packed top-K block TopkRows, results_to_host, the pinned ring PinnedRing, scoped scratch: step_common.cpp), what they need of
-// capi.cpp's private state (index.hip: bn_index_*; head.hip: bn_head_*; rank.hip: bn_head_rank_index; live.cpp: bn_step_live) and of each other (prior.hip:
+// capi.cpp's private state (index.hip: bn_index_*; head.hip: bn_head_*; rank.hip: bn_head_rank_index; cluster.hip: bn_index_assign, bn_index_cluster; live.cpp: bn_step_live) and of each other (prior.hip:
 // bn_prior_*; track.hip: bn_track_*).  A step's rows reach its stages as an argument (StepRows), never through a context's state.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -187,6 +187,11 @@ struct IndexScan {
     uint32_t *d_count = nullptr, *h_count = nullptr;
 };
 bn_status index_scan_state(bn_index *x, IndexScan *out);
+// index.hip <-> cluster.hip (bn_index_assign, bn_index_cluster): the clustering buffers of an index, owned by cluster.hip, NULL until
+// a call first needs them; bn_index_free hands them to cluster_state_free with the index's stream idle
+struct ClusterState;
+ClusterState **index_cluster_state(bn_index *x);
+void cluster_state_free(ClusterState *s);
 // head.hip -> rank.hip: what a kernel needs of a head (weights [cpad = classes rounded up to 16][dpad], bias [cpad], padding zero)
 struct HeadView {
     int device;

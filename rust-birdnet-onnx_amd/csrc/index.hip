@@ -15,7 +15,8 @@
 //     only while its entries still beat the running M-th.
 // Order everywhere: score descending, ties by id ascending (-0.0 == +0.0 through the float compare).  The candidate, the order and
 // the two merges live in topm_select.h, which rank.hip (bn_head_rank_index) shares; it also borrows this index's stream and
-// candidate buffers (index_scan_state).
+// candidate buffers (index_scan_state).  cluster.hip (bn_index_assign, bn_index_cluster) borrows the stream and keeps its own
+// buffers on the index (index_cluster_state).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -264,6 +265,7 @@ struct bn_index {
     uint32_t *d_count = nullptr;
     Cand *h_out = nullptr;  // pinned mirrors of d_out / d_count
     uint32_t *h_count = nullptr;
+    bn::ClusterState *cluster = nullptr;  // cluster.hip's buffers, allocated by the first bn_index_assign / bn_index_cluster
 };
 
 namespace {
@@ -283,6 +285,7 @@ void release(bn_index *x) {
     for (void *p : {(void *)x->slab, (void *)x->valid, (void *)x->d_stage, (void *)x->d_q, (void *)x->d_qvalid, (void *)x->d_qid, (void *)x->d_cand,
                     (void *)x->d_cand_len, (void *)x->d_out, (void *)x->d_count})
         if (p) (void)bn::gated::Free(p);
+    bn::cluster_state_free(x->cluster);
     if (x->h_out) (void)bn::gated::HostFree(x->h_out);
     if (x->h_count) (void)bn::gated::HostFree(x->h_count);
     if (x->stream) (void)bn::gated::StreamDestroy(x->stream);
@@ -369,6 +372,8 @@ bn_status bn::index_rows(bn_index *x, IndexRows *out) {
     out->size = x->size;
     return BN_OK;
 }
+
+bn::ClusterState **bn::index_cluster_state(bn_index *x) { return &x->cluster; }
 
 bn_status bn::index_scan_state(bn_index *x, IndexScan *out) {
     if (!x || !out) return set_last_error(BN_ERR_INVALID_ARG, "null index");
