@@ -11,7 +11,12 @@
 //    tensor is simply the view dims=[C,H,W], strides=[1,W*C,C] over it.
 //  * Conv+BatchNorm+activation(+residual Add) and MatMul/Gemm+bias+activation
 //    chains are folded into one launch at import time.
+//
+// The planner's other three pieces -- graph rewrites before lowering, DFT-bank recognition, passes over the finished plan -- are free
+// functions in files of their own (plan_build.h lists them); this file is Builder: one run over the graph and the lowering of every node.
 #include "engine.h"
+#include "dft_bank.h"
+#include "plan_build.h"
 #include "plan_rules.h"
 
 #include <algorithm>
@@ -25,61 +30,6 @@
 
 namespace bn {
 namespace {
-
-constexpr int64_t BATCH_SENTINEL = -1000000007;  // "the batch size" inside folded shape tensors
-
-using Dims = std::vector<int64_t>;
-
-int64_t prod(const Dims &d) {
-    int64_t n = 1;
-    for (auto v : d) n *= v;
-    return n;
-}
-Dims row_major(const Dims &d) {
-    Dims s(d.size());
-    int64_t acc = 1;
-    for (int i = (int)d.size() - 1; i >= 0; i--) {
-        s[i] = acc;
-        acc *= d[i];
-    }
-    return s;
-}
-std::string dims_str(const Dims &d) {
-    std::string s = "[";
-    for (size_t i = 0; i < d.size(); i++) s += (i ? "," : "") + std::to_string(d[i]);
-    return s + "]";
-}
-
-struct Val {
-    bool is_const = false;
-    bool is_int = false;
-    Dims dims;     // const: full dims; activation: per-sample dims
-    Dims strides;  // activation only (elements)
-    Space space = Space::NONE;
-    int32_t storage = -1;
-    int64_t offset = 0;
-    std::vector<float> f;
-    std::vector<int64_t> i;
-    // squeeze-excite: `is_gate` marks the per-channel gate vector produced by the fused SE kernel;
-    // `gate_storage >= 0` marks "x * gate" not yet applied (the consuming 1x1 conv applies it on load)
-    bool is_gate = false;
-    int32_t gate_storage = -1;
-    // (round 5) frames * window not yet applied: the constant `win_name` (vals_ key) multiplies along the `win_nu`-th NON-UNIT
-    // dimension; the DFT node that consumes the value folds it into its basis, any other consumer gets apply_window() in get()
-    std::string win_name;
-    int32_t win_nu = -1;
-    int64_t numel() const { return prod(dims); }
-    bool contiguous() const { return !is_const && strides_equal(row_major(dims)); }
-    bool strides_equal(const Dims &s) const {
-        for (size_t k = 0; k < dims.size(); k++)
-            if (dims[k] != 1 && strides[k] != s[k]) return false;
-        return true;
-    }
-};
-
-[[noreturn]] void unsupported(const OnnxNode &n, const std::string &why) {
-    throw UnsupportedModel("node '" + n.name + "' (" + n.op_type + "): " + why);
-}
 
 struct ActSpec {
     int32_t act = ACT_NONE;
@@ -103,7 +53,7 @@ class Builder {
             else { v.is_int = true; v.i = t.i; }
             vals_[t.name] = std::move(v);
         }
-        canonicalize_spectrogram_dialects();
+        canonicalize_spectrogram_dialects(m_, nodes_, vals_);
         // graph input
         const auto &in = m_.inputs[0];
         if (!in.has_shape || in.shape.size() < 2)
@@ -162,8 +112,9 @@ class Builder {
                 if (nd.inputs[k].empty()) throw UnsupportedModel("node '" + nd.name + "' (" + nd.op_type + "): required input " + std::to_string(k) + " is missing");
         }
 
-        prune_zero_rows();
-        merge_framing_products();
+        const LiveGraph graph{nodes_, vals_, live_, consumers_, wanted_names_};
+        prune_zero_rows(graph);
+        merge_framing_products(graph);
 
         for (size_t k = 0; k < nodes_.size(); k++) {
             if (!live_[k] || absorbed_[k]) continue;
@@ -187,9 +138,7 @@ class Builder {
             oi.computed = true;
             plan_.storages[v.storage].pinned = true;
         }
-        fuse_elementwise_chains();
-        pack_bf16x3_weights();
-        plan_memory();
+        run_plan_passes(plan_);
         for (auto &op : plan_.ops) {
             (op.mfma ? plan_.macs_mfma : plan_.macs_valu) += op.macs;
             plan_.macs_mfma += op.macs_mfma_extra;
@@ -199,9 +148,6 @@ class Builder {
             plan_.weight_bytes += op.weight_bytes;
             plan_.fft_flops += op.flops_fft;
         }
-        plan_.dft_gemm_macs = dft_gemm_macs_;
-        plan_.dft_performed_macs = dft_performed_macs_;
-        plan_.dft_fft_equiv_flops = dft_fft_equiv_flops_;
     }
 
    private:
@@ -213,7 +159,6 @@ class Builder {
     std::set<std::string> graph_outputs_, wanted_names_;
     std::vector<bool> live_, absorbed_;
     int cur_ = 0;
-    double dft_gemm_macs_ = 0, dft_performed_macs_ = 0, dft_fft_equiv_flops_ = 0;
 
     // ------------------------------------------------------------------ utils
     const Val &get(const OnnxNode &n, size_t idx) {
@@ -306,30 +251,10 @@ class Builder {
         v.storage = new_storage(ext);
         return v;
     }
-    int32_t add_const(const std::vector<float> &data) {
-        plan_.consts.push_back(data);
-        return (int32_t)plan_.consts.size() - 1;
-    }
+    int32_t add_const(const std::vector<float> &data) { return bn::add_const(plan_, data); }
     Ref ref_of(const Val &v) const { return Ref{v.space, v.storage, v.offset}; }
-    void touch(const Ref &r, int op_index) {
-        if (r.space != Space::ARENA) return;
-        auto &s = plan_.storages[r.id];
-        if (s.first < 0) s.first = op_index;
-        s.last = std::max(s.last, op_index);
-    }
-    void push_op(PlanOp &&op) {
-        int idx = (int)plan_.ops.size();
-        touch(op.out, idx);
-        touch(op.a, idx);
-        touch(op.b, idx);
-        touch(op.res, idx);
-        touch(op.scale, idx);
-        touch(op.w2, idx);
-        touch(op.bias2, idx);
-        for (auto &r : op.eb) touch(r, idx);
-        for (auto &r : op.x) touch(r, idx);
-        plan_.ops.push_back(std::move(op));
-    }
+    void touch(const Ref &r, int op_index) { bn::touch(plan_, r, op_index); }
+    void push_op(PlanOp &&op) { bn::push_op(plan_, std::move(op)); }
 
     // Physical order of logical dims (outermost first) for an activation.
     static std::vector<int> phys_order(const Val &v) {
@@ -441,12 +366,6 @@ class Builder {
         for (auto v : vs)
             if (v && !v->is_const) return false;
         return true;
-    }
-    Val make_const_f(const Dims &d, std::vector<float> f) {
-        Val v; v.is_const = true; v.dims = d; v.f = std::move(f); return v;
-    }
-    Val make_const_i(const Dims &d, std::vector<int64_t> i) {
-        Val v; v.is_const = true; v.is_int = true; v.dims = d; v.i = std::move(i); return v;
     }
     static Dims bcast_dims(const Dims &a, const Dims &b) {
         size_t r = std::max(a.size(), b.size());
@@ -584,800 +503,6 @@ class Builder {
         return o;
     }
 
-    // ------------------------------------------------------------- one spelling for the real / imaginary part of a spectrogram (round 5)
-    // Three exporter dialects write "the real part of an STFT" (what BirdNET v2.4 feeds its mel banks):
-    //   (a) Conv1D with the windowed cosine basis as weights -> Transpose                                  (the form every node-level pass below knows)
-    //   (b) STFT(signal, step, window) -> Gather(index c, last axis)                                        (torch.stft exports, opset 17)
-    //   (c) Reshape -> Gather(affine selector) -> Reshape  [tf.signal.frame]  -> Mul(window) -> Unsqueeze -> DFT(onesided) -> Gather(index c)
-    // (b) and (c) are rewritten into (a) here, before liveness and the passes that prune mel-dead bins, merge the mel product and pick the
-    // fold, so that all three spellings reach the same plan.  Only the exact patterns are rewritten (every intermediate has ONE consumer and
-    // is no graph output); anything else keeps its nodes and goes through lower_stft / lower_dft, which map the general case.
-    void canonicalize_spectrogram_dialects() {
-        if (sw_int(sw::BN_CANON_SPECTRO) == 0) return;
-        std::map<std::string, int> uses;
-        for (auto &nd : nodes_)
-            for (auto &i : nd.inputs)
-                if (!i.empty()) uses[i]++;
-        for (auto &o : m_.outputs) uses[o.name] += 2;  // a graph output is never an intermediate
-        std::map<std::string, int> producer;
-        for (size_t k = 0; k < nodes_.size(); k++)
-            for (auto &o : nodes_[k].outputs) producer[o] = (int)k;
-        auto cval = [&](const std::string &name) -> const Val * {
-            auto it = vals_.find(name);
-            return it != vals_.end() && it->second.is_const ? &it->second : nullptr;
-        };
-        auto ints = [&](const std::string &name, std::vector<int64_t> &out) {
-            const Val *v = cval(name);
-            if (!v) return false;
-            out = v->is_int ? v->i : std::vector<int64_t>(v->f.begin(), v->f.end());
-            return true;
-        };
-        auto sole_prod = [&](const std::string &t, const char *op) -> int {  // producer of t if it is `op` and t has one use
-            auto it = producer.find(t);
-            if (it == producer.end() || nodes_[it->second].op_type != op || uses[t] != 1) return -1;
-            return it->second;
-        };
-        std::vector<char> dead(nodes_.size(), 0);
-        std::vector<std::vector<OnnxNode>> repl(nodes_.size());
-        int serial = 0;
-        for (size_t gk = 0; gk < nodes_.size(); gk++) {
-            const OnnxNode &pick = nodes_[gk];
-            if (pick.op_type != "Gather" || pick.inputs.size() != 2) continue;
-            std::vector<int64_t> ci;
-            const Val *civ = cval(pick.inputs[1]);
-            if (!civ || civ->numel() != 1 || !civ->dims.empty() || !ints(pick.inputs[1], ci) || (ci[0] != 0 && ci[0] != 1)) continue;
-            const int64_t gax = pick.attr_i("axis", 0);
-            if (gax != 3 && gax != -1) continue;
-            std::string signal;
-            std::vector<float> window;
-            int64_t N = 0, hop = 0;
-            std::vector<int> chain;
-            int k1 = sole_prod(pick.inputs[0], "STFT");
-            if (k1 >= 0) {                                                      // ---- (b)
-                const OnnxNode &st = nodes_[k1];
-                std::vector<int64_t> stepv, lenv;
-                if (st.attr_i("onesided", 1) == 0 || st.inputs.size() < 2 || !ints(st.inputs[1], stepv) || stepv.size() != 1) continue;
-                const Val *w = st.inputs.size() > 2 && !st.inputs[2].empty() ? cval(st.inputs[2]) : nullptr;
-                if (st.inputs.size() > 2 && !st.inputs[2].empty() && (!w || w->is_int)) continue;
-                if (st.inputs.size() > 3 && !st.inputs[3].empty()) { if (!ints(st.inputs[3], lenv) || lenv.size() != 1) continue; N = lenv[0]; }
-                else if (w) N = w->numel();
-                if (N < 2 || (w && w->numel() != N)) continue;
-                if (w) window = w->f;
-                hop = stepv[0];
-                signal = st.inputs[0];
-                chain = {k1};
-            } else if ((k1 = sole_prod(pick.inputs[0], "DFT")) >= 0) {            // ---- (c)
-                const OnnxNode &df = nodes_[k1];
-                if (df.attr_i("onesided", 0) == 0 || df.attr_i("inverse", 0) != 0 || df.inputs.size() != 1) continue;
-                const int64_t dax = df.has("axis") ? df.attr_i("axis", 1) : (m_.opset >= 20 ? -2 : 1);
-                if (dax != 2 && dax != -2) continue;
-                const int ku = sole_prod(df.inputs[0], "Unsqueeze");
-                if (ku < 0) continue;
-                std::vector<int64_t> ax = nodes_[ku].attr_ints("axes");
-                if (ax.empty() && (nodes_[ku].inputs.size() < 2 || !ints(nodes_[ku].inputs[1], ax))) continue;
-                if (ax.size() != 1 || (ax[0] != 3 && ax[0] != -1)) continue;
-                std::string fr = nodes_[ku].inputs[0];
-                chain = {k1, ku};
-                const int km = sole_prod(fr, "Mul");
-                if (km >= 0) {
-                    const OnnxNode &mu = nodes_[km];
-                    const Val *w0 = cval(mu.inputs[0]), *w1 = cval(mu.inputs[1]);
-                    const Val *w = w0 ? w0 : w1;
-                    if (!w || (w0 && w1) || w->is_int) continue;
-                    int nu = 0;
-                    for (auto d : w->dims) nu += d != 1;
-                    if (nu != 1 || w->dims.empty() || w->dims.back() != w->numel()) continue;  // along the frames' last axis
-                    window = w->f;
-                    fr = mu.inputs[w0 ? 1 : 0];
-                    chain.push_back(km);
-                }
-                // tf.signal.frame: Reshape [0|-1, S / sub, sub] -> Gather(axis 1, selector[f][j] = f * h + j) -> Reshape [0|-1, F, L]
-                const int kr2 = sole_prod(fr, "Reshape");
-                if (kr2 < 0) continue;
-                std::vector<int64_t> shp2, shp0;
-                if (!ints(nodes_[kr2].inputs[1], shp2) || shp2.size() != 3) continue;
-                const int kg = sole_prod(nodes_[kr2].inputs[0], "Gather");
-                if (kg < 0 || nodes_[kg].attr_i("axis", 0) != 1) continue;
-                const Val *sel = cval(nodes_[kg].inputs[1]);
-                if (!sel || !sel->is_int || sel->dims.size() != 2) continue;
-                const int kr0 = sole_prod(nodes_[kg].inputs[0], "Reshape");
-                if (kr0 < 0 || !ints(nodes_[kr0].inputs[1], shp0) || shp0.size() != 3) continue;
-                const int64_t F = sel->dims[0], J = sel->dims[1], sub = shp0[2];
-                if (sub < 1 || F < 1 || J < 1 || shp2[1] != F || shp2[2] != J * sub) continue;
-                const int64_t h = F > 1 ? sel->i[(size_t)J] - sel->i[0] : 1;
-                bool affine = sel->i[0] == 0 && h >= 1;
-                for (int64_t f = 0; f < F && affine; f++)
-                    for (int64_t j = 0; j < J && affine; j++) affine = sel->i[(size_t)(f * J + j)] == f * h + j;
-                // (the Conv frames the WHOLE signal: the selector must take every frame that fits)
-                if (!affine || shp0[1] < (F - 1) * h + J || F != (shp0[1] - J) / h + 1) continue;
-                N = J * sub;
-                hop = h * sub;
-                if (!window.empty() && (int64_t)window.size() != N) continue;
-                signal = nodes_[kr0].inputs[0];
-                chain.insert(chain.end(), {kr2, kg, kr0});
-            } else continue;
-            if (hop < 1 || N > 8192) continue;
-            const int64_t bins = N / 2 + 1;
-            Val basis;
-            basis.is_const = true;
-            basis.dims = {bins, 1, N};
-            basis.f.resize((size_t)(bins * N));
-            for (int64_t k = 0; k < bins; k++)
-                for (int64_t t = 0; t < N; t++) {
-                    const double wv = window.empty() ? 1.0 : (double)window[(size_t)t];
-                    const double th = 2.0 * M_PI * (double)((k * t) % N) / (double)N;
-                    basis.f[(size_t)(k * N + t)] = (float)(ci[0] == 0 ? wv * std::cos(th) : -wv * std::sin(th));
-                }
-            const std::string base = "spectro" + std::to_string(serial++) + ":" + pick.outputs[0];
-            vals_[base + "/basis"] = std::move(basis);
-            vals_[base + "/shape"] = make_const_i({3}, {0, 1, -1});
-            OnnxNode rs = synth_node("Reshape", base + "/signal", {signal, base + "/shape"}, base + "/signal");
-            OnnxNode conv = synth_node("Conv", (pick.name.empty() ? pick.outputs[0] : pick.name) + (ci[0] == 0 ? "~re" : "~im"), {base + "/signal", base + "/basis"}, base + "/bank");
-            set_ints(conv, "strides", {hop});
-            set_ints(conv, "kernel_shape", {N});
-            OnnxNode tr = synth_node("Transpose", base + "/t", {base + "/bank"}, pick.outputs[0]);
-            set_ints(tr, "perm", {0, 2, 1});
-            repl[gk] = {rs, conv, tr};
-            dead[gk] = 1;
-            for (int c : chain) dead[(size_t)c] = 1;
-        }
-        if (!serial) return;
-        std::vector<OnnxNode> out;
-        for (size_t k = 0; k < nodes_.size(); k++) {
-            for (auto &r : repl[k]) out.push_back(r);
-            if (!dead[k]) out.push_back(nodes_[k]);
-        }
-        nodes_ = std::move(out);
-    }
-
-    // ------------------------------------------------------------- pruning
-    // Conv(out channels c) -> [Transpose] -> MatMul(const W[c, :]): output channels whose W row is
-    // all zero never influence the result, drop them (mel filterbanks cover a fraction of the bins).
-    void prune_zero_rows() {
-        for (size_t k = 0; k < nodes_.size(); k++) {
-            if (!live_[k] || nodes_[k].op_type != "Conv") continue;
-            OnnxNode &conv = nodes_[k];
-            int c1 = sole_consumer(conv.outputs[0]);
-            if (c1 < 0) continue;
-            int mm = -1;
-            if (nodes_[c1].op_type == "Transpose") {
-                auto perm = nodes_[c1].attr_ints("perm");
-                if (perm != std::vector<int64_t>{0, 2, 1}) continue;
-                mm = sole_consumer(nodes_[c1].outputs[0]);
-            } else continue;
-            if (mm < 0 || nodes_[mm].op_type != "MatMul") continue;
-            auto wi = vals_.find(nodes_[mm].inputs[1]);
-            auto cw = vals_.find(conv.inputs[1]);
-            if (wi == vals_.end() || cw == vals_.end() || !wi->second.is_const || !cw->second.is_const) continue;
-            Val &W = wi->second;
-            Val &CW = cw->second;
-            if (W.dims.size() != 2 || CW.dims.empty() || W.dims[0] != CW.dims[0] || W.is_int) continue;
-            // weights must not be shared with other nodes
-            if (live_consumers(nodes_[mm].inputs[1]).size() != 1 || live_consumers(conv.inputs[1]).size() != 1) continue;
-            int64_t C = W.dims[0], N = W.dims[1];
-            std::vector<int64_t> keep;
-            for (int64_t c = 0; c < C; c++) {
-                bool nz = false;
-                for (int64_t j = 0; j < N && !nz; j++) nz = W.f[c * N + j] != 0.0f;
-                if (nz) keep.push_back(c);
-            }
-            if ((int64_t)keep.size() == C || keep.empty()) continue;
-            // keep a multiple of 4 channels (a few dead neighbours stay): the consumer GEMM's K is then a whole number
-            // of float4 loads for both operands instead of scalar loads (K = 309 -> 312, 127 -> 128)
-            {
-                std::vector<char> kept((size_t)C, 0);
-                for (int64_t c : keep) kept[(size_t)c] = 1;
-                for (int64_t c = keep.back() + 1; c < C && keep.size() % 4; c++) { kept[(size_t)c] = 1; keep.push_back(c); }
-                for (int64_t c = keep.front() - 1; c >= 0 && keep.size() % 4; c--) { kept[(size_t)c] = 1; keep.push_back(c); }
-                std::sort(keep.begin(), keep.end());
-                if ((int64_t)keep.size() == C) continue;
-            }
-            int64_t per = CW.numel() / C;
-            std::vector<float> nw(keep.size() * per), nW(keep.size() * N);
-            for (size_t r = 0; r < keep.size(); r++) {
-                std::copy(CW.f.begin() + keep[r] * per, CW.f.begin() + (keep[r] + 1) * per, nw.begin() + r * per);
-                std::copy(W.f.begin() + keep[r] * N, W.f.begin() + (keep[r] + 1) * N, nW.begin() + r * N);
-            }
-            CW.f = nw; CW.dims[0] = (int64_t)keep.size();
-            W.f = nW; W.dims[0] = (int64_t)keep.size();
-            if (conv.inputs.size() > 2 && !conv.inputs[2].empty()) {
-                auto bi = vals_.find(conv.inputs[2]);
-                if (bi != vals_.end() && bi->second.is_const && live_consumers(conv.inputs[2]).size() == 1) {
-                    std::vector<float> nb(keep.size());
-                    for (size_t r = 0; r < keep.size(); r++) nb[r] = bi->second.f[keep[r]];
-                    bi->second.f = nb; bi->second.dims[0] = (int64_t)keep.size();
-                }
-            }
-        }
-    }
-
-    // ------------------------------------------------------------- framing conv x constant product -> one framing conv (round 4)
-    // Conv1D(one input channel, C filters of length L) -> Transpose -> MatMul(const W[C, N]) is ONE linear map of the frame when nothing
-    // sits between the two (v2.4 takes the REAL PART of its STFT straight into the mel bank): N filters  sum_c W[c][n] w_c  of length L,
-    // bias  sum_c W[c][n] b_c.  Worth it when N filters cost less than the C filters (as an FFT or as folded matrix products) plus the
-    // product: v2.4's 312 mel-live bins of the 1024-point branch -> 96 mel filters of 512 folded taps (the rows stay symmetric about the
-    // frame centre), against an FFT of every frame plus the mel phase; NOT its 127 bins of the 2048-point branch, which the quarter fold
-    // evaluates in 512 taps each where 96 merged filters would need 1024.  Costs in f32-MFMA SIMD-cycles per frame, the scale emit_stft
-    // calibrated.  The filters are summed in double and rounded once.  BN_CONVMERGE=0 disables, =1 merges wherever the pattern matches.
-    void merge_framing_products() {
-        const int mode = sw_int(sw::BN_CONVMERGE);
-        if (mode == 0) return;
-        if (sw_is(sw::BN_STFT, "1") && mode != 1) return;  // every recognised bank as an FFT: the banks stay banks
-        for (size_t k = 0; k < nodes_.size(); k++) {
-            if (!live_[k] || nodes_[k].op_type != "Conv") continue;
-            OnnxNode &conv = nodes_[k];
-            const int c1 = sole_consumer(conv.outputs[0]);
-            if (c1 < 0 || nodes_[c1].op_type != "Transpose" || nodes_[c1].attr_ints("perm") != std::vector<int64_t>{0, 2, 1}) continue;
-            const int mm = sole_consumer(nodes_[c1].outputs[0]);
-            if (mm < 0 || nodes_[mm].op_type != "MatMul" || nodes_[mm].inputs[0] != nodes_[c1].outputs[0]) continue;
-            auto wi = vals_.find(nodes_[mm].inputs[1]);
-            auto cw = vals_.find(conv.inputs[1]);
-            if (wi == vals_.end() || cw == vals_.end() || !wi->second.is_const || !cw->second.is_const || wi->second.is_int || cw->second.is_int) continue;
-            Val &W = wi->second;
-            Val &CW = cw->second;
-            if (W.dims.size() != 2 || CW.dims.size() != 3 || CW.dims[1] != 1 || W.dims[0] != CW.dims[0]) continue;  // [C, 1, L] x [C, N]
-            if (live_consumers(nodes_[mm].inputs[1]).size() != 1 || live_consumers(conv.inputs[1]).size() != 1) continue;
-            if (conv.attr_i("group", 1) != 1) continue;
-            const int64_t C = CW.dims[0], L = CW.dims[2], N = W.dims[1];
-            if (L < 128 || N >= C) continue;
-            Val *bias = nullptr;
-            if (conv.inputs.size() > 2 && !conv.inputs[2].empty()) {
-                auto bi = vals_.find(conv.inputs[2]);
-                if (bi == vals_.end() || !bi->second.is_const || bi->second.is_int || live_consumers(conv.inputs[2]).size() != 1) continue;
-                bias = &bi->second;
-            }
-            // symmetry of the rows about the frame centre (the fold rule's test, its tolerance)
-            float maxabs = 0.0f;
-            for (float v : CW.f) maxabs = std::max(maxabs, std::fabs(v));
-            const float eps = 1.1920929e-7f * maxabs;
-            bool all_sym = L % 64 == 0, all_folded = L % 64 == 0;
-            for (int64_t c = 0; c < C && all_folded; c++) {
-                const float *w = &CW.f[(size_t)(c * L)];
-                bool sym = std::fabs(w[0]) <= eps, anti = sym && std::fabs(w[L / 2]) <= eps;
-                for (int64_t t = 1; t < L / 2 && (sym || anti); t++) {
-                    if (!(std::fabs(w[t] - w[L - t]) <= eps)) sym = false;
-                    if (!(std::fabs(w[t] + w[L - t]) <= eps)) anti = false;
-                }
-                all_sym = all_sym && sym;
-                all_folded = all_folded && (sym || anti);
-            }
-            // separate: the cheapest form the bank may take + the product; merged: N filters, folded if every row is symmetric
-            const bool fft_size = L <= 2048 && ((L & (L - 1)) == 0 || fft_five_pow2(L));
-            double bank = (double)C * (double)(all_folded ? L / 2 : L) / 32.0;
-            bool product_inside = false;
-            if (all_sym && L % 128 == 0 && C <= 160) bank = std::min(bank, (double)C * (double)(L / 4 + 1) / 32.0);  // quarter fold
-            if (all_folded && fft_size && !sw_is(sw::BN_STFT, "0")) {
-                const double fft = 0.18 * (double)L * std::log2((double)L);  // (with its mel phase: emit_stft's calibration)
-                if (fft < bank) { bank = fft; product_inside = true; }
-            }
-            const double separate = bank + (product_inside ? 0.0 : (double)C * (double)N / 32.0);
-            const double merged = (double)N * (double)(all_sym ? L / 2 : L) / 32.0;
-            if (mode != 1 && !(merged < 0.9 * separate)) continue;
-            std::vector<float> nw((size_t)(N * L));
-            std::vector<double> acc((size_t)L);
-            for (int64_t n2 = 0; n2 < N; n2++) {
-                std::fill(acc.begin(), acc.end(), 0.0);
-                for (int64_t c = 0; c < C; c++) {
-                    const double m = (double)W.f[(size_t)(c * N + n2)];
-                    if (m == 0.0) continue;
-                    const float *w = &CW.f[(size_t)(c * L)];
-                    for (int64_t t = 0; t < L; t++) acc[(size_t)t] += m * (double)w[t];
-                }
-                for (int64_t t = 0; t < L; t++) nw[(size_t)(n2 * L + t)] = (float)acc[(size_t)t];
-                if (all_sym) {  // exactly symmetric again after the rounding (the fold keeps the first half)
-                    nw[(size_t)(n2 * L)] = 0.0f;
-                    for (int64_t t = 1; t < L / 2; t++) nw[(size_t)(n2 * L + L - t)] = nw[(size_t)(n2 * L + t)];
-                }
-            }
-            if (bias) {
-                std::vector<float> nb((size_t)N);
-                for (int64_t n2 = 0; n2 < N; n2++) {
-                    double a = 0.0;
-                    for (int64_t c = 0; c < C; c++) a += (double)W.f[(size_t)(c * N + n2)] * (double)bias->f[(size_t)c];
-                    nb[(size_t)n2] = (float)a;
-                }
-                bias->f = nb;
-                bias->dims[0] = N;
-            }
-            CW.f = nw;
-            CW.dims[0] = N;
-            // the product is gone: its node hands the transposed conv result on
-            OnnxNode &prod = nodes_[mm];
-            prod.op_type = "Identity";
-            prod.inputs.resize(1);
-        }
-    }
-
-    // ------------------------------------------------------------- windowed-DFT filter banks -> real FFT
-    // A single-channel 1-D filter bank whose every row is  a_c * w[n] * cos(2 pi k_c n / L)  (symmetric rows) or
-    // b_c * w[n] * sin(2 pi k_c n / L)  (antisymmetric rows) for ONE common window w and integer bins k_c is a
-    // short-time Fourier transform: out[c] = a_c Re Y[k_c] - b_c Im Y[k_c] with Y = FFT(w . frame).  The bank is
-    // recognised from the numbers alone (the exporter's node names say nothing): bins by the peak of each row's
-    // spectrum, window and amplitudes by alternating least squares over all rows, and the model is accepted only if
-    // every tap of every row agrees with it within f32 rounding of the taps (BN_STFT_TOL x max|row|, default 4e-7).
-    // Then ONE launch of stft_kernel (kernels.h, FftDesc) computes all rows -- cos and sin blocks together -- instead
-    // of one folded GEMM per symmetry run.  L must be a power of two in 128..2048, or five times a power of two (Perch's L = 640:
-    // mixed radix 5 x 4 x 16).  Whether a recognised bank runs as an FFT: emit_stft.
-    struct DftBank {
-        int64_t L = 0;
-        std::vector<float> window;
-        std::vector<int> k;
-        std::vector<double> a, b;
-    };
-    static void host_fft(std::vector<double> &re, std::vector<double> &im) {  // in-place radix-2, n a power of two
-        const size_t n = re.size();
-        for (size_t i = 1, j = 0; i < n; i++) {
-            size_t bit = n >> 1;
-            for (; j & bit; bit >>= 1) j ^= bit;
-            j ^= bit;
-            if (i < j) { std::swap(re[i], re[j]); std::swap(im[i], im[j]); }
-        }
-        for (size_t len = 2; len <= n; len <<= 1) {
-            const double ang = -2.0 * M_PI / (double)len;
-            for (size_t i = 0; i < n; i += len)
-                for (size_t k = 0; k < len / 2; k++) {
-                    const double wr = std::cos(ang * (double)k), wi = std::sin(ang * (double)k);
-                    const size_t u = i + k, v = i + k + len / 2;
-                    const double xr = re[v] * wr - im[v] * wi, xi = re[v] * wi + im[v] * wr;
-                    re[v] = re[u] - xr; im[v] = im[u] - xi;
-                    re[u] += xr; im[u] += xi;
-                }
-        }
-    }
-    // L = 10 * 4^j * 16 ... in the kernel's terms: M = L / 2 = 5 q with q = 4^j * 16 a power of FOUR times 16 (radix 5 first, then
-    // radix-4 passes down to the 16-point register blocks; a radix-2 pass exists only as a FIRST pass) -- 640 is the one in use
-    static bool fft_five_pow2(int64_t L) {
-        if (L % 10) return false;
-        int64_t q = L / 10;
-        if (q < 64 || (q & (q - 1))) return false;
-        int lg = 0;
-        while (((int64_t)1 << lg) < q) lg++;
-        return lg % 2 == 0;  // q = 16 * 4^j
-    }
-    // bins 0 .. n/2 of the DFT of a real row by the definition (any n; the peak search below reads no other bin)
-    static void host_dft_half(std::vector<double> &re, std::vector<double> &im) {
-        const size_t n = re.size();
-        std::vector<double> c(n), s_(n), xr(re);
-        for (size_t t = 0; t < n; t++) { c[t] = std::cos(2.0 * M_PI * (double)t / (double)n); s_[t] = std::sin(2.0 * M_PI * (double)t / (double)n); }
-        for (size_t k = 0; k <= n / 2; k++) {
-            double ar = 0, ai = 0;
-            for (size_t t = 0; t < n; t++) {
-                const size_t ph = (k * t) % n;
-                ar += xr[t] * c[ph];
-                ai -= xr[t] * s_[ph];
-            }
-            re[k] = ar; im[k] = ai;
-        }
-    }
-    bool detect_dft_bank(const std::vector<float> &wf, int64_t Cout, int64_t L, const std::vector<int> &cls, DftBank &bank) {
-        const bool pow2 = (L & (L - 1)) == 0;
-        if (L < 128 || L > 2048 || !(pow2 || fft_five_pow2(L))) return false;
-        const double tol = sw_double(sw::BN_STFT_TOL);
-        bank.L = L;
-        bank.k.assign((size_t)Cout, 0);
-        bank.a.assign((size_t)Cout, 0.0);
-        bank.b.assign((size_t)Cout, 0.0);
-        std::vector<double> rowmax((size_t)Cout, 0.0);
-        std::vector<char> is_sin((size_t)Cout, 0), live((size_t)Cout, 0);
-        double gmax = 0;
-        for (float v : wf) gmax = std::max(gmax, (double)std::fabs(v));
-        for (int64_t c = 0; c < Cout; c++) {
-            const float *w = &wf[(size_t)(c * L)];
-            double mx = 0;
-            for (int64_t n = 0; n < L; n++) mx = std::max(mx, (double)std::fabs(w[n]));
-            rowmax[(size_t)c] = mx;
-            // a row whose largest tap is below f32 resolution of the bank's largest tap (sin(pi n) of the Nyquist bin
-            // evaluated in floating point: ~1e-13) counts as the zero row it stands for
-            if (!(mx > 1e-7 * gmax)) continue;
-            live[(size_t)c] = 1;
-            is_sin[(size_t)c] = cls[(size_t)c] < 0;
-            std::vector<double> re(w, w + L), im((size_t)L, 0.0);
-            if (pow2) host_fft(re, im);
-            else host_dft_half(re, im);
-            int best = 0;
-            double bm = -1;
-            for (int64_t q = 0; q <= L / 2; q++) {
-                const double m2 = re[(size_t)q] * re[(size_t)q] + im[(size_t)q] * im[(size_t)q];
-                if (m2 > bm) { bm = m2; best = (int)q; }
-            }
-            bank.k[(size_t)c] = best;
-        }
-        // unit sinusoids of every live row, from one table of cos(2 pi t / L)
-        std::vector<double> ctab((size_t)L);
-        for (int64_t t = 0; t < L; t++) ctab[(size_t)t] = std::cos(2.0 * M_PI * (double)t / (double)L);
-        auto trig = [&](int64_t c, int64_t n) {
-            const int64_t ph = ((int64_t)bank.k[(size_t)c] * n) % L;  // exact phase reduction
-            return is_sin[(size_t)c] ? ctab[(size_t)((ph + 3 * L / 4) % L)] : ctab[(size_t)ph];  // sin x = cos(x - pi/2)
-        };
-        std::vector<double> amp((size_t)Cout, 0.0), win((size_t)L, 0.0), energy((size_t)Cout, 0.0);
-        for (int64_t c = 0; c < Cout; c++) {
-            if (!live[(size_t)c]) continue;
-            double e = 0;
-            for (int64_t n = 0; n < L; n++) e += (double)wf[(size_t)(c * L + n)] * wf[(size_t)(c * L + n)];
-            energy[(size_t)c] = e;
-        }
-        // start from the row energy: sum (w t)^2 is ~ sum w^2 / 2 for a sinusoid, sum w^2 for the DC / Nyquist rows
-        // (the sign settles in the first amplitude step)
-        auto init_amp = [&](int64_t c) {
-            const int k = bank.k[(size_t)c];
-            amp[(size_t)c] = std::sqrt(energy[(size_t)c] * ((k == 0 || k == L / 2) ? 1.0 : 2.0));
-        };
-        std::vector<char> use((size_t)Cout, 0);
-        auto als = [&](int max_it) {
-            for (int it = 0; it < max_it; it++) {
-                for (int64_t n = 0; n < L; n++) {
-                    double num = 0, den = 0;
-                    for (int64_t c = 0; c < Cout; c++) {
-                        if (!use[(size_t)c]) continue;
-                        const double t = amp[(size_t)c] * trig(c, n);
-                        num += t * (double)wf[(size_t)(c * L + n)];
-                        den += t * t;
-                    }
-                    win[(size_t)n] = den > 0 ? num / den : 0.0;
-                }
-                double wmax = 0;
-                for (double v : win) wmax = std::max(wmax, std::fabs(v));
-                if (!(wmax > 0)) return false;
-                for (double &v : win) v /= wmax;
-                double change = 0;
-                for (int64_t c = 0; c < Cout; c++) {
-                    if (!use[(size_t)c]) continue;
-                    double num = 0, den = 0;
-                    for (int64_t n = 0; n < L; n++) {
-                        const double t = win[(size_t)n] * trig(c, n);
-                        num += t * (double)wf[(size_t)(c * L + n)];
-                        den += t * t;
-                    }
-                    if (!(den > 0)) return false;  // e.g. a sine row at bin 0: identically zero model, non-zero row
-                    const double na = num / den;
-                    change = std::max(change, std::fabs(na - amp[(size_t)c]) / std::max(std::fabs(na), 1e-300));
-                    amp[(size_t)c] = na;
-                }
-                if (it > 0 && change < 1e-11) break;
-            }
-            return true;
-        };
-        // stage 1: rows whose spectral peak is unambiguous (bins 3 .. L/2 - 3: near DC and Nyquist the two mirror
-        // lobes of a windowed sinusoid overlap and the peak can sit one bin off) give a first window estimate
-        int64_t n_sure = 0;
-        for (int64_t c = 0; c < Cout; c++) {
-            use[(size_t)c] = live[(size_t)c] && bank.k[(size_t)c] >= 3 && bank.k[(size_t)c] <= L / 2 - 3;
-            n_sure += use[(size_t)c];
-            if (live[(size_t)c]) init_amp(c);
-        }
-        if (n_sure == 0)
-            for (int64_t c = 0; c < Cout; c++) use[(size_t)c] = live[(size_t)c];
-        // The amplitude SIGNS are unknown at this point (exporters write -sin rows next to +cos rows: with all-positive
-        // starting amplitudes the cos^2 and sin^2 contributions to a least-squares window cancel), so the first window
-        // comes from energies, which do not see signs: sum_c R_c[n]^2 = w[n]^2 sum_c a_c^2 t_c[n]^2, w >= 0 as every
-        // analysis window in use is.  The first amplitude step then settles the signs.
-        {
-            double wmax = 0;
-            for (int64_t n = 0; n < L; n++) {
-                double num = 0, den = 0;
-                for (int64_t c = 0; c < Cout; c++) {
-                    if (!use[(size_t)c]) continue;
-                    const double t = amp[(size_t)c] * trig(c, n), r = (double)wf[(size_t)(c * L + n)];
-                    num += r * r;
-                    den += t * t;
-                }
-                win[(size_t)n] = den > 0 ? std::sqrt(num / den) : 0.0;
-                wmax = std::max(wmax, win[(size_t)n]);
-            }
-            if (!(wmax > 0)) return false;
-            for (double &v : win) v /= wmax;
-            for (int64_t c = 0; c < Cout; c++) {
-                if (!use[(size_t)c]) continue;
-                double num = 0, den = 0;
-                for (int64_t n = 0; n < L; n++) {
-                    const double t = win[(size_t)n] * trig(c, n);
-                    num += t * (double)wf[(size_t)(c * L + n)];
-                    den += t * t;
-                }
-                if (!(den > 0)) return false;
-                amp[(size_t)c] = num / den;
-            }
-        }
-        if (!als(3)) return false;
-        // stage 2: every row's bin re-decided among the neighbours of its peak by the least-squares residual against
-        // that window
-        for (int64_t c = 0; c < Cout; c++) {
-            if (!live[(size_t)c]) continue;
-            const int k0 = bank.k[(size_t)c];
-            int best = k0;
-            double best_res = INFINITY;
-            for (int k = std::max(0, k0 - 2); k <= std::min<int>((int)(L / 2), k0 + 2); k++) {
-                bank.k[(size_t)c] = k;
-                double num = 0, den = 0;
-                for (int64_t n = 0; n < L; n++) {
-                    const double t = win[(size_t)n] * trig(c, n);
-                    num += t * (double)wf[(size_t)(c * L + n)];
-                    den += t * t;
-                }
-                const double res = den > 0 ? energy[(size_t)c] - num * num / den : INFINITY;
-                if (res < best_res) { best_res = res; best = k; }
-            }
-            if (sw_present(sw::BN_STFT_DEBUG) && (c < 4 || best != k0))
-                fprintf(stderr, "stft: row %lld %s peak bin %d -> %d (residual %.3g of energy %.3g)\n", (long long)c, is_sin[(size_t)c] ? "sin" : "cos", k0, best,
-                        best_res, energy[(size_t)c]);
-            bank.k[(size_t)c] = best;
-            {  // amplitude (with its sign) against the stage-1 window
-                double num = 0, den = 0;
-                for (int64_t n = 0; n < L; n++) {
-                    const double t = win[(size_t)n] * trig(c, n);
-                    num += t * (double)wf[(size_t)(c * L + n)];
-                    den += t * t;
-                }
-                if (!(den > 0)) return false;
-                amp[(size_t)c] = num / den;
-            }
-            use[(size_t)c] = 1;
-        }
-        // stage 3: all rows
-        if (!als(40)) return false;
-        // the window in f32 (what the kernel multiplies by); amplitudes refitted against the rounded window, then verify
-        bank.window.resize((size_t)L);
-        for (int64_t n = 0; n < L; n++) bank.window[(size_t)n] = (float)win[(size_t)n];
-        for (int64_t c = 0; c < Cout; c++) {
-            if (!live[(size_t)c]) continue;
-            for (int64_t n = 0; n < L; n++) {
-                const double model = amp[(size_t)c] * win[(size_t)n] * trig(c, n);
-                if (!(std::fabs(model - (double)wf[(size_t)(c * L + n)]) <= tol * rowmax[(size_t)c])) {
-                    if (sw_present(sw::BN_STFT_DEBUG))
-                        fprintf(stderr, "stft: row %lld (bin %d, %s) tap %lld: model %.9g vs %.9g (row max %.3g)\n", (long long)c, bank.k[(size_t)c],
-                                is_sin[(size_t)c] ? "sin" : "cos", (long long)n, model, (double)wf[(size_t)(c * L + n)], rowmax[(size_t)c]);
-                    return false;
-                }
-            }
-            if (is_sin[(size_t)c]) bank.b[(size_t)c] = amp[(size_t)c];
-            else bank.a[(size_t)c] = amp[(size_t)c];
-        }
-        return true;
-    }
-    // digit-reversed position of output k of an in-place DIF transform with the given radix sequence
-    static int dif_position(int k, int n, const std::vector<int> &radix, size_t idx) {
-        if (n == 1) return 0;
-        const int r = radix[idx];
-        return (k % r) * (n / r) + dif_position(k / r, n / r, radix, idx + 1);
-    }
-    bool emit_stft(const OnnxNode &n, const PlanOp &base, const DftBank &bank, int64_t Cout, int64_t OW, bool has_bias) {
-        // Which banks run as FFTs.  The alternative is the pruned + folded matrix product on the exact-f32 MFMA path, whose
-        // cost follows the number of LIVE bins: Cout * L/2 multiply-adds at 32 per SIMD-cycle, against roughly
-        // 0.18 * L * log2 L cycles of vector butterflies, address arithmetic and LDS traffic for the FFT plus its untangle
-        // and mel phases (both calibrated on the v2.4 banks, DESIGN.md section 4.11: L = 2048 with 127 live bins -- matrix
-        // product 69 us, FFT 76-93 us; L = 1024 with 309 live bins -- 85 us vs 62-75 us).  Default ("auto"): FFT when the
-        // matrix product is estimated at more than 1.5x the FFT.  BN_STFT=1: every recognised bank; BN_STFT=0: none;
-        // BN_STFT_MINBINS=<n> additionally keeps banks with fewer live bins on the matrix path.
-        if (sw_is(sw::BN_STFT, "0")) return false;
-        if (Cout < sw_i64(sw::BN_STFT_MINBINS)) return false;
-        if (!sw_is(sw::BN_STFT, "1")) {
-            const double lg = std::log2((double)bank.L);
-            const double gemm_cycles = (double)Cout * (double)(bank.L / 2) / 32.0, fft_cycles = 0.18 * (double)bank.L * lg;
-            if (!(gemm_cycles > 1.5 * fft_cycles)) return false;
-        }
-        const GemmDesc &g = base.gemm;
-        if (g.act != ACT_NONE || g.has_res || g.has_scale || g.lda <= 0 || g.lda > 4096 || g.ldc != Cout) return false;
-        const int L = (int)bank.L, M = L / 2;
-        PlanOp op;
-        op.kind = OpKind::FFT;
-        op.name = "stft:" + n.name;
-        op.out = base.out;
-        op.a = base.a;
-        op.bias = base.bias;
-        FftDesc &d = op.fft;
-        d.L = L; d.M = M; d.hop = (int32_t)g.lda; d.frames = (int32_t)OW; d.nout = (int32_t)Cout;
-        d.logM = 0;
-        while ((1 << d.logM) < M) d.logM++;
-        d.F = 1024 / M;
-        const bool five = M % 5 == 0;  // M = 5 q (detect_dft_bank: q = 16 * 4^j): three frames of 320 slots per wave pass
-        // frames per tile: as many as keep the tile's signal span within the kernel's staging registers (8192 floats)
-        if (five) {
-            // whole wave passes, one per wave of the block where the span allows: 8 waves x F frames
-            d.tpb = 8 * d.F;
-            while (d.tpb > d.F && (int64_t)(d.tpb - 1) * g.lda + L > 8192) d.tpb -= d.F;
-        } else {
-            d.tpb = 16;
-            while (d.tpb > d.F && (int64_t)(d.tpb - 1) * g.lda + L > 8192) d.tpb /= 2;
-        }
-        if ((int64_t)(d.tpb - 1) * g.lda + L > 8192 || d.tpb % d.F) return false;
-        d.a_bs = g.a_bs; d.ldc = g.ldc; d.c_bs = g.c_bs; d.has_bias = has_bias ? 1 : 0;
-        d.out_rs = g.ldc; d.out_cs = 1;
-        d.power = 0; d.otab_stride = 8;
-        // pass structure: radix 5 first for M = 5 q, radix 2 first when log2 M is odd, radix 4 down to 16-point blocks (registers)
-        std::vector<int> radix;
-        std::vector<float> tw;
-        int nn = M;
-        d.npass = 0;
-        while (nn > 16) {
-            const int r = (d.npass == 0 && five) ? 5 : (d.npass == 0 && (d.logM & 1)) ? 2 : 4;
-            if (nn % r) return false;
-            const int q = nn / r;
-            d.pass_n[d.npass] = nn; d.pass_r[d.npass] = r; d.pass_tw[d.npass] = (int32_t)(tw.size() / 2);
-            for (int pw = 1; pw < r; pw++)
-                for (int j = 0; j < q; j++) {
-                    const double ang = -2.0 * M_PI * (double)((int64_t)j * pw % nn) / (double)nn;
-                    tw.push_back((float)std::cos(ang));
-                    tw.push_back((float)std::sin(ang));
-                }
-            radix.push_back(r);
-            nn = q;
-            d.npass++;
-        }
-        if (nn != 16 || d.npass > 4) return false;
-        radix.push_back(4);
-        radix.push_back(4);
-        d.tw_count = (int32_t)(tw.size() / 2);
-        if (stft_lds_bytes(d, 8) > 156 * 1024) return false;
-        // per-output table
-        std::vector<float> otab((size_t)Cout * 8, 0.0f);  // per output: positions of Z[k], Z[M-k] (as floats), 4 coefficients, 2 pad
-        auto physpos = [&](int k) {
-            const int pp = dif_position(k, M, radix, 0);
-            return pp + 2 * (pp >> 4);
-        };
-        for (int64_t c = 0; c < Cout; c++) {
-            const int k = bank.k[(size_t)c];
-            const double a = bank.a[(size_t)c], b = bank.b[(size_t)c];
-            const double th = 2.0 * M_PI * (double)k / (double)L, cs = std::cos(th), sn = std::sin(th);
-            float *e = &otab[(size_t)c * 8];
-            e[0] = (float)physpos(k % M);
-            e[1] = (float)physpos((M - k % M) % M);
-            e[2] = (float)(0.5 * (a * (1.0 - sn) + b * cs));
-            e[3] = (float)(0.5 * (a * cs - b * (1.0 - sn)));
-            e[4] = (float)(0.5 * (a * (1.0 + sn) - b * cs));
-            e[5] = (float)(0.5 * (a * cs + b * (1.0 + sn)));
-        }
-        op.w = Ref{Space::CONSTS, add_const(bank.window), 0};
-        op.w2 = Ref{Space::CONSTS, add_const(tw), 0};
-        op.bias2 = Ref{Space::CONSTS, add_const(otab), 0};
-        const double log2L = std::log2((double)L);
-        op.flops_fft = (double)OW * 2.5 * L * log2L;
-        op.macs = op.flops_fft / 2;  // multiply-add equivalents actually performed (vector ALU)
-        op.mfma = false;
-        op.weight_bytes = 4.0 * (bank.window.size() + tw.size() + otab.size() + (has_bias ? Cout : 0));
-        op.bytes = base.bytes;
-        dft_gemm_macs_ += (double)OW * Cout * L;  // what the matrix-product evaluation of this bank multiplies
-        dft_fft_equiv_flops_ += op.flops_fft;
-        dft_performed_macs_ += op.flops_fft / 2;
-        push_op(std::move(op));
-        return true;
-    }
-
-    // ------------------------------------------------------------- quarter-folded cosine banks (round 4)
-    // A recognised bank of windowed COSINES only (the real part of an STFT) with a window symmetric about the frame centre: the even
-    // bins see the frame through S[n] = ye[n] + ye[L/2 - n], the odd ones through D[n] = ye[n] - ye[L/2 - n], n <= L/4 (kernels.h,
-    // GemmDesc::fold == 2; kernels.hip, frame_fold2_kernel) -- L/4 + 1 taps per output instead of L/2.  The filter rows become pure
-    // cosines x the fitted row amplitude (double -> f32), the window moves to the signal (two tables), the columns are grouped (even bins,
-    // padded to 32, then odd bins) and a column map sends every result to its output channel.  v2.4's 127 mel-live bins of the 2048-point
-    // branch: 17 K steps instead of 32.  BN_CONVFOLD2=0 keeps the half fold.
-    bool emit_quarter_fold(const OnnxNode &n, const PlanOp &base, const DftBank &bank, const std::vector<int> &cls, int64_t Cout, int64_t OW, bool has_bias) {
-        if (sw_int(sw::BN_CONVFOLD2) == 0) return false;
-        if (sw_int(sw::BN_FRAMEPAIR) == 1) return false;  // (opt-in rule J fuses the mel product behind the HALF fold's launch)
-        const int64_t L = bank.L;
-        if (L % 128 != 0) return false;
-        for (int64_t c = 0; c < Cout; c++)
-            if (cls[(size_t)c] < 0 || bank.b[(size_t)c] != 0.0) return false;  // a sine row: the half fold (or the FFT) keeps the bank
-        // the window: symmetric about the centre, nothing at tap 0 (the fold check saw that on the rows; here on the fitted window itself)
-        // (a tap at which every row's cosine vanishes -- n = L/4 for a bank of odd bins -- is invisible in the rows: the fitted window holds
-        // noise there, and nothing it multiplies reaches an output.  Such taps count as zero.)
-        std::vector<float> w = bank.window;
-        {
-            std::vector<double> seen((size_t)L, 0.0);
-            double smax = 0;
-            for (int64_t t = 0; t < L; t++) {
-                for (int64_t c = 0; c < Cout; c++) {
-                    const double v = bank.a[(size_t)c] * std::cos(2.0 * M_PI * (double)((bank.k[(size_t)c] * t) % L) / (double)L);
-                    seen[(size_t)t] += v * v;
-                }
-                smax = std::max(smax, seen[(size_t)t]);
-            }
-            for (int64_t t = 0; t < L; t++)
-                if (!(seen[(size_t)t] > 1e-20 * smax)) w[(size_t)t] = 0.0f;
-        }
-        float wmax = 0.0f;
-        for (float v : w) wmax = std::max(wmax, std::fabs(v));
-        const float eps = 4e-7f * wmax;
-        const bool dbg = sw_present(sw::BN_STFT_DEBUG);
-        if (!(std::fabs(w[0]) <= eps)) {
-            if (dbg) fprintf(stderr, "quarter fold: window tap 0 = %.3g\n", (double)w[0]);
-            return false;
-        }
-        for (int64_t t = 1; t < L / 2; t++)
-            if (!(std::fabs(w[(size_t)t] - w[(size_t)(L - t)]) <= eps)) {
-                if (dbg) fprintf(stderr, "quarter fold: window not symmetric at tap %lld: %.9g vs %.9g\n", (long long)t, (double)w[(size_t)t], (double)w[(size_t)(L - t)]);
-                return false;
-            }
-        std::vector<int32_t> even, odd, dead;
-        for (int64_t c = 0; c < Cout; c++) (bank.a[(size_t)c] == 0.0 ? dead : (bank.k[(size_t)c] & 1) ? odd : even).push_back((int32_t)c);
-        for (int32_t c : dead) {  // an all-zero row (its output is the bias) joins the group with room in its last wave column
-            const size_t se = (32 - even.size() % 32) % 32, so = (32 - odd.size() % 32) % 32;
-            (so > se ? odd : even).push_back(c);
-        }
-        const int64_t ne = ((int64_t)even.size() + 31) / 32 * 32, no = ((int64_t)odd.size() + 31) / 32 * 32, N2 = ne + no;
-        const int64_t Q = L / 4, K2 = Q + 32;
-        PlanOp f = base;
-        f.gemm.N = (int32_t)N2;
-        f.gemm.K = (int32_t)K2;
-        f.gemm.fold = 2;
-        f.gemm.fold_n = (int32_t)L;
-        f.gemm.fold_ne = (int32_t)ne;
-        if (!frame_fold2_shape_ok(f.gemm, nullptr)) {
-            if (dbg) fprintf(stderr, "quarter fold: shape outside the kernel (N = %lld + %lld columns, %zu bytes of LDS)\n", (long long)ne, (long long)no, frame_fold2_lds_bytes(f.gemm));
-            return false;
-        }
-        std::vector<float> colmap_bits((size_t)N2), wk((size_t)(N2 * K2), 0.0f), tabs((size_t)(2 * K2), 0.0f);
-        std::vector<int32_t> colmap((size_t)N2, -1);
-        for (size_t i = 0; i < even.size(); i++) colmap[i] = even[i];
-        for (size_t i = 0; i < odd.size(); i++) colmap[(size_t)ne + i] = odd[i];
-        static_assert(sizeof(int32_t) == sizeof(float), "the column map travels in a constant of floats");
-        std::memcpy(colmap_bits.data(), colmap.data(), (size_t)N2 * sizeof(float));
-        std::vector<double> ctab((size_t)L);
-        for (int64_t t = 0; t < L; t++) ctab[(size_t)t] = std::cos(2.0 * M_PI * (double)t / (double)L);
-        for (int64_t col = 0; col < N2; col++) {
-            const int32_t c = colmap[(size_t)col];
-            if (c < 0) continue;
-            const int64_t k = bank.k[(size_t)c];
-            const double a = bank.a[(size_t)c];
-            float *row = &wk[(size_t)(col * K2)];
-            for (int64_t t = 0; t < Q; t++) row[t] = (float)(a * ctab[(size_t)((k * t) % L)]);
-            row[Q] = (k & 1) ? 0.0f : (float)(a * ctab[(size_t)((k * Q) % L)]);  // cos(pi k / 2) = +-1 for even k
-        }
-        // S[n] = wa[n] (x[n] + x[L-n]) + wb[n] (x[L/2-n] + x[L/2+n]); n = 0: ye[0] = 0 and ye[L/2] = y[L/2] once; n = L/4: ye[L/4] once
-        for (int64_t t = 1; t < Q; t++) {
-            tabs[(size_t)t] = w[(size_t)t];
-            tabs[(size_t)(K2 + t)] = w[(size_t)(L / 2 - t)];
-        }
-        tabs[0] = 0.0f;
-        tabs[(size_t)K2] = 0.5f * w[(size_t)(L / 2)];
-        tabs[(size_t)Q] = w[(size_t)Q];
-        tabs[(size_t)(K2 + Q)] = 0.0f;
-        f.name = "Conv:" + n.name + "~quarter";
-        if (frame_fold2q_ok(f.gemm)) {  // (round 5) half-height blocks on the bf16 matrix pipe: three exact bf16 planes per filter element, fragment order
-            const int64_t steps = K2 / 32;
-            std::vector<uint16_t> img((size_t)(N2 * K2 * 3), 0);  // [column group][step][16-wide k group][plane][lane][8]
-            for (int64_t wn = 0; wn < N2 / 32; wn++)
-                for (int64_t ks = 0; ks < steps; ks++)
-                    for (int64_t g = 0; g < 2; g++)
-                        for (int64_t lane = 0; lane < 64; lane++) {
-                            const int64_t lr = lane & 31, lh = lane >> 5;
-                            for (int64_t j = 0; j < 8; j++) {
-                                uint16_t h, m, l;
-                                split_bf16x3(wk[(size_t)((wn * 32 + lr) * K2 + ks * 32 + 16 * g + 8 * lh + j)], h, m, l);
-                                const size_t at = (size_t)(((((wn * steps + ks) * 2 + g) * 3) * 64 + lane) * 8 + j);
-                                img[at] = h;
-                                img[at + 64 * 8] = m;
-                                img[at + 2 * 64 * 8] = l;
-                            }
-                        }
-            std::vector<float> pk(img.size() / 2);
-            std::memcpy(pk.data(), img.data(), img.size() * sizeof(uint16_t));
-            wk.swap(pk);
-            f.gemm.fold_wpk = 2;
-        } else if (frame_fold2p_ok(f.gemm)) {  // half-height blocks: the filter fragments in the order the waves load them
-            const int64_t steps = K2 / 32;
-            std::vector<float> pk((size_t)(N2 * K2));
-            for (int64_t wn = 0; wn < N2 / 32; wn++)
-                for (int64_t ks = 0; ks < steps; ks++)
-                    for (int64_t g = 0; g < 4; g++)
-                        for (int64_t lane = 0; lane < 64; lane++) {
-                            const int64_t lr = lane & 31, lh = lane >> 5;
-                            for (int64_t j = 0; j < 4; j++)
-                                pk[(size_t)((((wn * steps + ks) * 4 + g) * 64 + lane) * 4 + j)] = wk[(size_t)((wn * 32 + lr) * K2 + ks * 32 + 8 * g + 4 * lh + j)];
-                        }
-            wk.swap(pk);
-            f.gemm.fold_wpk = 1;
-        }
-        f.w = Ref{Space::CONSTS, add_const(wk), 0};
-        f.w2 = Ref{Space::CONSTS, add_const(tabs), 0};
-        f.bias2 = Ref{Space::CONSTS, add_const(colmap_bits), 0};
-        f.macs = (double)OW * (double)Cout * (double)(Q + 1);  // multiplications actually performed (padding columns excluded)
-        f.weight_bytes = 4.0 * (wk.size() + tabs.size() + colmap.size() + (has_bias ? Cout : 0));
-        dft_gemm_macs_ += (double)OW * Cout * L;
-        dft_performed_macs_ += f.macs;
-        dft_fft_equiv_flops_ += (double)OW * 2.5 * (double)L * std::log2((double)L);
-        push_op(std::move(f));
-        return true;
-    }
-
     // ------------------------------------------------------------- folded framing convolutions
     // A long single-channel 1-D filter bank whose rows are symmetric (w[n] == w[L-n], windowed cosine bases) or
     // antisymmetric (w[n] == -w[L-n], windowed sine bases) about the frame centre, with w[0] == 0 (Hann-type
@@ -1412,8 +537,8 @@ class Builder {
         {
             DftBank bank;
             if (detect_dft_bank(wf, Cout, L, cls, bank)) {
-                if (emit_stft(n, base, bank, Cout, OW, has_bias)) return true;
-                if (emit_quarter_fold(n, base, bank, cls, Cout, OW, has_bias)) return true;
+                if (emit_stft(plan_, n.name, base, bank, Cout, OW, has_bias)) return true;
+                if (emit_quarter_fold(plan_, n.name, base, bank, cls, Cout, OW, has_bias)) return true;
             }
         }
         struct Run { int64_t n0, n1; int sign; };
@@ -1426,9 +551,9 @@ class Builder {
             } else runs.push_back(Run{o, o + 1, c});
         }
         if (runs.size() > 4) return false;
-        dft_gemm_macs_ += (double)OW * Cout * L;
-        dft_performed_macs_ += (double)OW * Cout * (L / 2);  // folded: half the taps
-        dft_fft_equiv_flops_ += (double)OW * 2.5 * (double)L * std::log2((double)L);  // the same frames as real FFTs (SURVEY 8(d) pricing, any L)
+        plan_.dft_gemm_macs += (double)OW * Cout * L;
+        plan_.dft_performed_macs += (double)OW * Cout * (L / 2);  // folded: half the taps
+        plan_.dft_fft_equiv_flops += (double)OW * 2.5 * (double)L * std::log2((double)L);  // the same frames as real FFTs (SURVEY 8(d) pricing, any L)
         const int64_t K = L / 2;
         for (const Run &r : runs) {
             const int sign = r.sign == 0 ? 1 : r.sign;
@@ -1625,14 +750,6 @@ class Builder {
 
     // ---- operators lowered as short sequences of operators the planner already has (each step is an ordinary node to
     // the lowering: constants fold, elementwise steps fuse into chains)
-    OnnxNode synth_node(const std::string &op, const std::string &name, std::vector<std::string> ins, const std::string &out) {
-        OnnxNode s_;
-        s_.name = name;
-        s_.op_type = op;
-        s_.inputs = std::move(ins);
-        s_.outputs = {out};
-        return s_;
-    }
     std::string synth_const(const std::string &name, Dims dims, std::vector<float> f) {
         Val c;
         c.is_const = true;
@@ -1640,13 +757,6 @@ class Builder {
         c.f = std::move(f);
         vals_[name] = std::move(c);
         return name;
-    }
-    static void set_ints(OnnxNode &nd, const std::string &key, std::vector<int64_t> v) {
-        OnnxAttr a;
-        a.name = key;
-        a.type = 7;
-        a.ints = std::move(v);
-        nd.attrs[key] = a;
     }
     static void set_int(OnnxNode &nd, const std::string &key, int64_t v) {
         OnnxAttr a;
@@ -3665,799 +2775,6 @@ class Builder {
         op.bytes = 4.0 * ((double)rows * K + (double)rows * N);
         push_op(std::move(op));
         define(cur, out);
-    }
-
-    // --------------------------------------------------------- elementwise chain fusion
-    void all_refs(PlanOp &op, std::vector<Ref *> &out) {
-        out = {&op.out, &op.a, &op.b, &op.res, &op.scale, &op.w2, &op.bias2};
-        for (auto &r : op.eb) out.push_back(&r);
-        for (auto &r : op.x) out.push_back(&r);
-    }
-    void recompute_liveness() {
-        for (auto &st : plan_.storages) { st.first = -1; st.last = -1; }
-        std::vector<Ref *> refs;
-        for (size_t k = 0; k < plan_.ops.size(); k++) {
-            all_refs(plan_.ops[k], refs);
-            for (Ref *r : refs) touch(*r, (int)k);
-        }
-    }
-    // An ELT launch whose result is read by exactly one later ELT launch, as that launch's primary
-    // operand over the very same index space, is folded into it (its stages are prepended).
-    void fuse_elementwise_chains() {
-        bool changed = true;
-        while (changed) {
-            changed = false;
-            recompute_liveness();
-            // users per storage
-            std::vector<std::vector<int>> users(plan_.storages.size());
-            std::vector<Ref *> refs;
-            for (size_t k = 0; k < plan_.ops.size(); k++) {
-                all_refs(plan_.ops[k], refs);
-                for (Ref *r : refs)
-                    if (r->space == Space::ARENA && (users[r->id].empty() || users[r->id].back() != (int)k)) users[r->id].push_back((int)k);
-            }
-            for (size_t j = 0; j < plan_.ops.size() && !changed; j++) {
-                PlanOp &cons = plan_.ops[j];
-                if (cons.kind != OpKind::ELT || cons.a.space != Space::ARENA) continue;
-                const auto &u = users[cons.a.id];
-                if (u.size() != 2 || u[1] != (int)j || plan_.storages[cons.a.id].pinned) continue;
-                PlanOp &prod = plan_.ops[u[0]];
-                if (prod.kind != OpKind::ELT || prod.out.space != Space::ARENA || prod.out.id != cons.a.id) continue;
-                const int64_t delta = cons.a.offset - prod.out.offset;  // consumer may read a shifted / reversed view
-                if (prod.elt.nstages + cons.elt.nstages > ELT_MAX_STAGES) continue;
-                // (A) same index space: the consumer reads exactly what the producer wrote, or
-                // (B) the producer is a flat map over a dense buffer (offset in == offset out), so the
-                //     consumer's own strides address the producer's operands directly
-                const EltDesc &pe = prod.elt, &ce = cons.elt;
-                if (pe.bo != ce.ba) continue;
-                bool same = pe.nd == ce.nd && delta == 0;
-                for (int k = 0; same && k < pe.nd; k++) same = pe.size[k] == ce.size[k] && (pe.size[k] == 1 || pe.so[k] == ce.sa[k]);
-                bool flat_prod = pe.nd == 1 && pe.so[0] == 1 && pe.sa[0] == 1 && pe.per_sample == ce.per_sample;
-                for (int k = 0; flat_prod && k < pe.nstages; k++)
-                    flat_prod = pe.st[k].bin == BIN_NONE || pe.st[k].sb[0] == 0 || pe.st[k].sb[0] == 1;
-                // (C) the consumer is a flat map over the dense intermediate: it adopts the producer's index
-                //     space (its own strides scale by the producer's row-major runs)
-                bool flat_cons = !same && !flat_prod && ce.nd == 1 && ce.sa[0] == 1 && delta == 0 && pe.per_sample == ce.per_sample;
-                int64_t runs[ELT_MAX_DIMS] = {0};
-                if (flat_cons) {
-                    int64_t run = 1;
-                    for (int k = pe.nd - 1; k >= 0; k--) {
-                        if (pe.size[k] != 1 && pe.so[k] != run) flat_cons = false;
-                        runs[k] = run;
-                        run *= pe.size[k];
-                    }
-                }
-                if (!same && !flat_prod && !flat_cons) continue;
-                // the consumer must not also use the intermediate as a stage operand
-                {
-                    bool clash = false;
-                    for (int k = 0; k < ce.nstages; k++) clash = clash || (cons.eb[k].space == Space::ARENA && cons.eb[k].id == cons.a.id);
-                    if (clash) continue;
-                }
-                // nothing between the two may overwrite the producer's inputs: storages are single-assignment
-                // except concat targets, which are only read after all their writers ran -> safe.
-                PlanOp fused = cons;
-                fused.name = prod.name + "+" + cons.name;
-                fused.a = prod.a;
-                EltDesc &fe = fused.elt;
-                fe.ba = pe.ba;
-                fe.nstages = pe.nstages + ce.nstages;
-                if (same) {
-                    for (int k = 0; k < pe.nd; k++) fe.sa[k] = pe.sa[k];
-                    for (int k = 0; k < pe.nstages; k++) { fe.st[k] = pe.st[k]; fused.eb[k] = prod.eb[k]; }
-                } else if (flat_cons) {
-                    fe.nd = pe.nd;
-                    for (int k = 0; k < pe.nd; k++) { fe.size[k] = pe.size[k]; fe.sa[k] = pe.sa[k]; fe.so[k] = ce.so[0] * runs[k]; }
-                    for (int k = 0; k < pe.nstages; k++) { fe.st[k] = pe.st[k]; fused.eb[k] = prod.eb[k]; }
-                } else {
-                    // flat producer: its primary operand and every full-size stage operand are addressed
-                    // with the strides the consumer used for the intermediate (fe.sa is already ce.sa)
-                    fused.a.offset += delta;
-                    for (int k = 0; k < pe.nstages; k++) {
-                        fe.st[k] = pe.st[k];
-                        fused.eb[k] = prod.eb[k];
-                        const bool full = pe.st[k].bin != BIN_NONE && pe.st[k].sb[0] == 1;
-                        if (full) fused.eb[k].offset += delta;
-                        for (int q = 0; q < ELT_MAX_DIMS; q++) fe.st[k].sb[q] = (q < ce.nd && full) ? ce.sa[q] : 0;
-                    }
-                }
-                for (int k = 0; k < ce.nstages; k++) {
-                    fe.st[pe.nstages + k] = ce.st[k];
-                    fused.eb[pe.nstages + k] = cons.eb[k];
-                    if (flat_cons)
-                        for (int q = 0; q < ELT_MAX_DIMS; q++) fe.st[pe.nstages + k].sb[q] = q < pe.nd ? ce.st[k].sb[0] * runs[q] : 0;
-                }
-                fused.bytes = prod.bytes + cons.bytes - 8.0 * (double)pe.per_sample;  // the intermediate never touches memory
-                plan_.ops[j] = fused;
-                plan_.ops.erase(plan_.ops.begin() + u[0]);
-                changed = true;
-            }
-            // (D) a stage operand that is the square x*x of some view, produced only for this stage, is
-            //     read straight from x and squared in the consumer (|z|^2 = re*re + im*im in one launch)
-            for (size_t j = 0; j < plan_.ops.size() && !changed; j++) {
-                PlanOp &cons = plan_.ops[j];
-                if (cons.kind != OpKind::ELT) continue;
-                EltDesc &ce = cons.elt;
-                for (int k = 0; k < ce.nstages && !changed; k++) {
-                    EltStage &cs = ce.st[k];
-                    const Ref &br = cons.eb[k];
-                    if (cs.bin == BIN_NONE || cs.bsq || br.space != Space::ARENA || plan_.storages[br.id].pinned) continue;
-                    const auto &u = users[br.id];
-                    if (u.size() != 2 || u[1] != (int)j) continue;
-                    const PlanOp &prod = plan_.ops[u[0]];
-                    const EltDesc &pe = prod.elt;
-                    if (prod.kind != OpKind::ELT || prod.out.space != Space::ARENA || prod.out.id != br.id || prod.out.offset != br.offset) continue;
-                    if (pe.nstages != 1 || pe.st[0].bin != BIN_MUL || pe.st[0].act != ACT_NONE || pe.st[0].bsq) continue;
-                    if (prod.eb[0].space != prod.a.space || prod.eb[0].id != prod.a.id || prod.eb[0].offset != prod.a.offset || pe.st[0].bb != pe.ba) continue;
-                    if (cons.a.space == Space::ARENA && cons.a.id == br.id) continue;
-                    bool match = pe.nd == ce.nd && pe.bo == cs.bb;
-                    for (int q = 0; match && q < pe.nd; q++)
-                        match = pe.size[q] == ce.size[q] && pe.so[q] == cs.sb[q] && pe.st[0].sb[q] == pe.sa[q];
-                    if (!match) continue;
-                    cons.eb[k] = prod.a;
-                    for (int q = 0; q < ELT_MAX_DIMS; q++) cs.sb[q] = q < pe.nd ? pe.sa[q] : 0;
-                    cs.bb = pe.ba;
-                    cs.bsq = 1;
-                    cons.name += "+sq(" + prod.name + ")";
-                    cons.bytes += prod.bytes - 12.0 * (double)pe.per_sample + 4.0 * (double)pe.per_sample;
-                    plan_.ops.erase(plan_.ops.begin() + u[0]);
-                    changed = true;
-                }
-            }
-        }
-        absorb_chains_into_gemms();
-        absorb_into_stft();
-        planar_stft_tables();
-        fuse_fold_pairs();
-        pair_minmax_reductions();
-        fuse_gap_into_gemm();
-        absorb_se_into_gemms();
-        recompute_liveness();
-    }
-
-    // (I) The two small squeeze-excite products move into the prologue of the GEMM that consumes their gate, when that GEMM
-    // runs on the LDS-DMA kernel (gemm_dma.hip): every block of a sample recomputes the gate from the squeeze partial sums
-    // while its first K steps are in flight.  One launch less per MBConv block -- 7 - 8 us of the serial chain of a step,
-    // of which 3.6 us are the launch itself -- for C x Cr x 8 bytes of L2 reads per block; only up to BN_SEGEMM_MAXC
-    // channels (default 768: at C = 1152 the 442 KB of excite weights per block cost more than the launch they save).
-    // MEASURED (batch 32, v2.4): slower.  A block has 2 - 8 waves for two products the stand-alone excite kernel spreads
-    // over 80 per sample; the prologue is a chain of load latencies (K = 672: project conv 20 -> 52 us against 20 + 8 for
-    // the two launches), four contexts 52.7 k -> 47.2 k segments/s.  Opt-in (BN_SEGEMM=1), kept under test.
-    void absorb_se_into_gemms() {
-        if (!(sw_int(sw::BN_SEGEMM) == 1)) return;
-        const int max_c = gemm_dma_se_max_channels();
-        std::vector<Ref *> refs;
-        for (size_t j = 0; j < plan_.ops.size(); j++) {
-            if (plan_.ops[j].kind != OpKind::SEFC || plan_.ops[j].out.space != Space::ARENA) continue;
-            const int gate_id = plan_.ops[j].out.id;
-            if (plan_.storages[gate_id].pinned) continue;
-            int cons = -1, users = 0;
-            for (size_t k = 0; k < plan_.ops.size(); k++) {
-                if (k == j) continue;
-                all_refs(plan_.ops[k], refs);
-                bool uses = false;
-                for (Ref *r : refs) uses = uses || (r->space == Space::ARENA && r->id == gate_id);
-                if (uses) { users++; cons = (int)k; }
-            }
-            if (users != 1 || cons < (int)j) continue;
-            PlanOp &g = plan_.ops[cons];
-            const PlanOp &se = plan_.ops[j];
-            if (g.kind != OpKind::GEMM || !g.gemm.has_scale || g.scale.space != Space::ARENA || g.scale.id != gate_id || g.scale.offset != 0 || g.se_fused) continue;
-            if (se.se.C != g.gemm.K || se.se.C > max_c || se.se.C % 4 || !gemm_dma_shape(g.gemm)) continue;
-            g.se_fused = 1;
-            g.se = se.se;
-            g.gemm.se_inline = 1;
-            g.b = se.a;       // squeeze partial sums
-            g.x[0] = se.w;    // W1 [Cr][C]
-            g.x[1] = se.bias;
-            g.x[2] = se.w2;   // W2 transposed [Cr][C]
-            g.x[3] = se.bias2;
-            g.name = se.name + "+" + g.name;
-            g.macs_valu_extra += se.macs;
-            g.weight_bytes += se.weight_bytes;
-            g.bytes += se.bytes;
-            plan_.ops.erase(plan_.ops.begin() + (long)j);
-            j--;
-        }
-    }
-
-    // (G) Neighbours of an STFT launch move into it:
-    //  * the mel filter bank -- a GEMM over the spectrum rows with a SPARSE constant matrix (triangular filters: a few
-    //    bins per band) -- together with whatever rule E put into that GEMM's epilogue (compression chain, layout copy
-    //    into the spectrogram image): the spectrum rows never leave LDS.  BN_STFT_MEL=0 disables.
-    //  * the elementwise chain that produced the signal, when every stage operand is one number per sample (the
-    //    min-max normalisation of the v2.4 graph) and every reader of its result is an STFT launch: the chain runs
-    //    while the span is loaded, the normalised segment is never written.  BN_STFT_PRE=0 disables.
-    void absorb_into_stft() {
-        const bool mel_on = !sw_is(sw::BN_STFT_MEL, "0");
-        const bool pre_on = sw_on(sw::BN_STFT_PRE);
-        auto users_of = [&]() {
-            std::vector<std::vector<int>> users(plan_.storages.size());
-            std::vector<Ref *> refs;
-            for (size_t k = 0; k < plan_.ops.size(); k++) {
-                all_refs(plan_.ops[k], refs);
-                for (Ref *r : refs)
-                    if (r->space == Space::ARENA && (users[r->id].empty() || users[r->id].back() != (int)k)) users[r->id].push_back((int)k);
-            }
-            return users;
-        };
-        //  * (round 3) the power / magnitude pass behind a cos | sin bank: an elementwise launch  re*re + im*im [-> sqrt]  over
-        //    the two halves of every spectrum row, whose only reader it is -- the launch computes both linear forms of a bin
-        //    in one lane and stores f(u^2 + v^2): half the spectrum bytes written, none read back, one launch less, and the
-        //    mel bank that follows becomes a direct neighbour (next rule).  BN_STFT_POWER=0 disables.
-        if (sw_on(sw::BN_STFT_POWER)) {
-            bool again = true;
-            while (again) {
-                again = false;
-                auto users = users_of();
-                for (size_t i = 0; i < plan_.ops.size() && !again; i++) {
-                    PlanOp &f = plan_.ops[i];
-                    FftDesc &d = f.fft;
-                    if (f.kind != OpKind::FFT || d.nmel || d.power || d.has_bias || d.npost || f.out.space != Space::ARENA || plan_.storages[f.out.id].pinned) continue;
-                    if (d.nout % 2 || d.ldc != d.nout || d.out_rs != d.nout || d.out_cs != 1) continue;
-                    const auto &u = users[f.out.id];
-                    if (u.size() != 2 || u[0] != (int)i) continue;
-                    PlanOp &el = plan_.ops[u[1]];
-                    const EltDesc &e = el.elt;
-                    const int64_t nb = d.nout / 2;
-                    if (el.kind != OpKind::ELT || e.nd != 2 || e.size[0] != d.frames || e.size[1] != nb || e.sa[0] != d.nout || e.sa[1] != 1 || e.ba != d.c_bs) continue;
-                    if (el.a.space != Space::ARENA || el.a.id != f.out.id || el.a.offset != f.out.offset) continue;
-                    if (el.out.space != Space::ARENA || e.so[1] != 1 || e.so[0] < nb) continue;
-                    // stage 0: x * x (the operand is the same view); stage 1: + y^2 with y the other half of the row; [stage 2: sqrt]
-                    if (e.nstages < 2 || e.nstages > 3) continue;
-                    const EltStage &s0 = e.st[0], &s1 = e.st[1];
-                    const Ref &r0 = el.eb[0], &r1 = el.eb[1];
-                    if (s0.bin != BIN_MUL || s0.bsq || s0.act != ACT_NONE || r0.space != Space::ARENA || r0.id != f.out.id || r0.offset != f.out.offset ||
-                        s0.sb[0] != d.nout || s0.sb[1] != 1 || s0.bb != d.c_bs)
-                        continue;
-                    if (s1.bin != BIN_ADD || !s1.bsq || s1.act != ACT_NONE || r1.space != Space::ARENA || r1.id != f.out.id || r1.offset != f.out.offset + nb ||
-                        s1.sb[0] != d.nout || s1.sb[1] != 1 || s1.bb != d.c_bs)
-                        continue;
-                    if (e.nstages == 3 && !(e.st[2].bin == BIN_NONE && e.st[2].act == ACT_SQRT)) continue;
-                    // the two halves must be the two forms of the SAME bins in the same order (same buffer positions)
-                    const std::vector<float> &ot = plan_.consts[f.bias2.id];
-                    bool same = (int64_t)ot.size() >= f.bias2.offset + d.nout * 8;
-                    for (int64_t c = 0; c < nb && same; c++) {
-                        const float *u0 = &ot[(size_t)(f.bias2.offset + c * 8)], *v0 = &ot[(size_t)(f.bias2.offset + (c + nb) * 8)];
-                        same = u0[0] == v0[0] && u0[1] == v0[1];
-                    }
-                    if (!same) continue;
-                    std::vector<float> ot2((size_t)nb * 12, 0.0f);
-                    for (int64_t c = 0; c < nb; c++) {
-                        const float *u0 = &ot[(size_t)(f.bias2.offset + c * 8)], *v0 = &ot[(size_t)(f.bias2.offset + (c + nb) * 8)];
-                        float *o = &ot2[(size_t)c * 12];
-                        for (int q = 0; q < 6; q++) o[q] = u0[q];
-                        for (int q = 0; q < 4; q++) o[8 + q] = v0[2 + q];
-                    }
-                    FftDesc probe = d;
-                    probe.nout = (int32_t)nb; probe.otab_stride = 12; probe.power = e.nstages == 3 ? 2 : 1;
-                    if (stft_lds_bytes(probe, 8) > 156 * 1024) continue;
-                    d = probe;
-                    d.ldc = e.so[0]; d.out_rs = e.so[0]; d.out_cs = 1; d.c_bs = e.bo;
-                    f.bias2 = Ref{Space::CONSTS, add_const(ot2), 0};
-                    f.out = el.out;
-                    f.name += "+" + el.name;
-                    f.weight_bytes += 4.0 * (double)ot2.size() - 4.0 * 8.0 * (double)(2 * nb);
-                    f.bytes -= 4.0 * (double)d.frames * (double)nb;  // one value per bin is written instead of two; the cos | sin rows are never read back
-                    f.macs += 2.0 * (double)d.frames * (double)nb;
-                    f.flops_fft += 3.0 * (double)d.frames * (double)nb;
-                    plan_.ops.erase(plan_.ops.begin() + u[1]);
-                    again = true;
-                }
-            }
-        }
-        bool changed = mel_on;
-        while (changed) {
-            changed = false;
-            auto users = users_of();
-            for (size_t i = 0; i < plan_.ops.size() && !changed; i++) {
-                PlanOp &f = plan_.ops[i];
-                if (f.kind != OpKind::FFT || f.fft.nmel || f.out.space != Space::ARENA || plan_.storages[f.out.id].pinned) continue;
-                if (f.fft.tpb & (f.fft.tpb - 1)) continue;  // the mel phases index a tile's frames by shifts / 16-frame matrix tiles (M = 5 q banks: tiles of 24)
-                const auto &u = users[f.out.id];
-                if (u.size() != 2 || u[0] != (int)i) continue;
-                PlanOp &g = plan_.ops[u[1]];
-                const GemmDesc &gd = g.gemm;
-                if (g.kind != OpKind::GEMM || g.a.space != Space::ARENA || g.a.id != f.out.id || g.a.offset != f.out.offset) continue;
-                if (gd.fold || gd.has_scale || gd.has_res || gd.rows != f.fft.frames || gd.K != f.fft.nout || gd.lda != gd.K || gd.a_bs != f.fft.c_bs ||
-                    f.fft.ldc != f.fft.nout || g.w.space != Space::CONSTS)
-                    continue;
-                bool stages_ok = stft_act_supported(gd.act);
-                for (int q = 0; q < gd.npost; q++) stages_ok = stages_ok && stft_act_supported(gd.post_act[q]);
-                if (!stages_ok) continue;
-                const std::vector<float> &W = plan_.consts[g.w.id];  // [N][K]
-                const int64_t N = gd.N, K = gd.K;
-                std::vector<float> mstart, ment;  // row starts; (column, value) pairs
-                for (int64_t nn = 0; nn < N; nn++) {
-                    mstart.push_back((float)(ment.size() / 2));
-                    for (int64_t k = 0; k < K; k++) {
-                        const float v = W[(size_t)(g.w.offset + nn * K + k)];
-                        if (v != 0.0f) { ment.push_back((float)k); ment.push_back(v); }
-                    }
-                }
-                mstart.push_back((float)(ment.size() / 2));
-                const size_t nnz_count = ment.size() / 2;
-                if ((double)nnz_count > 0.3 * (double)N * (double)K || nnz_count >= (1u << 23) || N > 1024) continue;  // dense: stays a GEMM
-                FftDesc probe = f.fft;
-                probe.nmel = (int32_t)N;
-                probe.mel_nnz = (int32_t)nnz_count;
-                // the tile's spectrum rows join the LDS image.  Where 16 frames per tile no longer fit (v3.0: 513 bins, 128 bands)
-                // tiles of 8 would, but the launch then loses to FFT + dense mel GEMM (200 us against 97 + 66 at batch 64,
-                // 41.5 k against 44.0 k segments/s): BN_STFT_MEL=force takes the smaller tile anyway (tests)
-                if (sw_is(sw::BN_STFT_MEL, "force"))
-                    while (stft_lds_bytes(probe, 8) > 156 * 1024 && probe.tpb > 8 && (probe.tpb / 2) % probe.F == 0) probe.tpb /= 2;
-                if (stft_lds_bytes(probe, 8) > 156 * 1024) continue;
-                FftDesc &d = f.fft;
-                d.tpb = probe.tpb;
-                d.nmel = (int32_t)N;
-                d.mel_nnz = (int32_t)nnz_count;
-                d.mel_mode = 0; d.mel_groups = 0; d.spec_stride = d.nout;
-                // the bank as 16 x 16 tiles for the matrix cores (kernels.h, FftDesc::mel_mode): tile rows of 16 bands, of each
-                // only the 16-bin groups that hold a non-zero; a tile is stored in the lane order of the A fragment (lane (i, q)
-                // holds band i, bins 16 g + 4 q + 0..3).  BN_STFT_MELMFMA=0 keeps the (column, weight) lists on the vector ALU.
-                if (sw_on(sw::BN_STFT_MELMFMA) && d.tpb == 16) {
-                    const int64_t ntile = (N + 15) / 16, ngrp = (K + 15) / 16;
-                    std::vector<float> tab((size_t)ntile + 1, 0.0f), glist, pack;
-                    for (int64_t t = 0; t < ntile; t++) {
-                        tab[(size_t)t] = (float)glist.size();
-                        for (int64_t gq = 0; gq < ngrp; gq++) {
-                            bool any = false;
-                            for (int64_t i = 0; i < 16 && !any; i++)
-                                for (int64_t k = 0; k < 16 && !any; k++) {
-                                    const int64_t nn = 16 * t + i, kk = 16 * gq + k;
-                                    any = nn < N && kk < K && W[(size_t)(g.w.offset + nn * K + kk)] != 0.0f;
-                                }
-                            if (!any) continue;
-                            glist.push_back((float)gq);
-                            for (int lane = 0; lane < 64; lane++)
-                                for (int j = 0; j < 4; j++) {
-                                    const int64_t nn = 16 * t + (lane & 15), kk = 16 * gq + 4 * (lane >> 4) + j;
-                                    pack.push_back(nn < N && kk < K ? W[(size_t)(g.w.offset + nn * K + kk)] : 0.0f);
-                                }
-                        }
-                    }
-                    tab[(size_t)ntile] = (float)glist.size();
-                    FftDesc probe2 = d;
-                    probe2.mel_mode = 1; probe2.mel_groups = (int32_t)glist.size(); probe2.spec_stride = (int32_t)(16 * ngrp + 8);
-                    if (!glist.empty() && glist.size() < (1u << 22) && stft_lds_bytes(probe2, 8) <= 156 * 1024) {
-                        d = probe2;
-                        tab.insert(tab.end(), glist.begin(), glist.end());
-                        mstart = tab;
-                        ment = pack;
-                    }
-                }
-                if (ment.empty()) { ment.push_back(0.0f); ment.push_back(0.0f); }
-                d.mel_has_bias = gd.has_bias;
-                d.mel_act = gd.act; d.mel_p0 = gd.p0; d.mel_p1 = gd.p1;
-                d.npost = gd.npost;
-                for (int q = 0; q < 4; q++) { d.post_act[q] = gd.post_act[q]; d.post_p0[q] = gd.post_p0[q]; d.post_p1[q] = gd.post_p1[q]; }
-                d.c_bs = gd.c_bs;
-                if (gd.out_strided) { d.out_rs = gd.out_rs; d.out_cs = gd.out_cs; }
-                else { d.out_rs = gd.ldc; d.out_cs = 1; }
-                f.x[0] = Ref{Space::CONSTS, add_const(mstart), 0};
-                f.x[1] = Ref{Space::CONSTS, add_const(ment), 0};
-                f.x[3] = g.bias;
-                f.out = g.out;
-                f.name += "+" + g.name;
-                const double nnz = d.mel_mode == 1 ? 256.0 * (double)d.mel_groups : (double)nnz_count;  // multiply-adds performed per frame
-                f.flops_fft += 2.0 * nnz * (double)d.frames;
-                f.macs += nnz * (double)d.frames;
-                f.weight_bytes += 4.0 * (mstart.size() + ment.size());
-                f.bytes += g.bytes - 8.0 * (double)d.frames * (double)d.nout;  // the spectrum rows never touch memory
-                dft_gemm_macs_ += g.macs;  // the dense mel product belongs to the matrix-product count of the front end
-                dft_performed_macs_ += nnz * (double)d.frames;
-                dft_fft_equiv_flops_ += 2.0 * nnz * (double)d.frames;
-                plan_.ops.erase(plan_.ops.begin() + u[1]);
-                changed = true;
-            }
-        }
-        changed = pre_on;
-        while (changed) {
-            changed = false;
-            auto users = users_of();
-            for (size_t e = 0; e < plan_.ops.size() && !changed; e++) {
-                PlanOp &el = plan_.ops[e];
-                const EltDesc &ed = el.elt;
-                if (el.kind != OpKind::ELT || el.out.space != Space::ARENA || plan_.storages[el.out.id].pinned) continue;
-                if (ed.nd != 1 || ed.so[0] != 1 || ed.sa[0] != 1 || el.out.offset != 0) continue;
-                bool scalar_ops = true;
-                for (int k = 0; k < ed.nstages; k++)
-                    scalar_ops = scalar_ops && stft_act_supported(ed.st[k].act) &&
-                                 (ed.st[k].bin == BIN_NONE || (ed.st[k].sb[0] == 0 && !ed.st[k].bsq && stft_bin_supported(ed.st[k].bin)));
-                if (!scalar_ops) continue;
-                const auto &u = users[el.out.id];
-                if (u.size() < 2 || u[0] != (int)e) continue;
-                // every reader is a launch that can apply the chain while it loads its span: an STFT, or (round 4) a folded framing GEMM that
-                // is certain to run on its LDS-resident kernel (half fold: frame_fold_post_ok; quarter fold: always)
-                auto framing_gemm = [&](const PlanOp &f) {
-                    const GemmDesc &g = f.gemm;
-                    if (f.kind != OpKind::GEMM || f.pre.n != 0 || f.gemm2.N > 0 || f.se_fused || sw_int(sw::BN_FRAME_PRE) == 0) return false;
-                    if (sw_int(sw::BN_FRAMEPAIR) == 1) return false;  // (opt-in rule J runs later and its kernel does not carry the chain)
-                    if (!(g.fold == 2 ? frame_fold2_shape_ok(g, nullptr) : (g.fold == 1 || g.fold == -1) && frame_fold_post_ok(g))) return false;
-                    return g.a_bs == ed.bo && (g.rows - 1) * g.lda + g.fold_n <= ed.per_sample;
-                };
-                bool all_fft = true;
-                for (size_t q = 1; q < u.size(); q++) {
-                    const PlanOp &f = plan_.ops[u[q]];
-                    const bool stft_ok = f.kind == OpKind::FFT && f.fft.npre == 0 && f.fft.a_bs == ed.bo && (int64_t)(f.fft.frames - 1) * f.fft.hop + f.fft.L <= ed.per_sample;
-                    all_fft = all_fft && (stft_ok || framing_gemm(f)) && f.a.space == Space::ARENA && f.a.id == el.out.id && f.a.offset == 0;
-                    // (the launch must read the chain's result only through `a`)
-                    std::vector<Ref *> refs;
-                    all_refs(const_cast<PlanOp &>(f), refs);
-                    int reads = 0;
-                    for (Ref *r : refs) reads += (r->space == Space::ARENA && r->id == el.out.id) ? 1 : 0;
-                    all_fft = all_fft && reads == 1;
-                }
-                if (!all_fft) continue;
-                for (size_t q = 1; q < u.size(); q++) {
-                    PlanOp &f = plan_.ops[u[q]];
-                    f.a = el.a;
-                    if (f.kind == OpKind::FFT) {
-                        f.fft.a_bs = ed.ba;
-                        f.fft.npre = ed.nstages;
-                    } else {
-                        f.gemm.a_bs = ed.ba;
-                        f.pre.n = ed.nstages;
-                    }
-                    for (int k = 0; k < ed.nstages; k++) {
-                        if (f.kind == OpKind::FFT) {
-                            f.fft.pre_bin[k] = ed.st[k].bin; f.fft.pre_act[k] = ed.st[k].act;
-                            f.fft.pre_p0[k] = ed.st[k].p0; f.fft.pre_p1[k] = ed.st[k].p1; f.fft.pre_bb[k] = ed.st[k].bb;
-                        } else {
-                            f.pre.bin[k] = ed.st[k].bin; f.pre.act[k] = ed.st[k].act;
-                            f.pre.p0[k] = ed.st[k].p0; f.pre.p1[k] = ed.st[k].p1; f.pre.bb[k] = ed.st[k].bb;
-                        }
-                        f.eb[k] = el.eb[k];
-                    }
-                    f.name = el.name + "+" + f.name;
-                }
-                plan_.ops.erase(plan_.ops.begin() + (long)e);
-                changed = true;
-            }
-        }
-        // (round 5) the zero-padded copy of the signal a padded framing conv reads (pad_copy: one fill + one copy launch) in the STFT's span
-        // load: where the only reader of that copy is an FFT launch, the launch reads the signal itself and zero-fills the positions that
-        // fall into the padding (FftDesc::pad_l, in_len).  Perch's front end: two launches and a round trip of the signal less.
-        changed = sw_int(sw::BN_STFT_PAD) != 0;
-        while (changed) {
-            changed = false;
-            auto users = users_of();
-            for (size_t e = 0; e + 2 < plan_.ops.size() && !changed; e++) {
-                const PlanOp &fill = plan_.ops[e], &copy = plan_.ops[e + 1];
-                if (fill.kind != OpKind::ELT || copy.kind != OpKind::ELT || fill.name.rfind("pad.fill:", 0) != 0 || copy.name.rfind("pad.copy:", 0) != 0) continue;
-                if (fill.out.space != Space::ARENA || copy.out.space != Space::ARENA || fill.out.id != copy.out.id || fill.out.offset != 0 || plan_.storages[fill.out.id].pinned) continue;
-                const EltDesc &fd = fill.elt, &cd = copy.elt;
-                if (fd.nd != 1 || cd.nd != 1 || fd.nstages != 1 || cd.nstages != 1 || cd.so[0] != 1 || cd.sa[0] != 1) continue;
-                if (fd.st[0].bin != BIN_NONE || fd.st[0].act != ACT_NONE || cd.st[0].bin != BIN_NONE || cd.st[0].act != ACT_NONE) continue;
-                if (fill.a.space != Space::CONSTS || plan_.consts[(size_t)fill.a.id].empty() || plan_.consts[(size_t)fill.a.id][(size_t)fill.a.offset] != 0.0f) continue;
-                if (copy.a.space != Space::ARENA && copy.a.space != Space::INPUT) continue;
-                const auto &u = users[fill.out.id];
-                if (u.size() != 3 || u[0] != (int)e || u[1] != (int)e + 1) continue;
-                PlanOp &f = plan_.ops[(size_t)u[2]];
-                if (f.kind != OpKind::FFT || f.fft.in_len != 0 || f.fft.npre != 0 || f.a.space != Space::ARENA || f.a.id != fill.out.id || f.a.offset != 0) continue;
-                if (f.fft.a_bs != fd.bo || (int64_t)(f.fft.frames - 1) * f.fft.hop + f.fft.L > fd.per_sample || copy.out.offset + cd.per_sample > fd.per_sample) continue;
-                if (cd.per_sample >= ((int64_t)1 << 30) || copy.out.offset >= ((int64_t)1 << 30)) continue;
-                std::vector<Ref *> refs;
-                all_refs(f, refs);
-                int reads = 0;
-                for (Ref *r : refs) reads += (r->space == Space::ARENA && r->id == fill.out.id) ? 1 : 0;
-                if (reads != 1) continue;
-                f.a = copy.a;
-                f.fft.a_bs = cd.ba;
-                f.fft.pad_l = (int32_t)copy.out.offset;
-                f.fft.in_len = (int32_t)cd.per_sample;
-                f.bytes -= 4.0 * (double)(fd.per_sample - cd.per_sample);
-                f.name = "pad+" + f.name;
-                plan_.ops.erase(plan_.ops.begin() + (long)e, plan_.ops.begin() + (long)e + 2);
-                changed = true;
-            }
-        }
-    }
-
-    // (K, round 4) GlobalAveragePool behind a 1x1 conv whose 48 rows per sample sit in one block of the LDS-DMA GEMM (48-row tiles): the
-    // epilogue writes the mean over the rows instead of the rows (gemm_dma.hip; fixed order: m-tiles ascending, then a butterfly over the 16
-    // rows of a tile), the [48, N] tensor is neither written nor read and the reduction launch is gone.  v2.4's head: Conv_261 (320 -> 1024,
-    // ReLU) + GlobalAveragePool_264.  BN_GEMMGAP=0 disables.
-    void fuse_gap_into_gemm() {
-        if (sw_int(sw::BN_GEMMGAP) == 0) return;
-        bool changed = true;
-        while (changed) {
-            changed = false;
-            std::vector<std::vector<int>> users(plan_.storages.size());
-            std::vector<Ref *> refs;
-            for (size_t k = 0; k < plan_.ops.size(); k++) {
-                all_refs(plan_.ops[k], refs);
-                for (Ref *r : refs)
-                    if (r->space == Space::ARENA && (users[r->id].empty() || users[r->id].back() != (int)k)) users[r->id].push_back((int)k);
-            }
-            for (size_t j = 0; j < plan_.ops.size() && !changed; j++) {
-                PlanOp &red = plan_.ops[j];
-                const ReduceDesc &r = red.red;
-                if (red.kind != OpKind::REDUCE || r.op != RED_MEAN || r.pair || red.a.space != Space::ARENA || red.out.space != Space::ARENA) continue;
-                const auto &u = users[red.a.id];
-                if (u.size() != 2 || u[1] != (int)j || plan_.storages[red.a.id].pinned) continue;
-                PlanOp &g = plan_.ops[u[0]];
-                if (g.kind != OpKind::GEMM || g.out.space != Space::ARENA || g.out.id != red.a.id || g.out.offset != red.a.offset || g.se_fused || g.gemm2.N > 0) continue;
-                GemmDesc d = g.gemm;
-                if (d.gap || !gemm_gap_shape_ok(d) || gemm_dma_shape(d) != 2 || d.ldc != d.N || d.c_bs != d.rows * d.N) continue;
-                // the reduction: every channel's mean over the sample's rows, [rows, N] -> [N], dense
-                // (the reduced dims -- H, W of the map -- nest into one run of `rows` rows of N floats)
-                bool rows_run = r.nr >= 1 && r.nr <= 3 && r.rin[r.nr - 1] == d.N;
-                int64_t nrows = 1;
-                for (int q = r.nr - 1; q >= 0 && rows_run; q--) {
-                    rows_run = r.rin[q] == d.N * nrows;
-                    nrows *= r.rsize[q];
-                }
-                if (r.nk != 1 || !rows_run || nrows != d.rows || r.ksize[0] != d.N || r.kin[0] != 1 || r.kout[0] != 1 || r.bi != d.c_bs) continue;
-                if (red.out.offset % 4 != 0 || r.bo % 4 != 0) continue;  // (dwordx4 stores)
-                d.gap = 1;
-                d.c_bs = r.bo;
-                g.gemm = d;
-                g.out = red.out;
-                g.name += "+" + red.name;
-                g.bytes += red.bytes - 8.0 * (double)d.rows * d.N;  // the [rows, N] tensor never touches memory
-                plan_.ops.erase(plan_.ops.begin() + (long)j);
-                changed = true;
-            }
-        }
-    }
-
-    // (J) The product that consumes the rows of a folded framing GEMM -- the mel filter bank of a spectrogram branch that stayed on the
-    // matrix path: K2 = the bank's <= 128 live bins, with the compression chain and the layout copy rule E put into its epilogue --
-    // runs behind the K loop of the framing kernel on the block's own spectrum tile (kernels.hip, frame_fold_kernel<true>): the
-    // spectrum rows are neither written nor read back, one launch less.  Measured slower (kernels.hip, frame_fold_pair_ok): opt-in, BN_FRAMEPAIR=1.
-    void fuse_fold_pairs() {
-        bool changed = true;
-        while (changed) {
-            changed = false;
-            std::vector<std::vector<int>> users(plan_.storages.size());
-            std::vector<Ref *> refs;
-            for (size_t k = 0; k < plan_.ops.size(); k++) {
-                all_refs(plan_.ops[k], refs);
-                for (Ref *r : refs)
-                    if (r->space == Space::ARENA && (users[r->id].empty() || users[r->id].back() != (int)k)) users[r->id].push_back((int)k);
-            }
-            for (size_t i = 0; i < plan_.ops.size() && !changed; i++) {
-                PlanOp &f = plan_.ops[i];
-                if (f.kind != OpKind::GEMM || !f.gemm.fold || f.gemm2.N > 0 || f.gemm.npost || f.gemm.out_strided || f.se_fused) continue;
-                if (f.out.space != Space::ARENA || plan_.storages[f.out.id].pinned) continue;
-                const auto &u = users[f.out.id];
-                if (u.size() != 2 || u[0] != (int)i) continue;
-                PlanOp &g = plan_.ops[u[1]];
-                if (g.kind != OpKind::GEMM || g.se_fused || g.gemm2.N > 0 || g.a.space != Space::ARENA || g.a.id != f.out.id || g.a.offset != f.out.offset) continue;
-                if (g.w.space != Space::CONSTS || (g.gemm.has_bias && g.bias.space != Space::CONSTS)) continue;
-                if (!frame_fold_pair_ok(f.gemm, g.gemm)) continue;
-                f.gemm2 = g.gemm;
-                f.w2 = g.w;
-                f.bias2 = g.bias;
-                f.out = g.out;
-                f.name += "+" + g.name;
-                f.macs += g.macs;
-                f.weight_bytes += g.weight_bytes;
-                f.bytes += g.bytes - 8.0 * (double)f.gemm.rows * (double)f.gemm.N;  // the spectrum rows never touch memory
-                plan_.ops.erase(plan_.ops.begin() + u[1]);
-                changed = true;
-            }
-        }
-    }
-
-    // The untangle table of every FFT launch goes from rows [nout][8 | 12] to PLANES: [nout][4] (two buffer positions, first two
-    // coefficients), [nout][2] (the other two), [nout][4] (power mode: the second linear form).  The kernel's lanes read consecutive
-    // outputs: 32-byte row strides put the 16-byte reads 2-way and the 8-byte reads 4-way on the LDS banks (53 % of the bin phase's
-    // LDS cycles were conflicts); consecutive 16- and 8-byte elements of a plane do not conflict.
-    void planar_stft_tables() {
-        for (PlanOp &f : plan_.ops) {
-            FftDesc &d = f.fft;
-            if (f.kind != OpKind::FFT || d.otab_planar || f.bias2.space != Space::CONSTS) continue;
-            const int stride = d.otab_stride > 0 ? d.otab_stride : 8;
-            const std::vector<float> &ot = plan_.consts[f.bias2.id];
-            const int64_t n = d.nout;
-            if ((int64_t)ot.size() < f.bias2.offset + n * stride) continue;
-            std::vector<float> pl((size_t)(n * (d.power ? 10 : 6)), 0.0f);
-            for (int64_t c = 0; c < n; c++) {
-                const float *r = &ot[(size_t)(f.bias2.offset + c * stride)];
-                for (int q = 0; q < 4; q++) pl[(size_t)(c * 4 + q)] = r[q];
-                for (int q = 0; q < 2; q++) pl[(size_t)(4 * n + c * 2 + q)] = r[4 + q];
-                if (d.power)
-                    for (int q = 0; q < 4; q++) pl[(size_t)(6 * n + c * 4 + q)] = r[8 + q];
-            }
-            f.bias2 = Ref{Space::CONSTS, add_const(pl), 0};
-            d.otab_planar = 1;
-        }
-    }
-
-    // (F) The chunk stages of a whole-range min and a whole-range max over the SAME input (the min-max normalisation
-    // after the max(x - s) rewrite) read it in one pass: the later launch is folded into the earlier one (kernels.h,
-    // ReduceDesc::pair).  Exact, order-independent operations: same bits.  BN_REDUCE_PAIR=0 disables.
-    void pair_minmax_reductions() {
-        if (!sw_on(sw::BN_REDUCE_PAIR)) return;
-        for (size_t i = 0; i < plan_.ops.size(); i++) {
-            PlanOp &a = plan_.ops[i];
-            if (a.kind != OpKind::REDUCE || a.red.pair || a.red.op != RED_MIN) continue;
-            for (size_t j = i + 1; j < plan_.ops.size() && j < i + 4; j++) {
-                PlanOp &b = plan_.ops[j];
-                if (b.kind != OpKind::REDUCE || b.red.pair || b.red.op != RED_MAX) continue;
-                const ReduceDesc &x = a.red, &y = b.red;
-                const bool same_in = a.a.space == b.a.space && a.a.id == b.a.id && a.a.offset == b.a.offset;
-                const bool chunks = x.nk == 1 && x.nr == 1 && x.rin[0] == 1 && x.kout[0] == 1 && x.red % 4 == 0 && x.kin[0] % 4 == 0 && x.bi % 4 == 0 &&
-                                    a.a.offset % 4 == 0 && x.inner_kept == 0;
-                const bool same_shape = y.nk == 1 && y.nr == 1 && y.rin[0] == 1 && y.kout[0] == 1 && x.ksize[0] == y.ksize[0] && x.kin[0] == y.kin[0] &&
-                                        x.red == y.red && x.bi == y.bi && x.kept == y.kept;
-                if (!same_in || !chunks || !same_shape) continue;
-                // nothing in between may write the shared input or read the max partials (they are only read later)
-                bool clash = false;
-                for (size_t k = i + 1; k < j; k++) {
-                    const PlanOp &m = plan_.ops[k];
-                    clash = clash || (m.out.space == a.a.space && m.out.id == a.a.id) || (m.a.space == b.out.space && m.a.id == b.out.id);
-                }
-                if (clash) continue;
-                a.red.pair = 1;
-                a.red.bo2 = y.bo;
-                a.b = b.out;
-                a.name += "+" + b.name;
-                a.bytes += 4.0 * (double)y.kept;
-                plan_.ops.erase(plan_.ops.begin() + (long)j);
-                break;
-            }
-        }
-    }
-
-    // (E) An elementwise chain of unary stages (power-law compression, affine maps, layout copies) whose primary
-    // operand is the dense result of the GEMM launched just for it moves into that GEMM's epilogue: the stages run
-    // on the accumulators and the store goes through the chain's output view (kernels.h, GemmDesc::npost /
-    // out_strided).  v2.4 front end: mel MatMul -> x^2 -> x^p -> flip / transpose into the 2-channel image, per
-    // branch one launch instead of two and no dense [frames, mels] round trip.  BN_GEMMPOST=0 disables.
-    void absorb_chains_into_gemms() {
-        if (!sw_on(sw::BN_GEMMPOST)) return;
-        bool changed = true;
-        while (changed) {
-            changed = false;
-            std::vector<std::vector<int>> users(plan_.storages.size());
-            std::vector<Ref *> refs;
-            for (size_t k = 0; k < plan_.ops.size(); k++) {
-                all_refs(plan_.ops[k], refs);
-                for (Ref *r : refs)
-                    if (r->space == Space::ARENA && (users[r->id].empty() || users[r->id].back() != (int)k)) users[r->id].push_back((int)k);
-            }
-            for (size_t j = 0; j < plan_.ops.size() && !changed; j++) {
-                PlanOp &cons = plan_.ops[j];
-                if (cons.kind != OpKind::ELT || cons.a.space != Space::ARENA || cons.out.space != Space::ARENA) continue;
-                const auto &u = users[cons.a.id];
-                if (u.size() != 2 || u[1] != (int)j || plan_.storages[cons.a.id].pinned) continue;
-                PlanOp &prod = plan_.ops[u[0]];
-                if (prod.kind != OpKind::GEMM || prod.out.space != Space::ARENA || prod.out.id != cons.a.id) continue;
-                GemmDesc g = prod.gemm;
-                const EltDesc &ce = cons.elt;
-                // (round 4: the LDS-resident folded framing GEMM carries a chain of the compact stage functions and the consumer's view too)
-                const bool fold_post = (g.fold == 1 || g.fold == -1) && frame_fold_post_ok(g);
-                if (g.npost || g.out_strided || !(gemm_accepts_post(g) || fold_post) || g.ldc != g.N || g.c_bs != g.rows * g.N || ce.ba != g.c_bs) continue;
-                bool unary = true, compact = true;
-                int npost = 0;
-                for (int k = 0; k < ce.nstages; k++) {
-                    unary = unary && ce.st[k].bin == BIN_NONE;
-                    if (ce.st[k].act != ACT_NONE) { npost++; compact = compact && stft_act_supported(ce.st[k].act); }
-                }
-                if (!unary || npost > 4 || ce.per_sample != g.rows * g.N || (fold_post && !compact)) continue;
-                // the chain's index space must be (a signed permutation of) rows x N
-                int64_t rs = 0, cs = 0, base = cons.out.offset, want_delta = 0;
-                bool ok = true, have_row = g.rows == 1, have_col = g.N == 1;
-                for (int k = 0; k < ce.nd && ok; k++) {
-                    if (ce.size[k] == 1) continue;
-                    const int64_t sa = ce.sa[k], mag = sa < 0 ? -sa : sa;
-                    int64_t *dst = nullptr;
-                    if (!have_col && !have_row && sa == 1 && ce.size[k] == g.rows * g.N) {  // flat map over the dense result
-                        rs = g.N * ce.so[k]; cs = ce.so[k]; have_row = have_col = true;
-                        continue;
-                    }
-                    if (!have_col && mag == 1 && ce.size[k] == g.N) { dst = &cs; have_col = true; }
-                    else if (!have_row && mag == g.N && ce.size[k] == g.rows) { dst = &rs; have_row = true; }
-                    else { ok = false; break; }
-                    if (sa > 0) *dst = ce.so[k];
-                    else { *dst = -ce.so[k]; base += (ce.size[k] - 1) * ce.so[k]; want_delta += (ce.size[k] - 1) * mag; }
-                }
-                if (!ok || !have_row || !have_col || cons.a.offset - prod.out.offset != want_delta) continue;
-                g.out_strided = 1;
-                g.out_rs = rs; g.out_cs = cs;
-                g.c_bs = ce.bo;
-                g.npost = 0;
-                for (int k = 0; k < ce.nstages; k++)
-                    if (ce.st[k].act != ACT_NONE) {
-                        g.post_act[g.npost] = ce.st[k].act; g.post_p0[g.npost] = ce.st[k].p0; g.post_p1[g.npost] = ce.st[k].p1;
-                        g.npost++;
-                    }
-                prod.gemm = g;
-                prod.out = Ref{cons.out.space, cons.out.id, base};
-                prod.name += "+" + cons.name;
-                prod.bytes += cons.bytes - 8.0 * (double)ce.per_sample;  // the dense intermediate never touches memory
-                plan_.ops.erase(plan_.ops.begin() + j);
-                changed = true;
-            }
-        }
-    }
-
-    // --------------------------------------------------------- memory plan
-    // (round 5) every GEMM the one-tile-per-block LDS-DMA kernel takes gets its weights as three exact bf16 planes (plan_rules.h, pack_w3):
-    // the launch then runs on the bf16 matrix pipe with f32-complete products (gemm_dma3.hip).  Last pass over the descriptors: gate, pooled
-    // epilogue, inline squeeze-excite are all decided.  The f32 copy goes away with it when no other launch reads it.
-    void pack_bf16x3_weights() {
-        auto refs_of = [](PlanOp &op) {
-            std::vector<Ref *> r = {&op.a, &op.b, &op.w, &op.bias, &op.res, &op.scale, &op.w2, &op.bias2};
-            for (auto &e : op.eb) r.push_back(&e);
-            for (auto &e : op.x) r.push_back(&e);
-            return r;
-        };
-        for (auto &op : plan_.ops) {
-            if (op.kind != OpKind::GEMM || op.gemm2.N > 0 || op.gemm.fold || op.gemm.w3 || op.w.space != Space::CONSTS) continue;
-            if (!gemm_b3_shape_ok(op.gemm) && !gemm_dma3_wanted(op.gemm)) continue;
-            const int64_t N = op.gemm.N, K = op.gemm.K;
-            if ((int64_t)plan_.consts[(size_t)op.w.id].size() < op.w.offset + N * K) continue;
-            // BN_GEMM3: 0 = exact-f32 kernel, 1 = the LDS-DMA form everywhere, 2 (default) = the register-staged form wherever it applies
-            const bool b3 = gemm_b3_shape_ok(op.gemm);
-            std::vector<float> img = b3 ? pack_w3f(plan_.consts[(size_t)op.w.id].data() + op.w.offset, N, K) : pack_w3(plan_.consts[(size_t)op.w.id].data() + op.w.offset, N, K);
-            int users = 0;
-            for (auto &o2 : plan_.ops)
-                for (Ref *r : refs_of(o2)) users += r->space == Space::CONSTS && r->id == op.w.id;
-            if (users == 1 && op.w.offset == 0) plan_.consts[(size_t)op.w.id] = std::move(img);
-            else op.w = Ref{Space::CONSTS, add_const(img), 0};
-            op.gemm.w3 = b3 ? 2 : 1;
-            op.weight_bytes += 2.0 * (double)N * (double)((K + 31) / 32 * 32) + 4.0 * (double)N * (double)((K + 31) / 32 * 32 - K);  // 6 bytes per (padded) weight instead of 4
-        }
-    }
-
-    void plan_memory() {
-        // greedy first-fit over the linear launch order; storages are per-sample extents,
-        // rounded to 64 elements so that (offset * max_batch) stays 256-byte aligned.
-        struct Block { int64_t off, size; };
-        std::vector<Block> free_list;
-        int64_t top = 0;
-        auto alloc = [&](int64_t size) {
-            int best = -1;
-            for (size_t k = 0; k < free_list.size(); k++)
-                if (free_list[k].size >= size && (best < 0 || free_list[k].size < free_list[best].size)) best = (int)k;
-            if (best >= 0) {
-                int64_t off = free_list[best].off;
-                if (free_list[best].size == size) free_list.erase(free_list.begin() + best);
-                else { free_list[best].off += size; free_list[best].size -= size; }
-                return off;
-            }
-            int64_t off = top;
-            top += size;
-            return off;
-        };
-        auto release = [&](int64_t off, int64_t size) {
-            free_list.push_back({off, size});
-            std::sort(free_list.begin(), free_list.end(), [](const Block &a, const Block &b) { return a.off < b.off; });
-            for (size_t k = 0; k + 1 < free_list.size();) {
-                if (free_list[k].off + free_list[k].size == free_list[k + 1].off) { free_list[k].size += free_list[k + 1].size; free_list.erase(free_list.begin() + k + 1); }
-                else k++;
-            }
-            // give the tail back
-            if (!free_list.empty() && free_list.back().off + free_list.back().size == top) { top = free_list.back().off; free_list.pop_back(); }
-        };
-        auto rounded = [](int64_t e) { return (e + 63) / 64 * 64; };
-        int nops = (int)plan_.ops.size();
-        std::vector<std::vector<int>> starts(nops), ends(nops);
-        for (size_t s = 0; s < plan_.storages.size(); s++) {
-            auto &st = plan_.storages[s];
-            if (st.first < 0) continue;  // never touched
-            starts[st.first].push_back((int)s);
-            if (!st.pinned) ends[st.last].push_back((int)s);
-        }
-        int64_t peak = 0;
-        for (size_t s = 0; s < plan_.storages.size(); s++)
-            if (plan_.storages[s].persistent && plan_.storages[s].first >= 0) plan_.storages[s].arena_off = alloc(rounded(plan_.storages[s].elems));
-        for (int k = 0; k < nops; k++) {
-            for (int s : starts[k])
-                if (!plan_.storages[s].persistent) plan_.storages[s].arena_off = alloc(rounded(plan_.storages[s].elems));
-            peak = std::max(peak, top);
-            for (int s : ends[k]) release(plan_.storages[s].arena_off, rounded(plan_.storages[s].elems));
-        }
-        plan_.arena_elems = std::max<int64_t>(peak, 64);
-        // constants arena
-        int64_t coff = 0;
-        plan_.const_off.resize(plan_.consts.size());
-        for (size_t k = 0; k < plan_.consts.size(); k++) { plan_.const_off[k] = coff; coff += rounded((int64_t)plan_.consts[k].size()); }
-        plan_.consts_elems = std::max<int64_t>(coff, 64);
     }
 };
 

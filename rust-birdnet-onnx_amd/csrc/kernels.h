@@ -1,4 +1,4 @@
-// Launch descriptors shared by the planner (engine.cpp, host C++) and the HIP
+// Launch descriptors shared by the planner (engine.cpp and the files plan_build.h lists, host C++) and the HIP
 // kernels (kernels.hip, topk.hip).  All tensors are f32.  "Batch" is always the
 // outermost dimension and is the only run-time-variable size.
 #pragma once

@@ -1,4 +1,4 @@
-// Shape rules the planner (engine.cpp, host C++) and the launchers (*.hip) must agree on: which kernel a descriptor may
+// Shape rules the planner (engine.cpp and the files plan_build.h lists, host C++) and the launchers (*.hip) must agree on: which kernel a descriptor may
 // take and how much LDS that kernel carves up for it.  They are pure functions of per-sample quantities (and of the
 // BN_* switches, every one a row of the table in switches.h, read per call because the tests flip them), defined ONCE here and included by both sides --
 // so the host-only sanitizer build of the planner (tools/asan_plan.cpp, tests/test_planner_sanitizers.py) links without

@@ -35,7 +35,7 @@
     X(integer,     BN_GROUP_FORCE_RCCL,   0,      "non-zero: take the RCCL branch for ranks that share a device too (the test stub accepts such a communicator)") \
     X(present,     BN_GROUP_NO_RCCL,      false,  "gather with device copies even where RCCL would serve (presence only: =0 also disables RCCL)") \
     X(text,        BN_LIVE_SCATTER,       "direct", "copy = one async copy of the staging block, then the scatter on device memory; otherwise the kernel reads pinned memory") \
-    /* ---- planner: graph passes (engine.cpp) */ \
+    /* ---- planner: graph rewrites, lowering, plan passes (engine.cpp, onnx_rewrite.cpp, dft_bank.cpp, plan_passes.cpp) */ \
     X(integer,     BN_CANON_SPECTRO,      1,      "0 keeps the STFT / DFT exporter dialects as written instead of rewriting them into the framing-conv form") \
     X(integer,     BN_CONVMERGE,          -1,     "framing Conv -> Transpose -> MatMul as one filter bank: 0 never, 1 wherever the pattern matches, otherwise where it is cheaper") \
     X(text,        BN_CONVFOLD,           "1",    "0 = no symmetric fold of framing convs (only the exact text 0)") \
