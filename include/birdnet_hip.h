@@ -645,6 +645,72 @@ bn_status bn_index_cluster(bn_index *x, size_t k, uint64_t first_id, uint64_t n_
                            uint32_t *counts_out, bn_cluster_report *report, size_t report_size);
 
 /*
+ * Probed search: an inverted-file (IVF) view of an index.  The view holds k centroids, the exact assignment of the rows it covers
+ * and one member list per centroid; a search scores the query against the centroids, takes the nprobe best lists and scans only
+ * their rows.  The index's rule holds as a precise statement: A PROBED SEARCH RETURNS EXACTLY WHAT bn_index_search WOULD RETURN
+ * IF ONLY THE ROWS OF THE PROBED LISTS EXISTED, with the same score bits, order and tie rule.  The one approximation is which
+ * lists are probed, and that choice is exact, specified here and reported to the caller.  The reference has nothing of the kind;
+ * this comment is the contract.
+ *
+ *   Build          k in 1..1024; host centroids [k * dim] are used AS GIVEN and must be finite, as for bn_index_assign.  The
+ *                  assignment of rows [0, bn_index_size) is bn_index_assign's, to the byte: the same score chain, the same
+ *                  lowest-index tie rule, BN_CLUSTER_NONE for an invalid row and for one all of whose scores are NaN.  List c
+ *                  holds the ids of the rows assigned to c, ascending; a BN_CLUSTER_NONE row is in no list.  The view BORROWS
+ *                  the index: free it before the index, and keep to one thread at a time per index, the view included.
+ *   Memory         the view owns what it uses: the centroids [k, dim padded], the assignment planes and the member lists (3
+ *                  words per row of the index's capacity), 2 words per (query of a round, centroid) of probe scratch, and 32 MB
+ *                  of candidates.  A later bn_index_assign or bn_index_cluster on the index changes nothing the view returns.
+ *   Extend         rows appended after the build are not searched until bn_ivf_extend: before it every call behaves as if the
+ *                  index ended at bn_ivf_rows.  bn_ivf_extend assigns ids [bn_ivf_rows, bn_index_size) under the same centroids
+ *                  and rebuilds the lists; after it, lists and search results are byte-identical to a fresh bn_ivf_build with
+ *                  the same centroids.  The lists are rebuilt in place: a bn_ivf_extend that fails with BN_ERR_BACKEND leaves the
+ *                  view fit for bn_ivf_free only.
+ *   Probes         the score of a query against centroid c is the clustering score: the head block's chain + 0.0f, the bits of
+ *                  bn_head_apply_host for a head with W = centroids, no bias and flags 0.  For bn_ivf_search the chain runs on
+ *                  the query as the index normalises it (the row bn_index_read returns after bn_index_add_host of it); for
+ *                  bn_ivf_search_ids on the stored row.  Lists are taken by score descending, ties to the lowest centroid index
+ *                  (-0.0 == +0.0); a NaN score is never probed.  nprobe is in 1..k.  An empty list that ranks among the first
+ *                  nprobe still uses its slot.  probes_out[q * nprobe ..] receives the probed lists in that order; slots past
+ *                  the number probed, and every slot of an invalid query, hold BN_CLUSTER_NONE.  scanned_out[q] is the sum of
+ *                  the probed lists' sizes.  So for bn_ivf_search_ids the first probe of query id i is row i's assigned list.
+ *   Result         eligible rows are the members of the probed lists, less the exclusion radius for bn_ivf_search_ids.  Score,
+ *                  order, count, the top_m / m_stride limits and the handling of an invalid query (count 0) are
+ *                  bn_index_search's, word for word.  The bits of a (query, row) score are those bn_index_search gives that
+ *                  pair: they depend on the padded dim alone, not on the list, the row's position in it, nprobe, the number of
+ *                  queries of the call or how the lists are split among workgroups.  With nprobe == k and no BN_CLUSTER_NONE
+ *                  row, id_out, score_out and count_out equal bn_index_search's (bn_index_search_ids') bytes.
+ *   Refusals       BN_ERR_INVALID_ARG with a message, no output written and nothing changed: NULL where data is required (the
+ *                  index, the view, centroids, out, queries / query_ids, id_out, score_out, count_out, sizes_out, n_out, and
+ *                  ids_out for a list that is not empty), k outside 1..1024, nprobe outside 1..k, a non-finite centroid, top_m
+ *                  outside 1..256, m_stride < top_m, a query id >= bn_ivf_rows, list >= k, and cap smaller than the list (n_out
+ *                  still receives the size).
+ *   Empty cases    an empty index builds a view with k empty lists; its searches return count 0.
+ *   No device      without a gfx950 device every call that needs one (all but bn_ivf_free, bn_ivf_lists, bn_ivf_rows and
+ *                  bn_ivf_list_sizes) returns BN_ERR_NO_DEVICE and leaves the outputs untouched; a NULL output pointer, k outside
+ *                  1..1024, top_m outside 1..256 and m_stride < top_m are refused before the device is asked for.
+ *   Determinism    no floating-point atomics; two calls with the same inputs give the same bytes; one call with Q queries gives
+ *                  the same bytes as Q calls with one query each.
+ *
+ * Outputs are host arrays: id_out / score_out [n_queries * m_stride] and count_out [n_queries] as for bn_index_search;
+ * probes_out (u32) [n_queries * nprobe] and scanned_out (u64) [n_queries] may be NULL.  All calls are synchronous; like
+ * bn_index_search they first wait for a pending bn_index_add_ctx.  The index is unchanged.
+ */
+typedef struct bn_ivf bn_ivf;
+bn_status bn_ivf_build(bn_index *x, const float *centroids, size_t k, bn_ivf **out);
+void bn_ivf_free(bn_ivf *v);
+size_t bn_ivf_lists(const bn_ivf *v); /* k */
+size_t bn_ivf_rows(const bn_ivf *v);  /* the covered rows: ids [0, bn_ivf_rows) */
+bn_status bn_ivf_extend(bn_ivf *v);
+bn_status bn_ivf_list_sizes(const bn_ivf *v, uint32_t *sizes_out);
+/* ids_out [cap] receives the list's ids ascending, *n_out their number */
+bn_status bn_ivf_read_list(const bn_ivf *v, size_t list, uint64_t *ids_out, size_t cap, size_t *n_out);
+bn_status bn_ivf_search(bn_ivf *v, const float *queries, size_t n_queries, size_t nprobe, size_t top_m, size_t m_stride,
+                        uint64_t *id_out, float *score_out, uint32_t *count_out, uint32_t *probes_out, uint64_t *scanned_out);
+bn_status bn_ivf_search_ids(bn_ivf *v, const uint64_t *query_ids, size_t n_queries, int64_t exclude_radius, size_t nprobe,
+                            size_t top_m, size_t m_stride, uint64_t *id_out, float *score_out, uint32_t *count_out,
+                            uint32_t *probes_out, uint64_t *scanned_out);
+
+/*
  * Per-site species priors: the location / date prior of the reference's RangeFilter (src/rangefilter.rs) as an immutable
  * device table P[n_sites][n_species] (f32, row-major), applied to every row of a step.  The reference filters one
  * prediction list at a time on the host, by species name, after the cut to K; a table on the device serves a pool of a

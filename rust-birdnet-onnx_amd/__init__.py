@@ -54,6 +54,8 @@ ENGINE_SYMBOLS = [
     "bn_group_uses_rccl", "bn_group_get_stats", "bn_shard_range", "bn_group_analyze_recording", "bn_group_last_error", "bn_recording_create_resampled", "bn_resample_table", "bn_recording_read_f32", "bn_last_error",
     "bn_index_create", "bn_index_free", "bn_index_size", "bn_index_dim", "bn_index_add_host", "bn_index_add_ctx", "bn_index_read",
     "bn_index_search", "bn_index_search_ids", "bn_index_assign", "bn_index_cluster",
+    "bn_ivf_build", "bn_ivf_free", "bn_ivf_lists", "bn_ivf_rows", "bn_ivf_extend", "bn_ivf_list_sizes", "bn_ivf_read_list", "bn_ivf_search",
+    "bn_ivf_search_ids",
     "bn_head_create", "bn_head_free", "bn_head_dim", "bn_head_classes", "bn_head_flags", "bn_head_read", "bn_head_apply_host",
     "bn_head_fit", "bn_head_fit_index", "bn_head_rank_index", "bn_ctx_attach_head", "bn_step_head_results",
     "bn_prior_create", "bn_prior_free", "bn_prior_sites", "bn_prior_species", "bn_prior_threshold", "bn_prior_flags", "bn_prior_read",
@@ -226,6 +228,15 @@ def _load() -> C.CDLL:
         "bn_index_search_ids": (i32, [vp, C.POINTER(C.c_uint64), sz, C.c_int64, sz, sz, C.POINTER(C.c_uint64), f32p, u32p]),
         "bn_index_assign": (i32, [vp, f32p, sz, C.c_uint64, C.c_uint64, u32p, f32p]),
         "bn_index_cluster": (i32, [vp, sz, C.c_uint64, C.c_uint64, C.POINTER(BnClusterOpts), sz, f32p, u32p, f32p, u32p, C.POINTER(BnClusterReport), sz]),
+        "bn_ivf_build": (i32, [vp, f32p, sz, C.POINTER(vp)]),
+        "bn_ivf_free": (None, [vp]),
+        "bn_ivf_lists": (sz, [vp]),
+        "bn_ivf_rows": (sz, [vp]),
+        "bn_ivf_extend": (i32, [vp]),
+        "bn_ivf_list_sizes": (i32, [vp, u32p]),
+        "bn_ivf_read_list": (i32, [vp, sz, C.POINTER(C.c_uint64), sz, C.POINTER(sz)]),
+        "bn_ivf_search": (i32, [vp, f32p, sz, sz, sz, sz, C.POINTER(C.c_uint64), f32p, u32p, u32p, C.POINTER(C.c_uint64)]),
+        "bn_ivf_search_ids": (i32, [vp, C.POINTER(C.c_uint64), sz, C.c_int64, sz, sz, sz, C.POINTER(C.c_uint64), f32p, u32p, u32p, C.POINTER(C.c_uint64)]),
         "bn_head_create": (i32, [i32, sz, sz, f32p, f32p, C.c_uint32, C.POINTER(vp)]),
         "bn_head_free": (None, [vp]),
         "bn_head_dim": (sz, [vp]),
@@ -1277,6 +1288,89 @@ class Index:
                   "moved_last": int(rep.moved_last), "objective": float(rep.objective), "start_ids": None if ic is not None else start,
                   "objective_history": hist[:int(rep.history_len)].copy()}
         return cent, assign, scores, counts, report
+
+
+class Ivf:
+    """bn_ivf: an inverted-file view of an Index under `centroids` [k, dim] (used as given): the exact assignment of its rows and one
+    member list per centroid.  search / search_ids scan only the nprobe best lists of each query and return (ids [n, top_m] uint64,
+    scores [n, top_m] float32, counts [n] uint32, probes [n, nprobe] uint32, scanned [n] uint64): what Index.search would return if
+    only the probed lists' rows existed.  Rows appended to the index are searched after extend().  The view keeps the Index alive."""
+
+    def __init__(self, index: "Index", centroids):
+        c = np.ascontiguousarray(centroids, dtype=np.float32).reshape(-1, index.dim)
+        h = C.c_void_p()
+        st = lib.bn_ivf_build(index._h, c.ctypes.data_as(C.POINTER(C.c_float)), c.shape[0], C.byref(h))
+        if st:
+            raise EngineError(st)
+        self._h, self.index = h, index
+
+    def __del__(self):
+        if getattr(self, "_h", None) and lib is not None:
+            lib.bn_ivf_free(self._h)
+            self._h = None
+
+    def close(self):
+        self.__del__()
+
+    def __len__(self) -> int:
+        """the number of lists, k"""
+        return int(lib.bn_ivf_lists(self._h))
+
+    @property
+    def rows(self) -> int:
+        """the covered rows: ids [0, rows)"""
+        return int(lib.bn_ivf_rows(self._h))
+
+    def extend(self) -> None:
+        st = lib.bn_ivf_extend(self._h)
+        if st:
+            raise EngineError(st)
+
+    def list_sizes(self) -> np.ndarray:
+        out = np.zeros(len(self), dtype=np.uint32)
+        st = lib.bn_ivf_list_sizes(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32)))
+        if st:
+            raise EngineError(st)
+        return out
+
+    def read_list(self, c: int) -> np.ndarray:
+        """the ids of list c, ascending"""
+        n = C.c_size_t()
+        out = np.zeros(int(self.list_sizes()[c]) if 0 <= c < len(self) else 0, dtype=np.uint64)
+        st = lib.bn_ivf_read_list(self._h, c, out.ctypes.data_as(C.POINTER(C.c_uint64)), out.shape[0], C.byref(n))
+        if st:
+            raise EngineError(st)
+        return out[:int(n.value)]
+
+    @staticmethod
+    def _outputs(n: int, m_stride: int, nprobe: int):
+        return Index._outputs(n, m_stride) + (np.full((n, max(nprobe, 0)), BN_CLUSTER_NONE, dtype=np.uint32), np.zeros(n, dtype=np.uint64))
+
+    def search(self, queries, nprobe: int, top_m: int, m_stride: Optional[int] = None):
+        """Top-M rows by cosine among the nprobe best lists of each host query [n, dim]."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.index.dim)
+        m_stride = top_m if m_stride is None else m_stride
+        ids, scores, counts, probes, scanned = self._outputs(q.shape[0], max(m_stride, 0), nprobe)
+        st = lib.bn_ivf_search(self._h, q.ctypes.data_as(C.POINTER(C.c_float)), q.shape[0], nprobe, top_m, m_stride,
+                               ids.ctypes.data_as(C.POINTER(C.c_uint64)), scores.ctypes.data_as(C.POINTER(C.c_float)),
+                               counts.ctypes.data_as(C.POINTER(C.c_uint32)), probes.ctypes.data_as(C.POINTER(C.c_uint32)),
+                               scanned.ctypes.data_as(C.POINTER(C.c_uint64)))
+        if st:
+            raise EngineError(st)
+        return ids, scores, counts, probes, scanned
+
+    def search_ids(self, ids, nprobe: int, top_m: int, exclude_radius: int = -1, m_stride: Optional[int] = None):
+        """Query by example among the nprobe best lists of each stored row `ids`; rows within exclude_radius of a query's id are skipped."""
+        qi = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+        m_stride = top_m if m_stride is None else m_stride
+        out_ids, scores, counts, probes, scanned = self._outputs(qi.shape[0], max(m_stride, 0), nprobe)
+        st = lib.bn_ivf_search_ids(self._h, qi.ctypes.data_as(C.POINTER(C.c_uint64)), qi.shape[0], exclude_radius, nprobe, top_m, m_stride,
+                                   out_ids.ctypes.data_as(C.POINTER(C.c_uint64)), scores.ctypes.data_as(C.POINTER(C.c_float)),
+                                   counts.ctypes.data_as(C.POINTER(C.c_uint32)), probes.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                   scanned.ctypes.data_as(C.POINTER(C.c_uint64)))
+        if st:
+            raise EngineError(st)
+        return out_ids, scores, counts, probes, scanned
 
 
 def _fit_opts(n_classes: int, l2: float, tol: float, max_iters: int, l2norm: bool, pos_weight):

@@ -179,7 +179,7 @@ struct IndexScan {
     hipStream_t stream = nullptr;
     const float *slab = nullptr;     // rows padded to a multiple of 64, [.., dpad]
     const uint8_t *valid = nullptr;  // likewise
-    size_t dim = 0, dpad = 0, size = 0;
+    size_t dim = 0, dpad = 0, size = 0, cap_pad = 0;  // cap_pad: the rows the slab has room for
     int max_wg = 0;
     size_t lists = 0, out_lists = 0;
     topm::Cand *d_cand = nullptr, *d_out = nullptr, *h_out = nullptr;
@@ -187,6 +187,11 @@ struct IndexScan {
     uint32_t *d_count = nullptr, *h_count = nullptr;
 };
 bn_status index_scan_state(bn_index *x, IndexScan *out);
+// index.hip -> ivf.hip (bn_ivf_search, bn_ivf_search_ids): up to out_lists queries made ready in the index's own query buffers, on
+// its stream, exactly as bn_index_search / bn_index_search_ids prepare theirs: host rows normalised, or stored rows gathered by id
+// (ids below bn_index_size).  *d_q [n, dpad], *d_qvalid [n], *d_qid [n] (ids only) stay the index's
+bn_status index_stage_queries(bn_index *x, const float *queries, size_t n, const float **d_q, const uint8_t **d_qvalid);
+bn_status index_stage_query_ids(bn_index *x, const uint64_t *ids, size_t n, const float **d_q, const uint8_t **d_qvalid, const uint32_t **d_qid);
 // index.hip <-> cluster.hip (bn_index_assign, bn_index_cluster): the clustering buffers of an index, owned by cluster.hip, NULL until
 // a call first needs them; bn_index_free hands them to cluster_state_free with the index's stream idle
 struct ClusterState;

@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "capi_internal.h"
+#include "cluster_assign.h"
 #include "device_common.h"
 #include "hip_gate.h"
 #include "topm_select.h"
@@ -43,7 +44,7 @@ constexpr int TILE = 64;  // rows per workgroup tile: 4 waves x 16 rows
 constexpr int CP = 64;    // centroids per scan pass
 constexpr int WS_LD = KC + 4;
 constexpr int S_LD = TILE + 1;
-constexpr size_t K_MAX = 1024;
+using bn::cluster::K_MAX;
 constexpr uint32_t SEG = 256;         // members per segment of the update's sums
 constexpr int ARG_BLOCKS = 256;       // blocks of cluster_argmin_kernel
 constexpr uint32_t STATS_ROWS = 4096;  // rows per block of cluster_stats_kernel
@@ -351,13 +352,9 @@ __global__ __launch_bounds__(256) void cluster_pick_kernel(const Pick *__restric
 
 }  // namespace
 
-// an index's clustering buffers: each allocated when a call first needs it, grown when a call needs more
-struct bn::ClusterState {
-    float *d_cent = nullptr;  // [k, dpad]
-    size_t cent_n = 0;
-    float *d_best_s = nullptr;  // the running best plane, by row id
-    uint32_t *d_best_i = nullptr;
-    size_t best_n = 0;
+// an index's clustering buffers: each allocated when a call first needs it, grown when a call needs more (the centroids [k, dpad]
+// and the running best planes by row id are the base's)
+struct bn::ClusterState : bn::cluster::AssignBufs {
     uint32_t *d_prev_i = nullptr, *d_members = nullptr;  // the previous assignment; the member lists
     size_t list_n = 0;
     uint32_t *d_small = nullptr;  // counts [K_MAX], offsets [K_MAX + 1], scalars [2] (moved, kept centroids), start ids [K_MAX]
@@ -395,10 +392,6 @@ hipError_t ensure(T *&p, size_t &have, size_t n) {
     return e;
 }
 
-struct Range {
-    uint32_t id_lo, id_hi, tile_lo, tile_hi, tpw, n_wg;
-};
-
 bn_status check_common(const bn_index *x, size_t k, uint64_t first_id, uint64_t n_ids) {
     if (k < 1 || k > K_MAX) return set_last_error(BN_ERR_INVALID_ARG, "k must be in 1..1024, got " + std::to_string(k));
     const size_t size = bn_index_size(x);
@@ -406,6 +399,12 @@ bn_status check_common(const bn_index *x, size_t k, uint64_t first_id, uint64_t 
         return set_last_error(BN_ERR_INVALID_ARG, "rows [" + std::to_string(first_id) + ", +" + std::to_string(n_ids) + ") run past the index's " + std::to_string(size) + " rows");
     return BN_OK;
 }
+
+}  // namespace
+
+// ---- what ivf.hip shares (cluster_assign.h)
+namespace bn {
+namespace cluster {
 
 bn_status check_finite(const float *c, size_t n, const char *what) {
     for (size_t i = 0; i < n; i++)
@@ -427,7 +426,7 @@ Range range_of(const bn::IndexScan &s, uint64_t first_id, uint64_t n_ids) {
 }
 
 // the centroids and the running best planes (every row of the range's tiles is written by a pass)
-bn_status reserve_assign(bn::ClusterState *cs, const bn::IndexScan &s, size_t k) {
+bn_status reserve_assign(AssignBufs *cs, const bn::IndexScan &s, size_t k) {
     BN_HIP_TRY(ensure(cs->d_cent, cs->cent_n, k * s.dpad));
     const size_t rows = (s.size + TILE - 1) / TILE * TILE;
     if (rows > cs->best_n) {
@@ -439,7 +438,7 @@ bn_status reserve_assign(bn::ClusterState *cs, const bn::IndexScan &s, size_t k)
     return BN_OK;
 }
 
-bn_status upload_centroids(bn::ClusterState *cs, const bn::IndexScan &s, const float *c, size_t k) {
+bn_status upload_centroids(AssignBufs *cs, const bn::IndexScan &s, const float *c, size_t k) {
     std::vector<float> pad(k * s.dpad, 0.f);
     for (size_t i = 0; i < k; i++) memcpy(pad.data() + i * s.dpad, c + i * s.dim, s.dim * sizeof(float));
     BN_HIP_TRY(bn::gated::Memcpy(cs->d_cent, pad.data(), pad.size() * sizeof(float), hipMemcpyHostToDevice));
@@ -447,7 +446,7 @@ bn_status upload_centroids(bn::ClusterState *cs, const bn::IndexScan &s, const f
 }
 
 // one pass of the scan: centroids [c0, c0 + nc) of d_cent against the range
-bn_status enqueue_pass(bn::ClusterState *cs, const bn::IndexScan &s, const Range &r, size_t c0, int nc, bool first_pass) {
+bn_status enqueue_pass(AssignBufs *cs, const bn::IndexScan &s, const Range &r, size_t c0, int nc, bool first_pass) {
     const float *W = cs->d_cent + c0 * s.dpad;
     uint32_t lo = r.id_lo, hi = r.id_hi, d = (uint32_t)s.dpad, cc0 = (uint32_t)c0, tl = r.tile_lo, th = r.tile_hi, tpw = r.tpw;
     int first = first_pass ? 1 : 0;
@@ -457,13 +456,35 @@ bn_status enqueue_pass(bn::ClusterState *cs, const bn::IndexScan &s, const Range
 }
 
 // the exact assignment of the range under d_cent[0 .. k): ascending passes of CP centroids
-bn_status enqueue_assign(bn::ClusterState *cs, const bn::IndexScan &s, const Range &r, size_t k) {
+bn_status enqueue_assign(AssignBufs *cs, const bn::IndexScan &s, const Range &r, size_t k) {
     for (size_t c0 = 0; c0 < k; c0 += CP) {
         bn_status st = enqueue_pass(cs, s, r, c0, (int)std::min<size_t>(CP, k - c0), c0 == 0);
         if (st != BN_OK) return st;
     }
     return check_launch("cluster scan");
 }
+
+bn_status enqueue_member_lists(const uint32_t *d_best_i, uint32_t id_lo, uint32_t id_hi, const uint32_t *d_counts, uint32_t k, uint32_t *d_offsets,
+                               uint32_t *d_members, hipStream_t stream) {
+    const uint64_t n = id_hi - id_lo;
+    const uint32_t quarter = (uint32_t)(((n + 3) / 4 + 63) / 64 * 64);
+    hipLaunchKernelGGL(cluster_offsets_kernel, dim3(1), dim3(64), 0, stream, d_counts, k, d_offsets);
+    hipLaunchKernelGGL(cluster_members_kernel, dim3(k), dim3(256), 0, stream, d_best_i, id_lo, id_hi, quarter, d_offsets, d_members);
+    return check_launch("cluster member lists");
+}
+
+}  // namespace cluster
+}  // namespace bn
+
+namespace {
+
+using bn::cluster::check_finite;
+using bn::cluster::enqueue_assign;
+using bn::cluster::enqueue_pass;
+using bn::cluster::range_of;
+using bn::cluster::Range;
+using bn::cluster::reserve_assign;
+using bn::cluster::upload_centroids;
 
 bn_status planes_to_host(bn::ClusterState *cs, const bn::IndexScan &s, const Range &r, uint32_t *assign_out, float *score_out) {
     const size_t n = r.id_hi - r.id_lo;
@@ -633,9 +654,7 @@ extern "C" bn_status bn_index_cluster(bn_index *x, size_t k, uint64_t first_id, 
         if (rep.iters >= o.max_iters) break;
 
         // the update: member lists, segment sums folded in order, the norm
-        const uint32_t quarter = (uint32_t)(((n + 3) / 4 + 63) / 64 * 64);
-        hipLaunchKernelGGL(cluster_offsets_kernel, dim3(1), dim3(64), 0, s.stream, d_counts, kk, d_offsets);
-        hipLaunchKernelGGL(cluster_members_kernel, dim3(kk), dim3(256), 0, s.stream, cs->d_best_i, r.id_lo, r.id_hi, quarter, d_offsets, cs->d_members);
+        if ((st = bn::cluster::enqueue_member_lists(cs->d_best_i, r.id_lo, r.id_hi, d_counts, kk, d_offsets, cs->d_members, s.stream)) != BN_OK) return st;
         const uint32_t max_count = *std::max_element(h_counts, h_counts + k);
         const uint32_t n_seg = std::max<uint32_t>(1, (max_count + SEG - 1) / SEG);  // one round even for empty clusters: it zeroes acc
         for (uint32_t seg0 = 0; seg0 < n_seg; seg0 += slots) {

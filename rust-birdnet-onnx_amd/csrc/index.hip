@@ -350,6 +350,29 @@ void scatter(const bn_index *x, size_t nq, size_t M, size_t m_stride, uint64_t *
     }
 }
 
+// host queries [nq, dim] (nq <= QCHUNK) -> d_q / d_qvalid, normalised as appended rows are
+bn_status stage_host_queries(bn_index *x, const float *queries, size_t nq) {
+    for (size_t s0 = 0; s0 < nq; s0 += STAGE_ROWS) {
+        const size_t k = std::min(STAGE_ROWS, nq - s0);
+        BN_HIP_TRY(hipStreamSynchronize(x->stream));
+        BN_HIP_TRY(bn::gated::Memcpy(x->d_stage, queries + s0 * x->dim, k * x->dim * sizeof(float), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(index_normalise_kernel, dim3((unsigned)((k + 3) / 4)), dim3(256), 0, x->stream, x->d_stage, x->dim, (uint32_t)k,
+                           (uint32_t)x->dim, x->d_q + s0 * x->dpad, (uint32_t)x->dpad, x->d_qvalid + s0);
+        if (bn_status st = check_launch("index normalise"); st != BN_OK) return st;
+    }
+    return BN_OK;
+}
+
+// stored rows query_ids[0 .. nq) (nq <= QCHUNK, every id in the index) -> d_qid, d_q / d_qvalid
+bn_status stage_id_queries(bn_index *x, const uint64_t *query_ids, size_t nq) {
+    const std::vector<uint32_t> ids(query_ids, query_ids + nq);
+    BN_HIP_TRY(hipStreamSynchronize(x->stream));
+    BN_HIP_TRY(bn::gated::Memcpy(x->d_qid, ids.data(), nq * sizeof(uint32_t), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(index_gather_kernel, dim3((unsigned)nq), dim3(256), 0, x->stream, x->slab, x->valid, x->d_qid, (uint32_t)x->dpad, x->d_q,
+                       x->d_qvalid);
+    return check_launch("index gather");
+}
+
 bn_status reserve_rows(const bn_index *x, size_t n) {
     if (n > x->cap - x->size)
         return set_last_error(BN_ERR_INVALID_ARG, "append of " + std::to_string(n) + " rows exceeds the index capacity (" + std::to_string(x->size) + " of " +
@@ -373,6 +396,27 @@ bn_status bn::index_rows(bn_index *x, IndexRows *out) {
     return BN_OK;
 }
 
+bn_status bn::index_stage_queries(bn_index *x, const float *queries, size_t n, const float **d_q, const uint8_t **d_qvalid) {
+    if (!x || !queries || n > QCHUNK) return set_last_error(BN_ERR_INVALID_ARG, "index_stage_queries: bad argument");
+    bn_status st = begin(x);
+    if (st != BN_OK) return st;
+    if ((st = stage_host_queries(x, queries, n)) != BN_OK) return st;
+    *d_q = x->d_q;
+    *d_qvalid = x->d_qvalid;
+    return BN_OK;
+}
+
+bn_status bn::index_stage_query_ids(bn_index *x, const uint64_t *ids, size_t n, const float **d_q, const uint8_t **d_qvalid, const uint32_t **d_qid) {
+    if (!x || !ids || n > QCHUNK) return set_last_error(BN_ERR_INVALID_ARG, "index_stage_query_ids: bad argument");
+    bn_status st = begin(x);
+    if (st != BN_OK) return st;
+    if ((st = stage_id_queries(x, ids, n)) != BN_OK) return st;
+    *d_q = x->d_q;
+    *d_qvalid = x->d_qvalid;
+    *d_qid = x->d_qid;
+    return BN_OK;
+}
+
 bn::ClusterState **bn::index_cluster_state(bn_index *x) { return &x->cluster; }
 
 bn_status bn::index_scan_state(bn_index *x, IndexScan *out) {
@@ -386,6 +430,7 @@ bn_status bn::index_scan_state(bn_index *x, IndexScan *out) {
     out->dim = x->dim;
     out->dpad = x->dpad;
     out->size = x->size;
+    out->cap_pad = x->cap_pad;
     out->max_wg = x->max_wg;
     out->lists = QP;
     out->out_lists = QCHUNK;
@@ -520,14 +565,7 @@ bn_status bn_index_search(bn_index *x, const float *queries, size_t n_queries, s
             std::fill(count_out + q0, count_out + q0 + nq, 0u);
             continue;
         }
-        for (size_t s0 = 0; s0 < nq; s0 += STAGE_ROWS) {
-            const size_t k = std::min(STAGE_ROWS, nq - s0);
-            BN_HIP_TRY(hipStreamSynchronize(x->stream));
-            BN_HIP_TRY(bn::gated::Memcpy(x->d_stage, queries + (q0 + s0) * x->dim, k * x->dim * sizeof(float), hipMemcpyHostToDevice));
-            hipLaunchKernelGGL(index_normalise_kernel, dim3((unsigned)((k + 3) / 4)), dim3(256), 0, x->stream, x->d_stage, x->dim, (uint32_t)k,
-                               (uint32_t)x->dim, x->d_q + s0 * x->dpad, (uint32_t)x->dpad, x->d_qvalid + s0);
-            if ((st = check_launch("index normalise")) != BN_OK) return st;
-        }
+        if ((st = stage_host_queries(x, queries + q0 * x->dim, nq)) != BN_OK) return st;
         if ((st = run_search(x, nq, false, -1, (int)top_m)) != BN_OK) return st;
         scatter(x, nq, top_m, m_stride, id_out + q0 * m_stride, score_out + q0 * m_stride, count_out + q0);
     }
@@ -541,15 +579,9 @@ bn_status bn_index_search_ids(bn_index *x, const uint64_t *query_ids, size_t n_q
     for (size_t i = 0; i < n_queries; i++)
         if (query_ids[i] >= x->size) return set_last_error(BN_ERR_INVALID_ARG, "query id " + std::to_string(query_ids[i]) + " is not in the index");
     if ((st = begin(x)) != BN_OK) return st;
-    std::vector<uint32_t> ids;
     for (size_t q0 = 0; q0 < n_queries; q0 += QCHUNK) {
         const size_t nq = std::min(QCHUNK, n_queries - q0);
-        ids.assign(query_ids + q0, query_ids + q0 + nq);
-        BN_HIP_TRY(hipStreamSynchronize(x->stream));
-        BN_HIP_TRY(bn::gated::Memcpy(x->d_qid, ids.data(), nq * sizeof(uint32_t), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(index_gather_kernel, dim3((unsigned)nq), dim3(256), 0, x->stream, x->slab, x->valid, x->d_qid, (uint32_t)x->dpad, x->d_q,
-                           x->d_qvalid);
-        if ((st = check_launch("index gather")) != BN_OK) return st;
+        if ((st = stage_id_queries(x, query_ids + q0, nq)) != BN_OK) return st;
         if ((st = run_search(x, nq, true, exclude_radius, (int)top_m)) != BN_OK) return st;
         scatter(x, nq, top_m, m_stride, id_out + q0 * m_stride, score_out + q0 * m_stride, count_out + q0);
     }
