@@ -711,6 +711,78 @@ bn_status bn_ivf_search_ids(bn_ivf *v, const uint64_t *query_ids, size_t n_queri
                             uint32_t *probes_out, uint64_t *scanned_out);
 
 /*
+ * Persistence of an index: bn_index_save writes the slab's STORED BITS to a file, bn_index_load makes an index from one.  A loaded
+ * index behaves in every call exactly as the saved one did at the time of the save: searches, head fits and ranks, assignment,
+ * clustering and IVF views are all stated in the bits of the stored rows, and those are what the file holds.  bn_index_read
+ * followed by bn_index_add_host is NOT that: the append normalises again, x / sqrt(sum x^2) of a unit row is not the row in f32,
+ * and a fifth to a quarter of the rows come back with other bits (measured at dim 3, 130 and 1536).  Heads (bn_head_read /
+ * bn_head_create) and IVF views (bn_ivf_build from the caller's centroids) round-trip through their own entry points; only the
+ * index needs a file.
+ *
+ *   File           version 1, little-endian, fully determined by the index contents and chunk_rows:
+ *                    bytes 0..8    magic "BNINDEX1"
+ *                          8..12   u32 version = 1
+ *                          12..16  u32 dim
+ *                          16..24  u64 rows (bn_index_size at the time of the save)
+ *                          24..28  u32 chunk_rows (>= 1)
+ *                          28..32  u32 n_chunks = ceil(rows / chunk_rows), 0 when rows = 0
+ *                          32..40  u64 valid_rows
+ *                          40..56  zero
+ *                          56..64  u64 header digest
+ *                          64..    n_chunks x u64 chunk digests, then rows x dim f32 in id order, row stride dim (no padding)
+ *                  The size is exactly 64 + 8 * n_chunks + 4 * rows * dim.  No validity flags are stored: a row is invalid exactly
+ *                  when every element is +0.0 or -0.0 ((bits & 0x7fffffff) == 0) -- the index stores the rows it never returns as
+ *                  zeros, and a unit row has a non-zero element.
+ *   Digest         for the element of row r, component k, with f32 bits b: u = r * dim + k; z = u * 0x9E3779B97F4A7C15 + b;
+ *                  z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^= z >> 31 (mod 2^64).  A
+ *                  chunk's digest is the sum mod 2^64 of z over the elements of its rows [c * chunk_rows, (c + 1) * chunk_rows);
+ *                  the header digest is the same sum over the fourteen u32 words of bytes 0..56 (u = the word's number, b = the
+ *                  word).  A sum of integers: any order of addition gives the same digest, on the device and on the host.
+ *   Save           chunk_rows == 0 takes max(1, 2^21 / dim); a chunk_rows above 2^32 - 1 is refused.  The call waits for a pending
+ *                  bn_index_add_ctx as a search does, and leaves the index unchanged.  It writes to a temporary name in the
+ *                  directory of `path` ("<path>.tmp.<pid>.<n>", n counted per process: saves from two threads do not collide, and
+ *                  a temporary a crashed process left behind is stepped over, never opened) and renames it onto `path` only after
+ *                  everything is written and the file flushed (fsync).  The directory is flushed after the rename where the file
+ *                  system allows it; a failure of that last flush is not reported, so after a power loss the name may still be
+ *                  the old file's, never a partial one.  On any failure the temporary is removed and a file that existed at `path`
+ *                  is untouched.  Two saves of the same index with the same chunk_rows give identical bytes.
+ *   Load           capacity_rows == 0: the file's row count (1 for an empty file).  The new index has bn_index_size = the file's
+ *                  rows, bn_index_read returns the file's payload bytes, invalid rows (by the rule above) are never returned, and
+ *                  later appends continue the ids.  Every digest is recomputed on the device while the rows are placed, and every
+ *                  element is tested for finiteness; the index exists only if all of it agrees with the file.
+ *   Refusals       *out stays NULL, nothing is leaked, the message is in bn_last_error.
+ *                  BN_ERR_MODEL_LOAD (the file is unreadable or malformed; bn_index_load, bn_index_file_info and
+ *                  bn_index_file_verify alike): a path that cannot be opened, wrong magic, wrong version, a header digest
+ *                  mismatch, dim == 0 or above 2^20, rows above 2^32 - 66 (the largest capacity), chunk_rows == 0, an n_chunks not
+ *                  ceil(rows / chunk_rows), non-zero reserved bytes, a size other than the header's (truncated or trailing
+ *                  bytes); and, from bn_index_load and bn_index_file_verify, which read the payload: a chunk digest mismatch (the
+ *                  message names the first bad chunk), a non-finite element, a valid_rows that disagrees with the payload.
+ *                  BN_ERR_INVALID_ARG (the caller's mistake): NULL where data is required, a capacity_rows below the file's rows
+ *                  or above 2^32 - 66, a struct_size below the struct's, a chunk_rows above 2^32 - 1, and a `path` of
+ *                  bn_index_save whose temporary cannot be created (a directory that does not exist or is not writable).
+ *                  BN_ERR_BACKEND: a write, flush or rename of bn_index_save that fails after that (a full disk), and runtime errors.
+ *   No device      bn_index_file_info and bn_index_file_verify need none.  bn_index_load checks the header and the file size on the
+ *                  host FIRST (a malformed file is BN_ERR_MODEL_LOAD on every machine) and then returns BN_ERR_NO_DEVICE without a
+ *                  gfx950 device.
+ *   Determinism    no floating-point atomics; the digests are integer sums.
+ *
+ * bn_index_file_verify recomputes every digest on the CPU and applies the finite and valid_rows rules; *first_bad_chunk (may be
+ * NULL) receives the first chunk with a digest mismatch or, failing that, a non-finite element, and UINT64_MAX otherwise.
+ */
+typedef struct bn_index_file_info_t { /* the function of the same stem needs a type name of its own in C */
+    uint64_t rows;
+    uint64_t valid_rows;
+    uint32_t dim;
+    uint32_t chunk_rows;
+    uint32_t n_chunks;
+    uint32_t version;
+} bn_index_file_info_t;
+bn_status bn_index_save(bn_index *x, const char *path, size_t chunk_rows);
+bn_status bn_index_load(int32_t device, const char *path, size_t capacity_rows, bn_index **out);
+bn_status bn_index_file_info(const char *path, bn_index_file_info_t *out, size_t struct_size);
+bn_status bn_index_file_verify(const char *path, uint64_t *first_bad_chunk);
+
+/*
  * Per-site species priors: the location / date prior of the reference's RangeFilter (src/rangefilter.rs) as an immutable
  * device table P[n_sites][n_species] (f32, row-major), applied to every row of a step.  The reference filters one
  * prediction list at a time on the host, by species name, after the cut to K; a table on the device serves a pool of a

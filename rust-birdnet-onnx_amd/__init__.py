@@ -54,6 +54,7 @@ ENGINE_SYMBOLS = [
     "bn_group_uses_rccl", "bn_group_get_stats", "bn_shard_range", "bn_group_analyze_recording", "bn_group_last_error", "bn_recording_create_resampled", "bn_resample_table", "bn_recording_read_f32", "bn_last_error",
     "bn_index_create", "bn_index_free", "bn_index_size", "bn_index_dim", "bn_index_add_host", "bn_index_add_ctx", "bn_index_read",
     "bn_index_search", "bn_index_search_ids", "bn_index_assign", "bn_index_cluster",
+    "bn_index_save", "bn_index_load", "bn_index_file_info", "bn_index_file_verify",
     "bn_ivf_build", "bn_ivf_free", "bn_ivf_lists", "bn_ivf_rows", "bn_ivf_extend", "bn_ivf_list_sizes", "bn_ivf_read_list", "bn_ivf_search",
     "bn_ivf_search_ids",
     "bn_head_create", "bn_head_free", "bn_head_dim", "bn_head_classes", "bn_head_flags", "bn_head_read", "bn_head_apply_host",
@@ -125,6 +126,11 @@ class BnClusterOpts(C.Structure):
 class BnClusterReport(C.Structure):
     _fields_ = [("iters", C.c_uint32), ("converged", C.c_int32), ("empty_clusters", C.c_uint32), ("moved_last", C.c_uint32),
                 ("objective", C.c_double), ("history_len", C.c_uint32)]
+
+
+class BnIndexFileInfo(C.Structure):
+    _fields_ = [("rows", C.c_uint64), ("valid_rows", C.c_uint64), ("dim", C.c_uint32), ("chunk_rows", C.c_uint32), ("n_chunks", C.c_uint32),
+                ("version", C.c_uint32)]
 
 
 BN_CLUSTER_NONE = 0xFFFFFFFF  # the assignment of a row that belongs to no cluster
@@ -228,6 +234,10 @@ def _load() -> C.CDLL:
         "bn_index_search_ids": (i32, [vp, C.POINTER(C.c_uint64), sz, C.c_int64, sz, sz, C.POINTER(C.c_uint64), f32p, u32p]),
         "bn_index_assign": (i32, [vp, f32p, sz, C.c_uint64, C.c_uint64, u32p, f32p]),
         "bn_index_cluster": (i32, [vp, sz, C.c_uint64, C.c_uint64, C.POINTER(BnClusterOpts), sz, f32p, u32p, f32p, u32p, C.POINTER(BnClusterReport), sz]),
+        "bn_index_save": (i32, [vp, C.c_char_p, sz]),
+        "bn_index_load": (i32, [i32, C.c_char_p, sz, C.POINTER(vp)]),
+        "bn_index_file_info": (i32, [C.c_char_p, C.POINTER(BnIndexFileInfo), sz]),
+        "bn_index_file_verify": (i32, [C.c_char_p, C.POINTER(C.c_uint64)]),
         "bn_ivf_build": (i32, [vp, f32p, sz, C.POINTER(vp)]),
         "bn_ivf_free": (None, [vp]),
         "bn_ivf_lists": (sz, [vp]),
@@ -1243,6 +1253,25 @@ class Index:
             raise EngineError(st)
         return out_ids, scores, counts
 
+    def save(self, path, chunk_rows: int = 0) -> None:
+        """bn_index_save: the stored bits of every row to `path` (written under a temporary name, renamed when complete); chunk_rows
+        0 takes the default.  Index.load(path) gives an index that answers every call as this one does now."""
+        st = lib.bn_index_save(self._h, os.fsencode(path), chunk_rows)
+        if st:
+            raise EngineError(st)
+
+    @classmethod
+    def load(cls, path, device: int = 0, capacity_rows: int = 0) -> "Index":
+        """bn_index_load: an index holding the rows of a file Index.save wrote, with room for capacity_rows rows (0: the file's)."""
+        h = C.c_void_p()
+        st = lib.bn_index_load(device, os.fsencode(path), capacity_rows, C.byref(h))
+        if st:
+            raise EngineError(st)
+        x = cls.__new__(cls)
+        x._h, x.device, x.dim = h, device, int(lib.bn_index_dim(h))
+        x.capacity = capacity_rows if capacity_rows else max(int(lib.bn_index_size(h)), 1)
+        return x
+
     def _range(self, first_id: int, n_ids: int) -> int:
         return max((n_ids if n_ids else len(self) - first_id), 0)
 
@@ -1288,6 +1317,26 @@ class Index:
                   "moved_last": int(rep.moved_last), "objective": float(rep.objective), "start_ids": None if ic is not None else start,
                   "objective_history": hist[:int(rep.history_len)].copy()}
         return cent, assign, scores, counts, report
+
+
+def index_file_info(path) -> dict:
+    """bn_index_file_info: the header fields of an index file (host only): dim, rows, valid_rows, chunk_rows, n_chunks, version."""
+    info = BnIndexFileInfo()
+    st = lib.bn_index_file_info(os.fsencode(path), C.byref(info), C.sizeof(info))
+    if st:
+        raise EngineError(st)
+    return {k: int(getattr(info, k)) for k in ("dim", "rows", "valid_rows", "chunk_rows", "n_chunks", "version")}
+
+
+def index_file_verify(path) -> None:
+    """bn_index_file_verify: every digest of an index file recomputed on the CPU, the finite and valid_rows rules applied (host only).
+    Raises EngineError; its first_bad_chunk is the first chunk with a digest mismatch or a non-finite element, else None."""
+    bad = C.c_uint64()
+    st = lib.bn_index_file_verify(os.fsencode(path), C.byref(bad))
+    if st:
+        e = EngineError(st)
+        e.first_bad_chunk = None if bad.value == 0xFFFFFFFFFFFFFFFF else int(bad.value)
+        raise e
 
 
 class Ivf:

@@ -10,6 +10,7 @@
 
 #include "../../include/birdnet_hip.h"
 #include "hip_gate.h"
+#include "last_error.h"
 
 // a failed runtime call ends the enclosing function with BN_ERR_BACKEND and the call's text in the message
 #define BN_HIP_TRY(expr)                                                                                                   \
@@ -19,9 +20,6 @@
     } while (0)
 
 namespace bn {
-// sets the message bn_last_error() returns on this thread; returns st
-bn_status set_last_error(bn_status st, const std::string &msg);
-
 // ---- step_common.cpp ----
 // before a launch: drops the thread's pending launcher refusal and the runtime's sticky error, both of unrelated earlier calls
 void clear_launch_state();
@@ -192,6 +190,18 @@ bn_status index_scan_state(bn_index *x, IndexScan *out);
 // (ids below bn_index_size).  *d_q [n, dpad], *d_qvalid [n], *d_qid [n] (ids only) stay the index's
 bn_status index_stage_queries(bn_index *x, const float *queries, size_t n, const float **d_q, const uint8_t **d_qvalid);
 bn_status index_stage_query_ids(bn_index *x, const uint64_t *ids, size_t n, const float **d_q, const uint8_t **d_qvalid, const uint32_t **d_qid);
+// index.hip <-> index_io.hip (bn_index_save, bn_index_load): the slab itself.  index_io_state makes the device current and orders the
+// index's stream after a pending bn_index_add_ctx, without waiting.  index_adopt_rows ends a load: rows [0, n) of an EMPTY index
+// (n <= its capacity) were written, with their valid bytes and zeroed pad columns, by work that has completed
+struct IndexIo {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    float *slab = nullptr;     // [cap, dpad]
+    uint8_t *valid = nullptr;  // [cap]
+    size_t dim = 0, dpad = 0, size = 0, cap = 0;
+};
+bn_status index_io_state(bn_index *x, IndexIo *out);
+bn_status index_adopt_rows(bn_index *x, size_t n);
 // index.hip <-> cluster.hip (bn_index_assign, bn_index_cluster): the clustering buffers of an index, owned by cluster.hip, NULL until
 // a call first needs them; bn_index_free hands them to cluster_state_free with the index's stream idle
 struct ClusterState;

@@ -443,6 +443,27 @@ bn_status bn::index_scan_state(bn_index *x, IndexScan *out) {
     return BN_OK;
 }
 
+bn_status bn::index_io_state(bn_index *x, IndexIo *out) {
+    if (!x || !out) return set_last_error(BN_ERR_INVALID_ARG, "null index");
+    bn_status st = begin(x);
+    if (st != BN_OK) return st;
+    out->device = x->device;
+    out->stream = x->stream;
+    out->slab = x->slab;
+    out->valid = x->valid;
+    out->dim = x->dim;
+    out->dpad = x->dpad;
+    out->size = x->size;
+    out->cap = x->cap;
+    return BN_OK;
+}
+
+bn_status bn::index_adopt_rows(bn_index *x, size_t n) {
+    if (!x || x->size != 0 || n > x->cap) return set_last_error(BN_ERR_INVALID_ARG, "index_adopt_rows: bad argument");
+    x->size = n;
+    return BN_OK;
+}
+
 extern "C" {
 
 bn_status bn_index_create(int32_t device, size_t dim, size_t capacity_rows, bn_index **out) {
