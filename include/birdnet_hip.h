@@ -711,6 +711,74 @@ bn_status bn_ivf_search_ids(bn_ivf *v, const uint64_t *query_ids, size_t n_queri
                             uint32_t *probes_out, uint64_t *scanned_out);
 
 /*
+ * Coarse int8 search with exact re-rank: an 8-bit view of an index.  The view holds one code byte per slab element and one f32 scale
+ * per row; a search ranks every covered row by an exact integer key, keeps the `refine` best as the query's candidates and re-scores
+ * those with the index's own score.  The index's rule holds as a precise statement: A bn_sq8 SEARCH RETURNS EXACTLY WHAT
+ * bn_index_search WOULD RETURN IF ONLY THE QUERY'S `refine` COARSE CANDIDATES EXISTED, with the same score bits, order and tie rule.
+ * The one approximation is which rows become candidates, and that choice is exact, specified here and reported to the caller.  The
+ * reference has nothing of the kind; this comment is the contract.
+ *
+ *   Code of a row  r = the stored f32 row (what bn_index_read returns), a = max_k |r[k]|.  An invalid row (stored as zeros) has all
+ *                  codes 0 and scale +0.0f.  Otherwise inv = 127.0f / a (IEEE f32 division), code[k] = clamp(rint(r[k] * inv), -127,
+ *                  127) with the product ONE f32 multiply rounded to nearest and rint to nearest, ties to even, and scale = a /
+ *                  127.0f.  Pad columns hold code 0.  The bits are a function of the stored row alone: not of its id, the rows
+ *                  around it, or whether build or extend wrote them.
+ *   Query          the same rule, applied to the query as the index stages it: bn_sq8_search on the row as the index normalises it
+ *                  (what bn_index_read returns after bn_index_add_host of it), bn_sq8_search_ids on the stored row, whose code is
+ *                  therefore that row's code in the plane.
+ *   Coarse key     of (query, row): D = sum_k qcode[k] * code[k] in int32 -- exact, since 127^2 * dim < 2^31 for dim <= 131072,
+ *                  and free of summation order; key = (float)D * scale_row, a round-to-nearest int -> f32 conversion and one f32
+ *                  multiply.  The query's scale is a positive constant per query and is left out.  A key is always finite; D == 0
+ *                  gives +0.0f.
+ *   Candidates     a row is eligible when it is valid, has an id < bn_sq8_rows and, for bn_sq8_search_ids, lies outside the
+ *                  exclusion radius.  The candidates are the first `refine` eligible rows by key descending, ties by id ascending.
+ *                  cand_out[q * refine ..] receives their ids in that order, cand_count_out[q] = min(refine, eligible rows);
+ *                  entries past the count are not written.  An invalid query has cand_count 0 and count 0.
+ *   Result         the candidates re-scored with bn_index_search's score: the bits are those bn_index_search gives that (query,
+ *                  row) pair and depend on the padded dim alone, not on refine, the candidate's rank, the number of queries of the
+ *                  call or the split among workgroups.  Order: score descending, ties by id ascending.  count = min(top_m,
+ *                  cand_count); entries past count are not written.  With refine >= the number of eligible rows, id_out, score_out
+ *                  and count_out equal bn_index_search's (bn_index_search_ids') bytes.
+ *   Limits         1 <= top_m <= refine <= 256 and m_stride >= top_m.  256 is the widest list the selection keeps.
+ *   Extend         rows appended after the build are not searched until bn_sq8_extend: before it every call behaves as if the
+ *                  index ended at bn_sq8_rows.  bn_sq8_extend encodes ids [bn_sq8_rows, bn_index_size); after it codes, scales and
+ *                  every search result are byte-identical to a fresh bn_sq8_build.
+ *   Refusals       BN_ERR_INVALID_ARG with a message, no output written and nothing changed: NULL where data is required (the
+ *                  index, the view, out, queries / query_ids, id_out, score_out, count_out), dim > 131072, refine outside 1..256,
+ *                  top_m outside 1..refine, m_stride < top_m, a query id >= bn_sq8_rows, first + count > bn_sq8_rows.
+ *   Empty cases    an empty index builds a view of no rows; its searches return count 0 and cand_count 0.
+ *   No device      without a gfx950 device every call that needs one (all but bn_sq8_free and bn_sq8_rows) returns
+ *                  BN_ERR_NO_DEVICE and leaves the outputs untouched; a NULL out / queries / query_ids / id_out / score_out /
+ *                  count_out, refine outside 1..256, top_m outside 1..refine and m_stride < top_m are refused before the device is
+ *                  asked for.
+ *   Determinism    no floating-point atomics; two calls with the same inputs give the same bytes; one call with Q queries gives
+ *                  the same bytes as Q calls with one query each.
+ *   Threading      the index's rule, the view included: one thread at a time per index.  The view BORROWS the index: free it
+ *                  before the index.  All work runs on the index's stream, after a pending bn_index_add_ctx.
+ *   Memory         the view owns one byte per slab element (rows of the index's capacity rounded up to 64 x dim rounded up to
+ *                  128), 4 bytes per such row of scales, the codes of a round of 1024 queries, and the candidate buffers: 2 KB per
+ *                  (query of a pass of 64, scan workgroup) with two workgroups per compute unit -- 64 MB at 256 compute units --
+ *                  plus 3 KB per query of a round.
+ *   Persistence    none.  The plane is a deterministic function of the stored bits: bn_sq8_build after bn_index_load reproduces
+ *                  it to the byte.
+ *
+ * Outputs are host arrays: id_out / score_out [n_queries * m_stride] and count_out [n_queries] as for bn_index_search; cand_out
+ * (u64) [n_queries * refine] and cand_count_out (u32) [n_queries] may be NULL.  bn_sq8_read copies codes [count * dim] (no padding)
+ * and scales [count] of rows [first, first + count); either output may be NULL.  All calls are synchronous.  The index is unchanged.
+ */
+typedef struct bn_sq8 bn_sq8;
+bn_status bn_sq8_build(bn_index *x, bn_sq8 **out);
+void bn_sq8_free(bn_sq8 *v);
+size_t bn_sq8_rows(const bn_sq8 *v); /* the covered rows: ids [0, bn_sq8_rows) */
+bn_status bn_sq8_extend(bn_sq8 *v);
+bn_status bn_sq8_read(const bn_sq8 *v, uint64_t first, size_t count, int8_t *codes_out, float *scales_out);
+bn_status bn_sq8_search(bn_sq8 *v, const float *queries, size_t n_queries, size_t refine, size_t top_m, size_t m_stride,
+                        uint64_t *id_out, float *score_out, uint32_t *count_out, uint64_t *cand_out, uint32_t *cand_count_out);
+bn_status bn_sq8_search_ids(bn_sq8 *v, const uint64_t *query_ids, size_t n_queries, int64_t exclude_radius, size_t refine,
+                            size_t top_m, size_t m_stride, uint64_t *id_out, float *score_out, uint32_t *count_out,
+                            uint64_t *cand_out, uint32_t *cand_count_out);
+
+/*
  * Persistence of an index: bn_index_save writes the slab's STORED BITS to a file, bn_index_load makes an index from one.  A loaded
  * index behaves in every call exactly as the saved one did at the time of the save: searches, head fits and ranks, assignment,
  * clustering and IVF views are all stated in the bits of the stored rows, and those are what the file holds.  bn_index_read

@@ -57,6 +57,7 @@ ENGINE_SYMBOLS = [
     "bn_index_save", "bn_index_load", "bn_index_file_info", "bn_index_file_verify",
     "bn_ivf_build", "bn_ivf_free", "bn_ivf_lists", "bn_ivf_rows", "bn_ivf_extend", "bn_ivf_list_sizes", "bn_ivf_read_list", "bn_ivf_search",
     "bn_ivf_search_ids",
+    "bn_sq8_build", "bn_sq8_free", "bn_sq8_rows", "bn_sq8_extend", "bn_sq8_read", "bn_sq8_search", "bn_sq8_search_ids",
     "bn_head_create", "bn_head_free", "bn_head_dim", "bn_head_classes", "bn_head_flags", "bn_head_read", "bn_head_apply_host",
     "bn_head_fit", "bn_head_fit_index", "bn_head_rank_index", "bn_ctx_attach_head", "bn_step_head_results",
     "bn_prior_create", "bn_prior_free", "bn_prior_sites", "bn_prior_species", "bn_prior_threshold", "bn_prior_flags", "bn_prior_read",
@@ -247,6 +248,13 @@ def _load() -> C.CDLL:
         "bn_ivf_read_list": (i32, [vp, sz, C.POINTER(C.c_uint64), sz, C.POINTER(sz)]),
         "bn_ivf_search": (i32, [vp, f32p, sz, sz, sz, sz, C.POINTER(C.c_uint64), f32p, u32p, u32p, C.POINTER(C.c_uint64)]),
         "bn_ivf_search_ids": (i32, [vp, C.POINTER(C.c_uint64), sz, C.c_int64, sz, sz, sz, C.POINTER(C.c_uint64), f32p, u32p, u32p, C.POINTER(C.c_uint64)]),
+        "bn_sq8_build": (i32, [vp, C.POINTER(vp)]),
+        "bn_sq8_free": (None, [vp]),
+        "bn_sq8_rows": (sz, [vp]),
+        "bn_sq8_extend": (i32, [vp]),
+        "bn_sq8_read": (i32, [vp, C.c_uint64, sz, C.POINTER(C.c_int8), f32p]),
+        "bn_sq8_search": (i32, [vp, f32p, sz, sz, sz, sz, C.POINTER(C.c_uint64), f32p, u32p, C.POINTER(C.c_uint64), u32p]),
+        "bn_sq8_search_ids": (i32, [vp, C.POINTER(C.c_uint64), sz, C.c_int64, sz, sz, sz, C.POINTER(C.c_uint64), f32p, u32p, C.POINTER(C.c_uint64), u32p]),
         "bn_head_create": (i32, [i32, sz, sz, f32p, f32p, C.c_uint32, C.POINTER(vp)]),
         "bn_head_free": (None, [vp]),
         "bn_head_dim": (sz, [vp]),
@@ -1420,6 +1428,79 @@ class Ivf:
         if st:
             raise EngineError(st)
         return out_ids, scores, counts, probes, scanned
+
+
+class Sq8:
+    """bn_sq8: an int8 view of an Index: one code byte per element and one f32 scale per row.  search / search_ids rank every covered
+    row by an exact integer key, keep the `refine` best as candidates and re-score those exactly; they return (ids [n, top_m] uint64,
+    scores [n, top_m] float32, counts [n] uint32, cands [n, refine] uint64, cand_counts [n] uint32): what Index.search would return if
+    only the candidates existed.  Rows appended to the index are searched after extend().  The view keeps the Index alive."""
+
+    def __init__(self, index: "Index"):
+        h = C.c_void_p()
+        st = lib.bn_sq8_build(index._h, C.byref(h))
+        if st:
+            raise EngineError(st)
+        self._h, self.index = h, index
+
+    def __del__(self):
+        if getattr(self, "_h", None) and lib is not None:
+            lib.bn_sq8_free(self._h)
+            self._h = None
+
+    def close(self):
+        self.__del__()
+
+    @property
+    def rows(self) -> int:
+        """the covered rows: ids [0, rows)"""
+        return int(lib.bn_sq8_rows(self._h))
+
+    def extend(self) -> None:
+        st = lib.bn_sq8_extend(self._h)
+        if st:
+            raise EngineError(st)
+
+    def read(self, first: int = 0, count: Optional[int] = None):
+        """(codes [count, dim] int8, scales [count] float32) of rows [first, first + count); count None: to the last covered row"""
+        count = max(self.rows - first, 0) if count is None else count
+        codes = np.zeros((max(count, 0), self.index.dim), dtype=np.int8)
+        scales = np.zeros(max(count, 0), dtype=np.float32)
+        st = lib.bn_sq8_read(self._h, first, count, codes.ctypes.data_as(C.POINTER(C.c_int8)), scales.ctypes.data_as(C.POINTER(C.c_float)))
+        if st:
+            raise EngineError(st)
+        return codes, scales
+
+    @staticmethod
+    def _outputs(n: int, m_stride: int, refine: int):
+        return Index._outputs(n, m_stride) + (np.zeros((n, max(refine, 0)), dtype=np.uint64), np.zeros(n, dtype=np.uint32))
+
+    def search(self, queries, refine: int, top_m: int, m_stride: Optional[int] = None):
+        """Top-M rows by cosine among the `refine` coarse candidates of each host query [n, dim]."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.index.dim)
+        m_stride = top_m if m_stride is None else m_stride
+        ids, scores, counts, cands, cand_counts = self._outputs(q.shape[0], max(m_stride, 0), refine)
+        st = lib.bn_sq8_search(self._h, q.ctypes.data_as(C.POINTER(C.c_float)), q.shape[0], refine, top_m, m_stride,
+                               ids.ctypes.data_as(C.POINTER(C.c_uint64)), scores.ctypes.data_as(C.POINTER(C.c_float)),
+                               counts.ctypes.data_as(C.POINTER(C.c_uint32)), cands.ctypes.data_as(C.POINTER(C.c_uint64)),
+                               cand_counts.ctypes.data_as(C.POINTER(C.c_uint32)))
+        if st:
+            raise EngineError(st)
+        return ids, scores, counts, cands, cand_counts
+
+    def search_ids(self, ids, refine: int, top_m: int, exclude_radius: int = -1, m_stride: Optional[int] = None):
+        """Query by example among the `refine` coarse candidates of each stored row `ids`; rows within exclude_radius of a query's id
+        are neither candidates nor results."""
+        qi = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+        m_stride = top_m if m_stride is None else m_stride
+        out_ids, scores, counts, cands, cand_counts = self._outputs(qi.shape[0], max(m_stride, 0), refine)
+        st = lib.bn_sq8_search_ids(self._h, qi.ctypes.data_as(C.POINTER(C.c_uint64)), qi.shape[0], exclude_radius, refine, top_m, m_stride,
+                                   out_ids.ctypes.data_as(C.POINTER(C.c_uint64)), scores.ctypes.data_as(C.POINTER(C.c_float)),
+                                   counts.ctypes.data_as(C.POINTER(C.c_uint32)), cands.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                   cand_counts.ctypes.data_as(C.POINTER(C.c_uint32)))
+        if st:
+            raise EngineError(st)
+        return out_ids, scores, counts, cands, cand_counts
 
 
 def _fit_opts(n_classes: int, l2: float, tol: float, max_iters: int, l2norm: bool, pos_weight):

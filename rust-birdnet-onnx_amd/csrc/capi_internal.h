@@ -185,11 +185,27 @@ struct IndexScan {
     uint32_t *d_count = nullptr, *h_count = nullptr;
 };
 bn_status index_scan_state(bn_index *x, IndexScan *out);
-// index.hip -> ivf.hip (bn_ivf_search, bn_ivf_search_ids): up to out_lists queries made ready in the index's own query buffers, on
+// index.hip -> ivf.hip, sq8.hip (bn_ivf_search, bn_sq8_search and their _ids forms): up to out_lists queries made ready in the index's own query buffers, on
 // its stream, exactly as bn_index_search / bn_index_search_ids prepare theirs: host rows normalised, or stored rows gathered by id
 // (ids below bn_index_size).  *d_q [n, dpad], *d_qvalid [n], *d_qid [n] (ids only) stay the index's
 bn_status index_stage_queries(bn_index *x, const float *queries, size_t n, const float **d_q, const uint8_t **d_qvalid);
 bn_status index_stage_query_ids(bn_index *x, const uint64_t *ids, size_t n, const float **d_q, const uint8_t **d_qvalid, const uint32_t **d_qid);
+// ivf.hip -> sq8.hip (bn_sq8_search's re-rank): the gathered scan and the multi-wave merge, enqueued on `stream`.  The scan runs
+// n_queries x nprobe x segments units; unit (q, p, seg) scans tiles [seg * seg_tiles, + seg_tiles) of the list probes[q * nprobe + p]
+// (members[offsets[c] .. + counts[c]), ids of stored rows; BN_CLUSTER_NONE: no list) for query row q of `q`, with bn_index_search's
+// score bits, into cand[unit][256] (sorted, first M kept) and cand_len[unit].  The merge gives query q the first M of its `units`
+// consecutive sorted lists: out[q][M], count[q].  Every pointer is device memory
+struct IvfGather {
+    const float *slab = nullptr, *q = nullptr;  // [.., dpad]
+    uint32_t dpad = 0;
+    const uint32_t *qid = nullptr;  // with radius >= 0: rows within radius of qid[q] are left out
+    int64_t radius = -1;
+    const uint32_t *probes = nullptr, *counts = nullptr, *offsets = nullptr, *members = nullptr;
+    uint32_t nprobe = 1, seg_tiles = 1, segments = 1;
+};
+bn_status ivf_enqueue_scan(hipStream_t stream, const IvfGather &g, size_t n_queries, int M, topm::Cand *cand, int *cand_len);
+bn_status ivf_enqueue_merge(hipStream_t stream, const topm::Cand *cand, const int *cand_len, size_t n_queries, size_t units, int M, topm::Cand *out,
+                            uint32_t *count);
 // index.hip <-> index_io.hip (bn_index_save, bn_index_load): the slab itself.  index_io_state makes the device current and orders the
 // index's stream after a pending bn_index_add_ctx, without waiting.  index_adopt_rows ends a load: rows [0, n) of an EMPTY index
 // (n <= its capacity) were written, with their valid bytes and zeroed pad columns, by work that has completed

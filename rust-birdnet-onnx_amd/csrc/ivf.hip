@@ -19,6 +19,7 @@
 //   * ivf_merge_kernel -- one workgroup of 8 waves per query.  Wave w walks units w, w + 8, .. (unit order = probe order, so the
 //     best list comes first and the threshold rejects early), the next list's head loaded while the current one is taken; then
 //     wave 0 takes the other waves' lists the same way.  The order is strict and total, so the result does not depend on the split.
+// ivf_scan_kernel and ivf_merge_kernel are also sq8.hip's re-rank and merges, through ivf_enqueue_scan / ivf_enqueue_merge (capi_internal.h).
 // LDS: the scan takes 4.3 KB (two 128-float query chunks, 64 scores, 128 pending and 256 scratch candidates), the merge 40 KB.
 #include <hip/hip_runtime.h>
 
@@ -371,6 +372,22 @@ bn_status cover(bn_ivf *v, const bn::IndexScan &s, size_t from) {
     return BN_OK;
 }
 
+}  // namespace
+
+bn_status bn::ivf_enqueue_scan(hipStream_t stream, const IvfGather &g, size_t n_queries, int M, topm::Cand *cand, int *cand_len) {
+    hipLaunchKernelGGL(ivf_scan_kernel, dim3(g.segments, g.nprobe, (unsigned)n_queries), dim3(256), 0, stream, g.slab, g.dpad, g.q, g.qid, g.radius, M, g.probes,
+                       g.nprobe, g.counts, g.offsets, g.members, g.seg_tiles, cand, cand_len);
+    return check_launch("ivf scan");
+}
+
+bn_status bn::ivf_enqueue_merge(hipStream_t stream, const topm::Cand *cand, const int *cand_len, size_t n_queries, size_t units, int M, topm::Cand *out,
+                                uint32_t *count) {
+    hipLaunchKernelGGL(ivf_merge_kernel, dim3((unsigned)n_queries), dim3(64 * MERGE_WAVES), 0, stream, cand, cand_len, (int)units, M, out, count);
+    return check_launch("ivf merge");
+}
+
+namespace {
+
 bn_status check_search_args(size_t n_queries, size_t top_m, size_t m_stride, const void *queries, const uint64_t *id_out, const float *score_out,
                             const uint32_t *count_out) {
     if (top_m < 1 || top_m > (size_t)MMAX) return set_last_error(BN_ERR_INVALID_ARG, "top_m must be in 1..256, got " + std::to_string(top_m));
@@ -401,13 +418,21 @@ bn_status run_search(bn_ivf *v, const bn::IndexScan &s, size_t nq, const float *
     const size_t q_pass = UNIT_MAX / per_query;
     for (size_t p0 = 0; p0 < nq; p0 += q_pass) {
         const size_t n = std::min(q_pass, nq - p0);
-        hipLaunchKernelGGL(ivf_scan_kernel, dim3(segments, np32, (unsigned)n), dim3(256), 0, s.stream, s.slab, dpad, d_q + p0 * v->dpad,
-                           d_qid ? d_qid + p0 : nullptr, d_qid ? radius : (int64_t)-1, M, v->d_probes + p0 * nprobe, np32, d_counts, d_offsets, v->d_members,
-                           (uint32_t)seg_tiles, v->d_cand, v->d_cand_len);
-        if ((st = check_launch("ivf scan")) != BN_OK) return st;
-        hipLaunchKernelGGL(ivf_merge_kernel, dim3((unsigned)n), dim3(64 * MERGE_WAVES), 0, s.stream, v->d_cand, v->d_cand_len, (int)per_query, M,
-                           s.d_out + p0 * M, s.d_count + p0);
-        if ((st = check_launch("ivf merge")) != BN_OK) return st;
+        bn::IvfGather g;
+        g.slab = s.slab;
+        g.dpad = dpad;
+        g.q = d_q + p0 * v->dpad;
+        g.qid = d_qid ? d_qid + p0 : nullptr;
+        g.radius = d_qid ? radius : (int64_t)-1;
+        g.probes = v->d_probes + p0 * nprobe;
+        g.nprobe = np32;
+        g.counts = d_counts;
+        g.offsets = d_offsets;
+        g.members = v->d_members;
+        g.seg_tiles = (uint32_t)seg_tiles;
+        g.segments = segments;
+        if ((st = bn::ivf_enqueue_scan(s.stream, g, n, M, v->d_cand, v->d_cand_len)) != BN_OK) return st;
+        if ((st = bn::ivf_enqueue_merge(s.stream, v->d_cand, v->d_cand_len, n, per_query, M, s.d_out + p0 * M, s.d_count + p0)) != BN_OK) return st;
     }
     BN_HIP_TRY(hipMemcpyAsync(s.h_out, s.d_out, nq * M * sizeof(Cand), hipMemcpyDeviceToHost, s.stream));
     BN_HIP_TRY(hipMemcpyAsync(s.h_count, s.d_count, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, s.stream));
