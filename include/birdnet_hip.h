@@ -448,6 +448,21 @@ bn_status bn_index_search(bn_index *x, const float *queries, size_t n_queries, s
  * windows the neighbours are near-duplicates).  A query id >= bn_index_size is BN_ERR_INVALID_ARG. */
 bn_status bn_index_search_ids(bn_index *x, const uint64_t *query_ids, size_t n_queries, int64_t exclude_radius,
                               size_t top_m, size_t m_stride, uint64_t *id_out, float *score_out, uint32_t *count_out);
+/* Row tags: every row carries one tag below BN_INDEX_TAG_LIMIT, 0 until set: a source, a site, a species, a tombstone -- the caller's
+ * meaning.  bn_subset_select (below) chooses rows by tag; NOTHING ELSE reads a tag: bn_index_search, bn_index_search_ids, bn_ivf_*,
+ * bn_sq8_*, bn_head_fit_index, bn_head_rank_index, bn_index_assign, bn_index_cluster and bn_index_save behave the same, bit for bit, with
+ * and without tags.  The plane (two bytes per row of capacity) is allocated by the first bn_index_set_tags / bn_index_fill_tags; an index
+ * that never tags pays nothing, and an absent plane reads as zeros.  The index file has no tags: it stays format version 1 and a loaded
+ * index has every tag 0; carry tags alongside a file with bn_index_read_tags before the save and bn_index_set_tags after the load.
+ * bn_index_set_tags gives rows [first_id, first_id + n) the host values tags[0 .. n), bn_index_fill_tags gives them all one tag (the
+ * batch bn_index_add_ctx just appended: its first_id and batch_size), bn_index_read_tags copies the tags of rows [first, first + count)
+ * to host.  The rows must lie in [0, bn_index_size) and every tag must be below the limit, otherwise BN_ERR_INVALID_ARG with a message
+ * and no tag changed (the whole array is checked before any write).  The calls run on the index's stream, after a pending
+ * bn_index_add_ctx, and are synchronous. */
+#define BN_INDEX_TAG_LIMIT 65536u
+bn_status bn_index_set_tags(bn_index *x, uint64_t first_id, size_t n, const uint32_t *tags);
+bn_status bn_index_fill_tags(bn_index *x, uint64_t first_id, size_t n, uint32_t tag);
+bn_status bn_index_read_tags(const bn_index *x, uint64_t first, size_t count, uint32_t *tags_out);
 
 /*
  * Classifier heads: an immutable linear head z[c] = sum_k W[c][k] * x[k] + b[c] over a model's embedding, resident on one
@@ -777,6 +792,72 @@ bn_status bn_sq8_search(bn_sq8 *v, const float *queries, size_t n_queries, size_
 bn_status bn_sq8_search_ids(bn_sq8 *v, const uint64_t *query_ids, size_t n_queries, int64_t exclude_radius, size_t refine,
                             size_t top_m, size_t m_stride, uint64_t *id_out, float *score_out, uint32_t *count_out,
                             uint64_t *cand_out, uint32_t *cand_count_out);
+
+/*
+ * Filtered search: a bn_subset is a device-resident list of row ids of one index, strictly ascending, and a search over it reads only
+ * those rows, once for all queries of a pass.  The index's rule holds as a precise statement: A bn_subset SEARCH RETURNS EXACTLY WHAT
+ * bn_index_search / bn_index_search_ids WOULD RETURN IF ONLY THE SUBSET'S ROWS EXISTED, with the same score bits, order and tie rule.
+ * The reference has nothing of the kind; this comment is the contract.
+ *
+ *   Members        bn_subset_select: a row is a member exactly when its id lies in [first_id, first_id + n_ids) (n_ids == 0: to the
+ *                  end of the index, bn_index_assign's convention) and its tag passes the list: with tags == NULL or n_tags == 0
+ *                  tags are not tested; otherwise the tag must be in the list (duplicates allowed), or, under
+ *                  BN_FILTER_EXCLUDE_TAGS, must not be.  bn_subset_from_ids: the given ids, which must be strictly ascending and
+ *                  below bn_index_size.  Validity is NOT tested: a row stored as zeros may be a member; like everywhere else it is
+ *                  never returned.  bn_subset_size is the number of members, bn_subset_read copies members [first, first + count)
+ *                  of the ascending list.
+ *   Fixed          the list is made once.  Rows appended later and tags changed later do not alter it; its searches before and
+ *                  after such calls return the same bytes.
+ *   Result         the score of a (query, member) pair has the bits bn_index_search gives that pair: the same k-ordered chain over
+ *                  the padded dim, whatever the subset, the member's position in it, the number of queries of the call or the split
+ *                  among workgroups.  Order: score descending, ties by id ascending (-0.0 == +0.0).  count = min(top_m, valid
+ *                  members not excluded); entries past count are not written.  The subset of all rows returns bn_index_search's
+ *                  (bn_index_search_ids') bytes.
+ *   Query          bn_index_search's rules: a host query is normalised as an appended row is, and one with zero norm or a non-finite
+ *                  element returns count 0.  bn_subset_search_ids takes stored rows as queries: query_ids name ANY stored row of the
+ *                  index, in or out of the subset (the index's current size bounds them), and members whose id lies within
+ *                  exclude_radius of the query's own id are skipped (< 0: none; 0: the row itself).
+ *   Limits         1 <= top_m <= 256 and m_stride >= top_m.
+ *   Refusals       BN_ERR_INVALID_ARG with a message, no output written and nothing created: NULL where data is required (the index,
+ *                  the filter, ids, out, the subset, queries / query_ids, id_out, score_out, count_out), a struct_size smaller than
+ *                  bn_index_filter, an id range that does not lie in [0, bn_index_size], a listed tag >= BN_INDEX_TAG_LIMIT, flags
+ *                  other than BN_FILTER_EXCLUDE_TAGS, ids that are not strictly ascending or reach bn_index_size, top_m outside
+ *                  1..256, m_stride < top_m, a query id >= bn_index_size, first + count > bn_subset_size.
+ *   Empty cases    an empty subset is legal (an empty range, a tag nobody has, n == 0); its searches return count 0 without a launch.
+ *   No device      without a gfx950 device every call that needs one (all but bn_subset_free and bn_subset_size) returns
+ *                  BN_ERR_NO_DEVICE and leaves the outputs untouched; the refusals that need neither the index nor the subset (a NULL
+ *                  filter / out / queries / query_ids / id_out / score_out / count_out, struct_size, flags, a listed tag, ids out of
+ *                  order, top_m, m_stride) come before the device is asked for.
+ *   Determinism    no atomic decides a position and no floating-point atomics: two selections of the same state give the same
+ *                  bytes; two searches with the same inputs give the same bytes; one call with Q queries gives the same bytes as Q
+ *                  calls with one query each.
+ *   Threading      the index's rule, its views included: one thread at a time per index.  The subset BORROWS the index: free it
+ *                  before the index.  All work runs on the index's stream, after a pending bn_index_add_ctx; every call is
+ *                  synchronous.
+ *   Memory         four bytes per member.  A search uses the index's own query and candidate buffers.
+ *   Persistence    none: bn_subset_read / bn_subset_from_ids carry a list across processes.
+ *
+ * struct_size is sizeof(bn_index_filter) as the caller compiled it.  Outputs are host arrays: id_out / score_out
+ * [n_queries * m_stride] and count_out [n_queries] as for bn_index_search.  The index is unchanged by every call.
+ */
+typedef struct bn_subset bn_subset;
+typedef struct bn_index_filter {
+    uint64_t first_id;    /* the id range [first_id, first_id + n_ids) */
+    uint64_t n_ids;       /* 0: to the end of the index */
+    const uint32_t *tags; /* host list of tag values, duplicates allowed; NULL or n_tags == 0: tags are not tested */
+    size_t n_tags;
+    uint32_t flags; /* 0, or BN_FILTER_EXCLUDE_TAGS: the list names the tags left OUT */
+} bn_index_filter;
+#define BN_FILTER_EXCLUDE_TAGS 1u
+bn_status bn_subset_select(bn_index *x, const bn_index_filter *f, size_t struct_size, bn_subset **out);
+bn_status bn_subset_from_ids(bn_index *x, const uint64_t *ids, size_t n, bn_subset **out);
+void bn_subset_free(bn_subset *s);
+size_t bn_subset_size(const bn_subset *s);
+bn_status bn_subset_read(const bn_subset *s, size_t first, size_t count, uint64_t *ids_out);
+bn_status bn_subset_search(bn_subset *s, const float *queries, size_t n_queries, size_t top_m, size_t m_stride, uint64_t *id_out,
+                           float *score_out, uint32_t *count_out);
+bn_status bn_subset_search_ids(bn_subset *s, const uint64_t *query_ids, size_t n_queries, int64_t exclude_radius, size_t top_m,
+                               size_t m_stride, uint64_t *id_out, float *score_out, uint32_t *count_out);
 
 /*
  * Persistence of an index: bn_index_save writes the slab's STORED BITS to a file, bn_index_load makes an index from one.  A loaded

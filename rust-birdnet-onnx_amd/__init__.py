@@ -58,6 +58,8 @@ ENGINE_SYMBOLS = [
     "bn_ivf_build", "bn_ivf_free", "bn_ivf_lists", "bn_ivf_rows", "bn_ivf_extend", "bn_ivf_list_sizes", "bn_ivf_read_list", "bn_ivf_search",
     "bn_ivf_search_ids",
     "bn_sq8_build", "bn_sq8_free", "bn_sq8_rows", "bn_sq8_extend", "bn_sq8_read", "bn_sq8_search", "bn_sq8_search_ids",
+    "bn_index_set_tags", "bn_index_fill_tags", "bn_index_read_tags",
+    "bn_subset_select", "bn_subset_from_ids", "bn_subset_free", "bn_subset_size", "bn_subset_read", "bn_subset_search", "bn_subset_search_ids",
     "bn_head_create", "bn_head_free", "bn_head_dim", "bn_head_classes", "bn_head_flags", "bn_head_read", "bn_head_apply_host",
     "bn_head_fit", "bn_head_fit_index", "bn_head_rank_index", "bn_ctx_attach_head", "bn_step_head_results",
     "bn_prior_create", "bn_prior_free", "bn_prior_sites", "bn_prior_species", "bn_prior_threshold", "bn_prior_flags", "bn_prior_read",
@@ -134,6 +136,12 @@ class BnIndexFileInfo(C.Structure):
                 ("version", C.c_uint32)]
 
 
+class BnIndexFilter(C.Structure):
+    _fields_ = [("first_id", C.c_uint64), ("n_ids", C.c_uint64), ("tags", C.POINTER(C.c_uint32)), ("n_tags", C.c_size_t), ("flags", C.c_uint32)]
+
+
+BN_INDEX_TAG_LIMIT = 65536  # row tags lie below it
+BN_FILTER_EXCLUDE_TAGS = 1  # bn_index_filter flag: the tag list names the tags left out
 BN_CLUSTER_NONE = 0xFFFFFFFF  # the assignment of a row that belongs to no cluster
 BN_HEAD_L2NORM = 1
 BN_RANK_TOP, BN_RANK_UNCERTAIN = 0, 1
@@ -255,6 +263,16 @@ def _load() -> C.CDLL:
         "bn_sq8_read": (i32, [vp, C.c_uint64, sz, C.POINTER(C.c_int8), f32p]),
         "bn_sq8_search": (i32, [vp, f32p, sz, sz, sz, sz, C.POINTER(C.c_uint64), f32p, u32p, C.POINTER(C.c_uint64), u32p]),
         "bn_sq8_search_ids": (i32, [vp, C.POINTER(C.c_uint64), sz, C.c_int64, sz, sz, sz, C.POINTER(C.c_uint64), f32p, u32p, C.POINTER(C.c_uint64), u32p]),
+        "bn_index_set_tags": (i32, [vp, C.c_uint64, sz, u32p]),
+        "bn_index_fill_tags": (i32, [vp, C.c_uint64, sz, C.c_uint32]),
+        "bn_index_read_tags": (i32, [vp, C.c_uint64, sz, u32p]),
+        "bn_subset_select": (i32, [vp, C.POINTER(BnIndexFilter), sz, C.POINTER(vp)]),
+        "bn_subset_from_ids": (i32, [vp, C.POINTER(C.c_uint64), sz, C.POINTER(vp)]),
+        "bn_subset_free": (None, [vp]),
+        "bn_subset_size": (sz, [vp]),
+        "bn_subset_read": (i32, [vp, sz, sz, C.POINTER(C.c_uint64)]),
+        "bn_subset_search": (i32, [vp, f32p, sz, sz, sz, C.POINTER(C.c_uint64), f32p, u32p]),
+        "bn_subset_search_ids": (i32, [vp, C.POINTER(C.c_uint64), sz, C.c_int64, sz, sz, C.POINTER(C.c_uint64), f32p, u32p]),
         "bn_head_create": (i32, [i32, sz, sz, f32p, f32p, C.c_uint32, C.POINTER(vp)]),
         "bn_head_free": (None, [vp]),
         "bn_head_dim": (sz, [vp]),
@@ -1261,6 +1279,28 @@ class Index:
             raise EngineError(st)
         return out_ids, scores, counts
 
+    def set_tags(self, first_id: int, tags) -> None:
+        """bn_index_set_tags: rows [first_id, first_id + len(tags)) get the tags given (each below BN_INDEX_TAG_LIMIT)."""
+        t = np.ascontiguousarray(tags, dtype=np.uint32).reshape(-1)
+        st = lib.bn_index_set_tags(self._h, first_id, t.shape[0], t.ctypes.data_as(C.POINTER(C.c_uint32)))
+        if st:
+            raise EngineError(st)
+
+    def fill_tags(self, first_id: int, n: int, tag: int) -> None:
+        """bn_index_fill_tags: rows [first_id, first_id + n) all get `tag`, e.g. the batch add_context just appended."""
+        st = lib.bn_index_fill_tags(self._h, first_id, n, tag)
+        if st:
+            raise EngineError(st)
+
+    def tags(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """bn_index_read_tags: the tags of rows [first, first + count) as uint32; count None: to the last row.  A row never tagged has 0."""
+        count = max(len(self) - first, 0) if count is None else count
+        out = np.zeros(max(count, 0), dtype=np.uint32)
+        st = lib.bn_index_read_tags(self._h, first, count, out.ctypes.data_as(C.POINTER(C.c_uint32)))
+        if st:
+            raise EngineError(st)
+        return out
+
     def save(self, path, chunk_rows: int = 0) -> None:
         """bn_index_save: the stored bits of every row to `path` (written under a temporary name, renamed when complete); chunk_rows
         0 takes the default.  Index.load(path) gives an index that answers every call as this one does now."""
@@ -1501,6 +1541,84 @@ class Sq8:
         if st:
             raise EngineError(st)
         return out_ids, scores, counts, cands, cand_counts
+
+
+class Subset:
+    """bn_subset: a fixed, ascending list of row ids of an Index.  search / search_ids return (ids [n, top_m] uint64, scores [n, top_m]
+    float32, counts [n] uint32): what Index.search / Index.search_ids would return if only the subset's rows existed, from one read of
+    those rows for all queries of a pass.  Rows appended and tags changed afterwards do not alter the list.  The subset keeps the Index
+    alive.  Make one with Subset.select or Subset.from_ids."""
+
+    def __init__(self, index: "Index", handle):
+        self._h, self.index = handle, index
+
+    @classmethod
+    def select(cls, index: "Index", first_id: int = 0, n_ids: int = 0, tags=None, exclude: bool = False) -> "Subset":
+        """bn_subset_select: the rows of [first_id, first_id + n_ids) (n_ids 0: to the end) whose tag is in `tags`, or, with exclude,
+        is not in it; tags None or empty: every row of the range."""
+        t = None if tags is None else np.ascontiguousarray(tags, dtype=np.uint32).reshape(-1)
+        f = BnIndexFilter(first_id, n_ids, None if t is None else t.ctypes.data_as(C.POINTER(C.c_uint32)), 0 if t is None else t.shape[0],
+                          BN_FILTER_EXCLUDE_TAGS if exclude else 0)
+        h = C.c_void_p()
+        st = lib.bn_subset_select(index._h, C.byref(f), C.sizeof(f), C.byref(h))
+        if st:
+            raise EngineError(st)
+        return cls(index, h)
+
+    @classmethod
+    def from_ids(cls, index: "Index", ids) -> "Subset":
+        """bn_subset_from_ids: the rows `ids`, strictly ascending."""
+        a = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+        h = C.c_void_p()
+        st = lib.bn_subset_from_ids(index._h, a.ctypes.data_as(C.POINTER(C.c_uint64)), a.shape[0], C.byref(h))
+        if st:
+            raise EngineError(st)
+        return cls(index, h)
+
+    def __del__(self):
+        if getattr(self, "_h", None) and lib is not None:
+            lib.bn_subset_free(self._h)
+            self._h = None
+
+    def close(self):
+        self.__del__()
+
+    def __len__(self) -> int:
+        return int(lib.bn_subset_size(self._h))
+
+    @property
+    def ids(self) -> np.ndarray:
+        """the members, ascending, as uint64"""
+        out = np.zeros(len(self), dtype=np.uint64)
+        st = lib.bn_subset_read(self._h, 0, out.shape[0], out.ctypes.data_as(C.POINTER(C.c_uint64)))
+        if st:
+            raise EngineError(st)
+        return out
+
+    def search(self, queries, top_m: int, m_stride: Optional[int] = None):
+        """Top-M members by cosine for host queries [n, dim]."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.index.dim)
+        m_stride = top_m if m_stride is None else m_stride
+        ids, scores, counts = Index._outputs(q.shape[0], max(m_stride, 0))
+        st = lib.bn_subset_search(self._h, q.ctypes.data_as(C.POINTER(C.c_float)), q.shape[0], top_m, m_stride,
+                                  ids.ctypes.data_as(C.POINTER(C.c_uint64)), scores.ctypes.data_as(C.POINTER(C.c_float)),
+                                  counts.ctypes.data_as(C.POINTER(C.c_uint32)))
+        if st:
+            raise EngineError(st)
+        return ids, scores, counts
+
+    def search_ids(self, ids, top_m: int, exclude_radius: int = -1, m_stride: Optional[int] = None):
+        """Query by example: the stored rows `ids` of the index (members or not) are the queries; members within exclude_radius of a
+        query's id are skipped."""
+        qi = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+        m_stride = top_m if m_stride is None else m_stride
+        out_ids, scores, counts = Index._outputs(qi.shape[0], max(m_stride, 0))
+        st = lib.bn_subset_search_ids(self._h, qi.ctypes.data_as(C.POINTER(C.c_uint64)), qi.shape[0], exclude_radius, top_m, m_stride,
+                                      out_ids.ctypes.data_as(C.POINTER(C.c_uint64)), scores.ctypes.data_as(C.POINTER(C.c_float)),
+                                      counts.ctypes.data_as(C.POINTER(C.c_uint32)))
+        if st:
+            raise EngineError(st)
+        return out_ids, scores, counts
 
 
 def _fit_opts(n_classes: int, l2: float, tol: float, max_iters: int, l2norm: bool, pos_weight):

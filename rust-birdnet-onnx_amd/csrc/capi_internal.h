@@ -183,8 +183,13 @@ struct IndexScan {
     topm::Cand *d_cand = nullptr, *d_out = nullptr, *h_out = nullptr;
     int *d_cand_len = nullptr;
     uint32_t *d_count = nullptr, *h_count = nullptr;
+    const uint16_t *tags = nullptr;  // [cap_pad] row tags; NULL until a tag is first set: every tag is 0
 };
 bn_status index_scan_state(bn_index *x, IndexScan *out);
+// index.hip -> subset.hip (bn_subset_search): index_merge_kernel enqueued on `stream`: one wave per query walks the n_wg workgroups' sorted
+// lists cand[g][q][256] (lengths cand_len[g][q], IndexScan::lists lists per workgroup) into out[q][M], count[q]
+bn_status index_enqueue_merge(hipStream_t stream, const topm::Cand *cand, const int *cand_len, size_t n_queries, int n_wg, int M, topm::Cand *out,
+                              uint32_t *count);
 // index.hip -> ivf.hip, sq8.hip (bn_ivf_search, bn_sq8_search and their _ids forms): up to out_lists queries made ready in the index's own query buffers, on
 // its stream, exactly as bn_index_search / bn_index_search_ids prepare theirs: host rows normalised, or stored rows gathered by id
 // (ids below bn_index_size).  *d_q [n, dpad], *d_qvalid [n], *d_qid [n] (ids only) stay the index's

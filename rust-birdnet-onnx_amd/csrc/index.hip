@@ -16,7 +16,11 @@
 // Order everywhere: score descending, ties by id ascending (-0.0 == +0.0 through the float compare).  The candidate, the order and
 // the two merges live in topm_select.h, which rank.hip (bn_head_rank_index) shares; it also borrows this index's stream and
 // candidate buffers (index_scan_state).  cluster.hip (bn_index_assign, bn_index_cluster) borrows the stream and keeps its own
-// buffers on the index (index_cluster_state).
+// buffers on the index (index_cluster_state).  subset.hip (bn_subset_*) borrows the stream, the query staging, the candidate buffers and
+// index_merge_kernel (index_enqueue_merge), and reads the tag plane below.
+//
+// Row tags (bn_index_set_tags / fill_tags / read_tags): one u16 per row of capacity, allocated zeroed by the first call that sets one.
+// No kernel of this file reads it.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -266,6 +270,7 @@ struct bn_index {
     Cand *h_out = nullptr;  // pinned mirrors of d_out / d_count
     uint32_t *h_count = nullptr;
     bn::ClusterState *cluster = nullptr;  // cluster.hip's buffers, allocated by the first bn_index_assign / bn_index_cluster
+    uint16_t *tags = nullptr;  // [cap_pad], allocated by the first bn_index_set_tags / bn_index_fill_tags; absent: every tag is 0
 };
 
 namespace {
@@ -283,7 +288,7 @@ void release(bn_index *x) {
         (void)bn::gated::EventDestroy(x->ev);
     }
     for (void *p : {(void *)x->slab, (void *)x->valid, (void *)x->d_stage, (void *)x->d_q, (void *)x->d_qvalid, (void *)x->d_qid, (void *)x->d_cand,
-                    (void *)x->d_cand_len, (void *)x->d_out, (void *)x->d_count})
+                    (void *)x->d_cand_len, (void *)x->d_out, (void *)x->d_count, (void *)x->tags})
         if (p) (void)bn::gated::Free(p);
     bn::cluster_state_free(x->cluster);
     if (x->h_out) (void)bn::gated::HostFree(x->h_out);
@@ -373,6 +378,32 @@ bn_status stage_id_queries(bn_index *x, const uint64_t *query_ids, size_t nq) {
     return check_launch("index gather");
 }
 
+// the refusals of the tag calls that write; then the plane, zeroed, if this is the first of them
+bn_status prepare_tags(bn_index *x, uint64_t first_id, size_t n, const uint32_t *tags, size_t n_tags) {
+    if (!x) return set_last_error(BN_ERR_INVALID_ARG, "null index");
+    if (n && n_tags && !tags) return set_last_error(BN_ERR_INVALID_ARG, "null tags");
+    if (first_id > x->size || n > x->size - first_id)
+        return set_last_error(BN_ERR_INVALID_ARG, "rows [" + std::to_string(first_id) + ", +" + std::to_string(n) + ") are not in the index (" +
+                                                      std::to_string(x->size) + " rows)");
+    for (size_t i = 0; i < n_tags; i++)
+        if (tags[i] >= BN_INDEX_TAG_LIMIT)
+            return set_last_error(BN_ERR_INVALID_ARG, "tag " + std::to_string(tags[i]) + " is not below " + std::to_string(BN_INDEX_TAG_LIMIT));
+    if (!n) return BN_OK;
+    bn_status st = begin(x);
+    if (st != BN_OK) return st;
+    BN_HIP_TRY(hipStreamSynchronize(x->stream));
+    if (!x->tags) {
+        uint16_t *p = nullptr;
+        BN_HIP_TRY(bn::gated::Malloc(&p, x->cap_pad * sizeof(uint16_t)));
+        if (hipError_t e = bn::gated::Memset(p, 0, x->cap_pad * sizeof(uint16_t)); e != hipSuccess) {
+            (void)bn::gated::Free(p);
+            return set_last_error(BN_ERR_BACKEND, std::string("hipMemset of the tag plane failed: ") + hipGetErrorString(e));
+        }
+        x->tags = p;
+    }
+    return BN_OK;
+}
+
 bn_status reserve_rows(const bn_index *x, size_t n) {
     if (n > x->cap - x->size)
         return set_last_error(BN_ERR_INVALID_ARG, "append of " + std::to_string(n) + " rows exceeds the index capacity (" + std::to_string(x->size) + " of " +
@@ -440,7 +471,14 @@ bn_status bn::index_scan_state(bn_index *x, IndexScan *out) {
     out->d_count = x->d_count;
     out->h_out = x->h_out;
     out->h_count = x->h_count;
+    out->tags = x->tags;
     return BN_OK;
+}
+
+bn_status bn::index_enqueue_merge(hipStream_t stream, const topm::Cand *cand, const int *cand_len, size_t n_queries, int n_wg, int M, topm::Cand *out,
+                                  uint32_t *count) {
+    hipLaunchKernelGGL(index_merge_kernel, dim3((unsigned)n_queries), dim3(64), 0, stream, cand, cand_len, n_wg, M, out, count);
+    return check_launch("index merge");
 }
 
 bn_status bn::index_io_state(bn_index *x, IndexIo *out) {
@@ -572,6 +610,40 @@ bn_status bn_index_read(const bn_index *x, uint64_t first, size_t count, float *
         BN_HIP_TRY(bn::gated::Memcpy(tmp.data(), x->slab + (first + r0) * x->dpad, k * x->dpad * sizeof(float), hipMemcpyDeviceToHost));
         for (size_t i = 0; i < k; i++) memcpy(host_out + (r0 + i) * x->dim, tmp.data() + i * x->dpad, x->dim * sizeof(float));
     }
+    return BN_OK;
+}
+
+bn_status bn_index_set_tags(bn_index *x, uint64_t first_id, size_t n, const uint32_t *tags) {
+    bn_status st = prepare_tags(x, first_id, n, tags, n);
+    if (st != BN_OK || !n) return st;
+    const std::vector<uint16_t> t(tags, tags + n);
+    BN_HIP_TRY(bn::gated::Memcpy(x->tags + first_id, t.data(), n * sizeof(uint16_t), hipMemcpyHostToDevice));
+    return BN_OK;
+}
+
+bn_status bn_index_fill_tags(bn_index *x, uint64_t first_id, size_t n, uint32_t tag) {
+    bn_status st = prepare_tags(x, first_id, n, &tag, 1);
+    if (st != BN_OK || !n) return st;
+    const std::vector<uint16_t> t(n, (uint16_t)tag);
+    BN_HIP_TRY(bn::gated::Memcpy(x->tags + first_id, t.data(), n * sizeof(uint16_t), hipMemcpyHostToDevice));
+    return BN_OK;
+}
+
+bn_status bn_index_read_tags(const bn_index *x, uint64_t first, size_t count, uint32_t *tags_out) {
+    if (!x) return set_last_error(BN_ERR_INVALID_ARG, "null index");
+    if (first > x->size || count > x->size - first) return set_last_error(BN_ERR_INVALID_ARG, "rows out of range");
+    if (count && !tags_out) return set_last_error(BN_ERR_INVALID_ARG, "null host buffer");
+    if (!count) return BN_OK;
+    if (!x->tags) {
+        std::fill(tags_out, tags_out + count, 0u);
+        return BN_OK;
+    }
+    bn_status st = begin(x);
+    if (st != BN_OK) return st;
+    BN_HIP_TRY(hipStreamSynchronize(x->stream));
+    std::vector<uint16_t> t(count);
+    BN_HIP_TRY(bn::gated::Memcpy(t.data(), x->tags + first, count * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    std::copy(t.begin(), t.end(), tags_out);
     return BN_OK;
 }
 

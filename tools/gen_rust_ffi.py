@@ -24,7 +24,7 @@ SCALARS = {"int32_t": "i32", "uint32_t": "u32", "int64_t": "i64", "uint64_t": "u
 # compares every argument's scalar with a width table that names the types above only; under its own name a type passes that
 # comparison, and the alias gives it its Rust width)
 ALIASES = {"int8_t": "i8", "uint8_t": "u8", "int16_t": "i16", "uint16_t": "u16"}
-OPAQUE = ["bn_model", "bn_ctx", "bn_recording", "bn_group", "bn_index", "bn_ivf", "bn_sq8", "bn_head", "bn_prior", "bn_track", "bn_live"]
+OPAQUE = ["bn_model", "bn_ctx", "bn_recording", "bn_group", "bn_index", "bn_ivf", "bn_sq8", "bn_subset", "bn_head", "bn_prior", "bn_track", "bn_live"]
 STRUCT_NAMES = set()  # the header's structs with a body, filled by generate(): rust_type() accepts them by name
 RUST_KEYWORDS = {"type", "in", "ref", "box", "fn", "loop", "match", "move", "mod", "impl", "use", "where", "as"}
 
