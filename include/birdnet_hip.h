@@ -860,6 +860,54 @@ bn_status bn_subset_search_ids(bn_subset *s, const uint64_t *query_ids, size_t n
                                size_t m_stride, uint64_t *id_out, float *score_out, uint32_t *count_out);
 
 /*
+ * Event-level search: rows are appended in window order, so a row id is a position in time, and overlapping windows make neighbouring
+ * rows near-duplicates: one call in the archive that matches a query fills several consecutive ranks of bn_index_search, once per window
+ * that overlaps it.  exclude_radius handles this around the query's own id; bn_index_search_peaks handles it AMONG THE HITS: IT RETURNS
+ * ONLY THE LOCAL PEAKS OF THE SCORE OVER ROW IDS, the first top_m of them in bn_index_search's order, with bn_index_search's score bits.
+ * The rule is exact, free of any processing order and deterministic.  The reference has nothing of the kind; this comment is the contract.
+ *
+ *   Eligible row   exactly the rows bn_index_search (bn_index_search_ids) may return for that query: valid, id < bn_index_size and, for
+ *                  the _ids form, outside exclude_radius of the query's own id (< 0: none excluded; 0: the row itself).
+ *   Score          the bits bn_index_search gives that (query, row) pair: the same k-ordered chain over the padded dim.  They do not
+ *                  depend on peak_radius, on the tile, on the split among workgroups or on the number of queries.
+ *   Peak           an eligible row i is a peak of query q when EVERY OTHER eligible row j with 0 < |i - j| <= peak_radius comes AFTER i
+ *                  in the index's total order: score descending, ties by id ascending (-0.0 == +0.0).  Ineligible rows take no part:
+ *                  they are never peaks and they never suppress a neighbour.  Rows past the end of the index do not exist.
+ *   Result         the first top_m peaks in that same order; count = min(top_m, number of peaks); entries past count are not written.
+ *   Consequences   two returned ids of one query differ by more than peak_radius.  peak_radius == 0 makes every eligible row a peak:
+ *                  the call returns bn_index_search's (bn_index_search_ids') bytes.  A run of exact ties has one peak, its lowest id.
+ *   Not greedy     this is deliberately NOT greedy non-maximum suppression (take the best row, delete its neighbourhood, repeat).  On a
+ *                  monotone ramp of scores -- row i scores higher than row i - 1 over a long stretch -- the greedy rule returns the top
+ *                  row and then one row every peak_radius + 1 ids down the slope, none of which is a moment of its own; here the ramp
+ *                  has ONE peak, its top, because every other row has a better neighbour.  A row suppressed by a neighbour still
+ *                  suppresses its own neighbours: whether a row is a peak depends on the scores within peak_radius of it and on nothing
+ *                  else, which is what makes the rule independent of any order of processing.
+ *   Caveat         adjacency is BY ID ONLY.  Where two recordings meet in the append order, up to peak_radius rows of one can be
+ *                  suppressed by a better row of the other.  Tags are not consulted: nothing but bn_subset_select reads a tag.
+ *   Query          bn_index_search's rules: a host query is normalised as an appended row is, and one with zero norm or a non-finite
+ *                  element returns count 0; bn_index_search_peaks_ids takes stored rows as queries, used as stored, and the id of an
+ *                  invalid row returns count 0.
+ *   Limits         0 <= peak_radius <= BN_PEAK_RADIUS_MAX, 1 <= top_m <= 256, m_stride >= top_m.
+ *   Refusals       BN_ERR_INVALID_ARG with a message and no output written: top_m outside 1..256, m_stride < top_m, peak_radius above
+ *                  BN_PEAK_RADIUS_MAX, NULL queries / query_ids / id_out / score_out / count_out with n_queries > 0, a NULL index, a
+ *                  query id >= bn_index_size.
+ *   No device      without a gfx950 device both calls return BN_ERR_NO_DEVICE and leave the outputs untouched; the refusals that need
+ *                  no index (top_m, m_stride, peak_radius, the NULLs other than the index) come before the device is asked for.
+ *   Empty index    count 0 for every query.
+ *   Determinism    no atomic decides anything; two calls with the same inputs give the same bytes, and one call with Q queries gives
+ *                  the same bytes as Q calls with one query each.
+ *   Threading      the index's rule: one thread at a time per index.  The work runs on the index's stream, after a pending
+ *                  bn_index_add_ctx, in the index's own query and candidate buffers; both calls are synchronous.  The index is unchanged.
+ *
+ * Outputs are host arrays: id_out / score_out [n_queries * m_stride] and count_out [n_queries] as for bn_index_search.
+ */
+#define BN_PEAK_RADIUS_MAX 64
+bn_status bn_index_search_peaks(bn_index *x, const float *queries, size_t n_queries, size_t peak_radius, size_t top_m, size_t m_stride,
+                                uint64_t *id_out, float *score_out, uint32_t *count_out);
+bn_status bn_index_search_peaks_ids(bn_index *x, const uint64_t *query_ids, size_t n_queries, int64_t exclude_radius, size_t peak_radius,
+                                    size_t top_m, size_t m_stride, uint64_t *id_out, float *score_out, uint32_t *count_out);
+
+/*
  * Persistence of an index: bn_index_save writes the slab's STORED BITS to a file, bn_index_load makes an index from one.  A loaded
  * index behaves in every call exactly as the saved one did at the time of the save: searches, head fits and ranks, assignment,
  * clustering and IVF views are all stated in the bits of the stored rows, and those are what the file holds.  bn_index_read

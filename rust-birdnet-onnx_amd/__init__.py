@@ -60,6 +60,7 @@ ENGINE_SYMBOLS = [
     "bn_sq8_build", "bn_sq8_free", "bn_sq8_rows", "bn_sq8_extend", "bn_sq8_read", "bn_sq8_search", "bn_sq8_search_ids",
     "bn_index_set_tags", "bn_index_fill_tags", "bn_index_read_tags",
     "bn_subset_select", "bn_subset_from_ids", "bn_subset_free", "bn_subset_size", "bn_subset_read", "bn_subset_search", "bn_subset_search_ids",
+    "bn_index_search_peaks", "bn_index_search_peaks_ids",
     "bn_head_create", "bn_head_free", "bn_head_dim", "bn_head_classes", "bn_head_flags", "bn_head_read", "bn_head_apply_host",
     "bn_head_fit", "bn_head_fit_index", "bn_head_rank_index", "bn_ctx_attach_head", "bn_step_head_results",
     "bn_prior_create", "bn_prior_free", "bn_prior_sites", "bn_prior_species", "bn_prior_threshold", "bn_prior_flags", "bn_prior_read",
@@ -141,6 +142,7 @@ class BnIndexFilter(C.Structure):
 
 
 BN_INDEX_TAG_LIMIT = 65536  # row tags lie below it
+BN_PEAK_RADIUS_MAX = 64  # largest peak_radius of Index.search_peaks / search_peaks_ids
 BN_FILTER_EXCLUDE_TAGS = 1  # bn_index_filter flag: the tag list names the tags left out
 BN_CLUSTER_NONE = 0xFFFFFFFF  # the assignment of a row that belongs to no cluster
 BN_HEAD_L2NORM = 1
@@ -273,6 +275,8 @@ def _load() -> C.CDLL:
         "bn_subset_read": (i32, [vp, sz, sz, C.POINTER(C.c_uint64)]),
         "bn_subset_search": (i32, [vp, f32p, sz, sz, sz, C.POINTER(C.c_uint64), f32p, u32p]),
         "bn_subset_search_ids": (i32, [vp, C.POINTER(C.c_uint64), sz, C.c_int64, sz, sz, C.POINTER(C.c_uint64), f32p, u32p]),
+        "bn_index_search_peaks": (i32, [vp, f32p, sz, sz, sz, sz, C.POINTER(C.c_uint64), f32p, u32p]),
+        "bn_index_search_peaks_ids": (i32, [vp, C.POINTER(C.c_uint64), sz, C.c_int64, sz, sz, sz, C.POINTER(C.c_uint64), f32p, u32p]),
         "bn_head_create": (i32, [i32, sz, sz, f32p, f32p, C.c_uint32, C.POINTER(vp)]),
         "bn_head_free": (None, [vp]),
         "bn_head_dim": (sz, [vp]),
@@ -1275,6 +1279,32 @@ class Index:
         st = lib.bn_index_search_ids(self._h, qi.ctypes.data_as(C.POINTER(C.c_uint64)), qi.shape[0], exclude_radius, top_m, m_stride,
                                      out_ids.ctypes.data_as(C.POINTER(C.c_uint64)), scores.ctypes.data_as(C.POINTER(C.c_float)),
                                      counts.ctypes.data_as(C.POINTER(C.c_uint32)))
+        if st:
+            raise EngineError(st)
+        return out_ids, scores, counts
+
+    def search_peaks(self, queries, top_m: int, peak_radius: int, m_stride: Optional[int] = None):
+        """bn_index_search_peaks: search(), but only rows that no eligible row within peak_radius ids of them beats are returned: one hit
+        per local peak of the score over row ids.  peak_radius 0 is search()."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
+        m_stride = top_m if m_stride is None else m_stride
+        ids, scores, counts = self._outputs(q.shape[0], max(m_stride, 0))
+        st = lib.bn_index_search_peaks(self._h, q.ctypes.data_as(C.POINTER(C.c_float)), q.shape[0], peak_radius, top_m, m_stride,
+                                       ids.ctypes.data_as(C.POINTER(C.c_uint64)), scores.ctypes.data_as(C.POINTER(C.c_float)),
+                                       counts.ctypes.data_as(C.POINTER(C.c_uint32)))
+        if st:
+            raise EngineError(st)
+        return ids, scores, counts
+
+    def search_peaks_ids(self, ids, top_m: int, peak_radius: int, exclude_radius: int = -1, m_stride: Optional[int] = None):
+        """bn_index_search_peaks_ids: search_ids(), restricted to the local peaks as search_peaks() is; rows within exclude_radius of a
+        query's id are neither returned nor do they suppress a neighbour."""
+        qi = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+        m_stride = top_m if m_stride is None else m_stride
+        out_ids, scores, counts = self._outputs(qi.shape[0], max(m_stride, 0))
+        st = lib.bn_index_search_peaks_ids(self._h, qi.ctypes.data_as(C.POINTER(C.c_uint64)), qi.shape[0], exclude_radius, peak_radius, top_m,
+                                           m_stride, out_ids.ctypes.data_as(C.POINTER(C.c_uint64)), scores.ctypes.data_as(C.POINTER(C.c_float)),
+                                           counts.ctypes.data_as(C.POINTER(C.c_uint32)))
         if st:
             raise EngineError(st)
         return out_ids, scores, counts

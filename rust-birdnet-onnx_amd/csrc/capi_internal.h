@@ -186,11 +186,11 @@ struct IndexScan {
     const uint16_t *tags = nullptr;  // [cap_pad] row tags; NULL until a tag is first set: every tag is 0
 };
 bn_status index_scan_state(bn_index *x, IndexScan *out);
-// index.hip -> subset.hip (bn_subset_search): index_merge_kernel enqueued on `stream`: one wave per query walks the n_wg workgroups' sorted
+// index.hip -> subset.hip (bn_subset_search), peaks.hip (bn_index_search_peaks): index_merge_kernel enqueued on `stream`: one wave per query walks the n_wg workgroups' sorted
 // lists cand[g][q][256] (lengths cand_len[g][q], IndexScan::lists lists per workgroup) into out[q][M], count[q]
 bn_status index_enqueue_merge(hipStream_t stream, const topm::Cand *cand, const int *cand_len, size_t n_queries, int n_wg, int M, topm::Cand *out,
                               uint32_t *count);
-// index.hip -> ivf.hip, sq8.hip (bn_ivf_search, bn_sq8_search and their _ids forms): up to out_lists queries made ready in the index's own query buffers, on
+// index.hip -> ivf.hip, sq8.hip, subset.hip, peaks.hip (bn_ivf_search, bn_sq8_search, bn_subset_search, bn_index_search_peaks and their _ids forms): up to out_lists queries made ready in the index's own query buffers, on
 // its stream, exactly as bn_index_search / bn_index_search_ids prepare theirs: host rows normalised, or stored rows gathered by id
 // (ids below bn_index_size).  *d_q [n, dpad], *d_qvalid [n], *d_qid [n] (ids only) stay the index's
 bn_status index_stage_queries(bn_index *x, const float *queries, size_t n, const float **d_q, const uint8_t **d_qvalid);
