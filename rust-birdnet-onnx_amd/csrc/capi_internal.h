@@ -1,11 +1,15 @@
 // What the translation units of the C ABI share: the plumbing every entry point repeats (the error macro, launch and device checks,
 // the packed top-K block TopkRows, results_to_host, the pinned ring PinnedRing, scoped scratch: step_common.cpp), what they need of
-// capi.cpp's private state (index.hip: bn_index_*; head.hip: bn_head_*; rank.hip: bn_head_rank_index; cluster.hip: bn_index_assign, bn_index_cluster; live.cpp: bn_step_live) and of each other (prior.hip:
+// capi.cpp's private state (index.hip: bn_index_* and the host side every search over an index shares; head.hip: bn_head_*; rank.hip: bn_head_rank_index; cluster.hip: bn_index_assign, bn_index_cluster; live.cpp: bn_step_live) and of each other (prior.hip:
 // bn_prior_*; track.hip: bn_track_*).  A step's rows reach its stages as an argument (StepRows), never through a context's state.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <functional>
+#include <initializer_list>
+#include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/birdnet_hip.h"
@@ -186,10 +190,56 @@ struct IndexScan {
     const uint16_t *tags = nullptr;  // [cap_pad] row tags; NULL until a tag is first set: every tag is 0
 };
 bn_status index_scan_state(bn_index *x, IndexScan *out);
-// index.hip -> subset.hip (bn_subset_search), peaks.hip (bn_index_search_peaks): index_merge_kernel enqueued on `stream`: one wave per query walks the n_wg workgroups' sorted
+// index.hip -> subset.hip, peaks.hip, rank.hip: index_merge_kernel enqueued on `stream`: one wave per query walks the n_wg workgroups' sorted
 // lists cand[g][q][256] (lengths cand_len[g][q], IndexScan::lists lists per workgroup) into out[q][M], count[q]
 bn_status index_enqueue_merge(hipStream_t stream, const topm::Cand *cand, const int *cand_len, size_t n_queries, int n_wg, int M, topm::Cand *out,
                               uint32_t *count);
+// ---- index.hip: the host side that the searches over an index share (index, subset, peaks, rank, ivf, sq8) ----
+// The dynamic-LDS opt-in of a file's scan kernels beyond 64 KB, once per device, under the capture gate (it may not overlap a
+// capture).  One object per file, with static storage.
+struct LdsOptIn {
+    struct Kernel {
+        const void *fn;
+        size_t bytes;
+    };
+    std::mutex mu;
+    uint64_t ready = 0;  // devices (ordinal < 64) on which the kernels have been opted in
+    hipError_t prepare(int dev, std::initializer_list<Kernel> kernels);
+};
+// The refusals of a top-M search's arguments that need neither a handle nor a device, in bn_index_search's order and words: top_m
+// outside 1..256, then m_stride < top_m (check_top_m); a call with queries that lacks them or an output (check_search_buffers).  Two
+// calls, since bn_index_search_peaks refuses its radius between them
+bn_status check_top_m(size_t top_m, size_t m_stride);
+bn_status check_search_buffers(const void *queries, size_t n_queries, const uint64_t *id_out, const float *score_out, const uint32_t *count_out);
+// n_tiles >= 1 tiles in contiguous runs of tiles_per_wg, at most max_wg workgroups, none of them empty
+struct WgSplit {
+    uint32_t tiles_per_wg, n_wg;
+};
+inline WgSplit split_tiles(uint32_t n_tiles, size_t max_wg) {
+    const uint32_t tpw = (uint32_t)((n_tiles + max_wg - 1) / max_wg);
+    return {tpw, (n_tiles + tpw - 1) / tpw};
+}
+// f(std::integral_constant<int, NB>) for the NB = ceil(n / 16) in 1..4 blocks of 16 lists that a pass of n <= 64 lists fills: the
+// choice of a scan kernel's instantiation
+template <class F>
+inline void by_blocks(int n, F &&f) {
+    switch ((n + 15) / 16) {
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 3: f(std::integral_constant<int, 3>{}); break;
+        default: f(std::integral_constant<int, 4>{}); break;
+    }
+}
+// One round of a scan over n_lists <= out_lists staged lists with the index's own buffers, synchronous: per pass of s.lists lists
+// launch_scan(p0, np) enqueues the scan of lists [p0, p0 + np) on s.stream (n_wg workgroups, candidates into s.d_cand /
+// s.d_cand_len) and is checked as the launch `what`; `merge` (index_enqueue_merge's signature) then finishes the pass's lists
+// into s.d_out / s.d_count.  After the last pass both come back into s.h_out [n_lists][M] / s.h_count and the stream is waited for
+using MergeEnqueue = bn_status (*)(hipStream_t, const topm::Cand *, const int *, size_t, int, int, topm::Cand *, uint32_t *);
+bn_status run_scan_passes(const IndexScan &s, size_t n_lists, uint32_t n_wg, int M, const char *what,
+                          const std::function<void(size_t p0, int np)> &launch_scan, MergeEnqueue merge = index_enqueue_merge);
+// rows [n][M] of a round's results (h_count[i] entries each) -> the caller's arrays at stride m_stride; entries past a count stay
+void scatter_results(const topm::Cand *h_out, const uint32_t *h_count, size_t n, size_t M, size_t m_stride, uint64_t *id_out, float *score_out,
+                     uint32_t *count_out);
 // index.hip -> ivf.hip, sq8.hip, subset.hip, peaks.hip (bn_ivf_search, bn_sq8_search, bn_subset_search, bn_index_search_peaks and their _ids forms): up to out_lists queries made ready in the index's own query buffers, on
 // its stream, exactly as bn_index_search / bn_index_search_ids prepare theirs: host rows normalised, or stored rows gathered by id
 // (ids below bn_index_size).  *d_q [n, dpad], *d_qvalid [n], *d_qid [n] (ids only) stay the index's

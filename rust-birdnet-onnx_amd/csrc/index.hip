@@ -14,10 +14,12 @@
 //   * index_merge_kernel -- one wave per query merges the workgroups' sorted lists into the final top-M, reading each list
 //     only while its entries still beat the running M-th.
 // Order everywhere: score descending, ties by id ascending (-0.0 == +0.0 through the float compare).  The candidate, the order and
-// the two merges live in topm_select.h, which rank.hip (bn_head_rank_index) shares; it also borrows this index's stream and
-// candidate buffers (index_scan_state).  cluster.hip (bn_index_assign, bn_index_cluster) borrows the stream and keeps its own
-// buffers on the index (index_cluster_state).  subset.hip (bn_subset_*) borrows the stream, the query staging, the candidate buffers and
-// index_merge_kernel (index_enqueue_merge), and reads the tag plane below.
+// the two merges live in topm_select.h; the scan's constants and LDS layout in index_scan.h, which the subset, peaks and rank scans
+// carve theirs from too.  Other files borrow this index's stream and buffers: rank.hip, subset.hip, peaks.hip, ivf.hip
+// and sq8.hip through index_scan_state, cluster.hip through index_cluster_state.  The host side those searches share is defined
+// here once (declared in capi_internal.h): the LDS opt-in (LdsOptIn), the argument refusals (check_top_m, check_search_buffers),
+// the pass loop with its merge and copy-back (run_scan_passes, index_enqueue_merge) and the copy into the caller's arrays
+// (scatter_results); subset.hip also reads the tag plane below.
 //
 // Row tags (bn_index_set_tags / fill_tags / read_tags): one u16 per row of capacity, allocated zeroed by the first call that sets one.
 // No kernel of this file reads it.
@@ -34,18 +36,20 @@
 #include "capi_internal.h"
 #include "device_common.h"
 #include "hip_gate.h"
+#include "index_scan.h"
 #include "topm_select.h"
 
 namespace {
 
-constexpr int KC = 128;    // k-step of the scan; slab and query rows are padded to a multiple of it
-constexpr int TILE = 64;   // rows per workgroup tile: 4 waves x 16 rows
-constexpr int QP = 64;     // queries per scan pass
-constexpr int QS_LD = KC + 4;
-constexpr int S_LD = TILE + 1;
+using bn::scan::KC;
+using bn::scan::QS_LD;
+using bn::scan::S_LD;
+using bn::scan::TILE;
+constexpr int QP = bn::scan::LP;  // queries per scan pass
 constexpr size_t QCHUNK = 1024;  // queries normalised / searched per round of a call
 constexpr size_t STAGE_ROWS = 1024;
 
+using bn::floatx4;
 using bn::topm::Cand;
 using bn::topm::lanes_below;
 using bn::topm::merge_pending;
@@ -54,10 +58,7 @@ using bn::topm::PEND;
 using bn::topm::wave_sync;
 using Ord = bn::topm::ScoreDesc;  // the search's order: score descending, ties by id ascending
 
-constexpr size_t SCAN_LDS = (size_t)QP * QS_LD * 4 + (size_t)QP * S_LD * 4 + (size_t)QP * PEND * sizeof(Cand) + 4 * MMAX * sizeof(Cand) +
-                            QP * sizeof(Cand) + 2 * QP * sizeof(int);
-
-using bn::floatx4;
+constexpr size_t SCAN_LDS = bn::scan::Layout<1>::BYTES;
 
 // rows [n, dim] at src (row stride src_stride) -> normalised rows [n, dpad] at dst + validity flags
 __global__ __launch_bounds__(256) void index_normalise_kernel(const float *__restrict__ src, size_t src_stride, uint32_t n, uint32_t dim,
@@ -99,14 +100,15 @@ __global__ __launch_bounds__(256) void index_scan_kernel(const float *__restrict
                                                          uint32_t dpad, const float *__restrict__ q, const uint8_t *__restrict__ qvalid, int nq,
                                                          const uint32_t *__restrict__ qid, int64_t radius, int M, uint32_t tiles_per_wg,
                                                          Cand *__restrict__ cand, int *__restrict__ cand_len) {
-    extern __shared__ __align__(16) float idx_lds[];
-    float *Qs = idx_lds;                               // [QP][QS_LD]: the queries' current k chunk
-    float *S = Qs + QP * QS_LD;                        // [QP][S_LD]: scores of the current tile
-    Cand *pend = reinterpret_cast<Cand *>(S + QP * S_LD);  // [QP][PEND]
-    Cand *scratch = pend + QP * PEND;                  // [4][MMAX]
-    Cand *thr = scratch + 4 * MMAX;                    // [QP]
-    int *len = reinterpret_cast<int *>(thr + QP);      // [QP]
-    int *pn = len + QP;                                // [QP]
+    extern __shared__ __align__(16) char idx_lds[];
+    using L = bn::scan::Layout<1>;
+    float *Qs = reinterpret_cast<float *>(idx_lds + L::B);             // [QP][QS_LD]: the queries' current k chunk
+    float *S = reinterpret_cast<float *>(idx_lds + L::S);              // [QP][S_LD]: scores of the current tile
+    Cand *pend = reinterpret_cast<Cand *>(idx_lds + L::PENDING);       // [QP][PEND]
+    Cand *scratch = reinterpret_cast<Cand *>(idx_lds + L::SCRATCH);    // [4][MMAX]
+    Cand *thr = reinterpret_cast<Cand *>(idx_lds + L::THR);            // [QP]
+    int *len = reinterpret_cast<int *>(idx_lds + L::LEN);              // [QP]
+    int *pn = reinterpret_cast<int *>(idx_lds + L::PN);                // [QP]
 
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int r16 = lane & 15, h = lane >> 4;
@@ -230,23 +232,7 @@ __global__ __launch_bounds__(64) void index_merge_kernel(const Cand *__restrict_
     bn::topm::merge_lists<Ord>(cand, cand_len, QP, n_wg, M, out, count);
 }
 
-std::mutex g_lds_mu;
-uint64_t g_lds_ready = 0;  // devices (ordinal < 64) on which the scan kernels may use SCAN_LDS bytes
-
-// the > 64 KB LDS opt-in of the scan kernels, once per device (under the capture gate: it may not overlap a capture)
-hipError_t prepare_scan(int dev) {
-    std::lock_guard<std::mutex> lk(g_lds_mu);
-    if (dev < 64 && ((g_lds_ready >> dev) & 1)) return hipSuccess;
-    bn::gated::Shared g;
-    const void *ks[] = {reinterpret_cast<const void *>(index_scan_kernel<1>), reinterpret_cast<const void *>(index_scan_kernel<2>),
-                        reinterpret_cast<const void *>(index_scan_kernel<3>), reinterpret_cast<const void *>(index_scan_kernel<4>)};
-    for (const void *k : ks) {
-        hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SCAN_LDS);
-        if (e != hipSuccess) return e;
-    }
-    if (dev < 64) g_lds_ready |= 1ull << dev;
-    return hipSuccess;
-}
+bn::LdsOptIn g_scan_lds;
 
 }  // namespace
 
@@ -307,52 +293,45 @@ bn_status begin(const bn_index *x) {
 bn_status check_search_args(const bn_index *x, const void *queries, size_t n_queries, size_t top_m, size_t m_stride, const uint64_t *id_out,
                             const float *score_out, const uint32_t *count_out) {
     if (!x) return set_last_error(BN_ERR_INVALID_ARG, "null index");
-    if (top_m < 1 || top_m > MMAX) return set_last_error(BN_ERR_INVALID_ARG, "top_m must be in 1..256, got " + std::to_string(top_m));
-    if (m_stride < top_m) return set_last_error(BN_ERR_INVALID_ARG, "m_stride < top_m");
-    if (n_queries && (!queries || !id_out || !score_out || !count_out)) return set_last_error(BN_ERR_INVALID_ARG, "null argument");
-    return BN_OK;
+    if (bn_status st = bn::check_top_m(top_m, m_stride); st != BN_OK) return st;
+    return bn::check_search_buffers(queries, n_queries, id_out, score_out, count_out);
 }
 
-// the scan + merge passes over d_q[0 .. nq) (nq <= QCHUNK), results into the pinned mirrors; synchronous
+// what a scan on the index's own stream and buffers needs (capi_internal.h)
+bn::IndexScan scan_state_of(const bn_index *x) {
+    bn::IndexScan s;
+    s.device = x->device;
+    s.stream = x->stream;
+    s.slab = x->slab;
+    s.valid = x->valid;
+    s.dim = x->dim;
+    s.dpad = x->dpad;
+    s.size = x->size;
+    s.cap_pad = x->cap_pad;
+    s.max_wg = x->max_wg;
+    s.lists = QP;
+    s.out_lists = QCHUNK;
+    s.d_cand = x->d_cand;
+    s.d_cand_len = x->d_cand_len;
+    s.d_out = x->d_out;
+    s.d_count = x->d_count;
+    s.h_out = x->h_out;
+    s.h_count = x->h_count;
+    s.tags = x->tags;
+    return s;
+}
+
+// the scan + merge passes over d_q[0 .. nq) (nq <= QCHUNK, the index not empty), results into the pinned mirrors; synchronous
 bn_status run_search(bn_index *x, size_t nq, bool by_id, int64_t radius, int M) {
     const uint32_t n_rows = (uint32_t)x->size;
-    const uint32_t n_tiles = (n_rows + TILE - 1) / TILE;
-    const uint32_t tpw = (n_tiles + x->max_wg - 1) / x->max_wg;
-    const uint32_t n_wg = (n_tiles + tpw - 1) / tpw;
-    for (size_t p0 = 0; p0 < nq; p0 += QP) {
-        const int np = (int)std::min<size_t>(QP, nq - p0);
-        const float *q = x->d_q + p0 * x->dpad;
-        const uint8_t *qv = x->d_qvalid + p0;
-        const uint32_t *qid = by_id ? x->d_qid + p0 : nullptr;
-        const int64_t rad = by_id ? radius : -1;
-        const dim3 grid(n_wg), block(256);
-        switch ((np + 15) / 16) {
-            case 1: hipLaunchKernelGGL(index_scan_kernel<1>, grid, block, SCAN_LDS, x->stream, x->slab, x->valid, n_rows, (uint32_t)x->dpad, q, qv, np, qid, rad, M, tpw, x->d_cand, x->d_cand_len); break;
-            case 2: hipLaunchKernelGGL(index_scan_kernel<2>, grid, block, SCAN_LDS, x->stream, x->slab, x->valid, n_rows, (uint32_t)x->dpad, q, qv, np, qid, rad, M, tpw, x->d_cand, x->d_cand_len); break;
-            case 3: hipLaunchKernelGGL(index_scan_kernel<3>, grid, block, SCAN_LDS, x->stream, x->slab, x->valid, n_rows, (uint32_t)x->dpad, q, qv, np, qid, rad, M, tpw, x->d_cand, x->d_cand_len); break;
-            default: hipLaunchKernelGGL(index_scan_kernel<4>, grid, block, SCAN_LDS, x->stream, x->slab, x->valid, n_rows, (uint32_t)x->dpad, q, qv, np, qid, rad, M, tpw, x->d_cand, x->d_cand_len); break;
-        }
-        bn_status st = check_launch("index scan");
-        if (st != BN_OK) return st;
-        hipLaunchKernelGGL(index_merge_kernel, dim3(np), dim3(64), 0, x->stream, x->d_cand, x->d_cand_len, (int)n_wg, M, x->d_out + p0 * M, x->d_count + p0);
-        st = check_launch("index merge");
-        if (st != BN_OK) return st;
-    }
-    BN_HIP_TRY(hipMemcpyAsync(x->h_out, x->d_out, nq * M * sizeof(Cand), hipMemcpyDeviceToHost, x->stream));
-    BN_HIP_TRY(hipMemcpyAsync(x->h_count, x->d_count, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, x->stream));
-    BN_HIP_TRY(hipStreamSynchronize(x->stream));
-    return BN_OK;
-}
-
-void scatter(const bn_index *x, size_t nq, size_t M, size_t m_stride, uint64_t *id_out, float *score_out, uint32_t *count_out) {
-    for (size_t i = 0; i < nq; i++) {
-        const uint32_t n = x->h_count[i];
-        count_out[i] = n;
-        for (uint32_t j = 0; j < n; j++) {
-            id_out[i * m_stride + j] = x->h_out[i * M + j].id;
-            score_out[i * m_stride + j] = x->h_out[i * M + j].s;
-        }
-    }
+    const bn::WgSplit sp = bn::split_tiles((n_rows + TILE - 1) / TILE, x->max_wg);
+    return bn::run_scan_passes(scan_state_of(x), nq, sp.n_wg, M, "index scan", [&](size_t p0, int np) {
+        bn::by_blocks(np, [&](auto qb) {
+            hipLaunchKernelGGL(index_scan_kernel<decltype(qb)::value>, dim3(sp.n_wg), dim3(256), SCAN_LDS, x->stream, x->slab, x->valid, n_rows,
+                               (uint32_t)x->dpad, x->d_q + p0 * x->dpad, x->d_qvalid + p0, np, by_id ? x->d_qid + p0 : nullptr,
+                               by_id ? radius : (int64_t)-1, M, sp.tiles_per_wg, x->d_cand, x->d_cand_len);
+        });
+    });
 }
 
 // host queries [nq, dim] (nq <= QCHUNK) -> d_q / d_qvalid, normalised as appended rows are
@@ -454,24 +433,7 @@ bn_status bn::index_scan_state(bn_index *x, IndexScan *out) {
     if (!x || !out) return set_last_error(BN_ERR_INVALID_ARG, "null index");
     bn_status st = begin(x);
     if (st != BN_OK) return st;
-    out->device = x->device;
-    out->stream = x->stream;
-    out->slab = x->slab;
-    out->valid = x->valid;
-    out->dim = x->dim;
-    out->dpad = x->dpad;
-    out->size = x->size;
-    out->cap_pad = x->cap_pad;
-    out->max_wg = x->max_wg;
-    out->lists = QP;
-    out->out_lists = QCHUNK;
-    out->d_cand = x->d_cand;
-    out->d_cand_len = x->d_cand_len;
-    out->d_out = x->d_out;
-    out->d_count = x->d_count;
-    out->h_out = x->h_out;
-    out->h_count = x->h_count;
-    out->tags = x->tags;
+    *out = scan_state_of(x);
     return BN_OK;
 }
 
@@ -479,6 +441,56 @@ bn_status bn::index_enqueue_merge(hipStream_t stream, const topm::Cand *cand, co
                                   uint32_t *count) {
     hipLaunchKernelGGL(index_merge_kernel, dim3((unsigned)n_queries), dim3(64), 0, stream, cand, cand_len, n_wg, M, out, count);
     return check_launch("index merge");
+}
+
+hipError_t bn::LdsOptIn::prepare(int dev, std::initializer_list<Kernel> kernels) {
+    std::lock_guard<std::mutex> lk(mu);
+    if (dev < 64 && ((ready >> dev) & 1)) return hipSuccess;
+    bn::gated::Shared g;
+    for (const Kernel &k : kernels) {
+        hipError_t e = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.bytes);
+        if (e != hipSuccess) return e;
+    }
+    if (dev < 64) ready |= 1ull << dev;
+    return hipSuccess;
+}
+
+bn_status bn::check_top_m(size_t top_m, size_t m_stride) {
+    if (top_m < 1 || top_m > (size_t)MMAX) return set_last_error(BN_ERR_INVALID_ARG, "top_m must be in 1..256, got " + std::to_string(top_m));
+    if (m_stride < top_m) return set_last_error(BN_ERR_INVALID_ARG, "m_stride < top_m");
+    return BN_OK;
+}
+
+bn_status bn::check_search_buffers(const void *queries, size_t n_queries, const uint64_t *id_out, const float *score_out, const uint32_t *count_out) {
+    if (n_queries && (!queries || !id_out || !score_out || !count_out)) return set_last_error(BN_ERR_INVALID_ARG, "null argument");
+    return BN_OK;
+}
+
+bn_status bn::run_scan_passes(const IndexScan &s, size_t n_lists, uint32_t n_wg, int M, const char *what,
+                              const std::function<void(size_t p0, int np)> &launch_scan, MergeEnqueue merge) {
+    for (size_t p0 = 0; p0 < n_lists; p0 += s.lists) {
+        const int np = (int)std::min(s.lists, n_lists - p0);
+        launch_scan(p0, np);
+        bn_status st = check_launch(what);
+        if (st != BN_OK) return st;
+        if ((st = merge(s.stream, s.d_cand, s.d_cand_len, (size_t)np, (int)n_wg, M, s.d_out + p0 * M, s.d_count + p0)) != BN_OK) return st;
+    }
+    BN_HIP_TRY(hipMemcpyAsync(s.h_out, s.d_out, n_lists * M * sizeof(Cand), hipMemcpyDeviceToHost, s.stream));
+    BN_HIP_TRY(hipMemcpyAsync(s.h_count, s.d_count, n_lists * sizeof(uint32_t), hipMemcpyDeviceToHost, s.stream));
+    BN_HIP_TRY(hipStreamSynchronize(s.stream));
+    return BN_OK;
+}
+
+void bn::scatter_results(const topm::Cand *h_out, const uint32_t *h_count, size_t n, size_t M, size_t m_stride, uint64_t *id_out, float *score_out,
+                         uint32_t *count_out) {
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t c = h_count[i];
+        count_out[i] = c;
+        for (uint32_t j = 0; j < c; j++) {
+            id_out[i * m_stride + j] = h_out[i * M + j].id;
+            score_out[i * m_stride + j] = h_out[i * M + j].s;
+        }
+    }
 }
 
 bn_status bn::index_io_state(bn_index *x, IndexIo *out) {
@@ -513,7 +525,8 @@ bn_status bn_index_create(int32_t device, size_t dim, size_t capacity_rows, bn_i
     if (capacity_rows >= 0xffffffffull - TILE) return set_last_error(BN_ERR_INVALID_ARG, "capacity_rows must be below 2^32 - 64");
     if (bn_status dst = bn::require_device(device); dst != BN_OK) return dst;
     BN_HIP_TRY(bn::use_device(device));
-    BN_HIP_TRY(prepare_scan(device));
+    BN_HIP_TRY(g_scan_lds.prepare(device, {{(const void *)index_scan_kernel<1>, SCAN_LDS}, {(const void *)index_scan_kernel<2>, SCAN_LDS},
+                                            {(const void *)index_scan_kernel<3>, SCAN_LDS}, {(const void *)index_scan_kernel<4>, SCAN_LDS}}));
     std::unique_ptr<bn_index, void (*)(bn_index *)> x(new bn_index, release);
     x->device = device;
     x->dim = dim;
@@ -660,7 +673,7 @@ bn_status bn_index_search(bn_index *x, const float *queries, size_t n_queries, s
         }
         if ((st = stage_host_queries(x, queries + q0 * x->dim, nq)) != BN_OK) return st;
         if ((st = run_search(x, nq, false, -1, (int)top_m)) != BN_OK) return st;
-        scatter(x, nq, top_m, m_stride, id_out + q0 * m_stride, score_out + q0 * m_stride, count_out + q0);
+        bn::scatter_results(x->h_out, x->h_count, nq, top_m, m_stride, id_out + q0 * m_stride, score_out + q0 * m_stride, count_out + q0);
     }
     return BN_OK;
 }
@@ -676,7 +689,7 @@ bn_status bn_index_search_ids(bn_index *x, const uint64_t *query_ids, size_t n_q
         const size_t nq = std::min(QCHUNK, n_queries - q0);
         if ((st = stage_id_queries(x, query_ids + q0, nq)) != BN_OK) return st;
         if ((st = run_search(x, nq, true, exclude_radius, (int)top_m)) != BN_OK) return st;
-        scatter(x, nq, top_m, m_stride, id_out + q0 * m_stride, score_out + q0 * m_stride, count_out + q0);
+        bn::scatter_results(x->h_out, x->h_count, nq, top_m, m_stride, id_out + q0 * m_stride, score_out + q0 * m_stride, count_out + q0);
     }
     return BN_OK;
 }

@@ -388,14 +388,6 @@ bn_status bn::ivf_enqueue_merge(hipStream_t stream, const topm::Cand *cand, cons
 
 namespace {
 
-bn_status check_search_args(size_t n_queries, size_t top_m, size_t m_stride, const void *queries, const uint64_t *id_out, const float *score_out,
-                            const uint32_t *count_out) {
-    if (top_m < 1 || top_m > (size_t)MMAX) return set_last_error(BN_ERR_INVALID_ARG, "top_m must be in 1..256, got " + std::to_string(top_m));
-    if (m_stride < top_m) return set_last_error(BN_ERR_INVALID_ARG, "m_stride < top_m");
-    if (n_queries && (!queries || !id_out || !score_out || !count_out)) return set_last_error(BN_ERR_INVALID_ARG, "null argument");
-    return BN_OK;
-}
-
 // probe, scan and merge for the nq staged queries (nq <= out_lists); results into the index's pinned mirrors; synchronous
 bn_status run_search(bn_ivf *v, const bn::IndexScan &s, size_t nq, const float *d_q, const uint8_t *d_qvalid, const uint32_t *d_qid, int64_t radius,
                      size_t nprobe, int M) {
@@ -442,8 +434,9 @@ bn_status run_search(bn_ivf *v, const bn::IndexScan &s, size_t nq, const float *
 
 bn_status search(bn_ivf *v, const float *queries, const uint64_t *query_ids, size_t n_queries, int64_t radius, size_t nprobe, size_t top_m, size_t m_stride,
                  uint64_t *id_out, float *score_out, uint32_t *count_out, uint32_t *probes_out, uint64_t *scanned_out) {
-    bn_status st = check_search_args(n_queries, top_m, m_stride, queries ? (const void *)queries : (const void *)query_ids, id_out, score_out, count_out);
+    bn_status st = bn::check_top_m(top_m, m_stride);
     if (st != BN_OK) return st;
+    if ((st = bn::check_search_buffers(queries ? (const void *)queries : (const void *)query_ids, n_queries, id_out, score_out, count_out)) != BN_OK) return st;
     if ((st = bn::require_any_device()) != BN_OK) return st;
     if (!v) return set_last_error(BN_ERR_INVALID_ARG, "null view");
     if (nprobe < 1 || nprobe > v->k) return set_last_error(BN_ERR_INVALID_ARG, "nprobe must be in 1.." + std::to_string(v->k) + ", got " + std::to_string(nprobe));
@@ -462,14 +455,7 @@ bn_status search(bn_ivf *v, const float *queries, const uint64_t *query_ids, siz
         else st = bn::index_stage_queries(v->x, queries + q0 * v->dim, nq, &d_q, &d_qvalid);
         if (st != BN_OK) return st;
         if ((st = run_search(v, s, nq, d_q, d_qvalid, d_qid, radius, nprobe, (int)top_m)) != BN_OK) return st;
-        for (size_t i = 0; i < nq; i++) {
-            const uint32_t n = s.h_count[i];
-            count_out[q0 + i] = n;
-            for (uint32_t j = 0; j < n; j++) {
-                id_out[(q0 + i) * m_stride + j] = s.h_out[i * top_m + j].id;
-                score_out[(q0 + i) * m_stride + j] = s.h_out[i * top_m + j].s;
-            }
-        }
+        bn::scatter_results(s.h_out, s.h_count, nq, top_m, m_stride, id_out + q0 * m_stride, score_out + q0 * m_stride, count_out + q0);
         if (probes_out) BN_HIP_TRY(bn::gated::Memcpy(probes_out + q0 * nprobe, v->d_probes, nq * nprobe * sizeof(uint32_t), hipMemcpyDeviceToHost));
         if (scanned_out) BN_HIP_TRY(bn::gated::Memcpy(scanned_out + q0, v->d_scanned, nq * sizeof(uint64_t), hipMemcpyDeviceToHost));
     }

@@ -4,40 +4,40 @@
 // have bn_index_search's bits, and peak_radius == 0 is bn_index_search itself.
 //
 // Kernel of this file:
-//   * peaks_scan_kernel<QB> -- index_scan_kernel's tile loop written out again: 64 queries per pass in LDS, the exact-f32 MFMA
-//     v_mfma_f32_16x16x4_f32 with row = A operand and query = B operand, one accumulator per (query, row) over k ascending.  What differs
-//     lies between the MFMA and the selection.  The scores of THREE consecutive tiles stay in LDS (a ring of [QP][S_LD] planes, tile t in
-//     plane t mod 3); a pair that is not eligible (row invalid or past the end, id within the exclusion radius of the query's own) is
-//     stored as -inf, which can neither be a peak nor come before a finite score, from a validity word and query ids fetched ahead of
-//     the tile's MFMAs.  Tile t - 1 is judged when tile t's scores land: lane = row, the lane's 2 * radius neighbours read from the ring
-//     (consecutive lanes read consecutive words of one query's line, and the planes are a multiple of 64 words apart: no bank conflict),
-//     and only peaks enter index_scan_kernel's threshold-and-pending path.  A workgroup owns a contiguous run of tiles and computes, for
-//     their scores alone, the tile before and the tile after its run where they exist; those scores have the same bits in every
-//     workgroup, so no workgroup talks to another.  The sorted candidates go to the index's own buffers; index_merge_kernel
-//     (index_enqueue_merge) finishes the query.  LDS: index_scan_kernel's 125 184 B + two more score planes = 158 464 B (opted in per
-//     device).
+//   * peaks_scan_kernel<QB> -- index_scan_kernel's tile loop written out once more: 64 queries per pass in LDS, the exact-f32
+//     MFMA v_mfma_f32_16x16x4_f32 with row = A operand and query = B operand, one accumulator per (query, row) over k ascending.  It shares
+//     index_scan.h's constants and LDS layout (three score planes); the loop is this file's own (as an instantiation of one templated body
+//     it measured 1 to 3 % slower at 32 and 128 queries: DESIGN.md).  What differs from index_scan_kernel lies between the MFMA and
+//     the selection.  The scores of THREE consecutive tiles stay in LDS (a ring of [QP][S_LD] planes, tile t in plane t mod 3); a pair that
+//     is not eligible (row invalid or past the end, id within the exclusion radius of the query's own) is stored as -inf, which can
+//     neither be a peak nor come before a finite score, from a validity word and query ids fetched ahead of the tile's MFMAs.  Tile t - 1
+//     is judged when tile t's scores land: lane = row, the lane's 2 * radius neighbours read from the ring (consecutive lanes read
+//     consecutive words of one query's line, and the planes are a multiple of 64 words apart: no bank conflict), and only peaks enter the
+//     threshold-and-pending path.  A workgroup owns a contiguous run of tiles and computes, for their scores alone, the tile before and
+//     the tile after its run where they exist; those scores have the same bits in every workgroup, so no workgroup talks to another.  The
+//     sorted candidates go to the index's own buffers; index_merge_kernel (run_scan_passes) finishes the query.  LDS: index_scan_kernel's
+//     125 184 B + two more score planes = 158 464 B (opted in per device).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <mutex>
 #include <string>
 
 #include "capi_internal.h"
 #include "device_common.h"
 #include "hip_gate.h"
+#include "index_scan.h"
 #include "topm_select.h"
 
 namespace {
 
-constexpr int KC = 128;   // k-step of the scan; slab and query rows are padded to a multiple of it
-constexpr int TILE = 64;  // rows per tile: 4 waves x 16 rows
-constexpr int QP = 64;    // queries per scan pass
-constexpr int QS_LD = KC + 4;
-constexpr int S_LD = TILE + 1;
-constexpr int PLANE = QP * S_LD;  // words of one tile's scores; a multiple of 64, so the planes share their bank phase
+using bn::scan::KC;
+using bn::scan::PLANE;
+using bn::scan::QS_LD;
+using bn::scan::S_LD;
+using bn::scan::TILE;
+constexpr int QP = bn::scan::LP;  // queries per scan pass
 constexpr int RING = 3;           // tiles whose scores are kept: the judged one and its two neighbours
 static_assert(BN_PEAK_RADIUS_MAX <= TILE, "a row's neighbours must lie in its own tile and the two adjacent ones");
-static_assert(PLANE % 64 == 0, "the neighbour reads rely on planes of equal bank phase");
 
 using bn::floatx4;
 using bn::topm::Cand;
@@ -48,9 +48,7 @@ using bn::topm::PEND;
 using bn::topm::wave_sync;
 using Ord = bn::topm::ScoreDesc;  // the search's order: score descending, ties by id ascending
 
-constexpr size_t PEAKS_LDS = (size_t)QP * QS_LD * 4 + (size_t)RING * PLANE * 4 + (size_t)QP * PEND * sizeof(Cand) + 4 * MMAX * sizeof(Cand) +
-                             QP * sizeof(Cand) + 2 * QP * sizeof(int);
-static_assert(PEAKS_LDS <= 160 * 1024, "gfx950 has 160 KB of LDS per workgroup");
+constexpr size_t PEAKS_LDS = bn::scan::Layout<RING>::BYTES;  // index_scan_kernel's + two more score planes
 
 // Scan of one pass (nq <= QP queries, QB = ceil(nq / 16) query blocks), R = peak_radius in 1..TILE.  Workgroup g owns tiles
 // [g * tiles_per_wg, ...) and computes one tile more on either side where the index has one.  Operands as in index_scan_kernel: lane l
@@ -61,14 +59,15 @@ __global__ __launch_bounds__(256) void peaks_scan_kernel(const float *__restrict
                                                          uint32_t dpad, const float *__restrict__ q, const uint8_t *__restrict__ qvalid, int nq,
                                                          const uint32_t *__restrict__ qid, int64_t radius, int R, int M, uint32_t tiles_per_wg,
                                                          Cand *__restrict__ cand, int *__restrict__ cand_len) {
-    extern __shared__ __align__(16) float pk_lds[];
-    float *Qs = pk_lds;                                          // [QP][QS_LD]: the queries' current k chunk
-    float *S = Qs + QP * QS_LD;                                  // [RING][QP][S_LD]: scores of tile t in plane t mod 3, -inf where not eligible
-    Cand *pend = reinterpret_cast<Cand *>(S + RING * PLANE);     // [QP][PEND]
-    Cand *scratch = pend + QP * PEND;                            // [4][MMAX]
-    Cand *thr = scratch + 4 * MMAX;                              // [QP]
-    int *len = reinterpret_cast<int *>(thr + QP);                // [QP]
-    int *pn = len + QP;                                          // [QP]
+    extern __shared__ __align__(16) char pk_lds[];
+    using L = bn::scan::Layout<RING>;                              // the shared layout with three score planes
+    float *Qs = reinterpret_cast<float *>(pk_lds + L::B);         // [QP][QS_LD]: the queries' current k chunk
+    float *S = reinterpret_cast<float *>(pk_lds + L::S);          // [RING][QP][S_LD]: scores of tile t in plane t mod 3, -inf where not eligible
+    Cand *pend = reinterpret_cast<Cand *>(pk_lds + L::PENDING);   // [QP][PEND]
+    Cand *scratch = reinterpret_cast<Cand *>(pk_lds + L::SCRATCH);  // [4][MMAX]
+    Cand *thr = reinterpret_cast<Cand *>(pk_lds + L::THR);        // [QP]
+    int *len = reinterpret_cast<int *>(pk_lds + L::LEN);          // [QP]
+    int *pn = reinterpret_cast<int *>(pk_lds + L::PN);            // [QP]
 
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int r16 = lane & 15, h = lane >> 4;
@@ -231,70 +230,31 @@ __global__ __launch_bounds__(256) void peaks_scan_kernel(const float *__restrict
     }
 }
 
-std::mutex g_lds_mu;
-uint64_t g_lds_ready = 0;  // devices (ordinal < 64) on which the scan kernels may use PEAKS_LDS bytes
+bn::LdsOptIn g_scan_lds;
 
-// the > 64 KB LDS opt-in of the scan kernels, once per device (under the capture gate: it may not overlap a capture)
-hipError_t prepare_scan(int dev) {
-    std::lock_guard<std::mutex> lk(g_lds_mu);
-    if (dev < 64 && ((g_lds_ready >> dev) & 1)) return hipSuccess;
-    bn::gated::Shared g;
-    const void *ks[] = {reinterpret_cast<const void *>(peaks_scan_kernel<1>), reinterpret_cast<const void *>(peaks_scan_kernel<2>),
-                        reinterpret_cast<const void *>(peaks_scan_kernel<3>), reinterpret_cast<const void *>(peaks_scan_kernel<4>)};
-    for (const void *k : ks) {
-        hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PEAKS_LDS);
-        if (e != hipSuccess) return e;
-    }
-    if (dev < 64) g_lds_ready |= 1ull << dev;
-    return hipSuccess;
-}
-
-using bn::check_launch;
 using bn::set_last_error;
 
-// bn_index_search's refusals of its arguments, in its order, and the radius; none needs the index or a device
+// bn_index_search's refusals of its arguments, in its order, with the radius before the null arguments; none needs the index or a device
 bn_status check_args(const void *queries, size_t n_queries, size_t peak_radius, size_t top_m, size_t m_stride, const uint64_t *id_out,
                      const float *score_out, const uint32_t *count_out) {
-    if (top_m < 1 || top_m > (size_t)MMAX) return set_last_error(BN_ERR_INVALID_ARG, "top_m must be in 1..256, got " + std::to_string(top_m));
-    if (m_stride < top_m) return set_last_error(BN_ERR_INVALID_ARG, "m_stride < top_m");
+    if (bn_status st = bn::check_top_m(top_m, m_stride); st != BN_OK) return st;
     if (peak_radius > BN_PEAK_RADIUS_MAX)
         return set_last_error(BN_ERR_INVALID_ARG, "peak_radius must be in 0.." + std::to_string(BN_PEAK_RADIUS_MAX) + ", got " + std::to_string(peak_radius));
-    if (n_queries && (!queries || !id_out || !score_out || !count_out)) return set_last_error(BN_ERR_INVALID_ARG, "null argument");
-    return BN_OK;
-}
-
-template <int QB>
-void launch_scan(const bn::IndexScan &x, uint32_t n_wg, uint32_t tpw, const float *d_q, const uint8_t *d_qvalid, int np, const uint32_t *d_qid,
-                 int64_t radius, int R, int M) {
-    hipLaunchKernelGGL(peaks_scan_kernel<QB>, dim3(n_wg), dim3(256), PEAKS_LDS, x.stream, x.slab, x.valid, (uint32_t)x.size, (uint32_t)x.dpad, d_q, d_qvalid,
-                       np, d_qid, d_qid ? radius : (int64_t)-1, R, M, tpw, x.d_cand, x.d_cand_len);
+    return bn::check_search_buffers(queries, n_queries, id_out, score_out, count_out);
 }
 
 // the scan + merge passes over the nq staged queries (nq <= out_lists, the index not empty), results into the index's pinned mirrors;
 // synchronous.  The tiles are split among the workgroups as bn_index_search splits them: the result does not depend on the split, and
 // the two halo tiles cost the least time where a workgroup's run is shortest
 bn_status run_search(const bn::IndexScan &x, size_t nq, const float *d_q, const uint8_t *d_qvalid, const uint32_t *d_qid, int64_t radius, int R, int M) {
-    const uint32_t n_tiles = (uint32_t)((x.size + TILE - 1) / TILE);
-    const uint32_t tpw = (n_tiles + x.max_wg - 1) / x.max_wg;
-    const uint32_t n_wg = (n_tiles + tpw - 1) / tpw;
-    for (size_t p0 = 0; p0 < nq; p0 += QP) {
-        const int np = (int)std::min<size_t>(QP, nq - p0);
-        const float *q = d_q + p0 * x.dpad;
-        const uint32_t *qid = d_qid ? d_qid + p0 : nullptr;
-        switch ((np + 15) / 16) {
-            case 1: launch_scan<1>(x, n_wg, tpw, q, d_qvalid + p0, np, qid, radius, R, M); break;
-            case 2: launch_scan<2>(x, n_wg, tpw, q, d_qvalid + p0, np, qid, radius, R, M); break;
-            case 3: launch_scan<3>(x, n_wg, tpw, q, d_qvalid + p0, np, qid, radius, R, M); break;
-            default: launch_scan<4>(x, n_wg, tpw, q, d_qvalid + p0, np, qid, radius, R, M); break;
-        }
-        bn_status st = check_launch("peaks scan");
-        if (st != BN_OK) return st;
-        if ((st = bn::index_enqueue_merge(x.stream, x.d_cand, x.d_cand_len, (size_t)np, (int)n_wg, M, x.d_out + p0 * M, x.d_count + p0)) != BN_OK) return st;
-    }
-    BN_HIP_TRY(hipMemcpyAsync(x.h_out, x.d_out, nq * M * sizeof(Cand), hipMemcpyDeviceToHost, x.stream));
-    BN_HIP_TRY(hipMemcpyAsync(x.h_count, x.d_count, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, x.stream));
-    BN_HIP_TRY(hipStreamSynchronize(x.stream));
-    return BN_OK;
+    const bn::WgSplit sp = bn::split_tiles((uint32_t)((x.size + TILE - 1) / TILE), x.max_wg);
+    return bn::run_scan_passes(x, nq, sp.n_wg, M, "peaks scan", [&](size_t p0, int np) {
+        bn::by_blocks(np, [&](auto qb) {
+            hipLaunchKernelGGL(peaks_scan_kernel<decltype(qb)::value>, dim3(sp.n_wg), dim3(256), PEAKS_LDS, x.stream, x.slab, x.valid, (uint32_t)x.size,
+                               (uint32_t)x.dpad, d_q + p0 * x.dpad, d_qvalid + p0, np, d_qid ? d_qid + p0 : nullptr, d_qid ? radius : (int64_t)-1, R, M,
+                               sp.tiles_per_wg, x.d_cand, x.d_cand_len);
+        });
+    });
 }
 
 // by_id: the queries are the stored rows query_ids, otherwise the host rows `queries`
@@ -317,7 +277,8 @@ bn_status search(bn_index *ix, bool by_id, const float *queries, const uint64_t 
     }
     bn::IndexScan x;
     if ((st = bn::index_scan_state(ix, &x)) != BN_OK) return st;
-    BN_HIP_TRY(prepare_scan(x.device));
+    BN_HIP_TRY(g_scan_lds.prepare(x.device, {{(const void *)peaks_scan_kernel<1>, PEAKS_LDS}, {(const void *)peaks_scan_kernel<2>, PEAKS_LDS},
+                                              {(const void *)peaks_scan_kernel<3>, PEAKS_LDS}, {(const void *)peaks_scan_kernel<4>, PEAKS_LDS}}));
     for (size_t q0 = 0; q0 < n_queries; q0 += x.out_lists) {
         const size_t nq = std::min(x.out_lists, n_queries - q0);
         const float *d_q = nullptr;
@@ -327,14 +288,7 @@ bn_status search(bn_index *ix, bool by_id, const float *queries, const uint64_t 
         else st = bn::index_stage_queries(ix, queries + q0 * x.dim, nq, &d_q, &d_qvalid);
         if (st != BN_OK) return st;
         if ((st = run_search(x, nq, d_q, d_qvalid, d_qid, radius, (int)peak_radius, (int)top_m)) != BN_OK) return st;
-        for (size_t i = 0; i < nq; i++) {
-            const uint32_t c = x.h_count[i];
-            count_out[q0 + i] = c;
-            for (uint32_t j = 0; j < c; j++) {
-                id_out[(q0 + i) * m_stride + j] = x.h_out[i * top_m + j].id;
-                score_out[(q0 + i) * m_stride + j] = x.h_out[i * top_m + j].s;
-            }
-        }
+        bn::scatter_results(x.h_out, x.h_count, nq, top_m, m_stride, id_out + q0 * m_stride, score_out + q0 * m_stride, count_out + q0);
     }
     return BN_OK;
 }

@@ -12,27 +12,29 @@
 //     that beats the class's running M-th candidate joins a pending list; pending lists are merged by rank into the
 //     workgroup's running top-M.  A candidate carries the logit itself; the order derives its key from it (topm_select.h:
 //     ScoreDesc for TOP, AbsAsc for UNCERTAIN).  Out: [workgroups x classes x M] candidates; no [classes x rows] matrix exists.
-//   * rank_merge_kernel -- one wave per class merges the workgroups' sorted lists into the final top-M.
+//     LDS: index_scan_kernel's constants and layout (index_scan.h).
+//   * rank_merge_kernel -- UNCERTAIN: one wave per class merges the workgroups' sorted lists into the final top-M.  TOP's order
+//     is the search's, and index_merge_kernel merges it.
 // The scan runs on the index's stream and borrows the search's candidate and result buffers (one thread at a time per index).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <mutex>
 #include <string>
 #include <vector>
 
 #include "capi_internal.h"
 #include "device_common.h"
 #include "hip_gate.h"
+#include "index_scan.h"
 #include "topm_select.h"
 
 namespace {
 
-constexpr int KC = 128;   // k-step: the slab's and the head's rows are padded to a multiple of it
-constexpr int TILE = 64;  // rows per workgroup tile: 4 waves x 16 rows
-constexpr int CP = 64;    // classes per scan pass
-constexpr int WS_LD = KC + 4;
-constexpr int S_LD = TILE + 1;
+using bn::scan::KC;
+using bn::scan::S_LD;
+using bn::scan::TILE;
+constexpr int CP = bn::scan::LP;        // classes per scan pass
+constexpr int WS_LD = bn::scan::QS_LD;  // words of a class's k chunk in LDS
 
 using bn::floatx4;
 using bn::topm::Cand;
@@ -42,8 +44,7 @@ using bn::topm::MMAX;
 using bn::topm::PEND;
 using bn::topm::wave_sync;
 
-constexpr size_t SCAN_LDS = (size_t)CP * WS_LD * 4 + (size_t)CP * S_LD * 4 + (size_t)CP * PEND * sizeof(Cand) + 4 * MMAX * sizeof(Cand) +
-                            CP * sizeof(Cand) + 2 * CP * sizeof(int);
+constexpr size_t SCAN_LDS = bn::scan::Layout<1>::BYTES;
 
 template <uint32_t MODE>
 struct OrderOf {
@@ -69,14 +70,15 @@ __global__ __launch_bounds__(256) void rank_scan_kernel(const float *__restrict_
                                                         uint32_t tile_lo, uint32_t tile_hi, uint32_t tiles_per_wg, Cand *__restrict__ cand,
                                                         int *__restrict__ cand_len) {
     using Ord = typename OrderOf<MODE>::type;
-    extern __shared__ __align__(16) float rank_lds[];
-    float *Ws = rank_lds;                                    // [CP][WS_LD]: the classes' current k chunk
-    float *S = Ws + CP * WS_LD;                              // [CP][S_LD]: logits of the current tile
-    Cand *pend = reinterpret_cast<Cand *>(S + CP * S_LD);    // [CP][PEND]
-    Cand *scratch = pend + CP * PEND;                        // [4][MMAX]
-    Cand *thr = scratch + 4 * MMAX;                          // [CP]
-    int *len = reinterpret_cast<int *>(thr + CP);            // [CP]
-    int *pn = len + CP;                                      // [CP]
+    extern __shared__ __align__(16) char rank_lds[];
+    using L = bn::scan::Layout<1>;
+    float *Ws = reinterpret_cast<float *>(rank_lds + L::B);             // [CP][WS_LD]: the classes' current k chunk
+    float *S = reinterpret_cast<float *>(rank_lds + L::S);              // [CP][S_LD]: logits of the current tile
+    Cand *pend = reinterpret_cast<Cand *>(rank_lds + L::PENDING);       // [CP][PEND]
+    Cand *scratch = reinterpret_cast<Cand *>(rank_lds + L::SCRATCH);    // [4][MMAX]
+    Cand *thr = reinterpret_cast<Cand *>(rank_lds + L::THR);            // [CP]
+    int *len = reinterpret_cast<int *>(rank_lds + L::LEN);              // [CP]
+    int *pn = reinterpret_cast<int *>(rank_lds + L::PN);                // [CP]
 
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int r16 = lane & 15, h = lane >> 4;
@@ -191,11 +193,11 @@ __global__ __launch_bounds__(256) void rank_scan_kernel(const float *__restrict_
     }
 }
 
-// one wave per class: the workgroups' sorted lists -> the final top-M (out [nc][M], count [nc])
-template <uint32_t MODE>
+// one wave per class: the workgroups' sorted lists -> the final top-M (out [nc][M], count [nc]) in UNCERTAIN's order; TOP's is the
+// search's own, and index_merge_kernel (index_enqueue_merge) merges it
 __global__ __launch_bounds__(64) void rank_merge_kernel(const Cand *__restrict__ cand, const int *__restrict__ cand_len, int n_wg, int M,
                                                         Cand *__restrict__ out, uint32_t *__restrict__ count) {
-    bn::topm::merge_lists<typename OrderOf<MODE>::type>(cand, cand_len, CP, n_wg, M, out, count);
+    bn::topm::merge_lists<bn::topm::AbsAsc>(cand, cand_len, CP, n_wg, M, out, count);
 }
 
 template <uint32_t MODE>
@@ -209,21 +211,16 @@ const void *scan_of(int cb) {
 }
 const void *scan_of(uint32_t mode, int cb) { return mode == BN_RANK_UNCERTAIN ? scan_of<BN_RANK_UNCERTAIN>(cb) : scan_of<BN_RANK_TOP>(cb); }
 
-std::mutex g_lds_mu;
-uint64_t g_lds_ready = 0;  // devices (ordinal < 64) on which the scan kernels may use SCAN_LDS bytes
+bn::LdsOptIn g_scan_lds;
+hipError_t opt_in_scan(int dev) {
+    return g_scan_lds.prepare(dev, {{scan_of(BN_RANK_TOP, 1), SCAN_LDS}, {scan_of(BN_RANK_TOP, 2), SCAN_LDS}, {scan_of(BN_RANK_TOP, 3), SCAN_LDS},
+                                    {scan_of(BN_RANK_TOP, 4), SCAN_LDS}, {scan_of(BN_RANK_UNCERTAIN, 1), SCAN_LDS}, {scan_of(BN_RANK_UNCERTAIN, 2), SCAN_LDS},
+                                    {scan_of(BN_RANK_UNCERTAIN, 3), SCAN_LDS}, {scan_of(BN_RANK_UNCERTAIN, 4), SCAN_LDS}});
+}
 
-// the > 64 KB LDS opt-in of the scan kernels, once per device (under the capture gate: it may not overlap a capture)
-hipError_t prepare_scan(int dev) {
-    std::lock_guard<std::mutex> lk(g_lds_mu);
-    if (dev < 64 && ((g_lds_ready >> dev) & 1)) return hipSuccess;
-    bn::gated::Shared g;
-    for (uint32_t mode : {BN_RANK_TOP, BN_RANK_UNCERTAIN})
-        for (int cb = 1; cb <= 4; cb++) {
-            hipError_t e = hipFuncSetAttribute(scan_of(mode, cb), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SCAN_LDS);
-            if (e != hipSuccess) return e;
-        }
-    if (dev < 64) g_lds_ready |= 1ull << dev;
-    return hipSuccess;
+bn_status enqueue_abs_merge(hipStream_t stream, const Cand *cand, const int *cand_len, size_t n_classes, int n_wg, int M, Cand *out, uint32_t *count) {
+    hipLaunchKernelGGL(rank_merge_kernel, dim3((unsigned)n_classes), dim3(64), 0, stream, cand, cand_len, n_wg, M, out, count);
+    return bn::check_launch("rank merge");
 }
 
 using bn::check_launch;
@@ -238,8 +235,7 @@ extern "C" bn_status bn_head_rank_index(const bn_head *h, bn_index *x, uint32_t 
     if (!x) return set_last_error(BN_ERR_INVALID_ARG, "null index");
     if (!id_out || !logit_out || !count_out || (n_exclude && !exclude_ids)) return set_last_error(BN_ERR_INVALID_ARG, "null argument");
     if (mode != BN_RANK_TOP && mode != BN_RANK_UNCERTAIN) return set_last_error(BN_ERR_INVALID_ARG, "unknown mode " + std::to_string(mode));
-    if (top_m < 1 || top_m > (size_t)MMAX) return set_last_error(BN_ERR_INVALID_ARG, "top_m must be in 1..256, got " + std::to_string(top_m));
-    if (m_stride < top_m) return set_last_error(BN_ERR_INVALID_ARG, "m_stride < top_m");
+    if (bn_status ast = bn::check_top_m(top_m, m_stride); ast != BN_OK) return ast;
     const bn::HeadView hv = bn::head_view(h);
     const size_t size = bn_index_size(x), dim = bn_index_dim(x);
     if (!(hv.flags & BN_HEAD_L2NORM))
@@ -260,7 +256,7 @@ extern "C" bn_status bn_head_rank_index(const bn_head *h, bn_index *x, uint32_t 
         std::fill(count_out, count_out + C, 0u);
         return BN_OK;
     }
-    BN_HIP_TRY(prepare_scan(s.device));
+    BN_HIP_TRY(opt_in_scan(s.device));
     bn::Scratch bufs;  // waits for the stream before it frees the mask
     bufs.stream = s.stream;
     const uint8_t *mask = s.valid;
@@ -277,37 +273,22 @@ extern "C" bn_status bn_head_rank_index(const bn_head *h, bn_index *x, uint32_t 
         mask = d_mask;
     }
     // the grid rule: the range's tiles in contiguous runs, at most one workgroup per compute unit
-    const uint32_t tile_lo = id_lo / TILE, tile_hi = (id_hi + TILE - 1) / TILE, n_tiles = tile_hi - tile_lo;
-    uint32_t tpw = (n_tiles + s.max_wg - 1) / s.max_wg, n_wg = (n_tiles + tpw - 1) / tpw;
-    const uint32_t dpad = (uint32_t)s.dpad;
-    int Mi = (int)M, n_wg_i = (int)n_wg;
+    uint32_t lo = id_lo, hi = id_hi, dpad = (uint32_t)s.dpad, tile_lo = id_lo / TILE, tile_hi = (id_hi + TILE - 1) / TILE;
+    bn::WgSplit sp = bn::split_tiles(tile_hi - tile_lo, s.max_wg);
+    int Mi = (int)M;
     for (size_t c0 = 0; c0 < C; c0 += s.out_lists) {
         const size_t nc = std::min(s.out_lists, C - c0);
-        for (size_t p0 = 0; p0 < nc; p0 += CP) {
-            int np = (int)std::min<size_t>(CP, nc - p0);
-            const float *W = hv.d_W + (c0 + p0) * hv.dpad, *b = hv.d_b + c0 + p0;
-            uint32_t lo = id_lo, hi = id_hi, d = dpad, tl = tile_lo, th = tile_hi;
-            void *scan_args[] = {(void *)&s.slab, (void *)&mask, &lo, &hi, &d, (void *)&W, (void *)&b, &np, &Mi, &tl, &th, &tpw, &s.d_cand, &s.d_cand_len};
-            BN_HIP_TRY(hipLaunchKernel(scan_of(mode, (np + 15) / 16), dim3(n_wg), dim3(256), scan_args, SCAN_LDS, s.stream));
-            Cand *out = s.d_out + p0 * M;
-            uint32_t *cnt = s.d_count + p0;
-            if (mode == BN_RANK_UNCERTAIN)
-                hipLaunchKernelGGL(rank_merge_kernel<BN_RANK_UNCERTAIN>, dim3(np), dim3(64), 0, s.stream, s.d_cand, s.d_cand_len, n_wg_i, Mi, out, cnt);
-            else
-                hipLaunchKernelGGL(rank_merge_kernel<BN_RANK_TOP>, dim3(np), dim3(64), 0, s.stream, s.d_cand, s.d_cand_len, n_wg_i, Mi, out, cnt);
-            if ((st = check_launch("rank merge")) != BN_OK) return st;
-        }
-        BN_HIP_TRY(hipMemcpyAsync(s.h_out, s.d_out, nc * M * sizeof(Cand), hipMemcpyDeviceToHost, s.stream));
-        BN_HIP_TRY(hipMemcpyAsync(s.h_count, s.d_count, nc * sizeof(uint32_t), hipMemcpyDeviceToHost, s.stream));
-        BN_HIP_TRY(hipStreamSynchronize(s.stream));
-        for (size_t i = 0; i < nc; i++) {
-            const uint32_t n = s.h_count[i];
-            count_out[c0 + i] = n;
-            for (uint32_t j = 0; j < n; j++) {
-                id_out[(c0 + i) * m_stride + j] = s.h_out[i * M + j].id;
-                logit_out[(c0 + i) * m_stride + j] = s.h_out[i * M + j].s;
-            }
-        }
+        st = bn::run_scan_passes(
+            s, nc, sp.n_wg, Mi, "rank scan",
+            [&](size_t p0, int np) {
+                const float *W = hv.d_W + (c0 + p0) * hv.dpad, *b = hv.d_b + c0 + p0;
+                void *scan_args[] = {(void *)&s.slab, (void *)&mask, &lo, &hi, &dpad, (void *)&W, (void *)&b, &np, &Mi, &tile_lo, &tile_hi, &sp.tiles_per_wg,
+                                     &s.d_cand, &s.d_cand_len};
+                (void)hipLaunchKernel(scan_of(mode, (np + 15) / 16), dim3(sp.n_wg), dim3(256), scan_args, SCAN_LDS, s.stream);  // checked by the caller
+            },
+            mode == BN_RANK_UNCERTAIN ? enqueue_abs_merge : bn::index_enqueue_merge);
+        if (st != BN_OK) return st;
+        bn::scatter_results(s.h_out, s.h_count, nc, M, m_stride, id_out + c0 * m_stride, logit_out + c0 * m_stride, count_out + c0);
     }
     return BN_OK;
 }

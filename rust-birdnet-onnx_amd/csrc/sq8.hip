@@ -23,7 +23,6 @@
 #include <algorithm>
 #include <cstring>
 #include <memory>
-#include <mutex>
 #include <string>
 #include <vector>
 
@@ -235,23 +234,7 @@ __global__ __launch_bounds__(256) void sq8_members_kernel(const Cand *__restrict
     for (uint32_t i = threadIdx.x; i < n; i += 256) members[(size_t)q * MMAX + i] = coarse[(size_t)q * refine + i].id;
 }
 
-std::mutex g_lds_mu;
-uint64_t g_lds_ready = 0;  // devices (ordinal < 64) on which the wide scan kernels may use their LDS
-
-// the > 64 KB LDS opt-in of the scan kernels, once per device (under the capture gate: it may not overlap a capture)
-hipError_t prepare_scan(int dev) {
-    std::lock_guard<std::mutex> lk(g_lds_mu);
-    if (dev < 64 && ((g_lds_ready >> dev) & 1)) return hipSuccess;
-    bn::gated::Shared g;
-    const void *ks[] = {reinterpret_cast<const void *>(sq8_scan_kernel<1>), reinterpret_cast<const void *>(sq8_scan_kernel<2>),
-                        reinterpret_cast<const void *>(sq8_scan_kernel<3>), reinterpret_cast<const void *>(sq8_scan_kernel<4>)};
-    for (int i = 0; i < 4; i++) {
-        hipError_t e = hipFuncSetAttribute(ks[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)scan_lds(i + 1));
-        if (e != hipSuccess) return e;
-    }
-    if (dev < 64) g_lds_ready |= 1ull << dev;
-    return hipSuccess;
-}
+bn::LdsOptIn g_scan_lds;
 
 }  // namespace
 
@@ -303,9 +286,8 @@ bn_status check_search_args(size_t n_queries, size_t refine, size_t top_m, size_
     if (refine < 1 || refine > (size_t)MMAX) return set_last_error(BN_ERR_INVALID_ARG, "refine must be in 1..256, got " + std::to_string(refine));
     if (top_m < 1 || top_m > refine)
         return set_last_error(BN_ERR_INVALID_ARG, "top_m must be in 1..refine (" + std::to_string(refine) + "), got " + std::to_string(top_m));
-    if (m_stride < top_m) return set_last_error(BN_ERR_INVALID_ARG, "m_stride < top_m");
-    if (n_queries && (!queries || !id_out || !score_out || !count_out)) return set_last_error(BN_ERR_INVALID_ARG, "null argument");
-    return BN_OK;
+    if (bn_status st = bn::check_top_m(top_m, m_stride); st != BN_OK) return st;  // top_m <= refine <= 256: the stride's refusal
+    return bn::check_search_buffers(queries, n_queries, id_out, score_out, count_out);
 }
 
 template <int QB>
@@ -324,17 +306,11 @@ bn_status run_search(bn_sq8 *v, const bn::IndexScan &s, size_t nq, const float *
                        (uint32_t)v->dpad, v->d_qcodes, v->d_qscales);
     bn_status st = check_launch("sq8 encode");
     if (st != BN_OK) return st;
-    const uint32_t n_tiles = (uint32_t)((v->covered + TILE - 1) / TILE);
-    const uint32_t tpw = (uint32_t)((n_tiles + v->wg_max - 1) / v->wg_max);
-    const uint32_t n_wg = (n_tiles + tpw - 1) / tpw;
+    const bn::WgSplit sp = bn::split_tiles((uint32_t)((v->covered + TILE - 1) / TILE), v->wg_max);
+    const uint32_t tpw = sp.tiles_per_wg, n_wg = sp.n_wg;
     for (size_t p0 = 0; p0 < nq; p0 += QP) {
         const int np = (int)std::min<size_t>(QP, nq - p0);
-        switch ((np + 15) / 16) {
-            case 1: launch_scan<1>(v, s, n_wg, tpw, p0, np, d_qvalid, d_qid, radius, R); break;
-            case 2: launch_scan<2>(v, s, n_wg, tpw, p0, np, d_qvalid, d_qid, radius, R); break;
-            case 3: launch_scan<3>(v, s, n_wg, tpw, p0, np, d_qvalid, d_qid, radius, R); break;
-            default: launch_scan<4>(v, s, n_wg, tpw, p0, np, d_qvalid, d_qid, radius, R); break;
-        }
+        bn::by_blocks(np, [&](auto qb) { launch_scan<decltype(qb)::value>(v, s, n_wg, tpw, p0, np, d_qvalid, d_qid, radius, R); });
         if ((st = check_launch("sq8 scan")) != BN_OK) return st;
         if ((st = bn::ivf_enqueue_merge(s.stream, v->d_cand, v->d_cand_len, (size_t)np, n_wg, R, v->d_coarse + p0 * R, v->d_ccount + p0)) != BN_OK) return st;
     }
@@ -387,14 +363,7 @@ bn_status search(bn_sq8 *v, const float *queries, const uint64_t *query_ids, siz
         else st = bn::index_stage_queries(v->x, queries + q0 * v->dim, nq, &d_q, &d_qvalid);
         if (st != BN_OK) return st;
         if ((st = run_search(v, s, nq, d_q, d_qvalid, d_qid, radius, (int)refine, (int)top_m)) != BN_OK) return st;
-        for (size_t i = 0; i < nq; i++) {
-            const uint32_t n = s.h_count[i];
-            count_out[q0 + i] = n;
-            for (uint32_t j = 0; j < n; j++) {
-                id_out[(q0 + i) * m_stride + j] = s.h_out[i * top_m + j].id;
-                score_out[(q0 + i) * m_stride + j] = s.h_out[i * top_m + j].s;
-            }
-        }
+        bn::scatter_results(s.h_out, s.h_count, nq, top_m, m_stride, id_out + q0 * m_stride, score_out + q0 * m_stride, count_out + q0);
         if (!cand_out && !cand_count_out) continue;
         ccount.resize(nq);
         BN_HIP_TRY(bn::gated::Memcpy(ccount.data(), v->d_ccount, nq * sizeof(uint32_t), hipMemcpyDeviceToHost));
@@ -422,7 +391,8 @@ bn_status bn_sq8_build(bn_index *x, bn_sq8 **out) {
     bn::IndexScan s;
     bn_status st = bn::index_scan_state(x, &s);
     if (st != BN_OK) return st;
-    BN_HIP_TRY(prepare_scan(s.device));
+    BN_HIP_TRY(g_scan_lds.prepare(s.device, {{(const void *)sq8_scan_kernel<1>, scan_lds(1)}, {(const void *)sq8_scan_kernel<2>, scan_lds(2)},
+                                             {(const void *)sq8_scan_kernel<3>, scan_lds(3)}, {(const void *)sq8_scan_kernel<4>, scan_lds(4)}}));
     std::unique_ptr<bn_sq8, void (*)(bn_sq8 *)> v(new bn_sq8, release);
     v->x = x;
     v->device = s.device;

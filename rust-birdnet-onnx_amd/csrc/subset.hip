@@ -11,33 +11,35 @@
 //     position is a function of the data alone, never of an atomic or of timing, so the ids come out ascending and two selections
 //     of the same state give the same bytes.
 //   * subset_offsets_kernel -- one workgroup: the exclusive prefix sums of the blocks' counts (integers: exact), the total last.
-//   * subset_scan_kernel<QB> -- index_scan_kernel's tile loop over the list: 64 queries per pass in LDS, the exact-f32 MFMA
-//     v_mfma_f32_16x16x4_f32 with row = A operand and query = B operand, one accumulator per (query, row) over k ascending, so a score
-//     has bn_index_search's bits.  A tile's 64 rows are 64 consecutive list entries; the ids are fetched two tiles ahead of the rows
-//     they name, the row chunk one step ahead, and the id and validity a lane judges in the selection at the start of its tile.
-//     Lanes past the list's end read its last member and are masked by position.  Workgroup g owns a contiguous run of list tiles and leaves its sorted candidates in the index's own buffers; index_merge_kernel
-//     (index_enqueue_merge) finishes the query.  LDS: index_scan_kernel's 125 184 B (opted in per device).
+//   * subset_scan_kernel<QB> -- index_scan_kernel's tile loop written out again over the list: 64 queries per pass in
+//     LDS, the exact-f32 MFMA v_mfma_f32_16x16x4_f32 with row = A operand and query = B operand, one accumulator per (query, row) over k
+//     ascending, so a score has bn_index_search's bits.  The constants and the LDS layout are index_scan.h's; the loop is this file's
+//     own (as an instantiation of one templated body it measured slower: DESIGN.md).  A tile's 64 rows are 64 consecutive list entries;
+//     the ids are fetched two tiles ahead of the rows they name, the row chunk one step ahead, and the id and validity a lane judges in
+//     the selection at the start of its tile.  Lanes past the list's end read its last member and are masked by position.  Workgroup g
+//     owns a contiguous run of list tiles and leaves its sorted candidates in the index's own buffers; index_merge_kernel
+//     (run_scan_passes) finishes the query.  LDS: index_scan_kernel's 125 184 B (opted in per device).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstring>
 #include <memory>
-#include <mutex>
 #include <string>
 #include <vector>
 
 #include "capi_internal.h"
 #include "device_common.h"
 #include "hip_gate.h"
+#include "index_scan.h"
 #include "topm_select.h"
 
 namespace {
 
-constexpr int KC = 128;   // k-step of the scan; slab and query rows are padded to a multiple of it
-constexpr int TILE = 64;  // rows per tile: 4 waves x 16 rows
-constexpr int QP = 64;    // queries per scan pass
-constexpr int QS_LD = KC + 4;
-constexpr int S_LD = TILE + 1;
+using bn::scan::KC;
+using bn::scan::QS_LD;
+using bn::scan::S_LD;
+using bn::scan::TILE;
+constexpr int QP = bn::scan::LP;     // queries per scan pass
 constexpr uint32_t SEL_ROWS = 1024;  // ids per block of the selection: 4 waves x 4 groups of 64
 constexpr uint32_t MAP_WORDS = BN_INDEX_TAG_LIMIT / 32;
 
@@ -50,8 +52,7 @@ using bn::topm::PEND;
 using bn::topm::wave_sync;
 using Ord = bn::topm::ScoreDesc;  // the search's order: score descending, ties by id ascending
 
-constexpr size_t SCAN_LDS = (size_t)QP * QS_LD * 4 + (size_t)QP * S_LD * 4 + (size_t)QP * PEND * sizeof(Cand) + 4 * MMAX * sizeof(Cand) +
-                            QP * sizeof(Cand) + 2 * QP * sizeof(int);
+constexpr size_t SCAN_LDS = bn::scan::Layout<1>::BYTES;  // index_scan_kernel's
 
 // Block b: ids [first + b * SEL_ROWS, + SEL_ROWS) cut at `end`.  tags NULL: every tag is 0; admit NULL: tags are not tested.
 // SCATTER false: block_count[b] = the ids that pass.  SCATTER true: those ids, ascending, to ids_out[block_off[b] ..).
@@ -119,14 +120,15 @@ __global__ __launch_bounds__(256) void subset_scan_kernel(const float *__restric
                                                           uint32_t n, uint32_t dpad, const float *__restrict__ q, const uint8_t *__restrict__ qvalid, int nq,
                                                           const uint32_t *__restrict__ qid, int64_t radius, int M, uint32_t tiles_per_wg,
                                                           Cand *__restrict__ cand, int *__restrict__ cand_len) {
-    extern __shared__ __align__(16) float sub_lds[];
-    float *Qs = sub_lds;                                   // [QP][QS_LD]: the queries' current k chunk
-    float *S = Qs + QP * QS_LD;                            // [QP][S_LD]: scores of the current tile
-    Cand *pend = reinterpret_cast<Cand *>(S + QP * S_LD);  // [QP][PEND]
-    Cand *scratch = pend + QP * PEND;                      // [4][MMAX]
-    Cand *thr = scratch + 4 * MMAX;                        // [QP]
-    int *len = reinterpret_cast<int *>(thr + QP);          // [QP]
-    int *pn = len + QP;                                    // [QP]
+    extern __shared__ __align__(16) char sub_lds[];
+    using L = bn::scan::Layout<1>;                                  // index_scan_kernel's layout
+    float *Qs = reinterpret_cast<float *>(sub_lds + L::B);          // [QP][QS_LD]: the queries' current k chunk
+    float *S = reinterpret_cast<float *>(sub_lds + L::S);           // [QP][S_LD]: scores of the current tile
+    Cand *pend = reinterpret_cast<Cand *>(sub_lds + L::PENDING);    // [QP][PEND]
+    Cand *scratch = reinterpret_cast<Cand *>(sub_lds + L::SCRATCH);  // [4][MMAX]
+    Cand *thr = reinterpret_cast<Cand *>(sub_lds + L::THR);         // [QP]
+    int *len = reinterpret_cast<int *>(sub_lds + L::LEN);           // [QP]
+    int *pn = reinterpret_cast<int *>(sub_lds + L::PN);             // [QP]
 
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int r16 = lane & 15, h = lane >> 4;
@@ -262,22 +264,10 @@ __global__ __launch_bounds__(256) void subset_scan_kernel(const float *__restric
     }
 }
 
-std::mutex g_lds_mu;
-uint64_t g_lds_ready = 0;  // devices (ordinal < 64) on which the scan kernels may use SCAN_LDS bytes
-
-// the > 64 KB LDS opt-in of the scan kernels, once per device (under the capture gate: it may not overlap a capture)
-hipError_t prepare_scan(int dev) {
-    std::lock_guard<std::mutex> lk(g_lds_mu);
-    if (dev < 64 && ((g_lds_ready >> dev) & 1)) return hipSuccess;
-    bn::gated::Shared g;
-    const void *ks[] = {reinterpret_cast<const void *>(subset_scan_kernel<1>), reinterpret_cast<const void *>(subset_scan_kernel<2>),
-                        reinterpret_cast<const void *>(subset_scan_kernel<3>), reinterpret_cast<const void *>(subset_scan_kernel<4>)};
-    for (const void *k : ks) {
-        hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SCAN_LDS);
-        if (e != hipSuccess) return e;
-    }
-    if (dev < 64) g_lds_ready |= 1ull << dev;
-    return hipSuccess;
+bn::LdsOptIn g_scan_lds;
+hipError_t opt_in_scan(int dev) {
+    return g_scan_lds.prepare(dev, {{(const void *)subset_scan_kernel<1>, SCAN_LDS}, {(const void *)subset_scan_kernel<2>, SCAN_LDS},
+                                    {(const void *)subset_scan_kernel<3>, SCAN_LDS}, {(const void *)subset_scan_kernel<4>, SCAN_LDS}});
 }
 
 }  // namespace
@@ -303,53 +293,25 @@ void release(bn_subset *s) {
     delete s;
 }
 
-// bn_index_search's refusals, in its order, without the index
-bn_status check_search_args(const void *queries, size_t n_queries, size_t top_m, size_t m_stride, const uint64_t *id_out, const float *score_out,
-                            const uint32_t *count_out) {
-    if (top_m < 1 || top_m > (size_t)MMAX) return set_last_error(BN_ERR_INVALID_ARG, "top_m must be in 1..256, got " + std::to_string(top_m));
-    if (m_stride < top_m) return set_last_error(BN_ERR_INVALID_ARG, "m_stride < top_m");
-    if (n_queries && (!queries || !id_out || !score_out || !count_out)) return set_last_error(BN_ERR_INVALID_ARG, "null argument");
-    return BN_OK;
-}
-
-template <int QB>
-void launch_scan(const bn_subset *s, const bn::IndexScan &x, uint32_t n_wg, uint32_t tpw, const float *d_q, const uint8_t *d_qvalid, int np,
-                 const uint32_t *d_qid, int64_t radius, int M) {
-    hipLaunchKernelGGL(subset_scan_kernel<QB>, dim3(n_wg), dim3(256), SCAN_LDS, x.stream, x.slab, x.valid, s->d_ids, (uint32_t)s->n, (uint32_t)x.dpad, d_q,
-                       d_qvalid, np, d_qid, d_qid ? radius : (int64_t)-1, M, tpw, x.d_cand, x.d_cand_len);
-}
-
 // the scan + merge passes over the nq staged queries (nq <= out_lists, the subset not empty), results into the index's pinned
 // mirrors; synchronous.  The list's tiles are split among the workgroups as bn_index_search splits the slab's
 bn_status run_search(const bn_subset *s, const bn::IndexScan &x, size_t nq, const float *d_q, const uint8_t *d_qvalid, const uint32_t *d_qid, int64_t radius,
                      int M) {
-    const uint32_t n_tiles = (uint32_t)((s->n + TILE - 1) / TILE);
-    const uint32_t tpw = (n_tiles + x.max_wg - 1) / x.max_wg;
-    const uint32_t n_wg = (n_tiles + tpw - 1) / tpw;
-    for (size_t p0 = 0; p0 < nq; p0 += QP) {
-        const int np = (int)std::min<size_t>(QP, nq - p0);
-        const float *q = d_q + p0 * x.dpad;
-        const uint32_t *qid = d_qid ? d_qid + p0 : nullptr;
-        switch ((np + 15) / 16) {
-            case 1: launch_scan<1>(s, x, n_wg, tpw, q, d_qvalid + p0, np, qid, radius, M); break;
-            case 2: launch_scan<2>(s, x, n_wg, tpw, q, d_qvalid + p0, np, qid, radius, M); break;
-            case 3: launch_scan<3>(s, x, n_wg, tpw, q, d_qvalid + p0, np, qid, radius, M); break;
-            default: launch_scan<4>(s, x, n_wg, tpw, q, d_qvalid + p0, np, qid, radius, M); break;
-        }
-        bn_status st = check_launch("subset scan");
-        if (st != BN_OK) return st;
-        if ((st = bn::index_enqueue_merge(x.stream, x.d_cand, x.d_cand_len, (size_t)np, (int)n_wg, M, x.d_out + p0 * M, x.d_count + p0)) != BN_OK) return st;
-    }
-    BN_HIP_TRY(hipMemcpyAsync(x.h_out, x.d_out, nq * M * sizeof(Cand), hipMemcpyDeviceToHost, x.stream));
-    BN_HIP_TRY(hipMemcpyAsync(x.h_count, x.d_count, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, x.stream));
-    BN_HIP_TRY(hipStreamSynchronize(x.stream));
-    return BN_OK;
+    const bn::WgSplit sp = bn::split_tiles((uint32_t)((s->n + TILE - 1) / TILE), x.max_wg);
+    return bn::run_scan_passes(x, nq, sp.n_wg, M, "subset scan", [&](size_t p0, int np) {
+        bn::by_blocks(np, [&](auto qb) {
+            hipLaunchKernelGGL(subset_scan_kernel<decltype(qb)::value>, dim3(sp.n_wg), dim3(256), SCAN_LDS, x.stream, x.slab, x.valid, s->d_ids, (uint32_t)s->n,
+                               (uint32_t)x.dpad, d_q + p0 * x.dpad, d_qvalid + p0, np, d_qid ? d_qid + p0 : nullptr, d_qid ? radius : (int64_t)-1, M,
+                               sp.tiles_per_wg, x.d_cand, x.d_cand_len);
+        });
+    });
 }
 
 bn_status search(bn_subset *s, const float *queries, const uint64_t *query_ids, size_t n_queries, int64_t radius, size_t top_m, size_t m_stride,
                  uint64_t *id_out, float *score_out, uint32_t *count_out) {
-    bn_status st = check_search_args(queries ? (const void *)queries : (const void *)query_ids, n_queries, top_m, m_stride, id_out, score_out, count_out);
+    bn_status st = bn::check_top_m(top_m, m_stride);  // bn_index_search's refusals, in its order, without the index
     if (st != BN_OK) return st;
+    if ((st = bn::check_search_buffers(queries ? (const void *)queries : (const void *)query_ids, n_queries, id_out, score_out, count_out)) != BN_OK) return st;
     if ((st = bn::require_any_device()) != BN_OK) return st;
     if (!s) return set_last_error(BN_ERR_INVALID_ARG, "null subset");
     if (query_ids) {
@@ -372,14 +334,7 @@ bn_status search(bn_subset *s, const float *queries, const uint64_t *query_ids, 
         else st = bn::index_stage_queries(s->x, queries + q0 * x.dim, nq, &d_q, &d_qvalid);
         if (st != BN_OK) return st;
         if ((st = run_search(s, x, nq, d_q, d_qvalid, d_qid, radius, (int)top_m)) != BN_OK) return st;
-        for (size_t i = 0; i < nq; i++) {
-            const uint32_t c = x.h_count[i];
-            count_out[q0 + i] = c;
-            for (uint32_t j = 0; j < c; j++) {
-                id_out[(q0 + i) * m_stride + j] = x.h_out[i * top_m + j].id;
-                score_out[(q0 + i) * m_stride + j] = x.h_out[i * top_m + j].s;
-            }
-        }
+        bn::scatter_results(x.h_out, x.h_count, nq, top_m, m_stride, id_out + q0 * m_stride, score_out + q0 * m_stride, count_out + q0);
     }
     return BN_OK;
 }
@@ -418,7 +373,7 @@ bn_status bn_subset_select(bn_index *x, const bn_index_filter *f, size_t struct_
     bn::IndexScan xs;
     bn_status st = bn::index_scan_state(x, &xs);
     if (st != BN_OK) return st;
-    BN_HIP_TRY(prepare_scan(xs.device));
+    BN_HIP_TRY(opt_in_scan(xs.device));
     std::unique_ptr<bn_subset, void (*)(bn_subset *)> s(nullptr, release);
     if (first == end) {
         if ((st = make_subset(x, xs.device, 0, s)) != BN_OK) return st;
@@ -472,7 +427,7 @@ bn_status bn_subset_from_ids(bn_index *x, const uint64_t *ids, size_t n, bn_subs
     bn::IndexScan xs;
     bn_status st = bn::index_scan_state(x, &xs);
     if (st != BN_OK) return st;
-    BN_HIP_TRY(prepare_scan(xs.device));
+    BN_HIP_TRY(opt_in_scan(xs.device));
     std::unique_ptr<bn_subset, void (*)(bn_subset *)> s(nullptr, release);
     if ((st = make_subset(x, xs.device, n, s)) != BN_OK) return st;
     if (n) {

@@ -1,6 +1,7 @@
-// Exact top-M selection shared by the scans that stream the index's slab (index.hip: cosine search; rank.hip: ranking by a head's
-// logits): the candidate, its strict total orders, the merge of a pending list into a sorted running list by rank, and the walk
-// that merges the workgroups' sorted lists into the final one.  Device code only; include from a .hip file.
+// Exact top-M selection shared by the scans that keep per-list candidates (index.hip: cosine search; rank.hip: ranking by a head's
+// logits; subset.hip, peaks.hip, ivf.hip, sq8.hip): the candidate, its strict total orders, the merge of a pending list into a sorted
+// running list by rank, and the walk that merges the workgroups' sorted lists into the final one.  Device code only; include from a
+// .hip file.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -368,3 +368,42 @@ def test_normalisation_commutes_with_a_power_of_two_scale(bn, dim):
         dead.add(np.ldexp(X, e))
         assert len(dead) == n and not dead.read().any() and not dead.search(Q, 4)[2].any(), e
         assert not dead.search_ids([0, n - 1], 4)[2].any(), e
+
+
+def test_the_four_scan_routes_give_a_vector_and_row_the_same_score_bits(bn):
+    """index_scan_kernel, subset_scan_kernel, peaks_scan_kernel and rank_scan_kernel each write out the same tile loop over one LDS
+    layout (csrc/index_scan.h): for the same (vector, row) each must give the bits bn_index_search gives.  General data, dim 130 (two k chunks, the second with a k
+    tail), many tiles per workgroup and a ragged last tile, 17 queries (two query blocks), M = 256.  No tolerance anywhere."""
+    require_many_tiles()
+    dim, nq, M = 130, 17, 256
+    rng = np.random.default_rng(130)
+    idx = bn.Index(0, dim, N)
+    for a, X in gaussian_chunks(rng, N, dim):
+        assert idx.add(X) == a
+    Q = rng.standard_normal((nq, dim), dtype=np.float32)
+    want = idx.search(Q, M)
+    assert np.all(want[2] == M)
+
+    everything = bn.Subset.select(idx)
+    assert len(everything) == N
+    assert_exact(everything.search(Q, M), want, "a subset over all rows")
+
+    # the peaks are some of the rows, in the search's order: a search over exactly those rows returns the same lists
+    ids, scores, counts = idx.search_peaks(Q, M, 1)
+    assert counts.min() > 0
+    for q in range(nq):
+        k = int(counts[q])
+        only = bn.Subset.from_ids(idx, np.sort(ids[q, :k]))
+        si, ss, sc = only.search(Q[q:q + 1], M)
+        assert sc[0] == k and np.array_equal(si[0, :k], ids[q, :k]) and ss[0, :k].tobytes() == scores[q, :k].tobytes(), ("peaks", q)
+        both = np.isin(ids[q, :k], want[0][q])            # and where a peak is among the search's own top M, directly
+        at = np.array([np.flatnonzero(want[0][q] == i)[0] for i in ids[q, :k][both]], dtype=np.int64)
+        assert both.any() and scores[q, :k][both].tobytes() == want[1][q][at].tobytes(), ("peaks in the top M", q)
+
+    # the head's weight rows are the query rows as the search stores them (normalised by the same kernel), its bias is zero
+    stored = bn.Index(0, dim, nq)
+    stored.add(Q)
+    head = bn.Head(0, stored.read(), np.zeros(nq, dtype=np.float32), l2norm=True)
+    ri, rl, rc = head.rank_index(idx, M)
+    assert np.array_equal(rc, want[2]) and np.array_equal(ri, want[0])
+    assert np.array_equal(rl, want[1]), "logits differ from the scores"      # ==: a logit is score + 0.0, so -0.0 may come back +0.0
