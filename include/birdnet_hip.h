@@ -449,7 +449,7 @@ bn_status bn_index_search(bn_index *x, const float *queries, size_t n_queries, s
 bn_status bn_index_search_ids(bn_index *x, const uint64_t *query_ids, size_t n_queries, int64_t exclude_radius,
                               size_t top_m, size_t m_stride, uint64_t *id_out, float *score_out, uint32_t *count_out);
 /* Row tags: every row carries one tag below BN_INDEX_TAG_LIMIT, 0 until set: a source, a site, a species, a tombstone -- the caller's
- * meaning.  bn_subset_select (below) chooses rows by tag; NOTHING ELSE reads a tag: bn_index_search, bn_index_search_ids, bn_ivf_*,
+ * meaning.  bn_subset_select (below) chooses rows by tag and a match (bn_ctx_attach_index, bn_index_match) returns the tags of its hits; NOTHING ELSE reads a tag: bn_index_search, bn_index_search_ids, bn_ivf_*,
  * bn_sq8_*, bn_head_fit_index, bn_head_rank_index, bn_index_assign, bn_index_cluster and bn_index_save behave the same, bit for bit, with
  * and without tags.  The plane (two bytes per row of capacity) is allocated by the first bn_index_set_tags / bn_index_fill_tags; an index
  * that never tags pays nothing, and an absent plane reads as zeros.  The index file has no tags: it stays format version 1 and a loaded
@@ -578,6 +578,55 @@ bn_status bn_ctx_attach_head(bn_ctx *c, bn_head *h, size_t top_k, int32_t has_mi
 /* pinned host views of the last step's head results: logits [batch, n_classes], idx / conf [batch, k_stride], count [batch] */
 bn_status bn_step_head_results(const bn_ctx *c, const float **logits, const uint32_t **idx, const float **conf,
                                const uint32_t **count, size_t *k_stride, size_t *n_classes);
+
+/*
+ * Matching a step against an attached index (a watch list): a library of labelled example rows (an index with row tags) searched
+ * for every embedding row of every step, where the step runs.  Heads answer "a class I have fitted"; this answers "the nearest
+ * labelled examples of this window, now".  Nothing but finished results crosses the bus, and any number of contexts share one index.
+ *
+ *   Snapshot       the attachment searches rows [0, n), n = bn_index_size at the attach (a pending bn_index_add_ctx is waited for
+ *                  first).  The slab is allocated once at bn_index_create and an append writes only rows >= the size, so appends
+ *                  and every other index call, on other threads, are legal while attached steps run: the rows a step sees are
+ *                  masked by id, never by what an append may be writing.  Attaching again takes a new snapshot; refreshing one
+ *                  without re-attaching is not offered.  rows_searched reports n; n == 0 is legal and gives every count 0.
+ *   Query          the step's embedding row, normalised by the index's rule (the same bits as an append or a search query).  A
+ *                  row with zero norm, a non-finite element or an overflowing or underflowing sum of squares has count 0.
+ *   Score, order   the f32 score of bn_index_search, bit for bit; its bits depend on dim, the query and the row only: not on the
+ *                  batch size, the row's position in the batch, the number of rows searched or the entry point (a step or
+ *                  bn_index_match).  Score descending, ties by id ascending (-0.0 == +0.0).  A row stored as zeros is never returned.
+ *   Threshold      with has_min a row is a candidate iff its f32 score >= min_score, so the result is exactly the prefix of
+ *                  bn_index_search's list of the same top_m whose scores are >= min_score.  min_score must then be finite.
+ *   Tags           tag[j] is the tag of row id[j] as the tag plane holds it when the step executes (the plane is looked up at every
+ *                  step, not at the attach); an index that never tagged gives zeros.  bn_index_set_tags / bn_index_fill_tags must
+ *                  not run while an attached step is in flight: ordering the two is the caller's.
+ *   Results        pinned host arrays owned by the attachment: id, score, tag [batch * m_stride] (m_stride >= top_m is reported;
+ *                  query i's list starts at i * m_stride) and count [batch], valid after bn_ctx_synchronize until the context's
+ *                  next step; entries past a count are unspecified.  Before any step since the attach bn_step_index_results is
+ *                  BN_ERR_INVALID_ARG.
+ *   Step           bn_ctx_attach_index makes every later bn_step_device / bn_step_windows / bn_step_live of the context also run
+ *                  the match on that step's embedding rows, on the context's stream, after the plan and the step's own top-K
+ *                  and outside the captured plan graph (capture_fallbacks stays 0): three launches and one copy per step, whatever
+ *                  the batch.  The step's own outputs and the head's, prior's and tracker's results are unchanged, bit for bit.
+ *                  bn_infer*, tickets (bn_infer_submit / bn_infer_collect) and bn_group_* carry no match results.
+ *   Refusals       BN_ERR_INVALID_ARG with a message, nothing changed (an earlier attachment stays in place and working): a NULL
+ *                  context, a model without a computed embedding output, bn_index_dim != embedding_dim, an index on another
+ *                  device, top_m outside 1..256, m_stride < top_m, a non-finite min_score with has_min, NULL rows or outputs with
+ *                  n > 0.  Without a gfx950 device bn_index_match returns BN_ERR_NO_DEVICE.
+ *   Lifetime       the attachment holds a reference on the index: bn_index_free and bn_ctx_destroy may come in either order, the
+ *                  slab lives until the last of them.
+ *   Threading      an index may be attached to any number of contexts, each stepped by its own thread.  bn_ctx_attach_index and
+ *                  bn_index_match take one thread at a time per index, like every other index call.
+ */
+/* every later bn_step_device / bn_step_windows / bn_step_live on c also matches that step's embedding rows against the rows x
+ * holds now; x == NULL detaches (the other arguments are then ignored) */
+bn_status bn_ctx_attach_index(bn_ctx *c, bn_index *x, size_t top_m, int32_t has_min, float min_score);
+/* pinned host views of the last step's match results (any output may be NULL): id / score / tag [batch, m_stride], count [batch] */
+bn_status bn_step_index_results(const bn_ctx *c, const uint64_t **id, const float **score, const uint32_t **tag,
+                                const uint32_t **count, size_t *m_stride, size_t *rows_searched);
+/* the same kernels on n host rows [n * dim], without a model: outputs [n * m_stride] and count_out [n].  Synchronous, on the index's
+ * stream, over the index's current size (after a pending bn_index_add_ctx), any n (in rounds) */
+bn_status bn_index_match(bn_index *x, const float *rows, size_t n, size_t top_m, int32_t has_min, float min_score,
+                         size_t m_stride, uint64_t *id_out, float *score_out, uint32_t *tag_out, uint32_t *count_out);
 
 /*
  * Clustering an index: what is in the archive, before there is a window to search from or a label to fit on.  bn_index_assign

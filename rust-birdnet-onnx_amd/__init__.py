@@ -63,6 +63,7 @@ ENGINE_SYMBOLS = [
     "bn_index_search_peaks", "bn_index_search_peaks_ids",
     "bn_head_create", "bn_head_free", "bn_head_dim", "bn_head_classes", "bn_head_flags", "bn_head_read", "bn_head_apply_host",
     "bn_head_fit", "bn_head_fit_index", "bn_head_rank_index", "bn_ctx_attach_head", "bn_step_head_results",
+    "bn_ctx_attach_index", "bn_step_index_results", "bn_index_match",
     "bn_prior_create", "bn_prior_free", "bn_prior_sites", "bn_prior_species", "bn_prior_threshold", "bn_prior_flags", "bn_prior_read",
     "bn_prior_apply_host", "bn_ctx_attach_prior", "bn_ctx_prior_site", "bn_step_prior_results",
     "bn_track_create", "bn_track_free", "bn_track_sources", "bn_track_species", "bn_track_open_events", "bn_track_update_host",
@@ -290,6 +291,9 @@ def _load() -> C.CDLL:
         "bn_head_rank_index": (i32, [vp, vp, C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), sz, sz, sz, C.POINTER(C.c_uint64), f32p, u32p]),
         "bn_ctx_attach_head": (i32, [vp, vp, sz, i32, C.c_float]),
         "bn_step_head_results": (i32, [vp, C.POINTER(f32p), C.POINTER(u32p), C.POINTER(f32p), C.POINTER(u32p), C.POINTER(sz), C.POINTER(sz)]),
+        "bn_ctx_attach_index": (i32, [vp, vp, sz, i32, C.c_float]),
+        "bn_step_index_results": (i32, [vp, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(f32p), C.POINTER(u32p), C.POINTER(u32p), C.POINTER(sz), C.POINTER(sz)]),
+        "bn_index_match": (i32, [vp, f32p, sz, sz, i32, C.c_float, sz, C.POINTER(C.c_uint64), f32p, u32p, u32p]),
         "bn_prior_create": (i32, [i32, sz, sz, f32p, C.c_float, C.c_uint32, C.POINTER(vp)]),
         "bn_prior_free": (None, [vp]),
         "bn_prior_sites": (sz, [vp]),
@@ -1095,6 +1099,32 @@ class Context:
             raise EngineError(st)
         return _step_arrays(batch, ks.value, ix, cf, ct, lg, nc.value)
 
+    def attach_index(self, index: Optional["Index"], top_m: int = 10, min_score: Optional[float] = None):
+        """bn_ctx_attach_index: every later step of this context also matches the step's embedding rows against the rows `index`
+        holds now (None detaches); with min_score only rows scoring at least that much are returned."""
+        st = lib.bn_ctx_attach_index(self._h, None if index is None else index._h, top_m, *_min_args(min_score))
+        if st:
+            raise EngineError(st)
+        self._index = index
+
+    def step_index_results(self, batch: int):
+        """(ids [batch, top_m] uint64, scores [batch, top_m] float32, tags [batch, top_m] uint32, counts [batch] uint32,
+        rows_searched) of the last step's match, after synchronize(); entries past counts[i] are as Index.search leaves them (id 0,
+        score NaN, tag 0)."""
+        ip, sp, tp, cp = C.POINTER(C.c_uint64)(), C.POINTER(C.c_float)(), C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint32)()
+        ms, ns = C.c_size_t(), C.c_size_t()
+        st = lib.bn_step_index_results(self._h, C.byref(ip), C.byref(sp), C.byref(tp), C.byref(cp), C.byref(ms), C.byref(ns))
+        if st:
+            raise EngineError(st)
+        m = ms.value
+        counts = np.ctypeslib.as_array(cp, (batch,)).copy()
+        ids = np.ctypeslib.as_array(ip, (batch, m)).copy()
+        scores = np.ctypeslib.as_array(sp, (batch, m)).copy()
+        tags = np.ctypeslib.as_array(tp, (batch, m)).copy()
+        past = np.arange(m)[None, :] >= counts[:, None]
+        ids[past], scores[past], tags[past] = 0, np.nan, 0
+        return ids, scores, tags, counts, int(ns.value)
+
     def time_kernels(self, batch: int):
         cap = 1024
         names = C.create_string_buffer(cap * BN_NAME_LEN)
@@ -1261,6 +1291,20 @@ class Index:
         if st:
             raise EngineError(st)
         return ids, scores, counts
+
+    def match(self, rows, top_m: int, min_score: Optional[float] = None, m_stride: Optional[int] = None):
+        """bn_index_match: what a step of a context with this index attached computes for its embedding rows, on host rows [n, dim]:
+        (ids, scores, tags [n, top_m], counts [n]), the prefix of search()'s lists scoring at least min_score, with the tags of the hits."""
+        q = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, self.dim)
+        m_stride = top_m if m_stride is None else m_stride
+        ids, scores, counts = self._outputs(q.shape[0], max(m_stride, 0))
+        tags = np.zeros(ids.shape, dtype=np.uint32)
+        st = lib.bn_index_match(self._h, q.ctypes.data_as(C.POINTER(C.c_float)), q.shape[0], top_m, *_min_args(min_score), m_stride,
+                                ids.ctypes.data_as(C.POINTER(C.c_uint64)), scores.ctypes.data_as(C.POINTER(C.c_float)),
+                                tags.ctypes.data_as(C.POINTER(C.c_uint32)), counts.ctypes.data_as(C.POINTER(C.c_uint32)))
+        if st:
+            raise EngineError(st)
+        return ids, scores, tags, counts
 
     def search_head(self, head: "Head", top_m: int):
         """Per class, the top_m stored rows by head logit: bn_index_search with W_c as the query.  For a stored (unit) row

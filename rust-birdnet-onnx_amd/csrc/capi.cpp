@@ -172,6 +172,7 @@ struct bn_ctx {
     bn::HeadAttach *head = nullptr;  // bn_ctx_attach_head: run after every step's own work (head.hip)
     bn::PriorAttach *prior = nullptr;  // bn_ctx_attach_prior: the same, on the step's logits rows (prior.hip)
     bn::TrackAttach *track = nullptr;  // bn_ctx_attach_track: the same, for the steps whose rows carry window numbers (track.hip)
+    bn::MatchAttach *match = nullptr;  // bn_ctx_attach_index: the step's embedding rows matched against an index's snapshot (match.hip)
     // ---- asynchronous host-slice path (bn_infer_submit / bn_infer_collect): a ring of two batches per context.
     // Both slots own their device input, pinned input and pinned output buffers (allocated on first use), so a ticket
     // in flight shares nothing with the synchronous entry points (bn_infer_windows / bn_step_*) but the arena and the
@@ -725,6 +726,7 @@ void bn_ctx_destroy(bn_ctx *c) {
     bn::head_detach(c->head);
     bn::prior_detach(c->prior);
     bn::track_detach(c->track);
+    bn::match_detach(c->match);
     for (auto &kv : c->graphs) (void)gated::GraphExecDestroy(kv.second);
     if (c->d_arena) (void)gated::Free(c->d_arena);
     if (c->d_input) (void)gated::Free(c->d_input);
@@ -1269,6 +1271,11 @@ bn_status bn::step_device(bn_ctx *c, const float *d_pcm, const StepRows &rows, s
         st = bn::track_step(c->track, c->stream, d_logits, rows, c->prior);
         if (st != BN_OK) return st;
     }
+    if (c->match) {
+        const OutputInfo &eo = p.outputs[c->model->cfg.embedding_output];
+        st = bn::match_step(c->match, c->stream, resolve(c, eo.ref, d_pcm), batch);
+        if (st != BN_OK) return st;
+    }
     if (sync) BN_HIP_TRY(hipStreamSynchronize(c->stream));
     return BN_OK;
 }
@@ -1298,6 +1305,27 @@ bn_status bn_step_head_results(const bn_ctx *c, const float **logits, const uint
     if (!c) return fail(BN_ERR_INVALID_ARG, "null context");
     if (!c->head) return fail(BN_ERR_INVALID_ARG, "no head is attached to this context");
     return bn::head_step_results(c->head, logits, idx, conf, count, k_stride, n_classes);
+}
+
+bn_status bn_ctx_attach_index(bn_ctx *c, bn_index *x, size_t top_m, int32_t has_min, float min_score) {
+    if (!c) return fail(BN_ERR_INVALID_ARG, "null context");
+    const bn_model_config &cfg = c->model->cfg;
+    BN_HIP_TRY(bn::use_device(c->model->device));
+    bn::MatchAttach *a = nullptr;
+    if (x) {
+        const bool has_emb = cfg.has_embedding && cfg.embedding_output >= 0 && c->pd->plan->outputs[cfg.embedding_output].computed;
+        bn_status st = bn::match_attach(x, c->model->device, has_emb, has_emb ? (size_t)c->pd->plan->outputs[cfg.embedding_output].row_elems : 0,
+                                        c->max_batch, top_m, has_min, min_score, &a);
+        if (st != BN_OK) return st;
+    }
+    return install_attachment(c->stream, c->match, a, bn::match_detach);
+}
+
+bn_status bn_step_index_results(const bn_ctx *c, const uint64_t **id, const float **score, const uint32_t **tag, const uint32_t **count, size_t *m_stride,
+                                size_t *rows_searched) {
+    if (!c) return fail(BN_ERR_INVALID_ARG, "null context");
+    if (!c->match) return fail(BN_ERR_INVALID_ARG, "no index is attached to this context");
+    return bn::match_step_results(c->match, id, score, tag, count, m_stride, rows_searched);
 }
 
 bn_status bn_ctx_attach_prior(bn_ctx *c, bn_prior *p, const int32_t *source_sites, size_t n_source_sites, size_t top_k, int32_t has_min, float min_conf) {

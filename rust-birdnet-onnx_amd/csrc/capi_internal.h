@@ -278,6 +278,27 @@ bn_status index_adopt_rows(bn_index *x, size_t n);
 struct ClusterState;
 ClusterState **index_cluster_state(bn_index *x);
 void cluster_state_free(ClusterState *s);
+// index.hip -> match.hip: a reference on an index (bn_index_free drops the caller's; the slab lives until the last is gone), its
+// device and stream, the current tag plane ([capacity] u16 on the device, NULL until a tag is first set), and index_normalise_kernel
+// enqueued on `stream`: n rows at d_src (row stride src_stride floats) -> d_dst [n, dpad] + d_valid [n], the index's rule and bits
+void index_ref(bn_index *x);
+void index_unref(bn_index *x);
+int index_device(const bn_index *x);
+hipStream_t index_stream(const bn_index *x);
+const uint16_t *index_tags(const bn_index *x);
+bn_status index_enqueue_normalise(hipStream_t stream, const float *d_src, size_t src_stride, size_t n, size_t dim, float *d_dst, size_t dpad,
+                                  uint8_t *d_valid);
+// match.hip -> capi.cpp: an index attached to a context (a snapshot of its rows, its own scratch and result buffers; holds a reference
+// to the index).  match_ranges: the row ranges (workgroups per query pass) of a snapshot of n_tiles 64-row tiles
+struct MatchAttach;
+WgSplit match_ranges(uint32_t n_tiles);
+bn_status match_attach(bn_index *x, int device, bool has_embedding, size_t embedding_dim, size_t max_batch, size_t top_m, int32_t has_min,
+                       float min_score, MatchAttach **out);
+void match_detach(MatchAttach *a);  // the context's stream must be idle
+// normalise + scan + merge-and-pack + results to pinned memory, enqueued on the context's stream behind the step's own work
+bn_status match_step(MatchAttach *a, hipStream_t stream, const float *d_emb, size_t batch);
+bn_status match_step_results(const MatchAttach *a, const uint64_t **id, const float **score, const uint32_t **tag, const uint32_t **count,
+                             size_t *m_stride, size_t *rows_searched);
 // head.hip -> rank.hip: what a kernel needs of a head (weights [cpad = classes rounded up to 16][dpad], bias [cpad], padding zero)
 struct HeadView {
     int device;

@@ -23,9 +23,14 @@
 //
 // Row tags (bn_index_set_tags / fill_tags / read_tags): one u16 per row of capacity, allocated zeroed by the first call that sets one.
 // No kernel of this file reads it.
+//
+// An index is reference counted: bn_index_free drops the caller's reference, and every attachment of match.hip (bn_ctx_attach_index)
+// holds one, so the slab lives until the last of them.  match.hip reads the slab, the valid bytes and the tag plane on a context's
+// stream, with buffers of its own; what it needs of an index is index_rows, index_tags and index_enqueue_normalise.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstring>
 #include <memory>
@@ -237,6 +242,7 @@ bn::LdsOptIn g_scan_lds;
 }  // namespace
 
 struct bn_index {
+    std::atomic<int> refs{1};  // the caller's handle + one per attachment that matches against it (match.hip)
     int device = 0;
     size_t dim = 0, dpad = 0, cap = 0, cap_pad = 0, size = 0;
     int max_wg = 0;
@@ -281,6 +287,10 @@ void release(bn_index *x) {
     if (x->h_count) (void)bn::gated::HostFree(x->h_count);
     if (x->stream) (void)bn::gated::StreamDestroy(x->stream);
     delete x;
+}
+
+void unref(bn_index *x) {
+    if (x && x->refs.fetch_sub(1, std::memory_order_acq_rel) == 1) release(x);
 }
 
 // device and stream of the index current, and the index's stream ordered after the last bn_index_add_ctx
@@ -429,6 +439,19 @@ bn_status bn::index_stage_query_ids(bn_index *x, const uint64_t *ids, size_t n, 
 
 bn::ClusterState **bn::index_cluster_state(bn_index *x) { return &x->cluster; }
 
+void bn::index_ref(bn_index *x) { x->refs.fetch_add(1, std::memory_order_relaxed); }
+void bn::index_unref(bn_index *x) { unref(x); }
+int bn::index_device(const bn_index *x) { return x->device; }
+hipStream_t bn::index_stream(const bn_index *x) { return x->stream; }
+const uint16_t *bn::index_tags(const bn_index *x) { return x->tags; }
+
+bn_status bn::index_enqueue_normalise(hipStream_t stream, const float *d_src, size_t src_stride, size_t n, size_t dim, float *d_dst, size_t dpad,
+                                      uint8_t *d_valid) {
+    hipLaunchKernelGGL(index_normalise_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, d_src, src_stride, (uint32_t)n, (uint32_t)dim, d_dst,
+                       (uint32_t)dpad, d_valid);
+    return check_launch("index normalise");
+}
+
 bn_status bn::index_scan_state(bn_index *x, IndexScan *out) {
     if (!x || !out) return set_last_error(BN_ERR_INVALID_ARG, "null index");
     bn_status st = begin(x);
@@ -556,7 +579,7 @@ bn_status bn_index_create(int32_t device, size_t dim, size_t capacity_rows, bn_i
     return BN_OK;
 }
 
-void bn_index_free(bn_index *x) { release(x); }
+void bn_index_free(bn_index *x) { unref(x); }
 
 size_t bn_index_size(const bn_index *x) { return x ? x->size : 0; }
 size_t bn_index_dim(const bn_index *x) { return x ? x->dim : 0; }
