@@ -356,7 +356,6 @@ bool emit_stft(Plan &plan, const std::string &name, const PlanOp &base, const Df
 // branch: 17 K steps instead of 32.  BN_CONVFOLD2=0 keeps the half fold.
 bool emit_quarter_fold(Plan &plan, const std::string &name, const PlanOp &base, const DftBank &bank, const std::vector<int> &cls, int64_t Cout, int64_t OW, bool has_bias) {
     if (sw_int(sw::BN_CONVFOLD2) == 0) return false;
-    if (sw_int(sw::BN_FRAMEPAIR) == 1) return false;  // (opt-in rule J fuses the mel product behind the HALF fold's launch)
     const int64_t L = bank.L;
     if (L % 128 != 0) return false;
     for (int64_t c = 0; c < Cout; c++)

@@ -40,7 +40,6 @@ struct PlanOp {
     ReduceDesc red{};
     GemmDesc gemm{};
     FramePre pre{};    // GEMM with fold (LDS-resident framing kernels): per-sample chain applied while the span is loaded; operands in eb
-    GemmDesc gemm2{};  // GEMM with fold (planner rule J): the product fused behind it (N == 0: none); its weights in w2, its bias in bias2
     ConvDesc conv{};
     DwDesc dw{};
     GapDesc gap{};

@@ -55,7 +55,7 @@ const char *take_launch_error() {
 // count -- is done ONCE per device by prepare_device(), which bn_model_load / bn_ctx_create / the stand-alone top-K
 // entry points call before anything is launched.  Nothing but kernel launches is then issued between
 // hipStreamBeginCapture and hipStreamEndCapture: a hipFuncSetAttribute inside a capture (the first launch of the
-// 80 KB frame_fold_kernel of a plan) is what invalidated one graph capture in six when several ranks shared a device.
+// 80 KB framing kernel of a plan) is what invalidated one graph capture in six when several ranks shared a device.
 namespace {
 std::mutex g_prep_mu;
 std::atomic<uint64_t> g_prepared_mask{0};  // device ordinals < 64 that prepare_device() has completed on
@@ -775,10 +775,10 @@ __global__ __launch_bounds__(256) void gemm_mfma_kernel(GemmDesc d, float *__res
 // ------------------------------------------------------------------ folded framing GEMM, signal resident in LDS
 // The folded framing GEMM above re-reads every frame row from L2 once per K step and N tile: 530 MB of L2 -> L1
 // traffic per launch at batch 32 (6.8 TB/s; matrix pipe 40 % busy, PMC).  Frames overlap (hop 278 of 2048 taps), so
-// the 64 frames of a block span only 63*hop + L samples (<= 80 KB): this kernel loads that span into LDS ONCE and
-// builds each folded 64 x 32 operand tile from it (LDS -> LDS, double buffered), while the filter tile streams
-// through registers as before.  2*WN waves: wave w owns rows 32*(w&1).. and columns 32*(w>>1)..; one barrier per K
-// step.  Same K order, fragment layout and fold expression as gemm_mfma_kernel<.., FOLD>: bit-identical results.
+// the 64 frames of a block span only 63*hop + L samples (<= 80 KB): frame_foldh_kernel below loads that span into LDS
+// ONCE and builds each folded 64 x 32 operand tile from it (LDS -> LDS, double buffered), while the filter tile streams
+// through registers as before.  2*WN waves per K slice: wave w owns rows 32*(w&1).. and columns 32*(w>>1)..; one
+// barrier per K step.
 struct FrameDesc {
     int32_t rows, N, K, L, hop;   // per-sample frames, outputs, folded taps (L/2), filter length, frame hop
     int32_t tiles;                // 64-row tiles per sample
@@ -806,194 +806,6 @@ __device__ __noinline__ floatx16 act_small16(int act, float p0, float p1, floatx
     for (int r = 0; r < 16; r++) a[r] = v[r];
     return a;
 }
-// PAIR (planner rule J): the product that consumes the rows of this one -- the mel filter bank of the spectrogram branch, K2 = N <= 128
-// spectrum bins -> N2 <= 128 bands, with its absorbed epilogue chain and output view -- runs behind the K loop on the block's own 64 x N
-// spectrum tile (accumulators -> LDS as 32-deep K tiles of the second product, filter rows staged step by step, the shared
-// gemm_epilogue): the spectrum rows are neither written nor read back and the launch that did it is gone.
-template <bool PAIR>
-__global__ __launch_bounds__(PAIR ? 512 : 640) void frame_fold_kernel(FrameDesc d, float *__restrict__ C, const float *__restrict__ A,
-                                                         const float *__restrict__ W, const float *__restrict__ bias, GemmDesc d2,
-                                                         float *__restrict__ C2, const float *__restrict__ W2, const float *__restrict__ bias2) {
-    extern __shared__ __align__(16) float frame_lds[];
-    const int T = blockDim.x, tid = threadIdx.x;
-    const int BN = (T >> 7) * 32;  // WN wave columns of 32 outputs
-    float *sig = frame_lds;
-    float *As = sig + ((d.span + 3) & ~3);
-    float *Ws = As + 2 * FRAME_BM * GEMM_LD;
-    const int b = blockIdx.x / d.tiles, rt = blockIdx.x - b * d.tiles;
-    const int row0 = rt * FRAME_BM;
-    const int rows_here = min(FRAME_BM, d.rows - row0);
-    const float *src = A + (int64_t)b * d.a_bs + (int64_t)row0 * d.hop;
-    const int count = (rows_here - 1) * d.hop + d.L;
-    if (d.vec4) {
-        const float4 *s4 = reinterpret_cast<const float4 *>(src);
-        float4 *d4 = reinterpret_cast<float4 *>(sig);
-        const int n4 = count >> 2;
-        for (int i = tid; i < n4; i += T) d4[i] = s4[i];
-        for (int i = (n4 << 2) + tid; i < count; i += T) sig[i] = src[i];
-    } else {
-        for (int i = tid; i < count; i += T) sig[i] = src[i];
-    }
-    // filter tile staging: BN rows x 32 taps = BN * 8 float4, up to 2 per thread (BN <= 160, T = 4 * BN)
-    const int wq = tid & 7, wr = tid >> 3;  // float4 column, row of this thread's first filter vector
-    const int wrows_per_pass = T >> 3;      // = BN / 2
-    int n0 = 0;
-    auto w_ptr = [&](int pass, int k0) {
-        int n = n0 + wr + pass * wrows_per_pass;
-        n = n < d.N ? n : d.N - 1;
-        return reinterpret_cast<const float4 *>(W + (int64_t)n * d.K + k0 + 4 * wq);
-    };
-    float4 rw0, rw1;
-    const int ksteps = d.K / GEMM_BK;
-    // operand staging: a thread owns up to 4 (row, column pair) slots of the 64 x 32 tile, fixed over the K loop, so the
-    // row offsets are resolved once; per K step it reads the forward and mirrored pairs and writes one float2
-    // (measured: pairs beat the conflict-free one-element-per-lane mapping, 49 vs 54 us -- instruction count, not banks)
-    constexpr int SLOTS = 4;
-    int fwd_off[SLOTS], rev_off[SLOTS], dst_off[SLOTS];
-#pragma unroll
-    for (int i = 0; i < SLOTS; i++) {
-        const int p = tid + i * T;
-        const int r = (p >> 4) & (FRAME_BM - 1), cp = (p & 15) * 2;
-        const int re = r < rows_here ? r : rows_here - 1;
-        fwd_off[i] = re * d.hop + 1 + cp;
-        rev_off[i] = re * d.hop + d.L - 2 - cp;
-        dst_off[i] = p < FRAME_BM * 16 ? r * GEMM_LD + cp : -1;
-    }
-    auto stage_a = [&](int ks, float *dst) {
-        const int k0 = ks * GEMM_BK;
-#pragma unroll
-        for (int i = 0; i < SLOTS; i++) {
-            if (dst_off[i] >= 0) {
-                const float *f = sig + fwd_off[i] + k0, *m = sig + rev_off[i] - k0;
-                *reinterpret_cast<float2 *>(dst + dst_off[i]) = make_float2(fmaf(d.sign, m[1], f[0]), fmaf(d.sign, m[0], f[1]));
-            }
-        }
-    };
-    auto store_w = [&](float *dst) {
-        *reinterpret_cast<float4 *>(dst + wr * GEMM_LD + 4 * wq) = rw0;
-        *reinterpret_cast<float4 *>(dst + (wr + wrows_per_pass) * GEMM_LD + 4 * wq) = rw1;
-    };
-    const int wave = tid >> 6, lane = tid & 63, lr = lane & 31, lh = lane >> 5;
-    const int wm = wave & 1, wn = wave >> 1;
-    __syncthreads();  // signal span complete
-    // N tiles of this row tile: with grid.y == 1 one block walks all of them and the span is loaded once
-    for (int ny = blockIdx.y; ny * BN < d.N; ny += gridDim.y) {
-    n0 = ny * BN;
-    rw0 = *w_ptr(0, 0); rw1 = *w_ptr(1, 0);
-    stage_a(0, As);
-    store_w(Ws);
-    if (ksteps > 1) { rw0 = *w_ptr(0, GEMM_BK); rw1 = *w_ptr(1, GEMM_BK); }
-    __syncthreads();
-    floatx16 acc[1];
-#pragma unroll
-    for (int r = 0; r < 16; r++) acc[0][r] = 0.0f;
-    for (int ks = 0; ks < ksteps; ks++) {
-        const int cur = ks & 1;
-        float *An = As + (cur ^ 1) * FRAME_BM * GEMM_LD, *Wn = Ws + (cur ^ 1) * BN * GEMM_LD;
-        if (ks + 1 < ksteps) {
-            stage_a(ks + 1, An);
-            store_w(Wn);
-            if (ks + 2 < ksteps) { rw0 = *w_ptr(0, (ks + 2) * GEMM_BK); rw1 = *w_ptr(1, (ks + 2) * GEMM_BK); }
-        }
-        const float *ap = As + cur * FRAME_BM * GEMM_LD + (wm * 32 + lr) * GEMM_LD + 4 * lh;
-        const float *wp = Ws + cur * BN * GEMM_LD + (wn * 32 + lr) * GEMM_LD + 4 * lh;
-        mfma_ktile_full<1>(ap, wp, acc);
-        // LDS-only rendezvous: the operand tiles of step ks + 1 are in place.  (__syncthreads would also wait for the filter
-        // rows of step ks + 2, requested a moment ago: they are only needed after the next step's multiplications.)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-    }
-    const int n = n0 + wn * 32 + lr;
-    if constexpr (PAIR) {
-        // (one N tile covers the whole spectrum row: the launcher guarantees N <= BN and grid.y == 1)
-        // the spectrum tile (+ bias) as K tiles of the second product: S[ks = wn][row][k = lr]; columns n >= N hold copies of the
-        // last filter row's output and meet zero taps below
-        float *S = As;                                    // [BN / 32][64][GEMM_LD]  (both tile buffers are free: the K loop ended on a barrier)
-        float *W2s = S + (BN >> 5) * FRAME_BM * GEMM_LD;  // [<= 128][GEMM_LD]
-        {
-            const float bv = (d.has_bias && n < d.N) ? bias[n] : 0.0f;
-#pragma unroll
-            for (int reg = 0; reg < 16; reg++) {
-                const int r = wm * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
-                S[(wn * FRAME_BM + r) * GEMM_LD + lr] = acc[0][reg] + bv;
-            }
-        }
-        const int n2tiles = (d2.N + 31) >> 5, k2steps = (d2.K + 31) >> 5;
-        floatx16 acc2[1];
-#pragma unroll
-        for (int r = 0; r < 16; r++) acc2[0][r] = 0.0f;
-        for (int ks2 = 0; ks2 < k2steps; ks2++) {
-            // filter rows of this step: W2 is [N2][K2], K2 contiguous; rows / taps past the end are zero
-            for (int e = tid; e < n2tiles * 32 * 32; e += T) {
-                const int n2 = e >> 5, kk = e & 31, k = ks2 * 32 + kk;
-                W2s[n2 * GEMM_LD + kk] = (n2 < d2.N && k < d2.K) ? W2[(int64_t)n2 * d2.K + k] : 0.0f;
-            }
-            __syncthreads();  // (first step: the spectrum tile is complete as well)
-            if (wn < n2tiles)
-                mfma_ktile_full<1>(S + (ks2 * FRAME_BM + wm * 32 + lr) * GEMM_LD + 4 * lh, W2s + (wn * 32 + lr) * GEMM_LD + 4 * lh, acc2);
-            __syncthreads();
-        }
-        if (wn < n2tiles) {
-            const int64_t rb = (int64_t)b * d2.rows + row0;
-            // epilogue of the second product: bias, activation, the absorbed chain, the consumer's view (gemm_epilogue's semantics with
-            // the compact stage functions; the planner fuses only chains made of those)
-            const int n2 = wn * 32 + lr;
-            floatx16 a2 = acc2[0];
-            if (d2.has_bias) {
-                const float bv2 = n2 < d2.N ? bias2[n2] : 0.0f;
-#pragma unroll
-                for (int r = 0; r < 16; r++) a2[r] += bv2;
-            }
-            if (d2.act != ACT_NONE) a2 = act_small16(d2.act, d2.p0, d2.p1, a2);
-            if (0 < d2.npost) a2 = act_small16(d2.post_act[0], d2.post_p0[0], d2.post_p1[0], a2);
-            if (1 < d2.npost) a2 = act_small16(d2.post_act[1], d2.post_p0[1], d2.post_p1[1], a2);
-            if (2 < d2.npost) a2 = act_small16(d2.post_act[2], d2.post_p0[2], d2.post_p1[2], a2);
-            if (3 < d2.npost) a2 = act_small16(d2.post_act[3], d2.post_p0[3], d2.post_p1[3], a2);
-            if (n2 < d2.N) {
-                const int64_t rs = d2.out_strided ? d2.out_rs : d2.ldc, cs = d2.out_strided ? d2.out_cs : 1;
-                float *cb2 = C2 + (int64_t)b * d2.c_bs + (int64_t)n2 * cs;
-#pragma unroll
-                for (int reg = 0; reg < 16; reg++) {
-                    const int r = wm * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
-                    if (r < rows_here) cb2[(int64_t)(row0 + r) * rs] = a2[reg];
-                }
-            }
-            (void)rb;
-        }
-    } else if (d.npost || d.out_strided) {  // bias, the absorbed chain (compact stage functions), the consumer's view
-        floatx16 a2 = acc[0];
-        if (d.has_bias) {
-            const float bv = n < d.N ? bias[n] : 0.0f;
-#pragma unroll
-            for (int r = 0; r < 16; r++) a2[r] += bv;
-        }
-        if (0 < d.npost) a2 = act_small16(d.post_act[0], d.post_p0[0], d.post_p1[0], a2);
-        if (1 < d.npost) a2 = act_small16(d.post_act[1], d.post_p0[1], d.post_p1[1], a2);
-        if (2 < d.npost) a2 = act_small16(d.post_act[2], d.post_p0[2], d.post_p1[2], a2);
-        if (3 < d.npost) a2 = act_small16(d.post_act[3], d.post_p0[3], d.post_p1[3], a2);
-        if (n < d.N) {
-            const int64_t rs = d.out_strided ? d.out_rs : d.ldc, cs = d.out_strided ? d.out_cs : 1;
-            float *cb = C + (int64_t)b * d.c_bs + (int64_t)n * cs;
-#pragma unroll
-            for (int reg = 0; reg < 16; reg++) {
-                const int r = wm * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
-                if (r < rows_here) cb[(int64_t)(row0 + r) * rs] = a2[reg];
-            }
-        }
-    } else if (n < d.N) {
-        const float bv = d.has_bias ? bias[n] : 0.0f;
-        float *cb = C + (int64_t)b * d.c_bs + (int64_t)row0 * d.ldc + n;
-#pragma unroll
-        for (int reg = 0; reg < 16; reg++) {
-            const int r = wm * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
-            if (r < rows_here) cb[(int64_t)r * d.ldc] = acc[0][reg] + bv;
-        }
-    }
-    // (the last K step ended with a barrier: every wave is done with both tile buffers)
-    }
-}
-
 // LDS addresses as 32-bit byte offsets (ds_* instructions take base register + immediate; generic pointers cost an add each)
 typedef __attribute__((address_space(3))) float lds_float;
 typedef float lds_f2v __attribute__((ext_vector_type(2)));
@@ -1051,15 +863,15 @@ __device__ __forceinline__ void frame_load_span(float *sig, const float *__restr
     }
 }
 
-// ------------------------------------------------------------------ half-folded framing GEMM, round-4 form
-// frame_fold_kernel<false>'s job with the structure that paid for the quarter fold below: compile-time block shape (WN wave columns), LDS
+// ------------------------------------------------------------------ half-folded framing GEMM
+// The LDS-resident half fold with the structure that paid for the quarter fold below: compile-time block shape (WN wave columns), LDS
 // addresses as 32-bit byte offsets, the signal reads of the NEXT step's operand tile issued before this step's matrix instructions and
 // finished behind them, nothing conditional around the matrix instructions.  KS = 2: the 8-wide k groups of every step are split between
 // two sets of 2 WN waves (groups 0, 1 | groups 2, 3) whose partial tiles are added through LDS at the end, slice 0 + slice 1 -- for
 // THREE wave columns (N = 65 .. 96: v2.4's 96 merged mel filters) six waves leave two of the four SIMDs with one wave and the block
 // runs at the pace of the two that have two; twelve waves balance (3 per SIMD).  KS is a function of N alone (frame_fold_kslices), so a
 // segment's bits do not depend on the batch; with KS = 1 the k order, fragment layout and fold expression are those of
-// gemm_mfma_kernel<.., FOLD> and of frame_fold_kernel (bit-identical, tested), with KS = 2 the sum is cut once more.
+// gemm_mfma_kernel<.., FOLD> (bit-identical, tested), with KS = 2 the sum is cut once more.
 template <int NG>
 __device__ __forceinline__ void mfma_ktile_groups(const float *__restrict__ ap, const float *__restrict__ wp, floatx16 &acc) {
 #pragma unroll
@@ -1222,7 +1034,7 @@ __global__ __launch_bounds__(128 * WN * KS) void frame_foldh_kernel(FrameDesc d,
 // (n = 0 pairs ye[0] = 0 with the centre tap ye[L/2] = y[L/2]: table entries wa[0] = 0, wb[0] = w[L/2] / 2 say so.)  The window cannot stay
 // inside the filter rows as in the half fold -- w[n] != w[L/2-n] -- so it multiplies the signal: S[n] = wa[n] a + wb[n] b, D[n] = wa[n] a -
 // wb[n] b with a = x[n] + x[L-n], b = x[L/2-n] + x[L/2+n]; the filter rows are the planner's pure cosines (double -> f32) times the row's
-// amplitude.  Same structure as frame_fold_kernel: the block's signal span in LDS once, per 32-tap step TWO operand tiles (S and D) built
+// amplitude.  Same structure as frame_foldh_kernel: the block's signal span in LDS once, per 32-tap step TWO operand tiles (S and D) built
 // LDS -> LDS and one filter tile streamed through registers, one barrier per step; wave (w & 1, w >> 1) owns rows 32 (w & 1).. of the
 // columns 32 (w >> 1).. and reads the S tile if its columns are even bins (column < n_even), else the D tile.  L / 128 full steps + one
 // step of a single 8-wide group that carries tap L/4.  Half the matrix instructions of the half fold for ~3x its (small) staging
@@ -3114,8 +2926,6 @@ inline unsigned cap_blocks(int64_t want, int64_t cap) { return (unsigned)std::ma
 
 // every kernel of this file that may be launched with more than 64 KB of dynamic LDS (prepare_device opts them in)
 void register_kernels_hip() {
-    register_dynamic_lds_kernel(reinterpret_cast<const void *>(frame_fold_kernel<false>));
-    register_dynamic_lds_kernel(reinterpret_cast<const void *>(frame_fold_kernel<true>));
     register_dynamic_lds_kernel(reinterpret_cast<const void *>(frame_foldh_kernel<2, 1>));
     register_dynamic_lds_kernel(reinterpret_cast<const void *>(frame_foldh_kernel<3, 1>));
     register_dynamic_lds_kernel(reinterpret_cast<const void *>(frame_foldh_kernel<4, 1>));
@@ -3392,14 +3202,11 @@ static void launch_gemm_splitk(hipStream_t s, const GemmDesc &d, float *C, const
     }
 }
 
-// pair != nullptr: the fused second product (frame_fold_kernel<true>); the caller has checked frame_fold_pair_ok
 static bool launch_frame_fold(hipStream_t s, const GemmDesc &d, float *C, const float *A, const float *W, const float *bias, int64_t batch,
-                              const GemmDesc *pair = nullptr, float *C2 = nullptr, const float *W2 = nullptr, const float *bias2 = nullptr,
                               const FramePre *pre = nullptr) {
     if (!frame_fold_shape_ok(d, W)) return false;
     FramePre pre_v{};
     if (pre) pre_v = *pre;
-    if (pre_v.n > 0 && pair) return false;  // (only the round-4 kernels carry the chain; BN_FRAMEH=0 leaves launches WITH a chain on them)
     FrameDesc f{};
     f.rows = (int32_t)d.rows; f.N = d.N; f.K = d.K; f.L = d.fold_n; f.hop = (int32_t)d.lda;
     f.tiles = (int32_t)((d.rows + FRAME_BM - 1) / FRAME_BM);
@@ -3409,7 +3216,6 @@ static bool launch_frame_fold(hipStream_t s, const GemmDesc &d, float *C, const 
     f.sign = (float)d.fold; f.has_bias = d.has_bias;
     f.npost = d.npost; f.out_strided = d.out_strided; f.out_rs = d.out_rs; f.out_cs = d.out_cs;
     for (int q = 0; q < 4; q++) { f.post_act[q] = d.post_act[q]; f.post_p0[q] = d.post_p0[q]; f.post_p1[q] = d.post_p1[q]; }
-    if (pair && (d.npost || d.out_strided)) return false;  // (the fused second product carries its own chain)
     // wave columns: the N tile (32 * WN) with the least padding among 128 and 160 (fewer, wider tiles on a tie)
     static const int force_wn = sw_int(sw::BN_FRAME_WN);  // experiments only
     auto padded = [&](int bn) { return (d.N + bn - 1) / bn * bn; };
@@ -3419,16 +3225,14 @@ static bool launch_frame_fold(hipStream_t s, const GemmDesc &d, float *C, const 
     // enter any output's arithmetic (47 -> 27 us for one segment)
     // K slices (round 4): from the tile width N ALONE would get -- three wave columns leave the SIMDs unbalanced, see frame_foldh_kernel --
     // so that a segment's bits do not depend on the batch-dependent choices around it
-    const int ks = (!pair && wn == 3 && sw_int(sw::BN_FRAME_KS) == 2) ? 2 : 1;
+    const int ks = (wn == 3 && sw_int(sw::BN_FRAME_KS) == 2) ? 2 : 1;
     if ((int64_t)f.tiles * batch <= 32 && d.N > 64) wn = 2;
     if (force_wn >= 2 && force_wn <= 5) wn = force_wn;
-    if (pair) wn = std::max(2, (d.N + 31) / 32);  // one N tile holds the whole spectrum row (N <= 128)
     const int bn = 32 * wn;
     const size_t lds = (size_t)(((f.span + 3) & ~3) + 2 * FRAME_BM * GEMM_LD + 2 * bn * GEMM_LD) * sizeof(float);
     if (lds > 160 * 1024) return false;
     if (ks == 2 && wn > 3) return false;  // (a forced tile width the sliced instances do not cover)
-    const void *fn = pair ? reinterpret_cast<const void *>(frame_fold_kernel<true>)
-                   : ks == 2 ? (wn == 2 ? reinterpret_cast<const void *>(frame_foldh_kernel<2, 2>) : reinterpret_cast<const void *>(frame_foldh_kernel<3, 2>))
+    const void *fn = ks == 2 ? (wn == 2 ? reinterpret_cast<const void *>(frame_foldh_kernel<2, 2>) : reinterpret_cast<const void *>(frame_foldh_kernel<3, 2>))
                    : wn == 2 ? reinterpret_cast<const void *>(frame_foldh_kernel<2, 1>)
                    : wn == 3 ? reinterpret_cast<const void *>(frame_foldh_kernel<3, 1>)
                    : wn == 4 ? reinterpret_cast<const void *>(frame_foldh_kernel<4, 1>) : reinterpret_cast<const void *>(frame_foldh_kernel<5, 1>);
@@ -3437,25 +3241,14 @@ static bool launch_frame_fold(hipStream_t s, const GemmDesc &d, float *C, const 
     const int64_t row_blocks = (int64_t)f.tiles * batch;
     const int walk_env = sw_int(sw::BN_FRAME_WALK);  // tests / experiments
     const bool walk = walk_env >= 0 ? walk_env != 0 : row_blocks >= 256;
-    dim3 grid((unsigned)row_blocks, (walk || pair) ? 1u : (unsigned)((d.N + bn - 1) / bn));
-    GemmDesc none{};
-    if (pair) hipLaunchKernelGGL(frame_fold_kernel<true>, grid, dim3(128 * wn), lds, s, f, C, A, W, bias, *pair, C2, W2, bias2);
-    else if (sw_int(sw::BN_FRAMEH) == 0 && ks == 1 && pre_v.n == 0)  // the round-3 form of the same launch (A/B; bit-identical)
-        hipLaunchKernelGGL(frame_fold_kernel<false>, grid, dim3(128 * wn), lds, s, f, C, A, W, bias, none, nullptr, nullptr, nullptr);
-    else if (ks == 2 && wn == 2) hipLaunchKernelGGL((frame_foldh_kernel<2, 2>), grid, dim3(512), lds, s, f, C, A, W, bias, pre_v);
+    dim3 grid((unsigned)row_blocks, walk ? 1u : (unsigned)((d.N + bn - 1) / bn));
+    if (ks == 2 && wn == 2) hipLaunchKernelGGL((frame_foldh_kernel<2, 2>), grid, dim3(512), lds, s, f, C, A, W, bias, pre_v);
     else if (ks == 2) hipLaunchKernelGGL((frame_foldh_kernel<3, 2>), grid, dim3(768), lds, s, f, C, A, W, bias, pre_v);
     else if (wn == 2) hipLaunchKernelGGL((frame_foldh_kernel<2, 1>), grid, dim3(256), lds, s, f, C, A, W, bias, pre_v);
     else if (wn == 3) hipLaunchKernelGGL((frame_foldh_kernel<3, 1>), grid, dim3(384), lds, s, f, C, A, W, bias, pre_v);
     else if (wn == 4) hipLaunchKernelGGL((frame_foldh_kernel<4, 1>), grid, dim3(512), lds, s, f, C, A, W, bias, pre_v);
     else hipLaunchKernelGGL((frame_foldh_kernel<5, 1>), grid, dim3(640), lds, s, f, C, A, W, bias, pre_v);
     return true;
-}
-
-void launch_gemm_fold_pair(hipStream_t s, const GemmDesc &d, const GemmDesc &d2, float *C2, const float *A, const float *W, const float *bias,
-                           const float *W2, const float *bias2, int64_t batch) {
-    if (batch <= 0) return;
-    if (!frame_fold_pair_ok(d, d2) || !launch_frame_fold(s, d, nullptr, A, W, bias, batch, &d2, C2, W2, bias2))
-        launch_error("folded framing GEMM + fused product: shape outside what the planner may fuse");
 }
 
 void launch_gemm_fold2(hipStream_t s, const GemmDesc &d, float *C, const float *A, const float *W, const float *bias, const float *wtab,
@@ -3538,7 +3331,7 @@ void launch_gemm(hipStream_t s, const GemmDesc &d, float *C, const float *A, con
                  const float *res, const float *scale, int64_t batch, const FramePre *pre) {
     if (batch <= 0) return;
     if (pre && pre->n > 0) {  // (planner rule G moves a chain into a folded GEMM only where frame_fold_post_ok holds)
-        if (!(d.fold == 1 || d.fold == -1) || !launch_frame_fold(s, d, C, A, W, bias, batch, nullptr, nullptr, nullptr, nullptr, pre))
+        if (!(d.fold == 1 || d.fold == -1) || !launch_frame_fold(s, d, C, A, W, bias, batch, pre))
             launch_error("framing GEMM with an absorbed signal chain: the LDS-resident kernel refused the launch and no other kernel carries it");
         return;
     }

@@ -405,8 +405,7 @@ void absorb_into_stft(Plan &plan) {
             // is certain to run on its LDS-resident kernel (half fold: frame_fold_post_ok; quarter fold: always)
             auto framing_gemm = [&](const PlanOp &f) {
                 const GemmDesc &g = f.gemm;
-                if (f.kind != OpKind::GEMM || f.pre.n != 0 || f.gemm2.N > 0 || f.se_fused || sw_int(sw::BN_FRAME_PRE) == 0) return false;
-                if (sw_int(sw::BN_FRAMEPAIR) == 1) return false;  // (opt-in rule J runs later and its kernel does not carry the chain)
+                if (f.kind != OpKind::GEMM || f.pre.n != 0 || f.se_fused || sw_int(sw::BN_FRAME_PRE) == 0) return false;
                 if (!(g.fold == 2 ? frame_fold2_shape_ok(g, nullptr) : (g.fold == 1 || g.fold == -1) && frame_fold_post_ok(g))) return false;
                 return g.a_bs == ed.bo && (g.rows - 1) * g.lda + g.fold_n <= ed.per_sample;
             };
@@ -511,7 +510,7 @@ void fuse_gap_into_gemm(Plan &plan) {
             const auto &u = users[red.a.id];
             if (u.size() != 2 || u[1] != (int)j || plan.storages[red.a.id].pinned) continue;
             PlanOp &g = plan.ops[u[0]];
-            if (g.kind != OpKind::GEMM || g.out.space != Space::ARENA || g.out.id != red.a.id || g.out.offset != red.a.offset || g.se_fused || g.gemm2.N > 0) continue;
+            if (g.kind != OpKind::GEMM || g.out.space != Space::ARENA || g.out.id != red.a.id || g.out.offset != red.a.offset || g.se_fused) continue;
             GemmDesc d = g.gemm;
             if (d.gap || !gemm_gap_shape_ok(d) || gemm_dma_shape(d) != 2 || d.ldc != d.N || d.c_bs != d.rows * d.N) continue;
             // the reduction: every channel's mean over the sample's rows, [rows, N] -> [N], dense
@@ -531,45 +530,6 @@ void fuse_gap_into_gemm(Plan &plan) {
             g.name += "+" + red.name;
             g.bytes += red.bytes - 8.0 * (double)d.rows * d.N;  // the [rows, N] tensor never touches memory
             plan.ops.erase(plan.ops.begin() + (long)j);
-            changed = true;
-        }
-    }
-}
-
-// (J) The product that consumes the rows of a folded framing GEMM -- the mel filter bank of a spectrogram branch that stayed on the
-// matrix path: K2 = the bank's <= 128 live bins, with the compression chain and the layout copy rule E put into its epilogue --
-// runs behind the K loop of the framing kernel on the block's own spectrum tile (kernels.hip, frame_fold_kernel<true>): the
-// spectrum rows are neither written nor read back, one launch less.  Measured slower (kernels.hip, frame_fold_pair_ok): opt-in, BN_FRAMEPAIR=1.
-void fuse_fold_pairs(Plan &plan) {
-    bool changed = true;
-    while (changed) {
-        changed = false;
-        std::vector<std::vector<int>> users(plan.storages.size());
-        std::vector<Ref *> refs;
-        for (size_t k = 0; k < plan.ops.size(); k++) {
-            all_refs(plan.ops[k], refs);
-            for (Ref *r : refs)
-                if (r->space == Space::ARENA && (users[r->id].empty() || users[r->id].back() != (int)k)) users[r->id].push_back((int)k);
-        }
-        for (size_t i = 0; i < plan.ops.size() && !changed; i++) {
-            PlanOp &f = plan.ops[i];
-            if (f.kind != OpKind::GEMM || !f.gemm.fold || f.gemm2.N > 0 || f.gemm.npost || f.gemm.out_strided || f.se_fused) continue;
-            if (f.out.space != Space::ARENA || plan.storages[f.out.id].pinned) continue;
-            const auto &u = users[f.out.id];
-            if (u.size() != 2 || u[0] != (int)i) continue;
-            PlanOp &g = plan.ops[u[1]];
-            if (g.kind != OpKind::GEMM || g.se_fused || g.gemm2.N > 0 || g.a.space != Space::ARENA || g.a.id != f.out.id || g.a.offset != f.out.offset) continue;
-            if (g.w.space != Space::CONSTS || (g.gemm.has_bias && g.bias.space != Space::CONSTS)) continue;
-            if (!frame_fold_pair_ok(f.gemm, g.gemm)) continue;
-            f.gemm2 = g.gemm;
-            f.w2 = g.w;
-            f.bias2 = g.bias;
-            f.out = g.out;
-            f.name += "+" + g.name;
-            f.macs += g.macs;
-            f.weight_bytes += g.weight_bytes;
-            f.bytes += g.bytes - 8.0 * (double)f.gemm.rows * (double)f.gemm.N;  // the spectrum rows never touch memory
-            plan.ops.erase(plan.ops.begin() + u[1]);
             changed = true;
         }
     }
@@ -721,7 +681,7 @@ void pack_bf16x3_weights(Plan &plan) {
         return r;
     };
     for (auto &op : plan.ops) {
-        if (op.kind != OpKind::GEMM || op.gemm2.N > 0 || op.gemm.fold || op.gemm.w3 || op.w.space != Space::CONSTS) continue;
+        if (op.kind != OpKind::GEMM || op.gemm.fold || op.gemm.w3 || op.w.space != Space::CONSTS) continue;
         if (!gemm_b3_shape_ok(op.gemm) && !gemm_dma3_wanted(op.gemm)) continue;
         const int64_t N = op.gemm.N, K = op.gemm.K;
         if ((int64_t)plan.consts[(size_t)op.w.id].size() < op.w.offset + N * K) continue;
@@ -801,7 +761,6 @@ void run_plan_passes(Plan &plan) {
     absorb_chains_into_gemms(plan);
     absorb_into_stft(plan);
     planar_stft_tables(plan);
-    fuse_fold_pairs(plan);
     pair_minmax_reductions(plan);
     fuse_gap_into_gemm(plan);
     absorb_se_into_gemms(plan);

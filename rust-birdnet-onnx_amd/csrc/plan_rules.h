@@ -27,7 +27,7 @@ inline bool ptr_aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p
 // ---- tiled GEMM family (kernels.hip) ------------------------------------------------------------------------------
 constexpr int GEMM_BK_RULE = 32, GEMM_LD_RULE = GEMM_BK_RULE + 4, FRAME_BM_RULE = 64;
 
-// Folded framing GEMM from an LDS-resident signal span (frame_fold_kernel): per-sample quantities and, when given, the
+// Folded framing GEMM from an LDS-resident signal span (frame_foldh_kernel): per-sample quantities and, when given, the
 // filter pointer's alignment.  BN_FRAMELDS=0 disables.
 inline bool frame_fold_shape_ok(const GemmDesc &d, const float *W) {
     if (sw_int(sw::BN_FRAMELDS) == 0) return false;
@@ -74,28 +74,6 @@ inline bool frame_fold2_shape_ok(const GemmDesc &d, const float *W) {
     return frame_fold2_lds_bytes(d) <= 160 * 1024;
 }
 
-// Planner rule J and its launcher agree through this: the folded framing GEMM `d` (its LDS-resident kernel) followed by a plain
-// product over its rows (frame_fold_kernel<true>).
-// Opt-in (BN_FRAMEPAIR=1): correct, one launch and the spectrum's round trip less -- and slower: behind the K loop the block's eight
-// waves stage the second product's filter rows and run its epilogue with the CU to themselves, 68.4 us against 50 + 19 at batch 32 and
-// 63 against 56 us of marginal cost, where the separate launch spreads the same work over the chip beside the other contexts' kernels
-inline bool frame_fold_pair_ok(const GemmDesc &d, const GemmDesc &d2) {
-    if (sw_int(sw::BN_FRAMEPAIR) != 1) return false;
-    if (!d.fold || !frame_fold_shape_ok(d, nullptr)) return false;
-    if (d.N > 128 || d.ldc != d.N) return false;
-    const int wn = std::max(2, (d.N + 31) / 32);
-    const int64_t span = (int64_t)(FRAME_BM_RULE - 1) * d.lda + d.fold_n;
-    if ((size_t)(((span + 3) & ~3) + 2 * FRAME_BM_RULE * GEMM_LD_RULE + 2 * 32 * wn * GEMM_LD_RULE) * sizeof(float) > 160 * 1024) return false;
-    // the second product's tiles must fit the two tile buffers: K tiles of the spectrum + one step of its filter rows
-    const int n2pad = (d2.N + 31) / 32 * 32;
-    if (wn * FRAME_BM_RULE * GEMM_LD_RULE + n2pad * GEMM_LD_RULE > 2 * FRAME_BM_RULE * GEMM_LD_RULE + 2 * 32 * wn * GEMM_LD_RULE) return false;
-    if (d2.N > 32 * wn || d2.N < 1 || d2.K != d.N || d2.lda != d2.K || d2.rows != d.rows || d2.a_bs != d.c_bs) return false;
-    if (d2.fold || d2.has_scale || d2.has_res || d2.se_inline) return false;
-    bool stages = stft_act_supported(d2.act);  // the compact stage functions only
-    for (int q = 0; q < d2.npost && q < 4; q++) stages = stages && stft_act_supported(d2.post_act[q]);
-    return stages && d2.npost <= 4;
-}
-
 // ---- LDS-DMA GEMM (gemm_dma.hip) ----------------------------------------------------------------------------------
 // epilogue activations the kernel carries (one dispatch on the launch-uniform code); other codes keep the older kernels
 BN_HD inline bool gemm_dma_act_ok(int act) { return act_in(ACT_SET_GEMM_DMA, act); }
@@ -108,8 +86,8 @@ inline size_t gemm_dma_lds_bytes(const GemmDesc &d, int mtw, int ntw, int wm, in
     return std::max((size_t)(ks * depth * (tr + bn) * 32 + gate_floats + se_floats), (size_t)((ks - 1) * wm * wn * mtw * ntw * 256)) * sizeof(float);
 }
 
-// which block family the LDS-DMA kernel would take for this GEMM (0 = not eligible; 1 / 2: one tile per block, 64- / 48-row tiles;
-// 3: the streaming form): per-sample quantities only
+// which block family the LDS-DMA kernel would take for this GEMM (0 = not eligible; 1 / 2: one tile per block, 64- / 48-row tiles):
+// per-sample quantities only
 inline int gemm_dma_shape(const GemmDesc &d) {
     const int mode = sw_int(sw::BN_GEMMDMA);
     if (mode == 0) return 0;
@@ -125,13 +103,6 @@ inline int gemm_dma_shape(const GemmDesc &d) {
     // vector instruction is taken from the budget the other contexts' matrix work needs (BN_GEMMDMA_SMALLN=0 keeps
     // them on the tiled kernel)
     const bool small_n = d.N <= 32 && d.has_scale && sw_int(sw::BN_GEMMDMA_SMALLN) != 0;
-    // Round 4: the expand convs of the late stages (K 64 .. 127 here, N >= 128, no gate, no residual) CAN take the streaming form of the
-    // kernel (gemm_dma_stream_kernel: a block walks consecutive row tiles, its ring never drains) -- family 3.  Opt-in (BN_GEMMSTREAM=1):
-    // measured EQUAL to the tiled kernel on these shapes (BirdNET v3.0, K = 112 -> N = 672: 37.4 - 38.0 against 37.5 us at batch 64, 125
-    // against 124 us at batch 256, i.e. 79 TF/s either way; K = 80 -> 480: 76 against 82 us at batch 256, 26.0 against 25.6 at 64) --
-    // removing the per-tile prologue does not move a launch that already runs at the rate every f32-MFMA kernel of this library
-    // reaches at saturation.  The default plan is unchanged (and so are its bits).
-    if (sw_int(sw::BN_GEMMSTREAM) != 0 && !d.has_scale && !d.has_res && !d.se_inline && d.K >= 64 && d.K < 128 && d.N >= 128 && d.rows % 32 == 0) return 3;
     if (mode != 2 && d.K < 128 && !small_n) return 0;
     if (d.rows % 32 == 0) return 1;  // 64- or 32-row tiles x up to 128 channels, waves along the rows
     if (d.rows % 48 == 0) return 2;  // 48-row tiles x 32 / 64 / 128 channels, waves along the channels
@@ -479,14 +450,7 @@ BN_HD inline StftLds stft_layout(const FftDesc &d, int nw, int slots) {
     l.total = o;
     return l;
 }
-// 16 waves x 512 slots where a frame fits 512 complex points (opt-in BN_STFT_NW=16: measured slower -- 128-register cap at
-// 16 waves: 156 B of scratch per lane; 74.6 vs 69.1 us), else 8 x 1024
-inline bool stft_wide(const FftDesc &d) {
-    if (sw_int(sw::BN_STFT_NW) != 16) return false;
-    return d.M <= 512 && d.tpb % (512 / d.M) == 0;
-}
-inline size_t stft_lds_bytes(const FftDesc &d, int /*nwaves*/) {
-    return (size_t)(stft_wide(d) ? stft_layout(d, 16, 512) : stft_layout(d, 8, 1024)).total * sizeof(float);
-}
+// 8 waves x 1024 slots
+inline size_t stft_lds_bytes(const FftDesc &d, int /*nwaves*/) { return (size_t)stft_layout(d, 8, 1024).total * sizeof(float); }
 
 }  // namespace bn

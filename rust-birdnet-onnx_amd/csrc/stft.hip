@@ -37,8 +37,7 @@ namespace bn {
 namespace {
 
 // complex slots of one wave's transform buffer: SLOTS / 16 blocks of 16 + 2 slots of padding each.  SLOTS = 1024 with 8 waves per
-// block, or 512 with 16 waves (M <= 512: one frame per wave at a time) -- the same LDS either way, but four waves per SIMD
-// instead of two to cover the LDS round trips and barriers the kernel is bound by
+// block
 
 __device__ __forceinline__ int phys(int i) { return i + 2 * (i >> 4); }
 
@@ -607,18 +606,15 @@ void register_stft_kernels() {
     register_dynamic_lds_kernel(reinterpret_cast<const void *>(stft_kernel<8, 1024, false, 1>));
     register_dynamic_lds_kernel(reinterpret_cast<const void *>(stft_kernel<8, 1024, false, 2>));
     register_dynamic_lds_kernel(reinterpret_cast<const void *>(stft_kernel<8, 1024, true, -1>));
-    register_dynamic_lds_kernel(reinterpret_cast<const void *>(stft_kernel<16, 512, true, -1>));
 }
 
 void launch_stft(hipStream_t s, const FftDesc &d, const StftPtrs &p, int64_t batch) {
     if (batch <= 0) return;
-    const bool wide = stft_wide(d);
     const size_t lds = stft_lds_bytes(d, 0);
     const int span = (d.tpb - 1) * d.hop + d.L;
     const bool pre = d.npre > 0;
     const int melm = d.nmel == 0 ? 0 : (d.mel_mode == 1 ? 2 : 1);
-    const void *fn = wide  ? reinterpret_cast<const void *>(stft_kernel<16, 512, true, -1>)
-                     : pre ? reinterpret_cast<const void *>(stft_kernel<8, 1024, true, -1>)
+    const void *fn = pre ? reinterpret_cast<const void *>(stft_kernel<8, 1024, true, -1>)
                      : melm == 0 ? reinterpret_cast<const void *>(stft_kernel<8, 1024, false, 0>)
                      : melm == 1 ? reinterpret_cast<const void *>(stft_kernel<8, 1024, false, 1>)
                                  : reinterpret_cast<const void *>(stft_kernel<8, 1024, false, 2>);
@@ -637,8 +633,7 @@ void launch_stft(hipStream_t s, const FftDesc &d, const StftPtrs &p, int64_t bat
     const int64_t total = (int64_t)tps * batch;
     const int ncu = device_cu_count();  // asked once per device by prepare_device(), never inside a stream capture
     const unsigned grid = (unsigned)std::min<int64_t>(total, ncu);  // one block per CU (LDS-bound), persistent over its tiles
-    if (wide) hipLaunchKernelGGL((stft_kernel<16, 512, true, -1>), dim3(grid), dim3(16 * 64), lds, s, dd, p, (int)total, tps);
-    else if (pre) hipLaunchKernelGGL((stft_kernel<8, 1024, true, -1>), dim3(grid), dim3(8 * 64), lds, s, dd, p, (int)total, tps);
+    if (pre) hipLaunchKernelGGL((stft_kernel<8, 1024, true, -1>), dim3(grid), dim3(8 * 64), lds, s, dd, p, (int)total, tps);
     else if (melm == 0) hipLaunchKernelGGL((stft_kernel<8, 1024, false, 0>), dim3(grid), dim3(8 * 64), lds, s, dd, p, (int)total, tps);
     else if (melm == 1) hipLaunchKernelGGL((stft_kernel<8, 1024, false, 1>), dim3(grid), dim3(8 * 64), lds, s, dd, p, (int)total, tps);
     else hipLaunchKernelGGL((stft_kernel<8, 1024, false, 2>), dim3(grid), dim3(8 * 64), lds, s, dd, p, (int)total, tps);

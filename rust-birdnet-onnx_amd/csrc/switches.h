@@ -51,7 +51,6 @@
     X(on_unless_0, BN_STFT_POWER,         true,   "0 keeps the power / magnitude pass behind a cos | sin bank a launch of its own") \
     X(integer,     BN_STFT_PAD,           1,      "0 keeps the zero-padded copy of the signal a padded framing conv reads") \
     X(integer,     BN_FRAME_PRE,          1,      "0: a folded framing GEMM does not take the signal's scalar chain into its span load") \
-    X(integer,     BN_FRAMEPAIR,          0,      "exactly 1: planner rule J, the product over a framing GEMM's rows in the same launch (measured slower)") \
     X(on_unless_0, BN_GEMMPOST,           true,   "0 keeps elementwise chains behind a GEMM out of its epilogue") \
     X(integer,     BN_GEMMGAP,            1,      "0 keeps GlobalAveragePool behind a 1x1 conv a launch of its own") \
     X(integer,     BN_SEGEMM,             0,      "exactly 1: squeeze-excite in the prologue of the project GEMM (measured slower, kept under test)") \
@@ -80,7 +79,6 @@
     X(integer,     BN_GEMMDMA,            1,      "LDS-DMA GEMM: 0 never, 2 every eligible shape (tests), otherwise where it pays") \
     X(integer,     BN_GEMMDMA_KS,         0,      "1 or 2: K slices of the LDS-DMA GEMM; otherwise by K") \
     X(integer,     BN_GEMMDMA_SMALLN,     1,      "0 keeps the gated project convs with N <= 32 on the tiled kernel") \
-    X(integer,     BN_GEMMSTREAM,         0,      "non-zero: late-stage expand convs take the streaming LDS-DMA form (measured equal)") \
     X(integer,     BN_SEGEMM_MAXC,        768,    "largest channel count whose excite products a GEMM block computes for itself (0 = never)") \
     X(integer,     BN_SPLITK_MINK,        256,    "smallest K the split-K GEMM takes (read once)") \
     X(integer,     BN_SPLITK_MAXROWS,     256,    "most rows per sample the split-K GEMM takes (read once)") \
@@ -93,11 +91,8 @@
     X(integer,     BN_MBMAP_WS_BANDS,     1,      "0 keeps the 8 x 32 map in two bands off the wave-specialised kernel") \
     X(integer,     BN_MBMAP_WS_TR,        1,      "0: a 32 x 8 map is not walked transposed by the banded wave-specialised kernel") \
     X(integer,     BN_MBMAP_WS_DEEP,      1,      "0 keeps the 16 x 4 map with eight K steps off the wave-specialised kernel") \
-    X(integer,     BN_STFT_NW,            8,      "exactly 16: sixteen waves per STFT block where a frame fits 512 complex points (measured slower)") \
     /* ---- launchers (*.hip): grids and tiles, never the arithmetic unless the row says so */ \
     X(int64,       BN_GEMMDMA_MINBLOCKS,  0,      "blocks a big tile must give before both LDS-DMA GEMMs take it; unset: 64, or 1 on a shared device") \
-    X(integer,     BN_GEMMSTREAM_TR,      0,      "exactly 128: 128-row tiles in the streaming LDS-DMA GEMM (measured slower)") \
-    X(integer,     BN_GEMMSTREAM_TPB,     0,      "positive: row tiles per block of the streaming LDS-DMA GEMM") \
     X(integer,     BN_GEMMB3_MT,          0,      "2, 3 or 4: 16-row tiles per block of the register-staged bf16x3 GEMM") \
     X(integer,     BN_GEMMB3_NTW,         0,      "channel tiles per wave of the register-staged bf16x3 GEMM: 1 never two, 2 two wherever the block shape allows") \
     X(integer,     BN_FORCE_BN,           0,      "32, 64, 96 or 128: N tile of the tiled GEMM (experiments; read once)") \
@@ -108,7 +103,6 @@
     X(integer,     BN_FRAME_WN,           0,      "2 .. 5: wave columns of the LDS-resident framing GEMM (experiments; read once)") \
     X(integer,     BN_FRAME_KS,           2,      "anything but 2: no K slices in the framing GEMM with three wave columns (other bits)") \
     X(integer,     BN_FRAME_WALK,         -1,     "0 / positive: a framing GEMM block never / always walks all N tiles of its rows; negative: from 256 row blocks") \
-    X(integer,     BN_FRAMEH,             1,      "0: round 3's form of the framing GEMM launch where no chain rides on it (bit-identical)") \
     X(integer,     BN_SEFC_G,             0,      "exactly 4: a block of the squeeze-excite FC kernel serves four samples; otherwise one (read per call)") \
     X(integer,     BN_MBPIPE,             -1,     "software-pipelined fused MBConv: 0 never, 1 always, otherwise by the shape (bit-identical)") \
     X(integer,     BN_MBMAP2_NCH,         0,      "positive: channel chunks per block of the small-map kernels") \

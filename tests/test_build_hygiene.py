@@ -2,7 +2,7 @@
 
 Round 3 found that the 5 x 5 row-streaming MBConv instances had been spilling 160-590 bytes per lane to scratch memory since round 2
 (BirdNET v3.0 lost 7 % to it) -- nothing in the test suite could see that.  This test reads the AMDGPU metadata notes of every HIP
-object file of the in-tree build (`.private_segment_fixed_size` per kernel) and fails if any kernel outside a short allow-list has a
+object file of the in-tree build (`.private_segment_fixed_size` per kernel) and fails if any kernel has a
 non-zero scratch size.  It needs the objects `make` leaves next to the sources and the LLVM binutils of the ROCm image; it is skipped
 where either is missing (the GPU box runs the prebuilt .so only)."""
 import glob
@@ -15,8 +15,6 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(os.path.dirname(HERE), "rust-birdnet-onnx_amd", "csrc")
 LLVM = "/opt/rocm/lib/llvm/bin"
-# opt-in experiment (BN_STFT_NW=16), documented as slower because of exactly this
-ALLOWED = [re.compile(r"stft_kernelILi16ELi512E")]
 
 
 def kernels_with_scratch(obj, tmp):
@@ -56,7 +54,7 @@ def test_no_kernel_uses_scratch_memory(tmp_path):
         if ks is None:
             continue
         seen += len(ks)
-        offenders += [(os.path.basename(obj), n, b) for n, b in ks if b > 0 and not any(p.search(n) for p in ALLOWED)]
+        offenders += [(os.path.basename(obj), n, b) for n, b in ks if b > 0]
     assert before == {o: (os.stat(o).st_mtime_ns, os.stat(o).st_size) for o in objs}, "the test touched the build's object files"
     assert seen > 200, f"only {seen} kernels found: the objects are not the HIP build"
     assert not offenders, "kernels with scratch memory (register spills): " + "; ".join(f"{o}:{n} {b} B" for o, n, b in offenders[:8])

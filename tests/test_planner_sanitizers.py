@@ -48,11 +48,11 @@ def test_reader_and_planner_under_asan_ubsan(asan_binary, tmp_path):
     assert r.stdout.count("none crashed") == 4 and r.stdout.count("  ok:") == 4, r.stdout
 
 
-# the planner rules of rounds 2-3, each flipped away from its default: rule I (BN_SEGEMM), rule J (BN_FRAMEPAIR), the FFT front end
+# the planner rules of rounds 2-3, each flipped away from its default: rule I (BN_SEGEMM), the FFT front end
 # forced on / off, the small-map and LDS-DMA kernels off, the row kernel off -- at the FULL model sizes the bench runs
 RULE_SETS = [
     {},
-    {"BN_SEGEMM": "1", "BN_FRAMEPAIR": "1", "BN_STFT": "1", "BN_STFT_MEL": "force", "BN_MBMAP3": "1", "BN_GEMMSTREAM": "1"},
+    {"BN_SEGEMM": "1", "BN_STFT": "1", "BN_STFT_MEL": "force", "BN_MBMAP3": "1"},
     {"BN_STFT": "0", "BN_MBMAP2": "0", "BN_GEMMDMA": "0", "BN_MBROW": "0", "BN_CONVFOLD": "0", "BN_GEMMPOST": "0"},
     {"BN_GEMMDMA": "2", "BN_MBFUSE": "force", "BN_MBMAP": "1", "BN_STFT_MELMFMA": "0", "BN_STFT_POWER": "0", "BN_REDUCE_SPLIT": "0"},
     # round 4: quarter fold / merged filters / span-load chain / pooled epilogue off (the round-3 plan), and merging forced wherever the pattern matches

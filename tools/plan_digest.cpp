@@ -76,7 +76,7 @@ static void print(const PlanOp &op, size_t k) {
     switch (op.kind) {
         case OpKind::ELT: print(op.elt); break;
         case OpKind::REDUCE: print(op.red); break;
-        case OpKind::GEMM: print("gemm", op.gemm); print(op.pre); print("gemm2", op.gemm2); print(op.se); break;
+        case OpKind::GEMM: print("gemm", op.gemm); print(op.pre); print(op.se); break;
         case OpKind::CONV: print(op.conv); break;
         case OpKind::DWCONV: print(op.dw); print(op.se); break;
         case OpKind::GAP: print(op.gap); break;
