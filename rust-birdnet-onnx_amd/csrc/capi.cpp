@@ -40,10 +40,7 @@ bn_status fail(bn_status st, const std::string &msg) {
 
 struct PlanDev {
     std::unique_ptr<Plan> plan;
-    float *d_consts = nullptr;
-    ~PlanDev() {
-        if (d_consts) (void)gated::Free(d_consts);
-    }
+    DeviceBuf<float> d_consts;
 };
 
 bool device_is_gfx950(int dev) {
@@ -152,10 +149,10 @@ struct bn_ctx {
     PlanDev *pd = nullptr;
     size_t max_batch = 0;
     uint32_t flags = 0;
-    hipStream_t stream = nullptr;
-    float *d_arena = nullptr;
-    float *d_input = nullptr;
-    float *h_out = nullptr;    // pinned staging for logits + embeddings
+    bn::Stream stream, copy_stream;  // before every buffer their work touches: they go last (device_mem.h)
+    DeviceBuf<float> d_arena;
+    DeviceBuf<float> d_input;
+    PinnedBuf<float> h_out;  // pinned staging for logits + embeddings
     size_t h_out_elems = 0;
     size_t device_bytes = 0;
     bool holds_model = false;  // counted in model->refs (set once creation succeeded)
@@ -163,8 +160,8 @@ struct bn_ctx {
     bool in_flight = false;  // a cancelled/timed-out run may still be executing
     size_t last_batch = 0;
     // top-K scratch
-    uint32_t *d_tk_idx = nullptr, *d_tk_cnt = nullptr, *d_tk_flags = nullptr;
-    float *d_tk_conf = nullptr;
+    DeviceBuf<uint32_t> d_tk_idx, d_tk_cnt, d_tk_flags;
+    DeviceBuf<float> d_tk_conf;
     size_t tk_cap = 0;  // elements of idx/conf
     // bn_step_device: the top-K rows of a step in one device block and one pinned mirror, so they cross the bus as ONE copy (each
     // async copy is a ~7 us blit launch); bn_infer_submit fills the device block too, its mirror is the slot's
@@ -178,15 +175,15 @@ struct bn_ctx {
     // in flight shares nothing with the synchronous entry points (bn_infer_windows / bn_step_*) but the arena and the
     // top-K block, and those are ordered by the context's stream.
     struct HostSlot {
-        float *d_input = nullptr, *h_input = nullptr, *h_out = nullptr;
+        DeviceBuf<float> d_input;
+        PinnedBuf<float> h_input, h_out;
         bn::TopkRows tk;  // pinned only
-        hipEvent_t h2d_done = nullptr, plan_done = nullptr, out_done = nullptr;
-        bool owned = false, used = false, busy = false;
+        bn::Event h2d_done, plan_done, out_done;
+        bool used = false, busy = false;
         uint64_t ticket = 0;
         size_t batch = 0, k = 0;
     };
     HostSlot slots[2];
-    hipStream_t copy_stream = nullptr;
     uint64_t next_ticket = 1;
     struct GraphKey {
         size_t batch;
@@ -199,6 +196,7 @@ struct bn_ctx {
     // bn_ctx_get_stats: how the plan reached the stream
     uint64_t n_captures = 0, n_instantiates = 0, n_replays = 0, n_eager_runs = 0, n_capture_fallbacks = 0, n_evictions = 0, n_input_copies = 0;
     std::string last_fallback;  // why the most recent capture did not become a graph
+    ~bn_ctx();  // waits, detaches and drops the model reference; the members free themselves
 };
 
 namespace {
@@ -486,7 +484,7 @@ bn_status make_plan(bn_model *m, const std::vector<int> &wanted, std::unique_ptr
     BN_HIP_TRY(bn::use_device(m->device));
     if (!prepare_device(m->device)) return fail(BN_ERR_BACKEND, "device " + std::to_string(m->device) + " refused the kernels' dynamic-LDS opt-in");
     const Plan &p = *pd->plan;
-    BN_HIP_TRY(gated::Malloc(&pd->d_consts, (size_t)p.consts_elems * sizeof(float)));
+    BN_HIP_TRY(pd->d_consts.alloc((size_t)p.consts_elems * sizeof(float)));
     for (size_t k = 0; k < p.consts.size(); k++)
         if (!p.consts[k].empty())
             BN_HIP_TRY(gated::Memcpy(pd->d_consts + p.const_off[k], p.consts[k].data(), p.consts[k].size() * sizeof(float), hipMemcpyHostToDevice));
@@ -679,20 +677,20 @@ bn_status bn_ctx_create(bn_model *m, size_t max_batch, uint32_t flags, bn_ctx **
     const Plan &p = *pd->plan;
     BN_HIP_TRY(bn::use_device(m->device));
     if (!prepare_device(m->device)) return fail(BN_ERR_BACKEND, "device " + std::to_string(m->device) + " refused the kernels' dynamic-LDS opt-in");
-    BN_HIP_TRY(gated::StreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    BN_HIP_TRY(c->stream.create(hipStreamNonBlocking));
     const size_t arena_b = (size_t)p.arena_elems * max_batch * sizeof(float);
     const size_t in_b = (size_t)p.sample_count * max_batch * sizeof(float);
-    BN_HIP_TRY(gated::Malloc(&c->d_arena, arena_b));
+    BN_HIP_TRY(c->d_arena.alloc(arena_b));
     // the squeeze-excite ticket counters live here and must start at zero; on the context's OWN stream (a legacy-stream
     // hipMemset would serialise against -- and be seen by -- whatever sibling contexts are capturing or running)
     BN_HIP_TRY(hipMemsetAsync(c->d_arena, 0, arena_b, c->stream));
-    BN_HIP_TRY(gated::Malloc(&c->d_input, in_b));
+    BN_HIP_TRY(c->d_input.alloc(in_b));
     {
         size_t row = (size_t)p.outputs[m->cfg.logits_output].row_elems;
         if (m->cfg.embedding_output >= 0) row += (size_t)p.outputs[m->cfg.embedding_output].row_elems;
         c->h_out_elems = row * max_batch;
     }
-    BN_HIP_TRY(gated::HostMalloc(&c->h_out, c->h_out_elems * sizeof(float), hipHostMallocDefault));
+    BN_HIP_TRY(c->h_out.alloc(c->h_out_elems * sizeof(float)));
     c->device_bytes = arena_b + in_b;
     m->refs.fetch_add(1, std::memory_order_relaxed);
     c->holds_model = true;
@@ -701,10 +699,7 @@ bn_status bn_ctx_create(bn_model *m, size_t max_batch, uint32_t flags, bn_ctx **
     if (m->cfg.model_type != BN_MODEL_GENERIC) {
         const size_t n = (size_t)p.outputs[m->cfg.logits_output].row_elems;
         bn_status st = ensure_step_block(c.get(), std::min<size_t>(32, n));
-        if (st != BN_OK) {
-            bn_ctx_destroy(c.release());
-            return st;
-        }
+        if (st != BN_OK) return st;
     }
     BN_HIP_TRY(hipStreamSynchronize(c->stream));  // arena zeroed before anyone captures or launches
     bn::device_context_count_add(m->device, 1);
@@ -713,44 +708,20 @@ bn_status bn_ctx_create(bn_model *m, size_t max_batch, uint32_t flags, bn_ctx **
     return BN_OK;
 }
 
-void bn_ctx_destroy(bn_ctx *c) {
-    if (!c) return;
-    if (c->counted) bn::device_context_count_add(c->model->device, -1);
-    (void)bn::use_device(c->model->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    bn::head_detach(c->head);
-    bn::prior_detach(c->prior);
-    bn::track_detach(c->track);
-    bn::match_detach(c->match);
-    for (auto &kv : c->graphs) (void)gated::GraphExecDestroy(kv.second);
-    if (c->d_arena) (void)gated::Free(c->d_arena);
-    if (c->d_input) (void)gated::Free(c->d_input);
-    if (c->h_out) (void)gated::HostFree(c->h_out);
-    if (c->d_tk_idx) (void)gated::Free(c->d_tk_idx);
-    if (c->d_tk_conf) (void)gated::Free(c->d_tk_conf);
-    if (c->d_tk_cnt) (void)gated::Free(c->d_tk_cnt);
-    if (c->d_tk_flags) (void)gated::Free(c->d_tk_flags);
-    c->step.release();
-    if (c->copy_stream) {
-        (void)hipStreamSynchronize(c->copy_stream);
-        (void)gated::StreamDestroy(c->copy_stream);
-    }
-    for (auto &sl : c->slots) {
-        if (sl.owned) {
-            if (sl.d_input) (void)gated::Free(sl.d_input);
-            if (sl.h_input) (void)gated::HostFree(sl.h_input);
-            if (sl.h_out) (void)gated::HostFree(sl.h_out);
-        }
-        sl.tk.release();
-        if (sl.h2d_done) (void)gated::EventDestroy(sl.h2d_done);
-        if (sl.plan_done) (void)gated::EventDestroy(sl.plan_done);
-        if (sl.out_done) (void)gated::EventDestroy(sl.out_done);
-    }
-    if (c->stream) (void)gated::StreamDestroy(c->stream);
-    bn_model *m = c->holds_model ? c->model : nullptr;
-    delete c;
-    model_unref(m);
+bn_ctx::~bn_ctx() {
+    if (counted) bn::device_context_count_add(model->device, -1);
+    if (model) (void)bn::use_device(model->device);
+    if (stream) (void)hipStreamSynchronize(stream);
+    bn::head_detach(head);
+    bn::prior_detach(prior);
+    bn::track_detach(track);
+    bn::match_detach(match);
+    for (auto &kv : graphs) (void)gated::GraphExecDestroy(kv.second);
+    if (copy_stream) (void)hipStreamSynchronize(copy_stream);
+    if (holds_model) model_unref(model);
 }
+
+void bn_ctx_destroy(bn_ctx *c) { delete c; }
 
 size_t bn_ctx_max_batch(const bn_ctx *c) { return c ? c->max_batch : 0; }
 
@@ -836,19 +807,18 @@ static bn_status ensure_step_block(bn_ctx *c, size_t k);
 
 static bn_status ensure_slot(bn_ctx *c, bn_ctx::HostSlot &sl, int index) {
     const Plan &p = *c->pd->plan;
-    if (!c->copy_stream) BN_HIP_TRY(gated::StreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-    if (!sl.h2d_done) {
-        BN_HIP_TRY(gated::EventCreateWithFlags(&sl.h2d_done, hipEventDisableTiming));
-        BN_HIP_TRY(gated::EventCreateWithFlags(&sl.plan_done, hipEventDisableTiming));
-        BN_HIP_TRY(gated::EventCreateWithFlags(&sl.out_done, hipEventDisableTiming));
+    if (!c->copy_stream) BN_HIP_TRY(c->copy_stream.create(hipStreamNonBlocking));
+    if (!sl.out_done) {  // the last of the three: a failed attempt is made again
+        BN_HIP_TRY(sl.h2d_done.create(hipEventDisableTiming));
+        BN_HIP_TRY(sl.plan_done.create(hipEventDisableTiming));
+        BN_HIP_TRY(sl.out_done.create(hipEventDisableTiming));
     }
-    if (sl.d_input) return BN_OK;
+    if (sl.h_out) return BN_OK;  // the last of the three, likewise
     (void)index;
     const size_t in_b = (size_t)p.sample_count * c->max_batch * sizeof(float);
-    sl.owned = true;
-    BN_HIP_TRY(gated::Malloc(&sl.d_input, in_b));
-    BN_HIP_TRY(gated::HostMalloc(&sl.h_input, in_b, hipHostMallocDefault));
-    BN_HIP_TRY(gated::HostMalloc(&sl.h_out, c->h_out_elems * sizeof(float), hipHostMallocDefault));
+    BN_HIP_TRY(sl.d_input.alloc(in_b));
+    BN_HIP_TRY(sl.h_input.alloc(in_b));
+    BN_HIP_TRY(sl.h_out.alloc(c->h_out_elems * sizeof(float)));
     c->device_bytes += in_b;
     return BN_OK;
 }
@@ -1083,8 +1053,8 @@ size_t bn_ctx_time_kernels(bn_ctx *c, size_t batch, char (*names)[BN_NAME_LEN], 
     const Plan &p = *c->pd->plan;
     if (bn::use_device(c->model->device) != hipSuccess) return 0;
     (void)hipStreamSynchronize(c->stream);
-    std::vector<hipEvent_t> ev(p.ops.size() + 1);
-    for (auto &e : ev) (void)gated::EventCreate(&e);
+    std::vector<bn::Event> ev(p.ops.size() + 1);
+    for (auto &e : ev) (void)e.create();
     // warm (instruction caches, clocks) then measure
     for (auto &op : p.ops) launch_op(c, op, c->d_input, (int64_t)batch);
     (void)hipEventRecord(ev[0], c->stream);
@@ -1100,8 +1070,8 @@ size_t bn_ctx_time_kernels(bn_ctx *c, size_t batch, char (*names)[BN_NAME_LEN], 
     float overhead_us = 0.0f;
     {
         constexpr int NCAL = 16;
-        hipEvent_t ce[NCAL + 1];
-        for (auto &e : ce) (void)gated::EventCreate(&e);
+        bn::Event ce[NCAL + 1];
+        for (auto &e : ce) (void)e.create();
         launch_null(c->stream);
         (void)hipEventRecord(ce[0], c->stream);
         for (int k = 0; k < NCAL; k++) {
@@ -1117,7 +1087,6 @@ size_t bn_ctx_time_kernels(bn_ctx *c, size_t batch, char (*names)[BN_NAME_LEN], 
         }
         std::sort(iv.begin(), iv.end());
         overhead_us = std::max(0.0f, iv[NCAL / 2] - 3.6f);
-        for (auto &e : ce) (void)gated::EventDestroy(e);
     }
     (void)hipStreamSynchronize(c->stream);
     for (size_t k = 0; k < p.ops.size() && k < cap; k++) {
@@ -1131,7 +1100,6 @@ size_t bn_ctx_time_kernels(bn_ctx *c, size_t batch, char (*names)[BN_NAME_LEN], 
         if (macs) macs[k] = (p.ops[k].macs + p.ops[k].macs_mfma_extra + p.ops[k].macs_valu_extra) * (double)batch;
         if (bytes) bytes[k] = p.ops[k].bytes * (double)batch + p.ops[k].weight_bytes;
     }
-    for (auto &e : ev) (void)gated::EventDestroy(e);
     return p.ops.size();
 }
 
@@ -1201,16 +1169,14 @@ bn_status bn_topk(bn_ctx *c, size_t batch, size_t top_k, int32_t has_min, float 
 static bn_status ensure_topk_buffers(bn_ctx *c, size_t k) {
     const size_t need = c->max_batch * k;
     if (need > c->tk_cap) {
-        if (c->d_tk_idx) (void)gated::Free(c->d_tk_idx);
-        if (c->d_tk_conf) (void)gated::Free(c->d_tk_conf);
-        c->d_tk_idx = nullptr;
-        c->d_tk_conf = nullptr;
-        BN_HIP_TRY(gated::Malloc(&c->d_tk_idx, need * sizeof(uint32_t)));
-        BN_HIP_TRY(gated::Malloc(&c->d_tk_conf, need * sizeof(float)));
+        c->d_tk_idx.reset();  // both go before either comes back, as ever
+        c->d_tk_conf.reset();
+        BN_HIP_TRY(c->d_tk_idx.alloc(need * sizeof(uint32_t)));
+        BN_HIP_TRY(c->d_tk_conf.alloc(need * sizeof(float)));
         c->tk_cap = need;
     }
-    if (!c->d_tk_cnt) BN_HIP_TRY(gated::Malloc(&c->d_tk_cnt, c->max_batch * sizeof(uint32_t)));
-    if (!c->d_tk_flags) BN_HIP_TRY(gated::Malloc(&c->d_tk_flags, c->max_batch * sizeof(uint32_t)));
+    if (!c->d_tk_cnt) BN_HIP_TRY(c->d_tk_cnt.alloc(c->max_batch * sizeof(uint32_t)));
+    if (!c->d_tk_flags) BN_HIP_TRY(c->d_tk_flags.alloc(c->max_batch * sizeof(uint32_t)));
     return BN_OK;
 }
 
@@ -1399,19 +1365,13 @@ bn_status bn_topk_device(int32_t device, const float *d_logits, size_t rows, siz
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(BN_ERR_NO_DEVICE, "no HIP device is visible; this path has no CPU fallback");
     BN_HIP_TRY(bn::use_device(device));
     if (!prepare_device(device)) return fail(BN_ERR_BACKEND, "device refused the kernels' dynamic-LDS opt-in");
-    uint32_t *d_idx = nullptr, *d_cnt = nullptr, *d_flags = nullptr;
-    float *d_conf = nullptr;
-    BN_HIP_TRY(gated::Malloc(&d_idx, rows * k * sizeof(uint32_t)));
-    BN_HIP_TRY(gated::Malloc(&d_conf, rows * k * sizeof(float)));
-    BN_HIP_TRY(gated::Malloc(&d_cnt, rows * sizeof(uint32_t)));
-    BN_HIP_TRY(gated::Malloc(&d_flags, rows * sizeof(uint32_t)));
-    bn_status st = topk_run(device, nullptr, d_logits, rows, n, top_k, has_min, min_conf, k_stride, d_idx, d_conf, d_cnt, d_flags, idx_out, conf_out,
-                            count_out);
-    (void)gated::Free(d_idx);
-    (void)gated::Free(d_conf);
-    (void)gated::Free(d_cnt);
-    (void)gated::Free(d_flags);
-    return st;
+    DeviceBuf<uint32_t> d_idx, d_cnt, d_flags;
+    DeviceBuf<float> d_conf;
+    BN_HIP_TRY(d_idx.alloc(rows * k * sizeof(uint32_t)));
+    BN_HIP_TRY(d_conf.alloc(rows * k * sizeof(float)));
+    BN_HIP_TRY(d_cnt.alloc(rows * sizeof(uint32_t)));
+    BN_HIP_TRY(d_flags.alloc(rows * sizeof(uint32_t)));
+    return topk_run(device, nullptr, d_logits, rows, n, top_k, has_min, min_conf, k_stride, d_idx, d_conf, d_cnt, d_flags, idx_out, conf_out, count_out);
 }
 
 bn_status bn_topk_host(int32_t device, const float *logits, size_t rows, size_t n, size_t top_k, int32_t has_min, float min_conf,
@@ -1426,23 +1386,18 @@ bn_status bn_topk_host(int32_t device, const float *logits, size_t rows, size_t 
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(BN_ERR_NO_DEVICE, "no HIP device is visible; this path has no CPU fallback");
     BN_HIP_TRY(bn::use_device(device));
-    float *d = nullptr;
-    BN_HIP_TRY(gated::Malloc(&d, rows * n * sizeof(float)));
+    DeviceBuf<float> d;
+    BN_HIP_TRY(d.alloc(rows * n * sizeof(float)));
     hipError_t e = gated::Memcpy(d, logits, rows * n * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)gated::Free(d);
-        return fail(BN_ERR_BACKEND, std::string("hipMemcpy: ") + hipGetErrorString(e));
-    }
-    bn_status st = bn_topk_device(device, d, rows, n, top_k, has_min, min_conf, k_stride, idx_out, conf_out, count_out);
-    (void)gated::Free(d);
-    return st;
+    if (e != hipSuccess) return fail(BN_ERR_BACKEND, std::string("hipMemcpy: ") + hipGetErrorString(e));
+    return bn_topk_device(device, d, rows, n, top_k, has_min, min_conf, k_stride, idx_out, conf_out, count_out);
 }
 
 // ---- recording-level ingest (birdnet-analyze.rs:683-687, 707-743) ----
 struct bn_recording {
     int32_t device = 0;
     int32_t format = BN_PCM_I16;
-    void *d_pcm = nullptr;
+    DeviceBuf<void> d_pcm;
     size_t n_samples = 0;
     // asynchronous upload (bn_recording_create_async): a thread of the recording's own copies the caller's buffer chunk by chunk
     // (synchronous copies under the capture gate, like every other copy of the library); chunks_done chunks are on the device
@@ -1453,6 +1408,10 @@ struct bn_recording {
     std::thread uploader;
     std::mutex mu;
     std::condition_variable cv;
+    ~bn_recording() {
+        if (uploader.joinable()) uploader.join();  // (the caller's buffer is read until here at the latest)
+        (void)bn::use_device(device);
+    }
 };
 
 namespace {
@@ -1481,13 +1440,10 @@ bn_status bn_recording_create(int32_t device, const void *pcm, size_t n_samples,
     r->format = format;
     r->n_samples = n_samples;
     const size_t bytes = n_samples * (format == BN_PCM_I16 ? sizeof(int16_t) : sizeof(float));
-    BN_HIP_TRY(gated::Malloc(&r->d_pcm, std::max<size_t>(bytes, 16)));
+    BN_HIP_TRY(r->d_pcm.alloc(std::max<size_t>(bytes, 16)));
     if (bytes) {
         hipError_t e = gated::Memcpy(r->d_pcm, pcm, bytes, hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            (void)gated::Free(r->d_pcm);
-            return fail(BN_ERR_BACKEND, std::string("recording upload failed: ") + hipGetErrorString(e));
-        }
+        if (e != hipSuccess) return fail(BN_ERR_BACKEND, std::string("recording upload failed: ") + hipGetErrorString(e));
     }
     *out = r.release();
     return BN_OK;
@@ -1509,7 +1465,7 @@ bn_status bn_recording_create_async(int32_t device, const void *pcm, size_t n_sa
     r->device = device;
     r->format = format;
     r->n_samples = n_samples;
-    BN_HIP_TRY(gated::Malloc(&r->d_pcm, std::max<size_t>(n_samples * esz, 16)));
+    BN_HIP_TRY(r->d_pcm.alloc(std::max<size_t>(n_samples * esz, 16)));
     r->chunk_samples = std::max<size_t>(1, (chunk_mb << 20) / esz);
     r->n_chunks = (n_samples + r->chunk_samples - 1) / r->chunk_samples;
     bn_recording *raw = r.get();
@@ -1519,7 +1475,7 @@ bn_status bn_recording_create_async(int32_t device, const void *pcm, size_t n_sa
             for (size_t k = 0; k < raw->n_chunks && raw->upload_error.load() == 0; k++) {
                 const size_t a = k * raw->chunk_samples, n = std::min(raw->chunk_samples, raw->n_samples - a);
                 // a synchronous copy of its own kind (null stream; the contexts' streams are non-blocking and do not wait for it)
-                if (gated::Memcpy(static_cast<char *>(raw->d_pcm) + a * esz, static_cast<const char *>(pcm) + a * esz, n * esz, hipMemcpyHostToDevice) != hipSuccess) {
+                if (gated::Memcpy(static_cast<char *>(raw->d_pcm.get()) + a * esz, static_cast<const char *>(pcm) + a * esz, n * esz, hipMemcpyHostToDevice) != hipSuccess) {
                     (void)hipGetLastError();
                     raw->upload_error.store(1);
                 }
@@ -1536,8 +1492,6 @@ bn_status bn_recording_create_async(int32_t device, const void *pcm, size_t n_sa
             }
         });
     } catch (const std::exception &e) {  // std::system_error from the thread constructor must not cross the C boundary
-        (void)gated::Free(r->d_pcm);
-        r->d_pcm = nullptr;
         return fail(BN_ERR_BACKEND, std::string("could not start the upload thread: ") + e.what());
     }
     *out = r.release();
@@ -1631,22 +1585,18 @@ bn_status bn_recording_create_resampled(int32_t device, const void *pcm, size_t 
     r->device = device;
     r->format = BN_PCM_F32;
     r->n_samples = n_dst;
-    float *d_table = nullptr;
-    hipError_t e = gated::Malloc(&r->d_pcm, std::max<size_t>(n_dst * sizeof(float), 16));
-    if (e == hipSuccess) e = gated::Malloc(reinterpret_cast<void **>(&d_table), t.coef.size() * sizeof(float));
+    DeviceBuf<float> d_table;
+    hipError_t e = r->d_pcm.alloc(std::max<size_t>(n_dst * sizeof(float), 16));
+    if (e == hipSuccess) e = d_table.alloc(t.coef.size() * sizeof(float));
     if (e == hipSuccess) e = gated::Memcpy(d_table, t.coef.data(), t.coef.size() * sizeof(float), hipMemcpyHostToDevice);
     if (e == hipSuccess) {
         (void)hipGetLastError();
-        launch_resample(nullptr, static_cast<float *>(r->d_pcm), src->d_pcm, format == BN_PCM_I16, d_table, n_samples, n_dst, t.L, t.M, t.T);
+        launch_resample(nullptr, static_cast<float *>(r->d_pcm.get()), src->d_pcm, format == BN_PCM_I16, d_table, n_samples, n_dst, t.L, t.M, t.T);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = gated::DeviceSynchronize();
-    if (d_table) (void)gated::Free(d_table);
     bn_recording_free(src);
-    if (e != hipSuccess) {
-        if (r->d_pcm) (void)gated::Free(r->d_pcm);
-        return fail(BN_ERR_BACKEND, std::string("resampling failed: ") + hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return fail(BN_ERR_BACKEND, std::string("resampling failed: ") + hipGetErrorString(e));
     *out = r.release();
     return BN_OK;
 }
@@ -1658,17 +1608,11 @@ bn_status bn_recording_read_f32(const bn_recording *r, size_t first, size_t coun
     if (count == 0) return BN_OK;
     if (!recording_wait_samples(r, first + count - 1)) return fail(BN_ERR_BACKEND, "recording upload failed");
     BN_HIP_TRY(bn::use_device(r->device));
-    BN_HIP_TRY(gated::Memcpy(host_out, static_cast<const float *>(r->d_pcm) + first, count * sizeof(float), hipMemcpyDeviceToHost));
+    BN_HIP_TRY(gated::Memcpy(host_out, static_cast<const float *>(r->d_pcm.get()) + first, count * sizeof(float), hipMemcpyDeviceToHost));
     return BN_OK;
 }
 
-void bn_recording_free(bn_recording *r) {
-    if (!r) return;
-    if (r->uploader.joinable()) r->uploader.join();  // (the caller's buffer is read until here at the latest)
-    (void)bn::use_device(r->device);
-    if (r->d_pcm) (void)gated::Free(r->d_pcm);
-    delete r;
-}
+void bn_recording_free(bn_recording *r) { delete r; }
 
 size_t bn_recording_samples(const bn_recording *r) { return r ? r->n_samples : 0; }
 
@@ -1695,14 +1639,13 @@ bn_status bn_recording_windows(const bn_recording *r, size_t segment_samples, si
     if (count == 0) return BN_OK;
     if (!host_out) return fail(BN_ERR_INVALID_ARG, "null host buffer");
     BN_HIP_TRY(bn::use_device(r->device));
-    float *d = nullptr;
-    BN_HIP_TRY(gated::Malloc(reinterpret_cast<void **>(&d), count * segment_samples * sizeof(float)));
+    DeviceBuf<float> d;
+    BN_HIP_TRY(d.alloc(count * segment_samples * sizeof(float)));
     (void)hipGetLastError();
     launch_windows(nullptr, d, r->d_pcm, r->format == BN_PCM_I16, r->n_samples, (uint64_t)first_window * step_samples, step_samples, (uint32_t)segment_samples,
                    (uint32_t)count);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = gated::Memcpy(host_out, d, count * segment_samples * sizeof(float), hipMemcpyDeviceToHost);
-    (void)gated::Free(d);
     if (e != hipSuccess) return fail(BN_ERR_BACKEND, std::string("window kernel failed: ") + hipGetErrorString(e));
     return BN_OK;
 }

@@ -2,6 +2,7 @@
 // the packed top-K block TopkRows, results_to_host, the pinned ring PinnedRing, scoped scratch: step_common.cpp), what they need of
 // capi.cpp's private state (index.hip: bn_index_* and the host side every search over an index shares; head.hip: bn_head_*; rank.hip: bn_head_rank_index; cluster.hip: bn_index_assign, bn_index_cluster; live.cpp: bn_step_live) and of each other (prior.hip:
 // bn_prior_*; track.hip: bn_track_*).  A step's rows reach its stages as an argument (StepRows), never through a context's state.
+// Every device buffer, pinned buffer, stream and event is a member of device_mem.h's owner types: a handle's destructor waits, its members free.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -13,7 +14,7 @@
 #include <vector>
 
 #include "../../include/birdnet_hip.h"
-#include "hip_gate.h"
+#include "device_mem.h"
 #include "last_error.h"
 
 // a failed runtime call ends the enclosing function with BN_ERR_BACKEND and the call's text in the message
@@ -51,7 +52,8 @@ struct TopkRows {
         const uint32_t *count;
         size_t k;
     };
-    uint32_t *d = nullptr, *h = nullptr;
+    DeviceBuf<uint32_t> d;
+    PinnedBuf<uint32_t> h;
     size_t cap = 0;                     // words
     size_t last_batch = 0, last_k = 0;  // the rows last enqueued into the block (mark); last_k == 0: none since it was (re)allocated
 
@@ -88,8 +90,9 @@ bn_status enqueue_topk_rows(hipStream_t stream, const float *d_logits, size_t ro
 // acquired but not committed (the enqueue failed) is the next acquire's.
 struct PinnedRing {
     static constexpr int SLOTS = 4;
-    void *h[SLOTS] = {}, *d[SLOTS] = {};  // a block and its device alias
-    hipEvent_t ev[SLOTS] = {};
+    PinnedBuf<void> h[SLOTS];
+    void *d[SLOTS] = {};  // a block's device alias
+    Event ev[SLOTS];
     bool busy[SLOTS] = {};  // ev was recorded behind a reader of the block
     int next = 0;
 
@@ -103,19 +106,25 @@ struct PinnedRing {
 // device buffers, one pinned buffer and a stream of one call: on every way out the stream is waited for, the buffers freed and the
 // stream, if owned, destroyed
 struct Scratch {
-    std::vector<void *> ptrs;
-    void *pinned = nullptr;
-    hipStream_t stream = nullptr;
-    bool owns_stream = false;
-    Scratch() = default;
-    Scratch(const Scratch &) = delete;
-    Scratch &operator=(const Scratch &) = delete;
-    ~Scratch();
+    Stream own_stream;              // the stream, if it is the call's own
+    hipStream_t stream = nullptr;   // the stream that uses the buffers: own_stream or the caller's
+    std::vector<DeviceBuf<void>> bufs;
+    PinnedBuf<void> pinned;
+    ~Scratch() {
+        if (stream) (void)hipStreamSynchronize(stream);
+    }
+    hipError_t create_stream(unsigned flags) {
+        hipError_t e = own_stream.create(flags);
+        stream = own_stream;
+        return e;
+    }
     template <class T>
     hipError_t alloc(T **p, size_t bytes, bool zero = false) {
-        hipError_t e = gated::Malloc(p, bytes);
+        DeviceBuf<void> b;
+        hipError_t e = b.alloc(bytes);
         if (e != hipSuccess) return e;
-        ptrs.push_back(*p);
+        *p = static_cast<T *>(b.get());
+        bufs.push_back(std::move(b));
         return zero ? hipMemsetAsync(*p, 0, bytes, stream) : hipSuccess;  // on the stream that uses the buffer: ordered before every kernel
     }
 };

@@ -355,23 +355,17 @@ __global__ __launch_bounds__(256) void cluster_pick_kernel(const Pick *__restric
 // an index's clustering buffers: each allocated when a call first needs it, grown when a call needs more (the centroids [k, dpad]
 // and the running best planes by row id are the base's)
 struct bn::ClusterState : bn::cluster::AssignBufs {
-    uint32_t *d_prev_i = nullptr, *d_members = nullptr;  // the previous assignment; the member lists
+    bn::DeviceBuf<uint32_t> d_prev_i, d_members;  // the previous assignment; the member lists
     size_t list_n = 0;
-    uint32_t *d_small = nullptr;  // counts [K_MAX], offsets [K_MAX + 1], scalars [2] (moved, kept centroids), start ids [K_MAX]
-    Pick *d_pick = nullptr;       // [ARG_BLOCKS]
-    double *d_acc = nullptr;      // [k, dpad]
+    bn::DeviceBuf<uint32_t> d_small;  // counts [K_MAX], offsets [K_MAX + 1], scalars [2] (moved, kept centroids), start ids [K_MAX]
+    bn::DeviceBuf<Pick> d_pick;       // [ARG_BLOCKS]
+    bn::DeviceBuf<double> d_acc;      // [k, dpad]
     size_t acc_n = 0;
-    double *d_part = nullptr;  // [k, slots, dpad]
+    bn::DeviceBuf<double> d_part;  // [k, slots, dpad]
     size_t part_n = 0;
 };
 
-void bn::cluster_state_free(ClusterState *s) {
-    if (!s) return;
-    for (void *p : {(void *)s->d_cent, (void *)s->d_best_s, (void *)s->d_best_i, (void *)s->d_prev_i, (void *)s->d_members, (void *)s->d_small, (void *)s->d_pick,
-                    (void *)s->d_acc, (void *)s->d_part})
-        if (p) (void)bn::gated::Free(p);
-    delete s;
-}
+void bn::cluster_state_free(ClusterState *s) { delete s; }
 
 namespace {
 
@@ -382,12 +376,10 @@ constexpr size_t SMALL_COUNTS = 0, SMALL_OFFSETS = K_MAX, SMALL_SCALARS = 2 * K_
 
 // room for n elements; the stream is idle between calls, so the old block is free to go
 template <class T>
-hipError_t ensure(T *&p, size_t &have, size_t n) {
+hipError_t ensure(bn::DeviceBuf<T> &p, size_t &have, size_t n) {
     if (n <= have) return hipSuccess;
-    if (p) (void)bn::gated::Free(p);
-    p = nullptr;
     have = 0;
-    hipError_t e = bn::gated::Malloc(&p, n * sizeof(T));
+    hipError_t e = p.alloc(n * sizeof(T));  // the old block goes first
     if (e == hipSuccess) have = n;
     return e;
 }
@@ -450,7 +442,9 @@ bn_status enqueue_pass(AssignBufs *cs, const bn::IndexScan &s, const Range &r, s
     const float *W = cs->d_cent + c0 * s.dpad;
     uint32_t lo = r.id_lo, hi = r.id_hi, d = (uint32_t)s.dpad, cc0 = (uint32_t)c0, tl = r.tile_lo, th = r.tile_hi, tpw = r.tpw;
     int first = first_pass ? 1 : 0;
-    void *args[] = {(void *)&s.slab, (void *)&s.valid, &lo, &hi, &d, (void *)&W, &nc, &cc0, &first, &tl, &th, &tpw, &cs->d_best_s, &cs->d_best_i};
+    float *best_s = cs->d_best_s;
+    uint32_t *best_i = cs->d_best_i;
+    void *args[] = {(void *)&s.slab, (void *)&s.valid, &lo, &hi, &d, (void *)&W, &nc, &cc0, &first, &tl, &th, &tpw, &best_s, &best_i};
     BN_HIP_TRY(hipLaunchKernel(scan_of((nc + 15) / 16), dim3(r.n_wg), dim3(256), args, SCAN_LDS, s.stream));
     return BN_OK;
 }
@@ -589,8 +583,8 @@ extern "C" bn_status bn_index_cluster(bn_index *x, size_t k, uint64_t first_id, 
         BN_HIP_TRY(ensure(cs->d_members, b, rows));
         cs->list_n = rows;
     }
-    if (!cs->d_small) BN_HIP_TRY(bn::gated::Malloc(&cs->d_small, SMALL_N * sizeof(uint32_t)));
-    if (!cs->d_pick) BN_HIP_TRY(bn::gated::Malloc(&cs->d_pick, ARG_BLOCKS * sizeof(Pick)));
+    if (!cs->d_small) BN_HIP_TRY(cs->d_small.alloc(SMALL_N * sizeof(uint32_t)));
+    if (!cs->d_pick) BN_HIP_TRY(cs->d_pick.alloc(ARG_BLOCKS * sizeof(Pick)));
     const size_t dpad = s.dpad;
     const uint32_t slots = (uint32_t)std::max<size_t>(1, std::min<size_t>(64, PART_BYTES / (k * dpad * sizeof(double))));
     BN_HIP_TRY(ensure(cs->d_acc, cs->acc_n, k * dpad));

@@ -15,10 +15,10 @@ constexpr size_t K_MAX = 1024;  // most centroids of a call
 
 // the centroids [k, dpad] and the running best planes (by row id, whole tiles) one assignment works on
 struct AssignBufs {
-    float *d_cent = nullptr;
+    DeviceBuf<float> d_cent;
     size_t cent_n = 0;
-    float *d_best_s = nullptr;
-    uint32_t *d_best_i = nullptr;
+    DeviceBuf<float> d_best_s;
+    DeviceBuf<uint32_t> d_best_i;
     size_t best_n = 0;
 };
 

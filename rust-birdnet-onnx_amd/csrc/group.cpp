@@ -85,15 +85,21 @@ struct bn_group {
         bn_model *model = nullptr;
         int device = 0;
         std::vector<bn_ctx *> ctxs;
-        hipStream_t stream = nullptr;  // staging copies + the collective
-        float *d_logits = nullptr;     // [world * per_rank, N]: this rank's slab is filled locally, the rest by the gather
-        uint32_t *d_topk = nullptr;    // [world * per_rank, 2k + 1] packed rows: idx[k] | conf[k] | count
+        bn::Stream stream;              // staging copies + the collective
+        bn::DeviceBuf<float> d_logits;  // [world * per_rank, N]: this rank's slab is filled locally, the rest by the gather
+        bn::DeviceBuf<uint32_t> d_topk;  // [world * per_rank, 2k + 1] packed rows: idx[k] | conf[k] | count
         size_t cap_rows = 0, cap_k = 0, cap_rows_logits = 0;
         void *comm = nullptr;
         std::string error;
         bn_status status = BN_OK;
+        ~Rank() {
+            for (bn_ctx *c : ctxs) bn_ctx_destroy(c);
+            (void)bn::use_device(device);
+            if (comm && rccl().ok()) (void)rccl().CommDestroy(comm);
+        }
     };
-    std::vector<Rank> ranks;
+    std::vector<Rank> ranks;  // sized once, by the constructor: a Rank does not move
+    explicit bn_group(size_t n) : ranks(n) {}
     size_t max_batch = 0;
     size_t N = 0;
     bn_model_config cfg{};
@@ -109,10 +115,8 @@ bn_status gfail(bn_status st, const std::string &msg) {
 
 void free_rank_buffers(bn_group::Rank &r) {
     (void)bn::use_device(r.device);
-    if (r.d_logits) (void)gated::Free(r.d_logits);
-    if (r.d_topk) (void)gated::Free(r.d_topk);
-    r.d_logits = nullptr;
-    r.d_topk = nullptr;
+    r.d_logits.reset();
+    r.d_topk.reset();
     r.cap_rows = r.cap_k = r.cap_rows_logits = 0;
 }
 
@@ -137,9 +141,8 @@ bn_status bn_group_create(bn_model *const *models, const int32_t *devices, int32
     if (!models || !devices || !out || n <= 0) return gfail(BN_ERR_INVALID_ARG, "null argument / empty group");
     *out = nullptr;
     if (max_batch == 0 || contexts_per_device <= 0 || contexts_per_device > 8) return gfail(BN_ERR_INVALID_ARG, "max_batch must be positive, contexts_per_device in 1..8");
-    auto g = std::make_unique<bn_group>();
+    auto g = std::make_unique<bn_group>((size_t)n);
     g->max_batch = max_batch;
-    g->ranks.resize((size_t)n);
     std::set<int> distinct;
     for (int r = 0; r < n; r++) {
         if (!models[r]) return gfail(BN_ERR_INVALID_ARG, "model " + std::to_string(r) + " is null");
@@ -155,24 +158,16 @@ bn_status bn_group_create(bn_model *const *models, const int32_t *devices, int32
         g->ranks[(size_t)r].device = devices[r];
         distinct.insert(devices[r]);
     }
-    auto cleanup = [&](bn_status st, const std::string &msg) {
-        for (auto &rk : g->ranks) {
-            for (bn_ctx *c : rk.ctxs) bn_ctx_destroy(c);
-            if (rk.stream) { (void)bn::use_device(rk.device); (void)gated::StreamDestroy(rk.stream); }
-            if (rk.comm && rccl().ok()) (void)rccl().CommDestroy(rk.comm);
-        }
-        return gfail(st, msg);
-    };
     for (auto &rk : g->ranks) {
-        if (bn::use_device(rk.device) != hipSuccess) return cleanup(BN_ERR_NO_DEVICE, "device " + std::to_string(rk.device) + " is not usable");
-        if (gated::StreamCreateWithFlags(&rk.stream, hipStreamNonBlocking) != hipSuccess) return cleanup(BN_ERR_BACKEND, "hipStreamCreate failed");
+        if (bn::use_device(rk.device) != hipSuccess) return gfail(BN_ERR_NO_DEVICE, "device " + std::to_string(rk.device) + " is not usable");
+        if (rk.stream.create(hipStreamNonBlocking) != hipSuccess) return gfail(BN_ERR_BACKEND, "hipStreamCreate failed");
         for (int k = 0; k < contexts_per_device; k++) {
             bn_ctx *c = nullptr;
             bn_status st = bn_ctx_create(rk.model, max_batch, BN_CTX_DEFAULT, &c);
             if (st != BN_OK) {
                 char msg[512];
                 bn_last_error(msg, sizeof(msg));
-                return cleanup(st, std::string("bn_ctx_create: ") + msg);
+                return gfail(st, std::string("bn_ctx_create: ") + msg);
             }
             rk.ctxs.push_back(c);
         }
@@ -180,7 +175,7 @@ bn_status bn_group_create(bn_model *const *models, const int32_t *devices, int32
     {
         const float *dp = nullptr;
         size_t row = 0;
-        if (bn_ctx_output_device(g->ranks[0].ctxs[0], g->cfg.logits_output, &dp, &row) != BN_OK) return cleanup(BN_ERR_BACKEND, "logits output not planned");
+        if (bn_ctx_output_device(g->ranks[0].ctxs[0], g->cfg.logits_output, &dp, &row) != BN_OK) return gfail(BN_ERR_BACKEND, "logits output not planned");
         g->N = row;
     }
     // RCCL only for n > 1 ranks on pairwise distinct devices (one communicator per device in this process)
@@ -193,7 +188,7 @@ bn_status bn_group_create(bn_model *const *models, const int32_t *devices, int32
             std::vector<void *> comms((size_t)n, nullptr);
             std::vector<int> devs(devices, devices + n);
             const int res = rc.CommInitAll(comms.data(), n, devs.data());
-            if (res != 0) return cleanup(BN_ERR_BACKEND, std::string("ncclCommInitAll: ") + (rc.GetErrorString ? rc.GetErrorString(res) : "error"));
+            if (res != 0) return gfail(BN_ERR_BACKEND, std::string("ncclCommInitAll: ") + (rc.GetErrorString ? rc.GetErrorString(res) : "error"));
             for (int r = 0; r < n; r++) g->ranks[(size_t)r].comm = comms[(size_t)r];
             g->use_rccl = true;
         }
@@ -202,16 +197,7 @@ bn_status bn_group_create(bn_model *const *models, const int32_t *devices, int32
     return BN_OK;
 }
 
-void bn_group_destroy(bn_group *g) {
-    if (!g) return;
-    for (auto &rk : g->ranks) {
-        for (bn_ctx *c : rk.ctxs) bn_ctx_destroy(c);
-        free_rank_buffers(rk);
-        if (rk.comm && rccl().ok()) (void)rccl().CommDestroy(rk.comm);
-        if (rk.stream) { (void)bn::use_device(rk.device); (void)gated::StreamDestroy(rk.stream); }
-    }
-    delete g;
-}
+void bn_group_destroy(bn_group *g) { delete g; }
 
 int32_t bn_group_size(const bn_group *g) { return g ? (int32_t)g->ranks.size() : 0; }
 int32_t bn_group_uses_rccl(const bn_group *g) { return g && g->use_rccl ? 1 : 0; }
@@ -265,10 +251,10 @@ bn_status bn_group_analyze_recording(bn_group *g, const void *pcm, size_t n_samp
         if (per > rk.cap_rows || k > rk.cap_k || (logits_out && per > rk.cap_rows_logits)) {
             const bool had_logits = rk.cap_rows_logits > 0;
             free_rank_buffers(rk);
-            if ((logits_out || had_logits) && gated::Malloc(&rk.d_logits, R * per * N * sizeof(float)) != hipSuccess)
+            if ((logits_out || had_logits) && rk.d_logits.alloc(R * per * N * sizeof(float)) != hipSuccess)
                 return fail(BN_ERR_BACKEND, "out of device memory for the gathered logits");
             if (rk.d_logits) rk.cap_rows_logits = per;
-            if (k && gated::Malloc(&rk.d_topk, R * per * tkw * sizeof(uint32_t)) != hipSuccess) return fail(BN_ERR_BACKEND, "out of device memory for the gathered top-K rows");
+            if (k && rk.d_topk.alloc(R * per * tkw * sizeof(uint32_t)) != hipSuccess) return fail(BN_ERR_BACKEND, "out of device memory for the gathered top-K rows");
             rk.cap_rows = per;
             rk.cap_k = k;
         }

@@ -329,11 +329,15 @@ struct bn_head {
     int device = 0;
     size_t dim = 0, dpad = 0, classes = 0, cpad = 0;
     uint32_t flags = 0;
-    float *d_W = nullptr;  // [cpad, dpad]
-    float *d_b = nullptr;  // [cpad]
     // bn_head_apply_host's own stream and staging, allocated on first use
-    hipStream_t stream = nullptr;
-    float *d_raw = nullptr, *d_x = nullptr, *d_z = nullptr;  // [CHUNK, dim], [CHUNK, dpad], [CHUNK, classes]
+    bn::Stream stream;  // before the buffers: it goes last (device_mem.h)
+    bn::DeviceBuf<float> d_raw, d_x, d_z;  // [CHUNK, dim], [CHUNK, dpad], [CHUNK, classes]
+    bn::DeviceBuf<float> d_W;  // [cpad, dpad]
+    bn::DeviceBuf<float> d_b;  // [cpad]
+    ~bn_head() {
+        (void)bn::use_device(device);
+        if (stream) (void)hipStreamSynchronize(stream);
+    }
 };
 
 struct bn::HeadAttach {
@@ -341,11 +345,12 @@ struct bn::HeadAttach {
     size_t max_batch = 0, k = 0;
     int32_t has_min = 0;
     float min_conf = 0.f;
-    float *d_x = nullptr;       // [max_batch padded to 16, dpad]
-    float *d_z = nullptr;       // [max_batch, classes]
+    bn::DeviceBuf<float> d_x;   // [max_batch padded to 16, dpad]
+    bn::DeviceBuf<float> d_z;   // [max_batch, classes]
     bn::TopkRows rows;          // the last step's top-K rows: device block and pinned mirror
-    uint32_t *d_flags = nullptr;
-    float *h_z = nullptr;  // pinned mirror of d_z
+    bn::DeviceBuf<uint32_t> d_flags;
+    bn::PinnedBuf<float> h_z;  // pinned mirror of d_z
+    ~HeadAttach();             // drops the reference
 };
 
 namespace {
@@ -357,13 +362,7 @@ using bn::check_launch;
 size_t round_up(size_t v, size_t m) { return (v + m - 1) / m * m; }
 
 void head_unref(bn_head *h) {
-    if (!h || h->refs.fetch_sub(1, std::memory_order_acq_rel) != 1) return;
-    (void)bn::use_device(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (void *p : {(void *)h->d_W, (void *)h->d_b, (void *)h->d_raw, (void *)h->d_x, (void *)h->d_z})
-        if (p) (void)bn::gated::Free(p);
-    if (h->stream) (void)bn::gated::StreamDestroy(h->stream);
-    delete h;
+    if (h && h->refs.fetch_sub(1, std::memory_order_acq_rel) == 1) delete h;
 }
 
 bn_status check_shape(size_t dim, size_t n_classes) {
@@ -374,7 +373,7 @@ bn_status check_shape(size_t dim, size_t n_classes) {
 
 // a head on `device` whose weights and bias the caller fills WHOLE, padding included (bn_head_create from the host, a fit from
 // its solution)
-bn_status new_head(int32_t device, size_t dim, size_t n_classes, uint32_t flags, std::unique_ptr<bn_head, void (*)(bn_head *)> &h) {
+bn_status new_head(int32_t device, size_t dim, size_t n_classes, uint32_t flags, std::unique_ptr<bn_head> &h) {
     BN_HIP_TRY(bn::use_device(device));
     if (!bn::prepare_device(device)) return set_last_error(BN_ERR_BACKEND, "device refused the kernels' dynamic-LDS opt-in");
     h.reset(new bn_head);
@@ -384,8 +383,8 @@ bn_status new_head(int32_t device, size_t dim, size_t n_classes, uint32_t flags,
     h->classes = n_classes;
     h->cpad = round_up(n_classes, 16);
     h->flags = flags;
-    BN_HIP_TRY(bn::gated::Malloc(&h->d_W, h->cpad * h->dpad * sizeof(float)));
-    BN_HIP_TRY(bn::gated::Malloc(&h->d_b, h->cpad * sizeof(float)));
+    BN_HIP_TRY(h->d_W.alloc(h->cpad * h->dpad * sizeof(float)));
+    BN_HIP_TRY(h->d_b.alloc(h->cpad * sizeof(float)));
     return BN_OK;
 }
 
@@ -472,9 +471,8 @@ bn_status solve(bn::Scratch &bufs, bn_head *h, const float *d_X, size_t n, size_
     BN_HIP_TRY(bufs.alloc(&d_lossp, n_rblocks * sizeof(double), false));
     BN_HIP_TRY(bufs.alloc(&d_part, (size_t)RED_BLOCKS * NQ * sizeof(double), true));
     BN_HIP_TRY(bufs.alloc(&d_out, NQ * sizeof(double), false));
-    double *h_out = nullptr;
-    BN_HIP_TRY(bn::gated::HostMalloc(&h_out, NQ * sizeof(double), 0));
-    bufs.pinned = h_out;
+    BN_HIP_TRY(bufs.pinned.alloc(NQ * sizeof(double)));
+    double *h_out = static_cast<double *>(bufs.pinned.get());
 
     int cur = 0;  // d_x[cur], d_g[cur]: the current point and its gradient; [1 - cur]: the trial
     // (L, grad L) at d_x[1 - cur] and every dot product of the candidate pair; results in h_out
@@ -642,31 +640,24 @@ bn_status bn::head_attach(bn_head *h, int device, bool has_embedding, size_t emb
     bn_status st = bn::check_top_k(h->classes, top_k, &k);
     if (st != BN_OK) return st;
     BN_HIP_TRY(bn::use_device(device));
-    std::unique_ptr<HeadAttach, void (*)(HeadAttach *)> a(new HeadAttach, head_detach);
+    auto a = std::make_unique<HeadAttach>();
     a->max_batch = max_batch;
     a->k = k;
     a->has_min = has_min;
     a->min_conf = min_conf;
-    BN_HIP_TRY(bn::gated::Malloc(&a->d_x, round_up(max_batch, 16) * h->dpad * sizeof(float)));
-    BN_HIP_TRY(bn::gated::Malloc(&a->d_z, max_batch * h->classes * sizeof(float)));
+    BN_HIP_TRY(a->d_x.alloc(round_up(max_batch, 16) * h->dpad * sizeof(float)));
+    BN_HIP_TRY(a->d_z.alloc(max_batch * h->classes * sizeof(float)));
     if ((st = a->rows.reserve(max_batch, k, nullptr, true, true)) != BN_OK) return st;
-    BN_HIP_TRY(bn::gated::Malloc(&a->d_flags, max_batch * sizeof(uint32_t)));
-    BN_HIP_TRY(bn::gated::HostMalloc(&a->h_z, max_batch * h->classes * sizeof(float), hipHostMallocDefault));
+    BN_HIP_TRY(a->d_flags.alloc(max_batch * sizeof(uint32_t)));
+    BN_HIP_TRY(a->h_z.alloc(max_batch * h->classes * sizeof(float)));
     h->refs.fetch_add(1, std::memory_order_relaxed);
     a->head = h;
     *out = a.release();
     return BN_OK;
 }
 
-void bn::head_detach(HeadAttach *a) {
-    if (!a) return;
-    for (void *p : {(void *)a->d_x, (void *)a->d_z, (void *)a->d_flags})
-        if (p) (void)bn::gated::Free(p);
-    if (a->h_z) (void)bn::gated::HostFree(a->h_z);
-    a->rows.release();
-    head_unref(a->head);
-    delete a;
-}
+bn::HeadAttach::~HeadAttach() { head_unref(head); }
+void bn::head_detach(HeadAttach *a) { delete a; }
 
 bn_status bn::head_step(HeadAttach *a, hipStream_t stream, const float *d_emb, size_t batch) {
     const bn_head *h = a->head;
@@ -703,7 +694,7 @@ bn_status bn_head_create(int32_t device, size_t dim, size_t n_classes, const flo
     if (!W) return set_last_error(BN_ERR_INVALID_ARG, "null weights");
     if (flags & ~BN_HEAD_L2NORM) return set_last_error(BN_ERR_INVALID_ARG, "unknown flag");
     if ((st = bn::require_device(device)) != BN_OK) return st;
-    std::unique_ptr<bn_head, void (*)(bn_head *)> h(nullptr, head_unref);
+    std::unique_ptr<bn_head> h;
     if ((st = new_head(device, dim, n_classes, flags, h)) != BN_OK) return st;
     std::vector<float> pad(h->cpad * h->dpad, 0.f);
     for (size_t c = 0; c < n_classes; c++) memcpy(pad.data() + c * h->dpad, W + c * dim, dim * sizeof(float));
@@ -740,10 +731,10 @@ bn_status bn_head_apply_host(const bn_head *hc, const float *rows, size_t n, flo
     bn_head *h = const_cast<bn_head *>(hc);  // the staging buffers are not part of the head's value
     BN_HIP_TRY(bn::use_device(h->device));
     // each piece on its own: a call that failed half way leaves the rest to the next one
-    if (!h->stream) BN_HIP_TRY(bn::gated::StreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    if (!h->d_raw) BN_HIP_TRY(bn::gated::Malloc(&h->d_raw, CHUNK * h->dim * sizeof(float)));
-    if (!h->d_x) BN_HIP_TRY(bn::gated::Malloc(&h->d_x, CHUNK * h->dpad * sizeof(float)));
-    if (!h->d_z) BN_HIP_TRY(bn::gated::Malloc(&h->d_z, CHUNK * h->classes * sizeof(float)));
+    if (!h->stream) BN_HIP_TRY(h->stream.create(hipStreamNonBlocking));
+    if (!h->d_raw) BN_HIP_TRY(h->d_raw.alloc(CHUNK * h->dim * sizeof(float)));
+    if (!h->d_x) BN_HIP_TRY(h->d_x.alloc(CHUNK * h->dpad * sizeof(float)));
+    if (!h->d_z) BN_HIP_TRY(h->d_z.alloc(CHUNK * h->classes * sizeof(float)));
     for (size_t r0 = 0; r0 < n; r0 += CHUNK) {
         const size_t k = std::min(CHUNK, n - r0);
         BN_HIP_TRY(bn::gated::Memcpy(h->d_raw, rows + r0 * h->dim, k * h->dim * sizeof(float), hipMemcpyHostToDevice));
@@ -769,11 +760,10 @@ bn_status bn_head_fit(int32_t device, size_t dim, size_t n_classes, const float 
     if ((st = read_opts(opts, opts_size, n_classes, &o, &pw)) != BN_OK) return st;
     if ((st = check_labels(labels, n * n_classes)) != BN_OK) return st;
     if ((st = bn::require_device(device)) != BN_OK) return st;
-    std::unique_ptr<bn_head, void (*)(bn_head *)> h(nullptr, head_unref);
+    std::unique_ptr<bn_head> h;
     if ((st = new_head(device, dim, n_classes, o.flags, h)) != BN_OK) return st;
     bn::Scratch bufs;
-    BN_HIP_TRY(bn::gated::StreamCreateWithFlags(&bufs.stream, hipStreamNonBlocking));
-    bufs.owns_stream = true;
+    BN_HIP_TRY(bufs.create_stream(hipStreamNonBlocking));
     const size_t npad = round_up(n, RB);
     float *d_X = nullptr, *d_raw = nullptr;
     BN_HIP_TRY(bufs.alloc(&d_X, npad * h->dpad * sizeof(float), false));
@@ -820,11 +810,10 @@ bn_status bn_head_fit_index(bn_index *x, const uint64_t *ids, const uint8_t *lab
         if (!valid[ids[i]]) return set_last_error(BN_ERR_INVALID_ARG, "row " + std::to_string(ids[i]) + " of the index is stored as zeros (it had no direction)");
         id32[i] = (uint32_t)ids[i];
     }
-    std::unique_ptr<bn_head, void (*)(bn_head *)> h(nullptr, head_unref);
+    std::unique_ptr<bn_head> h;
     if ((st = new_head(ir.device, ir.dim, n_classes, o.flags, h)) != BN_OK) return st;
     bn::Scratch bufs;
-    BN_HIP_TRY(bn::gated::StreamCreateWithFlags(&bufs.stream, hipStreamNonBlocking));
-    bufs.owns_stream = true;
+    BN_HIP_TRY(bufs.create_stream(hipStreamNonBlocking));
     const size_t npad = round_up(n, RB);
     float *d_X = nullptr;
     uint32_t *d_ids = nullptr;

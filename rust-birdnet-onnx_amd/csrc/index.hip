@@ -246,23 +246,29 @@ struct bn_index {
     int device = 0;
     size_t dim = 0, dpad = 0, cap = 0, cap_pad = 0, size = 0;
     int max_wg = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev = nullptr;  // recorded after the last bn_index_add_ctx on the context's stream
+    bn::Stream stream;  // stream and event before the buffers: they go last (device_mem.h)
+    bn::Event ev;       // recorded after the last bn_index_add_ctx on the context's stream
     bool pending = false;
-    float *slab = nullptr;      // [cap_pad, dpad]
-    uint8_t *valid = nullptr;   // [cap_pad]
-    float *d_stage = nullptr;   // [STAGE_ROWS, dim]: host rows / queries on their way in
-    float *d_q = nullptr;       // [QCHUNK, dpad]
-    uint8_t *d_qvalid = nullptr;
-    uint32_t *d_qid = nullptr;  // [QCHUNK]
-    Cand *d_cand = nullptr;     // [max_wg, QP, MMAX]
-    int *d_cand_len = nullptr;  // [max_wg, QP]
-    Cand *d_out = nullptr;      // [QCHUNK, MMAX]
-    uint32_t *d_count = nullptr;
-    Cand *h_out = nullptr;  // pinned mirrors of d_out / d_count
-    uint32_t *h_count = nullptr;
+    bn::DeviceBuf<float> slab;      // [cap_pad, dpad]
+    bn::DeviceBuf<uint8_t> valid;   // [cap_pad]
+    bn::DeviceBuf<float> d_stage;   // [STAGE_ROWS, dim]: host rows / queries on their way in
+    bn::DeviceBuf<float> d_q;       // [QCHUNK, dpad]
+    bn::DeviceBuf<uint8_t> d_qvalid;
+    bn::DeviceBuf<uint32_t> d_qid;  // [QCHUNK]
+    bn::DeviceBuf<Cand> d_cand;     // [max_wg, QP, MMAX]
+    bn::DeviceBuf<int> d_cand_len;  // [max_wg, QP]
+    bn::DeviceBuf<Cand> d_out;      // [QCHUNK, MMAX]
+    bn::DeviceBuf<uint32_t> d_count;
+    bn::PinnedBuf<Cand> h_out;  // pinned mirrors of d_out / d_count
+    bn::PinnedBuf<uint32_t> h_count;
     bn::ClusterState *cluster = nullptr;  // cluster.hip's buffers, allocated by the first bn_index_assign / bn_index_cluster
-    uint16_t *tags = nullptr;  // [cap_pad], allocated by the first bn_index_set_tags / bn_index_fill_tags; absent: every tag is 0
+    bn::DeviceBuf<uint16_t> tags;  // [cap_pad], allocated by the first bn_index_set_tags / bn_index_fill_tags; absent: every tag is 0
+    ~bn_index() {
+        (void)bn::use_device(device);
+        if (stream) (void)hipStreamSynchronize(stream);
+        if (ev) (void)hipEventSynchronize(ev);
+        bn::cluster_state_free(cluster);
+    }
 };
 
 namespace {
@@ -271,26 +277,8 @@ using bn::set_last_error;
 
 using bn::check_launch;
 
-void release(bn_index *x) {
-    if (!x) return;
-    (void)bn::use_device(x->device);
-    if (x->stream) (void)hipStreamSynchronize(x->stream);
-    if (x->ev) {
-        (void)hipEventSynchronize(x->ev);
-        (void)bn::gated::EventDestroy(x->ev);
-    }
-    for (void *p : {(void *)x->slab, (void *)x->valid, (void *)x->d_stage, (void *)x->d_q, (void *)x->d_qvalid, (void *)x->d_qid, (void *)x->d_cand,
-                    (void *)x->d_cand_len, (void *)x->d_out, (void *)x->d_count, (void *)x->tags})
-        if (p) (void)bn::gated::Free(p);
-    bn::cluster_state_free(x->cluster);
-    if (x->h_out) (void)bn::gated::HostFree(x->h_out);
-    if (x->h_count) (void)bn::gated::HostFree(x->h_count);
-    if (x->stream) (void)bn::gated::StreamDestroy(x->stream);
-    delete x;
-}
-
 void unref(bn_index *x) {
-    if (x && x->refs.fetch_sub(1, std::memory_order_acq_rel) == 1) release(x);
+    if (x && x->refs.fetch_sub(1, std::memory_order_acq_rel) == 1) delete x;
 }
 
 // device and stream of the index current, and the index's stream ordered after the last bn_index_add_ctx
@@ -382,13 +370,11 @@ bn_status prepare_tags(bn_index *x, uint64_t first_id, size_t n, const uint32_t 
     if (st != BN_OK) return st;
     BN_HIP_TRY(hipStreamSynchronize(x->stream));
     if (!x->tags) {
-        uint16_t *p = nullptr;
-        BN_HIP_TRY(bn::gated::Malloc(&p, x->cap_pad * sizeof(uint16_t)));
-        if (hipError_t e = bn::gated::Memset(p, 0, x->cap_pad * sizeof(uint16_t)); e != hipSuccess) {
-            (void)bn::gated::Free(p);
+        bn::DeviceBuf<uint16_t> p;
+        BN_HIP_TRY(p.alloc(x->cap_pad * sizeof(uint16_t)));
+        if (hipError_t e = bn::gated::Memset(p, 0, x->cap_pad * sizeof(uint16_t)); e != hipSuccess)
             return set_last_error(BN_ERR_BACKEND, std::string("hipMemset of the tag plane failed: ") + hipGetErrorString(e));
-        }
-        x->tags = p;
+        x->tags = std::move(p);
     }
     return BN_OK;
 }
@@ -550,7 +536,7 @@ bn_status bn_index_create(int32_t device, size_t dim, size_t capacity_rows, bn_i
     BN_HIP_TRY(bn::use_device(device));
     BN_HIP_TRY(g_scan_lds.prepare(device, {{(const void *)index_scan_kernel<1>, SCAN_LDS}, {(const void *)index_scan_kernel<2>, SCAN_LDS},
                                             {(const void *)index_scan_kernel<3>, SCAN_LDS}, {(const void *)index_scan_kernel<4>, SCAN_LDS}}));
-    std::unique_ptr<bn_index, void (*)(bn_index *)> x(new bn_index, release);
+    auto x = std::make_unique<bn_index>();
     x->device = device;
     x->dim = dim;
     x->dpad = (dim + KC - 1) / KC * KC;
@@ -559,22 +545,22 @@ bn_status bn_index_create(int32_t device, size_t dim, size_t capacity_rows, bn_i
     int cus = 0;
     BN_HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
     x->max_wg = std::max(1, cus);
-    BN_HIP_TRY(bn::gated::StreamCreateWithFlags(&x->stream, hipStreamNonBlocking));
-    BN_HIP_TRY(bn::gated::EventCreateWithFlags(&x->ev, hipEventDisableTiming));
-    BN_HIP_TRY(bn::gated::Malloc(&x->slab, x->cap_pad * x->dpad * sizeof(float)));
+    BN_HIP_TRY(x->stream.create(hipStreamNonBlocking));
+    BN_HIP_TRY(x->ev.create(hipEventDisableTiming));
+    BN_HIP_TRY(x->slab.alloc(x->cap_pad * x->dpad * sizeof(float)));
     BN_HIP_TRY(bn::gated::Memset(x->slab, 0, x->cap_pad * x->dpad * sizeof(float)));
-    BN_HIP_TRY(bn::gated::Malloc(&x->valid, x->cap_pad));
+    BN_HIP_TRY(x->valid.alloc(x->cap_pad));
     BN_HIP_TRY(bn::gated::Memset(x->valid, 0, x->cap_pad));
-    BN_HIP_TRY(bn::gated::Malloc(&x->d_stage, STAGE_ROWS * dim * sizeof(float)));
-    BN_HIP_TRY(bn::gated::Malloc(&x->d_q, QCHUNK * x->dpad * sizeof(float)));
-    BN_HIP_TRY(bn::gated::Malloc(&x->d_qvalid, QCHUNK));
-    BN_HIP_TRY(bn::gated::Malloc(&x->d_qid, QCHUNK * sizeof(uint32_t)));
-    BN_HIP_TRY(bn::gated::Malloc(&x->d_cand, (size_t)x->max_wg * QP * MMAX * sizeof(Cand)));
-    BN_HIP_TRY(bn::gated::Malloc(&x->d_cand_len, (size_t)x->max_wg * QP * sizeof(int)));
-    BN_HIP_TRY(bn::gated::Malloc(&x->d_out, QCHUNK * MMAX * sizeof(Cand)));
-    BN_HIP_TRY(bn::gated::Malloc(&x->d_count, QCHUNK * sizeof(uint32_t)));
-    BN_HIP_TRY(bn::gated::HostMalloc(&x->h_out, QCHUNK * MMAX * sizeof(Cand), 0));
-    BN_HIP_TRY(bn::gated::HostMalloc(&x->h_count, QCHUNK * sizeof(uint32_t), 0));
+    BN_HIP_TRY(x->d_stage.alloc(STAGE_ROWS * dim * sizeof(float)));
+    BN_HIP_TRY(x->d_q.alloc(QCHUNK * x->dpad * sizeof(float)));
+    BN_HIP_TRY(x->d_qvalid.alloc(QCHUNK));
+    BN_HIP_TRY(x->d_qid.alloc(QCHUNK * sizeof(uint32_t)));
+    BN_HIP_TRY(x->d_cand.alloc((size_t)x->max_wg * QP * MMAX * sizeof(Cand)));
+    BN_HIP_TRY(x->d_cand_len.alloc((size_t)x->max_wg * QP * sizeof(int)));
+    BN_HIP_TRY(x->d_out.alloc(QCHUNK * MMAX * sizeof(Cand)));
+    BN_HIP_TRY(x->d_count.alloc(QCHUNK * sizeof(uint32_t)));
+    BN_HIP_TRY(x->h_out.alloc(QCHUNK * MMAX * sizeof(Cand)));
+    BN_HIP_TRY(x->h_count.alloc(QCHUNK * sizeof(uint32_t)));
     *out = x.release();
     return BN_OK;
 }

@@ -170,33 +170,24 @@ __global__ __launch_bounds__(256) void index_restore_kernel(const uint32_t *__re
 // d_meta: [n_chunks] chunk digests, then the valid-row count, then (low word) the first chunk with a non-finite element
 struct IoBuffers {
     hipStream_t stream = nullptr;
-    uint32_t *d_stage[NBUF] = {};
-    uint32_t *h_stage[NBUF] = {};
-    hipEvent_t ev[NBUF] = {};
-    u64 *d_meta = nullptr;
-    IoBuffers() = default;
-    IoBuffers(const IoBuffers &) = delete;
-    IoBuffers &operator=(const IoBuffers &) = delete;
+    bn::DeviceBuf<uint32_t> d_stage[NBUF];
+    bn::PinnedBuf<uint32_t> h_stage[NBUF];
+    bn::Event ev[NBUF];
+    bn::DeviceBuf<u64> d_meta;
     bn_status create(hipStream_t s, size_t n_chunks) {
         stream = s;
         for (int b = 0; b < NBUF; b++) {
-            BN_HIP_TRY(bn::gated::Malloc(&d_stage[b], STAGE_BYTES));
-            BN_HIP_TRY(bn::gated::HostMalloc(&h_stage[b], STAGE_BYTES, 0));
-            BN_HIP_TRY(bn::gated::EventCreateWithFlags(&ev[b], hipEventDisableTiming));
+            BN_HIP_TRY(d_stage[b].alloc(STAGE_BYTES));
+            BN_HIP_TRY(h_stage[b].alloc(STAGE_BYTES));
+            BN_HIP_TRY(ev[b].create(hipEventDisableTiming));
         }
-        BN_HIP_TRY(bn::gated::Malloc(&d_meta, (n_chunks + 2) * sizeof(u64)));
+        BN_HIP_TRY(d_meta.alloc((n_chunks + 2) * sizeof(u64)));
         BN_HIP_TRY(hipMemsetAsync(d_meta, 0, (n_chunks + 1) * sizeof(u64), stream));
         BN_HIP_TRY(hipMemsetAsync(d_meta + n_chunks + 1, 0xff, sizeof(u64), stream));
         return BN_OK;
     }
     ~IoBuffers() {
         if (stream) (void)hipStreamSynchronize(stream);
-        for (int b = 0; b < NBUF; b++) {
-            if (ev[b]) (void)bn::gated::EventDestroy(ev[b]);
-            if (d_stage[b]) (void)bn::gated::Free(d_stage[b]);
-            if (h_stage[b]) (void)bn::gated::HostFree(h_stage[b]);
-        }
-        if (d_meta) (void)bn::gated::Free(d_meta);
     }
     // the stream's work done; digests [n_chunks], the valid-row count and the non-finite chunk to the host
     bn_status read_meta(size_t n_chunks, std::vector<uint64_t> *meta) {

@@ -320,30 +320,22 @@ struct bn_ivf {
     int device = 0;
     size_t k = 0, dim = 0, dpad = 0, covered = 0, cap_pad = 0, out_lists = 0;
     bn::cluster::AssignBufs ab;     // the centroids [k, dpad]; the assignment planes [cap_pad]
-    uint32_t *d_small = nullptr;    // counts [k], offsets [k + 1]
-    uint32_t *d_members = nullptr;  // [cap_pad]
+    bn::DeviceBuf<uint32_t> d_small;    // counts [k], offsets [k + 1]
+    bn::DeviceBuf<uint32_t> d_members;  // [cap_pad]
     std::vector<uint32_t> h_counts, h_offsets;
     uint32_t max_count = 0;
-    float *d_pscore = nullptr;                // [out_lists, k] centroid scores
-    uint32_t *d_probes = nullptr;             // [out_lists, k] (a call uses [queries, nprobe])
-    unsigned long long *d_scanned = nullptr;  // [out_lists]
-    Cand *d_cand = nullptr;                   // [UNIT_MAX, MMAX]
-    int *d_cand_len = nullptr;                // [UNIT_MAX]
+    bn::DeviceBuf<float> d_pscore;                // [out_lists, k] centroid scores
+    bn::DeviceBuf<uint32_t> d_probes;             // [out_lists, k] (a call uses [queries, nprobe])
+    bn::DeviceBuf<unsigned long long> d_scanned;  // [out_lists]
+    bn::DeviceBuf<Cand> d_cand;                   // [UNIT_MAX, MMAX]
+    bn::DeviceBuf<int> d_cand_len;                // [UNIT_MAX]
+    ~bn_ivf() { (void)bn::use_device(device); }
 };
 
 namespace {
 
 using bn::check_launch;
 using bn::set_last_error;
-
-void release(bn_ivf *v) {
-    if (!v) return;
-    (void)bn::use_device(v->device);
-    for (void *p : {(void *)v->ab.d_cent, (void *)v->ab.d_best_s, (void *)v->ab.d_best_i, (void *)v->d_small, (void *)v->d_members, (void *)v->d_pscore,
-                    (void *)v->d_probes, (void *)v->d_scanned, (void *)v->d_cand, (void *)v->d_cand_len})
-        if (p) (void)bn::gated::Free(p);
-    delete v;
-}
 
 // assigns ids [from, size) (from a multiple of the tile) under the view's centroids, then rebuilds sizes, offsets and lists of [0, size)
 // The device lists are rebuilt in place and the host mirrors follow at the end: after a failure in between the two disagree, and the
@@ -475,7 +467,7 @@ bn_status bn_ivf_build(bn_index *x, const float *centroids, size_t k, bn_ivf **o
     if (st != BN_OK) return st;
     bn::IndexScan s;
     if ((st = bn::index_scan_state(x, &s)) != BN_OK) return st;
-    std::unique_ptr<bn_ivf, void (*)(bn_ivf *)> v(new bn_ivf, release);
+    auto v = std::make_unique<bn_ivf>();
     v->x = x;
     v->device = s.device;
     v->k = k;
@@ -483,25 +475,25 @@ bn_status bn_ivf_build(bn_index *x, const float *centroids, size_t k, bn_ivf **o
     v->dpad = s.dpad;
     v->cap_pad = s.cap_pad;
     v->out_lists = s.out_lists;
-    BN_HIP_TRY(bn::gated::Malloc(&v->ab.d_cent, k * s.dpad * sizeof(float)));
+    BN_HIP_TRY(v->ab.d_cent.alloc(k * s.dpad * sizeof(float)));
     v->ab.cent_n = k * s.dpad;
-    BN_HIP_TRY(bn::gated::Malloc(&v->ab.d_best_s, s.cap_pad * sizeof(float)));
-    BN_HIP_TRY(bn::gated::Malloc(&v->ab.d_best_i, s.cap_pad * sizeof(uint32_t)));
+    BN_HIP_TRY(v->ab.d_best_s.alloc(s.cap_pad * sizeof(float)));
+    BN_HIP_TRY(v->ab.d_best_i.alloc(s.cap_pad * sizeof(uint32_t)));
     v->ab.best_n = s.cap_pad;
-    BN_HIP_TRY(bn::gated::Malloc(&v->d_small, (2 * k + 1) * sizeof(uint32_t)));
-    BN_HIP_TRY(bn::gated::Malloc(&v->d_members, s.cap_pad * sizeof(uint32_t)));
-    BN_HIP_TRY(bn::gated::Malloc(&v->d_pscore, s.out_lists * k * sizeof(float)));
-    BN_HIP_TRY(bn::gated::Malloc(&v->d_probes, s.out_lists * k * sizeof(uint32_t)));
-    BN_HIP_TRY(bn::gated::Malloc(&v->d_scanned, s.out_lists * sizeof(unsigned long long)));
-    BN_HIP_TRY(bn::gated::Malloc(&v->d_cand, UNIT_MAX * MMAX * sizeof(Cand)));
-    BN_HIP_TRY(bn::gated::Malloc(&v->d_cand_len, UNIT_MAX * sizeof(int)));
+    BN_HIP_TRY(v->d_small.alloc((2 * k + 1) * sizeof(uint32_t)));
+    BN_HIP_TRY(v->d_members.alloc(s.cap_pad * sizeof(uint32_t)));
+    BN_HIP_TRY(v->d_pscore.alloc(s.out_lists * k * sizeof(float)));
+    BN_HIP_TRY(v->d_probes.alloc(s.out_lists * k * sizeof(uint32_t)));
+    BN_HIP_TRY(v->d_scanned.alloc(s.out_lists * sizeof(unsigned long long)));
+    BN_HIP_TRY(v->d_cand.alloc(UNIT_MAX * MMAX * sizeof(Cand)));
+    BN_HIP_TRY(v->d_cand_len.alloc(UNIT_MAX * sizeof(int)));
     if ((st = bn::cluster::upload_centroids(&v->ab, s, centroids, k)) != BN_OK) return st;
     if ((st = cover(v.get(), s, 0)) != BN_OK) return st;
     *out = v.release();
     return BN_OK;
 }
 
-void bn_ivf_free(bn_ivf *v) { release(v); }
+void bn_ivf_free(bn_ivf *v) { delete v; }
 
 size_t bn_ivf_lists(const bn_ivf *v) { return v ? v->k : 0; }
 size_t bn_ivf_rows(const bn_ivf *v) { return v ? v->covered : 0; }

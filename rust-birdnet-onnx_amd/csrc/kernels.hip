@@ -26,7 +26,7 @@
 
 #include "kernels.h"
 #include "plan_rules.h"
-#include "hip_gate.h"
+#include "device_mem.h"
 #include "bf16x3.h"
 #include "device_common.h"
 
@@ -111,15 +111,14 @@ bool prepare_device(int dev) {
     if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
     g_cu_count[dev].store(v, std::memory_order_relaxed);
     {  // a page of zeros: the source of LDS-DMA lanes whose chunk lies in a row's padding (mbmap.hip)
-        float *z = nullptr;
+        DeviceBuf<float> z;
         // only the opt-in padded-k small-map kernels read it (launch_mbmap refuses them on a null page): a failure here must not
         // take the device away from every other plan
-        if (gated::Malloc(&z, 4096) != hipSuccess || gated::Memset(z, 0, 4096) != hipSuccess || gated::DeviceSynchronize() != hipSuccess) {
+        if (z.alloc(4096) != hipSuccess || gated::Memset(z, 0, 4096) != hipSuccess || gated::DeviceSynchronize() != hipSuccess) {
             (void)hipGetLastError();
-            if (z) (void)gated::Free(z);
-            z = nullptr;
+            z.reset();
         }
-        g_zero_page[dev].store(z, std::memory_order_relaxed);
+        g_zero_page[dev].store(z.release(), std::memory_order_relaxed);  // the process's from here on
     }
     if (cur != dev && cur >= 0) (void)bn::use_device(cur);  // (restores the thread's launch-device note with it)
     if (ok) g_prepared_mask.fetch_or(1ull << dev, std::memory_order_release);

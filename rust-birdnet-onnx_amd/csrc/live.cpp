@@ -29,7 +29,6 @@
 #include <vector>
 
 #include "capi_internal.h"
-#include "hip_gate.h"
 #include "live.h"
 #include "switches.h"
 
@@ -51,15 +50,15 @@ struct Source {
 
 struct Gather {
     uint64_t id;
-    hipEvent_t ev;
+    bn::Event ev;
     bool done;
 };
 
 struct Stage {
-    char *h = nullptr;  // pinned: [tiles][data]
-    char *d = nullptr;  // device copy of the block (copy mode only)
+    bn::PinnedBuf<char> h;  // pinned: [tiles][data]
+    bn::DeviceBuf<char> d;  // device copy of the block (copy mode only)
     size_t cap = 0;
-    hipEvent_t ev = nullptr;
+    bn::Event ev;
     bool used = false;
 };
 
@@ -71,17 +70,17 @@ struct bn_live {
     int32_t format = BN_PCM_I16;
     size_t esz = 2;
     size_t S = 0, step = 0, R = 0;
-    void *slab = nullptr;
-    float *d_window = nullptr;  // bn_live_read_window's output [S]
-    hipStream_t stream = nullptr;
-    hipEvent_t scatter_ev = nullptr;
+    bn::Stream stream;  // before everything its work touches (device_mem.h)
+    bn::Event scatter_ev;
+    bn::DeviceBuf<void> slab;
+    bn::DeviceBuf<float> d_window;  // bn_live_read_window's output [S]
     bool scattered = false;
     bool copy_mode = false;  // BN_LIVE_SCATTER=copy: one async H2D copy of the staging block, then the kernel on device memory
     std::vector<Source> src;
     std::deque<std::pair<int32_t, uint64_t>> queue;  // ready, unscheduled windows (source, k) in sequence order
     std::deque<Gather> gathers;                       // gathers not yet known complete, ids increasing
     uint64_t next_gather = 0;
-    std::vector<hipEvent_t> free_events;
+    std::vector<bn::Event> free_events;
     std::vector<int32_t> touched;  // push_impl: per source, its entry in the call's list of touched sources (-1: none)
     Stage stage[N_STAGE];
     int next_stage = 0;
@@ -93,11 +92,16 @@ struct bn_live {
     uint32_t dst_rate = 0;
     std::vector<bn::LiveRsTable> tables;
     std::vector<uint32_t> table_tile;  // outputs per tile, per table: the span of a tile fits the table's span_cap
-    bn::LiveRsTable *d_tables = nullptr;
-    float *d_coef = nullptr;
-    float *d_hist = nullptr;  // [n_sources][hist_cap]
+    bn::DeviceBuf<bn::LiveRsTable> d_tables;
+    bn::DeviceBuf<float> d_coef;
+    bn::DeviceBuf<float> d_hist;  // [n_sources][hist_cap]
     size_t hist_cap = 0;
     uint32_t lds_bytes = 0;
+    ~bn_live() {
+        (void)bn::use_device(device);
+        if (stream) (void)hipStreamSynchronize(stream);
+        for (auto &g : gathers) (void)hipEventSynchronize(g.ev);
+    }
 };
 
 namespace {
@@ -162,7 +166,7 @@ void retire_gathers(bn_live *l) {
         Gather &g = l->gathers.front();
         if (!g.done && hipEventQuery(g.ev) == hipSuccess) g.done = true;
         if (!g.done) break;
-        l->free_events.push_back(g.ev);
+        l->free_events.push_back(std::move(g.ev));
         l->gathers.pop_front();
     }
 }
@@ -195,12 +199,11 @@ bn_status acquire_stage(bn_live *l, size_t bytes, Stage **out) {
     if (st.used) BN_HIP_TRY(hipEventSynchronize(st.ev));
     if (bytes > st.cap) {
         const size_t cap = std::max(bytes, st.cap * 3 / 2);
-        if (st.h) (void)bn::gated::HostFree(st.h);
-        if (st.d) (void)bn::gated::Free(st.d);
-        st.h = st.d = nullptr;
+        st.h.reset();
+        st.d.reset();
         st.cap = 0;
-        BN_HIP_TRY(bn::gated::HostMalloc(&st.h, cap, hipHostMallocDefault));
-        if (l->copy_mode) BN_HIP_TRY(bn::gated::Malloc(&st.d, cap));
+        BN_HIP_TRY(st.h.alloc(cap));
+        if (l->copy_mode) BN_HIP_TRY(st.d.alloc(cap));
         st.cap = cap;
     }
     *out = &st;
@@ -280,7 +283,7 @@ bn_status scatter_rates(bn_live *l, const std::vector<std::pair<int32_t, uint64_
         blk = st.d;
     }
     const bn::LiveRsJob *d_jobs = reinterpret_cast<const bn::LiveRsJob *>(blk);
-    bn::launch_live_resample(l->stream, static_cast<float *>(l->slab), l->in_i16, l->d_tables, l->d_coef, l->d_hist, d_jobs,
+    bn::launch_live_resample(l->stream, static_cast<float *>(l->slab.get()), l->in_i16, l->d_tables, l->d_coef, l->d_hist, d_jobs,
                              reinterpret_cast<const bn::LiveRsTile *>(blk + jobs_b), (uint32_t)tiles.size(), blk + jobs_b + tiles_b, l->lds_bytes);
     if (!closing) bn::launch_live_history(l->stream, l->d_hist, l->in_i16, l->d_tables, d_jobs, (uint32_t)jobs.size(), blk + jobs_b + tiles_b);
     if (bn_status lst = bn::check_launch("live resample"); lst != BN_OK) return lst;
@@ -413,30 +416,6 @@ bn_status push_impl(bn_live *l, size_t n, const int32_t *sources, const void *co
     return BN_OK;
 }
 
-void release(bn_live *l) {
-    if (!l) return;
-    (void)bn::use_device(l->device);
-    if (l->stream) (void)hipStreamSynchronize(l->stream);
-    for (auto &g : l->gathers) {
-        (void)hipEventSynchronize(g.ev);
-        (void)bn::gated::EventDestroy(g.ev);
-    }
-    for (auto e : l->free_events) (void)bn::gated::EventDestroy(e);
-    for (auto &st : l->stage) {
-        if (st.h) (void)bn::gated::HostFree(st.h);
-        if (st.d) (void)bn::gated::Free(st.d);
-        if (st.ev) (void)bn::gated::EventDestroy(st.ev);
-    }
-    if (l->scatter_ev) (void)bn::gated::EventDestroy(l->scatter_ev);
-    if (l->slab) (void)bn::gated::Free(l->slab);
-    if (l->d_tables) (void)bn::gated::Free(l->d_tables);
-    if (l->d_coef) (void)bn::gated::Free(l->d_coef);
-    if (l->d_hist) (void)bn::gated::Free(l->d_hist);
-    if (l->d_window) (void)bn::gated::Free(l->d_window);
-    if (l->stream) (void)bn::gated::StreamDestroy(l->stream);
-    delete l;
-}
-
 // the tables of a resampling pool, one per distinct source rate, the tile size of each, and the device buffers
 bn_status setup_rates(bn_live *l, uint32_t dst_rate, const uint32_t *src_rates, uint32_t zero_crossings) {
     std::vector<float> coef;
@@ -485,12 +464,12 @@ bn_status setup_rates(bn_live *l, uint32_t dst_rate, const uint32_t *src_rates, 
     l->lds_bytes = lds_floats * (uint32_t)sizeof(float);
     l->hist_cap = max_T - 1;
     const size_t hist_b = (size_t)l->n_sources * l->hist_cap * sizeof(float);
-    BN_HIP_TRY(bn::gated::Malloc(reinterpret_cast<void **>(&l->d_hist), hist_b));
+    BN_HIP_TRY(l->d_hist.alloc(hist_b));
     BN_HIP_TRY(bn::gated::Memset(l->d_hist, 0, hist_b));
     if (!l->tables.empty()) {
-        BN_HIP_TRY(bn::gated::Malloc(reinterpret_cast<void **>(&l->d_tables), l->tables.size() * sizeof(bn::LiveRsTable)));
+        BN_HIP_TRY(l->d_tables.alloc(l->tables.size() * sizeof(bn::LiveRsTable)));
         BN_HIP_TRY(bn::gated::Memcpy(l->d_tables, l->tables.data(), l->tables.size() * sizeof(bn::LiveRsTable), hipMemcpyHostToDevice));
-        BN_HIP_TRY(bn::gated::Malloc(reinterpret_cast<void **>(&l->d_coef), coef.size() * sizeof(float)));
+        BN_HIP_TRY(l->d_coef.alloc(coef.size() * sizeof(float)));
         BN_HIP_TRY(bn::gated::Memcpy(l->d_coef, coef.data(), coef.size() * sizeof(float), hipMemcpyHostToDevice));
     }
     return BN_OK;
@@ -514,7 +493,7 @@ bn_status create_pool(int32_t device, int32_t n_sources, int32_t format, size_t 
     }
     if (bn_status dst = bn::require_device(device); dst != BN_OK) return dst;
     BN_HIP_TRY(bn::use_device(device));
-    std::unique_ptr<bn_live, void (*)(bn_live *)> l(new bn_live, release);
+    auto l = std::make_unique<bn_live>();
     l->device = device;
     l->n_sources = n_sources;
     l->format = format;
@@ -544,12 +523,12 @@ bn_status create_pool(int32_t device, int32_t n_sources, int32_t format, size_t 
         }
     }
     const size_t slab_b = (size_t)n_sources * ring_samples * l->esz;
-    BN_HIP_TRY(bn::gated::StreamCreateWithFlags(&l->stream, hipStreamNonBlocking));
-    BN_HIP_TRY(bn::gated::EventCreateWithFlags(&l->scatter_ev, hipEventDisableTiming));
-    for (auto &st : l->stage) BN_HIP_TRY(bn::gated::EventCreateWithFlags(&st.ev, hipEventDisableTiming));
-    BN_HIP_TRY(bn::gated::Malloc(&l->slab, slab_b));
+    BN_HIP_TRY(l->stream.create(hipStreamNonBlocking));
+    BN_HIP_TRY(l->scatter_ev.create(hipEventDisableTiming));
+    for (auto &st : l->stage) BN_HIP_TRY(st.ev.create(hipEventDisableTiming));
+    BN_HIP_TRY(l->slab.alloc(slab_b));
     BN_HIP_TRY(bn::gated::Memset(l->slab, 0, slab_b));
-    BN_HIP_TRY(bn::gated::Malloc(&l->d_window, segment_samples * sizeof(float)));
+    BN_HIP_TRY(l->d_window.alloc(segment_samples * sizeof(float)));
     *out = l.release();
     return BN_OK;
 }
@@ -584,7 +563,7 @@ uint32_t bn_live_source_rate(const bn_live *l, int32_t source) {
     return l->src[source].rate;
 }
 
-void bn_live_free(bn_live *l) { release(l); }
+void bn_live_free(bn_live *l) { delete l; }
 
 bn_status bn_live_push(bn_live *l, int32_t source, const void *pcm, size_t n_samples) {
     return push_impl(l, 1, &source, &pcm, &n_samples);
@@ -678,16 +657,16 @@ bn_status bn_step_live(bn_ctx *c, bn_live *l, size_t max_windows, size_t top_k, 
     BN_HIP_TRY(bn::use_device(l->device));
     retire_gathers(l);
     // the gather's event first: once the gather is launched, its order against later scatters must not be lost
-    hipEvent_t ev = nullptr;
+    bn::Event ev;
     if (!l->free_events.empty()) {
-        ev = l->free_events.back();
+        ev = std::move(l->free_events.back());
         l->free_events.pop_back();
     } else {
-        BN_HIP_TRY(bn::gated::EventCreateWithFlags(&ev, hipEventDisableTiming));
+        BN_HIP_TRY(ev.create(hipEventDisableTiming));
     }
     const hipError_t we = l->scattered ? hipStreamWaitEvent(ci.stream, l->scatter_ev, 0) : hipSuccess;
     if (we != hipSuccess) {
-        l->free_events.push_back(ev);
+        l->free_events.push_back(std::move(ev));
         return set_last_error(BN_ERR_BACKEND, std::string("hipStreamWaitEvent failed: ") + hipGetErrorString(we));
     }
     // gather first, bookkeeping after: a launch failure leaves the pool unchanged
@@ -704,16 +683,16 @@ bn_status bn_step_live(bn_ctx *c, bn_live *l, size_t max_windows, size_t top_k, 
                                (uint32_t)m);
     }
     if (bn_status lst = bn::check_launch("live gather"); lst != BN_OK) {
-        l->free_events.push_back(ev);
+        l->free_events.push_back(std::move(ev));
         return lst;
     }
     const hipError_t re = hipEventRecord(ev, ci.stream);
     if (re != hipSuccess) {
         (void)hipStreamSynchronize(ci.stream);  // the gather's order is lost: wait for it instead
-        l->free_events.push_back(ev);
+        l->free_events.push_back(std::move(ev));
     } else {
         const uint64_t id = l->next_gather++;
-        l->gathers.push_back(Gather{id, ev, false});
+        l->gathers.push_back(Gather{id, std::move(ev), false});
         int32_t last = -1;
         for (size_t i = 0; i < B; i++) {
             const auto &q = l->queue[i];

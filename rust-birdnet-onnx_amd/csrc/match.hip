@@ -268,13 +268,15 @@ struct bn::MatchAttach {
     size_t max_batch = 0, M = 0;
     int32_t has_min = 0;
     float min_score = 0.f;
-    float *d_q = nullptr;          // [max_batch, dpad]
-    uint8_t *d_qvalid = nullptr;   // [max_batch]
-    Cand *d_cand = nullptr;        // [ranges][passes][64][256]
-    int *d_cand_len = nullptr;     // [ranges][passes][64]
-    void *d_rows = nullptr, *h_rows = nullptr;  // Rows of max_batch, and the pinned mirror
+    bn::DeviceBuf<float> d_q;          // [max_batch, dpad]
+    bn::DeviceBuf<uint8_t> d_qvalid;   // [max_batch]
+    bn::DeviceBuf<Cand> d_cand;        // [ranges][passes][64][256]
+    bn::DeviceBuf<int> d_cand_len;     // [ranges][passes][64]
+    bn::DeviceBuf<void> d_rows;        // Rows of max_batch
+    bn::PinnedBuf<void> h_rows;        // and the pinned mirror
     size_t last_batch = 0;
     bool stepped = false;
+    ~MatchAttach() { bn::index_unref(index); }
 };
 
 namespace {
@@ -289,7 +291,7 @@ bn_status make_attach(bn_index *x, const bn::IndexRows &v, size_t max_batch, siz
     BN_HIP_TRY(bn::use_device(v.device));
     BN_HIP_TRY(g_match_lds.prepare(v.device, {{(const void *)match_scan_kernel<1>, SCAN_LDS}, {(const void *)match_scan_kernel<2>, SCAN_LDS},
                                               {(const void *)match_scan_kernel<3>, SCAN_LDS}, {(const void *)match_scan_kernel<4>, SCAN_LDS}}));
-    std::unique_ptr<bn::MatchAttach, void (*)(bn::MatchAttach *)> a(new bn::MatchAttach, bn::match_detach);
+    auto a = std::make_unique<bn::MatchAttach>();
     a->device = v.device;
     a->slab = v.slab;
     a->valid = v.valid;
@@ -302,12 +304,12 @@ bn_status make_attach(bn_index *x, const bn::IndexRows &v, size_t max_batch, siz
     a->has_min = has_min;
     a->min_score = min_score;
     const size_t passes = (max_batch + QP - 1) / QP, units = std::max<size_t>(1, (size_t)a->split.n_wg * passes);
-    BN_HIP_TRY(bn::gated::Malloc(&a->d_q, std::max<size_t>(1, max_batch) * v.dpad * sizeof(float)));
-    BN_HIP_TRY(bn::gated::Malloc(&a->d_qvalid, std::max<size_t>(1, max_batch)));
-    BN_HIP_TRY(bn::gated::Malloc(&a->d_cand, units * QP * MMAX * sizeof(Cand)));
-    BN_HIP_TRY(bn::gated::Malloc(&a->d_cand_len, units * QP * sizeof(int)));
-    BN_HIP_TRY(bn::gated::Malloc(&a->d_rows, std::max<size_t>(16, Rows::bytes(max_batch, top_m))));
-    BN_HIP_TRY(bn::gated::HostMalloc(&a->h_rows, std::max<size_t>(16, Rows::bytes(max_batch, top_m)), hipHostMallocDefault));
+    BN_HIP_TRY(a->d_q.alloc(std::max<size_t>(1, max_batch) * v.dpad * sizeof(float)));
+    BN_HIP_TRY(a->d_qvalid.alloc(std::max<size_t>(1, max_batch)));
+    BN_HIP_TRY(a->d_cand.alloc(units * QP * MMAX * sizeof(Cand)));
+    BN_HIP_TRY(a->d_cand_len.alloc(units * QP * sizeof(int)));
+    BN_HIP_TRY(a->d_rows.alloc(std::max<size_t>(16, Rows::bytes(max_batch, top_m))));
+    BN_HIP_TRY(a->h_rows.alloc(std::max<size_t>(16, Rows::bytes(max_batch, top_m))));
     bn::index_ref(x);
     a->index = x;
     *out = a.release();
@@ -355,14 +357,7 @@ bn_status bn::match_attach(bn_index *x, int device, bool has_embedding, size_t e
     return make_attach(x, v, max_batch, top_m, has_min, min_score, out);
 }
 
-void bn::match_detach(MatchAttach *a) {
-    if (!a) return;
-    for (void *p : {(void *)a->d_q, (void *)a->d_qvalid, (void *)a->d_cand, (void *)a->d_cand_len, a->d_rows})
-        if (p) (void)bn::gated::Free(p);
-    if (a->h_rows) (void)bn::gated::HostFree(a->h_rows);
-    bn::index_unref(a->index);
-    delete a;
-}
+void bn::match_detach(MatchAttach *a) { delete a; }
 
 bn_status bn::match_step(MatchAttach *a, hipStream_t stream, const float *d_emb, size_t batch) {
     if (batch > a->max_batch) return set_last_error(BN_ERR_INVALID_ARG, "batch exceeds the context's max_batch");
@@ -402,7 +397,7 @@ bn_status bn_index_match(bn_index *x, const float *rows, size_t n, size_t top_m,
     // an attachment of one call, on the index's stream: the same snapshot, scratch and kernels as a step's
     bn::MatchAttach *raw = nullptr;
     if ((st = make_attach(x, v, std::min(n, ROUND), top_m, has_min, min_score, &raw)) != BN_OK) return st;
-    std::unique_ptr<bn::MatchAttach, void (*)(bn::MatchAttach *)> a(raw, bn::match_detach);
+    std::unique_ptr<bn::MatchAttach> a(raw);
     hipStream_t stream = bn::index_stream(x);
     bn::Scratch stage;  // waits for the stream before the attachment goes
     stage.stream = stream;

@@ -333,9 +333,13 @@ struct bn_prior {
     size_t n_sites = 0, n_species = 0, tstride = 0;  // device rows are padded to a multiple of 4 floats: every row 16-byte aligned
     float threshold = 0.f;
     uint32_t flags = 0;
-    float *d_table = nullptr;  // [n_sites, tstride]
-    std::mutex mu;             // bn_prior_apply_host / bn_prior_read: one thread at a time
-    hipStream_t stream = nullptr;
+    bn::Stream stream;  // bn_prior_apply_host's, created on first use; before the table: it goes last (device_mem.h)
+    bn::DeviceBuf<float> d_table;  // [n_sites, tstride]
+    std::mutex mu;                 // bn_prior_apply_host / bn_prior_read: one thread at a time
+    ~bn_prior() {
+        (void)bn::use_device(device);
+        if (stream) (void)hipStreamSynchronize(stream);
+    }
 };
 
 struct bn::PriorAttach {
@@ -347,8 +351,9 @@ struct bn::PriorAttach {
     std::vector<int32_t> source_sites;
     int32_t site = 0;
     bn::TopkRows rows;            // the last step's filtered rows: device block and pinned mirror
-    uint32_t *d_gkeys = nullptr;  // general select form: [max_batch, n_species]
+    bn::DeviceBuf<uint32_t> d_gkeys;  // general select form: [max_batch, n_species]
     bn::PinnedRing sites;  // per-row site ids of a live step under a map: [max_batch] int32, read by the kernel in place
+    ~PriorAttach();        // drops the reference
 };
 
 namespace {
@@ -360,12 +365,7 @@ using bn::check_launch;
 constexpr uint32_t KNOWN_FLAGS = BN_PRIOR_AFTER_TOPK | BN_PRIOR_RERANK;
 
 void prior_unref(bn_prior *p) {
-    if (!p || p->refs.fetch_sub(1, std::memory_order_acq_rel) != 1) return;
-    (void)bn::use_device(p->device);
-    if (p->stream) (void)hipStreamSynchronize(p->stream);
-    if (p->d_table) (void)bn::gated::Free(p->d_table);
-    if (p->stream) (void)bn::gated::StreamDestroy(p->stream);
-    delete p;
+    if (p && p->refs.fetch_sub(1, std::memory_order_acq_rel) == 1) delete p;
 }
 
 bool general_form(const bn_prior *p) { return (int64_t)p->n_species > bn::SEL_LDS_MAX_N || bn::sw_present(bn::sw::BN_PRIOR_GENERAL); }
@@ -464,7 +464,7 @@ bn_status bn::prior_attach(bn_prior *p, int device, size_t num_species, size_t m
         if (st != BN_OK) return st;
     }
     BN_HIP_TRY(bn::use_device(device));
-    std::unique_ptr<PriorAttach, void (*)(PriorAttach *)> a(new PriorAttach, prior_detach);
+    auto a = std::make_unique<PriorAttach>();
     a->max_batch = max_batch;
     a->top_k = top_k;
     a->has_min = has_min;
@@ -474,7 +474,7 @@ bn_status bn::prior_attach(bn_prior *p, int device, size_t num_species, size_t m
     if (!after) {
         bn_status st = a->rows.reserve(max_batch, k, nullptr, true, true);
         if (st != BN_OK) return st;
-        if (general_form(p)) BN_HIP_TRY(bn::gated::Malloc(&a->d_gkeys, max_batch * p->n_species * sizeof(uint32_t)));
+        if (general_form(p)) BN_HIP_TRY(a->d_gkeys.alloc(max_batch * p->n_species * sizeof(uint32_t)));
     }
     BN_HIP_TRY(a->sites.create(std::max<size_t>(max_batch, 1) * sizeof(int32_t)));
     p->refs.fetch_add(1, std::memory_order_relaxed);
@@ -483,14 +483,8 @@ bn_status bn::prior_attach(bn_prior *p, int device, size_t num_species, size_t m
     return BN_OK;
 }
 
-void bn::prior_detach(PriorAttach *a) {
-    if (!a) return;
-    a->rows.release();
-    if (a->d_gkeys) (void)bn::gated::Free(a->d_gkeys);
-    a->sites.release();
-    prior_unref(a->prior);
-    delete a;
-}
+bn::PriorAttach::~PriorAttach() { prior_unref(prior); }
+void bn::prior_detach(PriorAttach *a) { delete a; }
 
 bn_status bn::prior_set_site(PriorAttach *a, int32_t site) {
     bn_status st = check_site(a->prior, site, "site");
@@ -573,14 +567,14 @@ bn_status bn_prior_create(int32_t device, size_t n_sites, size_t n_species, cons
     if (bn_status dst = bn::require_device(device); dst != BN_OK) return dst;
     BN_HIP_TRY(bn::use_device(device));
     if (!bn::prepare_device(device)) return set_last_error(BN_ERR_BACKEND, "device refused the kernels' dynamic-LDS opt-in");
-    std::unique_ptr<bn_prior, void (*)(bn_prior *)> p(new bn_prior, prior_unref);
+    auto p = std::make_unique<bn_prior>();
     p->device = device;
     p->n_sites = n_sites;
     p->n_species = n_species;
     p->tstride = (n_species + 3) / 4 * 4;
     p->threshold = threshold;
     p->flags = flags;
-    BN_HIP_TRY(bn::gated::Malloc(&p->d_table, n_sites * p->tstride * sizeof(float)));
+    BN_HIP_TRY(p->d_table.alloc(n_sites * p->tstride * sizeof(float)));
     if (p->tstride == n_species) {
         BN_HIP_TRY(bn::gated::Memcpy(p->d_table, table, n_sites * n_species * sizeof(float), hipMemcpyHostToDevice));
     } else {
@@ -636,7 +630,7 @@ bn_status bn_prior_apply_host(const bn_prior *pc, const float *logits, size_t ro
     }
     std::lock_guard<std::mutex> lk(p->mu);
     BN_HIP_TRY(bn::use_device(p->device));
-    if (!p->stream) BN_HIP_TRY(bn::gated::StreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
+    if (!p->stream) BN_HIP_TRY(p->stream.create(hipStreamNonBlocking));
     bn::Scratch bufs;
     bufs.stream = p->stream;  // the prior's own: waited for, not destroyed
     constexpr size_t CHUNK = 1024;  // rows per round

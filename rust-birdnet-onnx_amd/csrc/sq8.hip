@@ -242,31 +242,23 @@ struct bn_sq8 {
     bn_index *x = nullptr;
     int device = 0;
     size_t dim = 0, dpad = 0, covered = 0, cap_pad = 0, out_lists = 0, wg_max = 0;
-    int8_t *d_codes = nullptr;    // [cap_pad, dpad]
-    float *d_scales = nullptr;    // [cap_pad]
-    int8_t *d_qcodes = nullptr;   // [out_lists, dpad]
-    float *d_qscales = nullptr;   // [out_lists]: written, never read (the query's scale is left out of the key)
-    Cand *d_cand = nullptr;       // the scan's [QP, wg_max, MMAX], then the re-rank's [out_lists * RR_SEG, MMAX]
-    int *d_cand_len = nullptr;
-    Cand *d_coarse = nullptr;     // [out_lists, refine]
-    uint32_t *d_ccount = nullptr;   // [out_lists]
-    uint32_t *d_members = nullptr;  // [out_lists, MMAX]
-    uint32_t *d_lists = nullptr;    // [2, out_lists]: q -> q (the list a query "probes"), q -> q * MMAX (its offset)
+    bn::DeviceBuf<int8_t> d_codes;    // [cap_pad, dpad]
+    bn::DeviceBuf<float> d_scales;    // [cap_pad]
+    bn::DeviceBuf<int8_t> d_qcodes;   // [out_lists, dpad]
+    bn::DeviceBuf<float> d_qscales;   // [out_lists]: written, never read (the query's scale is left out of the key)
+    bn::DeviceBuf<Cand> d_cand;       // the scan's [QP, wg_max, MMAX], then the re-rank's [out_lists * RR_SEG, MMAX]
+    bn::DeviceBuf<int> d_cand_len;
+    bn::DeviceBuf<Cand> d_coarse;     // [out_lists, refine]
+    bn::DeviceBuf<uint32_t> d_ccount;   // [out_lists]
+    bn::DeviceBuf<uint32_t> d_members;  // [out_lists, MMAX]
+    bn::DeviceBuf<uint32_t> d_lists;    // [2, out_lists]: q -> q (the list a query "probes"), q -> q * MMAX (its offset)
+    ~bn_sq8() { (void)bn::use_device(device); }
 };
 
 namespace {
 
 using bn::check_launch;
 using bn::set_last_error;
-
-void release(bn_sq8 *v) {
-    if (!v) return;
-    (void)bn::use_device(v->device);
-    for (void *p : {(void *)v->d_codes, (void *)v->d_scales, (void *)v->d_qcodes, (void *)v->d_qscales, (void *)v->d_cand, (void *)v->d_cand_len,
-                    (void *)v->d_coarse, (void *)v->d_ccount, (void *)v->d_members, (void *)v->d_lists})
-        if (p) (void)bn::gated::Free(p);
-    delete v;
-}
 
 // codes and scales of rows [from, size) on the index's stream, then waits: the view covers [0, size)
 bn_status cover(bn_sq8 *v, const bn::IndexScan &s, size_t from) {
@@ -393,7 +385,7 @@ bn_status bn_sq8_build(bn_index *x, bn_sq8 **out) {
     if (st != BN_OK) return st;
     BN_HIP_TRY(g_scan_lds.prepare(s.device, {{(const void *)sq8_scan_kernel<1>, scan_lds(1)}, {(const void *)sq8_scan_kernel<2>, scan_lds(2)},
                                              {(const void *)sq8_scan_kernel<3>, scan_lds(3)}, {(const void *)sq8_scan_kernel<4>, scan_lds(4)}}));
-    std::unique_ptr<bn_sq8, void (*)(bn_sq8 *)> v(new bn_sq8, release);
+    auto v = std::make_unique<bn_sq8>();
     v->x = x;
     v->device = s.device;
     v->dim = s.dim;
@@ -402,16 +394,16 @@ bn_status bn_sq8_build(bn_index *x, bn_sq8 **out) {
     v->out_lists = s.out_lists;
     v->wg_max = (size_t)WG_PER_CU * std::max(1, s.max_wg);
     const size_t units = std::max((size_t)QP * v->wg_max, s.out_lists * RR_SEG);
-    BN_HIP_TRY(bn::gated::Malloc(&v->d_codes, s.cap_pad * s.dpad));
-    BN_HIP_TRY(bn::gated::Malloc(&v->d_scales, s.cap_pad * sizeof(float)));
-    BN_HIP_TRY(bn::gated::Malloc(&v->d_qcodes, s.out_lists * s.dpad));
-    BN_HIP_TRY(bn::gated::Malloc(&v->d_qscales, s.out_lists * sizeof(float)));
-    BN_HIP_TRY(bn::gated::Malloc(&v->d_cand, units * MMAX * sizeof(Cand)));
-    BN_HIP_TRY(bn::gated::Malloc(&v->d_cand_len, units * sizeof(int)));
-    BN_HIP_TRY(bn::gated::Malloc(&v->d_coarse, s.out_lists * MMAX * sizeof(Cand)));
-    BN_HIP_TRY(bn::gated::Malloc(&v->d_ccount, s.out_lists * sizeof(uint32_t)));
-    BN_HIP_TRY(bn::gated::Malloc(&v->d_members, s.out_lists * MMAX * sizeof(uint32_t)));
-    BN_HIP_TRY(bn::gated::Malloc(&v->d_lists, 2 * s.out_lists * sizeof(uint32_t)));
+    BN_HIP_TRY(v->d_codes.alloc(s.cap_pad * s.dpad));
+    BN_HIP_TRY(v->d_scales.alloc(s.cap_pad * sizeof(float)));
+    BN_HIP_TRY(v->d_qcodes.alloc(s.out_lists * s.dpad));
+    BN_HIP_TRY(v->d_qscales.alloc(s.out_lists * sizeof(float)));
+    BN_HIP_TRY(v->d_cand.alloc(units * MMAX * sizeof(Cand)));
+    BN_HIP_TRY(v->d_cand_len.alloc(units * sizeof(int)));
+    BN_HIP_TRY(v->d_coarse.alloc(s.out_lists * MMAX * sizeof(Cand)));
+    BN_HIP_TRY(v->d_ccount.alloc(s.out_lists * sizeof(uint32_t)));
+    BN_HIP_TRY(v->d_members.alloc(s.out_lists * MMAX * sizeof(uint32_t)));
+    BN_HIP_TRY(v->d_lists.alloc(2 * s.out_lists * sizeof(uint32_t)));
     // rows past the covered ones are read by the scan a whole tile at a time and masked by position: they hold zeros
     BN_HIP_TRY(bn::gated::Memset(v->d_codes, 0, s.cap_pad * s.dpad));
     BN_HIP_TRY(bn::gated::Memset(v->d_scales, 0, s.cap_pad * sizeof(float)));
@@ -426,7 +418,7 @@ bn_status bn_sq8_build(bn_index *x, bn_sq8 **out) {
     return BN_OK;
 }
 
-void bn_sq8_free(bn_sq8 *v) { release(v); }
+void bn_sq8_free(bn_sq8 *v) { delete v; }
 
 size_t bn_sq8_rows(const bn_sq8 *v) { return v ? v->covered : 0; }
 

@@ -44,8 +44,8 @@ bn_status TopkRows::reserve(size_t max_batch, size_t k, hipStream_t drain, bool 
     if (need <= cap) return BN_OK;
     if (drain) BN_HIP_TRY(hipStreamSynchronize(drain));  // the last step may still write the old blocks
     release();
-    hipError_t e = device ? gated::Malloc(&d, need * sizeof(uint32_t)) : hipSuccess;
-    if (e == hipSuccess && pinned) e = gated::HostMalloc(&h, need * sizeof(uint32_t), hipHostMallocDefault);
+    hipError_t e = device ? d.alloc(need * sizeof(uint32_t)) : hipSuccess;
+    if (e == hipSuccess && pinned) e = h.alloc(need * sizeof(uint32_t));
     if (e != hipSuccess) {
         release();
         return set_last_error(BN_ERR_BACKEND, std::string("allocating the top-K rows failed: ") + hipGetErrorString(e));
@@ -55,9 +55,8 @@ bn_status TopkRows::reserve(size_t max_batch, size_t k, hipStream_t drain, bool 
 }
 
 void TopkRows::release() {
-    if (d) (void)gated::Free(d);
-    if (h) (void)gated::HostFree(h);
-    d = h = nullptr;
+    d.reset();
+    h.reset();
     cap = last_batch = last_k = 0;
 }
 
@@ -108,21 +107,15 @@ bn_status enqueue_topk_rows(hipStream_t stream, const float *d_logits, size_t ro
 hipError_t PinnedRing::create(size_t bytes) {
     hipError_t e = hipSuccess;
     for (int i = 0; i < SLOTS && e == hipSuccess; i++) {
-        e = gated::HostMalloc(&h[i], bytes, hipHostMallocDefault);
+        e = h[i].alloc(bytes);
         if (e == hipSuccess) e = hipHostGetDevicePointer(&d[i], h[i], 0);
-        if (e == hipSuccess) e = gated::EventCreateWithFlags(&ev[i], hipEventDisableTiming);
+        if (e == hipSuccess) e = ev[i].create(hipEventDisableTiming);
     }
     if (e != hipSuccess) release();
     return e;
 }
 
-void PinnedRing::release() {
-    for (int i = 0; i < SLOTS; i++) {
-        if (h[i]) (void)gated::HostFree(h[i]);
-        if (ev[i]) (void)gated::EventDestroy(ev[i]);
-    }
-    *this = PinnedRing{};
-}
+void PinnedRing::release() { *this = PinnedRing{}; }
 
 hipError_t PinnedRing::acquire(int *slot, void **host) {
     if (busy[next]) {
@@ -140,13 +133,6 @@ hipError_t PinnedRing::commit(int slot, hipStream_t stream) {
     busy[slot] = true;
     next = (slot + 1) % SLOTS;
     return hipSuccess;
-}
-
-Scratch::~Scratch() {
-    if (stream) (void)hipStreamSynchronize(stream);
-    for (void *p : ptrs) (void)gated::Free(p);
-    if (pinned) (void)gated::HostFree(pinned);
-    if (stream && owns_stream) (void)gated::StreamDestroy(stream);
 }
 
 }  // namespace bn

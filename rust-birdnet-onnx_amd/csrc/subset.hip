@@ -276,22 +276,16 @@ struct bn_subset {
     bn_index *x = nullptr;
     int device = 0;
     size_t n = 0;
-    uint32_t *d_ids = nullptr;  // [n] ascending ids of stored rows; NULL for an empty subset
+    bn::DeviceBuf<uint32_t> d_ids;  // [n] ascending ids of stored rows; NULL for an empty subset
+    ~bn_subset() {
+        if (d_ids) (void)bn::use_device(device);
+    }
 };
 
 namespace {
 
 using bn::check_launch;
 using bn::set_last_error;
-
-void release(bn_subset *s) {
-    if (!s) return;
-    if (s->d_ids) {
-        (void)bn::use_device(s->device);
-        (void)bn::gated::Free(s->d_ids);
-    }
-    delete s;
-}
 
 // the scan + merge passes over the nq staged queries (nq <= out_lists, the subset not empty), results into the index's pinned
 // mirrors; synchronous.  The list's tiles are split among the workgroups as bn_index_search splits the slab's
@@ -340,12 +334,12 @@ bn_status search(bn_subset *s, const float *queries, const uint64_t *query_ids, 
 }
 
 // a subset of n ids for index x, the list allocated (n > 0) and not yet written
-bn_status make_subset(bn_index *x, int device, size_t n, std::unique_ptr<bn_subset, void (*)(bn_subset *)> &s) {
+bn_status make_subset(bn_index *x, int device, size_t n, std::unique_ptr<bn_subset> &s) {
     s.reset(new bn_subset);
     s->x = x;
     s->device = device;
     s->n = n;
-    if (n) BN_HIP_TRY(bn::gated::Malloc(&s->d_ids, n * sizeof(uint32_t)));
+    if (n) BN_HIP_TRY(s->d_ids.alloc(n * sizeof(uint32_t)));
     return BN_OK;
 }
 
@@ -374,7 +368,7 @@ bn_status bn_subset_select(bn_index *x, const bn_index_filter *f, size_t struct_
     bn_status st = bn::index_scan_state(x, &xs);
     if (st != BN_OK) return st;
     BN_HIP_TRY(opt_in_scan(xs.device));
-    std::unique_ptr<bn_subset, void (*)(bn_subset *)> s(nullptr, release);
+    std::unique_ptr<bn_subset> s;
     if (first == end) {
         if ((st = make_subset(x, xs.device, 0, s)) != BN_OK) return st;
         *out = s.release();
@@ -428,7 +422,7 @@ bn_status bn_subset_from_ids(bn_index *x, const uint64_t *ids, size_t n, bn_subs
     bn_status st = bn::index_scan_state(x, &xs);
     if (st != BN_OK) return st;
     BN_HIP_TRY(opt_in_scan(xs.device));
-    std::unique_ptr<bn_subset, void (*)(bn_subset *)> s(nullptr, release);
+    std::unique_ptr<bn_subset> s;
     if ((st = make_subset(x, xs.device, n, s)) != BN_OK) return st;
     if (n) {
         const std::vector<uint32_t> v(ids, ids + n);
@@ -438,7 +432,7 @@ bn_status bn_subset_from_ids(bn_index *x, const uint64_t *ids, size_t n, bn_subs
     return BN_OK;
 }
 
-void bn_subset_free(bn_subset *s) { release(s); }
+void bn_subset_free(bn_subset *s) { delete s; }
 
 size_t bn_subset_size(const bn_subset *s) { return s ? s->n : 0; }
 

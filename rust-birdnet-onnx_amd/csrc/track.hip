@@ -222,13 +222,18 @@ struct bn_track {
     size_t n_sources = 0, n_species = 0, max_events = 0;
     float enter_conf = 0.f;
     uint32_t min_hits = 1, max_gap = 0, flags = 0;
-    uint32_t *d_state = nullptr;    // [N_PLANES][n_sources][n_species]
-    uint32_t *d_counter = nullptr;  // one word, zero between updates
-    std::vector<int64_t> last_window;  // per source; -1: none since creation / reset
-    hipStream_t stream = nullptr;      // bn_track_update_host / flush / reset / open_events
-    hipEvent_t last_ev = nullptr;      // recorded behind every update's kernels, on whatever stream ran them
-    bool updated = false;              // last_ev has been recorded
+    bn::Stream stream;                  // bn_track_update_host / flush / reset / open_events
+    bn::Event last_ev;                  // recorded behind every update's kernels, on whatever stream ran them
+    bn::DeviceBuf<uint32_t> d_state;    // [N_PLANES][n_sources][n_species]  (after stream and event: they go last, device_mem.h)
+    bn::DeviceBuf<uint32_t> d_counter;  // one word, zero between updates
+    std::vector<int64_t> last_window;   // per source; -1: none since creation / reset
+    bool updated = false;               // last_ev has been recorded
     std::mutex mu;
+    ~bn_track() {
+        (void)bn::use_device(device);
+        if (updated) (void)hipEventSynchronize(last_ev);
+        if (stream) (void)hipStreamSynchronize(stream);
+    }
 };
 
 struct bn::TrackAttach {
@@ -242,6 +247,7 @@ struct bn::TrackAttach {
     bool res_sorted = false;
     size_t res_stale = 0;
     std::vector<int32_t> order;  // scratch of the grouping
+    ~TrackAttach();              // drops the reference
 };
 
 namespace {
@@ -253,15 +259,7 @@ constexpr uint32_t KNOWN_FLAGS = BN_TRACK_PRIOR;
 constexpr uint64_t WINDOW_LIMIT = 1ull << 31;
 
 void track_unref(bn_track *t) {
-    if (!t || t->refs.fetch_sub(1, std::memory_order_acq_rel) != 1) return;
-    (void)bn::use_device(t->device);
-    if (t->updated) (void)hipEventSynchronize(t->last_ev);
-    if (t->stream) (void)hipStreamSynchronize(t->stream);
-    if (t->d_state) (void)bn::gated::Free(t->d_state);
-    if (t->d_counter) (void)bn::gated::Free(t->d_counter);
-    if (t->last_ev) (void)bn::gated::EventDestroy(t->last_ev);
-    if (t->stream) (void)bn::gated::StreamDestroy(t->stream);
-    delete t;
+    if (t && t->refs.fetch_sub(1, std::memory_order_acq_rel) == 1) delete t;
 }
 
 bn_status check_source(const bn_track *t, int64_t source, const char *what) {
@@ -390,7 +388,7 @@ bn_status bn::track_attach(bn_track *t, int device, size_t num_species, size_t m
     if (device != t->device)
         return set_last_error(BN_ERR_INVALID_ARG, "the context lives on device " + std::to_string(device) + ", the tracker on " + std::to_string(t->device));
     BN_HIP_TRY(bn::use_device(device));
-    std::unique_ptr<TrackAttach, void (*)(TrackAttach *)> a(new TrackAttach, track_detach);
+    auto a = std::make_unique<TrackAttach>();
     a->max_batch = max_batch;
     const size_t rows = std::max<size_t>(max_batch, 1);
     BN_HIP_TRY(a->ring.create(Stage::bytes(rows, rows, t->max_events)));
@@ -401,12 +399,8 @@ bn_status bn::track_attach(bn_track *t, int device, size_t num_species, size_t m
     return BN_OK;
 }
 
-void bn::track_detach(TrackAttach *a) {
-    if (!a) return;
-    a->ring.release();
-    track_unref(a->track);
-    delete a;
-}
+bn::TrackAttach::~TrackAttach() { track_unref(track); }
+void bn::track_detach(TrackAttach *a) { delete a; }
 
 bn_status bn::track_set_source(TrackAttach *a, int32_t source) {
     bn_status st = check_source(a->track, source, "source");
@@ -530,7 +524,7 @@ bn_status bn_track_create(int32_t device, size_t n_sources, size_t n_species, fl
     if (bn_status dst = bn::require_device(device); dst != BN_OK) return dst;
     BN_HIP_TRY(bn::use_device(device));
     if (!bn::prepare_device(device)) return set_last_error(BN_ERR_BACKEND, "device " + std::to_string(device) + " could not be prepared for the library's kernels");
-    std::unique_ptr<bn_track, void (*)(bn_track *)> t(new bn_track, track_unref);
+    auto t = std::make_unique<bn_track>();
     t->device = device;
     t->n_sources = n_sources;
     t->n_species = n_species;
@@ -541,10 +535,10 @@ bn_status bn_track_create(int32_t device, size_t n_sources, size_t n_species, fl
     t->flags = flags;
     t->last_window.assign(n_sources, -1);
     const size_t state_b = (size_t)bn::N_PLANES * n_sources * n_species * sizeof(uint32_t);
-    BN_HIP_TRY(bn::gated::StreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
-    BN_HIP_TRY(bn::gated::EventCreateWithFlags(&t->last_ev, hipEventDisableTiming));
-    BN_HIP_TRY(bn::gated::Malloc(&t->d_state, state_b));
-    BN_HIP_TRY(bn::gated::Malloc(&t->d_counter, sizeof(uint32_t)));
+    BN_HIP_TRY(t->stream.create(hipStreamNonBlocking));
+    BN_HIP_TRY(t->last_ev.create(hipEventDisableTiming));
+    BN_HIP_TRY(t->d_state.alloc(state_b));
+    BN_HIP_TRY(t->d_counter.alloc(sizeof(uint32_t)));
     BN_HIP_TRY(hipMemsetAsync(t->d_state, 0, state_b, t->stream));
     BN_HIP_TRY(hipMemsetAsync(t->d_counter, 0, sizeof(uint32_t), t->stream));
     BN_HIP_TRY(hipStreamSynchronize(t->stream));
@@ -604,7 +598,7 @@ bn_status bn_track_update_host(bn_track *t, const float *logits, size_t rows, co
     bufs.stream = t->stream;  // the tracker's own: waited for, not destroyed
     float *d_logits = nullptr;
     BN_HIP_TRY(bufs.alloc(&d_logits, rows * t->n_species * sizeof(float)));
-    BN_HIP_TRY(bn::gated::HostMalloc(&bufs.pinned, Stage::bytes(rows, rows, t->max_events), hipHostMallocDefault));
+    BN_HIP_TRY(bufs.pinned.alloc(Stage::bytes(rows, rows, t->max_events)));
     Stage sg;
     sg.carve(bufs.pinned, rows, rows, t->max_events);
     BN_HIP_TRY(bn::gated::Memcpy(d_logits, logits, rows * t->n_species * sizeof(float), hipMemcpyHostToDevice));
@@ -629,7 +623,7 @@ bn_status bn_track_flush(bn_track *t, int32_t source, bn_event *events_out, size
     const size_t groups = source < 0 ? t->n_sources : 1;
     bn::Scratch bufs;
     bufs.stream = t->stream;
-    BN_HIP_TRY(bn::gated::HostMalloc(&bufs.pinned, Stage::bytes(1, groups, t->max_events), hipHostMallocDefault));
+    BN_HIP_TRY(bufs.pinned.alloc(Stage::bytes(1, groups, t->max_events)));
     Stage sg;
     sg.carve(bufs.pinned, 1, groups, t->max_events);
     for (size_t g = 0; g < groups; g++) {  // no rows: every group closes what it has open

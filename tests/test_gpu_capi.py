@@ -274,3 +274,74 @@ def test_context_teardown_order_with_framework_objects_on_its_stream(bn, small):
     # the model outlives its contexts and serves a new one
     again, _ = bn.Context(m, 2).infer(x)
     assert again.tobytes() == want.tobytes()
+
+
+# the smallest synthetic model, and the smallest one with an embedding output: BirdNET v2.4 has logits only, so a head and an index
+# can be attached (BN_OK) only to the second
+LIFETIME_MODELS = {
+    "v24": lambda: synth.birdnet_v24(num_species=16, width=0.25, depth=0.25, head=32),
+    "v30_embedding": lambda: synth.birdnet_v30(num_species=16, width=0.25, depth=0.25, emb=32),
+}
+
+
+@pytest.mark.parametrize("family", list(LIFETIME_MODELS))
+def test_context_lifetimes_create_step_submit_attach_destroy(bn, family):
+    """Every way a context ends: destroyed with nothing run, after one step, with a submitted batch never collected, and after a
+    step with a head, an index, a prior and a tracker attached and detached again (and once destroyed with them still attached).
+    Every call is BN_OK (the wrappers raise otherwise) and a fresh context afterwards steps to the bits the first one gave."""
+    m = bn.Model(write_model(LIFETIME_MODELS[family]()))
+    cfg = m.config
+    S, N, B = cfg.sample_count, cfg.num_species, 2
+    x = synth.synthetic_segments(B, S, 48000 if family == "v24" else 32000)
+    rec = bn.Recording(np.ascontiguousarray(x.reshape(-1)))
+
+    def step(ctx):
+        ctx.step_windows(rec, S, 0, B, top_k=5, sync=True)
+        return [a.tobytes() for a in ctx.step_results(B)]
+
+    bn.Context(m, B).close()  # nothing run
+    ctx = bn.Context(m, B)
+    first = step(ctx)
+    assert bn.lib.bn_ctx_device_bytes(ctx._h) > B * S * 4
+    ctx.close()
+    ctx = bn.Context(m, B)
+    assert ctx.submit(x, 5) != 0  # in flight, never collected
+    ctx.close()
+
+    rng = np.random.RandomState(7)
+    prior = bn.Prior(0, rng.uniform(0.0, 1.0, (3, N)).astype(np.float32))
+    tracker = bn.Tracker(0, 1, N, 0.5)
+    head = index = None
+    if cfg.has_embedding:
+        E = cfg.embedding_dim
+        head = bn.Head(0, rng.standard_normal((4, E)).astype(np.float32))
+        index = bn.Index(0, E, 64)
+        index.add(rng.standard_normal((10, E)).astype(np.float32))
+    for detach in (True, False):
+        ctx = bn.Context(m, B)
+        if head is not None:
+            ctx.attach_head(head, top_k=3)
+            ctx.attach_index(index, top_m=4)
+        ctx.attach_prior(prior, top_k=5)
+        ctx.attach_track(tracker)
+        if not detach:
+            tracker.reset(0)  # the windows of a source must increase
+        assert step(ctx) == first
+        assert ctx.step_prior_results(B)[2].shape == (B,) and ctx.step_track_results()[1] == 0
+        if head is not None:
+            assert ctx.step_head_results(B)[0].shape == (B, 4)
+            assert ctx.step_index_results(B)[4] == 10
+        if detach:
+            if head is not None:
+                ctx.attach_head(None)
+                ctx.attach_index(None)
+            ctx.attach_prior(None)
+            ctx.attach_track(None)
+            assert step(ctx) == first  # and steps on without them
+        ctx.close()
+    for h in (head, index, prior, tracker):
+        if h is not None:
+            h.close()
+    ctx = bn.Context(m, B)
+    assert step(ctx) == first
+    ctx.close()
