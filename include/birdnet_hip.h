@@ -957,6 +957,58 @@ bn_status bn_index_search_peaks_ids(bn_index *x, const uint64_t *query_ids, size
                                     size_t top_m, size_t m_stride, uint64_t *id_out, float *score_out, uint32_t *count_out);
 
 /*
+ * Threshold search: EVERY row of an id range that scores at least min_score against a query, in id (= time) order, and how many there
+ * are.  The searches above answer "the M best rows" and stop at 256; a call rate or an occupancy count ("every window that sounds like
+ * this exemplar at cosine >= 0.8", or simply how many) is this call.  The reference has nothing of the kind; this comment is the contract.
+ *
+ *   Hit            row r is a hit of query i iff r lies in the id range, r is valid (not stored as zeros), for the _ids form r is
+ *                  outside exclude_radius of the query's own id by bn_index_search_ids' rule (< 0: none excluded; 0: the row itself),
+ *                  and score(i, r) >= min_score[i] as an IEEE f32 comparison.  min_score holds one value per query, [n_queries]:
+ *                  -inf is legal and makes every eligible row a hit, +inf is legal and gives no hit, NaN is refused.
+ *   Score          the f32 score of bn_index_search, bit for bit: the same k-ordered chain over the padded dim.  The bits depend on
+ *                  dim, the query and the row only: not on the id range, max_hits, the number of queries or the index size.
+ *   Query          bn_index_search's rules: a host query is normalised as an appended row is, and one with zero norm or a non-finite
+ *                  element has count 0; the _ids form takes stored rows as queries, used as stored, and the id of an invalid row
+ *                  has count 0.
+ *   Order          hits come out in id ascending order: the one order a list of unknown length has without a sort, and time order.
+ *   Counts         count_out[i] is the TOTAL number of hits of query i in the range, also when it exceeds max_hits.
+ *   Truncation     entries [0, min(count, max_hits)) of query i's list are written, at i * h_stride: the FIRST hits in id order.
+ *                  Entries past that are not written.  A caller that sees count > max_hits continues with
+ *                  first_id = the last returned id + 1 (and n_ids shortened to the same end); the pages put together are the
+ *                  unpaged list, byte for byte.
+ *   Count only     max_hits == 0 writes the counts alone; id_out, score_out and tag_out may then be NULL, and the call touches no
+ *                  staging memory.
+ *   Tags           tag_out may be NULL.  Otherwise tag_out[j] is the tag of row id_out[j] as the tag plane holds it at the call,
+ *                  or 0 for an index that never tagged (as bn_index_match reports them).  Tags do not decide what is a hit.
+ *   Id range       bn_head_rank_index's convention: rows [first_id, first_id + n_ids), n_ids == 0: to the end.
+ *   Limits         0 <= max_hits <= BN_ABOVE_MAX_HITS, h_stride >= max_hits.
+ *   Refusals       BN_ERR_INVALID_ARG with a message, no output written and nothing changed: max_hits above BN_ABOVE_MAX_HITS,
+ *                  h_stride < max_hits, NULL queries / query_ids, min_score or count_out with n_queries > 0, NULL id_out or score_out
+ *                  with max_hits > 0 and n_queries > 0, a NaN in min_score (the whole array is checked before any work), a NULL
+ *                  index, first_id > bn_index_size or a range that runs past the end, a query id >= bn_index_size.
+ *   Empty cases    an empty index, an empty range or n_queries == 0 gives BN_OK with every count 0.
+ *   No device      without a gfx950 device both calls return BN_ERR_NO_DEVICE and leave the outputs untouched; the refusals that need
+ *                  no index (max_hits, h_stride, the NULLs other than the index, NaN) come before the device is asked for.
+ *   Memory         staging lists and device results are allocated by the first call that needs them and stay with the index.  A
+ *                  pass over the slab serves up to 64 queries; that number shrinks (48, 32, 16, 8, 4, 2, 1) until
+ *                  queries x (workgroups x min(rows of a workgroup, max_hits) x 8 B + max_hits x 12 B) fits 64 MiB.  One query per
+ *                  pass is the floor: at most 8 B x min(rows in the range, workgroups x max_hits) + 12 B x max_hits, under 2 % of
+ *                  the slab.  A large max_hits on a large range therefore costs passes, not memory.
+ *   Determinism    no atomics of any kind; two calls with the same inputs give the same bytes.
+ *   Threading      the index's rule: one thread at a time per index.  The work runs on the index's stream, after a pending
+ *                  bn_index_add_ctx; both calls are synchronous.  The index, its tags and every other search's results are unchanged.
+ *
+ * Outputs are host arrays: id_out / score_out / tag_out [n_queries * h_stride] and count_out [n_queries].
+ */
+#define BN_ABOVE_MAX_HITS 65536u
+bn_status bn_index_search_above(bn_index *x, const float *queries, size_t n_queries, const float *min_score, uint64_t first_id,
+                                uint64_t n_ids, size_t max_hits, size_t h_stride, uint64_t *id_out, float *score_out,
+                                uint32_t *tag_out, uint32_t *count_out);
+bn_status bn_index_search_above_ids(bn_index *x, const uint64_t *query_ids, size_t n_queries, int64_t exclude_radius,
+                                    const float *min_score, uint64_t first_id, uint64_t n_ids, size_t max_hits, size_t h_stride,
+                                    uint64_t *id_out, float *score_out, uint32_t *tag_out, uint32_t *count_out);
+
+/*
  * Persistence of an index: bn_index_save writes the slab's STORED BITS to a file, bn_index_load makes an index from one.  A loaded
  * index behaves in every call exactly as the saved one did at the time of the save: searches, head fits and ranks, assignment,
  * clustering and IVF views are all stated in the bits of the stored rows, and those are what the file holds.  bn_index_read

@@ -61,6 +61,7 @@ ENGINE_SYMBOLS = [
     "bn_index_set_tags", "bn_index_fill_tags", "bn_index_read_tags",
     "bn_subset_select", "bn_subset_from_ids", "bn_subset_free", "bn_subset_size", "bn_subset_read", "bn_subset_search", "bn_subset_search_ids",
     "bn_index_search_peaks", "bn_index_search_peaks_ids",
+    "bn_index_search_above", "bn_index_search_above_ids",
     "bn_head_create", "bn_head_free", "bn_head_dim", "bn_head_classes", "bn_head_flags", "bn_head_read", "bn_head_apply_host",
     "bn_head_fit", "bn_head_fit_index", "bn_head_rank_index", "bn_ctx_attach_head", "bn_step_head_results",
     "bn_ctx_attach_index", "bn_step_index_results", "bn_index_match",
@@ -144,6 +145,7 @@ class BnIndexFilter(C.Structure):
 
 BN_INDEX_TAG_LIMIT = 65536  # row tags lie below it
 BN_PEAK_RADIUS_MAX = 64  # largest peak_radius of Index.search_peaks / search_peaks_ids
+BN_ABOVE_MAX_HITS = 65536  # largest max_hits of Index.search_above / search_above_ids
 BN_FILTER_EXCLUDE_TAGS = 1  # bn_index_filter flag: the tag list names the tags left out
 BN_CLUSTER_NONE = 0xFFFFFFFF  # the assignment of a row that belongs to no cluster
 BN_HEAD_L2NORM = 1
@@ -278,6 +280,9 @@ def _load() -> C.CDLL:
         "bn_subset_search_ids": (i32, [vp, C.POINTER(C.c_uint64), sz, C.c_int64, sz, sz, C.POINTER(C.c_uint64), f32p, u32p]),
         "bn_index_search_peaks": (i32, [vp, f32p, sz, sz, sz, sz, C.POINTER(C.c_uint64), f32p, u32p]),
         "bn_index_search_peaks_ids": (i32, [vp, C.POINTER(C.c_uint64), sz, C.c_int64, sz, sz, sz, C.POINTER(C.c_uint64), f32p, u32p]),
+        "bn_index_search_above": (i32, [vp, f32p, sz, f32p, C.c_uint64, C.c_uint64, sz, sz, C.POINTER(C.c_uint64), f32p, u32p, u32p]),
+        "bn_index_search_above_ids": (i32, [vp, C.POINTER(C.c_uint64), sz, C.c_int64, f32p, C.c_uint64, C.c_uint64, sz, sz, C.POINTER(C.c_uint64), f32p,
+                                            u32p, u32p]),
         "bn_head_create": (i32, [i32, sz, sz, f32p, f32p, C.c_uint32, C.POINTER(vp)]),
         "bn_head_free": (None, [vp]),
         "bn_head_dim": (sz, [vp]),
@@ -1352,6 +1357,56 @@ class Index:
         if st:
             raise EngineError(st)
         return out_ids, scores, counts
+
+    @staticmethod
+    def _thresholds(min_score, n: int) -> np.ndarray:
+        """a scalar or an array [n] -> f32 [n]"""
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(min_score, dtype=np.float32).reshape(-1), (n,)))
+
+    def search_above(self, queries, min_score, max_hits: int, first_id: int = 0, n_ids: int = 0, h_stride: Optional[int] = None):
+        """bn_index_search_above: EVERY row of [first_id, first_id + n_ids) (n_ids 0: to the end) scoring at least min_score (a scalar or
+        one value per query) for host queries [n, dim], in id order: (ids, scores, tags [n, h_stride], counts [n]).  counts[i] is the
+        total number of hits, also beyond max_hits; the first min(counts[i], max_hits) are returned, the entries past them stay as
+        written here (id 0, score NaN, tag 0)."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
+        thr = self._thresholds(min_score, q.shape[0])
+        h_stride = max_hits if h_stride is None else h_stride
+        ids, scores, counts = self._outputs(q.shape[0], max(h_stride, 0))
+        tags = np.zeros(ids.shape, dtype=np.uint32)
+        st = lib.bn_index_search_above(self._h, q.ctypes.data_as(C.POINTER(C.c_float)), q.shape[0], thr.ctypes.data_as(C.POINTER(C.c_float)), first_id,
+                                       n_ids, max_hits, h_stride, ids.ctypes.data_as(C.POINTER(C.c_uint64)), scores.ctypes.data_as(C.POINTER(C.c_float)),
+                                       tags.ctypes.data_as(C.POINTER(C.c_uint32)), counts.ctypes.data_as(C.POINTER(C.c_uint32)))
+        if st:
+            raise EngineError(st)
+        return ids, scores, tags, counts
+
+    def search_above_ids(self, ids, min_score, max_hits: int, exclude_radius: int = -1, first_id: int = 0, n_ids: int = 0,
+                         h_stride: Optional[int] = None):
+        """bn_index_search_above_ids: search_above() with the stored rows `ids` as the queries; rows within exclude_radius of a query's id
+        are no hits."""
+        qi = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+        thr = self._thresholds(min_score, qi.shape[0])
+        h_stride = max_hits if h_stride is None else h_stride
+        out_ids, scores, counts = self._outputs(qi.shape[0], max(h_stride, 0))
+        tags = np.zeros(out_ids.shape, dtype=np.uint32)
+        st = lib.bn_index_search_above_ids(self._h, qi.ctypes.data_as(C.POINTER(C.c_uint64)), qi.shape[0], exclude_radius,
+                                           thr.ctypes.data_as(C.POINTER(C.c_float)), first_id, n_ids, max_hits, h_stride,
+                                           out_ids.ctypes.data_as(C.POINTER(C.c_uint64)), scores.ctypes.data_as(C.POINTER(C.c_float)),
+                                           tags.ctypes.data_as(C.POINTER(C.c_uint32)), counts.ctypes.data_as(C.POINTER(C.c_uint32)))
+        if st:
+            raise EngineError(st)
+        return out_ids, scores, tags, counts
+
+    def count_above(self, queries, min_score, first_id: int = 0, n_ids: int = 0) -> np.ndarray:
+        """bn_index_search_above with max_hits 0: the number of rows of the range scoring at least min_score, per query [n] uint32."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
+        thr = self._thresholds(min_score, q.shape[0])
+        counts = np.zeros(q.shape[0], dtype=np.uint32)
+        st = lib.bn_index_search_above(self._h, q.ctypes.data_as(C.POINTER(C.c_float)), q.shape[0], thr.ctypes.data_as(C.POINTER(C.c_float)), first_id,
+                                       n_ids, 0, 0, None, None, None, counts.ctypes.data_as(C.POINTER(C.c_uint32)))
+        if st:
+            raise EngineError(st)
+        return counts
 
     def set_tags(self, first_id: int, tags) -> None:
         """bn_index_set_tags: rows [first_id, first_id + len(tags)) get the tags given (each below BN_INDEX_TAG_LIMIT)."""

@@ -16,7 +16,8 @@
 // Order everywhere: score descending, ties by id ascending (-0.0 == +0.0 through the float compare).  The candidate, the order and
 // the two merges live in topm_select.h; the scan's constants and LDS layout in index_scan.h, which the subset, peaks and rank scans
 // carve theirs from too.  Other files borrow this index's stream and buffers: rank.hip, subset.hip, peaks.hip, ivf.hip
-// and sq8.hip through index_scan_state, cluster.hip through index_cluster_state.  The host side those searches share is defined
+// and sq8.hip through index_scan_state, cluster.hip through index_cluster_state, above.hip through both index_scan_state and
+// index_above_state.  The host side those searches share is defined
 // here once (declared in capi_internal.h): the LDS opt-in (LdsOptIn), the argument refusals (check_top_m, check_search_buffers),
 // the pass loop with its merge and copy-back (run_scan_passes, index_enqueue_merge) and the copy into the caller's arrays
 // (scatter_results); subset.hip also reads the tag plane below.
@@ -263,11 +264,13 @@ struct bn_index {
     bn::PinnedBuf<uint32_t> h_count;
     bn::ClusterState *cluster = nullptr;  // cluster.hip's buffers, allocated by the first bn_index_assign / bn_index_cluster
     bn::DeviceBuf<uint16_t> tags;  // [cap_pad], allocated by the first bn_index_set_tags / bn_index_fill_tags; absent: every tag is 0
+    bn::AboveState *above = nullptr;  // above.hip's buffers, allocated by the first bn_index_search_above / _ids
     ~bn_index() {
         (void)bn::use_device(device);
         if (stream) (void)hipStreamSynchronize(stream);
         if (ev) (void)hipEventSynchronize(ev);
         bn::cluster_state_free(cluster);
+        bn::above_state_free(above);
     }
 };
 
@@ -424,6 +427,7 @@ bn_status bn::index_stage_query_ids(bn_index *x, const uint64_t *ids, size_t n, 
 }
 
 bn::ClusterState **bn::index_cluster_state(bn_index *x) { return &x->cluster; }
+bn::AboveState **bn::index_above_state(bn_index *x) { return &x->above; }
 
 void bn::index_ref(bn_index *x) { x->refs.fetch_add(1, std::memory_order_relaxed); }
 void bn::index_unref(bn_index *x) { unref(x); }

@@ -2,7 +2,8 @@
 // definition: the constants and the layout of their dynamic LDS.  index.hip (index_scan_kernel), subset.hip (subset_scan_kernel),
 // peaks.hip (peaks_scan_kernel) and rank.hip (rank_scan_kernel) carve their LDS from Layout's offsets and size their launches by
 // Layout::BYTES.  Each keeps its own copy of the tile loop: written as instantiations of one templated body the subset, peaks and
-// exact-search kernels measured slower than their hand-written forms ("One layout and one host path").
+// exact-search kernels measured slower than their hand-written forms ("One layout and one host path").  above.hip
+// (above_scan_kernel) keeps a copy of the loop too, over the smaller AboveLayout below.
 // Include from a .hip file.
 #pragma once
 #include <cstddef>
@@ -38,6 +39,18 @@ struct Layout {
 static_assert(Layout<1>::BYTES == 125184 && Layout<3>::BYTES == 158464, "the scans' LDS sizes are part of their launch contract");
 static_assert(Layout<3>::BYTES <= 160 * 1024, "gfx950 has 160 KB of LDS per workgroup");
 static_assert(Layout<1>::S % 16 == 0 && PLANE % 64 == 0, "float4 stores of the k chunk; planes of equal bank phase");
+
+// the dynamic LDS of the threshold scan (above.hip, above_scan_kernel): Layout<1>'s k chunk and score plane at the same offsets, then
+// one threshold and one running hit count per list.  It selects nothing, so it has no pending lists, merge scratch or running M-th
+struct AboveLayout {
+    static constexpr size_t B = Layout<1>::B;                 // float [LP][QS_LD]
+    static constexpr size_t S = Layout<1>::S;                 // float [LP][S_LD]
+    static constexpr size_t THR = S + (size_t)PLANE * 4;      // float [LP]: min_score of the list
+    static constexpr size_t CNT = THR + LP * sizeof(float);   // uint32 [LP]: hits of the list in this workgroup's tiles so far
+    static constexpr size_t BYTES = CNT + LP * sizeof(unsigned);
+};
+static_assert(AboveLayout::BYTES == 50944, "the threshold scan's LDS size is part of its launch contract");
+static_assert(AboveLayout::BYTES <= 64 * 1024, "below the size from which a kernel must opt in; three workgroups fit a CU's 160 KB");
 
 }  // namespace scan
 }  // namespace bn
