@@ -449,7 +449,7 @@ bn_status bn_index_search(bn_index *x, const float *queries, size_t n_queries, s
 bn_status bn_index_search_ids(bn_index *x, const uint64_t *query_ids, size_t n_queries, int64_t exclude_radius,
                               size_t top_m, size_t m_stride, uint64_t *id_out, float *score_out, uint32_t *count_out);
 /* Row tags: every row carries one tag below BN_INDEX_TAG_LIMIT, 0 until set: a source, a site, a species, a tombstone -- the caller's
- * meaning.  bn_subset_select (below) chooses rows by tag and a match (bn_ctx_attach_index, bn_index_match) returns the tags of its hits; NOTHING ELSE reads a tag: bn_index_search, bn_index_search_ids, bn_ivf_*,
+ * meaning.  bn_subset_select (below) chooses rows by tag, a match (bn_ctx_attach_index, bn_index_match) and bn_index_search_above return the tags of their hits and bn_index_group_above groups its hits by tag; NOTHING ELSE reads a tag: bn_index_search, bn_index_search_ids, bn_ivf_*,
  * bn_sq8_*, bn_head_fit_index, bn_head_rank_index, bn_index_assign, bn_index_cluster and bn_index_save behave the same, bit for bit, with
  * and without tags.  The plane (two bytes per row of capacity) is allocated by the first bn_index_set_tags / bn_index_fill_tags; an index
  * that never tags pays nothing, and an absent plane reads as zeros.  The index file has no tags: it stays format version 1 and a loaded
@@ -1007,6 +1007,67 @@ bn_status bn_index_search_above(bn_index *x, const float *queries, size_t n_quer
 bn_status bn_index_search_above_ids(bn_index *x, const uint64_t *query_ids, size_t n_queries, int64_t exclude_radius,
                                     const float *min_score, uint64_t first_id, uint64_t n_ids, size_t max_hits, size_t h_stride,
                                     uint64_t *id_out, float *score_out, uint32_t *tag_out, uint32_t *count_out);
+
+/*
+ * Grouped threshold search: the hits of bn_index_search_above grouped by row tag -- per (query, tag) how many there are, the best one,
+ * the first and the last in id (= time) order -- without returning a single hit.  "At which sites and on which days does this call
+ * occur, how often, from when to when, and which is the best example at each" is one pass over the slab, whatever the number of
+ * hits: what crosses the bus is one record per (query, group).  The reference has nothing of the kind; this comment is the contract.
+ *
+ *   Hit            bn_index_search_above's rule: row r is a hit of query i iff r lies in the id range, r is valid (not stored as
+ *                  zeros), for the _ids form r is outside exclude_radius of the query's own id by bn_index_search_ids' rule (< 0: none
+ *                  excluded; 0: the row itself), and score(i, r) >= min_score[i] as an IEEE f32 comparison.  min_score holds one value
+ *                  per query, [n_queries]: -inf is legal and makes every eligible row a hit, +inf is legal and gives no hit, NaN is
+ *                  refused.
+ *   Score          the f32 score of bn_index_search, bit for bit.
+ *   Query          bn_index_search's rules: a host query is normalised as an appended row is, and one with zero norm or a non-finite
+ *                  element has no hits; the _ids form takes stored rows as queries, used as stored, and the id of an invalid row has
+ *                  no hits.
+ *   Group          the group of a hit is the row's tag as the tag plane holds it at the call; every row of an index that never tagged
+ *                  has tag 0.  A hit whose tag is >= n_groups belongs to no group and is counted in other_out[i] only.
+ *   Record         of (query i, group g), at i * g_stride + g of each array:
+ *                    count_out                     the number of hits of the group (u32);
+ *                    best_id_out / best_score_out  the hit with the highest score, ties broken by the lowest id: the index's order,
+ *                                                  with -0.0 == +0.0;
+ *                    first_id_out / last_id_out    the smallest and the largest id among the hits.
+ *                  A group with count 0 gets BN_GROUP_NO_ROW in the three id arrays and 0.0f in best_score_out, so every byte of
+ *                  entries [0, n_groups) of a query's rows is determined.  Entries [n_groups, g_stride) are not written.
+ *   Totals         total_out[i] is the sum over the groups of count plus other_out[i]; it equals bn_index_search_above's count_out[i]
+ *                  for the same arguments.
+ *   Optional       each of best_id_out + best_score_out (a pair: both or neither), first_id_out, last_id_out, other_out and
+ *                  total_out may be NULL and is then not computed for the caller.  count_out is required when n_queries > 0.
+ *   Id range       bn_head_rank_index's convention: rows [first_id, first_id + n_ids), n_ids == 0: to the end.
+ *   Limits         1 <= n_groups <= BN_INDEX_TAG_LIMIT, g_stride >= n_groups.
+ *   Refusals       BN_ERR_INVALID_ARG with a message, no output written and nothing changed: n_groups outside 1..BN_INDEX_TAG_LIMIT,
+ *                  g_stride < n_groups, only one of best_id_out / best_score_out, NULL queries / query_ids, min_score or count_out
+ *                  with n_queries > 0, a NaN in min_score (the whole array is checked before any work), a NULL index,
+ *                  first_id > bn_index_size or a range that runs past the end, a query id >= bn_index_size.
+ *   Empty cases    an empty index, an empty range or n_queries == 0 gives BN_OK; every count, other and total is 0 and every record
+ *                  written is the empty record.
+ *   No device      without a gfx950 device both calls return BN_ERR_NO_DEVICE and leave the outputs untouched; the refusals that need
+ *                  no index (n_groups, g_stride, the pair, the NULLs other than the index, NaN) come before the device is asked for.
+ *   Memory         a device table of queries x n_groups records of 20 B, the finished records (as much again) and their pinned
+ *                  mirror are allocated by the first call that needs them, grown by a later call that needs more, and stay with the
+ *                  index.  A pass over the slab serves up to 64 queries; that number shrinks (48, 32, ...) until the table fits
+ *                  64 MiB: 48 queries per pass at n_groups = 65536, 64 up to n_groups = 52428.
+ *   Determinism    two calls with the same inputs give the same bytes.  The table is updated with integer atomics whose results do
+ *                  not depend on their order (add on counts, max on a packed score-and-id key, min and max on ids); no
+ *                  floating-point atomics.
+ *   Threading      the index's rule: one thread at a time per index.  The work runs on the index's stream, after a pending
+ *                  bn_index_add_ctx; both calls are synchronous.  The index, its tags and every other search's results are unchanged.
+ *
+ * Outputs are host arrays: count_out / best_id_out / best_score_out / first_id_out / last_id_out [n_queries * g_stride] and
+ * other_out / total_out [n_queries].
+ */
+#define BN_GROUP_NO_ROW UINT64_MAX
+bn_status bn_index_group_above(bn_index *x, const float *queries, size_t n_queries, const float *min_score, uint64_t first_id,
+                               uint64_t n_ids, size_t n_groups, size_t g_stride, uint32_t *count_out, uint64_t *best_id_out,
+                               float *best_score_out, uint64_t *first_id_out, uint64_t *last_id_out, uint32_t *other_out,
+                               uint32_t *total_out);
+bn_status bn_index_group_above_ids(bn_index *x, const uint64_t *query_ids, size_t n_queries, int64_t exclude_radius,
+                                   const float *min_score, uint64_t first_id, uint64_t n_ids, size_t n_groups, size_t g_stride,
+                                   uint32_t *count_out, uint64_t *best_id_out, float *best_score_out, uint64_t *first_id_out,
+                                   uint64_t *last_id_out, uint32_t *other_out, uint32_t *total_out);
 
 /*
  * Persistence of an index: bn_index_save writes the slab's STORED BITS to a file, bn_index_load makes an index from one.  A loaded

@@ -62,6 +62,7 @@ ENGINE_SYMBOLS = [
     "bn_subset_select", "bn_subset_from_ids", "bn_subset_free", "bn_subset_size", "bn_subset_read", "bn_subset_search", "bn_subset_search_ids",
     "bn_index_search_peaks", "bn_index_search_peaks_ids",
     "bn_index_search_above", "bn_index_search_above_ids",
+    "bn_index_group_above", "bn_index_group_above_ids",
     "bn_head_create", "bn_head_free", "bn_head_dim", "bn_head_classes", "bn_head_flags", "bn_head_read", "bn_head_apply_host",
     "bn_head_fit", "bn_head_fit_index", "bn_head_rank_index", "bn_ctx_attach_head", "bn_step_head_results",
     "bn_ctx_attach_index", "bn_step_index_results", "bn_index_match",
@@ -146,6 +147,7 @@ class BnIndexFilter(C.Structure):
 BN_INDEX_TAG_LIMIT = 65536  # row tags lie below it
 BN_PEAK_RADIUS_MAX = 64  # largest peak_radius of Index.search_peaks / search_peaks_ids
 BN_ABOVE_MAX_HITS = 65536  # largest max_hits of Index.search_above / search_above_ids
+BN_GROUP_NO_ROW = 0xFFFFFFFFFFFFFFFF  # the best / first / last id of a group without hits (Index.group_above / group_above_ids)
 BN_FILTER_EXCLUDE_TAGS = 1  # bn_index_filter flag: the tag list names the tags left out
 BN_CLUSTER_NONE = 0xFFFFFFFF  # the assignment of a row that belongs to no cluster
 BN_HEAD_L2NORM = 1
@@ -283,6 +285,10 @@ def _load() -> C.CDLL:
         "bn_index_search_above": (i32, [vp, f32p, sz, f32p, C.c_uint64, C.c_uint64, sz, sz, C.POINTER(C.c_uint64), f32p, u32p, u32p]),
         "bn_index_search_above_ids": (i32, [vp, C.POINTER(C.c_uint64), sz, C.c_int64, f32p, C.c_uint64, C.c_uint64, sz, sz, C.POINTER(C.c_uint64), f32p,
                                             u32p, u32p]),
+        "bn_index_group_above": (i32, [vp, f32p, sz, f32p, C.c_uint64, C.c_uint64, sz, sz, u32p, C.POINTER(C.c_uint64), f32p, C.POINTER(C.c_uint64),
+                                       C.POINTER(C.c_uint64), u32p, u32p]),
+        "bn_index_group_above_ids": (i32, [vp, C.POINTER(C.c_uint64), sz, C.c_int64, f32p, C.c_uint64, C.c_uint64, sz, sz, u32p, C.POINTER(C.c_uint64), f32p,
+                                           C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), u32p, u32p]),
         "bn_head_create": (i32, [i32, sz, sz, f32p, f32p, C.c_uint32, C.POINTER(vp)]),
         "bn_head_free": (None, [vp]),
         "bn_head_dim": (sz, [vp]),
@@ -1407,6 +1413,51 @@ class Index:
         if st:
             raise EngineError(st)
         return counts
+
+    @staticmethod
+    def _group_outputs(n: int, g_stride: int):
+        """the seven output arrays of group_above, as the binding fills them before the call: what lies past n_groups stays like this
+        (count 0, ids BN_GROUP_NO_ROW, score NaN)"""
+        none = np.uint64(BN_GROUP_NO_ROW)
+        return (np.zeros((n, g_stride), dtype=np.uint32), np.full((n, g_stride), none, dtype=np.uint64), np.full((n, g_stride), np.nan, dtype=np.float32),
+                np.full((n, g_stride), none, dtype=np.uint64), np.full((n, g_stride), none, dtype=np.uint64), np.zeros(n, dtype=np.uint32),
+                np.zeros(n, dtype=np.uint32))
+
+    @staticmethod
+    def _group_pointers(out):
+        u64p = C.POINTER(C.c_uint64)
+        u32p = C.POINTER(C.c_uint32)
+        return (out[0].ctypes.data_as(u32p), out[1].ctypes.data_as(u64p), out[2].ctypes.data_as(C.POINTER(C.c_float)), out[3].ctypes.data_as(u64p),
+                out[4].ctypes.data_as(u64p), out[5].ctypes.data_as(u32p), out[6].ctypes.data_as(u32p))
+
+    def group_above(self, queries, min_score, n_groups: int, first_id: int = 0, n_ids: int = 0, g_stride: Optional[int] = None):
+        """bn_index_group_above: the rows of [first_id, first_id + n_ids) (n_ids 0: to the end) scoring at least min_score (a scalar or one
+        value per query) for host queries [n, dim], grouped by row tag: (counts, best_ids, best_scores, first_ids, last_ids [n, g_stride],
+        other, total [n]).  Group g of query i is entry [i, g]; a group without hits has count 0, ids BN_GROUP_NO_ROW and score 0.0; hits
+        whose tag is >= n_groups are counted in other[i] only; total[i] = counts[i, :n_groups].sum() + other[i]."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
+        thr = self._thresholds(min_score, q.shape[0])
+        g_stride = n_groups if g_stride is None else g_stride
+        out = self._group_outputs(q.shape[0], max(g_stride, 0))
+        st = lib.bn_index_group_above(self._h, q.ctypes.data_as(C.POINTER(C.c_float)), q.shape[0], thr.ctypes.data_as(C.POINTER(C.c_float)), first_id,
+                                      n_ids, n_groups, g_stride, *self._group_pointers(out))
+        if st:
+            raise EngineError(st)
+        return out
+
+    def group_above_ids(self, ids, min_score, n_groups: int, exclude_radius: int = -1, first_id: int = 0, n_ids: int = 0,
+                        g_stride: Optional[int] = None):
+        """bn_index_group_above_ids: group_above() with the stored rows `ids` as the queries; rows within exclude_radius of a query's id
+        are no hits."""
+        qi = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+        thr = self._thresholds(min_score, qi.shape[0])
+        g_stride = n_groups if g_stride is None else g_stride
+        out = self._group_outputs(qi.shape[0], max(g_stride, 0))
+        st = lib.bn_index_group_above_ids(self._h, qi.ctypes.data_as(C.POINTER(C.c_uint64)), qi.shape[0], exclude_radius,
+                                          thr.ctypes.data_as(C.POINTER(C.c_float)), first_id, n_ids, n_groups, g_stride, *self._group_pointers(out))
+        if st:
+            raise EngineError(st)
+        return out
 
     def set_tags(self, first_id: int, tags) -> None:
         """bn_index_set_tags: rows [first_id, first_id + len(tags)) get the tags given (each below BN_INDEX_TAG_LIMIT)."""

@@ -292,6 +292,11 @@ void cluster_state_free(ClusterState *s);
 struct AboveState;
 AboveState **index_above_state(bn_index *x);
 void above_state_free(AboveState *s);
+// index.hip <-> group.hip (bn_index_group_above and its _ids form): the grouped threshold search's buffers of an index, owned by
+// group.hip, NULL until a call first needs them; bn_index_free hands them to group_state_free with the index's stream idle
+struct GroupState;
+GroupState **index_group_state(bn_index *x);
+void group_state_free(GroupState *s);
 // index.hip -> match.hip: a reference on an index (bn_index_free drops the caller's; the slab lives until the last is gone), its
 // device and stream, the current tag plane ([capacity] u16 on the device, NULL until a tag is first set), and index_normalise_kernel
 // enqueued on `stream`: n rows at d_src (row stride src_stride floats) -> d_dst [n, dpad] + d_valid [n], the index's rule and bits

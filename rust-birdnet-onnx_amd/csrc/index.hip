@@ -17,7 +17,7 @@
 // the two merges live in topm_select.h; the scan's constants and LDS layout in index_scan.h, which the subset, peaks and rank scans
 // carve theirs from too.  Other files borrow this index's stream and buffers: rank.hip, subset.hip, peaks.hip, ivf.hip
 // and sq8.hip through index_scan_state, cluster.hip through index_cluster_state, above.hip through both index_scan_state and
-// index_above_state.  The host side those searches share is defined
+// index_above_state, group.hip likewise through index_group_state.  The host side those searches share is defined
 // here once (declared in capi_internal.h): the LDS opt-in (LdsOptIn), the argument refusals (check_top_m, check_search_buffers),
 // the pass loop with its merge and copy-back (run_scan_passes, index_enqueue_merge) and the copy into the caller's arrays
 // (scatter_results); subset.hip also reads the tag plane below.
@@ -265,12 +265,14 @@ struct bn_index {
     bn::ClusterState *cluster = nullptr;  // cluster.hip's buffers, allocated by the first bn_index_assign / bn_index_cluster
     bn::DeviceBuf<uint16_t> tags;  // [cap_pad], allocated by the first bn_index_set_tags / bn_index_fill_tags; absent: every tag is 0
     bn::AboveState *above = nullptr;  // above.hip's buffers, allocated by the first bn_index_search_above / _ids
+    bn::GroupState *group = nullptr;  // group.hip's buffers, allocated by the first bn_index_group_above / _ids
     ~bn_index() {
         (void)bn::use_device(device);
         if (stream) (void)hipStreamSynchronize(stream);
         if (ev) (void)hipEventSynchronize(ev);
         bn::cluster_state_free(cluster);
         bn::above_state_free(above);
+        bn::group_state_free(group);
     }
 };
 
@@ -428,6 +430,7 @@ bn_status bn::index_stage_query_ids(bn_index *x, const uint64_t *ids, size_t n, 
 
 bn::ClusterState **bn::index_cluster_state(bn_index *x) { return &x->cluster; }
 bn::AboveState **bn::index_above_state(bn_index *x) { return &x->above; }
+bn::GroupState **bn::index_group_state(bn_index *x) { return &x->group; }
 
 void bn::index_ref(bn_index *x) { x->refs.fetch_add(1, std::memory_order_relaxed); }
 void bn::index_unref(bn_index *x) { unref(x); }
