@@ -244,7 +244,9 @@ bn_status bn_ctx_output_device(const bn_ctx *c, int32_t index, const float **d_p
 bn_status bn_ctx_read_output(bn_ctx *c, int32_t index, size_t batch_size, float *host_out);
 /* Block until the context's stream is idle (IoBinding::synchronize_outputs, batch_context.rs:276-281). */
 bn_status bn_ctx_synchronize(bn_ctx *c);
-/* The context's hipStream_t, for callers that order their own device work after it. */
+/* The context's hipStream_t, for callers that order their own device work after it.  It is a non-blocking stream at the greatest
+ * priority the device reports, so that the contexts' streams do not share the default level's hardware queues with the null
+ * stream (BN_CTX_STREAM_PRIO=0: default priority). */
 void *bn_ctx_stream(const bn_ctx *c);
 /* Mean device time per launch group of the last timed run is not kept here;
  * use bn_ctx_time_kernels to measure: runs the plan once for batch_size with a

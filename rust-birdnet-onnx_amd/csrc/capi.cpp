@@ -653,6 +653,42 @@ static bn_status ensure_step_block(bn_ctx *c, size_t k);
 
 void bn_set_sharing_mode(int32_t mode) { bn::device_sharing_mode(mode); }
 
+// ---- the stream a context runs its plans on --------------------------------------------------------------------
+// The runtime maps a process's streams onto hardware queues, GPU_MAX_HW_QUEUES (4 unless the caller exports more) PER PRIORITY LEVEL:
+// a level's pool is filled up to that budget before two of its streams share a queue.  The null stream -- torch's, and most callers'
+// -- and every default-priority stream of the process live in the default level's pool, so the fourth of four default-priority
+// contexts shares a queue with a sibling and its steps wait behind that sibling's (0.63 ms per step against 0.46 ms).
+// Streams that run plans are therefore created at ONE other level, the same for every context: they fill a pool of their own and
+// leave the default pool to the null stream, the caller's streams and the library's helper streams (group ranks, uploads, live
+// ingest, index / head / prior / tracker calls of their own), none of which runs plan-sized work next to the steps.  The greatest
+// priority is the level taken: where a context's step meets default-priority work of the same process (a copy in front of a
+// batch-1 request), the step is the work somebody waits for.  All contexts share the level, so nothing is prioritised AMONG them.
+enum class PlanStreamLevel { Default, Greatest };
+static constexpr PlanStreamLevel kPlanStreamLevel = PlanStreamLevel::Greatest;
+
+static hipError_t create_plan_stream(bn::Stream &s, int dev) {  // the thread's device is `dev`
+    static const bool own_pool = sw_on(sw::BN_CTX_STREAM_PRIO) && kPlanStreamLevel != PlanStreamLevel::Default;
+    if (!own_pool) return s.create(hipStreamNonBlocking);
+    struct Range {
+        int least, greatest;
+    };
+    static std::mutex mu;
+    static std::map<int, Range> ranges;  // asked once per device
+    Range r{};
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        auto it = ranges.find(dev);
+        if (it == ranges.end()) {
+            hipError_t e = hipDeviceGetStreamPriorityRange(&r.least, &r.greatest);
+            if (e != hipSuccess) return e;
+            it = ranges.emplace(dev, r).first;
+        }
+        r = it->second;
+    }
+    if (r.least == r.greatest) return s.create(hipStreamNonBlocking);  // one level: there is no second pool to take
+    return s.create(hipStreamNonBlocking, r.greatest);
+}
+
 bn_status bn_ctx_create(bn_model *m, size_t max_batch, uint32_t flags, bn_ctx **out) {
     if (!m || !out) return fail(BN_ERR_INVALID_ARG, "null argument");
     *out = nullptr;
@@ -677,7 +713,7 @@ bn_status bn_ctx_create(bn_model *m, size_t max_batch, uint32_t flags, bn_ctx **
     const Plan &p = *pd->plan;
     BN_HIP_TRY(bn::use_device(m->device));
     if (!prepare_device(m->device)) return fail(BN_ERR_BACKEND, "device " + std::to_string(m->device) + " refused the kernels' dynamic-LDS opt-in");
-    BN_HIP_TRY(c->stream.create(hipStreamNonBlocking));
+    BN_HIP_TRY(create_plan_stream(c->stream, m->device));
     const size_t arena_b = (size_t)p.arena_elems * max_batch * sizeof(float);
     const size_t in_b = (size_t)p.sample_count * max_batch * sizeof(float);
     BN_HIP_TRY(c->d_arena.alloc(arena_b));

@@ -17,6 +17,7 @@ struct GatedRuntime {
     static hipError_t host_alloc(void **p, size_t bytes, unsigned flags) { return gated::HostMalloc(p, bytes, flags); }
     static hipError_t host_free(void *p) { return gated::HostFree(p); }
     static hipError_t stream_create(hipStream_t *s, unsigned flags) { return gated::StreamCreateWithFlags(s, flags); }
+    static hipError_t stream_create_prio(hipStream_t *s, unsigned flags, int priority) { return gated::StreamCreateWithPriority(s, flags, priority); }
     static hipError_t stream_destroy(hipStream_t s) { return gated::StreamDestroy(s); }
     static hipError_t event_create(hipEvent_t *e, unsigned flags) { return gated::EventCreateWithFlags(e, flags); }
     static hipError_t event_destroy(hipEvent_t e) { return gated::EventDestroy(e); }
@@ -98,6 +99,14 @@ struct StreamOf : Owned<hipStream_t, StreamRelease<P>> {
         this->reset();
         hipStream_t s = nullptr;
         hipError_t e = P::stream_create(&s, flags);
+        if (e == hipSuccess) this->adopt(s);
+        return e;
+    }
+    // at a priority level of the device's range (hipDeviceGetStreamPriorityRange); released like any other stream
+    hipError_t create(unsigned flags, int priority) {
+        this->reset();
+        hipStream_t s = nullptr;
+        hipError_t e = P::stream_create_prio(&s, flags, priority);
         if (e == hipSuccess) this->adopt(s);
         return e;
     }

@@ -38,6 +38,7 @@ inline hipError_t HostFree(void *p) { Shared g; return ::hipHostFree(p); }
 inline hipError_t Memcpy(void *dst, const void *src, size_t n, hipMemcpyKind k) { Shared g; return ::hipMemcpy(dst, src, n, k); }
 inline hipError_t Memset(void *dst, int v, size_t n) { Shared g; return ::hipMemset(dst, v, n); }
 inline hipError_t StreamCreateWithFlags(hipStream_t *s, unsigned flags) { Shared g; return ::hipStreamCreateWithFlags(s, flags); }
+inline hipError_t StreamCreateWithPriority(hipStream_t *s, unsigned flags, int priority) { Shared g; return ::hipStreamCreateWithPriority(s, flags, priority); }
 inline hipError_t StreamDestroy(hipStream_t s) { Shared g; return ::hipStreamDestroy(s); }
 inline hipError_t EventCreate(hipEvent_t *e) { Shared g; return ::hipEventCreate(e); }
 inline hipError_t EventCreateWithFlags(hipEvent_t *e, unsigned flags) { Shared g; return ::hipEventCreateWithFlags(e, flags); }

@@ -26,7 +26,8 @@
     X(present,     BN_ALLOW_ANY_ARCH,     false,  "bn_model_load / bn_ctx_create accept a device that is not gfx950 (presence only: =0 also allows)") \
     X(present,     BN_NO_GRAPH,           false,  "every context runs its plan launch by launch, as with BN_CTX_NO_GRAPH (presence only: =0 also disables graphs)") \
     X(integer,     BN_STRICT_GRAPH,       0,      "non-zero: a capture that does not become a graph is an error instead of a counted fall-back (read once)") \
-    X(integer,     BN_INPUT_MEMCPY,       0,      "non-zero: a caller's device input reaches the context's buffer by hipMemcpyAsync, not by the copy kernel (read once)") \
+    X(on_unless_0, BN_CTX_STREAM_PRIO,    true,   "0 creates a context's stream at the default priority, in the queue pool the null stream and the caller's streams use (read once)") \
+    X(integer,     BN_INPUT_MEMCPY,      0,      "non-zero: a caller's device input reaches the context's buffer by hipMemcpyAsync, not by the copy kernel (read once)") \
     X(integer,     BN_SDMA_COPY,          0,      "non-zero: results reach pinned host memory by hipMemcpyAsync, not by the kernel's own stores (read once)") \
     X(int64,       BN_STAGE_THREADS,      0,      "threads that stage host slices into pinned memory, clamped to 0 .. 64; unset: min(6, half the hardware threads)") \
     X(integer,     BN_UPLOAD_CHUNK_MB,    4,      "MiB per piece of a constants upload (at least 1)") \

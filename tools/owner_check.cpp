@@ -54,6 +54,12 @@ struct Counting {
     static hipError_t host_alloc(void **p, size_t, unsigned) { return acquire_as(p); }
     static hipError_t host_free(void *p) { return give_back(reinterpret_cast<uintptr_t>(p)); }
     static hipError_t stream_create(hipStream_t *s, unsigned) { return acquire_as(s); }
+    static inline int prio_creates = 0, last_prio = 0;
+    static hipError_t stream_create_prio(hipStream_t *s, unsigned, int priority) {
+        hipError_t e = acquire_as(s);
+        if (e == hipSuccess) prio_creates++, last_prio = priority;
+        return e;
+    }
     static hipError_t stream_destroy(hipStream_t s) { return give_back(reinterpret_cast<uintptr_t>(s)); }
     static hipError_t event_create(hipEvent_t *e, unsigned) { return acquire_as(e); }
     static hipError_t event_destroy(hipEvent_t e) { return give_back(reinterpret_cast<uintptr_t>(e)); }
@@ -63,6 +69,7 @@ using Dev = bn::DeviceBuf<float, Counting>;
 using Pin = bn::PinnedBuf<float, Counting>;
 using Str = bn::StreamOf<Counting>;
 using Evt = bn::EventOf<Counting>;
+struct PrioStr : Str {};  // the same owner, acquired through create(flags, priority)
 
 int g_checks = 0, g_failed = 0;
 #define CHECK(cond)                                                            \
@@ -79,6 +86,7 @@ bool balanced() { return Counting::acquired == Counting::released && Counting::d
 hipError_t acquire(Dev &o) { return o.alloc(64); }
 hipError_t acquire(Pin &o) { return o.alloc(64); }
 hipError_t acquire(Str &o) { return o.create(hipStreamNonBlocking); }
+hipError_t acquire(PrioStr &o) { return o.create(hipStreamNonBlocking, -1); }
 hipError_t acquire(Evt &o) { return o.create(hipEventDisableTiming); }
 
 // what every owner promises, whichever resource it holds
@@ -234,6 +242,16 @@ int main() {
     check_owner<Pin>();
     check_owner<Str>();
     check_owner<Evt>();
+    const int before = Counting::prio_creates;
+    check_owner<PrioStr>();  // every promise again for a stream created at a priority level
+    CHECK(Counting::prio_creates > before && Counting::last_prio == -1);
+    Counting::restart();
+    {
+        Str s;  // one owner, both forms: each creation releases what the other left
+        CHECK(s.create(hipStreamNonBlocking, -1) == hipSuccess && s.create(hipStreamNonBlocking) == hipSuccess);
+        CHECK(Counting::released == 1 && s.create(hipStreamNonBlocking, 1) == hipSuccess && Counting::released == 2 && Counting::last_prio == 1);
+    }
+    CHECK(Counting::acquired == 3 && balanced());
     check_create_shape();
     // a typed buffer converts to its element pointer, so that arithmetic on it reads as on a raw member
     Counting::restart();
