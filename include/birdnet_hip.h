@@ -911,6 +911,48 @@ bn_status bn_subset_search_ids(bn_subset *s, const uint64_t *query_ids, size_t n
                                size_t m_stride, uint64_t *id_out, float *score_out, uint32_t *count_out);
 
 /*
+ * Copying rows between indexes: rows of one index are appended to ANOTHER index, device to device, WITH THE BITS THEY ARE STORED WITH,
+ * their validity and their tags.  An index has a fixed capacity, rows never leave it and two indexes never become one; a copy is what
+ * acts on a choice of rows (an id range, or a bn_subset made by bn_subset_select / bn_subset_from_ids): growing is a bigger index and
+ * the whole range, retention the last N rows into a fresh index, dropping tombstoned rows the subset that excludes the tombstone tag,
+ * merging several appends into one index.  Reading rows back and appending them again normalises a second time and changes bits;
+ * this does not.  The reference has nothing of the kind; this comment is the contract.
+ *
+ *   Result         the appended rows get ids *first_new_id + j, *first_new_id being dst's size before the call (first_new_id may be
+ *                  NULL) and j the position in the range or in the subset: the old id of new row j is first_id + j, or the j-th entry
+ *                  bn_subset_read gives.  No further map is returned.
+ *   Bits           bn_index_read(dst) of a new row returns the bytes bn_index_read(src) returns for its source row: nothing is
+ *                  normalised again, and the pad columns and the valid byte are copied too.  A source row stored as zeros arrives as
+ *                  zeros, counts toward bn_index_size(dst) and is never returned.  EVERYTHING THAT READS dst AFTERWARDS BEHAVES AS IF
+ *                  dst HAD BEEN BUILT BY APPENDS THAT PRODUCED EXACTLY THESE STORED BITS: every search, bn_index_assign /
+ *                  bn_index_cluster, bn_head_fit_index / bn_head_rank_index, bn_index_save, a match and attachments.
+ *   Tags           if src has a tag plane the new rows carry their source rows' tags, and dst's plane is allocated if absent.  If
+ *                  src has none the new rows' tags are 0; when dst has a plane those zeros are written, not assumed.  dst's older
+ *                  rows and their tags are untouched.
+ *   Views          the call is an append like any other: bn_ivf_extend and bn_sq8_extend pick the new rows up, subsets of dst stay
+ *                  fixed, and an attachment's snapshot behaves as it does after bn_index_add_host.  src and its views are unchanged.
+ *   Refusals       BN_ERR_INVALID_ARG with a message; nothing is appended, *first_new_id is untouched and both sizes are unchanged.
+ *                  A NULL dst, src or s (before the device is asked for); then dst == src, or a subset that borrows dst; different
+ *                  dim; different devices (rows are not copied between devices); a range that does not lie in
+ *                  [0, bn_index_size(src)]; an append past dst's capacity, refused whole as bn_index_add_host refuses it.
+ *   Empty cases    an empty range (first_id == bn_index_size(src)) or an empty subset is BN_OK: nothing is launched and
+ *                  *first_new_id is dst's size.
+ *   No device      without a gfx950 device both calls return BN_ERR_NO_DEVICE and leave *first_new_id untouched.
+ *   Ordering       the work runs on dst's stream after a pending bn_index_add_ctx of EITHER index; the call is synchronous, like
+ *                  bn_index_add_host.
+ *   Determinism    plain loads and stores, no atomics: the same state gives the same bytes.
+ *   Threading      the index's rule, for both indexes: one thread at a time per index, and neither may be in another call meanwhile.
+ *   Memory         none beyond dst's own slab, and its tag plane where the copy creates it.  Out of place by design: there is no
+ *                  compaction or truncation of an index in place (views, subsets and attachments hold ids and sizes of the index they
+ *                  borrow), so src and dst exist side by side for as long as the caller keeps both.
+ *   Not carried    IVF lists and int8 codes (rebuilt, or extended, from the copied rows), and tags in the index file.
+ */
+/* rows [first_id, first_id + n_ids) of src (n_ids == 0: to the end of src, bn_index_assign's convention) */
+bn_status bn_index_append_rows(bn_index *dst, bn_index *src, uint64_t first_id, uint64_t n_ids, uint64_t *first_new_id);
+/* the members of s, in the subset's (ascending) order, from the index s borrows */
+bn_status bn_index_append_subset(bn_index *dst, const bn_subset *s, uint64_t *first_new_id);
+
+/*
  * Event-level search: rows are appended in window order, so a row id is a position in time, and overlapping windows make neighbouring
  * rows near-duplicates: one call in the archive that matches a query fills several consecutive ranks of bn_index_search, once per window
  * that overlaps it.  exclude_radius handles this around the query's own id; bn_index_search_peaks handles it AMONG THE HITS: IT RETURNS

@@ -60,6 +60,7 @@ ENGINE_SYMBOLS = [
     "bn_sq8_build", "bn_sq8_free", "bn_sq8_rows", "bn_sq8_extend", "bn_sq8_read", "bn_sq8_search", "bn_sq8_search_ids",
     "bn_index_set_tags", "bn_index_fill_tags", "bn_index_read_tags",
     "bn_subset_select", "bn_subset_from_ids", "bn_subset_free", "bn_subset_size", "bn_subset_read", "bn_subset_search", "bn_subset_search_ids",
+    "bn_index_append_rows", "bn_index_append_subset",
     "bn_index_search_peaks", "bn_index_search_peaks_ids",
     "bn_index_search_above", "bn_index_search_above_ids",
     "bn_index_group_above", "bn_index_group_above_ids",
@@ -280,6 +281,8 @@ def _load() -> C.CDLL:
         "bn_subset_read": (i32, [vp, sz, sz, C.POINTER(C.c_uint64)]),
         "bn_subset_search": (i32, [vp, f32p, sz, sz, sz, C.POINTER(C.c_uint64), f32p, u32p]),
         "bn_subset_search_ids": (i32, [vp, C.POINTER(C.c_uint64), sz, C.c_int64, sz, sz, C.POINTER(C.c_uint64), f32p, u32p]),
+        "bn_index_append_rows": (i32, [vp, vp, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]),
+        "bn_index_append_subset": (i32, [vp, vp, C.POINTER(C.c_uint64)]),
         "bn_index_search_peaks": (i32, [vp, f32p, sz, sz, sz, sz, C.POINTER(C.c_uint64), f32p, u32p]),
         "bn_index_search_peaks_ids": (i32, [vp, C.POINTER(C.c_uint64), sz, C.c_int64, sz, sz, sz, C.POINTER(C.c_uint64), f32p, u32p]),
         "bn_index_search_above": (i32, [vp, f32p, sz, f32p, C.c_uint64, C.c_uint64, sz, sz, C.POINTER(C.c_uint64), f32p, u32p, u32p]),
@@ -1480,6 +1483,24 @@ class Index:
         if st:
             raise EngineError(st)
         return out
+
+    def append_rows(self, src: "Index", first_id: int = 0, n_ids: int = 0) -> int:
+        """bn_index_append_rows: rows [first_id, first_id + n_ids) of `src` (n_ids 0: to its end) appended with their stored bits, valid
+        bytes and tags, device to device; returns the id of the first new row."""
+        first = C.c_uint64()
+        st = lib.bn_index_append_rows(self._h, src._h, first_id, n_ids, C.byref(first))
+        if st:
+            raise EngineError(st)
+        return int(first.value)
+
+    def append_subset(self, subset: "Subset") -> int:
+        """bn_index_append_subset: the members of `subset` (of another index), in its order, appended as append_rows appends a range;
+        returns the id of the first new row.  New row j is the subset's j-th member."""
+        first = C.c_uint64()
+        st = lib.bn_index_append_subset(self._h, subset._h, C.byref(first))
+        if st:
+            raise EngineError(st)
+        return int(first.value)
 
     def save(self, path, chunk_rows: int = 0) -> None:
         """bn_index_save: the stored bits of every row to `path` (written under a temporary name, renamed when complete); chunk_rows

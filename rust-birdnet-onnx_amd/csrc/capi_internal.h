@@ -282,6 +282,34 @@ struct IndexIo {
 };
 bn_status index_io_state(bn_index *x, IndexIo *out);
 bn_status index_adopt_rows(bn_index *x, size_t n);
+// index.hip <-> index_copy.hip (bn_index_append_rows, bn_index_append_subset): both slabs of a copy of n rows of src to the end of
+// dst (dst != src, same device and dim, n >= 1).  index_copy_begin refuses an append past dst's capacity as every append does, makes the
+// device current, orders dst's stream after a pending bn_index_add_ctx of EITHER index without waiting, and gives dst a tag plane
+// (zeroed on that stream) when src has one and dst has none.  The dst pointers name the first new row.  index_copy_commit ends the
+// copy: the n rows, their valid bytes and, where dst has a plane, their tags were written by work that has completed.
+// index_copy_shape is the part of index_copy_begin that changes nothing: the capacity refusal, and what the plan of a copy needs
+struct IndexCopy {
+    int device = 0;
+    hipStream_t stream = nullptr;  // dst's
+    size_t dpad = 0, first = 0;    // first: dst's size, the id of the first new row
+    int max_wg = 0;
+    const float *src_slab = nullptr;    // [size, dpad]
+    const uint8_t *src_valid = nullptr;
+    const uint16_t *src_tags = nullptr;  // NULL: src never tagged
+    float *dst_slab = nullptr;
+    uint8_t *dst_valid = nullptr;
+    uint16_t *dst_tags = nullptr;  // NULL: neither index has a plane
+};
+bn_status index_copy_shape(const bn_index *dst, size_t n, size_t *dpad, int *max_wg);
+bn_status index_copy_begin(bn_index *dst, const bn_index *src, size_t n, IndexCopy *out);
+void index_copy_commit(bn_index *dst, size_t n);
+// subset.hip -> index_copy.hip: the index a subset borrows and its list on the device ([n] ascending ids; NULL for an empty subset)
+struct SubsetList {
+    bn_index *x = nullptr;
+    size_t n = 0;
+    const uint32_t *d_ids = nullptr;
+};
+SubsetList subset_list(const bn_subset *s);
 // index.hip <-> cluster.hip (bn_index_assign, bn_index_cluster): the clustering buffers of an index, owned by cluster.hip, NULL until
 // a call first needs them; bn_index_free hands them to cluster_state_free with the index's stream idle
 struct ClusterState;

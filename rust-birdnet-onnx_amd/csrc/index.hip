@@ -530,6 +530,44 @@ bn_status bn::index_adopt_rows(bn_index *x, size_t n) {
     return BN_OK;
 }
 
+bn_status bn::index_copy_shape(const bn_index *dst, size_t n, size_t *dpad, int *max_wg) {
+    if (!dst || !dpad || !max_wg) return set_last_error(BN_ERR_INVALID_ARG, "index_copy_shape: bad argument");
+    if (bn_status st = reserve_rows(dst, n); st != BN_OK) return st;
+    *dpad = dst->dpad;
+    *max_wg = dst->max_wg;
+    return BN_OK;
+}
+
+bn_status bn::index_copy_begin(bn_index *dst, const bn_index *src, size_t n, IndexCopy *out) {
+    if (!dst || !src || !out || dst == src || dst->dim != src->dim || dst->device != src->device)
+        return set_last_error(BN_ERR_INVALID_ARG, "index_copy_begin: bad argument");
+    bn_status st = reserve_rows(dst, n);
+    if (st != BN_OK) return st;
+    if ((st = begin(dst)) != BN_OK) return st;
+    // src's own stream is idle between calls; what may still be writing its rows is the context stream behind its event
+    if (src->pending) BN_HIP_TRY(hipStreamWaitEvent(dst->stream, src->ev, 0));
+    if (src->tags && !dst->tags) {
+        bn::DeviceBuf<uint16_t> p;
+        BN_HIP_TRY(p.alloc(dst->cap_pad * sizeof(uint16_t)));
+        BN_HIP_TRY(hipMemsetAsync(p, 0, dst->cap_pad * sizeof(uint16_t), dst->stream));  // on the stream that writes the new tags: ordered before them
+        dst->tags = std::move(p);
+    }
+    out->device = dst->device;
+    out->stream = dst->stream;
+    out->dpad = dst->dpad;
+    out->first = dst->size;
+    out->max_wg = dst->max_wg;
+    out->src_slab = src->slab;
+    out->src_valid = src->valid;
+    out->src_tags = src->tags;
+    out->dst_slab = dst->slab + dst->size * dst->dpad;
+    out->dst_valid = dst->valid + dst->size;
+    out->dst_tags = dst->tags ? dst->tags + dst->size : nullptr;
+    return BN_OK;
+}
+
+void bn::index_copy_commit(bn_index *dst, size_t n) { dst->size += n; }
+
 extern "C" {
 
 bn_status bn_index_create(int32_t device, size_t dim, size_t capacity_rows, bn_index **out) {
@@ -554,10 +592,12 @@ bn_status bn_index_create(int32_t device, size_t dim, size_t capacity_rows, bn_i
     x->max_wg = std::max(1, cus);
     BN_HIP_TRY(x->stream.create(hipStreamNonBlocking));
     BN_HIP_TRY(x->ev.create(hipEventDisableTiming));
+    // zeroed on the index's own stream and waited for below: a hipMemset of device memory may return before it has run, and nothing
+    // orders the null stream before a kernel that the first call after this one puts on a non-blocking stream
     BN_HIP_TRY(x->slab.alloc(x->cap_pad * x->dpad * sizeof(float)));
-    BN_HIP_TRY(bn::gated::Memset(x->slab, 0, x->cap_pad * x->dpad * sizeof(float)));
+    BN_HIP_TRY(hipMemsetAsync(x->slab, 0, x->cap_pad * x->dpad * sizeof(float), x->stream));
     BN_HIP_TRY(x->valid.alloc(x->cap_pad));
-    BN_HIP_TRY(bn::gated::Memset(x->valid, 0, x->cap_pad));
+    BN_HIP_TRY(hipMemsetAsync(x->valid, 0, x->cap_pad, x->stream));
     BN_HIP_TRY(x->d_stage.alloc(STAGE_ROWS * dim * sizeof(float)));
     BN_HIP_TRY(x->d_q.alloc(QCHUNK * x->dpad * sizeof(float)));
     BN_HIP_TRY(x->d_qvalid.alloc(QCHUNK));
@@ -568,6 +608,7 @@ bn_status bn_index_create(int32_t device, size_t dim, size_t capacity_rows, bn_i
     BN_HIP_TRY(x->d_count.alloc(QCHUNK * sizeof(uint32_t)));
     BN_HIP_TRY(x->h_out.alloc(QCHUNK * MMAX * sizeof(Cand)));
     BN_HIP_TRY(x->h_count.alloc(QCHUNK * sizeof(uint32_t)));
+    BN_HIP_TRY(hipStreamSynchronize(x->stream));
     *out = x.release();
     return BN_OK;
 }

@@ -345,6 +345,14 @@ bn_status make_subset(bn_index *x, int device, size_t n, std::unique_ptr<bn_subs
 
 }  // namespace
 
+bn::SubsetList bn::subset_list(const bn_subset *s) {
+    SubsetList l;
+    l.x = s->x;
+    l.n = s->n;
+    l.d_ids = s->d_ids;
+    return l;
+}
+
 extern "C" {
 
 bn_status bn_subset_select(bn_index *x, const bn_index_filter *f, size_t struct_size, bn_subset **out) {
