@@ -10,7 +10,7 @@ CXXFLAGS := -O3 -std=c++17 -fPIC -Wall -Wextra -Wno-unused-parameter -Iinclude
 # for the pairs with register moves (mbmap's depthwise phase: 120 v_pk_fma + 216 v_mov for 240 multiply-adds); on this part a packed
 # f32 instruction costs 1.56x a plain one (tools/mfma_valu_probe.cpp) and every vector instruction is paid out of the MFMA time
 HIPFLAGS := $(CXXFLAGS) --offload-arch=$(ARCH) -ffp-contract=off -fno-slp-vectorize
-OBJS := $(SRC)/onnx_proto.o $(SRC)/engine.o $(SRC)/onnx_rewrite.o $(SRC)/dft_bank.o $(SRC)/plan_passes.o $(SRC)/detect.o $(SRC)/capi.o $(SRC)/step_common.o $(SRC)/group.o $(SRC)/host_classifier.o $(SRC)/host_capi.o $(SRC)/host_rangefilter.o $(SRC)/kernels.o $(SRC)/topk.o $(SRC)/stft.o $(SRC)/mbrow.o $(SRC)/gemm_dma.o $(SRC)/gemm_dma3.o $(SRC)/gemm_b3.o $(SRC)/mbmap.o $(SRC)/mbmap_ws.o $(SRC)/index.o $(SRC)/head.o $(SRC)/rank.o $(SRC)/cluster.o $(SRC)/ivf.o $(SRC)/sq8.o $(SRC)/subset.o $(SRC)/index_copy.o $(SRC)/peaks.o $(SRC)/above.o $(SRC)/group_above.o $(SRC)/match.o $(SRC)/index_io.o $(SRC)/index_file.o $(SRC)/prior.o $(SRC)/track.o $(SRC)/live.o $(SRC)/live_kernels.o
+OBJS := $(SRC)/onnx_proto.o $(SRC)/engine.o $(SRC)/onnx_rewrite.o $(SRC)/dft_bank.o $(SRC)/plan_passes.o $(SRC)/detect.o $(SRC)/capi.o $(SRC)/step_common.o $(SRC)/group.o $(SRC)/host_classifier.o $(SRC)/host_capi.o $(SRC)/host_rangefilter.o $(SRC)/kernels.o $(SRC)/topk.o $(SRC)/stft.o $(SRC)/mbrow.o $(SRC)/gemm_dma.o $(SRC)/gemm_dma3.o $(SRC)/gemm_b3.o $(SRC)/mbmap.o $(SRC)/mbmap_ws.o $(SRC)/index.o $(SRC)/head.o $(SRC)/rank.o $(SRC)/cluster.o $(SRC)/ivf.o $(SRC)/sq8.o $(SRC)/subset.o $(SRC)/index_copy.o $(SRC)/peaks.o $(SRC)/seq.o $(SRC)/above.o $(SRC)/group_above.o $(SRC)/match.o $(SRC)/index_io.o $(SRC)/index_file.o $(SRC)/prior.o $(SRC)/track.o $(SRC)/live.o $(SRC)/live_kernels.o
 
 all: $(OUT) oracle
 
@@ -41,13 +41,15 @@ tools/gemm3_bench: tools/gemm3_bench.cpp $(OUT)
 	$(HIPCC) -O3 -std=c++17 --offload-arch=$(ARCH) -Iinclude -I$(SRC) -c tools/gemm3_bench.cpp -o /tmp/bn_gemm3_bench_main.o
 	$(HIPCC) --offload-arch=$(ARCH) /tmp/bn_gemm3_bench_main.o $(SRC)/kernels.o $(SRC)/stft.o $(SRC)/topk.o $(SRC)/mbrow.o $(SRC)/mbmap.o $(SRC)/mbmap_ws.o $(SRC)/gemm_dma.o $(SRC)/gemm_dma3.o $(SRC)/gemm_b3.o -o tools/gemm3_bench -lpthread -ldl
 
-# host-only sanitizer checks of the threshold searches' and the row copy's argument and plan arithmetic (no device)
+# host-only sanitizer checks of the threshold searches', the row copy's and the sequence search's argument and plan arithmetic (no device)
 ASAN_FLAGS := -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Iinclude -I$(SRC)
 tools/asan_above_plan: tools/asan_above_plan.cpp $(SRC)/above_plan.h $(SRC)/last_error.h
 	$(CXX) $(ASAN_FLAGS) $< -o $@
 tools/asan_group_plan: tools/asan_group_plan.cpp $(SRC)/group_plan.h $(SRC)/above_plan.h $(SRC)/last_error.h
 	$(CXX) $(ASAN_FLAGS) $< -o $@
 tools/asan_index_copy_plan: tools/asan_index_copy_plan.cpp $(SRC)/index_copy_plan.h $(SRC)/last_error.h
+	$(CXX) $(ASAN_FLAGS) $< -o $@
+tools/asan_seq_plan: tools/asan_seq_plan.cpp $(SRC)/seq_plan.h $(SRC)/last_error.h
 	$(CXX) $(ASAN_FLAGS) $< -o $@
 
 clean:

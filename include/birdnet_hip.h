@@ -1001,6 +1001,58 @@ bn_status bn_index_search_peaks_ids(bn_index *x, const uint64_t *query_ids, size
                                     size_t top_m, size_t m_stride, uint64_t *id_out, float *score_out, uint32_t *count_out);
 
 /*
+ * Sequence search: a call, a song bout or a chorus lasts longer than one window, and what a user marks in a recording is a RUN of
+ * seq_len consecutive windows.  Row ids are positions in time (see above), so the query "where in the archive does this run occur,
+ * aligned window by window" is the mean of the seq_len window scores along the diagonal, score(i) = mean_j dot(query_j, row[i + j]),
+ * for every start row i.  A returned id is the START row of a match.  Joining the top-M lists of the windows on the host is not exact
+ * (a run whose windows are each rank 300 never shows up); this is.  The reference has nothing of the kind; this comment is the contract.
+ *
+ *   Window score   s_j(r) has exactly the bits bn_index_search (bn_index_search_ids) gives the pair (query row j, index row r): the
+ *                  same k-ordered chain over the padded dim.  It does not depend on the tile, on the split among workgroups, on seq_len
+ *                  or on the number of sequences in the call.
+ *   Eligible start start i is eligible when i + seq_len <= bn_index_size, EVERY row i .. i + seq_len - 1 is valid and, for the _ids
+ *                  form, |i - first_id| > exclude_radius (< 0: none excluded; 0: only the query's own start).
+ *   Sequence score acc_0 = s_0(i); acc_j = fl32(acc_{j-1} + s_j(i + j)) for j = 1 .. seq_len - 1, in that order;
+ *                  score = fl32(acc_{seq_len-1} * inv) with inv = fl32(1.0f / (float)seq_len), computed once on the host.  No step is
+ *                  fused with another.  For seq_len == 1 the score is s_0(i) bit for bit.
+ *   Order          score descending, ties by id ascending (-0.0 == +0.0).
+ *   Peak           with peak_radius R in 1..BN_PEAK_RADIUS_MAX only peaks are returned: an eligible start i is a peak when EVERY OTHER
+ *                  eligible start j with 0 < |i - j| <= R comes AFTER i in that order: bn_index_search_peaks' rule over the sequence
+ *                  scores, NOT greedy suppression.  Ineligible starts are never peaks and never suppress a neighbour.  R == 0: every
+ *                  eligible start counts.
+ *   Result         the first top_m such starts in that order; count = min(top_m, their number); entries past count are not written.
+ *   Query          host form: each of the seq_len rows is normalised as an appended row is; a sequence with any zero-norm or
+ *                  non-finite row returns count 0.  _ids form: the query is the stored rows [first_id, first_id + seq_len), used as
+ *                  stored; an invalid row among them returns count 0.
+ *   Consequences   seq_len == 1 returns bn_index_search_peaks' bytes (the _ids form bn_index_search_peaks_ids'), and with R == 0
+ *                  bn_index_search's.  An index shorter than seq_len returns count 0.  One call with n sequences returns the bytes of n
+ *                  calls with one sequence each.  With R >= 1 two returned ids of one sequence differ by more than R.
+ *   Caveat         adjacency is BY ID ONLY, as for peaks: a match may span the point where two recordings meet in the append order.
+ *                  Tags are not read.
+ *   Limits         1 <= seq_len <= BN_SEQ_LEN_MAX, 0 <= peak_radius <= BN_PEAK_RADIUS_MAX, 1 <= top_m <= 256, m_stride >= top_m.
+ *   Refusals       BN_ERR_INVALID_ARG with a message and no output written: top_m outside 1..256, m_stride < top_m, seq_len outside
+ *                  1..BN_SEQ_LEN_MAX, peak_radius above BN_PEAK_RADIUS_MAX, NULL queries / first_ids / id_out / score_out / count_out
+ *                  with n_seq > 0, a NULL index, a first_id + seq_len above bn_index_size.
+ *   No device      without a gfx950 device both calls return BN_ERR_NO_DEVICE and leave the outputs untouched; the refusals that need
+ *                  no index (top_m, m_stride, seq_len, peak_radius, the NULLs other than the index) come before the device is asked for.
+ *   Determinism    no atomic decides anything; two calls with the same inputs give the same bytes.
+ *   Threading      the index's rule: one thread at a time per index.  The work runs on the index's stream, after a pending
+ *                  bn_index_add_ctx, in the index's own query and candidate buffers; both calls are synchronous.  The index is unchanged.
+ *   Cost           one scan of the slab per pass; a pass holds min(64 / seq_len, 28) sequences (64 query rows, and LDS for 28 lines of
+ *                  sequence scores): n_seq sequences take ceil(n_seq / that) passes.  seq_len 1 and 2 therefore take more passes than
+ *                  bn_index_search takes for as many query rows (64 x seq_len 1: three against one), and seq_len 33 to 63 leave query
+ *                  rows of the pass idle.  Measured times are in DESIGN.md.
+ *
+ * queries is a host array [n_seq * seq_len * dim], sequence after sequence, window after window.  Outputs are host arrays: id_out /
+ * score_out [n_seq * m_stride] and count_out [n_seq].
+ */
+#define BN_SEQ_LEN_MAX 64
+bn_status bn_index_search_seq(bn_index *x, const float *queries, size_t n_seq, size_t seq_len, size_t peak_radius, size_t top_m, size_t m_stride,
+                              uint64_t *id_out, float *score_out, uint32_t *count_out);
+bn_status bn_index_search_seq_ids(bn_index *x, const uint64_t *first_ids, size_t n_seq, size_t seq_len, int64_t exclude_radius, size_t peak_radius,
+                                  size_t top_m, size_t m_stride, uint64_t *id_out, float *score_out, uint32_t *count_out);
+
+/*
  * Threshold search: EVERY row of an id range that scores at least min_score against a query, in id (= time) order, and how many there
  * are.  The searches above answer "the M best rows" and stop at 256; a call rate or an occupancy count ("every window that sounds like
  * this exemplar at cosine >= 0.8", or simply how many) is this call.  The reference has nothing of the kind; this comment is the contract.

@@ -62,6 +62,7 @@ ENGINE_SYMBOLS = [
     "bn_subset_select", "bn_subset_from_ids", "bn_subset_free", "bn_subset_size", "bn_subset_read", "bn_subset_search", "bn_subset_search_ids",
     "bn_index_append_rows", "bn_index_append_subset",
     "bn_index_search_peaks", "bn_index_search_peaks_ids",
+    "bn_index_search_seq", "bn_index_search_seq_ids",
     "bn_index_search_above", "bn_index_search_above_ids",
     "bn_index_group_above", "bn_index_group_above_ids",
     "bn_head_create", "bn_head_free", "bn_head_dim", "bn_head_classes", "bn_head_flags", "bn_head_read", "bn_head_apply_host",
@@ -147,6 +148,7 @@ class BnIndexFilter(C.Structure):
 
 BN_INDEX_TAG_LIMIT = 65536  # row tags lie below it
 BN_PEAK_RADIUS_MAX = 64  # largest peak_radius of Index.search_peaks / search_peaks_ids
+BN_SEQ_LEN_MAX = 64  # largest seq_len of Index.search_seq / search_seq_ids
 BN_ABOVE_MAX_HITS = 65536  # largest max_hits of Index.search_above / search_above_ids
 BN_GROUP_NO_ROW = 0xFFFFFFFFFFFFFFFF  # the best / first / last id of a group without hits (Index.group_above / group_above_ids)
 BN_FILTER_EXCLUDE_TAGS = 1  # bn_index_filter flag: the tag list names the tags left out
@@ -285,6 +287,8 @@ def _load() -> C.CDLL:
         "bn_index_append_subset": (i32, [vp, vp, C.POINTER(C.c_uint64)]),
         "bn_index_search_peaks": (i32, [vp, f32p, sz, sz, sz, sz, C.POINTER(C.c_uint64), f32p, u32p]),
         "bn_index_search_peaks_ids": (i32, [vp, C.POINTER(C.c_uint64), sz, C.c_int64, sz, sz, sz, C.POINTER(C.c_uint64), f32p, u32p]),
+        "bn_index_search_seq": (i32, [vp, f32p, sz, sz, sz, sz, sz, C.POINTER(C.c_uint64), f32p, u32p]),
+        "bn_index_search_seq_ids": (i32, [vp, C.POINTER(C.c_uint64), sz, sz, C.c_int64, sz, sz, sz, C.POINTER(C.c_uint64), f32p, u32p]),
         "bn_index_search_above": (i32, [vp, f32p, sz, f32p, C.c_uint64, C.c_uint64, sz, sz, C.POINTER(C.c_uint64), f32p, u32p, u32p]),
         "bn_index_search_above_ids": (i32, [vp, C.POINTER(C.c_uint64), sz, C.c_int64, f32p, C.c_uint64, C.c_uint64, sz, sz, C.POINTER(C.c_uint64), f32p,
                                             u32p, u32p]),
@@ -1363,6 +1367,36 @@ class Index:
         st = lib.bn_index_search_peaks_ids(self._h, qi.ctypes.data_as(C.POINTER(C.c_uint64)), qi.shape[0], exclude_radius, peak_radius, top_m,
                                            m_stride, out_ids.ctypes.data_as(C.POINTER(C.c_uint64)), scores.ctypes.data_as(C.POINTER(C.c_float)),
                                            counts.ctypes.data_as(C.POINTER(C.c_uint32)))
+        if st:
+            raise EngineError(st)
+        return out_ids, scores, counts
+
+    def search_seq(self, queries, seq_len: int, top_m: int, peak_radius: int = 0, m_stride: Optional[int] = None):
+        """bn_index_search_seq: each query is a run of seq_len consecutive windows, host rows [n_seq * seq_len, dim]; start row i of the
+        index scores the mean of the window scores along the diagonal, mean_j dot(query_j, row[i + j]).  Returns the best top_m starts
+        per sequence (ids [n_seq, top_m] are START rows); with peak_radius >= 1 only local peaks over start ids, by search_peaks()' rule."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
+        n_seq = q.shape[0] // max(seq_len, 1)
+        if seq_len >= 1 and q.shape[0] != n_seq * seq_len:
+            raise ValueError(f"{q.shape[0]} query rows are not a whole number of sequences of {seq_len}")
+        m_stride = top_m if m_stride is None else m_stride
+        ids, scores, counts = self._outputs(n_seq, max(m_stride, 0))
+        st = lib.bn_index_search_seq(self._h, q.ctypes.data_as(C.POINTER(C.c_float)), n_seq, seq_len, peak_radius, top_m, m_stride,
+                                     ids.ctypes.data_as(C.POINTER(C.c_uint64)), scores.ctypes.data_as(C.POINTER(C.c_float)),
+                                     counts.ctypes.data_as(C.POINTER(C.c_uint32)))
+        if st:
+            raise EngineError(st)
+        return ids, scores, counts
+
+    def search_seq_ids(self, first_ids, seq_len: int, exclude_radius: int, top_m: int, peak_radius: int = 0, m_stride: Optional[int] = None):
+        """bn_index_search_seq_ids: search_seq() with the stored rows [first_ids[i], first_ids[i] + seq_len) as sequence i; starts within
+        exclude_radius of first_ids[i] are neither returned nor do they suppress a neighbour (< 0: none; 0: the query's own start)."""
+        qi = np.ascontiguousarray(first_ids, dtype=np.uint64).reshape(-1)
+        m_stride = top_m if m_stride is None else m_stride
+        out_ids, scores, counts = self._outputs(qi.shape[0], max(m_stride, 0))
+        st = lib.bn_index_search_seq_ids(self._h, qi.ctypes.data_as(C.POINTER(C.c_uint64)), qi.shape[0], seq_len, exclude_radius, peak_radius, top_m,
+                                         m_stride, out_ids.ctypes.data_as(C.POINTER(C.c_uint64)), scores.ctypes.data_as(C.POINTER(C.c_float)),
+                                         counts.ctypes.data_as(C.POINTER(C.c_uint32)))
         if st:
             raise EngineError(st)
         return out_ids, scores, counts

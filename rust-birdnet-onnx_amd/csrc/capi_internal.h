@@ -199,11 +199,12 @@ struct IndexScan {
     const uint16_t *tags = nullptr;  // [cap_pad] row tags; NULL until a tag is first set: every tag is 0
 };
 bn_status index_scan_state(bn_index *x, IndexScan *out);
-// index.hip -> subset.hip, peaks.hip, rank.hip: index_merge_kernel enqueued on `stream`: one wave per query walks the n_wg workgroups' sorted
-// lists cand[g][q][256] (lengths cand_len[g][q], IndexScan::lists lists per workgroup) into out[q][M], count[q]
+// index.hip -> subset.hip, peaks.hip, seq.hip, rank.hip: index_merge_kernel enqueued on `stream`: one wave per query walks the n_wg workgroups' sorted
+// lists cand[g][q][256] (lengths cand_len[g][q]; a workgroup's lists are ALWAYS index_scan.h's LP = 64 apart, whatever IndexScan::lists
+// says: that only sets how many lists a pass of run_scan_passes takes) into out[q][M], count[q]
 bn_status index_enqueue_merge(hipStream_t stream, const topm::Cand *cand, const int *cand_len, size_t n_queries, int n_wg, int M, topm::Cand *out,
                               uint32_t *count);
-// ---- index.hip: the host side that the searches over an index share (index, subset, peaks, rank, ivf, sq8) ----
+// ---- index.hip: the host side that the searches over an index share (index, subset, peaks, seq, rank, ivf, sq8) ----
 // The dynamic-LDS opt-in of a file's scan kernels beyond 64 KB, once per device, under the capture gate (it may not overlap a
 // capture).  One object per file, with static storage.
 struct LdsOptIn {
@@ -241,7 +242,8 @@ inline void by_blocks(int n, F &&f) {
 }
 // One round of a scan over n_lists <= out_lists staged lists with the index's own buffers, synchronous: per pass of s.lists lists
 // launch_scan(p0, np) enqueues the scan of lists [p0, p0 + np) on s.stream (n_wg workgroups, candidates into s.d_cand /
-// s.d_cand_len) and is checked as the launch `what`; `merge` (index_enqueue_merge's signature) then finishes the pass's lists
+// s.d_cand_len) and is checked as the launch `what` (seq.hip passes a copy of the state with fewer lists per pass: a list is a sequence
+// there, and a pass holds as many as fit the 64 query rows); `merge` (index_enqueue_merge's signature) then finishes the pass's lists
 // into s.d_out / s.d_count.  After the last pass both come back into s.h_out [n_lists][M] / s.h_count and the stream is waited for
 using MergeEnqueue = bn_status (*)(hipStream_t, const topm::Cand *, const int *, size_t, int, int, topm::Cand *, uint32_t *);
 bn_status run_scan_passes(const IndexScan &s, size_t n_lists, uint32_t n_wg, int M, const char *what,
@@ -249,7 +251,7 @@ bn_status run_scan_passes(const IndexScan &s, size_t n_lists, uint32_t n_wg, int
 // rows [n][M] of a round's results (h_count[i] entries each) -> the caller's arrays at stride m_stride; entries past a count stay
 void scatter_results(const topm::Cand *h_out, const uint32_t *h_count, size_t n, size_t M, size_t m_stride, uint64_t *id_out, float *score_out,
                      uint32_t *count_out);
-// index.hip -> ivf.hip, sq8.hip, subset.hip, peaks.hip (bn_ivf_search, bn_sq8_search, bn_subset_search, bn_index_search_peaks and their _ids forms): up to out_lists queries made ready in the index's own query buffers, on
+// index.hip -> ivf.hip, sq8.hip, subset.hip, peaks.hip, seq.hip (bn_ivf_search, bn_sq8_search, bn_subset_search, bn_index_search_peaks, bn_index_search_seq and their _ids forms): up to out_lists queries made ready in the index's own query buffers, on
 // its stream, exactly as bn_index_search / bn_index_search_ids prepare theirs: host rows normalised, or stored rows gathered by id
 // (ids below bn_index_size).  *d_q [n, dpad], *d_qvalid [n], *d_qid [n] (ids only) stay the index's
 bn_status index_stage_queries(bn_index *x, const float *queries, size_t n, const float **d_q, const uint8_t **d_qvalid);
