@@ -41,9 +41,12 @@ tools/gemm3_bench: tools/gemm3_bench.cpp $(OUT)
 	$(HIPCC) -O3 -std=c++17 --offload-arch=$(ARCH) -Iinclude -I$(SRC) -c tools/gemm3_bench.cpp -o /tmp/bn_gemm3_bench_main.o
 	$(HIPCC) --offload-arch=$(ARCH) /tmp/bn_gemm3_bench_main.o $(SRC)/kernels.o $(SRC)/stft.o $(SRC)/topk.o $(SRC)/mbrow.o $(SRC)/mbmap.o $(SRC)/mbmap_ws.o $(SRC)/gemm_dma.o $(SRC)/gemm_dma3.o $(SRC)/gemm_b3.o -o tools/gemm3_bench -lpthread -ldl
 
-# host-only sanitizer checks of the threshold searches', the row copy's and the sequence search's argument and plan arithmetic (no device)
+# host-only sanitizer checks of the threshold searches', the row copy's and the sequence search's argument and plan arithmetic, and of
+# the query source and round arithmetic every search over an index shares (no device)
 ASAN_FLAGS := -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Iinclude -I$(SRC)
 tools/asan_above_plan: tools/asan_above_plan.cpp $(SRC)/above_plan.h $(SRC)/last_error.h
+	$(CXX) $(ASAN_FLAGS) $< -o $@
+tools/asan_query_source: tools/asan_query_source.cpp $(SRC)/query_source.h $(SRC)/last_error.h
 	$(CXX) $(ASAN_FLAGS) $< -o $@
 tools/asan_group_plan: tools/asan_group_plan.cpp $(SRC)/group_plan.h $(SRC)/above_plan.h $(SRC)/last_error.h
 	$(CXX) $(ASAN_FLAGS) $< -o $@

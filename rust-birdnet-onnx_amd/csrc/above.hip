@@ -20,9 +20,10 @@
 // No atomics anywhere: every slot is a function of counts taken in a fixed order.  A count (max_hits == 0) runs the first two kernels
 // with a null staging pointer.
 //
-// Host side: the queries are staged by index.hip's helpers in rounds of out_lists, a round runs in passes of Plan::width queries
-// (above_plan.h: the width shrinks until staging plus results fit a fixed budget), and what comes back per pass is the counts, then
-// exactly the packed entries.  The buffers belong to the index (AboveState), allocated on first need and only ever grown.
+// Host side: index.hip's for_each_round stages the queries of either source in rounds of out_lists; a round is one
+// run_threshold_passes (shared with group.hip): the round's thresholds go up, then passes of Plan::width queries (above_plan.h: the
+// width shrinks until staging plus results fit a fixed budget), and what comes back per pass is the counts, then exactly the packed
+// entries.  The buffers belong to the index (AboveState), allocated on first need and only ever grown.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -254,16 +255,15 @@ bn_status state_of(bn_index *ix, const bn::IndexScan &x, bn::AboveState **out) {
     return BN_OK;
 }
 
-// One pass: queries [p0, p0 + np) of the staged round, np <= pl.width.  Scan, offsets, gather; the counts come back, then exactly the
-// packed entries; both into the caller's arrays at query index i0.  Synchronous
-bn_status run_pass(const bn::IndexScan &x, bn::AboveState &a, const bn::above::Plan &pl, uint32_t lo, uint32_t hi, const float *d_q, const uint8_t *d_qvalid,
-                   const uint32_t *d_qid, int64_t radius, size_t p0, int np, size_t max_hits, size_t h_stride, uint64_t *id_out, float *score_out,
-                   uint32_t *tag_out, uint32_t *count_out) {
+// One pass: the np <= pl.width queries `q` of the staged round, which are queries p0 .. of the round and i0 .. of the call.  Scan,
+// offsets, gather; the counts come back, then exactly the packed entries; both into the caller's arrays at query index i0.  Synchronous
+bn_status run_pass(const bn::IndexScan &x, bn::AboveState &a, const bn::above::Plan &pl, uint32_t lo, uint32_t hi, const bn::StagedQueries &q, size_t p0, int np,
+                   size_t i0, size_t max_hits, size_t h_stride, uint64_t *id_out, float *score_out, uint32_t *tag_out, uint32_t *count_out) {
     Cand *stage = max_hits ? a.d_stage.get() : nullptr;
     bn::by_blocks(np, [&](auto qb) {
         hipLaunchKernelGGL(above_scan_kernel<decltype(qb)::value>, dim3(pl.n_wg), dim3(256), ABOVE_LDS, x.stream, x.slab, x.valid, lo, hi, (uint32_t)x.dpad,
-                           d_q + p0 * x.dpad, d_qvalid + p0, np, d_qid ? d_qid + p0 : nullptr, d_qid ? radius : (int64_t)-1, a.d_thr + p0, pl.tile_lo,
-                           pl.tile_hi, pl.tiles_per_wg, pl.cap_wg, pl.width, stage, a.d_cnt.get());
+                           q.d_q, q.d_qvalid, np, q.d_qid, q.radius, a.d_thr + p0, pl.tile_lo, pl.tile_hi, pl.tiles_per_wg, pl.cap_wg, pl.width, stage,
+                           a.d_cnt.get());
     });
     if (bn_status st = check_launch("above scan"); st != BN_OK) return st;
     hipLaunchKernelGGL(above_offsets_kernel, dim3(1), dim3(QP), 0, x.stream, a.d_cnt, (int)pl.n_wg, np, (uint32_t)max_hits, a.d_off.get(), a.d_head.get());
@@ -287,8 +287,8 @@ bn_status run_pass(const bn::IndexScan &x, bn::AboveState &a, const bn::above::P
         BN_HIP_TRY(hipStreamSynchronize(x.stream));
     }
     for (int i = 0; i < np; i++) {
-        count_out[p0 + i] = count[i];
-        const size_t k = std::min<size_t>(count[i], max_hits), at = (p0 + i) * h_stride;
+        count_out[i0 + i] = count[i];
+        const size_t k = std::min<size_t>(count[i], max_hits), at = (i0 + i) * h_stride;
         for (size_t j = 0; j < k; j++) {
             id_out[at + j] = a.h_res[base[i] + j].id;
             score_out[at + j] = a.h_res[base[i] + j].s;
@@ -298,19 +298,16 @@ bn_status run_pass(const bn::IndexScan &x, bn::AboveState &a, const bn::above::P
     return BN_OK;
 }
 
-// by_id: the queries are the stored rows query_ids, otherwise the host rows `queries`
-bn_status search(bn_index *ix, bool by_id, const float *queries, const uint64_t *query_ids, size_t n_queries, int64_t radius, const float *min_score,
-                 uint64_t first_id, uint64_t n_ids, size_t max_hits, size_t h_stride, uint64_t *id_out, float *score_out, uint32_t *tag_out,
-                 uint32_t *count_out) {
-    bn_status st = bn::above::check_args(by_id ? (const void *)query_ids : (const void *)queries, n_queries, min_score, max_hits, h_stride, id_out, score_out,
-                                         count_out);
+bn_status search(bn_index *ix, const bn::QuerySource &src, size_t n_queries, const float *min_score, uint64_t first_id, uint64_t n_ids, size_t max_hits,
+                 size_t h_stride, uint64_t *id_out, float *score_out, uint32_t *tag_out, uint32_t *count_out) {
+    bn_status st = bn::above::check_args(src.data(), n_queries, min_score, max_hits, h_stride, id_out, score_out, count_out);
     if (st != BN_OK) return st;
     if ((st = bn::require_any_device()) != BN_OK) return st;
     if (!ix) return set_last_error(BN_ERR_INVALID_ARG, "null index");
     const size_t size = bn_index_size(ix);
     uint32_t lo = 0, hi = 0;
     if ((st = bn::above::check_range(first_id, n_ids, size, &lo, &hi)) != BN_OK) return st;
-    if (by_id && (st = bn::above::check_query_ids(query_ids, n_queries, size)) != BN_OK) return st;
+    if ((st = bn::check_query_ids(src, n_queries, size)) != BN_OK) return st;
     if (lo == hi || n_queries == 0) {  // an empty index, an empty range, no query: no launch
         std::fill(count_out, count_out + n_queries, 0u);
         return BN_OK;
@@ -330,24 +327,11 @@ bn_status search(bn_index *ix, bool by_id, const float *queries, const uint64_t 
             a->res_cap = pl.result_entries;
         }
     }
-    for (size_t q0 = 0; q0 < n_queries; q0 += x.out_lists) {
-        const size_t nq = std::min(x.out_lists, n_queries - q0);
-        const float *d_q = nullptr;
-        const uint8_t *d_qvalid = nullptr;
-        const uint32_t *d_qid = nullptr;
-        if (by_id) st = bn::index_stage_query_ids(ix, query_ids + q0, nq, &d_q, &d_qvalid, &d_qid);
-        else st = bn::index_stage_queries(ix, queries + q0 * x.dim, nq, &d_q, &d_qvalid);
-        if (st != BN_OK) return st;
-        BN_HIP_TRY(hipStreamSynchronize(x.stream));  // the last pass of the round before has read d_thr
-        BN_HIP_TRY(bn::gated::Memcpy(a->d_thr, min_score + q0, nq * sizeof(float), hipMemcpyHostToDevice));
-        for (size_t p0 = 0; p0 < nq; p0 += (size_t)pl.width) {
-            const int np = (int)std::min((size_t)pl.width, nq - p0);
-            st = run_pass(x, *a, pl, lo, hi, d_q, d_qvalid, d_qid, radius, p0, np, max_hits, h_stride, max_hits ? id_out + q0 * h_stride : nullptr,
-                          max_hits ? score_out + q0 * h_stride : nullptr, max_hits && tag_out ? tag_out + q0 * h_stride : nullptr, count_out + q0);
-            if (st != BN_OK) return st;
-        }
-    }
-    return BN_OK;
+    return bn::for_each_round(ix, src, n_queries, 1, [&](size_t q0, size_t nq, const bn::StagedQueries &staged) {
+        return bn::run_threshold_passes(x.stream, a->d_thr, min_score + q0, nq, (size_t)pl.width, [&](size_t p0, int np) {
+            return run_pass(x, *a, pl, lo, hi, staged.at(p0), p0, np, q0 + p0, max_hits, h_stride, id_out, score_out, tag_out, count_out);
+        });
+    });
 }
 
 }  // namespace
@@ -358,14 +342,14 @@ extern "C" {
 
 bn_status bn_index_search_above(bn_index *x, const float *queries, size_t n_queries, const float *min_score, uint64_t first_id, uint64_t n_ids,
                                 size_t max_hits, size_t h_stride, uint64_t *id_out, float *score_out, uint32_t *tag_out, uint32_t *count_out) {
-    return search(x, false, queries, nullptr, n_queries, -1, min_score, first_id, n_ids, max_hits, h_stride, id_out, score_out, tag_out, count_out);
+    return search(x, bn::QuerySource::host(queries), n_queries, min_score, first_id, n_ids, max_hits, h_stride, id_out, score_out, tag_out, count_out);
 }
 
 bn_status bn_index_search_above_ids(bn_index *x, const uint64_t *query_ids, size_t n_queries, int64_t exclude_radius, const float *min_score,
                                     uint64_t first_id, uint64_t n_ids, size_t max_hits, size_t h_stride, uint64_t *id_out, float *score_out,
                                     uint32_t *tag_out, uint32_t *count_out) {
-    return search(x, true, nullptr, query_ids, n_queries, exclude_radius, min_score, first_id, n_ids, max_hits, h_stride, id_out, score_out, tag_out,
-                  count_out);
+    return search(x, bn::QuerySource::stored(query_ids, exclude_radius), n_queries, min_score, first_id, n_ids, max_hits, h_stride, id_out, score_out,
+                  tag_out, count_out);
 }
 
 }  // extern "C"

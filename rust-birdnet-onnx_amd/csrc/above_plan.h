@@ -52,12 +52,6 @@ inline bn_status check_range(uint64_t first_id, uint64_t n_ids, size_t size, uin
     return BN_OK;
 }
 
-inline bn_status check_query_ids(const uint64_t *query_ids, size_t n_queries, size_t size) {
-    for (size_t i = 0; i < n_queries; i++)
-        if (query_ids[i] >= size) return set_last_error(BN_ERR_INVALID_ARG, "query id " + std::to_string(query_ids[i]) + " is not in the index");
-    return BN_OK;
-}
-
 struct Plan {
     uint32_t tile_lo = 0, tile_hi = 0;       // the 64-row tiles that cover the range
     uint32_t tiles_per_wg = 0, n_wg = 0;     // contiguous runs of tiles, at most max_wg workgroups, none empty

@@ -16,6 +16,7 @@
 #include "../../include/birdnet_hip.h"
 #include "device_mem.h"
 #include "last_error.h"
+#include "query_source.h"
 
 // a failed runtime call ends the enclosing function with BN_ERR_BACKEND and the call's text in the message
 #define BN_HIP_TRY(expr)                                                                                                   \
@@ -204,7 +205,11 @@ bn_status index_scan_state(bn_index *x, IndexScan *out);
 // says: that only sets how many lists a pass of run_scan_passes takes) into out[q][M], count[q]
 bn_status index_enqueue_merge(hipStream_t stream, const topm::Cand *cand, const int *cand_len, size_t n_queries, int n_wg, int M, topm::Cand *out,
                               uint32_t *count);
-// ---- index.hip: the host side that the searches over an index share (index, subset, peaks, seq, rank, ivf, sq8) ----
+// ---- index.hip: the host side that the searches over an index share (index, subset, peaks, seq, above, group, ivf, sq8; rank
+// all but the queries) ----
+// A search is its own refusals (the shared ones: check_top_m, check_search_buffers, query_source.h's check_query_ids), its own empty
+// case, its own state or plan, and ONE for_each_round whose function runs the round's passes (run_scan_passes, or its own pass loop
+// ending in copy_back_results; run_threshold_passes for the threshold searches) and copies out (scatter_results).
 // The dynamic-LDS opt-in of a file's scan kernels beyond 64 KB, once per device, under the capture gate (it may not overlap a
 // capture).  One object per file, with static storage.
 struct LdsOptIn {
@@ -240,22 +245,39 @@ inline void by_blocks(int n, F &&f) {
         default: f(std::integral_constant<int, 4>{}); break;
     }
 }
+// The queries of a round, made ready in the index's own query buffers on its stream: host rows normalised as appended rows are, or
+// stored rows gathered by id.  d_q [n, dpad], d_qvalid [n], d_qid [n] (NULL for host rows) stay the index's; radius is the source's
+struct StagedQueries {
+    const float *d_q = nullptr;
+    const uint8_t *d_qvalid = nullptr;
+    const uint32_t *d_qid = nullptr;
+    int64_t radius = -1;
+    size_t dpad = 0;
+    // from query row p0 on: what the launch of a pass takes
+    StagedQueries at(size_t p0) const { return {d_q + p0 * dpad, d_qvalid + p0, d_qid ? d_qid + p0 : nullptr, radius, dpad}; }
+};
+// The round loop of every search over an index (query_source.h, each_round over IndexScan::out_lists rows): the round's `count`
+// queries from `first` on (`unit` rows each; ids checked by the caller) are staged, then fn runs its passes and copies out.  The
+// staging orders the stream after a pending bn_index_add_ctx and waits for it before it overwrites a buffer the round before has read
+using RoundFn = std::function<bn_status(size_t first, size_t count, const StagedQueries &q)>;
+bn_status for_each_round(bn_index *x, const QuerySource &src, size_t n, size_t unit, const RoundFn &fn);
 // One round of a scan over n_lists <= out_lists staged lists with the index's own buffers, synchronous: per pass of s.lists lists
 // launch_scan(p0, np) enqueues the scan of lists [p0, p0 + np) on s.stream (n_wg workgroups, candidates into s.d_cand /
 // s.d_cand_len) and is checked as the launch `what` (seq.hip passes a copy of the state with fewer lists per pass: a list is a sequence
 // there, and a pass holds as many as fit the 64 query rows); `merge` (index_enqueue_merge's signature) then finishes the pass's lists
-// into s.d_out / s.d_count.  After the last pass both come back into s.h_out [n_lists][M] / s.h_count and the stream is waited for
+// into s.d_out / s.d_count.  After the last pass copy_back_results
 using MergeEnqueue = bn_status (*)(hipStream_t, const topm::Cand *, const int *, size_t, int, int, topm::Cand *, uint32_t *);
 bn_status run_scan_passes(const IndexScan &s, size_t n_lists, uint32_t n_wg, int M, const char *what,
                           const std::function<void(size_t p0, int np)> &launch_scan, MergeEnqueue merge = index_enqueue_merge);
-// rows [n][M] of a round's results (h_count[i] entries each) -> the caller's arrays at stride m_stride; entries past a count stay
-void scatter_results(const topm::Cand *h_out, const uint32_t *h_count, size_t n, size_t M, size_t m_stride, uint64_t *id_out, float *score_out,
-                     uint32_t *count_out);
-// index.hip -> ivf.hip, sq8.hip, subset.hip, peaks.hip, seq.hip (bn_ivf_search, bn_sq8_search, bn_subset_search, bn_index_search_peaks, bn_index_search_seq and their _ids forms): up to out_lists queries made ready in the index's own query buffers, on
-// its stream, exactly as bn_index_search / bn_index_search_ids prepare theirs: host rows normalised, or stored rows gathered by id
-// (ids below bn_index_size).  *d_q [n, dpad], *d_qvalid [n], *d_qid [n] (ids only) stay the index's
-bn_status index_stage_queries(bn_index *x, const float *queries, size_t n, const float **d_q, const uint8_t **d_qvalid);
-bn_status index_stage_query_ids(bn_index *x, const uint64_t *ids, size_t n, const float **d_q, const uint8_t **d_qvalid, const uint32_t **d_qid);
+// s.d_out [n][M] / s.d_count [n] into the pinned mirrors s.h_out / s.h_count; the stream is waited for
+bn_status copy_back_results(const IndexScan &s, size_t n, int M);
+// rows [n][M] of a round's results in the pinned mirrors (h_count[i] entries each) -> rows [first, first + n) of the caller's arrays
+// at stride m_stride; entries past a count stay
+void scatter_results(const IndexScan &s, size_t first, size_t n, size_t M, size_t m_stride, uint64_t *id_out, float *score_out, uint32_t *count_out);
+// A round of a threshold search (above.hip, group.hip): min_score[0 .. nq) into d_thr once the stream has run dry (the last pass of
+// the round before has read it), then pass(p0, np) for each pass of `width` queries
+bn_status run_threshold_passes(hipStream_t stream, float *d_thr, const float *min_score, size_t nq, size_t width,
+                               const std::function<bn_status(size_t p0, int np)> &pass);
 // ivf.hip -> sq8.hip (bn_sq8_search's re-rank): the gathered scan and the multi-wave merge, enqueued on `stream`.  The scan runs
 // n_queries x nprobe x segments units; unit (q, p, seg) scans tiles [seg * seg_tiles, + seg_tiles) of the list probes[q * nprobe + p]
 // (members[offsets[c] .. + counts[c]), ids of stored rows; BN_CLUSTER_NONE: no list) for query row q of `q`, with bn_index_search's

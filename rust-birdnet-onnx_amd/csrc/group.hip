@@ -21,9 +21,10 @@
 // No floating-point atomics, no scratch.  No workgroup-private LDS table as a second level: DESIGN.md ("Grouped threshold search")
 // has the measurement that decided it.
 //
-// Host side: the queries are staged by index.hip's helpers in rounds of out_lists, a round runs in passes of Plan::width queries
-// (group_plan.h), and what comes back per pass is one copy per output array the caller asked for.  The buffers belong to the index
-// (GroupState), allocated on first need and only ever grown.
+// Host side: index.hip's for_each_round stages the queries of either source in rounds of out_lists; a round is one
+// run_threshold_passes (shared with above.hip): the round's thresholds go up, then passes of Plan::width queries (group_plan.h), and
+// what comes back per pass is one copy per output array the caller asked for.  The buffers belong to the index (GroupState), allocated
+// on first need and only ever grown.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -315,7 +316,7 @@ bn_status state_of(bn_index *ix, const bn::IndexScan &x, size_t records, bn::Gro
     return BN_OK;
 }
 
-// the caller's arrays, each at the first query of the round; NULL where the caller passed NULL
+// the caller's arrays; NULL where the caller passed NULL
 struct Outputs {
     uint32_t *count;
     uint64_t *best_id;
@@ -326,18 +327,18 @@ struct Outputs {
 
 inline uint64_t wide(uint32_t id) { return id == NO_ROW ? BN_GROUP_NO_ROW : (uint64_t)id; }
 
-// One pass: queries [p0, p0 + np) of the staged round, np <= pl.width.  Scan, finish; one copy per array the caller asked for, then
-// into the caller's arrays at query index p0.  Synchronous
-bn_status run_pass(const bn::IndexScan &x, bn::GroupState &g, const bn::group::Plan &pl, uint32_t lo, uint32_t hi, const float *d_q, const uint8_t *d_qvalid,
-                   const uint32_t *d_qid, int64_t radius, size_t p0, int np, size_t n_groups, size_t g_stride, const Outputs &o) {
+// One pass: the np <= pl.width queries `q` of the staged round, which are queries p0 .. of the round and i0 .. of the call.  Scan,
+// finish; one copy per array the caller asked for, then into the caller's arrays at query index i0.  Synchronous
+bn_status run_pass(const bn::IndexScan &x, bn::GroupState &g, const bn::group::Plan &pl, uint32_t lo, uint32_t hi, const bn::StagedQueries &q, size_t p0, int np,
+                   size_t i0, size_t n_groups, size_t g_stride, const Outputs &o) {
     const size_t n = (size_t)np * n_groups;
     const Table tab = table_of(g);
     const Finished d = finished_of(g.d_out.get(), g.cap), hst = finished_of(g.h_out.get(), g.cap);
     g.dirty = true;
     bn::by_blocks(np, [&](auto qb) {
         hipLaunchKernelGGL(group_scan_kernel<decltype(qb)::value>, dim3(pl.n_wg), dim3(256), GROUP_LDS, x.stream, x.slab, x.valid, lo, hi, (uint32_t)x.dpad,
-                           d_q + p0 * x.dpad, d_qvalid + p0, np, d_qid ? d_qid + p0 : nullptr, d_qid ? radius : (int64_t)-1, g.d_thr + p0, pl.tile_lo,
-                           pl.tile_hi, pl.tiles_per_wg, x.tags, (uint32_t)n_groups, tab, g.d_head.get());
+                           q.d_q, q.d_qvalid, np, q.d_qid, q.radius, g.d_thr + p0, pl.tile_lo, pl.tile_hi, pl.tiles_per_wg, x.tags, (uint32_t)n_groups, tab,
+                           g.d_head.get());
     });
     if (bn_status st = check_launch("group scan"); st != BN_OK) return st;
     hipLaunchKernelGGL(group_finish_kernel, dim3(blocks_for(n)), dim3(256), 0, x.stream, tab, g.d_head.get(), n, d);
@@ -354,7 +355,7 @@ bn_status run_pass(const bn::IndexScan &x, bn::GroupState &g, const bn::group::P
     BN_HIP_TRY(hipStreamSynchronize(x.stream));
     g.dirty = false;
     for (int i = 0; i < np; i++) {
-        const size_t from = (size_t)i * n_groups, to = (p0 + i) * g_stride;
+        const size_t from = (size_t)i * n_groups, to = (i0 + i) * g_stride;
         std::copy(hst.count + from, hst.count + from + n_groups, o.count + to);
         if (o.best_id) {
             std::transform(hst.best_id + from, hst.best_id + from + n_groups, o.best_id + to, wide);
@@ -362,8 +363,8 @@ bn_status run_pass(const bn::IndexScan &x, bn::GroupState &g, const bn::group::P
         }
         if (o.first) std::transform(hst.first + from, hst.first + from + n_groups, o.first + to, wide);
         if (o.last) std::transform(hst.last + from, hst.last + from + n_groups, o.last + to, wide);
-        if (o.total) o.total[p0 + i] = hst.head[i];
-        if (o.other) o.other[p0 + i] = hst.head[QP + i];
+        if (o.total) o.total[i0 + i] = hst.head[i];
+        if (o.other) o.other[i0 + i] = hst.head[QP + i];
     }
     return BN_OK;
 }
@@ -384,18 +385,16 @@ void write_empty(size_t n_queries, size_t n_groups, size_t g_stride, const Outpu
     }
 }
 
-// by_id: the queries are the stored rows query_ids, otherwise the host rows `queries`
-bn_status group(bn_index *ix, bool by_id, const float *queries, const uint64_t *query_ids, size_t n_queries, int64_t radius, const float *min_score,
-                uint64_t first_id, uint64_t n_ids, size_t n_groups, size_t g_stride, const Outputs &o) {
-    bn_status st = bn::group::check_args(by_id ? (const void *)query_ids : (const void *)queries, n_queries, min_score, n_groups, g_stride, o.count, o.best_id,
-                                         o.best_score);
+bn_status group(bn_index *ix, const bn::QuerySource &src, size_t n_queries, const float *min_score, uint64_t first_id, uint64_t n_ids, size_t n_groups,
+                size_t g_stride, const Outputs &o) {
+    bn_status st = bn::group::check_args(src.data(), n_queries, min_score, n_groups, g_stride, o.count, o.best_id, o.best_score);
     if (st != BN_OK) return st;
     if ((st = bn::require_any_device()) != BN_OK) return st;
     if (!ix) return set_last_error(BN_ERR_INVALID_ARG, "null index");
     const size_t size = bn_index_size(ix);
     uint32_t lo = 0, hi = 0;
     if ((st = bn::above::check_range(first_id, n_ids, size, &lo, &hi)) != BN_OK) return st;
-    if (by_id && (st = bn::above::check_query_ids(query_ids, n_queries, size)) != BN_OK) return st;
+    if ((st = bn::check_query_ids(src, n_queries, size)) != BN_OK) return st;
     if (lo == hi || n_queries == 0) {  // an empty index, an empty range, no query: no launch
         write_empty(n_queries, n_groups, g_stride, o);
         return BN_OK;
@@ -405,29 +404,11 @@ bn_status group(bn_index *ix, bool by_id, const float *queries, const uint64_t *
     const bn::group::Plan pl = bn::group::plan(lo, hi, (size_t)x.max_wg, n_groups);
     bn::GroupState *g = nullptr;
     if ((st = state_of(ix, x, std::min<size_t>(pl.width, n_queries) * n_groups, &g)) != BN_OK) return st;  // the widest pass of this call
-    for (size_t q0 = 0; q0 < n_queries; q0 += x.out_lists) {
-        const size_t nq = std::min(x.out_lists, n_queries - q0);
-        const float *d_q = nullptr;
-        const uint8_t *d_qvalid = nullptr;
-        const uint32_t *d_qid = nullptr;
-        if (by_id) st = bn::index_stage_query_ids(ix, query_ids + q0, nq, &d_q, &d_qvalid, &d_qid);
-        else st = bn::index_stage_queries(ix, queries + q0 * x.dim, nq, &d_q, &d_qvalid);
-        if (st != BN_OK) return st;
-        BN_HIP_TRY(hipStreamSynchronize(x.stream));  // the last pass of the round before has read d_thr
-        BN_HIP_TRY(bn::gated::Memcpy(g->d_thr, min_score + q0, nq * sizeof(float), hipMemcpyHostToDevice));
-        const Outputs r{o.count + q0 * g_stride,
-                        o.best_id ? o.best_id + q0 * g_stride : nullptr,
-                        o.best_score ? o.best_score + q0 * g_stride : nullptr,
-                        o.first ? o.first + q0 * g_stride : nullptr,
-                        o.last ? o.last + q0 * g_stride : nullptr,
-                        o.other ? o.other + q0 : nullptr,
-                        o.total ? o.total + q0 : nullptr};
-        for (size_t p0 = 0; p0 < nq; p0 += (size_t)pl.width) {
-            const int np = (int)std::min((size_t)pl.width, nq - p0);
-            if ((st = run_pass(x, *g, pl, lo, hi, d_q, d_qvalid, d_qid, radius, p0, np, n_groups, g_stride, r)) != BN_OK) return st;
-        }
-    }
-    return BN_OK;
+    return bn::for_each_round(ix, src, n_queries, 1, [&](size_t q0, size_t nq, const bn::StagedQueries &staged) {
+        return bn::run_threshold_passes(x.stream, g->d_thr, min_score + q0, nq, (size_t)pl.width, [&](size_t p0, int np) {
+            return run_pass(x, *g, pl, lo, hi, staged.at(p0), p0, np, q0 + p0, n_groups, g_stride, o);
+        });
+    });
 }
 
 }  // namespace
@@ -439,14 +420,14 @@ extern "C" {
 bn_status bn_index_group_above(bn_index *x, const float *queries, size_t n_queries, const float *min_score, uint64_t first_id, uint64_t n_ids,
                                size_t n_groups, size_t g_stride, uint32_t *count_out, uint64_t *best_id_out, float *best_score_out, uint64_t *first_id_out,
                                uint64_t *last_id_out, uint32_t *other_out, uint32_t *total_out) {
-    return group(x, false, queries, nullptr, n_queries, -1, min_score, first_id, n_ids, n_groups, g_stride,
+    return group(x, bn::QuerySource::host(queries), n_queries, min_score, first_id, n_ids, n_groups, g_stride,
                  Outputs{count_out, best_id_out, best_score_out, first_id_out, last_id_out, other_out, total_out});
 }
 
 bn_status bn_index_group_above_ids(bn_index *x, const uint64_t *query_ids, size_t n_queries, int64_t exclude_radius, const float *min_score,
                                    uint64_t first_id, uint64_t n_ids, size_t n_groups, size_t g_stride, uint32_t *count_out, uint64_t *best_id_out,
                                    float *best_score_out, uint64_t *first_id_out, uint64_t *last_id_out, uint32_t *other_out, uint32_t *total_out) {
-    return group(x, true, nullptr, query_ids, n_queries, exclude_radius, min_score, first_id, n_ids, n_groups, g_stride,
+    return group(x, bn::QuerySource::stored(query_ids, exclude_radius), n_queries, min_score, first_id, n_ids, n_groups, g_stride,
                  Outputs{count_out, best_id_out, best_score_out, first_id_out, last_id_out, other_out, total_out});
 }
 

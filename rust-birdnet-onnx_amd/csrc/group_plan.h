@@ -1,6 +1,6 @@
 // The host-side arithmetic of the grouped threshold search (group.hip, bn_index_group_above and its _ids form) that needs neither a
 // device nor the runtime: the refusals of its arguments and the plan of a call -- the workgroup split of the range's tiles, which is
-// the threshold search's (above_plan.h, as are the id range and the query-id check: check_range, check_query_ids), and how many
+// the threshold search's (above_plan.h, as is the id range: check_range; the query-id check is query_source.h's), and how many
 // queries a pass takes so that the device table of (query, group) records stays within above_plan.h's budget.  Host code only, so that
 // a stand-alone program can run it under a sanitizer (tools/asan_group_plan.cpp).
 #pragma once

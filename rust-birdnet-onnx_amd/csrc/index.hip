@@ -19,8 +19,9 @@
 // and sq8.hip through index_scan_state, cluster.hip through index_cluster_state, above.hip through both index_scan_state and
 // index_above_state, group.hip likewise through index_group_state.  The host side those searches share is defined
 // here once (declared in capi_internal.h): the LDS opt-in (LdsOptIn), the argument refusals (check_top_m, check_search_buffers),
-// the pass loop with its merge and copy-back (run_scan_passes, index_enqueue_merge) and the copy into the caller's arrays
-// (scatter_results); subset.hip also reads the tag plane below.
+// the round loop that stages a round's queries from either source (for_each_round over query_source.h's QuerySource), the pass loop
+// with its merge and copy-back (run_scan_passes, index_enqueue_merge, copy_back_results), the threshold searches' round
+// (run_threshold_passes) and the copy into the caller's arrays (scatter_results); subset.hip also reads the tag plane below.
 //
 // Row tags (bn_index_set_tags / fill_tags / read_tags): one u16 per row of capacity, allocated zeroed by the first call that sets one.
 // No kernel of this file reads it.
@@ -324,40 +325,53 @@ bn::IndexScan scan_state_of(const bn_index *x) {
     return s;
 }
 
-// the scan + merge passes over d_q[0 .. nq) (nq <= QCHUNK, the index not empty), results into the pinned mirrors; synchronous
-bn_status run_search(bn_index *x, size_t nq, bool by_id, int64_t radius, int M) {
-    const uint32_t n_rows = (uint32_t)x->size;
-    const bn::WgSplit sp = bn::split_tiles((n_rows + TILE - 1) / TILE, x->max_wg);
-    return bn::run_scan_passes(scan_state_of(x), nq, sp.n_wg, M, "index scan", [&](size_t p0, int np) {
-        bn::by_blocks(np, [&](auto qb) {
-            hipLaunchKernelGGL(index_scan_kernel<decltype(qb)::value>, dim3(sp.n_wg), dim3(256), SCAN_LDS, x->stream, x->slab, x->valid, n_rows,
-                               (uint32_t)x->dpad, x->d_q + p0 * x->dpad, x->d_qvalid + p0, np, by_id ? x->d_qid + p0 : nullptr,
-                               by_id ? radius : (int64_t)-1, M, sp.tiles_per_wg, x->d_cand, x->d_cand_len);
-        });
-    });
-}
-
-// host queries [nq, dim] (nq <= QCHUNK) -> d_q / d_qvalid, normalised as appended rows are
-bn_status stage_host_queries(bn_index *x, const float *queries, size_t nq) {
-    for (size_t s0 = 0; s0 < nq; s0 += STAGE_ROWS) {
-        const size_t k = std::min(STAGE_ROWS, nq - s0);
+// The round's nq queries of `unit` rows from query `first` on (nq * unit <= QCHUNK, every id in the index) -> d_q / d_qvalid, and
+// d_qid for stored rows.  Host rows are normalised as appended rows are; a stored id stands for the `unit` rows from it on, gathered
+// as they are.  Every copy waits for the stream first: the round before has read the buffer it overwrites
+bn_status stage(bn_index *x, const bn::QuerySource &src, size_t first, size_t nq, size_t unit, bn::StagedQueries *out) {
+    const size_t rows = nq * unit;
+    if (src.ids) {
+        std::vector<uint32_t> ids(rows);
+        for (size_t i = 0; i < nq; i++)
+            for (size_t j = 0; j < unit; j++) ids[i * unit + j] = (uint32_t)(src.ids[first + i] + j);
         BN_HIP_TRY(hipStreamSynchronize(x->stream));
-        BN_HIP_TRY(bn::gated::Memcpy(x->d_stage, queries + s0 * x->dim, k * x->dim * sizeof(float), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(index_normalise_kernel, dim3((unsigned)((k + 3) / 4)), dim3(256), 0, x->stream, x->d_stage, x->dim, (uint32_t)k,
-                           (uint32_t)x->dim, x->d_q + s0 * x->dpad, (uint32_t)x->dpad, x->d_qvalid + s0);
-        if (bn_status st = check_launch("index normalise"); st != BN_OK) return st;
+        BN_HIP_TRY(bn::gated::Memcpy(x->d_qid, ids.data(), rows * sizeof(uint32_t), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(index_gather_kernel, dim3((unsigned)rows), dim3(256), 0, x->stream, x->slab, x->valid, x->d_qid, (uint32_t)x->dpad, x->d_q,
+                           x->d_qvalid);
+        if (bn_status st = check_launch("index gather"); st != BN_OK) return st;
+    } else {
+        for (size_t s0 = 0; s0 < rows; s0 += STAGE_ROWS) {
+            const size_t k = std::min(STAGE_ROWS, rows - s0);
+            BN_HIP_TRY(hipStreamSynchronize(x->stream));
+            BN_HIP_TRY(bn::gated::Memcpy(x->d_stage, src.rows + (first * unit + s0) * x->dim, k * x->dim * sizeof(float), hipMemcpyHostToDevice));
+            hipLaunchKernelGGL(index_normalise_kernel, dim3((unsigned)((k + 3) / 4)), dim3(256), 0, x->stream, x->d_stage, x->dim, (uint32_t)k,
+                               (uint32_t)x->dim, x->d_q + s0 * x->dpad, (uint32_t)x->dpad, x->d_qvalid + s0);
+            if (bn_status st = check_launch("index normalise"); st != BN_OK) return st;
+        }
     }
+    *out = {x->d_q, x->d_qvalid, src.ids ? x->d_qid.get() : nullptr, src.radius, x->dpad};
     return BN_OK;
 }
 
-// stored rows query_ids[0 .. nq) (nq <= QCHUNK, every id in the index) -> d_qid, d_q / d_qvalid
-bn_status stage_id_queries(bn_index *x, const uint64_t *query_ids, size_t nq) {
-    const std::vector<uint32_t> ids(query_ids, query_ids + nq);
-    BN_HIP_TRY(hipStreamSynchronize(x->stream));
-    BN_HIP_TRY(bn::gated::Memcpy(x->d_qid, ids.data(), nq * sizeof(uint32_t), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(index_gather_kernel, dim3((unsigned)nq), dim3(256), 0, x->stream, x->slab, x->valid, x->d_qid, (uint32_t)x->dpad, x->d_q,
-                       x->d_qvalid);
-    return check_launch("index gather");
+// bn_index_search and bn_index_search_ids behind their refusals (the index not empty): per round the scan + merge passes over the
+// staged queries, results through the pinned mirrors into the caller's arrays
+bn_status search_rounds(bn_index *x, const bn::QuerySource &src, size_t n_queries, size_t top_m, size_t m_stride, uint64_t *id_out, float *score_out,
+                        uint32_t *count_out) {
+    const uint32_t n_rows = (uint32_t)x->size;
+    const int M = (int)top_m;
+    const bn::WgSplit sp = bn::split_tiles((n_rows + TILE - 1) / TILE, x->max_wg);
+    return bn::for_each_round(x, src, n_queries, 1, [&](size_t q0, size_t nq, const bn::StagedQueries &staged) -> bn_status {
+        const bn::IndexScan s = scan_state_of(x);
+        bn_status st = bn::run_scan_passes(s, nq, sp.n_wg, M, "index scan", [&](size_t p0, int np) {
+            const bn::StagedQueries q = staged.at(p0);
+            bn::by_blocks(np, [&](auto qb) {
+                hipLaunchKernelGGL(index_scan_kernel<decltype(qb)::value>, dim3(sp.n_wg), dim3(256), SCAN_LDS, x->stream, x->slab, x->valid, n_rows,
+                                   (uint32_t)x->dpad, q.d_q, q.d_qvalid, np, q.d_qid, q.radius, M, sp.tiles_per_wg, x->d_cand, x->d_cand_len);
+            });
+        });
+        if (st == BN_OK) bn::scatter_results(s, q0, nq, top_m, m_stride, id_out, score_out, count_out);
+        return st;
+    });
 }
 
 // the refusals of the tag calls that write; then the plane, zeroed, if this is the first of them
@@ -407,25 +421,14 @@ bn_status bn::index_rows(bn_index *x, IndexRows *out) {
     return BN_OK;
 }
 
-bn_status bn::index_stage_queries(bn_index *x, const float *queries, size_t n, const float **d_q, const uint8_t **d_qvalid) {
-    if (!x || !queries || n > QCHUNK) return set_last_error(BN_ERR_INVALID_ARG, "index_stage_queries: bad argument");
-    bn_status st = begin(x);
-    if (st != BN_OK) return st;
-    if ((st = stage_host_queries(x, queries, n)) != BN_OK) return st;
-    *d_q = x->d_q;
-    *d_qvalid = x->d_qvalid;
-    return BN_OK;
-}
-
-bn_status bn::index_stage_query_ids(bn_index *x, const uint64_t *ids, size_t n, const float **d_q, const uint8_t **d_qvalid, const uint32_t **d_qid) {
-    if (!x || !ids || n > QCHUNK) return set_last_error(BN_ERR_INVALID_ARG, "index_stage_query_ids: bad argument");
-    bn_status st = begin(x);
-    if (st != BN_OK) return st;
-    if ((st = stage_id_queries(x, ids, n)) != BN_OK) return st;
-    *d_q = x->d_q;
-    *d_qvalid = x->d_qvalid;
-    *d_qid = x->d_qid;
-    return BN_OK;
+bn_status bn::for_each_round(bn_index *x, const QuerySource &src, size_t n, size_t unit, const RoundFn &fn) {
+    if (!x || (n && !src.data())) return set_last_error(BN_ERR_INVALID_ARG, "for_each_round: bad argument");
+    return each_round(n, QCHUNK, unit, [&](size_t first, size_t count) -> bn_status {
+        StagedQueries q;
+        bn_status st = begin(x);
+        if (st == BN_OK) st = stage(x, src, first, count, unit, &q);
+        return st == BN_OK ? fn(first, count, q) : st;
+    });
 }
 
 bn::ClusterState **bn::index_cluster_state(bn_index *x) { return &x->cluster; }
@@ -491,22 +494,35 @@ bn_status bn::run_scan_passes(const IndexScan &s, size_t n_lists, uint32_t n_wg,
         if (st != BN_OK) return st;
         if ((st = merge(s.stream, s.d_cand, s.d_cand_len, (size_t)np, (int)n_wg, M, s.d_out + p0 * M, s.d_count + p0)) != BN_OK) return st;
     }
-    BN_HIP_TRY(hipMemcpyAsync(s.h_out, s.d_out, n_lists * M * sizeof(Cand), hipMemcpyDeviceToHost, s.stream));
-    BN_HIP_TRY(hipMemcpyAsync(s.h_count, s.d_count, n_lists * sizeof(uint32_t), hipMemcpyDeviceToHost, s.stream));
+    return copy_back_results(s, n_lists, M);
+}
+
+bn_status bn::copy_back_results(const IndexScan &s, size_t n, int M) {
+    BN_HIP_TRY(hipMemcpyAsync(s.h_out, s.d_out, n * M * sizeof(Cand), hipMemcpyDeviceToHost, s.stream));
+    BN_HIP_TRY(hipMemcpyAsync(s.h_count, s.d_count, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s.stream));
     BN_HIP_TRY(hipStreamSynchronize(s.stream));
     return BN_OK;
 }
 
-void bn::scatter_results(const topm::Cand *h_out, const uint32_t *h_count, size_t n, size_t M, size_t m_stride, uint64_t *id_out, float *score_out,
-                         uint32_t *count_out) {
+void bn::scatter_results(const IndexScan &s, size_t first, size_t n, size_t M, size_t m_stride, uint64_t *id_out, float *score_out, uint32_t *count_out) {
     for (size_t i = 0; i < n; i++) {
-        const uint32_t c = h_count[i];
-        count_out[i] = c;
+        const uint32_t c = s.h_count[i];
+        const size_t at = (first + i) * m_stride;
+        count_out[first + i] = c;
         for (uint32_t j = 0; j < c; j++) {
-            id_out[i * m_stride + j] = h_out[i * M + j].id;
-            score_out[i * m_stride + j] = h_out[i * M + j].s;
+            id_out[at + j] = s.h_out[i * M + j].id;
+            score_out[at + j] = s.h_out[i * M + j].s;
         }
     }
+}
+
+bn_status bn::run_threshold_passes(hipStream_t stream, float *d_thr, const float *min_score, size_t nq, size_t width,
+                                   const std::function<bn_status(size_t p0, int np)> &pass) {
+    BN_HIP_TRY(hipStreamSynchronize(stream));  // the last pass of the round before has read d_thr
+    BN_HIP_TRY(bn::gated::Memcpy(d_thr, min_score, nq * sizeof(float), hipMemcpyHostToDevice));
+    for (size_t p0 = 0; p0 < nq; p0 += width)
+        if (bn_status st = pass(p0, (int)std::min(width, nq - p0)); st != BN_OK) return st;
+    return BN_OK;
 }
 
 bn_status bn::index_io_state(bn_index *x, IndexIo *out) {
@@ -721,34 +737,20 @@ bn_status bn_index_search(bn_index *x, const float *queries, size_t n_queries, s
                           uint32_t *count_out) {
     bn_status st = check_search_args(x, queries, n_queries, top_m, m_stride, id_out, score_out, count_out);
     if (st != BN_OK) return st;
-    if ((st = begin(x)) != BN_OK) return st;
-    for (size_t q0 = 0; q0 < n_queries; q0 += QCHUNK) {
-        const size_t nq = std::min(QCHUNK, n_queries - q0);
-        if (x->size == 0) {
-            std::fill(count_out + q0, count_out + q0 + nq, 0u);
-            continue;
-        }
-        if ((st = stage_host_queries(x, queries + q0 * x->dim, nq)) != BN_OK) return st;
-        if ((st = run_search(x, nq, false, -1, (int)top_m)) != BN_OK) return st;
-        bn::scatter_results(x->h_out, x->h_count, nq, top_m, m_stride, id_out + q0 * m_stride, score_out + q0 * m_stride, count_out + q0);
+    if (x->size == 0) {  // no launch
+        std::fill(count_out, count_out + n_queries, 0u);
+        return BN_OK;
     }
-    return BN_OK;
+    return search_rounds(x, bn::QuerySource::host(queries), n_queries, top_m, m_stride, id_out, score_out, count_out);
 }
 
 bn_status bn_index_search_ids(bn_index *x, const uint64_t *query_ids, size_t n_queries, int64_t exclude_radius, size_t top_m, size_t m_stride,
                               uint64_t *id_out, float *score_out, uint32_t *count_out) {
     bn_status st = check_search_args(x, query_ids, n_queries, top_m, m_stride, id_out, score_out, count_out);
     if (st != BN_OK) return st;
-    for (size_t i = 0; i < n_queries; i++)
-        if (query_ids[i] >= x->size) return set_last_error(BN_ERR_INVALID_ARG, "query id " + std::to_string(query_ids[i]) + " is not in the index");
-    if ((st = begin(x)) != BN_OK) return st;
-    for (size_t q0 = 0; q0 < n_queries; q0 += QCHUNK) {
-        const size_t nq = std::min(QCHUNK, n_queries - q0);
-        if ((st = stage_id_queries(x, query_ids + q0, nq)) != BN_OK) return st;
-        if ((st = run_search(x, nq, true, exclude_radius, (int)top_m)) != BN_OK) return st;
-        bn::scatter_results(x->h_out, x->h_count, nq, top_m, m_stride, id_out + q0 * m_stride, score_out + q0 * m_stride, count_out + q0);
-    }
-    return BN_OK;
+    const bn::QuerySource src = bn::QuerySource::stored(query_ids, exclude_radius);
+    if ((st = bn::check_query_ids(src, n_queries, x->size)) != BN_OK) return st;
+    return search_rounds(x, src, n_queries, top_m, m_stride, id_out, score_out, count_out);
 }
 
 }  // extern "C"

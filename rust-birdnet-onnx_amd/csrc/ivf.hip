@@ -381,13 +381,13 @@ bn_status bn::ivf_enqueue_merge(hipStream_t stream, const topm::Cand *cand, cons
 namespace {
 
 // probe, scan and merge for the nq staged queries (nq <= out_lists); results into the index's pinned mirrors; synchronous
-bn_status run_search(bn_ivf *v, const bn::IndexScan &s, size_t nq, const float *d_q, const uint8_t *d_qvalid, const uint32_t *d_qid, int64_t radius,
-                     size_t nprobe, int M) {
+bn_status run_search(bn_ivf *v, const bn::IndexScan &s, size_t nq, const bn::StagedQueries &staged, size_t nprobe, int M) {
     const uint32_t k = (uint32_t)v->k, dpad = (uint32_t)v->dpad, np32 = (uint32_t)nprobe;
     const uint32_t *d_counts = v->d_small, *d_offsets = v->d_small + k;
-    hipLaunchKernelGGL(ivf_probe_score_kernel, dim3((k + 63) / 64, (unsigned)((nq + 15) / 16)), dim3(256), 0, s.stream, d_q, (uint32_t)nq, v->ab.d_cent, k, dpad,
-                       v->d_pscore);
-    hipLaunchKernelGGL(ivf_probe_select_kernel, dim3((unsigned)nq), dim3(256), 0, s.stream, v->d_pscore, d_qvalid, k, np32, d_counts, v->d_probes, v->d_scanned);
+    hipLaunchKernelGGL(ivf_probe_score_kernel, dim3((k + 63) / 64, (unsigned)((nq + 15) / 16)), dim3(256), 0, s.stream, staged.d_q, (uint32_t)nq, v->ab.d_cent, k,
+                       dpad, v->d_pscore);
+    hipLaunchKernelGGL(ivf_probe_select_kernel, dim3((unsigned)nq), dim3(256), 0, s.stream, v->d_pscore, staged.d_qvalid, k, np32, d_counts, v->d_probes,
+                       v->d_scanned);
     bn_status st = check_launch("ivf probe");
     if (st != BN_OK) return st;
     // The split: every (query, probe slot) gets the same number of segments, sized for the largest list, since which lists are probed
@@ -402,12 +402,13 @@ bn_status run_search(bn_ivf *v, const bn::IndexScan &s, size_t nq, const float *
     const size_t q_pass = UNIT_MAX / per_query;
     for (size_t p0 = 0; p0 < nq; p0 += q_pass) {
         const size_t n = std::min(q_pass, nq - p0);
+        const bn::StagedQueries q = staged.at(p0);
         bn::IvfGather g;
         g.slab = s.slab;
         g.dpad = dpad;
-        g.q = d_q + p0 * v->dpad;
-        g.qid = d_qid ? d_qid + p0 : nullptr;
-        g.radius = d_qid ? radius : (int64_t)-1;
+        g.q = q.d_q;
+        g.qid = q.d_qid;
+        g.radius = q.radius;
         g.probes = v->d_probes + p0 * nprobe;
         g.nprobe = np32;
         g.counts = d_counts;
@@ -418,40 +419,27 @@ bn_status run_search(bn_ivf *v, const bn::IndexScan &s, size_t nq, const float *
         if ((st = bn::ivf_enqueue_scan(s.stream, g, n, M, v->d_cand, v->d_cand_len)) != BN_OK) return st;
         if ((st = bn::ivf_enqueue_merge(s.stream, v->d_cand, v->d_cand_len, n, per_query, M, s.d_out + p0 * M, s.d_count + p0)) != BN_OK) return st;
     }
-    BN_HIP_TRY(hipMemcpyAsync(s.h_out, s.d_out, nq * M * sizeof(Cand), hipMemcpyDeviceToHost, s.stream));
-    BN_HIP_TRY(hipMemcpyAsync(s.h_count, s.d_count, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, s.stream));
-    BN_HIP_TRY(hipStreamSynchronize(s.stream));
-    return BN_OK;
+    return bn::copy_back_results(s, nq, M);
 }
 
-bn_status search(bn_ivf *v, const float *queries, const uint64_t *query_ids, size_t n_queries, int64_t radius, size_t nprobe, size_t top_m, size_t m_stride,
-                 uint64_t *id_out, float *score_out, uint32_t *count_out, uint32_t *probes_out, uint64_t *scanned_out) {
+bn_status search(bn_ivf *v, const bn::QuerySource &src, size_t n_queries, size_t nprobe, size_t top_m, size_t m_stride, uint64_t *id_out, float *score_out,
+                 uint32_t *count_out, uint32_t *probes_out, uint64_t *scanned_out) {
     bn_status st = bn::check_top_m(top_m, m_stride);
     if (st != BN_OK) return st;
-    if ((st = bn::check_search_buffers(queries ? (const void *)queries : (const void *)query_ids, n_queries, id_out, score_out, count_out)) != BN_OK) return st;
+    if ((st = bn::check_search_buffers(src.data(), n_queries, id_out, score_out, count_out)) != BN_OK) return st;
     if ((st = bn::require_any_device()) != BN_OK) return st;
     if (!v) return set_last_error(BN_ERR_INVALID_ARG, "null view");
     if (nprobe < 1 || nprobe > v->k) return set_last_error(BN_ERR_INVALID_ARG, "nprobe must be in 1.." + std::to_string(v->k) + ", got " + std::to_string(nprobe));
-    if (query_ids)
-        for (size_t i = 0; i < n_queries; i++)
-            if (query_ids[i] >= v->covered)
-                return set_last_error(BN_ERR_INVALID_ARG, "query id " + std::to_string(query_ids[i]) + " is not among the view's " + std::to_string(v->covered) + " rows");
+    if ((st = bn::check_query_ids(src, n_queries, v->covered, bn::IdLimit::VIEW)) != BN_OK) return st;
     bn::IndexScan s;
     if ((st = bn::index_scan_state(v->x, &s)) != BN_OK) return st;
-    for (size_t q0 = 0; q0 < n_queries; q0 += v->out_lists) {
-        const size_t nq = std::min(v->out_lists, n_queries - q0);
-        const float *d_q = nullptr;
-        const uint8_t *d_qvalid = nullptr;
-        const uint32_t *d_qid = nullptr;
-        if (query_ids) st = bn::index_stage_query_ids(v->x, query_ids + q0, nq, &d_q, &d_qvalid, &d_qid);
-        else st = bn::index_stage_queries(v->x, queries + q0 * v->dim, nq, &d_q, &d_qvalid);
-        if (st != BN_OK) return st;
-        if ((st = run_search(v, s, nq, d_q, d_qvalid, d_qid, radius, nprobe, (int)top_m)) != BN_OK) return st;
-        bn::scatter_results(s.h_out, s.h_count, nq, top_m, m_stride, id_out + q0 * m_stride, score_out + q0 * m_stride, count_out + q0);
+    return bn::for_each_round(v->x, src, n_queries, 1, [&](size_t q0, size_t nq, const bn::StagedQueries &staged) -> bn_status {
+        if (bn_status rs = run_search(v, s, nq, staged, nprobe, (int)top_m); rs != BN_OK) return rs;
+        bn::scatter_results(s, q0, nq, top_m, m_stride, id_out, score_out, count_out);
         if (probes_out) BN_HIP_TRY(bn::gated::Memcpy(probes_out + q0 * nprobe, v->d_probes, nq * nprobe * sizeof(uint32_t), hipMemcpyDeviceToHost));
         if (scanned_out) BN_HIP_TRY(bn::gated::Memcpy(scanned_out + q0, v->d_scanned, nq * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    }
-    return BN_OK;
+        return BN_OK;
+    });
 }
 
 }  // namespace
@@ -536,13 +524,14 @@ bn_status bn_ivf_read_list(const bn_ivf *v, size_t list, uint64_t *ids_out, size
 bn_status bn_ivf_search(bn_ivf *v, const float *queries, size_t n_queries, size_t nprobe, size_t top_m, size_t m_stride, uint64_t *id_out, float *score_out,
                         uint32_t *count_out, uint32_t *probes_out, uint64_t *scanned_out) {
     if (n_queries && !queries) return set_last_error(BN_ERR_INVALID_ARG, "null argument");
-    return search(v, queries, nullptr, n_queries, -1, nprobe, top_m, m_stride, id_out, score_out, count_out, probes_out, scanned_out);
+    return search(v, bn::QuerySource::host(queries), n_queries, nprobe, top_m, m_stride, id_out, score_out, count_out, probes_out, scanned_out);
 }
 
 bn_status bn_ivf_search_ids(bn_ivf *v, const uint64_t *query_ids, size_t n_queries, int64_t exclude_radius, size_t nprobe, size_t top_m, size_t m_stride,
                             uint64_t *id_out, float *score_out, uint32_t *count_out, uint32_t *probes_out, uint64_t *scanned_out) {
     if (n_queries && !query_ids) return set_last_error(BN_ERR_INVALID_ARG, "null argument");
-    return search(v, nullptr, query_ids, n_queries, exclude_radius, nprobe, top_m, m_stride, id_out, score_out, count_out, probes_out, scanned_out);
+    return search(v, bn::QuerySource::stored(query_ids, exclude_radius), n_queries, nprobe, top_m, m_stride, id_out, score_out, count_out, probes_out,
+                  scanned_out);
 }
 
 }  // extern "C"

@@ -243,35 +243,20 @@ bn_status check_args(const void *queries, size_t n_queries, size_t peak_radius, 
     return bn::check_search_buffers(queries, n_queries, id_out, score_out, count_out);
 }
 
-// the scan + merge passes over the nq staged queries (nq <= out_lists, the index not empty), results into the index's pinned mirrors;
-// synchronous.  The tiles are split among the workgroups as bn_index_search splits them: the result does not depend on the split, and
-// the two halo tiles cost the least time where a workgroup's run is shortest
-bn_status run_search(const bn::IndexScan &x, size_t nq, const float *d_q, const uint8_t *d_qvalid, const uint32_t *d_qid, int64_t radius, int R, int M) {
-    const bn::WgSplit sp = bn::split_tiles((uint32_t)((x.size + TILE - 1) / TILE), x.max_wg);
-    return bn::run_scan_passes(x, nq, sp.n_wg, M, "peaks scan", [&](size_t p0, int np) {
-        bn::by_blocks(np, [&](auto qb) {
-            hipLaunchKernelGGL(peaks_scan_kernel<decltype(qb)::value>, dim3(sp.n_wg), dim3(256), PEAKS_LDS, x.stream, x.slab, x.valid, (uint32_t)x.size,
-                               (uint32_t)x.dpad, d_q + p0 * x.dpad, d_qvalid + p0, np, d_qid ? d_qid + p0 : nullptr, d_qid ? radius : (int64_t)-1, R, M,
-                               sp.tiles_per_wg, x.d_cand, x.d_cand_len);
-        });
-    });
-}
-
-// by_id: the queries are the stored rows query_ids, otherwise the host rows `queries`
-bn_status search(bn_index *ix, bool by_id, const float *queries, const uint64_t *query_ids, size_t n_queries, int64_t radius, size_t peak_radius,
-                 size_t top_m, size_t m_stride, uint64_t *id_out, float *score_out, uint32_t *count_out) {
-    bn_status st = check_args(by_id ? (const void *)query_ids : (const void *)queries, n_queries, peak_radius, top_m, m_stride, id_out, score_out, count_out);
+// Per round the scan + merge passes over the staged queries, results through the index's pinned mirrors.  The tiles are split among
+// the workgroups as bn_index_search splits them: the result does not depend on the split, and the two halo tiles cost the least time
+// where a workgroup's run is shortest
+bn_status search(bn_index *ix, const bn::QuerySource &src, size_t n_queries, size_t peak_radius, size_t top_m, size_t m_stride, uint64_t *id_out,
+                 float *score_out, uint32_t *count_out) {
+    bn_status st = check_args(src.data(), n_queries, peak_radius, top_m, m_stride, id_out, score_out, count_out);
     if (st != BN_OK) return st;
     if ((st = bn::require_any_device()) != BN_OK) return st;
     if (!ix) return set_last_error(BN_ERR_INVALID_ARG, "null index");
     if (peak_radius == 0)  // every eligible row is a peak: the exact search itself
-        return by_id ? bn_index_search_ids(ix, query_ids, n_queries, radius, top_m, m_stride, id_out, score_out, count_out)
-                         : bn_index_search(ix, queries, n_queries, top_m, m_stride, id_out, score_out, count_out);
-    const size_t size = bn_index_size(ix);
-    if (by_id)
-        for (size_t i = 0; i < n_queries; i++)
-            if (query_ids[i] >= size) return set_last_error(BN_ERR_INVALID_ARG, "query id " + std::to_string(query_ids[i]) + " is not in the index");
-    if (size == 0) {  // no launch
+        return src.ids ? bn_index_search_ids(ix, src.ids, n_queries, src.radius, top_m, m_stride, id_out, score_out, count_out)
+                       : bn_index_search(ix, src.rows, n_queries, top_m, m_stride, id_out, score_out, count_out);
+    if ((st = bn::check_query_ids(src, n_queries, bn_index_size(ix))) != BN_OK) return st;
+    if (bn_index_size(ix) == 0) {  // no launch
         std::fill(count_out, count_out + n_queries, 0u);
         return BN_OK;
     }
@@ -279,18 +264,19 @@ bn_status search(bn_index *ix, bool by_id, const float *queries, const uint64_t 
     if ((st = bn::index_scan_state(ix, &x)) != BN_OK) return st;
     BN_HIP_TRY(g_scan_lds.prepare(x.device, {{(const void *)peaks_scan_kernel<1>, PEAKS_LDS}, {(const void *)peaks_scan_kernel<2>, PEAKS_LDS},
                                               {(const void *)peaks_scan_kernel<3>, PEAKS_LDS}, {(const void *)peaks_scan_kernel<4>, PEAKS_LDS}}));
-    for (size_t q0 = 0; q0 < n_queries; q0 += x.out_lists) {
-        const size_t nq = std::min(x.out_lists, n_queries - q0);
-        const float *d_q = nullptr;
-        const uint8_t *d_qvalid = nullptr;
-        const uint32_t *d_qid = nullptr;
-        if (by_id) st = bn::index_stage_query_ids(ix, query_ids + q0, nq, &d_q, &d_qvalid, &d_qid);
-        else st = bn::index_stage_queries(ix, queries + q0 * x.dim, nq, &d_q, &d_qvalid);
-        if (st != BN_OK) return st;
-        if ((st = run_search(x, nq, d_q, d_qvalid, d_qid, radius, (int)peak_radius, (int)top_m)) != BN_OK) return st;
-        bn::scatter_results(x.h_out, x.h_count, nq, top_m, m_stride, id_out + q0 * m_stride, score_out + q0 * m_stride, count_out + q0);
-    }
-    return BN_OK;
+    const int R = (int)peak_radius, M = (int)top_m;
+    const bn::WgSplit sp = bn::split_tiles((uint32_t)((x.size + TILE - 1) / TILE), x.max_wg);
+    return bn::for_each_round(ix, src, n_queries, 1, [&](size_t q0, size_t nq, const bn::StagedQueries &staged) -> bn_status {
+        bn_status rs = bn::run_scan_passes(x, nq, sp.n_wg, M, "peaks scan", [&](size_t p0, int np) {
+            const bn::StagedQueries q = staged.at(p0);
+            bn::by_blocks(np, [&](auto qb) {
+                hipLaunchKernelGGL(peaks_scan_kernel<decltype(qb)::value>, dim3(sp.n_wg), dim3(256), PEAKS_LDS, x.stream, x.slab, x.valid, (uint32_t)x.size,
+                                   (uint32_t)x.dpad, q.d_q, q.d_qvalid, np, q.d_qid, q.radius, R, M, sp.tiles_per_wg, x.d_cand, x.d_cand_len);
+            });
+        });
+        if (rs == BN_OK) bn::scatter_results(x, q0, nq, top_m, m_stride, id_out, score_out, count_out);
+        return rs;
+    });
 }
 
 }  // namespace
@@ -299,12 +285,12 @@ extern "C" {
 
 bn_status bn_index_search_peaks(bn_index *x, const float *queries, size_t n_queries, size_t peak_radius, size_t top_m, size_t m_stride,
                                 uint64_t *id_out, float *score_out, uint32_t *count_out) {
-    return search(x, false, queries, nullptr, n_queries, -1, peak_radius, top_m, m_stride, id_out, score_out, count_out);
+    return search(x, bn::QuerySource::host(queries), n_queries, peak_radius, top_m, m_stride, id_out, score_out, count_out);
 }
 
 bn_status bn_index_search_peaks_ids(bn_index *x, const uint64_t *query_ids, size_t n_queries, int64_t exclude_radius, size_t peak_radius,
                                     size_t top_m, size_t m_stride, uint64_t *id_out, float *score_out, uint32_t *count_out) {
-    return search(x, true, nullptr, query_ids, n_queries, exclude_radius, peak_radius, top_m, m_stride, id_out, score_out, count_out);
+    return search(x, bn::QuerySource::stored(query_ids, exclude_radius), n_queries, peak_radius, top_m, m_stride, id_out, score_out, count_out);
 }
 
 }  // extern "C"

@@ -288,7 +288,7 @@ extern "C" bn_status bn_head_rank_index(const bn_head *h, bn_index *x, uint32_t 
             },
             mode == BN_RANK_UNCERTAIN ? enqueue_abs_merge : bn::index_enqueue_merge);
         if (st != BN_OK) return st;
-        bn::scatter_results(s.h_out, s.h_count, nc, M, m_stride, id_out + c0 * m_stride, logit_out + c0 * m_stride, count_out + c0);
+        bn::scatter_results(s, c0, nc, M, m_stride, id_out, logit_out, count_out);
     }
     return BN_OK;
 }

@@ -284,31 +284,17 @@ bn::LdsOptIn g_scan_lds;
 
 using bn::set_last_error;
 
-// the scan + merge passes over the ns staged sequences (the index not empty), results into the index's pinned mirrors; synchronous.  The
-// tiles are split among the workgroups as bn_index_search splits them: the result does not depend on the split
-bn_status run_search(bn::IndexScan x, size_t ns, int L, const float *d_q, const uint8_t *d_qvalid, const uint32_t *d_qid, int64_t radius, int R, int M) {
-    const bn::WgSplit sp = bn::split_tiles((uint32_t)((x.size + TILE - 1) / TILE), x.max_wg);
-    const float inv = 1.0f / (float)L;
-    x.lists = (size_t)bn::seq::per_pass((size_t)L);  // a pass of run_scan_passes is that many lists: one per sequence
-    return bn::run_scan_passes(x, ns, sp.n_wg, M, "sequence scan", [&](size_t p0, int np) {
-        bn::by_blocks(np * L, [&](auto qb) {
-            hipLaunchKernelGGL(seq_scan_kernel<decltype(qb)::value>, dim3(sp.n_wg), dim3(256), SEQ_LDS, x.stream, x.slab, x.valid, (uint32_t)x.size,
-                               (uint32_t)x.dpad, d_q + p0 * L * x.dpad, d_qvalid + p0 * L, np, L, inv, d_qid ? d_qid + p0 * L : nullptr,
-                               d_qid ? radius : (int64_t)-1, R, M, sp.tiles_per_wg, x.d_cand, x.d_cand_len);
-        });
-    });
-}
-
-// by_id: the sequences are the stored rows [first_ids[i], + seq_len), otherwise the host rows `queries`
-bn_status search(bn_index *ix, bool by_id, const float *queries, const uint64_t *first_ids, size_t n_seq, size_t seq_len, int64_t radius,
-                 size_t peak_radius, size_t top_m, size_t m_stride, uint64_t *id_out, float *score_out, uint32_t *count_out) {
-    bn_status st = bn::seq::check_args(by_id ? (const void *)first_ids : (const void *)queries, n_seq, seq_len, peak_radius, top_m, m_stride, id_out,
-                                       score_out, count_out);
+// The source's unit is a sequence: seq_len host rows, or the stored rows [first id, + seq_len).  Per round (as many sequences as the
+// index's query buffers hold rows for) the scan + merge passes over the staged sequences, results through the index's pinned mirrors.
+// The tiles are split among the workgroups as bn_index_search splits them: the result does not depend on the split
+bn_status search(bn_index *ix, const bn::QuerySource &src, size_t n_seq, size_t seq_len, size_t peak_radius, size_t top_m, size_t m_stride,
+                 uint64_t *id_out, float *score_out, uint32_t *count_out) {
+    bn_status st = bn::seq::check_args(src.data(), n_seq, seq_len, peak_radius, top_m, m_stride, id_out, score_out, count_out);
     if (st != BN_OK) return st;
     if ((st = bn::require_any_device()) != BN_OK) return st;
     if (!ix) return set_last_error(BN_ERR_INVALID_ARG, "null index");
     const size_t size = bn_index_size(ix);
-    if (by_id && (st = bn::seq::check_first_ids(first_ids, n_seq, seq_len, size)) != BN_OK) return st;
+    if (src.ids && (st = bn::seq::check_first_ids(src.ids, n_seq, seq_len, size)) != BN_OK) return st;
     if (size < seq_len) {  // no start is eligible: no launch
         std::fill(count_out, count_out + n_seq, 0u);
         return BN_OK;
@@ -317,26 +303,21 @@ bn_status search(bn_index *ix, bool by_id, const float *queries, const uint64_t 
     if ((st = bn::index_scan_state(ix, &x)) != BN_OK) return st;
     BN_HIP_TRY(g_scan_lds.prepare(x.device, {{(const void *)seq_scan_kernel<1>, SEQ_LDS}, {(const void *)seq_scan_kernel<2>, SEQ_LDS},
                                               {(const void *)seq_scan_kernel<3>, SEQ_LDS}, {(const void *)seq_scan_kernel<4>, SEQ_LDS}}));
-    const size_t round = bn::seq::per_round(seq_len, x.out_lists);
-    std::vector<uint64_t> ids;
-    for (size_t s0 = 0; s0 < n_seq; s0 += round) {
-        const size_t ns = std::min(round, n_seq - s0);
-        const float *d_q = nullptr;
-        const uint8_t *d_qvalid = nullptr;
-        const uint32_t *d_qid = nullptr;
-        if (by_id) {
-            ids.resize(ns * seq_len);
-            for (size_t i = 0; i < ns; i++)
-                for (size_t j = 0; j < seq_len; j++) ids[i * seq_len + j] = first_ids[s0 + i] + j;
-            st = bn::index_stage_query_ids(ix, ids.data(), ns * seq_len, &d_q, &d_qvalid, &d_qid);
-        } else {
-            st = bn::index_stage_queries(ix, queries + s0 * seq_len * x.dim, ns * seq_len, &d_q, &d_qvalid);
-        }
-        if (st != BN_OK) return st;
-        if ((st = run_search(x, ns, (int)seq_len, d_q, d_qvalid, d_qid, radius, (int)peak_radius, (int)top_m)) != BN_OK) return st;
-        bn::scatter_results(x.h_out, x.h_count, ns, top_m, m_stride, id_out + s0 * m_stride, score_out + s0 * m_stride, count_out + s0);
-    }
-    return BN_OK;
+    const int L = (int)seq_len, R = (int)peak_radius, M = (int)top_m;
+    const float inv = 1.0f / (float)L;
+    const bn::WgSplit sp = bn::split_tiles((uint32_t)((x.size + TILE - 1) / TILE), x.max_wg);
+    x.lists = (size_t)bn::seq::per_pass(seq_len);  // a pass of run_scan_passes is that many lists: one per sequence
+    return bn::for_each_round(ix, src, n_seq, seq_len, [&](size_t s0, size_t ns, const bn::StagedQueries &staged) -> bn_status {
+        bn_status rs = bn::run_scan_passes(x, ns, sp.n_wg, M, "sequence scan", [&](size_t p0, int np) {
+            const bn::StagedQueries q = staged.at(p0 * L);
+            bn::by_blocks(np * L, [&](auto qb) {
+                hipLaunchKernelGGL(seq_scan_kernel<decltype(qb)::value>, dim3(sp.n_wg), dim3(256), SEQ_LDS, x.stream, x.slab, x.valid, (uint32_t)x.size,
+                                   (uint32_t)x.dpad, q.d_q, q.d_qvalid, np, L, inv, q.d_qid, q.radius, R, M, sp.tiles_per_wg, x.d_cand, x.d_cand_len);
+            });
+        });
+        if (rs == BN_OK) bn::scatter_results(x, s0, ns, top_m, m_stride, id_out, score_out, count_out);
+        return rs;
+    });
 }
 
 }  // namespace
@@ -345,12 +326,12 @@ extern "C" {
 
 bn_status bn_index_search_seq(bn_index *x, const float *queries, size_t n_seq, size_t seq_len, size_t peak_radius, size_t top_m, size_t m_stride,
                               uint64_t *id_out, float *score_out, uint32_t *count_out) {
-    return search(x, false, queries, nullptr, n_seq, seq_len, -1, peak_radius, top_m, m_stride, id_out, score_out, count_out);
+    return search(x, bn::QuerySource::host(queries), n_seq, seq_len, peak_radius, top_m, m_stride, id_out, score_out, count_out);
 }
 
 bn_status bn_index_search_seq_ids(bn_index *x, const uint64_t *first_ids, size_t n_seq, size_t seq_len, int64_t exclude_radius, size_t peak_radius,
                                   size_t top_m, size_t m_stride, uint64_t *id_out, float *score_out, uint32_t *count_out) {
-    return search(x, true, nullptr, first_ids, n_seq, seq_len, exclude_radius, peak_radius, top_m, m_stride, id_out, score_out, count_out);
+    return search(x, bn::QuerySource::stored(first_ids, exclude_radius), n_seq, seq_len, peak_radius, top_m, m_stride, id_out, score_out, count_out);
 }
 
 }  // extern "C"

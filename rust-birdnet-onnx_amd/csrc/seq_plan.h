@@ -41,8 +41,7 @@ static_assert(Lds::Z % 16 == 0 && ((size_t)CAP * TILE) % 32 == 0, "the planes of
 constexpr int per_pass(size_t seq_len) { return (int)(SLOTS / seq_len) < CAP ? (int)(SLOTS / seq_len) : CAP; }
 // passes over the slab that n_seq sequences take
 constexpr size_t passes(size_t n_seq, size_t seq_len) { return (n_seq + per_pass(seq_len) - 1) / per_pass(seq_len); }
-// sequences per round of a call: a round stages at most stage_rows query rows (the index's query buffers)
-constexpr size_t per_round(size_t seq_len, size_t stage_rows) { return stage_rows / seq_len; }
+// the rounds of a call are query_source.h's, with a sequence as the unit
 
 // The tiles [c0, c1) whose window scores the workgroup owning tiles [t0, t1) of n_tiles computes: a start's windows reach into the next
 // tile, and with a peak radius the starts of the tile before and of the tile after the run are judged against

@@ -283,18 +283,15 @@ bn_status check_search_args(size_t n_queries, size_t refine, size_t top_m, size_
 }
 
 template <int QB>
-void launch_scan(const bn_sq8 *v, const bn::IndexScan &s, uint32_t n_wg, uint32_t tpw, size_t p0, int np, const uint8_t *d_qvalid, const uint32_t *d_qid,
-                 int64_t radius, int R) {
+void launch_scan(const bn_sq8 *v, const bn::IndexScan &s, uint32_t n_wg, uint32_t tpw, size_t p0, int np, const bn::StagedQueries &q, int R) {
     hipLaunchKernelGGL(sq8_scan_kernel<QB>, dim3(n_wg), dim3(256), scan_lds(QB), s.stream, v->d_codes, v->d_scales, s.valid, (uint32_t)v->covered,
-                       (uint32_t)v->dpad, v->d_qcodes + p0 * v->dpad, d_qvalid + p0, np, d_qid ? d_qid + p0 : nullptr, d_qid ? radius : (int64_t)-1, R, tpw,
-                       v->d_cand, v->d_cand_len);
+                       (uint32_t)v->dpad, v->d_qcodes + p0 * v->dpad, q.d_qvalid, np, q.d_qid, q.radius, R, tpw, v->d_cand, v->d_cand_len);
 }
 
 // encode, coarse scan + merge, re-rank + merge for the nq staged queries (nq <= out_lists, covered > 0); results into the index's pinned
 // mirrors, candidates left in d_members / d_ccount; synchronous
-bn_status run_search(bn_sq8 *v, const bn::IndexScan &s, size_t nq, const float *d_q, const uint8_t *d_qvalid, const uint32_t *d_qid, int64_t radius, int R,
-                     int M) {
-    hipLaunchKernelGGL(sq8_encode_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, s.stream, d_q, d_qvalid, (uint32_t)nq, (uint32_t)v->dim,
+bn_status run_search(bn_sq8 *v, const bn::IndexScan &s, size_t nq, const bn::StagedQueries &staged, int R, int M) {
+    hipLaunchKernelGGL(sq8_encode_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, s.stream, staged.d_q, staged.d_qvalid, (uint32_t)nq, (uint32_t)v->dim,
                        (uint32_t)v->dpad, v->d_qcodes, v->d_qscales);
     bn_status st = check_launch("sq8 encode");
     if (st != BN_OK) return st;
@@ -302,7 +299,7 @@ bn_status run_search(bn_sq8 *v, const bn::IndexScan &s, size_t nq, const float *
     const uint32_t tpw = sp.tiles_per_wg, n_wg = sp.n_wg;
     for (size_t p0 = 0; p0 < nq; p0 += QP) {
         const int np = (int)std::min<size_t>(QP, nq - p0);
-        bn::by_blocks(np, [&](auto qb) { launch_scan<decltype(qb)::value>(v, s, n_wg, tpw, p0, np, d_qvalid, d_qid, radius, R); });
+        bn::by_blocks(np, [&](auto qb) { launch_scan<decltype(qb)::value>(v, s, n_wg, tpw, p0, np, staged.at(p0), R); });
         if ((st = check_launch("sq8 scan")) != BN_OK) return st;
         if ((st = bn::ivf_enqueue_merge(s.stream, v->d_cand, v->d_cand_len, (size_t)np, n_wg, R, v->d_coarse + p0 * R, v->d_ccount + p0)) != BN_OK) return st;
     }
@@ -312,7 +309,7 @@ bn_status run_search(bn_sq8 *v, const bn::IndexScan &s, size_t nq, const float *
     bn::IvfGather g;
     g.slab = s.slab;
     g.dpad = (uint32_t)v->dpad;
-    g.q = d_q;
+    g.q = staged.d_q;
     g.probes = v->d_lists;
     g.nprobe = 1;
     g.counts = v->d_ccount;
@@ -322,41 +319,28 @@ bn_status run_search(bn_sq8 *v, const bn::IndexScan &s, size_t nq, const float *
     g.segments = (uint32_t)((R + TILE - 1) / TILE);
     if ((st = bn::ivf_enqueue_scan(s.stream, g, nq, M, v->d_cand, v->d_cand_len)) != BN_OK) return st;
     if ((st = bn::ivf_enqueue_merge(s.stream, v->d_cand, v->d_cand_len, nq, g.segments, M, s.d_out, s.d_count)) != BN_OK) return st;
-    BN_HIP_TRY(hipMemcpyAsync(s.h_out, s.d_out, nq * M * sizeof(Cand), hipMemcpyDeviceToHost, s.stream));
-    BN_HIP_TRY(hipMemcpyAsync(s.h_count, s.d_count, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, s.stream));
-    BN_HIP_TRY(hipStreamSynchronize(s.stream));
-    return BN_OK;
+    return bn::copy_back_results(s, nq, M);
 }
 
-bn_status search(bn_sq8 *v, const float *queries, const uint64_t *query_ids, size_t n_queries, int64_t radius, size_t refine, size_t top_m, size_t m_stride,
-                 uint64_t *id_out, float *score_out, uint32_t *count_out, uint64_t *cand_out, uint32_t *cand_count_out) {
-    bn_status st = check_search_args(n_queries, refine, top_m, m_stride, queries ? (const void *)queries : (const void *)query_ids, id_out, score_out, count_out);
+bn_status search(bn_sq8 *v, const bn::QuerySource &src, size_t n_queries, size_t refine, size_t top_m, size_t m_stride, uint64_t *id_out, float *score_out,
+                 uint32_t *count_out, uint64_t *cand_out, uint32_t *cand_count_out) {
+    bn_status st = check_search_args(n_queries, refine, top_m, m_stride, src.data(), id_out, score_out, count_out);
     if (st != BN_OK) return st;
     if ((st = bn::require_any_device()) != BN_OK) return st;
     if (!v) return set_last_error(BN_ERR_INVALID_ARG, "null view");
-    if (query_ids)
-        for (size_t i = 0; i < n_queries; i++)
-            if (query_ids[i] >= v->covered)
-                return set_last_error(BN_ERR_INVALID_ARG, "query id " + std::to_string(query_ids[i]) + " is not among the view's " + std::to_string(v->covered) + " rows");
+    if ((st = bn::check_query_ids(src, n_queries, v->covered, bn::IdLimit::VIEW)) != BN_OK) return st;
     bn::IndexScan s;
     if ((st = bn::index_scan_state(v->x, &s)) != BN_OK) return st;
+    if (v->covered == 0) {  // no launch
+        std::fill(count_out, count_out + n_queries, 0u);
+        if (cand_count_out) std::fill(cand_count_out, cand_count_out + n_queries, 0u);
+        return BN_OK;
+    }
     std::vector<uint32_t> members, ccount;
-    for (size_t q0 = 0; q0 < n_queries; q0 += v->out_lists) {
-        const size_t nq = std::min(v->out_lists, n_queries - q0);
-        if (v->covered == 0) {
-            std::fill(count_out + q0, count_out + q0 + nq, 0u);
-            if (cand_count_out) std::fill(cand_count_out + q0, cand_count_out + q0 + nq, 0u);
-            continue;
-        }
-        const float *d_q = nullptr;
-        const uint8_t *d_qvalid = nullptr;
-        const uint32_t *d_qid = nullptr;
-        if (query_ids) st = bn::index_stage_query_ids(v->x, query_ids + q0, nq, &d_q, &d_qvalid, &d_qid);
-        else st = bn::index_stage_queries(v->x, queries + q0 * v->dim, nq, &d_q, &d_qvalid);
-        if (st != BN_OK) return st;
-        if ((st = run_search(v, s, nq, d_q, d_qvalid, d_qid, radius, (int)refine, (int)top_m)) != BN_OK) return st;
-        bn::scatter_results(s.h_out, s.h_count, nq, top_m, m_stride, id_out + q0 * m_stride, score_out + q0 * m_stride, count_out + q0);
-        if (!cand_out && !cand_count_out) continue;
+    return bn::for_each_round(v->x, src, n_queries, 1, [&](size_t q0, size_t nq, const bn::StagedQueries &staged) -> bn_status {
+        if (bn_status rs = run_search(v, s, nq, staged, (int)refine, (int)top_m); rs != BN_OK) return rs;
+        bn::scatter_results(s, q0, nq, top_m, m_stride, id_out, score_out, count_out);
+        if (!cand_out && !cand_count_out) return BN_OK;
         ccount.resize(nq);
         BN_HIP_TRY(bn::gated::Memcpy(ccount.data(), v->d_ccount, nq * sizeof(uint32_t), hipMemcpyDeviceToHost));
         if (cand_count_out) std::copy(ccount.begin(), ccount.end(), cand_count_out + q0);
@@ -366,8 +350,8 @@ bn_status search(bn_sq8 *v, const float *queries, const uint64_t *query_ids, siz
             for (size_t i = 0; i < nq; i++)
                 for (uint32_t j = 0; j < ccount[i]; j++) cand_out[(q0 + i) * refine + j] = members[i * MMAX + j];
         }
-    }
-    return BN_OK;
+        return BN_OK;
+    });
 }
 
 }  // namespace
@@ -455,13 +439,14 @@ bn_status bn_sq8_read(const bn_sq8 *v, uint64_t first, size_t count, int8_t *cod
 bn_status bn_sq8_search(bn_sq8 *v, const float *queries, size_t n_queries, size_t refine, size_t top_m, size_t m_stride, uint64_t *id_out, float *score_out,
                         uint32_t *count_out, uint64_t *cand_out, uint32_t *cand_count_out) {
     if (n_queries && !queries) return set_last_error(BN_ERR_INVALID_ARG, "null argument");
-    return search(v, queries, nullptr, n_queries, -1, refine, top_m, m_stride, id_out, score_out, count_out, cand_out, cand_count_out);
+    return search(v, bn::QuerySource::host(queries), n_queries, refine, top_m, m_stride, id_out, score_out, count_out, cand_out, cand_count_out);
 }
 
 bn_status bn_sq8_search_ids(bn_sq8 *v, const uint64_t *query_ids, size_t n_queries, int64_t exclude_radius, size_t refine, size_t top_m, size_t m_stride,
                             uint64_t *id_out, float *score_out, uint32_t *count_out, uint64_t *cand_out, uint32_t *cand_count_out) {
     if (n_queries && !query_ids) return set_last_error(BN_ERR_INVALID_ARG, "null argument");
-    return search(v, nullptr, query_ids, n_queries, exclude_radius, refine, top_m, m_stride, id_out, score_out, count_out, cand_out, cand_count_out);
+    return search(v, bn::QuerySource::stored(query_ids, exclude_radius), n_queries, refine, top_m, m_stride, id_out, score_out, count_out, cand_out,
+                  cand_count_out);
 }
 
 }  // extern "C"

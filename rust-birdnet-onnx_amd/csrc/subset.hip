@@ -287,50 +287,35 @@ namespace {
 using bn::check_launch;
 using bn::set_last_error;
 
-// the scan + merge passes over the nq staged queries (nq <= out_lists, the subset not empty), results into the index's pinned
-// mirrors; synchronous.  The list's tiles are split among the workgroups as bn_index_search splits the slab's
-bn_status run_search(const bn_subset *s, const bn::IndexScan &x, size_t nq, const float *d_q, const uint8_t *d_qvalid, const uint32_t *d_qid, int64_t radius,
-                     int M) {
-    const bn::WgSplit sp = bn::split_tiles((uint32_t)((s->n + TILE - 1) / TILE), x.max_wg);
-    return bn::run_scan_passes(x, nq, sp.n_wg, M, "subset scan", [&](size_t p0, int np) {
-        bn::by_blocks(np, [&](auto qb) {
-            hipLaunchKernelGGL(subset_scan_kernel<decltype(qb)::value>, dim3(sp.n_wg), dim3(256), SCAN_LDS, x.stream, x.slab, x.valid, s->d_ids, (uint32_t)s->n,
-                               (uint32_t)x.dpad, d_q + p0 * x.dpad, d_qvalid + p0, np, d_qid ? d_qid + p0 : nullptr, d_qid ? radius : (int64_t)-1, M,
-                               sp.tiles_per_wg, x.d_cand, x.d_cand_len);
-        });
-    });
-}
-
-bn_status search(bn_subset *s, const float *queries, const uint64_t *query_ids, size_t n_queries, int64_t radius, size_t top_m, size_t m_stride,
-                 uint64_t *id_out, float *score_out, uint32_t *count_out) {
+// Per round the scan + merge passes over the staged queries, results through the index's pinned mirrors.  The list's tiles are split
+// among the workgroups as bn_index_search splits the slab's
+bn_status search(bn_subset *s, const bn::QuerySource &src, size_t n_queries, size_t top_m, size_t m_stride, uint64_t *id_out, float *score_out,
+                 uint32_t *count_out) {
     bn_status st = bn::check_top_m(top_m, m_stride);  // bn_index_search's refusals, in its order, without the index
     if (st != BN_OK) return st;
-    if ((st = bn::check_search_buffers(queries ? (const void *)queries : (const void *)query_ids, n_queries, id_out, score_out, count_out)) != BN_OK) return st;
+    if ((st = bn::check_search_buffers(src.data(), n_queries, id_out, score_out, count_out)) != BN_OK) return st;
     if ((st = bn::require_any_device()) != BN_OK) return st;
     if (!s) return set_last_error(BN_ERR_INVALID_ARG, "null subset");
-    if (query_ids) {
-        const size_t size = bn_index_size(s->x);
-        for (size_t i = 0; i < n_queries; i++)
-            if (query_ids[i] >= size) return set_last_error(BN_ERR_INVALID_ARG, "query id " + std::to_string(query_ids[i]) + " is not in the index");
-    }
+    if ((st = bn::check_query_ids(src, n_queries, bn_index_size(s->x))) != BN_OK) return st;
     if (s->n == 0) {  // no launch
         std::fill(count_out, count_out + n_queries, 0u);
         return BN_OK;
     }
     bn::IndexScan x;
     if ((st = bn::index_scan_state(s->x, &x)) != BN_OK) return st;
-    for (size_t q0 = 0; q0 < n_queries; q0 += x.out_lists) {
-        const size_t nq = std::min(x.out_lists, n_queries - q0);
-        const float *d_q = nullptr;
-        const uint8_t *d_qvalid = nullptr;
-        const uint32_t *d_qid = nullptr;
-        if (query_ids) st = bn::index_stage_query_ids(s->x, query_ids + q0, nq, &d_q, &d_qvalid, &d_qid);
-        else st = bn::index_stage_queries(s->x, queries + q0 * x.dim, nq, &d_q, &d_qvalid);
-        if (st != BN_OK) return st;
-        if ((st = run_search(s, x, nq, d_q, d_qvalid, d_qid, radius, (int)top_m)) != BN_OK) return st;
-        bn::scatter_results(x.h_out, x.h_count, nq, top_m, m_stride, id_out + q0 * m_stride, score_out + q0 * m_stride, count_out + q0);
-    }
-    return BN_OK;
+    const int M = (int)top_m;
+    const bn::WgSplit sp = bn::split_tiles((uint32_t)((s->n + TILE - 1) / TILE), x.max_wg);
+    return bn::for_each_round(s->x, src, n_queries, 1, [&](size_t q0, size_t nq, const bn::StagedQueries &staged) -> bn_status {
+        bn_status rs = bn::run_scan_passes(x, nq, sp.n_wg, M, "subset scan", [&](size_t p0, int np) {
+            const bn::StagedQueries q = staged.at(p0);
+            bn::by_blocks(np, [&](auto qb) {
+                hipLaunchKernelGGL(subset_scan_kernel<decltype(qb)::value>, dim3(sp.n_wg), dim3(256), SCAN_LDS, x.stream, x.slab, x.valid, s->d_ids,
+                                   (uint32_t)s->n, (uint32_t)x.dpad, q.d_q, q.d_qvalid, np, q.d_qid, q.radius, M, sp.tiles_per_wg, x.d_cand, x.d_cand_len);
+            });
+        });
+        if (rs == BN_OK) bn::scatter_results(x, q0, nq, top_m, m_stride, id_out, score_out, count_out);
+        return rs;
+    });
 }
 
 // a subset of n ids for index x, the list allocated (n > 0) and not yet written
@@ -460,13 +445,13 @@ bn_status bn_subset_read(const bn_subset *s, size_t first, size_t count, uint64_
 bn_status bn_subset_search(bn_subset *s, const float *queries, size_t n_queries, size_t top_m, size_t m_stride, uint64_t *id_out, float *score_out,
                            uint32_t *count_out) {
     if (n_queries && !queries) return set_last_error(BN_ERR_INVALID_ARG, "null argument");
-    return search(s, queries, nullptr, n_queries, -1, top_m, m_stride, id_out, score_out, count_out);
+    return search(s, bn::QuerySource::host(queries), n_queries, top_m, m_stride, id_out, score_out, count_out);
 }
 
 bn_status bn_subset_search_ids(bn_subset *s, const uint64_t *query_ids, size_t n_queries, int64_t exclude_radius, size_t top_m, size_t m_stride,
                                uint64_t *id_out, float *score_out, uint32_t *count_out) {
     if (n_queries && !query_ids) return set_last_error(BN_ERR_INVALID_ARG, "null argument");
-    return search(s, nullptr, query_ids, n_queries, exclude_radius, top_m, m_stride, id_out, score_out, count_out);
+    return search(s, bn::QuerySource::stored(query_ids, exclude_radius), n_queries, top_m, m_stride, id_out, score_out, count_out);
 }
 
 }  // extern "C"

@@ -74,9 +74,6 @@ int main() {
         EXPECT(refused(check_range(1, UINT64_MAX, 100, &lo, &hi), "past"));
         EXPECT(refused(check_range(UINT64_MAX, UINT64_MAX, big, &lo, &hi), "past"));
         EXPECT(lo == 7 && hi == 7);
-        const std::vector<uint64_t> ids{0, 99, 100};
-        EXPECT(check_query_ids(ids.data(), 2, 100) == BN_OK && check_query_ids(nullptr, 0, 0) == BN_OK);
-        EXPECT(refused(check_query_ids(ids.data(), 3, 100), "100"));
     }
     // ---- plans
     size_t plans = 0;

@@ -34,7 +34,6 @@ static bool refused(bn_status st, const char *word) {
 int main() {
     using namespace bn::group;
     using bn::above::BUDGET;
-    using bn::above::check_query_ids;
     using bn::above::check_range;
     using bn::above::TILE;
     using bn::above::WIDTHS;
@@ -75,7 +74,7 @@ int main() {
             EXPECT(refused(check_args(q.data(), 2, t.data(), 4, 4, cnt.data(), bid.data(), nullptr), "pair"));
         }
     }
-    // ---- the id range and the query ids: above_plan.h's, as group.hip calls them
+    // ---- the id range: above_plan.h's, as group.hip calls it
     {
         uint32_t lo = 7, hi = 7;
         const size_t big = 0xffffffffull - 65;  // the largest index
@@ -88,9 +87,6 @@ int main() {
         EXPECT(refused(check_range(99, 2, 100, &lo, &hi), "past"));
         EXPECT(refused(check_range(UINT64_MAX, UINT64_MAX, big, &lo, &hi), "past"));
         EXPECT(lo == 7 && hi == 7);
-        const std::vector<uint64_t> ids{0, 99, 100};
-        EXPECT(check_query_ids(ids.data(), 2, 100) == BN_OK && check_query_ids(nullptr, 0, 0) == BN_OK);
-        EXPECT(refused(check_query_ids(ids.data(), 3, 100), "100"));
     }
     // ---- plans
     size_t plans = 0;

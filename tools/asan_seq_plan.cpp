@@ -90,8 +90,6 @@ int main() {
             EXPECT(np * P >= n && (np == 0 || (np - 1) * P < n));
             plans++;
         }
-        const size_t r = per_round(L, 1024);
-        EXPECT(r >= 1 && r * L <= 1024 && (r + 1) * L > 1024);
     }
     // ---- the tiles a workgroup computes: what a judged start reads lies in them
     const uint32_t tiles[] = {1, 2, 3, 4, 5, 7, 100, 2561, 0x03ffffffu};
