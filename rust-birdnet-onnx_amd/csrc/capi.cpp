@@ -211,95 +211,95 @@ float *resolve(const bn_ctx *c, const Ref &r, const float *d_in) {
     }
 }
 
+// The squeeze-excite a launch carries (PlanOp::se_fused), as the kernels take it: finished by a DWCONV / MBCONV ...
 SeTail se_tail_of(const bn_ctx *c, const PlanOp &op, const float *d_in) {
     SeTail t{};
     if (!op.se_fused) return t;
+    const auto &se = op.r.se;
     t.on = 1;
     t.se = op.se;
-    t.w1 = resolve(c, op.x[0], d_in);
-    t.b1 = resolve(c, op.x[1], d_in);
-    t.w2t = resolve(c, op.x[2], d_in);
-    t.b2 = resolve(c, op.x[3], d_in);
-    t.gate = resolve(c, op.res, d_in);
-    t.counter = reinterpret_cast<uint32_t *>(resolve(c, op.scale, d_in));
-    t.cnt_bs = c->pd->plan->storages[op.scale.id].elems;
+    t.w1 = resolve(c, se.w1, d_in);
+    t.b1 = resolve(c, se.b1, d_in);
+    t.w2t = resolve(c, se.w2t, d_in);
+    t.b2 = resolve(c, se.b2, d_in);
+    t.gate = resolve(c, se.gate, d_in);
+    t.counter = reinterpret_cast<uint32_t *>(resolve(c, se.counter, d_in));  // one ticket word per sample
+    t.cnt_bs = c->pd->plan->storages[se.counter.id].elems;
     return t;
+}
+// ... or computed in a GEMM's prologue
+SeInline se_inline_of(const bn_ctx *c, const PlanOp &op, const float *d_in) {
+    const auto &se = op.r.se;
+    SeInline si{};
+    si.se = op.se;
+    si.partial = resolve(c, se.partial, d_in);
+    si.w1 = resolve(c, se.w1, d_in);
+    si.b1 = resolve(c, se.b1, d_in);
+    si.w2t = resolve(c, se.w2t, d_in);
+    si.b2 = resolve(c, se.b2, d_in);
+    return si;
 }
 
 void launch_op(const bn_ctx *c, const PlanOp &op, const float *d_in, int64_t batch) {
-    float *out = resolve(c, op.out, d_in);
-    const float *a = resolve(c, op.a, d_in);
+    const PlanOp::Operands &r = op.r;
+    auto at = [&](const Ref &ref) { return resolve(c, ref, d_in); };
+    float *out = at(r.out);
+    const float *a = at(r.a);
     switch (op.kind) {
         case OpKind::ELT: {
             const float *eb[ELT_MAX_STAGES];
-            for (int k = 0; k < ELT_MAX_STAGES; k++) eb[k] = resolve(c, op.eb[k], d_in);
+            for (int k = 0; k < ELT_MAX_STAGES; k++) eb[k] = at(r.chain[k]);
             launch_eltwise(c->stream, op.elt, out, a, eb, batch);
             break;
         }
-        case OpKind::REDUCE: launch_reduce(c->stream, op.red, out, a, batch, op.red.pair ? resolve(c, op.b, d_in) : nullptr); break;
+        case OpKind::REDUCE: launch_reduce(c->stream, op.red, out, a, batch, op.red.pair ? at(r.pair_out) : nullptr); break;
         case OpKind::GEMM:
             if (op.se_fused) {  // squeeze-excite in the GEMM's prologue: only the LDS-DMA kernel carries it (planner rule I)
-                SeInline si{};
-                si.se = op.se;
-                si.partial = resolve(c, op.b, d_in);
-                si.w1 = resolve(c, op.x[0], d_in);
-                si.b1 = resolve(c, op.x[1], d_in);
-                si.w2t = resolve(c, op.x[2], d_in);
-                si.b2 = resolve(c, op.x[3], d_in);
-                if (!(op.gemm.w3 ? launch_gemm_dma3 : launch_gemm_dma)(c->stream, op.gemm, out, a, resolve(c, op.w, d_in), resolve(c, op.bias, d_in), resolve(c, op.res, d_in),
-                                     resolve(c, op.scale, d_in), batch, &si))
+                const SeInline si = se_inline_of(c, op, d_in);
+                if (!(op.gemm.w3 ? launch_gemm_dma3 : launch_gemm_dma)(c->stream, op.gemm, out, a, at(r.w), at(r.bias), at(r.residual), at(r.gate), batch, &si))
                     launch_error("GEMM with inline squeeze-excite: operands are not 16-byte aligned");
                 break;
             }
             {
-                FramePre pre = op.pre;  // the signal chain a framing GEMM applies while it loads its span (planner rule G): operands in eb
-                for (int k = 0; k < ELT_MAX_STAGES; k++) pre.sc[k] = k < pre.n ? resolve(c, op.eb[k], d_in) : nullptr;
-                if (op.gemm.fold == 2) {  // quarter-folded cosine bank: window tables and column map ride in w2 / bias2
-                    launch_gemm_fold2(c->stream, op.gemm, out, a, resolve(c, op.w, d_in), resolve(c, op.bias, d_in), resolve(c, op.w2, d_in),
-                                      reinterpret_cast<const int32_t *>(resolve(c, op.bias2, d_in)), batch, &pre);
+                FramePre pre = op.pre;  // the signal chain a framing GEMM applies while it loads its span (planner rule G)
+                for (int k = 0; k < ELT_MAX_STAGES; k++) pre.sc[k] = k < pre.n ? at(r.chain[k]) : nullptr;
+                if (op.gemm.fold == 2) {  // quarter-folded cosine bank
+                    launch_gemm_fold2(c->stream, op.gemm, out, a, at(r.w), at(r.bias), at(r.fold2.tables),
+                                      reinterpret_cast<const int32_t *>(at(r.fold2.colmap)), batch, &pre);  // int32 bits in a constant of floats
                     break;
                 }
-                launch_gemm(c->stream, op.gemm, out, a, resolve(c, op.w, d_in), resolve(c, op.bias, d_in), resolve(c, op.res, d_in),
-                            resolve(c, op.scale, d_in), batch, &pre);
+                launch_gemm(c->stream, op.gemm, out, a, at(r.w), at(r.bias), at(r.residual), at(r.gate), batch, &pre);
             }
             break;
-        case OpKind::CONV:
-            launch_conv(c->stream, op.conv, out, a, resolve(c, op.w, d_in), resolve(c, op.bias, d_in), resolve(c, op.res, d_in), batch);
-            break;
+        case OpKind::CONV: launch_conv(c->stream, op.conv, out, a, at(r.w), at(r.bias), at(r.residual), batch); break;
         case OpKind::DWCONV: {
             SeTail tail = se_tail_of(c, op, d_in);
-            launch_dwconv(c->stream, op.dw, out, a, resolve(c, op.w, d_in), resolve(c, op.bias, d_in), resolve(c, op.b, d_in), batch, tail.on ? &tail : nullptr);
+            launch_dwconv(c->stream, op.dw, out, a, at(r.w), at(r.bias), at(r.gap_out), batch, tail.on ? &tail : nullptr);
             break;
         }
         case OpKind::GAP: launch_gap_partial(c->stream, op.gap, out, a, batch); break;
         case OpKind::POOL: launch_pool(c->stream, op.pool, out, a, batch); break;
-        case OpKind::MBCONV:
-        {
+        case OpKind::MBCONV: {
             SeTail tail = se_tail_of(c, op, d_in);
-            launch_mbconv(c->stream, op.mb, out, a, resolve(c, op.w, d_in), resolve(c, op.bias, d_in), resolve(c, op.w2, d_in),
-                          resolve(c, op.bias2, d_in), resolve(c, op.b, d_in), batch, tail.on ? &tail : nullptr);
+            launch_mbconv(c->stream, op.mb, out, a, at(r.w), at(r.bias), at(r.w2), at(r.bias2), at(r.gap_out), batch, tail.on ? &tail : nullptr);
             break;
         }
         case OpKind::FFT: {
             StftPtrs sp{};
             sp.out = out;
             sp.in = a;
-            sp.window = resolve(c, op.w, d_in);
-            sp.tw = reinterpret_cast<const float2 *>(resolve(c, op.w2, d_in));
-            sp.otab = resolve(c, op.bias2, d_in);
-            sp.bias = resolve(c, op.bias, d_in);
-            for (int k = 0; k < ELT_MAX_STAGES; k++) sp.pre[k] = resolve(c, op.eb[k], d_in);
-            sp.mstart = resolve(c, op.x[0], d_in);
-            sp.mcol = resolve(c, op.x[1], d_in);
-            sp.mval = resolve(c, op.x[2], d_in);
-            sp.mel_bias = resolve(c, op.x[3], d_in);
+            sp.window = at(r.fft.window);
+            sp.tw = reinterpret_cast<const float2 *>(at(r.fft.twiddles));  // (cos, sin) pairs
+            sp.otab = at(r.fft.otab);
+            sp.bias = at(r.bias);
+            for (int k = 0; k < ELT_MAX_STAGES; k++) sp.pre[k] = at(r.chain[k]);
+            sp.mstart = at(r.mel.start);
+            sp.mcol = at(r.mel.entries);  // (column, value) pairs; mval stays unused
+            sp.mel_bias = at(r.mel.bias);
             launch_stft(c->stream, op.fft, sp, batch);
             break;
         }
-        case OpKind::SEFC:
-            launch_se_fc(c->stream, op.se, out, resolve(c, op.b, d_in), a, resolve(c, op.w, d_in), resolve(c, op.bias, d_in), resolve(c, op.w2, d_in),
-                         resolve(c, op.bias2, d_in), batch);
-            break;
+        case OpKind::SEFC: launch_se_fc(c->stream, op.se, out, at(r.hidden), a, at(r.w), at(r.bias), at(r.w2), at(r.bias2), batch); break;
     }
 }
 

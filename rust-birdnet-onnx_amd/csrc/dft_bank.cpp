@@ -266,9 +266,9 @@ bool emit_stft(Plan &plan, const std::string &name, const PlanOp &base, const Df
     PlanOp op;
     op.kind = OpKind::FFT;
     op.name = "stft:" + name;
-    op.out = base.out;
-    op.a = base.a;
-    op.bias = base.bias;
+    op.r.out = base.r.out;
+    op.r.a = base.r.a;
+    op.r.bias = base.r.bias;
     FftDesc &d = op.fft;
     d.L = L; d.M = M; d.hop = (int32_t)g.lda; d.frames = (int32_t)OW; d.nout = (int32_t)Cout;
     d.logM = 0;
@@ -331,9 +331,9 @@ bool emit_stft(Plan &plan, const std::string &name, const PlanOp &base, const Df
         e[4] = (float)(0.5 * (a * (1.0 + sn) - b * cs));
         e[5] = (float)(0.5 * (a * cs + b * (1.0 + sn)));
     }
-    op.w = Ref{Space::CONSTS, add_const(plan, bank.window), 0};
-    op.w2 = Ref{Space::CONSTS, add_const(plan, tw), 0};
-    op.bias2 = Ref{Space::CONSTS, add_const(plan, otab), 0};
+    op.r.fft.window = Ref{Space::CONSTS, add_const(plan, bank.window), 0};
+    op.r.fft.twiddles = Ref{Space::CONSTS, add_const(plan, tw), 0};
+    op.r.fft.otab = Ref{Space::CONSTS, add_const(plan, otab), 0};
     const double log2L = std::log2((double)L);
     op.flops_fft = (double)OW * 2.5 * L * log2L;
     op.macs = op.flops_fft / 2;  // multiply-add equivalents actually performed (vector ALU)
@@ -470,9 +470,9 @@ bool emit_quarter_fold(Plan &plan, const std::string &name, const PlanOp &base, 
         wk.swap(pk);
         f.gemm.fold_wpk = 1;
     }
-    f.w = Ref{Space::CONSTS, add_const(plan, wk), 0};
-    f.w2 = Ref{Space::CONSTS, add_const(plan, tabs), 0};
-    f.bias2 = Ref{Space::CONSTS, add_const(plan, colmap_bits), 0};
+    f.r.w = Ref{Space::CONSTS, add_const(plan, wk), 0};
+    f.r.fold2.tables = Ref{Space::CONSTS, add_const(plan, tabs), 0};
+    f.r.fold2.colmap = Ref{Space::CONSTS, add_const(plan, colmap_bits), 0};
     f.macs = (double)OW * (double)Cout * (double)(Q + 1);  // multiplications actually performed (padding columns excluded)
     f.weight_bytes = 4.0 * (wk.size() + tabs.size() + colmap.size() + (has_bias ? Cout : 0));
     plan.dft_gemm_macs += (double)OW * Cout * L;

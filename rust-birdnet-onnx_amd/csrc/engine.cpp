@@ -319,9 +319,9 @@ class Builder {
         PlanOp op;
         op.kind = OpKind::ELT;
         op.name = name;
-        op.out = ref_of(out);
-        op.a = a;
-        op.eb[0] = b;
+        op.r.out = ref_of(out);
+        op.r.a = a;
+        op.r.chain[0] = b;
         EltDesc &d = op.elt;
         d.nd = (int)loops.size();
         d.per_sample = 1;
@@ -566,9 +566,9 @@ class Builder {
             }
             PlanOp f = base;
             f.name = "Conv:" + n.name + (sign > 0 ? "~sym" : "~anti");
-            f.out.offset += r.n0;
-            if (has_bias) f.bias.offset += r.n0;
-            f.w = Ref{Space::CONSTS, add_const(wk), 0};
+            f.r.out.offset += r.n0;
+            if (has_bias) f.r.bias.offset += r.n0;
+            f.r.w = Ref{Space::CONSTS, add_const(wk), 0};
             f.gemm.N = (int32_t)nn;
             f.gemm.K = (int32_t)K;
             f.gemm.fold = sign;
@@ -1702,8 +1702,8 @@ class Builder {
         PlanOp op;
         op.kind = OpKind::POOL;
         op.name = n.op_type + ":" + n.name;
-        op.out = ref_of(out);
-        op.a = ref_of(x);
+        op.r.out = ref_of(out);
+        op.r.a = ref_of(x);
         PoolDesc &d = op.pool;
         d.H = (int32_t)H; d.W = (int32_t)W; d.C = (int32_t)C; d.OH = (int32_t)OH; d.OW = (int32_t)OW;
         d.kh = (int32_t)kh; d.kw = (int32_t)kw; d.sh = (int32_t)sh; d.sw = (int32_t)sw; d.pt = (int32_t)pt; d.pl = (int32_t)pl;
@@ -2071,13 +2071,13 @@ class Builder {
         PlanOp *dwp = nullptr;
         if (!plan_.ops.empty()) {
             PlanOp &last = plan_.ops.back();
-            if (last.kind == OpKind::DWCONV && last.dw.tiled && last.out.space == Space::ARENA && last.out.id == x.storage && last.out.offset == 0)
+            if (last.kind == OpKind::DWCONV && last.dw.tiled && last.r.out.space == Space::ARENA && last.r.out.id == x.storage && last.r.out.offset == 0)
                 dwp = &last;
         }
         PlanOp *mbp = nullptr;
         if (!dwp && !plan_.ops.empty()) {
             PlanOp &last = plan_.ops.back();
-            if (last.kind == OpKind::MBCONV && last.out.space == Space::ARENA && last.out.id == x.storage && last.out.offset == 0) mbp = &last;
+            if (last.kind == OpKind::MBCONV && last.r.out.space == Space::ARENA && last.r.out.id == x.storage && last.r.out.offset == 0) mbp = &last;
         }
         if (dwp) splits = dwp->dw.nblk;
         if (mbp) splits = mbp->mb.tiles_x * mbp->mb.tiles_y;
@@ -2085,19 +2085,19 @@ class Builder {
         if (mbp) {
             mbp->mb.has_gap = 1;
             mbp->mb.gap_bs = plan_.storages[partial.storage].elems;
-            mbp->b = ref_of(partial);
-            touch(mbp->b, (int)plan_.ops.size() - 1);
+            mbp->r.gap_out = ref_of(partial);
+            touch(mbp->r.gap_out, (int)plan_.ops.size() - 1);
         } else if (dwp) {
             dwp->dw.has_gap = 1;
             dwp->dw.gap_bs = plan_.storages[partial.storage].elems;
-            dwp->b = ref_of(partial);
-            touch(dwp->b, (int)plan_.ops.size() - 1);
+            dwp->r.gap_out = ref_of(partial);
+            touch(dwp->r.gap_out, (int)plan_.ops.size() - 1);
         } else {
             PlanOp op;
             op.kind = OpKind::GAP;
             op.name = "se.squeeze:" + n.name;
-            op.out = ref_of(partial);
-            op.a = ref_of(x);
+            op.r.out = ref_of(partial);
+            op.r.a = ref_of(x);
             op.gap.HW = HW; op.gap.C = (int32_t)C; op.gap.splits = splits;
             op.gap.in_bs = batch_stride(x); op.gap.out_bs = plan_.storages[partial.storage].elems;
             op.bytes = 4.0 * (double)(HW * C + splits * C);
@@ -2133,14 +2133,14 @@ class Builder {
             const int hidx = (int)plan_.ops.size() - 1;
             host->se_fused = 1;
             host->se = sd;
-            host->x[0] = Ref{Space::CONSTS, add_const(w1), 0};
-            if (!b1.empty()) host->x[1] = Ref{Space::CONSTS, add_const(b1), 0};
-            host->x[2] = Ref{Space::CONSTS, add_const(w2t), 0};
-            if (!b2.empty()) host->x[3] = Ref{Space::CONSTS, add_const(b2), 0};
-            host->res = ref_of(gate);
-            host->scale = ref_of(cnt);
-            touch(host->res, hidx);
-            touch(host->scale, hidx);
+            host->r.se.w1 = Ref{Space::CONSTS, add_const(w1), 0};
+            if (!b1.empty()) host->r.se.b1 = Ref{Space::CONSTS, add_const(b1), 0};
+            host->r.se.w2t = Ref{Space::CONSTS, add_const(w2t), 0};
+            if (!b2.empty()) host->r.se.b2 = Ref{Space::CONSTS, add_const(b2), 0};
+            host->r.se.gate = ref_of(gate);
+            host->r.se.counter = ref_of(cnt);
+            touch(host->r.se.gate, hidx);
+            touch(host->r.se.counter, hidx);
             host->name += "+se";
             host->macs += 2.0 * (double)C * Cr;
             host->weight_bytes += 4.0 * (w1.size() + w2.size() + b1.size() + b2.size());
@@ -2150,13 +2150,13 @@ class Builder {
             Val hidden = new_act(Dims{Cr}, Dims{1});
             op.kind = OpKind::SEFC;
             op.name = "se.excite:" + n.name;
-            op.out = ref_of(gate);
-            op.a = ref_of(partial);
-            op.b = ref_of(hidden);  // scratch between the two excite launches
-            op.w = Ref{Space::CONSTS, add_const(w1), 0};
-            if (!b1.empty()) op.bias = Ref{Space::CONSTS, add_const(b1), 0};
-            op.w2 = Ref{Space::CONSTS, add_const(w2t), 0};
-            if (!b2.empty()) op.bias2 = Ref{Space::CONSTS, add_const(b2), 0};
+            op.r.out = ref_of(gate);
+            op.r.a = ref_of(partial);
+            op.r.hidden = ref_of(hidden);  // scratch between the two excite launches
+            op.r.w = Ref{Space::CONSTS, add_const(w1), 0};
+            if (!b1.empty()) op.r.bias = Ref{Space::CONSTS, add_const(b1), 0};
+            op.r.w2 = Ref{Space::CONSTS, add_const(w2t), 0};
+            if (!b2.empty()) op.r.bias2 = Ref{Space::CONSTS, add_const(b2), 0};
             op.se = sd;
             op.macs = 2.0 * (double)C * Cr;
             op.weight_bytes = 4.0 * (w1.size() + w2.size() + b1.size() + b2.size());
@@ -2269,8 +2269,8 @@ class Builder {
         plan_.storages[out.storage].elems = std::max<int64_t>(d.kept, 1);
         d.bi = batch_stride(v);
         d.bo = plan_.storages[out.storage].elems;
-        op_.out = ref_of(out);
-        op_.a = ref_of(v);
+        op_.r.out = ref_of(out);
+        op_.r.a = ref_of(v);
         op_.bytes = 4.0 * (double)(d.kept * d.red + d.kept);
         // A whole-segment min / max (144 000 samples -> one number) as ONE block per sample leaves the chip idle
         // (32 blocks at batch 32, 26 us).  Min and max do not depend on the order of evaluation, so the range is cut
@@ -2285,12 +2285,12 @@ class Builder {
                 Val part = new_act(Dims{c}, Dims{1});
                 PlanOp s1 = op_, s2 = op_;
                 s1.name += "/chunks";
-                s1.out = ref_of(part);
+                s1.r.out = ref_of(part);
                 s1.red.nk = 1; s1.red.ksize[0] = c; s1.red.kin[0] = d.red / c; s1.red.kout[0] = 1; s1.red.kept = c;
                 s1.red.rsize[0] = d.red / c; s1.red.red = d.red / c;
                 s1.red.bo = plan_.storages[part.storage].elems;
                 s1.bytes = 4.0 * (double)(d.red + c);
-                s2.a = ref_of(part);
+                s2.r.a = ref_of(part);
                 s2.red.rsize[0] = c; s2.red.red = c;
                 s2.red.bi = plan_.storages[part.storage].elems;
                 s2.bytes = 4.0 * (double)(c + 1);
@@ -2412,12 +2412,12 @@ class Builder {
         Val out = new_act(out_dims, out_strides);
         PlanOp op;
         op.name = "Conv:" + n.name;
-        op.out = ref_of(out);
+        op.r.out = ref_of(out);
         op.macs = (double)OH * OW * Cout * kh * kw * cpg;
         op.weight_bytes = 4.0 * (wf.size() + (has_bias ? Cout : 0));
         op.bytes = 4.0 * ((double)Cin * H * W + (double)Cout * OH * OW * (has_res ? 2 : 1));
-        if (has_bias) op.bias = Ref{Space::CONSTS, add_const(bias), 0};
-        if (has_res) op.res = ref_of(res);
+        if (has_bias) op.r.bias = Ref{Space::CONSTS, add_const(bias), 0};
+        if (has_res) op.r.residual = ref_of(res);
 
         bool unit_dil = dil[0] == 1 && dil[1] == 1;
         // a padded 1-D convolution with a long filter (STFT / learned front ends) is worth a padded copy
@@ -2443,7 +2443,7 @@ class Builder {
             // GEMM: 1x1 conv (rows = H*W) or 1-D conv as overlapping rows (rows = OW, K = kw*Cin)
             x = to_channels_last(x, n.name);
             if (gate_storage >= 0) {
-                op.scale = Ref{Space::ARENA, gate_storage, 0};
+                op.r.gate = Ref{Space::ARENA, gate_storage, 0};
                 op.gemm.has_scale = 1;
                 op.gemm.s_bs = plan_.storages[gate_storage].elems;
             }
@@ -2464,12 +2464,12 @@ class Builder {
             for (int64_t o = 0; o < Cout; o++)
                 for (int64_t c = 0; c < Cin; c++)
                     for (int64_t k = 0; k < kw; k++) wp[(o * kw + k) * Cin + c] = wf[(o * Cin + c) * kw + k];
-            op.a = ref_of(x);
+            op.r.a = ref_of(x);
             if (H == 1 && Cin == 1 && !has_res && gate_storage < 0 && fold_framing_conv(n, op, wf, Cout, kw, OW, has_bias)) {
                 define(cur, out);
                 return;
             }
-            op.w = Ref{Space::CONSTS, add_const(wp), 0};
+            op.r.w = Ref{Space::CONSTS, add_const(wp), 0};
         } else if (groups == Cin && cpg == 1 && Cout == Cin) {
             x = to_channels_last(x, n.name);
             if (has_res) {  // depthwise kernel has no residual input: undo that fusion
@@ -2504,8 +2504,8 @@ class Builder {
             std::vector<float> wp(wf.size());  // [C][1][kh][kw] -> [kh][kw][C]
             for (int64_t c = 0; c < Cin; c++)
                 for (int64_t k = 0; k < kh * kw; k++) wp[k * Cin + c] = wf[c * kh * kw + k];
-            op.w = Ref{Space::CONSTS, add_const(wp), 0};
-            op.a = ref_of(x);
+            op.r.w = Ref{Space::CONSTS, add_const(wp), 0};
+            op.r.a = ref_of(x);
             // expand 1x1 conv immediately before, consumed only here?  Then both run in one launch with the
             // expanded tensor kept in LDS (mbconv_expand_dw_kernel): the 6x-expanded activation never
             // touches HBM.  Measured on MI355X (batch 32, per pair): 48x256x16->96 s2: 101 -> 79 us,
@@ -2522,7 +2522,7 @@ class Builder {
                 PlanOp &pe = plan_.ops.back();
                 const ConvDesc &cd = pe.conv;
                 const bool act_zero = act_keeps_zero(cd.act, cd.p0, cd.p1);
-                const bool stem = pe.kind == OpKind::CONV && pe.out.space == Space::ARENA && pe.out.id == x.storage && pe.out.offset == 0 && x.offset == 0 &&
+                const bool stem = pe.kind == OpKind::CONV && pe.r.out.space == Space::ARENA && pe.r.out.id == x.storage && pe.r.out.offset == 0 && x.offset == 0 &&
                                   cd.groups == 1 && cd.kh == cd.kw && cd.sh == cd.sw && cd.dh == 1 && cd.dw == 1 && !cd.has_res && cd.Cin <= 4 &&
                                   cd.kh * cd.kw * cd.Cin <= 48 && cd.OH == H && cd.OW == W && cd.Cout == Cin && act_zero &&
                                   (H * W >= 3072 || sw_is(sw::BN_MBFUSE, "force"));
@@ -2532,20 +2532,20 @@ class Builder {
                     PlanOp mb;
                     mb.kind = OpKind::MBCONV;
                     mb.name = "stem:" + pe.name.substr(pe.name.find(':') + 1) + "+" + n.name;
-                    mb.out = op.out;
-                    mb.a = pe.a;
+                    mb.r.out = op.r.out;
+                    mb.r.a = pe.r.a;
                     // first-conv filters [kh][kw][Cin1][Cout] (as lowered for the direct kernel) -> [Cout][KW]: im2col column
                     // order (ky, kx, c), zero padded to 8-wide K groups
                     const int64_t K1 = (int64_t)cd.kh * cd.kw * cd.Cin, KW = (K1 + 7) / 8 * 8;
                     {
-                        const std::vector<float> &w0 = plan_.consts[pe.w.id];
+                        const std::vector<float> &w0 = plan_.consts[pe.r.w.id];
                         std::vector<float> wpk((size_t)(Cin * KW), 0.0f);
                         for (int64_t nn = 0; nn < Cin; nn++)
-                            for (int64_t k = 0; k < K1; k++) wpk[nn * KW + k] = w0[pe.w.offset + k * Cin + nn];
-                        mb.w = Ref{Space::CONSTS, add_const(wpk), 0};
+                            for (int64_t k = 0; k < K1; k++) wpk[nn * KW + k] = w0[pe.r.w.offset + k * Cin + nn];
+                        mb.r.w = Ref{Space::CONSTS, add_const(wpk), 0};
                     }
-                    mb.bias = pe.bias;
-                    mb.w2 = op.w; mb.bias2 = op.bias;
+                    mb.r.bias = pe.r.bias;
+                    mb.r.w2 = op.r.w; mb.r.bias2 = op.r.bias;
                     MbDesc &m = mb.mb;
                     m.H = (int32_t)H; m.W = (int32_t)W; m.Cin = (int32_t)K1; m.C = (int32_t)Cin; m.OH = (int32_t)OH; m.OW = (int32_t)OW;
                     m.k = (int32_t)kw; m.s = (int32_t)strides[1]; m.pt = (int32_t)pt; m.pl = (int32_t)pl;
@@ -2583,10 +2583,10 @@ class Builder {
                 // context throughput drops from 34.2k to 33.1k seg/s.
                 const bool map_off = !sw_is(sw::BN_MBMAP, "1");
                 const int64_t map_maxhw = sw_i64(sw::BN_MBMAP_MAXHW);
-                const bool producer0 = pe.kind == OpKind::GEMM && pe.out.space == Space::ARENA && pe.out.id == x.storage && pe.out.offset == 0 &&
+                const bool producer0 = pe.kind == OpKind::GEMM && pe.r.out.space == Space::ARENA && pe.r.out.id == x.storage && pe.r.out.offset == 0 &&
                                        x.offset == 0 && !pe.gemm.has_scale && !pe.gemm.has_res && pe.gemm.rows == H * W && pe.gemm.N == Cin &&
-                                       pe.gemm.lda == pe.gemm.K && pe.gemm.K % 4 == 0 && pe.a.offset % 4 == 0 && !pe.gemm.fold && !pe.gemm.npost &&
-                                       (pe.a.space != Space::ARENA || plan_.storages[pe.a.id].elems % 4 == 0);
+                                       pe.gemm.lda == pe.gemm.K && pe.gemm.K % 4 == 0 && pe.r.a.offset % 4 == 0 && !pe.gemm.fold && !pe.gemm.npost &&
+                                       (pe.r.a.space != Space::ARENA || plan_.storages[pe.r.a.id].elems % 4 == 0);
                 // Whole-map form with the INPUT resident in LDS (mbmap.hip, round 3): one block = one sample's map x a group of
                 // mid channels, input fetched once per block by LDS-DMA, no staging on the vector ALU.  Default wherever a
                 // configuration fits (192- and 48-pixel maps); BN_MBMAP2=0 disables.
@@ -2621,36 +2621,36 @@ class Builder {
                     PlanOp mb;
                     mb.kind = OpKind::MBCONV;
                     mb.name = "mbconv:" + pe.name.substr(pe.name.find(':') + 1) + "+" + n.name;
-                    mb.out = op.out;
-                    mb.a = pe.a;
+                    mb.r.out = op.r.out;
+                    mb.r.a = pe.r.a;
                     // expand filters repacked for the kernel: [C][KW] rows = Cin weights | zeros, KW = Cin rounded up to
                     // 8-wide K groups (the bias starts the accumulators)
                     if (whole_map && map2 && map_ws) {
                         // mbmap_ws.hip: the filters as bf16 planes in fragment order (plan_rules.h)
-                        mb.w = Ref{Space::CONSTS, add_const(pack_mbmap_w3p(plan_.consts[pe.w.id].data() + pe.w.offset, Cin, pe.gemm.K)), 0};
+                        mb.r.w = Ref{Space::CONSTS, add_const(pack_mbmap_w3p(plan_.consts[pe.r.w.id].data() + pe.r.w.offset, Cin, pe.gemm.K)), 0};
                     } else if (whole_map && map2 && mshape.cin_pad != pe.gemm.K) {
                         // mbmap.hip with padded k: the filter rows get the zeros the input rows get from the zero page
                         const int64_t Kc = pe.gemm.K, KP = mshape.cin_pad;
-                        const std::vector<float> &w0 = plan_.consts[pe.w.id];
+                        const std::vector<float> &w0 = plan_.consts[pe.r.w.id];
                         std::vector<float> wpk((size_t)(Cin * KP), 0.0f);
                         for (int64_t nn = 0; nn < Cin; nn++)
-                            for (int64_t k = 0; k < Kc; k++) wpk[nn * KP + k] = w0[pe.w.offset + nn * Kc + k];
-                        mb.w = Ref{Space::CONSTS, add_const(wpk), 0};
+                            for (int64_t k = 0; k < Kc; k++) wpk[nn * KP + k] = w0[pe.r.w.offset + nn * Kc + k];
+                        mb.r.w = Ref{Space::CONSTS, add_const(wpk), 0};
                     } else if (whole_map && map2 && map_b3) {
                         // mbmap.hip's bf16x3 form: the filters in the order of its LDS chunk image (plan_rules.h)
-                        mb.w = Ref{Space::CONSTS, add_const(pack_mbmap_w3f(plan_.consts[pe.w.id].data() + pe.w.offset, Cin, pe.gemm.K)), 0};
+                        mb.r.w = Ref{Space::CONSTS, add_const(pack_mbmap_w3f(plan_.consts[pe.r.w.id].data() + pe.r.w.offset, Cin, pe.gemm.K)), 0};
                     } else if (whole_map) {
-                        mb.w = pe.w;  // [C][Cin] as the GEMM had it
+                        mb.r.w = pe.r.w;  // [C][Cin] as the GEMM had it
                     } else {
                         const int64_t Kc = pe.gemm.K, KW = (Kc + 7) / 8 * 8;
-                        const std::vector<float> &w0 = plan_.consts[pe.w.id];
+                        const std::vector<float> &w0 = plan_.consts[pe.r.w.id];
                         std::vector<float> wpk((size_t)(Cin * KW), 0.0f);
                         for (int64_t nn = 0; nn < Cin; nn++)
-                            for (int64_t k = 0; k < Kc; k++) wpk[nn * KW + k] = w0[pe.w.offset + nn * Kc + k];
-                        mb.w = Ref{Space::CONSTS, add_const(wpk), 0};
+                            for (int64_t k = 0; k < Kc; k++) wpk[nn * KW + k] = w0[pe.r.w.offset + nn * Kc + k];
+                        mb.r.w = Ref{Space::CONSTS, add_const(wpk), 0};
                     }
-                    mb.bias = pe.bias;
-                    mb.w2 = op.w; mb.bias2 = op.bias;
+                    mb.r.bias = pe.r.bias;
+                    mb.r.w2 = op.r.w; mb.r.bias2 = op.r.bias;
                     MbDesc &m = mb.mb;
                     m.H = (int32_t)H; m.W = (int32_t)W; m.Cin = pe.gemm.K; m.C = (int32_t)Cin; m.OH = (int32_t)OH; m.OW = (int32_t)OW;
                     m.k = (int32_t)kw; m.s = (int32_t)strides[1]; m.pt = (int32_t)pt; m.pl = (int32_t)pl;
@@ -2701,8 +2701,8 @@ class Builder {
             for (int64_t o = 0; o < Cout; o++)
                 for (int64_t c = 0; c < cpg; c++)
                     for (int64_t k = 0; k < kh * kw; k++) wp[(k * cpg + c) * Cout + o] = wf[(o * cpg + c) * kh * kw + k];
-            op.w = Ref{Space::CONSTS, add_const(wp), 0};
-            op.a = ref_of(x);
+            op.r.w = Ref{Space::CONSTS, add_const(wp), 0};
+            op.r.a = ref_of(x);
         }
         push_op(std::move(op));
         define(cur, out);
@@ -2761,10 +2761,10 @@ class Builder {
         op.kind = OpKind::GEMM;
         op.mfma = true;
         op.name = n.op_type + ":" + n.name;
-        op.out = ref_of(out);
-        op.a = ref_of(a);
-        op.w = Ref{Space::CONSTS, add_const(wp), 0};
-        if (has_bias) op.bias = Ref{Space::CONSTS, add_const(bias), 0};
+        op.r.out = ref_of(out);
+        op.r.a = ref_of(a);
+        op.r.w = Ref{Space::CONSTS, add_const(wp), 0};
+        if (has_bias) op.r.bias = Ref{Space::CONSTS, add_const(bias), 0};
         GemmDesc &g = op.gemm;
         g.rows = rows; g.K = (int32_t)K; g.N = (int32_t)N;
         g.lda = K; g.a_bs = batch_stride(a);

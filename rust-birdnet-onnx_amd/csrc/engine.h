@@ -33,13 +33,30 @@ enum class OpKind : int32_t { ELT, REDUCE, GEMM, CONV, DWCONV, GAP, SEFC, MBCONV
 struct PlanOp {
     OpKind kind;
     std::string name;
-    Ref out, a, b, w, bias, res, scale, w2, bias2;
-    Ref eb[ELT_MAX_STAGES];  // ELT: second operand of each chain stage; FFT: operands of the absorbed prologue chain
-    Ref x[4];                // FFT: mel filter bank in CSR form (row starts, columns, values) and its bias
+    // Every buffer the launch reads or writes, one field per meaning: a field a kind does not use stays NONE.  Nothing but Refs
+    // (for_each_ref below visits them all).  Weights, biases and tables -- w, bias, w2, bias2, se.w1 .. se.b2, fft, mel, fold2 --
+    // are never in the arena (tools/asan_plan_operands.cpp checks it); the others are activations (a and chain entries: or constants).
+    struct Operands {
+        Ref out, a;
+        Ref w, bias;        // weights and bias of the launch's (first) layer
+        Ref residual;       // GEMM / CONV: added to the result
+        Ref gate;           // GEMM: per-channel scale of its input (the squeeze-excite gate)
+        Ref w2, bias2;      // the second layer of the launch: MBCONV's depthwise filters, SEFC's second product
+        Ref pair_out;       // REDUCE: the max of a min / max pair
+        Ref gap_out;        // DWCONV / MBCONV: per-block channel sums for the squeeze that follows
+        Ref hidden;         // SEFC: scratch between its two products
+        // a squeeze-excite carried by another launch (se_fused): in a GEMM's prologue (reads partial) or finished by the last block of
+        // a DWCONV / MBCONV (kernels.h, SeTail: writes gate; counter = one uint32 ticket per sample, zero between launches)
+        struct { Ref w1, b1, w2t, b2, partial, gate, counter; } se;
+        struct { Ref window, twiddles, otab; } fft;  // FFT: analysis window, pass twiddles (float2), untangle table
+        struct { Ref start, entries, bias; } mel;    // FFT: the absorbed mel bank, CSR row starts and (column, value) pairs or matrix tiles
+        struct { Ref tables, colmap; } fold2;        // quarter-folded GEMM: the two window tables, the int32 column map
+        Ref chain[ELT_MAX_STAGES];  // second operand of each stage: ELT's own chain, the chain a framing GEMM (pre) or an FFT absorbed
+    } r;
     EltDesc elt{};
     ReduceDesc red{};
     GemmDesc gemm{};
-    FramePre pre{};    // GEMM with fold (LDS-resident framing kernels): per-sample chain applied while the span is loaded; operands in eb
+    FramePre pre{};    // GEMM with fold (LDS-resident framing kernels): per-sample chain applied while the span is loaded; operands in r.chain
     ConvDesc conv{};
     DwDesc dw{};
     GapDesc gap{};
@@ -47,11 +64,8 @@ struct PlanOp {
     MbDesc mb{};
     PoolDesc pool{};
     FftDesc fft{};
-    // GEMM (gemm.se_inline, planner rule I): the squeeze-excite that PRECEDES it is computed in the GEMM's prologue: `se`
-    // holds its shape, b the squeeze partial sums, x[0..3] its weights (w1, b1, w2 transposed, b2).
-    // DWCONV / MBCONV: the squeeze-excite that follows is finished by the launch's last block per sample (kernels.h,
-    // SeTail): `se` holds its shape, x[0..3] its weights (w1, b1, w2 transposed, b2), res the gate, scale the
-    // per-sample ticket counters (a pinned arena storage of one word per sample, zero between launches)
+    // the launch carries a squeeze-excite (shape in `se`, operands in r.se): a GEMM (gemm.se_inline, planner rule I) computes the one
+    // that PRECEDES it in its prologue, a DWCONV / MBCONV finishes the one that follows in its last block per sample
     int32_t se_fused = 0;
     double flops_fft = 0;   // FFT: algorithmic flops per sample counted as an FFT (2.5 L log2 L per real frame) + sparse mel
     double macs = 0;        // per sample
@@ -62,6 +76,25 @@ struct PlanOp {
     double weight_bytes = 0;
     bool mfma = false;
 };
+
+// The one list of a launch's operands (O: PlanOp::Operands, const or not): liveness, the users of a storage or of a constant all go
+// through it and filter by space.  A field added to Operands and not listed here stops the build.
+template <class O, class F>
+constexpr void for_each_ref(O &r, F &&f) {
+    f(r.out); f(r.a); f(r.w); f(r.bias); f(r.residual); f(r.gate); f(r.w2); f(r.bias2); f(r.pair_out); f(r.gap_out); f(r.hidden);
+    f(r.se.w1); f(r.se.b1); f(r.se.w2t); f(r.se.b2); f(r.se.partial); f(r.se.gate); f(r.se.counter);
+    f(r.fft.window); f(r.fft.twiddles); f(r.fft.otab);
+    f(r.mel.start); f(r.mel.entries); f(r.mel.bias);
+    f(r.fold2.tables); f(r.fold2.colmap);
+    for (auto &c : r.chain) f(c);
+}
+constexpr size_t count_refs() {
+    PlanOp::Operands r{};
+    size_t n = 0;
+    for_each_ref(r, [&n](const Ref &) { n++; });
+    return n;
+}
+static_assert(sizeof(PlanOp::Operands) == count_refs() * sizeof(Ref), "for_each_ref must visit every field of PlanOp::Operands");
 
 struct Storage {
     int64_t elems = 0;  // per sample

@@ -109,15 +109,7 @@ inline int32_t add_const(Plan &plan, const std::vector<float> &data) {
 }
 inline void push_op(Plan &plan, PlanOp &&op) {
     int idx = (int)plan.ops.size();
-    touch(plan, op.out, idx);
-    touch(plan, op.a, idx);
-    touch(plan, op.b, idx);
-    touch(plan, op.res, idx);
-    touch(plan, op.scale, idx);
-    touch(plan, op.w2, idx);
-    touch(plan, op.bias2, idx);
-    for (auto &r : op.eb) touch(plan, r, idx);
-    for (auto &r : op.x) touch(plan, r, idx);
+    for_each_ref(op.r, [&](const Ref &r) { touch(plan, r, idx); });
     plan.ops.push_back(std::move(op));
 }
 

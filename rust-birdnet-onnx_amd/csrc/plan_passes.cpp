@@ -10,18 +10,24 @@ namespace bn {
 namespace {
 
 // --------------------------------------------------------- elementwise chain fusion
-void all_refs(PlanOp &op, std::vector<Ref *> &out) {
-    out = {&op.out, &op.a, &op.b, &op.res, &op.scale, &op.w2, &op.bias2};
-    for (auto &r : op.eb) out.push_back(&r);
-    for (auto &r : op.x) out.push_back(&r);
-}
 void recompute_liveness(Plan &plan) {
     for (auto &st : plan.storages) { st.first = -1; st.last = -1; }
-    std::vector<Ref *> refs;
-    for (size_t k = 0; k < plan.ops.size(); k++) {
-        all_refs(plan.ops[k], refs);
-        for (Ref *r : refs) touch(plan, *r, (int)k);
-    }
+    for (size_t k = 0; k < plan.ops.size(); k++) for_each_ref(plan.ops[k].r, [&](const Ref &r) { touch(plan, r, (int)k); });
+}
+// per arena storage: the launches that name it in any operand, ascending
+std::vector<std::vector<int>> arena_users(const Plan &plan) {
+    std::vector<std::vector<int>> users(plan.storages.size());
+    for (size_t k = 0; k < plan.ops.size(); k++)
+        for_each_ref(plan.ops[k].r, [&](const Ref &r) {
+            if (r.space == Space::ARENA && (users[r.id].empty() || users[r.id].back() != (int)k)) users[r.id].push_back((int)k);
+        });
+    return users;
+}
+// how many operands of `op` name `space`:`id`
+int refs_to(const PlanOp &op, Space space, int id) {
+    int n = 0;
+    for_each_ref(op.r, [&](const Ref &r) { n += r.space == space && r.id == id; });
+    return n;
 }
 // An ELT launch whose result is read by exactly one later ELT launch, as that launch's primary
 // operand over the very same index space, is folded into it (its stages are prepended).
@@ -30,22 +36,15 @@ void fuse_elementwise_chains(Plan &plan) {
     while (changed) {
         changed = false;
         recompute_liveness(plan);
-        // users per storage
-        std::vector<std::vector<int>> users(plan.storages.size());
-        std::vector<Ref *> refs;
-        for (size_t k = 0; k < plan.ops.size(); k++) {
-            all_refs(plan.ops[k], refs);
-            for (Ref *r : refs)
-                if (r->space == Space::ARENA && (users[r->id].empty() || users[r->id].back() != (int)k)) users[r->id].push_back((int)k);
-        }
+        const auto users = arena_users(plan);
         for (size_t j = 0; j < plan.ops.size() && !changed; j++) {
             PlanOp &cons = plan.ops[j];
-            if (cons.kind != OpKind::ELT || cons.a.space != Space::ARENA) continue;
-            const auto &u = users[cons.a.id];
-            if (u.size() != 2 || u[1] != (int)j || plan.storages[cons.a.id].pinned) continue;
+            if (cons.kind != OpKind::ELT || cons.r.a.space != Space::ARENA) continue;
+            const auto &u = users[cons.r.a.id];
+            if (u.size() != 2 || u[1] != (int)j || plan.storages[cons.r.a.id].pinned) continue;
             PlanOp &prod = plan.ops[u[0]];
-            if (prod.kind != OpKind::ELT || prod.out.space != Space::ARENA || prod.out.id != cons.a.id) continue;
-            const int64_t delta = cons.a.offset - prod.out.offset;  // consumer may read a shifted / reversed view
+            if (prod.kind != OpKind::ELT || prod.r.out.space != Space::ARENA || prod.r.out.id != cons.r.a.id) continue;
+            const int64_t delta = cons.r.a.offset - prod.r.out.offset;  // consumer may read a shifted / reversed view
             if (prod.elt.nstages + cons.elt.nstages > ELT_MAX_STAGES) continue;
             // (A) same index space: the consumer reads exactly what the producer wrote, or
             // (B) the producer is a flat map over a dense buffer (offset in == offset out), so the
@@ -73,39 +72,39 @@ void fuse_elementwise_chains(Plan &plan) {
             // the consumer must not also use the intermediate as a stage operand
             {
                 bool clash = false;
-                for (int k = 0; k < ce.nstages; k++) clash = clash || (cons.eb[k].space == Space::ARENA && cons.eb[k].id == cons.a.id);
+                for (int k = 0; k < ce.nstages; k++) clash = clash || (cons.r.chain[k].space == Space::ARENA && cons.r.chain[k].id == cons.r.a.id);
                 if (clash) continue;
             }
             // nothing between the two may overwrite the producer's inputs: storages are single-assignment
             // except concat targets, which are only read after all their writers ran -> safe.
             PlanOp fused = cons;
             fused.name = prod.name + "+" + cons.name;
-            fused.a = prod.a;
+            fused.r.a = prod.r.a;
             EltDesc &fe = fused.elt;
             fe.ba = pe.ba;
             fe.nstages = pe.nstages + ce.nstages;
             if (same) {
                 for (int k = 0; k < pe.nd; k++) fe.sa[k] = pe.sa[k];
-                for (int k = 0; k < pe.nstages; k++) { fe.st[k] = pe.st[k]; fused.eb[k] = prod.eb[k]; }
+                for (int k = 0; k < pe.nstages; k++) { fe.st[k] = pe.st[k]; fused.r.chain[k] = prod.r.chain[k]; }
             } else if (flat_cons) {
                 fe.nd = pe.nd;
                 for (int k = 0; k < pe.nd; k++) { fe.size[k] = pe.size[k]; fe.sa[k] = pe.sa[k]; fe.so[k] = ce.so[0] * runs[k]; }
-                for (int k = 0; k < pe.nstages; k++) { fe.st[k] = pe.st[k]; fused.eb[k] = prod.eb[k]; }
+                for (int k = 0; k < pe.nstages; k++) { fe.st[k] = pe.st[k]; fused.r.chain[k] = prod.r.chain[k]; }
             } else {
                 // flat producer: its primary operand and every full-size stage operand are addressed
                 // with the strides the consumer used for the intermediate (fe.sa is already ce.sa)
-                fused.a.offset += delta;
+                fused.r.a.offset += delta;
                 for (int k = 0; k < pe.nstages; k++) {
                     fe.st[k] = pe.st[k];
-                    fused.eb[k] = prod.eb[k];
+                    fused.r.chain[k] = prod.r.chain[k];
                     const bool full = pe.st[k].bin != BIN_NONE && pe.st[k].sb[0] == 1;
-                    if (full) fused.eb[k].offset += delta;
+                    if (full) fused.r.chain[k].offset += delta;
                     for (int q = 0; q < ELT_MAX_DIMS; q++) fe.st[k].sb[q] = (q < ce.nd && full) ? ce.sa[q] : 0;
                 }
             }
             for (int k = 0; k < ce.nstages; k++) {
                 fe.st[pe.nstages + k] = ce.st[k];
-                fused.eb[pe.nstages + k] = cons.eb[k];
+                fused.r.chain[pe.nstages + k] = cons.r.chain[k];
                 if (flat_cons)
                     for (int q = 0; q < ELT_MAX_DIMS; q++) fe.st[pe.nstages + k].sb[q] = q < pe.nd ? ce.st[k].sb[0] * runs[q] : 0;
             }
@@ -122,21 +121,21 @@ void fuse_elementwise_chains(Plan &plan) {
             EltDesc &ce = cons.elt;
             for (int k = 0; k < ce.nstages && !changed; k++) {
                 EltStage &cs = ce.st[k];
-                const Ref &br = cons.eb[k];
+                const Ref &br = cons.r.chain[k];
                 if (cs.bin == BIN_NONE || cs.bsq || br.space != Space::ARENA || plan.storages[br.id].pinned) continue;
                 const auto &u = users[br.id];
                 if (u.size() != 2 || u[1] != (int)j) continue;
                 const PlanOp &prod = plan.ops[u[0]];
                 const EltDesc &pe = prod.elt;
-                if (prod.kind != OpKind::ELT || prod.out.space != Space::ARENA || prod.out.id != br.id || prod.out.offset != br.offset) continue;
+                if (prod.kind != OpKind::ELT || prod.r.out.space != Space::ARENA || prod.r.out.id != br.id || prod.r.out.offset != br.offset) continue;
                 if (pe.nstages != 1 || pe.st[0].bin != BIN_MUL || pe.st[0].act != ACT_NONE || pe.st[0].bsq) continue;
-                if (prod.eb[0].space != prod.a.space || prod.eb[0].id != prod.a.id || prod.eb[0].offset != prod.a.offset || pe.st[0].bb != pe.ba) continue;
-                if (cons.a.space == Space::ARENA && cons.a.id == br.id) continue;
+                if (prod.r.chain[0].space != prod.r.a.space || prod.r.chain[0].id != prod.r.a.id || prod.r.chain[0].offset != prod.r.a.offset || pe.st[0].bb != pe.ba) continue;
+                if (cons.r.a.space == Space::ARENA && cons.r.a.id == br.id) continue;
                 bool match = pe.nd == ce.nd && pe.bo == cs.bb;
                 for (int q = 0; match && q < pe.nd; q++)
                     match = pe.size[q] == ce.size[q] && pe.so[q] == cs.sb[q] && pe.st[0].sb[q] == pe.sa[q];
                 if (!match) continue;
-                cons.eb[k] = prod.a;
+                cons.r.chain[k] = prod.r.a;
                 for (int q = 0; q < ELT_MAX_DIMS; q++) cs.sb[q] = q < pe.nd ? pe.sa[q] : 0;
                 cs.bb = pe.ba;
                 cs.bsq = 1;
@@ -160,32 +159,26 @@ void fuse_elementwise_chains(Plan &plan) {
 void absorb_se_into_gemms(Plan &plan) {
     if (!(sw_int(sw::BN_SEGEMM) == 1)) return;
     const int max_c = gemm_dma_se_max_channels();
-    std::vector<Ref *> refs;
     for (size_t j = 0; j < plan.ops.size(); j++) {
-        if (plan.ops[j].kind != OpKind::SEFC || plan.ops[j].out.space != Space::ARENA) continue;
-        const int gate_id = plan.ops[j].out.id;
+        if (plan.ops[j].kind != OpKind::SEFC || plan.ops[j].r.out.space != Space::ARENA) continue;
+        const int gate_id = plan.ops[j].r.out.id;
         if (plan.storages[gate_id].pinned) continue;
         int cons = -1, users = 0;
-        for (size_t k = 0; k < plan.ops.size(); k++) {
-            if (k == j) continue;
-            all_refs(plan.ops[k], refs);
-            bool uses = false;
-            for (Ref *r : refs) uses = uses || (r->space == Space::ARENA && r->id == gate_id);
-            if (uses) { users++; cons = (int)k; }
-        }
+        for (size_t k = 0; k < plan.ops.size(); k++)
+            if (k != j && refs_to(plan.ops[k], Space::ARENA, gate_id)) { users++; cons = (int)k; }
         if (users != 1 || cons < (int)j) continue;
         PlanOp &g = plan.ops[cons];
         const PlanOp &se = plan.ops[j];
-        if (g.kind != OpKind::GEMM || !g.gemm.has_scale || g.scale.space != Space::ARENA || g.scale.id != gate_id || g.scale.offset != 0 || g.se_fused) continue;
+        if (g.kind != OpKind::GEMM || !g.gemm.has_scale || g.r.gate.space != Space::ARENA || g.r.gate.id != gate_id || g.r.gate.offset != 0 || g.se_fused) continue;
         if (se.se.C != g.gemm.K || se.se.C > max_c || se.se.C % 4 || !gemm_dma_shape(g.gemm)) continue;
         g.se_fused = 1;
         g.se = se.se;
         g.gemm.se_inline = 1;
-        g.b = se.a;       // squeeze partial sums
-        g.x[0] = se.w;    // W1 [Cr][C]
-        g.x[1] = se.bias;
-        g.x[2] = se.w2;   // W2 transposed [Cr][C]
-        g.x[3] = se.bias2;
+        g.r.se.partial = se.r.a;  // squeeze partial sums
+        g.r.se.w1 = se.r.w;       // W1 [Cr][C]
+        g.r.se.b1 = se.r.bias;
+        g.r.se.w2t = se.r.w2;     // W2 transposed [Cr][C]
+        g.r.se.b2 = se.r.bias2;
         g.name = se.name + "+" + g.name;
         g.macs_valu_extra += se.macs;
         g.weight_bytes += se.weight_bytes;
@@ -205,16 +198,6 @@ void absorb_se_into_gemms(Plan &plan) {
 void absorb_into_stft(Plan &plan) {
     const bool mel_on = !sw_is(sw::BN_STFT_MEL, "0");
     const bool pre_on = sw_on(sw::BN_STFT_PRE);
-    auto users_of = [&]() {
-        std::vector<std::vector<int>> users(plan.storages.size());
-        std::vector<Ref *> refs;
-        for (size_t k = 0; k < plan.ops.size(); k++) {
-            all_refs(plan.ops[k], refs);
-            for (Ref *r : refs)
-                if (r->space == Space::ARENA && (users[r->id].empty() || users[r->id].back() != (int)k)) users[r->id].push_back((int)k);
-        }
-        return users;
-    };
     //  * (round 3) the power / magnitude pass behind a cos | sin bank: an elementwise launch  re*re + im*im [-> sqrt]  over
     //    the two halves of every spectrum row, whose only reader it is -- the launch computes both linear forms of a bin
     //    in one lane and stores f(u^2 + v^2): half the spectrum bytes written, none read back, one launch less, and the
@@ -223,42 +206,42 @@ void absorb_into_stft(Plan &plan) {
         bool again = true;
         while (again) {
             again = false;
-            auto users = users_of();
+            const auto users = arena_users(plan);
             for (size_t i = 0; i < plan.ops.size() && !again; i++) {
                 PlanOp &f = plan.ops[i];
                 FftDesc &d = f.fft;
-                if (f.kind != OpKind::FFT || d.nmel || d.power || d.has_bias || d.npost || f.out.space != Space::ARENA || plan.storages[f.out.id].pinned) continue;
+                if (f.kind != OpKind::FFT || d.nmel || d.power || d.has_bias || d.npost || f.r.out.space != Space::ARENA || plan.storages[f.r.out.id].pinned) continue;
                 if (d.nout % 2 || d.ldc != d.nout || d.out_rs != d.nout || d.out_cs != 1) continue;
-                const auto &u = users[f.out.id];
+                const auto &u = users[f.r.out.id];
                 if (u.size() != 2 || u[0] != (int)i) continue;
                 PlanOp &el = plan.ops[u[1]];
                 const EltDesc &e = el.elt;
                 const int64_t nb = d.nout / 2;
                 if (el.kind != OpKind::ELT || e.nd != 2 || e.size[0] != d.frames || e.size[1] != nb || e.sa[0] != d.nout || e.sa[1] != 1 || e.ba != d.c_bs) continue;
-                if (el.a.space != Space::ARENA || el.a.id != f.out.id || el.a.offset != f.out.offset) continue;
-                if (el.out.space != Space::ARENA || e.so[1] != 1 || e.so[0] < nb) continue;
+                if (el.r.a.space != Space::ARENA || el.r.a.id != f.r.out.id || el.r.a.offset != f.r.out.offset) continue;
+                if (el.r.out.space != Space::ARENA || e.so[1] != 1 || e.so[0] < nb) continue;
                 // stage 0: x * x (the operand is the same view); stage 1: + y^2 with y the other half of the row; [stage 2: sqrt]
                 if (e.nstages < 2 || e.nstages > 3) continue;
                 const EltStage &s0 = e.st[0], &s1 = e.st[1];
-                const Ref &r0 = el.eb[0], &r1 = el.eb[1];
-                if (s0.bin != BIN_MUL || s0.bsq || s0.act != ACT_NONE || r0.space != Space::ARENA || r0.id != f.out.id || r0.offset != f.out.offset ||
+                const Ref &r0 = el.r.chain[0], &r1 = el.r.chain[1];
+                if (s0.bin != BIN_MUL || s0.bsq || s0.act != ACT_NONE || r0.space != Space::ARENA || r0.id != f.r.out.id || r0.offset != f.r.out.offset ||
                     s0.sb[0] != d.nout || s0.sb[1] != 1 || s0.bb != d.c_bs)
                     continue;
-                if (s1.bin != BIN_ADD || !s1.bsq || s1.act != ACT_NONE || r1.space != Space::ARENA || r1.id != f.out.id || r1.offset != f.out.offset + nb ||
+                if (s1.bin != BIN_ADD || !s1.bsq || s1.act != ACT_NONE || r1.space != Space::ARENA || r1.id != f.r.out.id || r1.offset != f.r.out.offset + nb ||
                     s1.sb[0] != d.nout || s1.sb[1] != 1 || s1.bb != d.c_bs)
                     continue;
                 if (e.nstages == 3 && !(e.st[2].bin == BIN_NONE && e.st[2].act == ACT_SQRT)) continue;
                 // the two halves must be the two forms of the SAME bins in the same order (same buffer positions)
-                const std::vector<float> &ot = plan.consts[f.bias2.id];
-                bool same = (int64_t)ot.size() >= f.bias2.offset + d.nout * 8;
+                const std::vector<float> &ot = plan.consts[f.r.fft.otab.id];
+                bool same = (int64_t)ot.size() >= f.r.fft.otab.offset + d.nout * 8;
                 for (int64_t c = 0; c < nb && same; c++) {
-                    const float *u0 = &ot[(size_t)(f.bias2.offset + c * 8)], *v0 = &ot[(size_t)(f.bias2.offset + (c + nb) * 8)];
+                    const float *u0 = &ot[(size_t)(f.r.fft.otab.offset + c * 8)], *v0 = &ot[(size_t)(f.r.fft.otab.offset + (c + nb) * 8)];
                     same = u0[0] == v0[0] && u0[1] == v0[1];
                 }
                 if (!same) continue;
                 std::vector<float> ot2((size_t)nb * 12, 0.0f);
                 for (int64_t c = 0; c < nb; c++) {
-                    const float *u0 = &ot[(size_t)(f.bias2.offset + c * 8)], *v0 = &ot[(size_t)(f.bias2.offset + (c + nb) * 8)];
+                    const float *u0 = &ot[(size_t)(f.r.fft.otab.offset + c * 8)], *v0 = &ot[(size_t)(f.r.fft.otab.offset + (c + nb) * 8)];
                     float *o = &ot2[(size_t)c * 12];
                     for (int q = 0; q < 6; q++) o[q] = u0[q];
                     for (int q = 0; q < 4; q++) o[8 + q] = v0[2 + q];
@@ -268,8 +251,8 @@ void absorb_into_stft(Plan &plan) {
                 if (stft_lds_bytes(probe, 8) > 156 * 1024) continue;
                 d = probe;
                 d.ldc = e.so[0]; d.out_rs = e.so[0]; d.out_cs = 1; d.c_bs = e.bo;
-                f.bias2 = Ref{Space::CONSTS, add_const(plan, ot2), 0};
-                f.out = el.out;
+                f.r.fft.otab = Ref{Space::CONSTS, add_const(plan, ot2), 0};
+                f.r.out = el.r.out;
                 f.name += "+" + el.name;
                 f.weight_bytes += 4.0 * (double)ot2.size() - 4.0 * 8.0 * (double)(2 * nb);
                 f.bytes -= 4.0 * (double)d.frames * (double)nb;  // one value per bin is written instead of two; the cos | sin rows are never read back
@@ -283,29 +266,29 @@ void absorb_into_stft(Plan &plan) {
     bool changed = mel_on;
     while (changed) {
         changed = false;
-        auto users = users_of();
+        const auto users = arena_users(plan);
         for (size_t i = 0; i < plan.ops.size() && !changed; i++) {
             PlanOp &f = plan.ops[i];
-            if (f.kind != OpKind::FFT || f.fft.nmel || f.out.space != Space::ARENA || plan.storages[f.out.id].pinned) continue;
+            if (f.kind != OpKind::FFT || f.fft.nmel || f.r.out.space != Space::ARENA || plan.storages[f.r.out.id].pinned) continue;
             if (f.fft.tpb & (f.fft.tpb - 1)) continue;  // the mel phases index a tile's frames by shifts / 16-frame matrix tiles (M = 5 q banks: tiles of 24)
-            const auto &u = users[f.out.id];
+            const auto &u = users[f.r.out.id];
             if (u.size() != 2 || u[0] != (int)i) continue;
             PlanOp &g = plan.ops[u[1]];
             const GemmDesc &gd = g.gemm;
-            if (g.kind != OpKind::GEMM || g.a.space != Space::ARENA || g.a.id != f.out.id || g.a.offset != f.out.offset) continue;
+            if (g.kind != OpKind::GEMM || g.r.a.space != Space::ARENA || g.r.a.id != f.r.out.id || g.r.a.offset != f.r.out.offset) continue;
             if (gd.fold || gd.has_scale || gd.has_res || gd.rows != f.fft.frames || gd.K != f.fft.nout || gd.lda != gd.K || gd.a_bs != f.fft.c_bs ||
-                f.fft.ldc != f.fft.nout || g.w.space != Space::CONSTS)
+                f.fft.ldc != f.fft.nout || g.r.w.space != Space::CONSTS)
                 continue;
             bool stages_ok = stft_act_supported(gd.act);
             for (int q = 0; q < gd.npost; q++) stages_ok = stages_ok && stft_act_supported(gd.post_act[q]);
             if (!stages_ok) continue;
-            const std::vector<float> &W = plan.consts[g.w.id];  // [N][K]
+            const std::vector<float> &W = plan.consts[g.r.w.id];  // [N][K]
             const int64_t N = gd.N, K = gd.K;
             std::vector<float> mstart, ment;  // row starts; (column, value) pairs
             for (int64_t nn = 0; nn < N; nn++) {
                 mstart.push_back((float)(ment.size() / 2));
                 for (int64_t k = 0; k < K; k++) {
-                    const float v = W[(size_t)(g.w.offset + nn * K + k)];
+                    const float v = W[(size_t)(g.r.w.offset + nn * K + k)];
                     if (v != 0.0f) { ment.push_back((float)k); ment.push_back(v); }
                 }
             }
@@ -339,14 +322,14 @@ void absorb_into_stft(Plan &plan) {
                         for (int64_t i = 0; i < 16 && !any; i++)
                             for (int64_t k = 0; k < 16 && !any; k++) {
                                 const int64_t nn = 16 * t + i, kk = 16 * gq + k;
-                                any = nn < N && kk < K && W[(size_t)(g.w.offset + nn * K + kk)] != 0.0f;
+                                any = nn < N && kk < K && W[(size_t)(g.r.w.offset + nn * K + kk)] != 0.0f;
                             }
                         if (!any) continue;
                         glist.push_back((float)gq);
                         for (int lane = 0; lane < 64; lane++)
                             for (int j = 0; j < 4; j++) {
                                 const int64_t nn = 16 * t + (lane & 15), kk = 16 * gq + 4 * (lane >> 4) + j;
-                                pack.push_back(nn < N && kk < K ? W[(size_t)(g.w.offset + nn * K + kk)] : 0.0f);
+                                pack.push_back(nn < N && kk < K ? W[(size_t)(g.r.w.offset + nn * K + kk)] : 0.0f);
                             }
                     }
                 }
@@ -368,10 +351,10 @@ void absorb_into_stft(Plan &plan) {
             d.c_bs = gd.c_bs;
             if (gd.out_strided) { d.out_rs = gd.out_rs; d.out_cs = gd.out_cs; }
             else { d.out_rs = gd.ldc; d.out_cs = 1; }
-            f.x[0] = Ref{Space::CONSTS, add_const(plan, mstart), 0};
-            f.x[1] = Ref{Space::CONSTS, add_const(plan, ment), 0};
-            f.x[3] = g.bias;
-            f.out = g.out;
+            f.r.mel.start = Ref{Space::CONSTS, add_const(plan, mstart), 0};
+            f.r.mel.entries = Ref{Space::CONSTS, add_const(plan, ment), 0};
+            f.r.mel.bias = g.r.bias;
+            f.r.out = g.r.out;
             f.name += "+" + g.name;
             const double nnz = d.mel_mode == 1 ? 256.0 * (double)d.mel_groups : (double)nnz_count;  // multiply-adds performed per frame
             f.flops_fft += 2.0 * nnz * (double)d.frames;
@@ -388,18 +371,18 @@ void absorb_into_stft(Plan &plan) {
     changed = pre_on;
     while (changed) {
         changed = false;
-        auto users = users_of();
+        const auto users = arena_users(plan);
         for (size_t e = 0; e < plan.ops.size() && !changed; e++) {
             PlanOp &el = plan.ops[e];
             const EltDesc &ed = el.elt;
-            if (el.kind != OpKind::ELT || el.out.space != Space::ARENA || plan.storages[el.out.id].pinned) continue;
-            if (ed.nd != 1 || ed.so[0] != 1 || ed.sa[0] != 1 || el.out.offset != 0) continue;
+            if (el.kind != OpKind::ELT || el.r.out.space != Space::ARENA || plan.storages[el.r.out.id].pinned) continue;
+            if (ed.nd != 1 || ed.so[0] != 1 || ed.sa[0] != 1 || el.r.out.offset != 0) continue;
             bool scalar_ops = true;
             for (int k = 0; k < ed.nstages; k++)
                 scalar_ops = scalar_ops && stft_act_supported(ed.st[k].act) &&
                              (ed.st[k].bin == BIN_NONE || (ed.st[k].sb[0] == 0 && !ed.st[k].bsq && stft_bin_supported(ed.st[k].bin)));
             if (!scalar_ops) continue;
-            const auto &u = users[el.out.id];
+            const auto &u = users[el.r.out.id];
             if (u.size() < 2 || u[0] != (int)e) continue;
             // every reader is a launch that can apply the chain while it loads its span: an STFT, or (round 4) a folded framing GEMM that
             // is certain to run on its LDS-resident kernel (half fold: frame_fold_post_ok; quarter fold: always)
@@ -413,18 +396,14 @@ void absorb_into_stft(Plan &plan) {
             for (size_t q = 1; q < u.size(); q++) {
                 const PlanOp &f = plan.ops[u[q]];
                 const bool stft_ok = f.kind == OpKind::FFT && f.fft.npre == 0 && f.fft.a_bs == ed.bo && (int64_t)(f.fft.frames - 1) * f.fft.hop + f.fft.L <= ed.per_sample;
-                all_fft = all_fft && (stft_ok || framing_gemm(f)) && f.a.space == Space::ARENA && f.a.id == el.out.id && f.a.offset == 0;
+                all_fft = all_fft && (stft_ok || framing_gemm(f)) && f.r.a.space == Space::ARENA && f.r.a.id == el.r.out.id && f.r.a.offset == 0;
                 // (the launch must read the chain's result only through `a`)
-                std::vector<Ref *> refs;
-                all_refs(const_cast<PlanOp &>(f), refs);
-                int reads = 0;
-                for (Ref *r : refs) reads += (r->space == Space::ARENA && r->id == el.out.id) ? 1 : 0;
-                all_fft = all_fft && reads == 1;
+                all_fft = all_fft && refs_to(f, Space::ARENA, el.r.out.id) == 1;
             }
             if (!all_fft) continue;
             for (size_t q = 1; q < u.size(); q++) {
                 PlanOp &f = plan.ops[u[q]];
-                f.a = el.a;
+                f.r.a = el.r.a;
                 if (f.kind == OpKind::FFT) {
                     f.fft.a_bs = ed.ba;
                     f.fft.npre = ed.nstages;
@@ -440,7 +419,7 @@ void absorb_into_stft(Plan &plan) {
                         f.pre.bin[k] = ed.st[k].bin; f.pre.act[k] = ed.st[k].act;
                         f.pre.p0[k] = ed.st[k].p0; f.pre.p1[k] = ed.st[k].p1; f.pre.bb[k] = ed.st[k].bb;
                     }
-                    f.eb[k] = el.eb[k];
+                    f.r.chain[k] = el.r.chain[k];
                 }
                 f.name = el.name + "+" + f.name;
             }
@@ -454,30 +433,26 @@ void absorb_into_stft(Plan &plan) {
     changed = sw_int(sw::BN_STFT_PAD) != 0;
     while (changed) {
         changed = false;
-        auto users = users_of();
+        const auto users = arena_users(plan);
         for (size_t e = 0; e + 2 < plan.ops.size() && !changed; e++) {
             const PlanOp &fill = plan.ops[e], &copy = plan.ops[e + 1];
             if (fill.kind != OpKind::ELT || copy.kind != OpKind::ELT || fill.name.rfind("pad.fill:", 0) != 0 || copy.name.rfind("pad.copy:", 0) != 0) continue;
-            if (fill.out.space != Space::ARENA || copy.out.space != Space::ARENA || fill.out.id != copy.out.id || fill.out.offset != 0 || plan.storages[fill.out.id].pinned) continue;
+            if (fill.r.out.space != Space::ARENA || copy.r.out.space != Space::ARENA || fill.r.out.id != copy.r.out.id || fill.r.out.offset != 0 || plan.storages[fill.r.out.id].pinned) continue;
             const EltDesc &fd = fill.elt, &cd = copy.elt;
             if (fd.nd != 1 || cd.nd != 1 || fd.nstages != 1 || cd.nstages != 1 || cd.so[0] != 1 || cd.sa[0] != 1) continue;
             if (fd.st[0].bin != BIN_NONE || fd.st[0].act != ACT_NONE || cd.st[0].bin != BIN_NONE || cd.st[0].act != ACT_NONE) continue;
-            if (fill.a.space != Space::CONSTS || plan.consts[(size_t)fill.a.id].empty() || plan.consts[(size_t)fill.a.id][(size_t)fill.a.offset] != 0.0f) continue;
-            if (copy.a.space != Space::ARENA && copy.a.space != Space::INPUT) continue;
-            const auto &u = users[fill.out.id];
+            if (fill.r.a.space != Space::CONSTS || plan.consts[(size_t)fill.r.a.id].empty() || plan.consts[(size_t)fill.r.a.id][(size_t)fill.r.a.offset] != 0.0f) continue;
+            if (copy.r.a.space != Space::ARENA && copy.r.a.space != Space::INPUT) continue;
+            const auto &u = users[fill.r.out.id];
             if (u.size() != 3 || u[0] != (int)e || u[1] != (int)e + 1) continue;
             PlanOp &f = plan.ops[(size_t)u[2]];
-            if (f.kind != OpKind::FFT || f.fft.in_len != 0 || f.fft.npre != 0 || f.a.space != Space::ARENA || f.a.id != fill.out.id || f.a.offset != 0) continue;
-            if (f.fft.a_bs != fd.bo || (int64_t)(f.fft.frames - 1) * f.fft.hop + f.fft.L > fd.per_sample || copy.out.offset + cd.per_sample > fd.per_sample) continue;
-            if (cd.per_sample >= ((int64_t)1 << 30) || copy.out.offset >= ((int64_t)1 << 30)) continue;
-            std::vector<Ref *> refs;
-            all_refs(f, refs);
-            int reads = 0;
-            for (Ref *r : refs) reads += (r->space == Space::ARENA && r->id == fill.out.id) ? 1 : 0;
-            if (reads != 1) continue;
-            f.a = copy.a;
+            if (f.kind != OpKind::FFT || f.fft.in_len != 0 || f.fft.npre != 0 || f.r.a.space != Space::ARENA || f.r.a.id != fill.r.out.id || f.r.a.offset != 0) continue;
+            if (f.fft.a_bs != fd.bo || (int64_t)(f.fft.frames - 1) * f.fft.hop + f.fft.L > fd.per_sample || copy.r.out.offset + cd.per_sample > fd.per_sample) continue;
+            if (cd.per_sample >= ((int64_t)1 << 30) || copy.r.out.offset >= ((int64_t)1 << 30)) continue;
+            if (refs_to(f, Space::ARENA, fill.r.out.id) != 1) continue;
+            f.r.a = copy.r.a;
             f.fft.a_bs = cd.ba;
-            f.fft.pad_l = (int32_t)copy.out.offset;
+            f.fft.pad_l = (int32_t)copy.r.out.offset;
             f.fft.in_len = (int32_t)cd.per_sample;
             f.bytes -= 4.0 * (double)(fd.per_sample - cd.per_sample);
             f.name = "pad+" + f.name;
@@ -496,21 +471,15 @@ void fuse_gap_into_gemm(Plan &plan) {
     bool changed = true;
     while (changed) {
         changed = false;
-        std::vector<std::vector<int>> users(plan.storages.size());
-        std::vector<Ref *> refs;
-        for (size_t k = 0; k < plan.ops.size(); k++) {
-            all_refs(plan.ops[k], refs);
-            for (Ref *r : refs)
-                if (r->space == Space::ARENA && (users[r->id].empty() || users[r->id].back() != (int)k)) users[r->id].push_back((int)k);
-        }
+        const auto users = arena_users(plan);
         for (size_t j = 0; j < plan.ops.size() && !changed; j++) {
             PlanOp &red = plan.ops[j];
             const ReduceDesc &r = red.red;
-            if (red.kind != OpKind::REDUCE || r.op != RED_MEAN || r.pair || red.a.space != Space::ARENA || red.out.space != Space::ARENA) continue;
-            const auto &u = users[red.a.id];
-            if (u.size() != 2 || u[1] != (int)j || plan.storages[red.a.id].pinned) continue;
+            if (red.kind != OpKind::REDUCE || r.op != RED_MEAN || r.pair || red.r.a.space != Space::ARENA || red.r.out.space != Space::ARENA) continue;
+            const auto &u = users[red.r.a.id];
+            if (u.size() != 2 || u[1] != (int)j || plan.storages[red.r.a.id].pinned) continue;
             PlanOp &g = plan.ops[u[0]];
-            if (g.kind != OpKind::GEMM || g.out.space != Space::ARENA || g.out.id != red.a.id || g.out.offset != red.a.offset || g.se_fused) continue;
+            if (g.kind != OpKind::GEMM || g.r.out.space != Space::ARENA || g.r.out.id != red.r.a.id || g.r.out.offset != red.r.a.offset || g.se_fused) continue;
             GemmDesc d = g.gemm;
             if (d.gap || !gemm_gap_shape_ok(d) || gemm_dma_shape(d) != 2 || d.ldc != d.N || d.c_bs != d.rows * d.N) continue;
             // the reduction: every channel's mean over the sample's rows, [rows, N] -> [N], dense
@@ -522,11 +491,11 @@ void fuse_gap_into_gemm(Plan &plan) {
                 nrows *= r.rsize[q];
             }
             if (r.nk != 1 || !rows_run || nrows != d.rows || r.ksize[0] != d.N || r.kin[0] != 1 || r.kout[0] != 1 || r.bi != d.c_bs) continue;
-            if (red.out.offset % 4 != 0 || r.bo % 4 != 0) continue;  // (dwordx4 stores)
+            if (red.r.out.offset % 4 != 0 || r.bo % 4 != 0) continue;  // (dwordx4 stores)
             d.gap = 1;
             d.c_bs = r.bo;
             g.gemm = d;
-            g.out = red.out;
+            g.r.out = red.r.out;
             g.name += "+" + red.name;
             g.bytes += red.bytes - 8.0 * (double)d.rows * d.N;  // the [rows, N] tensor never touches memory
             plan.ops.erase(plan.ops.begin() + (long)j);
@@ -542,20 +511,20 @@ void fuse_gap_into_gemm(Plan &plan) {
 void planar_stft_tables(Plan &plan) {
     for (PlanOp &f : plan.ops) {
         FftDesc &d = f.fft;
-        if (f.kind != OpKind::FFT || d.otab_planar || f.bias2.space != Space::CONSTS) continue;
+        if (f.kind != OpKind::FFT || d.otab_planar || f.r.fft.otab.space != Space::CONSTS) continue;
         const int stride = d.otab_stride > 0 ? d.otab_stride : 8;
-        const std::vector<float> &ot = plan.consts[f.bias2.id];
+        const std::vector<float> &ot = plan.consts[f.r.fft.otab.id];
         const int64_t n = d.nout;
-        if ((int64_t)ot.size() < f.bias2.offset + n * stride) continue;
+        if ((int64_t)ot.size() < f.r.fft.otab.offset + n * stride) continue;
         std::vector<float> pl((size_t)(n * (d.power ? 10 : 6)), 0.0f);
         for (int64_t c = 0; c < n; c++) {
-            const float *r = &ot[(size_t)(f.bias2.offset + c * stride)];
+            const float *r = &ot[(size_t)(f.r.fft.otab.offset + c * stride)];
             for (int q = 0; q < 4; q++) pl[(size_t)(c * 4 + q)] = r[q];
             for (int q = 0; q < 2; q++) pl[(size_t)(4 * n + c * 2 + q)] = r[4 + q];
             if (d.power)
                 for (int q = 0; q < 4; q++) pl[(size_t)(6 * n + c * 4 + q)] = r[8 + q];
         }
-        f.bias2 = Ref{Space::CONSTS, add_const(plan, pl), 0};
+        f.r.fft.otab = Ref{Space::CONSTS, add_const(plan, pl), 0};
         d.otab_planar = 1;
     }
 }
@@ -572,9 +541,9 @@ void pair_minmax_reductions(Plan &plan) {
             PlanOp &b = plan.ops[j];
             if (b.kind != OpKind::REDUCE || b.red.pair || b.red.op != RED_MAX) continue;
             const ReduceDesc &x = a.red, &y = b.red;
-            const bool same_in = a.a.space == b.a.space && a.a.id == b.a.id && a.a.offset == b.a.offset;
+            const bool same_in = a.r.a.space == b.r.a.space && a.r.a.id == b.r.a.id && a.r.a.offset == b.r.a.offset;
             const bool chunks = x.nk == 1 && x.nr == 1 && x.rin[0] == 1 && x.kout[0] == 1 && x.red % 4 == 0 && x.kin[0] % 4 == 0 && x.bi % 4 == 0 &&
-                                a.a.offset % 4 == 0 && x.inner_kept == 0;
+                                a.r.a.offset % 4 == 0 && x.inner_kept == 0;
             const bool same_shape = y.nk == 1 && y.nr == 1 && y.rin[0] == 1 && y.kout[0] == 1 && x.ksize[0] == y.ksize[0] && x.kin[0] == y.kin[0] &&
                                     x.red == y.red && x.bi == y.bi && x.kept == y.kept;
             if (!same_in || !chunks || !same_shape) continue;
@@ -582,12 +551,12 @@ void pair_minmax_reductions(Plan &plan) {
             bool clash = false;
             for (size_t k = i + 1; k < j; k++) {
                 const PlanOp &m = plan.ops[k];
-                clash = clash || (m.out.space == a.a.space && m.out.id == a.a.id) || (m.a.space == b.out.space && m.a.id == b.out.id);
+                clash = clash || (m.r.out.space == a.r.a.space && m.r.out.id == a.r.a.id) || (m.r.a.space == b.r.out.space && m.r.a.id == b.r.out.id);
             }
             if (clash) continue;
             a.red.pair = 1;
             a.red.bo2 = y.bo;
-            a.b = b.out;
+            a.r.pair_out = b.r.out;
             a.name += "+" + b.name;
             a.bytes += 4.0 * (double)y.kept;
             plan.ops.erase(plan.ops.begin() + (long)j);
@@ -606,20 +575,14 @@ void absorb_chains_into_gemms(Plan &plan) {
     bool changed = true;
     while (changed) {
         changed = false;
-        std::vector<std::vector<int>> users(plan.storages.size());
-        std::vector<Ref *> refs;
-        for (size_t k = 0; k < plan.ops.size(); k++) {
-            all_refs(plan.ops[k], refs);
-            for (Ref *r : refs)
-                if (r->space == Space::ARENA && (users[r->id].empty() || users[r->id].back() != (int)k)) users[r->id].push_back((int)k);
-        }
+        const auto users = arena_users(plan);
         for (size_t j = 0; j < plan.ops.size() && !changed; j++) {
             PlanOp &cons = plan.ops[j];
-            if (cons.kind != OpKind::ELT || cons.a.space != Space::ARENA || cons.out.space != Space::ARENA) continue;
-            const auto &u = users[cons.a.id];
-            if (u.size() != 2 || u[1] != (int)j || plan.storages[cons.a.id].pinned) continue;
+            if (cons.kind != OpKind::ELT || cons.r.a.space != Space::ARENA || cons.r.out.space != Space::ARENA) continue;
+            const auto &u = users[cons.r.a.id];
+            if (u.size() != 2 || u[1] != (int)j || plan.storages[cons.r.a.id].pinned) continue;
             PlanOp &prod = plan.ops[u[0]];
-            if (prod.kind != OpKind::GEMM || prod.out.space != Space::ARENA || prod.out.id != cons.a.id) continue;
+            if (prod.kind != OpKind::GEMM || prod.r.out.space != Space::ARENA || prod.r.out.id != cons.r.a.id) continue;
             GemmDesc g = prod.gemm;
             const EltDesc &ce = cons.elt;
             // (round 4: the LDS-resident folded framing GEMM carries a chain of the compact stage functions and the consumer's view too)
@@ -633,7 +596,7 @@ void absorb_chains_into_gemms(Plan &plan) {
             }
             if (!unary || npost > 4 || ce.per_sample != g.rows * g.N || (fold_post && !compact)) continue;
             // the chain's index space must be (a signed permutation of) rows x N
-            int64_t rs = 0, cs = 0, base = cons.out.offset, want_delta = 0;
+            int64_t rs = 0, cs = 0, base = cons.r.out.offset, want_delta = 0;
             bool ok = true, have_row = g.rows == 1, have_col = g.N == 1;
             for (int k = 0; k < ce.nd && ok; k++) {
                 if (ce.size[k] == 1) continue;
@@ -649,7 +612,7 @@ void absorb_chains_into_gemms(Plan &plan) {
                 if (sa > 0) *dst = ce.so[k];
                 else { *dst = -ce.so[k]; base += (ce.size[k] - 1) * ce.so[k]; want_delta += (ce.size[k] - 1) * mag; }
             }
-            if (!ok || !have_row || !have_col || cons.a.offset - prod.out.offset != want_delta) continue;
+            if (!ok || !have_row || !have_col || cons.r.a.offset - prod.r.out.offset != want_delta) continue;
             g.out_strided = 1;
             g.out_rs = rs; g.out_cs = cs;
             g.c_bs = ce.bo;
@@ -660,7 +623,7 @@ void absorb_chains_into_gemms(Plan &plan) {
                     g.npost++;
                 }
             prod.gemm = g;
-            prod.out = Ref{cons.out.space, cons.out.id, base};
+            prod.r.out = Ref{cons.r.out.space, cons.r.out.id, base};
             prod.name += "+" + cons.name;
             prod.bytes += cons.bytes - 8.0 * (double)ce.per_sample;  // the dense intermediate never touches memory
             plan.ops.erase(plan.ops.begin() + j);
@@ -674,25 +637,18 @@ void absorb_chains_into_gemms(Plan &plan) {
 // the launch then runs on the bf16 matrix pipe with f32-complete products (gemm_dma3.hip).  Last pass over the descriptors: gate, pooled
 // epilogue, inline squeeze-excite are all decided.  The f32 copy goes away with it when no other launch reads it.
 void pack_bf16x3_weights(Plan &plan) {
-    auto refs_of = [](PlanOp &op) {
-        std::vector<Ref *> r = {&op.a, &op.b, &op.w, &op.bias, &op.res, &op.scale, &op.w2, &op.bias2};
-        for (auto &e : op.eb) r.push_back(&e);
-        for (auto &e : op.x) r.push_back(&e);
-        return r;
-    };
     for (auto &op : plan.ops) {
-        if (op.kind != OpKind::GEMM || op.gemm.fold || op.gemm.w3 || op.w.space != Space::CONSTS) continue;
+        if (op.kind != OpKind::GEMM || op.gemm.fold || op.gemm.w3 || op.r.w.space != Space::CONSTS) continue;
         if (!gemm_b3_shape_ok(op.gemm) && !gemm_dma3_wanted(op.gemm)) continue;
         const int64_t N = op.gemm.N, K = op.gemm.K;
-        if ((int64_t)plan.consts[(size_t)op.w.id].size() < op.w.offset + N * K) continue;
+        if ((int64_t)plan.consts[(size_t)op.r.w.id].size() < op.r.w.offset + N * K) continue;
         // BN_GEMM3: 0 = exact-f32 kernel, 1 = the LDS-DMA form everywhere, 2 (default) = the register-staged form wherever it applies
         const bool b3 = gemm_b3_shape_ok(op.gemm);
-        std::vector<float> img = b3 ? pack_w3f(plan.consts[(size_t)op.w.id].data() + op.w.offset, N, K) : pack_w3(plan.consts[(size_t)op.w.id].data() + op.w.offset, N, K);
+        std::vector<float> img = b3 ? pack_w3f(plan.consts[(size_t)op.r.w.id].data() + op.r.w.offset, N, K) : pack_w3(plan.consts[(size_t)op.r.w.id].data() + op.r.w.offset, N, K);
         int users = 0;
-        for (auto &o2 : plan.ops)
-            for (Ref *r : refs_of(o2)) users += r->space == Space::CONSTS && r->id == op.w.id;
-        if (users == 1 && op.w.offset == 0) plan.consts[(size_t)op.w.id] = std::move(img);
-        else op.w = Ref{Space::CONSTS, add_const(plan, img), 0};
+        for (const auto &o2 : plan.ops) users += refs_to(o2, Space::CONSTS, op.r.w.id);
+        if (users == 1 && op.r.w.offset == 0) plan.consts[(size_t)op.r.w.id] = std::move(img);
+        else op.r.w = Ref{Space::CONSTS, add_const(plan, img), 0};
         op.gemm.w3 = b3 ? 2 : 1;
         op.weight_bytes += 2.0 * (double)N * (double)((K + 31) / 32 * 32) + 4.0 * (double)N * (double)((K + 31) / 32 * 32 - K);  // 6 bytes per (padded) weight instead of 4
     }

@@ -20,7 +20,11 @@ using namespace bn;
 #define IA(d, f) do { printf(" " #f "="); for (auto v_ : (d).f) printf("%lld,", (long long)v_); } while (0)
 #define XA(d, f) do { printf(" " #f "="); for (auto v_ : (d).f) printf("%a,", (double)v_); } while (0)
 
-static void ref(const char *name, const Ref &r) { printf(" %s=%d:%d:%lld", name, (int)r.space, (int)r.id, (long long)r.offset); }
+static int refs_printed;  // ... that were not NONE, per launch
+static void ref(const char *name, const Ref &r) {
+    printf(" %s=%d:%d:%lld", name, (int)r.space, (int)r.id, (long long)r.offset);
+    refs_printed += r.space != Space::NONE;
+}
 
 static void print(const EltDesc &d) {
     printf("\n    elt:"); I(d, nd); IA(d, size); IA(d, so); IA(d, sa); I(d, bo); I(d, ba); I(d, per_sample); I(d, nstages);
@@ -69,10 +73,27 @@ static void print(const FftDesc &d) {
 static void print(const PlanOp &op, size_t k) {
     static const char *kinds[] = {"ELT", "REDUCE", "GEMM", "CONV", "DWCONV", "GAP", "SEFC", "MBCONV", "POOL", "FFT"};
     printf("op %zu %s '%s'\n   ", k, kinds[(int)op.kind], op.name.c_str());
-    ref("out", op.out); ref("a", op.a); ref("b", op.b); ref("w", op.w); ref("bias", op.bias); ref("res", op.res); ref("scale", op.scale);
-    ref("w2", op.w2); ref("bias2", op.bias2);
-    for (const Ref &r : op.eb) ref("eb", r);
-    for (const Ref &r : op.x) ref("x", r);
+    // The operands print in the nine generic slots, the chain ("eb") and the four extras ("x") the plan had before its fields were named, so
+    // that digests compare across that change: per kind, the named field that lived in each slot; a slot the kind left empty prints NONE.
+    const PlanOp::Operands &r = op.r;
+    const Ref none;
+    refs_printed = 0;
+    const bool gemm = op.kind == OpKind::GEMM, fft = op.kind == OpKind::FFT, two = op.kind == OpKind::MBCONV || op.kind == OpKind::SEFC;
+    const bool tail = op.se_fused && (op.kind == OpKind::DWCONV || op.kind == OpKind::MBCONV), inl = op.se_fused && gemm;
+    ref("out", r.out); ref("a", r.a);
+    ref("b", op.kind == OpKind::REDUCE ? r.pair_out : op.kind == OpKind::SEFC ? r.hidden : gemm ? r.se.partial : r.gap_out);
+    ref("w", fft ? r.fft.window : r.w); ref("bias", r.bias);
+    ref("res", tail ? r.se.gate : r.residual); ref("scale", tail ? r.se.counter : r.gate);
+    ref("w2", two ? r.w2 : fft ? r.fft.twiddles : gemm ? r.fold2.tables : none);
+    ref("bias2", two ? r.bias2 : fft ? r.fft.otab : gemm ? r.fold2.colmap : none);
+    for (const Ref &e : r.chain) ref("eb", e);
+    const Ref *x[4] = {&none, &none, &none, &none};
+    if (tail || inl) { x[0] = &r.se.w1; x[1] = &r.se.b1; x[2] = &r.se.w2t; x[3] = &r.se.b2; }
+    if (fft) { x[0] = &r.mel.start; x[1] = &r.mel.entries; x[3] = &r.mel.bias; }
+    for (const Ref *e : x) ref("x", *e);
+    int set = 0;  // a field set where its kind has no slot for it must not go unseen
+    for_each_ref(r, [&](const Ref &e) { set += e.space != Space::NONE; });
+    if (set != refs_printed) printf(" UNPRINTED=%d", set - refs_printed);
     switch (op.kind) {
         case OpKind::ELT: print(op.elt); break;
         case OpKind::REDUCE: print(op.red); break;
