@@ -54,6 +54,9 @@ tools/asan_index_copy_plan: tools/asan_index_copy_plan.cpp $(SRC)/index_copy_pla
 	$(CXX) $(ASAN_FLAGS) $< -o $@
 tools/asan_seq_plan: tools/asan_seq_plan.cpp $(SRC)/seq_plan.h $(SRC)/last_error.h
 	$(CXX) $(ASAN_FLAGS) $< -o $@
+# ... of the frame and byte arithmetic of the PCM layouts (offsets, upload chunks cut at frame boundaries, overflow refusals)
+tools/asan_pcm_layout: tools/asan_pcm_layout.cpp $(SRC)/pcm_layout.h include/birdnet_hip.h
+	$(CXX) $(ASAN_FLAGS) $< -o $@
 # ... and of the operands of finished plans: the planner's own files, as tools/asan_plan.cpp links them
 PLANNER_SRC := $(SRC)/onnx_proto.cpp $(SRC)/engine.cpp $(SRC)/onnx_rewrite.cpp $(SRC)/dft_bank.cpp $(SRC)/plan_passes.cpp $(SRC)/detect.cpp
 tools/asan_plan_operands: tools/asan_plan_operands.cpp $(PLANNER_SRC) $(wildcard $(SRC)/*.h)

@@ -341,7 +341,8 @@ bn_status bn_recording_create_resampled(int32_t device, const void *pcm, size_t 
  * returns L*T; *L_out, *M_out, *T_out receive the factors.  Needs no device. */
 size_t bn_resample_table(uint32_t src_rate, uint32_t dst_rate, uint32_t zero_crossings, float *table, size_t cap,
                          uint32_t *L_out, uint32_t *M_out, uint32_t *T_out);
-/* Copy samples [first, first+count) of an f32 recording back to the host (tests, diagnostics). */
+/* Copy samples [first, first+count) of an f32 recording back to the host (tests, diagnostics).  A recording created with a
+ * layout (below) is read in any format: frames [first, first+count) as the f32 samples the layout rule defines. */
 bn_status bn_recording_read_f32(const bn_recording *r, size_t first, size_t count, float *host_out);
 void bn_recording_free(bn_recording *r);
 size_t bn_recording_samples(const bn_recording *r);
@@ -365,6 +366,65 @@ bn_status bn_infer_windows(bn_ctx *c, const bn_recording *r, size_t step_samples
  * (src/bin/birdnet-analyze.rs:556-600) with several contexts in flight. */
 bn_status bn_step_windows(bn_ctx *c, const bn_recording *r, size_t step_samples, size_t first_window,
                           size_t count, size_t top_k, int32_t has_min, float min_conf, int32_t sync);
+
+/*
+ * PCM layouts: interleaved multi-channel and 8/24/32-bit PCM, converted ON THE DEVICE.  Field recorders and sound cards
+ * deliver stereo or 4-channel frames, very often 24-bit packed; with a layout such bytes are uploaded ONCE as they are and
+ * every consumer reads them through one rule.  No reference counterpart (the reference CLI takes mono int16 only).
+ *
+ * A layout is {format, channels, channel}.  PCM is interleaved frames of `channels` samples each, little-endian.  Every
+ * count of the API is in FRAMES: a layout recording of n_frames frames has bn_recording_samples() == n_frames, a push of
+ * n_samples to a layout pool carries n_samples frames.
+ *
+ *   format           storage                           f32 sample
+ *   BN_PCM_I16 (0)   int16                             v / 32768 (exact)
+ *   BN_PCM_F32 (1)   float                             as is (bits preserved, NaN payloads included)
+ *   BN_PCM_I24 (2)   3 packed bytes, two's complement  sign-extended, v / 8388608 (exact)
+ *   BN_PCM_I32 (3)   int32                             (float)v rounded to nearest even, then * 2^-31 (exact scale)
+ *   BN_PCM_U8  (4)   uint8                             (v - 128) / 128 (exact)
+ *
+ * channels is 1..16.  channel >= 0 selects that channel of every frame (a value >= channels is refused).  channel ==
+ * BN_PCM_MIX mixes the frame down: acc = s[0]; acc = acc + s[c] in f32 for c = 1, 2, ... ascending; result = acc * inv with
+ * inv = 1.0f / (float)channels rounded once.  No fused multiply-add anywhere in the rule.  With channels == 1 both ops are
+ * the identity, and for I16 and F32 the result is bit-identical to the mono entry points above.
+ *
+ * The invariant: every consumer of a layout recording or pool -- bn_recording_windows, bn_infer_windows, bn_step_windows,
+ * bn_recording_read_f32, the resampler, bn_live_push / bn_live_push_many / bn_live_read_window / bn_step_live -- sees exactly
+ * the f32 sample the rule defines, so any path over a layout input is BIT-FOR-BIT equal to the same path over a BN_PCM_F32
+ * mono input holding the rule's samples (the resampler's FIR arithmetic after the load is the same code).  The tail past
+ * n_frames reads 0, as chunk_audio pads.
+ *
+ * struct_size is sizeof(bn_pcm_layout) as the caller compiled it.  BN_ERR_INVALID_ARG, with a message, and no handle written:
+ * an unknown format, channels outside 1..16, channel outside [-1, channels), a NULL layout, a struct_size below the struct's.
+ *
+ * bn_recording_create_layout_async uploads in chunks (BN_UPLOAD_CHUNK_MB) cut at FRAME boundaries, and otherwise behaves as
+ * bn_recording_create_async.  bn_recording_create_layout_resampled converts during its synchronous upload as
+ * bn_recording_create_resampled does; its result is mono f32 at dst_rate.
+ *
+ * bn_recording_view_channel: a second recording over the SAME device bytes with another channel op -- no second upload; use
+ * it to analyse both channels of a stereo file.  Either recording may be freed first (an asynchronous upload is joined when
+ * the last of them goes).  The channel is checked against the recording's own layout; a resampled recording has no
+ * storage-format bytes left -- it is mono f32 -- and accepts only channel 0 or BN_PCM_MIX.
+ *
+ * Mono only, as before: bn_group_analyze_recording; WAV headers are the caller's to parse.
+ */
+#define BN_PCM_I24 2 /* 3 packed bytes, little-endian two's complement, value / 8388608.0 */
+#define BN_PCM_I32 3 /* int32_t, (float)value * 2^-31 */
+#define BN_PCM_U8 4  /* uint8_t, (value - 128) / 128.0 */
+#define BN_PCM_MIX (-1)
+typedef struct bn_pcm_layout {
+    int32_t format;    /* BN_PCM_* */
+    uint32_t channels; /* samples per frame, 1..16 */
+    int32_t channel;   /* the channel to select, or BN_PCM_MIX */
+} bn_pcm_layout;
+bn_status bn_recording_create_layout(int32_t device, const void *pcm, size_t n_frames, const bn_pcm_layout *layout,
+                                     size_t struct_size, bn_recording **out);
+bn_status bn_recording_create_layout_async(int32_t device, const void *pcm, size_t n_frames, const bn_pcm_layout *layout,
+                                           size_t struct_size, bn_recording **out);
+bn_status bn_recording_create_layout_resampled(int32_t device, const void *pcm, size_t n_frames, const bn_pcm_layout *layout,
+                                               size_t struct_size, uint32_t src_rate, uint32_t dst_rate,
+                                               uint32_t zero_crossings, bn_recording **out);
+bn_status bn_recording_view_channel(const bn_recording *r, int32_t channel, bn_recording **out);
 
 /* Device view of the packed top-K rows of the last bn_step_device / bn_step_windows on this context:
  * [idx: m*k][conf: m*k (float bits)][count: m] for the m rows and k = min(top_k, num_species) of that step.
@@ -1451,6 +1511,14 @@ bn_status bn_live_create(int32_t device, int32_t n_sources, int32_t format, size
                          size_t ring_samples, bn_live **out);
 /* a resampling pool: source s delivers `format` PCM at src_rates[s] (> 0), the windows are cut at dst_rate (> 0);
  * zero_crossings as bn_recording_create_resampled (0 => 16).  One table per distinct rate of the pool. */
+/* A pool whose pushes carry a PCM layout ("PCM layouts" above): one layout per pool, n_samples of a push counts FRAMES, every
+ * window is bit-identical to the mono f32 pool fed the layout rule's samples.  src_rates == NULL: no resampling (dst_rate and
+ * zero_crossings are ignored); else one rate per source, as bn_live_create_rates.  Mono int16 / float pushes are stored as they
+ * are; for any other layout the ring holds f32 and the scatter converts the frames as they land.  Refusals as
+ * bn_recording_create_layout, and those of bn_live_create / bn_live_create_rates. */
+bn_status bn_live_create_layout(int32_t device, int32_t n_sources, const bn_pcm_layout *layout, size_t struct_size,
+                                size_t segment_samples, size_t step_samples, size_t ring_samples, uint32_t dst_rate,
+                                const uint32_t *src_rates, uint32_t zero_crossings, bn_live **out);
 bn_status bn_live_create_rates(int32_t device, int32_t n_sources, int32_t format, size_t segment_samples, size_t step_samples,
                                size_t ring_samples, uint32_t dst_rate, const uint32_t *src_rates, uint32_t zero_crossings,
                                bn_live **out);

@@ -206,6 +206,11 @@ class Recording {
     Recording(const void *pcm, size_t n_samples, int32_t format, int device = 0);
     static Recording from_i16(const int16_t *pcm, size_t n_samples, int device = 0) { return Recording(pcm, n_samples, BN_PCM_I16, device); }
     static Recording from_f32(const float *pcm, size_t n_samples, int device = 0) { return Recording(pcm, n_samples, BN_PCM_F32, device); }
+    /* interleaved frames in any format (birdnet_hip.h, "PCM layouts"): n_frames frames of layout.channels samples, read as the
+     * layout's channel or mix on the device; n_samples() counts frames */
+    Recording(const void *pcm, size_t n_frames, const bn_pcm_layout &layout, int device = 0);
+    /* the same device bytes read with another channel op (bn_recording_view_channel): no second upload */
+    Recording view_channel(int32_t channel) const;
     size_t n_samples() const { return n_samples_; }
     const bn_recording *raw() const { return rec_.get(); }
 
@@ -277,6 +282,10 @@ class LiveSources {
      * predict_live's start times stay in the classifier's rate; push and room count source samples. */
     LiveSources(const Classifier &cl, const std::vector<uint32_t> &source_rates, int32_t format, float overlap_secs = 0.0f, size_t ring_samples = 0,
                 int device = -1, uint32_t zero_crossings = 0);
+    /* a pool whose pushes carry interleaved frames in any format (bn_live_create_layout); source_rates empty: n_sources sources at
+     * the classifier's rate, else one rate per source as above.  push and room count frames. */
+    LiveSources(const Classifier &cl, int32_t n_sources, const bn_pcm_layout &layout, const std::vector<uint32_t> &source_rates = {},
+                float overlap_secs = 0.0f, size_t ring_samples = 0, int device = -1, uint32_t zero_crossings = 0);
     void push(int32_t source, const void *pcm, size_t n_samples);
     void close(int32_t source);
     void reset(int32_t source);
@@ -286,8 +295,8 @@ class LiveSources {
     bn_live *raw() const { return live_.get(); }
 
    private:
-    void create(const Classifier &cl, int32_t n_sources, const uint32_t *source_rates, int32_t format, float overlap_secs, size_t ring_samples, int device,
-                uint32_t zero_crossings);
+    void create(const Classifier &cl, int32_t n_sources, const uint32_t *source_rates, const bn_pcm_layout *layout, int32_t format, float overlap_secs,
+                size_t ring_samples, int device, uint32_t zero_crossings);
     std::shared_ptr<bn_live> live_;
     size_t step_ = 0;
 };
@@ -463,6 +472,10 @@ size_t bnh_context_read_output(const bnh_context *ctx, int32_t index, size_t bat
 int32_t bnh_predict_recording(const bnh_classifier *c, bnh_context *ctx, const void *pcm, size_t n_samples, int32_t format, float overlap_secs,
                               size_t first_chunk, size_t count, int64_t timeout_ns, const volatile int32_t *cancel, bnh_results **out,
                               float *start_times, size_t times_cap, bnh_error *err);
+/* the same over interleaved frames in any format: format / channels / channel are a bn_pcm_layout's fields */
+int32_t bnh_predict_recording_layout(const bnh_classifier *c, bnh_context *ctx, const void *pcm, size_t n_frames, int32_t format, uint32_t channels,
+                                     int32_t channel, float overlap_secs, size_t first_chunk, size_t count, int64_t timeout_ns,
+                                     const volatile int32_t *cancel, bnh_results **out, float *start_times, size_t times_cap, bnh_error *err);
 /* LiveSources + Classifier::predict_live.  source_out / chunk_out / start_times receive row i's provenance for i < cap. */
 typedef struct bnh_live bnh_live;
 /* device < 0 => the classifier's device */
@@ -471,6 +484,10 @@ int32_t bnh_live_create(const bnh_classifier *c, int32_t n_sources, int32_t form
 /* the resampling pool: source_rates [n_sources] in Hz, converted to the classifier's sample rate on the device */
 int32_t bnh_live_create_rates(const bnh_classifier *c, int32_t n_sources, const uint32_t *source_rates, int32_t format, float overlap_secs,
                               size_t ring_samples, int32_t device, uint32_t zero_crossings, bnh_live **out, bnh_error *err);
+/* the layout pool: pushes carry frames of `channels` samples in `format`; source_rates NULL => every source at the classifier's rate */
+int32_t bnh_live_create_layout(const bnh_classifier *c, int32_t n_sources, int32_t format, uint32_t channels, int32_t channel,
+                               const uint32_t *source_rates, float overlap_secs, size_t ring_samples, int32_t device, uint32_t zero_crossings,
+                               bnh_live **out, bnh_error *err);
 void bnh_live_free(bnh_live *l);
 int32_t bnh_live_push(bnh_live *l, int32_t source, const void *pcm, size_t n_samples, bnh_error *err);
 int32_t bnh_live_close(bnh_live *l, int32_t source, bnh_error *err);

@@ -40,6 +40,9 @@ LIB_PATH = os.environ.get("BN_LIB") or os.path.join(_HERE, "libbirdnet_hip.so") 
 BN_MAX_OUTPUTS, BN_MAX_RANK, BN_NAME_LEN = 8, 6, 64
 BN_CTX_DEFAULT, BN_CTX_ALL_OUTPUTS, BN_CTX_NO_GRAPH = 0, 1, 2
 BN_PCM_I16, BN_PCM_F32 = 0, 1
+BN_PCM_I24, BN_PCM_I32, BN_PCM_U8 = 2, 3, 4  # layout entry points only (include/birdnet_hip.h, "PCM layouts")
+BN_PCM_MIX = -1  # bn_pcm_layout.channel: mix the frame down
+PCM_SAMPLE_BYTES = {BN_PCM_I16: 2, BN_PCM_F32: 4, BN_PCM_I24: 3, BN_PCM_I32: 4, BN_PCM_U8: 1}
 BN_ERR_MODEL_LOAD, BN_ERR_UNSUPPORTED_MODEL, BN_ERR_MODEL_DETECTION, BN_ERR_NO_DEVICE = 6, 7, 8, 9  # bn_status values the harness names
 
 # every symbol include/birdnet_hip.h and include/birdnet_host.h declare
@@ -52,6 +55,7 @@ ENGINE_SYMBOLS = [
     "bn_recording_create", "bn_recording_create_async", "bn_recording_wait", "bn_recording_free", "bn_recording_samples", "bn_chunk_count", "bn_recording_windows",
     "bn_infer_windows", "bn_step_windows", "bn_ctx_step_device_rows", "bn_group_create", "bn_group_destroy", "bn_group_size",
     "bn_group_uses_rccl", "bn_group_get_stats", "bn_shard_range", "bn_group_analyze_recording", "bn_group_last_error", "bn_recording_create_resampled", "bn_resample_table", "bn_recording_read_f32", "bn_last_error",
+    "bn_recording_create_layout", "bn_recording_create_layout_async", "bn_recording_create_layout_resampled", "bn_recording_view_channel", "bn_live_create_layout",
     "bn_index_create", "bn_index_free", "bn_index_size", "bn_index_dim", "bn_index_add_host", "bn_index_add_ctx", "bn_index_read",
     "bn_index_search", "bn_index_search_ids", "bn_index_assign", "bn_index_cluster",
     "bn_index_save", "bn_index_load", "bn_index_file_info", "bn_index_file_verify",
@@ -88,7 +92,7 @@ HOST_SYMBOLS = [
     "bnh_range_filter_predict", "bnh_range_filter_label", "bnh_filter_predictions",
     "bnh_range_filter_scores", "bnh_range_filter_prior_row", "bnh_prior_create", "bnh_prior_free", "bnh_prior_handle",
     "bnh_context_attach_prior", "bnh_context_set_prior_site", "bnh_context_prior_results",
-    "bnh_live_create", "bnh_live_create_rates", "bnh_live_free", "bnh_live_push", "bnh_live_close", "bnh_live_ready", "bnh_predict_live",
+    "bnh_live_create", "bnh_live_create_rates", "bnh_live_create_layout", "bnh_predict_recording_layout", "bnh_live_free", "bnh_live_push", "bnh_live_close", "bnh_live_ready", "bnh_predict_live",
 ]
 
 
@@ -140,6 +144,10 @@ class BnClusterReport(C.Structure):
 class BnIndexFileInfo(C.Structure):
     _fields_ = [("rows", C.c_uint64), ("valid_rows", C.c_uint64), ("dim", C.c_uint32), ("chunk_rows", C.c_uint32), ("n_chunks", C.c_uint32),
                 ("version", C.c_uint32)]
+
+
+class BnPcmLayout(C.Structure):
+    _fields_ = [("format", C.c_int32), ("channels", C.c_uint32), ("channel", C.c_int32)]
 
 
 class BnIndexFilter(C.Structure):
@@ -232,6 +240,10 @@ def _load() -> C.CDLL:
         "bn_recording_create_resampled": (i32, [i32, vp, sz, i32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(vp)]),
         "bn_resample_table": (sz, [C.c_uint32, C.c_uint32, C.c_uint32, f32p, sz, u32p, u32p, u32p]),
         "bn_recording_read_f32": (i32, [vp, sz, sz, f32p]),
+        "bn_recording_create_layout": (i32, [i32, vp, sz, C.POINTER(BnPcmLayout), sz, C.POINTER(vp)]),
+        "bn_recording_create_layout_async": (i32, [i32, vp, sz, C.POINTER(BnPcmLayout), sz, C.POINTER(vp)]),
+        "bn_recording_create_layout_resampled": (i32, [i32, vp, sz, C.POINTER(BnPcmLayout), sz, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(vp)]),
+        "bn_recording_view_channel": (i32, [vp, i32, C.POINTER(vp)]),
         "bn_last_error": (sz, [C.c_char_p, sz]),
         "bn_ctx_step_device_rows": (i32, [vp, C.POINTER(u32p)]),
         "bn_group_create": (i32, [C.POINTER(vp), C.POINTER(C.c_int32), i32, sz, i32, C.POINTER(vp)]),
@@ -337,6 +349,7 @@ def _load() -> C.CDLL:
         "bn_step_track_results": (i32, [vp, C.POINTER(C.POINTER(BnEvent)), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]),
         "bn_live_create": (i32, [i32, i32, i32, sz, sz, sz, C.POINTER(vp)]),
         "bn_live_create_rates": (i32, [i32, i32, i32, sz, sz, sz, C.c_uint32, u32p, C.c_uint32, C.POINTER(vp)]),
+        "bn_live_create_layout": (i32, [i32, i32, C.POINTER(BnPcmLayout), sz, sz, sz, sz, C.c_uint32, u32p, C.c_uint32, C.POINTER(vp)]),
         "bn_live_resampled_samples": (sz, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, i32]),
         "bn_live_source_rate": (C.c_uint32, [vp, i32]),
         "bn_live_free": (None, [vp]),
@@ -373,6 +386,8 @@ def _load() -> C.CDLL:
                                                  C.POINTER(C.c_int32), C.POINTER(vp), C.POINTER(BnhError)]),
         "bnh_predict_recording": (i32, [vp, vp, vp, sz, i32, C.c_float, sz, sz, C.c_int64, C.POINTER(C.c_int32), C.POINTER(vp),
                                         f32p, sz, C.POINTER(BnhError)]),
+        "bnh_predict_recording_layout": (i32, [vp, vp, vp, sz, i32, C.c_uint32, i32, C.c_float, sz, sz, C.c_int64, C.POINTER(C.c_int32), C.POINTER(vp),
+                                               f32p, sz, C.POINTER(BnhError)]),
         "bnh_parse_labels_format": (sz, [C.c_char_p, i32, C.c_char_p, sz, C.POINTER(BnhError)]),
         "bnh_calculate_week": (C.c_float, [C.c_uint32, C.c_uint32]),
         "bnh_validate_coordinates": (i32, [C.c_float, C.c_float, C.POINTER(BnhError)]),
@@ -392,6 +407,7 @@ def _load() -> C.CDLL:
         "bnh_filter_predictions": (sz, [C.POINTER(C.c_char_p), f32p, sz, C.POINTER(C.c_char_p), f32p, sz, C.c_float, i32, u32p, f32p]),
         "bnh_live_create": (i32, [vp, i32, i32, C.c_float, sz, i32, C.POINTER(vp), C.POINTER(BnhError)]),
         "bnh_live_create_rates": (i32, [vp, i32, u32p, i32, C.c_float, sz, i32, C.c_uint32, C.POINTER(vp), C.POINTER(BnhError)]),
+        "bnh_live_create_layout": (i32, [vp, i32, i32, C.c_uint32, i32, u32p, C.c_float, sz, i32, C.c_uint32, C.POINTER(vp), C.POINTER(BnhError)]),
         "bnh_live_free": (None, [vp]),
         "bnh_live_push": (i32, [vp, i32, vp, sz, C.POINTER(BnhError)]),
         "bnh_live_close": (i32, [vp, i32, C.POINTER(BnhError)]),
@@ -1211,6 +1227,49 @@ class Recording:
         self.n_samples = int(lib.bn_recording_samples(h))
         if async_upload:
             _pending_uploads.add(self)  # joined at interpreter exit: the uploader thread must not outlive the array it reads
+
+    @classmethod
+    def _adopt(cls, h, keep=None, pending=False):
+        r = cls.__new__(cls)
+        r._h, r._keep = h, keep
+        r.n_samples = int(lib.bn_recording_samples(h))
+        if pending:
+            _pending_uploads.add(r)
+        return r
+
+    @classmethod
+    def from_layout(cls, pcm, fmt: int, channels: int = 1, channel: int = 0, device: int = 0, async_upload: bool = False,
+                    src_rate: Optional[int] = None, dst_rate: Optional[int] = None, zero_crossings: int = 0) -> "Recording":
+        """bn_recording_create_layout[_async | _resampled]: `pcm` holds interleaved frames of `channels` samples in format `fmt`
+        (BN_PCM_*; bytes or any contiguous array -- packed 24-bit has no dtype of its own), read on the device as channel
+        `channel` or, at BN_PCM_MIX, mixed down.  n_samples counts frames."""
+        a = np.frombuffer(pcm, dtype=np.uint8) if isinstance(pcm, (bytes, bytearray, memoryview)) else np.ascontiguousarray(pcm).reshape(-1).view(np.uint8)
+        fb = PCM_SAMPLE_BYTES.get(fmt, 1) * max(int(channels), 1)
+        if a.shape[0] % fb:
+            raise ValueError(f"{a.shape[0]} bytes are no whole number of {fb}-byte frames")
+        n = a.shape[0] // fb
+        lay = BnPcmLayout(fmt, channels, channel)
+        h = C.c_void_p()
+        if async_upload and src_rate and dst_rate:
+            raise ValueError("async_upload cannot be combined with resampling")
+        if src_rate and dst_rate:
+            st = lib.bn_recording_create_layout_resampled(device, a.ctypes.data_as(C.c_void_p), n, C.byref(lay), C.sizeof(lay), src_rate, dst_rate, zero_crossings, C.byref(h))
+        elif async_upload:
+            st = lib.bn_recording_create_layout_async(device, a.ctypes.data_as(C.c_void_p), n, C.byref(lay), C.sizeof(lay), C.byref(h))
+        else:
+            st = lib.bn_recording_create_layout(device, a.ctypes.data_as(C.c_void_p), n, C.byref(lay), C.sizeof(lay), C.byref(h))
+        if st:
+            raise EngineError(st)
+        return cls._adopt(h, a if async_upload else None, async_upload)
+
+    def view_channel(self, channel: int) -> "Recording":
+        """bn_recording_view_channel: the same device bytes read with another channel op; no second upload.  Either may go first."""
+        h = C.c_void_p()
+        st = lib.bn_recording_view_channel(self._h, channel, C.byref(h))
+        if st:
+            raise EngineError(st)
+        keep = getattr(self, "_keep", None)
+        return Recording._adopt(h, keep, keep is not None)  # a view shares the upload: it keeps the source array alive as well
 
     def wait(self):
         """The whole recording is on the device (no-op for a synchronous upload)."""
@@ -2135,11 +2194,25 @@ class Live:
     Context.step_live batches the ready windows of all sources, cut on the device (chunk_audio per source)."""
 
     def __init__(self, device: int, n_sources: int, segment_samples: int, step_samples: int, ring_samples: int, fmt: int = BN_PCM_I16,
-                 dst_rate: Optional[int] = None, src_rates=None, zero_crossings: int = 0):
+                 dst_rate: Optional[int] = None, src_rates=None, zero_crossings: int = 0, layout=None):
         """dst_rate and src_rates (one rate in Hz per source) given: a resampling pool (bn_live_create_rates) -- pushes arrive at
-        the sources' own rates and are converted to dst_rate on the device; segment / step / ring stay in dst_rate samples."""
+        the sources' own rates and are converted to dst_rate on the device; segment / step / ring stay in dst_rate samples.
+        layout = (format, channels, channel): bn_live_create_layout -- pushes are interleaved frames (bytes or any contiguous
+        array) and count frames; with or without src_rates."""
         h = C.c_void_p()
-        if src_rates is None and dst_rate is None:
+        self._frame_bytes = 0
+        if layout is not None:
+            if (src_rates is None) != (dst_rate is None):
+                raise ValueError("a resampling pool needs both dst_rate and src_rates")
+            lay = BnPcmLayout(*layout)
+            fmt = lay.format
+            self._frame_bytes = PCM_SAMPLE_BYTES.get(lay.format, 1) * max(int(lay.channels), 1)
+            rates = None if src_rates is None else np.ascontiguousarray(src_rates, dtype=np.uint32).reshape(-1)
+            if rates is not None and rates.shape[0] != n_sources:
+                raise ValueError("src_rates needs one rate per source")
+            st = lib.bn_live_create_layout(device, n_sources, C.byref(lay), C.sizeof(lay), segment_samples, step_samples, ring_samples, dst_rate or 0,
+                                           None if rates is None else rates.ctypes.data_as(C.POINTER(C.c_uint32)), zero_crossings, C.byref(h))
+        elif src_rates is None and dst_rate is None:
             st = lib.bn_live_create(device, n_sources, fmt, segment_samples, step_samples, ring_samples, C.byref(h))
         else:
             if src_rates is None or dst_rate is None:
@@ -2164,22 +2237,29 @@ class Live:
         self.__del__()
 
     def _pcm(self, samples):
+        """the array a push hands over and the count it names: samples, or frames of a layout pool"""
+        if self._frame_bytes:
+            a = np.frombuffer(samples, dtype=np.uint8) if isinstance(samples, (bytes, bytearray, memoryview)) else np.ascontiguousarray(samples).reshape(-1).view(np.uint8)
+            if a.shape[0] % self._frame_bytes:
+                raise ValueError(f"{a.shape[0]} bytes are no whole number of {self._frame_bytes}-byte frames")
+            return a, a.shape[0] // self._frame_bytes
         a = np.ascontiguousarray(samples, dtype=self._dtype).reshape(-1)
-        return a
+        return a, a.shape[0]
 
     def push(self, source: int, samples):
-        a = self._pcm(samples)
-        st = lib.bn_live_push(self._h, source, a.ctypes.data_as(C.c_void_p), a.shape[0])
+        a, n = self._pcm(samples)
+        st = lib.bn_live_push(self._h, source, a.ctypes.data_as(C.c_void_p), n)
         if st:
             raise EngineError(st)
 
     def push_many(self, sources, chunks):
         """One call for many chunks: chunk i goes to sources[i]; refused whole if any chunk exceeds its source's room."""
-        arrs = [self._pcm(c) for c in chunks]
+        pairs = [self._pcm(c) for c in chunks]
+        arrs = [a for a, _ in pairs]
         n = len(arrs)
         src = (C.c_int32 * max(n, 1))(*[int(s) for s in sources])
         ptrs = (C.c_void_p * max(n, 1))(*[a.ctypes.data for a in arrs])
-        lens = (C.c_size_t * max(n, 1))(*[a.shape[0] for a in arrs])
+        lens = (C.c_size_t * max(n, 1))(*[k for _, k in pairs])
         st = lib.bn_live_push_many(self._h, n, src, ptrs, lens)
         if st:
             raise EngineError(st)

@@ -1430,107 +1430,173 @@ bn_status bn_topk_host(int32_t device, const float *logits, size_t rows, size_t 
 }
 
 // ---- recording-level ingest (birdnet-analyze.rs:683-687, 707-743) ----
-struct bn_recording {
+// The device bytes of a recording, in the format they were uploaded in, and their upload: shared by the recording that uploaded
+// them and its channel views (bn_recording_view_channel), freed -- the upload joined -- with the last of them.
+struct RecStore {
     int32_t device = 0;
-    int32_t format = BN_PCM_I16;
     DeviceBuf<void> d_pcm;
-    size_t n_samples = 0;
-    // asynchronous upload (bn_recording_create_async): a thread of the recording's own copies the caller's buffer chunk by chunk
-    // (synchronous copies under the capture gate, like every other copy of the library); chunks_done chunks are on the device
-    size_t chunk_samples = 0;  // 0: the whole recording was uploaded at creation
+    size_t n_frames = 0;
+    // asynchronous upload (bn_recording_create_async): a thread of the store's own copies the caller's buffer chunk by chunk
+    // (synchronous copies under the capture gate, like every other copy of the library); chunks_done chunks are on the device.
+    // A chunk is a whole number of FRAMES (pcm_layout.h), so "has frame i arrived" is i / chunk_frames
+    size_t chunk_frames = 0;  // 0: the whole recording was uploaded at creation
     size_t n_chunks = 0;
     std::atomic<size_t> chunks_done{0};
     std::atomic<int> upload_error{0};
     std::thread uploader;
     std::mutex mu;
     std::condition_variable cv;
-    ~bn_recording() {
+    ~RecStore() {
         if (uploader.joinable()) uploader.join();  // (the caller's buffer is read until here at the latest)
         (void)bn::use_device(device);
     }
 };
+struct bn_recording {
+    int32_t device = 0;
+    PcmLayout layout;        // how the store's bytes are read: frame -> f32 sample (pcm_read.h)
+    bool any_format = false;  // created with a layout: bn_recording_read_f32 converts whatever the format
+    bool resampled = false;   // the store holds the resampler's mono f32 output: no storage-format bytes are left
+    std::shared_ptr<RecStore> store;
+    size_t n_samples = 0;  // frames
+    PcmSrc src() const { return PcmSrc{store->d_pcm.get(), layout}; }
+};
 
 namespace {
-// blocks until sample `last` of the recording is on the device (kernels launched afterwards may read it); false if the upload failed
+// blocks until frame `last` of the recording is on the device (kernels launched afterwards may read it); false if the upload failed
 bool recording_wait_samples(const bn_recording *rc, size_t last) {
-    bn_recording *r = const_cast<bn_recording *>(rc);
-    if (!r->chunk_samples || r->n_chunks == 0) return true;
-    const size_t need = std::min(last / r->chunk_samples, r->n_chunks - 1) + 1;
+    RecStore *r = rc->store.get();
+    if (!r->chunk_frames || r->n_chunks == 0) return true;
+    const size_t need = pcm_chunks_for_frame(last, r->chunk_frames, r->n_chunks);
     if (r->chunks_done.load(std::memory_order_acquire) >= need) return r->upload_error.load() == 0;
     std::unique_lock<std::mutex> lk(r->mu);
     r->cv.wait(lk, [&] { return r->chunks_done.load(std::memory_order_acquire) >= need || r->upload_error.load() != 0; });
     return r->upload_error.load() == 0;
 }
 bool recording_wait_all(const bn_recording *r) { return recording_wait_samples(r, r->n_samples ? r->n_samples - 1 : 0); }
-}  // namespace
 
-bn_status bn_recording_create(int32_t device, const void *pcm, size_t n_samples, int32_t format, bn_recording **out) {
-    if (!out) return fail(BN_ERR_INVALID_ARG, "null argument");
-    *out = nullptr;
-    if (format != BN_PCM_I16 && format != BN_PCM_F32) return fail(BN_ERR_INVALID_ARG, "unknown PCM format");
-    if (n_samples && !pcm) return fail(BN_ERR_INVALID_ARG, "null PCM buffer");
+// every bn_recording_create*: the layout checked, the bytes uploaded at once or by the store's thread
+bn_status recording_create(int32_t device, const void *pcm, size_t n_frames, PcmLayout layout, bool any_format, bool async, bn_recording **out) {
+    if (const char *why = pcm_layout_problem(layout)) return fail(BN_ERR_INVALID_ARG, why);
+    layout = pcm_normalised(layout);
+    if (n_frames && !pcm) return fail(BN_ERR_INVALID_ARG, "null PCM buffer");
+    size_t bytes = 0;
+    if (!pcm_bytes(layout, n_frames, &bytes) || bytes > SIZE_MAX - 16) return fail(BN_ERR_INVALID_ARG, "n_frames * channels * bytes per sample exceeds the address space");
     if (bn_status dst = require_any_device(); dst != BN_OK) return dst;
     BN_HIP_TRY(bn::use_device(device));
     auto r = std::make_unique<bn_recording>();
     r->device = device;
-    r->format = format;
-    r->n_samples = n_samples;
-    const size_t bytes = n_samples * (format == BN_PCM_I16 ? sizeof(int16_t) : sizeof(float));
-    BN_HIP_TRY(r->d_pcm.alloc(std::max<size_t>(bytes, 16)));
-    if (bytes) {
-        hipError_t e = gated::Memcpy(r->d_pcm, pcm, bytes, hipMemcpyHostToDevice);
-        if (e != hipSuccess) return fail(BN_ERR_BACKEND, std::string("recording upload failed: ") + hipGetErrorString(e));
+    r->layout = layout;
+    r->any_format = any_format;
+    r->n_samples = n_frames;
+    r->store = std::make_shared<RecStore>();
+    RecStore *st = r->store.get();
+    st->device = device;
+    st->n_frames = n_frames;
+    BN_HIP_TRY(st->d_pcm.alloc(std::max<size_t>(bytes + PCM_READ_SLACK, 16)));
+    if (!async) {
+        if (bytes) {
+            hipError_t e = gated::Memcpy(st->d_pcm, pcm, bytes, hipMemcpyHostToDevice);
+            if (e != hipSuccess) return fail(BN_ERR_BACKEND, std::string("recording upload failed: ") + hipGetErrorString(e));
+        }
+        *out = r.release();
+        return BN_OK;
     }
-    *out = r.release();
-    return BN_OK;
-}
-
-bn_status bn_recording_create_async(int32_t device, const void *pcm, size_t n_samples, int32_t format, bn_recording **out) {
-    if (!out) return fail(BN_ERR_INVALID_ARG, "null argument");
-    *out = nullptr;
-    if (format != BN_PCM_I16 && format != BN_PCM_F32) return fail(BN_ERR_INVALID_ARG, "unknown PCM format");
-    if (n_samples && !pcm) return fail(BN_ERR_INVALID_ARG, "null PCM buffer");
-    if (bn_status dst = require_any_device(); dst != BN_OK) return dst;
-    BN_HIP_TRY(bn::use_device(device));
-    const size_t esz = format == BN_PCM_I16 ? sizeof(int16_t) : sizeof(float);
     // the uploader holds the capture gate (shared) for one chunk's synchronous copy and a context's first-time graph capture takes it
     // exclusively: 4 MiB keeps a capture's wait behind a chunk well under a millisecond (32 MiB chunks stalled exactly the first
     // windows' captures the overlap was meant to help)
     const size_t chunk_mb = (size_t)std::max(1, sw_int(sw::BN_UPLOAD_CHUNK_MB));
-    auto r = std::make_unique<bn_recording>();
-    r->device = device;
-    r->format = format;
-    r->n_samples = n_samples;
-    BN_HIP_TRY(r->d_pcm.alloc(std::max<size_t>(n_samples * esz, 16)));
-    r->chunk_samples = std::max<size_t>(1, (chunk_mb << 20) / esz);
-    r->n_chunks = (n_samples + r->chunk_samples - 1) / r->chunk_samples;
-    bn_recording *raw = r.get();
-    if (r->n_chunks) try {
-        r->uploader = std::thread([raw, pcm, esz]() {
-            if (bn::use_device(raw->device) != hipSuccess) raw->upload_error.store(1);
-            for (size_t k = 0; k < raw->n_chunks && raw->upload_error.load() == 0; k++) {
-                const size_t a = k * raw->chunk_samples, n = std::min(raw->chunk_samples, raw->n_samples - a);
+    const size_t fb = pcm_frame_bytes(layout);
+    st->chunk_frames = pcm_chunk_frames(layout, chunk_mb << 20);
+    st->n_chunks = pcm_chunk_count(n_frames, st->chunk_frames);
+    if (st->n_chunks) try {
+        st->uploader = std::thread([st, pcm, fb]() {
+            if (bn::use_device(st->device) != hipSuccess) st->upload_error.store(1);
+            for (size_t k = 0; k < st->n_chunks && st->upload_error.load() == 0; k++) {
+                const size_t a = k * st->chunk_frames, n = std::min(st->chunk_frames, st->n_frames - a);
                 // a synchronous copy of its own kind (null stream; the contexts' streams are non-blocking and do not wait for it)
-                if (gated::Memcpy(static_cast<char *>(raw->d_pcm.get()) + a * esz, static_cast<const char *>(pcm) + a * esz, n * esz, hipMemcpyHostToDevice) != hipSuccess) {
+                if (gated::Memcpy(static_cast<char *>(st->d_pcm.get()) + a * fb, static_cast<const char *>(pcm) + a * fb, n * fb, hipMemcpyHostToDevice) != hipSuccess) {
                     (void)hipGetLastError();
-                    raw->upload_error.store(1);
+                    st->upload_error.store(1);
                 }
                 {
-                    std::lock_guard<std::mutex> lk(raw->mu);
-                    raw->chunks_done.store(k + 1, std::memory_order_release);
+                    std::lock_guard<std::mutex> lk(st->mu);
+                    st->chunks_done.store(k + 1, std::memory_order_release);
                 }
-                raw->cv.notify_all();
+                st->cv.notify_all();
             }
-            if (raw->upload_error.load()) {  // wake every waiter
-                std::lock_guard<std::mutex> lk(raw->mu);
-                raw->chunks_done.store(raw->n_chunks, std::memory_order_release);
-                raw->cv.notify_all();
+            if (st->upload_error.load()) {  // wake every waiter
+                std::lock_guard<std::mutex> lk(st->mu);
+                st->chunks_done.store(st->n_chunks, std::memory_order_release);
+                st->cv.notify_all();
             }
         });
     } catch (const std::exception &e) {  // std::system_error from the thread constructor must not cross the C boundary
         return fail(BN_ERR_BACKEND, std::string("could not start the upload thread: ") + e.what());
     }
     *out = r.release();
+    return BN_OK;
+}
+}  // namespace
+
+extern "C++" bn_status bn::read_pcm_layout(const bn_pcm_layout *layout, size_t struct_size, PcmLayout *out) {
+    if (!layout) return fail(BN_ERR_INVALID_ARG, "null PCM layout");
+    if (struct_size < sizeof(bn_pcm_layout)) return fail(BN_ERR_INVALID_ARG, "struct_size is below sizeof(bn_pcm_layout)");
+    out->format = layout->format;
+    out->channels = layout->channels;
+    out->channel = layout->channel;
+    return BN_OK;
+}
+
+bn_status bn_recording_create(int32_t device, const void *pcm, size_t n_samples, int32_t format, bn_recording **out) {
+    if (!out) return fail(BN_ERR_INVALID_ARG, "null argument");
+    *out = nullptr;
+    if (format != BN_PCM_I16 && format != BN_PCM_F32) return fail(BN_ERR_INVALID_ARG, "unknown PCM format");
+    return recording_create(device, pcm, n_samples, PcmLayout{format, 1, 0}, false, false, out);
+}
+
+bn_status bn_recording_create_async(int32_t device, const void *pcm, size_t n_samples, int32_t format, bn_recording **out) {
+    if (!out) return fail(BN_ERR_INVALID_ARG, "null argument");
+    *out = nullptr;
+    if (format != BN_PCM_I16 && format != BN_PCM_F32) return fail(BN_ERR_INVALID_ARG, "unknown PCM format");
+    return recording_create(device, pcm, n_samples, PcmLayout{format, 1, 0}, false, true, out);
+}
+
+bn_status bn_recording_create_layout(int32_t device, const void *pcm, size_t n_frames, const bn_pcm_layout *layout, size_t struct_size, bn_recording **out) {
+    if (!out) return fail(BN_ERR_INVALID_ARG, "null argument");
+    *out = nullptr;
+    PcmLayout pl;
+    if (bn_status st = read_pcm_layout(layout, struct_size, &pl); st != BN_OK) return st;
+    return recording_create(device, pcm, n_frames, pl, true, false, out);
+}
+
+bn_status bn_recording_create_layout_async(int32_t device, const void *pcm, size_t n_frames, const bn_pcm_layout *layout, size_t struct_size,
+                                           bn_recording **out) {
+    if (!out) return fail(BN_ERR_INVALID_ARG, "null argument");
+    *out = nullptr;
+    PcmLayout pl;
+    if (bn_status st = read_pcm_layout(layout, struct_size, &pl); st != BN_OK) return st;
+    return recording_create(device, pcm, n_frames, pl, true, true, out);
+}
+
+bn_status bn_recording_view_channel(const bn_recording *r, int32_t channel, bn_recording **out) {
+    if (!out) return fail(BN_ERR_INVALID_ARG, "null argument");
+    *out = nullptr;
+    if (!r) return fail(BN_ERR_INVALID_ARG, "null recording");
+    PcmLayout l = r->layout;
+    l.channel = channel;
+    if (const char *why = pcm_layout_problem(l)) {
+        if (r->resampled)
+            return fail(BN_ERR_INVALID_ARG, "a resampled recording has no storage-format bytes left: it is mono f32 and takes channel 0 or BN_PCM_MIX only");
+        return fail(BN_ERR_INVALID_ARG, std::string(why) + " (channel " + std::to_string(channel) + " of " + std::to_string(l.channels) + ")");
+    }
+    auto v = std::make_unique<bn_recording>();
+    v->device = r->device;
+    v->layout = pcm_normalised(l);
+    v->any_format = true;
+    v->resampled = r->resampled;
+    v->store = r->store;
+    v->n_samples = r->n_samples;
+    *out = v.release();
     return BN_OK;
 }
 
@@ -1606,45 +1672,85 @@ size_t bn_resample_table(uint32_t src_rate, uint32_t dst_rate, uint32_t zero_cro
     return t.coef.size();
 }
 
+namespace {
+// bn_recording_create_resampled / bn_recording_create_layout_resampled: upload in the storage layout, convert on the device
+bn_status recording_create_resampled(int32_t device, const void *pcm, size_t n_frames, PcmLayout layout, bool any_format, uint32_t src_rate,
+                                     uint32_t dst_rate, uint32_t zero_crossings, bn_recording **out) {
+    if (src_rate == 0 || dst_rate == 0) return fail(BN_ERR_INVALID_ARG, "sample rates must be positive");
+    if (src_rate == dst_rate) return recording_create(device, pcm, n_frames, layout, any_format, false, out);
+    bn_recording *src = nullptr;
+    bn_status st = recording_create(device, pcm, n_frames, layout, any_format, false, &src);
+    if (st != BN_OK) return st;
+    std::unique_ptr<bn_recording> src_owner(src);
+    const ResampleTable t = make_resample_table(src_rate, dst_rate, zero_crossings);
+    const size_t n_dst = (size_t)(((unsigned __int128)n_frames * t.L + t.M - 1) / t.M);
+    auto r = std::make_unique<bn_recording>();
+    r->device = device;
+    r->layout = PcmLayout{BN_PCM_F32, 1, 0};
+    r->any_format = any_format;
+    r->resampled = true;
+    r->n_samples = n_dst;
+    r->store = std::make_shared<RecStore>();
+    r->store->device = device;
+    r->store->n_frames = n_dst;
+    DeviceBuf<float> d_table;
+    hipError_t e = r->store->d_pcm.alloc(std::max<size_t>(n_dst * sizeof(float), 16));
+    if (e == hipSuccess) e = d_table.alloc(t.coef.size() * sizeof(float));
+    if (e == hipSuccess) e = gated::Memcpy(d_table, t.coef.data(), t.coef.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        (void)hipGetLastError();
+        launch_resample(nullptr, static_cast<float *>(r->store->d_pcm.get()), src->src(), d_table, n_frames, n_dst, t.L, t.M, t.T);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = gated::DeviceSynchronize();
+    if (e != hipSuccess) return fail(BN_ERR_BACKEND, std::string("resampling failed: ") + hipGetErrorString(e));
+    *out = r.release();
+    return BN_OK;
+}
+}  // namespace
+
 bn_status bn_recording_create_resampled(int32_t device, const void *pcm, size_t n_samples, int32_t format, uint32_t src_rate, uint32_t dst_rate,
                                         uint32_t zero_crossings, bn_recording **out) {
     if (!out) return fail(BN_ERR_INVALID_ARG, "null argument");
     *out = nullptr;
     if (src_rate == 0 || dst_rate == 0) return fail(BN_ERR_INVALID_ARG, "sample rates must be positive");
-    if (src_rate == dst_rate) return bn_recording_create(device, pcm, n_samples, format, out);
-    bn_recording *src = nullptr;
-    bn_status st = bn_recording_create(device, pcm, n_samples, format, &src);
-    if (st != BN_OK) return st;
-    const ResampleTable t = make_resample_table(src_rate, dst_rate, zero_crossings);
-    const size_t n_dst = (size_t)(((unsigned __int128)n_samples * t.L + t.M - 1) / t.M);
-    auto r = std::make_unique<bn_recording>();
-    r->device = device;
-    r->format = BN_PCM_F32;
-    r->n_samples = n_dst;
-    DeviceBuf<float> d_table;
-    hipError_t e = r->d_pcm.alloc(std::max<size_t>(n_dst * sizeof(float), 16));
-    if (e == hipSuccess) e = d_table.alloc(t.coef.size() * sizeof(float));
-    if (e == hipSuccess) e = gated::Memcpy(d_table, t.coef.data(), t.coef.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        (void)hipGetLastError();
-        launch_resample(nullptr, static_cast<float *>(r->d_pcm.get()), src->d_pcm, format == BN_PCM_I16, d_table, n_samples, n_dst, t.L, t.M, t.T);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = gated::DeviceSynchronize();
-    bn_recording_free(src);
-    if (e != hipSuccess) return fail(BN_ERR_BACKEND, std::string("resampling failed: ") + hipGetErrorString(e));
-    *out = r.release();
-    return BN_OK;
+    if (format != BN_PCM_I16 && format != BN_PCM_F32) return fail(BN_ERR_INVALID_ARG, "unknown PCM format");
+    return recording_create_resampled(device, pcm, n_samples, PcmLayout{format, 1, 0}, false, src_rate, dst_rate, zero_crossings, out);
+}
+
+bn_status bn_recording_create_layout_resampled(int32_t device, const void *pcm, size_t n_frames, const bn_pcm_layout *layout, size_t struct_size,
+                                               uint32_t src_rate, uint32_t dst_rate, uint32_t zero_crossings, bn_recording **out) {
+    if (!out) return fail(BN_ERR_INVALID_ARG, "null argument");
+    *out = nullptr;
+    PcmLayout pl;
+    if (bn_status st = read_pcm_layout(layout, struct_size, &pl); st != BN_OK) return st;
+    if (const char *why = pcm_layout_problem(pl)) return fail(BN_ERR_INVALID_ARG, why);
+    return recording_create_resampled(device, pcm, n_frames, pl, true, src_rate, dst_rate, zero_crossings, out);
 }
 
 bn_status bn_recording_read_f32(const bn_recording *r, size_t first, size_t count, float *host_out) {
     if (!r || (count && !host_out)) return fail(BN_ERR_INVALID_ARG, "null argument");
-    if (r->format != BN_PCM_F32) return fail(BN_ERR_INVALID_ARG, "recording is not f32");
+    if (r->layout.format != BN_PCM_F32 && !r->any_format) return fail(BN_ERR_INVALID_ARG, "recording is not f32");
     if (first > r->n_samples || count > r->n_samples - first) return fail(BN_ERR_INVALID_ARG, "sample range exceeds the recording");
     if (count == 0) return BN_OK;
     if (!recording_wait_samples(r, first + count - 1)) return fail(BN_ERR_BACKEND, "recording upload failed");
     BN_HIP_TRY(bn::use_device(r->device));
-    BN_HIP_TRY(gated::Memcpy(host_out, static_cast<const float *>(r->d_pcm.get()) + first, count * sizeof(float), hipMemcpyDeviceToHost));
+    if (pcm_is_plain(r->layout) && r->layout.format == BN_PCM_F32) {
+        BN_HIP_TRY(gated::Memcpy(host_out, static_cast<const float *>(r->store->d_pcm.get()) + first, count * sizeof(float), hipMemcpyDeviceToHost));
+        return BN_OK;
+    }
+    // any other layout: the window kernel over [first, first + count), one window of up to 2^24 frames at a time
+    const size_t piece = (size_t)1 << 24;
+    DeviceBuf<float> d;
+    BN_HIP_TRY(d.alloc(std::min(piece, (count + 3) / 4 * 4) * sizeof(float)));
+    for (size_t done = 0; done < count; done += piece) {
+        const size_t n = std::min(piece, count - done);
+        (void)hipGetLastError();
+        launch_windows(nullptr, d, r->src(), r->n_samples, (uint64_t)(first + done), 1, (uint32_t)((n + 3) / 4 * 4), 1);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = gated::Memcpy(host_out + done, d, n * sizeof(float), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return fail(BN_ERR_BACKEND, std::string("sample read failed: ") + hipGetErrorString(e));
+    }
     return BN_OK;
 }
 
@@ -1678,7 +1784,7 @@ bn_status bn_recording_windows(const bn_recording *r, size_t segment_samples, si
     DeviceBuf<float> d;
     BN_HIP_TRY(d.alloc(count * segment_samples * sizeof(float)));
     (void)hipGetLastError();
-    launch_windows(nullptr, d, r->d_pcm, r->format == BN_PCM_I16, r->n_samples, (uint64_t)first_window * step_samples, step_samples, (uint32_t)segment_samples,
+    launch_windows(nullptr, d, r->src(), r->n_samples, (uint64_t)first_window * step_samples, step_samples, (uint32_t)segment_samples,
                    (uint32_t)count);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = gated::Memcpy(host_out, d, count * segment_samples * sizeof(float), hipMemcpyDeviceToHost);
@@ -1701,7 +1807,7 @@ bn_status bn_infer_windows(bn_ctx *c, const bn_recording *r, size_t step_samples
     if (st != BN_OK) return st;
     if (cancel && *cancel) return fail(BN_ERR_CANCELLED, "inference was cancelled");
     (void)hipGetLastError();
-    launch_windows(c->stream, c->d_input, r->d_pcm, r->format == BN_PCM_I16, r->n_samples, (uint64_t)first_window * step_samples, step_samples, (uint32_t)S,
+    launch_windows(c->stream, c->d_input, r->src(), r->n_samples, (uint64_t)first_window * step_samples, step_samples, (uint32_t)S,
                    (uint32_t)count);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(BN_ERR_BACKEND, std::string("window kernel launch failed: ") + hipGetErrorString(e));
@@ -1726,7 +1832,7 @@ bn_status bn_step_windows(bn_ctx *c, const bn_recording *r, size_t step_samples,
     BN_HIP_TRY(bn::use_device(c->model->device));
     (void)hipGetLastError();
     // stream order keeps this behind whatever the context still has in flight
-    launch_windows(c->stream, c->d_input, r->d_pcm, r->format == BN_PCM_I16, r->n_samples, (uint64_t)first_window * step_samples, step_samples, (uint32_t)S,
+    launch_windows(c->stream, c->d_input, r->src(), r->n_samples, (uint64_t)first_window * step_samples, step_samples, (uint32_t)S,
                    (uint32_t)count);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(BN_ERR_BACKEND, std::string("window kernel launch failed: ") + hipGetErrorString(e));

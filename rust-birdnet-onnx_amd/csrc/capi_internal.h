@@ -16,6 +16,7 @@
 #include "../../include/birdnet_hip.h"
 #include "device_mem.h"
 #include "last_error.h"
+#include "pcm_layout.h"
 #include "query_source.h"
 
 // a failed runtime call ends the enclosing function with BN_ERR_BACKEND and the call's text in the message
@@ -172,6 +173,10 @@ struct ResampleTable {
 // L, M and T alone (coef left empty): what the table would be, without building it
 ResampleTable resample_factors(uint32_t src_rate, uint32_t dst_rate, uint32_t zc);
 ResampleTable make_resample_table(uint32_t src_rate, uint32_t dst_rate, uint32_t zc);
+// a caller's bn_pcm_layout read through the size it was compiled with (a longer struct of a later header: its first fields);
+// BN_ERR_INVALID_ARG for NULL or a struct shorter than this header's.  The layout itself is checked by
+// pcm_layout_problem (pcm_layout.h)
+bn_status read_pcm_layout(const bn_pcm_layout *layout, size_t struct_size, PcmLayout *out);
 // index.hip -> head.hip (bn_head_fit_index): the stored rows of an index, every pending append waited for
 struct IndexRows {
     int device = 0;

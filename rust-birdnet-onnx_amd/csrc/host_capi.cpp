@@ -202,6 +202,23 @@ int32_t bnh_predict_recording(const bnh_classifier *c, bnh_context *ctx, const v
     });
 }
 
+int32_t bnh_predict_recording_layout(const bnh_classifier *c, bnh_context *ctx, const void *pcm, size_t n_frames, int32_t format, uint32_t channels,
+                                     int32_t channel, float overlap_secs, size_t first_chunk, size_t count, int64_t timeout_ns,
+                                     const volatile int32_t *cancel, bnh_results **out, float *start_times, size_t times_cap, bnh_error *err) {
+    if (out) *out = nullptr;
+    return guarded(err, [&] {
+        InferenceOptions o = make_opts(timeout_ns, cancel);
+        Recording rec(pcm, n_frames, bn_pcm_layout{format, channels, channel}, 0);
+        auto chunks = c->cl.predict_recording(*ctx->ctx, rec, overlap_secs, first_chunk, count, o);
+        auto r = std::make_unique<bnh_results>();
+        for (size_t i = 0; i < chunks.size(); i++) {
+            if (start_times && i < times_cap) start_times[i] = chunks[i].start_time;
+            r->v.push_back(std::move(chunks[i].result));
+        }
+        *out = r.release();
+    });
+}
+
 int32_t bnh_live_create(const bnh_classifier *c, int32_t n_sources, int32_t format, float overlap_secs, size_t ring_samples, int32_t device,
                         bnh_live **out, bnh_error *err) {
     if (!out) return set_other(err, "null argument");
@@ -216,6 +233,18 @@ int32_t bnh_live_create_rates(const bnh_classifier *c, int32_t n_sources, const 
     return guarded(err, [&] {
         *out = new bnh_live{LiveSources(c->cl, std::vector<uint32_t>(source_rates, source_rates + n_sources), format, overlap_secs, ring_samples, device,
                                         zero_crossings)};
+    });
+}
+int32_t bnh_live_create_layout(const bnh_classifier *c, int32_t n_sources, int32_t format, uint32_t channels, int32_t channel,
+                               const uint32_t *source_rates, float overlap_secs, size_t ring_samples, int32_t device, uint32_t zero_crossings,
+                               bnh_live **out, bnh_error *err) {
+    if (!out) return set_other(err, "null argument");
+    *out = nullptr;
+    if (n_sources < 1) return set_other(err, "a live pool needs at least one source");
+    return guarded(err, [&] {
+        std::vector<uint32_t> rates;
+        if (source_rates) rates.assign(source_rates, source_rates + n_sources);
+        *out = new bnh_live{LiveSources(c->cl, n_sources, bn_pcm_layout{format, channels, channel}, rates, overlap_secs, ring_samples, device, zero_crossings)};
     });
 }
 void bnh_live_free(bnh_live *l) { delete l; }

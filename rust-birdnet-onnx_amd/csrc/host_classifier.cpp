@@ -305,6 +305,21 @@ Recording::Recording(const void *pcm, size_t n_samples, int32_t format, int devi
     rec_ = std::shared_ptr<bn_recording>(r, [](bn_recording *p) { bn_recording_free(p); });
 }
 
+Recording::Recording(const void *pcm, size_t n_frames, const bn_pcm_layout &layout, int device) : n_samples_(n_frames) {
+    bn_recording *r = nullptr;
+    if (bn_recording_create_layout(device, pcm, n_frames, &layout, sizeof(layout), &r) != BN_OK)
+        throw inference("failed to upload recording: " + last_backend_error());
+    rec_ = std::shared_ptr<bn_recording>(r, [](bn_recording *p) { bn_recording_free(p); });
+}
+
+Recording Recording::view_channel(int32_t channel) const {
+    bn_recording *r = nullptr;
+    if (bn_recording_view_channel(rec_.get(), channel, &r) != BN_OK) throw inference("failed to view the recording: " + last_backend_error());
+    Recording v(*this);
+    v.rec_ = std::shared_ptr<bn_recording>(r, [](bn_recording *p) { bn_recording_free(p); });
+    return v;
+}
+
 std::vector<ChunkResult> Classifier::predict_recording(BatchInferenceContext &ctx, const Recording &rec, float overlap_secs, size_t first_chunk, size_t count,
                                                        const InferenceOptions &options) const {
     const ModelConfig &cfg = inner_->config;
@@ -333,17 +348,23 @@ std::vector<ChunkResult> Classifier::predict_recording(BatchInferenceContext &ct
 }
 
 LiveSources::LiveSources(const Classifier &cl, int32_t n_sources, int32_t format, float overlap_secs, size_t ring_samples, int device) {
-    create(cl, n_sources, nullptr, format, overlap_secs, ring_samples, device, 0);
+    create(cl, n_sources, nullptr, nullptr, format, overlap_secs, ring_samples, device, 0);
+}
+
+LiveSources::LiveSources(const Classifier &cl, int32_t n_sources, const bn_pcm_layout &layout, const std::vector<uint32_t> &source_rates,
+                         float overlap_secs, size_t ring_samples, int device, uint32_t zero_crossings) {
+    if (!source_rates.empty() && (size_t)n_sources != source_rates.size()) throw inference("a live pool takes one rate per source");
+    create(cl, n_sources, source_rates.empty() ? nullptr : source_rates.data(), &layout, layout.format, overlap_secs, ring_samples, device, zero_crossings);
 }
 
 LiveSources::LiveSources(const Classifier &cl, const std::vector<uint32_t> &source_rates, int32_t format, float overlap_secs, size_t ring_samples,
                          int device, uint32_t zero_crossings) {
     if (source_rates.empty()) throw inference("a live pool needs at least one source rate");
-    create(cl, (int32_t)source_rates.size(), source_rates.data(), format, overlap_secs, ring_samples, device, zero_crossings);
+    create(cl, (int32_t)source_rates.size(), source_rates.data(), nullptr, format, overlap_secs, ring_samples, device, zero_crossings);
 }
 
-void LiveSources::create(const Classifier &cl, int32_t n_sources, const uint32_t *source_rates, int32_t format, float overlap_secs, size_t ring_samples,
-                         int device, uint32_t zero_crossings) {
+void LiveSources::create(const Classifier &cl, int32_t n_sources, const uint32_t *source_rates, const bn_pcm_layout *layout, int32_t format,
+                         float overlap_secs, size_t ring_samples, int device, uint32_t zero_crossings) {
     const ModelConfig &cfg = cl.config();
     // chunk_audio's step, as predict_recording computes it
     const size_t overlap_samples = (size_t)(overlap_secs * (float)cfg.sample_rate);
@@ -352,7 +373,9 @@ void LiveSources::create(const Classifier &cl, int32_t n_sources, const uint32_t
     if (ring_samples == 0) ring_samples = 2 * cfg.sample_count + step_;
     if (device < 0) device = bn_model_device(cl.inner_->model);
     bn_live *l = nullptr;
-    const bn_status st = source_rates ? bn_live_create_rates(device, n_sources, format, cfg.sample_count, step_, ring_samples, cfg.sample_rate,
+    const bn_status st = layout ? bn_live_create_layout(device, n_sources, layout, sizeof(*layout), cfg.sample_count, step_, ring_samples, cfg.sample_rate,
+                                                        source_rates, zero_crossings, &l)
+                         : source_rates ? bn_live_create_rates(device, n_sources, format, cfg.sample_count, step_, ring_samples, cfg.sample_rate,
                                                              source_rates, zero_crossings, &l)
                                       : bn_live_create(device, n_sources, format, cfg.sample_count, step_, ring_samples, &l);
     if (st != BN_OK)

@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <cstdlib>
 
+#include "pcm_layout.h"
 #include "switches.h"
 
 namespace bn {
@@ -369,12 +370,10 @@ void launch_topk(hipStream_t s, const float *logits, int64_t rows, int64_t n, in
                  int has_min, float min_conf, int64_t k_stride, uint32_t *idx, float *conf,
                  uint32_t *count, uint32_t *flags);
 // LDS bytes the top-K kernel needs for (n, k); 0 if it cannot run (too large).
-// recording -> f32 windows (chunk_audio + i16/32768 conversion); S % 4 == 0
-void launch_windows(hipStream_t s, float *dst, const void *src, int32_t is_i16, uint64_t n_samples, uint64_t first_start, uint64_t step, uint32_t S,
-                    uint32_t count);
+// recording -> f32 windows (chunk_audio + the layout's sample read, pcm_read.h); counts in frames, S % 4 == 0
+void launch_windows(hipStream_t s, float *dst, const PcmSrc &src, uint64_t n_samples, uint64_t first_start, uint64_t step, uint32_t S, uint32_t count);
 // polyphase FIR resampler: table [L][T], output n reads phase (n*M)%L at source position (n*M)/L
-void launch_resample(hipStream_t s, float *dst, const void *src, int32_t is_i16, const float *table, uint64_t n_src, uint64_t n_dst, uint32_t L, uint32_t M,
-                     uint32_t T);
+void launch_resample(hipStream_t s, float *dst, const PcmSrc &src, const float *table, uint64_t n_src, uint64_t n_dst, uint32_t L, uint32_t M, uint32_t T);
 // Windowed-DFT filter bank as a real FFT (stft.hip).  Frames of L samples (L = 2 M, M a power of two in 64..1024) at
 // `hop`, per sample `frames` of them; a wave transforms F = 1024 / M frames at a time in place in LDS: `npass`
 // strided decimation-in-frequency passes (sub-problem size pass_n, radix pass_r, twiddles at tw + pass_tw), then

@@ -29,6 +29,7 @@
 #include "device_mem.h"
 #include "bf16x3.h"
 #include "device_common.h"
+#include "pcm_read.h"
 
 namespace bn {
 
@@ -3606,12 +3607,13 @@ void launch_pool(hipStream_t s, const PoolDesc &d, float *out, const float *in, 
 // ------------------------------------------------------------------ recording -> windows
 // chunk_audio on the device (reference src/bin/birdnet-analyze.rs:707-743) fused with the WAV
 // sample conversion (:683-687, f32::from(s) / 32768.0 -- a division by a power of two, exact):
-// window w of the launch starts at sample (first + w) * step; samples past the end of the recording
-// are 0.  One lane = 4 consecutive samples of a window (float4 store; S % 4 == 0 checked by the
-// caller), reads are 2- or 4-byte loads at arbitrary alignment.  grid (ceil(S/1024), count)
+// window w of the launch starts at frame (first + w) * step; frames past the end of the recording
+// are 0.  One lane = 4 consecutive frames of a window (float4 store; S % 4 == 0 checked by the
+// caller); the frame -> f32 sample read is the reader's (pcm_read.h: mono int16 / float as ever, or
+// an interleaved layout read once per output sample).  grid (ceil(S/1024), count)
 namespace {
-template <class T>
-__global__ __launch_bounds__(256) void windows_kernel(float *__restrict__ dst, const T *__restrict__ src, uint64_t n_samples, uint64_t first_start,
+template <class R>
+__global__ __launch_bounds__(256) void windows_kernel(float *__restrict__ dst, const R src, uint64_t n_samples, uint64_t first_start,
                                                      uint64_t step, uint32_t S) {
     const uint32_t i = (blockIdx.x * 256u + threadIdx.x) * 4u;
     if (i >= S) return;
@@ -3620,32 +3622,27 @@ __global__ __launch_bounds__(256) void windows_kernel(float *__restrict__ dst, c
 #pragma unroll
     for (int u = 0; u < 4; u++) {
         const uint64_t q = pos + u;
-        if (q < n_samples) {
-            if constexpr (sizeof(T) == 2) v[u] = (float)src[q] * (1.0f / 32768.0f);
-            else v[u] = (float)src[q];
-        } else {
-            v[u] = 0.0f;
-        }
+        if (q < n_samples) v[u] = src(q);
+        else v[u] = 0.0f;
     }
     *reinterpret_cast<float4 *>(dst + (uint64_t)blockIdx.y * S + i) = make_float4(v[0], v[1], v[2], v[3]);
 }
 }  // namespace
-void launch_windows(hipStream_t s, float *dst, const void *src, int32_t is_i16, uint64_t n_samples, uint64_t first_start, uint64_t step, uint32_t S,
-                    uint32_t count) {
+void launch_windows(hipStream_t s, float *dst, const PcmSrc &src, uint64_t n_samples, uint64_t first_start, uint64_t step, uint32_t S, uint32_t count) {
     if (count == 0 || S == 0) return;
     dim3 grid((S / 4 + 255) / 256, count);
-    if (is_i16) hipLaunchKernelGGL(windows_kernel<int16_t>, grid, dim3(256), 0, s, dst, static_cast<const int16_t *>(src), n_samples, first_start, step, S);
-    else hipLaunchKernelGGL(windows_kernel<float>, grid, dim3(256), 0, s, dst, static_cast<const float *>(src), n_samples, first_start, step, S);
+    pcm_visit(src, [&](auto rd) { hipLaunchKernelGGL(windows_kernel<decltype(rd)>, grid, dim3(256), 0, s, dst, rd, n_samples, first_start, step, S); });
 }
 
 // ------------------------------------------------------------------ polyphase resampler
 // y[n] = sum_j table[(n*M) % L][j] * x[(n*M) / L + j - (T/2 - 1)]   (zero outside the recording)
 // with a host-built windowed-sinc table (L phases x T taps, each phase normalised to unit DC gain).
 // One lane = one output sample; the phase rows are tiny and cache-resident, the input reads of a
-// wave overlap almost entirely.  The source is int16 (/32768, exact) or f32.
+// wave overlap almost entirely.  The source sample is the reader's (pcm_read.h); the chain after the
+// load is the same for every layout.
 namespace {
-template <class T_>
-__global__ __launch_bounds__(256) void resample_kernel(float *__restrict__ dst, const T_ *__restrict__ src, const float *__restrict__ table,
+template <class R>
+__global__ __launch_bounds__(256) void resample_kernel(float *__restrict__ dst, const R src, const float *__restrict__ table,
                                                       uint64_t n_src, uint64_t n_dst, uint32_t L, uint32_t M, uint32_t T) {
     const uint64_t n = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (n >= n_dst) return;
@@ -3658,21 +3655,16 @@ __global__ __launch_bounds__(256) void resample_kernel(float *__restrict__ dst, 
     for (uint32_t j = 0; j < T; j++) {
         const int64_t q = first + j;
         float x = 0.0f;
-        if (q >= 0 && (uint64_t)q < n_src) {
-            if constexpr (sizeof(T_) == 2) x = (float)src[q] * (1.0f / 32768.0f);
-            else x = (float)src[q];
-        }
+        if (q >= 0 && (uint64_t)q < n_src) x = src((uint64_t)q);
         acc = fmaf(row[j], x, acc);
     }
     dst[n] = acc;
 }
 }  // namespace
-void launch_resample(hipStream_t s, float *dst, const void *src, int32_t is_i16, const float *table, uint64_t n_src, uint64_t n_dst, uint32_t L, uint32_t M,
-                     uint32_t T) {
+void launch_resample(hipStream_t s, float *dst, const PcmSrc &src, const float *table, uint64_t n_src, uint64_t n_dst, uint32_t L, uint32_t M, uint32_t T) {
     if (n_dst == 0) return;
     dim3 grid((unsigned)((n_dst + 255) / 256));
-    if (is_i16) hipLaunchKernelGGL(resample_kernel<int16_t>, grid, dim3(256), 0, s, dst, static_cast<const int16_t *>(src), table, n_src, n_dst, L, M, T);
-    else hipLaunchKernelGGL(resample_kernel<float>, grid, dim3(256), 0, s, dst, static_cast<const float *>(src), table, n_src, n_dst, L, M, T);
+    pcm_visit(src, [&](auto rd) { hipLaunchKernelGGL(resample_kernel<decltype(rd)>, grid, dim3(256), 0, s, dst, rd, table, n_src, n_dst, L, M, T); });
 }
 
 // empty launch: calibrates the event-to-event overhead of bn_ctx_time_kernels

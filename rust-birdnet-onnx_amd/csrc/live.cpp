@@ -17,6 +17,10 @@
 // (live_resample_kernel), then a second launch on the pool's stream moves the source's last T - 1 samples into its device
 // history; a close converts the tail [F, ceil(in_pushed * L / M)) with zeros past the end.  Everything downstream of `pushed`
 // (readiness, rows, ordering, reset) is the plain pool's code.
+//
+// Layout pools (bn_live_create_layout).  Pushes carry interleaved frames in any format (pcm_layout.h) and count FRAMES.  Mono
+// int16 / float pushes are stored as they are, as ever; for any other layout the ring holds f32 and the scatter converts each
+// frame to the layout rule's sample as it lands (live.hip), so everything behind the ring is the f32 pool's code and bits.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -84,9 +88,9 @@ struct bn_live {
     std::vector<int32_t> touched;  // push_impl: per source, its entry in the call's list of touched sources (-1: none)
     Stage stage[N_STAGE];
     int next_stage = 0;
-    // what pushes carry: the storage format of a plain pool, the sources' format of a resampling pool (whose ring is f32)
-    bool in_i16 = true;
-    size_t in_esz = 2;
+    // what pushes carry (the ring stores it only when it is mono int16 / float and the pool does not resample; else the ring is f32)
+    bn::PcmLayout in_layout;
+    size_t in_esz = 2;  // bytes of one pushed frame
     // resampling pools
     bool rates = false;
     uint32_t dst_rate = 0;
@@ -248,7 +252,7 @@ bn_status scatter_rates(bn_live *l, const std::vector<std::pair<int32_t, uint64_
     if (tiles.empty() && total == 0) return BN_OK;
     const size_t jobs_b = pad256(jobs.size() * sizeof(bn::LiveRsJob));
     const size_t tiles_b = pad256(tiles.size() * sizeof(bn::LiveRsTile));
-    const size_t bytes = jobs_b + tiles_b + total * l->in_esz;
+    const size_t bytes = jobs_b + tiles_b + total * l->in_esz + bn::PCM_READ_SLACK;
     Stage *stp = nullptr;
     bn_status bs = acquire_stage(l, bytes, &stp);
     if (bs != BN_OK) return bs;
@@ -283,9 +287,10 @@ bn_status scatter_rates(bn_live *l, const std::vector<std::pair<int32_t, uint64_
         blk = st.d;
     }
     const bn::LiveRsJob *d_jobs = reinterpret_cast<const bn::LiveRsJob *>(blk);
-    bn::launch_live_resample(l->stream, static_cast<float *>(l->slab.get()), l->in_i16, l->d_tables, l->d_coef, l->d_hist, d_jobs,
-                             reinterpret_cast<const bn::LiveRsTile *>(blk + jobs_b), (uint32_t)tiles.size(), blk + jobs_b + tiles_b, l->lds_bytes);
-    if (!closing) bn::launch_live_history(l->stream, l->d_hist, l->in_i16, l->d_tables, d_jobs, (uint32_t)jobs.size(), blk + jobs_b + tiles_b);
+    const bn::PcmSrc staged{blk + jobs_b + tiles_b, l->in_layout};
+    bn::launch_live_resample(l->stream, static_cast<float *>(l->slab.get()), staged, l->d_tables, l->d_coef, l->d_hist, d_jobs,
+                             reinterpret_cast<const bn::LiveRsTile *>(blk + jobs_b), (uint32_t)tiles.size(), l->lds_bytes);
+    if (!closing) bn::launch_live_history(l->stream, l->d_hist, staged, l->d_tables, d_jobs, (uint32_t)jobs.size());
     if (bn_status lst = bn::check_launch("live resample"); lst != BN_OK) return lst;
     BN_HIP_TRY(hipEventRecord(st.ev, l->stream));
     BN_HIP_TRY(hipEventRecord(l->scatter_ev, l->stream));
@@ -364,7 +369,7 @@ bn_status push_impl(bn_live *l, size_t n, const int32_t *sources, const void *co
         }
     }
     const size_t tiles_b = (tiles.size() * sizeof(bn::LiveTile) + 255) / 256 * 256;
-    const size_t bytes = tiles_b + total * l->esz;
+    const size_t bytes = tiles_b + total * l->in_esz + bn::PCM_READ_SLACK;
     BN_HIP_TRY(bn::use_device(l->device));
     retire_gathers(l);
     // a staging block is reused only after the scatter that read it completed
@@ -379,8 +384,8 @@ bn_status push_impl(bn_live *l, size_t n, const int32_t *sources, const void *co
         char *p = st.h + tiles_b;
         for (size_t i = 0; i < n; i++) {
             if (!n_samples[i]) continue;
-            memcpy(p, pcm[i], n_samples[i] * l->esz);
-            p += n_samples[i] * l->esz;
+            memcpy(p, pcm[i], n_samples[i] * l->in_esz);
+            p += n_samples[i] * l->in_esz;
         }
     }
     // the scatter waits for the gathers that read the ring space it overwrites: positions below (write end - R)
@@ -399,8 +404,8 @@ bn_status push_impl(bn_live *l, size_t n, const int32_t *sources, const void *co
         BN_HIP_TRY(hipMemcpyAsync(st.d, st.h, bytes, hipMemcpyHostToDevice, l->stream));
         blk = st.d;
     }
-    bn::launch_live_scatter(l->stream, l->slab, l->format == BN_PCM_I16, reinterpret_cast<const bn::LiveTile *>(blk), (uint32_t)tiles.size(),
-                            blk + tiles_b);
+    bn::launch_live_scatter(l->stream, l->slab, bn::PcmSrc{blk + tiles_b, l->in_layout}, reinterpret_cast<const bn::LiveTile *>(blk),
+                            (uint32_t)tiles.size());
     if (bn_status lst = bn::check_launch("live scatter"); lst != BN_OK) return lst;
     BN_HIP_TRY(hipEventRecord(st.ev, l->stream));
     BN_HIP_TRY(hipEventRecord(l->scatter_ev, l->stream));
@@ -475,12 +480,15 @@ bn_status setup_rates(bn_live *l, uint32_t dst_rate, const uint32_t *src_rates, 
     return BN_OK;
 }
 
-// bn_live_create (src_rates == nullptr) and bn_live_create_rates
-bn_status create_pool(int32_t device, int32_t n_sources, int32_t format, size_t segment_samples, size_t step_samples, size_t ring_samples,
+// bn_live_create (src_rates == nullptr), bn_live_create_rates and bn_live_create_layout
+bn_status create_pool(int32_t device, int32_t n_sources, bn::PcmLayout layout, size_t segment_samples, size_t step_samples, size_t ring_samples,
                       uint32_t dst_rate, const uint32_t *src_rates, uint32_t zero_crossings, bn_live **out) {
     if (!out) return invalid("null argument");
     *out = nullptr;
-    if (format != BN_PCM_I16 && format != BN_PCM_F32) return invalid("unknown PCM format " + std::to_string(format));
+    if (const char *why = bn::pcm_layout_problem(layout))
+        return invalid(std::string(why) + " (format " + std::to_string(layout.format) + ", channels " + std::to_string(layout.channels) + ", channel " +
+                       std::to_string(layout.channel) + ")");
+    layout = bn::pcm_normalised(layout);
     if (n_sources < 1) return invalid("n_sources must be at least 1");
     if (segment_samples == 0 || segment_samples % 4 != 0) return invalid("segment_samples must be a positive multiple of 4");
     if (step_samples < 1 || step_samples > segment_samples) return invalid("step_samples must be in 1..segment_samples");
@@ -496,10 +504,11 @@ bn_status create_pool(int32_t device, int32_t n_sources, int32_t format, size_t 
     auto l = std::make_unique<bn_live>();
     l->device = device;
     l->n_sources = n_sources;
-    l->format = format;
-    l->esz = format == BN_PCM_I16 ? sizeof(int16_t) : sizeof(float);
-    l->in_i16 = format == BN_PCM_I16;
-    l->in_esz = l->esz;
+    l->in_layout = layout;
+    l->in_esz = bn::pcm_frame_bytes(layout);
+    // the ring stores mono int16 / float pushes as they are; any other layout lands in it as f32, converted by the scatter
+    l->format = bn::pcm_is_plain(layout) ? layout.format : BN_PCM_F32;
+    l->esz = l->format == BN_PCM_I16 ? sizeof(int16_t) : sizeof(float);
     l->S = segment_samples;
     l->step = step_samples;
     l->R = ring_samples;
@@ -522,7 +531,8 @@ bn_status create_pool(int32_t device, int32_t n_sources, int32_t format, size_t 
                                std::to_string(t.L) + "/" + std::to_string(t.M));
         }
     }
-    const size_t slab_b = (size_t)n_sources * ring_samples * l->esz;
+    size_t slab_b = 0;
+    if (!bn::pcm_ring_bytes((size_t)n_sources, ring_samples, l->esz, &slab_b)) return invalid("n_sources * ring_samples exceeds the address space");
     BN_HIP_TRY(l->stream.create(hipStreamNonBlocking));
     BN_HIP_TRY(l->scatter_ev.create(hipEventDisableTiming));
     for (auto &st : l->stage) BN_HIP_TRY(st.ev.create(hipEventDisableTiming));
@@ -539,7 +549,9 @@ extern "C" {
 
 bn_status bn_live_create(int32_t device, int32_t n_sources, int32_t format, size_t segment_samples, size_t step_samples, size_t ring_samples,
                          bn_live **out) {
-    return create_pool(device, n_sources, format, segment_samples, step_samples, ring_samples, 0, nullptr, 0, out);
+    if (out) *out = nullptr;
+    if (format != BN_PCM_I16 && format != BN_PCM_F32) return invalid("unknown PCM format " + std::to_string(format));
+    return create_pool(device, n_sources, bn::PcmLayout{format, 1, 0}, segment_samples, step_samples, ring_samples, 0, nullptr, 0, out);
 }
 
 bn_status bn_live_create_rates(int32_t device, int32_t n_sources, int32_t format, size_t segment_samples, size_t step_samples, size_t ring_samples,
@@ -548,7 +560,19 @@ bn_status bn_live_create_rates(int32_t device, int32_t n_sources, int32_t format
         if (out) *out = nullptr;
         return invalid("null argument");
     }
-    return create_pool(device, n_sources, format, segment_samples, step_samples, ring_samples, dst_rate, src_rates, zero_crossings, out);
+    if (out) *out = nullptr;
+    if (format != BN_PCM_I16 && format != BN_PCM_F32) return invalid("unknown PCM format " + std::to_string(format));
+    return create_pool(device, n_sources, bn::PcmLayout{format, 1, 0}, segment_samples, step_samples, ring_samples, dst_rate, src_rates, zero_crossings, out);
+}
+
+bn_status bn_live_create_layout(int32_t device, int32_t n_sources, const bn_pcm_layout *layout, size_t struct_size, size_t segment_samples,
+                                size_t step_samples, size_t ring_samples, uint32_t dst_rate, const uint32_t *src_rates, uint32_t zero_crossings,
+                                bn_live **out) {
+    if (!out) return invalid("null argument");
+    *out = nullptr;
+    bn::PcmLayout pl;
+    if (bn_status st = bn::read_pcm_layout(layout, struct_size, &pl); st != BN_OK) return st;
+    return create_pool(device, n_sources, pl, segment_samples, step_samples, ring_samples, dst_rate, src_rates, zero_crossings, out);
 }
 
 size_t bn_live_resampled_samples(uint32_t src_rate, uint32_t dst_rate, uint32_t zero_crossings, uint64_t pushed, int32_t closed) {

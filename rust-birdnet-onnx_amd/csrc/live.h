@@ -4,6 +4,8 @@
 
 #include <cstdint>
 
+#include "pcm_layout.h"
+
 namespace bn {
 
 // one row of a gather launch: window w of a slot's ring
@@ -54,18 +56,18 @@ struct LiveRsTile {
 constexpr uint32_t LIVE_RS_MAX_T = 512;          // taps per phase a resampling pool accepts (the history kernel holds T - 1 <= 2 * 256 - 1)
 constexpr uint32_t LIVE_RS_LDS_FLOATS = 16384;  // LDS budget of the resampling scatter: span, and the table when it fits beside it
 
-// dst [n, S] f32 <- rows of the slab (i16 / 32768 or f32); S % 4 == 0, ring_samples >= S, n <= LIVE_GATHER_ROWS
+// dst [n, S] f32 <- rows of the slab (a ring is mono int16, read as v / 32768, or f32); S % 4 == 0, ring_samples >= S, n <= LIVE_GATHER_ROWS
 void launch_live_gather(hipStream_t s, float *dst, const void *slab, int32_t is_i16, uint32_t ring_samples, uint32_t S, const LiveGatherRows &rows,
                         uint32_t n);
-// slab <- staged chunks; tiles and data may live in pinned host memory or on the device
-void launch_live_scatter(hipStream_t s, void *slab, int32_t is_i16, const LiveTile *tiles, uint32_t n_tiles, const void *data);
+// slab <- staged chunks; tiles and data may live in pinned host memory or on the device.  Mono int16 / float data is copied into a
+// ring of its own format; any other layout (pcm_layout.h) is converted frame by frame into an f32 ring, tiles counting frames
+void launch_live_scatter(hipStream_t s, void *slab, const PcmSrc &data, const LiveTile *tiles, uint32_t n_tiles);
 // slab (f32) <- the tiles' outputs: the T-tap fmaf chain of kernels.hip's resample_kernel over [history | staged chunk]; jobs,
 // tiles and data may live in pinned host memory or on the device; lds_bytes: the pool's dynamic LDS size
-void launch_live_resample(hipStream_t s, float *slab, int32_t in_i16, const LiveRsTable *tables, const float *coef, const float *hist,
-                          const LiveRsJob *jobs, const LiveRsTile *tiles, uint32_t n_tiles, const void *data, uint32_t lds_bytes);
+void launch_live_resample(hipStream_t s, float *slab, const PcmSrc &data, const LiveRsTable *tables, const float *coef, const float *hist,
+                          const LiveRsJob *jobs, const LiveRsTile *tiles, uint32_t n_tiles, uint32_t lds_bytes);
 // history <- the last T - 1 source samples of every job's stream after its push; launched after launch_live_resample on the
 // same stream (blocks of the resampling launch read the history, so it is not updated there)
-void launch_live_history(hipStream_t s, float *hist, int32_t in_i16, const LiveRsTable *tables, const LiveRsJob *jobs, uint32_t n_jobs,
-                         const void *data);
+void launch_live_history(hipStream_t s, float *hist, const PcmSrc &data, const LiveRsTable *tables, const LiveRsJob *jobs, uint32_t n_jobs);
 
 }  // namespace bn

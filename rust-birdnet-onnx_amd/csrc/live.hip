@@ -6,6 +6,9 @@
 //     0 (the zero-padded tail after close), i16 converts as v / 32768 exactly like windows_kernel.  grid (ceil(S/1024), rows)
 //   * live_scatter_kernel -- one workgroup per tile of a push's staged chunks; the host splits chunks at ring wraps and every
 //     LIVE_TILE samples, so a tile is one contiguous copy and lanes move consecutive samples.
+//   * live_scatter_frames_kernel -- the scatter of a pool whose pushes are interleaved frames or a format the ring does not store
+//     (bn_live_create_layout): the same tiles, counted in frames; lane i of a tile reads frame src + i through the layout's
+//     reader (pcm_read.h) and stores its f32 sample, so the ring holds exactly what a mono f32 pool fed those samples holds.
 //   * live_resample_kernel -- the scatter of a resampling pool (bn_live_create_rates): one workgroup per tile of consecutive
 //     FINAL outputs of one source.  The source span the tile's taps touch, [(n0*M)/L - (T/2-1), (n1*M)/L + T/2], is read
 //     ONCE into LDS as f32 -- from the source's history (the last T-1 samples before this push) and the staged chunk, 0
@@ -18,6 +21,7 @@
 //   * live_history_kernel -- one workgroup per job: the last T-1 source samples of the stream after the push, from the old
 //     history (shifted) and the staged chunk, read into registers before any is written.
 #include "live.h"
+#include "pcm_read.h"
 
 namespace bn {
 namespace {
@@ -53,25 +57,27 @@ __global__ __launch_bounds__(256) void live_scatter_kernel(T *__restrict__ slab,
     for (uint32_t i = threadIdx.x; i < t.len; i += 256u) dst[i] = src[i];
 }
 
-template <class T>
-__device__ __forceinline__ float live_to_f32(T v) {
-    if constexpr (sizeof(T) == 2) return (float)v * (1.0f / 32768.0f);
-    else return (float)v;
+template <class R>
+__global__ __launch_bounds__(256) void live_scatter_frames_kernel(float *__restrict__ slab, const LiveTile *__restrict__ tiles, const R data) {
+    const LiveTile t = tiles[blockIdx.x];
+    float *dst = slab + t.dst;
+    for (uint32_t i = threadIdx.x; i < t.len; i += 256u) dst[i] = data((uint64_t)t.src + i);
 }
 
-template <class T_>
+// R: the reader of the staged pushes (pcm_read.h), indexed in frames
+template <class R>
 __global__ __launch_bounds__(256) void live_resample_kernel(float *__restrict__ slab, const LiveRsTable *__restrict__ tables,
                                                             const float *__restrict__ coef, const float *__restrict__ hist,
                                                             const LiveRsJob *__restrict__ jobs, const LiveRsTile *__restrict__ tiles,
-                                                            const T_ *__restrict__ data) {
+                                                            const R data) {
     extern __shared__ float lds[];
     const LiveRsTile t = tiles[blockIdx.x];
     const LiveRsJob jb = jobs[t.job];
     float *dst = slab + t.dst;
-    const T_ *staged = data + jb.src;
+    const R staged = data.from(jb.src);
     if (jb.table == LIVE_RS_PASS) {
         const uint32_t first = (uint32_t)(t.n0 - jb.p0);
-        for (uint32_t i = threadIdx.x; i < t.len; i += 256u) dst[i] = live_to_f32(staged[first + i]);
+        for (uint32_t i = threadIdx.x; i < t.len; i += 256u) dst[i] = staged(first + i);
         return;
     }
     const LiveRsTable tb = tables[jb.table];
@@ -90,7 +96,7 @@ __global__ __launch_bounds__(256) void live_resample_kernel(float *__restrict__ 
         const int64_t q = q_lo + i;
         float v = 0.0f;
         if (q >= p0) {
-            if (q - p0 < (int64_t)jb.n_in) v = live_to_f32(staged[q - p0]);
+            if (q - p0 < (int64_t)jb.n_in) v = staged((uint64_t)(q - p0));
         } else if (q >= 0 && q >= h0) {
             v = hs[q - h0];
         }
@@ -114,14 +120,14 @@ __global__ __launch_bounds__(256) void live_resample_kernel(float *__restrict__ 
     }
 }
 
-template <class T_>
+template <class R>
 __global__ __launch_bounds__(256) void live_history_kernel(float *__restrict__ hist, const LiveRsTable *__restrict__ tables,
-                                                           const LiveRsJob *__restrict__ jobs, const T_ *__restrict__ data) {
+                                                           const LiveRsJob *__restrict__ jobs, const R data) {
     const LiveRsJob jb = jobs[blockIdx.x];
     if (jb.table == LIVE_RS_PASS || jb.n_in == 0) return;
     const uint32_t H = tables[jb.table].T - 1u;  // <= LIVE_RS_MAX_T - 1 = 2 * 256 - 1
     float *hs = hist + jb.hist;
-    const T_ *staged = data + jb.src;
+    const R staged = data.from(jb.src);
     // slot h of the new history holds stream sample p0 + n_in - H + h: staged sample n_in - H + h, or old slot h + n_in
     float v[2];
 #pragma unroll
@@ -130,7 +136,7 @@ __global__ __launch_bounds__(256) void live_history_kernel(float *__restrict__ h
         v[u] = 0.0f;
         if (h < H) {
             const int64_t k = (int64_t)jb.n_in - (int64_t)H + (int64_t)h;
-            v[u] = k >= 0 ? live_to_f32(staged[k]) : hs[h + jb.n_in];
+            v[u] = k >= 0 ? staged((uint64_t)k) : hs[h + jb.n_in];
         }
     }
     __syncthreads();
@@ -151,29 +157,33 @@ void launch_live_gather(hipStream_t s, float *dst, const void *slab, int32_t is_
     else hipLaunchKernelGGL(live_gather_kernel<float>, grid, dim3(256), 0, s, dst, static_cast<const float *>(slab), ring_samples, S, rows);
 }
 
-void launch_live_scatter(hipStream_t s, void *slab, int32_t is_i16, const LiveTile *tiles, uint32_t n_tiles, const void *data) {
+void launch_live_scatter(hipStream_t s, void *slab, const PcmSrc &data, const LiveTile *tiles, uint32_t n_tiles) {
     if (n_tiles == 0) return;
-    if (is_i16)
-        hipLaunchKernelGGL(live_scatter_kernel<int16_t>, dim3(n_tiles), dim3(256), 0, s, static_cast<int16_t *>(slab), tiles, static_cast<const int16_t *>(data));
-    else hipLaunchKernelGGL(live_scatter_kernel<float>, dim3(n_tiles), dim3(256), 0, s, static_cast<float *>(slab), tiles, static_cast<const float *>(data));
+    if (pcm_is_plain(data.layout)) {  // the ring stores what the pushes carry: a copy
+        if (data.layout.format == BN_PCM_I16)
+            hipLaunchKernelGGL(live_scatter_kernel<int16_t>, dim3(n_tiles), dim3(256), 0, s, static_cast<int16_t *>(slab), tiles,
+                               static_cast<const int16_t *>(data.base));
+        else
+            hipLaunchKernelGGL(live_scatter_kernel<float>, dim3(n_tiles), dim3(256), 0, s, static_cast<float *>(slab), tiles,
+                               static_cast<const float *>(data.base));
+        return;
+    }
+    pcm_visit(data, [&](auto rd) {
+        hipLaunchKernelGGL(live_scatter_frames_kernel<decltype(rd)>, dim3(n_tiles), dim3(256), 0, s, static_cast<float *>(slab), tiles, rd);
+    });
 }
 
-void launch_live_resample(hipStream_t s, float *slab, int32_t in_i16, const LiveRsTable *tables, const float *coef, const float *hist,
-                          const LiveRsJob *jobs, const LiveRsTile *tiles, uint32_t n_tiles, const void *data, uint32_t lds_bytes) {
+void launch_live_resample(hipStream_t s, float *slab, const PcmSrc &data, const LiveRsTable *tables, const float *coef, const float *hist,
+                          const LiveRsJob *jobs, const LiveRsTile *tiles, uint32_t n_tiles, uint32_t lds_bytes) {
     if (n_tiles == 0) return;
-    if (in_i16)
-        hipLaunchKernelGGL(live_resample_kernel<int16_t>, dim3(n_tiles), dim3(256), lds_bytes, s, slab, tables, coef, hist, jobs, tiles,
-                           static_cast<const int16_t *>(data));
-    else
-        hipLaunchKernelGGL(live_resample_kernel<float>, dim3(n_tiles), dim3(256), lds_bytes, s, slab, tables, coef, hist, jobs, tiles,
-                           static_cast<const float *>(data));
+    pcm_visit(data, [&](auto rd) {
+        hipLaunchKernelGGL(live_resample_kernel<decltype(rd)>, dim3(n_tiles), dim3(256), lds_bytes, s, slab, tables, coef, hist, jobs, tiles, rd);
+    });
 }
 
-void launch_live_history(hipStream_t s, float *hist, int32_t in_i16, const LiveRsTable *tables, const LiveRsJob *jobs, uint32_t n_jobs,
-                         const void *data) {
+void launch_live_history(hipStream_t s, float *hist, const PcmSrc &data, const LiveRsTable *tables, const LiveRsJob *jobs, uint32_t n_jobs) {
     if (n_jobs == 0) return;
-    if (in_i16) hipLaunchKernelGGL(live_history_kernel<int16_t>, dim3(n_jobs), dim3(256), 0, s, hist, tables, jobs, static_cast<const int16_t *>(data));
-    else hipLaunchKernelGGL(live_history_kernel<float>, dim3(n_jobs), dim3(256), 0, s, hist, tables, jobs, static_cast<const float *>(data));
+    pcm_visit(data, [&](auto rd) { hipLaunchKernelGGL(live_history_kernel<decltype(rd)>, dim3(n_jobs), dim3(256), 0, s, hist, tables, jobs, rd); });
 }
 
 }  // namespace bn
