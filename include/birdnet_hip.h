@@ -426,6 +426,88 @@ bn_status bn_recording_create_layout_resampled(int32_t device, const void *pcm, 
                                                uint32_t zero_crossings, bn_recording **out);
 bn_status bn_recording_view_channel(const bn_recording *r, int32_t channel, bn_recording **out);
 
+/*
+ * Window levels and list steps: analyse CHOSEN windows of many recordings.  No reference counterpart (the reference CLI runs every
+ * window of one file in order).  Two workloads: a mostly-quiet archive, where an amplitude gate picks the few windows worth the
+ * model (levels -> the host picks -> list steps), and a library of short clips, where one list step fills a batch from many files.
+ *
+ * bn_recording_levels: out[i] receives the levels of window first_window + i, i < count.  segment_samples, step_samples,
+ * first_window and count mean what they mean for bn_recording_windows (segment_samples % 4 == 0; a window k exists iff
+ * k * step_samples < bn_recording_samples), and a window's S = segment_samples samples are exactly the f32 values
+ * bn_recording_windows returns for it -- the layout rule's samples ("PCM layouts"), zeros past the end.  There is no second
+ * sample rule.
+ *
+ *   peak          max |s| over the window's S samples; exact
+ *   mean          (sum s) / S
+ *   mean_square   (sum s*s) / S         the divisor is always S, padding included: that is what the model sees
+ *   flags         BN_LEVEL_PADDED       iff the window reaches past the last sample (k * step + S > samples)
+ *                 BN_LEVEL_NONFINITE    iff any sample is NaN or +-Inf.  Then peak = mean_square = +Inf and mean = 0, whatever the
+ *                                       other samples are: such a window is never "quiet" to a gate that compares peak or
+ *                                       mean_square against a threshold
+ *
+ * Arithmetic.  Plain f32 operations, no fused multiply-add (s*s is rounded, then added); every partial sum is f32, in a fixed
+ * tree that is a function of S alone (csrc/levels.hip).  BN_LEVEL_SUM_DEPTH is the longest chain of additions any term passes
+ * through for S <= 2^20.  From it, against the float64 value of the same f32 samples and barring underflow of s*s:
+ *   mean_square   within (BN_LEVEL_SUM_DEPTH + 2) * 2^-24, relative (all terms are non-negative)
+ *   mean          within (BN_LEVEL_SUM_DEPTH + 1) * 2^-24 * mean|s|, absolute
+ * (derivation in DESIGN.md 7c).
+ *
+ * Invariance.  A window's four fields depend only on its S samples and on S: not on first_window, count, step_samples, the
+ * recording's length or its layout.  The same bits come from an I16 mono recording, an F32 mono recording of the rule's samples
+ * and a stereo I24 recording whose mix or selected channel gives those samples, and from any split of a window range into calls.
+ *
+ * The call blocks (on the host) on an asynchronous upload until the last sample its windows read has arrived, as
+ * bn_recording_windows does, and returns when `out` is written.  struct_size is sizeof(bn_window_level) as the caller compiled it;
+ * element i of `out` lies at byte offset i * struct_size, and bytes of an element past this header's struct are left alone.
+ * BN_ERR_INVALID_ARG, with a message: a NULL recording, a struct_size below the struct's, segment_samples that is 0 or no multiple
+ * of 4, step_samples == 0, a window range past the recording's windows, NULL `out` with count > 0.  count == 0 is BN_OK.
+ */
+#define BN_LEVEL_NONFINITE 1u
+#define BN_LEVEL_PADDED 2u
+#define BN_LEVEL_SUM_DEPTH 1034 /* 1024 (one of 1024 accumulators over S <= 2^20) + 2 (a lane's four) + 6 (a wave) + 2 (four waves) */
+typedef struct bn_window_level {
+    float peak;        /* max |s| over the window's S samples */
+    float mean;        /* sum s / S */
+    float mean_square; /* sum s*s / S */
+    uint32_t flags;    /* BN_LEVEL_NONFINITE | BN_LEVEL_PADDED */
+} bn_window_level;
+bn_status bn_recording_levels(const bn_recording *r, size_t segment_samples, size_t step_samples, size_t first_window,
+                              size_t count, bn_window_level *out, size_t struct_size);
+
+/*
+ * bn_step_window_list: bn_step_windows over an explicit list.  Row i of the batch is the S = sample_count frames of
+ * refs[i].recording from frame refs[i].start on, zeros past the end; start is any frame of the recording, no multiple of any step
+ * (a window centred on a peak is fine).  The rows are gathered on the device straight into the context's input buffer -- the
+ * recordings of one list may have different layouts -- and everything after the gather is the step of bn_step_windows: the row
+ * bits are those bn_step_windows produces for the same samples, the plan's graph is the one of that batch size (capture_fallbacks
+ * stays 0), and bn_step_results, bn_step_head_results, bn_step_prior_results, bn_step_index_results and bn_step_track_results read
+ * the results as after bn_step_live.  refs[i].source and refs[i].window are what an attached prior (its site map) and tracker see
+ * of row i, as bn_step_live's source_out[i] and window_out[i]: per source the tracker takes windows in increasing order, and a row
+ * whose window does not exceed its source's last is a stale row, as there.  Nothing of `refs` is read after the call returns.
+ *
+ * An asynchronously uploaded recording is waited for, on the host, up to the last frame any of its rows reads.
+ *
+ * struct_size is sizeof(bn_window_ref) as the caller compiled it; element i lies at byte offset i * struct_size.
+ * BN_ERR_INVALID_ARG, with a message, before anything is enqueued (the context stays as it was): a NULL context or list,
+ * a struct_size below the struct's, count == 0 or count > max_batch, a NULL recording, a recording on another device than the
+ * context, start >= bn_recording_samples(recording), a negative source, with a tracker attached a window of 2^31 or more, a top_k
+ * that bn_step_device refuses, and whatever an attached prior or tracker refuses of a bn_step_live over these sources (more
+ * sources than the site map or the tracker has).
+ *
+ * bn_recording_window_list: the gathered rows alone, copied back as host f32 [count, segment_samples] (segment_samples % 4 == 0),
+ * for tests; source and window are ignored, every recording lies on the first one's device, count == 0 is BN_OK.
+ */
+typedef struct bn_window_ref {
+    const bn_recording *recording;
+    uint64_t start;  /* first frame of the window; any value < bn_recording_samples(recording) */
+    int32_t source;  /* reported to an attached prior / tracker, as bn_step_live's sources */
+    uint64_t window; /* the window number reported to them */
+} bn_window_ref;
+bn_status bn_step_window_list(bn_ctx *c, const bn_window_ref *refs, size_t count, size_t struct_size, size_t top_k,
+                              int32_t has_min, float min_conf, int32_t sync);
+bn_status bn_recording_window_list(const bn_window_ref *refs, size_t count, size_t struct_size, size_t segment_samples,
+                                   float *host_out);
+
 /* Device view of the packed top-K rows of the last bn_step_device / bn_step_windows on this context:
  * [idx: m*k][conf: m*k (float bits)][count: m] for the m rows and k = min(top_k, num_species) of that step.
  * Valid until the next step; reading it must be ordered after the step on bn_ctx_stream(). */

@@ -211,12 +211,25 @@ class Recording {
     Recording(const void *pcm, size_t n_frames, const bn_pcm_layout &layout, int device = 0);
     /* the same device bytes read with another channel op (bn_recording_view_channel): no second upload */
     Recording view_channel(int32_t channel) const;
+    /* bn_recording_levels: peak, mean, mean square and flags of windows [first, first + count) of chunk_audio(segment_samples,
+     * step_samples), computed on the device over exactly the samples those windows hold (birdnet_hip.h, "Window levels and list
+     * steps"); count == SIZE_MAX means "to the last window".  Throws Error::Inference with the library's message on a refusal. */
+    std::vector<bn_window_level> levels(size_t segment_samples, size_t step_samples, size_t first = 0, size_t count = (size_t)-1) const;
     size_t n_samples() const { return n_samples_; }
     const bn_recording *raw() const { return rec_.get(); }
 
    private:
     std::shared_ptr<bn_recording> rec_;
     size_t n_samples_ = 0;
+};
+
+/* One row of Classifier::predict_window_list: the classifier's segment length of `recording` from frame `start` on, zeros past the
+ * end; `source` and `window` are what a prior or tracker attached to the context sees of the row (bn_window_ref). */
+struct WindowRef {
+    const Recording *recording = nullptr;
+    uint64_t start = 0;
+    int32_t source = 0;
+    uint64_t window = 0;
 };
 
 /* One chunk of a recording: start time as chunk_audio reports it + the prediction. */
@@ -263,6 +276,11 @@ class Classifier {
     /* Native extension: up to max_windows (<= ctx.max_batch_size()) ready windows of ALL live sources, oldest first (bn_step_live),
      * through one batch; labels, top_k, min_confidence, timeout and cancel as predict_recording.  Empty when nothing is ready. */
     std::vector<LiveChunkResult> predict_live(BatchInferenceContext &ctx, LiveSources &live, size_t max_windows, const InferenceOptions &options = {}) const;
+    /* Native extension: one batch over an explicit list of windows (bn_step_window_list): result i is row refs[i].  1 <= n <=
+     * ctx.max_batch_size(); the recordings may have different layouts; start is any frame of its recording.  With Recording::levels
+     * this is the gated loop for mostly-quiet archives, and it fills a batch from many short files.  labels, top_k, min_confidence,
+     * timeout and cancel as predict_live; a refusal of the library is Error::Inference with its message. */
+    std::vector<PredictionResult> predict_window_list(BatchInferenceContext &ctx, const WindowRef *refs, size_t n, const InferenceOptions &options = {}) const;
 
    private:
     friend class ClassifierBuilder;
@@ -494,6 +512,20 @@ int32_t bnh_live_close(bnh_live *l, int32_t source, bnh_error *err);
 size_t bnh_live_ready(const bnh_live *l, int32_t source);
 int32_t bnh_predict_live(const bnh_classifier *c, bnh_context *ctx, bnh_live *l, size_t max_windows, int64_t timeout_ns, const volatile int32_t *cancel,
                          bnh_results **out, int32_t *source_out, uint64_t *chunk_out, float *start_times, size_t cap, bnh_error *err);
+/* Recording + Recording::levels + Classifier::predict_window_list.  A bnh_recording is an uploaded recording (format / channels /
+ * channel are a bn_pcm_layout's fields; n_frames frames of `pcm`, which may be released when the call returns). */
+typedef struct bnh_recording bnh_recording;
+int32_t bnh_recording_create(const void *pcm, size_t n_frames, int32_t format, uint32_t channels, int32_t channel, int32_t device,
+                             bnh_recording **out, bnh_error *err);
+void bnh_recording_free(bnh_recording *r);
+size_t bnh_recording_samples(const bnh_recording *r);
+/* count == SIZE_MAX => to the last window; writes up to cap levels, *n_out = the number of windows asked for */
+int32_t bnh_recording_levels(const bnh_recording *r, size_t segment_samples, size_t step_samples, size_t first, size_t count,
+                             bn_window_level *out, size_t cap, size_t *n_out, bnh_error *err);
+/* row i: recordings[i] from frame starts[i]; sources / windows may be NULL (0 and the row's position) */
+int32_t bnh_predict_window_list(const bnh_classifier *c, bnh_context *ctx, const bnh_recording *const *recordings, const uint64_t *starts,
+                                const int32_t *sources, const uint64_t *windows, size_t n, int64_t timeout_ns, const volatile int32_t *cancel,
+                                bnh_results **out, bnh_error *err);
 size_t bnh_results_len(const bnh_results *r);
 int32_t bnh_result_model_type(const bnh_results *r, size_t i);
 size_t bnh_result_n_predictions(const bnh_results *r, size_t i);

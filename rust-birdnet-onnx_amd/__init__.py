@@ -56,6 +56,7 @@ ENGINE_SYMBOLS = [
     "bn_infer_windows", "bn_step_windows", "bn_ctx_step_device_rows", "bn_group_create", "bn_group_destroy", "bn_group_size",
     "bn_group_uses_rccl", "bn_group_get_stats", "bn_shard_range", "bn_group_analyze_recording", "bn_group_last_error", "bn_recording_create_resampled", "bn_resample_table", "bn_recording_read_f32", "bn_last_error",
     "bn_recording_create_layout", "bn_recording_create_layout_async", "bn_recording_create_layout_resampled", "bn_recording_view_channel", "bn_live_create_layout",
+    "bn_recording_levels", "bn_step_window_list", "bn_recording_window_list",
     "bn_index_create", "bn_index_free", "bn_index_size", "bn_index_dim", "bn_index_add_host", "bn_index_add_ctx", "bn_index_read",
     "bn_index_search", "bn_index_search_ids", "bn_index_assign", "bn_index_cluster",
     "bn_index_save", "bn_index_load", "bn_index_file_info", "bn_index_file_verify",
@@ -93,6 +94,7 @@ HOST_SYMBOLS = [
     "bnh_range_filter_scores", "bnh_range_filter_prior_row", "bnh_prior_create", "bnh_prior_free", "bnh_prior_handle",
     "bnh_context_attach_prior", "bnh_context_set_prior_site", "bnh_context_prior_results",
     "bnh_live_create", "bnh_live_create_rates", "bnh_live_create_layout", "bnh_predict_recording_layout", "bnh_live_free", "bnh_live_push", "bnh_live_close", "bnh_live_ready", "bnh_predict_live",
+    "bnh_recording_create", "bnh_recording_free", "bnh_recording_samples", "bnh_recording_levels", "bnh_predict_window_list",
 ]
 
 
@@ -148,6 +150,19 @@ class BnIndexFileInfo(C.Structure):
 
 class BnPcmLayout(C.Structure):
     _fields_ = [("format", C.c_int32), ("channels", C.c_uint32), ("channel", C.c_int32)]
+
+
+class BnWindowLevel(C.Structure):
+    _fields_ = [("peak", C.c_float), ("mean", C.c_float), ("mean_square", C.c_float), ("flags", C.c_uint32)]
+
+
+class BnWindowRef(C.Structure):
+    _fields_ = [("recording", C.c_void_p), ("start", C.c_uint64), ("source", C.c_int32), ("window", C.c_uint64)]
+
+
+BN_LEVEL_NONFINITE, BN_LEVEL_PADDED = 1, 2  # bn_window_level.flags
+BN_LEVEL_SUM_DEPTH = 1034  # include/birdnet_hip.h: the longest chain of f32 additions behind a level, for S <= 2^20
+LEVEL_DTYPE = np.dtype([("peak", np.float32), ("mean", np.float32), ("mean_square", np.float32), ("flags", np.uint32)])
 
 
 class BnIndexFilter(C.Structure):
@@ -244,6 +259,9 @@ def _load() -> C.CDLL:
         "bn_recording_create_layout_async": (i32, [i32, vp, sz, C.POINTER(BnPcmLayout), sz, C.POINTER(vp)]),
         "bn_recording_create_layout_resampled": (i32, [i32, vp, sz, C.POINTER(BnPcmLayout), sz, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(vp)]),
         "bn_recording_view_channel": (i32, [vp, i32, C.POINTER(vp)]),
+        "bn_recording_levels": (i32, [vp, sz, sz, sz, sz, C.POINTER(BnWindowLevel), sz]),
+        "bn_step_window_list": (i32, [vp, C.POINTER(BnWindowRef), sz, sz, sz, i32, C.c_float, i32]),
+        "bn_recording_window_list": (i32, [C.POINTER(BnWindowRef), sz, sz, sz, f32p]),
         "bn_last_error": (sz, [C.c_char_p, sz]),
         "bn_ctx_step_device_rows": (i32, [vp, C.POINTER(u32p)]),
         "bn_group_create": (i32, [C.POINTER(vp), C.POINTER(C.c_int32), i32, sz, i32, C.POINTER(vp)]),
@@ -412,6 +430,12 @@ def _load() -> C.CDLL:
         "bnh_live_push": (i32, [vp, i32, vp, sz, C.POINTER(BnhError)]),
         "bnh_live_close": (i32, [vp, i32, C.POINTER(BnhError)]),
         "bnh_live_ready": (sz, [vp, i32]),
+        "bnh_recording_create": (i32, [vp, sz, i32, C.c_uint32, i32, i32, C.POINTER(vp), C.POINTER(BnhError)]),
+        "bnh_recording_free": (None, [vp]),
+        "bnh_recording_samples": (sz, [vp]),
+        "bnh_recording_levels": (i32, [vp, sz, sz, sz, sz, C.POINTER(BnWindowLevel), sz, C.POINTER(sz), C.POINTER(BnhError)]),
+        "bnh_predict_window_list": (i32, [vp, vp, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(C.c_uint64), sz, C.c_int64,
+                                          C.POINTER(C.c_int32), C.POINTER(vp), C.POINTER(BnhError)]),
         "bnh_predict_live": (i32, [vp, vp, vp, sz, C.c_int64, C.POINTER(C.c_int32), C.POINTER(vp), C.POINTER(C.c_int32),
                                    C.POINTER(C.c_uint64), f32p, sz, C.POINTER(BnhError)]),
         "bnh_results_len": (sz, [vp]),
@@ -751,6 +775,55 @@ class Classifier:
         results = _collect(res)
         return [(int(src[i]), int(chunk[i]), float(times[i]), r) for i, r in enumerate(results)]
 
+    def predict_window_list(self, context: BatchInferenceContext, refs, options: Optional[InferenceOptions] = None) -> list:
+        """Classifier::predict_window_list: one batch over an explicit list of (HostRecording, start[, source[, window]]) rows;
+        result i is row i."""
+        options = options or InferenceOptions()
+        t, c = options._raw()
+        rows = [tuple(r) for r in refs]
+        n = len(rows)
+        recs = (C.c_void_p * max(n, 1))(*[None if r[0] is None else r[0]._h for r in rows])
+        starts = np.array([int(r[1]) for r in rows], dtype=np.uint64)
+        sources = np.array([int(r[2]) if len(r) > 2 else 0 for r in rows], dtype=np.int32)
+        windows = np.array([int(r[3]) if len(r) > 3 else i for i, r in enumerate(rows)], dtype=np.uint64)
+        res, err = C.c_void_p(), BnhError()
+        if lib.bnh_predict_window_list(self._h, context._h, recs, starts.ctypes.data_as(C.POINTER(C.c_uint64)), sources.ctypes.data_as(C.POINTER(C.c_int32)),
+                                       windows.ctypes.data_as(C.POINTER(C.c_uint64)), n, t, c, C.byref(res), C.byref(err)):
+            raise Error(err)
+        return _collect(res)
+
+
+class HostRecording:
+    """birdnet::Recording through the host mirror: interleaved frames in any format uploaded once (format / channels / channel are a
+    bn_pcm_layout's fields), for levels() and Classifier.predict_window_list."""
+
+    def __init__(self, pcm, fmt: int = BN_PCM_I16, channels: int = 1, channel: int = 0, device: int = 0):
+        a = np.frombuffer(pcm, dtype=np.uint8) if isinstance(pcm, (bytes, bytearray, memoryview)) else np.ascontiguousarray(pcm).reshape(-1).view(np.uint8)
+        fb = PCM_SAMPLE_BYTES.get(fmt, 1) * max(int(channels), 1)
+        if a.shape[0] % fb:
+            raise ValueError(f"{a.shape[0]} bytes are no whole number of {fb}-byte frames")
+        h, err = C.c_void_p(), BnhError()
+        if lib.bnh_recording_create(a.ctypes.data_as(C.c_void_p), a.shape[0] // fb, fmt, channels, channel, device, C.byref(h), C.byref(err)):
+            raise Error(err)
+        self._h = h
+        self.n_samples = int(lib.bnh_recording_samples(h))
+
+    def __del__(self):
+        if getattr(self, "_h", None) and lib is not None:
+            lib.bnh_recording_free(self._h)
+            self._h = None
+
+    def levels(self, segment_samples: int, step_samples: int, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """Recording::levels: a LEVEL_DTYPE array of windows [first, first + count) (count None: to the last window)."""
+        want = (1 << 64) - 1 if count is None else count
+        cap = max(int(lib.bn_chunk_count(self.n_samples, step_samples)) if step_samples else 0, 0 if count is None else count, 1)
+        out = np.zeros(cap, dtype=LEVEL_DTYPE)
+        n, err = C.c_size_t(), BnhError()
+        if lib.bnh_recording_levels(self._h, segment_samples, step_samples, first, want, out.ctypes.data_as(C.POINTER(BnWindowLevel)), cap, C.byref(n),
+                                    C.byref(err)):
+            raise Error(err)
+        return out[:n.value].copy()
+
 
 class LiveSources:
     """birdnet::LiveSources: live pools through the host mirror (windows of the classifier's segment length, chunk_audio's step
@@ -1051,6 +1124,15 @@ class Context:
         if st:
             raise EngineError(st)
 
+    def step_window_list(self, refs, top_k: int = 10, min_confidence: Optional[float] = None, sync: bool = False):
+        """bn_step_window_list: one hot-path pass over an explicit list of windows.  refs: (recording, start[, source[, window]]) per
+        row -- the S frames of `recording` from frame `start`, reported to an attached prior / tracker as window `window` of `source`
+        (defaults 0 and the row's position).  Results through step_results(len(refs)) and the other step_*_results."""
+        arr, keep = window_refs(refs)
+        st = lib.bn_step_window_list(self._h, arr, len(keep), C.sizeof(BnWindowRef), top_k, *_min_args(min_confidence), 1 if sync else 0)
+        if st:
+            raise EngineError(st)
+
     def step_live(self, live: "Live", max_windows: int, top_k: int = 10, min_confidence: Optional[float] = None,
                   sync: bool = False):
         """bn_step_live: up to max_windows ready windows of a live pool through the hot path; returns (sources, windows) of the
@@ -1198,6 +1280,29 @@ def _join_uploads():
 atexit.register(_join_uploads)
 
 
+def window_refs(refs):
+    """A bn_window_ref array of (recording, start[, source[, window]]) rows, and the recordings it points at (keep them alive as long
+    as the array is used)."""
+    rows = [tuple(r) for r in refs]
+    arr = (BnWindowRef * max(len(rows), 1))()
+    for i, r in enumerate(rows):
+        arr[i].recording = None if r[0] is None else r[0]._h
+        arr[i].start = int(r[1])
+        arr[i].source = int(r[2]) if len(r) > 2 else 0
+        arr[i].window = int(r[3]) if len(r) > 3 else i
+    return arr, rows
+
+
+def recording_window_list(refs, segment_samples: int) -> np.ndarray:
+    """bn_recording_window_list: the rows a list step would gather, copied back: f32 [len(refs), segment_samples]."""
+    arr, keep = window_refs(refs)
+    out = np.zeros((len(keep), segment_samples), dtype=np.float32)
+    st = lib.bn_recording_window_list(arr, len(keep), C.sizeof(BnWindowRef), segment_samples, out.ctypes.data_as(C.POINTER(C.c_float)))
+    if st:
+        raise EngineError(st)
+    return out
+
+
 class Recording:
     """bn_recording: a mono recording uploaded once in its storage format (int16 or float32)."""
 
@@ -1298,6 +1403,17 @@ class Recording:
         """chunk_audio on the device, copied back: f32 [count, segment_samples]."""
         out = np.zeros((count, segment_samples), dtype=np.float32)
         st = lib.bn_recording_windows(self._h, segment_samples, step_samples, first, count, out.ctypes.data_as(C.POINTER(C.c_float)))
+        if st:
+            raise EngineError(st)
+        return out
+
+    def levels(self, segment_samples: int, step_samples: int, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """bn_recording_levels: peak, mean, mean_square and flags of windows [first, first + count) as a LEVEL_DTYPE array, computed on
+        the device over exactly the samples windows() returns (count None: to the last window)."""
+        count = self.n_windows(step_samples) - first if count is None else count
+        out = np.zeros(max(count, 0), dtype=LEVEL_DTYPE)
+        st = lib.bn_recording_levels(self._h, segment_samples, step_samples, first, count, out.ctypes.data_as(C.POINTER(BnWindowLevel)),
+                                     C.sizeof(BnWindowLevel))
         if st:
             raise EngineError(st)
         return out

@@ -25,7 +25,9 @@
 #include "detect.h"
 #include "engine.h"
 #include "kernels.h"
+#include "levels.h"
 #include "plan_rules.h"
+#include "window_list_plan.h"
 
 using namespace bn;
 
@@ -1838,6 +1840,156 @@ bn_status bn_step_windows(bn_ctx *c, const bn_recording *r, size_t step_samples,
     if (e != hipSuccess) return fail(BN_ERR_BACKEND, std::string("window kernel launch failed: ") + hipGetErrorString(e));
     // row i is window first_window + i of the tracker attachment's source
     return bn::step_device(c, c->d_input, bn::StepRows{count, true, nullptr, nullptr, first_window}, top_k, has_min, min_conf, sync);
+}
+
+// ---- window levels and list steps (include/birdnet_hip.h, "Window levels and list steps"; kernels in levels.hip) ----
+bn_status bn_recording_levels(const bn_recording *r, size_t segment_samples, size_t step_samples, size_t first_window, size_t count,
+                              bn_window_level *out, size_t struct_size) {
+    if (struct_size < sizeof(bn_window_level)) return fail(BN_ERR_INVALID_ARG, "struct_size is below sizeof(bn_window_level)");
+    bn_status st = check_windows(r, segment_samples, step_samples, first_window, count);
+    if (st != BN_OK) return st;
+    if (count == 0) return BN_OK;
+    if (!out) return fail(BN_ERR_INVALID_ARG, "null output buffer");
+    BN_HIP_TRY(bn::use_device(r->device));
+    // one workgroup per window, at most 2^20 windows per launch
+    const size_t piece = (size_t)1 << 20;
+    DeviceBuf<WindowLevel> d;
+    BN_HIP_TRY(d.alloc(std::min(piece, count) * sizeof(WindowLevel)));
+    std::vector<WindowLevel> rows;  // only for a caller whose struct is longer than this header's
+    if (struct_size != sizeof(bn_window_level)) rows.resize(std::min(piece, count));
+    for (size_t done = 0; done < count; done += piece) {
+        const size_t n = std::min(piece, count - done);
+        (void)hipGetLastError();
+        launch_levels(nullptr, d, r->src(), r->n_samples, (uint64_t)(first_window + done) * step_samples, step_samples, (uint32_t)segment_samples,
+                      (uint32_t)n);
+        hipError_t e = hipGetLastError();
+        void *host = rows.empty() ? static_cast<void *>(out + done) : static_cast<void *>(rows.data());
+        if (e == hipSuccess) e = gated::Memcpy(host, d, n * sizeof(WindowLevel), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return fail(BN_ERR_BACKEND, std::string("level kernel failed: ") + hipGetErrorString(e));
+        for (size_t i = 0; i < rows.size() && i < n; i++) memcpy(reinterpret_cast<char *>(out) + (done + i) * struct_size, &rows[i], sizeof(WindowLevel));
+    }
+    return BN_OK;
+}
+
+namespace {
+// a caller's list of bn_window_ref, read and refused: its distinct recordings, its rows, and the plan of its gather
+struct WindowList {
+    std::vector<const bn_recording *> recs;
+    std::vector<wlist::Row> rows;
+    std::vector<int32_t> sources;
+    std::vector<uint64_t> windows;
+    wlist::Plan plan;
+};
+}  // namespace
+
+// `device` < 0: every recording lies where the first one does
+static bn_status read_window_list(const bn_window_ref *refs, size_t count, size_t struct_size, size_t S, int32_t device, WindowList *out) {
+    if (!refs) return fail(BN_ERR_INVALID_ARG, "null window list");
+    if (struct_size < sizeof(bn_window_ref)) return fail(BN_ERR_INVALID_ARG, "struct_size is below sizeof(bn_window_ref)");
+    if (S == 0 || S % 4 != 0 || S > 0xffffffffull) return fail(BN_ERR_INVALID_ARG, "segment_samples must be a positive multiple of 4");
+    // before anything is sized by the caller's count (build() repeats the first for the stand-alone plan check)
+    if (count > 0xffffffffull) return fail(BN_ERR_INVALID_ARG, "a window list holds fewer than 2^32 rows");
+    if (count > SIZE_MAX / sizeof(float) / S) return fail(BN_ERR_INVALID_ARG, "count * segment_samples exceeds the address space");
+    const bool of_ctx = device >= 0;
+    std::map<const bn_recording *, uint32_t> seen;
+    std::vector<wlist::Rec> infos;
+    try {
+        out->rows.resize(count);
+        out->sources.resize(count);
+        out->windows.resize(count);
+    } catch (const std::exception &) {  // must not cross the C boundary
+        return fail(BN_ERR_INVALID_ARG, "no host memory for a window list of " + std::to_string(count) + " rows");
+    }
+    for (size_t i = 0; i < count; i++) {
+        bn_window_ref ref;  // through the caller's stride, whatever its alignment
+        memcpy(&ref, reinterpret_cast<const char *>(refs) + i * struct_size, sizeof(ref));
+        if (!ref.recording) return fail(BN_ERR_INVALID_ARG, "row " + std::to_string(i) + ": null recording");
+        if (device < 0) device = ref.recording->device;
+        if (ref.recording->device != device)
+            return fail(BN_ERR_INVALID_ARG, "row " + std::to_string(i) + ": its recording lives on device " + std::to_string(ref.recording->device) +
+                                                ", the " + (of_ctx ? "context" : "list's first recording") + " on device " + std::to_string(device));
+        auto it = seen.find(ref.recording);
+        if (it == seen.end()) {
+            it = seen.emplace(ref.recording, (uint32_t)out->recs.size()).first;
+            out->recs.push_back(ref.recording);
+            infos.push_back(wlist::Rec{ref.recording->layout, (uint64_t)ref.recording->n_samples});
+        }
+        out->rows[i] = wlist::Row{it->second, ref.start};
+        out->sources[i] = ref.source;
+        out->windows[i] = ref.window;
+    }
+    return wlist::build(infos, out->rows.data(), count, S, &out->plan);
+}
+
+// an asynchronous recording: the last frame any of its rows reads must have arrived before the gather is launched
+static bn_status wait_window_list(const WindowList &wl) {
+    for (size_t r = 0; r < wl.recs.size(); r++)
+        if (wl.plan.used[r] && !recording_wait_samples(wl.recs[r], (size_t)wl.plan.last[r])) return fail(BN_ERR_BACKEND, "recording upload failed");
+    return BN_OK;
+}
+
+// the gather of a read list on `s`: one launch per reader kind and 128 rows, row i of the list to row i of dst [count, S]
+static void launch_list_rows(hipStream_t s, float *dst, uint32_t S, const WindowList &wl) {
+    std::vector<WindowListSrc> rows;
+    for (const wlist::Launch &ln : wl.plan.launches) {
+        rows.resize(ln.count);
+        for (size_t j = 0; j < ln.count; j++) {
+            const uint32_t i = wl.plan.order[ln.first + j];
+            const bn_recording *rc = wl.recs[wl.rows[i].rec];
+            const char *at = static_cast<const char *>(rc->store->d_pcm.get()) + pcm_frame_offset(rc->layout, (size_t)wl.rows[i].start);
+            rows[j] = WindowListSrc{PcmSrc{at, rc->layout}, (uint32_t)wlist::valid_frames(wl.rows[i].start, rc->n_samples, S), i};
+        }
+        launch_window_list(s, dst, S, rows.data(), (uint32_t)ln.count);  // the reader, and its fields per row, are pcm_visit's
+    }
+}
+
+bn_status bn_recording_window_list(const bn_window_ref *refs, size_t count, size_t struct_size, size_t segment_samples, float *host_out) {
+    if (count == 0) return BN_OK;
+    WindowList wl;
+    bn_status st = read_window_list(refs, count, struct_size, segment_samples, -1, &wl);
+    if (st != BN_OK) return st;
+    if (!host_out) return fail(BN_ERR_INVALID_ARG, "null host buffer");
+    if ((st = wait_window_list(wl)) != BN_OK) return st;
+    BN_HIP_TRY(bn::use_device(wl.recs[0]->device));
+    DeviceBuf<float> d;
+    BN_HIP_TRY(d.alloc(count * segment_samples * sizeof(float)));
+    bn::clear_launch_state();
+    launch_list_rows(nullptr, d, (uint32_t)segment_samples, wl);
+    if ((st = bn::check_launch("window list gather")) != BN_OK) return st;
+    hipError_t e = gated::Memcpy(host_out, d, count * segment_samples * sizeof(float), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(BN_ERR_BACKEND, std::string("window list gather failed: ") + hipGetErrorString(e));
+    return BN_OK;
+}
+
+bn_status bn_step_window_list(bn_ctx *c, const bn_window_ref *refs, size_t count, size_t struct_size, size_t top_k, int32_t has_min, float min_conf,
+                              int32_t sync) {
+    if (!c) return fail(BN_ERR_INVALID_ARG, "null context");
+    bn::CtxStepInput ci;
+    bn_status st = bn::ctx_step_input(c, top_k, &ci);
+    if (st != BN_OK) return st;
+    if (count == 0) return fail(BN_ERR_INVALID_ARG, "an empty window list");
+    if (count > ci.max_batch) return fail(BN_ERR_INVALID_ARG, "batch size " + std::to_string(count) + " exceeds context max " + std::to_string(ci.max_batch));
+    WindowList wl;
+    if ((st = read_window_list(refs, count, struct_size, ci.sample_count, ci.device, &wl)) != BN_OK) return st;
+    size_t n_sources = 0;
+    for (size_t i = 0; i < count; i++) {
+        if (wl.sources[i] < 0) return fail(BN_ERR_INVALID_ARG, "row " + std::to_string(i) + ": source " + std::to_string(wl.sources[i]) + " is negative");
+        n_sources = std::max(n_sources, (size_t)wl.sources[i] + 1);
+        // the list brings its own window numbers: what the tracker would refuse of a row only after the step was enqueued
+        if (c->track && wl.windows[i] >= ((uint64_t)1 << 31))
+            return fail(BN_ERR_INVALID_ARG, "row " + std::to_string(i) + ": a tracked window number must be below 2^31");
+    }
+    // what an attached prior and tracker refuse of a live step over that many sources
+    if ((st = bn::ctx_step_check(c, n_sources, 0, 0)) != BN_OK) return st;
+    if ((st = wait_window_list(wl)) != BN_OK) return st;
+    BN_HIP_TRY(bn::use_device(ci.device));
+    // stream order keeps the gather behind whatever the context still has in flight; the descriptors are kernel arguments, so
+    // nothing here can race a step in flight
+    bn::clear_launch_state();
+    launch_list_rows(ci.stream, ci.d_input, (uint32_t)ci.sample_count, wl);
+    if ((st = bn::check_launch("window list gather")) != BN_OK) return st;
+    // row i is window refs[i].window of source refs[i].source (the copies made above, read before the step returns)
+    return bn::step_device(c, ci.d_input, bn::StepRows{count, true, wl.sources.data(), wl.windows.data(), 0}, top_k, has_min, min_conf, sync);
 }
 
 size_t bn_model_survey(const char *onnx_path, char *buf, size_t cap, bn_status *status) {

@@ -15,6 +15,9 @@ struct bnh_context {
 struct bnh_live {
     LiveSources live;
 };
+struct bnh_recording {
+    Recording rec;
+};
 struct bnh_prior {
     std::unique_ptr<Prior> p;
 };
@@ -271,6 +274,42 @@ int32_t bnh_predict_live(const bnh_classifier *c, bnh_context *ctx, bnh_live *l,
             }
             r->v.push_back(std::move(rows[i].result));
         }
+        *out = r.release();
+    });
+}
+
+int32_t bnh_recording_create(const void *pcm, size_t n_frames, int32_t format, uint32_t channels, int32_t channel, int32_t device, bnh_recording **out,
+                             bnh_error *err) {
+    if (!out) return set_other(err, "null argument");
+    *out = nullptr;
+    return guarded(err, [&] { *out = new bnh_recording{Recording(pcm, n_frames, bn_pcm_layout{format, channels, channel}, device)}; });
+}
+void bnh_recording_free(bnh_recording *r) { delete r; }
+size_t bnh_recording_samples(const bnh_recording *r) { return r ? r->rec.n_samples() : 0; }
+
+int32_t bnh_recording_levels(const bnh_recording *r, size_t segment_samples, size_t step_samples, size_t first, size_t count, bn_window_level *out,
+                             size_t cap, size_t *n_out, bnh_error *err) {
+    if (n_out) *n_out = 0;
+    if (!r) return set_other(err, "null recording");
+    return guarded(err, [&] {
+        const std::vector<bn_window_level> lv = r->rec.levels(segment_samples, step_samples, first, count);
+        if (n_out) *n_out = lv.size();
+        if (out) memcpy(out, lv.data(), std::min(cap, lv.size()) * sizeof(bn_window_level));
+    });
+}
+
+int32_t bnh_predict_window_list(const bnh_classifier *c, bnh_context *ctx, const bnh_recording *const *recordings, const uint64_t *starts,
+                                const int32_t *sources, const uint64_t *windows, size_t n, int64_t timeout_ns, const volatile int32_t *cancel,
+                                bnh_results **out, bnh_error *err) {
+    if (out) *out = nullptr;
+    if (!c || !ctx || !out || (n && (!recordings || !starts))) return set_other(err, "null argument");
+    return guarded(err, [&] {
+        InferenceOptions o = make_opts(timeout_ns, cancel);
+        std::vector<WindowRef> refs(n);
+        for (size_t i = 0; i < n; i++)
+            refs[i] = WindowRef{recordings[i] ? &recordings[i]->rec : nullptr, starts[i], sources ? sources[i] : 0, windows ? windows[i] : (uint64_t)i};
+        auto r = std::make_unique<bnh_results>();
+        r->v = c->cl.predict_window_list(*ctx->ctx, refs.data(), n, o);
         *out = r.release();
     });
 }

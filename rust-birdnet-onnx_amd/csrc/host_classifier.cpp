@@ -320,6 +320,24 @@ Recording Recording::view_channel(int32_t channel) const {
     return v;
 }
 
+std::vector<bn_window_level> Recording::levels(size_t segment_samples, size_t step_samples, size_t first, size_t count) const {
+    if (count == (size_t)-1) {
+        const size_t total = bn_chunk_count(n_samples_, step_samples);
+        count = total > first ? total - first : 0;
+    }
+    // never an empty vector's data(): a count the library refuses (past the recording's windows) must reach it with a buffer
+    std::vector<bn_window_level> out;
+    try {
+        out.resize(count);
+    } catch (const std::exception &) {
+        throw inference("window range exceeds the address space");
+    }
+    bn_window_level none{};
+    if (bn_recording_levels(rec_.get(), segment_samples, step_samples, first, count, count ? out.data() : &none, sizeof(bn_window_level)) != BN_OK)
+        throw inference(last_backend_error());
+    return out;
+}
+
 std::vector<ChunkResult> Classifier::predict_recording(BatchInferenceContext &ctx, const Recording &rec, float overlap_secs, size_t first_chunk, size_t count,
                                                        const InferenceOptions &options) const {
     const ModelConfig &cfg = inner_->config;
@@ -395,6 +413,49 @@ void LiveSources::reset(int32_t source) {
     if (bn_live_reset(live_.get(), source) != BN_OK) throw inference(last_backend_error());
 }
 
+// The end of an asynchronous step of n rows (bn_step_live, bn_step_window_list): wait for it, honouring cancel / deadline like
+// bn_infer_windows (the stream is polled), then the rows as PredictionResults
+static std::vector<PredictionResult> finish_step(ClassifierInner &in, bn_ctx *c, size_t n, const InferenceOptions &options,
+                                                 std::chrono::steady_clock::time_point t0, const volatile int32_t *cancel, const char *what) {
+    hipStream_t stream = static_cast<hipStream_t>(bn_ctx_stream(c));
+    for (;;) {
+        const hipError_t q = hipStreamQuery(stream);
+        if (q == hipSuccess) break;
+        if (q != hipErrorNotReady) throw inference(std::string(what) + " failed: " + hipGetErrorString(q));
+        if (cancel && *cancel) throw from_status(BN_ERR_CANCELLED, options);
+        if (options.timeout && std::chrono::steady_clock::now() - t0 > *options.timeout) throw from_status(BN_ERR_TIMEOUT, options);
+        std::this_thread::sleep_for(std::chrono::microseconds(50));
+    }
+    const float *logits = nullptr, *conf = nullptr;
+    const uint32_t *idx = nullptr, *cnt = nullptr;
+    size_t kstride = 0;
+    if (bn_step_results(c, &logits, &idx, &conf, &cnt, &kstride) != BN_OK) throw inference(last_backend_error());
+    size_t N = in.config.num_species, E = in.config.embedding_dim.value_or(0);
+    {
+        const float *dp = nullptr;
+        size_t row = 0;
+        if (bn_ctx_output_device(c, in.raw_cfg.logits_output, &dp, &row) == BN_OK) N = row;
+        if (E && bn_ctx_output_device(c, in.raw_cfg.embedding_output, &dp, &row) == BN_OK) E = row;
+    }
+    std::vector<float> emb(n * E);
+    if (E && bn_ctx_read_output(c, in.raw_cfg.embedding_output, n, emb.data()) != BN_OK) throw inference(last_backend_error());
+    std::vector<PredictionResult> out;
+    out.reserve(n);
+    for (size_t i = 0; i < n; i++) {
+        PredictionResult r;
+        r.model_type = in.config.model_type;
+        r.raw_scores.assign(logits + i * N, logits + (i + 1) * N);
+        if (E) r.embeddings = std::vector<float>(emb.begin() + i * E, emb.begin() + (i + 1) * E);
+        const size_t k = in.top_k ? cnt[i] : 0;
+        for (size_t j = 0; j < k; j++) {
+            const size_t id = idx[i * kstride + j];
+            r.predictions.push_back(Prediction{id < in.labels.size() ? in.labels[id] : "unknown_" + std::to_string(id), conf[i * kstride + j], id});
+        }
+        out.push_back(std::move(r));
+    }
+    return out;
+}
+
 std::vector<LiveChunkResult> Classifier::predict_live(BatchInferenceContext &ctx, LiveSources &live, size_t max_windows,
                                                       const InferenceOptions &options) const {
     ClassifierInner &in = *inner_;
@@ -410,46 +471,29 @@ std::vector<LiveChunkResult> Classifier::predict_live(BatchInferenceContext &ctx
     bn_status st = bn_step_live(ctx.ctx_, live.raw(), n_ready, std::max<size_t>(in.top_k, 1), in.min_confidence ? 1 : 0,
                                 in.min_confidence.value_or(0.0f), src.data(), win.data(), &n, 0);
     if (st != BN_OK) throw from_status(st, options);
-    // wait for the step, honouring cancel / deadline like bn_infer_windows (the stream is polled)
-    hipStream_t stream = static_cast<hipStream_t>(bn_ctx_stream(ctx.ctx_));
-    for (;;) {
-        const hipError_t q = hipStreamQuery(stream);
-        if (q == hipSuccess) break;
-        if (q != hipErrorNotReady) throw inference(std::string("live step failed: ") + hipGetErrorString(q));
-        if (cancel && *cancel) throw from_status(BN_ERR_CANCELLED, options);
-        if (options.timeout && std::chrono::steady_clock::now() - t0 > *options.timeout) throw from_status(BN_ERR_TIMEOUT, options);
-        std::this_thread::sleep_for(std::chrono::microseconds(50));
-    }
-    const float *logits = nullptr, *conf = nullptr;
-    const uint32_t *idx = nullptr, *cnt = nullptr;
-    size_t kstride = 0;
-    if (bn_step_results(ctx.ctx_, &logits, &idx, &conf, &cnt, &kstride) != BN_OK) throw inference(last_backend_error());
-    size_t N = in.config.num_species, E = in.config.embedding_dim.value_or(0);
-    {
-        const float *dp = nullptr;
-        size_t row = 0;
-        if (bn_ctx_output_device(ctx.ctx_, in.raw_cfg.logits_output, &dp, &row) == BN_OK) N = row;
-        if (E && bn_ctx_output_device(ctx.ctx_, in.raw_cfg.embedding_output, &dp, &row) == BN_OK) E = row;
-    }
-    std::vector<float> emb(n * E);
-    if (E && bn_ctx_read_output(ctx.ctx_, in.raw_cfg.embedding_output, n, emb.data()) != BN_OK) throw inference(last_backend_error());
+    std::vector<PredictionResult> rows = finish_step(in, ctx.ctx_, n, options, t0, cancel, "live step");
     const float sr = (float)in.config.sample_rate;
     std::vector<LiveChunkResult> out;
     out.reserve(n);
-    for (size_t i = 0; i < n; i++) {
-        PredictionResult r;
-        r.model_type = in.config.model_type;
-        r.raw_scores.assign(logits + i * N, logits + (i + 1) * N);
-        if (E) r.embeddings = std::vector<float>(emb.begin() + i * E, emb.begin() + (i + 1) * E);
-        const size_t c = in.top_k ? cnt[i] : 0;
-        for (size_t j = 0; j < c; j++) {
-            const size_t id = idx[i * kstride + j];
-            r.predictions.push_back(Prediction{id < in.labels.size() ? in.labels[id] : "unknown_" + std::to_string(id), conf[i * kstride + j], id});
-        }
-        // start_time = pos as f32 / sample_rate as f32 (birdnet-analyze.rs:736)
-        out.push_back(LiveChunkResult{src[i], (size_t)win[i], (float)(win[i] * live.step_samples()) / sr, std::move(r)});
-    }
+    // start_time = pos as f32 / sample_rate as f32 (birdnet-analyze.rs:736)
+    for (size_t i = 0; i < n; i++) out.push_back(LiveChunkResult{src[i], (size_t)win[i], (float)(win[i] * live.step_samples()) / sr, std::move(rows[i])});
     return out;
+}
+
+std::vector<PredictionResult> Classifier::predict_window_list(BatchInferenceContext &ctx, const WindowRef *refs, size_t n, const InferenceOptions &options) const {
+    ClassifierInner &in = *inner_;
+    const volatile int32_t *cancel = options.cancellation_token ? options.cancellation_token->raw() : nullptr;
+    if (cancel && *cancel) throw from_status(BN_ERR_CANCELLED, options);
+    if (n && !refs) throw inference("null window list");
+    if (n > ctx.max_batch_size_) throw inference("batch size " + std::to_string(n) + " exceeds context max " + std::to_string(ctx.max_batch_size_));
+    std::vector<bn_window_ref> raw(n);
+    for (size_t i = 0; i < n; i++) raw[i] = bn_window_ref{refs[i].recording ? refs[i].recording->raw() : nullptr, refs[i].start, refs[i].source, refs[i].window};
+    const auto t0 = std::chrono::steady_clock::now();
+    // top_k 0 still runs the step and reports no predictions, as predict_live does
+    const bn_status st = bn_step_window_list(ctx.ctx_, raw.data(), n, sizeof(bn_window_ref), std::max<size_t>(in.top_k, 1), in.min_confidence ? 1 : 0,
+                                             in.min_confidence.value_or(0.0f), 0);
+    if (st != BN_OK) throw from_status(st, options);
+    return finish_step(in, ctx.ctx_, n, options, t0, cancel, "list step");
 }
 
 Classifier ClassifierBuilder::build() {
