@@ -475,6 +475,74 @@ bn_status bn_recording_levels(const bn_recording *r, size_t segment_samples, siz
                               size_t count, bn_window_level *out, size_t struct_size);
 
 /*
+ * bn_recording_band_levels: per window, the power inside caller-chosen frequency bands -- the levels a gate needs where wind,
+ * traffic or handling noise below a few hundred hertz makes every window "loud" to peak and mean_square.  out[i] receives the
+ * bands of window first_window + i; r, segment_samples, step_samples, first_window and count mean what they mean for
+ * bn_recording_levels, and a window is the same S = segment_samples f32 samples, zeros past the end.
+ *
+ * Frames.  A window is cut into frames of N = spec->frame samples every spec->hop samples, all inside the window: frame j covers
+ * window positions [j * hop, j * hop + N), n_frames = (S - N) / hop + 1.  The up to hop - 1 trailing positions that no full frame
+ * covers are not read: they change no field, not even the non-finite flag.
+ * Transform.  A frame x is multiplied by the periodic Hann window w_n = 0.5 - 0.5 cos(2 pi n / N) and transformed:
+ * X_k = sum_n w_n x_n exp(-2 pi i k n / N), k = 0 .. N/2.
+ * One-sided power.  P_k = c_k |X_k|^2 / (N * sum_n w_n^2), c_k = 1 for k = 0 and k = N/2, 2 otherwise.  sum_k P_k equals
+ * sum (w x)^2 / sum w^2, so a bin-centred sine of amplitude A reads A^2 / 2 in its band: the scale of mean_square.
+ * A band b is the bin range [bin_lo[b], bin_hi[b]); bands may overlap.  Its power in a frame is the sum of P_k over it; the
+ * frame's total the sum over all N/2 + 1 bins.
+ *
+ *   mean[b], max[b]          the mean and the maximum over the window's frames of band b's power; 0 for b >= n_bands
+ *   total_mean, total_max    the same pair for the total
+ *   n_frames                 (S - N) / hop + 1
+ *   flags                    BN_LEVEL_PADDED as for bn_recording_levels; BN_LEVEL_NONFINITE iff any sample a frame reads is NaN or
+ *                            +-Inf: then mean[b] and max[b] of every b < n_bands and both totals are +Inf, so such a window is
+ *                            never quiet
+ *
+ * Arithmetic.  Plain f32, no fused multiply-add, no math-library call on the device: window and twiddles are tables computed in
+ * double on the host and rounded once.  A frame is a radix-2 transform of N/2 complex points and the real-input unpack, the bins
+ * of a band are added in a fixed tree, the frames in ascending order in one of four chains (csrc/band_levels.hip).  Against the
+ * float64 value of the same f32 samples with the double-precision window, with u = 2^-24, eps = BN_BAND_EPS_ULPS * u,
+ * delta = (BN_BAND_SUM_DEPTH + ceil(n_frames / 4)) * u, P the reference value of the field and T the reference total_mean (for
+ * max[b] and total_max: total_max), barring underflow:
+ *   |got - P| <= 2 eps sqrt(P T) + eps^2 T + delta P
+ * (derivation in DESIGN.md 7c, "Band levels").
+ *
+ * Invariance.  A window's record depends only on its S samples, S and the spec: not on first_window, count, step_samples, the
+ * recording's length or its layout, nor on how a window range is split into calls.
+ *
+ * The call blocks on an asynchronous upload until the last sample its frames read has arrived, and returns when `out` is written.
+ * spec_size is sizeof(bn_band_spec), struct_size sizeof(bn_window_bands), as the caller compiled them; element i of `out` lies at
+ * byte offset i * struct_size and bytes of an element past this header's struct are left alone.  BN_ERR_INVALID_ARG, with a
+ * message and nothing enqueued: whatever bn_recording_levels refuses, a NULL spec, a spec_size below the struct's, a frame that is
+ * not 256, 512, 1024 or 2048, segment_samples < frame, hop 0 or above frame, n_bands 0 or above BN_BAND_MAX, a band with
+ * bin_lo >= bin_hi or bin_hi > frame / 2 + 1.  count == 0 is BN_OK.
+ *
+ * bn_band_bins (host only, no device): the bins of [lo_hz, hi_hz) at a sample rate -- a recording does not carry its rate.  Bin k
+ * lies at k * sample_rate / frame Hz and belongs to the band iff that centre does.  BN_ERR_INVALID_ARG: a rate of 0, a frame not
+ * in the list, lo_hz >= hi_hz (or a NaN), a band that holds no bin centre, a NULL output.
+ */
+#define BN_BAND_MAX 8
+#define BN_BAND_EPS_ULPS 80  /* 7 per radix-2 stage * 10 stages at frame 2048 + 2 (window) + 7 (unpack) + 1 (second order) */
+#define BN_BAND_SUM_DEPTH 32 /* 17 (a lane's bins) + 6 (a wave) + 2 (four waves) + 7 (squares, scale, division, reference scale) */
+typedef struct bn_band_spec {
+    uint32_t frame;   /* N: 256, 512, 1024 or 2048 */
+    uint32_t hop;     /* 1 .. N */
+    uint32_t n_bands; /* 1 .. BN_BAND_MAX */
+    uint32_t bin_lo[BN_BAND_MAX]; /* band b is bins [bin_lo[b], bin_hi[b]) */
+    uint32_t bin_hi[BN_BAND_MAX]; /* bin_lo[b] < bin_hi[b] <= N/2 + 1 */
+} bn_band_spec;
+typedef struct bn_window_bands {
+    float mean[BN_BAND_MAX]; /* entries >= n_bands are 0 */
+    float max[BN_BAND_MAX];
+    float total_mean;
+    float total_max;
+    uint32_t flags; /* BN_LEVEL_NONFINITE | BN_LEVEL_PADDED */
+    uint32_t n_frames;
+} bn_window_bands;
+bn_status bn_recording_band_levels(const bn_recording *r, size_t segment_samples, size_t step_samples, size_t first_window,
+                                   size_t count, const bn_band_spec *spec, size_t spec_size, bn_window_bands *out, size_t struct_size);
+bn_status bn_band_bins(uint32_t sample_rate, uint32_t frame, double lo_hz, double hi_hz, uint32_t *bin_lo, uint32_t *bin_hi);
+
+/*
  * bn_step_window_list: bn_step_windows over an explicit list.  Row i of the batch is the S = sample_count frames of
  * refs[i].recording from frame refs[i].start on, zeros past the end; start is any frame of the recording, no multiple of any step
  * (a window centred on a peak is fine).  The rows are gathered on the device straight into the context's input buffer -- the

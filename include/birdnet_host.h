@@ -215,6 +215,11 @@ class Recording {
      * step_samples), computed on the device over exactly the samples those windows hold (birdnet_hip.h, "Window levels and list
      * steps"); count == SIZE_MAX means "to the last window".  Throws Error::Inference with the library's message on a refusal. */
     std::vector<bn_window_level> levels(size_t segment_samples, size_t step_samples, size_t first = 0, size_t count = (size_t)-1) const;
+    /* bn_recording_band_levels: per window the power inside the bands of `spec`, mean and maximum over the window's frames, for the
+     * same windows as levels() (birdnet_hip.h, "bn_recording_band_levels"); count == SIZE_MAX means "to the last window".  Throws
+     * Error::Inference with the library's message on a refusal. */
+    std::vector<bn_window_bands> band_levels(size_t segment_samples, size_t step_samples, const bn_band_spec &spec, size_t first = 0,
+                                             size_t count = (size_t)-1) const;
     size_t n_samples() const { return n_samples_; }
     const bn_recording *raw() const { return rec_.get(); }
 
@@ -522,6 +527,9 @@ size_t bnh_recording_samples(const bnh_recording *r);
 /* count == SIZE_MAX => to the last window; writes up to cap levels, *n_out = the number of windows asked for */
 int32_t bnh_recording_levels(const bnh_recording *r, size_t segment_samples, size_t step_samples, size_t first, size_t count,
                              bn_window_level *out, size_t cap, size_t *n_out, bnh_error *err);
+/* Recording::band_levels; count, cap and *n_out as bnh_recording_levels */
+int32_t bnh_recording_band_levels(const bnh_recording *r, size_t segment_samples, size_t step_samples, const bn_band_spec *spec, size_t first,
+                                  size_t count, bn_window_bands *out, size_t cap, size_t *n_out, bnh_error *err);
 /* row i: recordings[i] from frame starts[i]; sources / windows may be NULL (0 and the row's position) */
 int32_t bnh_predict_window_list(const bnh_classifier *c, bnh_context *ctx, const bnh_recording *const *recordings, const uint64_t *starts,
                                 const int32_t *sources, const uint64_t *windows, size_t n, int64_t timeout_ns, const volatile int32_t *cancel,

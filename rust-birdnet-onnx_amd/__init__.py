@@ -56,7 +56,7 @@ ENGINE_SYMBOLS = [
     "bn_infer_windows", "bn_step_windows", "bn_ctx_step_device_rows", "bn_group_create", "bn_group_destroy", "bn_group_size",
     "bn_group_uses_rccl", "bn_group_get_stats", "bn_shard_range", "bn_group_analyze_recording", "bn_group_last_error", "bn_recording_create_resampled", "bn_resample_table", "bn_recording_read_f32", "bn_last_error",
     "bn_recording_create_layout", "bn_recording_create_layout_async", "bn_recording_create_layout_resampled", "bn_recording_view_channel", "bn_live_create_layout",
-    "bn_recording_levels", "bn_step_window_list", "bn_recording_window_list",
+    "bn_recording_levels", "bn_step_window_list", "bn_recording_window_list", "bn_recording_band_levels", "bn_band_bins",
     "bn_index_create", "bn_index_free", "bn_index_size", "bn_index_dim", "bn_index_add_host", "bn_index_add_ctx", "bn_index_read",
     "bn_index_search", "bn_index_search_ids", "bn_index_assign", "bn_index_cluster",
     "bn_index_save", "bn_index_load", "bn_index_file_info", "bn_index_file_verify",
@@ -95,6 +95,7 @@ HOST_SYMBOLS = [
     "bnh_context_attach_prior", "bnh_context_set_prior_site", "bnh_context_prior_results",
     "bnh_live_create", "bnh_live_create_rates", "bnh_live_create_layout", "bnh_predict_recording_layout", "bnh_live_free", "bnh_live_push", "bnh_live_close", "bnh_live_ready", "bnh_predict_live",
     "bnh_recording_create", "bnh_recording_free", "bnh_recording_samples", "bnh_recording_levels", "bnh_predict_window_list",
+    "bnh_recording_band_levels",
 ]
 
 
@@ -163,6 +164,41 @@ class BnWindowRef(C.Structure):
 BN_LEVEL_NONFINITE, BN_LEVEL_PADDED = 1, 2  # bn_window_level.flags
 BN_LEVEL_SUM_DEPTH = 1034  # include/birdnet_hip.h: the longest chain of f32 additions behind a level, for S <= 2^20
 LEVEL_DTYPE = np.dtype([("peak", np.float32), ("mean", np.float32), ("mean_square", np.float32), ("flags", np.uint32)])
+
+
+BN_BAND_MAX = 8  # include/birdnet_hip.h: bands per spec
+BN_BAND_EPS_ULPS, BN_BAND_SUM_DEPTH = 80, 32  # the constants of the header's bound on a band level
+
+
+class BnBandSpec(C.Structure):
+    _fields_ = [("frame", C.c_uint32), ("hop", C.c_uint32), ("n_bands", C.c_uint32), ("bin_lo", C.c_uint32 * BN_BAND_MAX), ("bin_hi", C.c_uint32 * BN_BAND_MAX)]
+
+
+class BnWindowBands(C.Structure):
+    _fields_ = [("mean", C.c_float * BN_BAND_MAX), ("max", C.c_float * BN_BAND_MAX), ("total_mean", C.c_float), ("total_max", C.c_float),
+                ("flags", C.c_uint32), ("n_frames", C.c_uint32)]
+
+
+BAND_DTYPE = np.dtype([("mean", np.float32, (BN_BAND_MAX,)), ("max", np.float32, (BN_BAND_MAX,)), ("total_mean", np.float32), ("total_max", np.float32),
+                       ("flags", np.uint32), ("n_frames", np.uint32)])
+
+
+def band_spec(frame: int, hop: int, bands) -> BnBandSpec:
+    """A bn_band_spec of frames of `frame` samples every `hop`, bands = [(bin_lo, bin_hi), ...]; nothing is checked here (more than
+    BN_BAND_MAX bands keep their count and lose the bands past the eighth: the library refuses the count)."""
+    sp = BnBandSpec(frame, hop, len(bands))
+    for b, (lo, hi) in enumerate(list(bands)[:BN_BAND_MAX]):
+        sp.bin_lo[b], sp.bin_hi[b] = lo, hi
+    return sp
+
+
+def band_bins(sample_rate: int, frame: int, lo_hz: float, hi_hz: float):
+    """bn_band_bins: (bin_lo, bin_hi) of the band [lo_hz, hi_hz) for frames of `frame` samples at `sample_rate`; host only."""
+    lo, hi = C.c_uint32(), C.c_uint32()
+    st = lib.bn_band_bins(sample_rate, frame, lo_hz, hi_hz, C.byref(lo), C.byref(hi))
+    if st:
+        raise EngineError(st)
+    return lo.value, hi.value
 
 
 class BnIndexFilter(C.Structure):
@@ -261,6 +297,8 @@ def _load() -> C.CDLL:
         "bn_recording_view_channel": (i32, [vp, i32, C.POINTER(vp)]),
         "bn_recording_levels": (i32, [vp, sz, sz, sz, sz, C.POINTER(BnWindowLevel), sz]),
         "bn_step_window_list": (i32, [vp, C.POINTER(BnWindowRef), sz, sz, sz, i32, C.c_float, i32]),
+        "bn_recording_band_levels": (i32, [vp, sz, sz, sz, sz, C.POINTER(BnBandSpec), sz, C.POINTER(BnWindowBands), sz]),
+        "bn_band_bins": (i32, [C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
         "bn_recording_window_list": (i32, [C.POINTER(BnWindowRef), sz, sz, sz, f32p]),
         "bn_last_error": (sz, [C.c_char_p, sz]),
         "bn_ctx_step_device_rows": (i32, [vp, C.POINTER(u32p)]),
@@ -434,6 +472,7 @@ def _load() -> C.CDLL:
         "bnh_recording_free": (None, [vp]),
         "bnh_recording_samples": (sz, [vp]),
         "bnh_recording_levels": (i32, [vp, sz, sz, sz, sz, C.POINTER(BnWindowLevel), sz, C.POINTER(sz), C.POINTER(BnhError)]),
+        "bnh_recording_band_levels": (i32, [vp, sz, sz, C.POINTER(BnBandSpec), sz, sz, C.POINTER(BnWindowBands), sz, C.POINTER(sz), C.POINTER(BnhError)]),
         "bnh_predict_window_list": (i32, [vp, vp, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(C.c_uint64), sz, C.c_int64,
                                           C.POINTER(C.c_int32), C.POINTER(vp), C.POINTER(BnhError)]),
         "bnh_predict_live": (i32, [vp, vp, vp, sz, C.c_int64, C.POINTER(C.c_int32), C.POINTER(vp), C.POINTER(C.c_int32),
@@ -821,6 +860,19 @@ class HostRecording:
         n, err = C.c_size_t(), BnhError()
         if lib.bnh_recording_levels(self._h, segment_samples, step_samples, first, want, out.ctypes.data_as(C.POINTER(BnWindowLevel)), cap, C.byref(n),
                                     C.byref(err)):
+            raise Error(err)
+        return out[:n.value].copy()
+
+    def band_levels(self, segment_samples: int, step_samples: int, frame: int, hop: int, bands, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """Recording::band_levels: a BAND_DTYPE array of windows [first, first + count) (count None: to the last window); bands =
+        [(bin_lo, bin_hi), ...]."""
+        want = (1 << 64) - 1 if count is None else count
+        cap = max(int(lib.bn_chunk_count(self.n_samples, step_samples)) if step_samples else 0, 0 if count is None else count, 1)
+        out = np.zeros(cap, dtype=BAND_DTYPE)
+        n, err = C.c_size_t(), BnhError()
+        sp = band_spec(frame, hop, bands)
+        if lib.bnh_recording_band_levels(self._h, segment_samples, step_samples, C.byref(sp), first, want, out.ctypes.data_as(C.POINTER(BnWindowBands)), cap,
+                                         C.byref(n), C.byref(err)):
             raise Error(err)
         return out[:n.value].copy()
 
@@ -1414,6 +1466,19 @@ class Recording:
         out = np.zeros(max(count, 0), dtype=LEVEL_DTYPE)
         st = lib.bn_recording_levels(self._h, segment_samples, step_samples, first, count, out.ctypes.data_as(C.POINTER(BnWindowLevel)),
                                      C.sizeof(BnWindowLevel))
+        if st:
+            raise EngineError(st)
+        return out
+
+    def band_levels(self, segment_samples: int, step_samples: int, frame: int, hop: int, bands, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """bn_recording_band_levels: per window the power inside bands = [(bin_lo, bin_hi), ...] of frames of `frame` samples every `hop`,
+        mean and maximum over the window's frames, as a BAND_DTYPE array (count None: to the last window).  band_bins() gives the bins
+        of a band in hertz."""
+        count = self.n_windows(step_samples) - first if count is None else count
+        out = np.zeros(max(count, 0), dtype=BAND_DTYPE)
+        sp = band_spec(frame, hop, bands)
+        st = lib.bn_recording_band_levels(self._h, segment_samples, step_samples, first, count, C.byref(sp), C.sizeof(BnBandSpec),
+                                          out.ctypes.data_as(C.POINTER(BnWindowBands)), C.sizeof(BnWindowBands))
         if st:
             raise EngineError(st)
         return out

@@ -25,6 +25,7 @@
 #include "detect.h"
 #include "engine.h"
 #include "kernels.h"
+#include "band_levels.h"
 #include "levels.h"
 #include "plan_rules.h"
 #include "window_list_plan.h"
@@ -1765,12 +1766,18 @@ size_t bn_chunk_count(size_t n_samples, size_t step_samples) {
     return (n_samples + step_samples - 1) / step_samples;  // one window for every pos = k*step < n_samples
 }
 
-static bn_status check_windows(const bn_recording *r, size_t S, size_t step, size_t first, size_t count) {
+// the refusals of a window range, without the wait of check_windows
+static bn_status check_window_range(const bn_recording *r, size_t S, size_t step, size_t first, size_t count) {
     if (!r) return fail(BN_ERR_INVALID_ARG, "null recording");
     if (S == 0 || S % 4 != 0 || S > 0xffffffffull) return fail(BN_ERR_INVALID_ARG, "segment_samples must be a positive multiple of 4");
     if (step == 0) return fail(BN_ERR_INVALID_ARG, "step_samples must be positive (overlap shorter than the segment)");
     const size_t total = bn_chunk_count(r->n_samples, step);
     if (first > total || count > total - first) return fail(BN_ERR_INVALID_ARG, "window range [" + std::to_string(first) + ", " + std::to_string(first + count) + ") exceeds the " + std::to_string(total) + " windows of the recording");
+    return BN_OK;
+}
+
+static bn_status check_windows(const bn_recording *r, size_t S, size_t step, size_t first, size_t count) {
+    if (bn_status st = check_window_range(r, S, step, first, count); st != BN_OK) return st;
     // an asynchronously uploaded recording: the last sample these windows read must have arrived before their kernel is launched
     if (count && r->n_samples && !recording_wait_samples(r, std::min(r->n_samples - 1, (first + count - 1) * step + S - 1)))
         return fail(BN_ERR_BACKEND, "recording upload failed");
@@ -1869,6 +1876,48 @@ bn_status bn_recording_levels(const bn_recording *r, size_t segment_samples, siz
         for (size_t i = 0; i < rows.size() && i < n; i++) memcpy(reinterpret_cast<char *>(out) + (done + i) * struct_size, &rows[i], sizeof(WindowLevel));
     }
     return BN_OK;
+}
+
+// ---- band-limited window levels (include/birdnet_hip.h, "bn_recording_band_levels"; kernel in band_levels.hip, arithmetic in band_plan.h) ----
+bn_status bn_recording_band_levels(const bn_recording *r, size_t segment_samples, size_t step_samples, size_t first_window, size_t count,
+                                   const bn_band_spec *spec, size_t spec_size, bn_window_bands *out, size_t struct_size) {
+    if (struct_size < sizeof(bn_window_bands)) return fail(BN_ERR_INVALID_ARG, "struct_size is below sizeof(bn_window_bands)");
+    bn_status st = check_window_range(r, segment_samples, step_samples, first_window, count);
+    if (st != BN_OK) return st;
+    band::Plan plan;
+    if ((st = band::check_spec(spec, spec_size, segment_samples, &plan)) != BN_OK) return st;
+    if (count == 0) return BN_OK;
+    if (!out) return fail(BN_ERR_INVALID_ARG, "null output buffer");
+    // an asynchronously uploaded recording: the last sample any frame of these windows reads must have arrived
+    uint64_t last = 0;
+    if (band::last_sample_read(r->n_samples, first_window + count - 1, step_samples, plan.span, &last) && !recording_wait_samples(r, (size_t)last))
+        return fail(BN_ERR_BACKEND, "recording upload failed");
+    BN_HIP_TRY(bn::use_device(r->device));
+    const float *tab = nullptr;
+    float scale = 0.0f;
+    BN_HIP_TRY(band_tables(r->device, plan.N, &tab, &scale));
+    // one workgroup per window, at most 2^20 windows per launch
+    const size_t piece = (size_t)1 << 20;
+    DeviceBuf<WindowBands> d;
+    BN_HIP_TRY(d.alloc(std::min(piece, count) * sizeof(WindowBands)));
+    std::vector<WindowBands> rows;  // only for a caller whose struct is longer than this header's
+    if (struct_size != sizeof(bn_window_bands)) rows.resize(std::min(piece, count));
+    for (size_t done = 0; done < count; done += piece) {
+        const size_t n = std::min(piece, count - done);
+        bn::clear_launch_state();
+        launch_band_levels(nullptr, d, r->src(), r->n_samples, (uint64_t)(first_window + done) * step_samples, step_samples, (uint32_t)segment_samples,
+                           (uint32_t)n, plan, tab, scale);
+        if ((st = bn::check_launch("band levels")) != BN_OK) return st;
+        void *host = rows.empty() ? static_cast<void *>(out + done) : static_cast<void *>(rows.data());
+        const hipError_t e = gated::Memcpy(host, d, n * sizeof(WindowBands), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return fail(BN_ERR_BACKEND, std::string("band level kernel failed: ") + hipGetErrorString(e));
+        for (size_t i = 0; i < rows.size() && i < n; i++) memcpy(reinterpret_cast<char *>(out) + (done + i) * struct_size, &rows[i], sizeof(WindowBands));
+    }
+    return BN_OK;
+}
+
+bn_status bn_band_bins(uint32_t sample_rate, uint32_t frame, double lo_hz, double hi_hz, uint32_t *bin_lo, uint32_t *bin_hi) {
+    return band::bins(sample_rate, frame, lo_hz, hi_hz, bin_lo, bin_hi);
 }
 
 namespace {

@@ -298,6 +298,18 @@ int32_t bnh_recording_levels(const bnh_recording *r, size_t segment_samples, siz
     });
 }
 
+int32_t bnh_recording_band_levels(const bnh_recording *r, size_t segment_samples, size_t step_samples, const bn_band_spec *spec, size_t first, size_t count,
+                                  bn_window_bands *out, size_t cap, size_t *n_out, bnh_error *err) {
+    if (n_out) *n_out = 0;
+    if (!r) return set_other(err, "null recording");
+    if (!spec) return set_other(err, "null band spec");
+    return guarded(err, [&] {
+        const std::vector<bn_window_bands> lv = r->rec.band_levels(segment_samples, step_samples, *spec, first, count);
+        if (n_out) *n_out = lv.size();
+        if (out) memcpy(out, lv.data(), std::min(cap, lv.size()) * sizeof(bn_window_bands));
+    });
+}
+
 int32_t bnh_predict_window_list(const bnh_classifier *c, bnh_context *ctx, const bnh_recording *const *recordings, const uint64_t *starts,
                                 const int32_t *sources, const uint64_t *windows, size_t n, int64_t timeout_ns, const volatile int32_t *cancel,
                                 bnh_results **out, bnh_error *err) {

@@ -338,6 +338,25 @@ std::vector<bn_window_level> Recording::levels(size_t segment_samples, size_t st
     return out;
 }
 
+std::vector<bn_window_bands> Recording::band_levels(size_t segment_samples, size_t step_samples, const bn_band_spec &spec, size_t first, size_t count) const {
+    if (count == (size_t)-1) {
+        const size_t total = bn_chunk_count(n_samples_, step_samples);
+        count = total > first ? total - first : 0;
+    }
+    // as levels(): a count the library refuses must reach it with a buffer
+    std::vector<bn_window_bands> out;
+    try {
+        out.resize(count);
+    } catch (const std::exception &) {
+        throw inference("window range exceeds the address space");
+    }
+    bn_window_bands none{};
+    if (bn_recording_band_levels(rec_.get(), segment_samples, step_samples, first, count, &spec, sizeof(bn_band_spec), count ? out.data() : &none,
+                                 sizeof(bn_window_bands)) != BN_OK)
+        throw inference(last_backend_error());
+    return out;
+}
+
 std::vector<ChunkResult> Classifier::predict_recording(BatchInferenceContext &ctx, const Recording &rec, float overlap_secs, size_t first_chunk, size_t count,
                                                        const InferenceOptions &options) const {
     const ModelConfig &cfg = inner_->config;

@@ -1,9 +1,12 @@
 #!/usr/bin/env python3
-"""Window levels and list steps, measured: two legs over a synthetic BirdNET-v2.4-style model.
+"""Window levels and list steps, measured: three legs over a synthetic BirdNET-v2.4-style model.
 
   gating       a synthetic recording of --hours with a --loud share of loud windows: bn_step_windows over every window, against
                bn_recording_levels + a host gate (peak >= 0.01, one window of hangover) + bn_step_window_list over the kept windows
                only; and the level pass alone, in GB/s of stored bytes.
+  band gate    the same hour with a 60 Hz rumble at -20 dBFS under everything and the calls at -50 dBFS: the windows the peak gate keeps
+               (all of them), the windows a 2 - 10 kHz gate on bn_recording_band_levels' max keeps, the band pass alone in GB/s of
+               stored bytes next to the level pass, and the band-gated run.
   short files  --files recordings of 4 windows each: one bn_step_windows per recording, against list steps of --batch rows.
 
 Every figure is the median of --runs timed runs after one warm-up; the JSON line at the end carries all of them.  No rate is a
@@ -90,7 +93,38 @@ def main():
     t_all, t_gate, t_lv = timed(everything, a.runs), timed(gated, a.runs), timed(lambda: rec.levels(S, S), a.runs)
     res["gating"] = {"windows": n_win, "loud": len(loud), "kept": kept[0], "all_s": t_all, "gated_s": t_gate, "levels_s": t_lv,
                      "levels_GBps": x.nbytes / t_lv[0] / 1e9}
-    del rec, x
+    del rec
+
+    # ---- band-gate leg: rumble under everything, the calls 30 dB below it
+    rate, N, hop = int(model.config.sample_rate), 1024, 512
+    band = bn.band_bins(rate, N, 2000.0, 10000.0)
+    y = 3276.8 * np.sin(2 * np.pi * 60.0 * np.arange(n_win * S) / rate)
+    for k in loud:
+        y[k * S + S // 4:k * S + S // 2] += 103.6 * np.sin(2 * np.pi * 5000.0 * np.arange(S // 4) / rate)
+    y = np.round(y).astype(np.int16)
+    rec = bn.Recording(y)
+    by_peak = int((rec.levels(S, S)["peak"] >= np.float32(0.01)).sum())
+    quiet_max = np.delete(rec.band_levels(S, S, N, hop, [band])["max"][:, 0], loud)
+    threshold = np.float32(10.0 * max(float(quiet_max.max()), 1e-12)) if len(quiet_max) else np.float32(1e-9)   # 10 dB over the loudest quiet window
+
+    def band_gated():
+        bl = rec.band_levels(S, S, N, hop, [band])
+        hit = np.flatnonzero(bl["max"][:, 0] >= threshold)
+        keep = np.zeros(n_win, dtype=bool)
+        for d in (-1, 0, 1):
+            keep[np.clip(hit + d, 0, n_win - 1)] = True
+        ks = np.flatnonzero(keep)
+        kept[:] = [len(ks), len(hit)]
+        for i in range(0, len(ks), B):
+            ctx.step_window_list([(rec, int(k) * S, 0, int(k)) for k in ks[i:i + B]], K, None, sync=False)
+        ctx.synchronize()
+
+    t_band_gate = timed(band_gated, a.runs)
+    t_bl, t_lv = timed(lambda: rec.band_levels(S, S, N, hop, [band]), a.runs), timed(lambda: rec.levels(S, S), a.runs)
+    res["band_gate"] = {"windows": n_win, "calls": len(loud), "kept_by_peak": by_peak, "hit_by_band": kept[1], "kept_by_band": kept[0], "frame": N, "hop": hop,
+                        "bins": list(band), "threshold": float(threshold), "band_gated_s": t_band_gate, "band_levels_s": t_bl, "levels_s": t_lv,
+                        "band_levels_GBps": y.nbytes / t_bl[0] / 1e9, "levels_GBps": y.nbytes / t_lv[0] / 1e9}
+    del rec, x, y
 
     # ---- short-files leg
     clips = [bn.Recording((3000 * rng.standard_normal(4 * S)).astype(np.int16)) for _ in range(a.files)]
