@@ -1,4 +1,4 @@
-// The kernel of bn_recording_band_levels (band_levels.hip), launched by capi.cpp: per window the power inside the bands of a checked
+// The kernel of bn_recording_band_levels (band_levels.hip), launched by recording.cpp: per window the power inside the bands of a checked
 // spec (band_plan.h), mean and maximum over the window's frames.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,4 +1,4 @@
-// band_levels_kernel -- the band meter of bn_recording_band_levels (launched by capi.cpp; declarations in band_levels.h, the rule in
+// band_levels_kernel -- the band meter of bn_recording_band_levels (launched by recording.cpp; declarations in band_levels.h, the rule in
 // include/birdnet_hip.h, "bn_recording_band_levels").  One workgroup of 256 lanes per window, templated on the frame length N and on
 // the reader (pcm_read.h) like levels_kernel, so a sample is exactly the f32 value bn_recording_windows returns, 0 past the end.
 // Wave w takes frames w, w + 4, ... of the window; nothing is shared between windows, so a window's bits cannot depend on the step.

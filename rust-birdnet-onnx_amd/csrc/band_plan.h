@@ -1,4 +1,4 @@
-// The host-side arithmetic of band-limited window levels (capi.cpp: bn_recording_band_levels, bn_band_bins; kernel in
+// The host-side arithmetic of band-limited window levels (recording.cpp: bn_recording_band_levels, bn_band_bins; kernel in
 // band_levels.hip) that needs neither a device nor the runtime: a spec checked and copied, the frames of a window and the samples
 // behind the last one that no frame reads, the last sample a window range reads (what an asynchronous upload is waited for; no sum
 // that can wrap is formed), the LDS a workgroup takes, the bins of a band given in hertz, and the tables the kernel reads (periodic

@@ -1,7 +1,7 @@
 // What the translation units of the C ABI share: the plumbing every entry point repeats (the error macro, launch and device checks,
 // the packed top-K block TopkRows, results_to_host, the pinned ring PinnedRing, scoped scratch: step_common.cpp), what they need of
-// capi.cpp's private state (index.hip: bn_index_* and the host side every search over an index shares; head.hip: bn_head_*; rank.hip: bn_head_rank_index; cluster.hip: bn_index_assign, bn_index_cluster; live.cpp: bn_step_live) and of each other (prior.hip:
-// bn_prior_*; track.hip: bn_track_*).  A step's rows reach its stages as an argument (StepRows), never through a context's state.
+// capi.cpp's private state (index.hip: bn_index_* and the host side every search over an index shares; head.hip: bn_head_*; rank.hip: bn_head_rank_index; cluster.hip: bn_index_assign, bn_index_cluster; live.cpp: bn_step_live; recording.cpp: bn_step_window_list) and of each other (prior.hip:
+// bn_prior_*; track.hip: bn_track_*; recording.cpp: bn_recording_* and what bn_infer_windows and bn_step_windows need of a recording).  A step's rows reach its stages as an argument (StepRows), never through a context's state.
 // Every device buffer, pinned buffer, stream and event is a member of device_mem.h's owner types: a handle's destructor waits, its members free.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -150,12 +150,12 @@ struct StepRows {
     const uint64_t *windows;  // NULL: row i is window first_window + i
     uint64_t first_window;
 };
-// the body of bn_step_device, bn_step_windows and bn_step_live
+// the body of bn_step_device, bn_step_windows, bn_step_window_list and bn_step_live
 bn_status step_device(bn_ctx *c, const float *d_pcm, const StepRows &rows, size_t top_k, int32_t has_min, float min_conf, int32_t sync);
 // the refusals of bn_step_windows (n_sources == 0) and bn_step_live (count == 0) that the attached prior and tracker make, before
 // anything is enqueued or taken from a pool: prior_step_check, track_step_check
 bn_status ctx_step_check(const bn_ctx *c, size_t n_sources, uint64_t first_window, size_t count);
-// what bn_step_live needs of a context: its device, stream and input buffer [max_batch, sample_count]; BN_ERR_INVALID_ARG
+// what bn_step_live and bn_step_window_list need of a context: its device, stream and input buffer [max_batch, sample_count]; BN_ERR_INVALID_ARG
 // (message set) for a top_k that bn_step_device would refuse
 struct CtxStepInput {
     int device = 0;
@@ -163,20 +163,9 @@ struct CtxStepInput {
     float *d_input = nullptr;
     size_t sample_count = 0;
     size_t max_batch = 0;
+    bool tracked = false;  // a tracker is attached: its refusals of a row's own window number apply
 };
 bn_status ctx_step_input(const bn_ctx *c, size_t top_k, CtxStepInput *out);
-// the polyphase table of the resampler (design in include/birdnet_hip.h): L/M = dst/src reduced, T taps per phase; zc 0 => 16
-struct ResampleTable {
-    uint32_t L = 1, M = 1, T = 0;
-    std::vector<float> coef;  // [L][T]
-};
-// L, M and T alone (coef left empty): what the table would be, without building it
-ResampleTable resample_factors(uint32_t src_rate, uint32_t dst_rate, uint32_t zc);
-ResampleTable make_resample_table(uint32_t src_rate, uint32_t dst_rate, uint32_t zc);
-// a caller's bn_pcm_layout read through the size it was compiled with (a longer struct of a later header: its first fields);
-// BN_ERR_INVALID_ARG for NULL or a struct shorter than this header's.  The layout itself is checked by
-// pcm_layout_problem (pcm_layout.h)
-bn_status read_pcm_layout(const bn_pcm_layout *layout, size_t struct_size, PcmLayout *out);
 // index.hip -> head.hip (bn_head_fit_index): the stored rows of an index, every pending append waited for
 struct IndexRows {
     int device = 0;
@@ -431,4 +420,24 @@ bn_status track_step_check(const TrackAttach *a, const PriorAttach *prior, size_
 // rows.first_window + i of the attachment's source (bn_step_windows)
 bn_status track_step(TrackAttach *a, hipStream_t stream, const float *d_logits, const StepRows &rows, const PriorAttach *prior);
 bn_status track_step_results(TrackAttach *a, const bn_event **events, size_t *n, size_t *dropped, size_t *stale_rows);
+// ---- recording.cpp ----
+// the polyphase table of the resampler (design in include/birdnet_hip.h): L/M = dst/src reduced, T taps per phase; zc 0 => 16
+struct ResampleTable {
+    uint32_t L = 1, M = 1, T = 0;
+    std::vector<float> coef;  // [L][T]
+};
+// L, M and T alone (coef left empty): what the table would be, without building it
+ResampleTable resample_factors(uint32_t src_rate, uint32_t dst_rate, uint32_t zc);
+ResampleTable make_resample_table(uint32_t src_rate, uint32_t dst_rate, uint32_t zc);
+// a caller's bn_pcm_layout read through the size it was compiled with (a longer struct of a later header: its first fields);
+// BN_ERR_INVALID_ARG for NULL or a struct shorter than this header's.  The layout itself is checked by
+// pcm_layout_problem (pcm_layout.h)
+bn_status read_pcm_layout(const bn_pcm_layout *layout, size_t struct_size, PcmLayout *out);
+// recording.cpp -> capi.cpp (bn_infer_windows, bn_step_windows): the refusals of windows [first, first + count) of S samples every
+// `step` of a recording (a null recording, the segment, the step, the range), then the wait for the last sample they read of an
+// asynchronous upload; *device (may be NULL): where the recording lives
+bn_status check_windows(const bn_recording *r, size_t S, size_t step, size_t first, size_t count, int32_t *device);
+// those windows, checked, into dst [count, S] by the window kernel enqueued on `stream` of `device` (the thread's device); a
+// recording on another device is refused
+bn_status enqueue_windows(hipStream_t stream, int32_t device, float *dst, const bn_recording *r, size_t S, size_t step, size_t first, size_t count);
 }  // namespace bn

@@ -1,4 +1,4 @@
-// Kernels in front of the plan that read chosen windows of recordings (levels.hip), launched by capi.cpp: the level meter
+// Kernels in front of the plan that read chosen windows of recordings (levels.hip), launched by recording.cpp: the level meter
 // (bn_recording_levels) and the gather of an explicit window list (bn_step_window_list, bn_recording_window_list).
 #pragma once
 #include <hip/hip_runtime.h>

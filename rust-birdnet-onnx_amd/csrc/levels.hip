@@ -1,4 +1,4 @@
-// Kernels that read chosen windows of recordings, in front of an unchanged plan (launched by capi.cpp; declarations in levels.h).
+// Kernels that read chosen windows of recordings, in front of an unchanged plan (launched by recording.cpp; declarations in levels.h).
 //
 //   * levels_kernel -- the level meter of bn_recording_levels: one workgroup of 256 lanes per window, templated on the reader
 //     (pcm_read.h) like kernels.hip's windows_kernel, so a sample is exactly the f32 value bn_recording_windows returns, 0 past

@@ -1,5 +1,5 @@
 // PCM layouts (include/birdnet_hip.h, "PCM layouts"): all arithmetic on frames and bytes of interleaved PCM, in one place and in
-// plain C++ -- the recording upload (capi.cpp), the live pool (live.cpp) and the kernels' sample read (pcm_read.h) take their
+// plain C++ -- the recording upload (recording.cpp), the live pool (live.cpp) and the kernels' sample read (pcm_read.h) take their
 // offsets, chunk cuts and sizes from here, and tools/asan_pcm_layout.cpp runs it under the sanitizers without a device.
 //
 // A layout is {format, channels, channel}: frames of `channels` samples, each pcm_sample_bytes(format) wide, little-endian;

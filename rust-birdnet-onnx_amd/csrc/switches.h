@@ -30,8 +30,8 @@
     X(integer,     BN_INPUT_MEMCPY,      0,      "non-zero: a caller's device input reaches the context's buffer by hipMemcpyAsync, not by the copy kernel (read once)") \
     X(integer,     BN_SDMA_COPY,          0,      "non-zero: results reach pinned host memory by hipMemcpyAsync, not by the kernel's own stores (read once)") \
     X(int64,       BN_STAGE_THREADS,      0,      "threads that stage host slices into pinned memory, clamped to 0 .. 64; unset: min(6, half the hardware threads)") \
+    /* ---- recordings (recording.cpp), device groups (group.cpp) and live pools (live.cpp) */ \
     X(integer,     BN_UPLOAD_CHUNK_MB,    4,      "MiB per piece of a constants upload (at least 1)") \
-    /* ---- device groups (group.cpp) and live pools (live.cpp) */ \
     X(text,        BN_RCCL_LIB,           "",     "RCCL library to load and nothing else; unset: librccl.so.1, librccl.so, then the ROCm install's") \
     X(integer,     BN_GROUP_FORCE_RCCL,   0,      "non-zero: take the RCCL branch for ranks that share a device too (the test stub accepts such a communicator)") \
     X(present,     BN_GROUP_NO_RCCL,      false,  "gather with device copies even where RCCL would serve (presence only: =0 also disables RCCL)") \

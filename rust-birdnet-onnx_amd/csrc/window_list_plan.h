@@ -1,4 +1,4 @@
-// The host-side arithmetic of a step over an explicit list of windows (capi.cpp: bn_step_window_list, bn_recording_window_list;
+// The host-side arithmetic of a step over an explicit list of windows (recording.cpp: bn_step_window_list, bn_recording_window_list;
 // kernel in levels.hip) that needs neither a device nor the runtime: which frames of its recording a row reads (the `start + S`
 // arithmetic, which never forms start + S), the reader kind of a layout, the grouping of a list's rows by reader kind, the cuts of a
 // group into launches of at most ROWS_PER_LAUNCH rows, and per recording the last frame any of its rows reads (what an asynchronous

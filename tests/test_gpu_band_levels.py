@@ -281,3 +281,21 @@ def test_host_mirror_and_asynchronous_upload(bn):
     a = bn.Recording(v, async_upload=True)
     assert a.band_levels(SEG, SEG, N, hop, bands).tobytes() == want.tobytes()
     a.wait()
+
+
+def test_a_second_piece_continues_the_first(bn):
+    """A call runs at most 2^20 windows per launch: 2^20 + 3 windows of one 256-sample frame at step 1 take two.  The rows either
+    side of the cut (three whole windows, two that reach past the end) are those of a call on just that range (one piece), byte for
+    byte, and the float64 reference's."""
+    N = S = min(ref.FRAMES)
+    piece, bands = 1 << 20, [(3, 40)]
+    count = piece + 3
+    v = np.random.RandomState(2021).randint(-32768, 32768, size=count + S - 3).astype(np.int16)
+    rec = bn.Recording(v)
+    whole = rec.band_levels(S, 1, N, N, bands, 0, count)
+    first, n = piece - 2, 5
+    edge = rec.band_levels(S, 1, N, N, bands, first, n)
+    assert len(whole) == count and whole[first:].tobytes() == edge.tobytes()
+    r = ref.band_levels(_f32(v[first:]), S, 1, N, N, bands, 0, n)  # the samples these windows read: the last S + 2
+    assert r["flags"].tolist() == [0, 0, 0, ref.PADDED, ref.PADDED] and r["n_frames"].tolist() == [1] * n
+    _check(bn, whole[first:], r, 1, "across the piece boundary")

@@ -130,3 +130,25 @@ def test_asynchronous_upload_gives_the_same_bits(bn):
     a = bn.Recording(v, async_upload=True)
     assert a.levels(S, step).tobytes() == rec.levels(S, step).tobytes()
     a.wait()
+
+
+def test_a_second_piece_continues_the_first(bn):
+    """A call runs at most 2^20 windows per launch: 2^20 + 3 windows of S = 4 at step 1 take two.  The rows either side of the cut
+    are those of a call on just that range (one piece), byte for byte, and the float64 reference's; a caller's longer struct keeps its
+    stride across the cut."""
+    S, piece = 4, 1 << 20
+    count = piece + 3
+    v = np.random.RandomState(2020).randint(-32768, 32768, size=count).astype(np.int16)
+    rec = bn.Recording(v)
+    assert rec.n_windows(1) == count
+    whole = rec.levels(S, 1)
+    first, n = piece - 2, 5
+    edge = rec.levels(S, 1, first, n)
+    assert len(whole) == count and whole[first:].tobytes() == edge.tobytes()
+    x = pcm_ref.mono(pcm_ref.pack(v[first:], pcm_ref.I16), pcm_ref.I16, 1, 0)  # the samples these windows read: the last 5
+    ref = levels_ref.levels(x, S, 1)
+    assert ref["flags"].tolist() == [0, 0, levels_ref.PADDED, levels_ref.PADDED, levels_ref.PADDED]
+    _check(bn, whole[first:], ref, "across the piece boundary", S)
+    wide = np.full((count, 6), 0xA5A5A5A5, dtype=np.uint32)
+    assert bn.lib.bn_recording_levels(rec._h, S, 1, 0, count, wide.ctypes.data_as(C.POINTER(bn.BnWindowLevel)), C.sizeof(bn.BnWindowLevel) + 8) == 0
+    assert np.ascontiguousarray(wide[:, :4]).tobytes() == whole.tobytes() and (wide[:, 4:] == 0xA5A5A5A5).all()

@@ -288,3 +288,16 @@ def test_mono_entry_point_and_its_layout_give_identical_windows(bn, fmt):
         new = bn.Recording.from_layout(raw, fmt, 1, op)
         assert bits(old.windows(S, STEP, 0, 11)) == bits(new.windows(S, STEP, 0, 11)) == bits(P.chunk_audio(P.mono(raw, fmt, 1, 0), S, STEP))
     assert bits(bn.Recording(a, async_upload=True).windows(S, STEP, 0, 11)) == bits(old.windows(S, STEP, 0, 11))
+
+
+# ---- 10. read_f32 past its first piece ------------------------------------------------------------------------------------
+def test_read_f32_converts_in_pieces_of_2_to_the_24(bn):
+    """a converting read runs the window kernel over at most 2^24 frames at a time: 2^24 + 5 frames take two pieces"""
+    piece = 1 << 24
+    n = piece + 5
+    pcm = np.random.RandomState(24).randint(-32768, 32768, size=(n, 2)).astype(np.int16)
+    want = pcm[:, 1].astype(np.float32) / np.float32(32768.0)  # exact: an int16 over a power of two
+    rec = bn.Recording.from_layout(pcm, P.I16, 2, 0).view_channel(1)
+    assert rec.n_samples == n
+    assert bits(rec.read_f32()) == bits(want)
+    assert bits(rec.read_f32(piece - 3, 7)) == bits(want[piece - 3:piece + 4])
