@@ -10,7 +10,7 @@ CXXFLAGS := -O3 -std=c++17 -fPIC -Wall -Wextra -Wno-unused-parameter -Iinclude
 # for the pairs with register moves (mbmap's depthwise phase: 120 v_pk_fma + 216 v_mov for 240 multiply-adds); on this part a packed
 # f32 instruction costs 1.56x a plain one (tools/mfma_valu_probe.cpp) and every vector instruction is paid out of the MFMA time
 HIPFLAGS := $(CXXFLAGS) --offload-arch=$(ARCH) -ffp-contract=off -fno-slp-vectorize
-OBJS := $(SRC)/onnx_proto.o $(SRC)/engine.o $(SRC)/onnx_rewrite.o $(SRC)/dft_bank.o $(SRC)/plan_passes.o $(SRC)/detect.o $(SRC)/capi.o $(SRC)/recording.o $(SRC)/step_common.o $(SRC)/group.o $(SRC)/host_classifier.o $(SRC)/host_capi.o $(SRC)/host_rangefilter.o $(SRC)/kernels.o $(SRC)/topk.o $(SRC)/stft.o $(SRC)/mbrow.o $(SRC)/gemm_dma.o $(SRC)/gemm_dma3.o $(SRC)/gemm_b3.o $(SRC)/mbmap.o $(SRC)/mbmap_ws.o $(SRC)/index.o $(SRC)/head.o $(SRC)/rank.o $(SRC)/cluster.o $(SRC)/ivf.o $(SRC)/sq8.o $(SRC)/subset.o $(SRC)/index_copy.o $(SRC)/peaks.o $(SRC)/seq.o $(SRC)/above.o $(SRC)/group_above.o $(SRC)/match.o $(SRC)/index_io.o $(SRC)/index_file.o $(SRC)/prior.o $(SRC)/track.o $(SRC)/live.o $(SRC)/live_kernels.o $(SRC)/levels.o $(SRC)/band_levels.o
+OBJS := $(SRC)/onnx_proto.o $(SRC)/engine.o $(SRC)/onnx_rewrite.o $(SRC)/dft_bank.o $(SRC)/mbconv_fuse.o $(SRC)/plan_passes.o $(SRC)/detect.o $(SRC)/capi.o $(SRC)/recording.o $(SRC)/step_common.o $(SRC)/group.o $(SRC)/host_classifier.o $(SRC)/host_capi.o $(SRC)/host_rangefilter.o $(SRC)/kernels.o $(SRC)/topk.o $(SRC)/stft.o $(SRC)/mbrow.o $(SRC)/gemm_dma.o $(SRC)/gemm_dma3.o $(SRC)/gemm_b3.o $(SRC)/mbmap.o $(SRC)/mbmap_ws.o $(SRC)/index.o $(SRC)/head.o $(SRC)/rank.o $(SRC)/cluster.o $(SRC)/ivf.o $(SRC)/sq8.o $(SRC)/subset.o $(SRC)/index_copy.o $(SRC)/peaks.o $(SRC)/seq.o $(SRC)/above.o $(SRC)/group_above.o $(SRC)/match.o $(SRC)/index_io.o $(SRC)/index_file.o $(SRC)/prior.o $(SRC)/track.o $(SRC)/live.o $(SRC)/live_kernels.o $(SRC)/levels.o $(SRC)/band_levels.o
 
 all: $(OUT) oracle
 
@@ -64,7 +64,7 @@ tools/asan_window_list_plan: tools/asan_window_list_plan.cpp $(SRC)/window_list_
 tools/asan_band_plan: tools/asan_band_plan.cpp $(SRC)/band_plan.h $(SRC)/last_error.h include/birdnet_hip.h
 	$(CXX) $(ASAN_FLAGS) $< -o $@
 # ... and of the operands of finished plans: the planner's own files, as tools/asan_plan.cpp links them
-PLANNER_SRC := $(SRC)/onnx_proto.cpp $(SRC)/engine.cpp $(SRC)/onnx_rewrite.cpp $(SRC)/dft_bank.cpp $(SRC)/plan_passes.cpp $(SRC)/detect.cpp
+PLANNER_SRC := $(SRC)/onnx_proto.cpp $(SRC)/engine.cpp $(SRC)/onnx_rewrite.cpp $(SRC)/dft_bank.cpp $(SRC)/mbconv_fuse.cpp $(SRC)/plan_passes.cpp $(SRC)/detect.cpp
 tools/asan_plan_operands: tools/asan_plan_operands.cpp $(PLANNER_SRC) $(wildcard $(SRC)/*.h)
 	$(CXX) $(ASAN_FLAGS) -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include $< $(PLANNER_SRC) -o $@
 

@@ -12,7 +12,7 @@
 //  * Conv+BatchNorm+activation(+residual Add) and MatMul/Gemm+bias+activation
 //    chains are folded into one launch at import time.
 //
-// The planner's other three pieces -- graph rewrites before lowering, DFT-bank recognition, passes over the finished plan -- are free
+// The planner's other four pieces -- graph rewrites before lowering, DFT-bank recognition, MBConv fusion, passes over the finished plan -- are free
 // functions in files of their own (plan_build.h lists them); this file is Builder: one run over the graph and the lowering of every node.
 #include "engine.h"
 #include "dft_bank.h"
@@ -35,6 +35,20 @@ struct ActSpec {
     int32_t act = ACT_NONE;
     float p0 = 0, p1 = 0;
 };
+
+// Outputs along one axis of a window of extent `ke` (dilation included) at stride `s`, floor mode (Conv and the pools): the pads as the
+// attributes gave them, or as auto_pad decides
+int64_t window_out_dim(const std::string &auto_pad, int64_t in, int64_t ke, int64_t s, int64_t &p0, int64_t &p1) {
+    if (auto_pad == "SAME_UPPER" || auto_pad == "SAME_LOWER") {
+        const int64_t o = (in + s - 1) / s;
+        const int64_t tot = std::max<int64_t>((o - 1) * s + ke - in, 0);
+        p0 = auto_pad == "SAME_UPPER" ? tot / 2 : tot - tot / 2;
+        p1 = tot - p0;
+        return o;
+    }
+    if (auto_pad == "VALID") p0 = p1 = 0;
+    return (in + p0 + p1 - ke) / s + 1;
+}
 
 class Builder {
    public:
@@ -579,49 +593,6 @@ class Builder {
             push_op(std::move(f));
         }
         return true;
-    }
-
-    // Fused MBConv blocks the row-streaming kernel takes (mbrow.hip: one wave per (band of output rows, strip of output
-    // columns, 32 mid channels), nothing in LDS): tiles_x / tiles_y become strips / bands -- the squeeze partials follow --
-    // and `halo` the pixels it expands per sample.  Per-sample shapes only, so a segment's bits do not depend on its batch.
-    // BN_MBROW=0 keeps the tiled kernels.
-    static void row_streaming(MbDesc &m, double &halo) {
-        if (sw_is(sw::BN_MBROW, "0")) return;
-        if (!mbconv_row_supported(m)) return;
-        const int outw = mbconv_row_outw(m.k, m.s);
-        // a strip expands 32 halo columns for `outw` outputs whatever the map's width: on narrow maps (Perch: 32 or 16
-        // columns against strips of 30 / 28 / 14) half of every strip is idle and the tiled kernel wins (measured: 0.53-0.57
-        // utilisation -> 1.2-2.5x slower, 0.71 and above -> faster).  Round 3: such maps are usually TALL (Perch: 125 x 32,
-        // 63 x 16) -- the kernel then streams along the map's rows' direction instead (MbDesc::row_tr: strips across the
-        // height), if that fills its strips.  BN_MBROW=force takes the row kernel regardless (tests), BN_MBROW_TR=0 never
-        // transposes, =1 always does where the kernel supports it
-        const bool force = sw_is(sw::BN_MBROW, "force");
-        const int strips = (m.OW + outw - 1) / outw, strips_t = (m.OH + outw - 1) / outw;
-        const double util = (double)m.OW / (double)(strips * outw), util_t = (double)m.OH / (double)(strips_t * outw);
-        bool tr = m.k1 == 0 && m.k == 3 && util_t >= 0.7 && util_t > util + 0.08;  // (5 x 5 instances: no register to spare for the second addressing form)
-        if (sw_is(sw::BN_MBROW_TR, "0")) tr = false;
-        if (sw_is(sw::BN_MBROW_TR, "1")) tr = m.k1 == 0 && m.k == 3;
-        if (tr) {
-            MbDesc probe = m;
-            probe.row_tr = 1;
-            if (!mbconv_row_supported(probe)) tr = false;
-        }
-        if (!force && !tr && util < 0.7) return;
-        m.row_mode = 1;
-        m.row_tr = tr ? 1 : 0;
-        m.row_b3 = (sw_int(sw::BN_MBROW_B3) != 0 && sw_int(sw::BN_GEMM3) != 0 && m.k1 == 0 && m.Cin % 8 == 0) ? 1 : 0;
-        const int rows_k = tr ? m.OW : m.OH, cols_k = tr ? m.OH : m.OW;  // the kernel's output rows / columns
-        // band height: a band of toh output rows expands (toh - 1) s + k halo rows, so taller bands recompute less (12 rows of a
-        // 5x5 block: 16 halo rows instead of 2 x 10) -- what several contexts sharing the chip pay for; a block with one or two
-        // 32-channel chunks keeps 8 so that one context alone still has enough waves (stem: 38 us at 8, 48 us at 12)
-        // (bands balanced: 16 rows are one band of 16, not 12 + 4)
-        const int toh_target = (m.C + 31) / 32 >= 3 ? 12 : 8;
-        const int nbands = std::max(1, (rows_k + toh_target / 2 - 1) / toh_target);
-        const int toh_default = (rows_k + nbands - 1) / nbands;
-        m.toh = std::min<int32_t>(rows_k, sw_is_set(sw::BN_MBROW_TOH) ? std::max(1, sw_int(sw::BN_MBROW_TOH)) : toh_default);
-        m.tiles_x = (cols_k + outw - 1) / outw;
-        m.tiles_y = (rows_k + m.toh - 1) / m.toh;
-        halo = 32.0 * m.tiles_x * (double)m.tiles_y * ((m.toh - 1) * m.s + m.k);
     }
 
     // ------------------------------------------------------------- lowering
@@ -1682,18 +1653,7 @@ class Builder {
         const int64_t sh = sp == 2 ? st[0] : 1, sw = sp == 2 ? st[1] : st[0];
         int64_t pt = sp == 2 ? pads[0] : 0, pl = sp == 2 ? pads[1] : pads[0], pb = sp == 2 ? pads[2] : 0, pr = sp == 2 ? pads[3] : pads[1];
         const std::string auto_pad = n.attr_s("auto_pad", "NOTSET");
-        auto out_dim = [&](int64_t in, int64_t k, int64_t s_, int64_t &p0, int64_t &p1) {
-            if (auto_pad == "SAME_UPPER" || auto_pad == "SAME_LOWER") {
-                const int64_t o = (in + s_ - 1) / s_;
-                const int64_t tot = std::max<int64_t>((o - 1) * s_ + k - in, 0);
-                p0 = auto_pad == "SAME_UPPER" ? tot / 2 : tot - tot / 2;
-                p1 = tot - p0;
-                return o;
-            }
-            if (auto_pad == "VALID") p0 = p1 = 0;
-            return (in + p0 + p1 - k) / s_ + 1;
-        };
-        const int64_t OH = out_dim(H, kh, sh, pt, pb), OW = out_dim(W, kw, sw, pl, pr);
+        const int64_t OH = window_out_dim(auto_pad, H, kh, sh, pt, pb), OW = window_out_dim(auto_pad, W, kw, sw, pl, pr);
         if (OH <= 0 || OW <= 0) unsupported(n, "empty pooling output");
         x = to_channels_last(x, n.name);
         Dims od = sp == 2 ? Dims{C, OH, OW} : Dims{C, OW};
@@ -2314,19 +2274,20 @@ class Builder {
         return materialize(v, want, why);
     }
 
-    void lower_conv(const OnnxNode &n) {
-        Val x = get(n, 0);
-        int32_t gate_storage = x.gate_storage;
-        x.gate_storage = -1;
-        const Val &w = get(n, 1);
-        const Val *bptr = opt(n, 2);
-        if (x.is_const || !w.is_const || (bptr && !bptr->is_const)) unsupported(n, "Conv needs an activation input and constant weights");
-        size_t sp = x.dims.size() - 1;  // spatial rank
+    // What a Conv node's attributes and operand shapes fix.  A 1-D conv is the 2-D case with H = kh = 1: stride and dilation 1 and no pad along h.
+    struct ConvGeom {
+        size_t sp = 0;  // spatial rank
+        int64_t H = 0, W = 0, kh = 0, kw = 0;
+        std::vector<int64_t> strides, dil;       // {h, w}
+        int64_t pt = 0, pl = 0, pb = 0, pr = 0;  // after auto_pad
+        int64_t OH = 0, OW = 0;
+    };
+    ConvGeom conv_geom(const OnnxNode &n, const Val &x, const Val &w, int64_t groups) {
+        ConvGeom g;
+        const size_t sp = g.sp = x.dims.size() - 1;
         if (sp != 1 && sp != 2) unsupported(n, "only 1-D and 2-D convolutions are supported");
         if (w.dims.size() != sp + 2) unsupported(n, "weight rank mismatch");
-        int64_t groups = n.attr_i("group", 1);
-        int64_t Cin = x.dims[0], Cout = w.dims[0], cpg = w.dims[1];
-        if (cpg * groups != Cin || Cout % groups) unsupported(n, "channel/group mismatch");
+        if (w.dims[1] * groups != x.dims[0] || w.dims[0] % groups) unsupported(n, "channel/group mismatch");
         auto get2 = [&](const char *key, int64_t dflt) {
             auto v = n.attr_ints(key);
             if (v.empty()) v.assign(sp, dflt);
@@ -2335,31 +2296,67 @@ class Builder {
             if (sp == 1) v.insert(v.begin(), dflt == 0 ? 0 : 1);
             return v;
         };
-        int64_t H = sp == 2 ? x.dims[1] : 1, W = sp == 2 ? x.dims[2] : x.dims[1];
-        int64_t kh = sp == 2 ? w.dims[2] : 1, kw = sp == 2 ? w.dims[3] : w.dims[2];
-        auto strides = get2("strides", 1), dil = get2("dilations", 1);
+        g.H = sp == 2 ? x.dims[1] : 1; g.W = sp == 2 ? x.dims[2] : x.dims[1];
+        g.kh = sp == 2 ? w.dims[2] : 1; g.kw = sp == 2 ? w.dims[3] : w.dims[2];
+        g.strides = get2("strides", 1); g.dil = get2("dilations", 1);
         std::vector<int64_t> pads = n.attr_ints("pads");
         if (pads.empty()) pads.assign(2 * sp, 0);
         if (pads.size() != 2 * sp) unsupported(n, "pads does not match the spatial rank");
         for (auto e : pads) if (e < 0) unsupported(n, "negative pads");
-        int64_t pt, pl, pb, pr;
-        if (sp == 2) { pt = pads[0]; pl = pads[1]; pb = pads[2]; pr = pads[3]; }
-        else { pt = pb = 0; pl = pads[0]; pr = pads[1]; }
-        std::string auto_pad = n.attr_s("auto_pad", "NOTSET");
-        auto out_dim = [&](int64_t in, int64_t k, int64_t s, int64_t d, int64_t &p0, int64_t &p1) {
-            int64_t ke = (k - 1) * d + 1;
-            if (auto_pad == "SAME_UPPER" || auto_pad == "SAME_LOWER") {
-                int64_t o = (in + s - 1) / s;
-                int64_t tot = std::max<int64_t>((o - 1) * s + ke - in, 0);
-                p0 = auto_pad == "SAME_UPPER" ? tot / 2 : tot - tot / 2;
-                p1 = tot - p0;
-                return o;
-            }
-            if (auto_pad == "VALID") p0 = p1 = 0;
-            return (in + p0 + p1 - ke) / s + 1;
-        };
-        int64_t OH = out_dim(H, kh, strides[0], dil[0], pt, pb), OW = out_dim(W, kw, strides[1], dil[1], pl, pr);
-        if (OH <= 0 || OW <= 0) unsupported(n, "empty convolution output");
+        if (sp == 2) { g.pt = pads[0]; g.pl = pads[1]; g.pb = pads[2]; g.pr = pads[3]; }
+        else { g.pt = g.pb = 0; g.pl = pads[0]; g.pr = pads[1]; }
+        const std::string auto_pad = n.attr_s("auto_pad", "NOTSET");
+        g.OH = window_out_dim(auto_pad, g.H, (g.kh - 1) * g.dil[0] + 1, g.strides[0], g.pt, g.pb);
+        g.OW = window_out_dim(auto_pad, g.W, (g.kw - 1) * g.dil[1] + 1, g.strides[1], g.pl, g.pr);
+        if (g.OH <= 0 || g.OW <= 0) unsupported(n, "empty convolution output");
+        return g;
+    }
+    // BatchNormalization with constant statistics as the only reader of `cur`: folded into the filters and the bias, `cur` moves past it
+    void fold_batchnorm(std::string &cur, std::vector<float> &wf, std::vector<float> &bias, bool &has_bias) {
+        const int64_t Cout = (int64_t)bias.size(), per_out = (int64_t)wf.size() / Cout;
+        int c = sole_consumer(cur);
+        if (c < 0 || nodes_[c].op_type != "BatchNormalization" || nodes_[c].inputs[0] != cur) return;
+        const OnnxNode &bn_ = nodes_[c];
+        const Val &sc = get(bn_, 1), &bi = get(bn_, 2), &mu = get(bn_, 3), &var = get(bn_, 4);
+        if (!(sc.is_const && bi.is_const && mu.is_const && var.is_const && sc.numel() == Cout)) return;
+        float eps = bn_.attr_f("epsilon", 1e-5f);
+        for (int64_t o = 0; o < Cout; o++) {
+            float s = sc.f[o] / std::sqrt(var.f[o] + eps);
+            for (int64_t k = 0; k < per_out; k++) wf[o * per_out + k] *= s;
+            bias[o] = (bias[o] - mu.f[o]) * s + bi.f[o];
+        }
+        has_bias = true;
+        absorbed_[c] = true;
+        cur = bn_.outputs[0];
+    }
+    // residual: Add(cur, other) as the only reader of `cur`, with `other` an available activation of identical shape and layout
+    bool absorb_residual(std::string &cur, const Dims &out_dims, const Dims &out_strides, Val &res) {
+        int c = sole_consumer(cur);
+        if (c < 0 || nodes_[c].op_type != "Add") return false;
+        const OnnxNode &ad = nodes_[c];
+        const std::string &other = ad.inputs[0] == cur ? ad.inputs[1] : ad.inputs[0];
+        auto it = vals_.find(other);
+        if (it == vals_.end() || it->second.is_const || it->second.dims != out_dims || it->second.space != Space::ARENA || !it->second.strides_equal(out_strides))
+            return false;
+        res = it->second;
+        absorbed_[c] = true;
+        cur = ad.outputs[0];
+        return true;
+    }
+
+    void lower_conv(const OnnxNode &n) {
+        Val x = get(n, 0);
+        int32_t gate_storage = x.gate_storage;
+        x.gate_storage = -1;
+        const Val &w = get(n, 1);
+        const Val *bptr = opt(n, 2);
+        if (x.is_const || !w.is_const || (bptr && !bptr->is_const)) unsupported(n, "Conv needs an activation input and constant weights");
+        const int64_t groups = n.attr_i("group", 1);
+        ConvGeom geo = conv_geom(n, x, w, groups);
+        const size_t sp = geo.sp;
+        const int64_t Cin = x.dims[0], Cout = w.dims[0], cpg = w.dims[1];
+        const int64_t H = geo.H, kh = geo.kh, kw = geo.kw, OH = geo.OH, OW = geo.OW;
+        const std::vector<int64_t> &strides = geo.strides, &dil = geo.dil;
 
         // ---- epilogue fusion: BatchNorm, activation, residual ----
         std::vector<float> wf = w.f;
@@ -2367,47 +2364,13 @@ class Builder {
         bool has_bias = bptr != nullptr;
         if (bptr) bias = bptr->f;
         std::string cur = n.outputs[0];
-        int64_t per_out = wf.size() / Cout;
-        {
-            int c = sole_consumer(cur);
-            if (c >= 0 && nodes_[c].op_type == "BatchNormalization" && nodes_[c].inputs[0] == cur) {
-                const OnnxNode &bn_ = nodes_[c];
-                const Val &sc = get(bn_, 1), &bi = get(bn_, 2), &mu = get(bn_, 3), &var = get(bn_, 4);
-                if (sc.is_const && bi.is_const && mu.is_const && var.is_const && sc.numel() == Cout) {
-                    float eps = bn_.attr_f("epsilon", 1e-5f);
-                    for (int64_t o = 0; o < Cout; o++) {
-                        float s = sc.f[o] / std::sqrt(var.f[o] + eps);
-                        for (int64_t k = 0; k < per_out; k++) wf[o * per_out + k] *= s;
-                        bias[o] = (bias[o] - mu.f[o]) * s + bi.f[o];
-                    }
-                    has_bias = true;
-                    absorbed_[c] = true;
-                    cur = bn_.outputs[0];
-                }
-            }
-        }
+        fold_batchnorm(cur, wf, bias, has_bias);
         ActSpec act;
         absorb_activation(cur, act);
-        // residual: Add(cur, other) with `other` an available activation of identical shape
-        Val res;
-        bool has_res = false;
         Dims out_dims = sp == 2 ? Dims{Cout, OH, OW} : Dims{Cout, OW};
         Dims out_strides = sp == 2 ? Dims{1, OW * Cout, Cout} : Dims{1, Cout};
-        {
-            int c = sole_consumer(cur);
-            if (c >= 0 && nodes_[c].op_type == "Add") {
-                const OnnxNode &ad = nodes_[c];
-                const std::string &other = ad.inputs[0] == cur ? ad.inputs[1] : ad.inputs[0];
-                auto it = vals_.find(other);
-                if (it != vals_.end() && !it->second.is_const && it->second.dims == out_dims && it->second.space == Space::ARENA &&
-                    it->second.strides_equal(out_strides)) {
-                    res = it->second;
-                    has_res = true;
-                    absorbed_[c] = true;
-                    cur = ad.outputs[0];
-                }
-            }
-        }
+        Val res;
+        const bool has_res = absorb_residual(cur, out_dims, out_strides, res);
 
         Val out = new_act(out_dims, out_strides);
         PlanOp op;
@@ -2415,30 +2378,34 @@ class Builder {
         op.r.out = ref_of(out);
         op.macs = (double)OH * OW * Cout * kh * kw * cpg;
         op.weight_bytes = 4.0 * (wf.size() + (has_bias ? Cout : 0));
-        op.bytes = 4.0 * ((double)Cin * H * W + (double)Cout * OH * OW * (has_res ? 2 : 1));
+        op.bytes = 4.0 * ((double)Cin * H * geo.W + (double)Cout * OH * OW * (has_res ? 2 : 1));
         if (has_bias) op.r.bias = Ref{Space::CONSTS, add_const(bias), 0};
         if (has_res) op.r.residual = ref_of(res);
 
-        bool unit_dil = dil[0] == 1 && dil[1] == 1;
-        // a padded 1-D convolution with a long filter (STFT / learned front ends) is worth a padded copy
-        // of its input: it then runs as the overlapping-rows GEMM on the matrix cores instead of the
-        // direct kernel (Perch-style front end: 14 ms -> GEMM time at batch 128)
-        if (groups == 1 && kh == 1 && H == 1 && unit_dil && pt == 0 && pb == 0 && (pl || pr) && kw * Cin >= 64) {
-            if (gate_storage >= 0) { Val gx = x; gx.gate_storage = gate_storage; x = apply_gate(gx, n.name); gate_storage = -1; }
-            Dims lo(x.dims.size(), 0), hi(x.dims.size(), 0);
-            lo.back() = pl; hi.back() = pr;
-            x = pad_copy(x, lo, hi, 0.0f, n.name);
-            W += pl + pr;
-            pl = pr = 0;
-        }
-        bool no_pad = pt == 0 && pl == 0 && pb == 0 && pr == 0;
-        const bool gemm_path = groups == 1 && kh == 1 && unit_dil && no_pad && (H == 1 || (kw == 1 && strides[0] == 1 && strides[1] == 1));
-        if (gate_storage >= 0 && !(gemm_path && kw == 1)) {  // only the 1x1 GEMM folds the SE gate
+        // the SE gate still pending on x as a launch of its own, where this conv cannot fold it
+        auto ungate = [&] {
+            if (gate_storage < 0) return;
             Val gx = x;
             gx.gate_storage = gate_storage;
             x = apply_gate(gx, n.name);
             gate_storage = -1;
+        };
+        bool unit_dil = dil[0] == 1 && dil[1] == 1;
+        // a padded 1-D convolution with a long filter (STFT / learned front ends) is worth a padded copy
+        // of its input: it then runs as the overlapping-rows GEMM on the matrix cores instead of the
+        // direct kernel (Perch-style front end: 14 ms -> GEMM time at batch 128)
+        if (groups == 1 && kh == 1 && H == 1 && unit_dil && geo.pt == 0 && geo.pb == 0 && (geo.pl || geo.pr) && kw * Cin >= 64) {
+            ungate();
+            Dims lo(x.dims.size(), 0), hi(x.dims.size(), 0);
+            lo.back() = geo.pl; hi.back() = geo.pr;
+            x = pad_copy(x, lo, hi, 0.0f, n.name);
+            geo.W += geo.pl + geo.pr;
+            geo.pl = geo.pr = 0;
         }
+        const int64_t W = geo.W, pt = geo.pt, pl = geo.pl;
+        bool no_pad = pt == 0 && pl == 0 && geo.pb == 0 && geo.pr == 0;
+        const bool gemm_path = groups == 1 && kh == 1 && unit_dil && no_pad && (H == 1 || (kw == 1 && strides[0] == 1 && strides[1] == 1));
+        if (!(gemm_path && kw == 1)) ungate();  // only the 1x1 GEMM folds the SE gate
         if (gemm_path) {
             // GEMM: 1x1 conv (rows = H*W) or 1-D conv as overlapping rows (rows = OW, K = kw*Cin)
             x = to_channels_last(x, n.name);
@@ -2506,186 +2473,10 @@ class Builder {
                 for (int64_t k = 0; k < kh * kw; k++) wp[k * Cin + c] = wf[c * kh * kw + k];
             op.r.w = Ref{Space::CONSTS, add_const(wp), 0};
             op.r.a = ref_of(x);
-            // expand 1x1 conv immediately before, consumed only here?  Then both run in one launch with the
-            // expanded tensor kept in LDS (mbconv_expand_dw_kernel): the 6x-expanded activation never
-            // touches HBM.  Measured on MI355X (batch 32, per pair): 48x256x16->96 s2: 101 -> 79 us,
-            // 24x128x24->144 s1: 80 -> 54 us, 5x5 s2: 60 -> 52 us, 12x64x40->240 5x5 s1: 54 -> 50 us; on
-            // the 6x32 maps (2 tiles per sample) and for K >= 80 the separate launches win, so the rule
-            // below keeps those unfused.  The rule only looks at per-sample shapes (batch invariance).
-            // BN_MBFUSE=0 disables, BN_MBFUSE=force fuses every eligible pair (tests).
-            const bool mb_off = sw_is(sw::BN_MBFUSE, "0");
-            // Stem variant: the producer is a dense k1 x k1 convolution with few input channels (k1*k1*Cin1 <= 48,
-            // e.g. the 3x3 stride-2 conv over the 2-channel spectrogram image).  Its output tile is rebuilt from im2col
-            // rows staged in LDS and never written to HBM either (same kernel, different staging).  BN_STEMFUSE=0 disables.
-            if (d.tiled && kh == kw && strides[0] == strides[1] && !mb_off && !plan_.ops.empty() &&
-                sw_on(sw::BN_STEMFUSE)) {
-                PlanOp &pe = plan_.ops.back();
-                const ConvDesc &cd = pe.conv;
-                const bool act_zero = act_keeps_zero(cd.act, cd.p0, cd.p1);
-                const bool stem = pe.kind == OpKind::CONV && pe.r.out.space == Space::ARENA && pe.r.out.id == x.storage && pe.r.out.offset == 0 && x.offset == 0 &&
-                                  cd.groups == 1 && cd.kh == cd.kw && cd.sh == cd.sw && cd.dh == 1 && cd.dw == 1 && !cd.has_res && cd.Cin <= 4 &&
-                                  cd.kh * cd.kw * cd.Cin <= 48 && cd.OH == H && cd.OW == W && cd.Cout == Cin && act_zero &&
-                                  (H * W >= 3072 || sw_is(sw::BN_MBFUSE, "force"));
-                MbDesc probe{};
-                probe.k = (int32_t)kw; probe.s = (int32_t)strides[1]; probe.Cin = stem ? cd.kh * cd.kw * cd.Cin : 4; probe.C = (int32_t)Cin;
-                if (stem && mbconv_lds_bytes(probe) <= 150 * 1024 && sole_consumer(n.inputs[0]) == cur_) {
-                    PlanOp mb;
-                    mb.kind = OpKind::MBCONV;
-                    mb.name = "stem:" + pe.name.substr(pe.name.find(':') + 1) + "+" + n.name;
-                    mb.r.out = op.r.out;
-                    mb.r.a = pe.r.a;
-                    // first-conv filters [kh][kw][Cin1][Cout] (as lowered for the direct kernel) -> [Cout][KW]: im2col column
-                    // order (ky, kx, c), zero padded to 8-wide K groups
-                    const int64_t K1 = (int64_t)cd.kh * cd.kw * cd.Cin, KW = (K1 + 7) / 8 * 8;
-                    {
-                        const std::vector<float> &w0 = plan_.consts[pe.r.w.id];
-                        std::vector<float> wpk((size_t)(Cin * KW), 0.0f);
-                        for (int64_t nn = 0; nn < Cin; nn++)
-                            for (int64_t k = 0; k < K1; k++) wpk[nn * KW + k] = w0[pe.r.w.offset + k * Cin + nn];
-                        mb.r.w = Ref{Space::CONSTS, add_const(wpk), 0};
-                    }
-                    mb.r.bias = pe.r.bias;
-                    mb.r.w2 = op.r.w; mb.r.bias2 = op.r.bias;
-                    MbDesc &m = mb.mb;
-                    m.H = (int32_t)H; m.W = (int32_t)W; m.Cin = (int32_t)K1; m.C = (int32_t)Cin; m.OH = (int32_t)OH; m.OW = (int32_t)OW;
-                    m.k = (int32_t)kw; m.s = (int32_t)strides[1]; m.pt = (int32_t)pt; m.pl = (int32_t)pl;
-                    m.act1 = cd.act; m.p0_1 = cd.p0; m.p1_1 = cd.p1; m.has_bias1 = cd.has_bias;
-                    m.act2 = act.act; m.p0_2 = act.p0; m.p1_2 = act.p1; m.has_bias2 = has_bias;
-                    m.in_bs = cd.in_bs; m.out_bs = d.out_bs;
-                    m.k1 = cd.kh; m.s1 = cd.sh; m.pt1 = cd.pt; m.pl1 = cd.pl; m.H1 = cd.H; m.W1 = cd.W; m.Cin1 = cd.Cin;
-                    const int toh = m.s == 1 ? 8 : 4, tow = m.s == 1 ? 16 : 8;
-                    m.tiles_x = (int32_t)((OW + tow - 1) / tow); m.tiles_y = (int32_t)((OH + toh - 1) / toh);
-                    double halo = (double)((toh - 1) * m.s + m.k) * ((tow - 1) * m.s + m.k) * m.tiles_x * m.tiles_y;
-                    row_streaming(m, halo);
-                    mb.macs = op.macs;
-                    mb.weight_bytes = op.weight_bytes + pe.weight_bytes;
-                    mb.bytes = 4.0 * ((double)cd.H * cd.W * cd.Cin + (double)OH * OW * Cin);
-                    mb.mfma = false;
-                    mb.macs_mfma_extra = halo * (double)K1 * Cin;
-                    mb.macs_recompute = std::max(0.0, mb.macs_mfma_extra - (double)H * W * (double)K1 * Cin);
-                    plan_.ops.pop_back();
-                    push_op(std::move(mb));
-                    define(cur, out);
-                    return;
-                }
-            }
-            if (d.tiled && kh == kw && strides[0] == strides[1] && !mb_off && !plan_.ops.empty()) {
-                PlanOp &pe = plan_.ops.back();
-                const int maxk = std::min(48, sw_int(sw::BN_MBFUSE_MAXK));  // kernel: <= 6 K groups in registers
-                // the kernel relies on act(0) == 0 for the expand activation (pixels outside the image)
-                const bool act_zero = act_keeps_zero(pe.gemm.act, pe.gemm.p0, pe.gemm.p1);
-                const double maxhalo = sw_double(sw::BN_MBFUSE_HALO);
-                // small feature maps can take the whole-map kernel (one block = 32 mid channels x the whole map:
-                // no halo, any K up to 256, complete squeeze sums).  Opt-in (BN_MBMAP=1): measured on MI355X at
-                // batch 32 it saves 10 launches and ~1% of single-stream latency, but its per-block fixed costs
-                // (filter slab + A rows per 32-channel chunk, half the waves idle on 3x16 maps) make the
-                // marginal cost per extra batch ~30% higher than GEMM + whole-map depthwise, and the three-
-                // context throughput drops from 34.2k to 33.1k seg/s.
-                const bool map_off = !sw_is(sw::BN_MBMAP, "1");
-                const int64_t map_maxhw = sw_i64(sw::BN_MBMAP_MAXHW);
-                const bool producer0 = pe.kind == OpKind::GEMM && pe.r.out.space == Space::ARENA && pe.r.out.id == x.storage && pe.r.out.offset == 0 &&
-                                       x.offset == 0 && !pe.gemm.has_scale && !pe.gemm.has_res && pe.gemm.rows == H * W && pe.gemm.N == Cin &&
-                                       pe.gemm.lda == pe.gemm.K && pe.gemm.K % 4 == 0 && pe.r.a.offset % 4 == 0 && !pe.gemm.fold && !pe.gemm.npost &&
-                                       (pe.r.a.space != Space::ARENA || plan_.storages[pe.r.a.id].elems % 4 == 0);
-                // Whole-map form with the INPUT resident in LDS (mbmap.hip, round 3): one block = one sample's map x a group of
-                // mid channels, input fetched once per block by LDS-DMA, no staging on the vector ALU.  Default wherever a
-                // configuration fits (192- and 48-pixel maps); BN_MBMAP2=0 disables.
-                int map2 = 0, map_b3 = 0, map_ws = 0;
-                MbmapShape mshape;
-                if (producer0) {
-                    MbDesc q{};
-                    q.H = (int32_t)H; q.W = (int32_t)W; q.Cin = pe.gemm.K; q.C = (int32_t)Cin; q.OH = (int32_t)OH; q.OW = (int32_t)OW;
-                    q.k = (int32_t)kw; q.s = (int32_t)strides[1]; q.pt = (int32_t)pt; q.pl = (int32_t)pl;
-                    q.act1 = pe.gemm.act; q.act2 = act.act; q.in_bs = pe.gemm.a_bs;
-                    mshape = mbmap_shape(q);
-                    map2 = mshape.cfg;
-                    map_b3 = mbmap_b3_steps(q, mshape);
-                    map_ws = mbmap_ws_steps(q, mshape);
-                }
-                const bool whole_map = map2 != 0 || (!map_off && H * W <= map_maxhw);
-                const bool producer = producer0 && (map2 != 0 || pe.gemm.K <= (whole_map ? 256 : maxk));
-                // halo recompute factor of the expand conv: staged halo pixels / image pixels
-                const int toh0 = strides[1] == 1 ? 8 : 4, tow0 = strides[1] == 1 ? 16 : 8;
-                const int64_t hp = ((toh0 - 1) * strides[1] + kw) * ((tow0 - 1) * strides[1] + kw);
-                const double halo_factor = (double)((hp + 31) / 32 * 32) * ((OW + tow0 - 1) / tow0) * ((OH + toh0 - 1) / toh0) / (double)(H * W);
-                const bool force = sw_is(sw::BN_MBFUSE, "force");  // tests: small feature maps too
-                // (round 3: stride-2 blocks on 768-pixel maps too -- with the row-streaming kernel the 12x64x40->240 s2 pair
-                // runs in 17.5 us instead of 16.5 + 16.4, marginal cost per extra batch 8.6 against 24 us)
-                const bool big_enough = H * W >= 768;
-                MbDesc probe{};
-                probe.k = (int32_t)kw; probe.s = (int32_t)strides[1]; probe.Cin = producer ? pe.gemm.K : 4; probe.C = (int32_t)Cin;
-                probe.H = (int32_t)H; probe.W = (int32_t)W; probe.whole_map = whole_map ? 1 : 0;
-                const bool fits = map2 != 0 || mbconv_lds_bytes(probe) <= 150 * 1024;
-                const bool tiled_ok = act_zero && ((halo_factor <= maxhalo && big_enough) || force);
-                if (producer && fits && (whole_map || tiled_ok) && sole_consumer(n.inputs[0]) == cur_) {
-                    PlanOp mb;
-                    mb.kind = OpKind::MBCONV;
-                    mb.name = "mbconv:" + pe.name.substr(pe.name.find(':') + 1) + "+" + n.name;
-                    mb.r.out = op.r.out;
-                    mb.r.a = pe.r.a;
-                    // expand filters repacked for the kernel: [C][KW] rows = Cin weights | zeros, KW = Cin rounded up to
-                    // 8-wide K groups (the bias starts the accumulators)
-                    if (whole_map && map2 && map_ws) {
-                        // mbmap_ws.hip: the filters as bf16 planes in fragment order (plan_rules.h)
-                        mb.r.w = Ref{Space::CONSTS, add_const(pack_mbmap_w3p(plan_.consts[pe.r.w.id].data() + pe.r.w.offset, Cin, pe.gemm.K)), 0};
-                    } else if (whole_map && map2 && mshape.cin_pad != pe.gemm.K) {
-                        // mbmap.hip with padded k: the filter rows get the zeros the input rows get from the zero page
-                        const int64_t Kc = pe.gemm.K, KP = mshape.cin_pad;
-                        const std::vector<float> &w0 = plan_.consts[pe.r.w.id];
-                        std::vector<float> wpk((size_t)(Cin * KP), 0.0f);
-                        for (int64_t nn = 0; nn < Cin; nn++)
-                            for (int64_t k = 0; k < Kc; k++) wpk[nn * KP + k] = w0[pe.r.w.offset + nn * Kc + k];
-                        mb.r.w = Ref{Space::CONSTS, add_const(wpk), 0};
-                    } else if (whole_map && map2 && map_b3) {
-                        // mbmap.hip's bf16x3 form: the filters in the order of its LDS chunk image (plan_rules.h)
-                        mb.r.w = Ref{Space::CONSTS, add_const(pack_mbmap_w3f(plan_.consts[pe.r.w.id].data() + pe.r.w.offset, Cin, pe.gemm.K)), 0};
-                    } else if (whole_map) {
-                        mb.r.w = pe.r.w;  // [C][Cin] as the GEMM had it
-                    } else {
-                        const int64_t Kc = pe.gemm.K, KW = (Kc + 7) / 8 * 8;
-                        const std::vector<float> &w0 = plan_.consts[pe.r.w.id];
-                        std::vector<float> wpk((size_t)(Cin * KW), 0.0f);
-                        for (int64_t nn = 0; nn < Cin; nn++)
-                            for (int64_t k = 0; k < Kc; k++) wpk[nn * KW + k] = w0[pe.r.w.offset + nn * Kc + k];
-                        mb.r.w = Ref{Space::CONSTS, add_const(wpk), 0};
-                    }
-                    mb.r.bias = pe.r.bias;
-                    mb.r.w2 = op.r.w; mb.r.bias2 = op.r.bias;
-                    MbDesc &m = mb.mb;
-                    m.H = (int32_t)H; m.W = (int32_t)W; m.Cin = pe.gemm.K; m.C = (int32_t)Cin; m.OH = (int32_t)OH; m.OW = (int32_t)OW;
-                    m.k = (int32_t)kw; m.s = (int32_t)strides[1]; m.pt = (int32_t)pt; m.pl = (int32_t)pl;
-                    m.act1 = pe.gemm.act; m.p0_1 = pe.gemm.p0; m.p1_1 = pe.gemm.p1; m.has_bias1 = pe.gemm.has_bias;
-                    m.act2 = act.act; m.p0_2 = act.p0; m.p1_2 = act.p1; m.has_bias2 = has_bias;
-                    m.in_bs = pe.gemm.a_bs; m.out_bs = d.out_bs;
-                    const int toh = m.s == 1 ? 8 : 4, tow = m.s == 1 ? 16 : 8;
-                    m.tiles_x = (int32_t)((OW + tow - 1) / tow); m.tiles_y = (int32_t)((OH + toh - 1) / toh);
-                    double halo = (double)((toh - 1) * m.s + m.k) * ((tow - 1) * m.s + m.k) * m.tiles_x * m.tiles_y;
-                    if (whole_map) {
-                        m.whole_map = map2 ? 2 : 1;
-                        m.tiles_x = m.tiles_y = 1;  // one squeeze partial per sample
-                        halo = (double)H * W;
-                        if (map2) {
-                            m.map_bands = mshape.bands; m.map_tr = mshape.tr; m.cin_pad = mshape.cin_pad;
-                            m.map_b3 = map_b3; m.map_ws = map_ws;
-                            m.tiles_y = mshape.bands;  // ... per band
-                            // expand work performed: every band expands the 6 rows it loads (the rows two bands share twice), over the padded k
-                            if (mshape.bands > 1) halo = (double)mshape.bands * 6.0 * (double)(mshape.tr ? H : W);
-                            halo *= (double)mshape.cin_pad / (double)pe.gemm.K;
-                        }
-                    } else {
-                        row_streaming(m, halo);
-                    }
-                    mb.macs = op.macs;                                   // depthwise part (VALU)
-                    mb.weight_bytes = op.weight_bytes + pe.weight_bytes;
-                    mb.bytes = 4.0 * ((double)H * W * pe.gemm.K + (double)OH * OW * Cin);
-                    mb.mfma = false;
-                    mb.macs_mfma_extra = halo * pe.gemm.K * Cin;          // expand part incl. halo recompute
-                    mb.macs_recompute = std::max(0.0, mb.macs_mfma_extra - (double)H * W * (double)pe.gemm.K * Cin);
-                    plan_.ops.pop_back();
-                    push_op(std::move(mb));
-                    define(cur, out);
-                    return;
-                }
+            // ... or, with the launch before it, one fused MBConv launch (mbconv_fuse.cpp)
+            if (fuse_mbconv(plan_, op, n.name, sole_consumer(n.inputs[0]) == cur_)) {
+                define(cur, out);
+                return;
             }
         } else {
             x = to_channels_last(x, n.name);

@@ -1,10 +1,11 @@
-// What the pieces of the planner share (private to csrc/; engine.h is the public face).  The planner is four programs:
+// What the pieces of the planner share (private to csrc/; engine.h is the public face).  The planner is five programs:
 //   engine.cpp        Builder: one run over the graph, the lowering of every node to launches
 //   onnx_rewrite.cpp  rewrites of the ONNX graph before lowering      -- nodes and constants, never the plan
 //   dft_bank.cpp      a filter bank recognised as a windowed DFT, and the FFT / quarter-fold launches it becomes
+//   mbconv_fuse.cpp   a depthwise conv and the launch before it as one fused MBConv launch, where a rule allows it
 //   plan_passes.cpp   passes over the finished launch list            -- the plan, never the graph
 // Here: the value a graph tensor has while planning (Val), the plan's three primitives (touch, add_const, push_op) and the entry points
-// of the other three files.  None of these symbols leaves the library.
+// of the other four files.  None of these symbols leaves the library.
 #pragma once
 #include <algorithm>
 #include <map>
@@ -126,6 +127,11 @@ struct LiveGraph {
 void canonicalize_spectrogram_dialects(const OnnxModel &m, std::vector<OnnxNode> &nodes, std::map<std::string, Val> &vals);  // before liveness
 void prune_zero_rows(const LiveGraph &g);
 void merge_framing_products(const LiveGraph &g);
+
+// ------------------------------------------------------------------ mbconv_fuse.cpp
+// The depthwise launch `dw` (not yet pushed) and the launch before it as ONE MBCONV launch, where a rule allows it: replaces
+// plan.ops.back() and returns true, or leaves the plan untouched.  `only_reader`: the producer's output feeds this node alone.
+bool fuse_mbconv(Plan &plan, const PlanOp &dw, const std::string &node_name, bool only_reader);
 
 // ------------------------------------------------------------------ plan_passes.cpp
 // Every pass over the lowered plan, in their one fixed order, down to the memory plan.

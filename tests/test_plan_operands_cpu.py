@@ -22,7 +22,7 @@ def test_plan_operands_under_asan_ubsan(tmp_path):
     src = os.path.join(ROOT, "rust-birdnet-onnx_amd", "csrc")
     cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-D__HIP_PLATFORM_AMD__",
            "-I/opt/rocm/include", "-I" + os.path.join(ROOT, "include"), "-I" + src, os.path.join(ROOT, "tools", "asan_plan_operands.cpp")]
-    cmd += [os.path.join(src, f + ".cpp") for f in ("onnx_proto", "engine", "onnx_rewrite", "dft_bank", "plan_passes", "detect")] + ["-o", str(out)]
+    cmd += [os.path.join(src, f + ".cpp") for f in ("onnx_proto", "engine", "onnx_rewrite", "dft_bank", "mbconv_fuse", "plan_passes", "detect")] + ["-o", str(out)]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         # only a missing sanitizer runtime is a reason to skip; any other compile / link error is a finding

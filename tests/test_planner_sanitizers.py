@@ -21,7 +21,7 @@ def asan_binary(tmp_path_factory):
     cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-D__HIP_PLATFORM_AMD__",
            "-I/opt/rocm/include", "-I" + os.path.join(ROOT, "include"), "-I" + src, os.path.join(ROOT, "tools", "asan_plan.cpp"),
            os.path.join(src, "onnx_proto.cpp"), os.path.join(src, "engine.cpp"), os.path.join(src, "onnx_rewrite.cpp"), os.path.join(src, "dft_bank.cpp"),
-           os.path.join(src, "plan_passes.cpp"), os.path.join(src, "detect.cpp"), "-o", str(out)]
+           os.path.join(src, "mbconv_fuse.cpp"), os.path.join(src, "plan_passes.cpp"), os.path.join(src, "detect.cpp"), "-o", str(out)]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         # only a missing sanitizer runtime is a reason to skip; any other compile / link error is a finding (round 3: the planner had

@@ -1,6 +1,6 @@
 // Host-side sanitizer check of the ONNX reader + planner (no device needed):
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude \
-//       -Irust-birdnet-onnx_amd/csrc tools/asan_plan.cpp rust-birdnet-onnx_amd/csrc/{onnx_proto,engine,onnx_rewrite,dft_bank,plan_passes,detect}.cpp -o /tmp/asan_plan
+//       -Irust-birdnet-onnx_amd/csrc tools/asan_plan.cpp rust-birdnet-onnx_amd/csrc/{onnx_proto,engine,onnx_rewrite,dft_bank,mbconv_fuse,plan_passes,detect}.cpp -o /tmp/asan_plan
 //   /tmp/asan_plan model.onnx [more.onnx ...]      (also feeds truncated / bit-flipped copies of each file)
 // The shape rules the planner shares with the launchers live in csrc/plan_rules.h (inline, host C++), so nothing is restated here and
 // no HIP object is linked.

@@ -1,7 +1,7 @@
 // Host-side printer of a launch plan, by value (no device needed): two builds of the planner agree on a model exactly when their outputs
 // here are the same text.  Built like tools/asan_plan.cpp, without the sanitizers:
 //   g++ -std=c++17 -O1 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude -Irust-birdnet-onnx_amd/csrc tools/plan_digest.cpp
-//       rust-birdnet-onnx_amd/csrc/{onnx_proto,engine,onnx_rewrite,dft_bank,plan_passes,detect}.cpp -o /tmp/plan_digest
+//       rust-birdnet-onnx_amd/csrc/{onnx_proto,engine,onnx_rewrite,dft_bank,mbconv_fuse,plan_passes,detect}.cpp -o /tmp/plan_digest
 //   /tmp/plan_digest model.onnx [more.onnx ...]      (BN_* switches from the environment, as for the library)
 // Every launch with its operands and every field of the descriptors its kind uses (field by field: struct padding is undefined), every
 // storage, every output, the plan's totals, and the length and an FNV-1a-64 hash of every constant.  Doubles and floats print as %a.
