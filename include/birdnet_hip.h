@@ -543,6 +543,40 @@ bn_status bn_recording_band_levels(const bn_recording *r, size_t segment_samples
 bn_status bn_band_bins(uint32_t sample_rate, uint32_t frame, double lo_hz, double hi_hz, uint32_t *bin_lo, uint32_t *bin_hi);
 
 /*
+ * FIR filtering: take the rumble out instead of gating around it.  bn_recording_create_filtered returns a NEW mono f32 recording
+ * of bn_recording_samples(src) samples on src's device,
+ *   y[n] = sum_t taps[t] * x[n + (n_taps - 1) / 2 - t],   t = 0 .. n_taps - 1,
+ * where x is the f32 sample src's layout rule defines ("PCM layouts": channel select or mix included) and 0 outside [0, samples),
+ * as chunk_audio pads.  The filter is centred: a symmetric (linear-phase) filter has its group delay removed, so window k of the
+ * result covers the same time as window k of src.  src may have any layout, be resampled, a channel view or asynchronously
+ * uploaded (the call waits for the whole upload); it is left untouched and may be freed first.  The result behaves as a resampled
+ * recording does: a mono f32 store that every consumer of a recording takes, and bn_recording_view_channel accepts channel 0 or
+ * BN_PCM_MIX only.  An empty source gives an empty recording.
+ *
+ * Arithmetic.  The filter runs as a banded Toeplitz product on the bf16 matrix pipe (csrc/fir.hip): taps and samples are each the
+ * exact sum of three bf16 terms, six of the nine partial products are kept, each exact in the f32 accumulator; the dropped ones
+ * are below 2^-21 |tap * sample|.  An output is one accumulation chain over the taps in a fixed order, so its bits depend on the
+ * taps, the samples it reads and n mod 16 only -- not on the recording's length or layout.  A tap of exactly 1.0 or a sample of
+ * exactly 1.0 reproduces its partner bit for bit.  Non-finite samples: a NaN or +-Inf sample makes the outputs within n_taps + 46
+ * samples of it NaN (the padded depth: an infinity times a zero term), as everywhere on this arithmetic; DESIGN.md 7c, "FIR filtering".
+ *
+ * BN_ERR_INVALID_ARG, with a message and no handle written: NULL src, taps or out, n_taps that is 0, even or above BN_FIR_MAX_TAPS,
+ * a tap that is NaN or +-Inf.
+ *
+ * bn_fir_bandpass (host only, no device): a linear-phase windowed-sinc design, computed in double and rounded to f32 once.  With
+ * tau = t - (n_taps - 1) / 2, f1 = lo_hz / sample_rate, f2 = hi_hz / sample_rate and sinc(x) = sin(pi x) / (pi x),
+ *   h[t] = (2 f2 sinc(2 f2 tau) - 2 f1 sinc(2 f1 tau)) * w(tau),   w(tau) = I0(8.6 sqrt(1 - (2 tau / (n_taps - 1))^2)) / I0(8.6)
+ * (the Kaiser window of the resampler's table; w = 1 for n_taps == 1).  lo_hz <= 0 makes it a low-pass (f1 = 0), hi_hz >=
+ * sample_rate / 2 a high-pass (f2 = 0.5).  The taps are divided, in double, by the response sum_t h[t] cos(2 pi fc tau) at the
+ * centre fc of the pass band [max(lo_hz, 0), min(hi_hz, sample_rate / 2)], so the gain there is 1 before the rounding; they are
+ * symmetric bit for bit.  The stop band lies about 87 dB down beyond a transition of 5.48 * sample_rate / (n_taps - 1) Hz.
+ * BN_ERR_INVALID_ARG: sample_rate 0, lo_hz >= hi_hz (or a NaN), lo_hz >= sample_rate / 2, hi_hz <= 0, n_taps as above, NULL output.
+ */
+#define BN_FIR_MAX_TAPS 2047
+bn_status bn_recording_create_filtered(const bn_recording *src, const float *taps, size_t n_taps, bn_recording **out);
+bn_status bn_fir_bandpass(uint32_t sample_rate, double lo_hz, double hi_hz, size_t n_taps, float *taps_out);
+
+/*
  * bn_step_window_list: bn_step_windows over an explicit list.  Row i of the batch is the S = sample_count frames of
  * refs[i].recording from frame refs[i].start on, zeros past the end; start is any frame of the recording, no multiple of any step
  * (a window centred on a peak is fine).  The rows are gathered on the device straight into the context's input buffer -- the

@@ -220,6 +220,9 @@ class Recording {
      * Error::Inference with the library's message on a refusal. */
     std::vector<bn_window_bands> band_levels(size_t segment_samples, size_t step_samples, const bn_band_spec &spec, size_t first = 0,
                                              size_t count = (size_t)-1) const;
+    /* bn_recording_create_filtered: a new mono f32 recording, this one through the centred FIR filter `taps` (birdnet_hip.h, "FIR
+     * filtering"; bn_fir_bandpass designs a band-pass).  Throws Error::Inference with the library's message on a refusal. */
+    Recording filtered(const float *taps, size_t n_taps) const;
     size_t n_samples() const { return n_samples_; }
     const bn_recording *raw() const { return rec_.get(); }
 
@@ -530,6 +533,8 @@ int32_t bnh_recording_levels(const bnh_recording *r, size_t segment_samples, siz
 /* Recording::band_levels; count, cap and *n_out as bnh_recording_levels */
 int32_t bnh_recording_band_levels(const bnh_recording *r, size_t segment_samples, size_t step_samples, const bn_band_spec *spec, size_t first,
                                   size_t count, bn_window_bands *out, size_t cap, size_t *n_out, bnh_error *err);
+/* Recording::filtered: *out is a new recording, freed with bnh_recording_free; r may be freed first */
+int32_t bnh_recording_filtered(const bnh_recording *r, const float *taps, size_t n_taps, bnh_recording **out, bnh_error *err);
 /* row i: recordings[i] from frame starts[i]; sources / windows may be NULL (0 and the row's position) */
 int32_t bnh_predict_window_list(const bnh_classifier *c, bnh_context *ctx, const bnh_recording *const *recordings, const uint64_t *starts,
                                 const int32_t *sources, const uint64_t *windows, size_t n, int64_t timeout_ns, const volatile int32_t *cancel,

@@ -57,6 +57,7 @@ ENGINE_SYMBOLS = [
     "bn_group_uses_rccl", "bn_group_get_stats", "bn_shard_range", "bn_group_analyze_recording", "bn_group_last_error", "bn_recording_create_resampled", "bn_resample_table", "bn_recording_read_f32", "bn_last_error",
     "bn_recording_create_layout", "bn_recording_create_layout_async", "bn_recording_create_layout_resampled", "bn_recording_view_channel", "bn_live_create_layout",
     "bn_recording_levels", "bn_step_window_list", "bn_recording_window_list", "bn_recording_band_levels", "bn_band_bins",
+    "bn_recording_create_filtered", "bn_fir_bandpass",
     "bn_index_create", "bn_index_free", "bn_index_size", "bn_index_dim", "bn_index_add_host", "bn_index_add_ctx", "bn_index_read",
     "bn_index_search", "bn_index_search_ids", "bn_index_assign", "bn_index_cluster",
     "bn_index_save", "bn_index_load", "bn_index_file_info", "bn_index_file_verify",
@@ -95,7 +96,7 @@ HOST_SYMBOLS = [
     "bnh_context_attach_prior", "bnh_context_set_prior_site", "bnh_context_prior_results",
     "bnh_live_create", "bnh_live_create_rates", "bnh_live_create_layout", "bnh_predict_recording_layout", "bnh_live_free", "bnh_live_push", "bnh_live_close", "bnh_live_ready", "bnh_predict_live",
     "bnh_recording_create", "bnh_recording_free", "bnh_recording_samples", "bnh_recording_levels", "bnh_predict_window_list",
-    "bnh_recording_band_levels",
+    "bnh_recording_band_levels", "bnh_recording_filtered",
 ]
 
 
@@ -201,6 +202,20 @@ def band_bins(sample_rate: int, frame: int, lo_hz: float, hi_hz: float):
     return lo.value, hi.value
 
 
+BN_FIR_MAX_TAPS = 2047  # include/birdnet_hip.h: the longest filter of Recording.filtered
+BN_FIR_CHUNK = 4096  # csrc/fir_plan.h: the outputs one workgroup of the filter kernel owns (the tests place their edges around it)
+
+
+def fir_bandpass(sample_rate: int, lo_hz: float, hi_hz: float, n_taps: int) -> np.ndarray:
+    """bn_fir_bandpass: the f32 taps of a linear-phase windowed-sinc band-pass (lo_hz <= 0: low-pass; hi_hz >= sample_rate / 2:
+    high-pass) with unit gain at the centre of its pass band; host only."""
+    taps = np.zeros(max(int(n_taps), 0), dtype=np.float32)
+    st = lib.bn_fir_bandpass(sample_rate, lo_hz, hi_hz, n_taps, taps.ctypes.data_as(C.POINTER(C.c_float)))
+    if st:
+        raise EngineError(st)
+    return taps
+
+
 class BnIndexFilter(C.Structure):
     _fields_ = [("first_id", C.c_uint64), ("n_ids", C.c_uint64), ("tags", C.POINTER(C.c_uint32)), ("n_tags", C.c_size_t), ("flags", C.c_uint32)]
 
@@ -299,6 +314,8 @@ def _load() -> C.CDLL:
         "bn_step_window_list": (i32, [vp, C.POINTER(BnWindowRef), sz, sz, sz, i32, C.c_float, i32]),
         "bn_recording_band_levels": (i32, [vp, sz, sz, sz, sz, C.POINTER(BnBandSpec), sz, C.POINTER(BnWindowBands), sz]),
         "bn_band_bins": (i32, [C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+        "bn_recording_create_filtered": (i32, [vp, C.POINTER(C.c_float), sz, C.POINTER(vp)]),
+        "bn_fir_bandpass": (i32, [C.c_uint32, C.c_double, C.c_double, sz, C.POINTER(C.c_float)]),
         "bn_recording_window_list": (i32, [C.POINTER(BnWindowRef), sz, sz, sz, f32p]),
         "bn_last_error": (sz, [C.c_char_p, sz]),
         "bn_ctx_step_device_rows": (i32, [vp, C.POINTER(u32p)]),
@@ -473,6 +490,7 @@ def _load() -> C.CDLL:
         "bnh_recording_samples": (sz, [vp]),
         "bnh_recording_levels": (i32, [vp, sz, sz, sz, sz, C.POINTER(BnWindowLevel), sz, C.POINTER(sz), C.POINTER(BnhError)]),
         "bnh_recording_band_levels": (i32, [vp, sz, sz, C.POINTER(BnBandSpec), sz, sz, C.POINTER(BnWindowBands), sz, C.POINTER(sz), C.POINTER(BnhError)]),
+        "bnh_recording_filtered": (i32, [vp, C.POINTER(C.c_float), sz, C.POINTER(vp), C.POINTER(BnhError)]),
         "bnh_predict_window_list": (i32, [vp, vp, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(C.c_uint64), sz, C.c_int64,
                                           C.POINTER(C.c_int32), C.POINTER(vp), C.POINTER(BnhError)]),
         "bnh_predict_live": (i32, [vp, vp, vp, sz, C.c_int64, C.POINTER(C.c_int32), C.POINTER(vp), C.POINTER(C.c_int32),
@@ -875,6 +893,16 @@ class HostRecording:
                                          C.byref(n), C.byref(err)):
             raise Error(err)
         return out[:n.value].copy()
+
+    def filtered(self, taps) -> "HostRecording":
+        """Recording::filtered: a new mono f32 recording, this one through the centred FIR filter `taps`."""
+        t = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
+        h, err = C.c_void_p(), BnhError()
+        if lib.bnh_recording_filtered(self._h, t.ctypes.data_as(C.POINTER(C.c_float)), t.shape[0], C.byref(h), C.byref(err)):
+            raise Error(err)
+        r = HostRecording.__new__(HostRecording)
+        r._h, r.n_samples = h, int(lib.bnh_recording_samples(h))
+        return r
 
 
 class LiveSources:
@@ -1483,6 +1511,16 @@ class Recording:
             raise EngineError(st)
         return out
 
+    def filtered(self, taps) -> "Recording":
+        """bn_recording_create_filtered: a new mono f32 recording y[n] = sum_t taps[t] x[n + (len(taps) - 1) / 2 - t] of this one's
+        samples (zeros outside it), computed on the device; an odd number of taps up to BN_FIR_MAX_TAPS.  fir_bandpass() designs a
+        band-pass.  This recording is left as it is and may go first."""
+        t = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
+        h = C.c_void_p()
+        st = lib.bn_recording_create_filtered(self._h, t.ctypes.data_as(C.POINTER(C.c_float)), t.shape[0], C.byref(h))
+        if st:
+            raise EngineError(st)
+        return Recording._adopt(h)
 
 
 class Index:

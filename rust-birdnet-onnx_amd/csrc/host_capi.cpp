@@ -310,6 +310,13 @@ int32_t bnh_recording_band_levels(const bnh_recording *r, size_t segment_samples
     });
 }
 
+int32_t bnh_recording_filtered(const bnh_recording *r, const float *taps, size_t n_taps, bnh_recording **out, bnh_error *err) {
+    if (!out) return set_other(err, "null argument");
+    *out = nullptr;
+    if (!r) return set_other(err, "null recording");
+    return guarded(err, [&] { *out = new bnh_recording{r->rec.filtered(taps, n_taps)}; });
+}
+
 int32_t bnh_predict_window_list(const bnh_classifier *c, bnh_context *ctx, const bnh_recording *const *recordings, const uint64_t *starts,
                                 const int32_t *sources, const uint64_t *windows, size_t n, int64_t timeout_ns, const volatile int32_t *cancel,
                                 bnh_results **out, bnh_error *err) {

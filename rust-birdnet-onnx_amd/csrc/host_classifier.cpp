@@ -357,6 +357,14 @@ std::vector<bn_window_bands> Recording::band_levels(size_t segment_samples, size
     return out;
 }
 
+Recording Recording::filtered(const float *taps, size_t n_taps) const {
+    bn_recording *r = nullptr;
+    if (bn_recording_create_filtered(rec_.get(), taps, n_taps, &r) != BN_OK) throw inference("failed to filter the recording: " + last_backend_error());
+    Recording f(*this);  // the same number of samples
+    f.rec_ = std::shared_ptr<bn_recording>(r, [](bn_recording *p) { bn_recording_free(p); });
+    return f;
+}
+
 std::vector<ChunkResult> Classifier::predict_recording(BatchInferenceContext &ctx, const Recording &rec, float overlap_secs, size_t first_chunk, size_t count,
                                                        const InferenceOptions &options) const {
     const ModelConfig &cfg = inner_->config;

@@ -1,4 +1,4 @@
-// Recordings of the C ABI (include/birdnet_hip.h): bn_recording_*, the resampler's table, and the explicit window lists
+// Recordings of the C ABI (include/birdnet_hip.h): bn_recording_*, the resampler's table, FIR filtering, and the explicit window lists
 // (bn_recording_window_list, bn_step_window_list: of a context they need what bn_step_live does).  bn_recording is private to this
 // file; capi.cpp's bn_infer_windows and bn_step_windows reach a recording through check_windows and enqueue_windows (capi_internal.h).
 // Every launch is clear_launch_state, the launcher, check_launch; results reach the host through launch_and_read or rows_in_pieces.
@@ -18,6 +18,7 @@
 
 #include "band_levels.h"
 #include "capi_internal.h"
+#include "fir.h"
 #include "kernels.h"
 #include "levels.h"
 #include "window_list_plan.h"
@@ -54,6 +55,7 @@ struct bn_recording {
     bool resampled = false;   // the store holds the resampler's mono f32 output: no storage-format bytes are left
     std::shared_ptr<RecStore> store;
     size_t n_samples = 0;  // frames
+    bool filtered = false;  // ... and that output went through bn_recording_create_filtered (the wording of a refused channel view)
     PcmSrc src() const { return PcmSrc{store->d_pcm.get(), layout}; }
 };
 
@@ -187,16 +189,7 @@ bn_status bn::read_pcm_layout(const bn_pcm_layout *layout, size_t struct_size, P
 }
 
 // ---- polyphase resampler (no reference counterpart; design documented in include/birdnet_hip.h) ----
-static double bessel_i0(double x) {
-    double sum = 1.0, term = 1.0;
-    const double q = x * x / 4.0;
-    for (int k = 1; k < 500; k++) {
-        term *= q / ((double)k * (double)k);
-        sum += term;
-        if (term < 1e-18 * sum) break;
-    }
-    return sum;
-}
+// (bessel_i0: fir_plan.h, shared with the band-pass designer)
 // shared with the live pool's streaming resampler (live.cpp): one table design, one implementation
 ResampleTable bn::resample_factors(uint32_t src_rate, uint32_t dst_rate, uint32_t zc) {
     ResampleTable t;
@@ -400,11 +393,13 @@ bn_status bn_recording_view_channel(const bn_recording *r, int32_t channel, bn_r
     PcmLayout l = r->layout;
     l.channel = channel;
     if (const char *why = pcm_layout_problem(l)) {
+        if (r->filtered)
+            return fail(BN_ERR_INVALID_ARG, "a filtered recording has no storage-format bytes left: it is mono f32 and takes channel 0 or BN_PCM_MIX only");
         if (r->resampled)
             return fail(BN_ERR_INVALID_ARG, "a resampled recording has no storage-format bytes left: it is mono f32 and takes channel 0 or BN_PCM_MIX only");
         return fail(BN_ERR_INVALID_ARG, std::string(why) + " (channel " + std::to_string(channel) + " of " + std::to_string(l.channels) + ")");
     }
-    *out = new bn_recording{r->device, pcm_normalised(l), true, r->resampled, r->store, r->n_samples};
+    *out = new bn_recording{r->device, pcm_normalised(l), true, r->resampled, r->store, r->n_samples, r->filtered};
     return BN_OK;
 }
 
@@ -514,6 +509,36 @@ bn_status bn_recording_band_levels(const bn_recording *r, size_t segment_samples
 
 bn_status bn_band_bins(uint32_t sample_rate, uint32_t frame, double lo_hz, double hi_hz, uint32_t *bin_lo, uint32_t *bin_hi) {
     return band::bins(sample_rate, frame, lo_hz, hi_hz, bin_lo, bin_hi);
+}
+
+// ---- FIR filtering (include/birdnet_hip.h, "FIR filtering"; kernel in fir.hip, arithmetic in fir_plan.h) ----
+bn_status bn_recording_create_filtered(const bn_recording *src, const float *taps, size_t n_taps, bn_recording **out) {
+    if (!out) return fail(BN_ERR_INVALID_ARG, "null argument");
+    *out = nullptr;
+    if (!src) return fail(BN_ERR_INVALID_ARG, "null recording");
+    if (bn_status st = fir::check_taps(taps, n_taps); st != BN_OK) return st;
+    // every output reads samples on both sides of it: the whole upload must have arrived
+    const size_t n = src->n_samples;
+    if (!recording_wait_samples(src, n ? n - 1 : 0)) return fail(BN_ERR_BACKEND, "recording upload failed");
+    BN_HIP_TRY(bn::use_device(src->device));
+    // a store of its own, as the resampler's output: mono f32, nothing shared with src
+    std::unique_ptr<bn_recording> r(new bn_recording{src->device, PcmLayout{BN_PCM_F32, 1, 0}, true, true, std::make_shared<RecStore>(src->device, n), n, true});
+    const std::vector<uint16_t> image = fir::pack_taps(taps, (uint32_t)n_taps);
+    DeviceBuf<uint16_t> d_image;
+    hipError_t e = r->store->d_pcm.alloc(std::max<size_t>(n * sizeof(float), 16));
+    if (e == hipSuccess) e = d_image.alloc(image.size() * sizeof(uint16_t));
+    if (e == hipSuccess) e = gated::Memcpy(d_image, image.data(), image.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return fail(BN_ERR_BACKEND, std::string("filtering failed: ") + hipGetErrorString(e));
+    bn::clear_launch_state();
+    launch_fir(nullptr, static_cast<float *>(r->store->d_pcm.get()), src->src(), n, d_image.get(), (uint32_t)n_taps);
+    if (bn_status st = bn::check_launch("fir"); st != BN_OK) return st;
+    if ((e = gated::DeviceSynchronize()) != hipSuccess) return fail(BN_ERR_BACKEND, std::string("filtering failed: ") + hipGetErrorString(e));
+    *out = r.release();
+    return BN_OK;
+}
+
+bn_status bn_fir_bandpass(uint32_t sample_rate, double lo_hz, double hi_hz, size_t n_taps, float *taps_out) {
+    return fir::bandpass(sample_rate, lo_hz, hi_hz, n_taps, taps_out);
 }
 
 bn_status bn_recording_window_list(const bn_window_ref *refs, size_t count, size_t struct_size, size_t segment_samples, float *host_out) {
