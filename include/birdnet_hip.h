@@ -543,6 +543,65 @@ bn_status bn_recording_band_levels(const bn_recording *r, size_t segment_samples
 bn_status bn_band_bins(uint32_t sample_rate, uint32_t frame, double lo_hz, double hi_hz, uint32_t *bin_lo, uint32_t *bin_hi);
 
 /*
+ * bn_recording_spectral_profile: per window, the spectrum itself and a per-bin statistic over time -- the mean power per bin (one
+ * column of a long-term spectral average) and the acoustic complexity index (ACI, Pieretti et al. 2011).  Windows, frames, the
+ * periodic Hann window, the transform, the one-sided power P[t,k] of frame t and bin k, the unread tail, flags and n_frames are
+ * those of bn_recording_band_levels above.  With A[t,k] = sqrt(P[t,k]), F = n_frames and the bins k of [bin_lo, bin_hi),
+ * n_bins = bin_hi - bin_lo:
+ *
+ *   out_bins     count * BN_PROFILE_PLANES * n_bins floats, or NULL: window i, plane p, bin k at (i * 3 + p) * n_bins + (k - bin_lo)
+ *     plane 0    M_k = (sum_t P[t,k]) / F
+ *     plane 1    S_k = sum_t A[t,k]
+ *     plane 2    D_k = sum_{t < F-1} |A[t+1,k] - A[t,k]|; 0 when F = 1
+ *   aci          sum_k D_k / S_k; a bin with S_k == 0 adds 0
+ *   total_mean   the mean over frames of the frame's total over all N/2 + 1 bins: the quantity bn_window_bands.total_mean is
+ *   flags        as for band levels; BN_LEVEL_NONFINITE makes aci, total_mean and every float of the window's three planes +Inf
+ *
+ * With out_bins == NULL only the records are written; their bits are the same either way.
+ *
+ * Arithmetic.  The transform is band levels' (the same code).  Each of four waves takes a run of ceil(F / 4) consecutive frames
+ * and adds them in ascending order from 0.0f, the four runs combine as (w0 + w1) + (w2 + w3); the square root is the correctly
+ * rounded one (csrc/spectral_profile.hip).  Against the float64 value of the same f32 samples with the double-precision window,
+ * u = 2^-24, eps = BN_BAND_EPS_ULPS * u, q = ceil(F / 4), T_t the reference total of frame t, T = total_mean's reference,
+ * R = eps * sum_t sqrt(T_t), delta = (BN_PROFILE_POW_DEPTH + q) * u, delta_a = (BN_PROFILE_AMP_DEPTH + q) * u, barring underflow:
+ *   plane 0      |got - M_k| <= 2 eps sqrt(M_k T) + eps^2 T + delta M_k
+ *   plane 1      |got - S_k| <= R + delta_a S_k                                  =: b1_k
+ *   plane 2      |got - D_k| <= 2 (R + delta_a S_k) + delta_a D_k                =: b2_k
+ *   aci          |got - aci| <= sum_k (b2_k + (D_k / S_k) b1_k) / (S_k - b1_k) + BN_PROFILE_ACI_DEPTH * u * aci
+ *                (no promise where some S_k <= b1_k: a bin whose amplitude is inside the transform's own error)
+ *   total_mean   band levels' bound for its total_mean
+ * (derivation in DESIGN.md 7c, "Spectral profile").
+ *
+ * Invariance.  A window's record and planes depend only on its S samples, S and the spec: not on first_window, count,
+ * step_samples, the recording's length or its layout, on how a window range is split into calls, or on whether out_bins is given.
+ *
+ * The call blocks on an asynchronous upload as band levels does.  spec_size is sizeof(bn_profile_spec), struct_size
+ * sizeof(bn_window_profile) as the caller compiled them, handled as band levels handles them; out_bins is dense.
+ * BN_ERR_INVALID_ARG, with a message and nothing enqueued: whatever band levels refuses about r, segment_samples, step_samples, the
+ * window range, frame and hop; a NULL spec, a spec_size or struct_size below the struct's; bin_lo >= bin_hi or
+ * bin_hi > frame / 2 + 1; NULL `out` with count > 0.  count == 0 is BN_OK.  bn_band_bins converts hertz to bins.
+ */
+#define BN_PROFILE_PLANES 3
+#define BN_PROFILE_POW_DEPTH 9  /* 2 (squares and their sum) + 3 (scale, its f32 constant, the division) + 2 (four waves) + 2 spare */
+#define BN_PROFILE_AMP_DEPTH 7  /* 2 (half of: squares, sum, scale, its constant) + 1 (square root) + 2 (four waves) + 2 spare */
+#define BN_PROFILE_ACI_DEPTH 16 /* 1 (the quotient) + 5 (a lane's bins at frame 2048) + 6 (a wave) + 2 (four waves) + 2 spare */
+typedef struct bn_profile_spec {
+    uint32_t frame;  /* N: 256, 512, 1024 or 2048 */
+    uint32_t hop;    /* 1 .. N */
+    uint32_t bin_lo; /* the bins [bin_lo, bin_hi), bin_lo < bin_hi <= N/2 + 1 */
+    uint32_t bin_hi;
+} bn_profile_spec;
+typedef struct bn_window_profile {
+    float aci;
+    float total_mean;
+    uint32_t flags; /* BN_LEVEL_NONFINITE | BN_LEVEL_PADDED */
+    uint32_t n_frames;
+} bn_window_profile;
+bn_status bn_recording_spectral_profile(const bn_recording *r, size_t segment_samples, size_t step_samples, size_t first_window,
+                                        size_t count, const bn_profile_spec *spec, size_t spec_size, bn_window_profile *out,
+                                        size_t struct_size, float *out_bins);
+
+/*
  * FIR filtering: take the rumble out instead of gating around it.  bn_recording_create_filtered returns a NEW mono f32 recording
  * of bn_recording_samples(src) samples on src's device,
  *   y[n] = sum_t taps[t] * x[n + (n_taps - 1) / 2 - t],   t = 0 .. n_taps - 1,

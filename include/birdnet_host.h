@@ -220,6 +220,11 @@ class Recording {
      * Error::Inference with the library's message on a refusal. */
     std::vector<bn_window_bands> band_levels(size_t segment_samples, size_t step_samples, const bn_band_spec &spec, size_t first = 0,
                                              size_t count = (size_t)-1) const;
+    /* bn_recording_spectral_profile: per window the acoustic complexity index and the total, and, if `bins` is not NULL, the three
+     * planes of the bins [spec.bin_lo, spec.bin_hi) as [window][plane][bin] (birdnet_hip.h, "bn_recording_spectral_profile"); count
+     * as for levels().  Throws Error::Inference with the library's message on a refusal. */
+    std::vector<bn_window_profile> spectral_profile(size_t segment_samples, size_t step_samples, const bn_profile_spec &spec, size_t first = 0,
+                                                    size_t count = (size_t)-1, std::vector<float> *bins = nullptr) const;
     /* bn_recording_create_filtered: a new mono f32 recording, this one through the centred FIR filter `taps` (birdnet_hip.h, "FIR
      * filtering"; bn_fir_bandpass designs a band-pass).  Throws Error::Inference with the library's message on a refusal. */
     Recording filtered(const float *taps, size_t n_taps) const;
@@ -533,6 +538,10 @@ int32_t bnh_recording_levels(const bnh_recording *r, size_t segment_samples, siz
 /* Recording::band_levels; count, cap and *n_out as bnh_recording_levels */
 int32_t bnh_recording_band_levels(const bnh_recording *r, size_t segment_samples, size_t step_samples, const bn_band_spec *spec, size_t first,
                                   size_t count, bn_window_bands *out, size_t cap, size_t *n_out, bnh_error *err);
+/* Recording::spectral_profile; count, cap and *n_out as bnh_recording_levels.  bins may be NULL; else it takes the planes of the
+ * first min(cap, *n_out) windows, 3 * (bin_hi - bin_lo) floats each */
+int32_t bnh_recording_spectral_profile(const bnh_recording *r, size_t segment_samples, size_t step_samples, const bn_profile_spec *spec, size_t first,
+                                       size_t count, bn_window_profile *out, float *bins, size_t cap, size_t *n_out, bnh_error *err);
 /* Recording::filtered: *out is a new recording, freed with bnh_recording_free; r may be freed first */
 int32_t bnh_recording_filtered(const bnh_recording *r, const float *taps, size_t n_taps, bnh_recording **out, bnh_error *err);
 /* row i: recordings[i] from frame starts[i]; sources / windows may be NULL (0 and the row's position) */

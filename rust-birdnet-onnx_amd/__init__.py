@@ -56,7 +56,7 @@ ENGINE_SYMBOLS = [
     "bn_infer_windows", "bn_step_windows", "bn_ctx_step_device_rows", "bn_group_create", "bn_group_destroy", "bn_group_size",
     "bn_group_uses_rccl", "bn_group_get_stats", "bn_shard_range", "bn_group_analyze_recording", "bn_group_last_error", "bn_recording_create_resampled", "bn_resample_table", "bn_recording_read_f32", "bn_last_error",
     "bn_recording_create_layout", "bn_recording_create_layout_async", "bn_recording_create_layout_resampled", "bn_recording_view_channel", "bn_live_create_layout",
-    "bn_recording_levels", "bn_step_window_list", "bn_recording_window_list", "bn_recording_band_levels", "bn_band_bins",
+    "bn_recording_levels", "bn_step_window_list", "bn_recording_window_list", "bn_recording_band_levels", "bn_band_bins", "bn_recording_spectral_profile",
     "bn_recording_create_filtered", "bn_fir_bandpass",
     "bn_index_create", "bn_index_free", "bn_index_size", "bn_index_dim", "bn_index_add_host", "bn_index_add_ctx", "bn_index_read",
     "bn_index_search", "bn_index_search_ids", "bn_index_assign", "bn_index_cluster",
@@ -96,7 +96,7 @@ HOST_SYMBOLS = [
     "bnh_context_attach_prior", "bnh_context_set_prior_site", "bnh_context_prior_results",
     "bnh_live_create", "bnh_live_create_rates", "bnh_live_create_layout", "bnh_predict_recording_layout", "bnh_live_free", "bnh_live_push", "bnh_live_close", "bnh_live_ready", "bnh_predict_live",
     "bnh_recording_create", "bnh_recording_free", "bnh_recording_samples", "bnh_recording_levels", "bnh_predict_window_list",
-    "bnh_recording_band_levels", "bnh_recording_filtered",
+    "bnh_recording_band_levels", "bnh_recording_spectral_profile", "bnh_recording_filtered",
 ]
 
 
@@ -200,6 +200,27 @@ def band_bins(sample_rate: int, frame: int, lo_hz: float, hi_hz: float):
     if st:
         raise EngineError(st)
     return lo.value, hi.value
+
+
+BN_PROFILE_PLANES = 3  # include/birdnet_hip.h: mean power, summed amplitude, summed absolute change of the amplitude
+BN_PROFILE_POW_DEPTH, BN_PROFILE_AMP_DEPTH, BN_PROFILE_ACI_DEPTH = 9, 7, 16  # the constants of the header's bounds on a profile
+
+
+class BnProfileSpec(C.Structure):
+    _fields_ = [("frame", C.c_uint32), ("hop", C.c_uint32), ("bin_lo", C.c_uint32), ("bin_hi", C.c_uint32)]
+
+
+class BnWindowProfile(C.Structure):
+    _fields_ = [("aci", C.c_float), ("total_mean", C.c_float), ("flags", C.c_uint32), ("n_frames", C.c_uint32)]
+
+
+PROFILE_DTYPE = np.dtype([("aci", np.float32), ("total_mean", np.float32), ("flags", np.uint32), ("n_frames", np.uint32)])
+
+
+def _profile_planes(count: int, bins, planes: bool):
+    """the [count, 3, n_bins] array of a spectral profile (None without planes; one spare float for a bin range the library refuses)"""
+    n_bins = max(int(bins[1]) - int(bins[0]), 0)
+    return np.zeros(max(count, 0) * BN_PROFILE_PLANES * n_bins + 1, dtype=np.float32) if planes else None, n_bins
 
 
 BN_FIR_MAX_TAPS = 2047  # include/birdnet_hip.h: the longest filter of Recording.filtered
@@ -313,6 +334,7 @@ def _load() -> C.CDLL:
         "bn_recording_levels": (i32, [vp, sz, sz, sz, sz, C.POINTER(BnWindowLevel), sz]),
         "bn_step_window_list": (i32, [vp, C.POINTER(BnWindowRef), sz, sz, sz, i32, C.c_float, i32]),
         "bn_recording_band_levels": (i32, [vp, sz, sz, sz, sz, C.POINTER(BnBandSpec), sz, C.POINTER(BnWindowBands), sz]),
+        "bn_recording_spectral_profile": (i32, [vp, sz, sz, sz, sz, C.POINTER(BnProfileSpec), sz, C.POINTER(BnWindowProfile), sz, C.POINTER(C.c_float)]),
         "bn_band_bins": (i32, [C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
         "bn_recording_create_filtered": (i32, [vp, C.POINTER(C.c_float), sz, C.POINTER(vp)]),
         "bn_fir_bandpass": (i32, [C.c_uint32, C.c_double, C.c_double, sz, C.POINTER(C.c_float)]),
@@ -489,6 +511,8 @@ def _load() -> C.CDLL:
         "bnh_recording_free": (None, [vp]),
         "bnh_recording_samples": (sz, [vp]),
         "bnh_recording_levels": (i32, [vp, sz, sz, sz, sz, C.POINTER(BnWindowLevel), sz, C.POINTER(sz), C.POINTER(BnhError)]),
+        "bnh_recording_spectral_profile": (i32, [vp, sz, sz, C.POINTER(BnProfileSpec), sz, sz, C.POINTER(BnWindowProfile), C.POINTER(C.c_float), sz, C.POINTER(sz),
+                                                 C.POINTER(BnhError)]),
         "bnh_recording_band_levels": (i32, [vp, sz, sz, C.POINTER(BnBandSpec), sz, sz, C.POINTER(BnWindowBands), sz, C.POINTER(sz), C.POINTER(BnhError)]),
         "bnh_recording_filtered": (i32, [vp, C.POINTER(C.c_float), sz, C.POINTER(vp), C.POINTER(BnhError)]),
         "bnh_predict_window_list": (i32, [vp, vp, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(C.c_uint64), sz, C.c_int64,
@@ -893,6 +917,21 @@ class HostRecording:
                                          C.byref(n), C.byref(err)):
             raise Error(err)
         return out[:n.value].copy()
+
+    def spectral_profile(self, segment_samples: int, step_samples: int, frame: int, hop: int, bins, first: int = 0, count: Optional[int] = None,
+                         planes: bool = True):
+        """Recording::spectral_profile: (a PROFILE_DTYPE array, the planes [n, 3, n_bins] float32 or None) of windows [first, first +
+        count) (count None: to the last window); bins = (bin_lo, bin_hi)."""
+        want = (1 << 64) - 1 if count is None else count
+        cap = max(int(lib.bn_chunk_count(self.n_samples, step_samples)) if step_samples else 0, 0 if count is None else count, 1)
+        out = np.zeros(cap, dtype=PROFILE_DTYPE)
+        pl, n_bins = _profile_planes(cap, bins, planes)
+        n, err = C.c_size_t(), BnhError()
+        sp = BnProfileSpec(frame, hop, bins[0], bins[1])
+        if lib.bnh_recording_spectral_profile(self._h, segment_samples, step_samples, C.byref(sp), first, want, out.ctypes.data_as(C.POINTER(BnWindowProfile)),
+                                              pl.ctypes.data_as(C.POINTER(C.c_float)) if planes else None, cap, C.byref(n), C.byref(err)):
+            raise Error(err)
+        return out[:n.value].copy(), (pl[:n.value * BN_PROFILE_PLANES * n_bins].reshape(n.value, BN_PROFILE_PLANES, n_bins).copy() if planes else None)
 
     def filtered(self, taps) -> "HostRecording":
         """Recording::filtered: a new mono f32 recording, this one through the centred FIR filter `taps`."""
@@ -1510,6 +1549,23 @@ class Recording:
         if st:
             raise EngineError(st)
         return out
+
+    def spectral_profile(self, segment_samples: int, step_samples: int, frame: int, hop: int, bins, first: int = 0, count: Optional[int] = None,
+                         planes: bool = True):
+        """bn_recording_spectral_profile: per window the acoustic complexity index and the total over the bins = (bin_lo, bin_hi) of
+        frames of `frame` samples every `hop`, as a PROFILE_DTYPE array (count None: to the last window), and, with planes, a float32
+        array [n, 3, n_bins]: per bin the mean power (one column of a long-term spectral average), the summed amplitude and the summed
+        absolute change of the amplitude from frame to frame; None without.  band_bins() gives the bins of a band in hertz."""
+        count = self.n_windows(step_samples) - first if count is None else count
+        out = np.zeros(max(count, 0), dtype=PROFILE_DTYPE)
+        pl, n_bins = _profile_planes(count, bins, planes)
+        sp = BnProfileSpec(frame, hop, bins[0], bins[1])
+        st = lib.bn_recording_spectral_profile(self._h, segment_samples, step_samples, first, count, C.byref(sp), C.sizeof(BnProfileSpec),
+                                               out.ctypes.data_as(C.POINTER(BnWindowProfile)), C.sizeof(BnWindowProfile),
+                                               pl.ctypes.data_as(C.POINTER(C.c_float)) if planes else None)
+        if st:
+            raise EngineError(st)
+        return out, (pl[:-1].reshape(len(out), BN_PROFILE_PLANES, n_bins) if planes else None)
 
     def filtered(self, taps) -> "Recording":
         """bn_recording_create_filtered: a new mono f32 recording y[n] = sum_t taps[t] x[n + (len(taps) - 1) / 2 - t] of this one's

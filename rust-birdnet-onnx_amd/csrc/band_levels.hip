@@ -3,7 +3,7 @@
 // the reader (pcm_read.h) like levels_kernel, so a sample is exactly the f32 value bn_recording_windows returns, 0 past the end.
 // Wave w takes frames w, w + 4, ... of the window; nothing is shared between windows, so a window's bits cannot depend on the step.
 //
-// ONE FRAME IN ONE WAVE, in registers and cross-lane moves (no LDS traffic, so no bank conflict to avoid).  The N real samples are
+// ONE FRAME IN ONE WAVE (band_fft.h, shared with spectral_profile.hip), in registers and cross-lane moves (no LDS traffic, so no bank conflict to avoid).  The N real samples are
 // windowed on load and packed as M = N/2 complex points z[m] = (w x)[2m] + i (w x)[2m+1]; lane l holds points m = 64 r + l in
 // registers r = 0 .. R-1, R = M/64 = 2, 4, 8 or 16 (its two samples are neighbours, a wave's loads one contiguous span).
 //   * log2 R radix-2 decimation-in-frequency stages pair points 64 h apart: both sit in one lane (registers r and r + h).
@@ -30,6 +30,7 @@
 #include <utility>
 #include <vector>
 
+#include "band_fft.h"
 #include "device_mem.h"
 #include "kernels.h"
 #include "pcm_read.h"
@@ -40,12 +41,8 @@ namespace {
 constexpr uint32_t BAND_WAVES = band::WAVES, BAND_SLOTS = BN_BAND_MAX + 1;  // the bands, then the total
 constexpr uint32_t BAND_DWORDS = sizeof(WindowBands) / 4;
 
-constexpr uint32_t ilog2(uint32_t v) { return v <= 1 ? 0 : 1 + ilog2(v >> 1); }
-constexpr uint32_t bitrev(uint32_t v, uint32_t bits) {
-    uint32_t r = 0;
-    for (uint32_t i = 0; i < bits; i++) r |= ((v >> i) & 1u) << (bits - 1 - i);
-    return r;
-}
+using band::bitrev;
+using band::ilog2;
 // eps: 7 u per radix-2 stage (twiddle rounding, the complex product, the additions) over the log2(N/2) stages of the
 // longest frame, 2 u for the rounded window and its product, 7 u for the unpack, 1 u for what is of second order
 static_assert(7 * ilog2(band::FRAME_MAX / 2) + 2 + 7 + 1 == BN_BAND_EPS_ULPS, "BN_BAND_EPS_ULPS is this transform's bound");
@@ -71,7 +68,6 @@ template <uint32_t N, class R>
 __global__ __launch_bounds__(256) void band_levels_kernel(WindowBands *__restrict__ out, const R src, uint64_t n_samples, uint64_t first_start, uint64_t step,
                                                          uint32_t S, const float *__restrict__ tab, const BandArgs a) {
     constexpr uint32_t M = N / 2, RR = M / 64, LR = ilog2(RR);
-    static_assert(RR >= 2 && RR <= 16 && (1u << LR) == RR, "frames of 256 .. 2048 samples");
     __shared__ float w_sum[BAND_WAVES][BAND_SLOTS], w_max[BAND_WAVES][BAND_SLOTS];
     __shared__ uint32_t w_bad[BAND_WAVES];
     static_assert(sizeof(w_sum) + sizeof(w_max) + sizeof(w_bad) == band::lds_bytes(N), "the LDS band_plan.h states");
@@ -79,27 +75,10 @@ __global__ __launch_bounds__(256) void band_levels_kernel(WindowBands *__restric
     const uint64_t start = first_start + (uint64_t)blockIdx.x * step;
     // frames of the window that the recording holds
     const uint64_t valid = start < n_samples ? (n_samples - start < S ? n_samples - start : (uint64_t)S) : 0;
-    const float2 *__restrict__ tw = reinterpret_cast<const float2 *>(tab + N);  // W_N^k, k < N/2
-    const uint32_t L = __brev(lane) >> 26;                                       // the 6-bit reversal of the lane
-    const uint32_t zero_from = __brev((64u - L) & 63u) >> 26;                    // the lane that holds Z[M - L R]
-
-    // ---- what a lane needs for every frame
-    float2 hw[RR];       // the window at its two samples of register r
-    float2 tw_reg[RR];   // stage s < LR, register r0 < RR >> (s + 1): at RR - (RR >> s) + r0 (RR - 1 in all)
-    float2 tw_lane[5];   // the stages h = 32 .. 2 (h = 1 multiplies by 1)
-    float2 tw_bin[RR];   // W_N^k of its bins
-#pragma unroll
-    for (uint32_t r = 0; r < RR; r++) {
-        hw[r] = *reinterpret_cast<const float2 *>(tab + 2u * (r * 64u + lane));
-        tw_bin[r] = tw[L * RR + bitrev(r, LR)];
-    }
-#pragma unroll
-    for (uint32_t s = 0; s < LR; s++) {
-#pragma unroll
-        for (uint32_t r0 = 0; r0 < (RR >> (s + 1)); r0++) tw_reg[RR - (RR >> s) + r0] = tw[(r0 * 64u + lane) << (s + 1)];
-    }
-#pragma unroll
-    for (uint32_t s = 0; s < 5; s++) tw_lane[s] = tw[(lane & ((32u >> s) - 1u)) * ((N / 64u) << s)];
+    // ---- what a lane needs for every frame (band_fft.h)
+    band::BandFft<N> fft;
+    fft.load_tables(tab, lane);
+    const uint32_t L = fft.L;
 
     float acc_sum[BAND_SLOTS], acc_max[BAND_SLOTS];
 #pragma unroll
@@ -109,84 +88,8 @@ __global__ __launch_bounds__(256) void band_levels_kernel(WindowBands *__restric
 
     for (uint32_t j = wave; j < a.n_frames; j += BAND_WAVES) {
         const uint32_t base = j * a.hop;  // base + N <= S
-        float zr[RR], zi[RR];
-#pragma unroll
-        for (uint32_t r = 0; r < RR; r++) {
-            const uint32_t p = base + 2u * (r * 64u + lane);
-            float x0 = 0.0f, x1 = 0.0f;
-            if (p < valid) x0 = src(start + p);
-            if ((uint64_t)p + 1u < valid) x1 = src(start + p + 1u);
-            bad |= !(fabsf(x0) < __builtin_inff());  // NaN or +-Inf
-            bad |= !(fabsf(x1) < __builtin_inff());
-            zr[r] = x0 * hw[r].x;
-            zi[r] = x1 * hw[r].y;
-        }
-        // ---- stages inside a lane: points 64 h apart, h = RR/2 .. 1
-#pragma unroll
-        for (uint32_t s = 0; s < LR; s++) {
-            const uint32_t h = RR >> (s + 1);
-#pragma unroll
-            for (uint32_t blk = 0; blk < RR; blk += 2 * h) {
-#pragma unroll
-                for (uint32_t r0 = 0; r0 < h; r0++) {
-                    const uint32_t i = blk + r0;
-                    const float2 w = tw_reg[RR - (RR >> s) + r0];
-                    const float ar = zr[i], ai = zi[i], br = zr[i + h], bi = zi[i + h];
-                    zr[i] = ar + br;
-                    zi[i] = ai + bi;
-                    const float dr = ar - br, di = ai - bi;
-                    zr[i + h] = dr * w.x - di * w.y;
-                    zi[i + h] = dr * w.y + di * w.x;
-                }
-            }
-        }
-        // ---- stages across lanes: points h = 32 .. 1 apart
-#pragma unroll
-        for (uint32_t s = 0; s < 6; s++) {
-            const uint32_t h = 32u >> s;
-            const bool upper = (lane & h) != 0;
-#pragma unroll
-            for (uint32_t r = 0; r < RR; r++) {
-                const float pr = __shfl_xor(zr[r], (int)h), pi = __shfl_xor(zi[r], (int)h);
-                const float ar = upper ? pr : zr[r], ai = upper ? pi : zi[r];
-                const float br = upper ? zr[r] : pr, bi = upper ? zi[r] : pi;
-                const float sr = ar + br, si = ai + bi, dr = ar - br, di = ai - bi;
-                if (s < 5) {
-                    const float2 w = tw_lane[s < 5 ? s : 0];
-                    const float mr = dr * w.x - di * w.y, mi = dr * w.y + di * w.x;
-                    zr[r] = upper ? mr : sr;
-                    zi[r] = upper ? mi : si;
-                } else {
-                    zr[r] = upper ? dr : sr;
-                    zi[r] = upper ? di : si;
-                }
-            }
-        }
-        // ---- the real-input unpack and the power of this lane's bins k = L RR + rev(r)
-        float e[RR];
-#pragma unroll
-        for (uint32_t r = 0; r < RR; r++) {
-            const uint32_t q = bitrev(r, LR);
-            float pr, pi;
-            if (q == 0) {
-                pr = __shfl(zr[0], (int)zero_from);
-                pi = __shfl(zi[0], (int)zero_from);
-            } else {
-                pr = __shfl_xor(zr[bitrev(RR - q, LR)], 63);
-                pi = __shfl_xor(zi[bitrev(RR - q, LR)], 63);
-            }
-            const float ar = zr[r] + pr, ai = zi[r] - pi, br = zr[r] - pr, bi = zi[r] + pi;
-            const float2 w = tw_bin[r];
-            const float cr = w.x * br - w.y * bi, ci = w.x * bi + w.y * br;
-            const float xr = ar + ci, xi = ai - cr;
-            e[r] = (xr * xr + xi * xi) * ((q == 0 && L == 0) ? s_edge : s_in);
-        }
-        // bin N/2, from Z[0]: lane 0, register 0
-        float e_top = 0.0f;
-        {
-            const float d = zr[0] - zi[0], d2 = d + d;
-            if (lane == 0) e_top = (d2 * d2 + 0.0f) * s_edge;
-        }
+        float e[RR], e_top;
+        fft.frame(src, start, base, valid, lane, s_in, s_edge, bad, e, e_top);
         // ---- the bands and the total of this frame
 #pragma unroll
         for (uint32_t b = 0; b < BAND_SLOTS; b++) {

@@ -310,6 +310,21 @@ int32_t bnh_recording_band_levels(const bnh_recording *r, size_t segment_samples
     });
 }
 
+int32_t bnh_recording_spectral_profile(const bnh_recording *r, size_t segment_samples, size_t step_samples, const bn_profile_spec *spec, size_t first,
+                                       size_t count, bn_window_profile *out, float *bins, size_t cap, size_t *n_out, bnh_error *err) {
+    if (n_out) *n_out = 0;
+    if (!r) return set_other(err, "null recording");
+    if (!spec) return set_other(err, "null profile spec");
+    return guarded(err, [&] {
+        std::vector<float> planes;
+        const std::vector<bn_window_profile> pr = r->rec.spectral_profile(segment_samples, step_samples, *spec, first, count, bins ? &planes : nullptr);
+        if (n_out) *n_out = pr.size();
+        const size_t n = std::min(cap, pr.size());
+        if (out) memcpy(out, pr.data(), n * sizeof(bn_window_profile));
+        if (bins && !pr.empty()) memcpy(bins, planes.data(), n * (planes.size() / pr.size()) * sizeof(float));
+    });
+}
+
 int32_t bnh_recording_filtered(const bnh_recording *r, const float *taps, size_t n_taps, bnh_recording **out, bnh_error *err) {
     if (!out) return set_other(err, "null argument");
     *out = nullptr;

@@ -357,6 +357,30 @@ std::vector<bn_window_bands> Recording::band_levels(size_t segment_samples, size
     return out;
 }
 
+std::vector<bn_window_profile> Recording::spectral_profile(size_t segment_samples, size_t step_samples, const bn_profile_spec &spec, size_t first, size_t count,
+                                                           std::vector<float> *bins) const {
+    if (count == (size_t)-1) {
+        const size_t total = bn_chunk_count(n_samples_, step_samples);
+        count = total > first ? total - first : 0;
+    }
+    // as levels(): a count the library refuses must reach it with a buffer.  The planes are sized only for a spec it will take
+    std::vector<bn_window_profile> out;
+    const size_t n_bins = spec.bin_hi > spec.bin_lo && spec.bin_hi <= 1025 ? spec.bin_hi - spec.bin_lo : 0;
+    try {
+        if (count > (size_t)-1 / sizeof(float) / (BN_PROFILE_PLANES * 1025 + 1)) throw std::length_error("count");
+        out.resize(count);
+        if (bins) bins->assign(count * BN_PROFILE_PLANES * n_bins + 1, 0.0f);
+    } catch (const std::exception &) {
+        throw inference("window range exceeds the address space");
+    }
+    bn_window_profile none{};
+    if (bn_recording_spectral_profile(rec_.get(), segment_samples, step_samples, first, count, &spec, sizeof(bn_profile_spec), count ? out.data() : &none,
+                                      sizeof(bn_window_profile), bins ? bins->data() : nullptr) != BN_OK)
+        throw inference(last_backend_error());
+    if (bins) bins->resize(count * BN_PROFILE_PLANES * n_bins);
+    return out;
+}
+
 Recording Recording::filtered(const float *taps, size_t n_taps) const {
     bn_recording *r = nullptr;
     if (bn_recording_create_filtered(rec_.get(), taps, n_taps, &r) != BN_OK) throw inference("failed to filter the recording: " + last_backend_error());

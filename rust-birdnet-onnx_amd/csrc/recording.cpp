@@ -21,6 +21,7 @@
 #include "fir.h"
 #include "kernels.h"
 #include "levels.h"
+#include "spectral_profile.h"
 #include "window_list_plan.h"
 
 using namespace bn;
@@ -86,9 +87,10 @@ bn_status launch_and_read(const char *what, const char *failed, void *host, cons
 }
 
 // `count` rows of Row into the caller's `out` (rows struct_size >= sizeof(Row) apart; the bytes behind a Row are left alone), at
-// most `piece` per launch: launch(done, n, d) writes rows [done, done + n) to the device block d
-template <class Row, class Launch>
-bn_status rows_in_pieces(const char *what, const char *failed, size_t count, size_t piece, void *out, size_t struct_size, Launch &&launch) {
+// most `piece` per launch: launch(done, n, d) writes rows [done, done + n) to the device block d.  also(done, n), if given, copies
+// whatever else that launch wrote (its hipError_t is worded with `failed`)
+template <class Row, class Launch, class Also>
+bn_status rows_in_pieces(const char *what, const char *failed, size_t count, size_t piece, void *out, size_t struct_size, Launch &&launch, Also &&also) {
     DeviceBuf<Row> d;
     BN_HIP_TRY(d.alloc(std::min(piece, count) * sizeof(Row)));
     std::vector<Row> rows;  // only for a caller whose struct is longer than this header's
@@ -99,8 +101,13 @@ bn_status rows_in_pieces(const char *what, const char *failed, size_t count, siz
         void *host = rows.empty() ? static_cast<void *>(at) : static_cast<void *>(rows.data());
         if (bn_status st = launch_and_read(what, failed, host, d, n * sizeof(Row), [&] { launch(done, n, d.get()); }); st != BN_OK) return st;
         for (size_t i = 0; i < rows.size() && i < n; i++) memcpy(at + i * struct_size, &rows[i], sizeof(Row));
+        if (const hipError_t e = also(done, n); e != hipSuccess) return fail(BN_ERR_BACKEND, std::string(failed) + hipGetErrorString(e));
     }
     return BN_OK;
+}
+template <class Row, class Launch>
+bn_status rows_in_pieces(const char *what, const char *failed, size_t count, size_t piece, void *out, size_t struct_size, Launch &&launch) {
+    return rows_in_pieces<Row>(what, failed, count, piece, out, struct_size, launch, [](size_t, size_t) { return hipSuccess; });
 }
 
 // The format argument of a create entry point, read: the layout it names, whether the recording converts any format
@@ -509,6 +516,39 @@ bn_status bn_recording_band_levels(const bn_recording *r, size_t segment_samples
 
 bn_status bn_band_bins(uint32_t sample_rate, uint32_t frame, double lo_hz, double hi_hz, uint32_t *bin_lo, uint32_t *bin_hi) {
     return band::bins(sample_rate, frame, lo_hz, hi_hz, bin_lo, bin_hi);
+}
+
+// ---- spectral profile (include/birdnet_hip.h, "bn_recording_spectral_profile"; kernel in spectral_profile.hip, arithmetic in profile_plan.h) ----
+bn_status bn_recording_spectral_profile(const bn_recording *r, size_t segment_samples, size_t step_samples, size_t first_window, size_t count,
+                                        const bn_profile_spec *spec, size_t spec_size, bn_window_profile *out, size_t struct_size, float *out_bins) {
+    if (struct_size < sizeof(bn_window_profile)) return fail(BN_ERR_INVALID_ARG, "struct_size is below sizeof(bn_window_profile)");
+    bn_status st = check_window_range(r, segment_samples, step_samples, first_window, count);
+    if (st != BN_OK) return st;
+    profile::Plan plan;
+    if ((st = profile::check_spec(spec, spec_size, segment_samples, &plan)) != BN_OK) return st;
+    if (count == 0) return BN_OK;
+    if (!out) return fail(BN_ERR_INVALID_ARG, "null output buffer");
+    size_t all_floats = 0;  // only asked whether it exists
+    if (out_bins && !profile::bins_floats(count, plan.n_bins, &all_floats)) return fail(BN_ERR_INVALID_ARG, "count * 3 * n_bins floats do not fit a size_t");
+    // an asynchronously uploaded recording: the last sample any frame of these windows reads must have arrived
+    uint64_t last = 0;
+    if (profile::last_sample_read(r->n_samples, first_window + count - 1, step_samples, plan.span, &last) && !recording_wait_samples(r, (size_t)last))
+        return fail(BN_ERR_BACKEND, "recording upload failed");
+    BN_HIP_TRY(bn::use_device(r->device));
+    const float *tab = nullptr;
+    float scale = 0.0f;
+    BN_HIP_TRY(band_tables(r->device, plan.N, &tab, &scale));
+    // one workgroup per window; a launch's planes, if wanted, are copied behind its records
+    const size_t piece = profile::piece_windows(plan.n_bins), per = (size_t)BN_PROFILE_PLANES * plan.n_bins;
+    DeviceBuf<float> d_planes;
+    if (out_bins) BN_HIP_TRY(d_planes.alloc(std::min(piece, count) * per * sizeof(float)));
+    return rows_in_pieces<WindowProfile>("spectral profile", "spectral profile kernel failed: ", count, piece, out, struct_size, [&](size_t done, size_t n, WindowProfile *d) {
+        launch_spectral_profile(nullptr, d, out_bins ? d_planes.get() : nullptr, r->src(), r->n_samples, (uint64_t)(first_window + done) * step_samples, step_samples,
+                                (uint32_t)segment_samples, (uint32_t)n, plan, tab, scale);
+    }, [&](size_t done, size_t n) {
+        if (!out_bins) return hipSuccess;
+        return gated::Memcpy(out_bins + done * per, d_planes.get(), n * per * sizeof(float), hipMemcpyDeviceToHost);
+    });
 }
 
 // ---- FIR filtering (include/birdnet_hip.h, "FIR filtering"; kernel in fir.hip, arithmetic in fir_plan.h) ----

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Window levels and list steps, measured: three legs over a synthetic BirdNET-v2.4-style model.
+"""Window levels and list steps, measured: four legs over a synthetic BirdNET-v2.4-style model.
 
   gating       a synthetic recording of --hours with a --loud share of loud windows: bn_step_windows over every window, against
                bn_recording_levels + a host gate (peak >= 0.01, one window of hangover) + bn_step_window_list over the kept windows
@@ -7,6 +7,9 @@
   band gate    the same hour with a 60 Hz rumble at -20 dBFS under everything and the calls at -50 dBFS: the windows the peak gate keeps
                (all of them), the windows a 2 - 10 kHz gate on bn_recording_band_levels' max keeps, the band pass alone in GB/s of
                stored bytes next to the level pass, and the band-gated run.
+  profile      one hour of 48 kHz int16 noise, S = 144000, frames of 1024 every 512: bn_recording_spectral_profile over all 513 bins with
+               and without the planes next to bn_recording_band_levels with 3 bands on the same recording; --reps calls back to back per
+               timed run, the three alternating.  --leg profile runs this leg alone (it needs no model).
   short files  --files recordings of 4 windows each: one bn_step_windows per recording, against list steps of --batch rows.
 
 Every figure is the median of --runs timed runs after one warm-up; the JSON line at the end carries all of them.  No rate is a
@@ -39,6 +42,29 @@ def timed(fn, runs):
     return statistics.median(out), min(out), max(out)
 
 
+def profile_leg(bn, runs, reps):
+    """launch to results on the host, per call: (median, min, max) over `runs` rounds of `reps` calls each, the three variants alternating"""
+    S, rate, N, hop = 144000, 48000, 1024, 512
+    n_win = 3600 * rate // S
+    v = (6000 * np.random.RandomState(5).standard_normal(n_win * S)).astype(np.int16)
+    rec, bins = bn.Recording(v), (0, N // 2 + 1)
+    bands = [bn.band_bins(rate, N, 2000.0, 10000.0), (0, 43), (214, 513)]
+    calls = {"band_levels_s": lambda: rec.band_levels(S, S, N, hop, bands), "profile_s": lambda: rec.spectral_profile(S, S, N, hop, bins, planes=False),
+             "profile_planes_s": lambda: rec.spectral_profile(S, S, N, hop, bins)}
+    times = {k: [] for k in calls}
+    for r in range(runs + 1):  # round 0 warms up
+        for k, fn in calls.items():
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                fn()
+            if r:
+                times[k].append((time.perf_counter() - t0) / reps)
+    out = {k: (statistics.median(t), min(t), max(t)) for k, t in times.items()}
+    out.update({"windows": n_win, "frame": N, "hop": hop, "bins": list(bins), "reps": reps, "profile_over_band_levels": out["profile_s"][0] / out["band_levels_s"][0],
+                "profile_planes_over_band_levels": out["profile_planes_s"][0] / out["band_levels_s"][0], "profile_GBps": v.nbytes / out["profile_s"][0] / 1e9})
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--hours", type=float, default=1.0)
@@ -48,8 +74,13 @@ def main():
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--width", type=float, default=1.0)
     ap.add_argument("--depth", type=float, default=1.0)
+    ap.add_argument("--reps", type=int, default=50, help="calls per timed run of the profile leg")
+    ap.add_argument("--leg", choices=("all", "profile"), default="all")
     a = ap.parse_args()
     bn = importlib.import_module("rust-birdnet-onnx_amd")
+    if a.leg == "profile":
+        print(json.dumps({"runs": a.runs, "profile": profile_leg(bn, a.runs, a.reps)}))
+        return
     synth = importlib.import_module("rust-birdnet-onnx_amd.synth")
     with tempfile.NamedTemporaryFile(suffix=".onnx", delete=False) as f:
         f.write(synth.birdnet_v24(num_species=6522, width=a.width, depth=a.depth))
@@ -142,6 +173,8 @@ def main():
         ctx.synchronize()
 
     res["short_files"] = {"files": a.files, "windows": len(refs), "per_file_s": timed(per_file, a.runs), "list_s": timed(listed, a.runs)}
+    del clips, refs
+    res["profile"] = profile_leg(bn, a.runs, a.reps)
     res["capture_fallbacks"] = ctx.stats()["capture_fallbacks"]
     print(json.dumps(res))
 
