@@ -10,7 +10,7 @@ CXXFLAGS := -O3 -std=c++17 -fPIC -Wall -Wextra -Wno-unused-parameter -Iinclude
 # for the pairs with register moves (mbmap's depthwise phase: 120 v_pk_fma + 216 v_mov for 240 multiply-adds); on this part a packed
 # f32 instruction costs 1.56x a plain one (tools/mfma_valu_probe.cpp) and every vector instruction is paid out of the MFMA time
 HIPFLAGS := $(CXXFLAGS) --offload-arch=$(ARCH) -ffp-contract=off -fno-slp-vectorize
-OBJS := $(SRC)/onnx_proto.o $(SRC)/engine.o $(SRC)/onnx_rewrite.o $(SRC)/dft_bank.o $(SRC)/mbconv_fuse.o $(SRC)/plan_passes.o $(SRC)/detect.o $(SRC)/capi.o $(SRC)/recording.o $(SRC)/step_common.o $(SRC)/group.o $(SRC)/host_classifier.o $(SRC)/host_capi.o $(SRC)/host_rangefilter.o $(SRC)/kernels.o $(SRC)/topk.o $(SRC)/stft.o $(SRC)/mbrow.o $(SRC)/gemm_dma.o $(SRC)/gemm_dma3.o $(SRC)/gemm_b3.o $(SRC)/mbmap.o $(SRC)/mbmap_ws.o $(SRC)/index.o $(SRC)/head.o $(SRC)/rank.o $(SRC)/cluster.o $(SRC)/ivf.o $(SRC)/sq8.o $(SRC)/subset.o $(SRC)/index_copy.o $(SRC)/peaks.o $(SRC)/seq.o $(SRC)/above.o $(SRC)/group_above.o $(SRC)/match.o $(SRC)/index_io.o $(SRC)/index_file.o $(SRC)/prior.o $(SRC)/track.o $(SRC)/live.o $(SRC)/live_kernels.o $(SRC)/levels.o $(SRC)/band_levels.o $(SRC)/spectral_profile.o $(SRC)/fir.o
+OBJS := $(SRC)/onnx_proto.o $(SRC)/engine.o $(SRC)/onnx_rewrite.o $(SRC)/dft_bank.o $(SRC)/mbconv_fuse.o $(SRC)/plan_passes.o $(SRC)/detect.o $(SRC)/capi.o $(SRC)/recording.o $(SRC)/step_common.o $(SRC)/group.o $(SRC)/host_classifier.o $(SRC)/host_capi.o $(SRC)/host_rangefilter.o $(SRC)/kernels.o $(SRC)/topk.o $(SRC)/stft.o $(SRC)/mbrow.o $(SRC)/gemm_dma.o $(SRC)/gemm_dma3.o $(SRC)/gemm_b3.o $(SRC)/mbmap.o $(SRC)/mbmap_ws.o $(SRC)/index.o $(SRC)/head.o $(SRC)/rank.o $(SRC)/cluster.o $(SRC)/ivf.o $(SRC)/sq8.o $(SRC)/subset.o $(SRC)/index_copy.o $(SRC)/peaks.o $(SRC)/seq.o $(SRC)/above.o $(SRC)/group_above.o $(SRC)/match.o $(SRC)/index_io.o $(SRC)/index_file.o $(SRC)/prior.o $(SRC)/track.o $(SRC)/live.o $(SRC)/live_kernels.o $(SRC)/levels.o $(SRC)/band_levels.o $(SRC)/spectral_profile.o $(SRC)/fir.o $(SRC)/denoise.o
 
 all: $(OUT) oracle
 
@@ -30,6 +30,9 @@ $(SRC)/fir.o: $(SRC)/fir.hip $(wildcard $(SRC)/*.h)
 	$(HIPCC) $(HIPFLAGS) -Xclang -target-feature -Xclang -packed-fp32-ops -c $< -o $@
 # spectral_profile.hip: the same switch (scalar f32 chains whose order is the contract; nothing to pack)
 $(SRC)/spectral_profile.o: $(SRC)/spectral_profile.hip $(wildcard $(SRC)/*.h)
+	$(HIPCC) $(HIPFLAGS) -Xclang -target-feature -Xclang -packed-fp32-ops -c $< -o $@
+# denoise.hip: the same switch (plain f32 butterflies whose bits are the contract)
+$(SRC)/denoise.o: $(SRC)/denoise.hip $(wildcard $(SRC)/*.h)
 	$(HIPCC) $(HIPFLAGS) -Xclang -target-feature -Xclang -packed-fp32-ops -c $< -o $@
 $(OUT): $(OBJS)
 	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $@ $(OBJS) -lpthread -ldl
@@ -72,6 +75,10 @@ tools/asan_band_plan: tools/asan_band_plan.cpp $(SRC)/band_plan.h $(SRC)/last_er
 	$(CXX) $(ASAN_FLAGS) $< -o $@
 # ... of the spectral profile's arithmetic: spec refusals, each wave's run of frames and its boundary frame, the LDS swizzle, the size of the planes
 tools/asan_profile_plan: tools/asan_profile_plan.cpp $(SRC)/profile_plan.h $(SRC)/band_plan.h $(SRC)/last_error.h include/birdnet_hip.h
+	$(CXX) $(ASAN_FLAGS) $< -o $@
+# ... of the noise reduction's arithmetic: spec and noise refusals, every (frame, register, lane) position the kernel reads or stores for
+# ragged lengths, the register shift, the window table, bn_noise_floor's selection
+tools/asan_denoise_plan: tools/asan_denoise_plan.cpp $(SRC)/denoise_plan.h $(SRC)/band_plan.h $(SRC)/last_error.h include/birdnet_hip.h
 	$(CXX) $(ASAN_FLAGS) $< -o $@
 # ... of the FIR filter's arithmetic: tap refusals, the designer, the chunk geometry, the packed Toeplitz operand (plan_rules.h's split
 # needs the runtime's headers, no more)

@@ -636,6 +636,59 @@ bn_status bn_recording_create_filtered(const bn_recording *src, const float *tap
 bn_status bn_fir_bandpass(uint32_t sample_rate, double lo_hz, double hi_hz, size_t n_taps, float *taps_out);
 
 /*
+ * Noise reduction: spectral gating, for stationary broadband noise that sits in the birds' own band (rain, insects, a stream, wind
+ * hiss, recorder self-noise), where no band-pass helps.  bn_recording_create_denoised returns a NEW mono f32 recording of
+ * n = bn_recording_samples(src) samples on src's device.  x is the f32 sample src's layout rule defines and 0 outside [0, n), the
+ * convention of bn_recording_create_filtered.  With N = spec->frame, H = N / 2 and noise[0 .. N/2]:
+ *
+ * Frames.  Frame t, t = 0 .. ceil(n / H), covers source positions [(t - 1) H, (t + 1) H): every sample of [0, n) lies in exactly
+ * two frames, the first H samples included.
+ * Window.  w_j = sin(pi j / N), the square root of the periodic Hann window, applied before the transform and again after the
+ * inverse; its squares add to 1 at hop N / 2.
+ * Transform and power.  X_t[k] = sum_j w_j x[(t - 1) H + j] exp(-2 pi i jk / N), k = 0 .. N/2;
+ * P[t,k] = c_k |X_t[k]|^2 / (N sum_j w_j^2), c_k as for band levels.  This is band levels' normalisation with this window, so white
+ * noise reads the same expected value per bin as in plane 0 of bn_recording_spectral_profile: that equality is what makes the
+ * profile over quiet windows a usable `noise` (bn_noise_floor below).
+ * Gain, memoryless, per frame and bin.  With a_k = alpha * noise[k] (formed in double, rounded to f32 once): g = 1 where a_k == 0;
+ * otherwise g = floor_gain where P == 0; otherwise g = max(floor_gain, 1 - a_k / P[t,k]).
+ * Synthesis.  y_t[j] = w_j * (1 / N) sum_{k=0}^{N-1} g_k X_t[k] exp(+2 pi i jk / N), g X extended Hermitian.  Output block b,
+ * samples [b H, (b + 1) H) cut to n, is the second half of y_b plus the first half of y_{b+1}.
+ *
+ * Consequences.  With alpha == 0 or an all-zero `noise` the result is src's samples to within the bound below.  Silence gives 0 in
+ * every sample.  Invariance: the bits of an output sample depend only on the 3 H source samples of its two frames, N, alpha,
+ * floor_gain and noise -- not on n, on the layout, or on where the sample falls in the grid of workgroups.  Non-finite samples are
+ * not special-cased: outputs within N samples of one are unspecified non-finite values, outputs further away keep their bits.
+ *
+ * Arithmetic.  Plain f32, no fused multiply-add, no math-library call on the device; one frame goes there and back in one wave's
+ * registers and the overlap-add is a register add (csrc/denoise.hip).  Against the float64 rule on the same f32 samples, noise and
+ * spec with the double window, u = 2^-24, eps = BN_BAND_EPS_ULPS * u per transform direction, w x_t frame t's windowed samples,
+ * for every output block b, barring underflow:
+ *   || got - ref ||_2  <=  (BN_DENOISE_K * eps + BN_DENOISE_GAIN_ULPS * u) * (|| w x_b ||_2 + || w x_{b+1} ||_2)
+ * (derivation in DESIGN.md 7c, "Noise reduction").
+ *
+ * src may have any layout, be resampled, a channel view, filtered or asynchronously uploaded (the call waits for the whole
+ * upload); it is left untouched and may be freed first.  An empty source gives an empty recording.  The result behaves as a
+ * filtered recording does, the wording of a refused channel view included.  BN_ERR_INVALID_ARG, with a message, nothing enqueued
+ * and no handle written: a NULL argument, a spec_size below the struct's, a frame that is not 256, 512, 1024 or 2048, alpha negative
+ * or non-finite, floor_gain outside [0, 1] or NaN, a noise entry that is negative or non-finite.
+ *
+ * bn_noise_floor (host only, no device): profile_bins is the out_bins of bn_recording_spectral_profile over `count` windows, taken
+ * with bin_lo = 0 and bin_hi = N/2 + 1 = n_bins.  Per bin, noise_out[k] is the plane-0 value of rank
+ * floor(quantile * (count - 1)) among the windows in ascending order; +Inf entries (BN_LEVEL_NONFINITE windows) sort last.
+ * BN_ERR_INVALID_ARG, nothing written: count or n_bins 0, quantile outside [0, 1] or NaN, a NULL pointer, a NaN in plane 0.
+ */
+#define BN_DENOISE_K 4          /* 1 (forward) + 2 (forward, through the gain) + 1 (inverse), in units of eps */
+#define BN_DENOISE_GAIN_ULPS 12 /* 1 (a_k) + 1 (division) + 1 (subtraction) + 4 (P) + 1 (g X) + 1 (overlap-add) + 3 spare */
+typedef struct bn_denoise_spec {
+    uint32_t frame;   /* N: 256, 512, 1024 or 2048 */
+    float alpha;      /* over-subtraction: a bin must rise above alpha * noise[k] to pass; >= 0 */
+    float floor_gain; /* the gain of a gated bin, in [0, 1] */
+} bn_denoise_spec;
+bn_status bn_recording_create_denoised(const bn_recording *src, const bn_denoise_spec *spec, size_t spec_size, const float *noise,
+                                       bn_recording **out);
+bn_status bn_noise_floor(const float *profile_bins, size_t count, size_t n_bins, double quantile, float *noise_out);
+
+/*
  * bn_step_window_list: bn_step_windows over an explicit list.  Row i of the batch is the S = sample_count frames of
  * refs[i].recording from frame refs[i].start on, zeros past the end; start is any frame of the recording, no multiple of any step
  * (a window centred on a peak is fine).  The rows are gathered on the device straight into the context's input buffer -- the

@@ -228,6 +228,10 @@ class Recording {
     /* bn_recording_create_filtered: a new mono f32 recording, this one through the centred FIR filter `taps` (birdnet_hip.h, "FIR
      * filtering"; bn_fir_bandpass designs a band-pass).  Throws Error::Inference with the library's message on a refusal. */
     Recording filtered(const float *taps, size_t n_taps) const;
+    /* bn_recording_create_denoised: a new mono f32 recording, this one through the spectral gate of `spec` against the noise estimate
+     * `noise` (spec.frame / 2 + 1 floats; birdnet_hip.h, "Noise reduction"; bn_noise_floor makes one from a spectral profile).  Throws
+     * Error::Inference with the library's message on a refusal. */
+    Recording denoised(const bn_denoise_spec &spec, const float *noise) const;
     size_t n_samples() const { return n_samples_; }
     const bn_recording *raw() const { return rec_.get(); }
 
@@ -544,6 +548,10 @@ int32_t bnh_recording_spectral_profile(const bnh_recording *r, size_t segment_sa
                                        size_t count, bn_window_profile *out, float *bins, size_t cap, size_t *n_out, bnh_error *err);
 /* Recording::filtered: *out is a new recording, freed with bnh_recording_free; r may be freed first */
 int32_t bnh_recording_filtered(const bnh_recording *r, const float *taps, size_t n_taps, bnh_recording **out, bnh_error *err);
+/* Recording::denoised: *out is a new recording, freed with bnh_recording_free; r may be freed first.  noise: spec->frame / 2 + 1 floats */
+int32_t bnh_recording_denoised(const bnh_recording *r, const bn_denoise_spec *spec, const float *noise, bnh_recording **out, bnh_error *err);
+/* bn_noise_floor through the mirror's error convention (host only) */
+int32_t bnh_noise_floor(const float *profile_bins, size_t count, size_t n_bins, double quantile, float *noise_out, bnh_error *err);
 /* row i: recordings[i] from frame starts[i]; sources / windows may be NULL (0 and the row's position) */
 int32_t bnh_predict_window_list(const bnh_classifier *c, bnh_context *ctx, const bnh_recording *const *recordings, const uint64_t *starts,
                                 const int32_t *sources, const uint64_t *windows, size_t n, int64_t timeout_ns, const volatile int32_t *cancel,

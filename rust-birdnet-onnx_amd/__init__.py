@@ -57,7 +57,7 @@ ENGINE_SYMBOLS = [
     "bn_group_uses_rccl", "bn_group_get_stats", "bn_shard_range", "bn_group_analyze_recording", "bn_group_last_error", "bn_recording_create_resampled", "bn_resample_table", "bn_recording_read_f32", "bn_last_error",
     "bn_recording_create_layout", "bn_recording_create_layout_async", "bn_recording_create_layout_resampled", "bn_recording_view_channel", "bn_live_create_layout",
     "bn_recording_levels", "bn_step_window_list", "bn_recording_window_list", "bn_recording_band_levels", "bn_band_bins", "bn_recording_spectral_profile",
-    "bn_recording_create_filtered", "bn_fir_bandpass",
+    "bn_recording_create_filtered", "bn_fir_bandpass", "bn_recording_create_denoised", "bn_noise_floor",
     "bn_index_create", "bn_index_free", "bn_index_size", "bn_index_dim", "bn_index_add_host", "bn_index_add_ctx", "bn_index_read",
     "bn_index_search", "bn_index_search_ids", "bn_index_assign", "bn_index_cluster",
     "bn_index_save", "bn_index_load", "bn_index_file_info", "bn_index_file_verify",
@@ -96,7 +96,7 @@ HOST_SYMBOLS = [
     "bnh_context_attach_prior", "bnh_context_set_prior_site", "bnh_context_prior_results",
     "bnh_live_create", "bnh_live_create_rates", "bnh_live_create_layout", "bnh_predict_recording_layout", "bnh_live_free", "bnh_live_push", "bnh_live_close", "bnh_live_ready", "bnh_predict_live",
     "bnh_recording_create", "bnh_recording_free", "bnh_recording_samples", "bnh_recording_levels", "bnh_predict_window_list",
-    "bnh_recording_band_levels", "bnh_recording_spectral_profile", "bnh_recording_filtered",
+    "bnh_recording_band_levels", "bnh_recording_spectral_profile", "bnh_recording_filtered", "bnh_recording_denoised", "bnh_noise_floor",
 ]
 
 
@@ -237,6 +237,27 @@ def fir_bandpass(sample_rate: int, lo_hz: float, hi_hz: float, n_taps: int) -> n
     return taps
 
 
+BN_DENOISE_K, BN_DENOISE_GAIN_ULPS = 4, 12  # include/birdnet_hip.h: the constants of the header's bound on a denoised block
+BN_DENOISE_RUN = 16  # csrc/denoise_plan.h: the output blocks one wave of the denoiser owns (the tests place their edges around 4 * RUN blocks)
+
+
+class BnDenoiseSpec(C.Structure):
+    _fields_ = [("frame", C.c_uint32), ("alpha", C.c_float), ("floor_gain", C.c_float)]
+
+
+def noise_floor(profile_bins, quantile: float) -> np.ndarray:
+    """bn_noise_floor: per bin the plane-0 value of rank floor(quantile * (count - 1)) among the windows of profile_bins, the planes
+    [count, 3, n_bins] of a spectral profile taken over bins (0, frame / 2 + 1); the `noise` of Recording.denoised.  Host only."""
+    pl = np.ascontiguousarray(profile_bins, dtype=np.float32)
+    if pl.ndim != 3 or pl.shape[1] != BN_PROFILE_PLANES:
+        raise ValueError("profile_bins must be [count, 3, n_bins]")
+    out = np.zeros(pl.shape[2], dtype=np.float32)
+    st = lib.bn_noise_floor(pl.ctypes.data_as(C.POINTER(C.c_float)), pl.shape[0], pl.shape[2], quantile, out.ctypes.data_as(C.POINTER(C.c_float)))
+    if st:
+        raise EngineError(st)
+    return out
+
+
 class BnIndexFilter(C.Structure):
     _fields_ = [("first_id", C.c_uint64), ("n_ids", C.c_uint64), ("tags", C.POINTER(C.c_uint32)), ("n_tags", C.c_size_t), ("flags", C.c_uint32)]
 
@@ -338,6 +359,8 @@ def _load() -> C.CDLL:
         "bn_band_bins": (i32, [C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
         "bn_recording_create_filtered": (i32, [vp, C.POINTER(C.c_float), sz, C.POINTER(vp)]),
         "bn_fir_bandpass": (i32, [C.c_uint32, C.c_double, C.c_double, sz, C.POINTER(C.c_float)]),
+        "bn_recording_create_denoised": (i32, [vp, C.POINTER(BnDenoiseSpec), sz, C.POINTER(C.c_float), C.POINTER(vp)]),
+        "bn_noise_floor": (i32, [C.POINTER(C.c_float), sz, sz, C.c_double, C.POINTER(C.c_float)]),
         "bn_recording_window_list": (i32, [C.POINTER(BnWindowRef), sz, sz, sz, f32p]),
         "bn_last_error": (sz, [C.c_char_p, sz]),
         "bn_ctx_step_device_rows": (i32, [vp, C.POINTER(u32p)]),
@@ -515,6 +538,8 @@ def _load() -> C.CDLL:
                                                  C.POINTER(BnhError)]),
         "bnh_recording_band_levels": (i32, [vp, sz, sz, C.POINTER(BnBandSpec), sz, sz, C.POINTER(BnWindowBands), sz, C.POINTER(sz), C.POINTER(BnhError)]),
         "bnh_recording_filtered": (i32, [vp, C.POINTER(C.c_float), sz, C.POINTER(vp), C.POINTER(BnhError)]),
+        "bnh_recording_denoised": (i32, [vp, C.POINTER(BnDenoiseSpec), C.POINTER(C.c_float), C.POINTER(vp), C.POINTER(BnhError)]),
+        "bnh_noise_floor": (i32, [C.POINTER(C.c_float), sz, sz, C.c_double, C.POINTER(C.c_float), C.POINTER(BnhError)]),
         "bnh_predict_window_list": (i32, [vp, vp, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(C.c_uint64), sz, C.c_int64,
                                           C.POINTER(C.c_int32), C.POINTER(vp), C.POINTER(BnhError)]),
         "bnh_predict_live": (i32, [vp, vp, vp, sz, C.c_int64, C.POINTER(C.c_int32), C.POINTER(vp), C.POINTER(C.c_int32),
@@ -938,6 +963,18 @@ class HostRecording:
         t = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
         h, err = C.c_void_p(), BnhError()
         if lib.bnh_recording_filtered(self._h, t.ctypes.data_as(C.POINTER(C.c_float)), t.shape[0], C.byref(h), C.byref(err)):
+            raise Error(err)
+        r = HostRecording.__new__(HostRecording)
+        r._h, r.n_samples = h, int(lib.bnh_recording_samples(h))
+        return r
+
+    def denoised(self, frame: int, noise, alpha: float = 1.0, floor_gain: float = 0.1) -> "HostRecording":
+        """Recording::denoised: a new mono f32 recording, this one through the spectral gate (see Recording.denoised)."""
+        nz = np.ascontiguousarray(noise, dtype=np.float32).reshape(-1)
+        if nz.shape[0] != frame // 2 + 1:
+            raise ValueError("noise must hold frame / 2 + 1 floats")
+        h, err, sp = C.c_void_p(), BnhError(), BnDenoiseSpec(frame, alpha, floor_gain)
+        if lib.bnh_recording_denoised(self._h, C.byref(sp), nz.ctypes.data_as(C.POINTER(C.c_float)), C.byref(h), C.byref(err)):
             raise Error(err)
         r = HostRecording.__new__(HostRecording)
         r._h, r.n_samples = h, int(lib.bnh_recording_samples(h))
@@ -1574,6 +1611,21 @@ class Recording:
         t = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
         h = C.c_void_p()
         st = lib.bn_recording_create_filtered(self._h, t.ctypes.data_as(C.POINTER(C.c_float)), t.shape[0], C.byref(h))
+        if st:
+            raise EngineError(st)
+        return Recording._adopt(h)
+
+    def denoised(self, frame: int, noise, alpha: float = 1.0, floor_gain: float = 0.1) -> "Recording":
+        """bn_recording_create_denoised: a new mono f32 recording, this one through a spectral gate computed on the device: frames of
+        `frame` samples at hop frame / 2 under a square-root Hann window, each bin k of each frame scaled by
+        max(floor_gain, 1 - alpha * noise[k] / P) (P its one-sided power, on the scale of plane 0 of spectral_profile), transformed
+        back and overlap-added.  noise: frame / 2 + 1 floats, e.g. noise_floor() of a profile.  This recording is left as it is and
+        may go first."""
+        nz = np.ascontiguousarray(noise, dtype=np.float32).reshape(-1)
+        if nz.shape[0] != frame // 2 + 1:
+            raise ValueError("noise must hold frame / 2 + 1 floats")
+        h, sp = C.c_void_p(), BnDenoiseSpec(frame, alpha, floor_gain)
+        st = lib.bn_recording_create_denoised(self._h, C.byref(sp), C.sizeof(BnDenoiseSpec), nz.ctypes.data_as(C.POINTER(C.c_float)), C.byref(h))
         if st:
             raise EngineError(st)
         return Recording._adopt(h)

@@ -332,6 +332,21 @@ int32_t bnh_recording_filtered(const bnh_recording *r, const float *taps, size_t
     return guarded(err, [&] { *out = new bnh_recording{r->rec.filtered(taps, n_taps)}; });
 }
 
+int32_t bnh_recording_denoised(const bnh_recording *r, const bn_denoise_spec *spec, const float *noise, bnh_recording **out, bnh_error *err) {
+    if (!out) return set_other(err, "null argument");
+    *out = nullptr;
+    if (!r) return set_other(err, "null recording");
+    if (!spec) return set_other(err, "null denoise spec");
+    return guarded(err, [&] { *out = new bnh_recording{r->rec.denoised(*spec, noise)}; });
+}
+
+int32_t bnh_noise_floor(const float *profile_bins, size_t count, size_t n_bins, double quantile, float *noise_out, bnh_error *err) {
+    if (bn_noise_floor(profile_bins, count, n_bins, quantile, noise_out) == BN_OK) return guarded(err, [] {});
+    char msg[256];
+    bn_last_error(msg, sizeof(msg));
+    return set_other(err, msg);
+}
+
 int32_t bnh_predict_window_list(const bnh_classifier *c, bnh_context *ctx, const bnh_recording *const *recordings, const uint64_t *starts,
                                 const int32_t *sources, const uint64_t *windows, size_t n, int64_t timeout_ns, const volatile int32_t *cancel,
                                 bnh_results **out, bnh_error *err) {

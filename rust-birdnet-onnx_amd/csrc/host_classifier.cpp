@@ -389,6 +389,15 @@ Recording Recording::filtered(const float *taps, size_t n_taps) const {
     return f;
 }
 
+Recording Recording::denoised(const bn_denoise_spec &spec, const float *noise) const {
+    bn_recording *r = nullptr;
+    if (bn_recording_create_denoised(rec_.get(), &spec, sizeof(bn_denoise_spec), noise, &r) != BN_OK)
+        throw inference("failed to denoise the recording: " + last_backend_error());
+    Recording f(*this);  // the same number of samples
+    f.rec_ = std::shared_ptr<bn_recording>(r, [](bn_recording *p) { bn_recording_free(p); });
+    return f;
+}
+
 std::vector<ChunkResult> Classifier::predict_recording(BatchInferenceContext &ctx, const Recording &rec, float overlap_secs, size_t first_chunk, size_t count,
                                                        const InferenceOptions &options) const {
     const ModelConfig &cfg = inner_->config;

@@ -1,4 +1,4 @@
-// Recordings of the C ABI (include/birdnet_hip.h): bn_recording_*, the resampler's table, FIR filtering, and the explicit window lists
+// Recordings of the C ABI (include/birdnet_hip.h): bn_recording_*, the resampler's table, FIR filtering, noise reduction, and the explicit window lists
 // (bn_recording_window_list, bn_step_window_list: of a context they need what bn_step_live does).  bn_recording is private to this
 // file; capi.cpp's bn_infer_windows and bn_step_windows reach a recording through check_windows and enqueue_windows (capi_internal.h).
 // Every launch is clear_launch_state, the launcher, check_launch; results reach the host through launch_and_read or rows_in_pieces.
@@ -18,6 +18,7 @@
 
 #include "band_levels.h"
 #include "capi_internal.h"
+#include "denoise.h"
 #include "fir.h"
 #include "kernels.h"
 #include "levels.h"
@@ -56,7 +57,7 @@ struct bn_recording {
     bool resampled = false;   // the store holds the resampler's mono f32 output: no storage-format bytes are left
     std::shared_ptr<RecStore> store;
     size_t n_samples = 0;  // frames
-    bool filtered = false;  // ... and that output went through bn_recording_create_filtered (the wording of a refused channel view)
+    bool filtered = false;  // ... and that output went through bn_recording_create_filtered or _denoised (the wording of a refused channel view)
     PcmSrc src() const { return PcmSrc{store->d_pcm.get(), layout}; }
 };
 
@@ -579,6 +580,42 @@ bn_status bn_recording_create_filtered(const bn_recording *src, const float *tap
 
 bn_status bn_fir_bandpass(uint32_t sample_rate, double lo_hz, double hi_hz, size_t n_taps, float *taps_out) {
     return fir::bandpass(sample_rate, lo_hz, hi_hz, n_taps, taps_out);
+}
+
+// ---- noise reduction (include/birdnet_hip.h, "Noise reduction"; kernel in denoise.hip, arithmetic in denoise_plan.h) ----
+bn_status bn_recording_create_denoised(const bn_recording *src, const bn_denoise_spec *spec, size_t spec_size, const float *noise, bn_recording **out) {
+    if (!out) return fail(BN_ERR_INVALID_ARG, "null argument");
+    *out = nullptr;
+    if (!src) return fail(BN_ERR_INVALID_ARG, "null recording");
+    denoise::Plan plan;
+    std::vector<float> a;
+    if (bn_status st = denoise::check_spec(spec, spec_size, noise, &plan, &a); st != BN_OK) return st;
+    // every output reads samples on both sides of it: the whole upload must have arrived
+    const size_t n = src->n_samples;
+    if (n > denoise::N_MAX) return fail(BN_ERR_INVALID_ARG, "the recording is too long to denoise");
+    if (!recording_wait_samples(src, n ? n - 1 : 0)) return fail(BN_ERR_BACKEND, "recording upload failed");
+    BN_HIP_TRY(bn::use_device(src->device));
+    // a store of its own, as the filter's output: mono f32, nothing shared with src
+    std::unique_ptr<bn_recording> r(new bn_recording{src->device, PcmLayout{BN_PCM_F32, 1, 0}, true, true, std::make_shared<RecStore>(src->device, n), n, true});
+    const float *band_tab = nullptr, *win_tab = nullptr;
+    float band_scale = 0.0f, scale = 0.0f;
+    DeviceBuf<float> d_a;
+    hipError_t e = r->store->d_pcm.alloc(std::max<size_t>(n * sizeof(float), 16));
+    if (e == hipSuccess) e = band_tables(src->device, plan.N, &band_tab, &band_scale);
+    if (e == hipSuccess) e = denoise_tables(src->device, plan.N, &win_tab, &scale);
+    if (e == hipSuccess) e = d_a.alloc(a.size() * sizeof(float));
+    if (e == hipSuccess) e = gated::Memcpy(d_a, a.data(), a.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return fail(BN_ERR_BACKEND, std::string("noise reduction failed: ") + hipGetErrorString(e));
+    bn::clear_launch_state();
+    launch_denoise(nullptr, static_cast<float *>(r->store->d_pcm.get()), src->src(), n, plan, band_tab, win_tab, d_a.get(), scale);
+    if (bn_status st = bn::check_launch("denoise"); st != BN_OK) return st;
+    if ((e = gated::DeviceSynchronize()) != hipSuccess) return fail(BN_ERR_BACKEND, std::string("noise reduction failed: ") + hipGetErrorString(e));
+    *out = r.release();
+    return BN_OK;
+}
+
+bn_status bn_noise_floor(const float *profile_bins, size_t count, size_t n_bins, double quantile, float *noise_out) {
+    return denoise::noise_floor(profile_bins, count, n_bins, quantile, noise_out);
 }
 
 bn_status bn_recording_window_list(const bn_window_ref *refs, size_t count, size_t struct_size, size_t segment_samples, float *host_out) {
