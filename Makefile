@@ -10,7 +10,7 @@ CXXFLAGS := -O3 -std=c++17 -fPIC -Wall -Wextra -Wno-unused-parameter -Iinclude
 # for the pairs with register moves (mbmap's depthwise phase: 120 v_pk_fma + 216 v_mov for 240 multiply-adds); on this part a packed
 # f32 instruction costs 1.56x a plain one (tools/mfma_valu_probe.cpp) and every vector instruction is paid out of the MFMA time
 HIPFLAGS := $(CXXFLAGS) --offload-arch=$(ARCH) -ffp-contract=off -fno-slp-vectorize
-OBJS := $(SRC)/onnx_proto.o $(SRC)/engine.o $(SRC)/onnx_rewrite.o $(SRC)/dft_bank.o $(SRC)/mbconv_fuse.o $(SRC)/plan_passes.o $(SRC)/detect.o $(SRC)/capi.o $(SRC)/recording.o $(SRC)/step_common.o $(SRC)/group.o $(SRC)/host_classifier.o $(SRC)/host_capi.o $(SRC)/host_rangefilter.o $(SRC)/kernels.o $(SRC)/topk.o $(SRC)/stft.o $(SRC)/mbrow.o $(SRC)/gemm_dma.o $(SRC)/gemm_dma3.o $(SRC)/gemm_b3.o $(SRC)/mbmap.o $(SRC)/mbmap_ws.o $(SRC)/index.o $(SRC)/head.o $(SRC)/rank.o $(SRC)/cluster.o $(SRC)/ivf.o $(SRC)/sq8.o $(SRC)/subset.o $(SRC)/index_copy.o $(SRC)/peaks.o $(SRC)/seq.o $(SRC)/above.o $(SRC)/group_above.o $(SRC)/match.o $(SRC)/index_io.o $(SRC)/index_file.o $(SRC)/prior.o $(SRC)/track.o $(SRC)/live.o $(SRC)/live_kernels.o $(SRC)/levels.o $(SRC)/band_levels.o $(SRC)/spectral_profile.o $(SRC)/fir.o $(SRC)/denoise.o
+OBJS := $(SRC)/onnx_proto.o $(SRC)/engine.o $(SRC)/onnx_rewrite.o $(SRC)/dft_bank.o $(SRC)/mbconv_fuse.o $(SRC)/plan_passes.o $(SRC)/detect.o $(SRC)/capi.o $(SRC)/recording.o $(SRC)/step_common.o $(SRC)/group.o $(SRC)/host_classifier.o $(SRC)/host_capi.o $(SRC)/host_rangefilter.o $(SRC)/kernels.o $(SRC)/topk.o $(SRC)/stft.o $(SRC)/mbrow.o $(SRC)/gemm_dma.o $(SRC)/gemm_dma3.o $(SRC)/gemm_b3.o $(SRC)/mbmap.o $(SRC)/mbmap_ws.o $(SRC)/index.o $(SRC)/head.o $(SRC)/rank.o $(SRC)/cluster.o $(SRC)/ivf.o $(SRC)/sq8.o $(SRC)/subset.o $(SRC)/index_copy.o $(SRC)/peaks.o $(SRC)/seq.o $(SRC)/above.o $(SRC)/group_above.o $(SRC)/match.o $(SRC)/index_io.o $(SRC)/index_file.o $(SRC)/prior.o $(SRC)/track.o $(SRC)/live.o $(SRC)/live_kernels.o $(SRC)/levels.o $(SRC)/band_levels.o $(SRC)/spectral_profile.o $(SRC)/fir.o $(SRC)/denoise.o $(SRC)/spectrogram.o
 
 all: $(OUT) oracle
 
@@ -33,6 +33,9 @@ $(SRC)/spectral_profile.o: $(SRC)/spectral_profile.hip $(wildcard $(SRC)/*.h)
 	$(HIPCC) $(HIPFLAGS) -Xclang -target-feature -Xclang -packed-fp32-ops -c $< -o $@
 # denoise.hip: the same switch (plain f32 butterflies whose bits are the contract)
 $(SRC)/denoise.o: $(SRC)/denoise.hip $(wildcard $(SRC)/*.h)
+	$(HIPCC) $(HIPFLAGS) -Xclang -target-feature -Xclang -packed-fp32-ops -c $< -o $@
+# spectrogram.hip: the same switch (band levels' transform and the split of a power pair)
+$(SRC)/spectrogram.o: $(SRC)/spectrogram.hip $(wildcard $(SRC)/*.h)
 	$(HIPCC) $(HIPFLAGS) -Xclang -target-feature -Xclang -packed-fp32-ops -c $< -o $@
 $(OUT): $(OBJS)
 	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $@ $(OBJS) -lpthread -ldl
@@ -83,6 +86,10 @@ tools/asan_denoise_plan: tools/asan_denoise_plan.cpp $(SRC)/denoise_plan.h $(SRC
 # ... of the FIR filter's arithmetic: tap refusals, the designer, the chunk geometry, the packed Toeplitz operand (plan_rules.h's split
 # needs the runtime's headers, no more)
 tools/asan_fir_plan: tools/asan_fir_plan.cpp $(SRC)/fir_plan.h $(SRC)/plan_rules.h $(SRC)/last_error.h include/birdnet_hip.h
+	$(CXX) $(ASAN_FLAGS) -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include $< -o $@
+# ... of the spectrogram's arithmetic: spec, bank and designer refusals, sizes and starts at extreme n_frames and hop, the LDS strides,
+# the packed bank re-summed to its weights with each tile's step range, the threshold table
+tools/asan_spectrogram_plan: tools/asan_spectrogram_plan.cpp $(SRC)/spectrogram_plan.h $(SRC)/band_plan.h $(SRC)/plan_rules.h $(SRC)/last_error.h include/birdnet_hip.h
 	$(CXX) $(ASAN_FLAGS) -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include $< -o $@
 # ... and of the operands of finished plans: the planner's own files, as tools/asan_plan.cpp links them
 PLANNER_SRC := $(SRC)/onnx_proto.cpp $(SRC)/engine.cpp $(SRC)/onnx_rewrite.cpp $(SRC)/dft_bank.cpp $(SRC)/mbconv_fuse.cpp $(SRC)/plan_passes.cpp $(SRC)/detect.cpp

@@ -689,6 +689,83 @@ bn_status bn_recording_create_denoised(const bn_recording *src, const bn_denoise
 bn_status bn_noise_floor(const float *profile_bins, size_t count, size_t n_bins, double quantile, float *noise_out);
 
 /*
+ * Spectrograms: the time-frequency plane itself, as bin rows or through a filter bank, as floats or as decibel codes.
+ * bn_recording_spectrogram writes n_frames * n_rows elements to `out`, dense and time-major: element (t, row) at index
+ * t * n_rows + row, a float (BN_SPECTROGRAM_F32) or a byte (BN_SPECTROGRAM_U8).
+ *
+ * Frames.  Frame t, t < n_frames, covers recording samples [first_sample + t * hop, first_sample + t * hop + N), N = spec->frame;
+ * x is the f32 sample r's layout rule defines and 0 at and past bn_recording_samples(r).  This is a spectrogram of a time range,
+ * not of the model's windows: the caller picks the range, e.g. a detection's window plus context.
+ * Window, transform and one-sided power P[t,k], k = 0 .. N/2, are those of bn_recording_band_levels (the periodic Hann window, the
+ * scale c_k / (N * sum w^2), the same code): the row of bin k equals what plane 0 of bn_recording_spectral_profile reads for a
+ * window that holds only that frame.
+ * Rows.  Without a bank, row j is P[t, bin_lo + j], n_rows = bin_hi - bin_lo.  With a bank, row m is
+ * E[t,m] = sum_k W[m,k] P[t,k], n_rows = bn_filterbank_rows(bank); W is the caller's dense row-major n_rows x (N/2 + 1) matrix of
+ * finite weights >= 0 (mel triangles, third-octave bands, a log-frequency axis), given to bn_filterbank_create, which packs and
+ * uploads it once.  The bank's frame must be spec->frame, its device the recording's; bin_lo and bin_hi must then both be 0.
+ * U8 codes.  bn_spectrogram_thresholds (host only) computes, in double,
+ *   thr[j - 1] = ref_power * 10^(((j - 0.5) * range_db / 255 - range_db) / 10),   j = 1 .. 255,
+ * rounds each to f32 once and forces the table non-decreasing.  The code of a pixel is the number of thresholds that are <= the
+ * f32 value BN_SPECTROGRAM_F32 stores for it: the U8 image is, bit for bit, the table applied to the F32 image (code 255 at
+ * ref_power and above, code 0 from ref_power - range_db down; a NaN counts as above every threshold).
+ * Non-finite samples.  A frame that reads a NaN or +-Inf sample stores +Inf in every one of its rows (code 255); other frames keep
+ * their bits.
+ * Invariance.  The bits of frame t's row depend only on its N samples, N, the bin range or the bank's weights, format, ref_power
+ * and range_db: not on first_sample, n_frames, where the frame falls in a tile or in the grid, the recording's length or layout,
+ * nor on how a range is split into calls.
+ *
+ * Arithmetic.  The transform is band levels'.  A bank row is a product on the bf16 matrix pipe (csrc/spectrogram.hip): weights and
+ * powers are each the exact sum of three bf16 terms, six of the nine partial products are kept, k ascending.  Against the float64
+ * value on the same f32 samples with the double window, u = 2^-24, eps = BN_BAND_EPS_ULPS * u, T_t the reference total of frame t,
+ * barring underflow:
+ *   bin rows    |got - P| <= 2 eps sqrt(P T_t) + eps^2 T_t + BN_SPECTROGRAM_POW_DEPTH * u * P                   =: b(t,k)
+ *   bank rows   |got - E| <= sum_k W[m,k] b(t,k) + (2^-21 + BN_SPECTROGRAM_BANK_DEPTH * u) * E
+ * (derivation in DESIGN.md 7c, "Spectrogram").  U8 has no bound of its own.
+ *
+ * The call blocks on an asynchronous upload until the last sample it reads has arrived, and returns when `out` is written.
+ * spec_size is sizeof(bn_spectrogram_spec) as the caller compiled it.  BN_ERR_INVALID_ARG, with a message, nothing enqueued and
+ * nothing written: a NULL r, spec or out, a spec_size below the struct's, a frame that is not 256, 512, 1024 or 2048, hop 0 or
+ * above frame, an unknown format; without a bank bin_lo >= bin_hi or bin_hi > frame / 2 + 1; with a bank a non-zero bin range, a
+ * bank of another frame or on another device; for U8 a ref_power or range_db that is not positive and finite;
+ * first_sample > bn_recording_samples(r); out_bytes below n_frames * n_rows * element size (formed without wrapping).
+ * n_frames == 0 is BN_OK.
+ *
+ * bn_filterbank_create refuses (BN_ERR_INVALID_ARG, no handle written) NULL weights or out, n_rows 0 or above
+ * BN_FILTERBANK_MAX_ROWS, a frame not in the list, a weight that is negative, NaN or +-Inf, a row of all zeros.
+ * bn_filterbank_rows / _frame of NULL are 0.
+ * bn_mel_filterbank (host only): n_mels x (frame / 2 + 1) weights, computed in double and rounded once.  HTK scale
+ * mel(f) = 2595 log10(1 + f / 700); n_mels + 2 points equally spaced in mel over [fmin_hz, fmax_hz]; triangle m rises from point m
+ * to 1 at point m + 1 and falls to 0 at point m + 2, evaluated at the bin centres k * sample_rate / frame; no area normalisation.
+ * BN_ERR_INVALID_ARG: a rate of 0, a frame not in the list, n_mels 0 or above BN_FILTERBANK_MAX_ROWS, fmin_hz < 0,
+ * fmin_hz >= fmax_hz, fmax_hz > sample_rate / 2, a NaN, a NULL output, a triangle that holds no bin centre (the message names the
+ * first such m).
+ * bn_spectrogram_thresholds refuses a ref_power or range_db that is not positive and finite, and a NULL output.
+ */
+#define BN_SPECTROGRAM_F32 0 /* one-sided power, float */
+#define BN_SPECTROGRAM_U8 1  /* decibel codes 0..255, one byte */
+#define BN_FILTERBANK_MAX_ROWS 256
+#define BN_SPECTROGRAM_POW_DEPTH 6    /* 2 (squares and their sum) + 2 (the scale, its f32 constant) + 2 spare */
+#define BN_SPECTROGRAM_BANK_DEPTH 206 /* 6 accumulator roundings per 32 bins * 33 steps at frame 2048 + 8 (FIR's fixed allowance) */
+typedef struct bn_filterbank bn_filterbank;
+typedef struct bn_spectrogram_spec {
+    uint32_t frame;  /* N: 256, 512, 1024 or 2048 */
+    uint32_t hop;    /* 1 .. N */
+    uint32_t bin_lo; /* bank == NULL: rows are the bins [bin_lo, bin_hi), bin_hi <= N/2 + 1 */
+    uint32_t bin_hi; /* with a bank: both must be 0 */
+    uint32_t format; /* BN_SPECTROGRAM_F32 or BN_SPECTROGRAM_U8 */
+    float ref_power; /* U8: the power that reaches code 255; > 0, finite */
+    float range_db;  /* U8: code 0 is ref_power - range_db or less; > 0, finite */
+} bn_spectrogram_spec;
+bn_status bn_recording_spectrogram(const bn_recording *r, size_t first_sample, size_t n_frames, const bn_spectrogram_spec *spec,
+                                   size_t spec_size, const bn_filterbank *bank, void *out, size_t out_bytes);
+bn_status bn_filterbank_create(int32_t device, uint32_t frame, size_t n_rows, const float *weights, bn_filterbank **out);
+void bn_filterbank_free(bn_filterbank *b);
+size_t bn_filterbank_rows(const bn_filterbank *b);
+uint32_t bn_filterbank_frame(const bn_filterbank *b);
+bn_status bn_mel_filterbank(uint32_t sample_rate, uint32_t frame, size_t n_mels, double fmin_hz, double fmax_hz, float *weights_out);
+bn_status bn_spectrogram_thresholds(float ref_power, float range_db, float *thr_out /* 255 */);
+
+/*
  * bn_step_window_list: bn_step_windows over an explicit list.  Row i of the batch is the S = sample_count frames of
  * refs[i].recording from frame refs[i].start on, zeros past the end; start is any frame of the recording, no multiple of any step
  * (a window centred on a peak is fine).  The rows are gathered on the device straight into the context's input buffer -- the

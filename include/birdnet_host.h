@@ -197,6 +197,20 @@ class BatchInferenceContext {
 
 struct ClassifierInner;
 
+/* bn_filterbank: n_rows x (frame / 2 + 1) non-negative weights applied to every frame's power spectrum by Recording::spectrogram,
+ * packed and uploaded once (birdnet_hip.h, "Spectrograms"; bn_mel_filterbank designs mel triangles).  Throws Error::Inference with
+ * the library's message on a refusal. */
+class Filterbank {
+   public:
+    Filterbank(uint32_t frame, size_t n_rows, const float *weights, int device = 0);
+    size_t rows() const;
+    uint32_t frame() const;
+    const bn_filterbank *raw() const { return bank_.get(); }
+
+   private:
+    std::shared_ptr<bn_filterbank> bank_;
+};
+
 /* A mono recording uploaded to the device once, in its storage format: the native form of the
  * reference CLI's read_wav (i16 / 32768.0, src/bin/birdnet-analyze.rs:683-687) + chunk_audio
  * (:707-743).  Windows are cut on the device (bn_infer_windows). */
@@ -232,6 +246,10 @@ class Recording {
      * `noise` (spec.frame / 2 + 1 floats; birdnet_hip.h, "Noise reduction"; bn_noise_floor makes one from a spectral profile).  Throws
      * Error::Inference with the library's message on a refusal. */
     Recording denoised(const bn_denoise_spec &spec, const float *noise) const;
+    /* bn_recording_spectrogram: n_frames frames from first_sample on as [frame][row] floats or codes in `out` (out_bytes of it), the
+     * rows being spec's bins or, with a bank, the bank's (birdnet_hip.h, "Spectrograms").  Throws Error::Inference with the library's
+     * message on a refusal. */
+    void spectrogram(size_t first_sample, size_t n_frames, const bn_spectrogram_spec &spec, const Filterbank *bank, void *out, size_t out_bytes) const;
     size_t n_samples() const { return n_samples_; }
     const bn_recording *raw() const { return rec_.get(); }
 
@@ -552,6 +570,13 @@ int32_t bnh_recording_filtered(const bnh_recording *r, const float *taps, size_t
 int32_t bnh_recording_denoised(const bnh_recording *r, const bn_denoise_spec *spec, const float *noise, bnh_recording **out, bnh_error *err);
 /* bn_noise_floor through the mirror's error convention (host only) */
 int32_t bnh_noise_floor(const float *profile_bins, size_t count, size_t n_bins, double quantile, float *noise_out, bnh_error *err);
+/* class Filterbank and Recording::spectrogram; bank may be NULL (bin rows) */
+typedef struct bnh_filterbank bnh_filterbank;
+int32_t bnh_filterbank_create(uint32_t frame, size_t n_rows, const float *weights, int32_t device, bnh_filterbank **out, bnh_error *err);
+void bnh_filterbank_free(bnh_filterbank *b);
+size_t bnh_filterbank_rows(const bnh_filterbank *b);
+int32_t bnh_recording_spectrogram(const bnh_recording *r, size_t first_sample, size_t n_frames, const bn_spectrogram_spec *spec,
+                                  const bnh_filterbank *bank, void *out, size_t out_bytes, bnh_error *err);
 /* row i: recordings[i] from frame starts[i]; sources / windows may be NULL (0 and the row's position) */
 int32_t bnh_predict_window_list(const bnh_classifier *c, bnh_context *ctx, const bnh_recording *const *recordings, const uint64_t *starts,
                                 const int32_t *sources, const uint64_t *windows, size_t n, int64_t timeout_ns, const volatile int32_t *cancel,

@@ -58,6 +58,8 @@ ENGINE_SYMBOLS = [
     "bn_recording_create_layout", "bn_recording_create_layout_async", "bn_recording_create_layout_resampled", "bn_recording_view_channel", "bn_live_create_layout",
     "bn_recording_levels", "bn_step_window_list", "bn_recording_window_list", "bn_recording_band_levels", "bn_band_bins", "bn_recording_spectral_profile",
     "bn_recording_create_filtered", "bn_fir_bandpass", "bn_recording_create_denoised", "bn_noise_floor",
+    "bn_recording_spectrogram", "bn_filterbank_create", "bn_filterbank_free", "bn_filterbank_rows", "bn_filterbank_frame", "bn_mel_filterbank",
+    "bn_spectrogram_thresholds",
     "bn_index_create", "bn_index_free", "bn_index_size", "bn_index_dim", "bn_index_add_host", "bn_index_add_ctx", "bn_index_read",
     "bn_index_search", "bn_index_search_ids", "bn_index_assign", "bn_index_cluster",
     "bn_index_save", "bn_index_load", "bn_index_file_info", "bn_index_file_verify",
@@ -97,6 +99,7 @@ HOST_SYMBOLS = [
     "bnh_live_create", "bnh_live_create_rates", "bnh_live_create_layout", "bnh_predict_recording_layout", "bnh_live_free", "bnh_live_push", "bnh_live_close", "bnh_live_ready", "bnh_predict_live",
     "bnh_recording_create", "bnh_recording_free", "bnh_recording_samples", "bnh_recording_levels", "bnh_predict_window_list",
     "bnh_recording_band_levels", "bnh_recording_spectral_profile", "bnh_recording_filtered", "bnh_recording_denoised", "bnh_noise_floor",
+    "bnh_recording_spectrogram", "bnh_filterbank_create", "bnh_filterbank_free", "bnh_filterbank_rows",
 ]
 
 
@@ -258,6 +261,84 @@ def noise_floor(profile_bins, quantile: float) -> np.ndarray:
     return out
 
 
+BN_SPECTROGRAM_F32, BN_SPECTROGRAM_U8 = 0, 1  # include/birdnet_hip.h: bn_spectrogram_spec.format
+BN_FILTERBANK_MAX_ROWS = 256
+BN_SPECTROGRAM_POW_DEPTH, BN_SPECTROGRAM_BANK_DEPTH = 6, 206  # the constants of the header's bounds on a spectrogram
+BN_SPECTROGRAM_TILE = 16  # csrc/spectrogram_plan.h: the frames one workgroup owns, the bank rows of one accumulator
+
+
+class BnSpectrogramSpec(C.Structure):
+    _fields_ = [("frame", C.c_uint32), ("hop", C.c_uint32), ("bin_lo", C.c_uint32), ("bin_hi", C.c_uint32), ("format", C.c_uint32),
+                ("ref_power", C.c_float), ("range_db", C.c_float)]
+
+
+def _spectrogram_call(n_frames: int, frame: int, hop: int, bins, bank, u8):
+    """(spec, out) of a spectrogram call: rows are the bins = (bin_lo, bin_hi) or the bank's, u8 = (ref_power, range_db) or None for
+    floats; `out` has a spare element, for a call the library refuses"""
+    lo, hi = (0, 0) if bins is None else bins
+    n_rows = bank.n_rows if bank is not None else max(int(hi) - int(lo), 0)
+    sp = BnSpectrogramSpec(frame, hop, lo, hi, BN_SPECTROGRAM_F32 if u8 is None else BN_SPECTROGRAM_U8, *((0.0, 0.0) if u8 is None else u8))
+    return sp, np.zeros(max(n_frames, 0) * n_rows + 1, dtype=np.float32 if u8 is None else np.uint8), n_rows
+
+
+def mel_filterbank(sample_rate: int, frame: int, n_mels: int, fmin_hz: float, fmax_hz: float) -> np.ndarray:
+    """bn_mel_filterbank: [n_mels, frame / 2 + 1] float32 HTK mel triangles with peak 1 (no area normalisation), evaluated at the
+    bin centres; the weights of a Filterbank.  Host only."""
+    w = np.zeros((max(int(n_mels), 0), frame // 2 + 1), dtype=np.float32)
+    st = lib.bn_mel_filterbank(sample_rate, frame, n_mels, fmin_hz, fmax_hz, w.ctypes.data_as(C.POINTER(C.c_float)))
+    if st:
+        raise EngineError(st)
+    return w
+
+
+def spectrogram_thresholds(ref_power: float, range_db: float) -> np.ndarray:
+    """bn_spectrogram_thresholds: the 255 float32 thresholds of the U8 codes; a pixel's code is the number of them that are <= its
+    power, i.e. numpy.searchsorted(thr, image, side="right").  Host only."""
+    thr = np.zeros(255, dtype=np.float32)
+    st = lib.bn_spectrogram_thresholds(ref_power, range_db, thr.ctypes.data_as(C.POINTER(C.c_float)))
+    if st:
+        raise EngineError(st)
+    return thr
+
+
+class Filterbank:
+    """bn_filterbank: a non-negative [n_rows, frame / 2 + 1] matrix applied to the power spectrum of every frame of
+    Recording.spectrogram, packed and uploaded once (mel_filterbank() designs mel triangles)."""
+
+    def __init__(self, device: int, frame: int, weights):
+        w = np.ascontiguousarray(weights, dtype=np.float32)
+        if w.ndim != 2 or w.shape[1] != frame // 2 + 1:
+            raise ValueError("weights must be [n_rows, frame / 2 + 1]")
+        h = C.c_void_p()
+        st = lib.bn_filterbank_create(device, frame, w.shape[0], w.ctypes.data_as(C.POINTER(C.c_float)), C.byref(h))
+        if st:
+            raise EngineError(st)
+        self._h, self.device, self.frame, self.n_rows = h, device, frame, int(lib.bn_filterbank_rows(h))
+
+    def __del__(self):
+        if getattr(self, "_h", None) and lib is not None:
+            lib.bn_filterbank_free(self._h)
+            self._h = None
+
+
+class HostFilterbank:
+    """birdnet::Filterbank: a Filterbank through the host mirror, for HostRecording.spectrogram."""
+
+    def __init__(self, frame: int, weights, device: int = 0):
+        w = np.ascontiguousarray(weights, dtype=np.float32)
+        if w.ndim != 2 or w.shape[1] != frame // 2 + 1:
+            raise ValueError("weights must be [n_rows, frame / 2 + 1]")
+        h, err = C.c_void_p(), BnhError()
+        if lib.bnh_filterbank_create(frame, w.shape[0], w.ctypes.data_as(C.POINTER(C.c_float)), device, C.byref(h), C.byref(err)):
+            raise Error(err)
+        self._h, self.frame, self.n_rows = h, frame, int(lib.bnh_filterbank_rows(h))
+
+    def __del__(self):
+        if getattr(self, "_h", None) and lib is not None:
+            lib.bnh_filterbank_free(self._h)
+            self._h = None
+
+
 class BnIndexFilter(C.Structure):
     _fields_ = [("first_id", C.c_uint64), ("n_ids", C.c_uint64), ("tags", C.POINTER(C.c_uint32)), ("n_tags", C.c_size_t), ("flags", C.c_uint32)]
 
@@ -361,6 +442,13 @@ def _load() -> C.CDLL:
         "bn_fir_bandpass": (i32, [C.c_uint32, C.c_double, C.c_double, sz, C.POINTER(C.c_float)]),
         "bn_recording_create_denoised": (i32, [vp, C.POINTER(BnDenoiseSpec), sz, C.POINTER(C.c_float), C.POINTER(vp)]),
         "bn_noise_floor": (i32, [C.POINTER(C.c_float), sz, sz, C.c_double, C.POINTER(C.c_float)]),
+        "bn_recording_spectrogram": (i32, [vp, sz, sz, C.POINTER(BnSpectrogramSpec), sz, vp, vp, sz]),
+        "bn_filterbank_create": (i32, [i32, C.c_uint32, sz, C.POINTER(C.c_float), C.POINTER(vp)]),
+        "bn_filterbank_free": (None, [vp]),
+        "bn_filterbank_rows": (sz, [vp]),
+        "bn_filterbank_frame": (C.c_uint32, [vp]),
+        "bn_mel_filterbank": (i32, [C.c_uint32, C.c_uint32, sz, C.c_double, C.c_double, C.POINTER(C.c_float)]),
+        "bn_spectrogram_thresholds": (i32, [C.c_float, C.c_float, C.POINTER(C.c_float)]),
         "bn_recording_window_list": (i32, [C.POINTER(BnWindowRef), sz, sz, sz, f32p]),
         "bn_last_error": (sz, [C.c_char_p, sz]),
         "bn_ctx_step_device_rows": (i32, [vp, C.POINTER(u32p)]),
@@ -540,6 +628,10 @@ def _load() -> C.CDLL:
         "bnh_recording_filtered": (i32, [vp, C.POINTER(C.c_float), sz, C.POINTER(vp), C.POINTER(BnhError)]),
         "bnh_recording_denoised": (i32, [vp, C.POINTER(BnDenoiseSpec), C.POINTER(C.c_float), C.POINTER(vp), C.POINTER(BnhError)]),
         "bnh_noise_floor": (i32, [C.POINTER(C.c_float), sz, sz, C.c_double, C.POINTER(C.c_float), C.POINTER(BnhError)]),
+        "bnh_recording_spectrogram": (i32, [vp, sz, sz, C.POINTER(BnSpectrogramSpec), vp, vp, sz, C.POINTER(BnhError)]),
+        "bnh_filterbank_create": (i32, [C.c_uint32, sz, C.POINTER(C.c_float), i32, C.POINTER(vp), C.POINTER(BnhError)]),
+        "bnh_filterbank_free": (None, [vp]),
+        "bnh_filterbank_rows": (sz, [vp]),
         "bnh_predict_window_list": (i32, [vp, vp, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(C.c_uint64), sz, C.c_int64,
                                           C.POINTER(C.c_int32), C.POINTER(vp), C.POINTER(BnhError)]),
         "bnh_predict_live": (i32, [vp, vp, vp, sz, C.c_int64, C.POINTER(C.c_int32), C.POINTER(vp), C.POINTER(C.c_int32),
@@ -979,6 +1071,15 @@ class HostRecording:
         r = HostRecording.__new__(HostRecording)
         r._h, r.n_samples = h, int(lib.bnh_recording_samples(h))
         return r
+
+    def spectrogram(self, first: int, n_frames: int, frame: int, hop: int, bins=None, bank=None, u8=None) -> np.ndarray:
+        """Recording::spectrogram: the [n_frames, n_rows] image of Recording.spectrogram; bank is a HostFilterbank."""
+        sp, out, n_rows = _spectrogram_call(n_frames, frame, hop, bins, bank, u8)
+        err = BnhError()
+        if lib.bnh_recording_spectrogram(self._h, first, n_frames, C.byref(sp), bank._h if bank is not None else None, out.ctypes.data_as(C.c_void_p),
+                                         out.nbytes - out.itemsize, C.byref(err)):
+            raise Error(err)
+        return out[:-1].reshape(n_frames, n_rows)
 
 
 class LiveSources:
@@ -1629,6 +1730,20 @@ class Recording:
         if st:
             raise EngineError(st)
         return Recording._adopt(h)
+
+    def spectrogram(self, first: int, n_frames: int, frame: int, hop: int, bins=None, bank=None, u8=None) -> np.ndarray:
+        """bn_recording_spectrogram: the one-sided power (band levels' scale) of n_frames frames of `frame` samples every `hop`
+        from sample `first` on, zeros past the recording's end, computed on the device, as an [n_frames, n_rows] array: the bins =
+        (bin_lo, bin_hi) without a bank, the rows of `bank` (a Filterbank of the same frame) applied to every frame's spectrum
+        with one.  u8 None: float32.  u8 = (ref_power, range_db): uint8 decibel codes, 255 at ref_power and above, 0 from
+        range_db below it down -- spectrogram_thresholds() applied to the float image, bit for bit.  A frame that reads a NaN or
+        +-Inf sample is +Inf (255) in every row."""
+        sp, out, n_rows = _spectrogram_call(n_frames, frame, hop, bins, bank, u8)
+        st = lib.bn_recording_spectrogram(self._h, first, n_frames, C.byref(sp), C.sizeof(BnSpectrogramSpec), bank._h if bank is not None else None,
+                                          out.ctypes.data_as(C.c_void_p), out.nbytes - out.itemsize)
+        if st:
+            raise EngineError(st)
+        return out[:-1].reshape(n_frames, n_rows)
 
 
 class Index:

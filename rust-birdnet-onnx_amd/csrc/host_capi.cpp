@@ -347,6 +347,24 @@ int32_t bnh_noise_floor(const float *profile_bins, size_t count, size_t n_bins, 
     return set_other(err, msg);
 }
 
+struct bnh_filterbank {
+    Filterbank bank;
+};
+int32_t bnh_filterbank_create(uint32_t frame, size_t n_rows, const float *weights, int32_t device, bnh_filterbank **out, bnh_error *err) {
+    if (!out) return set_other(err, "null argument");
+    *out = nullptr;
+    return guarded(err, [&] { *out = new bnh_filterbank{Filterbank(frame, n_rows, weights, device)}; });
+}
+void bnh_filterbank_free(bnh_filterbank *b) { delete b; }
+size_t bnh_filterbank_rows(const bnh_filterbank *b) { return b ? b->bank.rows() : 0; }
+
+int32_t bnh_recording_spectrogram(const bnh_recording *r, size_t first_sample, size_t n_frames, const bn_spectrogram_spec *spec, const bnh_filterbank *bank,
+                                  void *out, size_t out_bytes, bnh_error *err) {
+    if (!r) return set_other(err, "null recording");
+    if (!spec) return set_other(err, "null spectrogram spec");
+    return guarded(err, [&] { r->rec.spectrogram(first_sample, n_frames, *spec, bank ? &bank->bank : nullptr, out, out_bytes); });
+}
+
 int32_t bnh_predict_window_list(const bnh_classifier *c, bnh_context *ctx, const bnh_recording *const *recordings, const uint64_t *starts,
                                 const int32_t *sources, const uint64_t *windows, size_t n, int64_t timeout_ns, const volatile int32_t *cancel,
                                 bnh_results **out, bnh_error *err) {

@@ -398,6 +398,20 @@ Recording Recording::denoised(const bn_denoise_spec &spec, const float *noise) c
     return f;
 }
 
+Filterbank::Filterbank(uint32_t frame, size_t n_rows, const float *weights, int device) {
+    bn_filterbank *b = nullptr;
+    if (bn_filterbank_create(device, frame, n_rows, weights, &b) != BN_OK) throw inference("failed to create the filter bank: " + last_backend_error());
+    bank_ = std::shared_ptr<bn_filterbank>(b, [](bn_filterbank *p) { bn_filterbank_free(p); });
+}
+
+size_t Filterbank::rows() const { return bn_filterbank_rows(bank_.get()); }
+uint32_t Filterbank::frame() const { return bn_filterbank_frame(bank_.get()); }
+
+void Recording::spectrogram(size_t first_sample, size_t n_frames, const bn_spectrogram_spec &spec, const Filterbank *bank, void *out, size_t out_bytes) const {
+    if (bn_recording_spectrogram(rec_.get(), first_sample, n_frames, &spec, sizeof(bn_spectrogram_spec), bank ? bank->raw() : nullptr, out, out_bytes) != BN_OK)
+        throw inference(last_backend_error());
+}
+
 std::vector<ChunkResult> Classifier::predict_recording(BatchInferenceContext &ctx, const Recording &rec, float overlap_secs, size_t first_chunk, size_t count,
                                                        const InferenceOptions &options) const {
     const ModelConfig &cfg = inner_->config;

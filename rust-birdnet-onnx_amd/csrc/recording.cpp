@@ -1,4 +1,5 @@
-// Recordings of the C ABI (include/birdnet_hip.h): bn_recording_*, the resampler's table, FIR filtering, noise reduction, and the explicit window lists
+// Recordings of the C ABI (include/birdnet_hip.h): bn_recording_*, the resampler's table, FIR filtering, noise reduction, spectrograms and their
+// filter banks, and the explicit window lists
 // (bn_recording_window_list, bn_step_window_list: of a context they need what bn_step_live does).  bn_recording is private to this
 // file; capi.cpp's bn_infer_windows and bn_step_windows reach a recording through check_windows and enqueue_windows (capi_internal.h).
 // Every launch is clear_launch_state, the launcher, check_launch; results reach the host through launch_and_read or rows_in_pieces.
@@ -23,6 +24,7 @@
 #include "kernels.h"
 #include "levels.h"
 #include "spectral_profile.h"
+#include "spectrogram.h"
 #include "window_list_plan.h"
 
 using namespace bn;
@@ -60,6 +62,17 @@ struct bn_recording {
     bool filtered = false;  // ... and that output went through bn_recording_create_filtered or _denoised (the wording of a refused channel view)
     PcmSrc src() const { return PcmSrc{store->d_pcm.get(), layout}; }
 };
+// A filter bank of spectrograms: the packed A operand of its weights on the device (spectrogram_plan.h, pack_bank), the per-tile
+// step table in front of it
+struct bn_filterbank {
+    int32_t device = 0;
+    uint32_t frame = 0, n_tiles = 0;
+    size_t n_rows = 0;
+    DeviceBuf<uint8_t> d;  // spectro::BankTiles, then the fragments
+    const spectro::BankTiles *tiles() const { return reinterpret_cast<const spectro::BankTiles *>(d.get()); }
+    const void *image() const { return d.get() + sizeof(spectro::BankTiles); }
+};
+static_assert(sizeof(spectro::BankTiles) % 16 == 0, "the fragments behind the table are read 16 bytes at a time");
 
 namespace {
 bn_status fail(bn_status st, const std::string &msg) { return set_last_error(st, msg); }
@@ -617,6 +630,76 @@ bn_status bn_recording_create_denoised(const bn_recording *src, const bn_denoise
 bn_status bn_noise_floor(const float *profile_bins, size_t count, size_t n_bins, double quantile, float *noise_out) {
     return denoise::noise_floor(profile_bins, count, n_bins, quantile, noise_out);
 }
+
+// ---- spectrograms (include/birdnet_hip.h, "Spectrograms"; kernels in spectrogram.hip, arithmetic in spectrogram_plan.h) ----
+bn_status bn_recording_spectrogram(const bn_recording *r, size_t first_sample, size_t n_frames, const bn_spectrogram_spec *spec, size_t spec_size,
+                                   const bn_filterbank *bank, void *out, size_t out_bytes) {
+    if (!r) return fail(BN_ERR_INVALID_ARG, "null recording");
+    spectro::Plan plan;
+    if (bn_status st = spectro::check_spec(spec, spec_size, bank ? bank->n_rows : 0, bank ? bank->frame : 0, &plan); st != BN_OK) return st;
+    if (bank && bank->device != r->device)
+        return fail(BN_ERR_INVALID_ARG, "the filter bank lives on device " + std::to_string(bank->device) + ", the recording on device " + std::to_string(r->device));
+    if (first_sample > r->n_samples)
+        return fail(BN_ERR_INVALID_ARG, "first_sample " + std::to_string(first_sample) + " is past the " + std::to_string(r->n_samples) + " samples of the recording");
+    size_t need = 0;
+    if (!spectro::out_bytes(n_frames, plan.n_rows, plan.elem, &need)) return fail(BN_ERR_INVALID_ARG, "n_frames * n_rows elements do not fit a size_t");
+    if (n_frames == 0) return BN_OK;
+    if (!out) return fail(BN_ERR_INVALID_ARG, "null output buffer");
+    if (out_bytes < need) return fail(BN_ERR_INVALID_ARG, "out_bytes " + std::to_string(out_bytes) + " is below the " + std::to_string(need) + " bytes of the spectrogram");
+    // an asynchronously uploaded recording: the last sample any of these frames reads must have arrived
+    uint64_t last = 0;
+    if (spectro::last_sample_read(r->n_samples, first_sample, n_frames, plan.N, plan.hop, &last) && !recording_wait_samples(r, (size_t)last))
+        return fail(BN_ERR_BACKEND, "recording upload failed");
+    BN_HIP_TRY(bn::use_device(r->device));
+    const float *tab = nullptr;
+    float scale = 0.0f;
+    BN_HIP_TRY(band_tables(r->device, plan.N, &tab, &scale));
+    if (plan.N == band::FRAME_MAX) BN_HIP_TRY(spectrogram_prepare(r->device));
+    DeviceBuf<float> d_thr;
+    if (plan.format == BN_SPECTROGRAM_U8) {
+        float thr[spectro::N_THR];
+        if (bn_status st = spectro::thresholds(plan.ref_power, plan.range_db, thr); st != BN_OK) return st;
+        BN_HIP_TRY(d_thr.alloc(sizeof(thr)));
+        BN_HIP_TRY(gated::Memcpy(d_thr, thr, sizeof(thr), hipMemcpyHostToDevice));
+    }
+    // whole tiles of 16 frames per launch, read back piece by piece
+    const size_t piece = spectro::piece_frames(plan.n_rows), per = (size_t)plan.n_rows * plan.elem;
+    DeviceBuf<uint8_t> d;
+    BN_HIP_TRY(d.alloc(std::max<size_t>(std::min(piece, n_frames) * per, 16)));
+    for (size_t done = 0; done < n_frames; done += piece) {
+        const size_t n = std::min(piece, n_frames - done);
+        bn_status st = launch_and_read("spectrogram", "spectrogram kernel failed: ", static_cast<char *>(out) + done * per, d, n * per, [&] {
+            launch_spectrogram(nullptr, d.get(), r->src(), r->n_samples, spectro::frame_start(r->n_samples, first_sample, done, plan.hop), (uint32_t)n, plan, tab,
+                               scale, d_thr.get(), bank ? bank->image() : nullptr, bank ? bank->tiles() : nullptr, bank ? bank->n_tiles : 0);
+        });
+        if (st != BN_OK) return st;
+    }
+    return BN_OK;
+}
+
+bn_status bn_filterbank_create(int32_t device, uint32_t frame, size_t n_rows, const float *weights, bn_filterbank **out) {
+    if (!out) return fail(BN_ERR_INVALID_ARG, "null argument");
+    *out = nullptr;
+    if (bn_status st = spectro::check_bank(frame, n_rows, weights); st != BN_OK) return st;
+    if (bn_status dst = require_any_device(); dst != BN_OK) return dst;
+    BN_HIP_TRY(bn::use_device(device));
+    const spectro::PackedBank pb = spectro::pack_bank(frame, n_rows, weights);
+    std::unique_ptr<bn_filterbank> b(new bn_filterbank);
+    b->device = device, b->frame = frame, b->n_tiles = pb.n_tiles, b->n_rows = n_rows;
+    const size_t image_bytes = pb.image.size() * sizeof(uint16_t);
+    BN_HIP_TRY(b->d.alloc(sizeof(spectro::BankTiles) + image_bytes));
+    BN_HIP_TRY(gated::Memcpy(b->d.get(), &pb.tiles, sizeof(pb.tiles), hipMemcpyHostToDevice));
+    BN_HIP_TRY(gated::Memcpy(b->d.get() + sizeof(pb.tiles), pb.image.data(), image_bytes, hipMemcpyHostToDevice));
+    *out = b.release();
+    return BN_OK;
+}
+void bn_filterbank_free(bn_filterbank *b) { delete b; }
+size_t bn_filterbank_rows(const bn_filterbank *b) { return b ? b->n_rows : 0; }
+uint32_t bn_filterbank_frame(const bn_filterbank *b) { return b ? b->frame : 0; }
+bn_status bn_mel_filterbank(uint32_t sample_rate, uint32_t frame, size_t n_mels, double fmin_hz, double fmax_hz, float *weights_out) {
+    return spectro::mel_bank(sample_rate, frame, n_mels, fmin_hz, fmax_hz, weights_out);
+}
+bn_status bn_spectrogram_thresholds(float ref_power, float range_db, float *thr_out) { return spectro::thresholds(ref_power, range_db, thr_out); }
 
 bn_status bn_recording_window_list(const bn_window_ref *refs, size_t count, size_t struct_size, size_t segment_samples, float *host_out) {
     if (count == 0) return BN_OK;
