@@ -766,6 +766,96 @@ bn_status bn_mel_filterbank(uint32_t sample_rate, uint32_t frame, size_t n_mels,
 bn_status bn_spectrogram_thresholds(float ref_power, float range_db, float *thr_out /* 255 */);
 
 /*
+ * bn_recording_delay: per window, the time difference of arrival between two recordings -- two channel views of one file
+ * (bn_recording_view_channel), or two mono uploads from two synchronised recorders -- as a generalised cross-correlation over the
+ * lags -max_lag .. +max_lag, its peak and the two values beside the peak.  a and b are any two recordings on one device; filtered,
+ * denoised, resampled or asynchronously uploaded ones included.  out[i] receives window first_window + i.
+ *
+ * Windows and frames.  Windows, frames, the periodic Hann window, the transform X_t[k] and the unread tail are those of
+ * bn_recording_band_levels, applied to window k of a (A_t) and to window k of b (B_t): the same start k * step_samples, each reading
+ * zeros past its own recording's end.  A window exists iff k * step_samples < min(samples(a), samples(b)); BN_LEVEL_PADDED is set
+ * iff the window reaches past either end.  n_frames = (S - N) / hop + 1.
+ * Cross-spectrum.  G_k = sum_t A_t[k] conj(B_t[k]), k = 0 .. N/2.
+ * Weighting.  Psi_k = 0 outside [bin_lo, bin_hi).  Inside, BN_DELAY_PLAIN: Psi_k = G_k.  BN_DELAY_PHAT: Psi_k = G_k / |G_k|, and 0
+ * where |G_k| == 0.  The weighting comes after the sum over the window's frames: the window's summed cross-spectrum is whitened
+ * once, not frame by frame.
+ * Correlation.  r[tau] = (1 / Z) sum_{k=0}^{N/2} c_k Re(Psi_k exp(+2 pi i k tau / N)), -max_lag <= tau <= max_lag, c_k as for band
+ * levels: the inverse transform of the Hermitian extension, read at tau mod N.  PLAIN: Z = n_frames * N * sum_n w_n^2, so r[0] of a
+ * recording against itself is the band's mean power on band levels' scale.  PHAT: Z = sum_{k in band} c_k, so a pair whose
+ * cross-spectrum has one linear phase reads 1.0 at that lag.  A value of -0 is stored as +0.
+ * Sign.  If a[n] = b[n - d], the peak lies at tau = +d: peak_lag > 0 means the sound reaches a later than b.
+ * Peak.  The greatest r[tau] wins; among equal values the smallest |tau|, then the negative one.  Silence on either side gives
+ * peak_lag = 0 and peak = before = after = 0.  before and after are r[peak_lag - 1] and r[peak_lag + 1]; both exist because
+ * max_lag + 1 <= N/2, and they may lie outside the searched lags.
+ * Non-finite samples.  A window in which a frame of either recording reads a NaN or +-Inf sample gets BN_LEVEL_NONFINITE,
+ * peak_lag = 0, and a quiet NaN in peak, before, after and every float of its curve.
+ * out_curve.  Window i, lag tau at i * (2 max_lag + 1) + (tau + max_lag); dense.  With NULL only the records are written; their
+ * bits are the same either way.
+ *
+ * Arithmetic.  The forward transform is band levels' and the inverse is noise reduction's, one inverse per window; plain f32, no
+ * fused multiply-add.  A conj(B) is four products and two sums; each of four waves adds a run of q = ceil(n_frames / 4) consecutive
+ * frames in ascending order from 0.0f and the runs combine as (w0 + w1) + (w2 + w3) per component, an association that is a
+ * function of (S, spec) alone; |G_k| is the correctly rounded root, PHAT has one division per bin; Z enters as one f32 factor
+ * computed in double (csrc/delay.hip).  Against the float64 rule on the same f32 samples with the double window, u = 2^-24,
+ * eps = BN_BAND_EPS_ULPS * u, Ea_t = sum_k c_k |A_t[k]|^2 (frame t's energy, all bins) and Eb_t likewise, barring underflow and
+ * overflow: the computed cross-spectrum of bin k is within
+ *   delta_k = sum_t (eps (|B_t[k]| sqrt(Ea_t) + |A_t[k]| sqrt(Eb_t)) + eps^2 sqrt(Ea_t Eb_t))
+ *             + (BN_DELAY_ACC_DEPTH + 2 q) * u * sum_t |A_t[k]| |B_t[k]|
+ * of G_k, and for every lag, every value of the curve and peak, before and after:
+ *   PLAIN   |got - r[tau]| <= (1 / Z) sum_{k in band} c_k (delta_k + (eps + BN_DELAY_OUT_ULPS * u) |G_k|)
+ *   PHAT    |got - r[tau]| <= (1 / Z) sum_{k in band} c_k (min(2, delta_k / (|G_k| - delta_k)) + BN_DELAY_PHAT_ULPS * u
+ *                                                          + eps + BN_DELAY_OUT_ULPS * u)
+ *           (a bin with |G_k| <= delta_k counts 2: inside the transform's own error its phase is anybody's)
+ * (derivation in DESIGN.md 7c, "Cross-channel delay").  peak_lag is the rule's wherever the rule's peak leads every other lag by
+ * more than twice the bound.
+ *
+ * Invariance.  A window's record and curve depend only on its S samples of a, its S samples of b, S and the spec: not on
+ * first_window, count, step_samples, the recordings' lengths or layouts, on how a window range is split into calls, or on whether
+ * out_curve is given.
+ *
+ * One reader for both.  The kernel is instantiated per sample reader, the same one for a and b: mono int16, mono f32, or
+ * interleaved frames of one of the five formats.  Two channel views of one file always share theirs.  A pair of two kinds is
+ * refused; a one-tap bn_recording_create_filtered (taps = {1.0f}) of either side gives a mono f32 copy.
+ *
+ * The call blocks on an asynchronous upload of either recording as band levels does.  spec_size is sizeof(bn_delay_spec),
+ * struct_size sizeof(bn_window_delay) as the caller compiled them, handled as band levels handles them.  BN_ERR_INVALID_ARG, with a
+ * message, nothing enqueued and nothing written: whatever band levels refuses about a recording, segment_samples, step_samples, the
+ * window range (against the rule above), frame and hop; a NULL a, b or spec; a spec_size or struct_size below the struct's;
+ * bin_lo >= bin_hi or bin_hi > frame / 2 + 1; max_lag > frame / 2 - 1; an unknown weighting; NULL `out` with count > 0; recordings
+ * on different devices; recordings of two reader kinds.  count == 0 is BN_OK.
+ *
+ * bn_delay_refine (host only, no device): the sub-sample lag of a record, the vertex of the parabola through its three values,
+ * computed in double: lag = peak_lag + 0.5 * (before - after) / (before - 2 peak + after), clamped to peak_lag +- 0.5; peak_lag
+ * where the denominator is 0 or the record is flagged BN_LEVEL_NONFINITE.  BN_ERR_INVALID_ARG: a NULL argument, a struct_size below
+ * the struct's.
+ */
+#define BN_DELAY_PLAIN 0 /* cross-correlation */
+#define BN_DELAY_PHAT 1  /* phase transform: every bin of the band weighs the same */
+#define BN_DELAY_ACC_DEPTH 8 /* 3/2 (a complex magnitude) * (2 (products and their sum) + 2 (four waves)) + 2 spare */
+#define BN_DELAY_PHAT_ULPS 6 /* 1 (squares and their sum, halved by the root) + 1 (root) + 1 (reciprocal) + 1 (product) + 2 spare */
+#define BN_DELAY_OUT_ULPS 4  /* 1 (1 / Z as f32) + 1 (the product with it) + 2 spare */
+typedef struct bn_delay_spec {
+    uint32_t frame;     /* N: 256, 512, 1024 or 2048 */
+    uint32_t hop;       /* 1 .. N */
+    uint32_t bin_lo;    /* only bins [bin_lo, bin_hi) contribute, bin_lo < bin_hi <= N/2 + 1 */
+    uint32_t bin_hi;
+    uint32_t max_lag;   /* lags -max_lag .. +max_lag are searched and returned; 0 .. N/2 - 1 */
+    uint32_t weighting; /* BN_DELAY_PLAIN or BN_DELAY_PHAT */
+} bn_delay_spec;
+typedef struct bn_window_delay {
+    int32_t peak_lag;  /* the lag of the greatest r; samples, > 0: the sound reaches a later than b */
+    float peak;        /* r[peak_lag] */
+    float before;      /* r[peak_lag - 1] */
+    float after;       /* r[peak_lag + 1] */
+    uint32_t flags;    /* BN_LEVEL_NONFINITE | BN_LEVEL_PADDED */
+    uint32_t n_frames;
+} bn_window_delay;
+bn_status bn_recording_delay(const bn_recording *a, const bn_recording *b, size_t segment_samples, size_t step_samples,
+                             size_t first_window, size_t count, const bn_delay_spec *spec, size_t spec_size, bn_window_delay *out,
+                             size_t struct_size, float *out_curve /* count * (2 max_lag + 1), or NULL */);
+bn_status bn_delay_refine(const bn_window_delay *w, size_t struct_size, double *lag_out);
+
+/*
  * bn_step_window_list: bn_step_windows over an explicit list.  Row i of the batch is the S = sample_count frames of
  * refs[i].recording from frame refs[i].start on, zeros past the end; start is any frame of the recording, no multiple of any step
  * (a window centred on a peak is fine).  The rows are gathered on the device straight into the context's input buffer -- the

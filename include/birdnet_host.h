@@ -239,6 +239,12 @@ class Recording {
      * as for levels().  Throws Error::Inference with the library's message on a refusal. */
     std::vector<bn_window_profile> spectral_profile(size_t segment_samples, size_t step_samples, const bn_profile_spec &spec, size_t first = 0,
                                                     size_t count = (size_t)-1, std::vector<float> *bins = nullptr) const;
+    /* bn_recording_delay: per window the cross-correlation peak of this recording (a) against `other` (b) over the lags
+     * -spec.max_lag .. +spec.max_lag, and, if `curve` is not NULL, every lag's value as [window][2 max_lag + 1] (birdnet_hip.h,
+     * "bn_recording_delay"); count == SIZE_MAX means "to the last window both recordings have".  bn_delay_refine gives a record's
+     * sub-sample lag.  Throws Error::Inference with the library's message on a refusal. */
+    std::vector<bn_window_delay> delay(const Recording &other, size_t segment_samples, size_t step_samples, const bn_delay_spec &spec, size_t first = 0,
+                                       size_t count = (size_t)-1, std::vector<float> *curve = nullptr) const;
     /* bn_recording_create_filtered: a new mono f32 recording, this one through the centred FIR filter `taps` (birdnet_hip.h, "FIR
      * filtering"; bn_fir_bandpass designs a band-pass).  Throws Error::Inference with the library's message on a refusal. */
     Recording filtered(const float *taps, size_t n_taps) const;
@@ -564,6 +570,10 @@ int32_t bnh_recording_band_levels(const bnh_recording *r, size_t segment_samples
  * first min(cap, *n_out) windows, 3 * (bin_hi - bin_lo) floats each */
 int32_t bnh_recording_spectral_profile(const bnh_recording *r, size_t segment_samples, size_t step_samples, const bn_profile_spec *spec, size_t first,
                                        size_t count, bn_window_profile *out, float *bins, size_t cap, size_t *n_out, bnh_error *err);
+/* Recording::delay of a against b; count, cap and *n_out as bnh_recording_levels.  curve may be NULL; else it takes the lags of the
+ * first min(cap, *n_out) windows, 2 * max_lag + 1 floats each */
+int32_t bnh_recording_delay(const bnh_recording *a, const bnh_recording *b, size_t segment_samples, size_t step_samples, const bn_delay_spec *spec,
+                            size_t first, size_t count, bn_window_delay *out, float *curve, size_t cap, size_t *n_out, bnh_error *err);
 /* Recording::filtered: *out is a new recording, freed with bnh_recording_free; r may be freed first */
 int32_t bnh_recording_filtered(const bnh_recording *r, const float *taps, size_t n_taps, bnh_recording **out, bnh_error *err);
 /* Recording::denoised: *out is a new recording, freed with bnh_recording_free; r may be freed first.  noise: spec->frame / 2 + 1 floats */

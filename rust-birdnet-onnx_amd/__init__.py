@@ -59,7 +59,7 @@ ENGINE_SYMBOLS = [
     "bn_recording_levels", "bn_step_window_list", "bn_recording_window_list", "bn_recording_band_levels", "bn_band_bins", "bn_recording_spectral_profile",
     "bn_recording_create_filtered", "bn_fir_bandpass", "bn_recording_create_denoised", "bn_noise_floor",
     "bn_recording_spectrogram", "bn_filterbank_create", "bn_filterbank_free", "bn_filterbank_rows", "bn_filterbank_frame", "bn_mel_filterbank",
-    "bn_spectrogram_thresholds",
+    "bn_spectrogram_thresholds", "bn_recording_delay", "bn_delay_refine",
     "bn_index_create", "bn_index_free", "bn_index_size", "bn_index_dim", "bn_index_add_host", "bn_index_add_ctx", "bn_index_read",
     "bn_index_search", "bn_index_search_ids", "bn_index_assign", "bn_index_cluster",
     "bn_index_save", "bn_index_load", "bn_index_file_info", "bn_index_file_verify",
@@ -100,6 +100,7 @@ HOST_SYMBOLS = [
     "bnh_recording_create", "bnh_recording_free", "bnh_recording_samples", "bnh_recording_levels", "bnh_predict_window_list",
     "bnh_recording_band_levels", "bnh_recording_spectral_profile", "bnh_recording_filtered", "bnh_recording_denoised", "bnh_noise_floor",
     "bnh_recording_spectrogram", "bnh_filterbank_create", "bnh_filterbank_free", "bnh_filterbank_rows",
+    "bnh_recording_delay",
 ]
 
 
@@ -224,6 +225,41 @@ def _profile_planes(count: int, bins, planes: bool):
     """the [count, 3, n_bins] array of a spectral profile (None without planes; one spare float for a bin range the library refuses)"""
     n_bins = max(int(bins[1]) - int(bins[0]), 0)
     return np.zeros(max(count, 0) * BN_PROFILE_PLANES * n_bins + 1, dtype=np.float32) if planes else None, n_bins
+
+
+BN_DELAY_PLAIN, BN_DELAY_PHAT = 0, 1  # include/birdnet_hip.h: the weightings of Recording.delay
+BN_DELAY_ACC_DEPTH, BN_DELAY_PHAT_ULPS, BN_DELAY_OUT_ULPS = 8, 6, 4  # the constants of the header's bounds on a delay
+
+
+class BnDelaySpec(C.Structure):
+    _fields_ = [("frame", C.c_uint32), ("hop", C.c_uint32), ("bin_lo", C.c_uint32), ("bin_hi", C.c_uint32), ("max_lag", C.c_uint32),
+                ("weighting", C.c_uint32)]
+
+
+class BnWindowDelay(C.Structure):
+    _fields_ = [("peak_lag", C.c_int32), ("peak", C.c_float), ("before", C.c_float), ("after", C.c_float), ("flags", C.c_uint32),
+                ("n_frames", C.c_uint32)]
+
+
+DELAY_DTYPE = np.dtype([("peak_lag", np.int32), ("peak", np.float32), ("before", np.float32), ("after", np.float32), ("flags", np.uint32),
+                        ("n_frames", np.uint32)])
+
+
+def _delay_curve(count: int, max_lag: int, curve: bool):
+    """the [count, 2 max_lag + 1] array of a delay's curves (None without; one spare float for a max_lag the library refuses)"""
+    n_lags = 2 * int(max_lag) + 1 if 0 <= int(max_lag) < 1024 else 0
+    return np.zeros(max(count, 0) * n_lags + 1, dtype=np.float32) if curve else None, n_lags
+
+
+def delay_refine(record) -> float:
+    """bn_delay_refine: the sub-sample lag of one DELAY_DTYPE record, the vertex of the parabola through peak, before and after,
+    within half a sample of peak_lag; host only."""
+    rec = np.ascontiguousarray(record, dtype=DELAY_DTYPE).reshape(1)
+    lag = C.c_double()
+    st = lib.bn_delay_refine(rec.ctypes.data_as(C.POINTER(BnWindowDelay)), C.sizeof(BnWindowDelay), C.byref(lag))
+    if st:
+        raise EngineError(st)
+    return lag.value
 
 
 BN_FIR_MAX_TAPS = 2047  # include/birdnet_hip.h: the longest filter of Recording.filtered
@@ -442,6 +478,8 @@ def _load() -> C.CDLL:
         "bn_fir_bandpass": (i32, [C.c_uint32, C.c_double, C.c_double, sz, C.POINTER(C.c_float)]),
         "bn_recording_create_denoised": (i32, [vp, C.POINTER(BnDenoiseSpec), sz, C.POINTER(C.c_float), C.POINTER(vp)]),
         "bn_noise_floor": (i32, [C.POINTER(C.c_float), sz, sz, C.c_double, C.POINTER(C.c_float)]),
+        "bn_recording_delay": (i32, [vp, vp, sz, sz, sz, sz, C.POINTER(BnDelaySpec), sz, C.POINTER(BnWindowDelay), sz, C.POINTER(C.c_float)]),
+        "bn_delay_refine": (i32, [C.POINTER(BnWindowDelay), sz, C.POINTER(C.c_double)]),
         "bn_recording_spectrogram": (i32, [vp, sz, sz, C.POINTER(BnSpectrogramSpec), sz, vp, vp, sz]),
         "bn_filterbank_create": (i32, [i32, C.c_uint32, sz, C.POINTER(C.c_float), C.POINTER(vp)]),
         "bn_filterbank_free": (None, [vp]),
@@ -628,6 +666,8 @@ def _load() -> C.CDLL:
         "bnh_recording_filtered": (i32, [vp, C.POINTER(C.c_float), sz, C.POINTER(vp), C.POINTER(BnhError)]),
         "bnh_recording_denoised": (i32, [vp, C.POINTER(BnDenoiseSpec), C.POINTER(C.c_float), C.POINTER(vp), C.POINTER(BnhError)]),
         "bnh_noise_floor": (i32, [C.POINTER(C.c_float), sz, sz, C.c_double, C.POINTER(C.c_float), C.POINTER(BnhError)]),
+        "bnh_recording_delay": (i32, [vp, vp, sz, sz, C.POINTER(BnDelaySpec), sz, sz, C.POINTER(BnWindowDelay), C.POINTER(C.c_float), sz, C.POINTER(sz),
+                                      C.POINTER(BnhError)]),
         "bnh_recording_spectrogram": (i32, [vp, sz, sz, C.POINTER(BnSpectrogramSpec), vp, vp, sz, C.POINTER(BnhError)]),
         "bnh_filterbank_create": (i32, [C.c_uint32, sz, C.POINTER(C.c_float), i32, C.POINTER(vp), C.POINTER(BnhError)]),
         "bnh_filterbank_free": (None, [vp]),
@@ -1049,6 +1089,21 @@ class HostRecording:
                                               pl.ctypes.data_as(C.POINTER(C.c_float)) if planes else None, cap, C.byref(n), C.byref(err)):
             raise Error(err)
         return out[:n.value].copy(), (pl[:n.value * BN_PROFILE_PLANES * n_bins].reshape(n.value, BN_PROFILE_PLANES, n_bins).copy() if planes else None)
+
+    def delay(self, other: "HostRecording", segment_samples: int, step_samples: int, frame: int, hop: int, bins, max_lag: int,
+              weighting: int = BN_DELAY_PHAT, curve: bool = False, first: int = 0, count: Optional[int] = None):
+        """Recording::delay: (a DELAY_DTYPE array, the curves [n, 2 max_lag + 1] float32 or None) of windows [first, first + count)
+        (count None: to the last window both recordings have) of this recording against `other`; see Recording.delay."""
+        want = (1 << 64) - 1 if count is None else count
+        cap = max(int(lib.bn_chunk_count(min(self.n_samples, other.n_samples), step_samples)) if step_samples else 0, 0 if count is None else count, 1)
+        out = np.zeros(cap, dtype=DELAY_DTYPE)
+        cv, n_lags = _delay_curve(cap, max_lag, curve)
+        n, err = C.c_size_t(), BnhError()
+        sp = BnDelaySpec(frame, hop, bins[0], bins[1], max_lag, weighting)
+        if lib.bnh_recording_delay(self._h, other._h, segment_samples, step_samples, C.byref(sp), first, want, out.ctypes.data_as(C.POINTER(BnWindowDelay)),
+                                   cv.ctypes.data_as(C.POINTER(C.c_float)) if curve else None, cap, C.byref(n), C.byref(err)):
+            raise Error(err)
+        return out[:n.value].copy(), (cv[:n.value * n_lags].reshape(n.value, n_lags).copy() if curve else None)
 
     def filtered(self, taps) -> "HostRecording":
         """Recording::filtered: a new mono f32 recording, this one through the centred FIR filter `taps`."""
@@ -1704,6 +1759,25 @@ class Recording:
         if st:
             raise EngineError(st)
         return out, (pl[:-1].reshape(len(out), BN_PROFILE_PLANES, n_bins) if planes else None)
+
+    def delay(self, other: "Recording", segment_samples: int, step_samples: int, frame: int, hop: int, bins, max_lag: int,
+              weighting: int = BN_DELAY_PHAT, curve: bool = False, first: int = 0, count: Optional[int] = None):
+        """bn_recording_delay: per window the time difference of arrival between this recording (a) and `other` (b), e.g. two
+        view_channel()s of one upload, as a DELAY_DTYPE array (count None: to the last window both have): the cross-spectrum of the
+        windows' frames of `frame` samples every `hop`, summed over the window, restricted to bins = (bin_lo, bin_hi), whitened
+        (BN_DELAY_PHAT) or not (BN_DELAY_PLAIN), transformed back and searched over lags -max_lag .. +max_lag.  peak_lag > 0: the
+        sound reaches this recording later than `other`; delay_refine() gives the sub-sample lag.  With curve, also a float32 array
+        [n, 2 max_lag + 1] of every lag's value; None without.  Both recordings must take the same sample reader."""
+        count = int(lib.bn_chunk_count(min(self.n_samples, other.n_samples), step_samples)) - first if count is None else count
+        out = np.zeros(max(count, 0), dtype=DELAY_DTYPE)
+        cv, n_lags = _delay_curve(count, max_lag, curve)
+        sp = BnDelaySpec(frame, hop, bins[0], bins[1], max_lag, weighting)
+        st = lib.bn_recording_delay(self._h, other._h, segment_samples, step_samples, first, count, C.byref(sp), C.sizeof(BnDelaySpec),
+                                    out.ctypes.data_as(C.POINTER(BnWindowDelay)), C.sizeof(BnWindowDelay),
+                                    cv.ctypes.data_as(C.POINTER(C.c_float)) if curve else None)
+        if st:
+            raise EngineError(st)
+        return out, (cv[:-1].reshape(len(out), n_lags) if curve else None)
 
     def filtered(self, taps) -> "Recording":
         """bn_recording_create_filtered: a new mono f32 recording y[n] = sum_t taps[t] x[n + (len(taps) - 1) / 2 - t] of this one's

@@ -325,6 +325,21 @@ int32_t bnh_recording_spectral_profile(const bnh_recording *r, size_t segment_sa
     });
 }
 
+int32_t bnh_recording_delay(const bnh_recording *a, const bnh_recording *b, size_t segment_samples, size_t step_samples, const bn_delay_spec *spec,
+                            size_t first, size_t count, bn_window_delay *out, float *curve, size_t cap, size_t *n_out, bnh_error *err) {
+    if (n_out) *n_out = 0;
+    if (!a || !b) return set_other(err, "null recording");
+    if (!spec) return set_other(err, "null delay spec");
+    return guarded(err, [&] {
+        std::vector<float> lags;
+        const std::vector<bn_window_delay> dl = a->rec.delay(b->rec, segment_samples, step_samples, *spec, first, count, curve ? &lags : nullptr);
+        if (n_out) *n_out = dl.size();
+        const size_t n = std::min(cap, dl.size());
+        if (out) memcpy(out, dl.data(), n * sizeof(bn_window_delay));
+        if (curve && !dl.empty()) memcpy(curve, lags.data(), n * (lags.size() / dl.size()) * sizeof(float));
+    });
+}
+
 int32_t bnh_recording_filtered(const bnh_recording *r, const float *taps, size_t n_taps, bnh_recording **out, bnh_error *err) {
     if (!out) return set_other(err, "null argument");
     *out = nullptr;

@@ -381,6 +381,30 @@ std::vector<bn_window_profile> Recording::spectral_profile(size_t segment_sample
     return out;
 }
 
+std::vector<bn_window_delay> Recording::delay(const Recording &other, size_t segment_samples, size_t step_samples, const bn_delay_spec &spec, size_t first,
+                                              size_t count, std::vector<float> *curve) const {
+    if (count == (size_t)-1) {
+        const size_t total = bn_chunk_count(std::min(n_samples_, other.n_samples_), step_samples);
+        count = total > first ? total - first : 0;
+    }
+    // as levels(): a count the library refuses must reach it with a buffer.  The curve is sized only for a spec it will take
+    std::vector<bn_window_delay> out;
+    const size_t n_lags = spec.max_lag < 1024 ? 2 * (size_t)spec.max_lag + 1 : 0;
+    try {
+        if (count > (size_t)-1 / sizeof(float) / 2048) throw std::length_error("count");
+        out.resize(count);
+        if (curve) curve->assign(count * n_lags + 1, 0.0f);
+    } catch (const std::exception &) {
+        throw inference("window range exceeds the address space");
+    }
+    bn_window_delay none{};
+    if (bn_recording_delay(rec_.get(), other.rec_.get(), segment_samples, step_samples, first, count, &spec, sizeof(bn_delay_spec), count ? out.data() : &none,
+                           sizeof(bn_window_delay), curve ? curve->data() : nullptr) != BN_OK)
+        throw inference(last_backend_error());
+    if (curve) curve->resize(count * n_lags);
+    return out;
+}
+
 Recording Recording::filtered(const float *taps, size_t n_taps) const {
     bn_recording *r = nullptr;
     if (bn_recording_create_filtered(rec_.get(), taps, n_taps, &r) != BN_OK) throw inference("failed to filter the recording: " + last_backend_error());

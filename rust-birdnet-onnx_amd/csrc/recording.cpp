@@ -19,6 +19,7 @@
 
 #include "band_levels.h"
 #include "capi_internal.h"
+#include "delay.h"
 #include "denoise.h"
 #include "fir.h"
 #include "kernels.h"
@@ -283,14 +284,24 @@ bn_status recording_create_resampled(int32_t device, const void *pcm, size_t n_f
     return BN_OK;
 }
 
-// the refusals of a window range, without the wait of check_windows
-bn_status check_window_range(const bn_recording *r, size_t S, size_t step, size_t first, size_t count) {
-    if (!r) return fail(BN_ERR_INVALID_ARG, "null recording");
+// the refusals of a window range over n_samples samples, without the wait of check_windows
+bn_status check_window_range(size_t n_samples, size_t S, size_t step, size_t first, size_t count) {
     if (S == 0 || S % 4 != 0 || S > 0xffffffffull) return fail(BN_ERR_INVALID_ARG, "segment_samples must be a positive multiple of 4");
     if (step == 0) return fail(BN_ERR_INVALID_ARG, "step_samples must be positive (overlap shorter than the segment)");
-    const size_t total = bn_chunk_count(r->n_samples, step);
+    const size_t total = bn_chunk_count(n_samples, step);
     if (first > total || count > total - first) return fail(BN_ERR_INVALID_ARG, "window range [" + std::to_string(first) + ", " + std::to_string(first + count) + ") exceeds the " + std::to_string(total) + " windows of the recording");
     return BN_OK;
+}
+bn_status check_window_range(const bn_recording *r, size_t S, size_t step, size_t first, size_t count) {
+    if (!r) return fail(BN_ERR_INVALID_ARG, "null recording");
+    return check_window_range(r->n_samples, S, step, first, count);
+}
+
+// what bn_recording_delay's messages call the reader of a layout (wlist::reader_kind)
+const char *reader_name(int kind) {
+    static const char *const names[wlist::KINDS] = {"mono int16", "mono f32", "interleaved int16", "interleaved f32", "interleaved int24", "interleaved int32",
+                                                    "interleaved uint8"};
+    return kind >= 0 && kind < wlist::KINDS ? names[kind] : "unknown";
 }
 }  // namespace
 
@@ -564,6 +575,52 @@ bn_status bn_recording_spectral_profile(const bn_recording *r, size_t segment_sa
         return gated::Memcpy(out_bins + done * per, d_planes.get(), n * per * sizeof(float), hipMemcpyDeviceToHost);
     });
 }
+
+// ---- cross-channel delay (include/birdnet_hip.h, "bn_recording_delay"; kernel in delay.hip, arithmetic in delay_plan.h) ----
+bn_status bn_recording_delay(const bn_recording *a, const bn_recording *b, size_t segment_samples, size_t step_samples, size_t first_window, size_t count,
+                             const bn_delay_spec *spec, size_t spec_size, bn_window_delay *out, size_t struct_size, float *out_curve) {
+    if (struct_size < sizeof(bn_window_delay)) return fail(BN_ERR_INVALID_ARG, "struct_size is below sizeof(bn_window_delay)");
+    if (!a || !b) return fail(BN_ERR_INVALID_ARG, "null recording");
+    // a window exists where both recordings have a sample at its start
+    bn_status st = check_window_range(std::min(a->n_samples, b->n_samples), segment_samples, step_samples, first_window, count);
+    if (st != BN_OK) return st;
+    delay::Plan plan;
+    if ((st = delay::check_spec(spec, spec_size, segment_samples, &plan)) != BN_OK) return st;
+    if (a->device != b->device)
+        return fail(BN_ERR_INVALID_ARG, "the recordings live on devices " + std::to_string(a->device) + " and " + std::to_string(b->device));
+    const int kind_a = wlist::reader_kind(a->layout), kind_b = wlist::reader_kind(b->layout);
+    if (kind_a != kind_b)
+        return fail(BN_ERR_INVALID_ARG, std::string("the recordings are read as ") + reader_name(kind_a) + " and " + reader_name(kind_b) +
+                                            ", and the delay kernel takes one reader for both: bn_recording_create_filtered with the single tap 1.0 makes a mono "
+                                            "f32 copy of either");
+    if (count == 0) return BN_OK;
+    if (!out) return fail(BN_ERR_INVALID_ARG, "null output buffer");
+    size_t all_floats = 0;  // only asked whether it exists
+    if (out_curve && !delay::curve_floats(count, plan.n_lags, &all_floats)) return fail(BN_ERR_INVALID_ARG, "count * (2 max_lag + 1) floats do not fit a size_t");
+    // asynchronously uploaded recordings: the last sample any frame of these windows reads must have arrived, of both
+    for (const bn_recording *r : {a, b}) {
+        uint64_t last = 0;
+        if (delay::last_sample_read(r->n_samples, first_window + count - 1, step_samples, plan.span, &last) && !recording_wait_samples(r, (size_t)last))
+            return fail(BN_ERR_BACKEND, "recording upload failed");
+    }
+    BN_HIP_TRY(bn::use_device(a->device));
+    const float *tab = nullptr;
+    float scale = 0.0f;  // band levels' scale: the delay's own is the plan's
+    BN_HIP_TRY(band_tables(a->device, plan.N, &tab, &scale));
+    // one workgroup per window; a launch's curves, if wanted, are copied behind its records
+    const size_t piece = delay::piece_windows(plan.n_lags), per = plan.n_lags;
+    DeviceBuf<float> d_curve;
+    if (out_curve) BN_HIP_TRY(d_curve.alloc(std::min(piece, count) * per * sizeof(float)));
+    return rows_in_pieces<WindowDelay>("delay", "delay kernel failed: ", count, piece, out, struct_size, [&](size_t done, size_t n, WindowDelay *d) {
+        launch_delay(nullptr, d, out_curve ? d_curve.get() : nullptr, a->src(), a->n_samples, b->src(), b->n_samples,
+                     (uint64_t)(first_window + done) * step_samples, step_samples, (uint32_t)segment_samples, (uint32_t)n, plan, tab);
+    }, [&](size_t done, size_t n) {
+        if (!out_curve) return hipSuccess;
+        return gated::Memcpy(out_curve + done * per, d_curve.get(), n * per * sizeof(float), hipMemcpyDeviceToHost);
+    });
+}
+
+bn_status bn_delay_refine(const bn_window_delay *w, size_t struct_size, double *lag_out) { return delay::refine(w, struct_size, lag_out); }
 
 // ---- FIR filtering (include/birdnet_hip.h, "FIR filtering"; kernel in fir.hip, arithmetic in fir_plan.h) ----
 bn_status bn_recording_create_filtered(const bn_recording *src, const float *taps, size_t n_taps, bn_recording **out) {
