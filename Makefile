@@ -10,7 +10,7 @@ CXXFLAGS := -O3 -std=c++17 -fPIC -Wall -Wextra -Wno-unused-parameter -Iinclude
 # for the pairs with register moves (mbmap's depthwise phase: 120 v_pk_fma + 216 v_mov for 240 multiply-adds); on this part a packed
 # f32 instruction costs 1.56x a plain one (tools/mfma_valu_probe.cpp) and every vector instruction is paid out of the MFMA time
 HIPFLAGS := $(CXXFLAGS) --offload-arch=$(ARCH) -ffp-contract=off -fno-slp-vectorize
-OBJS := $(SRC)/onnx_proto.o $(SRC)/engine.o $(SRC)/onnx_rewrite.o $(SRC)/dft_bank.o $(SRC)/mbconv_fuse.o $(SRC)/plan_passes.o $(SRC)/detect.o $(SRC)/capi.o $(SRC)/recording.o $(SRC)/step_common.o $(SRC)/group.o $(SRC)/host_classifier.o $(SRC)/host_capi.o $(SRC)/host_rangefilter.o $(SRC)/kernels.o $(SRC)/topk.o $(SRC)/stft.o $(SRC)/mbrow.o $(SRC)/gemm_dma.o $(SRC)/gemm_dma3.o $(SRC)/gemm_b3.o $(SRC)/mbmap.o $(SRC)/mbmap_ws.o $(SRC)/index.o $(SRC)/head.o $(SRC)/rank.o $(SRC)/cluster.o $(SRC)/ivf.o $(SRC)/sq8.o $(SRC)/subset.o $(SRC)/index_copy.o $(SRC)/peaks.o $(SRC)/seq.o $(SRC)/above.o $(SRC)/group_above.o $(SRC)/match.o $(SRC)/index_io.o $(SRC)/index_file.o $(SRC)/prior.o $(SRC)/track.o $(SRC)/live.o $(SRC)/live_kernels.o $(SRC)/levels.o $(SRC)/band_levels.o $(SRC)/spectral_profile.o $(SRC)/fir.o $(SRC)/denoise.o $(SRC)/spectrogram.o $(SRC)/delay.o
+OBJS := $(SRC)/onnx_proto.o $(SRC)/engine.o $(SRC)/onnx_rewrite.o $(SRC)/dft_bank.o $(SRC)/mbconv_fuse.o $(SRC)/plan_passes.o $(SRC)/detect.o $(SRC)/capi.o $(SRC)/recording.o $(SRC)/step_common.o $(SRC)/group.o $(SRC)/host_classifier.o $(SRC)/host_capi.o $(SRC)/host_rangefilter.o $(SRC)/kernels.o $(SRC)/topk.o $(SRC)/stft.o $(SRC)/mbrow.o $(SRC)/gemm_dma.o $(SRC)/gemm_dma3.o $(SRC)/gemm_b3.o $(SRC)/mbmap.o $(SRC)/mbmap_ws.o $(SRC)/index.o $(SRC)/head.o $(SRC)/rank.o $(SRC)/cluster.o $(SRC)/ivf.o $(SRC)/sq8.o $(SRC)/subset.o $(SRC)/index_copy.o $(SRC)/peaks.o $(SRC)/seq.o $(SRC)/above.o $(SRC)/group_above.o $(SRC)/match.o $(SRC)/index_io.o $(SRC)/index_file.o $(SRC)/prior.o $(SRC)/track.o $(SRC)/live.o $(SRC)/live_kernels.o $(SRC)/levels.o $(SRC)/band_levels.o $(SRC)/spectral_profile.o $(SRC)/fir.o $(SRC)/denoise.o $(SRC)/spectrogram.o $(SRC)/delay.o $(SRC)/template.o
 
 all: $(OUT) oracle
 
@@ -86,6 +86,10 @@ tools/asan_profile_plan: tools/asan_profile_plan.cpp $(SRC)/profile_plan.h $(SRC
 # peak key against the tie rule, the curve's sizes, bn_delay_refine
 tools/asan_delay_plan: tools/asan_delay_plan.cpp $(SRC)/delay_plan.h $(SRC)/profile_plan.h $(SRC)/band_plan.h $(SRC)/last_error.h include/birdnet_hip.h
 	$(CXX) $(ASAN_FLAGS) $< -o $@
+# ... of template matching's arithmetic: the caps, the output and image sizes at extreme n_offsets, the launch pieces and their overlap, the
+# packed templates against a direct index formula with T1 and dT, the B operand's walk through LDS, bn_template_peaks
+tools/asan_template_plan: tools/asan_template_plan.cpp $(SRC)/template_plan.h $(SRC)/spectrogram_plan.h $(SRC)/band_plan.h $(SRC)/plan_rules.h $(SRC)/last_error.h include/birdnet_hip.h
+	$(CXX) $(ASAN_FLAGS) -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include $< -o $@
 # ... of the noise reduction's arithmetic: spec and noise refusals, every (frame, register, lane) position the kernel reads or stores for
 # ragged lengths, the register shift, the window table, bn_noise_floor's selection
 tools/asan_denoise_plan: tools/asan_denoise_plan.cpp $(SRC)/denoise_plan.h $(SRC)/band_plan.h $(SRC)/last_error.h include/birdnet_hip.h

@@ -856,6 +856,69 @@ bn_status bn_recording_delay(const bn_recording *a, const bn_recording *b, size_
 bn_status bn_delay_refine(const bn_window_delay *w, size_t struct_size, double *lag_out);
 
 /*
+ * Template matching: spectrogram cross-correlation against example calls, at frame granularity.  A template is a cut of what
+ * bn_recording_spectrogram(..., BN_SPECTROGRAM_U8) wrote for an example: W_q consecutive frames of R = n_rows codes, time-major.
+ * bn_templates_create packs and uploads up to BN_TEMPLATE_MAX_COUNT of them, of any lengths, once.
+ * bn_recording_template_match writes score[q][t], the Pearson correlation of template q with the W_q frames of the recording's
+ * code image from frame offset t on, for t < n_offsets, dense at out_scores[q * n_offsets + t].  Everything up to the final
+ * quotient is exact integer arithmetic on the codes, so the score is a function of the code image alone.
+ *
+ * Image.  C[t][j] is the byte bn_recording_spectrogram stores for frame t, row j of the range that starts at first_sample, with
+ * this spec (its format must be BN_SPECTROGRAM_U8) and bank: rows are a bin range or the bank's.  Frames run over
+ * t = 0 .. n_offsets + Wmax - 2, Wmax = bn_templates_max_frames(tpl).  Frames past the recording's end are code 0 and a frame that
+ * reads a non-finite sample is code 255 in every row, as that call defines them: the match reads that image and nothing else.
+ * Sums.  s = C - 128 and tau = T_q - 128, both exact in int8.  K = W_q * R counts the template's true elements.  For offset t, over
+ * w < W_q and j < R:
+ *   A = sum tau[w][j] s[t + w][j],   S1 = sum s[t + w][j],   S2 = sum s[t + w][j]^2;   per template T1 = sum tau, T2 = sum tau^2.
+ *   num = K A - T1 S1,   dT = K T2 - T1^2,   dS = K S2 - S1^2          (int64; the caps keep |A|, S2 <= 2^30 and dT, dS <= 2^46)
+ * Score.  score = (float)((double)num / sqrt((double)dT * (double)dS)), each operation in IEEE double.  dS == 0 gives +0.0f: a flat
+ * window, such as silence, correlates with nothing.  A template with dT == 0 is refused at creation.  The score lies in [-1, 1];
+ * the shift by 128 cancels.
+ * Invariance.  score[q][t] depends only on the codes of frames t .. t + W_q - 1 and on template q: not on n_offsets, on the other
+ * templates of the set, on where the offset falls in a tile or a launch piece, nor on how a range is split into calls -- offset t
+ * of a call at first_sample + d * hop is offset t + d of the call at first_sample, byte for byte.
+ *
+ * The call blocks on an asynchronous upload until the last sample it reads has arrived, and returns when out_scores is written.
+ * BN_ERR_INVALID_ARG, with a message, nothing enqueued and nothing written: whatever bn_recording_spectrogram refuses about r,
+ * spec, spec_size, bank and first_sample; a format other than BN_SPECTROGRAM_U8; a NULL tpl or out_scores; templates on another
+ * device than the recording; bn_templates_rows(tpl) different from the spec's or the bank's row count; out_floats below
+ * n_templates * n_offsets (formed without wrapping).  n_offsets == 0 is BN_OK.
+ * bn_templates_create refuses (BN_ERR_INVALID_ARG, no handle written, the message naming the first offender) a NULL argument,
+ * n_templates outside 1 .. BN_TEMPLATE_MAX_COUNT, n_rows outside 1 .. BN_TEMPLATE_MAX_ROWS, a template of 0 or more than
+ * BN_TEMPLATE_MAX_FRAMES frames or more than BN_TEMPLATE_MAX_ELEMS elements, a template with dT == 0 (every code the same).
+ * bn_templates_count / _rows / _max_frames of NULL are 0.
+ *
+ * bn_template_peaks (host only, no device): offset t of template q is a hit when score >= min_score and every other offset u of
+ * that template with 0 < |t - u| <= peak_radius comes AFTER t in the order "score descending, ties by offset ascending" --
+ * bn_index_search_peaks' rule, not greedy suppression.  A NaN is never a hit and never suppresses.  Hits are written template
+ * ascending, then offset ascending, struct_size bytes apart, up to cap; *n_out is the total even where it exceeds cap.
+ * BN_ERR_INVALID_ARG: a NULL scores (with anything to read), out (with cap > 0) or n_out, a struct_size below the struct's, a NaN
+ * min_score.
+ */
+#define BN_TEMPLATE_MAX_COUNT 64     /* templates of one set */
+#define BN_TEMPLATE_MAX_FRAMES 128   /* frames of one template */
+#define BN_TEMPLATE_MAX_ROWS 512     /* rows of the image */
+#define BN_TEMPLATE_MAX_ELEMS 65536  /* frames * rows of one template: keeps every i32 sum below 2^31 */
+typedef struct bn_templates bn_templates;
+bn_status bn_templates_create(int32_t device, size_t n_templates, size_t n_rows, const uint32_t *n_frames /* [n_templates] */,
+                              const uint8_t *codes /* the templates one after another, each time-major n_frames[q] x n_rows */,
+                              bn_templates **out);
+void bn_templates_free(bn_templates *t);
+size_t bn_templates_count(const bn_templates *t);
+size_t bn_templates_rows(const bn_templates *t);
+size_t bn_templates_max_frames(const bn_templates *t);
+bn_status bn_recording_template_match(const bn_recording *r, size_t first_sample, size_t n_offsets, const bn_spectrogram_spec *spec,
+                                      size_t spec_size, const bn_filterbank *bank, const bn_templates *tpl,
+                                      float *out_scores /* [n_templates][n_offsets] */, size_t out_floats);
+typedef struct bn_template_hit {
+    uint64_t offset;
+    uint32_t template_index;
+    float score;
+} bn_template_hit;
+bn_status bn_template_peaks(const float *scores, size_t n_templates, size_t n_offsets, float min_score, size_t peak_radius,
+                            bn_template_hit *out, size_t cap, size_t struct_size, size_t *n_out);
+
+/*
  * bn_step_window_list: bn_step_windows over an explicit list.  Row i of the batch is the S = sample_count frames of
  * refs[i].recording from frame refs[i].start on, zeros past the end; start is any frame of the recording, no multiple of any step
  * (a window centred on a peak is fine).  The rows are gathered on the device straight into the context's input buffer -- the

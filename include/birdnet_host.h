@@ -211,6 +211,20 @@ class Filterbank {
     std::shared_ptr<bn_filterbank> bank_;
 };
 
+/* bn_templates: a set of U8 spectrogram cuts matched by Recording::template_match, packed and uploaded once (birdnet_hip.h, "Template
+ * matching").  Throws Error::Inference with the library's message on a refusal. */
+class Templates {
+   public:
+    Templates(size_t n_templates, size_t n_rows, const uint32_t *n_frames, const uint8_t *codes, int device = 0);
+    size_t count() const;
+    size_t rows() const;
+    size_t max_frames() const;
+    const bn_templates *raw() const { return tpl_.get(); }
+
+   private:
+    std::shared_ptr<bn_templates> tpl_;
+};
+
 /* A mono recording uploaded to the device once, in its storage format: the native form of the
  * reference CLI's read_wav (i16 / 32768.0, src/bin/birdnet-analyze.rs:683-687) + chunk_audio
  * (:707-743).  Windows are cut on the device (bn_infer_windows). */
@@ -256,6 +270,10 @@ class Recording {
      * rows being spec's bins or, with a bank, the bank's (birdnet_hip.h, "Spectrograms").  Throws Error::Inference with the library's
      * message on a refusal. */
     void spectrogram(size_t first_sample, size_t n_frames, const bn_spectrogram_spec &spec, const Filterbank *bank, void *out, size_t out_bytes) const;
+    /* bn_recording_template_match: the [template][offset] correlation scores of n_offsets frame offsets from first_sample on, over the
+     * U8 image of `spec` and `bank` (birdnet_hip.h, "Template matching"); bn_template_peaks picks the hits.  Throws Error::Inference
+     * with the library's message on a refusal. */
+    std::vector<float> template_match(size_t first_sample, size_t n_offsets, const bn_spectrogram_spec &spec, const Filterbank *bank, const Templates &tpl) const;
     size_t n_samples() const { return n_samples_; }
     const bn_recording *raw() const { return rec_.get(); }
 
@@ -587,6 +605,15 @@ void bnh_filterbank_free(bnh_filterbank *b);
 size_t bnh_filterbank_rows(const bnh_filterbank *b);
 int32_t bnh_recording_spectrogram(const bnh_recording *r, size_t first_sample, size_t n_frames, const bn_spectrogram_spec *spec,
                                   const bnh_filterbank *bank, void *out, size_t out_bytes, bnh_error *err);
+/* class Templates and Recording::template_match; bank may be NULL (bin rows); out takes n_templates * n_offsets floats (out_floats of room) */
+typedef struct bnh_templates bnh_templates;
+int32_t bnh_templates_create(size_t n_templates, size_t n_rows, const uint32_t *n_frames, const uint8_t *codes, int32_t device, bnh_templates **out,
+                             bnh_error *err);
+void bnh_templates_free(bnh_templates *t);
+size_t bnh_templates_count(const bnh_templates *t);
+size_t bnh_templates_max_frames(const bnh_templates *t);
+int32_t bnh_recording_template_match(const bnh_recording *r, size_t first_sample, size_t n_offsets, const bn_spectrogram_spec *spec,
+                                     const bnh_filterbank *bank, const bnh_templates *tpl, float *out, size_t out_floats, bnh_error *err);
 /* row i: recordings[i] from frame starts[i]; sources / windows may be NULL (0 and the row's position) */
 int32_t bnh_predict_window_list(const bnh_classifier *c, bnh_context *ctx, const bnh_recording *const *recordings, const uint64_t *starts,
                                 const int32_t *sources, const uint64_t *windows, size_t n, int64_t timeout_ns, const volatile int32_t *cancel,

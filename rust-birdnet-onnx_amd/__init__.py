@@ -60,6 +60,8 @@ ENGINE_SYMBOLS = [
     "bn_recording_create_filtered", "bn_fir_bandpass", "bn_recording_create_denoised", "bn_noise_floor",
     "bn_recording_spectrogram", "bn_filterbank_create", "bn_filterbank_free", "bn_filterbank_rows", "bn_filterbank_frame", "bn_mel_filterbank",
     "bn_spectrogram_thresholds", "bn_recording_delay", "bn_delay_refine",
+    "bn_templates_create", "bn_templates_free", "bn_templates_count", "bn_templates_rows", "bn_templates_max_frames", "bn_recording_template_match",
+    "bn_template_peaks",
     "bn_index_create", "bn_index_free", "bn_index_size", "bn_index_dim", "bn_index_add_host", "bn_index_add_ctx", "bn_index_read",
     "bn_index_search", "bn_index_search_ids", "bn_index_assign", "bn_index_cluster",
     "bn_index_save", "bn_index_load", "bn_index_file_info", "bn_index_file_verify",
@@ -101,6 +103,7 @@ HOST_SYMBOLS = [
     "bnh_recording_band_levels", "bnh_recording_spectral_profile", "bnh_recording_filtered", "bnh_recording_denoised", "bnh_noise_floor",
     "bnh_recording_spectrogram", "bnh_filterbank_create", "bnh_filterbank_free", "bnh_filterbank_rows",
     "bnh_recording_delay",
+    "bnh_templates_create", "bnh_templates_free", "bnh_templates_count", "bnh_templates_max_frames", "bnh_recording_template_match",
 ]
 
 
@@ -357,6 +360,78 @@ class Filterbank:
             self._h = None
 
 
+BN_TEMPLATE_MAX_COUNT, BN_TEMPLATE_MAX_FRAMES, BN_TEMPLATE_MAX_ROWS, BN_TEMPLATE_MAX_ELEMS = 64, 128, 512, 65536  # include/birdnet_hip.h
+
+
+class BnTemplateHit(C.Structure):
+    _fields_ = [("offset", C.c_uint64), ("template_index", C.c_uint32), ("score", C.c_float)]
+
+
+TEMPLATE_HIT_DTYPE = np.dtype([("offset", np.uint64), ("template_index", np.uint32), ("score", np.float32)])
+
+
+def _template_args(templates):
+    """(n_templates, n_rows, n_frames, codes) of a list of [frames, n_rows] uint8 arrays, as bn_templates_create takes them"""
+    cuts = [np.ascontiguousarray(t, dtype=np.uint8) for t in templates]
+    if any(t.ndim != 2 for t in cuts) or len({t.shape[1] for t in cuts}) > 1:
+        raise ValueError("templates must be [frames, n_rows] arrays of one n_rows")
+    n_frames = np.array([t.shape[0] for t in cuts], dtype=np.uint32)
+    codes = np.concatenate([t.reshape(-1) for t in cuts] + [np.zeros(1, dtype=np.uint8)])
+    return len(cuts), cuts[0].shape[1] if cuts else 0, n_frames, codes
+
+
+class Templates:
+    """bn_templates: up to 64 cuts of U8 spectrograms (Recording.spectrogram(..., u8=...)), each [frames, n_rows] with one n_rows,
+    packed and uploaded once for Recording.template_match."""
+
+    def __init__(self, device: int, templates):
+        n, rows, n_frames, codes = _template_args(templates)
+        h = C.c_void_p()
+        st = lib.bn_templates_create(device, n, rows, n_frames.ctypes.data_as(C.POINTER(C.c_uint32)), codes.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(h))
+        if st:
+            raise EngineError(st)
+        self._h, self.device, self.n_templates, self.n_rows = h, device, int(lib.bn_templates_count(h)), int(lib.bn_templates_rows(h))
+        self.max_frames = int(lib.bn_templates_max_frames(h))
+
+    def __del__(self):
+        if getattr(self, "_h", None) and lib is not None:
+            lib.bn_templates_free(self._h)
+            self._h = None
+
+
+class HostTemplates:
+    """birdnet::Templates: Templates through the host mirror, for HostRecording.template_match."""
+
+    def __init__(self, templates, device: int = 0):
+        n, rows, n_frames, codes = _template_args(templates)
+        h, err = C.c_void_p(), BnhError()
+        if lib.bnh_templates_create(n, rows, n_frames.ctypes.data_as(C.POINTER(C.c_uint32)), codes.ctypes.data_as(C.POINTER(C.c_uint8)), device, C.byref(h),
+                                    C.byref(err)):
+            raise Error(err)
+        self._h, self.n_templates, self.n_rows, self.max_frames = h, int(lib.bnh_templates_count(h)), rows, int(lib.bnh_templates_max_frames(h))
+
+    def __del__(self):
+        if getattr(self, "_h", None) and lib is not None:
+            lib.bnh_templates_free(self._h)
+            self._h = None
+
+
+def template_peaks(scores, min_score: float, peak_radius: int, cap: Optional[int] = None) -> np.ndarray:
+    """bn_template_peaks: the hits of a [n_templates, n_offsets] float32 score array as a TEMPLATE_HIT_DTYPE array, template then
+    offset ascending: offsets scoring at least min_score that no other offset within peak_radius beats (score descending, ties by
+    offset ascending).  With cap, at most cap of them.  Host only."""
+    s = np.ascontiguousarray(scores, dtype=np.float32)
+    if s.ndim != 2:
+        raise ValueError("scores must be [n_templates, n_offsets]")
+    room = s.size if cap is None else cap
+    out, n = np.zeros(max(room, 1), dtype=TEMPLATE_HIT_DTYPE), C.c_size_t(0)
+    st = lib.bn_template_peaks(s.ctypes.data_as(C.POINTER(C.c_float)), s.shape[0], s.shape[1], min_score, peak_radius, out.ctypes.data_as(C.POINTER(BnTemplateHit)),
+                               room, C.sizeof(BnTemplateHit), C.byref(n))
+    if st:
+        raise EngineError(st)
+    return out[: min(n.value, room)]
+
+
 class HostFilterbank:
     """birdnet::Filterbank: a Filterbank through the host mirror, for HostRecording.spectrogram."""
 
@@ -480,6 +555,13 @@ def _load() -> C.CDLL:
         "bn_noise_floor": (i32, [C.POINTER(C.c_float), sz, sz, C.c_double, C.POINTER(C.c_float)]),
         "bn_recording_delay": (i32, [vp, vp, sz, sz, sz, sz, C.POINTER(BnDelaySpec), sz, C.POINTER(BnWindowDelay), sz, C.POINTER(C.c_float)]),
         "bn_delay_refine": (i32, [C.POINTER(BnWindowDelay), sz, C.POINTER(C.c_double)]),
+        "bn_templates_create": (i32, [i32, sz, sz, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.POINTER(vp)]),
+        "bn_templates_free": (None, [vp]),
+        "bn_templates_count": (sz, [vp]),
+        "bn_templates_rows": (sz, [vp]),
+        "bn_templates_max_frames": (sz, [vp]),
+        "bn_recording_template_match": (i32, [vp, sz, sz, C.POINTER(BnSpectrogramSpec), sz, vp, vp, C.POINTER(C.c_float), sz]),
+        "bn_template_peaks": (i32, [C.POINTER(C.c_float), sz, sz, C.c_float, sz, C.POINTER(BnTemplateHit), sz, sz, C.POINTER(sz)]),
         "bn_recording_spectrogram": (i32, [vp, sz, sz, C.POINTER(BnSpectrogramSpec), sz, vp, vp, sz]),
         "bn_filterbank_create": (i32, [i32, C.c_uint32, sz, C.POINTER(C.c_float), C.POINTER(vp)]),
         "bn_filterbank_free": (None, [vp]),
@@ -668,6 +750,11 @@ def _load() -> C.CDLL:
         "bnh_noise_floor": (i32, [C.POINTER(C.c_float), sz, sz, C.c_double, C.POINTER(C.c_float), C.POINTER(BnhError)]),
         "bnh_recording_delay": (i32, [vp, vp, sz, sz, C.POINTER(BnDelaySpec), sz, sz, C.POINTER(BnWindowDelay), C.POINTER(C.c_float), sz, C.POINTER(sz),
                                       C.POINTER(BnhError)]),
+        "bnh_templates_create": (i32, [sz, sz, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), i32, C.POINTER(vp), C.POINTER(BnhError)]),
+        "bnh_templates_free": (None, [vp]),
+        "bnh_templates_count": (sz, [vp]),
+        "bnh_templates_max_frames": (sz, [vp]),
+        "bnh_recording_template_match": (i32, [vp, sz, sz, C.POINTER(BnSpectrogramSpec), vp, vp, C.POINTER(C.c_float), sz, C.POINTER(BnhError)]),
         "bnh_recording_spectrogram": (i32, [vp, sz, sz, C.POINTER(BnSpectrogramSpec), vp, vp, sz, C.POINTER(BnhError)]),
         "bnh_filterbank_create": (i32, [C.c_uint32, sz, C.POINTER(C.c_float), i32, C.POINTER(vp), C.POINTER(BnhError)]),
         "bnh_filterbank_free": (None, [vp]),
@@ -1135,6 +1222,16 @@ class HostRecording:
                                          out.nbytes - out.itemsize, C.byref(err)):
             raise Error(err)
         return out[:-1].reshape(n_frames, n_rows)
+
+    def template_match(self, first: int, n_offsets: int, frame: int, hop: int, templates: "HostTemplates", bins=None, bank=None, u8=(1.0, 80.0)) -> np.ndarray:
+        """Recording::template_match: the [n_templates, n_offsets] scores of Recording.template_match; templates is a HostTemplates,
+        bank a HostFilterbank."""
+        sp, _, _ = _spectrogram_call(0, frame, hop, bins, bank, u8)
+        out, err = np.zeros(templates.n_templates * max(n_offsets, 0) + 1, dtype=np.float32), BnhError()
+        if lib.bnh_recording_template_match(self._h, first, n_offsets, C.byref(sp), bank._h if bank is not None else None, templates._h,
+                                            out.ctypes.data_as(C.POINTER(C.c_float)), out.size - 1, C.byref(err)):
+            raise Error(err)
+        return out[:-1].reshape(templates.n_templates, n_offsets)
 
 
 class LiveSources:
@@ -1818,6 +1915,23 @@ class Recording:
         if st:
             raise EngineError(st)
         return out[:-1].reshape(n_frames, n_rows)
+
+    def template_match(self, first: int, n_offsets: int, frame: int, hop: int, templates: "Templates", bins=None, bank=None, u8=(1.0, 80.0),
+                       out: Optional[np.ndarray] = None) -> np.ndarray:
+        """bn_recording_template_match: the Pearson correlation of every template of `templates` (a Templates set of cuts of such an
+        image) with the uint8 image spectrogram(first, n_offsets + max_frames - 1, frame, hop, bins, bank, u8) at each of n_offsets
+        frame offsets, computed on the device from exact integer sums, as an [n_templates, n_offsets] float32 array: score[q][t]
+        covers frames t .. t + frames_q - 1.  A flat window scores +0.0.  template_peaks() picks the hits.  `out`, if given, is the
+        caller's contiguous float32 buffer of at least n_templates * n_offsets elements (left untouched on a refusal)."""
+        sp, _, _ = _spectrogram_call(0, frame, hop, bins, bank, u8)
+        n = templates.n_templates * max(n_offsets, 0)
+        buf = np.zeros(n + 1, dtype=np.float32) if out is None else out
+        st = lib.bn_recording_template_match(self._h, first, n_offsets, C.byref(sp), C.sizeof(BnSpectrogramSpec), bank._h if bank is not None else None,
+                                             templates._h if templates is not None else None, buf.ctypes.data_as(C.POINTER(C.c_float)),
+                                             n if out is None else out.size)
+        if st:
+            raise EngineError(st)
+        return buf[:n].reshape(templates.n_templates, n_offsets)
 
 
 class Index:

@@ -380,6 +380,30 @@ int32_t bnh_recording_spectrogram(const bnh_recording *r, size_t first_sample, s
     return guarded(err, [&] { r->rec.spectrogram(first_sample, n_frames, *spec, bank ? &bank->bank : nullptr, out, out_bytes); });
 }
 
+struct bnh_templates {
+    Templates tpl;
+};
+int32_t bnh_templates_create(size_t n_templates, size_t n_rows, const uint32_t *n_frames, const uint8_t *codes, int32_t device, bnh_templates **out, bnh_error *err) {
+    if (!out) return set_other(err, "null argument");
+    *out = nullptr;
+    return guarded(err, [&] { *out = new bnh_templates{Templates(n_templates, n_rows, n_frames, codes, device)}; });
+}
+void bnh_templates_free(bnh_templates *t) { delete t; }
+size_t bnh_templates_count(const bnh_templates *t) { return t ? t->tpl.count() : 0; }
+size_t bnh_templates_max_frames(const bnh_templates *t) { return t ? t->tpl.max_frames() : 0; }
+
+int32_t bnh_recording_template_match(const bnh_recording *r, size_t first_sample, size_t n_offsets, const bn_spectrogram_spec *spec, const bnh_filterbank *bank,
+                                     const bnh_templates *tpl, float *out, size_t out_floats, bnh_error *err) {
+    if (!r) return set_other(err, "null recording");
+    if (!spec) return set_other(err, "null spectrogram spec");
+    if (!tpl || !out) return set_other(err, "null argument");
+    if (n_offsets && out_floats / n_offsets < tpl->tpl.count()) return set_other(err, "out_floats is below the scores of the match");
+    return guarded(err, [&] {
+        const std::vector<float> sc = r->rec.template_match(first_sample, n_offsets, *spec, bank ? &bank->bank : nullptr, tpl->tpl);
+        if (!sc.empty()) memcpy(out, sc.data(), sc.size() * sizeof(float));
+    });
+}
+
 int32_t bnh_predict_window_list(const bnh_classifier *c, bnh_context *ctx, const bnh_recording *const *recordings, const uint64_t *starts,
                                 const int32_t *sources, const uint64_t *windows, size_t n, int64_t timeout_ns, const volatile int32_t *cancel,
                                 bnh_results **out, bnh_error *err) {

@@ -436,6 +436,27 @@ void Recording::spectrogram(size_t first_sample, size_t n_frames, const bn_spect
         throw inference(last_backend_error());
 }
 
+Templates::Templates(size_t n_templates, size_t n_rows, const uint32_t *n_frames, const uint8_t *codes, int device) {
+    bn_templates *t = nullptr;
+    if (bn_templates_create(device, n_templates, n_rows, n_frames, codes, &t) != BN_OK) throw inference("failed to create the templates: " + last_backend_error());
+    tpl_ = std::shared_ptr<bn_templates>(t, [](bn_templates *p) { bn_templates_free(p); });
+}
+
+size_t Templates::count() const { return bn_templates_count(tpl_.get()); }
+size_t Templates::rows() const { return bn_templates_rows(tpl_.get()); }
+size_t Templates::max_frames() const { return bn_templates_max_frames(tpl_.get()); }
+
+std::vector<float> Recording::template_match(size_t first_sample, size_t n_offsets, const bn_spectrogram_spec &spec, const Filterbank *bank, const Templates &tpl) const {
+    // a count the library will refuse is not allocated first: one float of room lets it say why
+    const bool fits = n_offsets <= ((size_t)1 << 40) / BN_TEMPLATE_MAX_COUNT;
+    std::vector<float> out(fits ? std::max<size_t>(tpl.count() * n_offsets, 1) : 1);
+    if (bn_recording_template_match(rec_.get(), first_sample, n_offsets, &spec, sizeof(bn_spectrogram_spec), bank ? bank->raw() : nullptr, tpl.raw(), out.data(),
+                                    out.size()) != BN_OK)
+        throw inference(last_backend_error());
+    out.resize(tpl.count() * n_offsets);
+    return out;
+}
+
 std::vector<ChunkResult> Classifier::predict_recording(BatchInferenceContext &ctx, const Recording &rec, float overlap_secs, size_t first_chunk, size_t count,
                                                        const InferenceOptions &options) const {
     const ModelConfig &cfg = inner_->config;

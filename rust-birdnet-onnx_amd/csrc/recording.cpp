@@ -1,5 +1,5 @@
 // Recordings of the C ABI (include/birdnet_hip.h): bn_recording_*, the resampler's table, FIR filtering, noise reduction, spectrograms and their
-// filter banks, and the explicit window lists
+// filter banks, template matching, and the explicit window lists
 // (bn_recording_window_list, bn_step_window_list: of a context they need what bn_step_live does).  bn_recording is private to this
 // file; capi.cpp's bn_infer_windows and bn_step_windows reach a recording through check_windows and enqueue_windows (capi_internal.h).
 // Every launch is clear_launch_state, the launcher, check_launch; results reach the host through launch_and_read or rows_in_pieces.
@@ -26,6 +26,7 @@
 #include "levels.h"
 #include "spectral_profile.h"
 #include "spectrogram.h"
+#include "template.h"
 #include "window_list_plan.h"
 
 using namespace bn;
@@ -74,6 +75,13 @@ struct bn_filterbank {
     const void *image() const { return d.get() + sizeof(spectro::BankTiles); }
 };
 static_assert(sizeof(spectro::BankTiles) % 16 == 0, "the fragments behind the table are read 16 bytes at a time");
+// A set of templates: per template what the finish needs (template_plan.h, Meta), then the packed A operand of their codes
+struct bn_templates {
+    int32_t device = 0;
+    DeviceBuf<uint8_t> d;
+    TemplateSet set{};  // points into d
+};
+static_assert(sizeof(tmatch::Meta) == 24 && (tmatch::TILE_TEMPLATES * sizeof(tmatch::Meta)) % 16 == 0, "the fragments behind the table are read 16 bytes at a time");
 
 namespace {
 bn_status fail(bn_status st, const std::string &msg) { return set_last_error(st, msg); }
@@ -689,15 +697,44 @@ bn_status bn_noise_floor(const float *profile_bins, size_t count, size_t n_bins,
 }
 
 // ---- spectrograms (include/birdnet_hip.h, "Spectrograms"; kernels in spectrogram.hip, arithmetic in spectrogram_plan.h) ----
-bn_status bn_recording_spectrogram(const bn_recording *r, size_t first_sample, size_t n_frames, const bn_spectrogram_spec *spec, size_t spec_size,
-                                   const bn_filterbank *bank, void *out, size_t out_bytes) {
+namespace {
+// what bn_recording_spectrogram and bn_recording_template_match refuse about r, spec, spec_size, bank and first_sample; else the plan
+bn_status spectrogram_plan(const bn_recording *r, size_t first_sample, const bn_spectrogram_spec *spec, size_t spec_size, const bn_filterbank *bank,
+                           spectro::Plan *plan) {
     if (!r) return fail(BN_ERR_INVALID_ARG, "null recording");
-    spectro::Plan plan;
-    if (bn_status st = spectro::check_spec(spec, spec_size, bank ? bank->n_rows : 0, bank ? bank->frame : 0, &plan); st != BN_OK) return st;
+    if (bn_status st = spectro::check_spec(spec, spec_size, bank ? bank->n_rows : 0, bank ? bank->frame : 0, plan); st != BN_OK) return st;
     if (bank && bank->device != r->device)
         return fail(BN_ERR_INVALID_ARG, "the filter bank lives on device " + std::to_string(bank->device) + ", the recording on device " + std::to_string(r->device));
     if (first_sample > r->n_samples)
         return fail(BN_ERR_INVALID_ARG, "first_sample " + std::to_string(first_sample) + " is past the " + std::to_string(r->n_samples) + " samples of the recording");
+    return BN_OK;
+}
+
+// What every launch of a plan's spectrogram takes besides the range, made ready on the recording's device (the current one from here
+// on): band levels' tables, the LDS opt-in of frame 2048, the thresholds of the U8 codes
+struct SpectrogramTables {
+    const float *tab = nullptr;
+    float scale = 0.0f;
+    DeviceBuf<float> d_thr;
+    bn_status prepare(const bn_recording *r, const spectro::Plan &plan) {
+        BN_HIP_TRY(bn::use_device(r->device));
+        BN_HIP_TRY(band_tables(r->device, plan.N, &tab, &scale));
+        if (plan.N == band::FRAME_MAX) BN_HIP_TRY(spectrogram_prepare(r->device));
+        if (plan.format == BN_SPECTROGRAM_U8) {
+            float thr[spectro::N_THR];
+            if (bn_status st = spectro::thresholds(plan.ref_power, plan.range_db, thr); st != BN_OK) return st;
+            BN_HIP_TRY(d_thr.alloc(sizeof(thr)));
+            BN_HIP_TRY(gated::Memcpy(d_thr, thr, sizeof(thr), hipMemcpyHostToDevice));
+        }
+        return BN_OK;
+    }
+};
+}  // namespace
+
+bn_status bn_recording_spectrogram(const bn_recording *r, size_t first_sample, size_t n_frames, const bn_spectrogram_spec *spec, size_t spec_size,
+                                   const bn_filterbank *bank, void *out, size_t out_bytes) {
+    spectro::Plan plan;
+    if (bn_status st = spectrogram_plan(r, first_sample, spec, spec_size, bank, &plan); st != BN_OK) return st;
     size_t need = 0;
     if (!spectro::out_bytes(n_frames, plan.n_rows, plan.elem, &need)) return fail(BN_ERR_INVALID_ARG, "n_frames * n_rows elements do not fit a size_t");
     if (n_frames == 0) return BN_OK;
@@ -707,18 +744,8 @@ bn_status bn_recording_spectrogram(const bn_recording *r, size_t first_sample, s
     uint64_t last = 0;
     if (spectro::last_sample_read(r->n_samples, first_sample, n_frames, plan.N, plan.hop, &last) && !recording_wait_samples(r, (size_t)last))
         return fail(BN_ERR_BACKEND, "recording upload failed");
-    BN_HIP_TRY(bn::use_device(r->device));
-    const float *tab = nullptr;
-    float scale = 0.0f;
-    BN_HIP_TRY(band_tables(r->device, plan.N, &tab, &scale));
-    if (plan.N == band::FRAME_MAX) BN_HIP_TRY(spectrogram_prepare(r->device));
-    DeviceBuf<float> d_thr;
-    if (plan.format == BN_SPECTROGRAM_U8) {
-        float thr[spectro::N_THR];
-        if (bn_status st = spectro::thresholds(plan.ref_power, plan.range_db, thr); st != BN_OK) return st;
-        BN_HIP_TRY(d_thr.alloc(sizeof(thr)));
-        BN_HIP_TRY(gated::Memcpy(d_thr, thr, sizeof(thr), hipMemcpyHostToDevice));
-    }
+    SpectrogramTables tb;
+    if (bn_status st = tb.prepare(r, plan); st != BN_OK) return st;
     // whole tiles of 16 frames per launch, read back piece by piece
     const size_t piece = spectro::piece_frames(plan.n_rows), per = (size_t)plan.n_rows * plan.elem;
     DeviceBuf<uint8_t> d;
@@ -726,12 +753,89 @@ bn_status bn_recording_spectrogram(const bn_recording *r, size_t first_sample, s
     for (size_t done = 0; done < n_frames; done += piece) {
         const size_t n = std::min(piece, n_frames - done);
         bn_status st = launch_and_read("spectrogram", "spectrogram kernel failed: ", static_cast<char *>(out) + done * per, d, n * per, [&] {
-            launch_spectrogram(nullptr, d.get(), r->src(), r->n_samples, spectro::frame_start(r->n_samples, first_sample, done, plan.hop), (uint32_t)n, plan, tab,
-                               scale, d_thr.get(), bank ? bank->image() : nullptr, bank ? bank->tiles() : nullptr, bank ? bank->n_tiles : 0);
+            launch_spectrogram(nullptr, d.get(), r->src(), r->n_samples, spectro::frame_start(r->n_samples, first_sample, done, plan.hop), (uint32_t)n, plan, tb.tab,
+                               tb.scale, tb.d_thr.get(), bank ? bank->image() : nullptr, bank ? bank->tiles() : nullptr, bank ? bank->n_tiles : 0);
         });
         if (st != BN_OK) return st;
     }
     return BN_OK;
+}
+
+// ---- template matching (include/birdnet_hip.h, "Template matching"; kernel in template.hip, arithmetic in template_plan.h) ----
+bn_status bn_templates_create(int32_t device, size_t n_templates, size_t n_rows, const uint32_t *n_frames, const uint8_t *codes, bn_templates **out) {
+    if (!out) return fail(BN_ERR_INVALID_ARG, "null argument");
+    *out = nullptr;
+    tmatch::Packed p;
+    if (bn_status st = tmatch::pack(n_templates, n_rows, n_frames, codes, &p); st != BN_OK) return st;
+    if (bn_status dst = require_any_device(); dst != BN_OK) return dst;
+    BN_HIP_TRY(bn::use_device(device));
+    std::unique_ptr<bn_templates> t(new bn_templates);
+    t->device = device;
+    const size_t meta_bytes = p.meta.size() * sizeof(tmatch::Meta);
+    BN_HIP_TRY(t->d.alloc(meta_bytes + p.image.size()));
+    BN_HIP_TRY(gated::Memcpy(t->d.get(), p.meta.data(), meta_bytes, hipMemcpyHostToDevice));
+    BN_HIP_TRY(gated::Memcpy(t->d.get() + meta_bytes, p.image.data(), p.image.size(), hipMemcpyHostToDevice));
+    t->set = TemplateSet{t->d.get() + meta_bytes, reinterpret_cast<const tmatch::Meta *>(t->d.get()), p.tiles, p.n_templates, p.n_rows, p.n_tiles, p.max_frames};
+    *out = t.release();
+    return BN_OK;
+}
+void bn_templates_free(bn_templates *t) { delete t; }
+size_t bn_templates_count(const bn_templates *t) { return t ? t->set.n_templates : 0; }
+size_t bn_templates_rows(const bn_templates *t) { return t ? t->set.n_rows : 0; }
+size_t bn_templates_max_frames(const bn_templates *t) { return t ? t->set.max_frames : 0; }
+
+bn_status bn_recording_template_match(const bn_recording *r, size_t first_sample, size_t n_offsets, const bn_spectrogram_spec *spec, size_t spec_size,
+                                      const bn_filterbank *bank, const bn_templates *tpl, float *out_scores, size_t out_floats) {
+    spectro::Plan plan;
+    if (bn_status st = spectrogram_plan(r, first_sample, spec, spec_size, bank, &plan); st != BN_OK) return st;
+    if (plan.format != BN_SPECTROGRAM_U8) return fail(BN_ERR_INVALID_ARG, "template matching reads BN_SPECTROGRAM_U8 codes: the spec's format must be U8");
+    if (!tpl) return fail(BN_ERR_INVALID_ARG, "null templates");
+    if (!out_scores) return fail(BN_ERR_INVALID_ARG, "null output buffer");
+    const TemplateSet &set = tpl->set;
+    if (tpl->device != r->device)
+        return fail(BN_ERR_INVALID_ARG, "the templates live on device " + std::to_string(tpl->device) + ", the recording on device " + std::to_string(r->device));
+    if (set.n_rows != plan.n_rows)
+        return fail(BN_ERR_INVALID_ARG, "the templates have " + std::to_string(set.n_rows) + " rows, the image " + std::to_string(plan.n_rows) + " rows");
+    size_t need = 0, frames = 0;
+    if (!tmatch::out_floats(set.n_templates, n_offsets, &need) || !tmatch::image_frames(n_offsets, set.max_frames, &frames))
+        return fail(BN_ERR_INVALID_ARG, "n_templates * n_offsets floats do not fit a size_t");
+    if (out_floats < need) return fail(BN_ERR_INVALID_ARG, "out_floats " + std::to_string(out_floats) + " is below the " + std::to_string(need) + " scores of the match");
+    if (n_offsets == 0) return BN_OK;
+    uint64_t last = 0;
+    if (spectro::last_sample_read(r->n_samples, first_sample, frames, plan.N, plan.hop, &last) && !recording_wait_samples(r, (size_t)last))
+        return fail(BN_ERR_BACKEND, "recording upload failed");
+    SpectrogramTables tb;
+    if (bn_status st = tb.prepare(r, plan); st != BN_OK) return st;
+    if (tmatch::lds_bytes(set.max_frames, set.n_rows, set.n_tiles) > 64 * 1024) BN_HIP_TRY(template_match_prepare(r->device));
+    // Pieces of whole 64-offset tiles.  Stage 1 writes a piece's image, its offsets and the Wmax - 1 frames behind them, to the device
+    // (consecutive pieces re-make the frames they share); stage 2 reads it there; the scores come back template by template
+    const size_t piece = tmatch::piece_offsets(set.n_rows, set.max_frames, set.n_templates), first_n = std::min(piece, n_offsets);
+    DeviceBuf<uint8_t> d_img;
+    DeviceBuf<float> d_sc;
+    BN_HIP_TRY(d_img.alloc(std::max<size_t>((first_n + tmatch::piece_overlap(set.max_frames)) * set.n_rows, 16)));
+    BN_HIP_TRY(d_sc.alloc(first_n * set.n_templates * sizeof(float)));
+    for (size_t done = 0; done < n_offsets; done += piece) {
+        const size_t n = std::min(piece, n_offsets - done), nf = n + tmatch::piece_overlap(set.max_frames);
+        bn::clear_launch_state();
+        launch_spectrogram(nullptr, d_img.get(), r->src(), r->n_samples, spectro::frame_start(r->n_samples, first_sample, done, plan.hop), (uint32_t)nf, plan, tb.tab,
+                           tb.scale, tb.d_thr.get(), bank ? bank->image() : nullptr, bank ? bank->tiles() : nullptr, bank ? bank->n_tiles : 0);
+        if (bn_status st = bn::check_launch("spectrogram"); st != BN_OK) return st;
+        bn::clear_launch_state();
+        launch_template_match(nullptr, d_sc.get(), d_img.get(), nf, n, set);
+        if (bn_status st = bn::check_launch("template match"); st != BN_OK) return st;
+        // a piece's scores are [template][n]: the caller's layout where the piece is the whole call, a run per template otherwise
+        const size_t runs = n == n_offsets ? 1 : set.n_templates, len = n == n_offsets ? need : n;
+        for (size_t q = 0; q < runs; q++) {
+            const hipError_t e = gated::Memcpy(out_scores + q * n_offsets + done, d_sc.get() + q * n, len * sizeof(float), hipMemcpyDeviceToHost);
+            if (e != hipSuccess) return fail(BN_ERR_BACKEND, std::string("template match kernel failed: ") + hipGetErrorString(e));
+        }
+    }
+    return BN_OK;
+}
+
+bn_status bn_template_peaks(const float *scores, size_t n_templates, size_t n_offsets, float min_score, size_t peak_radius, bn_template_hit *out, size_t cap,
+                            size_t struct_size, size_t *n_out) {
+    return tmatch::peaks(scores, n_templates, n_offsets, min_score, peak_radius, out, cap, struct_size, n_out);
 }
 
 bn_status bn_filterbank_create(int32_t device, uint32_t frame, size_t n_rows, const float *weights, bn_filterbank **out) {
