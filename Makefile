@@ -10,7 +10,7 @@ CXXFLAGS := -O3 -std=c++17 -fPIC -Wall -Wextra -Wno-unused-parameter -Iinclude
 # for the pairs with register moves (mbmap's depthwise phase: 120 v_pk_fma + 216 v_mov for 240 multiply-adds); on this part a packed
 # f32 instruction costs 1.56x a plain one (tools/mfma_valu_probe.cpp) and every vector instruction is paid out of the MFMA time
 HIPFLAGS := $(CXXFLAGS) --offload-arch=$(ARCH) -ffp-contract=off -fno-slp-vectorize
-OBJS := $(SRC)/onnx_proto.o $(SRC)/engine.o $(SRC)/onnx_rewrite.o $(SRC)/dft_bank.o $(SRC)/mbconv_fuse.o $(SRC)/plan_passes.o $(SRC)/detect.o $(SRC)/capi.o $(SRC)/recording.o $(SRC)/step_common.o $(SRC)/group.o $(SRC)/host_classifier.o $(SRC)/host_capi.o $(SRC)/host_rangefilter.o $(SRC)/kernels.o $(SRC)/topk.o $(SRC)/stft.o $(SRC)/mbrow.o $(SRC)/gemm_dma.o $(SRC)/gemm_dma3.o $(SRC)/gemm_b3.o $(SRC)/mbmap.o $(SRC)/mbmap_ws.o $(SRC)/index.o $(SRC)/head.o $(SRC)/rank.o $(SRC)/cluster.o $(SRC)/ivf.o $(SRC)/sq8.o $(SRC)/subset.o $(SRC)/index_copy.o $(SRC)/peaks.o $(SRC)/seq.o $(SRC)/above.o $(SRC)/group_above.o $(SRC)/match.o $(SRC)/index_io.o $(SRC)/index_file.o $(SRC)/prior.o $(SRC)/track.o $(SRC)/live.o $(SRC)/live_kernels.o $(SRC)/levels.o $(SRC)/band_levels.o $(SRC)/spectral_profile.o $(SRC)/fir.o $(SRC)/denoise.o $(SRC)/spectrogram.o $(SRC)/delay.o $(SRC)/template.o
+OBJS := $(SRC)/onnx_proto.o $(SRC)/engine.o $(SRC)/onnx_rewrite.o $(SRC)/dft_bank.o $(SRC)/mbconv_fuse.o $(SRC)/plan_passes.o $(SRC)/detect.o $(SRC)/capi.o $(SRC)/recording.o $(SRC)/step_common.o $(SRC)/group.o $(SRC)/host_classifier.o $(SRC)/host_capi.o $(SRC)/host_rangefilter.o $(SRC)/kernels.o $(SRC)/topk.o $(SRC)/stft.o $(SRC)/mbrow.o $(SRC)/gemm_dma.o $(SRC)/gemm_dma3.o $(SRC)/gemm_b3.o $(SRC)/mbmap.o $(SRC)/mbmap_ws.o $(SRC)/index.o $(SRC)/head.o $(SRC)/rank.o $(SRC)/cluster.o $(SRC)/ivf.o $(SRC)/sq8.o $(SRC)/subset.o $(SRC)/index_copy.o $(SRC)/peaks.o $(SRC)/seq.o $(SRC)/above.o $(SRC)/group_above.o $(SRC)/match.o $(SRC)/index_io.o $(SRC)/index_file.o $(SRC)/prior.o $(SRC)/track.o $(SRC)/live.o $(SRC)/live_kernels.o $(SRC)/levels.o $(SRC)/band_levels.o $(SRC)/spectral_profile.o $(SRC)/fir.o $(SRC)/denoise.o $(SRC)/spectrogram.o $(SRC)/delay.o $(SRC)/template.o $(SRC)/pcen.o
 
 all: $(OUT) oracle
 
@@ -101,6 +101,10 @@ tools/asan_fir_plan: tools/asan_fir_plan.cpp $(SRC)/fir_plan.h $(SRC)/plan_rules
 # ... of the spectrogram's arithmetic: spec, bank and designer refusals, sizes and starts at extreme n_frames and hop, the LDS strides,
 # the packed bank re-summed to its weights with each tile's step range, the threshold table
 tools/asan_spectrogram_plan: tools/asan_spectrogram_plan.cpp $(SRC)/spectrogram_plan.h $(SRC)/band_plan.h $(SRC)/plan_rules.h $(SRC)/last_error.h include/birdnet_hip.h
+	$(CXX) $(ASAN_FLAGS) -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include $< -o $@
+# ... of PCEN's arithmetic: the spec's refusals field by field, bytes formed without wrapping, the launch pieces at a small piece length with
+# every chunk's start and the last partial chunk, apow against a running product, the threshold table
+tools/asan_pcen_plan: tools/asan_pcen_plan.cpp $(SRC)/pcen_plan.h $(SRC)/spectrogram_plan.h $(SRC)/band_plan.h $(SRC)/plan_rules.h $(SRC)/last_error.h include/birdnet_hip.h
 	$(CXX) $(ASAN_FLAGS) -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include $< -o $@
 # ... and of the operands of finished plans: the planner's own files, as tools/asan_plan.cpp links them
 PLANNER_SRC := $(SRC)/onnx_proto.cpp $(SRC)/engine.cpp $(SRC)/onnx_rewrite.cpp $(SRC)/dft_bank.cpp $(SRC)/mbconv_fuse.cpp $(SRC)/plan_passes.cpp $(SRC)/detect.cpp

@@ -919,6 +919,66 @@ bn_status bn_template_peaks(const float *scores, size_t n_templates, size_t n_of
                             bn_template_hit *out, size_t cap, size_t struct_size, size_t *n_out);
 
 /*
+ * PCEN: per-channel energy normalisation of a spectrogram (Wang et al. 2017; Lostanlen et al. 2019).  Each row is divided by a
+ * slowly smoothed copy of itself and compressed, so a call reads the same against a loud and a quiet background, where one
+ * ref_power of the decibel codes cannot follow.  bn_recording_pcen writes n_frames * n_rows elements to `out`, dense and
+ * time-major like bn_recording_spectrogram: a float (BN_PCEN_F32) or a byte (BN_PCEN_U8).
+ *
+ * Input.  E[t,j] is the f32 that bn_recording_spectrogram(..., BN_SPECTROGRAM_F32) stores for frame t, row j of the same range,
+ * spec and bank, bit for bit; spec->format must be BN_SPECTROGRAM_F32.  The float image never leaves the device.
+ * Rule.  With x = gain * E, s = smooth, a = 1 - s, per row j:
+ *   M[-1,j] = state_in[j]                      if state_in != NULL
+ *           = x[0,j] if finite, else 0         otherwise            (so M[0] = x[0]: no ramp-up)
+ *   M[t,j]  = a * M[t-1,j] + s * x[t,j]        where x[t,j] is finite; M[t,j] = M[t-1,j] otherwise
+ *   V[t,j]  = (x[t,j] / (eps + M[t,j])^alpha + delta)^r - delta^r
+ * Non-finite.  An element whose x is not finite -- the spectrogram's +Inf frames, an overflowing gain * E -- stores +Inf (code
+ * 255) and leaves M untouched.
+ * State.  state_out, if not NULL, receives M[n_frames - 1, j], n_rows floats; with n_frames == 0 it receives state_in, or nothing
+ * when state_in is NULL.  Feeding it to the next call as state_in continues the range within the bounds below, NOT bit for bit:
+ * the smoother is evaluated over chunks of 128 frames counted from frame 0 of the call, and a later call's chunks start elsewhere.
+ * U8 codes.  bn_pcen_thresholds (host only) computes thr[j - 1] = (j - 0.5) * max_value / 255, j = 1 .. 255, in double, rounds
+ * each to f32 once and forces the table non-decreasing.  The code of an element is the number of thresholds that are <= the f32
+ * BN_PCEN_F32 stores for it: the U8 image is, bit for bit, the table applied to the F32 image (a NaN counts as above every
+ * threshold).
+ * Invariance.  The bits of element (t, j) depend on E[0 .. t, j], the pcen spec, state_in and t: not on n_frames, the recording's
+ * layout, how the call is cut into launches, nor on the other rows.
+ *
+ * Arithmetic (csrc/pcen.hip).  Over a chunk, M_end = fma(apow[n], M_start, S): S is the recurrence run from 0 in f32 fmas, n the
+ * chunk's finite frames, apow[n] = a^n in double rounded once.  Powers are x^p = exp2(p * log2 x) on the hardware's exp2 and log2,
+ * one rule for every alpha and r; where x is 0, V is exactly 0.  Against float64 on the f32 image and the f32 parameters,
+ * u = 2^-24, barring underflow and overflow:
+ *   smoother   |M_got - M| <= B[t],   B[t] = a * B[t-1] + BN_PCEN_SMOOTH_DEPTH * u * M[t],   B[-1] = 0
+ *   value      |got - V| <= (alpha * r * B[t] / (eps + M[t]) + BN_PCEN_VALUE_DEPTH * u) * (V + delta^r)
+ * (derivation and measurement in DESIGN.md 7c, "PCEN").  At smooth == 1, M equals x exactly.  U8 has no bound of its own.
+ *
+ * The call blocks on an asynchronous upload until the last sample it reads has arrived, and returns when `out` and state_out are
+ * written.  BN_ERR_INVALID_ARG, with a message, nothing enqueued and nothing written: whatever bn_recording_spectrogram refuses
+ * about r, spec, spec_size, bank and first_sample; a spec->format other than BN_SPECTROGRAM_F32; a NULL pcen; a pcen_size below
+ * the struct's; an unknown pcen->format, smooth outside (0, 1], gain or eps not positive and finite, alpha outside [0, 1], delta
+ * negative or not finite, r outside (0, 1], for U8 a max_value not positive and finite (a NaN is outside every range); n_frames *
+ * n_rows * element size that does not fit a size_t; a NULL out; out_bytes below that product.  n_frames == 0 is BN_OK.
+ * bn_pcen_thresholds refuses a max_value that is not positive and finite, and a NULL output.
+ */
+#define BN_PCEN_F32 0 /* V, float */
+#define BN_PCEN_U8 1  /* codes 0..255 of V over [0, max_value], one byte */
+#define BN_PCEN_SMOOTH_DEPTH 6  /* 2 (gain * E and s * x, or a's rounding) + 1 (the fma) + 2 (apow[n] and the carry's fma, per chunk) + 1 spare */
+#define BN_PCEN_VALUE_DEPTH 90  /* 4 x 22.4, the worst ratio measured on an MI355X: two powers through exp2 / log2, a quotient, two sums */
+typedef struct bn_pcen_spec {
+    uint32_t format; /* BN_PCEN_F32 or BN_PCEN_U8 */
+    float smooth;    /* s, in (0, 1] */
+    float gain;      /* > 0, finite: the spectrogram's powers are normalised and small */
+    float alpha;     /* in [0, 1] */
+    float delta;     /* >= 0, finite */
+    float r;         /* in (0, 1] */
+    float eps;       /* > 0, finite */
+    float max_value; /* U8: the value that reaches code 255; > 0, finite */
+} bn_pcen_spec;
+bn_status bn_recording_pcen(const bn_recording *r, size_t first_sample, size_t n_frames, const bn_spectrogram_spec *spec, size_t spec_size,
+                            const bn_filterbank *bank, const bn_pcen_spec *pcen, size_t pcen_size, const float *state_in /* n_rows, or NULL */,
+                            float *state_out /* n_rows, or NULL */, void *out, size_t out_bytes);
+bn_status bn_pcen_thresholds(float max_value, float *thr_out /* 255 */);
+
+/*
  * bn_step_window_list: bn_step_windows over an explicit list.  Row i of the batch is the S = sample_count frames of
  * refs[i].recording from frame refs[i].start on, zeros past the end; start is any frame of the recording, no multiple of any step
  * (a window centred on a peak is fine).  The rows are gathered on the device straight into the context's input buffer -- the

@@ -274,6 +274,10 @@ class Recording {
      * U8 image of `spec` and `bank` (birdnet_hip.h, "Template matching"); bn_template_peaks picks the hits.  Throws Error::Inference
      * with the library's message on a refusal. */
     std::vector<float> template_match(size_t first_sample, size_t n_offsets, const bn_spectrogram_spec &spec, const Filterbank *bank, const Templates &tpl) const;
+    /* bn_recording_pcen: the PCEN image of the same frames and rows, floats or codes as pcen.format says; state_in / state_out are
+     * n_rows floats or NULL (birdnet_hip.h, "PCEN").  Throws Error::Inference with the library's message on a refusal. */
+    void pcen(size_t first_sample, size_t n_frames, const bn_spectrogram_spec &spec, const Filterbank *bank, const bn_pcen_spec &pcen, const float *state_in,
+              float *state_out, void *out, size_t out_bytes) const;
     size_t n_samples() const { return n_samples_; }
     const bn_recording *raw() const { return rec_.get(); }
 
@@ -605,6 +609,10 @@ void bnh_filterbank_free(bnh_filterbank *b);
 size_t bnh_filterbank_rows(const bnh_filterbank *b);
 int32_t bnh_recording_spectrogram(const bnh_recording *r, size_t first_sample, size_t n_frames, const bn_spectrogram_spec *spec,
                                   const bnh_filterbank *bank, void *out, size_t out_bytes, bnh_error *err);
+/* Recording::pcen and bn_pcen_thresholds (255 floats); bank, state_in and state_out may be NULL */
+int32_t bnh_recording_pcen(const bnh_recording *r, size_t first_sample, size_t n_frames, const bn_spectrogram_spec *spec, const bnh_filterbank *bank,
+                           const bn_pcen_spec *pcen, const float *state_in, float *state_out, void *out, size_t out_bytes, bnh_error *err);
+int32_t bnh_pcen_thresholds(float max_value, float *thr_out, bnh_error *err);
 /* class Templates and Recording::template_match; bank may be NULL (bin rows); out takes n_templates * n_offsets floats (out_floats of room) */
 typedef struct bnh_templates bnh_templates;
 int32_t bnh_templates_create(size_t n_templates, size_t n_rows, const uint32_t *n_frames, const uint8_t *codes, int32_t device, bnh_templates **out,

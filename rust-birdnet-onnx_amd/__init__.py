@@ -61,7 +61,7 @@ ENGINE_SYMBOLS = [
     "bn_recording_spectrogram", "bn_filterbank_create", "bn_filterbank_free", "bn_filterbank_rows", "bn_filterbank_frame", "bn_mel_filterbank",
     "bn_spectrogram_thresholds", "bn_recording_delay", "bn_delay_refine",
     "bn_templates_create", "bn_templates_free", "bn_templates_count", "bn_templates_rows", "bn_templates_max_frames", "bn_recording_template_match",
-    "bn_template_peaks",
+    "bn_template_peaks", "bn_recording_pcen", "bn_pcen_thresholds",
     "bn_index_create", "bn_index_free", "bn_index_size", "bn_index_dim", "bn_index_add_host", "bn_index_add_ctx", "bn_index_read",
     "bn_index_search", "bn_index_search_ids", "bn_index_assign", "bn_index_cluster",
     "bn_index_save", "bn_index_load", "bn_index_file_info", "bn_index_file_verify",
@@ -104,6 +104,7 @@ HOST_SYMBOLS = [
     "bnh_recording_spectrogram", "bnh_filterbank_create", "bnh_filterbank_free", "bnh_filterbank_rows",
     "bnh_recording_delay",
     "bnh_templates_create", "bnh_templates_free", "bnh_templates_count", "bnh_templates_max_frames", "bnh_recording_template_match",
+    "bnh_recording_pcen", "bnh_pcen_thresholds",
 ]
 
 
@@ -340,6 +341,36 @@ def spectrogram_thresholds(ref_power: float, range_db: float) -> np.ndarray:
     return thr
 
 
+BN_PCEN_F32, BN_PCEN_U8 = 0, 1  # include/birdnet_hip.h: bn_pcen_spec.format
+BN_PCEN_SMOOTH_DEPTH, BN_PCEN_VALUE_DEPTH = 6, 90  # the constants of the header's bounds on a PCEN image
+BN_PCEN_CHUNK = 128  # csrc/pcen_plan.h: the frames of one chunk of the scan
+
+
+class BnPcenSpec(C.Structure):
+    _fields_ = [("format", C.c_uint32), ("smooth", C.c_float), ("gain", C.c_float), ("alpha", C.c_float), ("delta", C.c_float), ("r", C.c_float),
+                ("eps", C.c_float), ("max_value", C.c_float)]
+
+
+def _pcen_call(n_frames: int, n_rows: int, smooth, gain, alpha, delta, r, eps, u8, state):
+    """(pcen spec, out, state_in or None, state_out) of a PCEN call: u8 is max_value or None for floats; `out` has a spare element,
+    for a call the library refuses"""
+    ps = BnPcenSpec(BN_PCEN_F32 if u8 is None else BN_PCEN_U8, smooth, gain, alpha, delta, r, eps, 0.0 if u8 is None else u8)
+    st_in = None if state is None else np.ascontiguousarray(state, dtype=np.float32)
+    if st_in is not None and st_in.shape != (n_rows,):
+        raise ValueError("state must hold n_rows floats")
+    return ps, np.zeros(max(n_frames, 0) * n_rows + 1, dtype=np.float32 if u8 is None else np.uint8), st_in, np.zeros(max(n_rows, 1), dtype=np.float32)
+
+
+def pcen_thresholds(max_value: float) -> np.ndarray:
+    """bn_pcen_thresholds: the 255 float32 thresholds of the U8 PCEN codes, (j - 0.5) * max_value / 255; an element's code is the
+    number of them that are <= its value, i.e. numpy.searchsorted(thr, image, side="right").  Host only."""
+    thr = np.zeros(255, dtype=np.float32)
+    st = lib.bn_pcen_thresholds(max_value, thr.ctypes.data_as(C.POINTER(C.c_float)))
+    if st:
+        raise EngineError(st)
+    return thr
+
+
 class Filterbank:
     """bn_filterbank: a non-negative [n_rows, frame / 2 + 1] matrix applied to the power spectrum of every frame of
     Recording.spectrogram, packed and uploaded once (mel_filterbank() designs mel triangles)."""
@@ -563,6 +594,8 @@ def _load() -> C.CDLL:
         "bn_recording_template_match": (i32, [vp, sz, sz, C.POINTER(BnSpectrogramSpec), sz, vp, vp, C.POINTER(C.c_float), sz]),
         "bn_template_peaks": (i32, [C.POINTER(C.c_float), sz, sz, C.c_float, sz, C.POINTER(BnTemplateHit), sz, sz, C.POINTER(sz)]),
         "bn_recording_spectrogram": (i32, [vp, sz, sz, C.POINTER(BnSpectrogramSpec), sz, vp, vp, sz]),
+        "bn_recording_pcen": (i32, [vp, sz, sz, C.POINTER(BnSpectrogramSpec), sz, vp, C.POINTER(BnPcenSpec), sz, C.POINTER(C.c_float), C.POINTER(C.c_float), vp, sz]),
+        "bn_pcen_thresholds": (i32, [C.c_float, C.POINTER(C.c_float)]),
         "bn_filterbank_create": (i32, [i32, C.c_uint32, sz, C.POINTER(C.c_float), C.POINTER(vp)]),
         "bn_filterbank_free": (None, [vp]),
         "bn_filterbank_rows": (sz, [vp]),
@@ -756,6 +789,9 @@ def _load() -> C.CDLL:
         "bnh_templates_max_frames": (sz, [vp]),
         "bnh_recording_template_match": (i32, [vp, sz, sz, C.POINTER(BnSpectrogramSpec), vp, vp, C.POINTER(C.c_float), sz, C.POINTER(BnhError)]),
         "bnh_recording_spectrogram": (i32, [vp, sz, sz, C.POINTER(BnSpectrogramSpec), vp, vp, sz, C.POINTER(BnhError)]),
+        "bnh_recording_pcen": (i32, [vp, sz, sz, C.POINTER(BnSpectrogramSpec), vp, C.POINTER(BnPcenSpec), C.POINTER(C.c_float), C.POINTER(C.c_float), vp, sz,
+                                     C.POINTER(BnhError)]),
+        "bnh_pcen_thresholds": (i32, [C.c_float, C.POINTER(C.c_float), C.POINTER(BnhError)]),
         "bnh_filterbank_create": (i32, [C.c_uint32, sz, C.POINTER(C.c_float), i32, C.POINTER(vp), C.POINTER(BnhError)]),
         "bnh_filterbank_free": (None, [vp]),
         "bnh_filterbank_rows": (sz, [vp]),
@@ -1222,6 +1258,18 @@ class HostRecording:
                                          out.nbytes - out.itemsize, C.byref(err)):
             raise Error(err)
         return out[:-1].reshape(n_frames, n_rows)
+
+    def pcen(self, first: int, n_frames: int, frame: int, hop: int, bins=None, bank=None, smooth=0.025, gain=2.0 ** 31, alpha=0.98, delta=2.0, r=0.5, eps=1e-6,
+             u8=None, state=None):
+        """Recording::pcen: (image, state) of Recording.pcen through the host mirror; bank is a HostFilterbank."""
+        sp, _, n_rows = _spectrogram_call(0, frame, hop, bins, bank, None)
+        ps, out, st_in, st_out = _pcen_call(n_frames, n_rows, smooth, gain, alpha, delta, r, eps, u8, state)
+        err = BnhError()
+        if lib.bnh_recording_pcen(self._h, first, n_frames, C.byref(sp), bank._h if bank is not None else None, C.byref(ps),
+                                  st_in.ctypes.data_as(C.POINTER(C.c_float)) if st_in is not None else None, st_out.ctypes.data_as(C.POINTER(C.c_float)),
+                                  out.ctypes.data_as(C.c_void_p), out.nbytes - out.itemsize, C.byref(err)):
+            raise Error(err)
+        return out[:-1].reshape(n_frames, n_rows), st_out[:n_rows]
 
     def template_match(self, first: int, n_offsets: int, frame: int, hop: int, templates: "HostTemplates", bins=None, bank=None, u8=(1.0, 80.0)) -> np.ndarray:
         """Recording::template_match: the [n_templates, n_offsets] scores of Recording.template_match; templates is a HostTemplates,
@@ -1915,6 +1963,24 @@ class Recording:
         if st:
             raise EngineError(st)
         return out[:-1].reshape(n_frames, n_rows)
+
+    def pcen(self, first: int, n_frames: int, frame: int, hop: int, bins=None, bank=None, smooth=0.025, gain=2.0 ** 31, alpha=0.98, delta=2.0, r=0.5, eps=1e-6,
+             u8=None, state=None):
+        """bn_recording_pcen: per-channel energy normalisation of the float image spectrogram(first, n_frames, frame, hop, bins, bank),
+        computed on the device without reading that image back.  Per row, x = gain * E, M[t] = (1 - smooth) M[t-1] + smooth x[t] and
+        V = (x / (eps + M)^alpha + delta)^r - delta^r.  Returns (image, state): image is [n_frames, n_rows], float32, or with
+        u8 = max_value uint8 codes -- pcen_thresholds(max_value) applied to the float image, bit for bit; state is M behind the last
+        frame, n_rows floats.  `state`, if given, is M in front of the first frame (a previous call's state continues its range,
+        within the header's bounds, not bit for bit); without one M starts at x[0].  An element that is not finite is +Inf (255) and
+        leaves M alone."""
+        sp, _, n_rows = _spectrogram_call(0, frame, hop, bins, bank, None)
+        ps, out, st_in, st_out = _pcen_call(n_frames, n_rows, smooth, gain, alpha, delta, r, eps, u8, state)
+        st = lib.bn_recording_pcen(self._h, first, n_frames, C.byref(sp), C.sizeof(BnSpectrogramSpec), bank._h if bank is not None else None, C.byref(ps),
+                                   C.sizeof(BnPcenSpec), st_in.ctypes.data_as(C.POINTER(C.c_float)) if st_in is not None else None,
+                                   st_out.ctypes.data_as(C.POINTER(C.c_float)), out.ctypes.data_as(C.c_void_p), out.nbytes - out.itemsize)
+        if st:
+            raise EngineError(st)
+        return out[:-1].reshape(n_frames, n_rows), st_out[:n_rows]
 
     def template_match(self, first: int, n_offsets: int, frame: int, hop: int, templates: "Templates", bins=None, bank=None, u8=(1.0, 80.0),
                        out: Optional[np.ndarray] = None) -> np.ndarray:

@@ -380,6 +380,21 @@ int32_t bnh_recording_spectrogram(const bnh_recording *r, size_t first_sample, s
     return guarded(err, [&] { r->rec.spectrogram(first_sample, n_frames, *spec, bank ? &bank->bank : nullptr, out, out_bytes); });
 }
 
+int32_t bnh_recording_pcen(const bnh_recording *r, size_t first_sample, size_t n_frames, const bn_spectrogram_spec *spec, const bnh_filterbank *bank,
+                           const bn_pcen_spec *pcen, const float *state_in, float *state_out, void *out, size_t out_bytes, bnh_error *err) {
+    if (!r) return set_other(err, "null recording");
+    if (!spec) return set_other(err, "null spectrogram spec");
+    if (!pcen) return set_other(err, "null PCEN spec");
+    return guarded(err, [&] { r->rec.pcen(first_sample, n_frames, *spec, bank ? &bank->bank : nullptr, *pcen, state_in, state_out, out, out_bytes); });
+}
+
+int32_t bnh_pcen_thresholds(float max_value, float *thr_out, bnh_error *err) {
+    if (bn_pcen_thresholds(max_value, thr_out) == BN_OK) return guarded(err, [] {});
+    char msg[256];
+    bn_last_error(msg, sizeof(msg));
+    return set_other(err, msg);
+}
+
 struct bnh_templates {
     Templates tpl;
 };

@@ -436,6 +436,13 @@ void Recording::spectrogram(size_t first_sample, size_t n_frames, const bn_spect
         throw inference(last_backend_error());
 }
 
+void Recording::pcen(size_t first_sample, size_t n_frames, const bn_spectrogram_spec &spec, const Filterbank *bank, const bn_pcen_spec &pcen, const float *state_in,
+                     float *state_out, void *out, size_t out_bytes) const {
+    if (bn_recording_pcen(rec_.get(), first_sample, n_frames, &spec, sizeof(bn_spectrogram_spec), bank ? bank->raw() : nullptr, &pcen, sizeof(bn_pcen_spec), state_in,
+                          state_out, out, out_bytes) != BN_OK)
+        throw inference(last_backend_error());
+}
+
 Templates::Templates(size_t n_templates, size_t n_rows, const uint32_t *n_frames, const uint8_t *codes, int device) {
     bn_templates *t = nullptr;
     if (bn_templates_create(device, n_templates, n_rows, n_frames, codes, &t) != BN_OK) throw inference("failed to create the templates: " + last_backend_error());

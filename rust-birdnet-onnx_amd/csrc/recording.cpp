@@ -1,5 +1,5 @@
 // Recordings of the C ABI (include/birdnet_hip.h): bn_recording_*, the resampler's table, FIR filtering, noise reduction, spectrograms and their
-// filter banks, template matching, and the explicit window lists
+// filter banks, template matching, PCEN, and the explicit window lists
 // (bn_recording_window_list, bn_step_window_list: of a context they need what bn_step_live does).  bn_recording is private to this
 // file; capi.cpp's bn_infer_windows and bn_step_windows reach a recording through check_windows and enqueue_windows (capi_internal.h).
 // Every launch is clear_launch_state, the launcher, check_launch; results reach the host through launch_and_read or rows_in_pieces.
@@ -24,6 +24,7 @@
 #include "fir.h"
 #include "kernels.h"
 #include "levels.h"
+#include "pcen.h"
 #include "spectral_profile.h"
 #include "spectrogram.h"
 #include "template.h"
@@ -698,7 +699,7 @@ bn_status bn_noise_floor(const float *profile_bins, size_t count, size_t n_bins,
 
 // ---- spectrograms (include/birdnet_hip.h, "Spectrograms"; kernels in spectrogram.hip, arithmetic in spectrogram_plan.h) ----
 namespace {
-// what bn_recording_spectrogram and bn_recording_template_match refuse about r, spec, spec_size, bank and first_sample; else the plan
+// what bn_recording_spectrogram, bn_recording_template_match and bn_recording_pcen refuse about r, spec, spec_size, bank and first_sample; else the plan
 bn_status spectrogram_plan(const bn_recording *r, size_t first_sample, const bn_spectrogram_spec *spec, size_t spec_size, const bn_filterbank *bank,
                            spectro::Plan *plan) {
     if (!r) return fail(BN_ERR_INVALID_ARG, "null recording");
@@ -837,6 +838,70 @@ bn_status bn_template_peaks(const float *scores, size_t n_templates, size_t n_of
                             size_t struct_size, size_t *n_out) {
     return tmatch::peaks(scores, n_templates, n_offsets, min_score, peak_radius, out, cap, struct_size, n_out);
 }
+
+// ---- PCEN (include/birdnet_hip.h, "PCEN"; kernels in pcen.hip, arithmetic in pcen_plan.h) ----
+bn_status bn_recording_pcen(const bn_recording *r, size_t first_sample, size_t n_frames, const bn_spectrogram_spec *spec, size_t spec_size,
+                            const bn_filterbank *bank, const bn_pcen_spec *pcen, size_t pcen_size, const float *state_in, float *state_out, void *out,
+                            size_t out_bytes) {
+    spectro::Plan plan;
+    if (bn_status st = spectrogram_plan(r, first_sample, spec, spec_size, bank, &plan); st != BN_OK) return st;
+    if (plan.format != BN_SPECTROGRAM_F32) return fail(BN_ERR_INVALID_ARG, "PCEN reads BN_SPECTROGRAM_F32 powers: the spec's format must be F32");
+    pcen::Plan pp;
+    if (bn_status st = pcen::check_spec(pcen, pcen_size, &pp); st != BN_OK) return st;
+    size_t need = 0;
+    if (!pcen::out_bytes(n_frames, plan.n_rows, pp.elem, &need)) return fail(BN_ERR_INVALID_ARG, "n_frames * n_rows elements do not fit a size_t");
+    const size_t R = plan.n_rows;
+    if (n_frames == 0) {
+        if (state_in && state_out) memcpy(state_out, state_in, R * sizeof(float));
+        return BN_OK;
+    }
+    if (!out) return fail(BN_ERR_INVALID_ARG, "null output buffer");
+    if (out_bytes < need) return fail(BN_ERR_INVALID_ARG, "out_bytes " + std::to_string(out_bytes) + " is below the " + std::to_string(need) + " bytes of the PCEN image");
+    // an asynchronously uploaded recording: the last sample any of these frames reads must have arrived
+    uint64_t last = 0;
+    if (spectro::last_sample_read(r->n_samples, first_sample, n_frames, plan.N, plan.hop, &last) && !recording_wait_samples(r, (size_t)last))
+        return fail(BN_ERR_BACKEND, "recording upload failed");
+    SpectrogramTables tb;
+    if (bn_status st = tb.prepare(r, plan); st != BN_OK) return st;
+    // Pieces of whole chunks.  Stage 1 writes a piece's f32 image to the device, stage 2 reads it there; the device state carries M
+    // from piece to piece, and a chunk's carry is formed the same way wherever the pieces are cut
+    const size_t piece = pcen::piece_frames(spectro::piece_frames(plan.n_rows)), first_n = std::min(piece, n_frames), per = R * pp.elem;
+    float tables[pcen::CHUNK + 1 + pcen::N_THR] = {};
+    pcen::apow(pp.s, tables);
+    if (pp.format == BN_PCEN_U8)
+        if (bn_status st = pcen::thresholds(pp.max_value, tables + pcen::CHUNK + 1); st != BN_OK) return st;
+    DeviceBuf<float> d_img, d_sums, d_carry, d_state, d_tables;
+    DeviceBuf<uint32_t> d_counts;
+    DeviceBuf<uint8_t> d_out;
+    const size_t chunk_floats = pcen::chunks(first_n) * R * sizeof(float);
+    BN_HIP_TRY(d_img.alloc(std::max<size_t>(first_n * R * sizeof(float), 16)));
+    BN_HIP_TRY(d_out.alloc(std::max<size_t>(first_n * per, 16)));
+    BN_HIP_TRY(d_sums.alloc(chunk_floats));
+    BN_HIP_TRY(d_counts.alloc(chunk_floats));
+    BN_HIP_TRY(d_carry.alloc(chunk_floats));
+    BN_HIP_TRY(d_state.alloc(R * sizeof(float)));
+    BN_HIP_TRY(d_tables.alloc(sizeof(tables)));
+    BN_HIP_TRY(gated::Memcpy(d_tables, tables, sizeof(tables), hipMemcpyHostToDevice));
+    if (state_in) BN_HIP_TRY(gated::Memcpy(d_state, state_in, R * sizeof(float), hipMemcpyHostToDevice));
+    const PcenScratch sc{d_sums.get(), d_counts.get(), d_carry.get(), d_state.get(), d_tables.get(), d_tables.get() + pcen::CHUNK + 1};
+    for (size_t done = 0; done < n_frames; done += piece) {
+        const size_t n = std::min(piece, n_frames - done);
+        bn::clear_launch_state();
+        launch_spectrogram(nullptr, d_img.get(), r->src(), r->n_samples, spectro::frame_start(r->n_samples, first_sample, done, plan.hop), (uint32_t)n, plan, tb.tab,
+                           tb.scale, nullptr, bank ? bank->image() : nullptr, bank ? bank->tiles() : nullptr, bank ? bank->n_tiles : 0);
+        if (bn_status st = bn::check_launch("spectrogram"); st != BN_OK) return st;
+        bn_status st = launch_and_read("pcen", "pcen kernel failed: ", static_cast<char *>(out) + done * per, d_out, n * per,
+                                       [&] { launch_pcen(nullptr, d_out.get(), d_img.get(), n, plan.n_rows, pp, sc, done == 0 && !state_in); });
+        if (st != BN_OK) return st;
+    }
+    if (state_out) {
+        const hipError_t e = gated::Memcpy(state_out, d_state, R * sizeof(float), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return fail(BN_ERR_BACKEND, std::string("pcen kernel failed: ") + hipGetErrorString(e));
+    }
+    return BN_OK;
+}
+
+bn_status bn_pcen_thresholds(float max_value, float *thr_out) { return pcen::thresholds(max_value, thr_out); }
 
 bn_status bn_filterbank_create(int32_t device, uint32_t frame, size_t n_rows, const float *weights, bn_filterbank **out) {
     if (!out) return fail(BN_ERR_INVALID_ARG, "null argument");
